@@ -21,7 +21,12 @@ every rank holds the table and searches its own batches; value = all ranks'
 lookups / max-over-ranks time ("weak").  `--mode sharded` runs the hash-prefix
 sharded index of configs[3] instead (one exchange step per batch).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+A plain run sets up, warms up, times the steps and prints the result line.  `--full` adds what the headline does
+not need: the parity check of the last timed batch against the CPU oracle, the CPU baseline, the per-kernel times
+with one batch in flight and, at N > 1, the sharded leg.  `--dump-outputs DIR` writes the hit lists of the last
+timed batch as DIR/<name>.npy (see dump_outputs).
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -115,6 +120,45 @@ def cpu_baseline(oix, queries, seconds=12.0, threads=None, kind="protein"):
             "queries_per_s": nqd / dt}
 
 
+DUMP_MAX_RESULTS = 20000     # results (queries, or ORFs of reads) beyond this: a fixed seeded sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, n_results, seed):
+    """The hit lists of a device-resident result, as a caller of the timed path reads them, into out_dir/<name>.npy
+    (float64, exact for u32 ids and counts):
+      result_index  which results are written (all of them, or a seeded sample of DUMP_MAX_RESULTS in result order)
+      hit_count     hits of each of those results
+      hit_pid       protein ids, result after result; each list in protein-id order (the order inside a list is
+                    not part of the result: the reference hands over a map)
+      hit_kmatch    Kmatch of each hit of hit_pid
+    Results are dropped from the end of the sample until everything fits DUMP_MAX_BYTES."""
+    import numpy as np
+    import torch
+    from kaamer_amd.sharded import dev_tensor
+    torch.cuda.synchronize()
+    off = dev_tensor(res.d_hit_off, n_results, torch.int64).cpu().numpy()
+    cnt = dev_tensor(res.d_hit_cnt, n_results, torch.int32).cpu().numpy().astype(np.int64)
+    cap = int(res.hit_capacity)
+    assert n_results == 0 or (off.min() >= 0 and cnt.min() >= 0 and int((off + cnt).max()) <= cap), "hit lists out of range"
+    sel = np.arange(n_results)
+    if n_results > DUMP_MAX_RESULTS:
+        sel = np.sort(np.random.default_rng(seed).choice(n_results, DUMP_MAX_RESULTS, replace=False))
+    while len(sel) > 1 and 8 * len(sel) * 2 + 16 * int(cnt[sel].sum()) > DUMP_MAX_BYTES:
+        sel = sel[:len(sel) // 2]
+    c = cnt[sel]
+    starts = np.cumsum(c) - c
+    idx = np.repeat(off[sel] - starts, c) + np.arange(int(c.sum()))   # entry of every hit in the device arrays
+    d_idx = torch.from_numpy(idx).cuda()
+    pid = dev_tensor(res.d_hit_pid, cap, torch.int32)[d_idx].cpu().numpy().view(np.uint32)
+    km = dev_tensor(res.d_hit_kmatch, cap, torch.int32)[d_idx].cpu().numpy()
+    order = np.lexsort((pid, np.repeat(np.arange(len(sel)), c)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("result_index", sel), ("hit_count", c), ("hit_pid", pid[order]), ("hit_kmatch", km[order])):
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    log("outputs: %d of %d results, %d hits -> %s" % (len(sel), n_results, len(idx), out_dir))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: this process -- which has not imported torch nor touched the GPU --
     starts N fresh children, one rank per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run sets
@@ -172,9 +216,15 @@ def main():
                     help="workspace bound: slots of the HBM counting tables of queries that overflow their LDS table "
                          "(default: the library's 32 M; 1 G for --db zipf, where most queries overflow)")
     ap.add_argument("--max-hits", type=int, default=0, help="workspace bound: hit entries per batch (default: sized for the workload)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: --check 50 and the CPU baseline by default, the kernels "
+                         "alone on the device (roofline `alone_on_the_device`) and, at N > 1, --sharded-leg 1 by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit lists of the last timed batch as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--check", type=int, default=50, help="queries checked against the oracle after timing")
+    ap.add_argument("--check", type=int, default=None,
+                    help="queries checked against the oracle after timing (default: 50 with --full, else 0)")
     ap.add_argument("--mode", choices=["replicas", "sharded"], default="replicas",
                     help="N>1: replicas = every rank holds the table and its own batches (default; the DB fits one GPU); "
                          "sharded = the table is split by hash prefix, all ranks search one common batch, partial hit "
@@ -182,11 +232,11 @@ def main():
     ap.add_argument("--transport", choices=["rccl", "torch"], default="rccl",
                     help="sharded mode: rccl = kaamer_rccl_alltoall on an ncclComm_t made with ncclCommInitRank (what a Go host "
                          "calls); torch = torch.distributed.all_to_all_single (backend nccl = RCCL)")
-    ap.add_argument("--sharded-leg", type=int, default=1,
+    ap.add_argument("--sharded-leg", type=int, default=None,
                     help="replicas mode with N > 1: after the timed region also run a short pass of the hash-prefix sharded index "
                          "(configs[3]'s data path: search -> pack -> RCCL all-to-all -> merge -> top-N) on the same database and "
                          "report it under `sharded_leg` (per-phase ms, bytes exchanged, the rank count RCCL saw); 0 = skip; "
-                         "2 = run it at N = 1 too (rehearsal of the code path on one GPU)")
+                         "2 = run it at N = 1 too (rehearsal of the code path on one GPU).  Default: 1 with --full, else 0")
     ap.add_argument("--time-every", type=int, default=16,
                     help="bracket the kernels of every k-th timed launch with HIP events (roofline.achieved is their average)")
     ap.add_argument("--post", type=int, default=0,
@@ -208,6 +258,10 @@ def main():
                     help="1: finish every batch with the hit lists packed in query order (one more scan + copy pass); "
                          "0 (default): each query's list stays where the search kernel wrote it (offset + count per query)")
     args = ap.parse_args()
+    if args.check is None:
+        args.check = 50 if args.full else 0
+    if args.sharded_leg is None:
+        args.sharded_leg = 1 if args.full else 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -473,13 +527,17 @@ def main():
         elapsed, first_timed, last = timed_region()
         finish_all()
     last_batch = (n_launch - 1) % n_distinct
+    if args.dump_outputs and rank == 0:
+        stride = world if sharded_mode else 1   # sharded: result i of rank 0 is query i * world of the batch
+        n_res = (int(per_batch[last_batch]["n_queries"]) + stride - 1) // stride
+        dump_outputs(args.dump_outputs, last, n_res, workload.SEED)
     tm = wss[0].kernel_ms_sum()
     n_calls = max(tm["calls"], 1)
     # with several batches in flight the kernels of neighbouring batches share the device: their durations in the
     # timed region say how the overlap went, not what a kernel can do.  A short untimed pass with ONE batch in flight
     # gives every kernel alone on the device (reported next to the timed-region figures)
     tm_alone = None
-    if args.inflight > 1 and not sharded_mode:
+    if args.full and args.inflight > 1 and not sharded_mode:
         # (a workspace of its own: the timed region's workspaces were created for batches in flight next to each other --
         # concurrent_batches -- and launch the counting kernel accordingly)
         ws1 = api.Workspace(ix, max_bytes, args.queries, **dict(ws_kw, concurrent_batches=1))
@@ -637,7 +695,7 @@ def main():
                          **alone("probe_ms", probe_bytes))),
                kern(("count_async_kernel" if (os.environ.get("KAAMER_COUNT_ASYNC", "0") not in ("", "0") and not nucl) else
                      "count_pack_kernel" if nucl else "count_group_kernel") + " (+ G tier, finalize)" +
-                    ("; one workgroup per CU in the timed region, three in alone_on_the_device" if (args.inflight > 1 and not nucl and not sharded_mode) else ""),
+                    ("; one workgroup per CU in the timed region, three in alone_on_the_device" if (tm_alone and not nucl) else ""),
                     count_s, count_bytes, alone("count_ms", count_bytes))]
     kernels.sort(key=lambda k: -k["ms"])
     roofline = {
@@ -647,8 +705,8 @@ def main():
         "traffic": traffic,
         "scope": "whole batch (prep [+ translation] + probe + count + G tier), wall clock of the timed region; per-kernel "
                  "ms are HIP-event durations inside the timed region" + (" (%d batches in flight: kernels of neighbouring "
-                 "batches overlap, `alone_on_the_device` is the same kernel with one batch in flight)" % args.inflight
-                                                                        if args.inflight > 1 else ""),
+                 "batches overlap%s)" % (args.inflight, ", `alone_on_the_device` is the same kernel with one batch in flight"
+                                                        if tm_alone else "") if args.inflight > 1 else ""),
         "algorithmic_bytes_per_batch": whole_bytes,
         "bytes_per_lookup": whole_bytes / max(c["n_lookup"], 1),
         "dominant_kernel": kernels[0], "other_kernels": kernels[1:], "timed_launches": n_calls,
@@ -712,7 +770,7 @@ def main():
         out["sharded_leg"] = leg
 
     if rank == 0:
-        want_cpu = not args.no_cpu_baseline and world == 1 and not sharded_mode
+        want_cpu = args.full and not args.no_cpu_baseline and world == 1 and not sharded_mode
         if args.check or want_cpu or args.host_api:
             from oracle import oracle as O  # the checker / the reported CPU baseline, never the product
             t0 = time.time()

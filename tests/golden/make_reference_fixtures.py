@@ -1,9 +1,9 @@
 """Generates the fixtures that pin the oracle to the reference's own text.
 
-Run in the build container (needs /root/reference, read as TEXT only — the
-reference is Go and cannot be executed here):
+Run with a checkout of the reference, read as TEXT only (the reference is Go and
+is not executed):
 
-    python tests/golden/make_reference_fixtures.py
+    python tests/golden/make_reference_fixtures.py <reference checkout>
 
 Outputs (data only: inputs and expected outputs, no reference source text):
   gcode_bacteria.json  codon -> [AA, Start, Stop], parsed from the map literal
@@ -16,8 +16,9 @@ Outputs (data only: inputs and expected outputs, no reference source text):
 import json
 import os
 import re
+import sys
 
-REF = "/root/reference"
+REF = "reference"   # the reference checkout, named on the command line
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -64,6 +65,7 @@ def matrix_scores():
 
 
 if __name__ == "__main__":
+    REF = sys.argv[1]
     json.dump(matrix_scores(), open(os.path.join(HERE, "matrix_scores.json"), "w"), indent=0, sort_keys=True)
     json.dump(gcode(), open(os.path.join(HERE, "gcode_bacteria.json"), "w"), indent=0, sort_keys=True)
     json.dump(docs_example(), open(os.path.join(HERE, "docs_example.json"), "w"), indent=1, sort_keys=True)

@@ -14,25 +14,25 @@ PMC="--steps 1 --warmup 0 --no-cpu-baseline --check 0 --time-every 0"
 case $PART in
 protein)
   echo "== default bench (configs[1]), no profiler"
-  timeout -k 10 600 python3 bench.py > $O/bench_default_n1.json 2> $O/bench_default_n1.log || exit 1
+  timeout -k 10 600 python3 bench.py --full > $O/bench_default_n1.json 2> $O/bench_default_n1.log || exit 1
   echo "== the same command under rocprofv3 --kernel-trace --stats (three batches in flight: overlapped durations)"
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_protein -- python3 bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats_protein.log || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_protein -- python3 bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/stats_protein.log || exit 1
   echo "== one batch in flight: every kernel alone on the device"
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_protein_if1 -- python3 bench.py --no-cpu-baseline --inflight 1 > $O/bench_inflight1_under_rocprof.json 2> $O/stats_protein_if1.log || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_protein_if1 -- python3 bench.py --full --no-cpu-baseline --inflight 1 > $O/bench_inflight1_under_rocprof.json 2> $O/stats_protein_if1.log || exit 1
   echo "== PMC: HBM traffic of a protein batch (FETCH_SIZE / WRITE_SIZE in separate passes)"
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 bench.py $PMC --batches-per-step 16 > $O/pmc_fetch.json 2> $O/pmc_fetch.log || exit 1
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 bench.py $PMC --batches-per-step 16 > $O/pmc_write.json 2> $O/pmc_write.log || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 bench.py --full $PMC --batches-per-step 16 > $O/pmc_fetch.json 2> $O/pmc_fetch.log || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 bench.py --full $PMC --batches-per-step 16 > $O/pmc_write.json 2> $O/pmc_write.log || exit 1
   echo "== where the wave cycles go (SQ counters)"
   bash tools/pmc_sq.sh $R/sq_protein > $O/sq_protein.txt 2>&1 || exit 1
   ;;
 reads)
   echo "== reads (configs[2]) bench + kernel stats + PMC traffic"
-  timeout -k 10 600 python3 bench.py --workload reads > $O/bench_reads_n1.json 2> $O/bench_reads_n1.log || exit 1
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_reads -- python3 bench.py --workload reads --no-cpu-baseline > $O/bench_reads_under_rocprof.json 2> $O/stats_reads.log || exit 1
+  timeout -k 10 600 python3 bench.py --full --workload reads > $O/bench_reads_n1.json 2> $O/bench_reads_n1.log || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_reads -- python3 bench.py --full --workload reads --no-cpu-baseline > $O/bench_reads_under_rocprof.json 2> $O/stats_reads.log || exit 1
   echo "== one read batch in flight: every kernel alone on the device"
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_reads_if1 -- python3 bench.py --workload reads --no-cpu-baseline --inflight 1 > $O/bench_reads_inflight1_under_rocprof.json 2> $O/stats_reads_if1.log || exit 1
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_reads -- python3 bench.py --workload reads $PMC --batches-per-step 8 > $O/pmc_fetch_reads.json 2> $O/pmc_fetch_reads.log || exit 1
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_reads -- python3 bench.py --workload reads $PMC --batches-per-step 8 > $O/pmc_write_reads.json 2> $O/pmc_write_reads.log || exit 1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_reads_if1 -- python3 bench.py --full --workload reads --no-cpu-baseline --inflight 1 > $O/bench_reads_inflight1_under_rocprof.json 2> $O/stats_reads_if1.log || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_reads -- python3 bench.py --full --workload reads $PMC --batches-per-step 8 > $O/pmc_fetch_reads.json 2> $O/pmc_fetch_reads.log || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_reads -- python3 bench.py --full --workload reads $PMC --batches-per-step 8 > $O/pmc_write_reads.json 2> $O/pmc_write_reads.log || exit 1
   FILTER="translate_reads|probe_kernel|count_pack|topn" BPS=2 bash tools/pmc_sq.sh $R/sq_reads --workload reads > $O/sq_reads.txt 2>&1 || exit 1
   ;;
 secondary)
