@@ -507,7 +507,8 @@ typedef struct {
     uint32_t world, rank;
     uint32_t q_cap;        /* owned queries a block can describe                 */
     uint32_t arrays;       /* entry arrays in a block: 3 = id, Kmatch, first     */
-                           /* position; 2 = no first positions (0 reads as 3)    */
+                           /* position; 2 = no first positions (0 reads as 3);   */
+                           /* 4 = the three + PositionHits bitmaps (below)       */
     uint64_t e_cap;        /* partial (id, Kmatch, first position) entries/block */
     uint64_t block_words;  /* u32 words per block; send / receive buffers hold   */
                            /* world blocks                                       */
@@ -532,6 +533,27 @@ int kaamer_exchange_layout_fit(const kaamer_exchange_layout *capacity, uint32_t 
  * header scan only (an event), not for the stream. */
 int kaamer_exchange_stats(kaamer_workspace *merge_ws, uint32_t back, uint64_t out[4]);
 uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws);
+/* Blocks that carry PositionHits (search.go:442-452; -pos, cmd/kaamer/main.go:69) through the exchange: arrays = 4.
+ * The block is the arrays = 3 block with two more sections:
+ *     [8 + q_cap .. 8 + 2 q_cap)  per owned query: SizeInKmer (every shard translates alike: the W blocks must agree)
+ *     then pid, kmatch, first_pos [e_cap] each as before, then, from u32 word
+ *         bits_off = (8 + 2 q_cap + 3 e_cap) rounded up to an even word  (8-byte aligned),
+ *     p_cap = (block_words - bits_off) / 2 u64 words of bitmaps: entry j of owned query i has ceil(SizeInKmer_i / 64)
+ *     words at bits_off + 2 (bbase[i] + j words_i), bbase = exclusive scan of entries_i x words_i.
+ * Header word [6] = bitmap words this block needed, [7] = the largest [6] over the sender's W blocks, status bit 4 =
+ * bitmaps inside.  A bitmap section that does not fit sets the overflow bits as the entries do (KAAMER_E_CAPACITY on
+ * every rank).  Both workspaces need want_positions = 1 and first_pos = 1; the merge ORs each received bitmap into its
+ * merged hit's (the shards' bitmaps of one hit are disjoint: bit-identical to the unsharded search) and returns them in
+ * kaamer_device_result.d_pos_off / d_pos_bits / d_pos_base as a search does. */
+int kaamer_exchange_layout_init_positions(uint32_t world, uint32_t rank, uint32_t max_queries, uint64_t max_entries_per_peer,
+                                          uint64_t max_pos_words_per_peer, kaamer_exchange_layout *out);
+/* the payload-sized layout of one batch (kaamer_exchange_layout_fit) with room for pos_words_per_block bitmap words;
+ * `capacity` must be an arrays = 4 layout; never beyond it */
+int kaamer_exchange_layout_fit_positions(const kaamer_exchange_layout *capacity, uint32_t n_queries, uint64_t entries_per_block,
+                                         uint64_t pos_words_per_block, kaamer_exchange_layout *out);
+/* the bitmap half of kaamer_exchange_stats: out = { bitmap words the largest block between ANY pair of ranks needed,
+ * non-zero if a bitmap section overflowed } (zeros after a merge of blocks without bitmaps) */
+int kaamer_exchange_stats_positions(kaamer_workspace *merge_ws, uint32_t back, uint64_t out[2]);
 /* the last search of `search_ws` -> d_send[world * block_words] */
 int kaamer_exchange_pack(kaamer_workspace *search_ws, const kaamer_exchange_layout *layout,
                          uint32_t *d_send, void *stream);
@@ -585,6 +607,22 @@ int kaamer_sharded_search_batch_top_flat(kaamer_sharded_index *sx, const uint8_t
 int kaamer_sharded_submit_batch_top_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets,
                                          uint32_t n_seqs, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                                          uint32_t max_results, kaamer_sharded_ticket **ticket);
+/* The full hit lists of a batch on the sharded handle: what kaamer_search_batch returns on an unsharded index of the
+ * whole database (the worker pool of search_protein.go:58-118 / search_fastq.go:94-118 when -pos asks for
+ * PositionHits, search.go:416,442-452): the same queries in the same order, each with the same (id, Kmatch, first
+ * position) set (unordered within a query, as there), the same q / orf_aa / starts_alt and, with want_positions, the
+ * same bitmaps.  Every shard searches and packs, every owner merges, compacts and copies its queries back; the host
+ * interleaves them into batch order.  Free the result with kaamer_batch_free. */
+int kaamer_sharded_search_batch(kaamer_sharded_index *sx, const kaamer_batch_in *in, kaamer_batch_out **out);
+int kaamer_sharded_search_batch_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                     int32_t seq_type, int32_t want_positions, kaamer_batch_out **out);
+/* in two halves, as kaamer_submit_batch_flat / kaamer_wait_batch (wait repeats the batch from the staging copy with
+ * grown bounds when one was too small) */
+typedef struct kaamer_sharded_full_ticket kaamer_sharded_full_ticket;
+int kaamer_sharded_submit_batch_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                     int32_t seq_type, int32_t want_positions, kaamer_sharded_full_ticket **ticket);
+int kaamer_sharded_wait_batch(kaamer_sharded_full_ticket *ticket, kaamer_batch_out **out);
+void kaamer_sharded_full_ticket_discard(kaamer_sharded_full_ticket *ticket);
 /* The exchange of the last finished call on the handle's first set: out = { bytes of one (shard -> owner) block as it
  * travelled, entries the largest block needed, queries of the batch, 1 if the blocks were sized from the previous
  * call's need (payload) rather than the buffers' capacity }. */

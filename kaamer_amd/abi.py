@@ -211,6 +211,19 @@ SYMBOLS = {
     "kaamer_sharded_submit_batch_top_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
                                                        C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "kaamer_sharded_exchange_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    # full hit lists (PositionHits included) on the sharded handle, and the exchange blocks that carry bitmaps
+    "kaamer_sharded_search_batch": (C.c_int, [C.c_void_p, C.POINTER(BatchIn), C.POINTER(C.POINTER(BatchOut))]),
+    "kaamer_sharded_search_batch_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
+                                                   C.POINTER(C.POINTER(BatchOut))]),
+    "kaamer_sharded_submit_batch_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
+                                                   C.POINTER(C.c_void_p)]),
+    "kaamer_sharded_wait_batch": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(BatchOut))]),
+    "kaamer_sharded_full_ticket_discard": (None, [C.c_void_p]),
+    "kaamer_exchange_layout_init_positions": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                                        C.POINTER(ExchangeLayout)]),
+    "kaamer_exchange_layout_fit_positions": (C.c_int, [C.POINTER(ExchangeLayout), C.c_uint32, C.c_uint64, C.c_uint64,
+                                                       C.POINTER(ExchangeLayout)]),
+    "kaamer_exchange_stats_positions": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "kaamer_workspace_reset_timers": (None, [C.c_void_p]),
     "kaamer_workspace_set_timing": (None, [C.c_void_p, C.c_uint32]),
     "kaamer_filter_results": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int64, C.c_int64]),

@@ -499,6 +499,32 @@ class ShardedIndex:
                                                                  len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
         return TopTicket(t, sharded=True)
 
+    def search(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False, flat=True):
+        """The full hit lists (PositionHits bitmaps with want_positions): what Index.search returns on an unsharded index
+        of the whole database (kaamer_sharded_search_batch_flat; flat=False: the struct form)."""
+        buf, offs = packed if packed is not None else pack_sequences(seqs)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        out = C.POINTER(abi.BatchOut)()
+        if flat:
+            abi.check(abi.lib().kaamer_sharded_search_batch_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
+                                                                 len(offs) - 1, seq_type, int(want_positions), C.byref(out)))
+        else:
+            bi = abi.BatchIn(buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type,
+                             int(want_positions))
+            abi.check(abi.lib().kaamer_sharded_search_batch(self._h, C.byref(bi), C.byref(out)))
+        return BatchResult(out)
+
+    def submit(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False):
+        """kaamer_sharded_submit_batch_flat -> a ticket whose wait() returns the BatchResult (full hit lists)"""
+        buf, offs = packed if packed is not None else pack_sequences(seqs)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        t = C.c_void_p()
+        abi.check(abi.lib().kaamer_sharded_submit_batch_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
+                                                             len(offs) - 1, seq_type, int(want_positions), C.byref(t)))
+        return FullTicket(t, sharded=True)
+
     def exchange_info(self):
         """-> dict(block_bytes, need_entries, queries, adaptive) of the last finished call on the handle's first set"""
         out = (C.c_uint64 * 4)()
@@ -579,21 +605,24 @@ class Replicas:
 
 
 class FullTicket:
-    """one full-hit-list batch in flight (kaamer_full_ticket); wait() exactly once, discarded when dropped"""
+    """one full-hit-list batch in flight (kaamer_full_ticket / kaamer_sharded_full_ticket); wait() exactly once,
+    discarded when dropped"""
 
-    def __init__(self, handle):
-        self._h = handle
+    def __init__(self, handle, sharded=False):
+        self._h, self._sharded = handle, sharded
 
     def wait(self):
         out = C.POINTER(abi.BatchOut)()
         h, self._h = self._h, None
-        abi.check(abi.lib().kaamer_wait_batch(h, C.byref(out)))
+        L = abi.lib()
+        abi.check((L.kaamer_sharded_wait_batch if self._sharded else L.kaamer_wait_batch)(h, C.byref(out)))
         return BatchResult(out)
 
     def discard(self):
         h, self._h = self._h, None
         if h:
-            abi.lib().kaamer_full_ticket_discard(h)
+            L = abi.lib()
+            (L.kaamer_sharded_full_ticket_discard if self._sharded else L.kaamer_full_ticket_discard)(h)
 
     def __del__(self):
         try:
@@ -726,6 +755,13 @@ class Workspace:
 
     def exchange_pack(self, layout, d_send_ptr, stream=0):
         abi.check(abi.lib().kaamer_exchange_pack(self._h, C.byref(layout), d_send_ptr, C.c_void_p(stream)))
+
+    def exchange_stats_positions(self, back=0):
+        """-> (bitmap words the largest block between any pair of ranks needed, a bitmap section overflowed) of the merge
+        `back` calls ago on this workspace (kaamer_exchange_stats_positions)"""
+        out = (C.c_uint64 * 2)()
+        abi.check(abi.lib().kaamer_exchange_stats_positions(self._h, back, out))
+        return int(out[0]), int(out[1])
 
     def exchange_stats(self, back=0):
         """-> (merge sequence number, queries of the batch, entries the largest block any pair of ranks needed, overflow)

@@ -1283,17 +1283,19 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
 // ---- PositionHits bitmaps: layout helpers ---------------------------------------------------------
 // words of one hit's bitmap = ceil(SizeInKmer / 64); a query's bitmaps are contiguous, in the
 // order of its hit list.
-__global__ void pos_words_kernel(const QInfo *qinfo, const uint32_t *q_cnt, const uint32_t *d_nq, uint32_t *words)
+// sizes: NULL = QInfo.size (a search); after an exchange merge, the owned queries' SizeInKmer (QInfo.size then holds
+// their entry counts)
+__global__ void pos_words_kernel(const QInfo *qinfo, const int32_t *sizes, const uint32_t *q_cnt, const uint32_t *d_nq, uint32_t *words)
 {
     const uint32_t nq = *d_nq;
     for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (uint64_t)gridDim.x * blockDim.x) {
-        const int32_t size = qinfo[q].size;
+        const int32_t size = sizes ? sizes[q] : qinfo[q].size;
         const uint64_t w = size > 0 ? (uint64_t)q_cnt[q] * (((uint32_t)size + 63u) >> 6) : 0;
         words[q] = w > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)w;
     }
 }
 
-__global__ void pos_layout_kernel(const QInfo *qinfo, const uint32_t *q_cnt, const uint64_t *hit_off, const uint64_t *pos_base,
+__global__ void pos_layout_kernel(const QInfo *qinfo, const int32_t *sizes, const uint32_t *q_cnt, const uint64_t *hit_off, const uint64_t *pos_base,
                                   const uint32_t *d_nq, uint64_t *pos_off, unsigned long long *pos_bits, uint64_t bits_cap,
                                   uint32_t *status)
 {
@@ -1305,7 +1307,7 @@ __global__ void pos_layout_kernel(const QInfo *qinfo, const uint32_t *q_cnt, con
     const uint32_t lane = threadIdx.x & 63u;
     for (uint64_t q = gtid >> 6; q < nq; q += gsz >> 6) {
         const uint32_t cnt = q_cnt[q];
-        const int32_t size = qinfo[q].size;
+        const int32_t size = sizes ? sizes[q] : qinfo[q].size;
         const uint64_t w = size > 0 ? (((uint32_t)size + 63u) >> 6) : 0;
         for (uint32_t i = lane; i < cnt; i += 64) pos_off[hit_off[q] + i] = pos_base[q] + (uint64_t)i * w;
     }

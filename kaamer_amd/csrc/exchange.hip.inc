@@ -13,9 +13,14 @@
 //                                    bit 3: some block of this sender exceeded its capacity: the batch fails on EVERY rank)
 //     [2] queries of the batch   [3] queries owned by d = ceil((nq - d) / W)
 //     [4] entries this block NEEDED (= [0] unless it overflowed)
-//     [5] the largest [4] over the sender's W blocks   [6], [7] zero
+//     [5] the largest [4] over the sender's W blocks   [6], [7] zero (arrays = 4: see below)
 //     [8 .. 8+q_cap)             per owned query i (global query d + i W): number of entries
 //     then pid[e_cap], kmatch[e_cap], first_pos[e_cap]   (structure of arrays)
+// Blocks with PositionHits bitmaps (arrays = 4; search.go:442-452) add, after the counts, SizeInKmer[q_cap] (the entry
+// arrays follow it), and after the entry arrays, from the even word bits_off = 8 + 2 q_cap + 3 e_cap (rounded up), a
+// section of p_cap = (block_words - bits_off) / 2 u64 words: entry j of owned query i has ceil(SizeInKmer_i / 64) words at
+// bbase[i] + j words_i (bbase: the scan of entries_i x words_i).  [6] = bitmap words this block needed, [7] = the largest
+// [6] of the sender's W blocks, status bit 4 = bitmaps inside; a section that does not fit sets bits 0 / 3 as the entries do.
 // so the transport is an all-to-all with equal splits (grouped ncclSend / ncclRecv over xGMI: all
 // seven links busy at once), whatever the data-dependent sizes are.  The block size of a batch is the
 // caller's choice within the buffers' capacity (kaamer_exchange_layout_fit): word [5] of the W received
@@ -29,6 +34,8 @@
 //   kaamer_exchange_merge  per source, tiled scan of the received counts + totals per owned query;
 //                          copy into per-query contiguous entries; then the merge
 //                          (count_group_kernel MODE 2) on the owner's workspace
+//   arrays = 4             the same scans over bitmap words (modes 2, 3), x_pack_bits_kernel / x_unpack_bits_kernel,
+//                          and after the merge's bitmap layout x_or_bits_kernel (the bitmaps of one hit, OR-merged)
 #define X_BLOCK 1024
 #define X_ITEMS 8
 #define X_TILE (X_BLOCK * X_ITEMS)
@@ -57,7 +64,36 @@ struct XParams {
     uint64_t *tile_sum; // [rows][n_tiles] scratch of the tiled scans
     uint32_t n_tiles;
     uint32_t with_fp;   // 0: first positions are not wanted (protein search without -pos): their third of the entries stays untouched
+    // blocks with PositionHits bitmaps (arrays = 4)
+    uint64_t p_cap;     // u64 words of a block's bitmap section
+    uint64_t bits_off;  // u32 word at which the bitmap section starts (even: 8-byte aligned)
+    uint32_t ent_base;  // u32 word at which the entry arrays start: 8 + q_cap, or 8 + 2 q_cap with the SizeInKmer section
+    const QInfo *qinfo; // pack: the search's queries (QInfo.size = the SizeInKmer its bitmaps were laid out with)
+    const uint64_t *pos_off;
+    const unsigned long long *pos_bits;
+    uint64_t *dst_boff; // pack: [world][q_cap] bitmap word offset of each owned query inside its block
+    uint64_t *src_boff; // unpack: [world][q_cap] the same inside each received block
+    uint64_t *ent_boff; // unpack: [q_cap + 1] first bitmap word of each owned query in m_bits (aligned with ent_off)
+    int32_t *m_size;    // unpack: SizeInKmer of each owned query (as every block carried it)
+    unsigned long long *m_bits;
+    uint64_t mb_cap;
+    unsigned long long *pstats;  // unpack: {largest bitmap need between any pair of ranks, a bitmap section overflowed}
+    // OR-merge: the merge workspace's result
+    const uint32_t *r_nq, *r_cnt, *r_pid;
+    const uint64_t *r_off, *r_pos_off, *r_pos_base;
+    unsigned long long *r_pos_bits;
+    uint64_t r_bits_cap;
+    uint64_t *m_dst;    // [m_cap] per received entry: first word of its merged hit's bitmap
+    unsigned long long *g_tab;  // [2 m_cap] hash tables of the queries whose merged hits exceed the LDS table
 };
+
+__device__ __forceinline__ uint32_t x_words(int32_t size) { return size > 0 ? ((uint32_t)size + 63u) >> 6 : 0u; }
+__device__ __forceinline__ unsigned long long *x_bits(uint32_t *blk, const XParams &p) { return reinterpret_cast<unsigned long long *>(blk + p.bits_off); }
+__device__ __forceinline__ const unsigned long long *x_bits(const uint32_t *blk, const XParams &p)
+{
+    return reinterpret_cast<const unsigned long long *>(blk + p.bits_off);
+}
+__device__ __forceinline__ uint32_t x_sat32(uint64_t v) { return v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v; }
 
 __device__ __forceinline__ uint32_t *x_block(uint32_t *base, const XParams &p, uint32_t peer) { return base + (uint64_t)peer * p.block_words; }
 __device__ __forceinline__ const uint32_t *x_block(const uint32_t *base, const XParams &p, uint32_t peer) { return base + (uint64_t)peer * p.block_words; }
@@ -100,9 +136,11 @@ __device__ __forceinline__ uint32_t x_owned_checked(const XParams &p)
 //   MODE 0 (pack):   row d = destination rank; item i = hit count of query d + i W; n_items = queries owned by d
 //   MODE 1 (unpack): row s < W = source rank, item i = entries block s holds for owned query i; row W = their sum over
 //                    the sources; n_items = owned queries
+//   MODE 2 (pack, arrays = 4):   as MODE 0, item = bitmap words of query d + i W (hits x ceil(SizeInKmer / 64))
+//   MODE 3 (unpack, arrays = 4): as MODE 1, item = bitmap words block s holds for owned query i; row W = their sum
 template <int MODE> __device__ __forceinline__ uint32_t x_items(const XParams &p, uint32_t row)
 {
-    if (MODE == 0) {
+    if (MODE == 0 || MODE == 2) {
         const uint32_t nq = *p.d_nq;
         const uint32_t n = nq > row ? (nq - row + p.world - 1) / p.world : 0u;
         return n < p.q_cap ? n : p.q_cap;
@@ -112,6 +150,18 @@ template <int MODE> __device__ __forceinline__ uint32_t x_items(const XParams &p
 template <int MODE> __device__ __forceinline__ uint32_t x_value(const XParams &p, uint32_t row, uint64_t idx)
 {
     if (MODE == 0) return p.hit_cnt[row + idx * p.world];
+    if (MODE == 2) {
+        const uint64_t q = row + idx * p.world;
+        return x_sat32((uint64_t)p.hit_cnt[q] * x_words(p.qinfo[q].size));
+    }
+    if (MODE == 3) {
+        uint64_t v = 0;
+        for (uint32_t t = (row < p.world ? row : 0u); t < (row < p.world ? row + 1u : p.world); t++) {
+            const uint32_t *b = x_block(p.recv, p, t);
+            v += (uint64_t)b[X_HDR + idx] * x_words((int32_t)b[X_HDR + p.q_cap + idx]);
+        }
+        return x_sat32(v);
+    }
     if (row < p.world) return x_block(p.recv, p, row)[X_HDR + idx];
     uint32_t v = 0;
     for (uint32_t t = 0; t < p.world; t++) v += x_block(p.recv, p, t)[X_HDR + idx];
@@ -140,7 +190,7 @@ template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_sums_kerne
 // total, the status and the number of owned queries (unpack)
 template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_top_kernel(XParams p)
 {
-    const uint32_t rows = MODE == 0 ? p.world : p.world + 1u;
+    const uint32_t rows = (MODE & 1) ? p.world + 1u : p.world;
     __shared__ uint64_t s_total[65];
     for (uint32_t row = 0; row < rows; row++) {
         uint64_t carry = 0;
@@ -158,6 +208,40 @@ template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_top_kernel
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
+    if (MODE == 2) {
+        // the bitmap sections: [6] = words this block needed, [7] = the largest [6] of the sender's W blocks, bit 4 =
+        // positions inside; a section that does not fit sets the overflow bit as the entries do (x_pack_copy_kernel
+        // spreads it to bit 3 of every block of this sender)
+        uint32_t mx = 0;
+        for (uint32_t d = 0; d < p.world; d++) {
+            uint32_t *blk = x_block(p.send, p, d);
+            const uint64_t need = s_total[d];
+            blk[6] = x_sat32(need);
+            blk[1] |= 16u | (need > p.p_cap ? 1u : 0u);
+            mx = blk[6] > mx ? blk[6] : mx;
+        }
+        for (uint32_t d = 0; d < p.world; d++) x_block(p.send, p, d)[7] = mx;
+        return;
+    }
+    if (MODE == 3) {
+        const uint32_t W = p.world;
+        const uint32_t n_owned = x_owned_checked(p);
+        const uint64_t carry = s_total[W];
+        p.ent_boff[n_owned] = carry;
+        uint32_t need = 0, povf = 0, bad = carry > p.mb_cap ? 1u : 0u;
+        for (uint32_t t = 0; t < W; t++) {
+            const uint32_t *bh = x_block(p.recv, p, t);
+            need = bh[7] > need ? bh[7] : need;
+            if (bh[6] > p.p_cap || bh[7] > p.p_cap) povf = 1u;
+            if (!(bh[1] & 16u)) bad = 1u;  // the owner wants bitmaps the sender did not pack: an error, not empty bitmaps
+        }
+        if (p.pstats) { p.pstats[0] = need; p.pstats[1] = povf; }
+        if (bad | povf) {
+            atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP);
+            *p.d_nq_owned = 0u;
+        }
+        return;
+    }
     if (MODE == 0) {
         const uint32_t nq = *p.d_nq;
         for (uint32_t d = 0; d < p.world; d++) {
@@ -222,7 +306,23 @@ template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_apply_kern
         const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
         if (idx >= n) continue;
         const uint64_t o = tbase + ex[i];
-        if (MODE == 0) {
+        if (MODE == 2) {
+            const uint64_t q = row + idx * p.world;
+            x_block(p.send, p, row)[X_HDR + p.q_cap + idx] = (uint32_t)p.qinfo[q].size;
+            p.dst_boff[(uint64_t)row * p.q_cap + idx] = o;
+        } else if (MODE == 3) {
+            if (row < p.world) {
+                p.src_boff[(uint64_t)row * p.q_cap + idx] = o;
+            } else {
+                p.ent_boff[idx] = o;
+                // all shards translate alike: every block must carry the same SizeInKmer, or they are not one batch
+                const uint32_t sz = x_block(p.recv, p, 0)[X_HDR + p.q_cap + idx];
+                bool same = true;
+                for (uint32_t t = 1; t < p.world; t++) same = same && x_block(p.recv, p, t)[X_HDR + p.q_cap + idx] == sz;
+                p.m_size[idx] = (int32_t)sz;
+                if (!same) { atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP); *p.d_nq_owned = 0u; }
+            }
+        } else if (MODE == 0) {
             x_block(p.send, p, row)[X_HDR + idx] = v[i];
             p.dst_off[(uint64_t)row * p.q_cap + idx] = o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o;
         } else if (row < p.world) {
@@ -317,7 +417,7 @@ __global__ __launch_bounds__(256) void x_pack_copy_kernel(XParams p)
         const uint64_t o = p.dst_off[(uint64_t)d * p.q_cap + i];
         if (o + n > p.e_cap) continue;  // over capacity: flagged by the scan kernel
         const uint64_t s = p.hit_off[q];
-        uint32_t *blk = x_block(p.send, p, d) + X_HDR + p.q_cap;
+        uint32_t *blk = x_block(p.send, p, d) + p.ent_base;
         for (uint32_t t = gl; t < n; t += X_GROUP_) {
             blk[o + t] = p.pid[s + t];
             blk[p.e_cap + o + t] = p.km[s + t];
@@ -396,7 +496,7 @@ __global__ __launch_bounds__(256) void x_unpack_copy_kernel(XParams p)
             const uint32_t n = blk[X_HDR + i];
             const uint64_t o = p.src_off[(uint64_t)s * p.q_cap + i];
             if (o + n > p.e_cap || dst + n > p.m_cap) break;  // flagged by the scan kernel
-            const uint32_t *ent = blk + X_HDR + p.q_cap;
+            const uint32_t *ent = blk + p.ent_base;
             for (uint32_t t = gl; t < n; t += X_GROUP_) {
                 p.m_pid[dst + t] = ent[o + t];
                 p.m_km[dst + t] = ent[p.e_cap + o + t];
@@ -404,5 +504,151 @@ __global__ __launch_bounds__(256) void x_unpack_copy_kernel(XParams p)
             }
             dst += n;
         }
+    }
+}
+
+// ---- PositionHits bitmaps through the exchange (arrays = 4) ------------------------------------------------------------
+// X_GROUP lanes per query: the bitmaps of its hits, in hit-list order, after the bitmaps of the query before it in the
+// block (hit j of owned query i at dst_boff[i] + j * ceil(SizeInKmer_i / 64)).  The search laid a query's bitmaps out at
+// pos_off[hit], words = ceil(QInfo.size / 64).
+template <uint32_t X_GROUP_T>
+__global__ __launch_bounds__(256) void x_pack_bits_kernel(XParams p)
+{
+    constexpr uint32_t X_GROUP_ = X_GROUP_T;
+    // a search that failed (its bitmap storage included: then pos_off was never laid out) sends no bitmaps; its blocks
+    // carry status bit 2 and the batch fails on every rank
+    if (p.src_status && *p.src_status) return;
+    const uint32_t nq = *p.d_nq, W = p.world, gl = threadIdx.x & (X_GROUP_ - 1u);
+    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / X_GROUP_;
+    const uint64_t n_grp = ((uint64_t)gridDim.x * blockDim.x) / X_GROUP_;
+    for (uint64_t q = grp; q < nq; q += n_grp) {
+        const uint32_t d = (uint32_t)(q % W);
+        const uint64_t i = q / W;
+        if (i >= p.q_cap) continue;
+        const uint32_t n = p.hit_cnt[q], w = x_words(p.qinfo[q].size);
+        const uint64_t tot = (uint64_t)n * w;
+        if (tot == 0) continue;
+        const uint64_t o = p.dst_boff[(uint64_t)d * p.q_cap + i];
+        if (o + tot > p.p_cap) continue;  // over capacity: flagged by the scan kernel
+        const uint64_t s = p.hit_off[q];
+        unsigned long long *dst = x_bits(x_block(p.send, p, d), p) + o;
+        for (uint64_t t = gl; t < tot; t += X_GROUP_) {
+            const uint64_t h = t / w;
+            dst[t] = p.pos_bits[p.pos_off[s + h] + (t - h * w)];
+        }
+    }
+}
+
+// X_GROUP lanes per owned query: the bitmaps of all sources, source after source -- entry k of the query's unpacked
+// entries (ent_off) has its bitmap at ent_boff[i] + k * words.  Nothing when the headers, the sizes or a section failed
+// (d_nq_owned = 0).
+template <uint32_t X_GROUP_T>
+__global__ __launch_bounds__(256) void x_unpack_bits_kernel(XParams p)
+{
+    constexpr uint32_t X_GROUP_ = X_GROUP_T;
+    const uint32_t W = p.world, gl = threadIdx.x & (X_GROUP_ - 1u);
+    const uint32_t n_owned = *p.d_nq_owned;
+    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / X_GROUP_;
+    const uint64_t n_grp = ((uint64_t)gridDim.x * blockDim.x) / X_GROUP_;
+    for (uint64_t i = grp; i < n_owned; i += n_grp) {
+        const uint32_t w = x_words(p.m_size[i]);
+        uint64_t dst = p.ent_boff[i];
+        for (uint32_t s = 0; s < W && w; s++) {
+            const uint32_t *blk = x_block(p.recv, p, s);
+            const uint64_t tot = (uint64_t)blk[X_HDR + i] * w;
+            const uint64_t o = p.src_boff[(uint64_t)s * p.q_cap + i];
+            if (o + tot > p.p_cap || dst + tot > p.mb_cap) break;  // flagged by the scan kernel
+            const unsigned long long *src = x_bits(blk, p) + o;
+            for (uint64_t t = gl; t < tot; t += X_GROUP_) p.m_bits[dst + t] = src[t];
+            dst += tot;
+        }
+    }
+}
+
+// One wave per owned query, after the merge (count_group_kernel MODE 2) and the layout of the merged bitmaps
+// (pos_words_kernel / scan / pos_layout_kernel, which zeroed them): every received entry's bitmap is ORed into the bitmap
+// of its merged hit.  A hash of the merged ids gives each entry its hit: in LDS (sized to the query), or -- for queries
+// with more merged hits than half the LDS table -- in HBM (2 x entries slots at 2 ent_off[i], as the G tier keeps its
+// tables); each entry's destination is kept in LDS, or in HBM (m_dst) for queries with more entries than that holds.
+// Only a query that touches HBM scratch pays a device-scope fence (an agent-scope release writes L2 back: with one
+// per query the pass took 148 ms of a 1 M-read batch).
+// Every k-mer key is owned by exactly one shard, so the bitmaps one (query, protein) receives from different shards are
+// DISJOINT: the 64-bit atomicOr of one word by several lanes sets each bit once, whatever the order, and the merged
+// bitmap equals the unsharded search's bit for bit.
+#define XO_LDS_SLOTS 1024u
+__device__ __forceinline__ uint32_t xo_hash(uint32_t pid) { return pid * 2654435761u; }
+
+__global__ __launch_bounds__(64) void x_or_bits_kernel(XParams p)
+{
+    __shared__ uint32_t s_key[XO_LDS_SLOTS], s_val[XO_LDS_SLOTS];
+    __shared__ uint64_t s_dst[XO_LDS_SLOTS];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t nq = *p.r_nq;
+    if (p.r_pos_base[nq] > p.r_bits_cap) return;   // pos_layout_kernel flagged ST_POS_CAP and laid nothing out
+    for (uint32_t i = blockIdx.x; i < nq; i += gridDim.x) {
+        const uint32_t m = p.r_cnt[i];
+        const uint64_t e0 = p.ent_off[i], ne = p.ent_off[i + 1] - e0;
+        const uint32_t w = x_words(p.m_size[i]);
+        if (m == 0 || ne == 0 || w == 0) continue;
+        const uint64_t hb = p.r_off[i];
+        const bool lds = m <= XO_LDS_SLOTS / 2, lds_dst = ne <= XO_LDS_SLOTS;
+        uint32_t lg = 6;
+        while ((1u << lg) < 2u * m && (1u << lg) < XO_LDS_SLOTS) lg++;
+        const uint32_t lcap = 1u << lg;
+        const uint64_t gcap = 2 * ne;   // >= 2 m: the merged ids are a subset of the entries' ids
+        unsigned long long *gt = p.g_tab + 2 * e0;
+        if (lds) for (uint32_t t = lane; t < lcap; t += 64) s_key[t] = KH_EMPTY_PID;
+        else for (uint64_t t = lane; t < gcap; t += 64) gt[t] = ~0ull;
+        if (!lds) __threadfence();
+        __syncthreads();
+        for (uint32_t j = lane; j < m; j += 64) {   // the merged ids are distinct
+            const uint32_t pid = p.r_pid[hb + j];
+            if (lds) {
+                uint32_t h = xo_hash(pid) >> (32 - lg);
+                while (atomicCAS(&s_key[h], KH_EMPTY_PID, pid) != KH_EMPTY_PID) h = (h + 1u) & (lcap - 1u);
+                s_val[h] = j;
+            } else {
+                const unsigned long long v = ((unsigned long long)pid << 32) | j;
+                uint64_t h = (uint64_t)xo_hash(pid) % gcap;
+                while (atomicCAS(&gt[h], ~0ull, v) != ~0ull) h = h + 1 == gcap ? 0 : h + 1;
+            }
+        }
+        if (!lds) __threadfence();
+        __syncthreads();
+        for (uint64_t k = lane; k < ne; k += 64) {
+            const uint32_t pid = p.m_pid[e0 + k];
+            uint64_t dst = ~0ull;
+            if (lds) {
+                uint32_t h = xo_hash(pid) >> (32 - lg);
+                for (uint32_t probe = 0; probe < lcap; probe++) {
+                    const uint32_t key = s_key[h];
+                    if (key == pid) { dst = p.r_pos_off[hb + s_val[h]]; break; }
+                    if (key == KH_EMPTY_PID) break;
+                    h = (h + 1u) & (lcap - 1u);
+                }
+            } else {
+                uint64_t h = (uint64_t)xo_hash(pid) % gcap;
+                for (uint64_t probe = 0; probe < gcap; probe++) {
+                    const unsigned long long v = __hip_atomic_load(&gt[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (v == ~0ull) break;
+                    if ((uint32_t)(v >> 32) == pid) { dst = p.r_pos_off[hb + (uint32_t)v]; break; }
+                    h = h + 1 == gcap ? 0 : h + 1;
+                }
+            }
+            // (~0: the merge lost this query -- its status already fails the batch)
+            if (lds_dst) s_dst[k] = dst;
+            else p.m_dst[e0 + k] = dst;
+        }
+        if (!lds_dst) __threadfence();
+        __syncthreads();
+        const uint64_t b0 = p.ent_boff[i], tot = ne * w;
+        for (uint64_t t = lane; t < tot; t += 64) {
+            const unsigned long long bits = p.m_bits[b0 + t];
+            if (!bits) continue;
+            const uint64_t k = t / w;
+            const uint64_t dst = lds_dst ? s_dst[k] : __hip_atomic_load(&p.m_dst[e0 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (dst != ~0ull) atomicOr(&p.r_pos_bits[dst + (t - k * w)], bits);
+        }
+        __syncthreads();
     }
 }

@@ -21,6 +21,8 @@ struct ShardState {
     kaamer_exchange_layout layout{};   // capacity: what d_send / d_recv hold
     kaamer_exchange_layout wire{};     // the blocks of the batch in flight (<= capacity)
     uint64_t e_cap = 0;
+    uint64_t p_cap = 0;                // bitmap words a block can hold (full calls with positions)
+    bool full = false;                 // workspaces of a full call (kaamer_sharded_search_batch): first_pos = 1, CSR merge
     uint32_t *d_send = nullptr, *d_recv = nullptr;
     size_t x_words = 0;
     hipStream_t stream = nullptr;
@@ -40,6 +42,7 @@ struct ShardSet {
     bool busy = false;
     uint64_t need_entries = 0;   // what the largest (shard -> owner) block of the previous batch on this set needed
     uint32_t need_queries = 0;   // its queries (ORFs)
+    uint64_t need_pos_words = 0; // the bitmap words it needed (0: the previous batch carried no bitmaps)
 };
 #define KAAMER_SHARDED_SETS 3   /* calls in flight per handle: the goroutines of search_fastq.go:60-66 against one handle */
 
@@ -169,6 +172,8 @@ template <class T> static int dev_grow(T **p, size_t *cap, size_t need)
 struct ShardBounds {
     uint64_t e_cap, g_slots, max_hits;
     uint32_t max_queries;
+    bool full, pos;      // a full call (hit lists to the host), with PositionHits bitmaps
+    uint64_t p_cap;      // bitmap words per block (pos)
 };
 
 static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq_bytes, uint32_t n_seqs, int32_t seq_type, const ShardBounds &b, uint32_t K)
@@ -178,7 +183,8 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
     const kaamer_workspace_opts &o = st.opts;
     const bool fits = st.ws && o.seq_type == seq_type && o.max_seq_bytes >= seq_bytes && o.max_seqs >= (n_seqs ? n_seqs : 1) &&
                       o.g_tier_slots >= b.g_slots && o.max_queries >= b.max_queries && st.e_cap >= b.e_cap &&
-                      o.max_hits >= b.max_hits && (b.max_hits != 0 || o.max_hits == 0);
+                      o.max_hits >= b.max_hits && (b.max_hits != 0 || o.max_hits == 0) &&
+                      st.full == b.full && (o.want_positions != 0) == b.pos && (!b.pos || st.p_cap >= b.p_cap);
     if (!fits) {
         HIPCHK(hipStreamSynchronize(st.stream));
         if (st.ws) kaamer_workspace_free(st.ws);
@@ -189,7 +195,9 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
         g.max_seq_bytes = seq_bytes + seq_bytes / 4 + 4096;
         g.max_seqs = (n_seqs ? n_seqs : 1) + n_seqs / 4 + 16;
         g.seq_type = seq_type;
-        g.first_pos = nucl ? 1u : 2u;  // the exchange wants an explicit, equal setting on both workspaces
+        // the exchange wants an explicit, equal setting on both workspaces; kaamer_batch_out always carries first positions
+        g.first_pos = (nucl || b.full) ? 1u : 2u;
+        g.want_positions = b.pos ? 1u : 0u;
         g.g_tier_slots = b.g_slots;
         g.max_queries = b.max_queries;
         g.max_hits = b.max_hits;       // 0: the library's default for the input size (as the unsharded call starts)
@@ -197,7 +205,10 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
         if (rc) { st.ws = nullptr; return rc; }
         st.opts = g;
         st.e_cap = b.e_cap + b.e_cap / 4;
-        rc = kaamer_exchange_layout_init(W, rank, st.ws->q_cap, st.e_cap, &st.layout);
+        st.full = b.full;
+        st.p_cap = b.pos ? b.p_cap + b.p_cap / 4 : 0;
+        if (b.pos) rc = kaamer_exchange_layout_init_positions(W, rank, st.ws->q_cap, st.e_cap, st.p_cap, &st.layout);
+        else rc = kaamer_exchange_layout_init(W, rank, st.ws->q_cap, st.e_cap, &st.layout);
         if (rc) return rc;
         kaamer_workspace_opts m;
         memset(&m, 0, sizeof m);
@@ -208,6 +219,9 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
         m.first_pos = g.first_pos;
         m.max_hits = (uint64_t)W * st.layout.e_cap;
         m.g_tier_slots = b.g_slots;
+        m.want_positions = g.want_positions;
+        m.max_pos_words = b.pos ? (uint64_t)W * x_p_cap(&st.layout) : 0;   // merged bitmaps <= the words received
+        m.compact = b.full ? 1u : 0u;   // the full call copies CSR to the host
         rc = kaamer_workspace_create(st.ix, &m, &st.mws);
         if (rc) { st.mws = nullptr; return rc; }
         const size_t words = (size_t)W * st.layout.block_words;
@@ -223,7 +237,7 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
     }
     int rc = dev_grow(&st.d_seqs, &st.seq_cap, (size_t)seq_bytes + 16);
     if (!rc) rc = dev_grow(&st.d_off, &st.off_cap, (size_t)n_seqs + 1);
-    if (!rc) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K));
+    if (!rc && !b.full) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K));
     return rc;
 }
 
@@ -238,6 +252,10 @@ struct kaamer_sharded_ticket {
     ShardBounds b;
     bool adaptive;   // this attempt's exchange blocks were sized from the previous call's need, not the capacity
     int attempt;
+};
+// a full call (kaamer_sharded_search_batch): the same pipeline without the post-steps (t.b.full)
+struct kaamer_sharded_full_ticket {
+    kaamer_sharded_ticket t;
 };
 
 static void sharded_sync_all(ShardSet *set)
@@ -273,13 +291,15 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
     }
     // the blocks of this batch: what the previous batch on this set needed + a quarter (its W x W headers, read after the
     // call), or the capacity for a first call and for a retry.  What the peer copies move is payload, not capacity.
-    t->adaptive = t->attempt == 0 && sx->need_entries != 0;
+    t->adaptive = t->attempt == 0 && sx->need_entries != 0 && (!t->b.pos || sx->need_pos_words != 0);
     for (uint32_t s = 0; s < W; s++) {
         ShardState &st = sh[s];
         st.wire = st.layout;
         if (t->adaptive) {
-            const int rc = kaamer_exchange_layout_fit(&st.layout, sx->need_queries + sx->need_queries / 4 + 64,
-                                                      sx->need_entries + sx->need_entries / 4 + 1024, nucl ? 1 : 0, &st.wire);
+            const uint32_t nq = sx->need_queries + sx->need_queries / 4 + 64;
+            const uint64_t ne = sx->need_entries + sx->need_entries / 4 + 1024;
+            const int rc = t->b.pos ? kaamer_exchange_layout_fit_positions(&st.layout, nq, ne, sx->need_pos_words + sx->need_pos_words / 4 + 1024, &st.wire)
+                                    : kaamer_exchange_layout_fit(&st.layout, nq, ne, (nucl || t->b.full) ? 1 : 0, &st.wire);
             if (rc) return rc;
         }
     }
@@ -309,6 +329,11 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
             else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, bw * 4, ow.stream));
         }
         kaamer_device_result mr;
+        if (t->b.full) {   // the merged CSR (bitmaps included) stays on the owner until sharded_collect_full copies it
+            const int rc = kaamer_exchange_merge(ow.mws, &ow.wire, ow.d_recv, ow.stream, &mr);
+            if (rc) return rc;
+            continue;
+        }
         kaamer_topn_result tr;
         kaamer_topn_opts tt = t->top;
         tt.best_start_codon = nucl ? 1u : 0u;
@@ -478,11 +503,9 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
 // The worker pool of search_protein.go:58-118 against ONE sharded handle: submit takes a free set of per-shard
 // workspaces, buffers and streams (callers beyond the sets wait for one), copies the caller's buffers into the set's
 // pinned staging and enqueues the whole batch on every device; wait collects it.  A ticket is waited for exactly once.
-int kaamer_sharded_submit_batch_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket **ticket)
+// top = NULL: a full call (kaamer_sharded_submit_batch_flat), `t` is then the caller's (a kaamer_sharded_full_ticket's)
+static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket *t)
 {
-    if (!sx || !in || !top || !ticket || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
-        return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top: bad argument");
-    *ticket = nullptr;
     ShardSet *set = nullptr;
     {
         std::unique_lock<std::mutex> lock(sx->mu);
@@ -494,13 +517,18 @@ int kaamer_sharded_submit_batch_top(kaamer_sharded_index *sx, const kaamer_batch
         }
         set->busy = true;
     }
-    kaamer_sharded_ticket *t = new (std::nothrow) kaamer_sharded_ticket();
-    if (!t) { sharded_release(sx, set); return kaamer_fail(KAAMER_E_NOMEM, "ticket"); }
     memset(t, 0, sizeof *t);
     t->sx = sx; t->set = set; t->n_seqs = in->n_seqs; t->seq_type = in->seq_type; t->seq_bytes = in->offsets[in->n_seqs];
-    t->top = *top;
+    if (top) t->top = *top;
     // entries one (shard -> owner) block can hold: data dependent; enlarged on KAAMER_E_CAPACITY like every bound
     t->b.e_cap = 2 * t->seq_bytes / sx->n + 65536;
+    t->b.full = top == nullptr;
+    t->b.pos = t->b.full && in->want_positions != 0;
+    if (t->b.pos) {   // bitmap words per entry ~ 1 + SizeInKmer / 64 (ORFs: a third of the nucleotides)
+        const bool nucl = in->seq_type == KAAMER_NUCLEOTIDE || in->seq_type == KAAMER_READS;
+        const uint64_t mean = t->seq_bytes / (in->n_seqs ? in->n_seqs : 1u) / (nucl ? 3u : 1u);
+        t->b.p_cap = t->b.e_cap * (1 + mean / 64);
+    }
     // the caller's buffers -> pinned staging, once; every device copies from there (and a retry runs from there)
     const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
     const size_t in_need = off_at + ((size_t)in->n_seqs + 1) * 8;
@@ -517,7 +545,19 @@ int kaamer_sharded_submit_batch_top(kaamer_sharded_index *sx, const kaamer_batch
         memcpy(set->h_in + off_at, in->offsets, ((size_t)in->n_seqs + 1) * 8);
         rc = sharded_enqueue(t);
     }
-    if (rc) { delete t; sharded_release(sx, set); return rc; }
+    if (rc) sharded_release(sx, set);
+    return rc;
+}
+
+int kaamer_sharded_submit_batch_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket **ticket)
+{
+    if (!sx || !in || !top || !ticket || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
+        return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top: bad argument");
+    *ticket = nullptr;
+    kaamer_sharded_ticket *t = new (std::nothrow) kaamer_sharded_ticket();
+    if (!t) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
+    const int rc = sharded_submit(sx, in, top, t);
+    if (rc) { delete t; return rc; }
     *ticket = t;
     return KAAMER_OK;
 }
@@ -586,6 +626,234 @@ int kaamer_sharded_search_batch_top_flat(kaamer_sharded_index *sx, const uint8_t
     const int rc = kaamer_sharded_submit_batch_top_flat(sx, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, &t);
     if (rc) return rc;
     return kaamer_sharded_wait_batch_top(t, out);
+}
+
+// ---- full hit lists (kaamer_sharded_search_batch) ----------------------------------------------------------------------
+// Waits for the attempt, checks every workspace and copies each owner's merged CSR (bitmaps included) to the host; then
+// interleaves the owners' queries back into batch order (query q is owned by shard q mod W).  The query data (q, orf_aa,
+// starts_alt) is shard 0's: every shard translates the batch alike.
+static int sharded_collect_full(kaamer_sharded_ticket *t, kaamer_batch_out **out)
+{
+    ShardSet *sx = t->set;
+    const uint32_t W = t->sx->n;
+    const bool pos = t->b.pos;
+    std::vector<ShardState> &sh = sx->sh;
+    struct Guard {
+        ShardSet *set; bool armed;
+        ~Guard() { if (armed) sharded_sync_all(set); }
+    } guard{ sx, true };
+    int err = KAAMER_OK;
+    char why[256] = "";
+    for (uint32_t d = 0; d < W; d++) {
+        ShardState &ow = sh[d];
+        const int rc = kaamer_workspace_finish(ow.mws, ow.stream, nullptr);
+        if (rc && !err) {
+            err = rc;
+            snprintf(why, sizeof why, "owner %u: %s", d, kaamer_last_error());
+            bool named = false;
+            for (uint32_t s = 0; s < W; s++) {   // which bound: a shard's own search status says what ran out there
+                uint32_t sst = 0;
+                (void)hipSetDevice(sh[s].device);
+                (void)hipStreamSynchronize(sh[s].stream);
+                if (hipMemcpy(&sst, sh[s].ws->d_status_out, 4, hipMemcpyDeviceToHost) == hipSuccess && sst) {
+                    sh[s].ws->clean = false;   // an aborted batch may leave per-batch state behind
+                    if (!named) snprintf(why, sizeof why, "shard %u: search status 0x%x", s, sst);
+                    named = true;
+                }
+            }
+        }
+    }
+    guard.armed = false;  // every owner's stream has been waited for (and with it every shard's packs)
+    {   // what this batch's blocks needed (every owner read the same W x W figures): sizes the next call's blocks
+        uint64_t st4[4], sp[2] = { 0, 0 };
+        if (kaamer_exchange_stats(sh[0].mws, 0, st4) == KAAMER_OK) { sx->need_queries = (uint32_t)st4[1]; sx->need_entries = st4[2]; }
+        if (kaamer_exchange_stats_positions(sh[0].mws, 0, sp) == KAAMER_OK) sx->need_pos_words = sp[0];
+    }
+    if (err) return kaamer_fail(err, "sharded search: %s", why);
+
+    kaamer_workspace *q_ws = sh[0].ws;
+    batch_out_owner *bo = new (std::nothrow) batch_out_owner();
+    if (!bo) return kaamer_fail(KAAMER_E_NOMEM, "batch_out");
+    std::unique_ptr<batch_out_owner> own(bo);
+    uint32_t nq = 0;
+    hipError_t e = hipSetDevice(sh[0].device);
+    if (e == hipSuccess) e = hipMemcpy(&nq, q_ws->d_nq, 4, hipMemcpyDeviceToHost);
+    // each owner's merged queries, CSR
+    struct OwnerCsr {
+        uint32_t n = 0;
+        std::vector<uint64_t> off, pos_base, pos_off, bits;
+        std::vector<uint32_t> cnt, pid, km, fp;
+    };
+    std::vector<OwnerCsr> oc(W);
+    uint64_t n_hits = 0, n_words = 0;
+    for (uint32_t d = 0; d < W && e == hipSuccess; d++) {
+        ShardState &ow = sh[d];
+        kaamer_workspace *m = ow.mws;
+        OwnerCsr &o = oc[d];
+        hipStream_t s = ow.stream;
+        e = hipSetDevice(ow.device);
+        if (e == hipSuccess) e = hipMemcpy(&o.n, m->d_nq, 4, hipMemcpyDeviceToHost);
+        const uint32_t want = nq > d ? (nq - d + W - 1) / W : 0u;
+        if (e == hipSuccess && o.n != want) return kaamer_fail(KAAMER_E_HIP, "sharded search: owner %u merged %u queries, expected %u", d, o.n, want);
+        o.off.resize((size_t)o.n + 1); o.cnt.resize((size_t)o.n + 1);
+        if (pos) o.pos_base.resize((size_t)o.n + 1);
+        if (e == hipSuccess) e = hipMemcpyAsync(o.off.data(), m->d_csr_off, ((size_t)o.n + 1) * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && o.n) e = hipMemcpyAsync(o.cnt.data(), m->d_q_cnt, (size_t)o.n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && pos) e = hipMemcpyAsync(o.pos_base.data(), m->d_pos_base, ((size_t)o.n + 1) * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) break;
+        const uint64_t h = o.off[o.n], w = pos ? o.pos_base[o.n] : 0;
+        o.pid.resize(h + 1); o.km.resize(h + 1); o.fp.resize(h + 1);
+        if (pos) { o.pos_off.resize(h + 1); o.bits.resize(w + 1); }
+        if (h) {
+            e = hipMemcpyAsync(o.pid.data(), m->d_c_pid, h * 4, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(o.km.data(), m->d_c_km, h * 4, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(o.fp.data(), m->d_c_fp, h * 4, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess && pos) e = hipMemcpyAsync(o.pos_off.data(), m->d_pos_off, h * 8, hipMemcpyDeviceToHost, s);
+        }
+        if (e == hipSuccess && w) e = hipMemcpyAsync(o.bits.data(), m->d_pos_bits, w * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        n_hits += h; n_words += w;
+    }
+    // the batch's queries as shard 0 translated them
+    uint64_t n_sa = 0;
+    unsigned long long n_aa = 0;
+    bo->q.resize(nq);
+    if (e == hipSuccess) e = hipSetDevice(sh[0].device);
+    if (e == hipSuccess && nq) e = hipMemcpy(bo->q.data(), q_ws->d_q, (size_t)nq * sizeof(kaamer_query_meta), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && q_ws->nucleotide) {
+        const size_t cap6 = (size_t)q_ws->max_seqs * 6;
+        e = hipMemcpy(&n_aa, q_ws->d_n_pos, sizeof n_aa, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&n_sa, q_ws->d_off3 + 2 * (cap6 + 1) + (size_t)t->n_seqs * 6, sizeof n_sa, hipMemcpyDeviceToHost);
+        bo->orf_aa.resize(n_aa + 1); bo->starts_alt.resize(n_sa + 1);
+        if (e == hipSuccess && n_aa) e = hipMemcpy(bo->orf_aa.data(), q_ws->d_orf_aa, n_aa, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && n_sa) e = hipMemcpy(bo->starts_alt.data(), q_ws->d_starts_alt, n_sa * sizeof(int32_t), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(e));
+
+    // ---- interleave into batch order
+    bo->hit_off.resize((size_t)nq + 1); bo->hit_cnt.resize((size_t)nq + 1);
+    if (!bo->pid.resize(n_hits) || !bo->km.resize(n_hits) || !bo->fp.resize(n_hits)) return kaamer_fail(KAAMER_E_NOMEM, "hit lists");
+    if (pos) { bo->pos_off.resize(n_hits + 1); bo->pos_bits.resize(n_words + 1); }
+    uint64_t hcur = 0, wcur = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        const OwnerCsr &o = oc[q % W];
+        const uint32_t i = q / W;
+        const uint64_t a = o.off[i], n = o.cnt[i];
+        bo->hit_off[q] = hcur;
+        bo->hit_cnt[q] = (uint32_t)n;
+        memcpy(bo->pid.data() + hcur, o.pid.data() + a, n * 4);
+        memcpy(bo->km.data() + hcur, o.km.data() + a, n * 4);
+        memcpy(bo->fp.data() + hcur, o.fp.data() + a, n * 4);
+        if (pos) {
+            const uint64_t b0 = o.pos_base[i], nw = o.pos_base[i + 1] - b0;
+            memcpy(bo->pos_bits.data() + wcur, o.bits.data() + b0, nw * 8);
+            for (uint64_t j = 0; j < n; j++) bo->pos_off[hcur + j] = wcur + (o.pos_off[a + j] - b0);
+            wcur += nw;
+        }
+        hcur += n;
+    }
+    bo->hit_off[nq] = hcur;
+    // work counters (the rule of the top call): lookups, probes, postings are the shards' (every key is looked up by one
+    // shard); inputs and queries one shard's; hits those of the merged result
+    kaamer_counters c;
+    memset(&c, 0, sizeof c);
+    for (uint32_t d = 0; d < W; d++) {
+        kaamer_counters sc;
+        HIPCHK(hipSetDevice(sh[d].device));
+        HIPCHK(hipMemcpy(&sc, sh[d].ws->d_counters, sizeof sc, hipMemcpyDeviceToHost));
+        c.n_lookup += sc.n_lookup; c.n_probe += sc.n_probe; c.n_found += sc.n_found; c.n_post += sc.n_post;
+        c.n_lists += sc.n_lists; c.n_list_ids += sc.n_list_ids; c.n_overflow += sc.n_overflow;
+        if (d == 0) { c.n_in = sc.n_in; c.n_queries = sc.n_queries; }
+    }
+    c.n_hits = n_hits;
+    memset(&bo->pub, 0, sizeof bo->pub);
+    bo->pub.n_queries = nq;
+    bo->pub.q = bo->q.data();
+    bo->pub.hit_off = bo->hit_off.data();
+    bo->pub.hit_cnt = bo->hit_cnt.data();
+    bo->pub.hit_pid = bo->pid.data();
+    bo->pub.hit_kmatch = bo->km.data();
+    bo->pub.hit_first_pos = bo->fp.data();
+    if (q_ws->nucleotide) { bo->pub.orf_aa = bo->orf_aa.data(); bo->pub.starts_alt = bo->starts_alt.data(); }
+    if (pos) { bo->pub.pos_off = bo->pos_off.data(); bo->pub.pos_bits = bo->pos_bits.data(); }
+    bo->pub.counters = c;
+    *out = &own.release()->pub;
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_submit_batch_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                     int32_t want_positions, kaamer_sharded_full_ticket **ticket)
+{
+    if (!sx || !ticket || !offsets || (n_seqs && !seqs)) return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch: bad argument");
+    *ticket = nullptr;
+    kaamer_batch_in in;
+    flat_in(&in, seqs, offsets, n_seqs, seq_type, want_positions);
+    kaamer_sharded_full_ticket *ft = new (std::nothrow) kaamer_sharded_full_ticket();
+    if (!ft) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
+    const int rc = sharded_submit(sx, &in, nullptr, &ft->t);
+    if (rc) { delete ft; return rc; }
+    *ticket = ft;
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_wait_batch(kaamer_sharded_full_ticket *ft, kaamer_batch_out **out)
+{
+    if (!ft || !out) return kaamer_fail(KAAMER_E_ARG, "sharded_wait_batch: bad argument");
+    *out = nullptr;
+    kaamer_sharded_ticket *t = &ft->t;
+    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
+    int rc;
+    for (;;) {
+        rc = sharded_collect_full(t, out);
+        if (rc != KAAMER_E_CAPACITY || t->attempt >= 6) break;
+        t->attempt++;
+        if (!t->adaptive) {   // the bounds themselves were too small: enlarge them all, as kaamer_sharded_wait_batch_top does
+            t->b.e_cap *= 4;
+            t->b.p_cap *= 4;
+            t->b.g_slots = t->b.g_slots ? t->b.g_slots * 4 : (128ull << 20);
+            t->b.max_hits = t->b.max_hits ? t->b.max_hits * 4 : t->seq_bytes * 8 + 65536;
+            if (nucl) {
+                const uint64_t hard = t->seq_bytes / 10 + (uint64_t)t->n_seqs * 6 + 64;
+                t->b.max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
+            }
+        }   // else: the blocks sized from the previous call were too small -- once more at the full capacity, same bounds
+        rc = sharded_enqueue(t);
+        if (rc) break;
+    }
+    sharded_release(t->sx, t->set);
+    delete ft;
+    return rc;
+}
+
+void kaamer_sharded_full_ticket_discard(kaamer_sharded_full_ticket *ft)
+{
+    if (!ft) return;
+    kaamer_sharded_ticket *t = &ft->t;
+    sharded_sync_all(t->set);
+    for (ShardState &st : t->set->sh) { if (st.ws) st.ws->clean = false; if (st.mws) st.mws->clean = false; }
+    sharded_release(t->sx, t->set);
+    delete ft;
+}
+
+int kaamer_sharded_search_batch(kaamer_sharded_index *sx, const kaamer_batch_in *in, kaamer_batch_out **out)
+{
+    if (out) *out = nullptr;
+    if (!sx || !in || !out || !in->offsets || (in->n_seqs && !in->seqs)) return kaamer_fail(KAAMER_E_ARG, "sharded_search_batch: bad argument");
+    kaamer_sharded_full_ticket *t = nullptr;
+    const int rc = kaamer_sharded_submit_batch_flat(sx, in->seqs, in->offsets, in->n_seqs, in->seq_type, in->want_positions, &t);
+    if (rc) return rc;
+    return kaamer_sharded_wait_batch(t, out);
+}
+
+int kaamer_sharded_search_batch_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                     int32_t want_positions, kaamer_batch_out **out)
+{
+    if (out) *out = nullptr;
+    kaamer_sharded_full_ticket *t = nullptr;
+    const int rc = kaamer_sharded_submit_batch_flat(sx, seqs, offsets, n_seqs, seq_type, want_positions, &t);
+    if (rc) return rc;
+    return kaamer_sharded_wait_batch(t, out);
 }
 
 // bytes the last call's exchange moved between devices per owner and what its blocks carried (tests, bench):

@@ -40,6 +40,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -1565,6 +1566,12 @@ struct kaamer_workspace {
     uint64_t *d_x_ent_off;
     uint64_t *d_x_tiles;                // tile sums of the exchange's tiled scans
     size_t x_tiles_cap;
+    // blocks with PositionHits bitmaps (arrays = 4): pack offsets; unpack offsets, sizes, bitmaps, OR-merge scratch
+    size_t x_dstb_cap, x_pq_cap, x_pb_cap, x_pbits_cap;
+    uint64_t *d_x_dst_boff, *d_x_src_boff, *d_x_ent_boff, *d_x_mdst;
+    int32_t *d_x_msize;
+    unsigned long long *d_x_mbits, *d_x_gtab;
+    unsigned long long *d_x_pstats;     // {largest bitmap need, a bitmap section overflowed} of the last merge's headers
     // reported-only packing of the top-N results (kaamer_search_batch_top), allocated on first use
     uint32_t rep_k;
     uint32_t *d_rep_flag, *d_rep_aalen, *d_rep_query, *d_rep_pid, *d_rep_km, *d_rep_fp;
@@ -1800,7 +1807,8 @@ void kaamer_workspace_free(kaamer_workspace *ws)
                      ws->d_pool_cursor, ws->d_lists, ws->d_list_counts, ws->d_status_out, ws->d_qinfo, ws->d_slots,
                      ws->d_slot_off, ws->d_group_first, ws->d_n_groups, ws->d_pos_words, ws->d_pos_base, ws->d_pos_off, ws->d_pos_bits, ws->d_g_keys,
                      ws->d_counter_replicas, ws->d_counters, ws->d_bsum, ws->d_chain, ws->d_tr_chain, ws->d_sched, ws->d_n_sched, ws->d_group_start, ws->d_lay_total, ws->d_slot_scale, ws->d_top_cnt, ws->d_top_pid, ws->d_top_km, ws->d_top_fp, ws->d_top_trim, ws->d_top_start, ws->d_top_size, ws->d_rep_flag, ws->d_rep_aalen, ws->d_rep_query, ws->d_rep_pid, ws->d_rep_km, ws->d_rep_fp, ws->d_rep_trim, ws->d_rep_rank, ws->d_rep_eoff, ws->d_rep_aoff, ws->d_rep_off, ws->d_rep_q, ws->d_rep_aa, ws->d_hit_off,
-                     ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp, ws->d_x_dst_off, ws->d_x_src_off, ws->d_x_nq_owned, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, ws->d_x_ent_off, ws->d_x_tiles, ws->d_x_stats };
+                     ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp, ws->d_x_dst_off, ws->d_x_src_off, ws->d_x_nq_owned, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, ws->d_x_ent_off, ws->d_x_tiles, ws->d_x_stats,
+                     ws->d_x_dst_boff, ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_mdst, ws->d_x_msize, ws->d_x_mbits, ws->d_x_gtab, ws->d_x_pstats };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (ws->h_x_stats) {
         (void)hipHostFree(ws->h_x_stats);
@@ -2054,6 +2062,27 @@ static void launch_layout(kaamer_workspace *ws, uint32_t nq_bound, uint32_t *sta
     if (schedule)  // (the pack kernel takes its packs by ticket in layout order: no schedule)
         hipLaunchKernelGGL(schedule_kernel, dim3(1), dim3(1024), 0, s, ws->d_group_first, ws->d_group_start, ws->d_slot_off, ws->d_n_groups,
                            ws->d_nq, ws->d_sched, ws->d_n_sched, cshift);
+}
+
+// PositionHits layout of the final hit lists: words per query, their scan (d_pos_base), pos_off per hit, bitmaps zeroed.
+// sizes: NULL = the search's own QInfo.size; a merge passes the owned queries' SizeInKmer
+static void launch_pos_layout(kaamer_workspace *ws, uint32_t nq_bound, const int32_t *sizes, uint32_t *status, hipStream_t s)
+{
+    uint32_t gb = (nq_bound + 255) / 256;
+    if (gb < 1) gb = 1;
+    if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
+    hipLaunchKernelGGL(pos_words_kernel, dim3(gb), dim3(256), 0, s, ws->d_qinfo, sizes, ws->d_q_cnt, ws->d_nq, ws->d_pos_words);
+    if (nq_bound <= 8 * SCAN_TILE) {
+        hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_pos_base);
+    } else {
+        const uint32_t nsb = (uint32_t)(((uint64_t)nq_bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
+        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_bsum);
+        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
+        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_bsum, ws->d_pos_base);
+    }
+    hipLaunchKernelGGL(pos_layout_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, ws->d_qinfo, sizes, ws->d_q_cnt,
+                       ws->compact ? ws->d_csr_off : ws->d_hit_off,
+                       ws->d_pos_base, ws->d_nq, ws->d_pos_off, ws->d_pos_bits, ws->bits_cap, status);
 }
 
 // optional last step of a search / merge: CSR in query order from the sharded hit arrays
@@ -2349,21 +2378,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     if (ws->want_positions) {
         // PositionHits bitmaps (search.go:442-452): layout from the final hit lists, then one more
         // pass of the group kernel that sets one bit per (hit, position)
-        uint32_t gb = (nq_bound + 255) / 256;
-        if (gb < 1) gb = 1;
-        if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
-        hipLaunchKernelGGL(pos_words_kernel, dim3(gb), dim3(256), 0, s, ws->d_qinfo, ws->d_q_cnt, ws->d_nq, ws->d_pos_words);
-        if (nq_bound <= 8 * SCAN_TILE) {
-            hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_pos_base);
-        } else {
-            const uint32_t nsb = (uint32_t)(((uint64_t)nq_bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
-            hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_bsum);
-            hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
-            hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_bsum, ws->d_pos_base);
-        }
-        hipLaunchKernelGGL(pos_layout_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, ws->d_qinfo, ws->d_q_cnt,
-                           ws->compact ? ws->d_csr_off : ws->d_hit_off,
-                           ws->d_pos_base, ws->d_nq, ws->d_pos_off, ws->d_pos_bits, ws->bits_cap, status);
+        launch_pos_layout(ws, nq_bound, nullptr, status, s);
         // the PositionHits pass runs on the group kernel: lay the tables out in its groups
         launch_layout(ws, nq_bound, status, s, GRP_SHIFT);
         uint64_t grp_blocks = ((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) / GRP_BUDGET + 1;
@@ -2410,9 +2425,11 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
 }
 
 // n_queries / n_entries are host-side bounds when d_n_queries (a device scalar) gives the actual number of queries
+// xpos: an exchange merge of blocks with bitmaps (arrays = 4) -- the merged bitmaps are laid out and ORed together before
+// the finalize step, so that a bitmap bound is reported like every other
 static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, const uint32_t *d_pid, const uint32_t *d_km,
                              const uint32_t *d_fp, uint32_t n_queries, const uint32_t *d_n_queries, uint64_t n_entries, void *stream,
-                             kaamer_device_result *out)
+                             kaamer_device_result *out, XParams *xpos = nullptr)
 {
     if (!ws || !out || (n_queries && !d_ent_off) || (n_entries && (!d_pid || !d_km || !d_fp)))
         return kaamer_fail(KAAMER_E_ARG, "merge_device: bad argument");
@@ -2471,6 +2488,19 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
     if ((uint32_t)g_grid > nq_bound) g_grid = nq_bound > 0 ? (int)nq_bound : 1;
     hipLaunchKernelGGL(merge_global_kernel, dim3(g_grid), dim3(256), 0, s, pg);
     if (ws->compact) launch_compaction(ws, nq_bound, status, s);
+    if (xpos) {
+        launch_pos_layout(ws, nq_bound, xpos->m_size, status, s);
+        xpos->r_nq = ws->d_nq;
+        xpos->r_cnt = ws->d_q_cnt;
+        xpos->r_off = ws->compact ? ws->d_csr_off : ws->d_hit_off;
+        xpos->r_pid = ws->compact ? ws->d_c_pid : ws->d_hit_pid;
+        xpos->r_pos_off = ws->d_pos_off;
+        xpos->r_pos_base = ws->d_pos_base;
+        xpos->r_pos_bits = ws->d_pos_bits;
+        xpos->r_bits_cap = ws->bits_cap;
+        uint32_t gb = nq_bound < (uint32_t)ws->n_cu * 16 ? nq_bound : (uint32_t)ws->n_cu * 16;
+        hipLaunchKernelGGL(x_or_bits_kernel, dim3(gb ? gb : 1), dim3(64), 0, s, *xpos);
+    }
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, ws->d_counter_replicas, ws->d_counters, ws->d_list_counts,
                        ws->d_status_out, ws->d_pool_cursor, (uint32_t *)nullptr, 16u, 16u);   // (a merge looks nothing up: the scale stays)
     HIPCHK(hipGetLastError());
@@ -2481,6 +2511,11 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
     out->d_n_queries = ws->d_nq;
     fill_result_hits(ws, out);
     out->d_counters = ws->d_counters;
+    if (xpos) {
+        out->d_pos_off = ws->d_pos_off;
+        out->d_pos_bits = (const uint64_t *)ws->d_pos_bits;
+        out->d_pos_base = ws->d_pos_base;
+    }
     return KAAMER_OK;
 }
 
@@ -2506,6 +2541,47 @@ int kaamer_exchange_layout_init(uint32_t world, uint32_t rank, uint32_t max_quer
     return KAAMER_OK;
 }
 
+// blocks with bitmaps (arrays = 4): the section starts at the even word after the three entry arrays, and what is left of
+// the block is its capacity: p_cap = (block_words - bits_off) / 2 u64 words
+static uint64_t x_bits_off(const kaamer_exchange_layout *L) { return (X_HDR + 2ull * L->q_cap + 3ull * L->e_cap + 1) & ~1ull; }
+static uint64_t x_p_cap(const kaamer_exchange_layout *L)
+{
+    const uint64_t o = x_bits_off(L);
+    return L->arrays == 4 && L->block_words > o ? (L->block_words - o) / 2 : 0;
+}
+
+int kaamer_exchange_layout_init_positions(uint32_t world, uint32_t rank, uint32_t max_queries, uint64_t max_entries_per_peer,
+                                          uint64_t max_pos_words_per_peer, kaamer_exchange_layout *out)
+{
+    if (!out || max_pos_words_per_peer == 0 || max_pos_words_per_peer > 0xFFFFFFF0ull)
+        return kaamer_fail(KAAMER_E_ARG, "exchange_layout_init_positions: bad argument (0 < pos words < 2^32)");
+    const int rc = kaamer_exchange_layout_init(world, rank, max_queries, max_entries_per_peer, out);
+    if (rc) return rc;
+    out->arrays = 4;
+    out->block_words = (x_bits_off(out) + 2 * max_pos_words_per_peer + 3) & ~3ull;
+    return KAAMER_OK;
+}
+
+int kaamer_exchange_layout_fit_positions(const kaamer_exchange_layout *cap, uint32_t n_queries, uint64_t entries_per_block,
+                                         uint64_t pos_words_per_block, kaamer_exchange_layout *out)
+{
+    if (!cap || !out || cap->world == 0 || cap->arrays != 4)
+        return kaamer_fail(KAAMER_E_ARG, "exchange_layout_fit_positions: bad argument (a capacity layout of kaamer_exchange_layout_init_positions)");
+    kaamer_exchange_layout L = *cap;
+    const uint64_t q = ((uint64_t)n_queries + cap->world - 1) / cap->world + 1;
+    if (q < L.q_cap) L.q_cap = (uint32_t)q;
+    uint64_t e = (entries_per_block + 3) & ~3ull;
+    if (e < 4) e = 4;
+    if (e < L.e_cap) L.e_cap = e;
+    uint64_t pw = pos_words_per_block < 2 ? 2 : pos_words_per_block;
+    const uint64_t pc = x_p_cap(cap);
+    if (pw > pc) pw = pc;
+    L.block_words = (x_bits_off(&L) + 2 * pw + 3) & ~3ull;
+    if (L.block_words > cap->block_words) L = *cap;   // never beyond what the buffers hold
+    *out = L;
+    return KAAMER_OK;
+}
+
 // scratch of the tiled scans: (world + 1) rows of tile sums
 static int x_tiles(kaamer_workspace *ws, const kaamer_exchange_layout *L, XParams *x)
 {
@@ -2527,12 +2603,18 @@ static void x_fill(XParams &x, const kaamer_exchange_layout *L)
 {
     memset(&x, 0, sizeof x);
     x.world = L->world; x.rank = L->rank; x.q_cap = L->q_cap; x.e_cap = L->e_cap; x.block_words = L->block_words;
+    x.ent_base = X_HDR + L->q_cap;
+    if (L->arrays == 4) { x.ent_base += L->q_cap; x.bits_off = x_bits_off(L); x.p_cap = x_p_cap(L); }
 }
 
 int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, uint32_t *d_send, void *stream)
 {
     if (!ws || !L || !d_send || L->world == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_pack: bad argument");
     if (L->arrays == 2 && ws->firstpos) return kaamer_fail(KAAMER_E_ARG, "exchange_pack: the layout has no room for the first positions this workspace computes");
+    const bool pos = L->arrays == 4;
+    if (pos && (!ws->want_positions || !ws->firstpos))
+        return kaamer_fail(KAAMER_E_ARG, "exchange_pack: blocks with bitmaps need a search workspace with want_positions = 1 and first_pos = 1");
+    if (pos && x_p_cap(L) == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_pack: the layout has no bitmap section");
     // (a layout fitted to fewer queries than the batch turns out to have is an overflow like any other: flagged in the
     // block headers by the scan, reported by every owner)
     HIPCHK(hipSetDevice(ws->device));
@@ -2544,6 +2626,14 @@ int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, 
         const int rc = dev_alloc(&ws->d_x_dst_off, (size_t)L->world * L->q_cap);
         if (rc) return rc;
         ws->x_dst_cap = (size_t)L->world * L->q_cap;
+    }
+    if (pos && ws->x_dstb_cap < (size_t)L->world * L->q_cap) {
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        if (ws->d_x_dst_boff) (void)hipFree(ws->d_x_dst_boff);
+        ws->d_x_dst_boff = nullptr; ws->x_dstb_cap = 0;
+        const int rc = dev_alloc(&ws->d_x_dst_boff, (size_t)L->world * L->q_cap);
+        if (rc) return rc;
+        ws->x_dstb_cap = (size_t)L->world * L->q_cap;
     }
     XParams x;
     x_fill(x, L);
@@ -2569,12 +2659,25 @@ int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, 
         hipLaunchKernelGGL(x_scan_top_kernel<0>, dim3(1), dim3(X_BLOCK), 0, s, x);
         hipLaunchKernelGGL(x_scan_apply_kernel<0>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
     }
+    if (pos) {   // the bitmap sections: SizeInKmer per owned query, where each query's bitmaps start, header words [6], [7]
+        x.qinfo = ws->d_qinfo;
+        x.pos_off = ws->d_pos_off;
+        x.pos_bits = ws->d_pos_bits;
+        x.dst_boff = ws->d_x_dst_boff;
+        hipLaunchKernelGGL(x_scan_sums_kernel<2>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
+        hipLaunchKernelGGL(x_scan_top_kernel<2>, dim3(1), dim3(X_BLOCK), 0, s, x);
+        hipLaunchKernelGGL(x_scan_apply_kernel<2>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
+    }
     const bool wide = ws->q_cap <= X_WIDE_QUERIES;   // few queries with long lists: a wave per query
     uint32_t gb = wide ? (ws->q_cap + 3) / 4 : (ws->q_cap + 15) / 16;  // 4 / 16 queries per 256-thread block
     if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
     if (gb < 1) gb = 1;
     if (wide) hipLaunchKernelGGL(x_pack_copy_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
     else hipLaunchKernelGGL(x_pack_copy_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
+    if (pos) {
+        if (wide) hipLaunchKernelGGL(x_pack_bits_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
+        else hipLaunchKernelGGL(x_pack_bits_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
+    }
     HIPCHK(hipGetLastError());
     return KAAMER_OK;
 }
@@ -2584,6 +2687,10 @@ int kaamer_exchange_merge(kaamer_workspace *ws, const kaamer_exchange_layout *L,
 {
     if (!ws || !L || !d_recv || !out || L->world == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_merge: bad argument");
     if (L->arrays == 2 && ws->firstpos) return kaamer_fail(KAAMER_E_ARG, "exchange_merge: the layout has no room for the first positions this workspace wants");
+    const bool pos = L->arrays == 4;
+    if (pos && (!ws->want_positions || !ws->firstpos))
+        return kaamer_fail(KAAMER_E_ARG, "exchange_merge: blocks with bitmaps need a merge workspace with want_positions = 1 and first_pos = 1");
+    if (pos && x_p_cap(L) == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_merge: the layout has no bitmap section");
     if (L->q_cap > ws->q_cap) return kaamer_fail(KAAMER_E_CAPACITY, "exchange_merge: %u owned queries exceed the merge workspace (%u)", L->q_cap, ws->q_cap);
     const uint64_t m_cap = (uint64_t)L->world * L->e_cap;
     if (m_cap > ws->hit_cap) return kaamer_fail(KAAMER_E_CAPACITY, "exchange_merge: %llu entries exceed the merge workspace's max_hits (%llu)",
@@ -2606,10 +2713,32 @@ int kaamer_exchange_merge(kaamer_workspace *ws, const kaamer_exchange_layout *L,
         if (rc) return rc;
         ws->x_src_cap = (size_t)L->world * L->q_cap; ws->x_ent_cap = (size_t)L->q_cap + 1; ws->x_m_cap = (size_t)m_cap;
     }
+    const uint64_t mb_cap = pos ? (uint64_t)L->world * x_p_cap(L) : 0;
+    const size_t pq = (size_t)L->world * L->q_cap + 1;   // per (source, owned query); also bounds the per-query arrays
+    if (pos && (ws->x_pq_cap < pq || ws->x_pb_cap < (size_t)m_cap || ws->x_pbits_cap < (size_t)mb_cap)) {
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        void *bufs[] = { ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_msize, ws->d_x_mdst, ws->d_x_gtab, ws->d_x_mbits };
+        for (void *b : bufs) if (b) (void)hipFree(b);
+        ws->d_x_src_boff = ws->d_x_ent_boff = ws->d_x_mdst = nullptr; ws->d_x_msize = nullptr; ws->d_x_gtab = ws->d_x_mbits = nullptr;
+        ws->x_pq_cap = ws->x_pb_cap = ws->x_pbits_cap = 0;
+        int rc = dev_alloc(&ws->d_x_src_boff, pq);
+        if (!rc) rc = dev_alloc(&ws->d_x_ent_boff, pq);
+        if (!rc) rc = dev_alloc(&ws->d_x_msize, pq);
+        if (!rc) rc = dev_alloc(&ws->d_x_mdst, (size_t)m_cap);
+        if (!rc) rc = dev_alloc(&ws->d_x_gtab, 2 * (size_t)m_cap);
+        if (!rc) rc = dev_alloc(&ws->d_x_mbits, (size_t)mb_cap);
+        if (rc) return rc;
+        ws->x_pq_cap = pq; ws->x_pb_cap = (size_t)m_cap; ws->x_pbits_cap = (size_t)mb_cap;
+    }
+    if (!ws->d_x_pstats) {
+        const int rc = dev_alloc(&ws->d_x_pstats, 2);
+        if (rc) return rc;
+    }
     if (!ws->h_x_stats) {
-        if (hipHostMalloc((void **)&ws->h_x_stats, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        // slots 0, 1: kaamer_exchange_stats (4 words each); then kaamer_exchange_stats_positions (2 words each)
+        if (hipHostMalloc((void **)&ws->h_x_stats, 12 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
             return kaamer_fail(KAAMER_E_NOMEM, "exchange_merge: pinned statistics");
-        memset(ws->h_x_stats, 0, 8 * sizeof(unsigned long long));
+        memset(ws->h_x_stats, 0, 12 * sizeof(unsigned long long));
         for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&ws->ev_x_stats[i], hipEventDisableTiming));
     }
     hipStream_t s = (hipStream_t)stream;
@@ -2648,14 +2777,33 @@ int kaamer_exchange_merge(kaamer_workspace *ws, const kaamer_exchange_layout *L,
     if (gb < 1) gb = 1;
     if (wide) hipLaunchKernelGGL(x_unpack_copy_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
     else hipLaunchKernelGGL(x_unpack_copy_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
+    if (pos) {   // the bitmap sections: sizes checked alike in all blocks, offsets per source and per owned query, copy
+        x.src_boff = ws->d_x_src_boff;
+        x.ent_boff = ws->d_x_ent_boff;
+        x.m_size = ws->d_x_msize;
+        x.m_bits = ws->d_x_mbits;
+        x.mb_cap = mb_cap;
+        x.pstats = ws->d_x_pstats;
+        x.m_dst = ws->d_x_mdst;
+        x.g_tab = ws->d_x_gtab;
+        hipLaunchKernelGGL(x_scan_sums_kernel<3>, dim3(x.n_tiles, L->world + 1), dim3(X_BLOCK), 0, s, x);
+        hipLaunchKernelGGL(x_scan_top_kernel<3>, dim3(1), dim3(X_BLOCK), 0, s, x);
+        hipLaunchKernelGGL(x_scan_apply_kernel<3>, dim3(x.n_tiles, L->world + 1), dim3(X_BLOCK), 0, s, x);
+        if (wide) hipLaunchKernelGGL(x_unpack_bits_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
+        else hipLaunchKernelGGL(x_unpack_bits_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
+    } else {
+        HIPCHK(hipMemsetAsync(ws->d_x_pstats, 0, 2 * sizeof(unsigned long long), s));
+    }
     HIPCHK(hipGetLastError());
     {   // what the W headers said, to the host: read by kaamer_exchange_stats without waiting for the merge itself
         const int slot = (int)(ws->x_merge_seq & 1u);
         HIPCHK(hipMemcpyAsync(ws->h_x_stats + 4 * slot, ws->d_x_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(ws->h_x_stats + 8 + 2 * slot, ws->d_x_pstats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(ws->ev_x_stats[slot], s));
         ws->x_merge_seq++;
     }
-    return merge_device_impl(ws, ws->d_x_ent_off, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, L->q_cap, ws->d_x_nq_owned, m_cap, stream, out);
+    return merge_device_impl(ws, ws->d_x_ent_off, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, L->q_cap, ws->d_x_nq_owned, m_cap, stream, out,
+                             pos ? &x : nullptr);
 }
 
 uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws) { return ws ? ws->q_cap : 0u; }
@@ -2694,6 +2842,18 @@ int kaamer_exchange_stats(kaamer_workspace *ws, uint32_t back, uint64_t out[4])
 
 // grouped ncclSend / ncclRecv of equal blocks, for hosts that own an RCCL communicator and nothing else to drive it
 // (the library does not link RCCL: the symbols are looked up in the process at first use)
+int kaamer_exchange_stats_positions(kaamer_workspace *ws, uint32_t back, uint64_t out[2])
+{
+    if (!ws || !out || back > 1) return kaamer_fail(KAAMER_E_ARG, "exchange_stats_positions: bad argument (back is 0 or 1)");
+    if (ws->x_merge_seq <= back || !ws->h_x_stats) return kaamer_fail(KAAMER_E_ARG, "exchange_stats_positions: no such merge yet");
+    const int slot = (int)((ws->x_merge_seq - 1 - back) & 1u);
+    HIPCHK(hipSetDevice(ws->device));
+    HIPCHK(hipEventSynchronize(ws->ev_x_stats[slot]));
+    out[0] = ws->h_x_stats[8 + 2 * slot + 0];
+    out[1] = ws->h_x_stats[8 + 2 * slot + 1];
+    return KAAMER_OK;
+}
+
 int kaamer_rccl_alltoall(void *nccl_comm, const void *d_send, void *d_recv, uint64_t bytes_per_peer, uint32_t world, void *stream)
 {
     typedef int (*grp_t)(void);

@@ -99,6 +99,15 @@ class RcclComm:
 PHASES = ("search", "pack", "alltoall", "merge", "topn")
 
 
+def pos_words_of(layout):
+    """u64 bitmap words a block of `layout` holds: 0 unless arrays = 4 (include/kaamer_hip.h: the section starts at the even
+    word after the three entry arrays and takes the rest of the block)"""
+    if layout.arrays != 4:
+        return 0
+    off = (8 + 2 * int(layout.q_cap) + 3 * int(layout.e_cap) + 1) & ~1
+    return max(0, (int(layout.block_words) - off) // 2)
+
+
 class ShardedSearcher:
     """Rank-local driver of the sharded index: search my shard, pack, all-to-all, merge my queries, post-steps.
     Every compute step is a C-ABI call enqueued on one stream.  Works for protein and for nucleotide / reads input
@@ -106,7 +115,7 @@ class ShardedSearcher:
 
     def __init__(self, index, rank, world, max_seq_bytes, max_seqs, seq_type=abi.PROTEIN, max_entries_per_peer=1 << 20,
                  group=None, max_hits=0, g_tier_slots=0, first_pos=None, transport="torch", comm=None, adaptive=True,
-                 margin=0.25, direct_at_world1=False, concurrent_batches=0):
+                 margin=0.25, direct_at_world1=False, concurrent_batches=0, want_positions=False, max_pos_words_per_peer=0):
         """first_pos: carry the lowest matching position of every hit through the exchange.  Default: as the reference
         fills PositionHits (search.go:416) -- nucleotide / reads input yes (SetBestStartCodon reads it), protein input no
         (a third less to pack, send, unpack and merge).
@@ -118,20 +127,31 @@ class ShardedSearcher:
         direct_at_world1: with ONE shard the partial lists ARE the results -- skip pack, exchange and merge (the second
         counting pass) and run the post-steps on the search workspace.
         concurrent_batches: how many searchers of this process have batches in flight next to each other (ShardedPipeline);
-        handed to the workspaces (kaamer_workspace_opts.concurrent_batches)."""
+        handed to the workspaces (kaamer_workspace_opts.concurrent_batches).
+        want_positions: PositionHits bitmaps (ExtractPositions) through the exchange: both workspaces compute them (and
+        first positions), the blocks carry them (kaamer_exchange_layout_init_positions, max_pos_words_per_peer u64 words
+        per block; 0: 4 per entry) and the merged result has them in d_pos_off / d_pos_bits / d_pos_base."""
         assert transport in ("rccl", "torch", "host")
         self.index, self.rank, self.world, self.group = index, rank, world, group
         self.transport = transport
         self.nucl = seq_type in (abi.READS, abi.NUCLEOTIDE)
+        self.want_positions = bool(want_positions)
         if first_pos is None:
             first_pos = self.nucl
+        if self.want_positions:
+            first_pos = True   # blocks with bitmaps carry first positions too
         fp = 1 if first_pos else 2
         self.ws_first_pos = bool(first_pos)
         self.ws = api.Workspace(index, max_seq_bytes, max_seqs, seq_type=seq_type, first_pos=fp, max_hits=max_hits,
-                                g_tier_slots=g_tier_slots, concurrent_batches=concurrent_batches)
+                                g_tier_slots=g_tier_slots, concurrent_batches=concurrent_batches, want_positions=self.want_positions)
         self.layout = abi.ExchangeLayout()
-        abi.check(abi.lib().kaamer_exchange_layout_init(world, rank, self.ws.query_capacity, max_entries_per_peer,
-                                                        C.byref(self.layout)))
+        if self.want_positions:
+            abi.check(abi.lib().kaamer_exchange_layout_init_positions(world, rank, self.ws.query_capacity, max_entries_per_peer,
+                                                                      max_pos_words_per_peer or 4 * max_entries_per_peer,
+                                                                      C.byref(self.layout)))
+        else:
+            abi.check(abi.lib().kaamer_exchange_layout_init(world, rank, self.ws.query_capacity, max_entries_per_peer,
+                                                            C.byref(self.layout)))
         L = self.layout            # the capacity layout: what the buffers hold
         self.wire = L              # the layout of the batch being enqueued
         self.adaptive, self.margin = bool(adaptive), float(margin)
@@ -139,7 +159,8 @@ class ShardedSearcher:
         self.n_steps = 0
         self.direct = bool(direct_at_world1) and world == 1
         self.mws = api.Workspace(index, 64, L.q_cap, max_queries=L.q_cap, first_pos=fp, max_hits=world * L.e_cap,
-                                 g_tier_slots=g_tier_slots)
+                                 g_tier_slots=g_tier_slots, want_positions=self.want_positions,
+                                 max_pos_words=world * pos_words_of(L))
         n = world * int(L.block_words)
         self.block_bytes = 4 * int(L.block_words)
         self.send = torch.empty(n, dtype=torch.int32, device="cuda")
@@ -160,10 +181,16 @@ class ShardedSearcher:
         if not self.adaptive or self.n_steps < 2:
             return self.layout
         _, nq, need, ovf = self.mws.exchange_stats(back=1)
-        if self._full_next or ovf:
+        pneed, povf = self.mws.exchange_stats_positions(back=1) if self.want_positions else (0, 0)
+        if self._full_next or ovf or povf:
             self._full_next = False
             return self.layout
         fit = abi.ExchangeLayout()
+        if self.want_positions:
+            abi.check(abi.lib().kaamer_exchange_layout_fit_positions(C.byref(self.layout), int(nq * (1.0 + self.margin)) + 64,
+                                                                     int(need * (1.0 + self.margin)) + 1024,
+                                                                     int(pneed * (1.0 + self.margin)) + 1024, C.byref(fit)))
+            return fit
         abi.check(abi.lib().kaamer_exchange_layout_fit(C.byref(self.layout), int(nq * (1.0 + self.margin)) + 64,
                                                        int(need * (1.0 + self.margin)) + 1024, int(self.ws_first_pos), C.byref(fit)))
         return fit
