@@ -505,16 +505,14 @@ __device__ unsigned long long g_phase_clock[2048][16];  // per workgroup: summed
 // (id, position) sets one bit of that hit's bitmap in HBM.  MODE 2: merge of partial hit
 // lists (sharded index, SURVEY 8e): a "position" is one partial entry (id, count, first
 // position) received from a shard; counts add, first positions take the minimum.
-// UNITW: group windows per unit.  2: a unit's tables may exceed the arena (sized for ONE window's worst overhang, so that three
-// workgroups fit a CU) and is then counted in two parts.  4: an arena that always holds a unit -- 98 KB of LDS, one workgroup
-// per CU: the launch for batches that overlap with others (one counting workgroup per CU anyway), half the barrier cycles again.
-template <bool FIRSTPOS, int MODE = 0, int UNITW = 2>
+// A unit of two group windows whose tables exceed the arena (sized for ONE window's worst overhang, so that three workgroups
+// fit a CU) is counted in two parts.
+template <bool FIRSTPOS, int MODE = 0>
 __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams p)
 {
     constexpr int WAVES = GRP_WAVES;
-    constexpr uint32_t UQMAX = (uint32_t)UNITW * GRP_QMAX;                                        // queries of a unit
-    constexpr uint32_t FIT = UNITW == 2 ? GRP_FIT : (uint32_t)UNITW * GRP_BUDGET - 64u + GRP_MAX_TABLE;   // slots of the arena
-    static_assert(UNITW == 2 || UNITW == 4, "units of two or four windows");
+    constexpr uint32_t UQMAX = 2u * GRP_QMAX;   // queries of a unit
+    constexpr uint32_t FIT = GRP_FIT;           // slots of the arena
     static_assert(UQMAX <= 256 && FIT <= 65535u, "query indices are bytes, table offsets 16-bit");
     constexpr int NWIN = GRP_NWIN;
     constexpr int XIT = 2;

@@ -1,9 +1,9 @@
-// count_pack.hip.inc — the counting kernel of a search batch (included by search.hip after count_group.hip.inc).
+// count_pack.hip.inc — the counting kernel of an ORF batch (included by search.hip after count_group.hip.inc).
 //
 // Replaces, for a whole batch, the per-id loop of KmerSearch (search.go:431-436): Counter[id]++ (and the lowest
 // matching position, what SetBestStartCodon reads from PositionHits) for every id of every found k-mer.
 //
-// Why not the group kernel (count_group.hip.inc, still used for the PositionHits pass and the merge of a sharded
+// Why not the group kernel (count_group.hip.inc: protein batches, the PositionHits pass and the merge of a sharded
 // index): with eight waves sharing a group of tables every group costs four workgroup barriers, a ticket on one
 // global word, and a software pipeline that never fills (2-3 windows per wave); 78 % of its wave cycles were waits
 // (profiles/r02_sq_protein.txt) and the skeleton alone -- no counting at all -- took 53 of its 97 us.
@@ -20,20 +20,19 @@
 // A table larger than the arena allows (PK_ARENA - budget + 64 slots) is counted in that many slots all the same: a
 // table is sized for the worst case (1.5 slots per position) and a query has ~0.5 distinct hits per position, so it
 // nearly always fits; if it does not, the query goes to the G tier like any query whose table fills up.
-// PK_ARENA (template parameter): table slots per wave.  1600 (12.8 KB of keys + counts, 11 waves per CU) holds protein
-// queries of up to ~770 k-mers next to a window of 512 slots; 640 (5 KB, 24 waves per CU) is for ORF batches, whose
-// tables are 64-128 slots.
+// PK_ARENA (template parameter): table slots per wave.  640 (5 KB of keys + counts, 24 waves per CU) for ORFs of reads,
+// whose tables are 64-128 slots; 1024 for longer ORFs (search.hip: PK_ARENA_ORF_LONG).  Counts and lowest positions
+// are always kept: the ORFs of nucleotide input carry PositionHits in the reference (search.go:416).
 #define PK_QMAX 32u      /* queries of a pack: budget / 64 at most */
 #define PK_WHINT 64u     /* windows with a start hint (the rest search the prefix) */
 #define PK_TICKETS 64u   /* ticket counters (ranges of packs) */
 
-template <bool FIRSTPOS, uint32_t PK_ARENA>
+template <uint32_t PK_ARENA>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void count_pack_kernel(CountParams p)
 {
     constexpr int XIT = 2;
-    constexpr bool PACKED = FIRSTPOS;  // count (low 16 bits) and lowest position (high 16 bits) share one word
     __shared__ uint32_t a_keys[PK_ARENA];
-    __shared__ uint32_t a_cnt[PK_ARENA];
+    __shared__ uint32_t a_cnt[PK_ARENA];  // count (low 16 bits) and lowest position (high 16 bits) share one word
     __shared__ uint32_t g_q[PK_QMAX], g_size[PK_QMAX], g_tab[PK_QMAX], g_cap[PK_QMAX], g_ovf[PK_QMAX], g_eoff[PK_QMAX];
     __shared__ uint32_t g_pref[PK_QMAX + 1];
     __shared__ uint64_t g_aa[PK_QMAX];
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
                         g_eoff[idx] = (uint32_t)(e - e_first);
                         g_tab[idx] = tab_run + cinc - capu;
                         g_cap[idx] = capu;
-                        g_ovf[idx] = (PACKED && qi.size >= 65535) ? 1u : 0u;  // 16-bit counts and positions
+                        g_ovf[idx] = qi.size >= 65535 ? 1u : 0u;  // 16-bit counts and positions
                     }
                 }
                 tab_run += (uint32_t)__builtin_amdgcn_readlane((int)cinc, 63);
@@ -171,7 +170,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
         // ---- 2. clear the tables in use
         for (uint32_t i = lane; i < n_slots; i += 64) {
             a_keys[i] = KH_EMPTY_PID;
-            a_cnt[i] = PACKED ? 0xFFFF0000u : 0u;
+            a_cnt[i] = 0xFFFF0000u;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -234,17 +233,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
                 const uint32_t kk = old == KH_EMPTY_PID ? pid : old;
 #endif
                 if (kk == pid) {
-                    if (PACKED) {
-                        // count += n and position = min(position, pos) in one word: the adds of a wave are serialised per
-                        // slot by the hardware, other waves never touch this arena
-                        uint32_t old = atomicAdd(&a_cnt[base + hh], n) + n;
-                        while (pos < (old >> 16)) {
-                            const uint32_t seen = atomicCAS(&a_cnt[base + hh], old, (old & 0xFFFFu) | (pos << 16));
-                            if (seen == old) break;
-                            old = seen;
-                        }
-                    } else {
-                        atomicAdd(&a_cnt[base + hh], n);
+                    // count += n and position = min(position, pos) in one word: the adds of a wave are serialised per
+                    // slot by the hardware, other waves never touch this arena
+                    uint32_t old = atomicAdd(&a_cnt[base + hh], n) + n;
+                    while (pos < (old >> 16)) {
+                        const uint32_t seen = atomicCAS(&a_cnt[base + hh], old, (old & 0xFFFFu) | (pos << 16));
+                        if (seen == old) break;
+                        old = seen;
                     }
                     return;
                 }
@@ -398,8 +393,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
                         const uint32_t idx = running + (uint32_t)__popcll(bm & below);
                         p.hit_pid[base + idx] = k;
                         const uint32_t cw = a_cnt[base_slot + i0 + lane];
-                        p.hit_km[base + idx] = PACKED ? (cw & 0xFFFFu) : cw;
-                        if (FIRSTPOS) p.hit_fp[base + idx] = cw >> 16;
+                        p.hit_km[base + idx] = cw & 0xFFFFu;
+                        p.hit_fp[base + idx] = cw >> 16;
                     }
                     running += (uint32_t)__popcll(bm);
                 }

@@ -743,8 +743,6 @@ __device__ __forceinline__ void mark_invalid_range(unsigned long long *invalid, 
 }
 
 #include "count_group.hip.inc"
-#include "count_async.hip.inc"
-#define PK_ARENA_PROT 1600u
 #ifndef PK_ARENA_ORF
 #define PK_ARENA_ORF 640u
 #endif
@@ -1499,10 +1497,9 @@ struct kaamer_workspace {
     uint64_t *d_csr_off;                // compact form: CSR offsets
     uint32_t *d_c_pid, *d_c_km, *d_c_fp;
     int g_grid, p_grid, n_cu, pack_grid, pack_grid_long;
-    bool use_group;
-    bool count_async;                   // protein batches are counted by count_async_kernel instead of count_group_kernel<., 0> (KAAMER_COUNT_ASYNC=1)
-    int unit_windows;                   // group windows per unit of count_group_kernel<., 0>: 2, or 4 with one workgroup per CU
-    uint32_t pack_shift;                // log2 of the pack window (slots) of a search: 8 for protein, 10 for ORF batches
+    uint32_t pack_shift;                // log2 of the group / pack window (slots) of a search: 12 for protein, 9 for ORF batches
+    int wide_reads;                     // lane-per-read kernel: 1 the wide one, 0 the narrow one, -1 picked from the mean read length
+    bool pack_long;                     // ORF batches always take the pack kernel's larger arena
     // device buffers
     kaamer_query_meta *d_q;
     uint32_t *d_nq;
@@ -1524,7 +1521,6 @@ struct kaamer_workspace {
     hipEvent_t ev_probe, ev_count;
     bool split_pending;                 // the last search's counting stage is on count_stream: consumers wait for ev_count
     int grp_grid;
-    bool sched_identity;                // groups handed out in index order (no longest-first schedule is built)
     // nucleotide / reads input: 6-frame translation products
     bool nucleotide;
     uint64_t aa_cap, sa_cap;
@@ -1612,18 +1608,8 @@ template <class T> static int dev_alloc(T **p, size_t n)
     return KAAMER_OK;
 }
 
-static void launch_group(const CountParams &p, int grid, bool firstpos, hipStream_t s, bool async, int unit_windows)
+static void launch_group(const CountParams &p, int grid, bool firstpos, hipStream_t s)
 {
-    if (!async && unit_windows == 4) {   // units of four windows: 98 KB of LDS, one workgroup per CU (overlapping batches)
-        if (firstpos) hipLaunchKernelGGL((count_group_kernel<true, 0, 4>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
-        else hipLaunchKernelGGL((count_group_kernel<false, 0, 4>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
-        return;
-    }
-    if (async) {   // the barrier-free form (count_async.hip.inc); KAAMER_COUNT_ASYNC=0: the round-3 kernel
-        if (firstpos) hipLaunchKernelGGL((count_async_kernel<true>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
-        else hipLaunchKernelGGL((count_async_kernel<false>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
-        return;
-    }
     if (firstpos) hipLaunchKernelGGL((count_group_kernel<true, 0>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
     else hipLaunchKernelGGL((count_group_kernel<false, 0>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
 }
@@ -1636,6 +1622,43 @@ static void launch_group_merge(const CountParams &p, int grid, bool firstpos, hi
     // without first positions the merge tables need no third array: three workgroups per CU instead of two
     if (firstpos) hipLaunchKernelGGL((count_group_kernel<true, 2>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
     else hipLaunchKernelGGL((count_group_kernel<false, 2>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
+}
+
+// The search's environment knobs (tools/README.md), read where a workspace or an index is created and nowhere on the
+// per-batch path (a host that calls in through cgo may setenv on another thread).  A knob that is not set leaves the
+// shipped value.
+struct SearchKnobs {
+    int grp_per_cu, p_per_cu, pack_per_cu;  // workgroups per CU of the counting / probe / pack kernels (0: as many as fit)
+    int wide_reads;                         // lane-per-read kernel: 1 the wide one, 0 the narrow one, -1 picked per batch
+    uint32_t slot_scale_cap;                // ceiling of the table scale, sixteenths
+    uint32_t slot_scale_margin;             // sixteenths: tables of (hits per k-mer) x this
+    bool pack_long;                         // ORF batches always take the pack kernel's larger arena
+    bool ws_trace;                          // a workspace prints its sizes when it is created
+    int host_slots;                         // calls in flight through the host-buffer boundary
+};
+
+static SearchKnobs read_knobs()
+{
+    auto num = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; };
+    SearchKnobs k;
+    k.grp_per_cu = num("KAAMER_GRP_PER_CU");
+    k.p_per_cu = num("KAAMER_P_PER_CU");
+    k.pack_per_cu = num("KAAMER_PACK_PER_CU");
+    const char *e = getenv("KAAMER_WIDE_READS");
+    k.wide_reads = e ? atoi(e) != 0 : -1;
+    // (never above 8: at 3e9 residues on one device, 6.6 hits per k-mer, tables of 12 x 1.5 x SizeInKmer leave the pack
+    // kernel's arena and the batch takes 92 ms instead of 44; profiles/r03_dense_database.md)
+    double cap = 128.0;
+    if ((e = getenv("KAAMER_SLOT_SCALE_MAX"))) cap = atof(e) * 16.0;
+    k.slot_scale_cap = cap < 16.0 ? 16u : cap > 128.0 ? 128u : (uint32_t)cap;
+    k.slot_scale_margin = 30u;   // x 1.9: the hits of a query spread around the batch's mean (measured on DB-UR-lite: 1.2 -> 22.8 ms per
+                                 // batch, 1.5 -> 13.9, 1.9 -> 11.9; profiles/r03_dense_database.md)
+    if ((e = getenv("KAAMER_SLOT_MARGIN"))) k.slot_scale_margin = (uint32_t)(atof(e) * 16.0);
+    k.pack_long = getenv("KAAMER_PACK_LONG") != nullptr;
+    k.ws_trace = getenv("KAAMER_WS_TRACE") != nullptr;
+    const int hs = num("KAAMER_HOST_SLOTS");
+    k.host_slots = hs >= 1 && hs <= KAAMER_MAX_HOST_SLOTS ? hs : 4;
+    return k;
 }
 
 extern "C" {
@@ -1674,8 +1697,7 @@ int kaamer_index_open_image(const kaamer_image *img, int device, kaamer_index **
     kaamer_index *ix = new (std::nothrow) kaamer_index();
     if (!ix) return kaamer_fail(KAAMER_E_NOMEM, "index alloc");
     ix->device = device;
-    ix->n_top = 4;  // calls in flight through the host-buffer boundary
-    if (const char *e = getenv("KAAMER_HOST_SLOTS")) { const int v = atoi(e); if (v >= 1 && v <= KAAMER_MAX_HOST_SLOTS) ix->n_top = v; }
+    ix->n_top = read_knobs().host_slots;
     ix->hdr = img->hdr;
     ix->d_buckets = nullptr;
     ix->d_arena = nullptr;
@@ -1743,8 +1765,7 @@ int kaamer_index_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
     kaamer_index *ix = new (std::nothrow) kaamer_index();
     if (!ix) { (void)hipFree(di.d_buckets); (void)hipFree(di.d_arena); return kaamer_fail(KAAMER_E_NOMEM, "index alloc"); }
     ix->device = device;
-    ix->n_top = 4;
-    if (const char *e = getenv("KAAMER_HOST_SLOTS")) { const int v = atoi(e); if (v >= 1 && v <= KAAMER_MAX_HOST_SLOTS) ix->n_top = v; }
+    ix->n_top = read_knobs().host_slots;
     ix->hdr = di.hdr;
     ix->d_buckets = di.d_buckets;
     ix->d_arena = di.d_arena;   // its first 16 bytes are zero (builder_device.hip), as kaamer_index_open_image leaves them
@@ -1860,20 +1881,10 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     }
     // the reference fills PositionHits only for nucleotide/reads input or with -pos (search.go:416)
     ws->firstpos = opts->first_pos == 1 || (opts->first_pos == 0 && (opts->seq_type == KAAMER_NUCLEOTIDE || opts->seq_type == KAAMER_READS));
+    const SearchKnobs knobs = read_knobs();
     int grp_per_cu = 0, p_per_cu = 0;
-    // Which counting kernel takes protein batches: count_group_kernel over units of two group windows (count_group.hip.inc).
-    // The barrier-free count_async_kernel (count_async.hip.inc; KAAMER_COUNT_ASYNC=1) beat the single-window group kernel
-    // when batches overlap (ONE counting workgroup per CU, below: 0.1290-0.1308 against 0.1343-0.1344 ms per batch, same box)
-    // and lost alone on the device (115 against 95 us); units then took the group kernel to 0.1268-0.1273 ms with three
-    // batches in flight (the barrier-free kernel in the same call: 0.1294-0.1320) and to 89 us alone
-    // (profiles/r04_experiments.md).  Both kernels stay under the parity tests (test_both_counting_kernels).
-    ws->count_async = false;
-    if (const char *e = getenv("KAAMER_COUNT_ASYNC")) ws->count_async = atoi(e) != 0;
-    hipError_t oe = ws->count_async
-        ? (ws->firstpos ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_async_kernel<true>, 64 * GRP_WAVES, 0)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_async_kernel<false>, 64 * GRP_WAVES, 0))
-        : (ws->firstpos ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_group_kernel<true, 0>, 64 * GRP_WAVES, 0)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_group_kernel<false, 0>, 64 * GRP_WAVES, 0));
+    hipError_t oe = ws->firstpos ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_group_kernel<true, 0>, 64 * GRP_WAVES, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_group_kernel<false, 0>, 64 * GRP_WAVES, 0);
     if (oe == hipSuccess)
         oe = ws->nucleotide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&p_per_cu, probe_kernel<true>, 64 * P_WAVES, 0)
                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&p_per_cu, probe_kernel<false>, 64 * P_WAVES, 0);
@@ -1888,12 +1899,8 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     // registers and wave slots to the neighbours' probe kernels; three fill the register file and lock them out
     // (tools/r4_sweep.sh: 0.134-0.143 ms per batch against 0.148-0.155 with three batches in flight, 0.26 against 0.20 alone)
     if (opts->concurrent_batches > 1 && !ws->nucleotide) grp_per_cu = 1;
-    // (measured with one workgroup per CU and three batches in flight, same box, A/B/A/B: 0.1381-0.1406 ms per batch with the
-    // longest-first schedule, 0.1430-0.1441 with the groups in index order: the schedule stays)
-    ws->sched_identity = false;
-    if (const char *e = getenv("KAAMER_SCHED_IDENTITY")) ws->sched_identity = atoi(e) != 0;
-    if (const char *e = getenv("KAAMER_GRP_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 3) grp_per_cu = v < grp_per_cu || opts->concurrent_batches > 1 ? v : grp_per_cu; }
-    if (const char *e = getenv("KAAMER_P_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < p_per_cu) p_per_cu = v; }
+    if (const int v = knobs.grp_per_cu; v >= 1 && v <= 3) grp_per_cu = v < grp_per_cu || opts->concurrent_batches > 1 ? v : grp_per_cu;
+    if (const int v = knobs.p_per_cu; v >= 1 && v < p_per_cu) p_per_cu = v;
     ws->n_cu = prop.multiProcessorCount;
     ws->grp_grid = ws->n_cu * grp_per_cu;
     // the G tier is rare on a database like DB-SP, but with a skewed database 15 % of the queries overflow their LDS
@@ -1906,36 +1913,20 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     ws->p_grid = ws->n_cu * p_per_cu;
     {
         int pk_per_cu = 0;
-        hipError_t ke = ws->nucleotide ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&pk_per_cu, count_pack_kernel<true, PK_ARENA_ORF>, 64, 0)
-                        : ws->firstpos ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&pk_per_cu, count_pack_kernel<true, PK_ARENA_PROT>, 64, 0)
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&pk_per_cu, count_pack_kernel<false, PK_ARENA_PROT>, 64, 0);
-        if (ke != hipSuccess || pk_per_cu < 1) pk_per_cu = 1;
-        if (const char *e = getenv("KAAMER_PACK_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < pk_per_cu) pk_per_cu = v; }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pk_per_cu, count_pack_kernel<PK_ARENA_ORF>, 64, 0) != hipSuccess || pk_per_cu < 1) pk_per_cu = 1;
+        if (const int v = knobs.pack_per_cu; v >= 1 && v < pk_per_cu) pk_per_cu = v;
         ws->pack_grid = ws->n_cu * pk_per_cu;
         int pl = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pl, count_pack_kernel<true, PK_ARENA_ORF_LONG>, 64, 0) != hipSuccess || pl < 1) pl = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pl, count_pack_kernel<PK_ARENA_ORF_LONG>, 64, 0) != hipSuccess || pl < 1) pl = 1;
         ws->pack_grid_long = ws->n_cu * pl;
     }
-    // the pack window: a protein query's table is ~530 slots, so a window of 512 slots holds one or two table starts
-    // (tables up to PK_ARENA - 448 slots at full size); an ORF batch has tables of 64-128 slots: 8-16 ORFs to a pack
-    ws->pack_shift = 9u;
-    if (const char *e = getenv("KAAMER_PACK_SHIFT")) { const int v = atoi(e); if (v >= 8 && v <= 10) ws->pack_shift = (uint32_t)v; }
-    // Which counting kernel: ORF batches (tables of 64-128 slots, 24 one-wave workgroups per CU) take the pack kernel;
-    // protein batches the group kernel -- a wave alone on a 700-position query is a 50 us critical path, and with the
-    // 11 waves per CU a protein arena allows the pack kernel took 117-156 us against the group kernel's 100
-    // (profiles/r03_count_kernels.md).  KAAMER_COUNT_GROUP / KAAMER_COUNT_PACK force one or the other (A/B runs).
-    ws->use_group = !ws->nucleotide;
-    if (getenv("KAAMER_COUNT_GROUP")) ws->use_group = true;
-    if (getenv("KAAMER_COUNT_PACK")) ws->use_group = false;
-    // protein batches: count_group_kernel takes UNITS of two group windows (count_group.hip.inc); the barrier-free kernel
-    // keeps single windows (two of them alive in its arena)
-    // (units of four windows -- an arena of 98 KB, one workgroup per CU: KAAMER_UNIT_WINDOWS=4 -- were measured for the
-    // overlapping launch, where there is one counting workgroup per CU anyway: 0.157-0.159 against 0.1255-0.1287 ms per batch;
-    // the probe kernels of the neighbouring batches miss the LDS and the registers.  Two it is.)
-    ws->unit_windows = 2;
-    if (const char *e = getenv("KAAMER_UNIT_WINDOWS")) { const int v = atoi(e); if (v == 2 || (v == 4 && grp_per_cu == 1)) ws->unit_windows = v; }
-    if (ws->use_group) ws->pack_shift = ws->count_async ? GRP_SHIFT : ws->unit_windows == 4 ? GRP_SHIFT + 2u : GRP_SHIFT + 1u;
-    if (const char *e = getenv("KAAMER_GROUP_SHIFT")) { const int v = atoi(e); if (ws->use_group && !ws->count_async && ws->unit_windows == 2 && (v == (int)GRP_SHIFT || v == (int)GRP_SHIFT + 1)) ws->pack_shift = (uint32_t)v; }
+    // Which counting kernel: ORF batches (tables of 64-128 slots, 24 one-wave workgroups per CU) take the pack kernel, 8-16
+    // ORFs to a pack window of 512 slots; protein batches the group kernel over UNITS of two group windows
+    // (count_group.hip.inc) -- a wave alone on a 700-position query is a 50 us critical path, and with the 11 waves per CU
+    // a protein arena allows the pack kernel took 117-156 us against the group kernel's 100 (profiles/r03_count_kernels.md)
+    ws->pack_shift = ws->nucleotide ? 9u : GRP_SHIFT + 1u;
+    ws->wide_reads = knobs.wide_reads;
+    ws->pack_long = knobs.pack_long;
     // a table has at most max(64, 3 x SizeInKmer) slots
     {
         // (a merge counts partial entries instead of positions: as many as max_hits)
@@ -1999,16 +1990,10 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
         // tables scale inside that room is settled per batch on the device, from the batch's own positions
         // (fit_table_scale): a workspace sized for 2 amino acids per nucleotide holds ORFs of 0.5 per nucleotide at 4 x
         ws->table_room = (unsigned long long)(0.7 * (double)ws->sparse_cap);
-        double cap = 128.0;
-        // (never above 8: at 3e9 residues on one device, 6.6 hits per k-mer, tables of 12 x 1.5 x SizeInKmer leave the pack
-        // kernel's arena and the batch takes 92 ms instead of 44; profiles/r03_dense_database.md)
-        if (getenv("KAAMER_SLOT_SCALE_MAX")) cap = atof(getenv("KAAMER_SLOT_SCALE_MAX")) * 16.0;
-        ws->slot_scale_cap = cap < 16.0 ? 16u : cap > 128.0 ? 128u : (uint32_t)cap;
-        ws->slot_scale_margin = 30u;   // x 1.9: the hits of a query spread around the batch's mean (measured on DB-UR-lite: 1.2 -> 22.8 ms per
-                                       // batch, 1.5 -> 13.9, 1.9 -> 11.9; profiles/r03_dense_database.md)
-        ws->dense_tables = getenv("KAAMER_PACK_LONG") != nullptr;
-        if (getenv("KAAMER_SLOT_MARGIN")) ws->slot_scale_margin = (uint32_t)(atof(getenv("KAAMER_SLOT_MARGIN")) * 16.0);
-        if (getenv("KAAMER_WS_TRACE"))
+        ws->slot_scale_cap = knobs.slot_scale_cap;
+        ws->slot_scale_margin = knobs.slot_scale_margin;
+        ws->dense_tables = ws->pack_long;
+        if (knobs.ws_trace)
             fprintf(stderr, "[kaamer workspace] pos_cap %llu q_cap %u hit_cap %llu sparse_cap %llu table_room %llu slot_scale_cap %u/16\n", (unsigned long long)ws->pos_cap,
                     ws->q_cap, (unsigned long long)ws->hit_cap, (unsigned long long)ws->sparse_cap, ws->table_room, ws->slot_scale_cap);
     }
@@ -2197,8 +2182,9 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
         pl.status = status; pl.sched = ws->d_sched; pl.d_n_sched = ws->d_n_sched;
         pl.tiles_done = ws->d_list_counts + SLOT_TILES_DONE;
         pl.slots = ws->d_slots; pl.bshift = ws->pack_shift; pl.cshift = ws->pack_shift > GRP_SHIFT ? 10u : ws->pack_shift >= GRP_SHIFT ? 9u : 7u;
-        // (KAAMER_SCHED_IDENTITY=1: no longest-first schedule, groups in index order -- an A/B knob)
-        pl.no_sched = (ws->use_group && !ws->sched_identity) ? 0u : 1u;
+        // the group kernel takes the groups longest first (measured with one workgroup per CU and three batches in flight:
+        // 0.1381-0.1406 ms per batch, 0.1430-0.1441 with the groups in index order)
+        pl.no_sched = 0u;
         pl.d_total = ws->d_lay_total;
         pl.slot_scale = ws->d_slot_scale;
         pl.room_slots = ws->table_room;
@@ -2216,8 +2202,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
         tp.q_cap = ws->q_cap; tp.aa_cap = ws->aa_cap; tp.sa_cap = ws->sa_cap; tp.status = status;
         // which lane-per-read kernel: the wide one (reads up to 384 nt, 2 waves per SIMD) when the batch's mean length says that
         // reads beyond 192 nt are common; a batch of 100-150-nt reads is 4 % slower through it (translate.hip.inc)
-        bool wide_reads = seq_bytes > 160ull * (n_seqs ? n_seqs : 1u);
-        if (const char *e = getenv("KAAMER_WIDE_READS")) wide_reads = atoi(e) != 0;
+        const bool wide_reads = ws->wide_reads >= 0 ? ws->wide_reads != 0 : seq_bytes > 160ull * (n_seqs ? n_seqs : 1u);
         tp.ts_max = wide_reads ? TS_MAX_WIDE : TS_MAX;
         int tgrid = ws->n_cu * 8;  // 256-thread blocks, one (sequence, frame, piece) item per wave at a time
         tp.d_n6 = ws->d_n6;
@@ -2274,7 +2259,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     }
 
     // ---- query groups: table layout, first query of each group, schedule (protein: done with the prep)
-    if (nucl) launch_layout(ws, nq_bound, status, s, ws->pack_shift, ws->use_group);
+    if (nucl) launch_layout(ws, nq_bound, status, s, ws->pack_shift, false);
 
     // ---- kernel P: flat probe
     ProbeParams pp;
@@ -2336,30 +2321,25 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     pc.last_group_pass = ws->want_positions ? 0u : 1u;
     pc.pack_shift = ws->pack_shift;
     pc.pack_tickets = ws->d_list_counts + SLOT_PACK_TICKETS;
-    {
+    if (!nucl) {
+        uint64_t gg = ((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) / GRP_BUDGET + 1;
+        if (gg > (uint64_t)ws->grp_grid) gg = ws->grp_grid;
+        launch_group(pc, (int)gg, ws->firstpos, s);
+    } else {
         // one wave per workgroup, packs dealt out statically: never more waves than packs
         uint64_t gb = (((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) >> ws->pack_shift) + 1;
         if (gb > (uint64_t)ws->pack_grid) gb = ws->pack_grid;
-        if (ws->use_group) {
-            uint64_t gg = ((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) / GRP_BUDGET + 1;
-            if (gg > (uint64_t)ws->grp_grid) gg = ws->grp_grid;
-            launch_group(pc, (int)gg, ws->firstpos, s, ws->count_async, ws->unit_windows);
-        } else if (ws->nucleotide) {
-            // reads of ~150 nt: ORFs of <= 50 residues, tables of 64-128 slots -> the small arena (20 waves per CU);
-            // longer sequences (mixed read lengths, contigs): the arena that holds tables of up to 576 slots, or 66 000
-            // ORFs of a 1 M mixed-read batch went to the G tier (measured: 8.19 -> 6.73 ms for the counting stage of
-            // that batch, while the 150-nt batch loses 0.4 ms with the larger arena)
-            const bool long_orfs = seq_bytes > 200ull * (n_seqs ? n_seqs : 1u) || ws->dense_tables;
-            uint64_t g2 = gb;
-            if (long_orfs) {
-                if (g2 > (uint64_t)ws->pack_grid_long) g2 = ws->pack_grid_long;
-                hipLaunchKernelGGL((count_pack_kernel<true, PK_ARENA_ORF_LONG>), dim3((unsigned)g2), dim3(64), 0, s, pc);
-            } else {
-                hipLaunchKernelGGL((count_pack_kernel<true, PK_ARENA_ORF>), dim3((unsigned)g2), dim3(64), 0, s, pc);
-            }
+        // reads of ~150 nt: ORFs of <= 50 residues, tables of 64-128 slots -> the small arena (20 waves per CU);
+        // longer sequences (mixed read lengths, contigs): the arena that holds tables of up to 576 slots, or 66 000
+        // ORFs of a 1 M mixed-read batch went to the G tier (measured: 8.19 -> 6.73 ms for the counting stage of
+        // that batch, while the 150-nt batch loses 0.4 ms with the larger arena)
+        const bool long_orfs = seq_bytes > 200ull * (n_seqs ? n_seqs : 1u) || ws->dense_tables;
+        if (long_orfs) {
+            if (gb > (uint64_t)ws->pack_grid_long) gb = ws->pack_grid_long;
+            hipLaunchKernelGGL((count_pack_kernel<PK_ARENA_ORF_LONG>), dim3((unsigned)gb), dim3(64), 0, s, pc);
+        } else {
+            hipLaunchKernelGGL((count_pack_kernel<PK_ARENA_ORF>), dim3((unsigned)gb), dim3(64), 0, s, pc);
         }
-        else if (ws->firstpos) hipLaunchKernelGGL((count_pack_kernel<true, PK_ARENA_PROT>), dim3((unsigned)gb), dim3(64), 0, s, pc);
-        else hipLaunchKernelGGL((count_pack_kernel<false, PK_ARENA_PROT>), dim3((unsigned)gb), dim3(64), 0, s, pc);
     }
     CountParams pg = p;
     pg.list = list_ptr(LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
@@ -2960,7 +2940,7 @@ int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void 
 // counters: from a scale of 2 on, ORF batches take the pack kernel with the larger arena (tables of 200-500 slots).
 static void ws_note_density(kaamer_workspace *ws, const kaamer_counters &c)
 {
-    if (!c.n_lookup || getenv("KAAMER_PACK_LONG")) return;
+    if (!c.n_lookup || ws->pack_long) return;
     unsigned long long t = (c.n_hits * ws->slot_scale_margin + c.n_lookup - 1ull) / c.n_lookup;
     if (t > ws->slot_scale_cap) t = ws->slot_scale_cap;
     ws->dense_tables = t >= 2u * SLOT_SCALE_ONE;

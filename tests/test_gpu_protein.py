@@ -344,13 +344,11 @@ def test_counting_tables_follow_the_previous_batch(klib, oracle, gpu_device):
 
 
 @pytest.mark.parametrize("first_pos", [1, -1])
-def test_both_counting_kernels(small, klib, oracle, gpu_device, first_pos, monkeypatch):
-    """Protein batches are counted by count_group_kernel (units of two group windows per barrier cycle; four with a larger
-    arena behind an experiment knob) or, with
-    KAAMER_COUNT_ASYNC=1, by the barrier-free kernel (count_async.hip.inc: window, stripe and build jobs from LDS counters,
-    two groups alive per workgroup): same hit lists, first positions and counters from both,
-    equal to the oracle's -- on a ragged batch of many groups per workgroup, with empty and too-short queries, queries
-    that leave their table for the G tier, and tables as large as the arena allows."""
+def test_counting_alone_and_overlapped(small, klib, oracle, gpu_device, first_pos):
+    """Protein batches are counted by count_group_kernel (units of two group windows per barrier cycle) with three
+    workgroups per CU when a batch has the device to itself and one when batches overlap: same hit lists, first positions
+    and counters from both, equal to the oracle's -- on a ragged batch of many groups per workgroup, with empty and
+    too-short queries, queries that leave their table for the G tier, and tables as large as the arena allows."""
     from kaamer_amd import api, workload
     db, img, ix, oix = small
     rng = np.random.default_rng(11)
@@ -361,11 +359,8 @@ def test_both_counting_kernels(small, klib, oracle, gpu_device, first_pos, monke
     seqs += workload.unpack(workload.make_protein_queries(db, 500, seed=6))
     exp = _oracle_hits(oix, oracle, seqs)
     ref_c = None
-    # alone: three workgroups per CU; next to other batches: one, with units of two or (KAAMER_UNIT_WINDOWS=4, an experiment
-    # knob) four windows; the barrier-free kernel only when told to
-    for cb, asyn, uw in ((0, "0", "2"), (3, "0", "2"), (3, "0", "4"), (3, "1", "2")):
-        monkeypatch.setenv("KAAMER_COUNT_ASYNC", asyn)
-        monkeypatch.setenv("KAAMER_UNIT_WINDOWS", uw)
+    # alone: three workgroups per CU; next to other batches: one
+    for cb in (0, 3):
         hits, first, c = _device_search(ix, seqs, first_pos=first_pos, concurrent_batches=cb)
         for i, (h, f) in enumerate(exp):
             assert hits[i] == h, (cb, i)
@@ -377,7 +372,7 @@ def test_both_counting_kernels(small, klib, oracle, gpu_device, first_pos, monke
             ref_c = c
         else:
             assert {k: v for k, v in c.items() if k != "n_overflow"} == {k: v for k, v in ref_c.items() if k != "n_overflow"}
-    # a skewed family: 9 000 proteins behind one motif (tables that fill up, the G tier's three stages) through both kernels
+    # a skewed family: 9 000 proteins behind one motif (tables that fill up, the G tier's three stages) in both launches
     alpha = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", dtype=np.uint8)
     core = bytes(alpha[rng.integers(0, 20, 40)])
     fam = [bytes(alpha[rng.integers(0, 20, 8)]) + core[(i % 5):] + bytes(alpha[rng.integers(0, 20, 8)]) for i in range(9000)]
@@ -386,9 +381,7 @@ def test_both_counting_kernels(small, klib, oracle, gpu_device, first_pos, monke
     fq = [core, bytes(alpha[rng.integers(0, 20, 300)]) + core + bytes(alpha[rng.integers(0, 20, 400)]), fam[7], core[:20]] * 6
     fq += [bytes(alpha[rng.integers(0, 20, int(n))]) for n in rng.integers(20, 900, 200)]
     fexp = _oracle_hits(foix, oracle, fq)
-    for cb, asyn, uw in ((0, "0", "2"), (3, "0", "4"), (3, "1", "2")):
-        monkeypatch.setenv("KAAMER_COUNT_ASYNC", asyn)
-        monkeypatch.setenv("KAAMER_UNIT_WINDOWS", uw)
+    for cb in (0, 3):
         hits, first, c = _device_search(fix, fq, first_pos=first_pos, concurrent_batches=cb)
         for i, (h, f) in enumerate(fexp):
             assert hits[i] == h, (cb, i)

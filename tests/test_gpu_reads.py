@@ -208,16 +208,18 @@ def test_contig_piece_boundaries(small, oracle):
 
 
 @pytest.mark.parametrize("wide", ["0", "1"])
-def test_both_lane_per_read_kernels(small, oracle, monkeypatch, wide):
+def test_both_lane_per_read_kernels(small, oracle, gpu_device, monkeypatch, wide):
     """translate_reads_kernel exists for reads of up to 192 nt (64 codons per frame, three ORFs queued per frame) and of
     up to 384 nt (128 codons: two mask words, six ORFs per frame); the library picks per batch from the mean read length
     and KAAMER_WIDE_READS forces either.  The same reads through both: lengths around both limits (what is longer goes a
     wave per frame through translate_kernel), six 21-codon ORFs back to back in one frame on either strand, ORFs that
-    start in the first mask word and end in the second, 128 start codons in a row."""
+    start in the first mask word and end in the second, 128 start codons in a row.  The knob is read when a workspace is
+    created, so the test searches an index of its own (the shared one's workspaces are reused)."""
     import random
-    from kaamer_amd import workload
-    db, ix, oix = small
+    from kaamer_amd import api, workload
+    db, _, oix = small
     monkeypatch.setenv("KAAMER_WIDE_READS", wide)
+    ix = api.Index.from_image(api.Image.from_proteins(packed=db), gpu_device)
     rng = random.Random(23)
 
     def rnd(n, alphabet="ACGT"):
@@ -241,3 +243,4 @@ def test_both_lane_per_read_kernels(small, oracle, monkeypatch, wide):
     res = ix.search(reads, seq_type=abi.READS)
     _check_reads(res, reads, oracle, oix)
     assert sum(len(oracle.get_orfs(r)) >= 6 for r in reads[-15:]) >= 6
+    ix.close()
