@@ -170,8 +170,8 @@ template <class T> static int dev_grow(T **p, size_t *cap, size_t need)
 
 // workspaces, exchange buffers and staging of one shard for a batch of this size
 struct ShardBounds {
-    uint64_t e_cap, g_slots, max_hits;
-    uint32_t max_queries;
+    BatchBounds bb;      // of each shard's search workspace
+    uint64_t e_cap;      // entries per (shard -> owner) block
     bool full, pos;      // a full call (hit lists to the host), with PositionHits bitmaps
     uint64_t p_cap;      // bitmap words per block (pos)
 };
@@ -179,11 +179,11 @@ struct ShardBounds {
 static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq_bytes, uint32_t n_seqs, int32_t seq_type, const ShardBounds &b, uint32_t K)
 {
     HIPCHK(hipSetDevice(st.device));
-    const bool nucl = seq_type == KAAMER_NUCLEOTIDE || seq_type == KAAMER_READS;
+    const bool nucl = is_nucl(seq_type);
     const kaamer_workspace_opts &o = st.opts;
     const bool fits = st.ws && o.seq_type == seq_type && o.max_seq_bytes >= seq_bytes && o.max_seqs >= (n_seqs ? n_seqs : 1) &&
-                      o.g_tier_slots >= b.g_slots && o.max_queries >= b.max_queries && st.e_cap >= b.e_cap &&
-                      o.max_hits >= b.max_hits && (b.max_hits != 0 || o.max_hits == 0) &&
+                      o.g_tier_slots >= b.bb.g_slots && o.max_queries >= b.bb.max_queries && st.e_cap >= b.e_cap &&
+                      o.max_hits >= b.bb.max_hits && (b.bb.max_hits != 0 || o.max_hits == 0) &&
                       st.full == b.full && (o.want_positions != 0) == b.pos && (!b.pos || st.p_cap >= b.p_cap);
     if (!fits) {
         HIPCHK(hipStreamSynchronize(st.stream));
@@ -198,9 +198,9 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
         // the exchange wants an explicit, equal setting on both workspaces; kaamer_batch_out always carries first positions
         g.first_pos = (nucl || b.full) ? 1u : 2u;
         g.want_positions = b.pos ? 1u : 0u;
-        g.g_tier_slots = b.g_slots;
-        g.max_queries = b.max_queries;
-        g.max_hits = b.max_hits;       // 0: the library's default for the input size (as the unsharded call starts)
+        g.g_tier_slots = b.bb.g_slots;
+        g.max_queries = b.bb.max_queries;
+        g.max_hits = b.bb.max_hits;       // 0: the library's default for the input size (as the unsharded call starts)
         int rc = kaamer_workspace_create(st.ix, &g, &st.ws);
         if (rc) { st.ws = nullptr; return rc; }
         st.opts = g;
@@ -218,7 +218,7 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
         m.seq_type = KAAMER_PROTEIN;
         m.first_pos = g.first_pos;
         m.max_hits = (uint64_t)W * st.layout.e_cap;
-        m.g_tier_slots = b.g_slots;
+        m.g_tier_slots = b.bb.g_slots;
         m.want_positions = g.want_positions;
         m.max_pos_words = b.pos ? (uint64_t)W * x_p_cap(&st.layout) : 0;   // merged bitmaps <= the words received
         m.compact = b.full ? 1u : 0u;   // the full call copies CSR to the host
@@ -278,7 +278,7 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
     ShardSet *sx = t->set;
     const uint32_t W = sx_->n;
     const uint64_t seq_bytes = t->seq_bytes;
-    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
+    const bool nucl = is_nucl(t->seq_type);
     std::vector<ShardState> &sh = sx->sh;
     const size_t off_at = ((size_t)seq_bytes + 7) & ~(size_t)7;
     struct Guard {   // every early return: nothing of this attempt is left running on any device
@@ -364,7 +364,7 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     kaamer_sharded_index *sx_ = t->sx;
     ShardSet *sx = t->set;
     const uint32_t W = sx_->n;
-    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
+    const bool nucl = is_nucl(t->seq_type);
     std::vector<ShardState> &sh = sx->sh;
     struct Guard {
         ShardSet *set; bool armed;
@@ -525,7 +525,7 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     t->b.full = top == nullptr;
     t->b.pos = t->b.full && in->want_positions != 0;
     if (t->b.pos) {   // bitmap words per entry ~ 1 + SizeInKmer / 64 (ORFs: a third of the nucleotides)
-        const bool nucl = in->seq_type == KAAMER_NUCLEOTIDE || in->seq_type == KAAMER_READS;
+        const bool nucl = is_nucl(in->seq_type);
         const uint64_t mean = t->seq_bytes / (in->n_seqs ? in->n_seqs : 1u) / (nucl ? 3u : 1u);
         t->b.p_cap = t->b.e_cap * (1 + mean / 64);
     }
@@ -566,23 +566,17 @@ int kaamer_sharded_wait_batch_top(kaamer_sharded_ticket *t, kaamer_batch_top **o
 {
     if (!t || !out) return kaamer_fail(KAAMER_E_ARG, "sharded_wait_batch_top: bad argument");
     *out = nullptr;
-    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
     int rc;
     for (;;) {
         rc = sharded_collect(t, out);
-        if (rc != KAAMER_E_CAPACITY || t->attempt >= 6) break;
+        if (rc != KAAMER_E_CAPACITY || t->attempt >= MAX_BOUND_RETRIES) break;
         t->attempt++;
         if (!t->adaptive) {
             // the bounds themselves were too small: enlarge them all (hit pool included: the unsharded call does the same)
             t->b.e_cap *= 4;
-            t->b.g_slots = t->b.g_slots ? t->b.g_slots * 4 : (128ull << 20);
-            t->b.max_hits = t->b.max_hits ? t->b.max_hits * 4 : t->seq_bytes * 8 + 65536;
-            if (nucl) {
-                const uint64_t hard = t->seq_bytes / 10 + (uint64_t)t->n_seqs * 6 + 64;
-                t->b.max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
-            }
+            bounds_grow(t->b.bb, t->seq_bytes, t->n_seqs, is_nucl(t->seq_type));
         }   // else: the blocks sized from the previous call were too small -- once more at the full capacity, same bounds
-        rc = sharded_enqueue(t);
+        rc = sharded_enqueue(t);   // (an error here ends the loop, E_CAPACITY included: kept as it was)
         if (rc) break;
     }
     sharded_release(t->sx, t->set);
@@ -802,23 +796,17 @@ int kaamer_sharded_wait_batch(kaamer_sharded_full_ticket *ft, kaamer_batch_out *
     if (!ft || !out) return kaamer_fail(KAAMER_E_ARG, "sharded_wait_batch: bad argument");
     *out = nullptr;
     kaamer_sharded_ticket *t = &ft->t;
-    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
     int rc;
     for (;;) {
         rc = sharded_collect_full(t, out);
-        if (rc != KAAMER_E_CAPACITY || t->attempt >= 6) break;
+        if (rc != KAAMER_E_CAPACITY || t->attempt >= MAX_BOUND_RETRIES) break;
         t->attempt++;
         if (!t->adaptive) {   // the bounds themselves were too small: enlarge them all, as kaamer_sharded_wait_batch_top does
             t->b.e_cap *= 4;
             t->b.p_cap *= 4;
-            t->b.g_slots = t->b.g_slots ? t->b.g_slots * 4 : (128ull << 20);
-            t->b.max_hits = t->b.max_hits ? t->b.max_hits * 4 : t->seq_bytes * 8 + 65536;
-            if (nucl) {
-                const uint64_t hard = t->seq_bytes / 10 + (uint64_t)t->n_seqs * 6 + 64;
-                t->b.max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
-            }
+            bounds_grow(t->b.bb, t->seq_bytes, t->n_seqs, is_nucl(t->seq_type));
         }   // else: the blocks sized from the previous call were too small -- once more at the full capacity, same bounds
-        rc = sharded_enqueue(t);
+        rc = sharded_enqueue(t);   // (an error here ends the loop, E_CAPACITY included: kept as it was)
         if (rc) break;
     }
     sharded_release(t->sx, t->set);

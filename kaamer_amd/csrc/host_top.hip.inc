@@ -30,22 +30,9 @@ struct kaamer_ticket {
     kaamer_topn_opts top;
     uint8_t *h_block;
     size_t h_block_cap, copied;
-    uint64_t max_hits, g_slots;
-    uint32_t max_queries;
+    BatchBounds b;
     int attempt;
 };
-
-static void scan_u32_on(kaamer_workspace *ws, const uint32_t *cnt, const uint32_t *d_count, uint64_t bound, uint64_t *off, hipStream_t s)
-{
-    if (bound <= 8 * (uint64_t)SCAN_TILE) {
-        hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, cnt, d_count, off);
-    } else {
-        const uint32_t nsb = (uint32_t)((bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
-        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, cnt, d_count, ws->d_bsum);
-        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, cnt, d_count, ws->d_bsum, off);
-    }
-}
 
 // upper bound of the result block of a batch searched on `ws`, whose queries belong to `src` (ws itself, or the
 // workspace that translated the batch: merged results of a sharded index)
@@ -194,16 +181,16 @@ static int top_enqueue(kaamer_ticket *t)
 {
     kaamer_index *ix = t->ix;
     TopSlot &h = ix->top[t->slot];
-    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
+    const bool nucl = is_nucl(t->seq_type);
     kaamer_workspace_opts o;
     memset(&o, 0, sizeof o);
     o.max_seq_bytes = t->seq_bytes;
     o.max_seqs = t->n_seqs ? t->n_seqs : 1;
-    o.max_hits = t->max_hits;
-    o.g_tier_slots = t->g_slots;
+    o.max_hits = t->b.max_hits;
+    o.g_tier_slots = t->b.g_slots;
     o.seq_type = t->seq_type;
     o.first_pos = 0;  // as the reference fills PositionHits: nucleotide / reads input only (search.go:416)
-    o.max_queries = t->max_queries;
+    o.max_queries = t->b.max_queries;
     o.concurrent_batches = (uint32_t)ix->n_top;   // the slots exist so that batches overlap
     int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results);
     if (rc) return rc;
@@ -304,7 +291,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
     *out = nullptr;
     kaamer_index *ix = t->ix;
     TopSlot &h = ix->top[t->slot];
-    const bool nucl = t->seq_type == KAAMER_NUCLEOTIDE || t->seq_type == KAAMER_READS;
+    const bool nucl = is_nucl(t->seq_type);
     int rc = KAAMER_OK;
     hipError_t e = hipSetDevice(ix->device);
     if (e != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
@@ -316,16 +303,11 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         if (status) h.ws->clean = false;  // an aborted batch may leave per-batch state behind
         rc = status_to_error(status, h.ws);
         if (!rc && (hdr->status & 0x80000000u)) rc = kaamer_fail(KAAMER_E_CAPACITY, "result block capacity exceeded");
-        if (rc == KAAMER_E_CAPACITY && t->attempt < 6) {
-            // the hit count of a batch is data dependent: enlarge the bounds and run the batch again from the staging copy
+        if (rc == KAAMER_E_CAPACITY && t->attempt < MAX_BOUND_RETRIES) {
+            // enlarge the bounds and run the batch again from the staging copy
             t->attempt++;
-            t->max_hits = t->max_hits ? t->max_hits * 4 : t->seq_bytes * 8 + 65536;
-            t->g_slots = t->g_slots ? t->g_slots * 4 : (128ull << 20);
-            if (nucl) {  // hard bound: a frame of n codons holds at most n/21 + 1 ORFs
-                const uint64_t hard = t->seq_bytes / 10 + (uint64_t)t->n_seqs * 6 + 64;
-                t->max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
-            }
-            rc = top_enqueue(t);
+            bounds_grow(t->b, t->seq_bytes, t->n_seqs, nucl);
+            rc = top_enqueue(t);   // (an error here ends the loop, E_CAPACITY included: kept as it was)
             continue;
         }
         if (rc) break;

@@ -84,6 +84,27 @@ struct HostSlot {
     bool busy = false;              // (under kaamer_index::pool_mu)
 };
 
+static inline bool is_nucl(int32_t seq_type) { return seq_type == KAAMER_NUCLEOTIDE || seq_type == KAAMER_READS; }
+
+// the data-dependent bounds of a host-buffer call (0: the library's default for the input size).  The hit count of a
+// batch is data dependent: a call starts from an estimate and, while the device reports KAAMER_E_CAPACITY (results are
+// never partial), runs the batch again with grown bounds, at most MAX_BOUND_RETRIES times.
+struct BatchBounds { uint64_t max_hits, g_slots; uint32_t max_queries; };
+static const int MAX_BOUND_RETRIES = 6;
+
+// where the full-list calls start (the top-N calls start from 0, the workspace's own default)
+static uint64_t full_start_hits(uint64_t seq_bytes) { return seq_bytes * 8 + 65536; }
+
+static void bounds_grow(BatchBounds &b, uint64_t seq_bytes, uint32_t n_seqs, bool nucl)
+{
+    b.max_hits = b.max_hits ? b.max_hits * 4 : full_start_hits(seq_bytes);
+    b.g_slots = b.g_slots ? b.g_slots * 4 : (128ull << 20);
+    if (nucl) {  // hard bound: a frame of n codons holds at most n/21 + 1 ORFs
+        const uint64_t hard = seq_bytes / 10 + (uint64_t)n_seqs * 6 + 64;
+        b.max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
+    }
+}
+
 // one in-flight call of the pipelined host-buffer boundary (host_top.hip.inc)
 struct TopSlot {
     kaamer_workspace *ws = nullptr;
@@ -1624,6 +1645,84 @@ static void launch_group_merge(const CountParams &p, int grid, bool firstpos, hi
     else hipLaunchKernelGGL((count_group_kernel<false, 2>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
 }
 
+// exclusive scan of cnt[0..*d_count) -> off[0..*d_count]; bound: host-side bound of *d_count (which launch, grid sizing)
+static void scan_u32_on(kaamer_workspace *ws, const uint32_t *cnt, const uint32_t *d_count, uint64_t bound, uint64_t *off, hipStream_t s)
+{
+    if (bound <= 8 * (uint64_t)SCAN_TILE) {
+        hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, cnt, d_count, off);
+    } else {
+        const uint32_t nsb = (uint32_t)((bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
+        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, cnt, d_count, ws->d_bsum);
+        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
+        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, cnt, d_count, ws->d_bsum, off);
+    }
+}
+
+// a workspace that is not `clean` (first batch, or a batch that did not run to its finalize kernel) back to the
+// per-batch zero state; what becomes of ws->clean is the caller's business
+static int ws_reset_if_dirty(kaamer_workspace *ws, hipStream_t s)
+{
+    if (ws->clean) return KAAMER_OK;
+    HIPCHK(hipMemsetAsync(ws->d_pool_cursor, 0, (size_t)3 * CURSOR_STRIDE * sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(ws->d_list_counts, 0, N_SMALL_SLOTS * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(ws->d_counter_replicas, 0, sizeof(unsigned long long) * CTR_REPLICAS * CTR_N, s));
+    HIPCHK(hipMemsetAsync(ws->d_valid, 0, (size_t)(ws->pos_cap / 64 + 2) * sizeof(unsigned long long), s));
+    return KAAMER_OK;
+}
+
+static WorkItem *ws_list(const kaamer_workspace *ws, int which) { return ws->d_lists + (size_t)which * ws->q_cap; }
+
+// what every counting launch of a search and of a merge shares: group / schedule arrays, hit arrays, cursors, G-tier arena,
+// counters, status.  Everything else is zero.
+static CountParams count_params_base(const kaamer_workspace *ws)
+{
+    CountParams p;
+    memset(&p, 0, sizeof p);
+    p.qinfo = ws->d_qinfo;
+    p.slot_off = ws->d_slot_off;
+    p.group_first = ws->d_group_first;
+    p.sched = ws->d_sched;
+    p.d_n_sched = ws->d_n_sched;
+    p.d_n_groups = ws->d_n_groups;
+    p.d_nq = ws->d_nq;
+    p.list_cap = ws->q_cap;
+    p.group_queue = ws->d_list_counts + SLOT_GROUP_QUEUE;
+    p.hit_off = ws->d_hit_off;
+    p.q_cnt = ws->d_q_cnt;
+    p.hit_pid = ws->d_hit_pid;
+    p.hit_km = ws->d_hit_km;
+    p.hit_fp = ws->d_hit_fp;
+    p.hit_cap = ws->sparse_cap;
+    p.tail_cursor = ws->d_pool_cursor;
+    p.g_keys = ws->d_g_keys;
+    p.g_slots = ws->g_slots;
+    p.g_cursor = ws->d_pool_cursor + CURSOR_STRIDE;
+    p.counters = ws->d_counter_replicas;
+    p.status = ws->d_list_counts + SLOT_STATUS;
+    return p;
+}
+
+// workgroups of a group-kernel launch over nq tables that hold `items` items in all
+static int group_grid(const kaamer_workspace *ws, uint64_t nq, uint64_t items)
+{
+    const uint64_t g = ((uint64_t)GRP_MIN_TABLE * nq + 3 * items) / GRP_BUDGET + 1;
+    return (int)(g > (uint64_t)ws->grp_grid ? (uint64_t)ws->grp_grid : g);
+}
+
+// workgroups of a G-tier launch: never more than queries
+static int g_tier_grid(const kaamer_workspace *ws, uint32_t nq_bound)
+{
+    return (uint32_t)ws->g_grid > nq_bound ? (nq_bound > 0 ? (int)nq_bound : 1) : ws->g_grid;
+}
+
+// epochs of the chained-tile kernels: 24 bits, never 0
+static uint32_t next_epoch(uint32_t &e)
+{
+    e = (e + 1u) & 0xFFFFFFu;
+    if (e == 0) e = 1;
+    return e;
+}
+
 // The search's environment knobs (tools/README.md), read where a workspace or an index is created and nowhere on the
 // per-batch path (a host that calls in through cgo may setenv on another thread).  A knob that is not set leaves the
 // shipped value.
@@ -1852,7 +1951,7 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     memset(ws, 0, sizeof *ws);
     ws->device = ix->device;
     ws->opts = *opts;
-    ws->nucleotide = opts->seq_type == KAAMER_NUCLEOTIDE || opts->seq_type == KAAMER_READS;
+    ws->nucleotide = is_nucl(opts->seq_type);
     ws->max_seqs = opts->max_seqs ? opts->max_seqs : 1;
     if (ws->nucleotide) {
         // six frames of len/3 codons: at most 2 amino acids per nucleotide, an ORF needs >= 21 of them
@@ -1880,7 +1979,7 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
         ws->sparse_cap = items + items / 2 + 64ull * ws->q_cap + GRP_MAX_TABLE + ws->hit_cap / 2 + (1u << 20);
     }
     // the reference fills PositionHits only for nucleotide/reads input or with -pos (search.go:416)
-    ws->firstpos = opts->first_pos == 1 || (opts->first_pos == 0 && (opts->seq_type == KAAMER_NUCLEOTIDE || opts->seq_type == KAAMER_READS));
+    ws->firstpos = opts->first_pos == 1 || (opts->first_pos == 0 && is_nucl(opts->seq_type));
     const SearchKnobs knobs = read_knobs();
     int grp_per_cu = 0, p_per_cu = 0;
     hipError_t oe = ws->firstpos ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&grp_per_cu, count_group_kernel<true, 0>, 64 * GRP_WAVES, 0)
@@ -2039,11 +2138,9 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
 static void launch_layout(kaamer_workspace *ws, uint32_t nq_bound, uint32_t *status, hipStream_t s, uint32_t bshift, bool schedule = true)
 {
     const uint32_t cshift = bshift > GRP_SHIFT ? 10u : bshift >= GRP_SHIFT ? 9u : 7u;  // 16 schedule classes over the slots a group / pack can hold
-    ws->lay_epoch = (ws->lay_epoch + 1u) & 0xFFFFFFu;
-    if (ws->lay_epoch == 0) ws->lay_epoch = 1;
     const uint32_t tiles = (uint32_t)(((uint64_t)nq_bound + 1 + LAY_TILE - 1) / LAY_TILE);
     hipLaunchKernelGGL(layout_kernel, dim3(tiles), dim3(LAY_THREADS), 0, s, ws->d_slots, ws->d_nq, ws->d_slot_off, ws->d_group_first,
-                       ws->d_group_start, ws->d_n_groups, ws->groups_cap, ws->d_chain, ws->lay_epoch, status, bshift);
+                       ws->d_group_start, ws->d_n_groups, ws->groups_cap, ws->d_chain, next_epoch(ws->lay_epoch), status, bshift);
     if (schedule)  // (the pack kernel takes its packs by ticket in layout order: no schedule)
         hipLaunchKernelGGL(schedule_kernel, dim3(1), dim3(1024), 0, s, ws->d_group_first, ws->d_group_start, ws->d_slot_off, ws->d_n_groups,
                            ws->d_nq, ws->d_sched, ws->d_n_sched, cshift);
@@ -2057,14 +2154,7 @@ static void launch_pos_layout(kaamer_workspace *ws, uint32_t nq_bound, const int
     if (gb < 1) gb = 1;
     if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
     hipLaunchKernelGGL(pos_words_kernel, dim3(gb), dim3(256), 0, s, ws->d_qinfo, sizes, ws->d_q_cnt, ws->d_nq, ws->d_pos_words);
-    if (nq_bound <= 8 * SCAN_TILE) {
-        hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_pos_base);
-    } else {
-        const uint32_t nsb = (uint32_t)(((uint64_t)nq_bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
-        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_bsum);
-        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_pos_words, ws->d_nq, ws->d_bsum, ws->d_pos_base);
-    }
+    scan_u32_on(ws, ws->d_pos_words, ws->d_nq, nq_bound, ws->d_pos_base, s);
     hipLaunchKernelGGL(pos_layout_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, ws->d_qinfo, sizes, ws->d_q_cnt,
                        ws->compact ? ws->d_csr_off : ws->d_hit_off,
                        ws->d_pos_base, ws->d_nq, ws->d_pos_off, ws->d_pos_bits, ws->bits_cap, status);
@@ -2073,14 +2163,7 @@ static void launch_pos_layout(kaamer_workspace *ws, uint32_t nq_bound, const int
 // optional last step of a search / merge: CSR in query order from the sharded hit arrays
 static void launch_compaction(kaamer_workspace *ws, uint32_t nq_bound, uint32_t *status, hipStream_t s)
 {
-    if (nq_bound <= 8 * SCAN_TILE) {
-        hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_q_cnt, ws->d_nq, ws->d_csr_off);
-    } else {
-        const uint32_t nsb = (uint32_t)(((uint64_t)nq_bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
-        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_q_cnt, ws->d_nq, ws->d_bsum);
-        hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, ws->d_q_cnt, ws->d_nq, ws->d_bsum, ws->d_csr_off);
-    }
+    scan_u32_on(ws, ws->d_q_cnt, ws->d_nq, nq_bound, ws->d_csr_off, s);
     uint32_t gb = (nq_bound + 3) / 4;
     if (gb < 1) gb = 1;
     if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
@@ -2119,13 +2202,202 @@ int kaamer_workspace_set_count_stream(kaamer_workspace *ws, void *stream)
     return KAAMER_OK;
 }
 
+// ---- the stages of a search, in the order they run: each enqueues its launches on `s` (errors: the caller's hipGetLastError)
+
+// protein batches: prep + table layout + group schedule in one launch (count_group.hip.inc)
+static void enqueue_protein_prep(kaamer_workspace *ws, const uint8_t *d_seqs, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t seq_bytes,
+                                 uint32_t *status, hipStream_t s)
+{
+    PrepLayoutParams pl;
+    memset(&pl, 0, sizeof pl);
+    pl.seqs = d_seqs; pl.pos_bound = seq_bytes; pl.offsets = d_offsets; pl.n_seqs = n_seqs;
+    pl.q = ws->d_q; pl.d_nq = ws->d_nq; pl.d_n_pos = ws->d_n_pos; pl.invalid = ws->d_valid; pl.qinfo = ws->d_qinfo;
+    pl.hit_off = ws->d_hit_off; pl.q_cnt = ws->d_q_cnt;
+    pl.E = ws->d_slot_off; pl.group_first = ws->d_group_first; pl.group_start = ws->d_group_start;
+    pl.d_n_groups = ws->d_n_groups; pl.groups_cap = ws->groups_cap; pl.chain = ws->d_chain;
+    pl.epoch = next_epoch(ws->lay_epoch);
+    pl.status = status; pl.sched = ws->d_sched; pl.d_n_sched = ws->d_n_sched;
+    pl.tiles_done = ws->d_list_counts + SLOT_TILES_DONE;
+    pl.slots = ws->d_slots; pl.bshift = ws->pack_shift; pl.cshift = ws->pack_shift > GRP_SHIFT ? 10u : ws->pack_shift >= GRP_SHIFT ? 9u : 7u;
+    // the group kernel takes the groups longest first (measured with one workgroup per CU and three batches in flight:
+    // 0.1381-0.1406 ms per batch, 0.1430-0.1441 with the groups in index order)
+    pl.no_sched = 0u;
+    pl.d_total = ws->d_lay_total;
+    pl.slot_scale = ws->d_slot_scale;
+    pl.room_slots = ws->table_room;
+    const uint32_t tiles = (uint32_t)(((uint64_t)n_seqs + 1 + PL_TILE - 1) / PL_TILE);
+    hipLaunchKernelGGL(prep_layout_schedule_kernel, dim3(tiles), dim3(LAY_THREADS), 0, s, pl);
+}
+
+// what the probe and the counting stages work on: the protein records themselves, or the ORFs of a translated batch
+struct QueryInput {
+    const uint8_t *residues;   // what kernel P reads
+    uint64_t pos_bound;        // host-side bound of the residue positions (grid sizing only)
+    uint32_t nq_bound;         // host-side bound of the number of queries
+};
+
+// nucleotide batches: 6-frame translation -- count, scan, write, order (translate.hip.inc) -- and the ORFs' prep
+static QueryInput enqueue_translate(kaamer_workspace *ws, const uint8_t *d_seqs, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t seq_bytes,
+                                    uint32_t *status, hipStream_t s)
+{
+    const size_t cap6 = (size_t)ws->max_seqs * 6;
+    TranslateParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.seqs = d_seqs; tp.offsets = d_offsets; tp.n_seqs = n_seqs; tp.seq_bound = seq_bytes; tp.max_long = ws->max_long; tp.max_piece_items = ws->max_piece_items;
+    tp.cnt_orf = ws->d_cnt3; tp.cnt_aa = ws->d_cnt3 + cap6; tp.cnt_sa = ws->d_cnt3 + 2 * cap6;
+    tp.off_orf = ws->d_off3; tp.off_aa = ws->d_off3 + (cap6 + 1); tp.off_sa = ws->d_off3 + 2 * (cap6 + 1);
+    tp.tmp_meta = ws->d_tmp_meta; tp.orf_aa = ws->d_orf_aa; tp.starts_alt = ws->d_starts_alt;
+    tp.q_cap = ws->q_cap; tp.aa_cap = ws->aa_cap; tp.sa_cap = ws->sa_cap; tp.status = status;
+    // which lane-per-read kernel: the wide one (reads up to 384 nt, 2 waves per SIMD) when the batch's mean length says that
+    // reads beyond 192 nt are common; a batch of 100-150-nt reads is 4 % slower through it (translate.hip.inc)
+    const bool wide_reads = ws->wide_reads >= 0 ? ws->wide_reads != 0 : seq_bytes > 160ull * (n_seqs ? n_seqs : 1u);
+    tp.ts_max = wide_reads ? TS_MAX_WIDE : TS_MAX;
+    int tgrid = ws->n_cu * 8;  // 256-thread blocks, one (sequence, frame, piece) item per wave at a time
+    tp.d_n6 = ws->d_n6;
+    int sgrid = ws->n_cu * 8;  // lane-per-read kernel: 2-wave blocks, 13 KB (COUNT) / 30 KB (WRITE) of LDS each
+    if ((uint64_t)sgrid * TS_WAVES * 64 > (uint64_t)n_seqs) sgrid = n_seqs > 0 ? (int)(((uint64_t)n_seqs + TS_WAVES * 64 - 1) / (TS_WAVES * 64)) : 1;
+    tp.n_long = ws->d_list_counts + SLOT_N_LONG;
+    const size_t mpi = (size_t)ws->max_piece_items;
+    tp.long_seq = ws->d_long_seq; tp.long_np = ws->d_long_np; tp.piece_base = ws->d_piece_base; tp.piece_li = ws->d_piece_li;
+    tp.pcnt_orf = ws->d_pcnt3; tp.pcnt_aa = ws->d_pcnt3 + mpi; tp.pcnt_sa = ws->d_pcnt3 + 2 * mpi;
+    tp.poff_orf = ws->d_poff3; tp.poff_aa = ws->d_poff3 + (mpi + 1); tp.poff_sa = ws->d_poff3 + 2 * (mpi + 1);
+    tp.d_n_piece_items = ws->d_n_piece_items;
+    // reads: a lane each; longer sequences: listed, cut in pieces, a wave per piece
+    const uint64_t long_bound = (uint64_t)ws->max_long < n_seqs ? ws->max_long : n_seqs;
+    const uint64_t seq_long_max = seq_bytes / (TS_MAX + 1) + 1;
+    const uint64_t n_long_bound = long_bound < seq_long_max ? long_bound : seq_long_max;
+    const uint64_t piece_bound = 6ull * (seq_bytes / 3 / TP_PIECE + n_long_bound + 1);
+    if ((uint64_t)tgrid * 4 > piece_bound) tgrid = (int)((piece_bound + 3) / 4);
+    if (tgrid < 1) tgrid = 1;
+    tp.ticket = ws->d_list_counts + SLOT_TR_TICKET;
+    tp.chain = ws->d_tr_chain;
+    tp.epoch = next_epoch(ws->tr_epoch);
+    tp.out_meta = ws->d_q; tp.d_nq = ws->d_nq; tp.d_n_pos = ws->d_n_pos;
+    tp.w_off_orf = ws->d_off3; tp.w_off_aa = ws->d_off3 + (cap6 + 1); tp.w_off_sa = ws->d_off3 + 2 * (cap6 + 1);
+    // long sequences first (listed, cut in pieces, counted: a wave per piece) -- a reads-only batch falls through
+    // these launches; then everything of the reads and the output offsets of both kinds in one kernel
+    hipLaunchKernelGGL(list_long_kernel, dim3((unsigned)(((uint64_t)n_seqs + LL_BLOCK - 1) / LL_BLOCK + (n_seqs ? 0 : 1))), dim3(LL_BLOCK), 0, s, tp);
+    scan_u32_on(ws, ws->d_long_np, tp.n_long, n_long_bound, ws->d_piece_base, s);
+    hipLaunchKernelGGL(piece_li_kernel, dim3((unsigned)((n_long_bound + 255) / 256)), dim3(256), 0, s, tp);
+    hipLaunchKernelGGL(translate_kernel<false>, dim3(tgrid), dim3(256), 0, s, tp);
+    for (int a = 0; a < 3; a++) scan_u32_on(ws, ws->d_pcnt3 + a * mpi, ws->d_n_piece_items, piece_bound, ws->d_poff3 + a * (mpi + 1), s);
+    hipLaunchKernelGGL(long_totals_kernel, dim3((unsigned)((n_long_bound * 6 + 255) / 256)), dim3(256), 0, s, tp);
+    if (wide_reads) hipLaunchKernelGGL(translate_reads_kernel<TS_MAX_WIDE>, dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
+    else hipLaunchKernelGGL(translate_reads_kernel<TS_MAX>, dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
+    hipLaunchKernelGGL(translate_kernel<true>, dim3(tgrid), dim3(256), 0, s, tp);
+    hipLaunchKernelGGL(orf_order_long_kernel, dim3((unsigned)(n_long_bound < (uint64_t)ws->n_cu * 32 ? (n_long_bound + 3) / 4 + 1 : (uint64_t)ws->n_cu * 8)), dim3(256), 0, s,
+                       ws->d_tmp_meta, tp.off_orf, ws->d_long_seq, tp.n_long, ws->d_q, ws->d_nq);
+    hipLaunchKernelGGL(prep_orf_kernel, dim3(ws->n_cu * 4), dim3(256), 0, s, ws->d_q, ws->d_nq, ws->d_valid, ws->d_n_pos,
+                       ws->d_qinfo, ws->d_slots, ws->d_hit_off, ws->d_q_cnt, ws->d_slot_scale, ws->table_room);
+    return QueryInput{ ws->d_orf_aa, ws->aa_cap, ws->q_cap };
+}
+
+// kernel P: flat probe
+static void enqueue_probe(const kaamer_index *ix, kaamer_workspace *ws, const uint8_t *residues, uint64_t pos_bound, hipStream_t s)
+{
+    ProbeParams pp;
+    pp.table = reinterpret_cast<const uint4 *>(ix->d_buckets);
+    pp.n_buckets = ix->hdr.n_buckets;
+    pp.n_shards = ix->hdr.n_shards;
+    pp.shard = ix->hdr.shard;
+    pp.residues = residues;
+    pp.invalid = ws->d_valid;
+    pp.d_n_pos = ws->d_n_pos;
+    pp.vals = ws->d_vals;
+    pp.counters = ws->d_counter_replicas;
+    pp.nontemporal = pos_bound < ix->hdr.n_buckets ? 1u : 0u;
+    uint64_t p_blocks = (pos_bound / 64 + 1 + P_WAVES - 1) / P_WAVES;
+    if (p_blocks > (uint64_t)ws->p_grid) p_blocks = ws->p_grid;
+    if (p_blocks < 1) p_blocks = 1;
+    if (ws->nucleotide) hipLaunchKernelGGL(probe_kernel<true>, dim3((unsigned)p_blocks), dim3(64 * P_WAVES), 0, s, pp);
+    else hipLaunchKernelGGL(probe_kernel<false>, dim3((unsigned)p_blocks), dim3(64 * P_WAVES), 0, s, pp);
+}
+
+// the counting launches of a search share these on top of count_params_base
+static CountParams search_count_params(const kaamer_index *ix, const kaamer_workspace *ws)
+{
+    CountParams p = count_params_base(ws);
+    p.arena = ix->d_arena;
+    p.vals = ws->d_vals;
+    p.queue_head = ws->d_list_counts + SLOT_QUEUE_HEAD;
+    p.n_proteins = ix->hdr.max_protein_id + 1u ? ix->hdr.max_protein_id + 1u : 0xFFFFFFFFu;
+    return p;
+}
+
+// a search finalizes inside the G-tier kernel when nothing follows it
+static bool fused_finalize(const kaamer_workspace *ws) { return !ws->compact && !ws->want_positions; }
+
+// kernel C: counting -- group kernel (protein) or pack kernel (ORFs), the G tier behind it, compaction
+static void enqueue_count(const kaamer_index *ix, kaamer_workspace *ws, bool nucl, uint64_t seq_bytes, uint32_t n_seqs, uint32_t nq_bound,
+                          uint64_t pos_bound, hipStream_t s)
+{
+    const CountParams p = search_count_params(ix, ws);
+    CountParams pc = p;
+    pc.ovf_list = ws_list(ws, LIST_G); pc.ovf_count = ws->d_list_counts + LIST_G;
+    pc.last_group_pass = ws->want_positions ? 0u : 1u;
+    pc.pack_shift = ws->pack_shift;
+    pc.pack_tickets = ws->d_list_counts + SLOT_PACK_TICKETS;
+    if (!nucl) {
+        launch_group(pc, group_grid(ws, nq_bound, pos_bound), ws->firstpos, s);
+    } else {
+        // one wave per workgroup, packs dealt out statically: never more waves than packs (group_grid's bound, with the
+        // pack's own budget 1 << pack_shift)
+        uint64_t gb = (((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) >> ws->pack_shift) + 1;
+        if (gb > (uint64_t)ws->pack_grid) gb = ws->pack_grid;
+        // reads of ~150 nt: ORFs of <= 50 residues, tables of 64-128 slots -> the small arena (20 waves per CU);
+        // longer sequences (mixed read lengths, contigs): the arena that holds tables of up to 576 slots, or 66 000
+        // ORFs of a 1 M mixed-read batch went to the G tier (measured: 8.19 -> 6.73 ms for the counting stage of
+        // that batch, while the 150-nt batch loses 0.4 ms with the larger arena)
+        const bool long_orfs = seq_bytes > 200ull * (n_seqs ? n_seqs : 1u) || ws->dense_tables;
+        if (long_orfs) {
+            if (gb > (uint64_t)ws->pack_grid_long) gb = ws->pack_grid_long;
+            hipLaunchKernelGGL((count_pack_kernel<PK_ARENA_ORF_LONG>), dim3((unsigned)gb), dim3(64), 0, s, pc);
+        } else {
+            hipLaunchKernelGGL((count_pack_kernel<PK_ARENA_ORF>), dim3((unsigned)gb), dim3(64), 0, s, pc);
+        }
+    }
+    CountParams pg = p;
+    pg.list = ws_list(ws, LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
+    if (fused_finalize(ws)) {
+        pg.fin_out = ws->d_counters; pg.fin_small = ws->d_list_counts; pg.fin_status_out = ws->d_status_out;
+        pg.fin_cursors = ws->d_pool_cursor;
+        pg.fin_slot_scale = ws->d_slot_scale; pg.fin_scale_cap = ws->slot_scale_cap; pg.fin_scale_margin = ws->slot_scale_margin;
+    }
+    hipLaunchKernelGGL(count_global_kernel, dim3(g_tier_grid(ws, nq_bound)), dim3(64 * G_WAVES), 0, s, pg);
+    if (ws->compact) launch_compaction(ws, nq_bound, p.status, s);
+}
+
+// PositionHits bitmaps (search.go:442-452): layout from the final hit lists, then one more pass of the group kernel
+// that sets one bit per (hit, position)
+static void enqueue_positions(const kaamer_index *ix, kaamer_workspace *ws, uint32_t nq_bound, uint64_t pos_bound, hipStream_t s)
+{
+    const CountParams p = search_count_params(ix, ws);
+    launch_pos_layout(ws, nq_bound, nullptr, p.status, s);
+    // the PositionHits pass runs on the group kernel: lay the tables out in its groups
+    launch_layout(ws, nq_bound, p.status, s, GRP_SHIFT);
+    CountParams pp2 = p;
+    pp2.pack_shift = GRP_SHIFT;   // (the layout just above)
+    pp2.last_group_pass = 1u;
+    pp2.pos_base = ws->d_pos_base;
+    pp2.pos_bits = ws->d_pos_bits;
+    pp2.group_queue = ws->d_list_counts + SLOT_GROUP_QUEUE_POS;
+    pp2.ovf_list = ws_list(ws, LIST_SO); pp2.ovf_count = ws->d_list_counts + LIST_SO;
+    launch_group_positions(pp2, group_grid(ws, nq_bound, pos_bound), s);
+    CountParams pg2 = p;   // the G tier's queries: their hit lists are final, the counting arena is free again
+    pg2.list = ws_list(ws, LIST_G); pg2.list_count = ws->d_list_counts + LIST_G;
+    pg2.pos_base = ws->d_pos_base;
+    pg2.pos_bits = ws->d_pos_bits;
+    pg2.g_cursor = ws->d_pool_cursor + 2 * CURSOR_STRIDE;
+    hipLaunchKernelGGL(positions_global_kernel, dim3(g_tier_grid(ws, nq_bound)), dim3(64 * G_WAVES), 0, s, pg2);
+}
+
 int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *d_seqs, const uint64_t *d_offsets,
                          uint32_t n_seqs, uint64_t seq_bytes, int32_t seq_type, void *stream,
                          kaamer_device_result *out)
 {
     if (!ix || !ws || !out || (n_seqs && (!d_seqs || !d_offsets))) return kaamer_fail(KAAMER_E_ARG, "search_device: bad argument");
     if (ix->device != ws->device) return kaamer_fail(KAAMER_E_ARG, "workspace belongs to another device");
-    const bool nucl = seq_type == KAAMER_NUCLEOTIDE || seq_type == KAAMER_READS;
+    const bool nucl = is_nucl(seq_type);
     if (!nucl && seq_type != KAAMER_PROTEIN) return kaamer_fail(KAAMER_E_ARG, "search_device: unknown sequence type %d", seq_type);
     if (nucl != ws->nucleotide) return kaamer_fail(KAAMER_E_ARG, "workspace was created for %s input", ws->nucleotide ? "nucleotide" : "protein");
     if (n_seqs > ws->max_seqs) return kaamer_fail(KAAMER_E_CAPACITY, "batch of %u sequences exceeds workspace max_seqs %u", n_seqs, ws->max_seqs);
@@ -2152,133 +2424,23 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
         ev = ws->ev->data() + (size_t)ws->n_timed * EV_PER_CALL;
         HIPCHK(hipEventRecord(ev[0], s));
     }
-    if (!ws->clean) {
-        // first batch, or a previous batch did not run to its finalize kernel
-        HIPCHK(hipMemsetAsync(ws->d_pool_cursor, 0, (size_t)3 * CURSOR_STRIDE * sizeof(unsigned long long), s));
-        HIPCHK(hipMemsetAsync(ws->d_list_counts, 0, N_SMALL_SLOTS * sizeof(uint32_t), s));
-        HIPCHK(hipMemsetAsync(ws->d_counter_replicas, 0, sizeof(unsigned long long) * CTR_REPLICAS * CTR_N, s));
-        HIPCHK(hipMemsetAsync(ws->d_valid, 0, (size_t)(ws->pos_cap / 64 + 2) * sizeof(unsigned long long), s));
+    {
+        const int rrc = ws_reset_if_dirty(ws, s);
+        if (rrc) return rrc;
+        ws->clean = false;
     }
-    ws->clean = false;
-
     uint32_t *status = ws->d_list_counts + SLOT_STATUS;
-    uint32_t *queue_head = ws->d_list_counts + SLOT_QUEUE_HEAD;
-    const int pb = 256;
-    const uint8_t *residues = d_seqs;   // what kernel P reads: the protein records, or the ORF amino acids
-    uint64_t pos_bound = seq_bytes;     // host-side bound of the residue positions (grid sizing only)
-    uint32_t nq_bound = n_seqs;         // host-side bound of the number of queries
+
+    // ---- queries: protein records (prep, table layout and group schedule in one launch), or ORFs and their table layout
+    QueryInput qin = { d_seqs, seq_bytes, n_seqs };
     if (!nucl) {
-        // prep + table layout + group schedule: one launch (count_group.hip.inc)
-        PrepLayoutParams pl;
-        memset(&pl, 0, sizeof pl);
-        pl.seqs = d_seqs; pl.pos_bound = seq_bytes; pl.offsets = d_offsets; pl.n_seqs = n_seqs;
-        pl.q = ws->d_q; pl.d_nq = ws->d_nq; pl.d_n_pos = ws->d_n_pos; pl.invalid = ws->d_valid; pl.qinfo = ws->d_qinfo;
-        pl.hit_off = ws->d_hit_off; pl.q_cnt = ws->d_q_cnt;
-        pl.E = ws->d_slot_off; pl.group_first = ws->d_group_first; pl.group_start = ws->d_group_start;
-        pl.d_n_groups = ws->d_n_groups; pl.groups_cap = ws->groups_cap; pl.chain = ws->d_chain;
-        ws->lay_epoch = (ws->lay_epoch + 1u) & 0xFFFFFFu;
-        if (ws->lay_epoch == 0) ws->lay_epoch = 1;
-        pl.epoch = ws->lay_epoch;
-        pl.status = status; pl.sched = ws->d_sched; pl.d_n_sched = ws->d_n_sched;
-        pl.tiles_done = ws->d_list_counts + SLOT_TILES_DONE;
-        pl.slots = ws->d_slots; pl.bshift = ws->pack_shift; pl.cshift = ws->pack_shift > GRP_SHIFT ? 10u : ws->pack_shift >= GRP_SHIFT ? 9u : 7u;
-        // the group kernel takes the groups longest first (measured with one workgroup per CU and three batches in flight:
-        // 0.1381-0.1406 ms per batch, 0.1430-0.1441 with the groups in index order)
-        pl.no_sched = 0u;
-        pl.d_total = ws->d_lay_total;
-        pl.slot_scale = ws->d_slot_scale;
-        pl.room_slots = ws->table_room;
-        const uint32_t tiles = (uint32_t)(((uint64_t)n_seqs + 1 + PL_TILE - 1) / PL_TILE);
-        hipLaunchKernelGGL(prep_layout_schedule_kernel, dim3(tiles), dim3(LAY_THREADS), 0, s, pl);
+        enqueue_protein_prep(ws, d_seqs, d_offsets, n_seqs, seq_bytes, status, s);
     } else {
-        // 6-frame translation: count, scan, write, order (translate.hip.inc)
-        const size_t cap6 = (size_t)ws->max_seqs * 6;
-        TranslateParams tp;
-        memset(&tp, 0, sizeof tp);
-        tp.seqs = d_seqs; tp.offsets = d_offsets; tp.n_seqs = n_seqs; tp.seq_bound = seq_bytes; tp.max_long = ws->max_long; tp.max_piece_items = ws->max_piece_items;
-        tp.cnt_orf = ws->d_cnt3; tp.cnt_aa = ws->d_cnt3 + cap6; tp.cnt_sa = ws->d_cnt3 + 2 * cap6;
-        tp.off_orf = ws->d_off3; tp.off_aa = ws->d_off3 + (cap6 + 1); tp.off_sa = ws->d_off3 + 2 * (cap6 + 1);
-        tp.tmp_meta = ws->d_tmp_meta; tp.orf_aa = ws->d_orf_aa; tp.starts_alt = ws->d_starts_alt;
-        tp.q_cap = ws->q_cap; tp.aa_cap = ws->aa_cap; tp.sa_cap = ws->sa_cap; tp.status = status;
-        // which lane-per-read kernel: the wide one (reads up to 384 nt, 2 waves per SIMD) when the batch's mean length says that
-        // reads beyond 192 nt are common; a batch of 100-150-nt reads is 4 % slower through it (translate.hip.inc)
-        const bool wide_reads = ws->wide_reads >= 0 ? ws->wide_reads != 0 : seq_bytes > 160ull * (n_seqs ? n_seqs : 1u);
-        tp.ts_max = wide_reads ? TS_MAX_WIDE : TS_MAX;
-        int tgrid = ws->n_cu * 8;  // 256-thread blocks, one (sequence, frame, piece) item per wave at a time
-        tp.d_n6 = ws->d_n6;
-        int sgrid = ws->n_cu * 8;  // lane-per-read kernel: 2-wave blocks, 13 KB (COUNT) / 30 KB (WRITE) of LDS each
-        if ((uint64_t)sgrid * TS_WAVES * 64 > (uint64_t)n_seqs) sgrid = n_seqs > 0 ? (int)(((uint64_t)n_seqs + TS_WAVES * 64 - 1) / (TS_WAVES * 64)) : 1;
-        tp.n_long = ws->d_list_counts + SLOT_N_LONG;
-        const size_t mpi = (size_t)ws->max_piece_items;
-        tp.long_seq = ws->d_long_seq; tp.long_np = ws->d_long_np; tp.piece_base = ws->d_piece_base; tp.piece_li = ws->d_piece_li;
-        tp.pcnt_orf = ws->d_pcnt3; tp.pcnt_aa = ws->d_pcnt3 + mpi; tp.pcnt_sa = ws->d_pcnt3 + 2 * mpi;
-        tp.poff_orf = ws->d_poff3; tp.poff_aa = ws->d_poff3 + (mpi + 1); tp.poff_sa = ws->d_poff3 + 2 * (mpi + 1);
-        tp.d_n_piece_items = ws->d_n_piece_items;
-        auto scan_u32 = [&](const uint32_t *cnt, const uint32_t *d_count, uint64_t bound, uint64_t *off) {
-            if (bound <= 8 * (uint64_t)SCAN_TILE) {
-                hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, cnt, d_count, off);
-            } else {
-                const uint32_t nsb = (uint32_t)((bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
-                hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, cnt, d_count, ws->d_bsum);
-                hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, ws->d_bsum, nsb);
-                hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(SCAN_BLOCK), 0, s, cnt, d_count, ws->d_bsum, off);
-            }
-        };
-        // reads: a lane each; longer sequences: listed, cut in pieces, a wave per piece
-        const uint64_t long_bound = (uint64_t)ws->max_long < n_seqs ? ws->max_long : n_seqs;
-        const uint64_t seq_long_max = seq_bytes / (TS_MAX + 1) + 1;
-        const uint64_t n_long_bound = long_bound < seq_long_max ? long_bound : seq_long_max;
-        const uint64_t piece_bound = 6ull * (seq_bytes / 3 / TP_PIECE + n_long_bound + 1);
-        if ((uint64_t)tgrid * 4 > piece_bound) tgrid = (int)((piece_bound + 3) / 4);
-        if (tgrid < 1) tgrid = 1;
-        tp.ticket = ws->d_list_counts + SLOT_TR_TICKET;
-        tp.chain = ws->d_tr_chain;
-        ws->tr_epoch = (ws->tr_epoch + 1u) & 0xFFFFFFu;
-        if (ws->tr_epoch == 0) ws->tr_epoch = 1;
-        tp.epoch = ws->tr_epoch;
-        tp.out_meta = ws->d_q; tp.d_nq = ws->d_nq; tp.d_n_pos = ws->d_n_pos;
-        tp.w_off_orf = ws->d_off3; tp.w_off_aa = ws->d_off3 + (cap6 + 1); tp.w_off_sa = ws->d_off3 + 2 * (cap6 + 1);
-        // long sequences first (listed, cut in pieces, counted: a wave per piece) -- a reads-only batch falls through
-        // these launches; then everything of the reads and the output offsets of both kinds in one kernel
-        hipLaunchKernelGGL(list_long_kernel, dim3((unsigned)(((uint64_t)n_seqs + LL_BLOCK - 1) / LL_BLOCK + (n_seqs ? 0 : 1))), dim3(LL_BLOCK), 0, s, tp);
-        scan_u32(ws->d_long_np, tp.n_long, n_long_bound, ws->d_piece_base);
-        hipLaunchKernelGGL(piece_li_kernel, dim3((unsigned)((n_long_bound + 255) / 256)), dim3(256), 0, s, tp);
-        hipLaunchKernelGGL(translate_kernel<false>, dim3(tgrid), dim3(256), 0, s, tp);
-        for (int a = 0; a < 3; a++) scan_u32(ws->d_pcnt3 + a * mpi, ws->d_n_piece_items, piece_bound, ws->d_poff3 + a * (mpi + 1));
-        hipLaunchKernelGGL(long_totals_kernel, dim3((unsigned)((n_long_bound * 6 + 255) / 256)), dim3(256), 0, s, tp);
-        if (wide_reads) hipLaunchKernelGGL(translate_reads_kernel<TS_MAX_WIDE>, dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
-        else hipLaunchKernelGGL(translate_reads_kernel<TS_MAX>, dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
-        hipLaunchKernelGGL(translate_kernel<true>, dim3(tgrid), dim3(256), 0, s, tp);
-        hipLaunchKernelGGL(orf_order_long_kernel, dim3((unsigned)(n_long_bound < (uint64_t)ws->n_cu * 32 ? (n_long_bound + 3) / 4 + 1 : (uint64_t)ws->n_cu * 8)), dim3(256), 0, s,
-                           ws->d_tmp_meta, tp.off_orf, ws->d_long_seq, tp.n_long, ws->d_q, ws->d_nq);
-        hipLaunchKernelGGL(prep_orf_kernel, dim3(ws->n_cu * 4), dim3(pb), 0, s, ws->d_q, ws->d_nq, ws->d_valid, ws->d_n_pos,
-                           ws->d_qinfo, ws->d_slots, ws->d_hit_off, ws->d_q_cnt, ws->d_slot_scale, ws->table_room);
-        residues = ws->d_orf_aa;
-        pos_bound = ws->aa_cap;
-        nq_bound = ws->q_cap;
+        qin = enqueue_translate(ws, d_seqs, d_offsets, n_seqs, seq_bytes, status, s);
+        launch_layout(ws, qin.nq_bound, status, s, ws->pack_shift, false);
     }
-
-    // ---- query groups: table layout, first query of each group, schedule (protein: done with the prep)
-    if (nucl) launch_layout(ws, nq_bound, status, s, ws->pack_shift, false);
-
-    // ---- kernel P: flat probe
-    ProbeParams pp;
-    pp.table = reinterpret_cast<const uint4 *>(ix->d_buckets);
-    pp.n_buckets = ix->hdr.n_buckets;
-    pp.n_shards = ix->hdr.n_shards;
-    pp.shard = ix->hdr.shard;
-    pp.residues = residues;
-    pp.invalid = ws->d_valid;
-    pp.d_n_pos = ws->d_n_pos;
-    pp.vals = ws->d_vals;
-    pp.counters = ws->d_counter_replicas;
-    pp.nontemporal = pos_bound < ix->hdr.n_buckets ? 1u : 0u;
-    uint64_t p_blocks = (pos_bound / 64 + 1 + P_WAVES - 1) / P_WAVES;
-    if (p_blocks > (uint64_t)ws->p_grid) p_blocks = ws->p_grid;
-    if (p_blocks < 1) p_blocks = 1;
     if (timed) HIPCHK(hipEventRecord(ev[1], s));
-    if (ws->nucleotide) hipLaunchKernelGGL(probe_kernel<true>, dim3((unsigned)p_blocks), dim3(64 * P_WAVES), 0, s, pp);
-    else hipLaunchKernelGGL(probe_kernel<false>, dim3((unsigned)p_blocks), dim3(64 * P_WAVES), 0, s, pp);
+    enqueue_probe(ix, ws, qin.residues, qin.pos_bound, s);
     if (timed) HIPCHK(hipEventRecord(ev[2], s));
     const bool split = ws->count_stream && ws->count_stream != s && !timed;
     if (split) {   // everything from here on runs on the count stream, behind the probe kernel
@@ -2286,99 +2448,10 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
         HIPCHK(hipStreamWaitEvent(ws->count_stream, ws->ev_probe, 0));
         s = ws->count_stream;
     }
-    // ---- kernel C: counting
-    CountParams p;
-    memset(&p, 0, sizeof p);
-    p.arena = ix->d_arena;
-    p.vals = ws->d_vals;
-    p.qinfo = ws->d_qinfo;
-    p.slot_off = ws->d_slot_off;
-    p.group_first = ws->d_group_first;
-    p.sched = ws->d_sched;
-    p.d_n_sched = ws->d_n_sched;
-    p.d_n_groups = ws->d_n_groups;
-    p.d_nq = ws->d_nq;
-    p.list_cap = ws->q_cap;
-    p.queue_head = queue_head;
-    p.group_queue = ws->d_list_counts + SLOT_GROUP_QUEUE;
-    p.hit_off = ws->d_hit_off;
-    p.q_cnt = ws->d_q_cnt;
-    p.hit_pid = ws->d_hit_pid;
-    p.hit_km = ws->d_hit_km;
-    p.hit_fp = ws->d_hit_fp;
-    p.hit_cap = ws->sparse_cap;
-    p.tail_cursor = ws->d_pool_cursor;
-    p.g_keys = ws->d_g_keys;
-    p.g_slots = ws->g_slots;
-    p.g_cursor = ws->d_pool_cursor + CURSOR_STRIDE;
-    p.n_proteins = ix->hdr.max_protein_id + 1u ? ix->hdr.max_protein_id + 1u : 0xFFFFFFFFu;
-    p.counters = ws->d_counter_replicas;
-    p.status = status;
-    auto list_ptr = [&](int which) { return ws->d_lists + (size_t)which * ws->q_cap; };
-
-    CountParams pc = p;
-    pc.ovf_list = list_ptr(LIST_G); pc.ovf_count = ws->d_list_counts + LIST_G;
-    pc.last_group_pass = ws->want_positions ? 0u : 1u;
-    pc.pack_shift = ws->pack_shift;
-    pc.pack_tickets = ws->d_list_counts + SLOT_PACK_TICKETS;
-    if (!nucl) {
-        uint64_t gg = ((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) / GRP_BUDGET + 1;
-        if (gg > (uint64_t)ws->grp_grid) gg = ws->grp_grid;
-        launch_group(pc, (int)gg, ws->firstpos, s);
-    } else {
-        // one wave per workgroup, packs dealt out statically: never more waves than packs
-        uint64_t gb = (((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) >> ws->pack_shift) + 1;
-        if (gb > (uint64_t)ws->pack_grid) gb = ws->pack_grid;
-        // reads of ~150 nt: ORFs of <= 50 residues, tables of 64-128 slots -> the small arena (20 waves per CU);
-        // longer sequences (mixed read lengths, contigs): the arena that holds tables of up to 576 slots, or 66 000
-        // ORFs of a 1 M mixed-read batch went to the G tier (measured: 8.19 -> 6.73 ms for the counting stage of
-        // that batch, while the 150-nt batch loses 0.4 ms with the larger arena)
-        const bool long_orfs = seq_bytes > 200ull * (n_seqs ? n_seqs : 1u) || ws->dense_tables;
-        if (long_orfs) {
-            if (gb > (uint64_t)ws->pack_grid_long) gb = ws->pack_grid_long;
-            hipLaunchKernelGGL((count_pack_kernel<PK_ARENA_ORF_LONG>), dim3((unsigned)gb), dim3(64), 0, s, pc);
-        } else {
-            hipLaunchKernelGGL((count_pack_kernel<PK_ARENA_ORF>), dim3((unsigned)gb), dim3(64), 0, s, pc);
-        }
-    }
-    CountParams pg = p;
-    pg.list = list_ptr(LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
-    int g_grid = ws->g_grid;
-    if ((uint32_t)g_grid > nq_bound) g_grid = nq_bound > 0 ? (int)nq_bound : 1;
-    const bool fused_finalize = !ws->compact && !ws->want_positions;
-    if (fused_finalize) {
-        pg.fin_out = ws->d_counters; pg.fin_small = ws->d_list_counts; pg.fin_status_out = ws->d_status_out;
-        pg.fin_cursors = ws->d_pool_cursor;
-        pg.fin_slot_scale = ws->d_slot_scale; pg.fin_scale_cap = ws->slot_scale_cap; pg.fin_scale_margin = ws->slot_scale_margin;
-    }
-    hipLaunchKernelGGL(count_global_kernel, dim3(g_grid), dim3(64 * G_WAVES), 0, s, pg);
-    if (ws->compact) launch_compaction(ws, nq_bound, status, s);
+    enqueue_count(ix, ws, nucl, seq_bytes, n_seqs, qin.nq_bound, qin.pos_bound, s);
     if (timed) HIPCHK(hipEventRecord(ev[3], s));
-
-    if (ws->want_positions) {
-        // PositionHits bitmaps (search.go:442-452): layout from the final hit lists, then one more
-        // pass of the group kernel that sets one bit per (hit, position)
-        launch_pos_layout(ws, nq_bound, nullptr, status, s);
-        // the PositionHits pass runs on the group kernel: lay the tables out in its groups
-        launch_layout(ws, nq_bound, status, s, GRP_SHIFT);
-        uint64_t grp_blocks = ((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * pos_bound) / GRP_BUDGET + 1;
-        if (grp_blocks > (uint64_t)ws->grp_grid) grp_blocks = ws->grp_grid;
-        CountParams pp2 = p;
-        pp2.pack_shift = GRP_SHIFT;   // (the layout just above)
-        pp2.last_group_pass = 1u;
-        pp2.pos_base = ws->d_pos_base;
-        pp2.pos_bits = ws->d_pos_bits;
-        pp2.group_queue = ws->d_list_counts + SLOT_GROUP_QUEUE_POS;
-        pp2.ovf_list = list_ptr(LIST_SO); pp2.ovf_count = ws->d_list_counts + LIST_SO;
-        launch_group_positions(pp2, (int)grp_blocks, s);
-        CountParams pg2 = pg;   // the G tier's queries: their hit lists are final, the counting arena is free again
-        pg2.fin_out = nullptr;
-        pg2.pos_base = ws->d_pos_base;
-        pg2.pos_bits = ws->d_pos_bits;
-        pg2.g_cursor = ws->d_pool_cursor + 2 * CURSOR_STRIDE;
-        hipLaunchKernelGGL(positions_global_kernel, dim3(g_grid), dim3(64 * G_WAVES), 0, s, pg2);
-    }
-    if (!fused_finalize)
+    if (ws->want_positions) enqueue_positions(ix, ws, qin.nq_bound, qin.pos_bound, s);
+    if (!fused_finalize(ws))
         hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, ws->d_counter_replicas, ws->d_counters, ws->d_list_counts,
                            ws->d_status_out, ws->d_pool_cursor, ws->d_slot_scale, ws->slot_scale_cap, ws->slot_scale_margin);
     if (timed) HIPCHK(hipEventRecord(ev[4], s));
@@ -2417,13 +2490,11 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
     if (n_entries > ws->hit_cap) return kaamer_fail(KAAMER_E_CAPACITY, "merge of %llu entries exceeds workspace max_hits", (unsigned long long)n_entries);
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ws->device));
-    if (!ws->clean) {
-        HIPCHK(hipMemsetAsync(ws->d_pool_cursor, 0, (size_t)3 * CURSOR_STRIDE * sizeof(unsigned long long), s));
-        HIPCHK(hipMemsetAsync(ws->d_list_counts, 0, N_SMALL_SLOTS * sizeof(uint32_t), s));
-        HIPCHK(hipMemsetAsync(ws->d_counter_replicas, 0, sizeof(unsigned long long) * CTR_REPLICAS * CTR_N, s));
-        HIPCHK(hipMemsetAsync(ws->d_valid, 0, (size_t)(ws->pos_cap / 64 + 2) * sizeof(unsigned long long), s));
+    {
+        const int rrc = ws_reset_if_dirty(ws, s);
+        if (rrc) return rrc;
+        ws->clean = false;
     }
-    ws->clean = false;
     uint32_t *status = ws->d_list_counts + SLOT_STATUS;
     const uint32_t nq_bound = n_queries;
     const int pb = 256;
@@ -2431,42 +2502,15 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
                        n_queries, d_n_queries, ws->d_qinfo, ws->d_slots, ws->d_nq, ws->d_hit_off, ws->d_q_cnt);
     // (the merge runs on count_group_kernel<., 2>: units of two group windows, as the search of protein batches)
     launch_layout(ws, nq_bound, status, s, GRP_SHIFT + 1u);
-    CountParams p;
-    memset(&p, 0, sizeof p);
-    p.qinfo = ws->d_qinfo;
-    p.slot_off = ws->d_slot_off;
-    p.group_first = ws->d_group_first;
-    p.sched = ws->d_sched;
-    p.d_n_sched = ws->d_n_sched;
-    p.d_n_groups = ws->d_n_groups;
-    p.d_nq = ws->d_nq;
+    CountParams p = count_params_base(ws);
     p.last_group_pass = 1u;
     p.pack_shift = GRP_SHIFT + 1u;
-    p.group_queue = ws->d_list_counts + SLOT_GROUP_QUEUE;
     p.m_pid = d_pid; p.m_km = d_km; p.m_fp = d_fp; p.merge_fp = ws->firstpos ? 1u : 0u;
-    p.list_cap = ws->q_cap;
-    p.hit_off = ws->d_hit_off;
-    p.q_cnt = ws->d_q_cnt;
-    p.hit_pid = ws->d_hit_pid; p.hit_km = ws->d_hit_km; p.hit_fp = ws->d_hit_fp;
-    p.hit_cap = ws->sparse_cap;
-    p.tail_cursor = ws->d_pool_cursor;
-    p.g_keys = ws->d_g_keys;
-    p.g_slots = ws->g_slots;
-    p.g_cursor = ws->d_pool_cursor + CURSOR_STRIDE;
-    p.counters = ws->d_counter_replicas;
-    p.status = status;
-    auto list_ptr = [&](int which) { return ws->d_lists + (size_t)which * ws->q_cap; };
-    p.ovf_list = list_ptr(LIST_G); p.ovf_count = ws->d_list_counts + LIST_G;
-    {
-        uint64_t gb = ((uint64_t)GRP_MIN_TABLE * nq_bound + 3 * n_entries) / GRP_BUDGET + 1;
-        if (gb > (uint64_t)ws->grp_grid) gb = ws->grp_grid;
-        launch_group_merge(p, (int)gb, ws->firstpos, s);
-    }
+    p.ovf_list = ws_list(ws, LIST_G); p.ovf_count = ws->d_list_counts + LIST_G;
+    launch_group_merge(p, group_grid(ws, nq_bound, n_entries), ws->firstpos, s);
     CountParams pg = p;
-    pg.list = list_ptr(LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
-    int g_grid = ws->g_grid;
-    if ((uint32_t)g_grid > nq_bound) g_grid = nq_bound > 0 ? (int)nq_bound : 1;
-    hipLaunchKernelGGL(merge_global_kernel, dim3(g_grid), dim3(256), 0, s, pg);
+    pg.list = ws_list(ws, LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
+    hipLaunchKernelGGL(merge_global_kernel, dim3(g_tier_grid(ws, nq_bound)), dim3(256), 0, s, pg);
     if (ws->compact) launch_compaction(ws, nq_bound, status, s);
     if (xpos) {
         launch_pos_layout(ws, nq_bound, xpos->m_size, status, s);
@@ -2722,11 +2766,9 @@ int kaamer_exchange_merge(kaamer_workspace *ws, const kaamer_exchange_layout *L,
         for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&ws->ev_x_stats[i], hipEventDisableTiming));
     }
     hipStream_t s = (hipStream_t)stream;
-    if (!ws->clean) {  // the status word the unpack kernels may set must start from zero
-        HIPCHK(hipMemsetAsync(ws->d_pool_cursor, 0, (size_t)3 * CURSOR_STRIDE * sizeof(unsigned long long), s));
-        HIPCHK(hipMemsetAsync(ws->d_list_counts, 0, N_SMALL_SLOTS * sizeof(uint32_t), s));
-        HIPCHK(hipMemsetAsync(ws->d_counter_replicas, 0, sizeof(unsigned long long) * CTR_REPLICAS * CTR_N, s));
-        HIPCHK(hipMemsetAsync(ws->d_valid, 0, (size_t)(ws->pos_cap / 64 + 2) * sizeof(unsigned long long), s));
+    {   // the status word the unpack kernels may set must start from zero
+        const int rrc = ws_reset_if_dirty(ws, s);
+        if (rrc) return rrc;
         ws->clean = true;
     }
     XParams x;
@@ -3115,22 +3157,21 @@ static int host_slot_acquire(kaamer_index *ix, HostSlot &h, const kaamer_workspa
 }
 
 // host buffers -> device, search enqueued on the slot's stream; nothing is waited for
-static int search_batch_enqueue(kaamer_index *ix, HostSlot &slot, const kaamer_batch_in *in, uint64_t max_hits, uint64_t g_slots,
-                                uint32_t max_queries, kaamer_device_result *dr)
+static int search_batch_enqueue(kaamer_index *ix, HostSlot &slot, const kaamer_batch_in *in, const BatchBounds &b, kaamer_device_result *dr)
 {
     const uint64_t seq_bytes = in->offsets[in->n_seqs];
     kaamer_workspace_opts o;
     memset(&o, 0, sizeof o);
     o.max_seq_bytes = seq_bytes;
     o.max_seqs = in->n_seqs ? in->n_seqs : 1;
-    o.max_hits = max_hits;
-    o.g_tier_slots = g_slots;
+    o.max_hits = b.max_hits;
+    o.g_tier_slots = b.g_slots;
     o.seq_type = in->seq_type;
     o.first_pos = 1;  // kaamer_batch_out always carries hit_first_pos
     o.want_positions = in->want_positions ? 1u : 0u;
     o.compact = 1u;  // the host form is CSR
-    o.max_pos_words = max_hits * 8;
-    o.max_queries = max_queries;
+    o.max_pos_words = b.max_hits * 8;
+    o.max_queries = b.max_queries;
     int rc = host_slot_acquire(ix, slot, o, seq_bytes, in->n_seqs);
     if (rc) return rc;
     if (!slot.stream) HIPCHK(hipStreamCreateWithFlags(&slot.stream, hipStreamNonBlocking));
@@ -3211,11 +3252,10 @@ done:
     return rc;
 }
 
-static int search_batch_once(kaamer_index *ix, HostSlot &slot, const kaamer_batch_in *in, uint64_t max_hits, uint64_t g_slots,
-                             uint32_t max_queries, kaamer_batch_out **out)
+static int search_batch_once(kaamer_index *ix, HostSlot &slot, const kaamer_batch_in *in, const BatchBounds &b, kaamer_batch_out **out)
 {
     kaamer_device_result dr;
-    const int rc = search_batch_enqueue(ix, slot, in, max_hits, g_slots, max_queries, &dr);
+    const int rc = search_batch_enqueue(ix, slot, in, b, &dr);
     if (rc) return rc;
     return search_batch_collect(slot, in, dr, out);
 }
@@ -3230,11 +3270,11 @@ struct kaamer_full_ticket {
     std::vector<uint64_t> *offs;
     kaamer_batch_in in;
     kaamer_device_result dr;
-    uint64_t max_hits, g_slots;
-    uint32_t max_queries;
+    BatchBounds b;
     int attempt;
 };
 
+// a free slot (one whose workspace already serves this kind of batch, if there is one); callers beyond the slots wait
 static HostSlot *host_slot_take(kaamer_index *ix, int32_t seq_type)
 {
     HostSlot *slot = nullptr;
@@ -3270,9 +3310,9 @@ int kaamer_submit_batch_flat(kaamer_index *ix, const uint8_t *seqs, const uint64
     if (!t->seqs || !t->offs) { delete t->seqs; delete t->offs; delete t; return kaamer_fail(KAAMER_E_NOMEM, "ticket"); }
     t->in.seqs = t->seqs->data(); t->in.offsets = t->offs->data(); t->in.n_seqs = n_seqs; t->in.seq_type = seq_type;
     t->in.want_positions = want_positions;
-    t->max_hits = offsets[n_seqs] * 8 + 65536;
+    t->b.max_hits = full_start_hits(offsets[n_seqs]);
     t->slot = host_slot_take(ix, seq_type);
-    const int rc = search_batch_enqueue(ix, *t->slot, &t->in, t->max_hits, t->g_slots, t->max_queries, &t->dr);
+    const int rc = search_batch_enqueue(ix, *t->slot, &t->in, t->b, &t->dr);
     if (rc && rc != KAAMER_E_CAPACITY) {
         if (t->slot->stream) (void)hipStreamSynchronize(t->slot->stream);
         host_slot_give(ix, t->slot);
@@ -3290,19 +3330,13 @@ int kaamer_wait_batch(kaamer_full_ticket *t, kaamer_batch_out **out)
     *out = nullptr;
     kaamer_index *ix = t->ix;
     int rc = hipSetDevice(ix->device) == hipSuccess ? KAAMER_OK : kaamer_fail(KAAMER_E_HIP, "hipSetDevice");
-    const bool nucl = t->in.seq_type == KAAMER_NUCLEOTIDE || t->in.seq_type == KAAMER_READS;
     while (!rc) {
         rc = t->attempt < 0 ? KAAMER_E_CAPACITY : search_batch_collect(*t->slot, &t->in, t->dr, out);
         if (t->attempt < 0) t->attempt = 0;
-        if (rc != KAAMER_E_CAPACITY || t->attempt >= 6) break;
+        if (rc != KAAMER_E_CAPACITY || t->attempt >= MAX_BOUND_RETRIES) break;
         t->attempt++;
-        t->max_hits *= 4;
-        t->g_slots = t->g_slots ? t->g_slots * 4 : (128ull << 20);
-        if (nucl) {
-            const uint64_t hard = t->in.offsets[t->in.n_seqs] / 10 + (uint64_t)t->in.n_seqs * 6 + 64;
-            t->max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
-        }
-        rc = search_batch_enqueue(ix, *t->slot, &t->in, t->max_hits, t->g_slots, t->max_queries, &t->dr);
+        bounds_grow(t->b, t->in.offsets[t->in.n_seqs], t->in.n_seqs, is_nucl(t->in.seq_type));
+        rc = search_batch_enqueue(ix, *t->slot, &t->in, t->b, &t->dr);   // (an error here, E_CAPACITY included, ends the loop: kept as it was)
     }
     if (rc && t->slot->stream) (void)hipStreamSynchronize(t->slot->stream);
     host_slot_give(ix, t->slot);
@@ -3325,36 +3359,16 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
     if (!ix || !in || !out || !in->offsets || (in->n_seqs && !in->seqs)) return kaamer_fail(KAAMER_E_ARG, "search_batch: bad argument");
     *out = nullptr;
     HIPCHK(hipSetDevice(ix->device));
-    // a free slot (one whose workspace already serves this kind of batch, if there is one); callers beyond the slots wait
-    HostSlot *slot = nullptr;
-    {
-        std::unique_lock<std::mutex> lock(ix->pool_mu);
-        for (;;) {
-            for (HostSlot &h : ix->host)
-                if (!h.busy && (!slot || (h.ws && h.opts.seq_type == in->seq_type && !(slot->ws && slot->opts.seq_type == in->seq_type)))) slot = &h;
-            if (slot) break;
-            ix->pool_cv.wait(lock);
-        }
-        slot->busy = true;
-    }
+    HostSlot *slot = host_slot_take(ix, in->seq_type);
     struct Release {
         kaamer_index *ix; HostSlot *h;
-        ~Release() { { std::lock_guard<std::mutex> lock(ix->pool_mu); h->busy = false; } ix->pool_cv.notify_all(); }
+        ~Release() { host_slot_give(ix, h); }
     } release{ ix, slot };
-    // The hit count of a batch is data dependent: start from a generous estimate and
-    // enlarge on KAAMER_E_CAPACITY (the device reports it; results are never partial).
-    uint64_t max_hits = in->offsets[in->n_seqs] * 8 + 65536, g_slots = 0;
-    uint32_t max_queries = 0;
-    const bool nucl = in->seq_type == KAAMER_NUCLEOTIDE || in->seq_type == KAAMER_READS;
+    BatchBounds b = { full_start_hits(in->offsets[in->n_seqs]), 0, 0 };
     for (int attempt = 0;; attempt++) {
-        const int rc = search_batch_once(ix, *slot, in, max_hits, g_slots, max_queries, out);
-        if (rc != KAAMER_E_CAPACITY || attempt >= 6) return rc;
-        max_hits *= 4;
-        g_slots = g_slots ? g_slots * 4 : (128ull << 20);
-        if (nucl) {  // hard bound: a frame of n codons holds at most n/21 + 1 ORFs
-            const uint64_t hard = in->offsets[in->n_seqs] / 10 + (uint64_t)in->n_seqs * 6 + 64;
-            max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
-        }
+        const int rc = search_batch_once(ix, *slot, in, b, out);
+        if (rc != KAAMER_E_CAPACITY || attempt >= MAX_BOUND_RETRIES) return rc;
+        bounds_grow(b, in->offsets[in->n_seqs], in->n_seqs, is_nucl(in->seq_type));
     }
 }
 

@@ -207,6 +207,46 @@ def test_sharded_positions_growth_and_alternation(klib, oracle, gpu_device):
 
 
 @pytest.mark.gpu
+def test_sharded_calls_grow_their_bounds(klib, oracle, gpu_device):
+    """a skewed database (the one of test_zipf_database_parity): a query has thousands of hits, far more than the
+    exchange blocks and hit arrays of a first call hold, so the first top call and the first full call on a fresh handle
+    (nothing to size the blocks from: not adaptive) each repeat their batch with every bound grown.  Reported hits and
+    full hit lists equal the unsharded calls', and a sample the oracle's."""
+    from kaamer_amd import api, workload
+    db = workload.make_db_zipf(40000, seed=11, n_motifs=1500, zipf_a=1.0, per_residues=60)
+    oix = oracle.Index.from_proteins(None, packed=db)
+    q = workload.make_protein_queries(db, 200, seed=12)
+    seqs = workload.unpack(q)
+    ix1 = api.Index.from_image(api.Image.from_proteins(packed=db), gpu_device)
+    ref_top = ix1.search_top(packed=q)
+    ref_full = ix1.search(packed=q)
+    images = [api.Image.from_proteins(packed=db, shard=r, n_shards=2) for r in range(2)]
+    sx = api.ShardedIndex.from_images(images, [gpu_device] * 2)
+    e_cap = 2 * len(q[0]) // 2 + 65536      # entries per (shard -> owner) block of a first attempt
+    top = sx.search_top(packed=q)
+    assert not sx.exchange_info()["adaptive"] and sx.exchange_info()["need_entries"] > e_cap
+    for f in ("rep_query", "top_off", "top_pid", "top_kmatch"):
+        assert getattr(top, f).tolist() == getattr(ref_top, f).tolist(), f
+    sx.close()
+    sx = api.ShardedIndex.from_images(images, [gpu_device] * 2)
+    full = sx.search(packed=q)
+    assert not sx.exchange_info()["adaptive"] and sx.exchange_info()["need_entries"] > e_cap
+    _check_full(full, ref_full, False)
+    sx.close()
+    tp, tk = top.dense()
+    for i in range(0, len(seqs), 5):
+        s = seqs[i]
+        exp, keep = {}, 0
+        if oracle.size_in_kmer(s) >= 7:
+            pid, km, _ = oix.search(s)
+            exp = dict(zip(pid.tolist(), km.tolist()))
+            keep = oracle.filter_results(km, oracle.size_in_kmer(s)) if len(km) else 0
+            assert tp[i, :keep].tolist() == pid[:keep].tolist() and tk[i, :keep].tolist() == km[:keep].tolist(), i
+        assert int(top.top_cnt[i]) == keep, i
+        assert full.hits(i) == exp, i
+
+
+@pytest.mark.gpu
 def test_protein_search_driver_on_sharded_index(klib, oracle, gpu_device):
     from kaamer_amd import api, search, workload
     db = workload.make_db(600, seed=6)

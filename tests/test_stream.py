@@ -331,3 +331,29 @@ def test_full_hit_lists_in_two_halves(klib, oracle, gpu_device):
             p_, k_, _ = oix.search(seqs[i])
             exp = dict(zip(p_.tolist(), k_.tolist()))
         assert got[0].hits(i) == exp
+
+
+@pytest.mark.gpu
+def test_full_hit_lists_in_two_halves_grow_their_bounds(klib, oracle, gpu_device):
+    """a skewed database (the one of test_zipf_database_parity): a query has thousands of hits, so the bounds a full-list
+    call starts from (8 hits per input byte) are too small and kaamer_wait_batch repeats the batch with grown bounds
+    from its copy of the input; every {protein id -> Kmatch} and first position vs the oracle"""
+    from kaamer_amd import api, workload
+    db = workload.make_db_zipf(40000, seed=11, n_motifs=1500, zipf_a=1.0, per_residues=60)
+    ix = api.Index.from_image(api.Image.from_proteins(packed=db), gpu_device)
+    oix = oracle.Index.from_proteins(None, packed=db)
+    q = workload.make_protein_queries(db, 200, seed=12)
+    seqs = workload.unpack(q)
+    res = ix.submit(packed=q).wait()
+    assert res.n_queries == len(seqs)
+    # more than the first attempt's hit arrays hold (a fresh slot's workspace: the bound plus a quarter of headroom)
+    assert res.counters["n_hits"] > (8 * len(q[0]) + 65536) * 5 // 4
+    for i, s in enumerate(seqs):
+        exp, fp = {}, {}
+        if oracle.size_in_kmer(s) >= 7:
+            pid, km, pos = oix.search(s, want_positions=True)
+            exp = dict(zip(pid.tolist(), km.tolist()))
+            fp = {int(p): int(np.argmax(pos[j])) for j, p in enumerate(pid)}
+        assert res.hits(i) == exp, "query %d" % i
+        assert res.first_pos(i) == fp, "query %d" % i
+
