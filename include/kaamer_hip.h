@@ -411,6 +411,31 @@ typedef struct {
 
 int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void *stream,
                        kaamer_topn_result *out);
+/* PositionHits (search.go:442-452) of the hits kaamer_topn_device kept, and of those only: the reference fills a bitmap
+ * for every hit of a query and prints them for the at most MaxResults hits it reports (search.go:520-522,540-543,
+ * 591-594).  Enqueued on `stream` behind kaamer_topn_device (`top` is its result; on the count stream when the
+ * workspace's counting stage runs there, like kaamer_topn_device itself).  For every query q with d_top_cnt[q] > 0 and
+ * every kept hit r < d_top_cnt[q]:
+ *     words_q = ceil(d_pos_bits_len[q] / 64) u64 words at d_pos_bits + d_pos_base[q] + r * words_q,
+ *     bit pos set iff d_top_pid[q * max_results + r] is in index[key(pos)], pos in [0, d_pos_bits_len[q]);
+ * d_pos_bits_len[q] is the query's SizeInKmer AS SEARCHED -- for an ORF the untrimmed one: the reference stores the
+ * positions before SetBestStartCodon and never re-bases them (search_fastq.go:94-123, dna.go:252-270), exactly as
+ * d_top_first_pos is relative to the untrimmed ORF -- and 0 for a query that reports nothing (no words either);
+ * d_pos_base[n_queries] is the total.
+ * max_pos_words: u64 words of bitmap storage (allocated on first use, grow-only); 0 = (residue positions of the
+ * workspace / 64 + max_queries) x f, f = min(max_results, 16) for protein and 1 for nucleotide / reads workspaces: room
+ * for every query to report f hits.  A batch that needs more is reported as KAAMER_E_CAPACITY by
+ * kaamer_workspace_finish, never a partial result.  KAAMER_E_ARG when the workspace's last result is a merge
+ * (kaamer_merge_device / kaamer_exchange_merge): the probe results the bitmaps are read from live on the shards. */
+typedef struct {
+    const uint64_t *d_pos_base;       /* [n_queries + 1] first word of each query's bitmaps */
+    const int32_t *d_pos_bits_len;    /* [n_queries] bits per bitmap                        */
+    const uint64_t *d_pos_bits;
+    uint64_t pos_words_capacity;      /* the bound this call ran with                       */
+} kaamer_topn_positions;
+int kaamer_topn_positions_device(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *top, uint64_t max_pos_words,
+                                 void *stream, kaamer_topn_positions *out);
+
 /* Host-buffer call that returns what the reference's drivers report
  * (search_protein.go:105-112, search_fastq.go:118-126): the queries FilterResults left
  * with at least one hit, their hits in sortMapByValue order, after SetBestStartCodon
@@ -465,6 +490,31 @@ int kaamer_submit_batch_top_flat(kaamer_index *ix, const uint8_t *seqs, const ui
                                  int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
                                  kaamer_ticket **ticket);
 
+/* The same calls for a request with ExtractPositions (-pos; nucleotide / reads requests always, search.go:416): the
+ * PositionHits bitmaps of the REPORTED hits (what FormatPositionsToString is called on, search.go:520-522,540-543,
+ * 591-594) ride in the same packed block, so a call still costs one device-to-host copy and at most max_results
+ * bitmaps per query cross PCIe instead of one per (query, protein) hit (kaamer_search_batch_flat with want_positions).
+ * Arguments and result as the forms above; a ticket is waited for with kaamer_wait_batch_top or dropped with
+ * kaamer_ticket_discard.  The bitmap storage is a bound like every other (kaamer_topn_positions_device states the
+ * rule): a batch beyond it is repeated with a larger one inside the call. */
+int kaamer_search_batch_top_pos_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                     int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                     kaamer_batch_top **out);
+int kaamer_submit_batch_top_pos_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                     int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                     kaamer_ticket **ticket);
+/* The bitmaps of a result (kaamer_batch_top itself is unchanged): reported query i has pos_bits_len[i] bits per bitmap --
+ * its SizeInKmer as searched, for an ORF the untrimmed one (q[i].size_in_kmer is the trimmed one; top_first_pos is
+ * relative to the same untrimmed ORF) -- and entry e of the CSR arrays (top_pid[e], ...) has its
+ * ceil(pos_bits_len[i] / 64) words at pos_bits + pos_off[e]; pos_off has top_off[n_reported] + 1 entries, the last one
+ * the total.  All three are NULL for a result that was not asked for positions (every result of the sharded handle
+ * included); they live as long as the result does. */
+int kaamer_batch_top_positions(const kaamer_batch_top *out, const int32_t **pos_bits_len, const uint64_t **pos_off,
+                               const uint64_t **pos_bits);
+/* The FIRST bitmap bound (u64 words) of the host calls above on this index, for callers who know how densely their
+ * batches report; 0 (default): the rule.  A batch beyond it is repeated with the rule's bound. */
+int kaamer_index_set_top_positions_bound(kaamer_index *ix, uint64_t words);
+
 /* Streaming (BASELINE configs[4]: reads streamed host -> GPU with double-buffered copies): a FIFO of batches with
  * fixed options.  push copies chunk i + 1 and starts it while chunk i is still being searched; pop returns the
  * oldest chunk's reported hits.  push returns KAAMER_E_BUSY instead of blocking when every slot holds one of this
@@ -473,6 +523,9 @@ typedef struct kaamer_stream kaamer_stream;
 int kaamer_stream_open(kaamer_index *ix, int32_t seq_type, const kaamer_topn_opts *top, kaamer_stream **out);
 int kaamer_stream_open_flat(kaamer_index *ix, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                             uint32_t max_results, kaamer_stream **out);
+/* a stream whose results carry the bitmaps of the reported hits (kaamer_batch_top_positions); push / pop / close as above */
+int kaamer_stream_open_pos_flat(kaamer_index *ix, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                uint32_t max_results, kaamer_stream **out);
 int kaamer_stream_push(kaamer_stream *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs);
 int kaamer_stream_pop(kaamer_stream *st, kaamer_batch_top **out);
 uint32_t kaamer_stream_pending(const kaamer_stream *st);
@@ -693,6 +746,14 @@ int64_t kaamer_filter_results(const uint32_t *kmatch_sorted, int64_t n_hits, int
 /* sortMapByValue, search.go:132-152: order hit indices by Kmatch descending;
  * ties (nondeterministic in the reference) are broken by ascending protein id. */
 void kaamer_sort_hits(const uint32_t *pid, const uint32_t *kmatch, int64_t n_hits, uint32_t *order);
+/* FormatPositionsToString, search.go:694-742, byte for byte, on one bitmap of n_bits positions (bit pos of word
+ * pos / 64): the maximal runs of set positions as "start-end", comma separated, 1-based, where end is ONE PAST the run's
+ * last set position (the reference closes a run at the first unset position and prints that position's number), or
+ * n_bits for a run that reaches the end; with_alignment adds KAAMER_KMER_SIZE - 1 to every end (the residues the last
+ * k-mer covers).  Writes at most cap bytes into buf, NUL-terminated when cap > 0, and returns the length of the whole
+ * string without the NUL: a return >= cap means buf was too short.  buf may be NULL with cap 0.  (The TSV writer's hit
+ * count, strings.Count(posString, ","), is derived from the string by the caller.) */
+uint64_t kaamer_format_positions(const uint64_t *bits, int32_t n_bits, int32_t with_alignment, char *buf, uint64_t cap);
 
 /* SetBestStartCodon, dna.go:198-272: hits in sortMapByValue order with their first
  * matching positions; trims the ORF to the start codon preceding the first best-hit

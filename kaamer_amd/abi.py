@@ -115,6 +115,11 @@ class TopnResult(C.Structure):
                 ("d_start_position", C.c_void_p), ("d_size_in_kmer", C.c_void_p)]
 
 
+class TopnPositions(C.Structure):
+    _fields_ = [("d_pos_base", C.c_void_p), ("d_pos_bits_len", C.c_void_p), ("d_pos_bits", C.c_void_p),
+                ("pos_words_capacity", C.c_uint64)]
+
+
 # every symbol include/kaamer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "kaamer_last_error": (C.c_char_p, []),
@@ -266,6 +271,18 @@ SYMBOLS = {
     "kaamer_reader_done": (C.c_int, [C.c_void_p]),
     "kaamer_reader_records": (C.c_uint64, [C.c_void_p]),
     "kaamer_reader_close": (None, [C.c_void_p]),
+    # PositionHits bitmaps of the reported hits on the top-N calls
+    "kaamer_topn_positions_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TopnResult), C.c_uint64, C.c_void_p,
+                                               C.POINTER(TopnPositions)]),
+    "kaamer_search_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
+                                                   C.c_int64, C.c_uint32, C.c_void_p]),
+    "kaamer_submit_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
+                                                   C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_stream_open_pos_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_batch_top_positions": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint64)),
+                                             C.POINTER(C.POINTER(C.c_uint64))]),
+    "kaamer_index_set_top_positions_bound": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "kaamer_format_positions": (C.c_uint64, [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
 }
 
 _lib = None

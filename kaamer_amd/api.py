@@ -229,6 +229,29 @@ class TopResult:
         self.top_cnt = np.zeros(n, np.uint32)
         if r:
             self.top_cnt[self.rep_query] = np.diff(self.top_off.astype(np.int64)).astype(np.uint32)
+        # PositionHits of the reported hits (kaamer_batch_top_positions): None unless the call asked for them
+        self.pos_bits_len = self.pos_off = self.pos_bits = None
+        pl, po, pb = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        abi.check(abi.lib().kaamer_batch_top_positions(out, C.byref(pl), C.byref(po), C.byref(pb)))
+        if bool(po) and bool(pb):
+            self.pos_bits_len = np.ctypeslib.as_array(pl, shape=(r,)).copy() if r else np.zeros(0, np.int32)
+            self.pos_off = np.ctypeslib.as_array(po, shape=(ne + 1,)).copy()
+            nw = int(self.pos_off[ne])
+            self.pos_bits = np.ctypeslib.as_array(pb, shape=(nw,)).copy() if nw else np.zeros(0, np.uint64)
+
+    def positions(self, i):
+        """{protein id: bool[S]} of REPORTED query i (index into rep_query), shaped like BatchResult.positions: the
+        PositionHits of its reported hits (search.go:442-452); S = pos_bits_len[i], the SizeInKmer as searched (for an
+        ORF the untrimmed one, like top_first_pos)."""
+        if self.pos_bits is None:
+            raise ValueError("this result was not asked for positions (want_positions=True)")
+        size = int(self.pos_bits_len[i])
+        words = (size + 63) // 64
+        out = {}
+        for e in range(int(self.top_off[i]), int(self.top_off[i + 1])):
+            w = self.pos_bits[int(self.pos_off[e]):int(self.pos_off[e]) + words]
+            out[int(self.top_pid[e])] = np.unpackbits(w.view(np.uint8), bitorder="little")[:size].astype(bool)
+        return out
 
     def dense(self):
         """(top_pid, top_kmatch) as [n_queries, max_results] arrays, zero beyond top_cnt"""
@@ -397,14 +420,20 @@ class Index:
                                                      seq_type, int(want_positions), C.byref(t)))
         return FullTicket(t)
 
-    def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True):
+    def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
+                   want_positions=False):
         """Host-buffer form that returns the reported hits only (kaamer_search_batch_top_flat; flat=False: the struct
-        form): sortMapByValue order, SetBestStartCodon for nucleotide/reads, FilterResults -- all on the device."""
+        form): sortMapByValue order, SetBestStartCodon for nucleotide/reads, FilterResults -- all on the device.
+        want_positions: the PositionHits bitmaps of the reported hits come along (kaamer_search_batch_top_pos_flat;
+        TopResult.positions)."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         out = C.POINTER(abi.BatchTop)()
-        if flat:
+        if want_positions:
+            abi.check(abi.lib().kaamer_search_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
+                                                                 len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
+        elif flat:
             abi.check(abi.lib().kaamer_search_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
                                                              len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
         else:
@@ -416,14 +445,19 @@ class Index:
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True):
+    def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
+                   want_positions=False):
         """kaamer_submit_batch_top[_flat]: the batch is copied and enqueued on a free slot; -> a ticket whose wait() returns
-        the TopResult.  Several tickets may be in flight; submit blocks while every slot is busy."""
+        the TopResult.  Several tickets may be in flight; submit blocks while every slot is busy.
+        want_positions: kaamer_submit_batch_top_pos_flat (the bitmaps of the reported hits come along)."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         t = C.c_void_p()
-        if flat:
+        if want_positions:
+            abi.check(abi.lib().kaamer_submit_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
+                                                                 len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
+        elif flat:
             abi.check(abi.lib().kaamer_submit_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
                                                              len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
         else:
@@ -432,8 +466,12 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
-    def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10):
-        return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results)
+    def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False):
+        return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions)
+
+    def set_top_positions_bound(self, words):
+        """kaamer_index_set_top_positions_bound: the first bitmap bound (u64 words) of the want_positions calls; 0: the rule"""
+        abi.check(abi.lib().kaamer_index_set_top_positions_bound(self._h, int(words)))
 
     def close(self):
         if self._h:
@@ -664,10 +702,13 @@ class TopTicket:
 class TopStream:
     """kaamer_stream_*: a FIFO of batches with fixed options (push chunk i + 1 while chunk i is searched)"""
 
-    def __init__(self, index, seq_type, min_k_ratio, min_k_match, max_results):
+    def __init__(self, index, seq_type, min_k_ratio, min_k_match, max_results, want_positions=False):
         to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
         h = C.c_void_p()
-        abi.check(abi.lib().kaamer_stream_open(index._h, seq_type, C.byref(to), C.byref(h)))
+        if want_positions:
+            abi.check(abi.lib().kaamer_stream_open_pos_flat(index._h, seq_type, min_k_ratio, min_k_match, max_results, C.byref(h)))
+        else:
+            abi.check(abi.lib().kaamer_stream_open(index._h, seq_type, C.byref(to), C.byref(h)))
         self._h, self.index = h, index
 
     def push(self, buf, offs):
@@ -743,6 +784,14 @@ class Workspace:
                          orf_source._h if orf_source is not None else None, q_first, q_stride)
         r = abi.TopnResult()
         abi.check(abi.lib().kaamer_topn_device(self._h, C.byref(o), C.c_void_p(stream), C.byref(r)))
+        return r
+
+    def topn_positions_device(self, top, max_pos_words=0, stream=0):
+        """kaamer_topn_positions_device: the PositionHits bitmaps of the hits the last topn_device call (`top`, its
+        result) kept, left on the device -> abi.TopnPositions (d_pos_base[n + 1], d_pos_bits_len[n], d_pos_bits)"""
+        r = abi.TopnPositions()
+        abi.check(abi.lib().kaamer_topn_positions_device(self.index._h, self._h, C.byref(top), int(max_pos_words),
+                                                         C.c_void_p(stream), C.byref(r)))
         return r
 
     def set_count_stream(self, stream):

@@ -511,4 +511,41 @@ void kaamer_sort_hits(const uint32_t *pid, const uint32_t *kmatch, int64_t n_hit
     for (int64_t i = 0; i < n_hits; i++) order[i] = idx[(size_t)i];
 }
 
+// FormatPositionsToString, search.go:694-742, byte for byte.  A run is closed by the first unset position `pos` and
+// printed as start-end with start = first set position + 1 and end = pos + 1 (one past the run's last position as the
+// reference counts from 1); a run that reaches the end prints len(positions); with_alignment adds KMER_SIZE - 1 to the
+// end.  (The reference's single-number branch needs pos + 1 <= currentStart and can never be taken.)
+uint64_t kaamer_format_positions(const uint64_t *bits, int32_t n_bits, int32_t with_alignment, char *buf, uint64_t cap)
+{
+    uint64_t len = 0;
+    auto put = [&](char c) { if (buf && len < cap) buf[len] = c; len++; };
+    auto put_int = [&](long long v) {
+        char tmp[24];
+        int n = 0;
+        do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+        while (n) put(tmp[--n]);
+    };
+    auto put_run = [&](long long start, long long end) {
+        if (len) put(',');
+        put_int(start);
+        put('-');
+        put_int(with_alignment ? end + KAAMER_KMER_SIZE - 1 : end);
+    };
+    long long current_start = 0;
+    bool in_sequence = false;
+    const long long n = (bits && n_bits > 0) ? n_bits : 0;
+    for (long long pos = 0; pos < n; pos++) {
+        const bool match = (bits[pos >> 6] >> (pos & 63)) & 1ull;
+        if (match) {
+            if (!in_sequence) { current_start = pos + 1; in_sequence = true; }
+        } else if (in_sequence) {
+            put_run(current_start, pos + 1);
+            in_sequence = false;
+        }
+    }
+    if (in_sequence) put_run(current_start, n);
+    if (buf && cap) buf[len < cap ? len : cap - 1] = '\0';
+    return len;
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@ struct batch_top_owner {
     uint8_t *block = nullptr;  // everything pub points to
     size_t block_cap = 0;
     bool pinned = true;        // from the pinned cache (else malloc: the interleaved result of a sharded index)
+    bool has_pos = false;      // the block carries the bitmap sections (RepPosExt, top_positions.hip.inc)
 };
 
 struct kaamer_ticket {
@@ -32,14 +33,17 @@ struct kaamer_ticket {
     size_t h_block_cap, copied;
     BatchBounds b;
     int attempt;
+    bool want_pos;   // PositionHits of the reported hits ride in the block (the *_pos_flat calls)
 };
 
 // upper bound of the result block of a batch searched on `ws`, whose queries belong to `src` (ws itself, or the
 // workspace that translated the batch: merged results of a sharded index)
-static size_t rep_block_bound(const kaamer_workspace *ws, const kaamer_workspace *src, uint32_t K)
+static size_t rep_block_bound(const kaamer_workspace *ws, const kaamer_workspace *src, uint32_t K, uint64_t pos_words = 0)
 {
     const size_t nq = ws->q_cap;
-    return sizeof(RepBlockHdr) + nq * (4 + 4 + sizeof(kaamer_query_meta) + 8) + 64 + nq * (size_t)K * 12 + (src->nucleotide ? (size_t)src->aa_cap + 64 : 0) + 64;
+    // the bitmap sections: bit length per query, CSR per entry, the words
+    const size_t pos = pos_words ? nq * 4 + 8 + (nq * (size_t)K + 1) * 8 + (size_t)pos_words * 8 : 0;
+    return pos + sizeof(RepBlockHdr) + nq * (4 + 4 + sizeof(kaamer_query_meta) + 8) + 64 + nq * (size_t)K * 12 + (src->nucleotide ? (size_t)src->aa_cap + 64 : 0) + 64;
 }
 
 // packs the reported queries of the last kaamer_topn_device call on `ws` into `d_block` (topn.hip.inc); `src`: the
@@ -73,6 +77,24 @@ static int topn_pack_block(kaamer_workspace *ws, const kaamer_workspace *src, ui
     scan_u32_on(ws, tr->d_top_cnt, ws->d_nq, bound, ws->d_rep_eoff, s);
     scan_u32_on(ws, ws->d_rep_aalen, ws->d_nq, bound, ws->d_rep_aoff, s);
     hipLaunchKernelGGL(rep_block_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, p);
+    HIPCHK(hipGetLastError());
+    return KAAMER_OK;
+}
+
+// the bitmaps of the reported hits behind the sections topn_pack_block just laid out (top_positions.hip.inc); a block
+// that cannot hold them gets ST_POS_CAP in its header: the caller repeats the batch with a larger bound
+static int topn_pack_positions(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *tr, hipStream_t s, uint8_t *d_block,
+                               size_t block_cap, uint64_t pos_words)
+{
+    int rc = tp_check(ix, ws, tr, "search_batch_top_pos");
+    if (!rc) rc = tp_prepare(ws);
+    if (rc) return rc;
+    TopPosParams p = tp_params(ix, ws, tr);
+    p.cap = pos_words;
+    p.block = d_block; p.block_cap = block_cap;
+    p.rank = ws->d_rep_rank; p.eoff = ws->d_rep_eoff; p.aoff = ws->d_rep_aoff;
+    tp_enqueue_layout(ws, p, s);
+    hipLaunchKernelGGL(top_pos_bits_kernel, dim3(ws->n_cu * 8), dim3(64 * TP_WAVES), 0, s, p);
     HIPCHK(hipGetLastError());
     return KAAMER_OK;
 }
@@ -124,7 +146,8 @@ static void top_slot_free(TopSlot &h)
 }
 
 // workspace, staging and result block of a slot: rebuilt only when the batch outgrows them
-static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace_opts &need, uint64_t seq_bytes, uint32_t n_seqs, uint32_t K)
+static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace_opts &need, uint64_t seq_bytes, uint32_t n_seqs, uint32_t K,
+                            bool want_pos = false, uint32_t pos_scale = 0)
 {
     if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
     const kaamer_workspace_opts &o = h.opts;
@@ -165,7 +188,17 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
         if (hipHostMalloc((void **)&h.h_in, cap, hipHostMallocDefault) != hipSuccess) return kaamer_fail(KAAMER_E_NOMEM, "pinned input staging (%zu bytes)", cap);
         h.h_in_cap = cap;
     }
-    const size_t bneed = rep_block_bound(h.ws, h.ws, K);
+    // the bitmap bound (the rule next to kaamer_topn_positions_device); a first bound set on the index holds for the
+    // first attempt only: the repeat of a batch that exceeded it takes the rule's
+    h.pos_words = 0;
+    if (want_pos) {
+        uint64_t first = 0;
+        { std::lock_guard<std::mutex> lock(ix->pool_mu); first = ix->top_pos_words; }
+        const uint64_t hard = tp_hard_words(h.ws, K);
+        h.pos_words = (first && pos_scale <= 1) ? (first < hard ? first : hard) : tp_default_words(h.ws, K, pos_scale);
+    }
+    const size_t bneed = rep_block_bound(h.ws, h.ws, K, h.pos_words);
+    h.block_use = bneed;
     if (h.d_block_cap < bneed) {
         if (h.d_block) (void)hipFree(h.d_block);
         h.d_block = nullptr; h.d_block_cap = 0;
@@ -192,7 +225,7 @@ static int top_enqueue(kaamer_ticket *t)
     o.first_pos = 0;  // as the reference fills PositionHits: nucleotide / reads input only (search.go:416)
     o.max_queries = t->b.max_queries;
     o.concurrent_batches = (uint32_t)ix->n_top;   // the slots exist so that batches overlap
-    int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results);
+    int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results, t->want_pos, t->b.pos_scale);
     if (rc) return rc;
     hipStream_t s = h.stream;
     const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
@@ -207,11 +240,12 @@ static int top_enqueue(kaamer_ticket *t)
     top.d_size_in_kmer = nullptr; top.orf_source = nullptr;
     rc = kaamer_search_device(ix, h.ws, h.d_seqs, h.d_off, t->n_seqs, t->seq_bytes, t->seq_type, s, &dr);
     if (!rc) rc = kaamer_topn_device(h.ws, &top, s, &tr);
-    if (!rc) rc = topn_pack_block(h.ws, h.ws, 0u, 1u, &tr, s, h.d_block, h.d_block_cap);
+    if (!rc) rc = topn_pack_block(h.ws, h.ws, 0u, 1u, &tr, s, h.d_block, h.block_use);
+    if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
     if (rc) return rc;
     // the speculative copy: as much as the previous call's block took (plus a quarter), never more than the block can hold
     size_t want = h.guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : h.guess;
-    if (want > h.d_block_cap) want = h.d_block_cap;
+    if (want > h.block_use) want = h.block_use;
     if (t->h_block_cap < want) {
         if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
         t->h_block = (uint8_t *)pinned_get(want, &t->h_block_cap);
@@ -223,7 +257,8 @@ static int top_enqueue(kaamer_ticket *t)
     return KAAMER_OK;
 }
 
-static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool blocking, kaamer_ticket **out)
+static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool blocking, kaamer_ticket **out,
+                      bool want_pos = false)
 {
     if (!ix || !in || !top || !out || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
         return kaamer_fail(KAAMER_E_ARG, "submit_batch_top: bad argument");
@@ -245,6 +280,7 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
     memset(t, 0, sizeof *t);
     t->ix = ix; t->slot = slot; t->n_seqs = in->n_seqs; t->seq_type = in->seq_type; t->seq_bytes = in->offsets[in->n_seqs];
     t->top = *top;
+    t->want_pos = want_pos;
     int rc = KAAMER_OK;
     hipError_t he = hipSetDevice(ix->device);
     if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(he));
@@ -338,6 +374,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         top_owner_fill(bo);
         if (ix->top[t->slot].ws) ws_note_density(ix->top[t->slot].ws, bo->pub.counters);
         bo->pub.max_results = t->top.max_results;
+        bo->has_pos = t->want_pos;
         if (!nucl) bo->pub.orf_aa = nullptr;
         *out = &bo->pub;
     }
@@ -362,6 +399,7 @@ void kaamer_ticket_discard(kaamer_ticket *t)
     delete t;
 }
 
+static void stream_set_positions(kaamer_stream *st);
 static void flat_in(kaamer_batch_in *in, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type, int32_t want_positions)
 {
     memset(in, 0, sizeof *in);
@@ -393,6 +431,44 @@ int kaamer_search_batch_top_flat(kaamer_index *ix, const uint8_t *seqs, const ui
     return kaamer_wait_batch_top(t, out);
 }
 
+// ---- the same calls with the PositionHits bitmaps of the reported hits in the block (search.go:442-452,520-522) ----
+int kaamer_submit_batch_top_pos_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_ticket **ticket)
+{
+    kaamer_batch_in in;
+    kaamer_topn_opts top;
+    flat_in(&in, seqs, offsets, n_seqs, seq_type, 1);
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    return top_submit(ix, &in, &top, true, ticket, true);
+}
+
+int kaamer_search_batch_top_pos_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_batch_top_pos_flat(ix, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+int kaamer_batch_top_positions(const kaamer_batch_top *out, const int32_t **pos_bits_len, const uint64_t **pos_off, const uint64_t **pos_bits)
+{
+    if (pos_bits_len) *pos_bits_len = nullptr;
+    if (pos_off) *pos_off = nullptr;
+    if (pos_bits) *pos_bits = nullptr;
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_positions: bad argument");
+    const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
+    if (!bo->has_pos || !bo->block) return KAAMER_OK;   // not asked for positions: all NULL
+    const RepBlockHdr *h = reinterpret_cast<const RepBlockHdr *>(bo->block);
+    const RepPosExt *x = reinterpret_cast<const RepPosExt *>(h->reserved);
+    if (!x->off_pos_bits) return KAAMER_OK;
+    if (pos_bits_len) *pos_bits_len = reinterpret_cast<const int32_t *>(bo->block + x->off_pos_len);
+    if (pos_off) *pos_off = reinterpret_cast<const uint64_t *>(bo->block + x->off_pos_off);
+    if (pos_bits) *pos_bits = reinterpret_cast<const uint64_t *>(bo->block + x->off_pos_bits);
+    return KAAMER_OK;
+}
+
 int kaamer_search_batch_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
                              int32_t want_positions, kaamer_batch_out **out)
 {
@@ -406,6 +482,13 @@ int kaamer_stream_open_flat(kaamer_index *ix, int32_t seq_type, double min_k_rat
     kaamer_topn_opts top;
     flat_top(&top, min_k_ratio, min_k_match, max_results);
     return kaamer_stream_open(ix, seq_type, &top, out);
+}
+
+int kaamer_stream_open_pos_flat(kaamer_index *ix, int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_stream **out)
+{
+    const int rc = kaamer_stream_open_flat(ix, seq_type, min_k_ratio, min_k_match, max_results, out);
+    if (!rc) stream_set_positions(*out);
+    return rc;
 }
 
 int kaamer_search_batch_top(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_batch_top **out)
@@ -431,7 +514,9 @@ struct kaamer_stream {
     int32_t seq_type;
     kaamer_topn_opts top;
     std::vector<kaamer_ticket *> *fifo;
+    bool want_pos;
 };
+static void stream_set_positions(kaamer_stream *st) { st->want_pos = true; }
 
 int kaamer_stream_open(kaamer_index *ix, int32_t seq_type, const kaamer_topn_opts *top, kaamer_stream **out)
 {
@@ -439,7 +524,7 @@ int kaamer_stream_open(kaamer_index *ix, int32_t seq_type, const kaamer_topn_opt
     *out = nullptr;
     kaamer_stream *st = new (std::nothrow) kaamer_stream();
     if (!st) return kaamer_fail(KAAMER_E_NOMEM, "stream");
-    st->ix = ix; st->seq_type = seq_type; st->top = *top;
+    st->ix = ix; st->seq_type = seq_type; st->top = *top; st->want_pos = false;
     st->fifo = new (std::nothrow) std::vector<kaamer_ticket *>();
     if (!st->fifo) { delete st; return kaamer_fail(KAAMER_E_NOMEM, "stream"); }
     *out = st;
@@ -454,7 +539,7 @@ int kaamer_stream_push(kaamer_stream *st, const uint8_t *seqs, const uint64_t *o
     in.seqs = seqs; in.offsets = offsets; in.n_seqs = n_seqs; in.seq_type = st->seq_type;
     kaamer_ticket *t = nullptr;
     // never block on a slot this stream itself holds: when every slot is busy the caller pops first
-    const int rc = top_submit(st->ix, &in, &st->top, st->fifo->empty(), &t);
+    const int rc = top_submit(st->ix, &in, &st->top, st->fifo->empty(), &t, st->want_pos);
     if (rc) return rc;
     st->fifo->push_back(t);
     return KAAMER_OK;

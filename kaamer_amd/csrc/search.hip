@@ -89,7 +89,7 @@ static inline bool is_nucl(int32_t seq_type) { return seq_type == KAAMER_NUCLEOT
 // the data-dependent bounds of a host-buffer call (0: the library's default for the input size).  The hit count of a
 // batch is data dependent: a call starts from an estimate and, while the device reports KAAMER_E_CAPACITY (results are
 // never partial), runs the batch again with grown bounds, at most MAX_BOUND_RETRIES times.
-struct BatchBounds { uint64_t max_hits, g_slots; uint32_t max_queries; };
+struct BatchBounds { uint64_t max_hits, g_slots; uint32_t max_queries; uint32_t pos_scale; /* reported-hit bitmaps: x the default rule (0 = 1) */ };
 static const int MAX_BOUND_RETRIES = 6;
 
 // where the full-list calls start (the top-N calls start from 0, the workspace's own default)
@@ -103,6 +103,7 @@ static void bounds_grow(BatchBounds &b, uint64_t seq_bytes, uint32_t n_seqs, boo
         const uint64_t hard = seq_bytes / 10 + (uint64_t)n_seqs * 6 + 64;
         b.max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
     }
+    b.pos_scale = b.pos_scale ? (b.pos_scale < (1u << 24) ? b.pos_scale * 4 : b.pos_scale) : 4;
 }
 
 // one in-flight call of the pipelined host-buffer boundary (host_top.hip.inc)
@@ -117,6 +118,8 @@ struct TopSlot {
     size_t h_in_cap = 0;
     uint8_t *d_block = nullptr;
     size_t d_block_cap = 0;
+    size_t block_use = 0;      // bytes of d_block this call may fill: its bound (<= d_block_cap)
+    uint64_t pos_words = 0;    // bitmap words of that bound (calls that ask for PositionHits of the reported hits)
     size_t guess = 1u << 16;   // bytes of the block copied before its size is known (adapts to the previous call)
     bool busy = false;
 };
@@ -136,6 +139,7 @@ struct kaamer_index {
     std::condition_variable pool_cv;
     TopSlot top[KAAMER_MAX_HOST_SLOTS];
     int n_top;
+    uint64_t top_pos_words = 0;   // kaamer_index_set_top_positions_bound: first bitmap bound of the host calls (0: the rule)
 };
 
 enum { ST_POOL_FULL = 1u, ST_LIST_FULL = 2u, ST_QUERY_CAP = 4u, ST_AA_CAP = 8u, ST_G_ARENA_FULL = 16u, ST_G_TABLE_FULL = 32u,
@@ -1361,6 +1365,7 @@ __global__ __launch_bounds__(64 * G_WAVES) void positions_global_kernel(CountPar
 
 #include "translate.hip.inc"
 #include "topn.hip.inc"
+#include "top_positions.hip.inc"
 
 // ------------------------------------------------------------------------------------
 // exclusive scan of q_cnt[0..nq) -> hit_off[0..nq]
@@ -1572,6 +1577,12 @@ struct kaamer_workspace {
     uint32_t *d_top_cnt, *d_top_pid, *d_top_km, *d_top_fp;
     int32_t *d_top_trim, *d_top_start, *d_top_size;
     bool last_was_merge;
+    // PositionHits of the reported hits (kaamer_topn_positions_device), allocated on first use
+    uint32_t *d_tp_words;
+    int32_t *d_tp_len;
+    uint64_t *d_tp_base;
+    unsigned long long *d_tp_bits;
+    uint64_t tp_alloc;                  // words d_tp_bits holds (grow-only)
     // exchange step of the sharded index (kaamer_exchange_pack / _merge), allocated on first use
     // exchange scratch: grow-only (the block layout may change from batch to batch within the buffers' capacity)
     size_t x_dst_cap, x_src_cap, x_ent_cap, x_m_cap;
@@ -1928,7 +1939,8 @@ void kaamer_workspace_free(kaamer_workspace *ws)
                      ws->d_slot_off, ws->d_group_first, ws->d_n_groups, ws->d_pos_words, ws->d_pos_base, ws->d_pos_off, ws->d_pos_bits, ws->d_g_keys,
                      ws->d_counter_replicas, ws->d_counters, ws->d_bsum, ws->d_chain, ws->d_tr_chain, ws->d_sched, ws->d_n_sched, ws->d_group_start, ws->d_lay_total, ws->d_slot_scale, ws->d_top_cnt, ws->d_top_pid, ws->d_top_km, ws->d_top_fp, ws->d_top_trim, ws->d_top_start, ws->d_top_size, ws->d_rep_flag, ws->d_rep_aalen, ws->d_rep_query, ws->d_rep_pid, ws->d_rep_km, ws->d_rep_fp, ws->d_rep_trim, ws->d_rep_rank, ws->d_rep_eoff, ws->d_rep_aoff, ws->d_rep_off, ws->d_rep_q, ws->d_rep_aa, ws->d_hit_off,
                      ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp, ws->d_x_dst_off, ws->d_x_src_off, ws->d_x_nq_owned, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, ws->d_x_ent_off, ws->d_x_tiles, ws->d_x_stats,
-                     ws->d_x_dst_boff, ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_mdst, ws->d_x_msize, ws->d_x_mbits, ws->d_x_gtab, ws->d_x_pstats };
+                     ws->d_x_dst_boff, ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_mdst, ws->d_x_msize, ws->d_x_mbits, ws->d_x_gtab, ws->d_x_pstats,
+                     ws->d_tp_words, ws->d_tp_len, ws->d_tp_base, ws->d_tp_bits };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (ws->h_x_stats) {
         (void)hipHostFree(ws->h_x_stats);
@@ -2975,6 +2987,118 @@ int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void 
     out->d_trim = ws->d_top_trim;
     out->d_start_position = ws->d_top_start;
     out->d_size_in_kmer = ws->d_top_size;
+    return KAAMER_OK;
+}
+
+// ---- PositionHits of the reported hits (top_positions.hip.inc) -------------------------------------------------------
+// Storage rule.  A reported hit of query q takes ceil(S_q / 64) words, so a batch needs at most
+//     K x sum_q ceil(S_q / 64)  <=  K x (pos_cap / 64 + q_cap)          (the hard bound: every query reports K hits)
+// words.  The default provisions f hits per query instead of K: f = min(K, 16) for protein batches (a protein query of
+// the flagship database reports its MaxResults = 10), f = 1 for ORF batches (most ORFs of a reads batch report nothing;
+// 1 M reads: 4.2 M ORFs, a few per cent reported).  A batch beyond the bound is an ST_POS_CAP / KAAMER_E_CAPACITY like
+// any other bound; the host calls repeat it with 4 x the words (BatchBounds::pos_scale), never beyond the hard bound.
+static uint64_t tp_hard_words(const kaamer_workspace *ws, uint32_t K)
+{
+    const uint64_t per_hit = ws->pos_cap / 64 + ws->q_cap + 1;
+    const uint64_t lim = 0xFFFFFFF0ull;   // the per-query word counts saturate at 32 bits (top_pos_words_kernel)
+    return per_hit > lim / K ? lim : per_hit * K;
+}
+static uint64_t tp_default_words(const kaamer_workspace *ws, uint32_t K, uint32_t scale)
+{
+    const uint32_t f = ws->nucleotide ? 1u : (K < 16u ? K : 16u);
+    const uint64_t hard = tp_hard_words(ws, K);
+    uint64_t w = (ws->pos_cap / 64 + ws->q_cap + 1) * f;
+    if (scale > 1) w = w > hard / scale ? hard : w * scale;
+    return w > hard ? hard : w;
+}
+
+static int tp_prepare(kaamer_workspace *ws)
+{
+    if (ws->d_tp_words) return KAAMER_OK;
+    int rc = dev_alloc(&ws->d_tp_words, ws->q_cap);
+    if (!rc) rc = dev_alloc(&ws->d_tp_len, ws->q_cap);
+    if (!rc) rc = dev_alloc(&ws->d_tp_base, (size_t)ws->q_cap + 1);
+    if (rc) {
+        void *bufs[] = { ws->d_tp_words, ws->d_tp_len, ws->d_tp_base };
+        for (void *b : bufs) if (b) (void)hipFree(b);
+        ws->d_tp_words = nullptr; ws->d_tp_len = nullptr; ws->d_tp_base = nullptr;
+    }
+    return rc;
+}
+
+static TopPosParams tp_params(const kaamer_index *ix, const kaamer_workspace *ws, const kaamer_topn_result *top)
+{
+    TopPosParams p;
+    memset(&p, 0, sizeof p);
+    p.d_nq = ws->d_nq; p.qinfo = ws->d_qinfo; p.vals = ws->d_vals; p.arena = ix->d_arena;
+    p.top_cnt = top->d_top_cnt; p.top_pid = top->d_top_pid; p.K = top->max_results;
+    p.words = ws->d_tp_words; p.bits_len = ws->d_tp_len; p.base = ws->d_tp_base;
+    p.status = ws->d_status_out;
+    return p;
+}
+
+// per-query words and their scan: everything the bitmap kernel and the block layout need to know
+static void tp_enqueue_layout(kaamer_workspace *ws, const TopPosParams &p, hipStream_t s)
+{
+    uint32_t gb = (ws->q_cap + 255) / 256;
+    if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
+    hipLaunchKernelGGL(top_pos_words_kernel, dim3(gb), dim3(256), 0, s, p);
+    scan_u32_on(ws, ws->d_tp_words, ws->d_nq, ws->q_cap, ws->d_tp_base, s);
+}
+
+static int tp_check(const kaamer_index *ix, const kaamer_workspace *ws, const kaamer_topn_result *top, const char *who)
+{
+    if (!ix || !ws || !top) return kaamer_fail(KAAMER_E_ARG, "%s: bad argument", who);
+    if (ix->device != ws->device) return kaamer_fail(KAAMER_E_ARG, "%s: workspace belongs to another device", who);
+    if (ws->last_was_merge) return kaamer_fail(KAAMER_E_ARG, "%s: the workspace's last result is a merge: the probe results live on the shards", who);
+    if (!ws->d_top_cnt || top->d_top_cnt != ws->d_top_cnt || top->d_top_pid != ws->d_top_pid || top->max_results < 1 || top->max_results > ws->topn_k)
+        return kaamer_fail(KAAMER_E_ARG, "%s: not the result of this workspace's last kaamer_topn_device", who);
+    return KAAMER_OK;
+}
+
+int kaamer_topn_positions_device(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *top, uint64_t max_pos_words,
+                                 void *stream, kaamer_topn_positions *out)
+{
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "topn_positions_device: bad argument");
+    int rc = tp_check(ix, ws, top, "topn_positions_device");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ws->device));
+    const uint64_t hard = tp_hard_words(ws, top->max_results);
+    uint64_t cap = max_pos_words ? max_pos_words : tp_default_words(ws, top->max_results, 1);
+    if (cap > hard) cap = hard;
+    // the post-steps of a search whose counting stage ran on the count stream follow it there (kaamer_topn_device)
+    const bool on_count_stream = ws->split_pending && ws->count_stream;
+    hipStream_t s = on_count_stream ? ws->count_stream : (hipStream_t)stream;
+    rc = tp_prepare(ws);
+    if (rc) return rc;
+    if (ws->tp_alloc < cap) {
+        if (ws->d_tp_bits) {   // an earlier batch may still be writing it
+            HIPCHK(hipStreamSynchronize(s));
+            (void)hipFree(ws->d_tp_bits);
+            ws->d_tp_bits = nullptr; ws->tp_alloc = 0;
+        }
+        rc = dev_alloc(&ws->d_tp_bits, (size_t)cap);
+        if (rc) return rc;
+        ws->tp_alloc = cap;
+    }
+    TopPosParams p = tp_params(ix, ws, top);
+    p.bits = ws->d_tp_bits; p.cap = cap;
+    tp_enqueue_layout(ws, p, s);
+    hipLaunchKernelGGL(top_pos_bits_kernel, dim3(ws->n_cu * 8), dim3(64 * TP_WAVES), 0, s, p);
+    if (on_count_stream) HIPCHK(hipEventRecord(ws->ev_count, s));
+    HIPCHK(hipGetLastError());
+    out->d_pos_base = ws->d_tp_base;
+    out->d_pos_bits_len = ws->d_tp_len;
+    out->d_pos_bits = (const uint64_t *)ws->d_tp_bits;
+    out->pos_words_capacity = cap;
+    return KAAMER_OK;
+}
+
+int kaamer_index_set_top_positions_bound(kaamer_index *ix, uint64_t words)
+{
+    if (!ix) return kaamer_fail(KAAMER_E_ARG, "index_set_top_positions_bound: bad argument");
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    ix->top_pos_words = words;
     return KAAMER_OK;
 }
 

@@ -1,0 +1,185 @@
+// top_positions.hip.inc — PositionHits bitmaps of the REPORTED hits only (included by search.hip after topn.hip.inc).
+//
+// The reference fills PositionHits for every hit of a query (search.go:442-452) and prints them for the hits it reports
+// (search.go:520-522,540-543,591-594: at most MaxResults per query).  Once kaamer_topn_device has run, everything the
+// bitmaps of those few hits need is resident: the probe's vals[] (one word per residue position: 0, an inline protein id,
+// or the offset of a postings list in the arena, kaamer_layout.h), the queries' QInfo (SizeInKmer as searched -- for an
+// ORF the untrimmed one, as top_first_pos is -- and the first residue position) and top_cnt / top_pid.  No counting
+// table, no LDS bitmap, no atomics:
+//
+//   top_pos_words_kernel   per query: reported hits x ceil(SizeInKmer / 64) words (saturating at 32 bits, as
+//                          pos_words_kernel does) and the bit length; the caller scans the words into per-query bases
+//   top_pos_bits_kernel    one wave per reported query, 64 positions (one output word per hit) at a time: lane = position.
+//                          The lane walks the ids under its k-mer and keeps a mask with bit r set when an id is reported
+//                          hit r (the reported ids of the query sit in LDS, 64 at a time: MaxResults > 64 takes rounds).
+//                          Postings lists longer than TP_COOP_MIN ids are not walked by their lane (10^4 ids would stall
+//                          the wave behind one lane): the whole wave scans such a list with coalesced loads and ORs the
+//                          lanes' masks together.  No order of the ids inside a list is assumed.
+//                          Word `stripe` of hit r is then __ballot(bit r of the masks); lane r stores hit r's word.
+// Layout as pos_layout_kernel's: the bitmaps of a query are contiguous, in reported order, ceil(SizeInKmer / 64) words
+// each; every word of every bitmap is stored (nothing needs zeroing first).
+// The same kernel serves both forms of the call: the device-resident one writes into the workspace's own storage, the
+// host-buffer one appends three sections to the packed result block (topn.hip.inc) behind rep_block_kernel:
+//   ... | pos_bits_len i32[n_rep] | pos_off u64[n_ent + 1] (CSR, in words) | pos_bits u64[pos_off[n_ent]]
+#define TP_WAVES 4
+#define TP_COOP_MIN 16u   /* ids; longer lists are scanned by the whole wave */
+
+// what the host-buffer form adds to RepBlockHdr, in its reserved bytes (zero in a block without bitmaps)
+struct RepPosExt {
+    uint64_t off_pos_len, off_pos_off, off_pos_bits;   // byte offsets of the three sections
+    uint64_t n_pos_words;
+};
+static_assert(sizeof(RepPosExt) <= sizeof(((RepBlockHdr *)nullptr)->reserved), "the header's reserved bytes hold the bitmap sections");
+static_assert(offsetof(RepBlockHdr, reserved) % 8 == 0, "aligned");
+
+struct TopPosParams {
+    const uint32_t *d_nq;
+    const QInfo *qinfo;
+    const uint32_t *vals;
+    const uint32_t *arena;
+    const uint32_t *top_cnt, *top_pid;
+    uint32_t K;
+    uint32_t *words;               // per query: reported hits x words per hit (saturating)
+    int32_t *bits_len;             // per query: SizeInKmer of a query that reports, else 0
+    const uint64_t *base;          // exclusive scan of words[], [nq] = total
+    unsigned long long *bits;      // device-resident form: the workspace's storage
+    uint64_t cap;                  // ... and its capacity in words
+    uint32_t *status;              // ST_POS_CAP goes here (the status of the last finished batch)
+    // host-buffer form: the packed block and the scans rep_block_kernel laid it out from
+    uint8_t *block;
+    uint64_t block_cap;
+    const uint64_t *rank, *eoff, *aoff;
+};
+
+__global__ void top_pos_words_kernel(TopPosParams p)
+{
+    const uint32_t nq = *p.d_nq;
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (uint64_t)gridDim.x * blockDim.x) {
+        const int32_t size = p.qinfo[q].size;
+        const uint32_t cnt = p.top_cnt[q];
+        const uint64_t w = size > 0 ? (uint64_t)cnt * (((uint32_t)size + 63u) >> 6) : 0;
+        p.words[q] = w > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)w;
+        p.bits_len[q] = (cnt && size > 0) ? size : 0;
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_or_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
+    return v;
+}
+
+// bit r set iff `id` is the r-th of the n reported ids in LDS (all lanes read the same address: a broadcast)
+__device__ __forceinline__ unsigned long long tp_match(const uint32_t *pid, uint32_t n, uint32_t id)
+{
+    unsigned long long m = 0ull;
+    for (uint32_t r = 0; r < n; r++) m |= (unsigned long long)(pid[r] == id) << r;
+    return m;
+}
+
+__global__ __launch_bounds__(64 * TP_WAVES) void top_pos_bits_kernel(TopPosParams p)
+{
+    __shared__ uint32_t s_pid[TP_WAVES][64];
+    if (*p.status) return;   // the batch exceeded a bound earlier: its result is refused, whatever is left of it is not read
+    const uint32_t nq = *p.d_nq;
+    const uint64_t total = p.base[nq];
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    unsigned long long *bits = p.bits;
+    uint64_t cap = p.cap;
+    int32_t *rep_len = nullptr;
+    uint64_t *rep_poff = nullptr;
+    if (p.block) {
+        // the sections rep_block_kernel wrote, from the same three totals (every thread computes the same)
+        const uint64_t n_rep = p.rank[nq], n_ent = p.eoff[nq], n_aa = p.aoff[nq];
+        uint64_t o = rep_align8(sizeof(RepBlockHdr) + 4 * n_rep);              // rep_query
+        o = rep_align8(o + 4 * n_rep);                                          // trim
+        o = rep_align8(o + sizeof(kaamer_query_meta) * n_rep);                  // q
+        o = o + 8 * (n_rep + 1);                                                // top_off
+        o = rep_align8(o + 4 * n_ent);                                          // pid
+        o = rep_align8(o + 4 * n_ent);                                          // kmatch
+        o = rep_align8(o + 4 * n_ent);                                          // first_pos
+        const uint64_t base_total = rep_align8(o + n_aa);                       // orf_aa
+        if (base_total > p.block_cap) return;   // rep_block_kernel flagged the block: nothing was laid out
+        RepPosExt x;
+        x.off_pos_len = base_total;
+        x.off_pos_off = rep_align8(x.off_pos_len + 4 * n_rep);
+        x.off_pos_bits = x.off_pos_off + 8 * (n_ent + 1);
+        x.n_pos_words = total;
+        RepBlockHdr *hdr = reinterpret_cast<RepBlockHdr *>(p.block);
+        const bool fits = total <= cap && x.off_pos_bits <= p.block_cap && total <= (p.block_cap - x.off_pos_bits) / 8;
+        if (!fits) {   // a bound like every other: the whole batch is repeated with a larger one, never a partial block
+            if (first) hdr->status |= (uint32_t)ST_POS_CAP;
+            return;
+        }
+        if (first) {
+            *reinterpret_cast<RepPosExt *>(hdr->reserved) = x;
+            hdr->total_bytes = x.off_pos_bits + 8 * total;
+            reinterpret_cast<uint64_t *>(p.block + x.off_pos_off)[n_ent] = total;   // CSR end
+        }
+        rep_len = reinterpret_cast<int32_t *>(p.block + x.off_pos_len);
+        rep_poff = reinterpret_cast<uint64_t *>(p.block + x.off_pos_off);
+        bits = reinterpret_cast<unsigned long long *>(p.block + x.off_pos_bits);
+    } else if (total > cap) {
+        if (first) atomicOr(p.status, (uint32_t)ST_POS_CAP);
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t *pid = s_pid[wv];
+    const uint64_t wave = (uint64_t)blockIdx.x * TP_WAVES + wv, n_waves = (uint64_t)gridDim.x * TP_WAVES;
+    for (uint64_t q = wave; q < nq; q += n_waves) {
+        const uint32_t cnt = p.top_cnt[q];
+        if (cnt == 0) continue;   // most ORFs of a reads batch: no words, no work
+        const QInfo qi = p.qinfo[q];
+        const uint32_t size = qi.size > 0 ? (uint32_t)qi.size : 0u;
+        const uint32_t nw = (size + 63u) >> 6;
+        const uint64_t qbase = p.base[q];
+        if (rep_len) {
+            if (lane == 0) rep_len[p.rank[q]] = (int32_t)size;
+            const uint64_t e = p.eoff[q];
+            for (uint32_t i = lane; i < cnt; i += 64) rep_poff[e + i] = qbase + (uint64_t)i * nw;
+        }
+        if (nw == 0) continue;
+        const uint32_t *vals = p.vals + qi.aa_off;
+        unsigned long long *out = bits + qbase;
+        for (uint32_t r0 = 0; r0 < cnt; r0 += 64) {   // cnt <= K; K may exceed 64
+            const uint32_t nr = cnt - r0 < 64u ? cnt - r0 : 64u;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous round's readers are done
+            __builtin_amdgcn_wave_barrier();
+            pid[lane] = lane < nr ? p.top_pid[q * p.K + r0 + lane] : KH_EMPTY_PID;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (uint32_t st = 0; st < nw; st++) {
+                const uint32_t pos = (st << 6) + lane;
+                const uint32_t v = pos < size ? vals[pos] : 0u;
+                unsigned long long mask = 0ull;
+                uint32_t n_ids = 0;
+                if (v & KH_INLINE_BIT) mask = tp_match(pid, nr, v & ~KH_INLINE_BIT);
+                else if (v) {
+                    const uint32_t *l = p.arena + (uint64_t)v * 4;   // {count, ids...}
+                    n_ids = l[0];
+                    if (n_ids <= TP_COOP_MIN)
+                        for (uint32_t t = 0; t < n_ids; t++) mask |= tp_match(pid, nr, l[1 + t]);
+                }
+                unsigned long long todo = __ballot(n_ids > TP_COOP_MIN);
+                while (todo) {   // wave-uniform: the long lists of this stripe, one after the other
+                    const int src = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1ull;
+                    const uint32_t lv = (uint32_t)__shfl((int)v, src, 64), ln = (uint32_t)__shfl((int)n_ids, src, 64);
+                    const uint32_t *ids = p.arena + (uint64_t)lv * 4 + 1;
+                    unsigned long long m = 0ull;
+                    for (uint32_t t = lane; t < ln; t += 64) m |= tp_match(pid, nr, ids[t]);
+                    m = wave_or_u64(m);
+                    if ((int)lane == src) mask = m;
+                }
+                unsigned long long mine = 0ull;
+                for (uint32_t j = 0; j < nr; j++) {
+                    const unsigned long long b = __ballot((mask >> j) & 1ull);
+                    if (lane == j) mine = b;
+                }
+                if (lane < nr) out[(uint64_t)(r0 + lane) * nw + st] = mine;
+            }
+        }
+    }
+}
