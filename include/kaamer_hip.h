@@ -507,8 +507,9 @@ int kaamer_submit_batch_top_pos_flat(kaamer_index *ix, const uint8_t *seqs, cons
  * its SizeInKmer as searched, for an ORF the untrimmed one (q[i].size_in_kmer is the trimmed one; top_first_pos is
  * relative to the same untrimmed ORF) -- and entry e of the CSR arrays (top_pid[e], ...) has its
  * ceil(pos_bits_len[i] / 64) words at pos_bits + pos_off[e]; pos_off has top_off[n_reported] + 1 entries, the last one
- * the total.  All three are NULL for a result that was not asked for positions (every result of the sharded handle
- * included); they live as long as the result does. */
+ * the total.  All three are NULL for a result that was not asked for positions (on the sharded handle: every result
+ * but those of kaamer_sharded_search_batch_top_pos_flat / kaamer_sharded_submit_batch_top_pos_flat); they live as long
+ * as the result does. */
 int kaamer_batch_top_positions(const kaamer_batch_top *out, const int32_t **pos_bits_len, const uint64_t **pos_off,
                                const uint64_t **pos_bits);
 /* The FIRST bitmap bound (u64 words) of the host calls above on this index, for callers who know how densely their
@@ -660,6 +661,27 @@ int kaamer_sharded_search_batch_top_flat(kaamer_sharded_index *sx, const uint8_t
 int kaamer_sharded_submit_batch_top_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets,
                                          uint32_t n_seqs, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                                          uint32_t max_results, kaamer_sharded_ticket **ticket);
+/* The same calls for a request with ExtractPositions (-pos; nucleotide / reads requests always, search.go:416): the
+ * PositionHits bitmaps of the REPORTED hits (search.go:442-452 fills them, search.go:520-522,540-543,591-594 prints
+ * them: at most max_results per query), bit for bit what kaamer_search_batch_top_pos_flat returns on an unsharded index
+ * of the whole database; read them with kaamer_batch_top_positions.  The reported hits are known at the owner after
+ * the merge while the probe results live on the shards, so one more round trip follows the top-N step on the same
+ * streams: every owner sends the ids of its reported hits to every shard, every shard makes the bitmaps its own keys
+ * give, the owner ORs the W parts (disjoint) into its result block.  Only the reported hits' bitmaps cross devices
+ * (kaamer_sharded_search_batch_flat with want_positions moves those of every hit).  The ids blocks and the bitmap
+ * segments are bounds like every other (the rule of kaamer_topn_positions_device, divided over the owners; sized from
+ * the previous call's need when there was one): a batch beyond them is repeated inside the wait, never returned in
+ * part.  A ticket is waited for with kaamer_sharded_wait_batch_top or dropped with kaamer_sharded_ticket_discard. */
+int kaamer_sharded_search_batch_top_pos_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets,
+                                             uint32_t n_seqs, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                             uint32_t max_results, kaamer_batch_top **out);
+int kaamer_sharded_submit_batch_top_pos_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets,
+                                             uint32_t n_seqs, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                             uint32_t max_results, kaamer_sharded_ticket **ticket);
+/* That round trip of the last finished call with positions on the handle's first set (no Go counterpart: the reference
+ * is one process, search_fastq.go:94-118): out = { bytes of one ids block as it travelled, bytes of one (shard ->
+ * owner) bitmap segment as it travelled, bitmap words the largest segment needed, attempts the call took }. */
+int kaamer_sharded_positions_info(kaamer_sharded_index *sx, uint64_t out[4]);
 /* The full hit lists of a batch on the sharded handle: what kaamer_search_batch returns on an unsharded index of the
  * whole database (the worker pool of search_protein.go:58-118 / search_fastq.go:94-118 when -pos asks for
  * PositionHits, search.go:416,442-452): the same queries in the same order, each with the same (id, Kmatch, first

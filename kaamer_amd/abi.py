@@ -282,6 +282,12 @@ SYMBOLS = {
     "kaamer_batch_top_positions": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint64)),
                                              C.POINTER(C.POINTER(C.c_uint64))]),
     "kaamer_index_set_top_positions_bound": (C.c_int, [C.c_void_p, C.c_uint64]),
+    # ... and on the sharded handle
+    "kaamer_sharded_search_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
+                                                           C.c_int64, C.c_uint32, C.c_void_p]),
+    "kaamer_sharded_submit_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
+                                                           C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_sharded_positions_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_format_positions": (C.c_uint64, [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
 }
 

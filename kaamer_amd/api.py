@@ -510,12 +510,19 @@ class ShardedIndex:
         abi.check(abi.lib().kaamer_index_open_sharded(arr, dev, n, C.byref(h)))
         return cls(h.value)
 
-    def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True):
+    def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
+                   want_positions=False):
+        """What Index.search_top returns on an unsharded index of the whole database.  want_positions: the PositionHits
+        bitmaps of the reported hits come along (kaamer_sharded_search_batch_top_pos_flat; TopResult.positions)."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         out = C.POINTER(abi.BatchTop)()
-        if flat:
+        if want_positions:
+            abi.check(abi.lib().kaamer_sharded_search_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
+                                                                         len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results,
+                                                                         C.byref(out)))
+        elif flat:
             abi.check(abi.lib().kaamer_sharded_search_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
                                                                      len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
         else:
@@ -527,15 +534,25 @@ class ShardedIndex:
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10):
-        """kaamer_sharded_submit_batch_top_flat -> a ticket (wait() -> TopResult); up to three calls in flight per handle"""
+    def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10,
+                   want_positions=False):
+        """kaamer_sharded_submit_batch_top_flat -> a ticket (wait() -> TopResult); up to three calls in flight per handle.
+        want_positions: kaamer_sharded_submit_batch_top_pos_flat (the bitmaps of the reported hits come along)."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         t = C.c_void_p()
-        abi.check(abi.lib().kaamer_sharded_submit_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                                 len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
+        fn = abi.lib().kaamer_sharded_submit_batch_top_pos_flat if want_positions else abi.lib().kaamer_sharded_submit_batch_top_flat
+        abi.check(fn(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
+                     max_results, C.byref(t)))
         return TopTicket(t, sharded=True)
+
+    def positions_info(self):
+        """-> dict(ids_block_bytes, segment_bytes, need_words, attempts) of the last finished call with positions on the
+        handle's first set (kaamer_sharded_positions_info)"""
+        out = (C.c_uint64 * 4)()
+        abi.check(abi.lib().kaamer_sharded_positions_info(self._h, out))
+        return {"ids_block_bytes": int(out[0]), "segment_bytes": int(out[1]), "need_words": int(out[2]), "attempts": int(out[3])}
 
     def search(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False, flat=True):
         """The full hit lists (PositionHits bitmaps with want_positions): what Index.search returns on an unsharded index

@@ -9,6 +9,11 @@
 //   every owner d:  waits for the W pack events, pulls block (s -> d) of every shard with hipMemcpyPeerAsync
 //                   (xGMI point to point: every owner pulls from every shard at once), kaamer_exchange_merge,
 //                   kaamer_topn_device(orf_source = its own translation of the batch), the packed result block, one D2H
+//   with PositionHits of the reported hits (kaamer_sharded_search_batch_top_pos_flat), one more round trip before the D2H
+//   (top_positions_sharded.hip.inc), on the same streams and without a host synchronisation:
+//   every owner d:  its reported ids as a compact ids block; every shard pulls all W of them
+//   every shard s:  per owner, the partial bitmaps its own vals[] give, into segment d of a send buffer
+//   every owner d:  pulls segment d of every shard and ORs them into the pos_bits section of its result block
 //   host:  interleaves the W owners' reported queries back into batch order (query q is owned by shard q mod W)
 // No external communicator, no second process.  (One process per GPU with RCCL is the other deployment:
 // kaamer_exchange_pack / kaamer_rccl_alltoall / kaamer_exchange_merge, INTEGRATION.md 4b.)
@@ -32,6 +37,16 @@ struct ShardState {
     size_t seq_cap = 0, off_cap = 0;
     uint8_t *d_block = nullptr, *h_block = nullptr;
     size_t d_block_cap = 0, h_block_cap = 0, guess = 1u << 16, copied = 0;
+    // top calls with the PositionHits of the reported hits (top_positions_sharded.hip.inc)
+    bool tpos = false;                 // workspaces and buffers of such a call
+    uint32_t tp_k = 0, tp_scale = 0;   // MaxResults and BatchBounds::pos_scale the capacities below were made for
+    TpsIdsLayout ids_cap{}, ids_wire{};   // the ids block: capacity, and as it travels for the batch in flight
+    uint64_t tp_cap = 0, tp_wire = 0;     // bitmap words of one (shard -> owner) segment: capacity, as it travels
+    uint32_t *d_ids = nullptr, *d_ids_recv = nullptr;                   // the owner's ids block; the W owners' blocks as pulled
+    unsigned long long *d_seg_send = nullptr, *d_seg_recv = nullptr;    // W segments each (one header word + the bitmap words)
+    uint32_t *d_tps_words = nullptr, *d_tps_n = nullptr;                // [rq_cap]; per owner {reported queries, status}
+    uint64_t *d_tps_base = nullptr;                                     // [W][rq_cap + 1] word offsets per owner
+    hipEvent_t ev_ids = nullptr, ev_bits = nullptr;
 };
 
 // everything one call in flight needs on every shard (the indices themselves are shared by all sets)
@@ -43,6 +58,12 @@ struct ShardSet {
     uint64_t need_entries = 0;   // what the largest (shard -> owner) block of the previous batch on this set needed
     uint32_t need_queries = 0;   // its queries (ORFs)
     uint64_t need_pos_words = 0; // the bitmap words it needed (0: the previous batch carried no bitmaps)
+    // the previous top call with positions on this set: what the largest ids block and bitmap segment needed
+    bool tp_seen = false;
+    uint32_t need_ids_rq = 0;
+    uint64_t need_ids_ent = 0, need_tp_words = 0;
+    uint64_t tp_ids_bytes = 0, tp_seg_bytes = 0, tp_attempts = 0;   // kaamer_sharded_positions_info
+    uint32_t seq = 0;            // batch sequence of the ids blocks and segments
 };
 #define KAAMER_SHARDED_SETS 3   /* calls in flight per handle: the goroutines of search_fastq.go:60-66 against one handle */
 
@@ -55,6 +76,14 @@ struct kaamer_sharded_index {
     std::condition_variable cv;
 };
 
+static void shard_tps_free(ShardState &s)
+{
+    void *bufs[] = { s.d_ids, s.d_ids_recv, s.d_seg_send, s.d_seg_recv, s.d_tps_words, s.d_tps_n, s.d_tps_base };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    s.d_ids = s.d_ids_recv = nullptr; s.d_seg_send = s.d_seg_recv = nullptr;
+    s.d_tps_words = s.d_tps_n = nullptr; s.d_tps_base = nullptr;
+}
+
 static void shard_state_free(ShardState &s)
 {
     (void)hipSetDevice(s.device);
@@ -63,8 +92,11 @@ static void shard_state_free(ShardState &s)
     if (s.mws) kaamer_workspace_free(s.mws);
     void *bufs[] = { s.d_send, s.d_recv, s.d_seqs, s.d_off, s.d_block };
     for (void *b : bufs) if (b) (void)hipFree(b);
+    shard_tps_free(s);
     if (s.h_block) pinned_put(s.h_block, s.h_block_cap);
     if (s.ev_packed) (void)hipEventDestroy(s.ev_packed);
+    if (s.ev_ids) (void)hipEventDestroy(s.ev_ids);
+    if (s.ev_bits) (void)hipEventDestroy(s.ev_bits);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = ShardState();   // (the index belongs to the handle)
 }
@@ -113,6 +145,8 @@ static int sharded_open_common(uint32_t n, const int *devices, kaamer_sharded_in
             hipError_t e = hipSetDevice(devices[s]);
             if (e == hipSuccess) e = hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&st.ev_packed, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&st.ev_ids, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&st.ev_bits, hipEventDisableTiming);
             if (e != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "index_open_sharded: %s", hipGetErrorString(e));
         }
         if (rc) { kaamer_sharded_index_close(sx); return rc; }
@@ -174,7 +208,83 @@ struct ShardBounds {
     uint64_t e_cap;      // entries per (shard -> owner) block
     bool full, pos;      // a full call (hit lists to the host), with PositionHits bitmaps
     uint64_t p_cap;      // bitmap words per block (pos)
+    bool tpos;           // a top call with the PositionHits of the reported hits (its bounds: bb.pos_scale x the rule)
 };
+
+// ---- the four device steps of the reported hits' bitmaps, as functions of (workspaces, buffers, stream) ------------------
+// owner: the reported ids of the last kaamer_topn_device / topn_pack_block on `mws` into the ids block `d_ids`
+static int tps_enqueue_ids_pack(kaamer_workspace *mws, const kaamer_topn_result *tr, uint8_t *d_block, size_t block_cap, uint32_t *d_ids,
+                                const TpsIdsLayout &L, uint32_t owner, uint32_t W, uint32_t seq, hipStream_t s)
+{
+    TpsParams p;
+    memset(&p, 0, sizeof p);
+    p.world = W; p.owner = owner; p.seq = seq; p.ids_layout = L;
+    p.m_nq = mws->d_nq; p.top_cnt = tr->d_top_cnt; p.top_pid = tr->d_top_pid; p.K = tr->max_results;
+    p.rank = mws->d_rep_rank; p.eoff = mws->d_rep_eoff; p.aoff = mws->d_rep_aoff;
+    p.m_status = mws->d_status_out;
+    p.block = d_block; p.block_cap = block_cap;
+    p.ids_out = d_ids;
+    hipLaunchKernelGGL(tps_ids_pack_kernel, dim3(mws->n_cu * 8), dim3(256), 0, s, p);
+    HIPCHK(hipGetLastError());
+    return KAAMER_OK;
+}
+
+// what the shard-side steps share: the search workspace of the shard (kaamer_exchange_pack reads the hit lists and
+// writes the send blocks, its own offsets and tile sums only: vals[], qinfo and the index's arena are as the search
+// left them, which is what the unsharded path assumes after counting)
+static TpsParams tps_shard_params(const kaamer_index *ix, const kaamer_workspace *ws, const uint32_t *d_ids, const TpsIdsLayout &L, uint32_t owner,
+                                  uint32_t W, uint32_t seq, uint32_t K, uint32_t *d_n, uint32_t *d_words, const uint64_t *d_base)
+{
+    TpsParams p;
+    memset(&p, 0, sizeof p);
+    p.world = W; p.owner = owner; p.seq = seq; p.ids_layout = L; p.K = K;
+    p.ids = d_ids;
+    p.s_nq = ws->d_nq; p.qinfo = ws->d_qinfo; p.vals = ws->d_vals; p.arena = ix->d_arena; p.s_status = ws->d_status_out;
+    p.n_out = d_n; p.words = d_words; p.base = d_base;
+    return p;
+}
+
+// shard: the bitmap words of every reported query of `owner` and their scan (the same on every shard and on the owner)
+static int tps_enqueue_words(const kaamer_index *ix, kaamer_workspace *ws, const uint32_t *d_ids, const TpsIdsLayout &L, uint32_t owner, uint32_t W,
+                             uint32_t seq, uint32_t K, uint32_t *d_n, uint32_t *d_words, uint64_t *d_base, hipStream_t s)
+{
+    const TpsParams p = tps_shard_params(ix, ws, d_ids, L, owner, W, seq, K, d_n, d_words, d_base);
+    uint32_t gb = (L.rq_cap + 255) / 256;
+    if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
+    if (gb < 1) gb = 1;
+    hipLaunchKernelGGL(tps_words_kernel, dim3(gb), dim3(256), 0, s, p);
+    // (an owner reports at most the batch's queries: the workspace's scan scratch, sized for q_cap, is enough)
+    scan_u32_on(ws, d_words, d_n, L.rq_cap < ws->q_cap ? L.rq_cap : ws->q_cap, d_base, s);
+    HIPCHK(hipGetLastError());
+    return KAAMER_OK;
+}
+
+// shard: its partial bitmaps of the reported hits of `owner` into the segment `d_seg` (header word + seg_cap words)
+static int tps_enqueue_bits(const kaamer_index *ix, kaamer_workspace *ws, const uint32_t *d_ids, const TpsIdsLayout &L, uint32_t owner, uint32_t W,
+                            uint32_t seq, uint32_t K, uint32_t *d_n, const uint64_t *d_base, unsigned long long *d_seg, uint64_t seg_cap, hipStream_t s)
+{
+    TpsParams p = tps_shard_params(ix, ws, d_ids, L, owner, W, seq, K, d_n, nullptr, d_base);
+    p.seg = d_seg; p.seg_cap = seg_cap;
+    hipLaunchKernelGGL(tps_bits_kernel, dim3(ws->n_cu * 8), dim3(64 * TP_WAVES), 0, s, p);
+    HIPCHK(hipGetLastError());
+    return KAAMER_OK;
+}
+
+// owner: the W received segments (seg_stride u64 words apart) OR-ed into the bitmap sections of its packed block; `ws`,
+// d_n and d_base: the owner's own shard and what it computed for this owner's ids block
+static int tps_enqueue_or(const kaamer_index *ix, kaamer_workspace *mws, kaamer_workspace *ws, uint8_t *d_block, size_t block_cap, const uint32_t *d_ids,
+                          const TpsIdsLayout &L, uint32_t owner, uint32_t W, uint32_t seq, uint32_t *d_n, const uint64_t *d_base,
+                          unsigned long long *d_seg_recv, uint64_t seg_stride, uint64_t seg_cap, hipStream_t s)
+{
+    TpsParams p = tps_shard_params(ix, ws, d_ids, L, owner, W, seq, 0, d_n, nullptr, d_base);
+    p.m_nq = mws->d_nq;
+    p.rank = mws->d_rep_rank; p.eoff = mws->d_rep_eoff; p.aoff = mws->d_rep_aoff;
+    p.block = d_block; p.block_cap = block_cap;
+    p.seg = d_seg_recv; p.seg_stride = seg_stride; p.seg_cap = seg_cap;
+    hipLaunchKernelGGL(tps_or_kernel, dim3(mws->n_cu * 8), dim3(256), 0, s, p);
+    HIPCHK(hipGetLastError());
+    return KAAMER_OK;
+}
 
 static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq_bytes, uint32_t n_seqs, int32_t seq_type, const ShardBounds &b, uint32_t K)
 {
@@ -184,7 +294,8 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
     const bool fits = st.ws && o.seq_type == seq_type && o.max_seq_bytes >= seq_bytes && o.max_seqs >= (n_seqs ? n_seqs : 1) &&
                       o.g_tier_slots >= b.bb.g_slots && o.max_queries >= b.bb.max_queries && st.e_cap >= b.e_cap &&
                       o.max_hits >= b.bb.max_hits && (b.bb.max_hits != 0 || o.max_hits == 0) &&
-                      st.full == b.full && (o.want_positions != 0) == b.pos && (!b.pos || st.p_cap >= b.p_cap);
+                      st.full == b.full && (o.want_positions != 0) == b.pos && (!b.pos || st.p_cap >= b.p_cap) &&
+                      st.tpos == b.tpos;
     if (!fits) {
         HIPCHK(hipStreamSynchronize(st.stream));
         if (st.ws) kaamer_workspace_free(st.ws);
@@ -234,10 +345,39 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
             if (rc) return rc;
             st.x_words = words;
         }
+        shard_tps_free(st);   // (sized from the workspaces: made again below)
+        st.tpos = b.tpos;
+        st.tp_k = 0; st.tp_scale = 0;
+    }
+    // the reported hits' bitmaps: the unsharded rule (next to kaamer_topn_positions_device) divided over the owners,
+    // x pos_scale on a repeat, never beyond the hard bound; the ids block likewise (every owned query may report).  A
+    // repeat that grows pos_scale alone (or a larger MaxResults) makes these buffers and the result block again, nothing
+    // else: the workspaces and the exchange buffers stay.
+    const uint32_t scale = b.bb.pos_scale ? b.bb.pos_scale : 1u;
+    if (b.tpos && (st.tp_k < K || st.tp_scale < scale)) {
+        HIPCHK(hipStreamSynchronize(st.stream));
+        shard_tps_free(st);
+        const uint64_t hard = tp_hard_words(st.ws, K);
+        const uint64_t rule = tp_default_words(st.ws, K, scale), w = rule / W + 1024;
+        st.tp_cap = (rule >= hard || w > hard) ? hard : w;   // (one owner may own all the long queries: the hard bound is not divided)
+        const uint64_t oq = st.layout.q_cap, f = nucl ? 1u : (K < 16u ? K : 16u);
+        const uint64_t e_hard = oq * K, e = oq * f > e_hard / scale ? e_hard : oq * f * scale;
+        st.ids_cap.rq_cap = (uint32_t)oq;
+        st.ids_cap.ent_cap = (e > e_hard ? e_hard : e) + 64;
+        const size_t iw = (size_t)tps_ids_words(st.ids_cap), sw = (size_t)st.tp_cap + 1;
+        int rc = dev_alloc(&st.d_ids, iw);
+        if (!rc) rc = dev_alloc(&st.d_ids_recv, (size_t)W * iw);
+        if (!rc) rc = dev_alloc(&st.d_seg_send, (size_t)W * sw);
+        if (!rc) rc = dev_alloc(&st.d_seg_recv, (size_t)W * sw);
+        if (!rc) rc = dev_alloc(&st.d_tps_words, (size_t)oq + 1);
+        if (!rc) rc = dev_alloc(&st.d_tps_n, (size_t)2 * W);
+        if (!rc) rc = dev_alloc(&st.d_tps_base, (size_t)W * (oq + 1));
+        if (rc) { shard_tps_free(st); st.tp_k = 0; st.tp_scale = 0; return rc; }
+        st.tp_k = K; st.tp_scale = scale;
     }
     int rc = dev_grow(&st.d_seqs, &st.seq_cap, (size_t)seq_bytes + 16);
     if (!rc) rc = dev_grow(&st.d_off, &st.off_cap, (size_t)n_seqs + 1);
-    if (!rc && !b.full) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K));
+    if (!rc && !b.full) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K, b.tpos ? st.tp_cap : 0));
     return rc;
 }
 
@@ -251,6 +391,8 @@ struct kaamer_sharded_ticket {
     kaamer_topn_opts top;
     ShardBounds b;
     bool adaptive;   // this attempt's exchange blocks were sized from the previous call's need, not the capacity
+    bool pos_only;   // the attempt failed on the reported hits' ids blocks / bitmap segments alone (ST_IDS_CAP, ST_POS_CAP):
+                     // only their bound (BatchBounds::pos_scale) grows, and only their buffers are made again
     int attempt;
 };
 // a full call (kaamer_sharded_search_batch): the same pipeline without the post-steps (t.b.full)
@@ -268,6 +410,21 @@ static void sharded_release(kaamer_sharded_index *sx, ShardSet *set)
 {
     { std::lock_guard<std::mutex> lock(sx->mu); set->busy = false; }
     sx->cv.notify_one();
+}
+
+// the speculative copy of an owner's result block: as much as the previous call's block took (plus a quarter)
+static int sharded_copy_back(ShardState &ow)
+{
+    size_t want = ow.guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : ow.guess;
+    if (want > ow.d_block_cap) want = ow.d_block_cap;
+    if (ow.h_block_cap < want) {
+        if (ow.h_block) pinned_put(ow.h_block, ow.h_block_cap);
+        ow.h_block = (uint8_t *)pinned_get(want, &ow.h_block_cap);
+        if (!ow.h_block) { ow.h_block_cap = 0; return kaamer_fail(KAAMER_E_NOMEM, "pinned result block"); }
+    }
+    HIPCHK(hipMemcpyAsync(ow.h_block, ow.d_block, want, hipMemcpyDeviceToHost, ow.stream));
+    ow.copied = want;
+    return KAAMER_OK;
 }
 
 // the batch (in the set's pinned staging) onto every shard's stream: search, pack, peer copies, merge, post-steps, result
@@ -291,7 +448,8 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
     }
     // the blocks of this batch: what the previous batch on this set needed + a quarter (its W x W headers, read after the
     // call), or the capacity for a first call and for a retry.  What the peer copies move is payload, not capacity.
-    t->adaptive = t->attempt == 0 && sx->need_entries != 0 && (!t->b.pos || sx->need_pos_words != 0);
+    t->adaptive = t->attempt == 0 && sx->need_entries != 0 && (!t->b.pos || sx->need_pos_words != 0) && (!t->b.tpos || sx->tp_seen);
+    const uint32_t seq = ++sx->seq;
     for (uint32_t s = 0; s < W; s++) {
         ShardState &st = sh[s];
         st.wire = st.layout;
@@ -301,6 +459,17 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
             const int rc = t->b.pos ? kaamer_exchange_layout_fit_positions(&st.layout, nq, ne, sx->need_pos_words + sx->need_pos_words / 4 + 1024, &st.wire)
                                     : kaamer_exchange_layout_fit(&st.layout, nq, ne, (nucl || t->b.full) ? 1 : 0, &st.wire);
             if (rc) return rc;
+        }
+        if (t->b.tpos) {   // the ids blocks and bitmap segments of this batch: sized the same way
+            st.ids_wire = st.ids_cap;
+            st.tp_wire = st.tp_cap;
+            if (t->adaptive) {
+                const uint64_t rq = (uint64_t)sx->need_ids_rq + sx->need_ids_rq / 4 + 64, ne = sx->need_ids_ent + sx->need_ids_ent / 4 + 1024,
+                               nw = sx->need_tp_words + sx->need_tp_words / 4 + 1024;
+                if (rq < st.ids_cap.rq_cap) st.ids_wire.rq_cap = (uint32_t)rq;
+                if (ne < st.ids_cap.ent_cap) st.ids_wire.ent_cap = ne;
+                if (nw < st.tp_cap) st.tp_wire = nw;
+            }
         }
     }
     // ---- every shard: the whole batch against its keys, partial hit lists packed per owner
@@ -342,16 +511,57 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
         int rc = kaamer_exchange_merge(ow.mws, &ow.wire, ow.d_recv, ow.stream, &mr);
         if (!rc) rc = kaamer_topn_device(ow.mws, &tt, ow.stream, &tr);
         if (!rc) rc = topn_pack_block(ow.mws, ow.ws, d, W, &tr, ow.stream, ow.d_block, ow.d_block_cap);
-        if (rc) return rc;
-        size_t want = ow.guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : ow.guess;
-        if (want > ow.d_block_cap) want = ow.d_block_cap;
-        if (ow.h_block_cap < want) {
-            if (ow.h_block) pinned_put(ow.h_block, ow.h_block_cap);
-            ow.h_block = (uint8_t *)pinned_get(want, &ow.h_block_cap);
-            if (!ow.h_block) { ow.h_block_cap = 0; return kaamer_fail(KAAMER_E_NOMEM, "pinned result block"); }
+        if (!rc && t->b.tpos) {   // the result block waits for its bitmaps (below)
+            rc = tps_enqueue_ids_pack(ow.mws, &tr, ow.d_block, ow.d_block_cap, ow.d_ids, ow.ids_wire, d, W, seq, ow.stream);
+            if (rc) return rc;
+            HIPCHK(hipEventRecord(ow.ev_ids, ow.stream));
+            continue;
         }
-        HIPCHK(hipMemcpyAsync(ow.h_block, ow.d_block, want, hipMemcpyDeviceToHost, ow.stream));
-        ow.copied = want;
+        if (rc) return rc;
+        rc = sharded_copy_back(ow);
+        if (rc) return rc;
+    }
+    if (t->b.tpos) {
+        const uint32_t K = t->top.max_results;
+        // ---- every shard: pulls the W ids blocks, its partial bitmaps of each owner's reported hits into segment d
+        for (uint32_t s = 0; s < W; s++) {
+            ShardState &st = sh[s];
+            HIPCHK(hipSetDevice(st.device));
+            const size_t iw = (size_t)tps_ids_words(st.ids_wire), sw = (size_t)st.tp_wire + 1, bw = (size_t)st.ids_wire.rq_cap + 1;
+            for (uint32_t d = 0; d < W; d++) {
+                ShardState &ow = sh[d];
+                if (d != s) HIPCHK(hipStreamWaitEvent(st.stream, ow.ev_ids, 0));
+                uint32_t *to = st.d_ids_recv + (size_t)d * iw;
+                if (ow.device == st.device) HIPCHK(hipMemcpyAsync(to, ow.d_ids, iw * 4, hipMemcpyDeviceToDevice, st.stream));
+                else HIPCHK(hipMemcpyPeerAsync(to, st.device, ow.d_ids, ow.device, iw * 4, st.stream));
+            }
+            for (uint32_t d = 0; d < W; d++) {
+                const uint32_t *ids = st.d_ids_recv + (size_t)d * iw;
+                int rc = tps_enqueue_words(st.ix, st.ws, ids, st.ids_wire, d, W, seq, K, st.d_tps_n + 2 * d, st.d_tps_words, st.d_tps_base + (size_t)d * bw, st.stream);
+                if (!rc) rc = tps_enqueue_bits(st.ix, st.ws, ids, st.ids_wire, d, W, seq, K, st.d_tps_n + 2 * d, st.d_tps_base + (size_t)d * bw,
+                                               st.d_seg_send + (size_t)d * sw, st.tp_wire, st.stream);
+                if (rc) return rc;
+            }
+            HIPCHK(hipEventRecord(st.ev_bits, st.stream));
+        }
+        // ---- every owner: pulls segment d of every shard, ORs them into its result block, one D2H
+        for (uint32_t d = 0; d < W; d++) {
+            ShardState &ow = sh[d];
+            HIPCHK(hipSetDevice(ow.device));
+            const size_t iw = (size_t)tps_ids_words(ow.ids_wire), sw = (size_t)ow.tp_wire + 1, bw = (size_t)ow.ids_wire.rq_cap + 1;
+            for (uint32_t s = 0; s < W; s++) {
+                ShardState &src = sh[s];
+                if (s != d) HIPCHK(hipStreamWaitEvent(ow.stream, src.ev_bits, 0));
+                const unsigned long long *from = src.d_seg_send + (size_t)d * sw;
+                unsigned long long *to = ow.d_seg_recv + (size_t)s * sw;
+                if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, sw * 8, hipMemcpyDeviceToDevice, ow.stream));
+                else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, sw * 8, ow.stream));
+            }
+            int rc = tps_enqueue_or(ow.ix, ow.mws, ow.ws, ow.d_block, ow.d_block_cap, ow.d_ids_recv + (size_t)d * iw, ow.ids_wire, d, W, seq,
+                                    ow.d_tps_n + 2 * d, ow.d_tps_base + (size_t)d * bw, ow.d_seg_recv, sw, ow.tp_wire, ow.stream);
+            if (!rc) rc = sharded_copy_back(ow);
+            if (rc) return rc;
+        }
     }
     guard.armed = false;
     return KAAMER_OK;
@@ -372,12 +582,14 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     } guard{ sx, true };
     int err = KAAMER_OK;
     char why[256] = "";
+    t->pos_only = true;   // (read only on the KAAMER_E_CAPACITY path of kaamer_sharded_wait_batch_top: cleared by any other failure bit)
     for (uint32_t d = 0; d < W; d++) {
         ShardState &ow = sh[d];
         HIPCHK(hipSetDevice(ow.device));
         HIPCHK(hipStreamSynchronize(ow.stream));
         const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(ow.h_block);
         const uint32_t status = hdr->status & 0x7FFFFFFFu;
+        if (hdr->status & ~(uint32_t)(ST_POS_CAP | ST_IDS_CAP)) t->pos_only = false;
         if (status) { ow.mws->clean = false; ow.ws->clean = false; }
         int rc = status_to_error(status, ow.mws);
         if (!rc && (hdr->status & 0x80000000u)) rc = kaamer_fail(KAAMER_E_CAPACITY, "result block capacity exceeded");
@@ -395,7 +607,10 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
                     snprintf(why, sizeof why, "shard %u: search status 0x%x (%s%s%s)", bad, sst, (sst & ST_POOL_FULL) ? "hit pool " : "",
                              (sst & (ST_G_ARENA_FULL | ST_G_TABLE_FULL)) ? "G-tier arena " : "", (sst & (ST_QUERY_CAP | ST_AA_CAP)) ? "ORF capacity " : "");
                 else
-                    snprintf(why, sizeof why, "owner %u: merge status 0x%x (%s)", d, status, (status & ST_EXCHANGE_CAP) ? "an exchange block overflowed" : "merge bounds");
+                    snprintf(why, sizeof why, "owner %u: merge status 0x%x (%s)", d, status,
+                             (status & ST_POS_CAP) ? "the reported hits' bitmaps exceed a segment" :
+                             (status & ST_IDS_CAP) ? "the reported hits' ids exceed an ids block" :
+                             (status & ST_EXCHANGE_CAP) ? "an exchange block overflowed" : "merge bounds");
                 err = rc;
             }
             continue;
@@ -421,8 +636,26 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     }
     if (err) return kaamer_fail(err, "sharded search: %s", why);
     // ---- interleave the owners' reported queries back into batch order
-    uint64_t n_rep = 0, n_ent = 0, n_aa = 0, nq = 0;
+    const bool tpos = t->b.tpos;
+    uint64_t n_rep = 0, n_ent = 0, n_aa = 0, nq = 0, n_words = 0;
     std::vector<batch_top_owner> view(W);
+    std::vector<const RepPosExt *> px(W, nullptr);
+    if (tpos) {   // what the ids blocks and segments of this batch needed: sizes the next call's
+        sx->need_ids_rq = 0; sx->need_ids_ent = 0; sx->need_tp_words = 0;
+        for (uint32_t d = 0; d < W; d++) {
+            const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
+            px[d] = reinterpret_cast<const RepPosExt *>(hdr->reserved);
+            if (!px[d]->off_pos_bits) return kaamer_fail(KAAMER_E_HIP, "sharded search: owner %u returned a block without its bitmap sections", d);
+            if (hdr->n_rep > sx->need_ids_rq) sx->need_ids_rq = hdr->n_rep;
+            if (hdr->n_ent > sx->need_ids_ent) sx->need_ids_ent = hdr->n_ent;
+            if (px[d]->n_pos_words > sx->need_tp_words) sx->need_tp_words = px[d]->n_pos_words;
+            n_words += px[d]->n_pos_words;
+        }
+        sx->tp_seen = true;
+        sx->tp_ids_bytes = 4ull * tps_ids_words(sh[0].ids_wire);
+        sx->tp_seg_bytes = 8ull * (sh[0].tp_wire + 1);
+        sx->tp_attempts = (uint64_t)t->attempt + 1;
+    }
     for (uint32_t d = 0; d < W; d++) {
         view[d].block = sh[d].h_block;
         top_owner_fill(&view[d]);
@@ -447,7 +680,9 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     }
     const size_t o_rq = 0, o_trim = rep_align8(o_rq + 4 * n_rep), o_q = rep_align8(o_trim + 4 * n_rep),
                  o_off = rep_align8(o_q + sizeof(kaamer_query_meta) * n_rep), o_pid = o_off + 8 * (n_rep + 1), o_km = rep_align8(o_pid + 4 * n_ent),
-                 o_fp = rep_align8(o_km + 4 * n_ent), o_aa = rep_align8(o_fp + 4 * n_ent), total = rep_align8(o_aa + n_aa) + 8;
+                 o_fp = rep_align8(o_km + 4 * n_ent), o_aa = rep_align8(o_fp + 4 * n_ent), o_plen = rep_align8(o_aa + n_aa) + 8,
+                 o_poff = rep_align8(o_plen + (tpos ? 4 * n_rep : 0)), o_pbits = o_poff + (tpos ? 8 * (n_ent + 1) : 0),
+                 total = o_pbits + (tpos ? 8 * n_words : 0) + 8;
     batch_top_owner *bo = new (std::nothrow) batch_top_owner();
     uint8_t *blk = bo ? (uint8_t *)malloc(total) : nullptr;
     if (!bo || !blk) { delete bo; free(blk); return kaamer_fail(KAAMER_E_NOMEM, "merged result (%zu bytes)", total); }
@@ -458,8 +693,10 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     uint64_t *off = (uint64_t *)(blk + o_off);
     uint32_t *pid = (uint32_t *)(blk + o_pid), *km = (uint32_t *)(blk + o_km), *fp = (uint32_t *)(blk + o_fp);
     uint8_t *aa = blk + o_aa;
+    int32_t *plen = (int32_t *)(blk + o_plen);
+    uint64_t *poff = (uint64_t *)(blk + o_poff), *pbits = (uint64_t *)(blk + o_pbits);
     std::vector<uint32_t> cur(W, 0);
-    uint64_t r = 0, e = 0, a = 0;
+    uint64_t r = 0, e = 0, a = 0, w = 0;
     for (;;) {  // W-way merge by global query index (each owner's list ascends)
         uint32_t best = W;
         uint64_t best_q = ~0ull;
@@ -479,6 +716,15 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
         memcpy(pid + e, v.top_pid + b0, (b1 - b0) * 4);
         memcpy(km + e, v.top_kmatch + b0, (b1 - b0) * 4);
         memcpy(fp + e, v.top_first_pos + b0, (b1 - b0) * 4);
+        if (tpos) {   // the owner's bitmaps of the query are contiguous: re-based as a whole
+            const uint8_t *ob = view[best].block;
+            const uint64_t *v_off = reinterpret_cast<const uint64_t *>(ob + px[best]->off_pos_off);
+            const uint64_t w0 = v_off[b0], w1 = v_off[b1];
+            plen[r] = reinterpret_cast<const int32_t *>(ob + px[best]->off_pos_len)[i];
+            for (uint64_t j = b0; j < b1; j++) poff[e + (j - b0)] = w + (v_off[j] - w0);
+            memcpy(pbits + w, reinterpret_cast<const uint64_t *>(ob + px[best]->off_pos_bits) + w0, (w1 - w0) * 8);
+            w += w1 - w0;
+        }
         e += b1 - b0;
         if (nucl) {
             memcpy(aa + a, v.orf_aa + v.q[i].aa_off, v.q[i].aa_len);
@@ -488,6 +734,11 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
         r++;
     }
     off[r] = e;
+    if (tpos) {
+        poff[e] = w;
+        bo->has_pos = true;
+        bo->m_pos_len = plen; bo->m_pos_off = poff; bo->m_pos_bits = pbits;
+    }
     memset(&bo->pub, 0, sizeof bo->pub);
     bo->pub.n_queries = (uint32_t)nq;
     bo->pub.n_reported = (uint32_t)n_rep;
@@ -504,7 +755,8 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
 // workspaces, buffers and streams (callers beyond the sets wait for one), copies the caller's buffers into the set's
 // pinned staging and enqueues the whole batch on every device; wait collects it.  A ticket is waited for exactly once.
 // top = NULL: a full call (kaamer_sharded_submit_batch_flat), `t` is then the caller's (a kaamer_sharded_full_ticket's)
-static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket *t)
+static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket *t,
+                          bool top_pos)
 {
     ShardSet *set = nullptr;
     {
@@ -524,6 +776,7 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     t->b.e_cap = 2 * t->seq_bytes / sx->n + 65536;
     t->b.full = top == nullptr;
     t->b.pos = t->b.full && in->want_positions != 0;
+    t->b.tpos = !t->b.full && top_pos;   // the bitmaps of the reported hits (kaamer_sharded_submit_batch_top_pos_flat)
     if (t->b.pos) {   // bitmap words per entry ~ 1 + SizeInKmer / 64 (ORFs: a third of the nucleotides)
         const bool nucl = is_nucl(in->seq_type);
         const uint64_t mean = t->seq_bytes / (in->n_seqs ? in->n_seqs : 1u) / (nucl ? 3u : 1u);
@@ -549,17 +802,22 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     return rc;
 }
 
-int kaamer_sharded_submit_batch_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket **ticket)
+static int sharded_submit_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool top_pos, kaamer_sharded_ticket **ticket)
 {
     if (!sx || !in || !top || !ticket || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
         return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top: bad argument");
     *ticket = nullptr;
     kaamer_sharded_ticket *t = new (std::nothrow) kaamer_sharded_ticket();
     if (!t) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
-    const int rc = sharded_submit(sx, in, top, t);
+    const int rc = sharded_submit(sx, in, top, t, top_pos);
     if (rc) { delete t; return rc; }
     *ticket = t;
     return KAAMER_OK;
+}
+
+int kaamer_sharded_submit_batch_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket **ticket)
+{
+    return sharded_submit_top(sx, in, top, false, ticket);
 }
 
 int kaamer_sharded_wait_batch_top(kaamer_sharded_ticket *t, kaamer_batch_top **out)
@@ -572,9 +830,10 @@ int kaamer_sharded_wait_batch_top(kaamer_sharded_ticket *t, kaamer_batch_top **o
         if (rc != KAAMER_E_CAPACITY || t->attempt >= MAX_BOUND_RETRIES) break;
         t->attempt++;
         if (!t->adaptive) {
-            // the bounds themselves were too small: enlarge them all (hit pool included: the unsharded call does the same)
-            t->b.e_cap *= 4;
-            bounds_grow(t->b.bb, t->seq_bytes, t->n_seqs, is_nucl(t->seq_type));
+            // the bounds themselves were too small: enlarge them all (hit pool included: the unsharded call does the same),
+            // or the bitmap segments alone when nothing else was exceeded
+            if (t->pos_only) bounds_grow_positions(t->b.bb);
+            else { t->b.e_cap *= 4; bounds_grow(t->b.bb, t->seq_bytes, t->n_seqs, is_nucl(t->seq_type)); }
         }   // else: the blocks sized from the previous call were too small -- once more at the full capacity, same bounds
         rc = sharded_enqueue(t);   // (an error here ends the loop, E_CAPACITY included: kept as it was)
         if (rc) break;
@@ -620,6 +879,43 @@ int kaamer_sharded_search_batch_top_flat(kaamer_sharded_index *sx, const uint8_t
     const int rc = kaamer_sharded_submit_batch_top_flat(sx, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, &t);
     if (rc) return rc;
     return kaamer_sharded_wait_batch_top(t, out);
+}
+
+// ---- the same calls with the PositionHits bitmaps of the reported hits (search.go:442-452,520-522) ---------------------
+int kaamer_sharded_submit_batch_top_pos_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                             double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_sharded_ticket **ticket)
+{
+    kaamer_batch_in in;
+    kaamer_topn_opts top;
+    flat_in(&in, seqs, offsets, n_seqs, seq_type, 1);
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    return sharded_submit_top(sx, &in, &top, true, ticket);
+}
+
+int kaamer_sharded_search_batch_top_pos_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                             double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_sharded_ticket *t = nullptr;
+    const int rc = kaamer_sharded_submit_batch_top_pos_flat(sx, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, &t);
+    if (rc) return rc;
+    return kaamer_sharded_wait_batch_top(t, out);
+}
+
+// the ids blocks and bitmap segments of the last finished call with positions on the handle's first set (tests, bench):
+// out = { bytes of one ids block as it travelled, bytes of one (shard -> owner) bitmap segment as it travelled, bitmap
+// words the largest segment needed, attempts the call took }
+int kaamer_sharded_positions_info(kaamer_sharded_index *sx, uint64_t out[4])
+{
+    if (!sx || !out) return kaamer_fail(KAAMER_E_ARG, "sharded_positions_info: bad argument");
+    std::lock_guard<std::mutex> lock(sx->mu);
+    const ShardSet &set = sx->sets[0];
+    if (!set.tp_seen) return kaamer_fail(KAAMER_E_ARG, "sharded_positions_info: no call with positions yet");
+    out[0] = set.tp_ids_bytes;
+    out[1] = set.tp_seg_bytes;
+    out[2] = set.need_tp_words;
+    out[3] = set.tp_attempts;
+    return KAAMER_OK;
 }
 
 // ---- full hit lists (kaamer_sharded_search_batch) ----------------------------------------------------------------------
@@ -785,7 +1081,7 @@ int kaamer_sharded_submit_batch_flat(kaamer_sharded_index *sx, const uint8_t *se
     flat_in(&in, seqs, offsets, n_seqs, seq_type, want_positions);
     kaamer_sharded_full_ticket *ft = new (std::nothrow) kaamer_sharded_full_ticket();
     if (!ft) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
-    const int rc = sharded_submit(sx, &in, nullptr, &ft->t);
+    const int rc = sharded_submit(sx, &in, nullptr, &ft->t, false);
     if (rc) { delete ft; return rc; }
     *ticket = ft;
     return KAAMER_OK;

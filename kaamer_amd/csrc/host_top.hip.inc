@@ -20,6 +20,9 @@ struct batch_top_owner {
     size_t block_cap = 0;
     bool pinned = true;        // from the pinned cache (else malloc: the interleaved result of a sharded index)
     bool has_pos = false;      // the block carries the bitmap sections (RepPosExt, top_positions.hip.inc)
+    // ... or, in the interleaved result of a sharded index (no RepBlockHdr), the three arrays are at these places
+    const int32_t *m_pos_len = nullptr;
+    const uint64_t *m_pos_off = nullptr, *m_pos_bits = nullptr;
 };
 
 struct kaamer_ticket {
@@ -460,6 +463,12 @@ int kaamer_batch_top_positions(const kaamer_batch_top *out, const int32_t **pos_
     if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_positions: bad argument");
     const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
     if (!bo->has_pos || !bo->block) return KAAMER_OK;   // not asked for positions: all NULL
+    if (bo->m_pos_off) {
+        if (pos_bits_len) *pos_bits_len = bo->m_pos_len;
+        if (pos_off) *pos_off = bo->m_pos_off;
+        if (pos_bits) *pos_bits = bo->m_pos_bits;
+        return KAAMER_OK;
+    }
     const RepBlockHdr *h = reinterpret_cast<const RepBlockHdr *>(bo->block);
     const RepPosExt *x = reinterpret_cast<const RepPosExt *>(h->reserved);
     if (!x->off_pos_bits) return KAAMER_OK;

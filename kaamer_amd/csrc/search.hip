@@ -95,6 +95,12 @@ static const int MAX_BOUND_RETRIES = 6;
 // where the full-list calls start (the top-N calls start from 0, the workspace's own default)
 static uint64_t full_start_hits(uint64_t seq_bytes) { return seq_bytes * 8 + 65536; }
 
+// the bitmaps of the reported hits alone (a batch that exceeded nothing else)
+static void bounds_grow_positions(BatchBounds &b)
+{
+    b.pos_scale = b.pos_scale ? (b.pos_scale < (1u << 24) ? b.pos_scale * 4 : b.pos_scale) : 4;
+}
+
 static void bounds_grow(BatchBounds &b, uint64_t seq_bytes, uint32_t n_seqs, bool nucl)
 {
     b.max_hits = b.max_hits ? b.max_hits * 4 : full_start_hits(seq_bytes);
@@ -103,7 +109,7 @@ static void bounds_grow(BatchBounds &b, uint64_t seq_bytes, uint32_t n_seqs, boo
         const uint64_t hard = seq_bytes / 10 + (uint64_t)n_seqs * 6 + 64;
         b.max_queries = (uint32_t)(hard > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : hard);
     }
-    b.pos_scale = b.pos_scale ? (b.pos_scale < (1u << 24) ? b.pos_scale * 4 : b.pos_scale) : 4;
+    bounds_grow_positions(b);
 }
 
 // one in-flight call of the pipelined host-buffer boundary (host_top.hip.inc)
@@ -143,7 +149,8 @@ struct kaamer_index {
 };
 
 enum { ST_POOL_FULL = 1u, ST_LIST_FULL = 2u, ST_QUERY_CAP = 4u, ST_AA_CAP = 8u, ST_G_ARENA_FULL = 16u, ST_G_TABLE_FULL = 32u,
-       ST_POS_UNSUPPORTED = 64u, ST_POS_CAP = 128u, ST_CHAIN_TIMEOUT = 256u, ST_EXCHANGE_CAP = 512u, ST_PEER_FAILED = 1024u };
+       ST_POS_UNSUPPORTED = 64u, ST_POS_CAP = 128u, ST_CHAIN_TIMEOUT = 256u, ST_EXCHANGE_CAP = 512u, ST_PEER_FAILED = 1024u,
+       ST_IDS_CAP = 2048u /* an ids block of the sharded handle (top_positions_sharded.hip.inc) */ };
 enum { CTR_IN = 0, CTR_QUERIES, CTR_LOOKUP, CTR_PROBE, CTR_FOUND, CTR_POST, CTR_HITS, CTR_OVERFLOW, CTR_LISTS, CTR_LIST_IDS, CTR_N };
 static_assert(sizeof(kaamer_counters) == CTR_N * 8, "counter layout");
 #define CTR_REPLICAS 64
@@ -1480,6 +1487,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const uint32_t *
 }
 
 #include "exchange.hip.inc"
+#include "top_positions_sharded.hip.inc"
 
 // optional compaction: sharded hit arrays -> CSR in query order (one wave per query)
 __global__ __launch_bounds__(256) void gather_hits_kernel(const uint32_t *d_nq, const uint64_t *csr_off, const uint64_t *hit_off,
@@ -2961,7 +2969,8 @@ int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void 
     p.hit_off = ws->compact ? ws->d_csr_off : ws->d_hit_off;
     p.pid = ws->compact ? ws->d_c_pid : ws->d_hit_pid;
     p.km = ws->compact ? ws->d_c_km : ws->d_hit_km;
-    p.fp = ws->compact ? ws->d_c_fp : ws->d_hit_fp;
+    // without first positions top_first_pos is zeros (kaamer_hip.h), whatever the counting tiers left in the hit arrays
+    p.fp = !ws->firstpos ? nullptr : ws->compact ? ws->d_c_fp : ws->d_hit_fp;
     p.orf_aa = src->d_orf_aa;
     p.starts_alt = src->d_starts_alt;
     p.min_k_ratio = opts->min_k_ratio;

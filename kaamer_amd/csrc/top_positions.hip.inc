@@ -21,6 +21,8 @@
 // The same kernel serves both forms of the call: the device-resident one writes into the workspace's own storage, the
 // host-buffer one appends three sections to the packed result block (topn.hip.inc) behind rep_block_kernel:
 //   ... | pos_bits_len i32[n_rep] | pos_off u64[n_ent + 1] (CSR, in words) | pos_bits u64[pos_off[n_ent]]
+// tp_query_bits (the bitmaps of one reported query) and tp_block_sections (where the three sections go) are shared with
+// the sharded handle's kernels (top_positions_sharded.hip.inc), where every shard makes the part its own vals[] gives.
 #define TP_WAVES 4
 #define TP_COOP_MIN 16u   /* ids; longer lists are scanned by the whole wave */
 
@@ -78,6 +80,90 @@ __device__ __forceinline__ unsigned long long tp_match(const uint32_t *pid, uint
     return m;
 }
 
+// The bitmap sections behind a block that rep_block_kernel laid out from the three totals (n_rep, n_ent, n_aa); `total`
+// bitmap words are wanted, `cap` is the bound.  Every thread computes the same; `first` (one thread of the grid) writes
+// the header.  0: rep_block_kernel flagged the block, nothing was laid out; -1: the words do not fit (ST_POS_CAP is set:
+// a bound like every other, the whole batch is repeated with a larger one, never a partial block); 1: laid out.
+__device__ __forceinline__ int tp_block_sections(uint8_t *block, uint64_t block_cap, uint64_t n_rep, uint64_t n_ent, uint64_t n_aa,
+                                                 uint64_t total, uint64_t cap, bool first, RepPosExt *xo)
+{
+    uint64_t o = rep_align8(sizeof(RepBlockHdr) + 4 * n_rep);              // rep_query
+    o = rep_align8(o + 4 * n_rep);                                          // trim
+    o = rep_align8(o + sizeof(kaamer_query_meta) * n_rep);                  // q
+    o = o + 8 * (n_rep + 1);                                                // top_off
+    o = rep_align8(o + 4 * n_ent);                                          // pid
+    o = rep_align8(o + 4 * n_ent);                                          // kmatch
+    o = rep_align8(o + 4 * n_ent);                                          // first_pos
+    const uint64_t base_total = rep_align8(o + n_aa);                       // orf_aa
+    if (base_total > block_cap) return 0;
+    RepPosExt x;
+    x.off_pos_len = base_total;
+    x.off_pos_off = rep_align8(x.off_pos_len + 4 * n_rep);
+    x.off_pos_bits = x.off_pos_off + 8 * (n_ent + 1);
+    x.n_pos_words = total;
+    RepBlockHdr *hdr = reinterpret_cast<RepBlockHdr *>(block);
+    const bool fits = total <= cap && x.off_pos_bits <= block_cap && total <= (block_cap - x.off_pos_bits) / 8;
+    if (!fits) {
+        if (first) hdr->status |= (uint32_t)ST_POS_CAP;
+        return -1;
+    }
+    if (first) {
+        *reinterpret_cast<RepPosExt *>(hdr->reserved) = x;
+        hdr->total_bytes = x.off_pos_bits + 8 * total;
+        reinterpret_cast<uint64_t *>(block + x.off_pos_off)[n_ent] = total;   // CSR end
+    }
+    *xo = x;
+    return 1;
+}
+
+// The bitmaps of ONE reported query, by one wave: `ids[0..cnt)` its reported protein ids, `vals[0..size)` the probe's
+// words of its residue positions, out[r * nw + stripe] word `stripe` of reported hit r (nw = ceil(size / 64) > 0).
+// `pid`: 64 words of LDS of this wave.  vals[] of a shard image hold the keys that shard owns: the result is then the
+// bitmap restricted to those positions.
+__device__ __forceinline__ void tp_query_bits(uint32_t *pid, const uint32_t *ids, uint32_t cnt, const uint32_t *vals, uint32_t size,
+                                              const uint32_t *arena, unsigned long long *out, uint32_t lane)
+{
+    const uint32_t nw = (size + 63u) >> 6;
+    for (uint32_t r0 = 0; r0 < cnt; r0 += 64) {   // cnt <= K; K may exceed 64
+        const uint32_t nr = cnt - r0 < 64u ? cnt - r0 : 64u;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous round's readers are done
+        __builtin_amdgcn_wave_barrier();
+        pid[lane] = lane < nr ? ids[r0 + lane] : KH_EMPTY_PID;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t st = 0; st < nw; st++) {
+            const uint32_t pos = (st << 6) + lane;
+            const uint32_t v = pos < size ? vals[pos] : 0u;
+            unsigned long long mask = 0ull;
+            uint32_t n_ids = 0;
+            if (v & KH_INLINE_BIT) mask = tp_match(pid, nr, v & ~KH_INLINE_BIT);
+            else if (v) {
+                const uint32_t *l = arena + (uint64_t)v * 4;   // {count, ids...}
+                n_ids = l[0];
+                if (n_ids <= TP_COOP_MIN)
+                    for (uint32_t t = 0; t < n_ids; t++) mask |= tp_match(pid, nr, l[1 + t]);
+            }
+            unsigned long long todo = __ballot(n_ids > TP_COOP_MIN);
+            while (todo) {   // wave-uniform: the long lists of this stripe, one after the other
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const uint32_t lv = (uint32_t)__shfl((int)v, src, 64), ln = (uint32_t)__shfl((int)n_ids, src, 64);
+                const uint32_t *lids = arena + (uint64_t)lv * 4 + 1;
+                unsigned long long m = 0ull;
+                for (uint32_t t = lane; t < ln; t += 64) m |= tp_match(pid, nr, lids[t]);
+                m = wave_or_u64(m);
+                if ((int)lane == src) mask = m;
+            }
+            unsigned long long mine = 0ull;
+            for (uint32_t j = 0; j < nr; j++) {
+                const unsigned long long b = __ballot((mask >> j) & 1ull);
+                if (lane == j) mine = b;
+            }
+            if (lane < nr) out[(uint64_t)(r0 + lane) * nw + st] = mine;
+        }
+    }
+}
+
 __global__ __launch_bounds__(64 * TP_WAVES) void top_pos_bits_kernel(TopPosParams p)
 {
     __shared__ uint32_t s_pid[TP_WAVES][64];
@@ -91,32 +177,8 @@ __global__ __launch_bounds__(64 * TP_WAVES) void top_pos_bits_kernel(TopPosParam
     uint64_t *rep_poff = nullptr;
     if (p.block) {
         // the sections rep_block_kernel wrote, from the same three totals (every thread computes the same)
-        const uint64_t n_rep = p.rank[nq], n_ent = p.eoff[nq], n_aa = p.aoff[nq];
-        uint64_t o = rep_align8(sizeof(RepBlockHdr) + 4 * n_rep);              // rep_query
-        o = rep_align8(o + 4 * n_rep);                                          // trim
-        o = rep_align8(o + sizeof(kaamer_query_meta) * n_rep);                  // q
-        o = o + 8 * (n_rep + 1);                                                // top_off
-        o = rep_align8(o + 4 * n_ent);                                          // pid
-        o = rep_align8(o + 4 * n_ent);                                          // kmatch
-        o = rep_align8(o + 4 * n_ent);                                          // first_pos
-        const uint64_t base_total = rep_align8(o + n_aa);                       // orf_aa
-        if (base_total > p.block_cap) return;   // rep_block_kernel flagged the block: nothing was laid out
         RepPosExt x;
-        x.off_pos_len = base_total;
-        x.off_pos_off = rep_align8(x.off_pos_len + 4 * n_rep);
-        x.off_pos_bits = x.off_pos_off + 8 * (n_ent + 1);
-        x.n_pos_words = total;
-        RepBlockHdr *hdr = reinterpret_cast<RepBlockHdr *>(p.block);
-        const bool fits = total <= cap && x.off_pos_bits <= p.block_cap && total <= (p.block_cap - x.off_pos_bits) / 8;
-        if (!fits) {   // a bound like every other: the whole batch is repeated with a larger one, never a partial block
-            if (first) hdr->status |= (uint32_t)ST_POS_CAP;
-            return;
-        }
-        if (first) {
-            *reinterpret_cast<RepPosExt *>(hdr->reserved) = x;
-            hdr->total_bytes = x.off_pos_bits + 8 * total;
-            reinterpret_cast<uint64_t *>(p.block + x.off_pos_off)[n_ent] = total;   // CSR end
-        }
+        if (tp_block_sections(p.block, p.block_cap, p.rank[nq], p.eoff[nq], p.aoff[nq], total, cap, first, &x) <= 0) return;
         rep_len = reinterpret_cast<int32_t *>(p.block + x.off_pos_len);
         rep_poff = reinterpret_cast<uint64_t *>(p.block + x.off_pos_off);
         bits = reinterpret_cast<unsigned long long *>(p.block + x.off_pos_bits);
@@ -143,43 +205,6 @@ __global__ __launch_bounds__(64 * TP_WAVES) void top_pos_bits_kernel(TopPosParam
         if (nw == 0) continue;
         const uint32_t *vals = p.vals + qi.aa_off;
         unsigned long long *out = bits + qbase;
-        for (uint32_t r0 = 0; r0 < cnt; r0 += 64) {   // cnt <= K; K may exceed 64
-            const uint32_t nr = cnt - r0 < 64u ? cnt - r0 : 64u;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous round's readers are done
-            __builtin_amdgcn_wave_barrier();
-            pid[lane] = lane < nr ? p.top_pid[q * p.K + r0 + lane] : KH_EMPTY_PID;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            for (uint32_t st = 0; st < nw; st++) {
-                const uint32_t pos = (st << 6) + lane;
-                const uint32_t v = pos < size ? vals[pos] : 0u;
-                unsigned long long mask = 0ull;
-                uint32_t n_ids = 0;
-                if (v & KH_INLINE_BIT) mask = tp_match(pid, nr, v & ~KH_INLINE_BIT);
-                else if (v) {
-                    const uint32_t *l = p.arena + (uint64_t)v * 4;   // {count, ids...}
-                    n_ids = l[0];
-                    if (n_ids <= TP_COOP_MIN)
-                        for (uint32_t t = 0; t < n_ids; t++) mask |= tp_match(pid, nr, l[1 + t]);
-                }
-                unsigned long long todo = __ballot(n_ids > TP_COOP_MIN);
-                while (todo) {   // wave-uniform: the long lists of this stripe, one after the other
-                    const int src = __ffsll((long long)todo) - 1;
-                    todo &= todo - 1ull;
-                    const uint32_t lv = (uint32_t)__shfl((int)v, src, 64), ln = (uint32_t)__shfl((int)n_ids, src, 64);
-                    const uint32_t *ids = p.arena + (uint64_t)lv * 4 + 1;
-                    unsigned long long m = 0ull;
-                    for (uint32_t t = lane; t < ln; t += 64) m |= tp_match(pid, nr, ids[t]);
-                    m = wave_or_u64(m);
-                    if ((int)lane == src) mask = m;
-                }
-                unsigned long long mine = 0ull;
-                for (uint32_t j = 0; j < nr; j++) {
-                    const unsigned long long b = __ballot((mask >> j) & 1ull);
-                    if (lane == j) mine = b;
-                }
-                if (lane < nr) out[(uint64_t)(r0 + lane) * nw + st] = mine;
-            }
-        }
+        tp_query_bits(pid, p.top_pid + q * p.K, cnt, vals, size, p.arena, out, lane);
     }
 }
