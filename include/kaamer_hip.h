@@ -96,7 +96,14 @@ int kaamer_image_build_pairs(const kaamer_pair *pairs, uint64_t n, uint32_t shar
                              uint32_t n_shards, double load_factor, kaamer_image **out);
 /* Emit loop + build: every window seqs[off[p]+i .. +7), i in [0,len-7], of
  * every protein with len >= 7, under id ids[p] (ids == NULL: the TSV rule,
- * 0-based running index, inputTSV.go:141-142). */
+ * 0-based running index, inputTSV.go:141-142).
+ * Postings lists are laid out in the order in which a walk over the proteins
+ * (input order) and their windows (ascending position) first refers to them, a
+ * shared list by its first reference (build_pairs: the order of the pairs), so
+ * that the lists behind consecutive windows of a protein are neighbours in the
+ * arena.  This is a property of where lists sit, not of the image format: same
+ * header and version, and an image file written by an earlier build (lists in
+ * ascending-key order) loads and searches as before. */
 int kaamer_image_build_proteins(const uint8_t *seqs, const uint64_t *offsets,
                                 const uint32_t *ids, uint32_t n_proteins, uint32_t shard,
                                 uint32_t n_shards, double load_factor, kaamer_image **out);

@@ -16,6 +16,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -97,6 +99,75 @@ uint64_t hash_list(const uint32_t *ids, uint32_t n)
     return h ? h : 1;
 }
 
+// The sorted distinct keys of a build behind a directory on their top bits: key -> index in a few steps.
+struct KeyIndex {
+    const uint32_t *keys;
+    uint64_t n;
+    int shift;
+    std::vector<uint32_t> dir;   // dir[d] = first index whose key >> shift is >= d
+    KeyIndex(const uint32_t *k, uint64_t n_keys) : keys(k), n(n_keys)
+    {
+        int bits = 4;
+        while (bits < 22 && (8ull << bits) < n) bits++;
+        shift = 32 - bits;
+        dir.assign(((size_t)1 << bits) + 1, (uint32_t)n);
+        for (uint64_t i = n; i-- > 0;) dir[keys[i] >> shift] = (uint32_t)i;
+        for (size_t d = dir.size() - 1; d-- > 0;) dir[d] = std::min(dir[d], dir[d + 1]);
+    }
+    uint64_t find(uint32_t key) const   // the key is one of keys[]
+    {
+        uint64_t lo = dir[key >> shift], hi = dir[(key >> shift) + 1];
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (keys[mid] <= key) lo = mid; else hi = mid;
+        }
+        return lo;
+    }
+};
+
+inline void atomic_min(std::atomic<uint64_t> &a, uint64_t v)
+{
+    uint64_t c = a.load(std::memory_order_relaxed);
+    while (v < c && !a.compare_exchange_weak(c, v, std::memory_order_relaxed)) {}
+}
+
+// fills rank[k], preset to ~0, with the smallest window index that refers to key k (see build_from_sorted_input)
+using RankFill = std::function<void(const KeyIndex &, std::atomic<uint64_t> *)>;
+
+struct RankedList { uint64_t rank; uint32_t list; };
+
+// ascending rank (ranks are distinct and <= max_rank): partition on the top 11 bits, std::sort the parts in parallel
+void sort_ranked(std::vector<RankedList> &a, uint64_t max_rank)
+{
+    const size_t n = a.size();
+    const auto less = [](const RankedList &x, const RankedList &y) { return x.rank < y.rank; };
+    unsigned nt = n_threads();
+    if (n < (1u << 16) || nt == 1) { std::sort(a.begin(), a.end(), less); return; }
+    const int B = 11, NB = 1 << B;
+    int shift = 0;
+    while ((max_rank >> shift) >= (uint64_t)NB) shift++;
+    std::vector<size_t> cnt(NB + 1, 0);
+    for (size_t i = 0; i < n; i++) cnt[(a[i].rank >> shift) + 1]++;
+    for (int i = 0; i < NB; i++) cnt[i + 1] += cnt[i];
+    std::vector<RankedList> tmp(n);
+    {
+        std::vector<size_t> pos(cnt.begin(), cnt.end() - 1);
+        for (size_t i = 0; i < n; i++) tmp[pos[a[i].rank >> shift]++] = a[i];
+    }
+    std::atomic<int> next(0);
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; t++)
+        th.emplace_back([&] {
+            for (;;) {
+                int b = next.fetch_add(1);
+                if (b >= NB) break;
+                std::sort(tmp.begin() + cnt[b], tmp.begin() + cnt[b + 1], less);
+            }
+        });
+    for (auto &x : th) x.join();
+    a.swap(tmp);
+}
+
 }  // namespace
 
 int kaamer_image_alloc(kaamer_image *img, uint64_t n_buckets, uint64_t arena_words)
@@ -113,8 +184,15 @@ int kaamer_image_alloc(kaamer_image *img, uint64_t n_buckets, uint64_t arena_wor
 }
 
 // pairs64: key<<32|id, any order, possibly with duplicates; consumed (sorted in place)
+//
+// Order of the arena.  The rank of a stored postings list is the smallest window index that refers to it, over every
+// key that shares the list; rank_of_keys supplies it per key (build_proteins: the absolute residue position of the
+// window, so proteins in input order and positions ascending; build_pairs: the index of the pair in the input).  Lists
+// are laid out in ascending rank from unit 1: the lists behind consecutive windows of a protein are consecutive 16-byte
+// units, four heads to a 64-byte sector, and a query that resembles the protein reads them coalesced.  The rank is a
+// minimum and not "the order a walk meets them", so builder_device.hip computes it in parallel and lands on the same bytes.
 static int build_from_sorted_input(uint64_t *pairs64, uint64_t n, uint32_t shard, uint32_t n_shards,
-                                   double load, kaamer_image **out)
+                                   double load, const RankFill &rank_of_keys, kaamer_image **out)
 {
     if (!(load > 0.05 && load <= 0.95)) load = 0.5;
     Trace tr;
@@ -127,9 +205,19 @@ static int build_from_sorted_input(uint64_t *pairs64, uint64_t n, uint32_t shard
     uint64_t n_keys = 0;
     for (uint64_t i = 0; i < n; i++)
         if (i == 0 || (pairs64[i] >> 32) != (pairs64[i - 1] >> 32)) n_keys++;
+    std::vector<uint64_t> kstart((size_t)n_keys + 1);
+    std::vector<uint32_t> keys((size_t)n_keys);
+    {
+        uint64_t k = 0;
+        for (uint64_t i = 0; i < n; i++)
+            if (i == 0 || (pairs64[i] >> 32) != (pairs64[i - 1] >> 32)) { kstart[k] = i; keys[k++] = (uint32_t)(pairs64[i] >> 32); }
+        kstart[n_keys] = n;
+    }
 
     kaamer_image *img = new (std::nothrow) kaamer_image();
     if (!img) return kaamer_fail(KAAMER_E_NOMEM, "image alloc");
+    img->buckets = nullptr;
+    img->arena = nullptr;
     memset(&img->hdr, 0, sizeof img->hdr);
     img->hdr.magic = KH_IMAGE_MAGIC;
     img->hdr.version = KH_IMAGE_VERSION;
@@ -143,84 +231,105 @@ static int build_from_sorted_input(uint64_t *pairs64, uint64_t n, uint32_t shard
     uint64_t n_buckets = (uint64_t)((double)n_keys / (KH_SLOTS_PER_BUCKET * load)) + 1;
     if (n_buckets >= (1ull << 32)) { delete img; return kaamer_fail(KAAMER_E_ARG, "too many buckets"); }
 
-    // ---- postings arena with set sharing ------------------------------------
-    // pass 1: upper bound of arena words (no sharing) to size the buffer
-    uint64_t ub_words = 4;  // offset 0 is reserved (val 0 never used)
-    {
-        uint64_t i = 0;
-        while (i < n) {
-            uint64_t j = i + 1;
-            while (j < n && (pairs64[j] >> 32) == (pairs64[i] >> 32)) j++;
-            uint64_t c = j - i;
-            if (!(c == 1 && (uint32_t)pairs64[i] < KH_INLINE_BIT)) ub_words += ((1 + c + 3) / 4) * 4;
-            i = j;
-        }
+    // ---- rank of every key: its first window -------------------------------
+    std::unique_ptr<std::atomic<uint64_t>[]> rank(new (std::nothrow) std::atomic<uint64_t>[(size_t)n_keys + 1]);
+    if (!rank) { delete img; return kaamer_fail(KAAMER_E_NOMEM, "rank buffer"); }
+    for (uint64_t k = 0; k < n_keys; k++) rank[k].store(~0ull, std::memory_order_relaxed);
+    if (n_keys) {
+        const KeyIndex ki(keys.data(), n_keys);
+        rank_of_keys(ki, rank.get());
     }
-    if (ub_words / 4 >= KH_INLINE_BIT) { delete img; return kaamer_fail(KAAMER_E_ARG, "arena exceeds 32 GiB per shard"); }
-    int rc = kaamer_image_alloc(img, n_buckets, ub_words);
-    if (rc) { kaamer_image_free(img); return kaamer_fail(rc, "image buffers"); }
-    memset(img->buckets, 0xFF, (size_t)n_buckets * sizeof(kh_bucket));
-    memset(img->arena, 0, 16);
+    tr.lap("first windows", n_keys);
 
-    // dedupe table: open addressing on the 64-bit content hash -> arena offset (16-B units)
-    uint64_t n_lists_ub = 0;
-    {
-        uint64_t i = 0;
-        while (i < n) {
-            uint64_t j = i + 1;
-            while (j < n && (pairs64[j] >> 32) == (pairs64[i] >> 32)) j++;
-            if (!(j - i == 1 && (uint32_t)pairs64[i] < KH_INLINE_BIT)) n_lists_ub++;
-            i = j;
-        }
-    }
+    // ---- postings sets with sharing ----------------------------------------
+    // a set is stored once: keys are matched through an open-addressed table on the 64-bit content hash of their set
+    // and verified against the pairs of the set's first key; the set's rank is the minimum over its keys
+    auto is_inline = [&](uint64_t k) { return kstart[k + 1] - kstart[k] == 1 && (uint32_t)pairs64[kstart[k]] < KH_INLINE_BIT; };
+    uint64_t n_lists_ub = 0, ub_words = 4;   // offset 0 is reserved (val 0 never used)
+    for (uint64_t k = 0; k < n_keys; k++)
+        if (!is_inline(k)) { n_lists_ub++; ub_words += ((1 + (kstart[k + 1] - kstart[k]) + 3) / 4) * 4; }
+    if (ub_words / 4 >= KH_INLINE_BIT) { delete img; return kaamer_fail(KAAMER_E_ARG, "arena exceeds 32 GiB per shard"); }
     uint64_t dcap = 16;
     while (dcap < n_lists_ub * 2) dcap <<= 1;
     std::vector<uint64_t> dh(dcap, 0);
-    std::vector<uint32_t> doff(dcap, 0);
+    std::vector<uint32_t> dlist(dcap, 0);
+    std::vector<uint32_t> list_of((size_t)n_keys, 0);   // list index of a key, later its slot value
+    std::vector<uint32_t> lkey;                         // first key of a list
+    std::vector<RankedList> order;
 
-    uint64_t words = 4, n_inline = 0, n_lists = 0, max_list = 0, n_displaced = 0;
+    uint64_t n_inline = 0, max_list = 0, n_displaced = 0, max_rank = 0;
     uint32_t max_pid = 0;
     std::vector<uint32_t> tmp;
-    uint64_t i = 0;
-    while (i < n) {
-        uint64_t j = i + 1;
-        while (j < n && (pairs64[j] >> 32) == (pairs64[i] >> 32)) j++;
-        uint32_t key = (uint32_t)(pairs64[i] >> 32);
-        uint32_t c = (uint32_t)(j - i);
-        uint32_t val;
-        max_pid = std::max(max_pid, (uint32_t)pairs64[j - 1]);
-        if (c == 1 && (uint32_t)pairs64[i] < KH_INLINE_BIT) {
-            val = KH_INLINE_BIT | (uint32_t)pairs64[i];
-            n_inline++;
-        } else {
-            tmp.resize(c);
-            for (uint32_t t = 0; t < c; t++) tmp[t] = (uint32_t)pairs64[i + t];  // ascending
-            uint64_t h = hash_list(tmp.data(), c);
-            uint64_t s = h & (dcap - 1);
-            val = 0;
-            for (;;) {
-                if (dh[s] == 0) break;
-                if (dh[s] == h) {
-                    const uint32_t *l = img->arena + (uint64_t)doff[s] * 4;
-                    if (l[0] == c && memcmp(l + 1, tmp.data(), (size_t)c * 4) == 0) { val = doff[s]; break; }
-                }
-                s = (s + 1) & (dcap - 1);
+    for (uint64_t k = 0; k < n_keys; k++) {
+        const uint64_t i = kstart[k];
+        const uint32_t c = (uint32_t)(kstart[k + 1] - i);
+        max_pid = std::max(max_pid, (uint32_t)pairs64[i + c - 1]);
+        if (is_inline(k)) { n_inline++; continue; }
+        tmp.resize(c);
+        for (uint32_t t = 0; t < c; t++) tmp[t] = (uint32_t)pairs64[i + t];  // ascending
+        const uint64_t h = hash_list(tmp.data(), c);
+        const uint64_t r = rank[k].load(std::memory_order_relaxed);
+        uint64_t s = h & (dcap - 1);
+        bool found = false;
+        for (;;) {
+            if (dh[s] == 0) break;
+            if (dh[s] == h) {
+                const uint64_t ri = kstart[lkey[dlist[s]]];
+                bool same = kstart[lkey[dlist[s]] + 1] - ri == c;
+                for (uint32_t t = 0; same && t < c; t++) same = (uint32_t)pairs64[ri + t] == tmp[t];
+                if (same) { found = true; break; }
             }
-            if (!val) {
-                val = (uint32_t)(words / 4);
-                uint32_t *l = img->arena + words;
-                l[0] = c;
-                memcpy(l + 1, tmp.data(), (size_t)c * 4);
-                uint64_t used = 1 + (uint64_t)c, padded = ((used + 3) / 4) * 4;
-                for (uint64_t p = used; p < padded; p++) l[p] = KH_EMPTY_PID;
-                words += padded;
-                dh[s] = h;
-                doff[s] = val;
-                n_lists++;
-                max_list = std::max<uint64_t>(max_list, c);
-            }
+            s = (s + 1) & (dcap - 1);
         }
-        // ---- insert into the bucket table ------------------------------------
+        if (found) {
+            list_of[k] = dlist[s];
+            order[dlist[s]].rank = std::min(order[dlist[s]].rank, r);
+        } else {
+            dh[s] = h;
+            dlist[s] = list_of[k] = (uint32_t)lkey.size();
+            lkey.push_back((uint32_t)k);
+            order.push_back(RankedList{ r, (uint32_t)order.size() });
+            max_list = std::max<uint64_t>(max_list, c);
+        }
+    }
+    const uint64_t n_lists = lkey.size();
+    for (const RankedList &o : order) max_rank = std::max(max_rank, o.rank);
+    std::vector<uint64_t>().swap(dh);
+    std::vector<uint32_t>().swap(dlist);
+    rank.reset();
+    tr.lap("share lists", n_lists);
+
+    // ---- arena in ascending rank -------------------------------------------
+    sort_ranked(order, max_rank);
+    std::vector<uint32_t> loff((size_t)n_lists);   // list -> offset in 16-byte units
+    uint64_t words = 4;
+    for (const RankedList &o : order) {
+        loff[o.list] = (uint32_t)(words / 4);
+        const uint64_t k = lkey[o.list];
+        words += ((1 + (kstart[k + 1] - kstart[k]) + 3) / 4) * 4;
+    }
+    std::vector<RankedList>().swap(order);
+    int rc = kaamer_image_alloc(img, n_buckets, words);
+    if (rc) { kaamer_image_free(img); return kaamer_fail(rc, "image buffers"); }
+    memset(img->buckets, 0xFF, (size_t)n_buckets * sizeof(kh_bucket));
+    memset(img->arena, 0, 16);
+    parallel_for((size_t)n_lists, n_threads(), [&](size_t b, size_t e, unsigned) {
+        for (size_t li = b; li < e; li++) {
+            const uint64_t i = kstart[lkey[li]];
+            const uint32_t c = (uint32_t)(kstart[lkey[li] + 1] - i);
+            uint32_t *l = img->arena + (uint64_t)loff[li] * 4;
+            l[0] = c;
+            for (uint32_t t = 0; t < c; t++) l[1 + t] = (uint32_t)pairs64[i + t];
+            const uint64_t used = 1 + (uint64_t)c, padded = ((used + 3) / 4) * 4;
+            for (uint64_t p = used; p < padded; p++) l[p] = KH_EMPTY_PID;
+        }
+    });
+    tr.lap("arena", words);
+
+    // ---- the bucket table, keys in ascending order ---------------------------
+    for (uint64_t k = 0; k < n_keys; k++) {
+        const uint32_t key = keys[k];
+        const uint32_t val = is_inline(k) ? (KH_INLINE_BIT | (uint32_t)pairs64[kstart[k]]) : loff[list_of[k]];
         uint64_t b = kh_home_bucket(key, n_shards, n_buckets);
         bool placed = false, home = true;
         for (uint64_t tries = 0; tries < n_buckets && !placed; tries++) {
@@ -237,9 +346,8 @@ static int build_from_sorted_input(uint64_t *pairs64, uint64_t n, uint32_t shard
         }
         if (!placed) { kaamer_image_free(img); return kaamer_fail(KAAMER_E_CAPACITY, "table full"); }
         if (!home) n_displaced++;
-        i = j;
     }
-    tr.lap("lists + placement", n_keys);
+    tr.lap("placement", n_keys);
     img->hdr.arena_words = words;
     img->hdr.n_inline = n_inline;
     img->hdr.n_lists = n_lists;
@@ -280,7 +388,16 @@ int kaamer_image_build_pairs(const kaamer_pair *pairs, uint64_t n, uint32_t shar
         if (n_shards > 1 && kh_shard_of(pairs[i].key, n_shards) != shard) continue;
         p64[m++] = ((uint64_t)pairs[i].key << 32) | pairs[i].protein_id;
     }
-    int rc = build_from_sorted_input(p64, m, shard, n_shards, load_factor, out);
+    // a pair stands for a window; the windows' order is the order of the pairs
+    const RankFill by_input_order = [&](const KeyIndex &ki, std::atomic<uint64_t> *rank) {
+        parallel_for(n, n_threads(), [&](size_t b, size_t e, unsigned) {
+            for (size_t i = b; i < e; i++) {
+                if (n_shards > 1 && kh_shard_of(pairs[i].key, n_shards) != shard) continue;
+                atomic_min(rank[ki.find(pairs[i].key)], i);
+            }
+        });
+    };
+    int rc = build_from_sorted_input(p64, m, shard, n_shards, load_factor, by_input_order, out);
     free(p64);
     return rc;
 }
@@ -307,7 +424,7 @@ int kaamer_image_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
             c[6] = kh_residue_code(s[i + 6]);
             const uint32_t key = kh_key_from_codes(c[0], c[1], c[2], c[3], c[4], c[5], c[6]);
             if (n_shards > 1 && kh_shard_of(key, n_shards) != shard) continue;
-            f(key);
+            f(key, i);
         }
     };
     std::vector<uint64_t> woff((size_t)n_proteins + 1, 0);
@@ -321,7 +438,7 @@ int kaamer_image_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
                 woff[p + 1] = len >= KAAMER_KMER_SIZE ? len - KAAMER_KMER_SIZE + 1 : 0;
             } else {
                 uint64_t k = 0;
-                for_windows(p, [&](uint32_t) { k++; });
+                for_windows(p, [&](uint32_t, uint64_t) { k++; });
                 woff[p + 1] = k;
             }
         }
@@ -335,10 +452,19 @@ int kaamer_image_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
         for (size_t p = b; p < e; p++) {
             const uint32_t id = ids ? ids[p] : (uint32_t)p;
             uint64_t *w = p64 + woff[p];
-            for_windows(p, [&](uint32_t key) { *w++ = ((uint64_t)key << 32) | id; });
+            for_windows(p, [&](uint32_t key, uint64_t) { *w++ = ((uint64_t)key << 32) | id; });
         }
     });
-    int rc = build_from_sorted_input(p64, total, shard, n_shards, load_factor, out);
+    // window index = absolute residue position of the window: proteins in input order, positions ascending
+    const RankFill by_walk = [&](const KeyIndex &ki, std::atomic<uint64_t> *rank) {
+        parallel_for(n_proteins, n_threads(), [&](size_t b, size_t e, unsigned) {
+            for (size_t p = b; p < e; p++) {
+                const uint64_t at = offsets[p];
+                for_windows(p, [&](uint32_t key, uint64_t i) { atomic_min(rank[ki.find(key)], at + i); });
+            }
+        });
+    };
+    int rc = build_from_sorted_input(p64, total, shard, n_shards, load_factor, by_walk, out);
     free(p64);
     return rc;
 }
@@ -458,9 +584,10 @@ uint32_t kaamer_image_get(const kaamer_image *img, uint32_t key, uint32_t *ids, 
     return 0;
 }
 
-// EXPERIMENT (tools/r4_arena_order.sh, not declared in the public header): re-orders the postings lists of `img` by FIRST TOUCH
-// -- the order in which a walk over the proteins (input order) and their windows (ascending position) meets them -- so that
-// the lists behind consecutive windows of a protein sit in consecutive 16-byte units (four list heads per 64-byte sector).
+// Re-lays the postings lists of `img` in the order in which a walk over the proteins (input order) and their windows
+// (ascending position) first meets them: the order both builders produce, so on an image they built from these proteins
+// it reproduces the image.  On an image file of an older build (lists in ascending-key order, same format) it gives the
+// new order.  bench.py calls it under KAAMER_EXP_ARENA_ORDER=2; not declared in the public header.
 int kaamer_exp_relayout_first_touch(kaamer_image *img, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_proteins)
 {
     if (!img || !offsets || (!seqs && n_proteins)) return kaamer_fail(KAAMER_E_ARG, "exp_relayout: bad argument");

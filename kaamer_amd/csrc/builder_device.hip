@@ -11,7 +11,10 @@
 //   (1) a set's place in the arena is decided by the SMALLEST key that holds it (its representative): sets
 //       are matched through a table on a 64-bit content hash, every match is verified word by word (a
 //       mismatch = hash collision -> the pass is repeated under another seed), and the representatives'
-//       padded sizes are prefix-summed in key order;
+//       padded sizes are prefix-summed in the order of the arena: ascending RANK, the smallest window index (absolute
+//       residue position: proteins in input order, positions ascending) over every key that holds the set.  A second
+//       run of the window kernel takes that minimum per key, the keys of a set hand theirs to the representative, and
+//       a radix sort of the representatives by rank replaces builder.cpp's sort;
 //   (2) a bucket keeps the 8 earliest arrivals (arrival order = key order) among its own keys and the ones
 //       the previous bucket could not hold, and hands the rest on.  How MANY it hands on is
 //       carry[b] = max(0, carry[b-1] + keys_at_home[b] - 8): a scan under  f o g  of the maps
@@ -104,11 +107,32 @@ __device__ inline uint32_t protein_of(const uint64_t *off, uint32_t lo, uint32_t
     return lo;
 }
 
-template <bool EMIT>
+// The sorted distinct keys behind a directory on their top bits (key -> key index in a few steps), and the word per key
+// that takes the smallest position of a window with that key.
+struct FirstWindow {
+    const uint32_t *keys;          // [n_keys] ascending
+    const uint32_t *dir;           // [(1 << (32 - shift)) + 1]  dir[d] = first index whose key >> shift is >= d
+    uint32_t shift, n_keys;
+    unsigned long long *min_pos;   // [n_keys], preset to ~0
+};
+
+__device__ inline uint32_t key_index(const FirstWindow &f, uint32_t key)   // the key is one of f.keys[]
+{
+    uint32_t lo = f.dir[key >> f.shift], hi = f.dir[(key >> f.shift) + 1];
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (f.keys[mid] <= key) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+enum { BD_COUNT = 0, BD_EMIT = 1, BD_FIRST = 2 };   // what bd_windows_kernel does with the windows
+
+template <int MODE>
 __global__ __launch_bounds__(BD_THREADS) void bd_windows_kernel(const uint8_t *__restrict__ seqs, const uint64_t *__restrict__ off,
                                                                  const uint32_t *__restrict__ ids, uint32_t n_prot, uint64_t origin,
                                                                  uint64_t total_res, uint32_t shard, uint32_t n_shards,
-                                                                 uint64_t *__restrict__ pairs, uint64_t cap, BuildStats *st)
+                                                                 uint64_t *__restrict__ pairs, uint64_t cap, BuildStats *st, FirstWindow fw)
 {
     // A thread owns BD_PER_THREAD CONSECUTIVE positions: their residues are 22 bytes read once (a wave reads 1 KB in one
     // piece) and coded once, the windows slide over them, and the protein of a position is the previous position's or
@@ -153,6 +177,19 @@ __global__ __launch_bounds__(BD_THREADS) void bd_windows_kernel(const uint8_t *_
             mine += ok;
         }
     }
+    if (MODE == BD_FIRST) {
+        // one word per key: the atomics are as spread as the keys are, and a window that cannot lower its key's word
+        // (the usual case after the key's first protein) only reads it
+#pragma unroll
+        for (uint32_t k = 0; k < BD_PER_THREAD; k++)
+            if ((okmask >> k) & 1u) {
+                const uint32_t ki = key_index(fw, keys[k]);
+                if (ki >= fw.n_keys || fw.keys[ki] != keys[k]) { st->bad = 1; continue; }   // (every window's key was emitted)
+                unsigned long long *w = fw.min_pos + ki;
+                if (pos0 + k < __atomic_load_n(w, __ATOMIC_RELAXED)) atomicMin(w, (unsigned long long)(pos0 + k));
+            }
+        return;
+    }
     // one reservation per wave
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t incl = mine;
@@ -161,7 +198,7 @@ __global__ __launch_bounds__(BD_THREADS) void bd_windows_kernel(const uint8_t *_
     unsigned long long wbase = 0;
     if (lane == 63 && wave_total) wbase = atomicAdd(&st->n_windows, (unsigned long long)wave_total);
     wbase = __shfl(wbase, 63, 64);
-    if (!EMIT) return;
+    if (MODE != BD_EMIT) return;
     uint64_t at = wbase + (incl - mine);
 #pragma unroll
     for (uint32_t k = 0; k < BD_PER_THREAD; k++)
@@ -189,7 +226,11 @@ struct KeyArrays {
     const uint32_t *run_start;  // [n_keys] sorted position of the first element with the same hash
     uint32_t *rep_of;        // [n_keys] representative of a list key's set = the smallest key index with its hash
     uint32_t *units;         // [n_keys] 16-byte units a key ADDS to the arena
-    uint32_t *uoff;          // [n_keys] exclusive prefix of units, from 1
+    uint32_t *uoff;          // [n_keys] arena offset of a representative's list, in units
+    uint32_t *dkeys;         // [n_keys] the keys
+    unsigned long long *rank;   // [n_keys] smallest window position of a key; of a representative: of its set
+    uint32_t *order;         // [n_keys] key indices, to be sorted by rank
+    unsigned long long no_rank; // above every position: the rank of keys that own no list
     uint32_t *arena;
     uint64_t *pkeys;         // [n_keys] home bucket << 32 | key
     uint32_t *pvals;         // [n_keys] slot value
@@ -281,6 +322,63 @@ __global__ __launch_bounds__(256) void bd_share_kernel(KeyArrays a)
     }
     n_lists = wave_sum(n_lists);
     if ((threadIdx.x & 63u) == 0 && n_lists) atomicAdd(&a.st->n_lists, n_lists);
+}
+
+// ---- order of the arena -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bd_keys_kernel(KeyArrays a)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < a.n_keys) a.dkeys[k] = (uint32_t)(a.pairs[a.kstart[k]] >> 32);
+}
+
+// dir[d] = first key index with key >> shift >= d, d in [0, n_dir]
+__global__ __launch_bounds__(256) void bd_dir_kernel(const uint32_t *__restrict__ keys, uint32_t n_keys, uint32_t shift, uint32_t n_dir,
+                                                     uint32_t *__restrict__ dir)
+{
+    const uint32_t d = blockIdx.x * 256u + threadIdx.x;
+    if (d > n_dir) return;
+    uint32_t lo = 0, hi = n_keys;
+    if (d == n_dir) lo = n_keys;
+    const uint32_t want = d << shift;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    dir[d] = lo;
+}
+
+// a set's rank is the minimum over its keys: every other key hands its own to the representative (only representatives'
+// words are written here, and only the others' are read)
+__global__ __launch_bounds__(256) void bd_rank_share_kernel(KeyArrays a)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= a.n_keys) return;
+    uint32_t s, c;
+    if (key_is_inline(a, k, s, c)) return;
+    const uint32_t rep = a.rep_of[k];
+    if (rep != k) atomicMin(a.rank + rep, a.rank[k]);
+}
+
+// sort input: representatives by rank, everything else behind them
+__global__ __launch_bounds__(256) void bd_rank_keys_kernel(KeyArrays a)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= a.n_keys) return;
+    if (a.units[k] == 0) a.rank[k] = a.no_rank;
+    else if (a.rank[k] >= a.no_rank) a.st->bad = 3;   // a stored set that no window reached
+    a.order[k] = k;
+}
+
+struct UnitsInOrder {
+    const uint32_t *units, *order;
+    __device__ uint32_t operator()(uint32_t j) const { return units[order[j]]; }
+};
+
+__global__ __launch_bounds__(256) void bd_offsets_kernel(const uint32_t *__restrict__ order, const uint32_t *__restrict__ soff, uint32_t n_keys,
+                                                         uint32_t *__restrict__ uoff)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < n_keys) uoff[order[j]] = soff[j];
 }
 
 // pass 3: postings into the arena, slot values, and the (home bucket, key) records of the placement
@@ -424,8 +522,9 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
     // ---- emit ----------------------------------------------------------------------------------------------
     DevMem d_pairs, d_pairs_alt;
     uint64_t n_emit = 0;
+    DevMem d_seqs, d_off, d_ids;   // kept for the second run of the window kernel (the order of the arena)
+    uint64_t n_tiles = 0;
     if (total_res >= KAAMER_KMER_SIZE) {
-        DevMem d_seqs, d_off, d_ids;
         BD_HIP(d_seqs.alloc(total_res + 32));   // (a thread of the emit kernel reads 24 bytes from its first position)
         BD_HIP(d_off.alloc(((size_t)n_proteins + 1) * 8));
         BD_HIP(hipMemcpy(d_seqs.p, seqs + origin, total_res, hipMemcpyHostToDevice));
@@ -435,18 +534,18 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
             BD_HIP(hipMemcpy(d_ids.p, ids, (size_t)n_proteins * 4, hipMemcpyHostToDevice));
         }
         tr.lap("upload", total_res);
-        const uint64_t n_tiles = (total_res + BD_TILE - 1) / BD_TILE;
+        n_tiles = (total_res + BD_TILE - 1) / BD_TILE;
         if (n_tiles >= (1ull << 31)) return kaamer_fail(KAAMER_E_CAPACITY, "device build: database too large for one call");
-        hipLaunchKernelGGL(bd_windows_kernel<false>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
-                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st);
+        hipLaunchKernelGGL(bd_windows_kernel<BD_COUNT>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
+                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st, FirstWindow{});
         BD_HIP(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
         n_emit = hs.n_windows;
         tr.lap("count windows", n_emit);
         BD_HIP(d_pairs.alloc(n_emit * 8));
         BD_HIP(d_pairs_alt.alloc(n_emit * 8));
         BD_HIP(hipMemset(st, 0, sizeof(BuildStats)));
-        hipLaunchKernelGGL(bd_windows_kernel<true>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
-                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, d_pairs.as<uint64_t>(), n_emit, st);
+        hipLaunchKernelGGL(bd_windows_kernel<BD_EMIT>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
+                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, d_pairs.as<uint64_t>(), n_emit, st, FirstWindow{});
         BD_HIP(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
         if (hs.bad || hs.n_windows != n_emit) return kaamer_fail(KAAMER_E_HIP, "device build: the emit pass disagrees with the count pass");
         tr.lap("emit", n_emit);
@@ -573,17 +672,56 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
         }
         tr.lap("hash + share", hs.n_lists);
         if (hs.ub_units + 1 >= KH_INLINE_BIT) return kaamer_fail(KAAMER_E_ARG, "arena exceeds 32 GiB per shard");   // builder.cpp's bound
-        d_hv.release(); d_hv_alt.release(); d_hk.release(); d_hk_alt.release(); d_run.release();
+        // ---- order of the arena: representatives by the first window that refers to their set ------------------
+        // (the buffers of the hash pass are taken over: rank <- hv, order <- hk, keys and sorted offsets <- run)
         {
+            a.dkeys = d_run.as<uint32_t>();
+            a.rank = (unsigned long long *)d_hv.p;
+            a.order = d_hk.as<uint32_t>();
+            a.no_rank = origin + total_res;
+            uint32_t bits = 4;
+            while (bits < 22 && (8ull << bits) < n_keys) bits++;
+            const uint32_t n_dir = 1u << bits;
+            DevMem d_dir;
+            BD_HIP(d_dir.alloc(((size_t)n_dir + 1) * 4));
+            hipLaunchKernelGGL(bd_keys_kernel, dim3(kb), dim3(256), 0, 0, a);
+            hipLaunchKernelGGL(bd_dir_kernel, dim3(blocks_for((uint64_t)n_dir + 1, 256)), dim3(256), 0, 0, a.dkeys, n_keys, 32u - bits, n_dir, d_dir.as<uint32_t>());
+            BD_HIP(hipMemset(a.rank, 0xFF, (size_t)n_keys * 8));
+            hipLaunchKernelGGL(bd_windows_kernel<BD_FIRST>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
+                               d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st,
+                               FirstWindow{ a.dkeys, d_dir.as<uint32_t>(), 32u - bits, n_keys, a.rank });
+            hipLaunchKernelGGL(bd_rank_share_kernel, dim3(kb), dim3(256), 0, 0, a);
+            hipLaunchKernelGGL(bd_rank_keys_kernel, dim3(kb), dim3(256), 0, 0, a);
+            BD_HIP(hipGetLastError());
+            tr.lap("first windows", n_keys);
+            d_seqs.release(); d_off.release(); d_ids.release();
+            uint32_t rank_bits = 1;
+            while (rank_bits < 64 && (a.no_rank >> rank_bits)) rank_bits++;
+            rocprim::double_buffer<unsigned long long> rb((unsigned long long *)d_hv.p, (unsigned long long *)d_hv_alt.p);
+            rocprim::double_buffer<uint32_t> ob(d_hk.as<uint32_t>(), d_hk_alt.as<uint32_t>());
             size_t need = 0;
-            BD_HIP(rocprim::exclusive_scan(nullptr, need, a.units, a.uoff, 1u, (size_t)n_keys, rocprim::plus<uint32_t>()));
+            BD_HIP(rocprim::radix_sort_pairs(nullptr, need, rb, ob, (size_t)n_keys, 0u, rank_bits));
             if (need > tmp_bytes) { BD_HIP(d_tmp.alloc(need)); tmp_bytes = need; }
-            BD_HIP(rocprim::exclusive_scan(d_tmp.p, need, a.units, a.uoff, 1u, (size_t)n_keys, rocprim::plus<uint32_t>()));
-            uint32_t last_off = 0, last_units = 0;
-            BD_HIP(hipMemcpy(&last_off, a.uoff + (n_keys - 1), 4, hipMemcpyDeviceToHost));
-            BD_HIP(hipMemcpy(&last_units, a.units + (n_keys - 1), 4, hipMemcpyDeviceToHost));
+            BD_HIP(rocprim::radix_sort_pairs(d_tmp.p, need, rb, ob, (size_t)n_keys, 0u, rank_bits));
+            const uint32_t *order = ob.current();
+            uint32_t *soff = d_run.as<uint32_t>();   // (the keys are not needed any more)
+            auto units_in_order = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0), UnitsInOrder{ a.units, order });
+            need = 0;
+            BD_HIP(rocprim::exclusive_scan(nullptr, need, units_in_order, soff, 1u, (size_t)n_keys, rocprim::plus<uint32_t>()));
+            if (need > tmp_bytes) { BD_HIP(d_tmp.alloc(need)); tmp_bytes = need; }
+            BD_HIP(rocprim::exclusive_scan(d_tmp.p, need, units_in_order, soff, 1u, (size_t)n_keys, rocprim::plus<uint32_t>()));
+            hipLaunchKernelGGL(bd_offsets_kernel, dim3(kb), dim3(256), 0, 0, order, soff, n_keys, a.uoff);
+            uint32_t last_key = 0, last_off = 0, last_units = 0;
+            BD_HIP(hipMemcpy(&last_key, order + (n_keys - 1), 4, hipMemcpyDeviceToHost));
+            BD_HIP(hipMemcpy(&last_off, soff + (n_keys - 1), 4, hipMemcpyDeviceToHost));
+            BD_HIP(hipMemcpy(&last_units, a.units + last_key, 4, hipMemcpyDeviceToHost));
             arena_words = ((uint64_t)last_off + last_units) * 4;
+            BuildStats rs;
+            BD_HIP(hipMemcpy(&rs, st, sizeof rs, hipMemcpyDeviceToHost));
+            if (rs.bad) return kaamer_fail(KAAMER_E_HIP, "device build: a postings set without a window");
+            tr.lap("sort by first window", hs.n_lists);
         }
+        d_hv.release(); d_hv_alt.release(); d_hk.release(); d_hk_alt.release(); d_run.release();
         BD_HIP(d_arena.alloc((size_t)arena_words * 4));
         BD_HIP(hipMemset(d_arena.p, 0, 16));
         BD_HIP(d_pkeys.alloc((size_t)n_keys * 8));

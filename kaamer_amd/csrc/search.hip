@@ -1822,46 +1822,8 @@ int kaamer_index_open_image(const kaamer_image *img, int device, kaamer_index **
     int rc = dev_alloc(&ix->d_buckets, (size_t)img->hdr.n_buckets);
     if (!rc) rc = dev_alloc(&ix->d_arena, (size_t)(img->hdr.arena_words < 4 ? 4 : img->hdr.arena_words));
     if (rc) { kaamer_index_close(ix); return rc; }
-    const kh_bucket *up_buckets = img->buckets;
-    const uint32_t *up_arena = img->arena;
-    std::vector<kh_bucket> ex_buckets;
-    std::vector<uint32_t> ex_arena;
-    if (const char *ev = getenv("KAAMER_EXP_ARENA_ORDER")) {
-        // EXPERIMENT (tools/r4_arena_order.sh), not a product path: the postings lists re-ordered before the upload, to
-        // measure what locality between the lists of one protein's k-mers is worth.  1 = by (first id, old offset)
-        struct Ref { uint32_t first_id, off; };
-        std::vector<Ref> refs;
-        const uint64_t nb = img->hdr.n_buckets;
-        for (uint64_t b = 0; b < nb; b++)
-            for (int t = 0; t < KH_SLOTS_PER_BUCKET; t++) {
-                const kh_slot &sl = img->buckets[b].s[t];
-                if (sl.key != KH_EMPTY_KEY && !(sl.val & KH_INLINE_BIT) && sl.val) refs.push_back(Ref{ img->arena[(uint64_t)sl.val * 4 + 1], sl.val });
-            }
-        std::sort(refs.begin(), refs.end(), [](const Ref &a, const Ref &b) { return a.off < b.off; });
-        refs.erase(std::unique(refs.begin(), refs.end(), [](const Ref &a, const Ref &b) { return a.off == b.off; }), refs.end());
-        if (atoi(ev) == 1) std::stable_sort(refs.begin(), refs.end(), [](const Ref &a, const Ref &b) { return a.first_id < b.first_id; });
-        ex_arena.assign((size_t)img->hdr.arena_words, 0u);
-        std::vector<uint32_t> new_off((size_t)(img->hdr.arena_words / 4 + 1), 0u);
-        uint32_t cur = 1;   // unit 0 is "no list"
-        for (const Ref &r : refs) {
-            const uint32_t cnt = img->arena[(uint64_t)r.off * 4];
-            const uint32_t units = (1u + cnt + 3u) / 4u;
-            memcpy(&ex_arena[(size_t)cur * 4], &img->arena[(size_t)r.off * 4], (size_t)units * 16);
-            new_off[r.off] = cur;
-            cur += units;
-        }
-        ex_buckets.assign(img->buckets, img->buckets + nb);
-        for (uint64_t b = 0; b < nb; b++)
-            for (int t = 0; t < KH_SLOTS_PER_BUCKET; t++) {
-                kh_slot &sl = ex_buckets[b].s[t];
-                if (sl.key != KH_EMPTY_KEY && !(sl.val & KH_INLINE_BIT) && sl.val) sl.val = new_off[sl.val];
-            }
-        fprintf(stderr, "[kaamer experiment] arena re-ordered (%zu lists, %u units of %llu)\n", refs.size(), cur, (unsigned long long)(img->hdr.arena_words / 4));
-        up_buckets = ex_buckets.data();
-        up_arena = ex_arena.data();
-    }
-    hipError_t e = hipMemcpy(ix->d_buckets, up_buckets, (size_t)img->hdr.n_buckets * sizeof(kh_bucket), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ix->d_arena, up_arena, (size_t)img->hdr.arena_words * 4, hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(ix->d_buckets, img->buckets, (size_t)img->hdr.n_buckets * sizeof(kh_bucket), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_arena, img->arena, (size_t)img->hdr.arena_words * 4, hipMemcpyHostToDevice);
     // list offset 0 is never handed out (kaamer_layout.h) and reads as "no list": the counting kernel loads it for
     // positions without a list instead of branching around the load (count_pack.hip.inc)
     if (e == hipSuccess) e = hipMemset(ix->d_arena, 0, 16);
