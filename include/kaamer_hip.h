@@ -841,6 +841,101 @@ int kaamer_align_matrix_scores(const char *sub_matrix, int32_t gap_open, int32_t
 int32_t kaamer_align_matrix_entry(int32_t a, int32_t b);
 
 /* ------------------------------------------------------------------------- */
+/* Alignment of the reported hits INSIDE the top-N call (`-aln` in one call):     */
+/* QueryResultHandler (search.go:483-494) aligns every reported hit with its query */
+/* (align.Align(query.Sequence, HitEntries[hit.Key].Sequence, ...)) and re-sorts    */
+/* the hits by BitScore (search.go:492).  With the database's Protein.Sequence      */
+/* table resident next to the index, the alignment of the reported hits is enqueued  */
+/* behind kaamer_topn_device on the same stream: no download of the hits, no lookup, */
+/* no packing, no upload, no rounds in between; only the per-pair integers and, on   */
+/* request, the operations come back, in the same packed block.  Matrix, gap column  */
+/* and tie rules are kaamer_align_pairs' own (one statement, align.hip); the numbers  */
+/* equal that call's bit for bit.  One device only: the sharded handle, replicas,     */
+/* kaamer_stream_* and kaamer_search_file have no such form.                          */
+/* ------------------------------------------------------------------------- */
+/* HitEntries (FetchHitsInformation, search.go:454-470) made resident: every entry's stored Protein.Sequence
+ * (kaamer_protein_entry.sequence / sequence_len, not the Length clip), its letter codes, a "letter outside the
+ * alphabet" flag and its length go to the index's device, with an id -> entry map that resolves an id exactly as
+ * kaamer_fetch_hits does (a later record with the same id wins: the FASTA reader's duplicated last id); KStats.NumberOfAA
+ * (EValue, align.go:142) is taken from the table.  The device copy is the library's; the TABLE ITSELF IS BORROWED and
+ * must outlive the index, or the next attach (results with text read the subjects' letters from it).  A second attach
+ * replaces the first; kaamer_index_close frees the device copy.  Not to be called while calls are in flight on the
+ * index.  KAAMER_ALIGN_GAP_COLUMN is read once per process, not per call. */
+int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p);
+/* out = { bytes of HBM the attached table takes (0: none attached), entries, longest stored sequence, NumberOfAA,
+ * direction-array budget in bytes, resident waves of the last alignment stage on the index, bytes of one direction slab
+ * of that stage, resident waves of its long-subject kernel (0: not launched) } */
+int kaamer_index_align_info(const kaamer_index *ix, uint64_t out[8]);
+/* Bytes of direction array (one byte per cell: ceil(nq / 64) x (ns + 63) x 64 per pair) ONE grid of the alignment stage of
+ * ONE call may hold.  The stage runs a grid of waves, each the owner of one slab sized for the batch's longest query
+ * against the table's longest subject (capped at 2048, the wave kernel's LDS row), that take pairs by ticket: the budget
+ * sets the number of waves, never the result -- at least one, and no more than five per compute unit (what the kernel's
+ * LDS lets run at once; a sizing rule: nothing depends on the waves being resident together).  The few pairs with a
+ * longer subject run on a second grid whose slabs (the table's longest subject) take up to the same budget again.
+ * The slabs belong to the workspace: a host call keeps them with its slot, so HBM in use is up to 2 x budget x the slots
+ * that have served an aligning call (KAAMER_HOST_SLOTS, default 4: up to 32 GiB at the default; the DB-SP protein batch
+ * takes 4.3 GB + 4 GiB per slot).  Lower the budget where that is too much.  0: the default (4 GiB). */
+int kaamer_index_set_align_budget(kaamer_index *ix, uint64_t bytes);
+
+/* One (query, reported hit) pair as the device leaves it: integers only (align.go:87-133 from the traceback). */
+typedef struct {
+    int32_t status;               /* kaamer_alignment.status: 0, 2, 3; 4 = the hit id has no entry in the attached table, */
+                                  /* or follows such a hit of its query: FetchHitsInformation stops there               */
+                                  /* (search.go:461-463) and the hit keeps the empty AlignmentResult                     */
+    int32_t n_ops;                /* columns                                                                              */
+    int32_t start_i, start_j;     /* 0-based cell before the first column (QueryStart = start_i + 1 when n_ops > 0)       */
+    int32_t end_i, end_j;         /* QueryEnd, SubjectEnd                                                                 */
+    int32_t identical, similar, mismatches, gap_openings, raw;
+    uint32_t query_len;           /* len(Query.Sequence): the trimmed ORF (EValue, align.go:142)                          */
+    uint64_t off;                 /* host-buffer form: first operation in the block's operations section                  */
+    uint32_t entry;               /* entry of the attached table                                                          */
+    uint32_t subject_len;
+} kaamer_align_pair;
+typedef struct {
+    char sub_matrix[16];          /* SearchOptions.SubMatrix / GapOpen / GapExtend (api/server.go:149-151)                */
+    int32_t gap_open, gap_extend;
+    uint32_t max_query_len;       /* residues of the batch's longest query (sizes the direction slabs; a longer query's   */
+                                  /* pairs get status 3); 0: the workspace's max_seq_bytes (ample, and costly)            */
+    uint32_t reserved;
+    uint64_t max_pairs;           /* pair records to provision; 0: min(max_queries x max_results, max_hits)               */
+} kaamer_topn_align_opts;
+typedef struct {
+    const uint64_t *d_pair_off;          /* [n_queries + 1] pair e = d_pair_off[q] + r is hit r of query q (d_top_pid order) */
+    const kaamer_align_pair *d_pairs;
+    uint64_t pair_capacity;
+    uint32_t n_waves, n_long_waves;      /* resident waves of the two kernels                                             */
+    uint64_t slab_bytes;                 /* one wave's direction slab                                                     */
+} kaamer_topn_alignments;
+/* The device-resident form: enqueued on `stream` behind kaamer_topn_device (`top` is its result; on the count stream when
+ * the workspace's counting stage runs there), no host synchronisation.  Options without a row in AllMatrixScores, or a
+ * matrix other than BLOSUM62: KAAMER_E_ARG (the host calls below report status 1 per item instead).  More pairs than
+ * provisioned: KAAMER_E_CAPACITY at kaamer_workspace_finish.  KAAMER_E_ARG when no table is attached or the workspace's
+ * last result is a merge. */
+int kaamer_topn_align_device(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *top,
+                             const kaamer_topn_align_opts *opts, void *stream, kaamer_topn_alignments *out);
+/* kaamer_search_batch_top_flat / kaamer_search_batch_top_pos_flat (want_positions != 0) with the alignment of every
+ * reported hit in the same call and the same packed block (replaces search.go:454-470 + :483-494 for the whole batch).
+ * In the result the hits of every reported query are in the reference's FINAL order: BitScore descending, ties in
+ * sortMapByValue order (top_pid, top_kmatch, top_first_pos and the bitmaps' pos_off permuted together).  A hit whose
+ * alignment failed keeps the empty AlignmentResult (BitScore 0).  Options without a row in AllMatrixScores, or a matrix
+ * other than BLOSUM62: every item has status 1 and the hits stay in sortMapByValue order.  want_text = 0: numbers only
+ * (no operations cross PCIe).  KAAMER_E_ARG when no table is attached.  A ticket is waited for with
+ * kaamer_wait_batch_top or dropped with kaamer_ticket_discard. */
+int kaamer_search_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                     int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                     int32_t want_positions, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                     int32_t want_text, kaamer_batch_top **out);
+int kaamer_submit_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                     int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                     int32_t want_positions, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                     int32_t want_text, kaamer_ticket **ticket);
+/* The alignments of a result (kaamer_batch_top itself is unchanged): items[e] belongs to entry e of the CSR arrays
+ * (top_pid[e], ...); status as kaamer_alignment states it, plus 4 (kaamer_align_pair.status); aln_off points into `text`
+ * (three rows of `length` bytes), which is NULL for a result without text.  Both NULL for a result of a call without
+ * alignments.  They live as long as the result does. */
+int kaamer_batch_top_alignments(const kaamer_batch_top *out, const kaamer_alignment **items, const char **text);
+
+/* ------------------------------------------------------------------------- */
 /* Readers — GetQueriesFasta / GetQueriesFastq (search.go:222-412) on a text   */
 /* buffer (already decompressed): packed sequences + SizeInKmer + names, with  */
 /* the reference's quirks (every FASTA record but the last is upper-cased; '*' */

@@ -109,6 +109,23 @@ class Alignment(C.Structure):
                 ("aln_off", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AlignPair(C.Structure):   # kaamer_align_pair: one (query, reported hit) pair as the device leaves it
+    _fields_ = [("status", C.c_int32), ("n_ops", C.c_int32), ("start_i", C.c_int32), ("start_j", C.c_int32), ("end_i", C.c_int32),
+                ("end_j", C.c_int32), ("identical", C.c_int32), ("similar", C.c_int32), ("mismatches", C.c_int32),
+                ("gap_openings", C.c_int32), ("raw", C.c_int32), ("query_len", C.c_uint32), ("off", C.c_uint64),
+                ("entry", C.c_uint32), ("subject_len", C.c_uint32)]
+
+
+class TopnAlignOpts(C.Structure):
+    _fields_ = [("sub_matrix", C.c_char * 16), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("max_query_len", C.c_uint32),
+                ("reserved", C.c_uint32), ("max_pairs", C.c_uint64)]
+
+
+class TopnAlignments(C.Structure):
+    _fields_ = [("d_pair_off", C.c_void_p), ("d_pairs", C.c_void_p), ("pair_capacity", C.c_uint64), ("n_waves", C.c_uint32),
+                ("n_long_waves", C.c_uint32), ("slab_bytes", C.c_uint64)]
+
+
 class TopnResult(C.Structure):
     _fields_ = [("max_results", C.c_uint32), ("d_top_cnt", C.c_void_p), ("d_top_pid", C.c_void_p),
                 ("d_top_kmatch", C.c_void_p), ("d_top_first_pos", C.c_void_p), ("d_trim", C.c_void_p),
@@ -289,6 +306,18 @@ SYMBOLS = {
                                                            C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "kaamer_sharded_positions_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_format_positions": (C.c_uint64, [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
+    # the alignment of the reported hits inside the top-N call
+    "kaamer_index_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kaamer_index_align_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_index_set_align_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "kaamer_topn_align_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TopnResult), C.POINTER(TopnAlignOpts), C.c_void_p,
+                                           C.POINTER(TopnAlignments)]),
+    "kaamer_search_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
+                                                   C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "kaamer_submit_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
+                                                   C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.POINTER(C.c_void_p)]),
+    "kaamer_batch_top_alignments": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Alignment)), C.POINTER(C.POINTER(C.c_char))]),
 }
 
 _lib = None

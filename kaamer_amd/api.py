@@ -238,6 +238,23 @@ class TopResult:
             self.pos_off = np.ctypeslib.as_array(po, shape=(ne + 1,)).copy()
             nw = int(self.pos_off[ne])
             self.pos_bits = np.ctypeslib.as_array(pb, shape=(nw,)).copy() if nw else np.zeros(0, np.uint64)
+        # the alignments of the reported hits (kaamer_batch_top_alignments): None unless the call asked for them; else one
+        # dict per CSR entry (fields of kaamer_alignment; "aln": the three rows, None for a result without text), and the
+        # CSR arrays above are in the reference's final order (BitScore descending)
+        self.alignments = None
+        items, text = C.POINTER(abi.Alignment)(), C.POINTER(C.c_char)()
+        abi.check(abi.lib().kaamer_batch_top_alignments(out, C.byref(items), C.byref(text)))
+        if bool(items):
+            self.alignments = []
+            for e in range(ne):
+                a = items[e]
+                d = {k: getattr(a, k) for k, _ in abi.Alignment._fields_ if k not in ("aln_off", "reserved")}
+                d["aln"] = None
+                if bool(text) and a.status == 0:
+                    ln = a.length
+                    raw = C.string_at(C.addressof(text.contents) + a.aln_off, 3 * ln) if ln else b""
+                    d["aln"] = (raw[:ln].decode("latin-1"), raw[ln:2 * ln].decode("latin-1"), raw[2 * ln:].decode("latin-1"))
+                self.alignments.append(d)
 
     def positions(self, i):
         """{protein id: bool[S]} of REPORTED query i (index into rep_query), shaped like BatchResult.positions: the
@@ -361,6 +378,7 @@ class Index:
     def __init__(self, handle, device):
         self._h = C.c_void_p(handle)
         self.device = device
+        self.proteins = None   # attach_proteins
 
     @classmethod
     def from_image(cls, image, device=0):
@@ -421,16 +439,24 @@ class Index:
         return FullTicket(t)
 
     def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
-                   want_positions=False):
+                   want_positions=False, align=None):
         """Host-buffer form that returns the reported hits only (kaamer_search_batch_top_flat; flat=False: the struct
         form): sortMapByValue order, SetBestStartCodon for nucleotide/reads, FilterResults -- all on the device.
         want_positions: the PositionHits bitmaps of the reported hits come along (kaamer_search_batch_top_pos_flat;
-        TopResult.positions)."""
+        TopResult.positions).
+        align: dict(sub_matrix="blosum62", gap_open=11, gap_extend=1, text=True) -- every reported hit aligned with its
+        query in the same call (kaamer_search_batch_top_aln_flat; needs attach_proteins): TopResult.alignments, hits in
+        BitScore order."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         out = C.POINTER(abi.BatchTop)()
-        if want_positions:
+        if align is not None:
+            abi.check(abi.lib().kaamer_search_batch_top_aln_flat(
+                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
+                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
+                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(out)))
+        elif want_positions:
             abi.check(abi.lib().kaamer_search_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
                                                                  len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
         elif flat:
@@ -446,15 +472,22 @@ class Index:
             abi.lib().kaamer_batch_top_free(out)
 
     def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
-                   want_positions=False):
+                   want_positions=False, align=None):
         """kaamer_submit_batch_top[_flat]: the batch is copied and enqueued on a free slot; -> a ticket whose wait() returns
         the TopResult.  Several tickets may be in flight; submit blocks while every slot is busy.
-        want_positions: kaamer_submit_batch_top_pos_flat (the bitmaps of the reported hits come along)."""
+        want_positions: kaamer_submit_batch_top_pos_flat (the bitmaps of the reported hits come along).
+        align: as search_top's -- kaamer_submit_batch_top_aln_flat: the reported hits aligned with their queries in the
+        same call (needs attach_proteins); the ticket's TopResult carries `alignments`, hits in BitScore order."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         t = C.c_void_p()
-        if want_positions:
+        if align is not None:   # kaamer_submit_batch_top_aln_flat (search_top's `align`)
+            abi.check(abi.lib().kaamer_submit_batch_top_aln_flat(
+                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
+                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
+                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(t)))
+        elif want_positions:
             abi.check(abi.lib().kaamer_submit_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
                                                                  len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
         elif flat:
@@ -468,6 +501,23 @@ class Index:
 
     def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False):
         return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions)
+
+    def attach_proteins(self, proteins):
+        """kaamer_index_attach_proteins: the table's Protein.Sequence entries become resident next to the index (the
+        subjects of search_top(align=...)).  The table is borrowed by the library: the index keeps it alive."""
+        abi.check(abi.lib().kaamer_index_attach_proteins(self._h, proteins._h))
+        self.proteins = proteins
+
+    def align_info(self):
+        """kaamer_index_align_info -> dict"""
+        out = (C.c_uint64 * 8)()
+        abi.check(abi.lib().kaamer_index_align_info(self._h, out))
+        return dict(zip(("table_bytes", "entries", "max_subject_len", "number_of_aa", "budget_bytes", "waves", "slab_bytes", "long_waves"),
+                        (int(v) for v in out)))
+
+    def set_align_budget(self, nbytes):
+        """kaamer_index_set_align_budget: bytes of direction array one call's alignment stage may hold; 0: the default"""
+        abi.check(abi.lib().kaamer_index_set_align_budget(self._h, int(nbytes)))
 
     def set_top_positions_bound(self, words):
         """kaamer_index_set_top_positions_bound: the first bitmap bound (u64 words) of the want_positions calls; 0: the rule"""
@@ -809,6 +859,15 @@ class Workspace:
         r = abi.TopnPositions()
         abi.check(abi.lib().kaamer_topn_positions_device(self.index._h, self._h, C.byref(top), int(max_pos_words),
                                                          C.c_void_p(stream), C.byref(r)))
+        return r
+
+    def topn_align_device(self, top, sub_matrix="blosum62", gap_open=11, gap_extend=1, max_query_len=0, max_pairs=0, stream=0):
+        """kaamer_topn_align_device: every hit the last topn_device call (`top`, its result) kept, aligned with its query
+        against the index's attached protein table, left on the device -> abi.TopnAlignments (d_pair_off[n + 1],
+        d_pairs: abi.AlignPair records)"""
+        o = abi.TopnAlignOpts(sub_matrix.encode(), gap_open, gap_extend, int(max_query_len), 0, int(max_pairs))
+        r = abi.TopnAlignments()
+        abi.check(abi.lib().kaamer_topn_align_device(self.index._h, self._h, C.byref(top), C.byref(o), C.c_void_p(stream), C.byref(r)))
         return r
 
     def set_count_stream(self, stream):

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "kaamer_internal.h"
+#include "align_wave.hip.inc"   // the recurrence, its tie rules and the tallies: one statement for both launch forms
 
 namespace {
 
@@ -80,20 +81,8 @@ bool matrix_scores(const char *sub_matrix, int gap_open, int gap_extend, double 
 
 // AAPosInMatrix (matrixScores.go:117) = biogo's protein alphabet
 const char ALPHA[] = "-ABCDEFGHIJKLMNPQRSTVWXYZ*";
-constexpr int NL = 26;
-
-int letter_index(int c)   // exact letters (the map of matrixScores.go:117); -1: a map miss
-{
-    if (c == '-') return 0;
-    if (c == '*') return 25;
-    if (c >= 'A' && c <= 'Z' && c != 'O' && c != 'U') {
-        int i = c - 'A' + 1;          // A=1 .. N=14
-        if (c > 'O') i--;             // P=15 .. T=19
-        if (c > 'U') i--;             // V=20 .. Z=24
-        return i;
-    }
-    return -1;
-}
+constexpr int NL = ALN_NL;
+inline int letter_index(int c) { return aln_letter_index(c); }   // (align_wave.hip.inc)
 
 // BLOSUM62 in the alphabet's order.  Rows of the NCBI matrix (ARNDCQEGHILKMFPSTWYVBZX*), re-indexed once at start-up;
 // J after the NCBI matrices that carry it; row / column 0 (the gap) = gap_col.  It is 0: align.go:127 recognises a gap feature
@@ -141,10 +130,6 @@ struct WaveDesc {   // 64 pairs of similar size
     uint64_t ops_off;   // bytes: (max_nq + max_ns) x 64 lanes
 };
 
-struct PairOut {
-    int32_t max_s, end_i, end_j, start_i, start_j, n_ops;
-};
-
 struct AlignParams {
     const uint8_t *codes;      // letter indices of every sequence (U already '*', case folded)
     const PairDesc *pairs;
@@ -156,14 +141,6 @@ struct AlignParams {
     uint8_t *ops;
     PairOut *out;
 };
-
-// first maximum of (a, b, c): its value and its index + 1
-__device__ __forceinline__ void arg3(int a, int b, int c, int &v, unsigned &k)
-{
-    v = a; k = 1u;
-    if (b > v) { v = b; k = 2u; }
-    if (c > v) { v = c; k = 3u; }
-}
 
 __global__ __launch_bounds__(64) void align_kernel(AlignParams p)
 {
@@ -242,8 +219,6 @@ __global__ __launch_bounds__(64) void align_kernel(AlignParams p)
 }
 
 // ---- one wave per pair: anti-diagonal wavefront ----------------------------------------------------------------------
-#define ALN_WAVE_NS 2048u   /* longest subject the LDS row buffer holds (3 layers x 4 bytes x (ALN_WAVE_NS + 1)) */
-
 struct WPair {
     uint32_t q_off, nq, s_off, ns;
     uint64_t dir_off;   // bytes: strips x (ns + 63) steps x 64 lanes
@@ -261,102 +236,17 @@ struct WaveParams {
     uint32_t first;     // index of pairs[0] in `out`
 };
 
-// value of the next lower lane (lane 0: `first`): DPP wave_shr:1
-__device__ __forceinline__ int from_lower_lane(int v, int first)
-{
-    return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false);
-}
-
 __global__ __launch_bounds__(64) void align_wave_kernel(WaveParams p)
 {
-    __shared__ int s_m[NL * NL];
-    __shared__ int s_bnd[3][ALN_WAVE_NS + 1];   // the last row of the previous strip, per layer, by column (0 = zeros)
-    __shared__ uint8_t s_sub[ALN_WAVE_NS];
+    __shared__ AlnWaveLds L;
     const uint32_t lane = threadIdx.x;
     const WPair d = p.pairs[blockIdx.x];
-    for (uint32_t i = lane; i < NL * NL; i += 64) s_m[i] = p.matrix[i];
-    for (uint32_t j = lane; j < d.ns; j += 64) s_sub[j] = p.codes[d.s_off + j];
-    for (uint32_t j = lane; j <= d.ns; j += 64) { s_bnd[0][j] = 0; s_bnd[1][j] = 0; s_bnd[2][j] = 0; }
-    __syncthreads();
-    const uint32_t steps = d.ns + 63u;
-    uint8_t *const dir = p.dirs + d.dir_off + lane;
-    int best = 0, best_i = 0, best_j = 0, best_l = 0;
-    uint32_t strip = 0;
-    for (uint32_t i0 = 0; i0 < d.nq; i0 += 64, strip++) {
-        const uint32_t i = i0 + lane + 1;                 // this lane's row (1-based)
-        const bool row_live = i <= d.nq;
-        const int rv = row_live ? (int)p.codes[d.q_off + i - 1] : 0;
-        const int gr = s_m[rv * NL];                      // the gap-column score of the query letter
-        int cm = 0, cu = 0, cl = 0;                       // this lane's last cell (zeros: column 0 / not a cell)
-        int pu_m = 0, pu_u = 0, pu_l = 0;                 // the cell above last step's cell = this step's diagonal
-        uint8_t *const sdir = dir + (uint64_t)strip * steps * 64;
-        for (uint32_t st = 0; st < steps; st++) {
-            const int j = (int)st - (int)lane + 1;        // this step's column (1-based)
-            const bool cell = row_live && j >= 1 && j <= (int)d.ns;
-            // the cell above: the lower lane's last results (its row is i - 1, its last column was j); lane 0 reads the
-            // previous strip's last row
-            const int jc = j < 0 ? 0 : (j > (int)d.ns ? (int)d.ns : j);
-            const int b_m = s_bnd[0][jc], b_u = s_bnd[1][jc], b_l = s_bnd[2][jc];
-            const int up_m = from_lower_lane(cm, b_m), up_u = from_lower_lane(cu, b_u), up_l = from_lower_lane(cl, b_l);
-            const int qv = cell ? (int)s_sub[j - 1] : 0;
-            int v, nm = 0, nu = 0, nl = 0;
-            unsigned k, f = 0;
-            arg3(pu_m, pu_u, pu_l, v, k);                 // diag: the best layer of (i-1, j-1) + the substitution score
-            const int pm = v;
-            v += s_m[rv * NL + qv];
-            if (v > 0) { nm = v; f |= pm > 0 ? k : 0u; }
-            arg3(up_m + p.gap_open + gr, up_u + gr, up_l + p.gap_open + gr, v, k);       // up: consumes the query letter
-            if (v > 0) { nu = v; f |= k << 2; }
-            const int gq = s_m[qv];
-            arg3(cm + p.gap_open + gq, cu + p.gap_open + gq, cl + gq, v, k);             // left: consumes the subject letter
-            if (v > 0) { nl = v; f |= k << 4; }
-            if (!cell) { nm = nu = nl = 0; f = 0; }
-            sdir[(uint64_t)st * 64] = (uint8_t)f;
-            // the first best cell in row-major order: within a row columns ascend, a lane's rows ascend with the strips
-            if (nm > best) { best = nm; best_i = (int)i; best_j = j; best_l = 0; }
-            if (nu > best) { best = nu; best_i = (int)i; best_j = j; best_l = 1; }
-            if (nl > best) { best = nl; best_i = (int)i; best_j = j; best_l = 2; }
-            pu_m = up_m; pu_u = up_u; pu_l = up_l;
-            cm = nm; cu = nu; cl = nl;
-            // the strip's last row feeds the next strip (column j was read by lane 0 sixty-three steps ago)
-            if (lane == 63 && cell) { s_bnd[0][j] = nm; s_bnd[1][j] = nu; s_bnd[2][j] = nl; }
-        }
-        __syncthreads();   // (one wave: orders the LDS row between strips)
-    }
-    // the best cell over the lanes: highest score, then the smallest row
-    unsigned long long key = ((unsigned long long)(uint32_t)best << 32) | (uint32_t)(0x7FFFFFFF - best_i);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o, 64);
-        key = other > key ? other : key;
-    }
-    const int w_best = (int)(key >> 32), w_i = 0x7FFFFFFF - (int)(uint32_t)key;
-    const unsigned long long mine = __ballot(best == w_best && best_i == w_i && w_best > 0);
-    int max_j = 0, max_l = 0;
-    if (mine) {
-        const int src = __ffsll((long long)mine) - 1;
-        max_j = __shfl(best_j, src, 64);
-        max_l = __shfl(best_l, src, 64);
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (lane != 0) return;
-    // traceback (lane 0): cell (i, j) lives in strip (i-1)/64 at step (j-1) + (i-1)%64, lane (i-1)%64
-    uint8_t *const ops = p.ops + d.ops_off;
-    int i = w_best > 0 ? w_i : 0, j = max_j, l = max_l, n_ops = 0;
-    const int end_i = i, end_j = j;
-    while (i > 0 && j > 0) {
-        const uint32_t ln = (uint32_t)(i - 1) & 63u, sp = (uint32_t)(i - 1) >> 6;
-        const unsigned f = p.dirs[d.dir_off + ((uint64_t)sp * steps + (uint32_t)(j - 1) + ln) * 64 + ln];
-        const unsigned pred = (f >> (2 * l)) & 3u;
-        ops[n_ops++] = l == 0 ? 'M' : l == 1 ? 'U' : 'L';
-        if (l == 0) { i--; j--; } else if (l == 1) i--; else j--;
-        if (pred == 0) break;
-        l = (int)pred - 1;
-    }
+    for (uint32_t i = lane; i < NL * NL; i += 64) L.m[i] = p.matrix[i];
     PairOut o;
-    o.max_s = w_best; o.end_i = end_i; o.end_j = end_j; o.start_i = i; o.start_j = j; o.n_ops = n_ops;
-    p.out[p.first + blockIdx.x] = o;
+    AlnTally unused;
+    align_wave_pair<false, false>(L, p.codes + d.q_off, d.nq, p.codes + d.s_off, d.ns, p.gap_open, p.dirs + d.dir_off, p.ops + d.ops_off,
+                                  nullptr, nullptr, nullptr, 0, 0, o, unused);
+    if (lane == 0) p.out[p.first + blockIdx.x] = o;
 }
 
 template <class T> struct DevBuf {
@@ -370,7 +260,68 @@ template <class T> struct DevBuf {
     }
 };
 
+// KAAMER_ALIGN_GAP_COLUMN (biogo's gap column, should it differ: see the header), read once per process
+int gap_column_once()
+{
+    static const int v = [] { const char *e = getenv("KAAMER_ALIGN_GAP_COLUMN"); return e ? atoi(e) : 0; }();
+    return v;
+}
+
 }  // namespace
+
+// ---- what the top-N alignment stage (search.hip: top_align.hip.inc) takes from this file: the matrix with its gap column,
+// the aligner's GapOpen, the options' statistics, the host arithmetic and the three rows
+int kaamer_align_dp_open() { return -11; }   // align.go:62-65: BLOSUM62, GapOpen -11, whatever the options are
+void kaamer_align_matrix(int *m) { fill_matrix(m, gap_column_once()); }
+bool kaamer_align_options(const char *sub_matrix, int gap_open, int gap_extend, double *lambda, double *k)
+{
+    // align.go:48-52: GetMatrixScores fails -> an empty AlignmentResult and an error (the caller `continue`s).  The similarity
+    // marks read matrixScores.SubMatrix (align.go:96): only BLOSUM62's data is carried here, other matrices report the same
+    std::string mlow(sub_matrix ? sub_matrix : "");
+    for (char &c : mlow) if (c >= 'A' && c <= 'Z') c = (char)(c + 32);
+    return matrix_scores(sub_matrix, gap_open, gap_extend, lambda, k) && mlow == "blosum62";
+}
+// align.go:101-102,137,142,153-156 from the integers of one alignment (query_len = len(Query.Sequence))
+void kaamer_align_finish(kaamer_alignment *a, const kaamer_align_ints *t, uint64_t query_len, uint64_t number_of_aa, double lambda, double kk)
+{
+    const int len = t->n_ops;
+    float identity = (float)t->identical, similarity = (float)t->similar;
+    const float nb_pos = (float)len;
+    identity = (identity / nb_pos) * 100;                                               // align.go:101-102 (float32)
+    similarity = (similarity / nb_pos) * 100;
+    a->identity = identity;
+    a->similarity = similarity;
+    a->length = len;
+    a->mismatches = t->mismatches;
+    a->gap_openings = t->gap_openings;
+    a->raw = t->raw;
+    a->bitscore = ((lambda * (double)t->raw) - std::log(kk)) / std::log(2.0);           // align.go:137
+    a->evalue = (double)query_len * (double)number_of_aa / std::pow(2.0, a->bitscore);  // align.go:142
+    a->query_start = len ? t->start_i + 1 : 1;                                          // align.go:153-156
+    a->query_end = len ? t->end_i : 0;
+    a->subject_start = len ? t->start_j + 1 : 1;
+    a->subject_end = len ? t->end_j : 0;
+    a->status = 0;
+}
+// align.Format: the three rows (query, match, subject; `len` bytes each at rows, rows + len, rows + 2 len) from the
+// operations in reverse, and the tallies of the same columns
+void kaamer_align_rows(const uint8_t *ops_rev, int len, const uint8_t *q, const uint8_t *s, int start_i, int start_j, const int *matrix,
+                       int gap_open, int gap_extend, char *rows, kaamer_align_ints *t)
+{
+    char *row_a = rows, *row_m = rows + len, *row_b = rows + 2 * (size_t)len;
+    AlnTally ty;
+    ty.init();
+    int ai = start_i, bj = start_j;
+    for (int x = 0; x < len; x++) {
+        const int op = ops_rev[(size_t)(len - 1 - x)];
+        const int qa = op == 'L' ? 0 : q[ai++], sb = op == 'U' ? 0 : s[bj++];
+        row_a[x] = op == 'L' ? '-' : (char)aln_star(qa);
+        row_b[x] = op == 'U' ? '-' : (char)aln_star(sb);
+        row_m[x] = ty.step(op, qa, sb, matrix, kaamer_align_dp_open(), gap_open, gap_extend);
+    }
+    ty.close_run(kaamer_align_dp_open(), gap_open, gap_extend);
+    if (t) { t->identical = ty.identical; t->similar = ty.similar; t->mismatches = ty.mismatches; t->gap_openings = ty.gap_openings; t->raw = ty.raw; }
+}
 
 struct kaamer_alignments {
     std::vector<kaamer_alignment> items;
@@ -420,19 +371,14 @@ int kaamer_align_pairs(int device, const uint8_t *seqs, const uint64_t *offsets,
     res->items.assign(n_pairs, kaamer_alignment());
     for (kaamer_alignment &a : res->items) memset(&a, 0, sizeof a);
     double lambda = 0, kk = 0;
-    // align.go:48-52: GetMatrixScores fails -> an empty AlignmentResult and an error (the caller `continue`s).  The similarity
-    // marks read matrixScores.SubMatrix (align.go:96): only BLOSUM62's data is carried here, other matrices report the same
-    std::string mlow(sub_matrix);
-    for (char &c : mlow) if (c >= 'A' && c <= 'Z') c = (char)(c + 32);
-    if (!matrix_scores(sub_matrix, gap_open, gap_extend, &lambda, &kk) || mlow != "blosum62") {
+    if (!kaamer_align_options(sub_matrix, gap_open, gap_extend, &lambda, &kk)) {
         for (kaamer_alignment &a : res->items) a.status = 1;
         *out = res;
         return KAAMER_OK;
     }
-    int gap_col = 0, dp_open = -11;                     // align.go:62-65: BLOSUM62, GapOpen -11, whatever the options are
-    if (const char *e = getenv("KAAMER_ALIGN_GAP_COLUMN")) gap_col = atoi(e);   // biogo's gap column, should it differ (see the header)
+    const int dp_open = kaamer_align_dp_open();
     int matrix[NL * NL];
-    fill_matrix(matrix, gap_col);
+    kaamer_align_matrix(matrix);
     // ---- letters: [uU] -> '*' (align.go:54-55), then the aligner's index (not case sensitive); a letter outside: the pair fails
     const uint64_t total = n_seqs ? offsets[n_seqs] : 0;
     std::vector<uint8_t> codes((size_t)total + 1, 0);
@@ -585,64 +531,16 @@ int kaamer_align_pairs(int device, const uint8_t *seqs, const uint64_t *offsets,
         const std::vector<uint8_t> &ops = ops_of[wi];
         const uint32_t q = pair_query[pi], s = pair_subject[pi];
         const uint8_t *qa = seqs + offsets[q], *sb = seqs + offsets[s];
-        auto qchar = [&](int i) { const int c = qa[i]; return (char)((c == 'u' || c == 'U') ? '*' : c); };
-        auto schar = [&](int j) { const int c = sb[j]; return (char)((c == 'u' || c == 'U') ? '*' : c); };
         const int len = o.n_ops;
         a.aln_off = res->text.size();
         res->text.resize(res->text.size() + 3 * (size_t)len);
-        char *row_a = res->text.data() + a.aln_off, *row_m = row_a + len, *row_b = row_a + 2 * len;
-        float identity = 0, similarity = 0, nb_pos = 0;
-        int mismatches = 0, ai = o.start_i, bj = o.start_j;
-        for (int t = 0; t < len; t++) {
-            const uint8_t op = ops[(size_t)(len - 1 - t)];
-            const char ca = op == 'L' ? '-' : qchar(ai++), cb = op == 'U' ? '-' : schar(bj++);
-            row_a[t] = ca; row_b[t] = cb;
-            if (cb == ca) { identity += 1; similarity += 1; row_m[t] = cb; }                 // align.go:87-90
-            else {
-                if (cb != '-' && ca != '-') mismatches += 1;                                // align.go:92-94
-                const int ib = letter_index(cb), ia = letter_index(ca);
-                if (matrix[(ib < 0 ? 0 : ib) * NL + (ia < 0 ? 0 : ia)] > 0) { similarity += 1; row_m[t] = '+'; }   // GetAlnScoreAA > 0
-                else row_m[t] = ' ';
-            }
-            nb_pos += 1;
-        }
-        identity = (identity / nb_pos) * 100;                                               // align.go:101-102 (float32)
-        similarity = (similarity / nb_pos) * 100;
-        // align.go:105-133 over the feature pairs = maximal runs of one operation
-        int raw = 0, gap_openings = 0;
-        ai = o.start_i; bj = o.start_j;
-        for (int t = 0; t < len;) {
-            const uint8_t op = ops[(size_t)(len - 1 - t)];
-            int run = 0, score = 0;
-            while (t + run < len && ops[(size_t)(len - 1 - t - run)] == op) {
-                if (op == 'M') score += matrix[codes[(size_t)(offsets[q] + ai)] * NL + codes[(size_t)(offsets[s] + bj)]];
-                else if (op == 'U') score += matrix[codes[(size_t)(offsets[q] + ai)] * NL];
-                else score += matrix[codes[(size_t)(offsets[s] + bj)]];
-                if (op != 'L') ai++;
-                if (op != 'U') bj++;
-                run++;
-            }
-            if (op != 'M') score += dp_open;
-            raw += score;
-            if (score == -gap_open) {                                                       // align.go:127
-                gap_openings += 1;
-                raw -= (run - 1) * gap_extend;                                              // align.go:129-130
-            }
-            t += run;
-        }
-        a.identity = identity;
-        a.similarity = similarity;
-        a.length = len;
-        a.mismatches = mismatches;
-        a.gap_openings = gap_openings;
-        a.raw = raw;
-        a.bitscore = ((lambda * (double)raw) - std::log(kk)) / std::log(2.0);               // align.go:137
-        a.evalue = (double)(offsets[q + 1] - offsets[q]) * (double)number_of_aa / std::pow(2.0, a.bitscore);   // align.go:142
-        a.query_start = len ? o.start_i + 1 : 1;                                            // align.go:153-156
-        a.query_end = len ? o.end_i : 0;
-        a.subject_start = len ? o.start_j + 1 : 1;
-        a.subject_end = len ? o.end_j : 0;
-        a.status = 0;
+        kaamer_align_ints t;
+        memset(&t, 0, sizeof t);
+        t.n_ops = len; t.start_i = o.start_i; t.start_j = o.start_j; t.end_i = o.end_i; t.end_j = o.end_j;
+        kaamer_align_rows(ops.data(), len, qa, sb, o.start_i, o.start_j, matrix, gap_open, gap_extend, res->text.data() + a.aln_off, &t);
+        const uint64_t off = a.aln_off;
+        kaamer_align_finish(&a, &t, offsets[q + 1] - offsets[q], number_of_aa, lambda, kk);
+        a.aln_off = off;
     }
     *out = res;
     return KAAMER_OK;

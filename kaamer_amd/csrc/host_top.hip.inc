@@ -23,6 +23,18 @@ struct batch_top_owner {
     // ... or, in the interleaved result of a sharded index (no RepBlockHdr), the three arrays are at these places
     const int32_t *m_pos_len = nullptr;
     const uint64_t *m_pos_off = nullptr, *m_pos_bits = nullptr;
+    // the alignments of the reported hits (host_top_align.hip.inc), parallel to the CSR entries
+    bool has_aln = false, has_text = false;
+    std::vector<kaamer_alignment> aln;
+    std::vector<char> aln_text;
+};
+
+// the alignment half of a request (kaamer_*_batch_top_aln_flat)
+struct TopAlnRequest {
+    bool on = false;               // the options have a row in AllMatrixScores and name BLOSUM62
+    double lambda = 0, kk = 0;
+    int32_t gap_open = 0, gap_extend = 0;
+    bool text = false;
 };
 
 struct kaamer_ticket {
@@ -37,7 +49,17 @@ struct kaamer_ticket {
     BatchBounds b;
     int attempt;
     bool want_pos;   // PositionHits of the reported hits ride in the block (the *_pos_flat calls)
+    // the alignments of the reported hits ride in the block (the *_aln_flat calls)
+    bool want_aln, aln_on, aln_text;
+    int32_t gap_open, gap_extend;
+    double lambda, kk;
+    uint32_t max_query_len;   // residues of the batch's longest query (a bound for ORFs): sizes the direction slabs
+    uint64_t aln_cap;         // bytes the block's two sections may take
 };
+static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
+static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
+static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h);
+static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_owner *bo);
 
 // upper bound of the result block of a batch searched on `ws`, whose queries belong to `src` (ws itself, or the
 // workspace that translated the batch: merged results of a sharded index)
@@ -150,7 +172,7 @@ static void top_slot_free(TopSlot &h)
 
 // workspace, staging and result block of a slot: rebuilt only when the batch outgrows them
 static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace_opts &need, uint64_t seq_bytes, uint32_t n_seqs, uint32_t K,
-                            bool want_pos = false, uint32_t pos_scale = 0)
+                            bool want_pos = false, uint32_t pos_scale = 0, uint64_t aln_bytes = 0)
 {
     if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
     const kaamer_workspace_opts &o = h.opts;
@@ -200,7 +222,7 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
         const uint64_t hard = tp_hard_words(h.ws, K);
         h.pos_words = (first && pos_scale <= 1) ? (first < hard ? first : hard) : tp_default_words(h.ws, K, pos_scale);
     }
-    const size_t bneed = rep_block_bound(h.ws, h.ws, K, h.pos_words);
+    const size_t bneed = rep_block_bound(h.ws, h.ws, K, h.pos_words) + (aln_bytes ? (size_t)aln_bytes + 64 : 0);
     h.block_use = bneed;
     if (h.d_block_cap < bneed) {
         if (h.d_block) (void)hipFree(h.d_block);
@@ -228,7 +250,9 @@ static int top_enqueue(kaamer_ticket *t)
     o.first_pos = 0;  // as the reference fills PositionHits: nucleotide / reads input only (search.go:416)
     o.max_queries = t->b.max_queries;
     o.concurrent_batches = (uint32_t)ix->n_top;   // the slots exist so that batches overlap
-    int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results, t->want_pos, t->b.pos_scale);
+    const bool aligns = t->want_aln && t->aln_on;   // (without a matrix row nothing is aligned: the host marks every item)
+    if (aligns && !t->aln_cap) t->aln_cap = ta_first_cap(t, h);
+    int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results, t->want_pos, t->b.pos_scale, aligns ? t->aln_cap : 0);
     if (rc) return rc;
     hipStream_t s = h.stream;
     const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
@@ -245,6 +269,7 @@ static int top_enqueue(kaamer_ticket *t)
     if (!rc) rc = kaamer_topn_device(h.ws, &top, s, &tr);
     if (!rc) rc = topn_pack_block(h.ws, h.ws, 0u, 1u, &tr, s, h.d_block, h.block_use);
     if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
+    if (!rc && aligns) rc = top_enqueue_alignments(t, h, &tr, s);
     if (rc) return rc;
     // the speculative copy: as much as the previous call's block took (plus a quarter), never more than the block can hold
     size_t want = h.guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : h.guess;
@@ -261,7 +286,7 @@ static int top_enqueue(kaamer_ticket *t)
 }
 
 static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool blocking, kaamer_ticket **out,
-                      bool want_pos = false)
+                      bool want_pos = false, const TopAlnRequest *aln = nullptr)
 {
     if (!ix || !in || !top || !out || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
         return kaamer_fail(KAAMER_E_ARG, "submit_batch_top: bad argument");
@@ -284,6 +309,15 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
     t->ix = ix; t->slot = slot; t->n_seqs = in->n_seqs; t->seq_type = in->seq_type; t->seq_bytes = in->offsets[in->n_seqs];
     t->top = *top;
     t->want_pos = want_pos;
+    if (aln) {
+        t->want_aln = true; t->aln_on = aln->on; t->aln_text = aln->text;
+        t->gap_open = aln->gap_open; t->gap_extend = aln->gap_extend; t->lambda = aln->lambda; t->kk = aln->kk;
+        uint64_t longest = 0;
+        for (uint32_t i = 0; i < in->n_seqs; i++)
+            if (in->offsets[i + 1] >= in->offsets[i] && in->offsets[i + 1] - in->offsets[i] > longest) longest = in->offsets[i + 1] - in->offsets[i];
+        if (is_nucl(in->seq_type)) longest = longest / 3 + 2;   // an ORF holds at most a frame's codons
+        t->max_query_len = longest > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)longest;
+    }
     int rc = KAAMER_OK;
     hipError_t he = hipSetDevice(ix->device);
     if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(he));
@@ -350,6 +384,12 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
             continue;
         }
         if (rc) break;
+        if (t->want_aln && t->aln_on && ta_needs_repeat(t, h)) {   // the alignment sections were too small: once more, with what they needed
+            if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "alignment sections of the result block"); break; }
+            t->attempt++;
+            rc = top_enqueue(t);
+            continue;
+        }
         const size_t total = (size_t)hdr->total_bytes;
         h.guess = total + total / 4 + 4096;
         if (total > t->copied) {  // the guess was short: the rest of the block
@@ -378,8 +418,10 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         if (ix->top[t->slot].ws) ws_note_density(ix->top[t->slot].ws, bo->pub.counters);
         bo->pub.max_results = t->top.max_results;
         bo->has_pos = t->want_pos;
+        if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
         if (!nucl) bo->pub.orf_aa = nullptr;
-        *out = &bo->pub;
+        if (!rc) *out = &bo->pub;
+        else kaamer_batch_top_free(&bo->pub);
     }
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
     top_slot_release(ix, t->slot);

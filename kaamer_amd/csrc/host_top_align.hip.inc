@@ -1,0 +1,358 @@
+// host_top_align.hip.inc — the host side of the alignment of the reported hits (included by search.hip inside its
+// extern "C" block, after host_top.hip.inc; the kernels are in top_align.hip.inc):
+//   kaamer_index_attach_proteins      HitEntries (search.go:454-470) made resident next to the index
+//   ta_enqueue                        the stage on a stream, for both forms of the call
+//   kaamer_topn_align_device          the device-resident form
+//   kaamer_*_batch_top_aln_flat       the host-buffer form: top-N + alignment, one packed block, one D2H copy
+//   ta_finish_host                    floats, the sort by BitScore (search.go:492) and the three rows, on the host, through
+//                                     the code kaamer_align_pairs uses (align.hip)
+#define TA_DEFAULT_BUDGET (4ull << 30)
+#define TA_WAVES_PER_CU 5          /* a sizing rule, not a requirement: AlnWaveLds is 29 KB, five workgroups share a CU's 160 KB of
+                                      LDS, and slabs beyond what runs at once would only hold memory (waves take pairs by ticket) */
+#define TA_LONG_WAVES_MAX 256u       /* the long-subject kernel: as many slabs as the budget allows, up to this */
+
+int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p)
+{
+    if (!ix || !p) return kaamer_fail(KAAMER_E_ARG, "index_attach_proteins: bad argument");
+    HIPCHK(hipSetDevice(ix->device));
+    // the entries: one per distinct id, resolved as kaamer_fetch_hits resolves it (a later record with the same id wins)
+    const uint32_t n_rec = kaamer_proteins_count(p);
+    const uint32_t *ids = kaamer_proteins_ids(p);
+    std::vector<uint32_t> uniq(ids, ids + n_rec);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const uint32_t n = (uint32_t)uniq.size();
+    const uint64_t map_n = n ? (uint64_t)uniq.back() + 1 : 0;
+    if (map_n > (1ull << 31)) return kaamer_fail(KAAMER_E_ARG, "index_attach_proteins: protein ids up to %llu: the id map is dense", (unsigned long long)map_n);
+    std::vector<kaamer_protein_entry> ent(n);
+    int rc = kaamer_fetch_hits(p, uniq.data(), n, ent.data());
+    if (rc) return rc;
+    std::vector<uint64_t> off((size_t)n + 1, 0);
+    for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + ent[i].sequence_len;
+    std::vector<uint8_t> raw((size_t)off[n] + 1, 0), codes((size_t)off[n] + 1, 0), bad((size_t)n + 1, 0);
+    std::vector<uint32_t> idmap((size_t)map_n + 1, TA_NONE);
+    uint32_t max_ns = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        idmap[uniq[i]] = i;
+        if (ent[i].sequence_len > max_ns) max_ns = ent[i].sequence_len;
+        for (uint32_t j = 0; j < ent[i].sequence_len; j++) {
+            const int c = ent[i].sequence[j];
+            int k = aln_code(c);
+            if (k < 0) { bad[i] = 1; k = 0; }
+            raw[(size_t)off[i] + j] = (uint8_t)c;
+            codes[(size_t)off[i] + j] = (uint8_t)k;
+        }
+    }
+    uint64_t st[3] = {0, 0, 0};
+    kaamer_proteins_stats(p, st);
+    {   // nothing of the index may be running: the slots' streams are idle when no slot is busy
+        std::lock_guard<std::mutex> lock(ix->pool_mu);
+        for (int i = 0; i < ix->n_top; i++)
+            if (ix->top[i].busy) return kaamer_fail(KAAMER_E_BUSY, "index_attach_proteins: calls are in flight on the index");
+    }
+    HIPCHK(hipDeviceSynchronize());
+    const uint64_t budget = ix->aln_budget;
+    aln_table_free(ix);   // a second attach replaces the first
+    ix->aln_budget = budget;
+    rc = dev_alloc(&ix->d_aln_raw, raw.size());
+    if (!rc) rc = dev_alloc(&ix->d_aln_codes, codes.size());
+    if (!rc) rc = dev_alloc(&ix->d_aln_bad, bad.size());
+    if (!rc) rc = dev_alloc(&ix->d_aln_off, off.size());
+    if (!rc) rc = dev_alloc(&ix->d_aln_idmap, idmap.size());
+    if (!rc) rc = dev_alloc(&ix->d_aln_matrix, (size_t)ALN_NL * ALN_NL);
+    if (rc) { aln_table_free(ix); return rc; }
+    kaamer_align_matrix(ix->aln_matrix);
+    hipError_t e = hipMemcpy(ix->d_aln_raw, raw.data(), raw.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_aln_codes, codes.data(), codes.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_aln_bad, bad.data(), bad.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_aln_off, off.data(), off.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_aln_idmap, idmap.data(), idmap.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_aln_matrix, ix->aln_matrix, sizeof ix->aln_matrix, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { aln_table_free(ix); return kaamer_fail(KAAMER_E_HIP, "protein table upload: %s", hipGetErrorString(e)); }
+    ix->aln_host = p;
+    ix->aln_idmap_n = (uint32_t)map_n; ix->aln_entries = n; ix->aln_max_ns = max_ns;
+    ix->aln_number_of_aa = st[1];
+    ix->aln_bytes = raw.size() + codes.size() + bad.size() + off.size() * 8 + idmap.size() * 4 + sizeof ix->aln_matrix;
+    return KAAMER_OK;
+}
+
+int kaamer_index_align_info(const kaamer_index *cix, uint64_t out[8])
+{
+    if (!cix || !out) return kaamer_fail(KAAMER_E_ARG, "index_align_info: bad argument");
+    kaamer_index *ix = const_cast<kaamer_index *>(cix);
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    out[0] = ix->aln_bytes; out[1] = ix->aln_entries; out[2] = ix->aln_max_ns; out[3] = ix->aln_number_of_aa;
+    out[4] = ix->aln_budget ? ix->aln_budget : TA_DEFAULT_BUDGET;
+    out[5] = ix->aln_last[0]; out[6] = ix->aln_last[1]; out[7] = ix->aln_last[2];
+    return KAAMER_OK;
+}
+
+int kaamer_index_set_align_budget(kaamer_index *ix, uint64_t bytes)
+{
+    if (!ix) return kaamer_fail(KAAMER_E_ARG, "index_set_align_budget: bad argument");
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    ix->aln_budget = bytes;
+    return KAAMER_OK;
+}
+
+static int ta_check(const kaamer_index *ix, const kaamer_workspace *ws, const kaamer_topn_result *tr, const char *who)
+{
+    int rc = tp_check(ix, ws, tr, who);   // (a merged result: the queries' residues live on the owner's search workspace)
+    if (rc) return rc;
+    if (!ix->d_aln_raw) return kaamer_fail(KAAMER_E_ARG, "%s: no protein table is attached to the index (kaamer_index_attach_proteins)", who);
+    return KAAMER_OK;
+}
+
+// The stage on `s`, behind kaamer_topn_device (and, for the host-buffer form, topn_pack_block / topn_pack_positions).
+// eoff: the exclusive scan of top_cnt.  block != NULL: the two sections go behind the packed block; else pair records
+// into items[items_cap].
+static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *tr, const uint64_t *eoff, hipStream_t s,
+                      uint8_t *block, uint64_t block_cap, uint64_t aln_cap, bool want_text, int gap_open, int gap_extend,
+                      uint32_t max_query_len, kaamer_align_pair *items, uint64_t items_cap, uint64_t info[3])
+{
+    uint64_t budget;
+    { std::lock_guard<std::mutex> lock(ix->pool_mu); budget = ix->aln_budget ? ix->aln_budget : TA_DEFAULT_BUDGET; }
+    {   // first use; each buffer on its own, so that a failed allocation is tried again by the next call
+        int rc = KAAMER_OK;
+        if (!ws->d_ta_lay) rc = dev_alloc(&ws->d_ta_lay, 1);
+        if (!rc && !ws->d_ta_ctr) rc = dev_alloc(&ws->d_ta_ctr, 4);
+        if (!rc && !ws->d_ta_qcodes) rc = dev_alloc(&ws->d_ta_qcodes, (size_t)ws->pos_cap + 64);   // (pos_cap is fixed per workspace)
+        if (rc) return rc;
+    }
+    // slabs: the batch's longest query against the table's longest subject, capped at the wave kernel's LDS row
+    const uint64_t mq = max_query_len ? max_query_len : 1, strips = (mq + 63) / 64;
+    const uint64_t sub = ix->aln_max_ns < ALN_WAVE_NS ? (ix->aln_max_ns ? ix->aln_max_ns : 1) : ALN_WAVE_NS;
+    const uint64_t slab = strips * (sub + 63) * 64, opsb = (mq + sub + 63) & ~63ull;
+    uint64_t n_waves = budget / (slab + opsb);
+    const uint64_t resident = (uint64_t)ws->n_cu * TA_WAVES_PER_CU;
+    n_waves = n_waves < 1 ? 1 : (n_waves > resident ? resident : n_waves);
+    int rc = ta_grow(&ws->d_ta_dirs, &ws->ta_dirs_cap, n_waves * slab, s);
+    if (!rc) rc = ta_grow(&ws->d_ta_ops, &ws->ta_ops_cap, n_waves * opsb, s);
+    uint64_t n_long = 0, lslab = 0, lops = 0, lbnd = 0;
+    if (!rc && ix->aln_max_ns > ALN_WAVE_NS) {   // the table holds subjects beyond the LDS row: slabs of its longest one
+        const uint64_t ns = ix->aln_max_ns;
+        lslab = strips * (ns + 63) * 64; lops = (mq + ns + 63) & ~63ull; lbnd = 3 * (ns + 1);
+        n_long = budget / (lslab + lops + 4 * lbnd);
+        n_long = n_long < 1 ? 1 : (n_long > TA_LONG_WAVES_MAX ? TA_LONG_WAVES_MAX : n_long);
+        rc = ta_grow(&ws->d_ta_ldirs, &ws->ta_ldirs_cap, n_long * lslab, s);
+        if (!rc) rc = ta_grow(&ws->d_ta_lops, &ws->ta_lops_cap, n_long * lops, s);
+        if (!rc) rc = ta_grow(&ws->d_ta_lbnd, &ws->ta_lbnd_cap, n_long * lbnd, s);
+    }
+    if (rc) return rc;
+    TaParams p;
+    memset(&p, 0, sizeof p);
+    p.d_nq = ws->d_nq; p.q = ws->d_q;
+    p.top_cnt = tr->d_top_cnt; p.top_pid = tr->d_top_pid; p.trim = tr->d_trim; p.K = tr->max_results;
+    p.eoff = eoff;
+    p.qraw = ws->nucleotide ? ws->d_orf_aa : ws->last_seqs;
+    p.qcodes = ws->d_ta_qcodes;
+    p.tab.raw = ix->d_aln_raw; p.tab.codes = ix->d_aln_codes; p.tab.off = ix->d_aln_off; p.tab.bad = ix->d_aln_bad;
+    p.tab.idmap = ix->d_aln_idmap; p.tab.idmap_n = ix->aln_idmap_n;
+    p.matrix = ix->d_aln_matrix;
+    p.dp_open = kaamer_align_dp_open(); p.gap_open = gap_open; p.gap_extend = gap_extend;
+    p.lay = ws->d_ta_lay; p.ctr = ws->d_ta_ctr;
+    p.block = block; p.block_cap = block_cap; p.aln_cap = aln_cap; p.want_text = want_text ? 1 : 0;
+    p.items = items; p.items_cap = items_cap;
+    p.status = ws->d_status_out;
+    p.dirs = ws->d_ta_dirs; p.opsbuf = ws->d_ta_ops; p.slab_bytes = slab; p.ops_bytes = opsb;
+    hipLaunchKernelGGL(ta_layout_kernel, dim3(1), dim3(1), 0, s, p);
+    hipLaunchKernelGGL(ta_pairs_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(ta_wave_kernel<false>, dim3((unsigned)n_waves), dim3(64), 0, s, p);
+    if (n_long) {
+        TaParams pl = p;
+        pl.dirs = ws->d_ta_ldirs; pl.opsbuf = ws->d_ta_lops; pl.slab_bytes = lslab; pl.ops_bytes = lops;
+        pl.bnd = ws->d_ta_lbnd; pl.bnd_ints = lbnd;
+        hipLaunchKernelGGL(ta_wave_kernel<true>, dim3((unsigned)n_long), dim3(64), 0, s, pl);
+    }
+    if (block) hipLaunchKernelGGL(ta_finish_kernel, dim3(1), dim3(1), 0, s, p);
+    HIPCHK(hipGetLastError());
+    info[0] = n_waves; info[1] = slab; info[2] = n_long;
+    { std::lock_guard<std::mutex> lock(ix->pool_mu); ix->aln_last[0] = n_waves; ix->aln_last[1] = slab; ix->aln_last[2] = n_long; }
+    return KAAMER_OK;
+}
+
+int kaamer_topn_align_device(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *top, const kaamer_topn_align_opts *opts,
+                             void *stream, kaamer_topn_alignments *out)
+{
+    if (!opts || !out) return kaamer_fail(KAAMER_E_ARG, "topn_align_device: bad argument");
+    int rc = ta_check(ix, ws, top, "topn_align_device");
+    if (rc) return rc;
+    char name[sizeof opts->sub_matrix + 1];
+    memcpy(name, opts->sub_matrix, sizeof opts->sub_matrix);
+    name[sizeof opts->sub_matrix] = 0;
+    double lambda = 0, kk = 0;
+    if (!kaamer_align_options(name, opts->gap_open, opts->gap_extend, &lambda, &kk))
+        return kaamer_fail(KAAMER_E_ARG, "topn_align_device: No matrix found (or not BLOSUM62)");
+    HIPCHK(hipSetDevice(ws->device));
+    const bool on_count_stream = ws->split_pending && ws->count_stream;
+    hipStream_t s = on_count_stream ? ws->count_stream : (hipStream_t)stream;
+    uint64_t cap = opts->max_pairs;
+    if (!cap) { cap = (uint64_t)ws->q_cap * top->max_results; if (ws->hit_cap && ws->hit_cap < cap) cap = ws->hit_cap; }
+    if (!ws->d_ta_eoff) rc = dev_alloc(&ws->d_ta_eoff, (size_t)ws->q_cap + 1);   // (q_cap is fixed per workspace)
+    if (!rc) rc = ta_grow(&ws->d_ta_items, &ws->ta_items_cap, cap, s);
+    if (rc) return rc;
+    scan_u32_on(ws, top->d_top_cnt, ws->d_nq, ws->q_cap, ws->d_ta_eoff, s);
+    uint64_t mq = opts->max_query_len ? opts->max_query_len : ws->opts.max_seq_bytes;
+    if (mq > 0x3FFFFFFFull) mq = 0x3FFFFFFFull;
+    uint64_t info[3];
+    rc = ta_enqueue(ix, ws, top, ws->d_ta_eoff, s, nullptr, 0, 0, false, opts->gap_open, opts->gap_extend, (uint32_t)mq, ws->d_ta_items, cap, info);
+    if (rc) return rc;
+    if (on_count_stream) HIPCHK(hipEventRecord(ws->ev_count, s));
+    out->d_pair_off = ws->d_ta_eoff;
+    out->d_pairs = ws->d_ta_items;
+    out->pair_capacity = cap;
+    out->n_waves = (uint32_t)info[0]; out->n_long_waves = (uint32_t)info[2];
+    out->slab_bytes = info[1];
+    return KAAMER_OK;
+}
+
+// ---- the host-buffer form ---------------------------------------------------------------------------------------------
+// the stage of one ticket, behind its packed block (called by top_enqueue)
+static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s)
+{
+    int rc = ta_check(t->ix, h.ws, tr, "search_batch_top_aln");
+    if (rc) return rc;
+    uint64_t info[3];
+    return ta_enqueue(t->ix, h.ws, tr, h.ws->d_rep_eoff, s, h.d_block, h.block_use, t->aln_cap, t->aln_text, t->gap_open, t->gap_extend,
+                      t->max_query_len, nullptr, 0, info);
+}
+
+// what the block's two sections may take on the first attempt (a batch beyond it is repeated with what it needed)
+static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h)
+{
+    if (h.aln_guess) return h.aln_guess;
+    const uint64_t K = t->top.max_results;
+    if (is_nucl(t->seq_type)) return (1ull << 20) + t->seq_bytes / 4;
+    return (uint64_t)t->n_seqs * K * sizeof(kaamer_align_pair) + (t->aln_text ? 2 * K * t->seq_bytes : 0) + 4096;
+}
+
+// after the stream is done and the batch's status is fine: 1 = the sections were too small, repeat with t->aln_cap grown
+static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h)
+{
+    const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(t->h_block);
+    const RepAlnExt *x = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+    h.aln_guess = x->need_bytes + x->need_bytes / 4 + 4096;
+    if (x->need_bytes <= x->cap_bytes && x->off_items) return 0;
+    t->aln_cap = x->need_bytes + x->need_bytes / 4 + 65536;
+    return 1;
+}
+
+// floats, sort and rows of a finished result (bo's block is complete; the slot is still the ticket's)
+static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_owner *bo)
+{
+    kaamer_index *ix = t->ix;
+    const kaamer_batch_top &r = bo->pub;
+    const uint64_t n_ent = r.top_off[r.n_reported];
+    kaamer_alignment zero;
+    memset(&zero, 0, sizeof zero);
+    bo->aln.assign((size_t)n_ent, zero);
+    bo->has_aln = true;
+    bo->has_text = t->aln_text;
+    if (!t->aln_on) {   // "No matrix found": every hit keeps the empty AlignmentResult, in sortMapByValue order
+        for (kaamer_alignment &a : bo->aln) a.status = 1;
+        return KAAMER_OK;
+    }
+    const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(bo->block);
+    const RepAlnExt *x = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+    const kaamer_align_pair *items = reinterpret_cast<const kaamer_align_pair *>(bo->block + x->off_items);
+    const uint8_t *ops = bo->block + x->off_ops;
+    const bool nucl = is_nucl(t->seq_type);
+    uint32_t *pid = const_cast<uint32_t *>(r.top_pid), *km = const_cast<uint32_t *>(r.top_kmatch), *fp = const_cast<uint32_t *>(r.top_first_pos);
+    uint64_t *pos_off = nullptr;
+    if (bo->has_pos) {
+        const RepPosExt *px = reinterpret_cast<const RepPosExt *>(hdr->reserved);
+        if (px->off_pos_bits) pos_off = reinterpret_cast<uint64_t *>(bo->block + px->off_pos_off);
+    }
+    std::vector<uint32_t> order;
+    std::vector<kaamer_alignment> tmp_a;
+    std::vector<uint32_t> tmp_u;
+    std::vector<uint64_t> tmp_o;
+    for (uint32_t i = 0; i < r.n_reported; i++) {
+        const uint64_t a = r.top_off[i], b = r.top_off[i + 1];
+        // Query.Sequence: the reported ORF's residues in the block, or the record in the slot's copy of the batch input
+        const uint8_t *qraw = nucl ? r.orf_aa + r.q[i].aa_off : h.h_in + r.q[i].aa_off;
+        for (uint64_t e = a; e < b; e++) {
+            const kaamer_align_pair &it = items[e];
+            kaamer_alignment &al = bo->aln[(size_t)e];
+            if (it.status != 0) { al.status = it.status; continue; }   // the empty AlignmentResult (BitScore 0)
+            kaamer_align_ints ti;
+            ti.n_ops = it.n_ops; ti.start_i = it.start_i; ti.start_j = it.start_j; ti.end_i = it.end_i; ti.end_j = it.end_j;
+            ti.identical = it.identical; ti.similar = it.similar; ti.mismatches = it.mismatches; ti.gap_openings = it.gap_openings; ti.raw = it.raw;
+            kaamer_align_finish(&al, &ti, it.query_len, ix->aln_number_of_aa, t->lambda, t->kk);
+            if (t->aln_text) {
+                al.aln_off = bo->aln_text.size();
+                if (it.n_ops > 0) {
+                    kaamer_protein_entry pe;
+                    const int rc = kaamer_fetch_hits(ix->aln_host, &pid[e], 1, &pe);
+                    if (rc) return rc;
+                    if (!pe.found || it.off + (uint64_t)it.n_ops > x->ops_bytes) return kaamer_fail(KAAMER_E_FORMAT, "search_batch_top_aln: inconsistent result block");
+                    bo->aln_text.resize(bo->aln_text.size() + 3 * (size_t)it.n_ops);
+                    kaamer_align_rows(ops + it.off, it.n_ops, qraw, pe.sequence, it.start_i, it.start_j, ix->aln_matrix, t->gap_open, t->gap_extend,
+                                      bo->aln_text.data() + al.aln_off, nullptr);
+                }
+            }
+        }
+        // sort.Slice by BitScore, descending (search.go:492); ties keep sortMapByValue's order
+        const size_t n = (size_t)(b - a);
+        order.resize(n);
+        for (size_t k = 0; k < n; k++) order[k] = (uint32_t)k;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t u, uint32_t v) { return bo->aln[(size_t)a + u].bitscore > bo->aln[(size_t)a + v].bitscore; });
+        bool same = true;
+        for (size_t k = 0; k < n; k++) same = same && order[k] == k;
+        if (same) continue;
+        tmp_a.assign(bo->aln.begin() + (size_t)a, bo->aln.begin() + (size_t)b);
+        for (size_t k = 0; k < n; k++) bo->aln[(size_t)a + k] = tmp_a[order[k]];
+        for (uint32_t *arr : { pid, km, fp }) {
+            tmp_u.assign(arr + a, arr + b);
+            for (size_t k = 0; k < n; k++) arr[a + k] = tmp_u[order[k]];
+        }
+        if (pos_off) {
+            tmp_o.assign(pos_off + a, pos_off + b);
+            for (size_t k = 0; k < n; k++) pos_off[a + k] = tmp_o[order[k]];
+        }
+    }
+    return KAAMER_OK;
+}
+
+int kaamer_submit_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t want_positions,
+                                     const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text, kaamer_ticket **ticket)
+{
+    if (!ix || !sub_matrix || !ticket) return kaamer_fail(KAAMER_E_ARG, "submit_batch_top_aln: bad argument");
+    if (!ix->d_aln_raw) return kaamer_fail(KAAMER_E_ARG, "submit_batch_top_aln: no protein table is attached to the index (kaamer_index_attach_proteins)");
+    kaamer_batch_in in;
+    kaamer_topn_opts top;
+    flat_in(&in, seqs, offsets, n_seqs, seq_type, want_positions ? 1 : 0);
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    TopAlnRequest rq;
+    rq.on = kaamer_align_options(sub_matrix, gap_open, gap_extend, &rq.lambda, &rq.kk);
+    rq.gap_open = gap_open; rq.gap_extend = gap_extend; rq.text = want_text != 0;
+    return top_submit(ix, &in, &top, true, ticket, want_positions != 0, &rq);
+}
+
+int kaamer_search_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t want_positions,
+                                     const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text, kaamer_batch_top **out)
+{
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "search_batch_top_aln: bad argument");
+    *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_batch_top_aln_flat(ix, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, want_positions,
+                                                    sub_matrix, gap_open, gap_extend, want_text, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+int kaamer_batch_top_alignments(const kaamer_batch_top *out, const kaamer_alignment **items, const char **text)
+{
+    if (items) *items = nullptr;
+    if (text) *text = nullptr;
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_alignments: bad argument");
+    const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
+    if (!bo->has_aln) return KAAMER_OK;   // a call without alignments: both NULL
+    static const kaamer_alignment none = {};
+    if (items) *items = bo->aln.empty() ? &none : bo->aln.data();
+    static const char no_text[1] = { 0 };
+    if (text && bo->has_text) *text = bo->aln_text.empty() ? no_text : bo->aln_text.data();
+    return KAAMER_OK;
+}

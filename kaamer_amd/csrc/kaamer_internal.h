@@ -36,3 +36,19 @@ extern "C" void kaamer_proteins_raw(const kaamer_proteins *p, const uint8_t **se
 // Returns 0, or KAAMER_E_FORMAT when not even the first header is a gzip header (gzip.NewReader fails: no input).
 bool kaamer_is_gzip(const char *text, uint64_t len);
 int kaamer_gunzip(const char *text, uint64_t len, std::string *out);
+
+// The alignment step's shared statements (align.hip), for the stage that aligns the reported hits of a top-N call
+// (search.hip: top_align.hip.inc): the integers of one alignment as the device leaves them ...
+struct kaamer_align_ints {
+    int32_t n_ops, start_i, start_j, end_i, end_j;   // columns; 0-based cell before the first column, 1-based last cell
+    int32_t identical, similar, mismatches, gap_openings, raw;
+};
+int kaamer_align_dp_open();                 // the aligner's GapOpen (align.go:62-65)
+void kaamer_align_matrix(int *m676);        // BLOSUM62 in AAPosInMatrix order, row / column 0 = KAAMER_ALIGN_GAP_COLUMN (read once)
+// GetMatrixScores + "BLOSUM62 only": false = every alignment of the request has status 1
+bool kaamer_align_options(const char *sub_matrix, int gap_open, int gap_extend, double *lambda, double *k);
+// ... the floats of align.go:101-102,137,142 and the coordinates of :153-156 from them (aln_off is left alone)
+void kaamer_align_finish(kaamer_alignment *a, const kaamer_align_ints *t, uint64_t query_len, uint64_t number_of_aa, double lambda, double kk);
+// ... and the three rows from the operations (in reverse) and the raw letters; t (may be NULL) receives the tallies
+void kaamer_align_rows(const uint8_t *ops_rev, int len, const uint8_t *q, const uint8_t *s, int start_i, int start_j, const int *matrix,
+                       int gap_open, int gap_extend, char *rows, kaamer_align_ints *t);

@@ -127,6 +127,7 @@ struct TopSlot {
     size_t block_use = 0;      // bytes of d_block this call may fill: its bound (<= d_block_cap)
     uint64_t pos_words = 0;    // bitmap words of that bound (calls that ask for PositionHits of the reported hits)
     size_t guess = 1u << 16;   // bytes of the block copied before its size is known (adapts to the previous call)
+    uint64_t aln_guess = 0;    // bytes the alignment sections of the previous call needed, plus a quarter (0: none yet)
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
@@ -146,11 +147,23 @@ struct kaamer_index {
     TopSlot top[KAAMER_MAX_HOST_SLOTS];
     int n_top;
     uint64_t top_pos_words = 0;   // kaamer_index_set_top_positions_bound: first bitmap bound of the host calls (0: the rule)
+    // kaamer_index_attach_proteins: the Protein.Sequence table next to the index (top_align.hip.inc)
+    const kaamer_proteins *aln_host = nullptr;   // borrowed: the rows of a result with text read the subjects from it
+    uint8_t *d_aln_raw = nullptr, *d_aln_codes = nullptr, *d_aln_bad = nullptr;
+    uint64_t *d_aln_off = nullptr;
+    uint32_t *d_aln_idmap = nullptr;
+    int *d_aln_matrix = nullptr;
+    int aln_matrix[26 * 26];
+    uint32_t aln_idmap_n = 0, aln_entries = 0, aln_max_ns = 0;
+    uint64_t aln_bytes = 0, aln_number_of_aa = 0;
+    uint64_t aln_budget = 0;                     // kaamer_index_set_align_budget (0: the default)
+    uint64_t aln_last[3] = {0, 0, 0};            // the last stage: resident waves, slab bytes, long waves
 };
 
 enum { ST_POOL_FULL = 1u, ST_LIST_FULL = 2u, ST_QUERY_CAP = 4u, ST_AA_CAP = 8u, ST_G_ARENA_FULL = 16u, ST_G_TABLE_FULL = 32u,
        ST_POS_UNSUPPORTED = 64u, ST_POS_CAP = 128u, ST_CHAIN_TIMEOUT = 256u, ST_EXCHANGE_CAP = 512u, ST_PEER_FAILED = 1024u,
-       ST_IDS_CAP = 2048u /* an ids block of the sharded handle (top_positions_sharded.hip.inc) */ };
+       ST_IDS_CAP = 2048u /* an ids block of the sharded handle (top_positions_sharded.hip.inc) */,
+       ST_ALN_CAP = 4096u /* pair records of kaamer_topn_align_device (top_align.hip.inc) */ };
 enum { CTR_IN = 0, CTR_QUERIES, CTR_LOOKUP, CTR_PROBE, CTR_FOUND, CTR_POST, CTR_HITS, CTR_OVERFLOW, CTR_LISTS, CTR_LIST_IDS, CTR_N };
 static_assert(sizeof(kaamer_counters) == CTR_N * 8, "counter layout");
 #define CTR_REPLICAS 64
@@ -1373,6 +1386,7 @@ __global__ __launch_bounds__(64 * G_WAVES) void positions_global_kernel(CountPar
 #include "translate.hip.inc"
 #include "topn.hip.inc"
 #include "top_positions.hip.inc"
+#include "top_align.hip.inc"
 
 // ------------------------------------------------------------------------------------
 // exclusive scan of q_cnt[0..nq) -> hit_off[0..nq]
@@ -1591,6 +1605,17 @@ struct kaamer_workspace {
     uint64_t *d_tp_base;
     unsigned long long *d_tp_bits;
     uint64_t tp_alloc;                  // words d_tp_bits holds (grow-only)
+    // alignment of the reported hits (top_align.hip.inc), allocated on first use, grow-only
+    const uint8_t *last_seqs;           // the batch input of the last search (protein queries are aligned from it)
+    uint8_t *d_ta_qcodes;               // the queries' letter codes, by residue position
+    TaLayout *d_ta_lay;
+    unsigned long long *d_ta_ctr;
+    uint64_t *d_ta_eoff;                // device-resident form: its own scan of top_cnt
+    kaamer_align_pair *d_ta_items;      // ... and its pair records
+    uint64_t ta_items_cap;
+    uint8_t *d_ta_dirs, *d_ta_ops, *d_ta_ldirs, *d_ta_lops;   // per resident wave: direction slab, operations (wave / long form)
+    int *d_ta_lbnd;
+    uint64_t ta_dirs_cap, ta_ops_cap, ta_ldirs_cap, ta_lops_cap, ta_lbnd_cap;
     // exchange step of the sharded index (kaamer_exchange_pack / _merge), allocated on first use
     // exchange scratch: grow-only (the block layout may change from batch to batch within the buffers' capacity)
     size_t x_dst_cap, x_src_cap, x_ent_cap, x_m_cap;
@@ -1779,6 +1804,25 @@ static SearchKnobs read_knobs()
     return k;
 }
 
+// a grow-only device buffer of the workspace; whatever still reads the old one is on `s`
+template <class T> static int ta_grow(T **buf, uint64_t *cap, uint64_t need, hipStream_t s)
+{
+    if (*buf && *cap >= need) return KAAMER_OK;
+    if (*buf) { HIPCHK(hipStreamSynchronize(s)); (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
+    const int rc = dev_alloc(buf, (size_t)need);
+    if (!rc) *cap = need;
+    return rc;
+}
+
+// the device copy of the attached Protein.Sequence table (kaamer_index_attach_proteins)
+static void aln_table_free(kaamer_index *ix)
+{
+    void *bufs[] = { ix->d_aln_raw, ix->d_aln_codes, ix->d_aln_bad, ix->d_aln_off, ix->d_aln_idmap, ix->d_aln_matrix };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    ix->d_aln_raw = ix->d_aln_codes = ix->d_aln_bad = nullptr; ix->d_aln_off = nullptr; ix->d_aln_idmap = nullptr; ix->d_aln_matrix = nullptr;
+    ix->aln_host = nullptr; ix->aln_idmap_n = ix->aln_entries = ix->aln_max_ns = 0; ix->aln_bytes = ix->aln_number_of_aa = 0;
+}
+
 extern "C" {
 
 const char *kaamer_last_error(void) { return g_err; }
@@ -1889,6 +1933,7 @@ void kaamer_index_close(kaamer_index *ix)
     for (TopSlot &h : ix->top) top_slot_free(h);
     if (ix->d_buckets) (void)hipFree(ix->d_buckets);
     if (ix->d_arena) (void)hipFree(ix->d_arena);
+    aln_table_free(ix);
     delete ix;
 }
 
@@ -1910,7 +1955,8 @@ void kaamer_workspace_free(kaamer_workspace *ws)
                      ws->d_counter_replicas, ws->d_counters, ws->d_bsum, ws->d_chain, ws->d_tr_chain, ws->d_sched, ws->d_n_sched, ws->d_group_start, ws->d_lay_total, ws->d_slot_scale, ws->d_top_cnt, ws->d_top_pid, ws->d_top_km, ws->d_top_fp, ws->d_top_trim, ws->d_top_start, ws->d_top_size, ws->d_rep_flag, ws->d_rep_aalen, ws->d_rep_query, ws->d_rep_pid, ws->d_rep_km, ws->d_rep_fp, ws->d_rep_trim, ws->d_rep_rank, ws->d_rep_eoff, ws->d_rep_aoff, ws->d_rep_off, ws->d_rep_q, ws->d_rep_aa, ws->d_hit_off,
                      ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp, ws->d_x_dst_off, ws->d_x_src_off, ws->d_x_nq_owned, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, ws->d_x_ent_off, ws->d_x_tiles, ws->d_x_stats,
                      ws->d_x_dst_boff, ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_mdst, ws->d_x_msize, ws->d_x_mbits, ws->d_x_gtab, ws->d_x_pstats,
-                     ws->d_tp_words, ws->d_tp_len, ws->d_tp_base, ws->d_tp_bits };
+                     ws->d_tp_words, ws->d_tp_len, ws->d_tp_base, ws->d_tp_bits,
+                     ws->d_ta_qcodes, ws->d_ta_lay, ws->d_ta_ctr, ws->d_ta_eoff, ws->d_ta_items, ws->d_ta_dirs, ws->d_ta_ops, ws->d_ta_ldirs, ws->d_ta_lops, ws->d_ta_lbnd };
     for (void *b : bufs) if (b) (void)hipFree(b);
     if (ws->h_x_stats) {
         (void)hipHostFree(ws->h_x_stats);
@@ -2444,6 +2490,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     }
     ws->clean = true;  // everything up to finalize is enqueued
     ws->last_was_merge = false;
+    ws->last_seqs = d_seqs;
     if (timed) ws->n_timed++;
 
     out->n_queries_cap = ws->q_cap;
@@ -3103,6 +3150,7 @@ int kaamer_workspace_finish(kaamer_workspace *ws, void *stream, kaamer_counters 
         return kaamer_fail(KAAMER_E_CAPACITY, "more ORFs than the workspace holds: raise workspace max_queries (now %u)", ws->q_cap);
     if (status & ST_EXCHANGE_CAP) return kaamer_fail(KAAMER_E_CAPACITY, "exchange block capacity exceeded (or the blocks do not describe one batch): raise max_entries_per_peer / max_queries of the exchange layout");
     if (status & ST_PEER_FAILED) return kaamer_fail(KAAMER_E_CAPACITY, "a peer's search of this batch exceeded one of its workspace bounds: nothing was merged (that rank's kaamer_workspace_finish says which bound)");
+    if (status & ST_ALN_CAP) return kaamer_fail(KAAMER_E_CAPACITY, "more reported (query, hit) pairs than kaamer_topn_align_device provisioned: raise kaamer_topn_align_opts.max_pairs");
     if (status & ST_POS_CAP) return kaamer_fail(KAAMER_E_CAPACITY, "position bitmaps exceed the workspace: raise max_pos_words (now %llu)", (unsigned long long)ws->bits_cap);
     if (status & ST_G_ARENA_FULL)
         return kaamer_fail(KAAMER_E_CAPACITY, "global counting arena exhausted: raise workspace g_tier_slots (now %llu)", (unsigned long long)ws->g_slots);
@@ -3468,6 +3516,7 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 }
 
 #include "host_top.hip.inc"
+#include "host_top_align.hip.inc"
 #include "host_sharded.hip.inc"
 #include "host_replicas.hip.inc"
 

@@ -4,7 +4,10 @@ search_fastq.go, search_nucleotide.go) over the C ABI: same option names and def
 reference's JSON (docs/client.md:131-180).  All compute is in libkaamer_hip.so: readers and
 k-mer search; sortMapByValue, SetBestStartCodon and FilterResults run on the device
 (kaamer_search_batch_top) unless ExtractPositions asks for the full hit lists + bitmaps, in
-which case the host versions of the same C ABI are used.
+which case the host versions of the same C ABI are used.  With SearchOptions.Align and a protein table attached to the
+index (Index.attach_proteins) the drivers also return HitEntries and every hit's Alignment, hits in BitScore order: the
+alignment of the reported hits runs inside the same call (kaamer_search_batch_top_aln_flat).  Without a table the route
+is the one below: FetchHitsInformation, then AlignHits.
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -29,6 +32,37 @@ class SearchOptions:  # search.go:56-71 (the fields the hot path reads); default
     GapExtend: int = 1
 
 
+_EMPTY_ALN = {"Identity": 0.0, "Similarity": 0.0, "Length": 0, "Mismatches": 0, "GapOpenings": 0, "Raw": 0, "BitScore": 0.0,
+              "EValue": 0.0, "AlnString": "", "QueryStart": 0, "QueryEnd": 0, "SubjectStart": 0, "SubjectEnd": 0}
+
+
+def _one_call(index, o):
+    """SearchOptions.Align on an index with an attached protein table: top-N and the alignment of the reported hits in ONE
+    call (kaamer_search_batch_top_aln_flat) instead of FetchHitsInformation + AlignHits afterwards"""
+    return dict(sub_matrix=o.SubMatrix, gap_open=o.GapOpen, gap_extend=o.GapExtend, text=True) \
+        if o.Align and getattr(index, "proteins", None) is not None else None
+
+
+def _with_alignments(qr, top, i, proteins):
+    """QueryResultHandler's additions (search.go:454-494) to one QueryResult from a result with alignments: HitEntries
+    and every hit's Alignment; the hits already are in BitScore order"""
+    a, b = int(top.top_off[i]), int(top.top_off[i + 1])
+    alns = top.alignments[a:b]
+    keys = [int(p) for p in top.top_pid[a:b] ]
+    found = [k for k, al in zip(keys, alns) if al["status"] != 4]      # (4: no entry; FetchHitsInformation stopped there)
+    he = qr.setdefault("HitEntries", {})
+    for k, e in zip(found, proteins.fetch_hits(found) if found else []):
+        he[k] = {"EntryId": e["EntryId"].decode("latin-1"), "Sequence": e["Sequence"].decode("latin-1"), "Length": e["Length"],
+                 "Features": {n.decode("latin-1"): v.decode("latin-1") for n, v in e["Features"].items()}}
+    for h, al in zip(qr["SearchResults"]["Hits"], alns):
+        h["Alignment"] = dict(_EMPTY_ALN) if al["status"] else {
+            "Identity": al["identity"], "Similarity": al["similarity"], "Length": al["length"], "Mismatches": al["mismatches"],
+            "GapOpenings": al["gap_openings"], "Raw": al["raw"], "BitScore": al["bitscore"], "EValue": al["evalue"],
+            "AlnString": "\n".join(al["aln"]), "QueryStart": al["query_start"], "QueryEnd": al["query_end"],
+            "SubjectStart": al["subject_start"], "SubjectEnd": al["subject_end"]}
+    return qr
+
+
 def _sorted_hits(res, q):
     """sortMapByValue (search.go:132-152): Kmatch descending (ties by protein id)"""
     a, b = res.span(q)
@@ -51,8 +85,9 @@ def ProteinSearch(index, fasta_text, options=None):
     queries = api.parse_reads(fasta_text, "fasta")
     if not o.ExtractPositions:
         # sortMapByValue + FilterResults on the device: only the reported hits come back
+        aln = _one_call(index, o)
         top = index.search_top([q["seq"] for q in queries], seq_type=abi.PROTEIN, min_k_ratio=o.MinKRatio,
-                               min_k_match=o.MinKMatch, max_results=o.MaxResults)
+                               min_k_match=o.MinKMatch, max_results=o.MaxResults, align=aln)
         out = []
         for r in range(top.n_reported):   # search_protein.go:74-76, :108: the others are not reported
             q = queries[int(top.rep_query[r])]
@@ -62,6 +97,8 @@ def ProteinSearch(index, fasta_text, options=None):
                                                "StartsAlternative": []}, "Contig": ""},
                         "SearchResults": {"Hits": [{"Key": int(p), "Kmatch": int(k)}
                                                    for p, k in zip(top.top_pid[a:b], top.top_kmatch[a:b])]}})
+            if aln is not None:
+                _with_alignments(out[-1], top, r, index.proteins)
         return out
     res = index.search([q["seq"] for q in queries], seq_type=abi.PROTEIN, want_positions=o.ExtractPositions)
     out = []
@@ -86,8 +123,9 @@ def ProteinSearch(index, fasta_text, options=None):
 def _orf_results(index, reads, names, o, seq_type):
     if not o.ExtractPositions:
         # SetBestStartCodon, its gate and FilterResults on the device (kaamer_search_batch_top)
+        aln = _one_call(index, o)
         top = index.search_top(reads, seq_type=seq_type, min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch,
-                               max_results=o.MaxResults)
+                               max_results=o.MaxResults, align=aln)
         out = []
         for i in range(top.n_reported):
             a, b = int(top.top_off[i]), int(top.top_off[i + 1])
@@ -100,6 +138,8 @@ def _orf_results(index, reads, names, o, seq_type):
                                   "Contig": ""},
                         "SearchResults": {"Hits": [{"Key": int(p), "Kmatch": int(k)}
                                                    for p, k in zip(top.top_pid[a:b], top.top_kmatch[a:b])]}})
+            if aln is not None:
+                _with_alignments(out[-1], top, i, index.proteins)
         return out
     res = index.search(reads, seq_type=seq_type, want_positions=o.ExtractPositions)
     out = []
