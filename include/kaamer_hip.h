@@ -850,8 +850,8 @@ int32_t kaamer_align_matrix_entry(int32_t a, int32_t b);
 /* no packing, no upload, no rounds in between; only the per-pair integers and, on   */
 /* request, the operations come back, in the same packed block.  Matrix, gap column  */
 /* and tie rules are kaamer_align_pairs' own (one statement, align.hip); the numbers  */
-/* equal that call's bit for bit.  One device only: the sharded handle, replicas,     */
-/* kaamer_stream_* and kaamer_search_file have no such form.                          */
+/* equal that call's bit for bit.  On one device, and on the one-process sharded       */
+/* handle (below); replicas, kaamer_stream_* and kaamer_search_file have no such form. */
 /* ------------------------------------------------------------------------- */
 /* HitEntries (FetchHitsInformation, search.go:454-470) made resident: every entry's stored Protein.Sequence
  * (kaamer_protein_entry.sequence / sequence_len, not the Length clip), its letter codes, a "letter outside the
@@ -934,6 +934,48 @@ int kaamer_submit_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, cons
  * (three rows of `length` bytes), which is NULL for a result without text.  Both NULL for a result of a call without
  * alignments.  They live as long as the result does. */
 int kaamer_batch_top_alignments(const kaamer_batch_top *out, const kaamer_alignment **items, const char **text);
+
+/* The same on the one-process sharded handle (kaamer_index_open_sharded): replaces search.go:454-470 + :483-494 for a
+ * database larger than one device.  The reported hits of a query are known at its owner (device q mod W) only; the
+ * Protein.Sequence table is PARTITIONED, not replicated: device s of the handle receives the entries whose protein id
+ * satisfies id mod W == s -- their stored bytes, an offsets array and a local id -> entry map indexed by id / W -- so
+ * per-device HBM is about 1 / W of the sequence bytes and no device holds another's entries.  Ids resolve as
+ * kaamer_fetch_hits resolves them (a later record with the same id wins).  One more exchange behind top-N brings the
+ * subjects of the reported hits, and only those, to the owner, which aligns them there.  The rules of
+ * kaamer_index_attach_proteins carry over: the table is borrowed and must outlive the handle (or the next attach), a
+ * second attach replaces the first, KAAMER_E_BUSY while calls are in flight, NumberOfAA / the longest stored sequence /
+ * the BLOSUM62 matrix are kept per handle, kaamer_sharded_index_close frees the device copies. */
+int kaamer_sharded_index_attach_proteins(kaamer_sharded_index *sx, const kaamer_proteins *p);
+/* The direction-array budget of each owner's alignment stage: kaamer_index_set_align_budget's meaning, per owner. */
+int kaamer_sharded_index_set_align_budget(kaamer_sharded_index *sx, uint64_t bytes);
+/* out = { table bytes over all devices (0: none attached), the largest device's share, entries, longest stored sequence,
+ * NumberOfAA, bytes of the largest (holder -> owner) subject segment as it travelled in the last finished aligning call on
+ * the handle's first set, bytes that segment needed, attempts of that call } */
+int kaamer_sharded_align_info(kaamer_sharded_index *sx, uint64_t out[8]);
+/* Measurement (no Go counterpart): on != 0 brackets the three stages of every later aligning call with HIP events on the
+ * per-shard streams (no host synchronisation is added; off by default).  kaamer_sharded_align_stage_info: of the last
+ * finished aligning call on the handle's first set, out = { 1 if timing is on, microseconds of the gather stage (all owners'
+ * segments of one holder; the slowest holder), of the assemble stage (headers, layout, pairs kernel; the slowest owner), of
+ * the alignment stage (wave kernels and finish; the slowest owner) -- zeros while timing is off --, bytes of one ids block
+ * as it travelled, and of the owners' alignment stages the largest number of resident waves, bytes of one direction slab,
+ * resident waves of the long-subject kernel (0: not launched on any owner) } */
+int kaamer_sharded_index_set_align_timing(kaamer_sharded_index *sx, int32_t on);
+int kaamer_sharded_align_stage_info(kaamer_sharded_index *sx, uint64_t out[8]);
+/* kaamer_sharded_search_batch_top_flat / _top_pos_flat (want_positions != 0) with the alignment of every reported hit in
+ * the same call (search.go:454-470 + :483-494 for the whole batch): what kaamer_search_batch_top_aln_flat returns on an
+ * unsharded index of the whole database with the whole table attached, field for field, read with
+ * kaamer_batch_top_alignments / kaamer_batch_top_positions.  A subject segment or an alignment section that is too
+ * small repeats the batch inside kaamer_sharded_wait_batch_top with that bound grown alone; never a partial result; a
+ * failure on any shard or owner fails the call.  KAAMER_E_ARG when no table is attached to the handle.  A ticket is
+ * waited for with kaamer_sharded_wait_batch_top or dropped with kaamer_sharded_ticket_discard. */
+int kaamer_sharded_search_batch_top_aln_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                             int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                             int32_t want_positions, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                             int32_t want_text, kaamer_batch_top **out);
+int kaamer_sharded_submit_batch_top_aln_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                                             int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                             int32_t want_positions, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                             int32_t want_text, kaamer_sharded_ticket **ticket);
 
 /* ------------------------------------------------------------------------- */
 /* Readers — GetQueriesFasta / GetQueriesFastq (search.go:222-412) on a text   */

@@ -318,6 +318,17 @@ SYMBOLS = {
                                                    C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
                                                    C.POINTER(C.c_void_p)]),
     "kaamer_batch_top_alignments": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Alignment)), C.POINTER(C.POINTER(C.c_char))]),
+    # ... and on the sharded handle
+    "kaamer_sharded_index_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kaamer_sharded_index_set_align_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "kaamer_sharded_align_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_sharded_index_set_align_timing": (C.c_int, [C.c_void_p, C.c_int32]),
+    "kaamer_sharded_align_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_sharded_search_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
+                                                           C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "kaamer_sharded_submit_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
+                                                           C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.POINTER(C.c_void_p)]),
 }
 
 _lib = None

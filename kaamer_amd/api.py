@@ -541,6 +541,7 @@ class ShardedIndex:
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
+        self.proteins = None   # attach_proteins
 
     @classmethod
     def from_images(cls, images, devices):
@@ -561,14 +562,21 @@ class ShardedIndex:
         return cls(h.value)
 
     def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
-                   want_positions=False):
+                   want_positions=False, align=None):
         """What Index.search_top returns on an unsharded index of the whole database.  want_positions: the PositionHits
-        bitmaps of the reported hits come along (kaamer_sharded_search_batch_top_pos_flat; TopResult.positions)."""
+        bitmaps of the reported hits come along (kaamer_sharded_search_batch_top_pos_flat; TopResult.positions).
+        align: as Index.search_top's -- every reported hit aligned with its query in the same call
+        (kaamer_sharded_search_batch_top_aln_flat; needs attach_proteins): TopResult.alignments, hits in BitScore order."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         out = C.POINTER(abi.BatchTop)()
-        if want_positions:
+        if align is not None:
+            abi.check(abi.lib().kaamer_sharded_search_batch_top_aln_flat(
+                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
+                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
+                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(out)))
+        elif want_positions:
             abi.check(abi.lib().kaamer_sharded_search_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
                                                                          len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results,
                                                                          C.byref(out)))
@@ -585,17 +593,53 @@ class ShardedIndex:
             abi.lib().kaamer_batch_top_free(out)
 
     def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10,
-                   want_positions=False):
+                   want_positions=False, align=None):
         """kaamer_sharded_submit_batch_top_flat -> a ticket (wait() -> TopResult); up to three calls in flight per handle.
-        want_positions: kaamer_sharded_submit_batch_top_pos_flat (the bitmaps of the reported hits come along)."""
+        want_positions: kaamer_sharded_submit_batch_top_pos_flat (the bitmaps of the reported hits come along).
+        align: as search_top's (kaamer_sharded_submit_batch_top_aln_flat)."""
         buf, offs = packed if packed is not None else pack_sequences(seqs)
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         t = C.c_void_p()
+        if align is not None:
+            abi.check(abi.lib().kaamer_sharded_submit_batch_top_aln_flat(
+                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
+                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
+                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(t)))
+            return TopTicket(t, sharded=True)
         fn = abi.lib().kaamer_sharded_submit_batch_top_pos_flat if want_positions else abi.lib().kaamer_sharded_submit_batch_top_flat
         abi.check(fn(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
                      max_results, C.byref(t)))
         return TopTicket(t, sharded=True)
+
+    def attach_proteins(self, proteins):
+        """kaamer_sharded_index_attach_proteins: the table's Protein.Sequence entries become resident on the handle's
+        devices, partitioned by id mod W (the subjects of search_top(align=...)).  The table is borrowed by the library:
+        the handle keeps it alive."""
+        abi.check(abi.lib().kaamer_sharded_index_attach_proteins(self._h, proteins._h))
+        self.proteins = proteins
+
+    def align_info(self):
+        """kaamer_sharded_align_info -> dict"""
+        out = (C.c_uint64 * 8)()
+        abi.check(abi.lib().kaamer_sharded_align_info(self._h, out))
+        return dict(zip(("table_bytes", "largest_share", "entries", "max_subject_len", "number_of_aa", "segment_bytes", "need_bytes",
+                         "attempts"), (int(v) for v in out)))
+
+    def set_align_timing(self, on=True):
+        """kaamer_sharded_index_set_align_timing: HIP events around the gather, assemble and alignment stages of later calls"""
+        abi.check(abi.lib().kaamer_sharded_index_set_align_timing(self._h, int(bool(on))))
+
+    def align_stage_info(self):
+        """kaamer_sharded_align_stage_info -> dict (stage times in microseconds: zeros unless set_align_timing)"""
+        out = (C.c_uint64 * 8)()
+        abi.check(abi.lib().kaamer_sharded_align_stage_info(self._h, out))
+        return dict(zip(("timing", "gather_us", "assemble_us", "align_us", "ids_block_bytes", "waves", "slab_bytes", "long_waves"),
+                        (int(v) for v in out)))
+
+    def set_align_budget(self, nbytes):
+        """kaamer_sharded_index_set_align_budget: bytes of direction array each owner's alignment stage may hold; 0: the default"""
+        abi.check(abi.lib().kaamer_sharded_index_set_align_budget(self._h, int(nbytes)))
 
     def positions_info(self):
         """-> dict(ids_block_bytes, segment_bytes, need_words, attempts) of the last finished call with positions on the

@@ -14,6 +14,12 @@
 //   every owner d:  its reported ids as a compact ids block; every shard pulls all W of them
 //   every shard s:  per owner, the partial bitmaps its own vals[] give, into segment d of a send buffer
 //   every owner d:  pulls segment d of every shard and ORs them into the pos_bits section of its result block
+//   with the alignment of the reported hits (kaamer_sharded_search_batch_top_aln_flat), the same round trip carries the
+//   subjects (top_align_sharded.hip.inc): the Protein.Sequence table is partitioned over the devices by id mod W
+//   every owner d:  the same ids block (packed and pulled once when positions are wanted too)
+//   every holder s: per owner, the stored bytes of the reported subjects it holds, into segment d of a send buffer
+//   every owner d:  pulls segment d of every holder, assembles the pairs and aligns them (ta_stage, host_top_align.hip.inc);
+//                   pair records and operations are two more sections of its result block
 //   host:  interleaves the W owners' reported queries back into batch order (query q is owned by shard q mod W)
 // No external communicator, no second process.  (One process per GPU with RCCL is the other deployment:
 // kaamer_exchange_pack / kaamer_rccl_alltoall / kaamer_exchange_merge, INTEGRATION.md 4b.)
@@ -46,7 +52,17 @@ struct ShardState {
     unsigned long long *d_seg_send = nullptr, *d_seg_recv = nullptr;    // W segments each (one header word + the bitmap words)
     uint32_t *d_tps_words = nullptr, *d_tps_n = nullptr;                // [rq_cap]; per owner {reported queries, status}
     uint64_t *d_tps_base = nullptr;                                     // [W][rq_cap + 1] word offsets per owner
-    hipEvent_t ev_ids = nullptr, ev_bits = nullptr;
+    hipEvent_t ev_ids = nullptr, ev_bits = nullptr;   // the owner's ids block is packed; the shard's segments (bitmaps, subjects) are made
+    // top calls that align the reported hits (top_align_sharded.hip.inc)
+    TasLayout sa_cap{}, sa_wire{};     // a (holder -> owner) subject segment: capacity, and as it travels for the batch in flight
+    uint8_t *d_sa_send = nullptr, *d_sa_recv = nullptr, *d_sa_codes = nullptr;   // W segments each; the letter codes of the received ones
+    uint32_t *d_sa_qbytes = nullptr, *d_sa_n = nullptr;                          // [rq_cap + 1]; per owner {reported queries, status}
+    uint64_t *d_sa_off = nullptr;                                                // owner: per pair, where its subject lies in d_sa_recv
+    unsigned long long *d_sa_need = nullptr;                                     // holder: per owner {payload bytes needed, status}
+    uint64_t aln_guess = 0;            // bytes the alignment sections of this owner's previous block needed, plus a quarter
+    uint64_t sa_stage[3] = {0, 0, 0};  // the owner's last alignment stage: resident waves, slab bytes, long-subject waves
+    hipEvent_t ev_t[5] = {};           // kaamer_sharded_index_set_align_timing: gather begin / end, assemble begin, alignment begin / end
+    bool timed = false;                // ... recorded for the attempt in flight
 };
 
 // everything one call in flight needs on every shard (the indices themselves are shared by all sets)
@@ -64,6 +80,13 @@ struct ShardSet {
     uint64_t need_ids_ent = 0, need_tp_words = 0;
     uint64_t tp_ids_bytes = 0, tp_seg_bytes = 0, tp_attempts = 0;   // kaamer_sharded_positions_info
     uint32_t seq = 0;            // batch sequence of the ids blocks and segments
+    // the previous aligning call on this set: payload bytes the largest subject segment needed; kaamer_sharded_align_info
+    bool sa_seen = false;
+    uint64_t need_sa_bytes = 0;
+    uint64_t sa_seg_bytes = 0, sa_need_seg = 0, sa_attempts = 0;
+    uint64_t sa_ids_bytes = 0;                  // one ids block as it travelled in that call
+    uint64_t sa_us[3] = {0, 0, 0};              // its gather, assemble and alignment stages: the slowest device's, microseconds (timing on)
+    uint64_t sa_stage[3] = {0, 0, 0};           // waves, slab bytes, long-subject waves: the largest over the owners
 };
 #define KAAMER_SHARDED_SETS 3   /* calls in flight per handle: the goroutines of search_fastq.go:60-66 against one handle */
 
@@ -74,6 +97,22 @@ struct kaamer_sharded_index {
     ShardSet *sets = nullptr;                    // KAAMER_SHARDED_SETS of them; a call takes a free one, callers beyond wait
     std::mutex mu;
     std::condition_variable cv;
+    // kaamer_sharded_index_attach_proteins: the Protein.Sequence table, partitioned over the devices by id mod W
+    struct AlnPart {
+        uint8_t *d_raw = nullptr;      // the stored bytes of the entries this device holds
+        uint64_t *d_off = nullptr;     // entries + 1
+        uint32_t *d_idmap = nullptr;   // id / W -> entry, TA_NONE: no entry
+        int *d_matrix = nullptr;
+        uint32_t idmap_n = 0, entries = 0;
+        uint64_t bytes = 0;
+    };
+    std::vector<AlnPart> *aln = nullptr;         // one per device once a table is attached
+    const kaamer_proteins *aln_host = nullptr;   // borrowed: the rows of a result with text read the subjects from it
+    int aln_matrix[26 * 26];
+    uint32_t aln_entries = 0, aln_max_ns = 0;
+    uint64_t aln_bytes = 0, aln_share = 0, aln_number_of_aa = 0;
+    uint64_t aln_budget = 0;                     // kaamer_sharded_index_set_align_budget (0: the default)
+    bool aln_timing = false;                     // kaamer_sharded_index_set_align_timing
 };
 
 static void shard_tps_free(ShardState &s)
@@ -82,6 +121,28 @@ static void shard_tps_free(ShardState &s)
     for (void *b : bufs) if (b) (void)hipFree(b);
     s.d_ids = s.d_ids_recv = nullptr; s.d_seg_send = s.d_seg_recv = nullptr;
     s.d_tps_words = s.d_tps_n = nullptr; s.d_tps_base = nullptr;
+}
+
+static void shard_sa_free(ShardState &s)
+{
+    void *bufs[] = { s.d_sa_send, s.d_sa_recv, s.d_sa_codes, s.d_sa_qbytes, s.d_sa_n, s.d_sa_off, s.d_sa_need };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    s.d_sa_send = s.d_sa_recv = s.d_sa_codes = nullptr; s.d_sa_qbytes = s.d_sa_n = nullptr; s.d_sa_off = nullptr; s.d_sa_need = nullptr;
+    s.sa_cap = TasLayout();
+}
+
+static void sharded_aln_free(kaamer_sharded_index *sx)
+{
+    if (!sx->aln) return;
+    for (uint32_t s = 0; s < sx->n; s++) {
+        kaamer_sharded_index::AlnPart &a = (*sx->aln)[s];
+        (void)hipSetDevice((*sx->dev)[s]);
+        void *bufs[] = { a.d_raw, a.d_off, a.d_idmap, a.d_matrix };
+        for (void *b : bufs) if (b) (void)hipFree(b);
+    }
+    delete sx->aln;
+    sx->aln = nullptr; sx->aln_host = nullptr;
+    sx->aln_entries = sx->aln_max_ns = 0; sx->aln_bytes = sx->aln_share = sx->aln_number_of_aa = 0;
 }
 
 static void shard_state_free(ShardState &s)
@@ -93,10 +154,12 @@ static void shard_state_free(ShardState &s)
     void *bufs[] = { s.d_send, s.d_recv, s.d_seqs, s.d_off, s.d_block };
     for (void *b : bufs) if (b) (void)hipFree(b);
     shard_tps_free(s);
+    shard_sa_free(s);
     if (s.h_block) pinned_put(s.h_block, s.h_block_cap);
     if (s.ev_packed) (void)hipEventDestroy(s.ev_packed);
     if (s.ev_ids) (void)hipEventDestroy(s.ev_ids);
     if (s.ev_bits) (void)hipEventDestroy(s.ev_bits);
+    for (hipEvent_t e : s.ev_t) if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = ShardState();   // (the index belongs to the handle)
 }
@@ -111,6 +174,7 @@ void kaamer_sharded_index_close(kaamer_sharded_index *sx)
         }
         delete[] sx->sets;
     }
+    if (sx->dev) sharded_aln_free(sx);
     if (sx->ix) {
         for (kaamer_index *ix : *sx->ix) if (ix) kaamer_index_close(ix);
         delete sx->ix;
@@ -209,6 +273,9 @@ struct ShardBounds {
     bool full, pos;      // a full call (hit lists to the host), with PositionHits bitmaps
     uint64_t p_cap;      // bitmap words per block (pos)
     bool tpos;           // a top call with the PositionHits of the reported hits (its bounds: bb.pos_scale x the rule)
+    bool aln;            // a top call that aligns the reported hits
+    uint64_t sa_bytes;   // payload bytes of one (holder -> owner) subject segment (aln)
+    uint64_t aln_cap;    // bytes the alignment sections of an owner's result block may take (aln)
 };
 
 // ---- the four device steps of the reported hits' bitmaps, as functions of (workspaces, buffers, stream) ------------------
@@ -286,6 +353,39 @@ static int tps_enqueue_or(const kaamer_index *ix, kaamer_workspace *mws, kaamer_
     return KAAMER_OK;
 }
 
+// ---- the two device steps of the reported hits' alignment (top_align_sharded.hip.inc) ----------------------------------
+// holder `st` (device s): the stored bytes of the subjects it holds among owner d's reported ids, into segment d
+static int tas_enqueue_gather(kaamer_sharded_index *sx, ShardState &st, uint32_t s, uint32_t d, uint32_t W, uint32_t seq, uint32_t K)
+{
+    const kaamer_sharded_index::AlnPart &part = (*sx->aln)[s];
+    const size_t iw = (size_t)tps_ids_words(st.ids_wire), ab = (size_t)tas_seg_bytes(st.sa_wire);
+    TasParams p;
+    memset(&p, 0, sizeof p);
+    p.world = W; p.owner = d; p.self = s; p.seq = seq; p.K = K;
+    p.ids_layout = st.ids_wire; p.lay = st.sa_wire;
+    p.ids = st.d_ids_recv + (size_t)d * iw;
+    p.s_nq = st.ws->d_nq; p.s_status = st.ws->d_status_out;
+    p.raw = part.d_raw; p.off = part.d_off; p.idmap = part.d_idmap; p.idmap_n = part.idmap_n;
+    p.n_out = st.d_sa_n + 2 * d; p.qbytes = st.d_sa_qbytes;
+    p.seg = st.d_sa_send + (size_t)d * ab;
+    p.need_out = st.d_sa_need + 2 * d;
+    uint32_t gb = (st.sa_wire.rq_cap + 3) / 4;   // a wave per reported query
+    if (gb > (uint32_t)st.ws->n_cu * 8) gb = (uint32_t)st.ws->n_cu * 8;
+    if (gb < 1) gb = 1;
+    hipLaunchKernelGGL(tas_len_kernel, dim3(gb), dim3(256), 0, st.stream, p);
+    // (an owner reports at most the batch's queries: the workspace's scan scratch, sized for q_cap, is enough)
+    scan_u32_on(st.ws, st.d_sa_qbytes, st.d_sa_n + 2 * d, st.sa_wire.rq_cap < st.ws->q_cap ? st.sa_wire.rq_cap : st.ws->q_cap,
+                reinterpret_cast<uint64_t *>(p.seg + tas_base_at()), st.stream);
+    hipLaunchKernelGGL(tas_gather_kernel, dim3(gb), dim3(256), 0, st.stream, p);
+    HIPCHK(hipGetLastError());
+    return KAAMER_OK;
+}
+
+// owner `ow` (device d), its W segments pulled: the headers, then the stage of host_top_align.hip.inc fed the gathered
+// subjects; pair records and operations go behind the packed block (and its bitmaps)
+static int tas_enqueue_align(kaamer_sharded_index *sx, const kaamer_sharded_ticket *t, ShardState &ow, const kaamer_topn_result *tr, uint32_t d,
+                             uint32_t W, uint32_t seq, uint64_t budget);
+
 static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq_bytes, uint32_t n_seqs, int32_t seq_type, const ShardBounds &b, uint32_t K)
 {
     HIPCHK(hipSetDevice(st.device));
@@ -354,7 +454,7 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
     // repeat that grows pos_scale alone (or a larger MaxResults) makes these buffers and the result block again, nothing
     // else: the workspaces and the exchange buffers stay.
     const uint32_t scale = b.bb.pos_scale ? b.bb.pos_scale : 1u;
-    if (b.tpos && (st.tp_k < K || st.tp_scale < scale)) {
+    if ((b.tpos || b.aln) && (st.tp_k < K || st.tp_scale < scale)) {   // (the ids block serves both kinds; the rest is the bitmaps')
         HIPCHK(hipStreamSynchronize(st.stream));
         shard_tps_free(st);
         const uint64_t hard = tp_hard_words(st.ws, K);
@@ -367,20 +467,40 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
         const size_t iw = (size_t)tps_ids_words(st.ids_cap), sw = (size_t)st.tp_cap + 1;
         int rc = dev_alloc(&st.d_ids, iw);
         if (!rc) rc = dev_alloc(&st.d_ids_recv, (size_t)W * iw);
-        if (!rc) rc = dev_alloc(&st.d_seg_send, (size_t)W * sw);
-        if (!rc) rc = dev_alloc(&st.d_seg_recv, (size_t)W * sw);
-        if (!rc) rc = dev_alloc(&st.d_tps_words, (size_t)oq + 1);
-        if (!rc) rc = dev_alloc(&st.d_tps_n, (size_t)2 * W);
-        if (!rc) rc = dev_alloc(&st.d_tps_base, (size_t)W * (oq + 1));
+        if (!rc && b.tpos) rc = dev_alloc(&st.d_seg_send, (size_t)W * sw);
+        if (!rc && b.tpos) rc = dev_alloc(&st.d_seg_recv, (size_t)W * sw);
+        if (!rc && b.tpos) rc = dev_alloc(&st.d_tps_words, (size_t)oq + 1);
+        if (!rc && b.tpos) rc = dev_alloc(&st.d_tps_n, (size_t)2 * W);
+        if (!rc && b.tpos) rc = dev_alloc(&st.d_tps_base, (size_t)W * (oq + 1));
         if (rc) { shard_tps_free(st); st.tp_k = 0; st.tp_scale = 0; return rc; }
         st.tp_k = K; st.tp_scale = scale;
     }
+    // the subject segments: what the ids block can describe, and the payload bound of this attempt.  They alone are made
+    // again when that bound grows.
+    if (b.aln && (!st.d_sa_send || st.sa_cap.rq_cap < st.ids_cap.rq_cap || st.sa_cap.ent_cap < st.ids_cap.ent_cap || st.sa_cap.byte_cap < b.sa_bytes)) {
+        HIPCHK(hipStreamSynchronize(st.stream));
+        TasLayout L;
+        L.rq_cap = st.ids_cap.rq_cap; L.ent_cap = st.ids_cap.ent_cap;
+        L.byte_cap = st.sa_cap.byte_cap > b.sa_bytes ? st.sa_cap.byte_cap : b.sa_bytes;
+        shard_sa_free(st);
+        const size_t sb = (size_t)tas_seg_bytes(L);
+        int rc = dev_alloc(&st.d_sa_send, (size_t)W * sb);
+        if (!rc) rc = dev_alloc(&st.d_sa_recv, (size_t)W * sb);
+        if (!rc) rc = dev_alloc(&st.d_sa_codes, (size_t)W * sb);
+        if (!rc) rc = dev_alloc(&st.d_sa_qbytes, (size_t)L.rq_cap + 1);
+        if (!rc) rc = dev_alloc(&st.d_sa_n, (size_t)2 * W);
+        if (!rc) rc = dev_alloc(&st.d_sa_off, (size_t)L.ent_cap + 1);
+        if (!rc) rc = dev_alloc(&st.d_sa_need, (size_t)2 * W);
+        if (rc) { shard_sa_free(st); return rc; }
+        st.sa_cap = L;
+    }
     int rc = dev_grow(&st.d_seqs, &st.seq_cap, (size_t)seq_bytes + 16);
     if (!rc) rc = dev_grow(&st.d_off, &st.off_cap, (size_t)n_seqs + 1);
-    if (!rc && !b.full) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K, b.tpos ? st.tp_cap : 0));
+    if (!rc && !b.full) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K, b.tpos ? st.tp_cap : 0) + (b.aln ? (size_t)b.aln_cap + 64 : 0));
     return rc;
 }
 
+struct kaamer_sharded_ticket;
 // one call in flight on a set: what submit leaves for wait
 struct kaamer_sharded_ticket {
     kaamer_sharded_index *sx;
@@ -394,11 +514,51 @@ struct kaamer_sharded_ticket {
     bool pos_only;   // the attempt failed on the reported hits' ids blocks / bitmap segments alone (ST_IDS_CAP, ST_POS_CAP):
                      // only their bound (BatchBounds::pos_scale) grows, and only their buffers are made again
     int attempt;
+    // the alignment of the reported hits (kaamer_sharded_submit_batch_top_aln_flat)
+    bool want_aln;            // the result carries alignments; b.aln: the options name BLOSUM62 with a row, the exchange runs
+    TopAlnRequest aln;
+    uint32_t max_query_len;   // residues of the batch's longest query (a bound for ORFs): sizes the direction slabs
+    uint32_t cap_bits;        // the owners' status words of the attempt, OR-ed
+    bool grow_sections;       // the attempt was fine but for an owner's alignment sections: they alone grow
 };
 // a full call (kaamer_sharded_search_batch): the same pipeline without the post-steps (t.b.full)
 struct kaamer_sharded_full_ticket {
     kaamer_sharded_ticket t;
 };
+
+static int tas_enqueue_align(kaamer_sharded_index *sx, const kaamer_sharded_ticket *t, ShardState &ow, const kaamer_topn_result *tr, uint32_t d,
+                             uint32_t W, uint32_t seq, uint64_t budget)
+{
+    const kaamer_sharded_index::AlnPart &part = (*sx->aln)[d];
+    const size_t iw = (size_t)tps_ids_words(ow.ids_wire), ab = (size_t)tas_seg_bytes(ow.sa_wire);
+    kaamer_workspace *mws = ow.mws, *ws = ow.ws;
+    TasParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.world = W; sp.owner = d; sp.self = d; sp.seq = seq; sp.K = tr->max_results;
+    sp.ids_layout = ow.ids_wire; sp.lay = ow.sa_wire;
+    sp.ids = ow.d_ids_recv + (size_t)d * iw;
+    sp.m_nq = mws->d_nq; sp.q = ws->d_q;
+    sp.top_cnt = tr->d_top_cnt; sp.top_pid = tr->d_top_pid; sp.trim = tr->d_trim;
+    sp.rank = mws->d_rep_rank; sp.eoff = mws->d_rep_eoff;
+    sp.qraw = ws->nucleotide ? ws->d_orf_aa : ws->last_seqs;
+    sp.segs = ow.d_sa_recv; sp.seg_stride = ab; sp.codes = ow.d_sa_codes; sp.pair_off = ow.d_sa_off;
+    sp.block = ow.d_block;
+    hipLaunchKernelGGL(tas_check_kernel, dim3(1), dim3(1), 0, ow.stream, sp);
+    TaParams p;
+    memset(&p, 0, sizeof p);
+    p.d_nq = mws->d_nq; p.q = ws->d_q;
+    p.top_cnt = tr->d_top_cnt; p.top_pid = tr->d_top_pid; p.trim = tr->d_trim; p.K = tr->max_results;
+    p.eoff = mws->d_rep_eoff;
+    p.qraw = sp.qraw;
+    p.tab.raw = ow.d_sa_recv; p.tab.codes = ow.d_sa_codes; p.tab.off = ow.d_sa_off;   // (bad, idmap: ta_pairs_kernel's, not read here)
+    p.matrix = part.d_matrix;
+    p.gap_open = t->aln.gap_open; p.gap_extend = t->aln.gap_extend;
+    p.block = ow.d_block; p.block_cap = ow.d_block_cap; p.aln_cap = t->b.aln_cap; p.want_text = t->aln.text ? 1 : 0;
+    p.status = mws->d_status_out;
+    return ta_stage(ws, p, budget, sx->aln_max_ns, t->max_query_len, &sp, ow.stream, ow.sa_stage, ow.timed ? ow.ev_t + 2 : nullptr);
+}
+
+static inline bool tpos_or_aln(const kaamer_sharded_ticket *t) { return t->b.tpos || t->b.aln; }
 
 static void sharded_sync_all(ShardSet *set)
 {
@@ -444,11 +604,18 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
     } guard{ sx, true };
     for (uint32_t s = 0; s < W; s++) {
         const int rc = shard_prepare(sh[s], W, s, seq_bytes, t->n_seqs, t->seq_type, t->b, t->top.max_results);
-        if (rc) return rc;
+        if (rc) {
+            // some shards are prepared for this call and some are not: the ids blocks and segments have one layout on every
+            // shard of a set, so all of them are sized again by the next call
+            for (ShardState &x : sh) { x.tp_k = 0; x.tp_scale = 0; x.sa_cap = TasLayout(); }
+            return rc;
+        }
     }
     // the blocks of this batch: what the previous batch on this set needed + a quarter (its W x W headers, read after the
     // call), or the capacity for a first call and for a retry.  What the peer copies move is payload, not capacity.
-    t->adaptive = t->attempt == 0 && sx->need_entries != 0 && (!t->b.pos || sx->need_pos_words != 0) && (!t->b.tpos || sx->tp_seen);
+    t->adaptive = t->attempt == 0 && sx->need_entries != 0 && (!t->b.pos || sx->need_pos_words != 0) && (!t->b.tpos || sx->tp_seen) &&
+                  (!t->b.aln || sx->sa_seen);
+    const bool ids = t->b.tpos || t->b.aln;   // the round trip after top-N: the owners' ids blocks, the shards' segments
     const uint32_t seq = ++sx->seq;
     for (uint32_t s = 0; s < W; s++) {
         ShardState &st = sh[s];
@@ -460,7 +627,7 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
                                     : kaamer_exchange_layout_fit(&st.layout, nq, ne, (nucl || t->b.full) ? 1 : 0, &st.wire);
             if (rc) return rc;
         }
-        if (t->b.tpos) {   // the ids blocks and bitmap segments of this batch: sized the same way
+        if (ids) {   // the ids blocks and segments of this batch: sized the same way
             st.ids_wire = st.ids_cap;
             st.tp_wire = st.tp_cap;
             if (t->adaptive) {
@@ -469,6 +636,16 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
                 if (rq < st.ids_cap.rq_cap) st.ids_wire.rq_cap = (uint32_t)rq;
                 if (ne < st.ids_cap.ent_cap) st.ids_wire.ent_cap = ne;
                 if (nw < st.tp_cap) st.tp_wire = nw;
+            }
+        }
+        if (t->b.aln) {   // a subject segment describes what the previous batch reported + a quarter, and holds its payload + a quarter
+            st.sa_wire = st.sa_cap;
+            if (t->adaptive) {
+                const uint64_t rq = (uint64_t)sx->need_ids_rq + sx->need_ids_rq / 4 + 16, ne = sx->need_ids_ent + sx->need_ids_ent / 4 + 64,
+                               nb = sx->need_sa_bytes + sx->need_sa_bytes / 4 + 256;
+                if (rq < st.sa_cap.rq_cap) st.sa_wire.rq_cap = (uint32_t)rq;
+                if (ne < st.sa_cap.ent_cap) st.sa_wire.ent_cap = ne;
+                if (nb < st.sa_cap.byte_cap) st.sa_wire.byte_cap = nb;
             }
         }
     }
@@ -485,6 +662,7 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
         HIPCHK(hipEventRecord(st.ev_packed, st.stream));
     }
     // ---- every owner: pull its blocks, merge, post-steps, result block
+    std::vector<kaamer_topn_result> trs(W);
     for (uint32_t d = 0; d < W; d++) {
         ShardState &ow = sh[d];
         HIPCHK(hipSetDevice(ow.device));
@@ -511,7 +689,8 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
         int rc = kaamer_exchange_merge(ow.mws, &ow.wire, ow.d_recv, ow.stream, &mr);
         if (!rc) rc = kaamer_topn_device(ow.mws, &tt, ow.stream, &tr);
         if (!rc) rc = topn_pack_block(ow.mws, ow.ws, d, W, &tr, ow.stream, ow.d_block, ow.d_block_cap);
-        if (!rc && t->b.tpos) {   // the result block waits for its bitmaps (below)
+        trs[d] = tr;
+        if (!rc && ids) {   // the result block waits for its bitmaps and alignments (below)
             rc = tps_enqueue_ids_pack(ow.mws, &tr, ow.d_block, ow.d_block_cap, ow.d_ids, ow.ids_wire, d, W, seq, ow.stream);
             if (rc) return rc;
             HIPCHK(hipEventRecord(ow.ev_ids, ow.stream));
@@ -521,9 +700,14 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
         rc = sharded_copy_back(ow);
         if (rc) return rc;
     }
-    if (t->b.tpos) {
+    if (ids) {
         const uint32_t K = t->top.max_results;
-        // ---- every shard: pulls the W ids blocks, its partial bitmaps of each owner's reported hits into segment d
+        const bool tpos = t->b.tpos, aln = t->b.aln;
+        uint64_t budget = 0;
+        bool timing = false;
+        if (aln) { std::lock_guard<std::mutex> lock(sx_->mu); budget = sx_->aln_budget ? sx_->aln_budget : TA_DEFAULT_BUDGET; timing = sx_->aln_timing; }
+        // ---- every shard: pulls the W ids blocks; per owner, its partial bitmaps of the reported hits and the stored bytes
+        // of the reported subjects it holds, into segment d of the two send buffers
         for (uint32_t s = 0; s < W; s++) {
             ShardState &st = sh[s];
             HIPCHK(hipSetDevice(st.device));
@@ -535,7 +719,18 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
                 if (ow.device == st.device) HIPCHK(hipMemcpyAsync(to, ow.d_ids, iw * 4, hipMemcpyDeviceToDevice, st.stream));
                 else HIPCHK(hipMemcpyPeerAsync(to, st.device, ow.d_ids, ow.device, iw * 4, st.stream));
             }
-            for (uint32_t d = 0; d < W; d++) {
+            st.timed = false;
+            if (aln && timing) {   // (made on first use, on the shard's device)
+                for (hipEvent_t &e : st.ev_t) if (!e) HIPCHK(hipEventCreate(&e));
+                st.timed = true;
+                HIPCHK(hipEventRecord(st.ev_t[0], st.stream));
+            }
+            for (uint32_t d = 0; d < W && aln; d++) {
+                const int rc = tas_enqueue_gather(sx_, st, s, d, W, seq, K);
+                if (rc) return rc;
+            }
+            if (st.timed) HIPCHK(hipEventRecord(st.ev_t[1], st.stream));
+            for (uint32_t d = 0; d < W && tpos; d++) {
                 const uint32_t *ids = st.d_ids_recv + (size_t)d * iw;
                 int rc = tps_enqueue_words(st.ix, st.ws, ids, st.ids_wire, d, W, seq, K, st.d_tps_n + 2 * d, st.d_tps_words, st.d_tps_base + (size_t)d * bw, st.stream);
                 if (!rc) rc = tps_enqueue_bits(st.ix, st.ws, ids, st.ids_wire, d, W, seq, K, st.d_tps_n + 2 * d, st.d_tps_base + (size_t)d * bw,
@@ -544,21 +739,33 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
             }
             HIPCHK(hipEventRecord(st.ev_bits, st.stream));
         }
-        // ---- every owner: pulls segment d of every shard, ORs them into its result block, one D2H
+        // ---- every owner: pulls segment d of every shard, ORs the bitmaps into its result block, aligns the pairs behind
+        // them, one D2H
         for (uint32_t d = 0; d < W; d++) {
             ShardState &ow = sh[d];
             HIPCHK(hipSetDevice(ow.device));
             const size_t iw = (size_t)tps_ids_words(ow.ids_wire), sw = (size_t)ow.tp_wire + 1, bw = (size_t)ow.ids_wire.rq_cap + 1;
+            const size_t ab = aln ? (size_t)tas_seg_bytes(ow.sa_wire) : 0;
             for (uint32_t s = 0; s < W; s++) {
                 ShardState &src = sh[s];
                 if (s != d) HIPCHK(hipStreamWaitEvent(ow.stream, src.ev_bits, 0));
-                const unsigned long long *from = src.d_seg_send + (size_t)d * sw;
-                unsigned long long *to = ow.d_seg_recv + (size_t)s * sw;
-                if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, sw * 8, hipMemcpyDeviceToDevice, ow.stream));
-                else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, sw * 8, ow.stream));
+                if (tpos) {
+                    const unsigned long long *from = src.d_seg_send + (size_t)d * sw;
+                    unsigned long long *to = ow.d_seg_recv + (size_t)s * sw;
+                    if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, sw * 8, hipMemcpyDeviceToDevice, ow.stream));
+                    else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, sw * 8, ow.stream));
+                }
+                if (aln) {
+                    const uint8_t *from = src.d_sa_send + (size_t)d * ab;
+                    uint8_t *to = ow.d_sa_recv + (size_t)s * ab;
+                    if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, ab, hipMemcpyDeviceToDevice, ow.stream));
+                    else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, ab, ow.stream));
+                }
             }
-            int rc = tps_enqueue_or(ow.ix, ow.mws, ow.ws, ow.d_block, ow.d_block_cap, ow.d_ids_recv + (size_t)d * iw, ow.ids_wire, d, W, seq,
-                                    ow.d_tps_n + 2 * d, ow.d_tps_base + (size_t)d * bw, ow.d_seg_recv, sw, ow.tp_wire, ow.stream);
+            int rc = KAAMER_OK;
+            if (tpos) rc = tps_enqueue_or(ow.ix, ow.mws, ow.ws, ow.d_block, ow.d_block_cap, ow.d_ids_recv + (size_t)d * iw, ow.ids_wire, d, W, seq,
+                                          ow.d_tps_n + 2 * d, ow.d_tps_base + (size_t)d * bw, ow.d_seg_recv, sw, ow.tp_wire, ow.stream);
+            if (!rc && aln) rc = tas_enqueue_align(sx_, t, ow, &trs[d], d, W, seq, budget);
             if (!rc) rc = sharded_copy_back(ow);
             if (rc) return rc;
         }
@@ -583,13 +790,15 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     int err = KAAMER_OK;
     char why[256] = "";
     t->pos_only = true;   // (read only on the KAAMER_E_CAPACITY path of kaamer_sharded_wait_batch_top: cleared by any other failure bit)
+    t->cap_bits = 0; t->grow_sections = false;
     for (uint32_t d = 0; d < W; d++) {
         ShardState &ow = sh[d];
         HIPCHK(hipSetDevice(ow.device));
         HIPCHK(hipStreamSynchronize(ow.stream));
         const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(ow.h_block);
         const uint32_t status = hdr->status & 0x7FFFFFFFu;
-        if (hdr->status & ~(uint32_t)(ST_POS_CAP | ST_IDS_CAP)) t->pos_only = false;
+        if (hdr->status & ~(uint32_t)(ST_POS_CAP | ST_IDS_CAP | ST_SEG_CAP)) t->pos_only = false;
+        t->cap_bits |= hdr->status;
         if (status) { ow.mws->clean = false; ow.ws->clean = false; }
         int rc = status_to_error(status, ow.mws);
         if (!rc && (hdr->status & 0x80000000u)) rc = kaamer_fail(KAAMER_E_CAPACITY, "result block capacity exceeded");
@@ -608,6 +817,7 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
                              (sst & (ST_G_ARENA_FULL | ST_G_TABLE_FULL)) ? "G-tier arena " : "", (sst & (ST_QUERY_CAP | ST_AA_CAP)) ? "ORF capacity " : "");
                 else
                     snprintf(why, sizeof why, "owner %u: merge status 0x%x (%s)", d, status,
+                             (status & ST_SEG_CAP) ? "the reported hits' subjects exceed a segment" :
                              (status & ST_POS_CAP) ? "the reported hits' bitmaps exceed a segment" :
                              (status & ST_IDS_CAP) ? "the reported hits' ids exceed an ids block" :
                              (status & ST_EXCHANGE_CAP) ? "an exchange block overflowed" : "merge bounds");
@@ -634,20 +844,71 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
         uint64_t st4[4];
         if (kaamer_exchange_stats(sh[0].mws, 0, st4) == KAAMER_OK) { sx->need_queries = (uint32_t)st4[1]; sx->need_entries = st4[2]; }
     }
+    const bool aln = t->b.aln;
+    if (tpos_or_aln(t)) {   // what the ids blocks of this batch needed (the block headers hold it, whatever became of the batch)
+        sx->need_ids_rq = 0; sx->need_ids_ent = 0;
+        for (uint32_t d = 0; d < W; d++) {
+            const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
+            if (hdr->n_rep > sx->need_ids_rq) sx->need_ids_rq = hdr->n_rep;
+            if (hdr->n_ent > sx->need_ids_ent) sx->need_ids_ent = hdr->n_ent;
+        }
+    }
+    if (aln) {   // ... and the payload of the largest subject segment, as its holder counted it
+        std::vector<unsigned long long> nd((size_t)2 * W);
+        uint64_t need = 0;
+        for (uint32_t s = 0; s < W; s++) {
+            HIPCHK(hipSetDevice(sh[s].device));
+            HIPCHK(hipMemcpy(nd.data(), sh[s].d_sa_need, nd.size() * 8, hipMemcpyDeviceToHost));
+            for (uint32_t d = 0; d < W; d++) if (nd[2 * d] > need) need = nd[2 * d];
+        }
+        sx->need_sa_bytes = need;
+        sx->sa_seen = true;
+        sx->sa_seg_bytes = tas_seg_bytes(sh[0].sa_wire);
+        sx->sa_need_seg = 16 + 8ull * ((uint64_t)sx->need_ids_rq + 1) + 4ull * sx->need_ids_ent + need;
+        sx->sa_attempts = (uint64_t)t->attempt + 1;
+        sx->sa_ids_bytes = 4ull * tps_ids_words(sh[0].ids_wire);
+        for (int k = 0; k < 3; k++) { sx->sa_us[k] = 0; sx->sa_stage[k] = 0; }
+        for (uint32_t d = 0; d < W; d++) {
+            for (int k = 0; k < 3; k++) if (sh[d].sa_stage[k] > sx->sa_stage[k]) sx->sa_stage[k] = sh[d].sa_stage[k];
+            if (!sh[d].timed) continue;
+            const int from[3] = { 0, 2, 3 }, to[3] = { 1, 3, 4 };
+            for (int k = 0; k < 3; k++) {
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, sh[d].ev_t[from[k]], sh[d].ev_t[to[k]]) != hipSuccess) { (void)hipGetLastError(); continue; }
+                const uint64_t us = (uint64_t)(ms * 1000.0f);
+                if (us > sx->sa_us[k]) sx->sa_us[k] = us;
+            }
+        }
+    }
     if (err) return kaamer_fail(err, "sharded search: %s", why);
+    std::vector<const RepAlnExt *> ax(W, nullptr);
+    if (aln) {   // an owner whose alignment sections were too small: the batch once more, with what they needed
+        uint64_t need = 0;
+        bool small = false;
+        for (uint32_t d = 0; d < W; d++) {
+            const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
+            ax[d] = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+            sh[d].aln_guess = ax[d]->need_bytes + ax[d]->need_bytes / 4 + 4096;
+            if (ax[d]->need_bytes > need) need = ax[d]->need_bytes;
+            if (ax[d]->need_bytes > ax[d]->cap_bytes || !ax[d]->off_items) small = true;
+        }
+        if (small) {
+            t->grow_sections = true;
+            t->b.aln_cap = need + need / 4 + 65536;
+            return kaamer_fail(KAAMER_E_CAPACITY, "sharded search: the alignment sections of a result block (%llu bytes needed)", (unsigned long long)need);
+        }
+    }
     // ---- interleave the owners' reported queries back into batch order
     const bool tpos = t->b.tpos;
     uint64_t n_rep = 0, n_ent = 0, n_aa = 0, nq = 0, n_words = 0;
     std::vector<batch_top_owner> view(W);
     std::vector<const RepPosExt *> px(W, nullptr);
-    if (tpos) {   // what the ids blocks and segments of this batch needed: sizes the next call's
-        sx->need_ids_rq = 0; sx->need_ids_ent = 0; sx->need_tp_words = 0;
+    if (tpos) {   // what the bitmap segments of this batch needed: sizes the next call's
+        sx->need_tp_words = 0;
         for (uint32_t d = 0; d < W; d++) {
             const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
             px[d] = reinterpret_cast<const RepPosExt *>(hdr->reserved);
             if (!px[d]->off_pos_bits) return kaamer_fail(KAAMER_E_HIP, "sharded search: owner %u returned a block without its bitmap sections", d);
-            if (hdr->n_rep > sx->need_ids_rq) sx->need_ids_rq = hdr->n_rep;
-            if (hdr->n_ent > sx->need_ids_ent) sx->need_ids_ent = hdr->n_ent;
             if (px[d]->n_pos_words > sx->need_tp_words) sx->need_tp_words = px[d]->n_pos_words;
             n_words += px[d]->n_pos_words;
         }
@@ -695,6 +956,17 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     uint8_t *aa = blk + o_aa;
     int32_t *plen = (int32_t *)(blk + o_plen);
     uint64_t *poff = (uint64_t *)(blk + o_poff), *pbits = (uint64_t *)(blk + o_pbits);
+    // the owners' pair records in batch order; their operations one owner behind the other, the records' offsets re-based
+    std::vector<kaamer_align_pair> items(aln ? (size_t)n_ent : 0);
+    std::vector<uint64_t> ops_base(W + 1, 0);
+    std::vector<uint8_t> ops;
+    if (aln) {
+        for (uint32_t d = 0; d < W; d++) ops_base[d + 1] = ops_base[d] + ax[d]->ops_bytes;
+        ops.resize((size_t)ops_base[W] + 1);
+        for (uint32_t d = 0; d < W; d++)
+            if (ax[d]->ops_bytes) memcpy(ops.data() + ops_base[d], sh[d].h_block + ax[d]->off_ops, (size_t)ax[d]->ops_bytes);
+    }
+    bool aln_bad = false;
     std::vector<uint32_t> cur(W, 0);
     uint64_t r = 0, e = 0, a = 0, w = 0;
     for (;;) {  // W-way merge by global query index (each owner's list ascends)
@@ -716,6 +988,17 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
         memcpy(pid + e, v.top_pid + b0, (b1 - b0) * 4);
         memcpy(km + e, v.top_kmatch + b0, (b1 - b0) * 4);
         memcpy(fp + e, v.top_first_pos + b0, (b1 - b0) * 4);
+        if (aln) {
+            const kaamer_align_pair *src = reinterpret_cast<const kaamer_align_pair *>(view[best].block + ax[best]->off_items);
+            for (uint64_t j = b0; j < b1; j++) {
+                kaamer_align_pair it = src[j];
+                if (it.status == 0 && it.n_ops > 0 && t->aln.text) {
+                    if (it.off + (uint64_t)it.n_ops > ax[best]->ops_bytes) aln_bad = true;
+                    it.off += ops_base[best];
+                }
+                items[(size_t)(e + (j - b0))] = it;
+            }
+        }
         if (tpos) {   // the owner's bitmaps of the query are contiguous: re-based as a whole
             const uint8_t *ob = view[best].block;
             const uint64_t *v_off = reinterpret_cast<const uint64_t *>(ob + px[best]->off_pos_off);
@@ -747,6 +1030,16 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     bo->pub.top_pid = pid; bo->pub.top_kmatch = km; bo->pub.top_first_pos = fp;
     bo->pub.orf_aa = nucl ? aa : nullptr;
     bo->pub.counters = c;
+    if (t->want_aln) {   // floats, rows and the sort by BitScore on the combined result: the one-device call's finish
+        TaFinish f;
+        f.table = sx_->aln_host; f.matrix = sx_->aln_matrix; f.number_of_aa = sx_->aln_number_of_aa;
+        f.on = t->aln.on; f.text = t->aln.text; f.nucl = nucl;
+        f.lambda = t->aln.lambda; f.kk = t->aln.kk; f.gap_open = t->aln.gap_open; f.gap_extend = t->aln.gap_extend;
+        f.h_in = sx->h_in;
+        int rc = aln_bad ? kaamer_fail(KAAMER_E_FORMAT, "sharded search: inconsistent alignment sections") : KAAMER_OK;
+        if (!rc) rc = ta_finish_rows(f, bo, items.data(), ops.data(), ops_base[W], tpos ? poff : nullptr);
+        if (rc) { kaamer_batch_top_free(&bo->pub); return rc; }
+    }
     *out = &bo->pub;
     return KAAMER_OK;
 }
@@ -755,8 +1048,27 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
 // workspaces, buffers and streams (callers beyond the sets wait for one), copies the caller's buffers into the set's
 // pinned staging and enqueues the whole batch on every device; wait collects it.  A ticket is waited for exactly once.
 // top = NULL: a full call (kaamer_sharded_submit_batch_flat), `t` is then the caller's (a kaamer_sharded_full_ticket's)
+// what the subject segments and the blocks' alignment sections may take on the first attempt on a set (a batch beyond
+// either is repeated with what it needed; later calls start from the previous call's need plus a quarter).  Segments: the
+// pairs a query reports (MaxResults, at most 16 as for the ids blocks) x the table's mean stored length, the batch's
+// queries dealt over W owners and their subjects over W holders, doubled for skew.  Sections: ta_first_cap's rule per owner.
+static void tas_first_caps(const kaamer_sharded_index *sx, kaamer_sharded_ticket *t)
+{
+    const uint64_t W = sx->n, K = t->top.max_results, f = K < 16 ? K : 16;
+    const uint64_t mean = sx->aln_entries ? sx->aln_number_of_aa / sx->aln_entries + 1 : 1;
+    const bool nucl = is_nucl(t->seq_type);
+    const uint64_t queries = nucl ? t->seq_bytes / 300 + t->n_seqs : t->n_seqs;   // (an ORF that reports is about a read long)
+    t->b.sa_bytes = 2 * (queries / W + 1) * f * mean / W + 65536;
+    if (t->b.sa_bytes > (1ull << 30)) t->b.sa_bytes = 1ull << 30;   // (three buffers of W segments each: a batch beyond it says what it needs)
+    uint64_t guess = 0;
+    for (const ShardState &st : t->set->sh) if (st.aln_guess > guess) guess = st.aln_guess;
+    if (guess) t->b.aln_cap = guess;
+    else if (nucl) t->b.aln_cap = (1ull << 20) + t->seq_bytes / 4 / W;
+    else t->b.aln_cap = ((uint64_t)t->n_seqs / W + 1) * K * sizeof(kaamer_align_pair) + (t->aln.text ? 2 * K * t->seq_bytes / W : 0) + 4096;
+}
+
 static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket *t,
-                          bool top_pos)
+                          bool top_pos, const TopAlnRequest *aln = nullptr)
 {
     ShardSet *set = nullptr;
     {
@@ -767,6 +1079,9 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
             if (set) break;
             sx->cv.wait(lock);
         }
+        // an aligning call takes its set while the table is there: kaamer_sharded_index_attach_proteins refuses to replace
+        // it from here on (same lock)
+        if (aln && !sx->aln) return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top_aln: no protein table is attached to the handle (kaamer_sharded_index_attach_proteins)");
         set->busy = true;
     }
     memset(t, 0, sizeof *t);
@@ -777,6 +1092,16 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     t->b.full = top == nullptr;
     t->b.pos = t->b.full && in->want_positions != 0;
     t->b.tpos = !t->b.full && top_pos;   // the bitmaps of the reported hits (kaamer_sharded_submit_batch_top_pos_flat)
+    if (aln && !t->b.full) {
+        t->want_aln = true; t->aln = *aln;
+        t->b.aln = aln->on;   // (without a matrix row nothing is aligned and no exchange runs: the host marks every item)
+        uint64_t longest = 0;
+        for (uint32_t i = 0; i < in->n_seqs; i++)
+            if (in->offsets[i + 1] >= in->offsets[i] && in->offsets[i + 1] - in->offsets[i] > longest) longest = in->offsets[i + 1] - in->offsets[i];
+        if (is_nucl(in->seq_type)) longest = longest / 3 + 2;   // an ORF holds at most a frame's codons
+        t->max_query_len = longest > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)longest;
+        if (t->b.aln) tas_first_caps(sx, t);
+    }
     if (t->b.pos) {   // bitmap words per entry ~ 1 + SizeInKmer / 64 (ORFs: a third of the nucleotides)
         const bool nucl = is_nucl(in->seq_type);
         const uint64_t mean = t->seq_bytes / (in->n_seqs ? in->n_seqs : 1u) / (nucl ? 3u : 1u);
@@ -802,14 +1127,15 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     return rc;
 }
 
-static int sharded_submit_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool top_pos, kaamer_sharded_ticket **ticket)
+static int sharded_submit_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool top_pos, kaamer_sharded_ticket **ticket,
+                              const TopAlnRequest *aln = nullptr)
 {
     if (!sx || !in || !top || !ticket || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
         return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top: bad argument");
     *ticket = nullptr;
     kaamer_sharded_ticket *t = new (std::nothrow) kaamer_sharded_ticket();
     if (!t) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
-    const int rc = sharded_submit(sx, in, top, t, top_pos);
+    const int rc = sharded_submit(sx, in, top, t, top_pos, aln);
     if (rc) { delete t; return rc; }
     *ticket = t;
     return KAAMER_OK;
@@ -829,10 +1155,17 @@ int kaamer_sharded_wait_batch_top(kaamer_sharded_ticket *t, kaamer_batch_top **o
         rc = sharded_collect(t, out);
         if (rc != KAAMER_E_CAPACITY || t->attempt >= MAX_BOUND_RETRIES) break;
         t->attempt++;
-        if (!t->adaptive) {
+        if (t->cap_bits & ST_SEG_CAP) {   // a subject segment: its holder counted what it needs (also when sized from the previous call)
+            const uint64_t need = t->set->need_sa_bytes + t->set->need_sa_bytes / 4 + 4096;
+            if (need >= 0xFFFFFFFFull) { rc = kaamer_fail(KAAMER_E_CAPACITY, "sharded search: a subject segment of %llu bytes (the bound is 4 GiB)", (unsigned long long)need); break; }
+            if (need > t->b.sa_bytes) t->b.sa_bytes = need;
+        }
+        if (t->grow_sections) {
+            // nothing but an owner's alignment sections was too small: t->b.aln_cap has grown, every other bound stays
+        } else if (!t->adaptive) {
             // the bounds themselves were too small: enlarge them all (hit pool included: the unsharded call does the same),
-            // or the bitmap segments alone when nothing else was exceeded
-            if (t->pos_only) bounds_grow_positions(t->b.bb);
+            // or the ids blocks and segments alone when nothing else was exceeded
+            if (t->pos_only) { if (t->cap_bits & (ST_POS_CAP | ST_IDS_CAP)) bounds_grow_positions(t->b.bb); }
             else { t->b.e_cap *= 4; bounds_grow(t->b.bb, t->seq_bytes, t->n_seqs, is_nucl(t->seq_type)); }
         }   // else: the blocks sized from the previous call were too small -- once more at the full capacity, same bounds
         rc = sharded_enqueue(t);   // (an error here ends the loop, E_CAPACITY included: kept as it was)
@@ -898,6 +1231,145 @@ int kaamer_sharded_search_batch_top_pos_flat(kaamer_sharded_index *sx, const uin
     if (out) *out = nullptr;
     kaamer_sharded_ticket *t = nullptr;
     const int rc = kaamer_sharded_submit_batch_top_pos_flat(sx, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, &t);
+    if (rc) return rc;
+    return kaamer_sharded_wait_batch_top(t, out);
+}
+
+// ---- ... and with the alignment of the reported hits (search.go:483-494) ------------------------------------------------
+int kaamer_sharded_index_attach_proteins(kaamer_sharded_index *sx, const kaamer_proteins *p)
+{
+    if (!sx || !p) return kaamer_fail(KAAMER_E_ARG, "sharded_index_attach_proteins: bad argument");
+    const uint32_t W = sx->n;
+    // the entries: one per distinct id, resolved as kaamer_fetch_hits resolves it (a later record with the same id wins)
+    const uint32_t n_rec = kaamer_proteins_count(p);
+    const uint32_t *ids = kaamer_proteins_ids(p);
+    std::vector<uint32_t> uniq(ids, ids + n_rec);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const uint32_t n = (uint32_t)uniq.size();
+    const uint64_t map_n = n ? (uint64_t)uniq.back() / W + 1 : 0;   // of a device's local map, indexed by id / W
+    if (map_n > (1ull << 31)) return kaamer_fail(KAAMER_E_ARG, "sharded_index_attach_proteins: protein ids up to %llu: the id maps are dense", (unsigned long long)uniq.back());
+    std::vector<kaamer_protein_entry> ent(n);
+    int rc = kaamer_fetch_hits(p, uniq.data(), n, ent.data());
+    if (rc) return rc;
+    uint64_t st[3] = {0, 0, 0};
+    kaamer_proteins_stats(p, st);
+    std::unique_lock<std::mutex> lock(sx->mu);   // held to the end: no call starts on a half-made table
+    for (int k = 0; k < KAAMER_SHARDED_SETS; k++)
+        if (sx->sets[k].busy) return kaamer_fail(KAAMER_E_BUSY, "sharded_index_attach_proteins: calls are in flight on the handle");
+    for (uint32_t s = 0; s < W; s++) { HIPCHK(hipSetDevice((*sx->dev)[s])); HIPCHK(hipDeviceSynchronize()); }
+    const uint64_t budget = sx->aln_budget;
+    sharded_aln_free(sx);   // a second attach replaces the first
+    sx->aln_budget = budget;
+    sx->aln = new (std::nothrow) std::vector<kaamer_sharded_index::AlnPart>(W);
+    if (!sx->aln) return kaamer_fail(KAAMER_E_NOMEM, "protein table");
+    kaamer_align_matrix(sx->aln_matrix);
+    uint32_t max_ns = 0;
+    uint64_t total = 0, share = 0;
+    std::vector<uint64_t> off;
+    std::vector<uint8_t> raw;
+    std::vector<uint32_t> idmap;
+    for (uint32_t s = 0; s < W && !rc; s++) {   // device s: the entries whose id mod W == s, in id order
+        kaamer_sharded_index::AlnPart &a = (*sx->aln)[s];
+        off.assign(1, 0); raw.clear();
+        idmap.assign((size_t)map_n + 1, TA_NONE);
+        for (uint32_t i = 0; i < n; i++) {
+            if (uniq[i] % W != s) continue;
+            idmap[uniq[i] / W] = (uint32_t)off.size() - 1;
+            raw.insert(raw.end(), ent[i].sequence, ent[i].sequence + ent[i].sequence_len);
+            off.push_back(raw.size());
+            if (ent[i].sequence_len > max_ns) max_ns = ent[i].sequence_len;
+        }
+        raw.resize(raw.size() + 16, 0);
+        hipError_t e = hipSetDevice((*sx->dev)[s]);
+        if (e != hipSuccess) { rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(e)); break; }
+        rc = dev_alloc(&a.d_raw, raw.size());
+        if (!rc) rc = dev_alloc(&a.d_off, off.size());
+        if (!rc) rc = dev_alloc(&a.d_idmap, idmap.size());
+        if (!rc) rc = dev_alloc(&a.d_matrix, (size_t)ALN_NL * ALN_NL);
+        if (rc) break;
+        e = hipMemcpy(a.d_raw, raw.data(), raw.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(a.d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(a.d_idmap, idmap.data(), idmap.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(a.d_matrix, sx->aln_matrix, sizeof sx->aln_matrix, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { rc = kaamer_fail(KAAMER_E_HIP, "protein table upload: %s", hipGetErrorString(e)); break; }
+        a.idmap_n = (uint32_t)map_n; a.entries = (uint32_t)off.size() - 1;
+        a.bytes = raw.size() + off.size() * 8 + idmap.size() * 4 + sizeof sx->aln_matrix;
+        total += a.bytes;
+        if (a.bytes > share) share = a.bytes;
+    }
+    if (rc) { sharded_aln_free(sx); return rc; }
+    sx->aln_host = p;
+    sx->aln_entries = n; sx->aln_max_ns = max_ns; sx->aln_number_of_aa = st[1];
+    sx->aln_bytes = total; sx->aln_share = share;
+    for (int k = 0; k < KAAMER_SHARDED_SETS; k++) {   // what earlier calls needed was measured on another table
+        sx->sets[k].sa_seen = false; sx->sets[k].need_sa_bytes = 0;
+        for (ShardState &sh : sx->sets[k].sh) sh.aln_guess = 0;
+    }
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_index_set_align_budget(kaamer_sharded_index *sx, uint64_t bytes)
+{
+    if (!sx) return kaamer_fail(KAAMER_E_ARG, "sharded_index_set_align_budget: bad argument");
+    std::lock_guard<std::mutex> lock(sx->mu);
+    sx->aln_budget = bytes;
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_align_info(kaamer_sharded_index *sx, uint64_t out[8])
+{
+    if (!sx || !out) return kaamer_fail(KAAMER_E_ARG, "sharded_align_info: bad argument");
+    std::lock_guard<std::mutex> lock(sx->mu);
+    const ShardSet &set = sx->sets[0];
+    out[0] = sx->aln_bytes; out[1] = sx->aln_share; out[2] = sx->aln_entries; out[3] = sx->aln_max_ns; out[4] = sx->aln_number_of_aa;
+    out[5] = set.sa_seg_bytes; out[6] = set.sa_need_seg; out[7] = set.sa_attempts;
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_index_set_align_timing(kaamer_sharded_index *sx, int32_t on)
+{
+    if (!sx) return kaamer_fail(KAAMER_E_ARG, "sharded_index_set_align_timing: bad argument");
+    std::lock_guard<std::mutex> lock(sx->mu);
+    sx->aln_timing = on != 0;
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_align_stage_info(kaamer_sharded_index *sx, uint64_t out[8])
+{
+    if (!sx || !out) return kaamer_fail(KAAMER_E_ARG, "sharded_align_stage_info: bad argument");
+    std::lock_guard<std::mutex> lock(sx->mu);
+    const ShardSet &set = sx->sets[0];
+    out[0] = sx->aln_timing ? 1 : 0;
+    out[1] = set.sa_us[0]; out[2] = set.sa_us[1]; out[3] = set.sa_us[2];
+    out[4] = set.sa_ids_bytes;
+    out[5] = set.sa_stage[0]; out[6] = set.sa_stage[1]; out[7] = set.sa_stage[2];
+    return KAAMER_OK;
+}
+
+int kaamer_sharded_submit_batch_top_aln_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                             double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t want_positions,
+                                             const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text, kaamer_sharded_ticket **ticket)
+{
+    if (!sx || !sub_matrix || !ticket) return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top_aln: bad argument");
+    kaamer_batch_in in;
+    kaamer_topn_opts top;
+    flat_in(&in, seqs, offsets, n_seqs, seq_type, want_positions ? 1 : 0);
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    TopAlnRequest rq;
+    rq.on = kaamer_align_options(sub_matrix, gap_open, gap_extend, &rq.lambda, &rq.kk);
+    rq.gap_open = gap_open; rq.gap_extend = gap_extend; rq.text = want_text != 0;
+    return sharded_submit_top(sx, &in, &top, want_positions != 0, ticket, &rq);
+}
+
+int kaamer_sharded_search_batch_top_aln_flat(kaamer_sharded_index *sx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,
+                                             double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t want_positions,
+                                             const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_sharded_ticket *t = nullptr;
+    const int rc = kaamer_sharded_submit_batch_top_aln_flat(sx, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, want_positions,
+                                                            sub_matrix, gap_open, gap_extend, want_text, &t);
     if (rc) return rc;
     return kaamer_sharded_wait_batch_top(t, out);
 }

@@ -1,10 +1,10 @@
 // host_top_align.hip.inc — the host side of the alignment of the reported hits (included by search.hip inside its
 // extern "C" block, after host_top.hip.inc; the kernels are in top_align.hip.inc):
 //   kaamer_index_attach_proteins      HitEntries (search.go:454-470) made resident next to the index
-//   ta_enqueue                        the stage on a stream, for both forms of the call
+//   ta_stage / ta_enqueue             the stage on a stream: sizing and launches (shared with the sharded handle), one-device form
 //   kaamer_topn_align_device          the device-resident form
 //   kaamer_*_batch_top_aln_flat       the host-buffer form: top-N + alignment, one packed block, one D2H copy
-//   ta_finish_host                    floats, the sort by BitScore (search.go:492) and the three rows, on the host, through
+//   ta_finish_rows / ta_finish_host   floats, the sort by BitScore (search.go:492) and the three rows, on the host, through
 //                                     the code kaamer_align_pairs uses (align.hip)
 #define TA_DEFAULT_BUDGET (4ull << 30)
 #define TA_WAVES_PER_CU 5          /* a sizing rule, not a requirement: AlnWaveLds is 29 KB, five workgroups share a CU's 160 KB of
@@ -103,15 +103,15 @@ static int ta_check(const kaamer_index *ix, const kaamer_workspace *ws, const ka
     return KAAMER_OK;
 }
 
-// The stage on `s`, behind kaamer_topn_device (and, for the host-buffer form, topn_pack_block / topn_pack_positions).
-// eoff: the exclusive scan of top_cnt.  block != NULL: the two sections go behind the packed block; else pair records
-// into items[items_cap].
-static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *tr, const uint64_t *eoff, hipStream_t s,
-                      uint8_t *block, uint64_t block_cap, uint64_t aln_cap, bool want_text, int gap_open, int gap_extend,
-                      uint32_t max_query_len, kaamer_align_pair *items, uint64_t items_cap, uint64_t info[3])
+// What both forms of the stage share, on one device or on an owner of the sharded handle: first-use buffers, the sizing of
+// the direction slabs (the batch's longest query against the table's longest subject, the number of waves from the byte
+// budget) and the launches.  `ws` holds the stage's buffers; `p` arrives with the result it aligns, the table, the matrix
+// and where the output goes.  sharded != NULL: the pairs come from tas_pairs_kernel (top_align_sharded.hip.inc) instead
+// of ta_pairs_kernel.
+// marks: NULL, or three timing events recorded before the layout, behind the pairs kernel and behind the last kernel.
+static int ta_stage(kaamer_workspace *ws, TaParams p, uint64_t budget, uint32_t table_max_ns, uint32_t max_query_len, const TasParams *sharded,
+                    hipStream_t s, uint64_t info[3], const hipEvent_t *marks = nullptr)
 {
-    uint64_t budget;
-    { std::lock_guard<std::mutex> lock(ix->pool_mu); budget = ix->aln_budget ? ix->aln_budget : TA_DEFAULT_BUDGET; }
     {   // first use; each buffer on its own, so that a failed allocation is tried again by the next call
         int rc = KAAMER_OK;
         if (!ws->d_ta_lay) rc = dev_alloc(&ws->d_ta_lay, 1);
@@ -121,7 +121,7 @@ static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_
     }
     // slabs: the batch's longest query against the table's longest subject, capped at the wave kernel's LDS row
     const uint64_t mq = max_query_len ? max_query_len : 1, strips = (mq + 63) / 64;
-    const uint64_t sub = ix->aln_max_ns < ALN_WAVE_NS ? (ix->aln_max_ns ? ix->aln_max_ns : 1) : ALN_WAVE_NS;
+    const uint64_t sub = table_max_ns < ALN_WAVE_NS ? (table_max_ns ? table_max_ns : 1) : ALN_WAVE_NS;
     const uint64_t slab = strips * (sub + 63) * 64, opsb = (mq + sub + 63) & ~63ull;
     uint64_t n_waves = budget / (slab + opsb);
     const uint64_t resident = (uint64_t)ws->n_cu * TA_WAVES_PER_CU;
@@ -129,8 +129,8 @@ static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_
     int rc = ta_grow(&ws->d_ta_dirs, &ws->ta_dirs_cap, n_waves * slab, s);
     if (!rc) rc = ta_grow(&ws->d_ta_ops, &ws->ta_ops_cap, n_waves * opsb, s);
     uint64_t n_long = 0, lslab = 0, lops = 0, lbnd = 0;
-    if (!rc && ix->aln_max_ns > ALN_WAVE_NS) {   // the table holds subjects beyond the LDS row: slabs of its longest one
-        const uint64_t ns = ix->aln_max_ns;
+    if (!rc && table_max_ns > ALN_WAVE_NS) {   // the table holds subjects beyond the LDS row: slabs of its longest one
+        const uint64_t ns = table_max_ns;
         lslab = strips * (ns + 63) * 64; lops = (mq + ns + 63) & ~63ull; lbnd = 3 * (ns + 1);
         n_long = budget / (lslab + lops + 4 * lbnd);
         n_long = n_long < 1 ? 1 : (n_long > TA_LONG_WAVES_MAX ? TA_LONG_WAVES_MAX : n_long);
@@ -139,24 +139,18 @@ static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_
         if (!rc) rc = ta_grow(&ws->d_ta_lbnd, &ws->ta_lbnd_cap, n_long * lbnd, s);
     }
     if (rc) return rc;
-    TaParams p;
-    memset(&p, 0, sizeof p);
-    p.d_nq = ws->d_nq; p.q = ws->d_q;
-    p.top_cnt = tr->d_top_cnt; p.top_pid = tr->d_top_pid; p.trim = tr->d_trim; p.K = tr->max_results;
-    p.eoff = eoff;
-    p.qraw = ws->nucleotide ? ws->d_orf_aa : ws->last_seqs;
     p.qcodes = ws->d_ta_qcodes;
-    p.tab.raw = ix->d_aln_raw; p.tab.codes = ix->d_aln_codes; p.tab.off = ix->d_aln_off; p.tab.bad = ix->d_aln_bad;
-    p.tab.idmap = ix->d_aln_idmap; p.tab.idmap_n = ix->aln_idmap_n;
-    p.matrix = ix->d_aln_matrix;
-    p.dp_open = kaamer_align_dp_open(); p.gap_open = gap_open; p.gap_extend = gap_extend;
+    p.dp_open = kaamer_align_dp_open();
     p.lay = ws->d_ta_lay; p.ctr = ws->d_ta_ctr;
-    p.block = block; p.block_cap = block_cap; p.aln_cap = aln_cap; p.want_text = want_text ? 1 : 0;
-    p.items = items; p.items_cap = items_cap;
-    p.status = ws->d_status_out;
     p.dirs = ws->d_ta_dirs; p.opsbuf = ws->d_ta_ops; p.slab_bytes = slab; p.ops_bytes = opsb;
+    if (marks) HIPCHK(hipEventRecord(marks[0], s));
     hipLaunchKernelGGL(ta_layout_kernel, dim3(1), dim3(1), 0, s, p);
-    hipLaunchKernelGGL(ta_pairs_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, p);
+    if (sharded) {
+        TasParams sp = *sharded;
+        sp.qcodes = ws->d_ta_qcodes; sp.tlay = ws->d_ta_lay;
+        hipLaunchKernelGGL(tas_pairs_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, sp);
+    } else hipLaunchKernelGGL(ta_pairs_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, p);
+    if (marks) HIPCHK(hipEventRecord(marks[1], s));
     hipLaunchKernelGGL(ta_wave_kernel<false>, dim3((unsigned)n_waves), dim3(64), 0, s, p);
     if (n_long) {
         TaParams pl = p;
@@ -164,10 +158,38 @@ static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_
         pl.bnd = ws->d_ta_lbnd; pl.bnd_ints = lbnd;
         hipLaunchKernelGGL(ta_wave_kernel<true>, dim3((unsigned)n_long), dim3(64), 0, s, pl);
     }
-    if (block) hipLaunchKernelGGL(ta_finish_kernel, dim3(1), dim3(1), 0, s, p);
+    if (p.block) hipLaunchKernelGGL(ta_finish_kernel, dim3(1), dim3(1), 0, s, p);
+    if (marks) HIPCHK(hipEventRecord(marks[2], s));
     HIPCHK(hipGetLastError());
     info[0] = n_waves; info[1] = slab; info[2] = n_long;
-    { std::lock_guard<std::mutex> lock(ix->pool_mu); ix->aln_last[0] = n_waves; ix->aln_last[1] = slab; ix->aln_last[2] = n_long; }
+    return KAAMER_OK;
+}
+
+// The stage on `s`, behind kaamer_topn_device (and, for the host-buffer form, topn_pack_block / topn_pack_positions).
+// eoff: the exclusive scan of top_cnt.  block != NULL: the two sections go behind the packed block; else pair records
+// into items[items_cap].
+static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_result *tr, const uint64_t *eoff, hipStream_t s,
+                      uint8_t *block, uint64_t block_cap, uint64_t aln_cap, bool want_text, int gap_open, int gap_extend,
+                      uint32_t max_query_len, kaamer_align_pair *items, uint64_t items_cap, uint64_t info[3])
+{
+    uint64_t budget;
+    { std::lock_guard<std::mutex> lock(ix->pool_mu); budget = ix->aln_budget ? ix->aln_budget : TA_DEFAULT_BUDGET; }
+    TaParams p;
+    memset(&p, 0, sizeof p);
+    p.d_nq = ws->d_nq; p.q = ws->d_q;
+    p.top_cnt = tr->d_top_cnt; p.top_pid = tr->d_top_pid; p.trim = tr->d_trim; p.K = tr->max_results;
+    p.eoff = eoff;
+    p.qraw = ws->nucleotide ? ws->d_orf_aa : ws->last_seqs;
+    p.tab.raw = ix->d_aln_raw; p.tab.codes = ix->d_aln_codes; p.tab.off = ix->d_aln_off; p.tab.bad = ix->d_aln_bad;
+    p.tab.idmap = ix->d_aln_idmap; p.tab.idmap_n = ix->aln_idmap_n;
+    p.matrix = ix->d_aln_matrix;
+    p.gap_open = gap_open; p.gap_extend = gap_extend;
+    p.block = block; p.block_cap = block_cap; p.aln_cap = aln_cap; p.want_text = want_text ? 1 : 0;
+    p.items = items; p.items_cap = items_cap;
+    p.status = ws->d_status_out;
+    const int rc = ta_stage(ws, p, budget, ix->aln_max_ns, max_query_len, nullptr, s, info);
+    if (rc) return rc;
+    { std::lock_guard<std::mutex> lock(ix->pool_mu); ix->aln_last[0] = info[0]; ix->aln_last[1] = info[1]; ix->aln_last[2] = info[2]; }
     return KAAMER_OK;
 }
 
@@ -237,40 +259,41 @@ static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h)
     return 1;
 }
 
-// floats, sort and rows of a finished result (bo's block is complete; the slot is still the ticket's)
-static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_owner *bo)
+// what the host finish needs beside the result: the request, the borrowed table, and where protein queries' residues are
+struct TaFinish {
+    const kaamer_proteins *table;
+    const int *matrix;
+    uint64_t number_of_aa;
+    bool on, text, nucl;
+    double lambda, kk;
+    int32_t gap_open, gap_extend;
+    const uint8_t *h_in;   // the staging copy of the batch input (protein queries)
+};
+
+// floats, sort and rows of a finished result, for both forms: bo->pub is complete; items / ops are the pair records and
+// operations parallel to its CSR entries; pos_off: the bitmaps' offsets to permute with the hits (or NULL)
+static int ta_finish_rows(const TaFinish &f, batch_top_owner *bo, const kaamer_align_pair *items, const uint8_t *ops, uint64_t ops_bytes, uint64_t *pos_off)
 {
-    kaamer_index *ix = t->ix;
     const kaamer_batch_top &r = bo->pub;
     const uint64_t n_ent = r.top_off[r.n_reported];
     kaamer_alignment zero;
     memset(&zero, 0, sizeof zero);
     bo->aln.assign((size_t)n_ent, zero);
     bo->has_aln = true;
-    bo->has_text = t->aln_text;
-    if (!t->aln_on) {   // "No matrix found": every hit keeps the empty AlignmentResult, in sortMapByValue order
+    bo->has_text = f.text;
+    if (!f.on) {   // "No matrix found": every hit keeps the empty AlignmentResult, in sortMapByValue order
         for (kaamer_alignment &a : bo->aln) a.status = 1;
         return KAAMER_OK;
     }
-    const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(bo->block);
-    const RepAlnExt *x = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
-    const kaamer_align_pair *items = reinterpret_cast<const kaamer_align_pair *>(bo->block + x->off_items);
-    const uint8_t *ops = bo->block + x->off_ops;
-    const bool nucl = is_nucl(t->seq_type);
     uint32_t *pid = const_cast<uint32_t *>(r.top_pid), *km = const_cast<uint32_t *>(r.top_kmatch), *fp = const_cast<uint32_t *>(r.top_first_pos);
-    uint64_t *pos_off = nullptr;
-    if (bo->has_pos) {
-        const RepPosExt *px = reinterpret_cast<const RepPosExt *>(hdr->reserved);
-        if (px->off_pos_bits) pos_off = reinterpret_cast<uint64_t *>(bo->block + px->off_pos_off);
-    }
     std::vector<uint32_t> order;
     std::vector<kaamer_alignment> tmp_a;
     std::vector<uint32_t> tmp_u;
     std::vector<uint64_t> tmp_o;
     for (uint32_t i = 0; i < r.n_reported; i++) {
         const uint64_t a = r.top_off[i], b = r.top_off[i + 1];
-        // Query.Sequence: the reported ORF's residues in the block, or the record in the slot's copy of the batch input
-        const uint8_t *qraw = nucl ? r.orf_aa + r.q[i].aa_off : h.h_in + r.q[i].aa_off;
+        // Query.Sequence: the reported ORF's residues in the block, or the record in the staging copy of the batch input
+        const uint8_t *qraw = f.nucl ? r.orf_aa + r.q[i].aa_off : f.h_in + r.q[i].aa_off;
         for (uint64_t e = a; e < b; e++) {
             const kaamer_align_pair &it = items[e];
             kaamer_alignment &al = bo->aln[(size_t)e];
@@ -278,16 +301,16 @@ static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_ow
             kaamer_align_ints ti;
             ti.n_ops = it.n_ops; ti.start_i = it.start_i; ti.start_j = it.start_j; ti.end_i = it.end_i; ti.end_j = it.end_j;
             ti.identical = it.identical; ti.similar = it.similar; ti.mismatches = it.mismatches; ti.gap_openings = it.gap_openings; ti.raw = it.raw;
-            kaamer_align_finish(&al, &ti, it.query_len, ix->aln_number_of_aa, t->lambda, t->kk);
-            if (t->aln_text) {
+            kaamer_align_finish(&al, &ti, it.query_len, f.number_of_aa, f.lambda, f.kk);
+            if (f.text) {
                 al.aln_off = bo->aln_text.size();
                 if (it.n_ops > 0) {
                     kaamer_protein_entry pe;
-                    const int rc = kaamer_fetch_hits(ix->aln_host, &pid[e], 1, &pe);
+                    const int rc = kaamer_fetch_hits(f.table, &pid[e], 1, &pe);
                     if (rc) return rc;
-                    if (!pe.found || it.off + (uint64_t)it.n_ops > x->ops_bytes) return kaamer_fail(KAAMER_E_FORMAT, "search_batch_top_aln: inconsistent result block");
+                    if (!pe.found || it.off + (uint64_t)it.n_ops > ops_bytes) return kaamer_fail(KAAMER_E_FORMAT, "search_batch_top_aln: inconsistent result block");
                     bo->aln_text.resize(bo->aln_text.size() + 3 * (size_t)it.n_ops);
-                    kaamer_align_rows(ops + it.off, it.n_ops, qraw, pe.sequence, it.start_i, it.start_j, ix->aln_matrix, t->gap_open, t->gap_extend,
+                    kaamer_align_rows(ops + it.off, it.n_ops, qraw, pe.sequence, it.start_i, it.start_j, f.matrix, f.gap_open, f.gap_extend,
                                       bo->aln_text.data() + al.aln_off, nullptr);
                 }
             }
@@ -312,6 +335,25 @@ static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_ow
         }
     }
     return KAAMER_OK;
+}
+
+// the finish of a one-device result (bo's block is complete; the slot is still the ticket's)
+static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_owner *bo)
+{
+    kaamer_index *ix = t->ix;
+    TaFinish f;
+    f.table = ix->aln_host; f.matrix = ix->aln_matrix; f.number_of_aa = ix->aln_number_of_aa;
+    f.on = t->aln_on; f.text = t->aln_text; f.nucl = is_nucl(t->seq_type);
+    f.lambda = t->lambda; f.kk = t->kk; f.gap_open = t->gap_open; f.gap_extend = t->gap_extend;
+    f.h_in = h.h_in;
+    const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(bo->block);
+    const RepAlnExt *x = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+    uint64_t *pos_off = nullptr;
+    if (bo->has_pos) {
+        const RepPosExt *px = reinterpret_cast<const RepPosExt *>(hdr->reserved);
+        if (px->off_pos_bits) pos_off = reinterpret_cast<uint64_t *>(bo->block + px->off_pos_off);
+    }
+    return ta_finish_rows(f, bo, reinterpret_cast<const kaamer_align_pair *>(bo->block + x->off_items), bo->block + x->off_ops, x->ops_bytes, pos_off);
 }
 
 int kaamer_submit_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs, int32_t seq_type,

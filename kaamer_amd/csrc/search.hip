@@ -163,7 +163,8 @@ struct kaamer_index {
 enum { ST_POOL_FULL = 1u, ST_LIST_FULL = 2u, ST_QUERY_CAP = 4u, ST_AA_CAP = 8u, ST_G_ARENA_FULL = 16u, ST_G_TABLE_FULL = 32u,
        ST_POS_UNSUPPORTED = 64u, ST_POS_CAP = 128u, ST_CHAIN_TIMEOUT = 256u, ST_EXCHANGE_CAP = 512u, ST_PEER_FAILED = 1024u,
        ST_IDS_CAP = 2048u /* an ids block of the sharded handle (top_positions_sharded.hip.inc) */,
-       ST_ALN_CAP = 4096u /* pair records of kaamer_topn_align_device (top_align.hip.inc) */ };
+       ST_ALN_CAP = 4096u /* pair records of kaamer_topn_align_device (top_align.hip.inc) */,
+       ST_SEG_CAP = 8192u /* a subject segment of the sharded handle (top_align_sharded.hip.inc) */ };
 enum { CTR_IN = 0, CTR_QUERIES, CTR_LOOKUP, CTR_PROBE, CTR_FOUND, CTR_POST, CTR_HITS, CTR_OVERFLOW, CTR_LISTS, CTR_LIST_IDS, CTR_N };
 static_assert(sizeof(kaamer_counters) == CTR_N * 8, "counter layout");
 #define CTR_REPLICAS 64
@@ -1502,6 +1503,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply_kernel(const uint32_t *
 
 #include "exchange.hip.inc"
 #include "top_positions_sharded.hip.inc"
+#include "top_align_sharded.hip.inc"
 
 // optional compaction: sharded hit arrays -> CSR in query order (one wave per query)
 __global__ __launch_bounds__(256) void gather_hits_kernel(const uint32_t *d_nq, const uint64_t *csr_off, const uint64_t *hit_off,
@@ -1669,7 +1671,10 @@ template <class T> static int dev_alloc(T **p, size_t n)
 {
     *p = nullptr;
     hipError_t e = hipMalloc((void **)p, (n ? n : 1) * sizeof(T));
-    if (e != hipSuccess) return kaamer_fail(KAAMER_E_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // a refused allocation is reported here, not by the next launch check on this thread
+        return kaamer_fail(KAAMER_E_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
+    }
     return KAAMER_OK;
 }
 
