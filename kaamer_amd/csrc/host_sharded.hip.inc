@@ -517,7 +517,7 @@ struct kaamer_sharded_ticket {
     // the alignment of the reported hits (kaamer_sharded_submit_batch_top_aln_flat)
     bool want_aln;            // the result carries alignments; b.aln: the options name BLOSUM62 with a row, the exchange runs
     TopAlnRequest aln;
-    uint32_t max_query_len;   // residues of the batch's longest query (a bound for ORFs): sizes the direction slabs
+    uint32_t max_query_len;   // batch_max_query_len
     uint32_t cap_bits;        // the owners' status words of the attempt, OR-ed
     bool grow_sections;       // the attempt was fine but for an owner's alignment sections: they alone grow
 };
@@ -566,25 +566,61 @@ static void sharded_sync_all(ShardSet *set)
         if (st.stream) { (void)hipSetDevice(st.device); (void)hipStreamSynchronize(st.stream); }
 }
 
+namespace {
+struct ShardSyncGuard {   // every early return of its scope: nothing of the attempt is left running on any device
+    ShardSet *set; bool armed;
+    ~ShardSyncGuard() { if (armed) sharded_sync_all(set); }
+};
+}
+
+// a block of `bytes` from another shard's device (or this one) onto `s`, a stream of dst_device
+static hipError_t peer_pull_async(void *dst, int dst_device, const void *src, int src_device, size_t bytes, hipStream_t s)
+{
+    return src_device == dst_device ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipMemcpyPeerAsync(dst, dst_device, src, src_device, bytes, s);
+}
+
+// the shards' work counters, summed: lookups, probes, postings are those of the shards' searches (every key is looked up by
+// one shard); inputs and queries one shard's; n_hits is the caller's (those of the merged results)
+static int sharded_sum_counters(std::vector<ShardState> &sh, kaamer_counters *c)
+{
+    memset(c, 0, sizeof *c);
+    for (size_t d = 0; d < sh.size(); d++) {
+        kaamer_counters sc;
+        HIPCHK(hipSetDevice(sh[d].device));
+        HIPCHK(hipMemcpy(&sc, sh[d].ws->d_counters, sizeof sc, hipMemcpyDeviceToHost));
+        c->n_lookup += sc.n_lookup; c->n_probe += sc.n_probe; c->n_found += sc.n_found; c->n_post += sc.n_post;
+        c->n_lists += sc.n_lists; c->n_list_ids += sc.n_list_ids; c->n_overflow += sc.n_overflow;
+        if (d == 0) { c->n_in = sc.n_in; c->n_queries = sc.n_queries; }
+    }
+    return KAAMER_OK;
+}
+
+// Which bound: the first shard whose own search status word says what ran out there (*sst; sh.size(): none does).  Every
+// shard's stream is waited for; a shard that failed may have left per-batch state behind.
+static uint32_t sharded_failed_shard(std::vector<ShardState> &sh, uint32_t *sst)
+{
+    uint32_t bad = (uint32_t)sh.size();
+    for (uint32_t s = 0; s < sh.size(); s++) {
+        uint32_t st = 0;
+        (void)hipSetDevice(sh[s].device);
+        (void)hipStreamSynchronize(sh[s].stream);
+        if (hipMemcpy(&st, sh[s].ws->d_status_out, 4, hipMemcpyDeviceToHost) != hipSuccess || !st) continue;
+        sh[s].ws->clean = false;
+        if (bad == sh.size()) { bad = s; *sst = st; }
+    }
+    return bad;
+}
+
 static void sharded_release(kaamer_sharded_index *sx, ShardSet *set)
 {
     { std::lock_guard<std::mutex> lock(sx->mu); set->busy = false; }
     sx->cv.notify_one();
 }
 
-// the speculative copy of an owner's result block: as much as the previous call's block took (plus a quarter)
+// the speculative copy of an owner's result block
 static int sharded_copy_back(ShardState &ow)
 {
-    size_t want = ow.guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : ow.guess;
-    if (want > ow.d_block_cap) want = ow.d_block_cap;
-    if (ow.h_block_cap < want) {
-        if (ow.h_block) pinned_put(ow.h_block, ow.h_block_cap);
-        ow.h_block = (uint8_t *)pinned_get(want, &ow.h_block_cap);
-        if (!ow.h_block) { ow.h_block_cap = 0; return kaamer_fail(KAAMER_E_NOMEM, "pinned result block"); }
-    }
-    HIPCHK(hipMemcpyAsync(ow.h_block, ow.d_block, want, hipMemcpyDeviceToHost, ow.stream));
-    ow.copied = want;
-    return KAAMER_OK;
+    return rep_block_copy_guess(ow.d_block, ow.d_block_cap, ow.guess, &ow.h_block, &ow.h_block_cap, &ow.copied, ow.stream);
 }
 
 // the batch (in the set's pinned staging) onto every shard's stream: search, pack, peer copies, merge, post-steps, result
@@ -598,10 +634,7 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
     const bool nucl = is_nucl(t->seq_type);
     std::vector<ShardState> &sh = sx->sh;
     const size_t off_at = ((size_t)seq_bytes + 7) & ~(size_t)7;
-    struct Guard {   // every early return: nothing of this attempt is left running on any device
-        ShardSet *set; bool armed;
-        ~Guard() { if (armed) sharded_sync_all(set); }
-    } guard{ sx, true };
+    ShardSyncGuard guard{ sx, true };
     for (uint32_t s = 0; s < W; s++) {
         const int rc = shard_prepare(sh[s], W, s, seq_bytes, t->n_seqs, t->seq_type, t->b, t->top.max_results);
         if (rc) {
@@ -672,8 +705,7 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
             if (s != d) HIPCHK(hipStreamWaitEvent(ow.stream, src.ev_packed, 0));
             const uint32_t *from = src.d_send + (size_t)d * bw;
             uint32_t *to = ow.d_recv + (size_t)s * bw;
-            if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, bw * 4, hipMemcpyDeviceToDevice, ow.stream));
-            else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, bw * 4, ow.stream));
+            HIPCHK(peer_pull_async(to, ow.device, from, src.device, bw * 4, ow.stream));
         }
         kaamer_device_result mr;
         if (t->b.full) {   // the merged CSR (bitmaps included) stays on the owner until sharded_collect_full copies it
@@ -716,8 +748,7 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
                 ShardState &ow = sh[d];
                 if (d != s) HIPCHK(hipStreamWaitEvent(st.stream, ow.ev_ids, 0));
                 uint32_t *to = st.d_ids_recv + (size_t)d * iw;
-                if (ow.device == st.device) HIPCHK(hipMemcpyAsync(to, ow.d_ids, iw * 4, hipMemcpyDeviceToDevice, st.stream));
-                else HIPCHK(hipMemcpyPeerAsync(to, st.device, ow.d_ids, ow.device, iw * 4, st.stream));
+                HIPCHK(peer_pull_async(to, st.device, ow.d_ids, ow.device, iw * 4, st.stream));
             }
             st.timed = false;
             if (aln && timing) {   // (made on first use, on the shard's device)
@@ -752,14 +783,12 @@ static int sharded_enqueue(kaamer_sharded_ticket *t)
                 if (tpos) {
                     const unsigned long long *from = src.d_seg_send + (size_t)d * sw;
                     unsigned long long *to = ow.d_seg_recv + (size_t)s * sw;
-                    if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, sw * 8, hipMemcpyDeviceToDevice, ow.stream));
-                    else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, sw * 8, ow.stream));
+                    HIPCHK(peer_pull_async(to, ow.device, from, src.device, sw * 8, ow.stream));
                 }
                 if (aln) {
                     const uint8_t *from = src.d_sa_send + (size_t)d * ab;
                     uint8_t *to = ow.d_sa_recv + (size_t)s * ab;
-                    if (src.device == ow.device) HIPCHK(hipMemcpyAsync(to, from, ab, hipMemcpyDeviceToDevice, ow.stream));
-                    else HIPCHK(hipMemcpyPeerAsync(to, ow.device, from, src.device, ab, ow.stream));
+                    HIPCHK(peer_pull_async(to, ow.device, from, src.device, ab, ow.stream));
                 }
             }
             int rc = KAAMER_OK;
@@ -783,10 +812,7 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     const uint32_t W = sx_->n;
     const bool nucl = is_nucl(t->seq_type);
     std::vector<ShardState> &sh = sx->sh;
-    struct Guard {
-        ShardSet *set; bool armed;
-        ~Guard() { if (armed) sharded_sync_all(set); }
-    } guard{ sx, true };
+    ShardSyncGuard guard{ sx, true };
     int err = KAAMER_OK;
     char why[256] = "";
     t->pos_only = true;   // (read only on the KAAMER_E_CAPACITY path of kaamer_sharded_wait_batch_top: cleared by any other failure bit)
@@ -806,12 +832,8 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
             if (!err) {
                 // which bound: the owner's merge status says "a peer failed" or "a block overflowed"; the shards' own
                 // search status words say what ran out there (ADVICE r3: a generic message hid a hit pool that never grew)
-                uint32_t sst = 0, bad = W;
-                for (uint32_t s = 0; s < W && bad == W; s++) {
-                    (void)hipSetDevice(sh[s].device);
-                    (void)hipStreamSynchronize(sh[s].stream);
-                    if (hipMemcpy(&sst, sh[s].ws->d_status_out, 4, hipMemcpyDeviceToHost) == hipSuccess && sst) bad = s;
-                }
+                uint32_t sst = 0;
+                const uint32_t bad = sharded_failed_shard(sh, &sst);
                 if (bad < W)
                     snprintf(why, sizeof why, "shard %u: search status 0x%x (%s%s%s)", bad, sst, (sst & ST_POOL_FULL) ? "hit pool " : "",
                              (sst & (ST_G_ARENA_FULL | ST_G_TABLE_FULL)) ? "G-tier arena " : "", (sst & (ST_QUERY_CAP | ST_AA_CAP)) ? "ORF capacity " : "");
@@ -825,19 +847,8 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
             }
             continue;
         }
-        const size_t total = (size_t)hdr->total_bytes;
-        ow.guess = total + total / 4 + 4096;
-        if (total > ow.copied) {
-            size_t cap = 0;
-            uint8_t *nb = (uint8_t *)pinned_get(total, &cap);
-            if (!nb) return kaamer_fail(KAAMER_E_NOMEM, "pinned result block");
-            memcpy(nb, ow.h_block, ow.copied);
-            hipError_t e = hipMemcpyAsync(nb + ow.copied, ow.d_block + ow.copied, total - ow.copied, hipMemcpyDeviceToHost, ow.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ow.stream);
-            pinned_put(ow.h_block, ow.h_block_cap);
-            ow.h_block = nb; ow.h_block_cap = cap; ow.copied = total;
-            if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(e));
-        }
+        rc = rep_block_fetch_rest(ow.d_block, &ow.guess, &ow.h_block, &ow.h_block_cap, &ow.copied, ow.stream);
+        if (rc) return rc;
     }
     guard.armed = false;  // every stream has been waited for
     {   // what this batch's blocks needed (every owner read the same W x W figures): sizes the next call's blocks
@@ -886,8 +897,7 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
         uint64_t need = 0;
         bool small = false;
         for (uint32_t d = 0; d < W; d++) {
-            const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
-            ax[d] = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+            ax[d] = rep_aln_ext(reinterpret_cast<const RepBlockHdr *>(sh[d].h_block));
             sh[d].aln_guess = ax[d]->need_bytes + ax[d]->need_bytes / 4 + 4096;
             if (ax[d]->need_bytes > need) need = ax[d]->need_bytes;
             if (ax[d]->need_bytes > ax[d]->cap_bytes || !ax[d]->off_items) small = true;
@@ -906,8 +916,7 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     if (tpos) {   // what the bitmap segments of this batch needed: sizes the next call's
         sx->need_tp_words = 0;
         for (uint32_t d = 0; d < W; d++) {
-            const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
-            px[d] = reinterpret_cast<const RepPosExt *>(hdr->reserved);
+            px[d] = rep_pos_ext(reinterpret_cast<const RepBlockHdr *>(sh[d].h_block));
             if (!px[d]->off_pos_bits) return kaamer_fail(KAAMER_E_HIP, "sharded search: owner %u returned a block without its bitmap sections", d);
             if (px[d]->n_pos_words > sx->need_tp_words) sx->need_tp_words = px[d]->n_pos_words;
             n_words += px[d]->n_pos_words;
@@ -926,19 +935,10 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
         const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(sh[d].h_block);
         n_aa += hdr->n_aa;
     }
-    // work counters: lookups, probes, postings are those of the shards' searches (every key is looked up by one shard);
-    // queries and hits those of the merged results
     kaamer_counters c;
-    memset(&c, 0, sizeof c);
-    for (uint32_t d = 0; d < W; d++) {
-        kaamer_counters sc;
-        HIPCHK(hipSetDevice(sh[d].device));
-        HIPCHK(hipMemcpy(&sc, sh[d].ws->d_counters, sizeof sc, hipMemcpyDeviceToHost));
-        c.n_lookup += sc.n_lookup; c.n_probe += sc.n_probe; c.n_found += sc.n_found; c.n_post += sc.n_post;
-        c.n_lists += sc.n_lists; c.n_list_ids += sc.n_list_ids; c.n_overflow += sc.n_overflow;
-        if (d == 0) { c.n_in = sc.n_in; c.n_queries = sc.n_queries; }
-        c.n_hits += view[d].pub.counters.n_hits;
-    }
+    const int crc = sharded_sum_counters(sh, &c);
+    if (crc) return crc;
+    for (uint32_t d = 0; d < W; d++) c.n_hits += view[d].pub.counters.n_hits;
     const size_t o_rq = 0, o_trim = rep_align8(o_rq + 4 * n_rep), o_q = rep_align8(o_trim + 4 * n_rep),
                  o_off = rep_align8(o_q + sizeof(kaamer_query_meta) * n_rep), o_pid = o_off + 8 * (n_rep + 1), o_km = rep_align8(o_pid + 4 * n_ent),
                  o_fp = rep_align8(o_km + 4 * n_ent), o_aa = rep_align8(o_fp + 4 * n_ent), o_plen = rep_align8(o_aa + n_aa) + 8,
@@ -1033,8 +1033,7 @@ static int sharded_collect(kaamer_sharded_ticket *t, kaamer_batch_top **out)
     if (t->want_aln) {   // floats, rows and the sort by BitScore on the combined result: the one-device call's finish
         TaFinish f;
         f.table = sx_->aln_host; f.matrix = sx_->aln_matrix; f.number_of_aa = sx_->aln_number_of_aa;
-        f.on = t->aln.on; f.text = t->aln.text; f.nucl = nucl;
-        f.lambda = t->aln.lambda; f.kk = t->aln.kk; f.gap_open = t->aln.gap_open; f.gap_extend = t->aln.gap_extend;
+        f.rq = t->aln; f.nucl = nucl;
         f.h_in = sx->h_in;
         int rc = aln_bad ? kaamer_fail(KAAMER_E_FORMAT, "sharded search: inconsistent alignment sections") : KAAMER_OK;
         if (!rc) rc = ta_finish_rows(f, bo, items.data(), ops.data(), ops_base[W], tpos ? poff : nullptr);
@@ -1095,11 +1094,7 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     if (aln && !t->b.full) {
         t->want_aln = true; t->aln = *aln;
         t->b.aln = aln->on;   // (without a matrix row nothing is aligned and no exchange runs: the host marks every item)
-        uint64_t longest = 0;
-        for (uint32_t i = 0; i < in->n_seqs; i++)
-            if (in->offsets[i + 1] >= in->offsets[i] && in->offsets[i + 1] - in->offsets[i] > longest) longest = in->offsets[i + 1] - in->offsets[i];
-        if (is_nucl(in->seq_type)) longest = longest / 3 + 2;   // an ORF holds at most a frame's codons
-        t->max_query_len = longest > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)longest;
+        t->max_query_len = batch_max_query_len(in);
         if (t->b.aln) tas_first_caps(sx, t);
     }
     if (t->b.pos) {   // bitmap words per entry ~ 1 + SizeInKmer / 64 (ORFs: a third of the nucleotides)
@@ -1240,18 +1235,13 @@ int kaamer_sharded_index_attach_proteins(kaamer_sharded_index *sx, const kaamer_
 {
     if (!sx || !p) return kaamer_fail(KAAMER_E_ARG, "sharded_index_attach_proteins: bad argument");
     const uint32_t W = sx->n;
-    // the entries: one per distinct id, resolved as kaamer_fetch_hits resolves it (a later record with the same id wins)
-    const uint32_t n_rec = kaamer_proteins_count(p);
-    const uint32_t *ids = kaamer_proteins_ids(p);
-    std::vector<uint32_t> uniq(ids, ids + n_rec);
-    std::sort(uniq.begin(), uniq.end());
-    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    std::vector<uint32_t> uniq;
+    std::vector<kaamer_protein_entry> ent;
+    int rc = proteins_distinct(p, uniq, ent);
+    if (rc) return rc;
     const uint32_t n = (uint32_t)uniq.size();
     const uint64_t map_n = n ? (uint64_t)uniq.back() / W + 1 : 0;   // of a device's local map, indexed by id / W
     if (map_n > (1ull << 31)) return kaamer_fail(KAAMER_E_ARG, "sharded_index_attach_proteins: protein ids up to %llu: the id maps are dense", (unsigned long long)uniq.back());
-    std::vector<kaamer_protein_entry> ent(n);
-    int rc = kaamer_fetch_hits(p, uniq.data(), n, ent.data());
-    if (rc) return rc;
     uint64_t st[3] = {0, 0, 0};
     kaamer_proteins_stats(p, st);
     std::unique_lock<std::mutex> lock(sx->mu);   // held to the end: no call starts on a half-made table
@@ -1356,9 +1346,7 @@ int kaamer_sharded_submit_batch_top_aln_flat(kaamer_sharded_index *sx, const uin
     kaamer_topn_opts top;
     flat_in(&in, seqs, offsets, n_seqs, seq_type, want_positions ? 1 : 0);
     flat_top(&top, min_k_ratio, min_k_match, max_results);
-    TopAlnRequest rq;
-    rq.on = kaamer_align_options(sub_matrix, gap_open, gap_extend, &rq.lambda, &rq.kk);
-    rq.gap_open = gap_open; rq.gap_extend = gap_extend; rq.text = want_text != 0;
+    const TopAlnRequest rq = top_aln_request(sub_matrix, gap_open, gap_extend, want_text);
     return sharded_submit_top(sx, &in, &top, want_positions != 0, ticket, &rq);
 }
 
@@ -1400,10 +1388,7 @@ static int sharded_collect_full(kaamer_sharded_ticket *t, kaamer_batch_out **out
     const uint32_t W = t->sx->n;
     const bool pos = t->b.pos;
     std::vector<ShardState> &sh = sx->sh;
-    struct Guard {
-        ShardSet *set; bool armed;
-        ~Guard() { if (armed) sharded_sync_all(set); }
-    } guard{ sx, true };
+    ShardSyncGuard guard{ sx, true };
     int err = KAAMER_OK;
     char why[256] = "";
     for (uint32_t d = 0; d < W; d++) {
@@ -1412,17 +1397,9 @@ static int sharded_collect_full(kaamer_sharded_ticket *t, kaamer_batch_out **out
         if (rc && !err) {
             err = rc;
             snprintf(why, sizeof why, "owner %u: %s", d, kaamer_last_error());
-            bool named = false;
-            for (uint32_t s = 0; s < W; s++) {   // which bound: a shard's own search status says what ran out there
-                uint32_t sst = 0;
-                (void)hipSetDevice(sh[s].device);
-                (void)hipStreamSynchronize(sh[s].stream);
-                if (hipMemcpy(&sst, sh[s].ws->d_status_out, 4, hipMemcpyDeviceToHost) == hipSuccess && sst) {
-                    sh[s].ws->clean = false;   // an aborted batch may leave per-batch state behind
-                    if (!named) snprintf(why, sizeof why, "shard %u: search status 0x%x", s, sst);
-                    named = true;
-                }
-            }
+            uint32_t sst = 0;
+            const uint32_t bad = sharded_failed_shard(sh, &sst);   // which bound: a shard's own search status says what ran out there
+            if (bad < W) snprintf(why, sizeof why, "shard %u: search status 0x%x", bad, sst);
         }
     }
     guard.armed = false;  // every owner's stream has been waited for (and with it every shard's packs)
@@ -1516,18 +1493,9 @@ static int sharded_collect_full(kaamer_sharded_ticket *t, kaamer_batch_out **out
         hcur += n;
     }
     bo->hit_off[nq] = hcur;
-    // work counters (the rule of the top call): lookups, probes, postings are the shards' (every key is looked up by one
-    // shard); inputs and queries one shard's; hits those of the merged result
     kaamer_counters c;
-    memset(&c, 0, sizeof c);
-    for (uint32_t d = 0; d < W; d++) {
-        kaamer_counters sc;
-        HIPCHK(hipSetDevice(sh[d].device));
-        HIPCHK(hipMemcpy(&sc, sh[d].ws->d_counters, sizeof sc, hipMemcpyDeviceToHost));
-        c.n_lookup += sc.n_lookup; c.n_probe += sc.n_probe; c.n_found += sc.n_found; c.n_post += sc.n_post;
-        c.n_lists += sc.n_lists; c.n_list_ids += sc.n_list_ids; c.n_overflow += sc.n_overflow;
-        if (d == 0) { c.n_in = sc.n_in; c.n_queries = sc.n_queries; }
-    }
+    const int crc = sharded_sum_counters(sh, &c);
+    if (crc) return crc;
     c.n_hits = n_hits;
     memset(&bo->pub, 0, sizeof bo->pub);
     bo->pub.n_queries = nq;

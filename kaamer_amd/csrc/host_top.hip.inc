@@ -19,7 +19,7 @@ struct batch_top_owner {
     uint8_t *block = nullptr;  // everything pub points to
     size_t block_cap = 0;
     bool pinned = true;        // from the pinned cache (else malloc: the interleaved result of a sharded index)
-    bool has_pos = false;      // the block carries the bitmap sections (RepPosExt, top_positions.hip.inc)
+    bool has_pos = false;      // the block carries the bitmap sections (RepPosExt, topn.hip.inc)
     // ... or, in the interleaved result of a sharded index (no RepBlockHdr), the three arrays are at these places
     const int32_t *m_pos_len = nullptr;
     const uint64_t *m_pos_off = nullptr, *m_pos_bits = nullptr;
@@ -37,6 +37,24 @@ struct TopAlnRequest {
     bool text = false;
 };
 
+static TopAlnRequest top_aln_request(const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text)
+{
+    TopAlnRequest rq;
+    rq.on = kaamer_align_options(sub_matrix, gap_open, gap_extend, &rq.lambda, &rq.kk);
+    rq.gap_open = gap_open; rq.gap_extend = gap_extend; rq.text = want_text != 0;
+    return rq;
+}
+
+// residues of the batch's longest query (a bound for ORFs): sizes the direction slabs
+static uint32_t batch_max_query_len(const kaamer_batch_in *in)
+{
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < in->n_seqs; i++)
+        if (in->offsets[i + 1] >= in->offsets[i] && in->offsets[i + 1] - in->offsets[i] > longest) longest = in->offsets[i + 1] - in->offsets[i];
+    if (is_nucl(in->seq_type)) longest = longest / 3 + 2;   // an ORF holds at most a frame's codons
+    return longest > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)longest;
+}
+
 struct kaamer_ticket {
     kaamer_index *ix;
     int slot;
@@ -49,11 +67,9 @@ struct kaamer_ticket {
     BatchBounds b;
     int attempt;
     bool want_pos;   // PositionHits of the reported hits ride in the block (the *_pos_flat calls)
-    // the alignments of the reported hits ride in the block (the *_aln_flat calls)
-    bool want_aln, aln_on, aln_text;
-    int32_t gap_open, gap_extend;
-    double lambda, kk;
-    uint32_t max_query_len;   // residues of the batch's longest query (a bound for ORFs): sizes the direction slabs
+    bool want_aln;   // the alignments of the reported hits ride in the block (the *_aln_flat calls)
+    TopAlnRequest aln;
+    uint32_t max_query_len;   // batch_max_query_len
     uint64_t aln_cap;         // bytes the block's two sections may take
 };
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
@@ -140,6 +156,43 @@ static void top_owner_fill(batch_top_owner *bo)
     bo->pub.top_first_pos = reinterpret_cast<const uint32_t *>(bo->block + h->off_fp);
     bo->pub.orf_aa = bo->block + h->off_aa;
     bo->pub.counters = h->counters;
+}
+
+// The host protocol of a packed block, on both handles: copy a guess -- as much as the previous call's block took (plus a
+// quarter), never more than the `usable` bytes of d_block -- into a pinned block, read the header once the stream is done
+// (the caller), fetch the rest only when the guess was short.
+static int rep_block_copy_guess(const uint8_t *d_block, size_t usable, size_t guess, uint8_t **h_block, size_t *h_block_cap, size_t *copied, hipStream_t s)
+{
+    size_t want = guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : guess;
+    if (want > usable) want = usable;
+    if (*h_block_cap < want) {
+        if (*h_block) pinned_put(*h_block, *h_block_cap);
+        *h_block = (uint8_t *)pinned_get(want, h_block_cap);
+        if (!*h_block) { *h_block_cap = 0; return kaamer_fail(KAAMER_E_NOMEM, "pinned result block (%zu bytes)", want); }
+    }
+    const hipError_t e = hipMemcpyAsync(*h_block, d_block, want, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(e));
+    *copied = want;
+    return KAAMER_OK;
+}
+
+// ... the header (in *h_block) is fine: what the guess missed, and the next call's guess
+static int rep_block_fetch_rest(const uint8_t *d_block, size_t *guess, uint8_t **h_block, size_t *h_block_cap, size_t *copied, hipStream_t s)
+{
+    const size_t total = (size_t)reinterpret_cast<const RepBlockHdr *>(*h_block)->total_bytes;
+    *guess = total + total / 4 + 4096;
+    if (total <= *copied) return KAAMER_OK;
+    size_t cap = 0;
+    uint8_t *nb = (uint8_t *)pinned_get(total, &cap);
+    if (!nb) return kaamer_fail(KAAMER_E_NOMEM, "pinned result block (%zu bytes)", total);
+    memcpy(nb, *h_block, *copied);
+    hipError_t e = hipMemcpyAsync(nb + *copied, d_block + *copied, total - *copied, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    pinned_put(*h_block, *h_block_cap);
+    *h_block = nb; *h_block_cap = cap;
+    if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(e));
+    *copied = total;
+    return KAAMER_OK;
 }
 
 static int status_to_error(uint32_t status, const kaamer_workspace *ws)
@@ -250,7 +303,7 @@ static int top_enqueue(kaamer_ticket *t)
     o.first_pos = 0;  // as the reference fills PositionHits: nucleotide / reads input only (search.go:416)
     o.max_queries = t->b.max_queries;
     o.concurrent_batches = (uint32_t)ix->n_top;   // the slots exist so that batches overlap
-    const bool aligns = t->want_aln && t->aln_on;   // (without a matrix row nothing is aligned: the host marks every item)
+    const bool aligns = t->want_aln && t->aln.on;   // (without a matrix row nothing is aligned: the host marks every item)
     if (aligns && !t->aln_cap) t->aln_cap = ta_first_cap(t, h);
     int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results, t->want_pos, t->b.pos_scale, aligns ? t->aln_cap : 0);
     if (rc) return rc;
@@ -271,18 +324,7 @@ static int top_enqueue(kaamer_ticket *t)
     if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
     if (!rc && aligns) rc = top_enqueue_alignments(t, h, &tr, s);
     if (rc) return rc;
-    // the speculative copy: as much as the previous call's block took (plus a quarter), never more than the block can hold
-    size_t want = h.guess < sizeof(RepBlockHdr) ? sizeof(RepBlockHdr) : h.guess;
-    if (want > h.block_use) want = h.block_use;
-    if (t->h_block_cap < want) {
-        if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
-        t->h_block = (uint8_t *)pinned_get(want, &t->h_block_cap);
-        if (!t->h_block) { t->h_block_cap = 0; return kaamer_fail(KAAMER_E_NOMEM, "pinned result block (%zu bytes)", want); }
-    }
-    e = hipMemcpyAsync(t->h_block, h.d_block, want, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(e));
-    t->copied = want;
-    return KAAMER_OK;
+    return rep_block_copy_guess(h.d_block, h.block_use, h.guess, &t->h_block, &t->h_block_cap, &t->copied, s);
 }
 
 static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool blocking, kaamer_ticket **out,
@@ -310,13 +352,8 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
     t->top = *top;
     t->want_pos = want_pos;
     if (aln) {
-        t->want_aln = true; t->aln_on = aln->on; t->aln_text = aln->text;
-        t->gap_open = aln->gap_open; t->gap_extend = aln->gap_extend; t->lambda = aln->lambda; t->kk = aln->kk;
-        uint64_t longest = 0;
-        for (uint32_t i = 0; i < in->n_seqs; i++)
-            if (in->offsets[i + 1] >= in->offsets[i] && in->offsets[i + 1] - in->offsets[i] > longest) longest = in->offsets[i + 1] - in->offsets[i];
-        if (is_nucl(in->seq_type)) longest = longest / 3 + 2;   // an ORF holds at most a frame's codons
-        t->max_query_len = longest > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)longest;
+        t->want_aln = true; t->aln = *aln;
+        t->max_query_len = batch_max_query_len(in);
     }
     int rc = KAAMER_OK;
     hipError_t he = hipSetDevice(ix->device);
@@ -384,26 +421,13 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
             continue;
         }
         if (rc) break;
-        if (t->want_aln && t->aln_on && ta_needs_repeat(t, h)) {   // the alignment sections were too small: once more, with what they needed
+        if (t->want_aln && t->aln.on && ta_needs_repeat(t, h)) {   // the alignment sections were too small: once more, with what they needed
             if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "alignment sections of the result block"); break; }
             t->attempt++;
             rc = top_enqueue(t);
             continue;
         }
-        const size_t total = (size_t)hdr->total_bytes;
-        h.guess = total + total / 4 + 4096;
-        if (total > t->copied) {  // the guess was short: the rest of the block
-            size_t cap = 0;
-            uint8_t *nb = (uint8_t *)pinned_get(total, &cap);
-            if (!nb) { rc = kaamer_fail(KAAMER_E_NOMEM, "pinned result block (%zu bytes)", total); break; }
-            memcpy(nb, t->h_block, t->copied);
-            e = hipMemcpyAsync(nb + t->copied, h.d_block + t->copied, total - t->copied, hipMemcpyDeviceToHost, h.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h.stream);
-            pinned_put(t->h_block, t->h_block_cap);
-            t->h_block = nb; t->h_block_cap = cap;
-            if (e != hipSuccess) { rc = kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(e)); break; }
-            t->copied = total;
-        }
+        rc = rep_block_fetch_rest(h.d_block, &h.guess, &t->h_block, &t->h_block_cap, &t->copied, h.stream);
         break;
     }
     batch_top_owner *bo = nullptr;
@@ -511,8 +535,7 @@ int kaamer_batch_top_positions(const kaamer_batch_top *out, const int32_t **pos_
         if (pos_bits) *pos_bits = bo->m_pos_bits;
         return KAAMER_OK;
     }
-    const RepBlockHdr *h = reinterpret_cast<const RepBlockHdr *>(bo->block);
-    const RepPosExt *x = reinterpret_cast<const RepPosExt *>(h->reserved);
+    const RepPosExt *x = rep_pos_ext(reinterpret_cast<const RepBlockHdr *>(bo->block));
     if (!x->off_pos_bits) return KAAMER_OK;
     if (pos_bits_len) *pos_bits_len = reinterpret_cast<const int32_t *>(bo->block + x->off_pos_len);
     if (pos_off) *pos_off = reinterpret_cast<const uint64_t *>(bo->block + x->off_pos_off);

@@ -11,22 +11,29 @@
                                       LDS, and slabs beyond what runs at once would only hold memory (waves take pairs by ticket) */
 #define TA_LONG_WAVES_MAX 256u       /* the long-subject kernel: as many slabs as the budget allows, up to this */
 
+// the entries of a protein table, both handles': one per distinct id (uniq, ascending), resolved as kaamer_fetch_hits
+// resolves it (a later record with the same id wins)
+static int proteins_distinct(const kaamer_proteins *p, std::vector<uint32_t> &uniq, std::vector<kaamer_protein_entry> &ent)
+{
+    const uint32_t *ids = kaamer_proteins_ids(p);
+    uniq = std::vector<uint32_t>(ids, ids + kaamer_proteins_count(p));
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    ent = std::vector<kaamer_protein_entry>(uniq.size());
+    return kaamer_fetch_hits(p, uniq.data(), (uint32_t)uniq.size(), ent.data());
+}
+
 int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p)
 {
     if (!ix || !p) return kaamer_fail(KAAMER_E_ARG, "index_attach_proteins: bad argument");
     HIPCHK(hipSetDevice(ix->device));
-    // the entries: one per distinct id, resolved as kaamer_fetch_hits resolves it (a later record with the same id wins)
-    const uint32_t n_rec = kaamer_proteins_count(p);
-    const uint32_t *ids = kaamer_proteins_ids(p);
-    std::vector<uint32_t> uniq(ids, ids + n_rec);
-    std::sort(uniq.begin(), uniq.end());
-    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    std::vector<uint32_t> uniq;
+    std::vector<kaamer_protein_entry> ent;
+    int rc = proteins_distinct(p, uniq, ent);
+    if (rc) return rc;
     const uint32_t n = (uint32_t)uniq.size();
     const uint64_t map_n = n ? (uint64_t)uniq.back() + 1 : 0;
     if (map_n > (1ull << 31)) return kaamer_fail(KAAMER_E_ARG, "index_attach_proteins: protein ids up to %llu: the id map is dense", (unsigned long long)map_n);
-    std::vector<kaamer_protein_entry> ent(n);
-    int rc = kaamer_fetch_hits(p, uniq.data(), n, ent.data());
-    if (rc) return rc;
     std::vector<uint64_t> off((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + ent[i].sequence_len;
     std::vector<uint8_t> raw((size_t)off[n] + 1, 0), codes((size_t)off[n] + 1, 0), bad((size_t)n + 1, 0);
@@ -235,7 +242,7 @@ static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_top
     int rc = ta_check(t->ix, h.ws, tr, "search_batch_top_aln");
     if (rc) return rc;
     uint64_t info[3];
-    return ta_enqueue(t->ix, h.ws, tr, h.ws->d_rep_eoff, s, h.d_block, h.block_use, t->aln_cap, t->aln_text, t->gap_open, t->gap_extend,
+    return ta_enqueue(t->ix, h.ws, tr, h.ws->d_rep_eoff, s, h.d_block, h.block_use, t->aln_cap, t->aln.text, t->aln.gap_open, t->aln.gap_extend,
                       t->max_query_len, nullptr, 0, info);
 }
 
@@ -245,14 +252,13 @@ static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h)
     if (h.aln_guess) return h.aln_guess;
     const uint64_t K = t->top.max_results;
     if (is_nucl(t->seq_type)) return (1ull << 20) + t->seq_bytes / 4;
-    return (uint64_t)t->n_seqs * K * sizeof(kaamer_align_pair) + (t->aln_text ? 2 * K * t->seq_bytes : 0) + 4096;
+    return (uint64_t)t->n_seqs * K * sizeof(kaamer_align_pair) + (t->aln.text ? 2 * K * t->seq_bytes : 0) + 4096;
 }
 
 // after the stream is done and the batch's status is fine: 1 = the sections were too small, repeat with t->aln_cap grown
 static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h)
 {
-    const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(t->h_block);
-    const RepAlnExt *x = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+    const RepAlnExt *x = rep_aln_ext(reinterpret_cast<const RepBlockHdr *>(t->h_block));
     h.aln_guess = x->need_bytes + x->need_bytes / 4 + 4096;
     if (x->need_bytes <= x->cap_bytes && x->off_items) return 0;
     t->aln_cap = x->need_bytes + x->need_bytes / 4 + 65536;
@@ -264,9 +270,8 @@ struct TaFinish {
     const kaamer_proteins *table;
     const int *matrix;
     uint64_t number_of_aa;
-    bool on, text, nucl;
-    double lambda, kk;
-    int32_t gap_open, gap_extend;
+    TopAlnRequest rq;
+    bool nucl;
     const uint8_t *h_in;   // the staging copy of the batch input (protein queries)
 };
 
@@ -280,8 +285,8 @@ static int ta_finish_rows(const TaFinish &f, batch_top_owner *bo, const kaamer_a
     memset(&zero, 0, sizeof zero);
     bo->aln.assign((size_t)n_ent, zero);
     bo->has_aln = true;
-    bo->has_text = f.text;
-    if (!f.on) {   // "No matrix found": every hit keeps the empty AlignmentResult, in sortMapByValue order
+    bo->has_text = f.rq.text;
+    if (!f.rq.on) {   // "No matrix found": every hit keeps the empty AlignmentResult, in sortMapByValue order
         for (kaamer_alignment &a : bo->aln) a.status = 1;
         return KAAMER_OK;
     }
@@ -301,8 +306,8 @@ static int ta_finish_rows(const TaFinish &f, batch_top_owner *bo, const kaamer_a
             kaamer_align_ints ti;
             ti.n_ops = it.n_ops; ti.start_i = it.start_i; ti.start_j = it.start_j; ti.end_i = it.end_i; ti.end_j = it.end_j;
             ti.identical = it.identical; ti.similar = it.similar; ti.mismatches = it.mismatches; ti.gap_openings = it.gap_openings; ti.raw = it.raw;
-            kaamer_align_finish(&al, &ti, it.query_len, f.number_of_aa, f.lambda, f.kk);
-            if (f.text) {
+            kaamer_align_finish(&al, &ti, it.query_len, f.number_of_aa, f.rq.lambda, f.rq.kk);
+            if (f.rq.text) {
                 al.aln_off = bo->aln_text.size();
                 if (it.n_ops > 0) {
                     kaamer_protein_entry pe;
@@ -310,7 +315,7 @@ static int ta_finish_rows(const TaFinish &f, batch_top_owner *bo, const kaamer_a
                     if (rc) return rc;
                     if (!pe.found || it.off + (uint64_t)it.n_ops > ops_bytes) return kaamer_fail(KAAMER_E_FORMAT, "search_batch_top_aln: inconsistent result block");
                     bo->aln_text.resize(bo->aln_text.size() + 3 * (size_t)it.n_ops);
-                    kaamer_align_rows(ops + it.off, it.n_ops, qraw, pe.sequence, it.start_i, it.start_j, f.matrix, f.gap_open, f.gap_extend,
+                    kaamer_align_rows(ops + it.off, it.n_ops, qraw, pe.sequence, it.start_i, it.start_j, f.matrix, f.rq.gap_open, f.rq.gap_extend,
                                       bo->aln_text.data() + al.aln_off, nullptr);
                 }
             }
@@ -343,16 +348,12 @@ static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_ow
     kaamer_index *ix = t->ix;
     TaFinish f;
     f.table = ix->aln_host; f.matrix = ix->aln_matrix; f.number_of_aa = ix->aln_number_of_aa;
-    f.on = t->aln_on; f.text = t->aln_text; f.nucl = is_nucl(t->seq_type);
-    f.lambda = t->lambda; f.kk = t->kk; f.gap_open = t->gap_open; f.gap_extend = t->gap_extend;
+    f.rq = t->aln; f.nucl = is_nucl(t->seq_type);
     f.h_in = h.h_in;
     const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(bo->block);
-    const RepAlnExt *x = reinterpret_cast<const RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
-    uint64_t *pos_off = nullptr;
-    if (bo->has_pos) {
-        const RepPosExt *px = reinterpret_cast<const RepPosExt *>(hdr->reserved);
-        if (px->off_pos_bits) pos_off = reinterpret_cast<uint64_t *>(bo->block + px->off_pos_off);
-    }
+    const RepAlnExt *x = rep_aln_ext(hdr);
+    const RepPosExt *px = rep_pos_ext(hdr);
+    uint64_t *pos_off = bo->has_pos && px->off_pos_bits ? reinterpret_cast<uint64_t *>(bo->block + px->off_pos_off) : nullptr;
     return ta_finish_rows(f, bo, reinterpret_cast<const kaamer_align_pair *>(bo->block + x->off_items), bo->block + x->off_ops, x->ops_bytes, pos_off);
 }
 
@@ -366,9 +367,7 @@ int kaamer_submit_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, cons
     kaamer_topn_opts top;
     flat_in(&in, seqs, offsets, n_seqs, seq_type, want_positions ? 1 : 0);
     flat_top(&top, min_k_ratio, min_k_match, max_results);
-    TopAlnRequest rq;
-    rq.on = kaamer_align_options(sub_matrix, gap_open, gap_extend, &rq.lambda, &rq.kk);
-    rq.gap_open = gap_open; rq.gap_extend = gap_extend; rq.text = want_text != 0;
+    const TopAlnRequest rq = top_aln_request(sub_matrix, gap_open, gap_extend, want_text);
     return top_submit(ix, &in, &top, true, ticket, want_positions != 0, &rq);
 }
 

@@ -32,14 +32,6 @@
 
 static_assert(sizeof(kaamer_align_pair) == 64, "pair record");
 
-// what the host-buffer form adds to RepBlockHdr, in its reserved bytes behind RepPosExt (zero in a block without alignments)
-struct RepAlnExt {
-    uint64_t off_items, off_ops;   // byte offsets of the two sections
-    uint64_t ops_bytes;            // operations stored
-    uint64_t need_bytes, cap_bytes;   // both sections: what the batch needed, what this call ran with
-};
-static_assert(sizeof(RepPosExt) + sizeof(RepAlnExt) <= sizeof(((RepBlockHdr *)nullptr)->reserved), "the header's reserved bytes hold both extensions");
-
 struct TaTable {   // the attached Protein.Sequence table on the device
     const uint8_t *raw, *codes;    // stored bytes; the aligner's letter codes
     const uint64_t *off;           // n_entries + 1
@@ -106,13 +98,60 @@ __global__ void ta_layout_kernel(TaParams p)
                 hdr->total_bytes = at + ib;
             }
         }
-        *reinterpret_cast<RepAlnExt *>(hdr->reserved + sizeof(RepPosExt)) = x;
+        *rep_aln_ext(hdr) = x;
     } else if (*p.status == 0) {
         const uint64_t n_ent = p.eoff[*p.d_nq];
         if (n_ent > p.items_cap) atomicOr(p.status, (uint32_t)ST_ALN_CAP);
         else { l.items = p.items; l.n_ent = n_ent; l.items_bytes = sizeof(kaamer_align_pair) * n_ent; l.ok = 1; }
     }
     *p.lay = l;
+}
+
+// by one wave: n letters to the aligner's codes, at the same offsets; true: a letter outside the alphabet (its code is 0)
+__device__ __forceinline__ bool ta_wave_codes(const uint8_t *raw, uint8_t *codes, uint32_t n, uint32_t lane)
+{
+    bool bad = false;
+    for (uint32_t i = lane; i < n; i += 64) {
+        int c = aln_code(raw[i]);
+        if (c < 0) { bad = true; c = 0; }
+        codes[i] = (uint8_t)c;
+    }
+    return __ballot(bad) != 0ull;
+}
+
+// by one wave: the first of a query's cnt reported hits for which miss(r) holds, cnt when there is none.  That id without
+// an entry ends the query's HitEntries (search.go:461-463)
+template <class Miss> __device__ __forceinline__ uint32_t ta_first_missing(uint32_t cnt, uint32_t lane, Miss miss)
+{
+    uint32_t first_missing = cnt;
+    for (uint32_t r0 = 0; r0 < cnt && first_missing == cnt; r0 += 64) {
+        const uint32_t r = r0 + lane;
+        const unsigned long long mm = __ballot(r < cnt && miss(r));
+        if (mm) first_missing = r0 + (uint32_t)__ffsll((long long)mm) - 1u;
+    }
+    return first_missing;
+}
+
+// The pair record of one reported hit, before any kernel aligns it.  missing: the hit lies at or behind the query's
+// first_missing.  ns: the subject's stored length (TA_NS_TOO_LONG: one too long to have travelled); sbad: it holds a
+// letter outside the alphabet.
+#define TA_NS_TOO_LONG 0xFFFFFFFFull
+__device__ __forceinline__ kaamer_align_pair ta_pair(uint32_t qlen, uint64_t qoff, bool qbad, bool missing, uint32_t entry, uint64_t ns, bool sbad)
+{
+    kaamer_align_pair it;
+    it.n_ops = it.start_i = it.start_j = it.end_i = it.end_j = 0;
+    it.identical = it.similar = it.mismatches = it.gap_openings = it.raw = 0;
+    it.query_len = qlen; it.off = qoff; it.entry = TA_NONE; it.subject_len = 0;
+    if (missing) it.status = 4;
+    else {
+        it.entry = entry;
+        it.subject_len = ns > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ns;
+        if (qbad || sbad) it.status = 2;
+        else if (qlen > 0x3FFFFFFFu || ns > 0x3FFFFFFFull) it.status = 3;
+        else if (qlen == 0 || ns == 0) it.status = 0;                       // no cell: the empty alignment
+        else it.status = ns <= ALN_WAVE_NS ? TA_WAVE : TA_LONG;
+    }
+    return it;
 }
 
 __global__ __launch_bounds__(256) void ta_pairs_kernel(TaParams p)
@@ -130,43 +169,23 @@ __global__ __launch_bounds__(256) void ta_pairs_kernel(TaParams p)
         const uint32_t tr = (uint32_t)p.trim[q];
         const uint32_t qlen = m.aa_len - tr;            // Query.Sequence as the handler holds it: the trimmed ORF
         const uint64_t qoff = m.aa_off + tr;
-        bool bad = false;
-        for (uint32_t i = lane; i < qlen; i += 64) {
-            int c = aln_code(p.qraw[qoff + i]);
-            if (c < 0) { bad = true; c = 0; }
-            p.qcodes[qoff + i] = (uint8_t)c;
-        }
-        const bool qbad = __ballot(bad) != 0ull;
-        // the first reported id without an entry ends the query's HitEntries (search.go:461-463)
-        uint32_t first_missing = cnt;
-        for (uint32_t r0 = 0; r0 < cnt && first_missing == cnt; r0 += 64) {
-            const uint32_t r = r0 + lane;
-            bool miss = false;
-            if (r < cnt) {
-                const uint32_t pid = p.top_pid[q * p.K + r];
-                miss = pid >= p.tab.idmap_n || p.tab.idmap[pid] == TA_NONE;
-            }
-            const unsigned long long mm = __ballot(miss);
-            if (mm) first_missing = r0 + (uint32_t)__ffsll((long long)mm) - 1u;
-        }
+        const bool qbad = ta_wave_codes(p.qraw + qoff, p.qcodes + qoff, qlen, lane);
+        const uint32_t first_missing = ta_first_missing(cnt, lane, [&](uint32_t r) {
+            const uint32_t pid = p.top_pid[q * p.K + r];
+            return pid >= p.tab.idmap_n || p.tab.idmap[pid] == TA_NONE;
+        });
         const uint64_t e0 = p.eoff[q];
         for (uint32_t r = lane; r < cnt; r += 64) {
-            kaamer_align_pair it;
-            it.n_ops = it.start_i = it.start_j = it.end_i = it.end_j = 0;
-            it.identical = it.similar = it.mismatches = it.gap_openings = it.raw = 0;
-            it.query_len = qlen; it.off = qoff; it.entry = TA_NONE; it.subject_len = 0;
-            if (r >= first_missing) it.status = 4;
-            else {
-                const uint32_t ent = p.tab.idmap[p.top_pid[q * p.K + r]];
-                const uint64_t ns = p.tab.off[ent + 1] - p.tab.off[ent];
-                it.entry = ent;
-                it.subject_len = ns > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ns;
-                if (qbad || p.tab.bad[ent]) it.status = 2;
-                else if (qlen > 0x3FFFFFFFu || ns > 0x3FFFFFFFull) it.status = 3;
-                else if (qlen == 0 || ns == 0) it.status = 0;                       // no cell: the empty alignment
-                else it.status = ns <= ALN_WAVE_NS ? TA_WAVE : TA_LONG;
+            const bool missing = r >= first_missing;
+            uint32_t ent = TA_NONE;
+            uint64_t ns = 0;
+            bool sbad = false;
+            if (!missing) {
+                ent = p.tab.idmap[p.top_pid[q * p.K + r]];
+                ns = p.tab.off[ent + 1] - p.tab.off[ent];
+                sbad = !qbad && p.tab.bad[ent];   // (read as the rules read it: only where it decides)
             }
-            items[e0 + r] = it;
+            items[e0 + r] = ta_pair(qlen, qoff, qbad, missing, ent, ns, sbad);
         }
     }
 }
@@ -239,7 +258,7 @@ __global__ void ta_finish_kernel(TaParams p)
 {
     if (!p.block || !p.lay->ok) return;
     RepBlockHdr *hdr = reinterpret_cast<RepBlockHdr *>(p.block);
-    RepAlnExt *x = reinterpret_cast<RepAlnExt *>(hdr->reserved + sizeof(RepPosExt));
+    RepAlnExt *x = rep_aln_ext(hdr);
     const uint64_t used = p.ctr[2];
     x->need_bytes = p.lay->items_bytes + used;
     if (used <= p.lay->ops_cap) {

@@ -27,13 +27,13 @@
 //                         result): folds the query's letters, takes every pair's length and byte offset from the ONE
 //                         segment whose holder is id mod W, derives the subject's letter codes and its bad-letter flag from
 //                         the raw bytes (aln_code) into a codes buffer at the same offsets, and classifies the pair by the
-//                         rules ta_pairs_kernel states.  entry = the pair's own index; pair_off[] holds its byte offset:
+//                         rules ta_pairs_kernel follows (ta_pair).  entry = the pair's own index; pair_off[] holds its byte offset:
 //                         TaTable { raw = the received segments, codes, off = pair_off } describes the gathered subjects.
 // ta_layout_kernel, ta_wave_kernel<false> / <true> and ta_finish_kernel then run unchanged on the owner.
 #define TAS_NOT_MINE 0xFFFFFFFFu
 #define TAS_NO_ENTRY 0xFFFFFFFEu
 #define TAS_TOO_LONG 0xFFFFFFFDu
-#define TAS_MAX_LEN 0x3FFFFFFFu   /* a stored length that travels; beyond it the pair fails with status 3, as in ta_pairs_kernel */
+#define TAS_MAX_LEN 0x3FFFFFFFu   /* a stored length that travels; beyond it the pair fails with status 3 (ta_pair) */
 
 struct TasLayout {
     uint32_t rq_cap;      // reported queries the segment describes
@@ -77,17 +77,6 @@ struct TasParams {
     const TaLayout *tlay;
 };
 
-// 0: the ids block describes this batch, no failure, within its bounds and the segment's
-__device__ __forceinline__ uint32_t tas_ids_check(const TasParams &p)
-{
-    const uint32_t *h = p.ids;
-    const uint64_t n_ent = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
-    uint32_t st = h[4] | *p.s_status;
-    if (h[0] != p.seq || h[1] > p.ids_layout.rq_cap || h[1] > *p.s_nq || n_ent > p.ids_layout.ent_cap) st |= (uint32_t)ST_PEER_FAILED;
-    if (!st && (h[1] > p.lay.rq_cap || n_ent > p.lay.ent_cap)) st |= (uint32_t)ST_SEG_CAP;
-    return st;
-}
-
 __device__ __forceinline__ uint64_t tas_shfl64(uint64_t v, int src)
 {
     const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
@@ -105,22 +94,21 @@ __device__ __forceinline__ uint64_t tas_incl_scan(uint64_t v, uint32_t lane)
 
 __global__ __launch_bounds__(256) void tas_len_kernel(TasParams p)
 {
-    const uint32_t st = tas_ids_check(p);
-    const uint32_t n = st ? 0u : p.ids[1];
+    const TpsIds v = tps_ids_view(p.ids, p.ids_layout);
+    uint32_t st = tps_ids_check(v, p.seq, p.ids_layout, *p.s_nq, *p.s_status);
+    if (!st && (v.n_rep > p.lay.rq_cap || v.n_ent > p.lay.ent_cap)) st |= (uint32_t)ST_SEG_CAP;   // ... and within the segment's
+    const uint32_t n = st ? 0u : v.n_rep;
     if (blockIdx.x == 0 && threadIdx.x == 0) { p.n_out[0] = n; p.n_out[1] = st; }
-    const uint64_t n_ent = (uint64_t)p.ids[2] | ((uint64_t)p.ids[3] << 32);
-    const uint64_t *off = reinterpret_cast<const uint64_t *>(p.ids + tps_ids_off_at(p.ids_layout));
-    const uint32_t *ids = p.ids + tps_ids_pid_at(p.ids_layout);
     uint32_t *len = reinterpret_cast<uint32_t *>(p.seg + tas_len_at(p.lay));
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     for (uint64_t i = wave; i < n; i += n_waves) {
-        const uint64_t e = off[i], e1 = off[i + 1];
+        const uint64_t e = v.off[i], e1 = v.off[i + 1];
         uint64_t sum = 0;
-        if (e <= e1 && e1 <= n_ent) {
+        if (e <= e1 && e1 <= v.n_ent) {
             for (uint64_t j = e + lane; j < e1; j += 64) {
-                const uint32_t pid = ids[j];
+                const uint32_t pid = v.pid[j];
                 uint32_t l = TAS_NOT_MINE;
                 if (pid % p.world == p.self) {
                     const uint32_t local = pid / p.world;
@@ -170,17 +158,15 @@ __global__ __launch_bounds__(256) void tas_gather_kernel(TasParams p)
         p.need_out[0] = total; p.need_out[1] = st;
     }
     if (st) return;
-    const uint64_t *off = reinterpret_cast<const uint64_t *>(p.ids + tps_ids_off_at(p.ids_layout));
-    const uint32_t *ids = p.ids + tps_ids_pid_at(p.ids_layout);
+    const TpsIds v = tps_ids_view(p.ids, p.ids_layout);
     const uint32_t *len = reinterpret_cast<const uint32_t *>(p.seg + tas_len_at(p.lay));
     uint8_t *bytes = p.seg + tas_bytes_at(p.lay);
-    const uint64_t n_ent = (uint64_t)p.ids[2] | ((uint64_t)p.ids[3] << 32);
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     for (uint64_t i = wave; i < n; i += n_waves) {
-        const uint64_t e = off[i], e1 = off[i + 1];
-        if (e > e1 || e1 > n_ent) continue;   // (as tas_len_kernel: nothing was counted for it)
+        const uint64_t e = v.off[i], e1 = v.off[i + 1];
+        if (e > e1 || e1 > v.n_ent) continue;   // (as tas_len_kernel: nothing was counted for it)
         uint64_t run = base[i];
         const uint64_t end = base[i + 1];
         for (uint64_t j0 = e; j0 < e1; j0 += 64) {
@@ -189,7 +175,7 @@ __global__ __launch_bounds__(256) void tas_gather_kernel(TasParams p)
             uint64_t src = 0;
             if (j < e1) {
                 l = len[j];
-                if (l <= TAS_MAX_LEN) src = p.off[p.idmap[ids[j] / p.world]];
+                if (l <= TAS_MAX_LEN) src = p.off[p.idmap[v.pid[j] / p.world]];
             }
             const uint32_t c = l <= TAS_MAX_LEN ? l : 0u;
             const uint64_t incl = tas_incl_scan(c, lane);
@@ -210,13 +196,8 @@ __global__ __launch_bounds__(256) void tas_gather_kernel(TasParams p)
 __global__ void tas_check_kernel(TasParams p)
 {
     RepBlockHdr *hdr = reinterpret_cast<RepBlockHdr *>(p.block);
-    if (hdr->status || p.ids[4]) return;   // a batch that failed earlier: refused as it is
-    uint32_t st = 0;
-    for (uint32_t s = 0; s < p.world; s++) {
-        const unsigned long long h = *reinterpret_cast<const unsigned long long *>(p.segs + (uint64_t)s * p.seg_stride);
-        if ((uint32_t)h != p.seq) st |= (uint32_t)ST_PEER_FAILED;
-        st |= (uint32_t)(h >> 32);
-    }
+    if (hdr->status || tps_ids_view(p.ids, p.ids_layout).status) return;   // a batch that failed earlier: refused as it is
+    const uint32_t st = tps_segs_status(p.segs, p.seg_stride, p.world, p.seq);
     if (st) hdr->status |= st;
 }
 
@@ -236,28 +217,15 @@ __global__ __launch_bounds__(256) void tas_pairs_kernel(TasParams p)
         const uint32_t tr = (uint32_t)p.trim[q];
         const uint32_t qlen = m.aa_len - tr;            // Query.Sequence as the handler holds it: the trimmed ORF
         const uint64_t qoff = m.aa_off + tr;
-        bool bad = false;
-        for (uint32_t i = lane; i < qlen; i += 64) {
-            int c = aln_code(p.qraw[qoff + i]);
-            if (c < 0) { bad = true; c = 0; }
-            p.qcodes[qoff + i] = (uint8_t)c;
-        }
-        const bool qbad = __ballot(bad) != 0ull;
+        const bool qbad = ta_wave_codes(p.qraw + qoff, p.qcodes + qoff, qlen, lane);
         const uint64_t e0 = p.eoff[q], rk = p.rank[q];
-        // the first reported id without an entry ends the query's HitEntries (search.go:461-463); a holder that did not
-        // answer for its own id (never, with checked headers) counts as one
-        uint32_t first_missing = cnt;
-        for (uint32_t r0 = 0; r0 < cnt && first_missing == cnt; r0 += 64) {
-            const uint32_t r = r0 + lane;
-            bool miss = false;
-            if (r < cnt) {
-                const uint32_t h = p.top_pid[q * p.K + r] % p.world;
-                const uint32_t l = reinterpret_cast<const uint32_t *>(p.segs + (uint64_t)h * p.seg_stride + len_at)[e0 + r];
-                miss = l == TAS_NO_ENTRY || l == TAS_NOT_MINE;
-            }
-            const unsigned long long mm = __ballot(miss);
-            if (mm) first_missing = r0 + (uint32_t)__ffsll((long long)mm) - 1u;
-        }
+        // the length of reported id r, as its holder h = id mod W stored it in its segment
+        auto len_of = [&](uint32_t h, uint32_t r) { return reinterpret_cast<const uint32_t *>(p.segs + (uint64_t)h * p.seg_stride + len_at)[e0 + r]; };
+        // a holder that did not answer for its own id (never, with checked headers) counts as an id without an entry
+        const uint32_t first_missing = ta_first_missing(cnt, lane, [&](uint32_t r) {
+            const uint32_t l = len_of(p.top_pid[q * p.K + r] % p.world, r);
+            return l == TAS_NO_ENTRY || l == TAS_NOT_MINE;
+        });
         // lane h: where the query's next subject lies in holder h's payload
         uint64_t run = 0, run_end = 0;
         if (lane < p.world) {
@@ -268,10 +236,7 @@ __global__ __launch_bounds__(256) void tas_pairs_kernel(TasParams p)
             const uint32_t r = r0 + lane;
             const bool valid = r < cnt;
             uint32_t h = 0xFFFFFFFFu, l = TAS_NOT_MINE;
-            if (valid) {
-                h = p.top_pid[q * p.K + r] % p.world;
-                l = reinterpret_cast<const uint32_t *>(p.segs + (uint64_t)h * p.seg_stride + len_at)[e0 + r];
-            }
+            if (valid) { h = p.top_pid[q * p.K + r] % p.world; l = len_of(h, r); }
             const uint32_t c = l <= TAS_MAX_LEN ? l : 0u;
             uint64_t soff = 0;
             bool inside = true;
@@ -295,30 +260,11 @@ __global__ __launch_bounds__(256) void tas_pairs_kernel(TasParams p)
                 const uint32_t lj = (uint32_t)__shfl((int)l, (int)j, 64);
                 if (lj > TAS_MAX_LEN) continue;
                 const uint64_t oj = tas_shfl64(soff, (int)j);
-                bool b = false;
-                for (uint32_t i = lane; i < lj; i += 64) {
-                    int k = aln_code(p.segs[oj + i]);
-                    if (k < 0) { b = true; k = 0; }
-                    p.codes[oj + i] = (uint8_t)k;
-                }
-                const bool any = __ballot(b) != 0ull;
+                const bool any = ta_wave_codes(p.segs + oj, p.codes + oj, lj, lane);
                 if (lane == j) sbad = any;
             }
             if (!valid) continue;
-            kaamer_align_pair it;
-            it.n_ops = it.start_i = it.start_j = it.end_i = it.end_j = 0;
-            it.identical = it.similar = it.mismatches = it.gap_openings = it.raw = 0;
-            it.query_len = qlen; it.off = qoff; it.entry = TA_NONE; it.subject_len = 0;
-            if (r >= first_missing) it.status = 4;
-            else {
-                it.entry = (uint32_t)(e0 + r);
-                it.subject_len = l <= TAS_MAX_LEN ? l : 0xFFFFFFFFu;
-                if (qbad || sbad) it.status = 2;
-                else if (qlen > 0x3FFFFFFFu || l > TAS_MAX_LEN) it.status = 3;
-                else if (qlen == 0 || l == 0) it.status = 0;                        // no cell: the empty alignment
-                else it.status = l <= ALN_WAVE_NS ? TA_WAVE : TA_LONG;
-            }
-            items[e0 + r] = it;
+            items[e0 + r] = ta_pair(qlen, qoff, qbad, r >= first_missing, (uint32_t)(e0 + r), l <= TAS_MAX_LEN ? l : TA_NS_TOO_LONG, sbad);
         }
     }
 }

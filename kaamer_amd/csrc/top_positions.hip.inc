@@ -26,14 +26,6 @@
 #define TP_WAVES 4
 #define TP_COOP_MIN 16u   /* ids; longer lists are scanned by the whole wave */
 
-// what the host-buffer form adds to RepBlockHdr, in its reserved bytes (zero in a block without bitmaps)
-struct RepPosExt {
-    uint64_t off_pos_len, off_pos_off, off_pos_bits;   // byte offsets of the three sections
-    uint64_t n_pos_words;
-};
-static_assert(sizeof(RepPosExt) <= sizeof(((RepBlockHdr *)nullptr)->reserved), "the header's reserved bytes hold the bitmap sections");
-static_assert(offsetof(RepBlockHdr, reserved) % 8 == 0, "aligned");
-
 struct TopPosParams {
     const uint32_t *d_nq;
     const QInfo *qinfo;
@@ -87,14 +79,9 @@ __device__ __forceinline__ unsigned long long tp_match(const uint32_t *pid, uint
 __device__ __forceinline__ int tp_block_sections(uint8_t *block, uint64_t block_cap, uint64_t n_rep, uint64_t n_ent, uint64_t n_aa,
                                                  uint64_t total, uint64_t cap, bool first, RepPosExt *xo)
 {
-    uint64_t o = rep_align8(sizeof(RepBlockHdr) + 4 * n_rep);              // rep_query
-    o = rep_align8(o + 4 * n_rep);                                          // trim
-    o = rep_align8(o + sizeof(kaamer_query_meta) * n_rep);                  // q
-    o = o + 8 * (n_rep + 1);                                                // top_off
-    o = rep_align8(o + 4 * n_ent);                                          // pid
-    o = rep_align8(o + 4 * n_ent);                                          // kmatch
-    o = rep_align8(o + 4 * n_ent);                                          // first_pos
-    const uint64_t base_total = rep_align8(o + n_aa);                       // orf_aa
+    RepBlockHdr l;
+    rep_block_layout(l, n_rep, n_ent, n_aa);
+    const uint64_t base_total = l.total_bytes;
     if (base_total > block_cap) return 0;
     RepPosExt x;
     x.off_pos_len = base_total;
@@ -108,7 +95,7 @@ __device__ __forceinline__ int tp_block_sections(uint8_t *block, uint64_t block_
         return -1;
     }
     if (first) {
-        *reinterpret_cast<RepPosExt *>(hdr->reserved) = x;
+        *rep_pos_ext(hdr) = x;
         hdr->total_bytes = x.off_pos_bits + 8 * total;
         reinterpret_cast<uint64_t *>(block + x.off_pos_off)[n_ent] = total;   // CSR end
     }

@@ -40,6 +40,31 @@ __host__ __device__ __forceinline__ uint64_t tps_ids_off_at(const TpsIdsLayout &
 __host__ __device__ __forceinline__ uint64_t tps_ids_pid_at(const TpsIdsLayout &L) { return tps_ids_off_at(L) + 2ull * ((uint64_t)L.rq_cap + 1); }
 __host__ __device__ __forceinline__ uint64_t tps_ids_words(const TpsIdsLayout &L) { return (tps_ids_pid_at(L) + L.ent_cap + 1ull) & ~1ull; }
 
+struct TpsIdsHdr {   // words [0..7] of an ids block
+    uint32_t seq, n_rep;
+    uint64_t n_ent;
+    uint32_t status, zero[3];
+};
+static_assert(sizeof(TpsIdsHdr) == 4 * TPS_HDR && offsetof(TpsIdsHdr, n_ent) == 8 && offsetof(TpsIdsHdr, status) == 16, "ids block header");
+
+struct TpsIds {   // an ids block as its readers see it
+    uint32_t seq, n_rep, status;
+    uint64_t n_ent;
+    const uint32_t *rq;
+    const uint64_t *off;
+    const uint32_t *pid;
+};
+__host__ __device__ __forceinline__ TpsIds tps_ids_view(const uint32_t *ids, const TpsIdsLayout &L)
+{
+    const TpsIdsHdr *h = reinterpret_cast<const TpsIdsHdr *>(ids);
+    TpsIds v;
+    v.seq = h->seq; v.n_rep = h->n_rep; v.n_ent = h->n_ent; v.status = h->status;
+    v.rq = ids + TPS_HDR;
+    v.off = reinterpret_cast<const uint64_t *>(ids + tps_ids_off_at(L));
+    v.pid = ids + tps_ids_pid_at(L);
+    return v;
+}
+
 struct TpsParams {
     uint32_t world, owner, seq;
     TpsIdsLayout ids_layout;
@@ -82,13 +107,13 @@ __global__ __launch_bounds__(256) void tps_ids_pack_kernel(TpsParams p)
     const bool fits = n_rep <= p.ids_layout.rq_cap && n_ent <= p.ids_layout.ent_cap;
     const bool ok = !failed && fits;
     if (first) {
-        uint32_t *h = p.ids_out;
-        h[0] = p.seq;
-        h[1] = ok ? (uint32_t)n_rep : 0u;
-        h[2] = ok ? (uint32_t)n_ent : 0u;
-        h[3] = ok ? (uint32_t)(n_ent >> 32) : 0u;
-        h[4] = failed | (fits ? 0u : (uint32_t)ST_IDS_CAP);
-        h[5] = h[6] = h[7] = 0u;
+        TpsIdsHdr h;
+        h.seq = p.seq;
+        h.n_rep = ok ? (uint32_t)n_rep : 0u;
+        h.n_ent = ok ? n_ent : 0ull;
+        h.status = failed | (fits ? 0u : (uint32_t)ST_IDS_CAP);
+        h.zero[0] = h.zero[1] = h.zero[2] = 0u;
+        *reinterpret_cast<TpsIdsHdr *>(p.ids_out) = h;
         if (!fits) hdr->status |= (uint32_t)ST_IDS_CAP;
     }
     if (!ok) return;
@@ -105,28 +130,37 @@ __global__ __launch_bounds__(256) void tps_ids_pack_kernel(TpsParams p)
     }
 }
 
-// 0: the block describes this batch, no failure, within its bounds
-__device__ __forceinline__ uint32_t tps_ids_check(const TpsParams &p)
+// 0: the block describes this batch, no failure, within its bounds; s_nq, s_status: the reader's own search workspace's
+__device__ __forceinline__ uint32_t tps_ids_check(const TpsIds &v, uint32_t seq, const TpsIdsLayout &L, uint32_t s_nq, uint32_t s_status)
 {
-    const uint32_t *h = p.ids;
-    const uint64_t n_ent = (uint64_t)h[2] | ((uint64_t)h[3] << 32);
-    uint32_t st = h[4] | *p.s_status;
-    if (h[0] != p.seq || h[1] > p.ids_layout.rq_cap || h[1] > *p.s_nq || n_ent > p.ids_layout.ent_cap) st |= (uint32_t)ST_PEER_FAILED;
+    uint32_t st = v.status | s_status;
+    if (v.seq != seq || v.n_rep > L.rq_cap || v.n_rep > s_nq || v.n_ent > L.ent_cap) st |= (uint32_t)ST_PEER_FAILED;
+    return st;
+}
+
+// the W received segment headers (seq | status << 32), stride bytes apart, folded into a status word
+__device__ __forceinline__ uint32_t tps_segs_status(const void *segs, uint64_t stride, uint32_t world, uint32_t seq)
+{
+    uint32_t st = 0;
+    for (uint32_t s = 0; s < world; s++) {
+        const uint64_t h = *reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(segs) + (uint64_t)s * stride);
+        if ((uint32_t)h != seq) st |= (uint32_t)ST_PEER_FAILED;
+        st |= (uint32_t)(h >> 32);
+    }
     return st;
 }
 
 __global__ __launch_bounds__(256) void tps_words_kernel(TpsParams p)
 {
-    const uint32_t st = tps_ids_check(p);
-    const uint32_t n = st ? 0u : p.ids[1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) { p.n_out[0] = n; p.n_out[1] = st; }
+    const TpsIds v = tps_ids_view(p.ids, p.ids_layout);
     const uint32_t nq = *p.s_nq;
-    const uint32_t *rq = p.ids + TPS_HDR;
-    const uint64_t *off = reinterpret_cast<const uint64_t *>(p.ids + tps_ids_off_at(p.ids_layout));
+    const uint32_t st = tps_ids_check(v, p.seq, p.ids_layout, nq, *p.s_status);
+    const uint32_t n = st ? 0u : v.n_rep;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { p.n_out[0] = n; p.n_out[1] = st; }
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t q = (uint64_t)p.owner + (uint64_t)rq[i] * p.world;
+        const uint64_t q = (uint64_t)p.owner + (uint64_t)v.rq[i] * p.world;
         const int32_t size = q < nq ? p.qinfo[q].size : 0;
-        const uint64_t cnt = off[i + 1] - off[i];
+        const uint64_t cnt = v.off[i + 1] - v.off[i];
         const uint64_t w = cnt <= p.K ? cnt * x_words(size) : 0ull;
         p.words[i] = x_sat32(w);
     }
@@ -144,19 +178,17 @@ __global__ __launch_bounds__(64 * TP_WAVES) void tps_bits_kernel(TpsParams p)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint32_t *pid = s_pid[wv];
-    const uint32_t *rq = p.ids + TPS_HDR;
-    const uint64_t *off = reinterpret_cast<const uint64_t *>(p.ids + tps_ids_off_at(p.ids_layout));
-    const uint32_t *ids = p.ids + tps_ids_pid_at(p.ids_layout);
+    const TpsIds v = tps_ids_view(p.ids, p.ids_layout);
     unsigned long long *bits = p.seg + 1;
     const uint64_t wave = (uint64_t)blockIdx.x * TP_WAVES + wv, n_waves = (uint64_t)gridDim.x * TP_WAVES;
     for (uint64_t i = wave; i < n; i += n_waves) {
-        const uint64_t q = (uint64_t)p.owner + (uint64_t)rq[i] * p.world;
+        const uint64_t q = (uint64_t)p.owner + (uint64_t)v.rq[i] * p.world;
         if (q >= nq) continue;
         const QInfo qi = p.qinfo[q];
         const uint32_t size = qi.size > 0 ? (uint32_t)qi.size : 0u;
-        const uint64_t e = off[i], cnt = off[i + 1] - e;
+        const uint64_t e = v.off[i], cnt = v.off[i + 1] - e;
         if (size == 0 || cnt == 0 || cnt > p.K) continue;   // (no words were counted for it)
-        tp_query_bits(pid, ids + e, (uint32_t)cnt, p.vals + qi.aa_off, size, p.arena, bits + p.base[i], lane);
+        tp_query_bits(pid, v.pid + e, (uint32_t)cnt, p.vals + qi.aa_off, size, p.arena, bits + p.base[i], lane);
     }
 }
 
@@ -166,13 +198,9 @@ __global__ __launch_bounds__(256) void tps_or_kernel(TpsParams p)
     RepBlockHdr *hdr = reinterpret_cast<RepBlockHdr *>(p.block);
     // a batch that failed earlier (on the owner, on a shard, or in the ids block): refused as it is.  The checks below
     // depend on the received headers only, so every thread takes the same way whatever it reads here.
-    if (hdr->status || p.ids[4]) return;
-    uint32_t st = 0;
-    for (uint32_t s = 0; s < p.world; s++) {
-        const uint64_t h = p.seg[(uint64_t)s * p.seg_stride];
-        if ((uint32_t)h != p.seq) st |= (uint32_t)ST_PEER_FAILED;
-        st |= (uint32_t)(h >> 32);
-    }
+    const TpsIds v = tps_ids_view(p.ids, p.ids_layout);
+    if (hdr->status || v.status) return;
+    uint32_t st = tps_segs_status(p.seg, 8 * p.seg_stride, p.world, p.seq);
     const uint32_t nq = *p.m_nq;
     const uint64_t n_rep = p.rank[nq], n_ent = p.eoff[nq], n_aa = p.aoff[nq];
     if (p.n_out[0] != n_rep) st |= (uint32_t)ST_PEER_FAILED;   // the owner's own shard walked the same ids block
@@ -186,17 +214,15 @@ __global__ __launch_bounds__(256) void tps_or_kernel(TpsParams p)
     int32_t *rep_len = reinterpret_cast<int32_t *>(p.block + x.off_pos_len);
     uint64_t *rep_poff = reinterpret_cast<uint64_t *>(p.block + x.off_pos_off);
     unsigned long long *bits = reinterpret_cast<unsigned long long *>(p.block + x.off_pos_bits);
-    const uint32_t *rq = p.ids + TPS_HDR;
-    const uint64_t *off = reinterpret_cast<const uint64_t *>(p.ids + tps_ids_off_at(p.ids_layout));
     const uint32_t s_nq = *p.s_nq;
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
     for (uint64_t i = wave; i < n_rep; i += n_waves) {
-        const uint64_t q = (uint64_t)p.owner + (uint64_t)rq[i] * p.world;
+        const uint64_t q = (uint64_t)p.owner + (uint64_t)v.rq[i] * p.world;
         const int32_t size = q < s_nq ? p.qinfo[q].size : 0;
         const uint32_t nw = x_words(size);
-        const uint64_t e = off[i], cnt = off[i + 1] - e, b = p.base[i];
+        const uint64_t e = v.off[i], cnt = v.off[i + 1] - e, b = p.base[i];
         if (lane == 0) rep_len[i] = size > 0 ? size : 0;
         for (uint64_t j = lane; j < cnt; j += 64) rep_poff[e + j] = b + j * nw;
     }

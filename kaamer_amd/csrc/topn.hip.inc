@@ -179,6 +179,41 @@ struct RepBlockHdr {
 };
 static_assert(sizeof(RepBlockHdr) == 256, "block header is 256 bytes");
 
+// what the bitmaps of the reported hits add to the header, in its reserved bytes (top_positions.hip.inc; zero in a block
+// without bitmaps)
+struct RepPosExt {
+    uint64_t off_pos_len, off_pos_off, off_pos_bits;   // byte offsets of the three sections
+    uint64_t n_pos_words;
+};
+// ... and their alignments, behind RepPosExt (top_align.hip.inc; zero in a block without alignments)
+struct RepAlnExt {
+    uint64_t off_items, off_ops;   // byte offsets of the two sections
+    uint64_t ops_bytes;            // operations stored
+    uint64_t need_bytes, cap_bytes;   // both sections: what the batch needed, what this call ran with
+};
+static_assert(sizeof(RepPosExt) + sizeof(RepAlnExt) <= sizeof(((RepBlockHdr *)nullptr)->reserved), "the header's reserved bytes hold both extensions");
+static_assert(offsetof(RepBlockHdr, reserved) % 8 == 0, "aligned");
+__host__ __device__ __forceinline__ RepPosExt *rep_pos_ext(RepBlockHdr *h) { return reinterpret_cast<RepPosExt *>(h->reserved); }
+__host__ __device__ __forceinline__ const RepPosExt *rep_pos_ext(const RepBlockHdr *h) { return reinterpret_cast<const RepPosExt *>(h->reserved); }
+__host__ __device__ __forceinline__ RepAlnExt *rep_aln_ext(RepBlockHdr *h) { return reinterpret_cast<RepAlnExt *>(h->reserved + sizeof(RepPosExt)); }
+__host__ __device__ __forceinline__ const RepAlnExt *rep_aln_ext(const RepBlockHdr *h) { return reinterpret_cast<const RepAlnExt *>(h->reserved + sizeof(RepPosExt)); }
+
+__host__ __device__ __forceinline__ uint64_t rep_align8(uint64_t x) { return (x + 7ull) & ~7ull; }
+
+// the section offsets and the size of a block, from its three totals
+__host__ __device__ __forceinline__ void rep_block_layout(RepBlockHdr &h, uint64_t n_rep, uint64_t n_ent, uint64_t n_aa)
+{
+    h.off_rep_query = sizeof(RepBlockHdr);
+    h.off_trim = rep_align8(h.off_rep_query + 4 * n_rep);
+    h.off_q = rep_align8(h.off_trim + 4 * n_rep);
+    h.off_top_off = rep_align8(h.off_q + sizeof(kaamer_query_meta) * n_rep);
+    h.off_pid = h.off_top_off + 8 * (n_rep + 1);
+    h.off_km = rep_align8(h.off_pid + 4 * n_ent);
+    h.off_fp = rep_align8(h.off_km + 4 * n_ent);
+    h.off_aa = rep_align8(h.off_fp + 4 * n_ent);
+    h.total_bytes = rep_align8(h.off_aa + n_aa);
+}
+
 struct RepParams {
     const uint32_t *d_nq;
     const kaamer_query_meta *q;     // the queries the results belong to: result i is query q_first + i * q_stride
@@ -206,8 +241,6 @@ __global__ void rep_flags_kernel(RepParams p)
     }
 }
 
-__host__ __device__ __forceinline__ uint64_t rep_align8(uint64_t x) { return (x + 7ull) & ~7ull; }
-
 __global__ __launch_bounds__(256) void rep_block_kernel(RepParams p)
 {
     const uint32_t nq = *p.d_nq;
@@ -217,15 +250,7 @@ __global__ __launch_bounds__(256) void rep_block_kernel(RepParams p)
     // section offsets from the three totals (every thread computes the same)
     const uint64_t n_rep = p.rank[nq], n_ent = p.eoff[nq], n_aa = p.aoff[nq];
     RepBlockHdr h;
-    h.off_rep_query = sizeof(RepBlockHdr);
-    h.off_trim = rep_align8(h.off_rep_query + 4 * n_rep);
-    h.off_q = rep_align8(h.off_trim + 4 * n_rep);
-    h.off_top_off = rep_align8(h.off_q + sizeof(kaamer_query_meta) * n_rep);
-    h.off_pid = h.off_top_off + 8 * (n_rep + 1);
-    h.off_km = rep_align8(h.off_pid + 4 * n_ent);
-    h.off_fp = rep_align8(h.off_km + 4 * n_ent);
-    h.off_aa = rep_align8(h.off_fp + 4 * n_ent);
-    h.total_bytes = rep_align8(h.off_aa + n_aa);
+    rep_block_layout(h, n_rep, n_ent, n_aa);
     const bool fits = h.total_bytes <= p.block_cap;
     if (wave == 0 && lane == 0) {
         RepBlockHdr *out = reinterpret_cast<RepBlockHdr *>(p.block);

@@ -10,7 +10,7 @@ import threading
 import numpy as np
 import pytest
 
-from test_top_align import READS_SEED, _against_oracle, _fasta, _same, indel_queries
+from test_top_align import MANY, READS_SEED, _against_oracle, _fasta, _same, check_second_round, indel_queries, many_hits_case, table_without
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_ONLY = bool(os.environ.get("KAAMER_HOST_ONLY"))   # the sanitized CPU build holds the host sources only
@@ -235,6 +235,31 @@ def test_hit_without_an_entry_w3(klib, gpu_device):
         middle += 0 < first < len(order) - 1
         far += first < len(order) and order[first] % W != q % W
     assert on_missing > 0 and middle > 0 and far > 0
+    sx.close()
+
+
+@pytest.mark.gpu
+def test_more_than_64_hits_of_one_query_w3(klib, gpu_device):
+    """the set-up of test_top_align.test_more_than_64_hits_of_one_query: the second round of tas_pairs_kernel's walk over a
+    query's hits, with the full table and with a first id without an entry in that round"""
+    from kaamer_amd import api
+    W = 3
+    recs, qs = many_hits_case()
+    full = api.Proteins.from_fasta(_fasta(recs).encode())
+    ix = api.Index.from_image(full.image(device=gpu_device), gpu_device)
+    ix.attach_proteins(full)
+    sx = _sharded(api, full, gpu_device, W)
+    plain = sx.search_top(qs, **MANY)
+    long_i = plain.rep_query.tolist().index(1)
+    assert int(plain.top_off[long_i + 1] - plain.top_off[long_i]) == 70
+    _same_top(sx.search_top(qs, align=dict(text=True), **MANY), ix.search_top(qs, align=dict(text=True), **MANY))
+    pid = int(plain.top_pid[int(plain.top_off[long_i]) + 66])
+    sub = table_without(recs, full, pid)
+    ix.attach_proteins(sub)   # (a second attach replaces the first)
+    sx.attach_proteins(sub)
+    top = sx.search_top(qs, align=dict(text=True), **MANY)
+    check_second_round(top, plain, long_i, pid)
+    _same_top(top, ix.search_top(qs, align=dict(text=True), **MANY))
     sx.close()
 
 

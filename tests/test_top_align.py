@@ -254,6 +254,64 @@ def test_hit_without_an_entry(klib, gpu_device):
     assert on_missing > 0 and later > 0 and middle > 0
 
 
+MANY = dict(min_k_ratio=0.0, min_k_match=1, max_results=70)
+
+
+def many_hits_case():
+    """-> (records of a 400-protein database, three queries): two ordinary queries and, between them, the concatenation of
+    the database's 80 shortest records, which reports MaxResults = 70 hits under MANY: more than the 64 a wave classifies
+    per round.  (The shortest: the restatement of the aligner costs query x subject.)"""
+    from kaamer_amd import workload
+    db = workload.make_db(400, seed=43)
+    recs = workload.unpack(db)
+    pick = sorted(range(390), key=lambda i: (len(recs[i]), i))[:80]   # (the FASTA reader's last two records share an id)
+    two = workload.unpack(workload.make_protein_queries(db, 2, seed=44))
+    return recs, [two[0], b"".join(recs[i] for i in pick), two[1]]
+
+
+def table_without(recs, full, pid):
+    """the protein table of `recs` without the one record whose id is pid (", partial": dropped without renumbering the others)"""
+    from kaamer_amd import api
+    ids = full.ids.tolist()
+    assert ids.count(pid) == 1
+    gone = ids.index(pid)
+    sub = api.Proteins.from_fasta("".join(">sp|P%05d|N%d%s\n%s\n" % (i, i, " fragment, partial" if i == gone else "", s.decode())
+                                          for i, s in enumerate(recs)).encode())
+    assert set(ids) - set(sub.ids.tolist()) == {pid}
+    return sub
+
+
+def check_second_round(top, plain, long_i, pid):
+    """the long query's hits, in sortMapByValue order: aligned before the id without an entry, status 4 from it on"""
+    a, b = int(top.top_off[long_i]), int(top.top_off[long_i + 1])
+    order = plain.top_pid[a:b].tolist()
+    stat = {int(top.top_pid[e]): top.alignments[e]["status"] for e in range(a, b)}
+    first = order.index(pid)
+    assert b - a == 70 and first >= 64
+    assert [stat[p] for p in order] == [0] * first + [4] * (len(order) - first), (order, stat)
+
+
+def test_more_than_64_hits_of_one_query(klib, oracle, gpu_device):
+    """a query that reports 70 hits: the second round of ta_pairs_kernel's walk over a query's hits, 64 at a time, and a
+    first id without an entry that falls into that round"""
+    from kaamer_amd import api, search
+    recs, qs = many_hits_case()
+    full = api.Proteins.from_fasta(_fasta(recs).encode())
+    new = api.Index.from_image(full.image(device=gpu_device), gpu_device)
+    new.attach_proteins(full)
+    plain = new.search_top(qs, **MANY)
+    long_i = plain.rep_query.tolist().index(1)
+    assert int(plain.top_off[long_i + 1] - plain.top_off[long_i]) == 70
+    qtext = "".join(">q%d\n%s\n" % (i, s.decode()) for i, s in enumerate(qs))
+    res = search.ProteinSearch(new, qtext, search.SearchOptions(MaxResults=70, MinKRatio=0.0, MinKMatch=1, Align=True))
+    assert len(res[1]["SearchResults"]["Hits"]) == 70
+    n, _ = _against_oracle(oracle, res, full.stats()["NumberOfAA"])
+    assert n >= 70
+    pid = int(plain.top_pid[int(plain.top_off[long_i]) + 66])
+    new.attach_proteins(table_without(recs, full, pid))   # (a second attach replaces the first)
+    check_second_round(new.search_top(qs, align=dict(text=True), **MANY), plain, long_i, pid)
+
+
 def test_options(klib, gpu_device):
     from kaamer_amd import abi, api, workload
     prot, old, new = _db(400, 41, gpu_device)
