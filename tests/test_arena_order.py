@@ -7,75 +7,12 @@ The walk here is Python (tests/pyref.py for the key encoding) and resolves every
 saved image; the ids behind every key are checked against the oracle index.  Host builder only: that the device
 builder lands on the same bytes is tests/test_builder_device.py."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import pyref
-
-EMPTY = 0xFFFFFFFF
-INLINE = 0x80000000
-
-
-def _mix32(h):   # kaamer_layout.h kh_mix32
-    h ^= h >> 16
-    h = (h * 0x85ebca6b) & 0xFFFFFFFF
-    h ^= h >> 13
-    h = (h * 0xc2b2ae35) & 0xFFFFFFFF
-    h ^= h >> 16
-    return h
-
-
-def _shard_of(key, n_shards):
-    return (_mix32(key) * n_shards) >> 32
-
-
-def _home(key, n_shards, n_buckets):
-    rest = (_mix32(key) * n_shards) & 0xFFFFFFFF
-    return (rest * n_buckets) >> 32
-
-
-def _image_bytes(img, tmp_path, name="a.kgi"):
-    p = os.path.join(str(tmp_path), name)
-    img.save(p)
-    with open(p, "rb") as f:
-        b = f.read()
-    os.unlink(p)
-    return b
-
-
-class _Table:
-    """buckets and arena of a saved image, and the lookup of kaamer_layout.h"""
-
-    def __init__(self, raw, st):
-        w = np.frombuffer(raw, dtype=np.uint32)
-        self.nb = st["n_buckets"]
-        self.n_shards = st["n_shards"]
-        self.slots = w[1024:1024 + self.nb * 16].reshape(self.nb, 8, 2)
-        self.arena = w[1024 + self.nb * 16:]
-        assert len(self.arena) == st["arena_words"]
-
-    def val(self, key):
-        b = _home(key, self.n_shards, self.nb)
-        for _ in range(self.nb):
-            ks = self.slots[b, :, 0]
-            at = np.flatnonzero(ks == key)
-            if len(at):
-                return int(self.slots[b, at[0], 1])
-            if (ks == EMPTY).any():
-                return None
-            b = 0 if b + 1 == self.nb else b + 1
-        return None
-
-    def units(self, off):
-        return (1 + int(self.arena[off * 4]) + 3) // 4
-
-    def ids(self, val):
-        if val & INLINE:
-            return [val & ~INLINE]
-        c = int(self.arena[val * 4])
-        return self.arena[val * 4 + 1:val * 4 + 1 + c].tolist()
+from tableref import EMPTY, INLINE, _Table, _image_bytes, _shard_of
 
 
 def _check_walk_order(api, oracle, tmp_path, db, shard, n_shards):
