@@ -164,6 +164,100 @@ static int ko_arg3(const int s[3])
 }
 
 /*
+ * The recurrence, stated once: the three candidates of layer `l` at cell p = i * c + j, in the order the first maximum is
+ * taken in (predecessor layer diag, up, left).  rv / qv: the indices of query[i-1] / subject[j-1].  The fill below and the
+ * census (ko_align_census) both read it.
+ */
+static void ko_candidates(int (*tab)[3], size_t p, int c, int l, int rv, int qv, int dp_gap_open, int gap_col, int s[3])
+{
+    if (l == L_DIAG) {
+        /* diag: the best of the three layers at (i-1, j-1); the substitution score is added to the winner */
+        s[0] = tab[p - c - 1][L_DIAG]; s[1] = tab[p - c - 1][L_UP]; s[2] = tab[p - c - 1][L_LEFT];
+    } else if (l == L_UP) {
+        /* up: a gap position that consumes query[i-1]; entering the layer costs the gap-open penalty */
+        s[0] = tab[p - c][L_DIAG] + dp_gap_open + ko_b62(rv, 0, gap_col);
+        s[1] = tab[p - c][L_UP] + ko_b62(rv, 0, gap_col);
+        s[2] = tab[p - c][L_LEFT] + dp_gap_open + ko_b62(rv, 0, gap_col);
+    } else {
+        /* left: a gap position that consumes subject[j-1] */
+        s[0] = tab[p - 1][L_DIAG] + dp_gap_open + ko_b62(0, qv, gap_col);
+        s[1] = tab[p - 1][L_UP] + dp_gap_open + ko_b62(0, qv, gap_col);
+        s[2] = tab[p - 1][L_LEFT] + ko_b62(0, qv, gap_col);
+    }
+}
+
+/* one pair's tables and traceback: what ko_align formats and ko_align_census counts */
+typedef struct {
+    char *a, *b;            /* the strings the aligner holds: [uU] -> '*' (align.go:54-55) */
+    int r, c;               /* rows nq + 1, columns ns + 1 */
+    int (*tab)[3];
+    unsigned char *from;    /* 2 bits per layer: predecessor layer + 1, 0 = start */
+    int max_s, max_i, max_j, max_l;
+    char *ops;              /* in reverse: 'M' (both), 'U' (query letter against '-'), 'L' ('-' against subject letter) */
+    int n_ops, qs, ss;      /* 0-based start of the aligned ranges */
+} ko_dp;
+
+static void ko_dp_free(ko_dp *d)
+{
+    free(d->a); free(d->b); free(d->tab); free(d->from); free(d->ops);
+    memset(d, 0, sizeof *d);
+}
+
+/* SWAffine.Align: fill and traceback.  Returns 0, 2 = a letter outside the alphabet, 3 = out of memory (d is freed). */
+static int ko_dp_run(const char *query, int nq, const char *subject, int ns, int dp_gap_open, int gap_col, ko_dp *d)
+{
+    memset(d, 0, sizeof *d);
+    char *a = d->a = (char *)malloc((size_t)nq + 1), *b = d->b = (char *)malloc((size_t)ns + 1);
+    if (!a || !b) { ko_dp_free(d); return 3; }
+    for (int i = 0; i < nq; i++) a[i] = (query[i] == 'u' || query[i] == 'U') ? '*' : query[i];       /* align.go:54 */
+    for (int j = 0; j < ns; j++) b[j] = (subject[j] == 'u' || subject[j] == 'U') ? '*' : subject[j]; /* align.go:55 */
+    for (int i = 0; i < nq; i++) if (ko_dp_letter(a[i]) < 0) { ko_dp_free(d); return 2; }
+    for (int j = 0; j < ns; j++) if (ko_dp_letter(b[j]) < 0) { ko_dp_free(d); return 2; }
+    const int r = d->r = nq + 1, c = d->c = ns + 1;
+    int (*tab)[3] = d->tab = (int (*)[3])calloc((size_t)r * c, sizeof(int[3]));
+    unsigned char *from = d->from = (unsigned char *)calloc((size_t)r * c, 1);
+    char *ops = d->ops = (char *)malloc((size_t)nq + ns + 2);
+    if (!tab || !from || !ops) { ko_dp_free(d); return 3; }
+    int max_s = 0, max_i = 0, max_j = 0, max_l = L_DIAG;
+    for (int i = 1; i < r; i++) {
+        const int rv = ko_dp_letter(a[i - 1]);
+        for (int j = 1; j < c; j++) {
+            const int qv = ko_dp_letter(b[j - 1]);
+            const size_t p = (size_t)i * c + j;
+            int s[3], k;
+            unsigned f = 0;
+            ko_candidates(tab, p, c, L_DIAG, rv, qv, dp_gap_open, gap_col, s);
+            k = ko_arg3(s);
+            int v = s[k] + ko_b62(rv, qv, gap_col);           /* + the substitution score, floored at zero */
+            if (v > 0) { tab[p][L_DIAG] = v; f |= (unsigned)(s[k] > 0 ? k + 1 : 0); }
+            ko_candidates(tab, p, c, L_UP, rv, qv, dp_gap_open, gap_col, s);
+            k = ko_arg3(s);
+            if (s[k] > 0) { tab[p][L_UP] = s[k]; f |= (unsigned)(k + 1) << 2; }
+            ko_candidates(tab, p, c, L_LEFT, rv, qv, dp_gap_open, gap_col, s);
+            k = ko_arg3(s);
+            if (s[k] > 0) { tab[p][L_LEFT] = s[k]; f |= (unsigned)(k + 1) << 4; }
+            from[p] = (unsigned char)f;
+            for (int l = 0; l < 3; l++)
+                if (tab[p][l] > max_s) { max_s = tab[p][l]; max_i = i; max_j = j; max_l = l; }
+        }
+    }
+    /* traceback -> operations in reverse */
+    int n_ops = 0, i = max_i, j = max_j, l = max_l;
+    while (i > 0 && j > 0 && max_s > 0) {
+        const size_t p = (size_t)i * c + j;
+        if (tab[p][l] <= 0) break;
+        const unsigned pred = (from[p] >> (2 * l)) & 3u;
+        ops[n_ops++] = l == L_DIAG ? 'M' : l == L_UP ? 'U' : 'L';
+        if (l == L_DIAG) { i--; j--; } else if (l == L_UP) i--; else j--;
+        if (pred == 0) break;   /* the alignment starts here */
+        l = (int)pred - 1;
+    }
+    d->max_s = max_s; d->max_i = max_i; d->max_j = max_j; d->max_l = max_l;
+    d->n_ops = n_ops; d->qs = i; d->ss = j;
+    return 0;
+}
+
+/*
  * align.Align (align.go:46-161).  aln_out receives the three lines of AlnString (query row, match row, subject row),
  * each *aln_len characters; it must hold 3 * (nq + ns) bytes.  Returns 0, 1 = "No matrix found" (align.go:50-52: the
  * caller keeps an empty AlignmentResult), 2 = a letter outside the alphabet (SWAffine.Align fails; the reference ignores
@@ -178,60 +272,11 @@ int ko_align(const char *query, int nq, const char *subject, int ns, uint64_t nu
     if (ko_matrix_scores(sub_matrix, gap_open, gap_extend, &lambda, &kk)) return 1;
     /* the similarity marks use matrixScores.SubMatrix (align.go:96); only BLOSUM62's data is restated here */
     if (strncmp(sub_matrix, "blosum62", 8) && strncmp(sub_matrix, "BLOSUM62", 8)) return 1;
-    char *a = (char *)malloc((size_t)nq + 1), *b = (char *)malloc((size_t)ns + 1);
-    if (!a || !b) { free(a); free(b); return 3; }
-    for (int i = 0; i < nq; i++) a[i] = (query[i] == 'u' || query[i] == 'U') ? '*' : query[i];       /* align.go:54 */
-    for (int j = 0; j < ns; j++) b[j] = (subject[j] == 'u' || subject[j] == 'U') ? '*' : subject[j]; /* align.go:55 */
-    for (int i = 0; i < nq; i++) if (ko_dp_letter(a[i]) < 0) { free(a); free(b); return 2; }
-    for (int j = 0; j < ns; j++) if (ko_dp_letter(b[j]) < 0) { free(a); free(b); return 2; }
-    const int r = nq + 1, c = ns + 1;
-    int (*tab)[3] = (int (*)[3])calloc((size_t)r * c, sizeof(int[3]));
-    unsigned char *from = (unsigned char *)calloc((size_t)r * c, 1);  /* 2 bits per layer: predecessor layer + 1, 0 = start */
-    if (!tab || !from) { free(a); free(b); free(tab); free(from); return 3; }
-    int max_s = 0, max_i = 0, max_j = 0, max_l = L_DIAG;
-    for (int i = 1; i < r; i++) {
-        const int rv = ko_dp_letter(a[i - 1]);
-        for (int j = 1; j < c; j++) {
-            const int qv = ko_dp_letter(b[j - 1]);
-            const size_t p = (size_t)i * c + j;
-            int s[3], k;
-            unsigned f = 0;
-            /* diag: the best of the three layers at (i-1, j-1) + the substitution score, floored at zero */
-            s[0] = tab[p - c - 1][L_DIAG]; s[1] = tab[p - c - 1][L_UP]; s[2] = tab[p - c - 1][L_LEFT];
-            k = ko_arg3(s);
-            int v = s[k] + ko_b62(rv, qv, gap_col);
-            if (v > 0) { tab[p][L_DIAG] = v; f |= (unsigned)(s[k] > 0 ? k + 1 : 0); }
-            /* up: a gap position that consumes query[i-1]; entering the layer costs the gap-open penalty */
-            s[0] = tab[p - c][L_DIAG] + dp_gap_open + ko_b62(rv, 0, gap_col);
-            s[1] = tab[p - c][L_UP] + ko_b62(rv, 0, gap_col);
-            s[2] = tab[p - c][L_LEFT] + dp_gap_open + ko_b62(rv, 0, gap_col);
-            k = ko_arg3(s);
-            if (s[k] > 0) { tab[p][L_UP] = s[k]; f |= (unsigned)(k + 1) << 2; }
-            /* left: a gap position that consumes subject[j-1] */
-            s[0] = tab[p - 1][L_DIAG] + dp_gap_open + ko_b62(0, qv, gap_col);
-            s[1] = tab[p - 1][L_UP] + dp_gap_open + ko_b62(0, qv, gap_col);
-            s[2] = tab[p - 1][L_LEFT] + ko_b62(0, qv, gap_col);
-            k = ko_arg3(s);
-            if (s[k] > 0) { tab[p][L_LEFT] = s[k]; f |= (unsigned)(k + 1) << 4; }
-            from[p] = (unsigned char)f;
-            for (int l = 0; l < 3; l++)
-                if (tab[p][l] > max_s) { max_s = tab[p][l]; max_i = i; max_j = j; max_l = l; }
-        }
-    }
-    /* traceback -> operations in reverse: 'M' (both), 'U' (query letter against '-'), 'L' ('-' against subject letter) */
-    char *ops = (char *)malloc((size_t)nq + ns + 2);
-    if (!ops) { free(a); free(b); free(tab); free(from); return 3; }
-    int n_ops = 0, i = max_i, j = max_j, l = max_l;
-    while (i > 0 && j > 0 && max_s > 0) {
-        const size_t p = (size_t)i * c + j;
-        if (tab[p][l] <= 0) break;
-        const unsigned pred = (from[p] >> (2 * l)) & 3u;
-        ops[n_ops++] = l == L_DIAG ? 'M' : l == L_UP ? 'U' : 'L';
-        if (l == L_DIAG) { i--; j--; } else if (l == L_UP) i--; else j--;
-        if (pred == 0) break;   /* the alignment starts here */
-        l = (int)pred - 1;
-    }
-    const int qs = i, ss = j;   /* 0-based start of the aligned ranges */
+    ko_dp d;
+    const int rc = ko_dp_run(query, nq, subject, ns, dp_gap_open, gap_col, &d);
+    if (rc) return rc;
+    const char *a = d.a, *b = d.b, *ops = d.ops;
+    const int n_ops = d.n_ops, qs = d.qs, ss = d.ss, max_i = d.max_i, max_j = d.max_j;
     /* align.Format + align.go:70-103, walking the operations forward */
     float identity = 0, similarity = 0, nb_pos = 0;
     int mismatches = 0, len = n_ops;
@@ -288,6 +333,75 @@ int ko_align(const char *query, int nq, const char *subject, int ns, uint64_t nu
     out->s_start = n_ops ? ss + 1 : 1;
     out->s_end = n_ops ? max_j : 0;
     *aln_len = len;
-    free(a); free(b); free(tab); free(from); free(ops);
+    ko_dp_free(&d);
+    return 0;
+}
+
+/*
+ * What an input exercises (tests/test_align_edges.py): the ties and the gap geometry of one pair's alignment, counted on the
+ * tables and the traceback ko_align formats.  Nothing here is compared with the product: it proves that an input carries
+ * the tie or the gap it was built for.
+ *   best_ties_same_row / _other_row   cells other than the chosen one, in its row / in later rows, whose best layer equals the
+ *                                     maximum (earlier rows and earlier columns hold none: the chosen cell is the first)
+ *   best_ties_row_plus_64k            those of the later rows that lie a multiple of 64 rows below the chosen one
+ *   path_ties_diag / _up / _left      cells of the traceback path, by the layer the path is in, where two or more of that
+ *                                     layer's candidates equal the positive maximum (a zero maximum is the alignment's start:
+ *                                     there is no predecessor to choose)
+ *   gap_runs_adjacent                 places where a 'U' run touches an 'L' run
+ *   gap_runs_crossing                 rows 64k strictly inside a 'U' run (it holds rows 64k and 64k + 1) + rows 64k at which an
+ *                                     'L' run lies; crossings[] receives them, +row for a 'U' run, -row for an 'L' run, up to
+ *                                     crossings_cap (one 'U' and one 'L' run at most per row: 2 * (nq / 64) always suffices)
+ * Returns as ko_dp_run.
+ */
+typedef struct {
+    int32_t best_ties_same_row, best_ties_other_row, best_ties_row_plus_64k;
+    int32_t path_ties_diag, path_ties_up, path_ties_left;
+    int32_t gap_runs_adjacent, gap_runs_crossing;
+} ko_census;
+
+int ko_align_census(const char *query, int nq, const char *subject, int ns, int dp_gap_open, int gap_col, ko_census *out,
+                    int32_t *crossings, int crossings_cap)
+{
+    memset(out, 0, sizeof *out);
+    ko_dp d;
+    const int rc = ko_dp_run(query, nq, subject, ns, dp_gap_open, gap_col, &d);
+    if (rc) return rc;
+    const int c = d.c;
+    if (d.max_s > 0)
+        for (int i = d.max_i; i < d.r; i++)
+            for (int j = 1; j < c; j++) {
+                if (i == d.max_i && j == d.max_j) continue;
+                const int *t = d.tab[(size_t)i * c + j];
+                const int best = t[0] > t[1] ? (t[0] > t[2] ? t[0] : t[2]) : (t[1] > t[2] ? t[1] : t[2]);
+                if (best != d.max_s) continue;
+                if (i == d.max_i) out->best_ties_same_row++;
+                else {
+                    out->best_ties_other_row++;
+                    if ((i - d.max_i) % 64 == 0) out->best_ties_row_plus_64k++;
+                }
+            }
+    /* the path again, cell by cell (the operations in reverse name the layers it is in) */
+    int i = d.max_i, j = d.max_j;
+    for (int t = 0; t < d.n_ops; t++) {
+        const char op = d.ops[t];
+        const int l = op == 'M' ? L_DIAG : op == 'U' ? L_UP : L_LEFT;
+        int s[3];
+        ko_candidates(d.tab, (size_t)i * c + j, c, l, ko_dp_letter(d.a[i - 1]), ko_dp_letter(d.b[j - 1]), dp_gap_open, gap_col, s);
+        const int k = ko_arg3(s);
+        if (s[k] > 0 && (s[0] == s[k]) + (s[1] == s[k]) + (s[2] == s[k]) >= 2) {
+            if (l == L_DIAG) out->path_ties_diag++; else if (l == L_UP) out->path_ties_up++; else out->path_ties_left++;
+        }
+        /* gap geometry: 'U' at this cell consumes query row i, 'L' lies at row i */
+        if (t + 1 < d.n_ops && op != 'M' && d.ops[t + 1] != 'M' && d.ops[t + 1] != op) out->gap_runs_adjacent++;
+        int hit = 0;
+        if (op == 'U' && t + 1 < d.n_ops && d.ops[t + 1] == 'U' && (i - 1) % 64 == 0 && i > 1) hit = i - 1;   /* rows i - 1 and i */
+        if (op == 'L' && i % 64 == 0 && (t + 1 == d.n_ops || d.ops[t + 1] != 'L')) hit = -i;                  /* once per run */
+        if (hit) {
+            if (out->gap_runs_crossing < crossings_cap && crossings) crossings[out->gap_runs_crossing] = hit;
+            out->gap_runs_crossing++;
+        }
+        if (l == L_DIAG) { i--; j--; } else if (l == L_UP) i--; else j--;
+    }
+    ko_dp_free(&d);
     return 0;
 }

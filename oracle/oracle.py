@@ -320,3 +320,30 @@ def align(query, subject, number_of_aa, sub_matrix="blosum62", gap_open=11, gap_
     d = {k: getattr(out, k) for k, _ in _Alignment._fields_}
     d["aln"] = (raw[:ln].decode("latin-1"), raw[ln:2 * ln].decode("latin-1"), raw[2 * ln:3 * ln].decode("latin-1"))
     return d
+
+
+class _Census(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("best_ties_same_row", "best_ties_other_row", "best_ties_row_plus_64k", "path_ties_diag",
+                                         "path_ties_up", "path_ties_left", "gap_runs_adjacent", "gap_runs_crossing")]
+
+
+def align_census(query, subject, dp_gap_open=-11, gap_col=0):
+    """ko_align_census: which ties and which gap geometry the alignment of one pair meets (the tables and the traceback of
+    `align`) -> dict of the counts documented in align_oracle.c, plus "crossings": [("U" | "L", row)], the strip-boundary rows
+    (multiples of 64) inside a 'U' run or under an 'L' run.  Raises ValueError on a letter outside the alphabet."""
+    L = lib()
+    L.ko_align_census.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_Census),
+                                  C.POINTER(C.c_int32), C.c_int]
+    q = query if isinstance(query, bytes) else query.encode("latin-1")
+    s = subject if isinstance(subject, bytes) else subject.encode("latin-1")
+    out = _Census()
+    cap = 2 * (len(q) // 64) + 2
+    rows = (C.c_int32 * cap)()
+    rc = L.ko_align_census(q, len(q), s, len(s), dp_gap_open, gap_col, C.byref(out), rows, cap)
+    if rc == 2:
+        raise ValueError("letter outside the protein alphabet")
+    if rc:
+        raise MemoryError()
+    d = {k: getattr(out, k) for k, _ in _Census._fields_}
+    d["crossings"] = [("U" if v > 0 else "L", abs(v)) for v in rows[:out.gap_runs_crossing]]
+    return d
