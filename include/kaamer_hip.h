@@ -534,6 +534,13 @@ int kaamer_stream_open_flat(kaamer_index *ix, int32_t seq_type, double min_k_rat
 /* a stream whose results carry the bitmaps of the reported hits (kaamer_batch_top_positions); push / pop / close as above */
 int kaamer_stream_open_pos_flat(kaamer_index *ix, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                                 uint32_t max_results, kaamer_stream **out);
+/* ... and the alignment of every reported hit (FastqSearch / ProteinSearch with -aln chunk by chunk, search_fastq.go:60-136 +
+ * search.go:483-494): a push goes the way kaamer_submit_batch_top_aln_flat goes, arguments as there; pop returns a block
+ * that kaamer_batch_top_alignments (and, with want_positions, kaamer_batch_top_positions) read.  KAAMER_E_ARG when no
+ * table is attached to the index (kaamer_index_attach_proteins, declared below). */
+int kaamer_stream_open_aln_flat(kaamer_index *ix, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                uint32_t max_results, int32_t want_positions, const char *sub_matrix, int32_t gap_open,
+                                int32_t gap_extend, int32_t want_text, kaamer_stream **out);
 int kaamer_stream_push(kaamer_stream *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs);
 int kaamer_stream_pop(kaamer_stream *st, kaamer_batch_top **out);
 uint32_t kaamer_stream_pending(const kaamer_stream *st);
@@ -745,6 +752,67 @@ int kaamer_search_file(kaamer_replicas *r, const char *path, int format, int str
                        double min_k_ratio, int64_t min_k_match, uint32_t max_results, uint32_t chunk_seqs,
                        uint64_t chunk_bytes, uint32_t in_flight, kaamer_chunk_cb cb, void *user, kaamer_counters *total);
 
+/* The same drivers for a request with -pos (search.go:416,442-452,520-522) and -aln (search.go:454-470,483-494).
+ * kaamer_replicas_attach_proteins: kaamer_index_attach_proteins on every replica, the same rules (the table is borrowed,
+ * a second attach replaces the first, not while calls are in flight); a failure on replica i is reported as such and
+ * leaves replicas 0 .. i-1 attached. */
+int kaamer_replicas_attach_proteins(kaamer_replicas *r, const kaamer_proteins *p);
+/* replica streams whose chunks carry the bitmaps (kaamer_stream_open_pos_flat on every replica) and the alignments
+ * (kaamer_stream_open_aln_flat on every replica) of the reported hits; push / pop / pending / close as above */
+int kaamer_replica_stream_open_pos_flat(kaamer_replicas *r, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                        uint32_t max_results, kaamer_replica_stream **out);
+int kaamer_replica_stream_open_aln_flat(kaamer_replicas *r, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                        uint32_t max_results, int32_t want_positions, const char *sub_matrix,
+                                        int32_t gap_open, int32_t gap_extend, int32_t want_text, kaamer_replica_stream **out);
+/* kaamer_search_file for such a request (FastqSearch / ProteinSearch / NucleotideSearch over a file with -pos / -aln,
+ * search_fastq.go:60-136, search_protein.go:40-118, search_nucleotide.go:27-160): want_positions != 0: `top` of the
+ * callback carries the chunk's bitmaps (kaamer_batch_top_positions); want_aln != 0: its alignments
+ * (kaamer_batch_top_alignments; sub_matrix / gap_open / gap_extend / want_text as kaamer_search_batch_top_aln_flat takes
+ * them, sub_matrix may be NULL otherwise), hits in BitScore order.  Everything else as kaamer_search_file, which is this
+ * call with both switched off. */
+int kaamer_search_file_opts(kaamer_replicas *r, const char *path, int format, int strict_scanner, int32_t seq_type,
+                            double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t want_positions,
+                            int32_t want_aln, const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text,
+                            uint32_t chunk_seqs, uint64_t chunk_bytes, uint32_t in_flight, kaamer_chunk_cb cb, void *user,
+                            kaamer_counters *total);
+
+/* ------------------------------------------------------------------------- */
+/* The same two drivers on the one-process sharded handle: a database larger    */
+/* than one device behind FastqSearch / ProteinSearch / NucleotideSearch over a  */
+/* file of any size (search_fastq.go:60-136, search_protein.go:40-118,            */
+/* search_nucleotide.go:27-160; BASELINE configs[3]).                              */
+/* ------------------------------------------------------------------------- */
+/* A FIFO of kaamer_sharded_ticket with fixed options, the contract of kaamer_stream_*: push copies the chunk and starts
+ * it on a free set of the handle, pop is kaamer_sharded_wait_batch_top on the oldest chunk (a chunk beyond a bound is
+ * repeated inside it; a chunk whose wait fails is consumed), close lets run out and drops what nobody popped.  The
+ * handle has KAAMER_SHARDED_SETS sets: push returns KAAMER_E_BUSY, without waiting, when the stream holds that many
+ * chunks, or when it holds at least one and other callers hold the rest: pop first.  A stream that holds nothing waits
+ * for a set like any other caller.  One thread per stream; other threads may go on calling the handle.  The _pos form's
+ * results carry the bitmaps of the reported hits (kaamer_sharded_submit_batch_top_pos_flat per chunk), the _aln form's
+ * their alignments (kaamer_sharded_submit_batch_top_aln_flat per chunk; KAAMER_E_ARG when no table is attached);
+ * kaamer_sharded_index_attach_proteins returns KAAMER_E_BUSY while a stream holds a chunk. */
+#define KAAMER_SHARDED_SETS 3
+typedef struct kaamer_sharded_stream kaamer_sharded_stream;
+int kaamer_sharded_stream_open_flat(kaamer_sharded_index *sx, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                    uint32_t max_results, kaamer_sharded_stream **out);
+int kaamer_sharded_stream_open_pos_flat(kaamer_sharded_index *sx, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                        uint32_t max_results, kaamer_sharded_stream **out);
+int kaamer_sharded_stream_open_aln_flat(kaamer_sharded_index *sx, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                        uint32_t max_results, int32_t want_positions, const char *sub_matrix,
+                                        int32_t gap_open, int32_t gap_extend, int32_t want_text, kaamer_sharded_stream **out);
+int kaamer_sharded_stream_push(kaamer_sharded_stream *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs);
+int kaamer_sharded_stream_pop(kaamer_sharded_stream *st, kaamer_batch_top **out);
+uint32_t kaamer_sharded_stream_pending(const kaamer_sharded_stream *st);
+void kaamer_sharded_stream_close(kaamer_sharded_stream *st);
+/* kaamer_search_file_opts on the sharded handle: same arguments, same callback (rep_query / q[].src_seq of `top` count
+ * from the chunk's first record), same result as on an unsharded index of the whole database.  in_flight counts chunks
+ * per HANDLE: 0 means 3, more than KAAMER_SHARDED_SETS is cut to that. */
+int kaamer_sharded_search_file(kaamer_sharded_index *sx, const char *path, int format, int strict_scanner, int32_t seq_type,
+                               double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t want_positions,
+                               int32_t want_aln, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                               int32_t want_text, uint32_t chunk_seqs, uint64_t chunk_bytes, uint32_t in_flight,
+                               kaamer_chunk_cb cb, void *user, kaamer_counters *total);
+
 /* Waits for `stream`, copies the counters to the host and reports a deferred
  * KAAMER_E_CAPACITY if a device-side bound was exceeded during the batch. */
 int kaamer_workspace_finish(kaamer_workspace *ws, void *stream, kaamer_counters *out);
@@ -851,7 +919,9 @@ int32_t kaamer_align_matrix_entry(int32_t a, int32_t b);
 /* request, the operations come back, in the same packed block.  Matrix, gap column  */
 /* and tie rules are kaamer_align_pairs' own (one statement, align.hip); the numbers  */
 /* equal that call's bit for bit.  On one device, and on the one-process sharded       */
-/* handle (below); replicas, kaamer_stream_* and kaamer_search_file have no such form. */
+/* handle (below).  kaamer_stream_open_aln_flat, kaamer_replica_stream_open_aln_flat,   */
+/* kaamer_search_file_opts and the sharded stream / file driver put the same call        */
+/* behind a FIFO and a file reader.                                                       */
 /* ------------------------------------------------------------------------- */
 /* HitEntries (FetchHitsInformation, search.go:454-470) made resident: every entry's stored Protein.Sequence
  * (kaamer_protein_entry.sequence / sequence_len, not the Length clip), its letter codes, a "letter outside the

@@ -329,7 +329,33 @@ SYMBOLS = {
     "kaamer_sharded_submit_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
                                                            C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
                                                            C.POINTER(C.c_void_p)]),
+    # streams and whole-file drivers with the bitmaps / alignments of the reported hits, on all three handle kinds
+    # stream open forms: (handle, seq_type, min_k_ratio, min_k_match, max_results[, want_positions, sub_matrix, gap_open, gap_extend,
+    # want_text], out)
+    "kaamer_stream_open_aln_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32, C.c_char_p, C.c_int32,
+                                              C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_replicas_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kaamer_replica_stream_open_pos_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_replica_stream_open_aln_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32, C.c_char_p,
+                                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_sharded_stream_open_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_sharded_stream_open_pos_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_sharded_stream_open_aln_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32, C.c_char_p,
+                                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_sharded_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kaamer_sharded_stream_pop": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kaamer_sharded_stream_pending": (C.c_uint32, [C.c_void_p]),
+    "kaamer_sharded_stream_close": (None, [C.c_void_p]),
+    # (handle, path, format, strict_scanner, seq_type, min_k_ratio, min_k_match, max_results, want_positions, want_aln, sub_matrix,
+    #  gap_open, gap_extend, want_text, chunk_seqs, chunk_bytes, in_flight, cb, user, total)
+    "kaamer_search_file_opts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                          C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    "kaamer_sharded_search_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                             C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 }
+SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 
 _lib = None
 

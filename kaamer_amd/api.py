@@ -499,8 +499,9 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
-    def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False):
-        return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions)
+    def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
+        """kaamer_stream_open[_pos|_aln]_flat; align: as search_top's (needs attach_proteins)"""
+        return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions, align)
 
     def attach_proteins(self, proteins):
         """kaamer_index_attach_proteins: the table's Protein.Sequence entries become resident next to the index (the
@@ -674,6 +675,16 @@ class ShardedIndex:
                                                              len(offs) - 1, seq_type, int(want_positions), C.byref(t)))
         return FullTicket(t, sharded=True)
 
+    def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
+        """kaamer_sharded_stream_open[_pos|_aln]_flat: a FIFO of at most abi.SHARDED_SETS chunks on the handle"""
+        return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions, align)
+
+    def search_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
+                    chunk_seqs=1 << 20, chunk_bytes=1 << 28, in_flight=0, strict=False, on_chunk=None, want_positions=False, align=None):
+        """kaamer_sharded_search_file: Replicas.search_file on the sharded handle (in_flight: chunks per handle)"""
+        return _search_file(abi.lib().kaamer_sharded_search_file, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
+                            chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, want_positions, align)
+
     def exchange_info(self):
         """-> dict(block_bytes, need_entries, queries, adaptive) of the last finished call on the handle's first set"""
         out = (C.c_uint64 * 4)()
@@ -700,6 +711,7 @@ class Replicas:
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
+        self.proteins = None   # attach_proteins
 
     @classmethod
     def from_image(cls, image, devices):
@@ -718,28 +730,27 @@ class Replicas:
     def __len__(self):
         return int(abi.lib().kaamer_replicas_count(self._h))
 
-    def search_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
-                    chunk_seqs=1 << 20, chunk_bytes=1 << 28, in_flight=0, strict=False, on_chunk=None):
-        """kaamer_search_file.  on_chunk(first_seq, reads_handle, TopResult) per chunk, in input order (the reads handle is
-        valid during the call: kaamer_reads_* accessors / api._reads_to_arrays).  -> summed counters"""
-        err = []
+    def attach_proteins(self, proteins):
+        """kaamer_replicas_attach_proteins: Index.attach_proteins on every replica (the subjects of search_file(align=...)
+        and stream(align=...)).  The table is borrowed by the library: the set keeps it alive."""
+        abi.check(abi.lib().kaamer_replicas_attach_proteins(self._h, proteins._h))
+        self.proteins = proteins
 
-        def cb(user, first, reads, top):
-            try:
-                if on_chunk is not None:
-                    on_chunk(int(first), C.c_void_p(reads), TopResult(top))
-                return 0
-            except BaseException as e:  # noqa: BLE001  (must not propagate through the C frames)
-                err.append(e)
-                return 1
-        c = abi.Counters()
-        fn = self.CHUNK_CB(cb)
-        rc = abi.lib().kaamer_search_file(self._h, str(path).encode(), 1 if fmt == "fastq" else 0, int(strict), seq_type, min_k_ratio,
-                                          min_k_match, max_results, chunk_seqs, chunk_bytes, in_flight, C.cast(fn, C.c_void_p), None, C.byref(c))
-        if err:
-            raise err[0]
-        abi.check(rc)
-        return c.as_dict()
+    def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
+        """kaamer_replica_stream_open[_pos|_aln]_flat: chunk k goes to replica k mod n, pop returns them in push order"""
+        return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions, align)
+
+    def search_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
+                    chunk_seqs=1 << 20, chunk_bytes=1 << 28, in_flight=0, strict=False, on_chunk=None, want_positions=False, align=None):
+        """kaamer_search_file.  on_chunk(first_seq, reads_handle, TopResult) per chunk, in input order (the reads handle is
+        valid during the call: kaamer_reads_* accessors / api._reads_to_arrays).  -> summed counters
+        want_positions / align (as Index.search_top's; align needs attach_proteins): kaamer_search_file_opts -- the
+        TopResult of every chunk carries the bitmaps / the alignments of its reported hits."""
+        if not want_positions and align is None:
+            return _search_file(abi.lib().kaamer_search_file, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
+                                chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, None, None)
+        return _search_file(abi.lib().kaamer_search_file_opts, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
+                            chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, want_positions, align)
 
     def close(self):
         if self._h:
@@ -751,6 +762,41 @@ class Replicas:
             self.close()
         except Exception:
             pass
+
+
+def _align_args(align):
+    """(sub_matrix, gap_open, gap_extend, want_text) of an `align` dict (Index.search_top)"""
+    return (str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)), int(align.get("gap_extend", 1)),
+            int(bool(align.get("text", True))))
+
+
+def _search_file(fn, handle, path, fmt, seq_type, min_k_ratio, min_k_match, max_results, chunk_seqs, chunk_bytes, in_flight, strict, on_chunk,
+                 want_positions, align):
+    """the three whole-file calls behind one callback wrapper; want_positions is None for kaamer_search_file, which has no
+    such arguments"""
+    err = []
+
+    def cb(user, first, reads, top):
+        try:
+            if on_chunk is not None:
+                on_chunk(int(first), C.c_void_p(reads), TopResult(top))
+            return 0
+        except BaseException as e:  # noqa: BLE001  (must not propagate through the C frames)
+            err.append(e)
+            return 1
+    c = abi.Counters()
+    cfn = Replicas.CHUNK_CB(cb)
+    head = (handle, str(path).encode(), 1 if fmt == "fastq" else 0, int(strict), seq_type, min_k_ratio, min_k_match, max_results)
+    tail = (chunk_seqs, chunk_bytes, in_flight, C.cast(cfn, C.c_void_p), None, C.byref(c))
+    if want_positions is None:
+        rc = fn(*(head + tail))
+    else:
+        aln = _align_args(align) if align is not None else (None, 0, 0, 0)
+        rc = fn(*(head + (int(bool(want_positions)), int(align is not None)) + aln + tail))
+    if err:
+        raise err[0]
+    abi.check(rc)
+    return c.as_dict()
 
 
 class FullTicket:
@@ -811,22 +857,31 @@ class TopTicket:
 
 
 class TopStream:
-    """kaamer_stream_*: a FIFO of batches with fixed options (push chunk i + 1 while chunk i is searched)"""
+    """kaamer_stream_* / kaamer_replica_stream_* / kaamer_sharded_stream_*: a FIFO of batches with fixed options (push
+    chunk i + 1 while chunk i is searched) on an Index, a Replicas set or a ShardedIndex"""
 
-    def __init__(self, index, seq_type, min_k_ratio, min_k_match, max_results, want_positions=False):
-        to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
+    def __init__(self, index, seq_type, min_k_ratio, min_k_match, max_results, want_positions=False, align=None):
+        L = abi.lib()
+        kind = "sharded_stream" if isinstance(index, ShardedIndex) else "replica_stream" if isinstance(index, Replicas) else "stream"
+        self._fn = {k: getattr(L, "kaamer_%s_%s" % (kind, k)) for k in ("push", "pop", "pending", "close")}
         h = C.c_void_p()
-        if want_positions:
-            abi.check(abi.lib().kaamer_stream_open_pos_flat(index._h, seq_type, min_k_ratio, min_k_match, max_results, C.byref(h)))
+        if align is not None:
+            abi.check(getattr(L, "kaamer_%s_open_aln_flat" % kind)(index._h, seq_type, min_k_ratio, min_k_match, max_results,
+                                                                   int(bool(want_positions)), *(_align_args(align) + (C.byref(h),))))
+        elif want_positions:
+            abi.check(getattr(L, "kaamer_%s_open_pos_flat" % kind)(index._h, seq_type, min_k_ratio, min_k_match, max_results, C.byref(h)))
+        elif kind == "stream":
+            to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
+            abi.check(L.kaamer_stream_open(index._h, seq_type, C.byref(to), C.byref(h)))
         else:
-            abi.check(abi.lib().kaamer_stream_open(index._h, seq_type, C.byref(to), C.byref(h)))
+            abi.check(getattr(L, "kaamer_%s_open_flat" % kind)(index._h, seq_type, min_k_ratio, min_k_match, max_results, C.byref(h)))
         self._h, self.index = h, index
 
     def push(self, buf, offs):
-        """-> False when every slot is busy with this stream's own chunks (pop first), True when the chunk was taken"""
+        """-> False when every slot (set) is busy with this stream's own chunks (pop first), True when the chunk was taken"""
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        rc = abi.lib().kaamer_stream_push(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1)
+        rc = self._fn["push"](self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1)
         if rc == abi.E_BUSY:
             return False
         abi.check(rc)
@@ -834,7 +889,7 @@ class TopStream:
 
     def pop(self):
         out = C.POINTER(abi.BatchTop)()
-        abi.check(abi.lib().kaamer_stream_pop(self._h, C.byref(out)))
+        abi.check(self._fn["pop"](self._h, C.byref(out)))
         try:
             return TopResult(out)
         finally:
@@ -842,11 +897,11 @@ class TopStream:
 
     @property
     def pending(self):
-        return int(abi.lib().kaamer_stream_pending(self._h))
+        return int(self._fn["pending"](self._h))
 
     def close(self):
         if self._h:
-            abi.lib().kaamer_stream_close(self._h)
+            self._fn["close"](self._h)
             self._h = None
 
     def __del__(self):

@@ -72,8 +72,19 @@ void kaamer_replica_stream_close(kaamer_replica_stream *rs)
     delete rs;
 }
 
-int kaamer_replica_stream_open_flat(kaamer_replicas *r, int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
-                                    kaamer_replica_stream **out)
+// the fixed options of a stream, in the three forms the ABI has: plain, with the bitmaps, with the alignments
+struct StreamForm {
+    int32_t seq_type;
+    double min_k_ratio;
+    int64_t min_k_match;
+    uint32_t max_results;
+    int32_t want_positions, want_aln;
+    const char *sub_matrix;   // want_aln only
+    int32_t gap_open, gap_extend, want_text;
+};
+
+// one kaamer_stream per replica
+static int replica_stream_open_form(kaamer_replicas *r, const StreamForm &f, kaamer_replica_stream **out)
 {
     if (!r || !r->ix || !out) return kaamer_fail(KAAMER_E_ARG, "replica_stream_open: bad argument");
     *out = nullptr;
@@ -82,10 +93,57 @@ int kaamer_replica_stream_open_flat(kaamer_replicas *r, int32_t seq_type, double
     rs->st = new (std::nothrow) std::vector<kaamer_stream *>(r->ix->size(), nullptr);
     if (!rs->st) { delete rs; return kaamer_fail(KAAMER_E_NOMEM, "replica stream"); }
     for (size_t i = 0; i < r->ix->size(); i++) {
-        const int rc = kaamer_stream_open_flat((*r->ix)[i], seq_type, min_k_ratio, min_k_match, max_results, &(*rs->st)[i]);
+        kaamer_index *ix = (*r->ix)[i];
+        kaamer_stream **st = &(*rs->st)[i];
+        int rc;
+        if (f.want_aln) rc = kaamer_stream_open_aln_flat(ix, f.seq_type, f.min_k_ratio, f.min_k_match, f.max_results, f.want_positions, f.sub_matrix,
+                                                         f.gap_open, f.gap_extend, f.want_text, st);
+        else if (f.want_positions) rc = kaamer_stream_open_pos_flat(ix, f.seq_type, f.min_k_ratio, f.min_k_match, f.max_results, st);
+        else rc = kaamer_stream_open_flat(ix, f.seq_type, f.min_k_ratio, f.min_k_match, f.max_results, st);
         if (rc) { kaamer_replica_stream_close(rs); return rc; }
     }
     *out = rs;
+    return KAAMER_OK;
+}
+
+int kaamer_replica_stream_open_flat(kaamer_replicas *r, int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                    kaamer_replica_stream **out)
+{
+    const StreamForm f = { seq_type, min_k_ratio, min_k_match, max_results, 0, 0, nullptr, 0, 0, 0 };
+    return replica_stream_open_form(r, f, out);
+}
+
+// the chunks' results carry the bitmaps of the reported hits (kaamer_stream_open_pos_flat on every replica)
+int kaamer_replica_stream_open_pos_flat(kaamer_replicas *r, int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                        kaamer_replica_stream **out)
+{
+    const StreamForm f = { seq_type, min_k_ratio, min_k_match, max_results, 1, 0, nullptr, 0, 0, 0 };
+    return replica_stream_open_form(r, f, out);
+}
+
+// ... and the alignments (kaamer_stream_open_aln_flat on every replica: KAAMER_E_ARG unless each has its table,
+// kaamer_replicas_attach_proteins)
+int kaamer_replica_stream_open_aln_flat(kaamer_replicas *r, int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                        int32_t want_positions, const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text,
+                                        kaamer_replica_stream **out)
+{
+    const StreamForm f = { seq_type, min_k_ratio, min_k_match, max_results, want_positions, 1, sub_matrix, gap_open, gap_extend, want_text };
+    return replica_stream_open_form(r, f, out);
+}
+
+// kaamer_index_attach_proteins on every replica (HitEntries next to every copy of the index, search.go:454-470); a failure
+// on replica i is reported as such and leaves replicas 0 .. i-1 attached
+int kaamer_replicas_attach_proteins(kaamer_replicas *r, const kaamer_proteins *p)
+{
+    if (!r || !r->ix || !p) return kaamer_fail(KAAMER_E_ARG, "replicas_attach_proteins: bad argument");
+    for (size_t i = 0; i < r->ix->size(); i++) {
+        const int rc = kaamer_index_attach_proteins((*r->ix)[i], p);
+        if (rc) {
+            char why[400];
+            snprintf(why, sizeof why, "%s", kaamer_last_error());
+            return kaamer_fail(rc, "replicas_attach_proteins: replica %zu of %zu: %s", i, r->ix->size(), why);
+        }
+    }
     return KAAMER_OK;
 }
 
@@ -112,29 +170,28 @@ uint32_t kaamer_replica_stream_pending(const kaamer_replica_stream *rs) { return
 
 // ---- FastqSearch / ProteinSearch over a FILE of any size (search_fastq.go:60-136: reader goroutine -> queryChan ->
 // worker goroutines -> result writer): chunks of at most chunk_seqs records / about chunk_bytes of sequence, up to
-// `in_flight` chunks per replica in flight, the callback once per chunk, in input order, with the chunk's records
-// (names, sequences: what QueryResultHandler needs next to the hits) and its reported hits.  first_seq = index of the
-// chunk's first record in the file.  A non-zero return of the callback ends the run with KAAMER_E_ARG.
-int kaamer_search_file(kaamer_replicas *r, const char *path, int format, int strict_scanner, int32_t seq_type, double min_k_ratio,
-                       int64_t min_k_match, uint32_t max_results, uint32_t chunk_seqs, uint64_t chunk_bytes, uint32_t in_flight,
-                       kaamer_chunk_cb cb, void *user, kaamer_counters *total)
+// max_pending chunks in flight, the callback once per chunk, in input order, with the chunk's records (names, sequences:
+// what QueryResultHandler needs next to the hits) and its reported hits.  first_seq = index of the chunk's first record in
+// the file.  A non-zero return of the callback ends the run with KAAMER_E_ARG.
+// The loop is written once, over what it needs of a FIFO of chunks: a replica stream or a sharded stream.
+struct ChunkFifo {
+    void *st;
+    int (*push)(void *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs);   // KAAMER_E_BUSY: pop first
+    int (*pop)(void *st, kaamer_batch_top **out);                                           // a failed chunk is consumed too
+    uint32_t (*pending)(const void *st);
+    uint32_t max_pending;
+};
+
+static int search_file_loop(kaamer_reader *rd, const ChunkFifo &q, uint32_t chunk_seqs, uint64_t chunk_bytes, kaamer_chunk_cb cb, void *user,
+                            kaamer_counters *total)
 {
-    if (!r || !path || chunk_seqs == 0) return kaamer_fail(KAAMER_E_ARG, "search_file: bad argument");
-    if (total) memset(total, 0, sizeof *total);
-    if (in_flight < 1) in_flight = 3;
-    kaamer_reader *rd = nullptr;
-    int rc = kaamer_reader_open(path, format, strict_scanner, &rd);
-    if (rc) return rc;
-    kaamer_replica_stream *rs = nullptr;
-    rc = kaamer_replica_stream_open_flat(r, seq_type, min_k_ratio, min_k_match, max_results, &rs);
-    if (rc) { kaamer_reader_close(rd); return rc; }
-    const uint32_t max_pending = in_flight * kaamer_replicas_count(r);
+    int rc = KAAMER_OK;
     std::vector<kaamer_reads *> fifo;   // the chunks in flight, oldest first (the callback gets the records with the hits)
     std::vector<uint64_t> first;
     uint64_t n_seen = 0;
     auto pop_one = [&]() -> int {
         kaamer_batch_top *top = nullptr;
-        int prc = kaamer_replica_stream_pop(rs, &top);
+        int prc = q.pop(q.st, &top);
         kaamer_reads *chunk = fifo.front();
         const uint64_t f0 = first.front();
         fifo.erase(fifo.begin());
@@ -160,8 +217,8 @@ int kaamer_search_file(kaamer_replicas *r, const char *path, int format, int str
         if (n == 0) { kaamer_reads_free(chunk); continue; }
         for (;;) {
             int prc = KAAMER_E_BUSY;
-            if (kaamer_replica_stream_pending(rs) < max_pending)
-                prc = kaamer_replica_stream_push(rs, kaamer_reads_seqs(chunk), kaamer_reads_offsets(chunk), n);
+            if (q.pending(q.st) < q.max_pending)
+                prc = q.push(q.st, kaamer_reads_seqs(chunk), kaamer_reads_offsets(chunk), n);
             if (prc == KAAMER_OK) break;
             if (prc != KAAMER_E_BUSY || fifo.empty()) { rc = prc; break; }
             rc = pop_one();
@@ -176,7 +233,51 @@ int kaamer_search_file(kaamer_replicas *r, const char *path, int format, int str
         const int prc = pop_one();
         if (!rc) rc = prc;
     }
+    return rc;
+}
+
+static int replica_fifo_push(void *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs)
+{
+    return kaamer_replica_stream_push(static_cast<kaamer_replica_stream *>(st), seqs, offsets, n_seqs);
+}
+static int replica_fifo_pop(void *st, kaamer_batch_top **out) { return kaamer_replica_stream_pop(static_cast<kaamer_replica_stream *>(st), out); }
+static uint32_t replica_fifo_pending(const void *st) { return kaamer_replica_stream_pending(static_cast<const kaamer_replica_stream *>(st)); }
+
+// reader -> stream of form `f` -> loop
+static int search_file_replicas(kaamer_replicas *r, const char *path, int format, int strict_scanner, const StreamForm &f, uint32_t chunk_seqs,
+                                uint64_t chunk_bytes, uint32_t in_flight, kaamer_chunk_cb cb, void *user, kaamer_counters *total)
+{
+    if (!r || !path || chunk_seqs == 0 || (f.want_aln && !f.sub_matrix)) return kaamer_fail(KAAMER_E_ARG, "search_file: bad argument");
+    if (total) memset(total, 0, sizeof *total);
+    if (in_flight < 1) in_flight = 3;
+    kaamer_reader *rd = nullptr;
+    int rc = kaamer_reader_open(path, format, strict_scanner, &rd);
+    if (rc) return rc;
+    kaamer_replica_stream *rs = nullptr;
+    rc = replica_stream_open_form(r, f, &rs);
+    if (rc) { kaamer_reader_close(rd); return rc; }
+    const ChunkFifo q = { rs, replica_fifo_push, replica_fifo_pop, replica_fifo_pending, in_flight * kaamer_replicas_count(r) };
+    rc = search_file_loop(rd, q, chunk_seqs, chunk_bytes, cb, user, total);
     kaamer_replica_stream_close(rs);
     kaamer_reader_close(rd);
     return rc;
+}
+
+int kaamer_search_file(kaamer_replicas *r, const char *path, int format, int strict_scanner, int32_t seq_type, double min_k_ratio,
+                       int64_t min_k_match, uint32_t max_results, uint32_t chunk_seqs, uint64_t chunk_bytes, uint32_t in_flight,
+                       kaamer_chunk_cb cb, void *user, kaamer_counters *total)
+{
+    const StreamForm f = { seq_type, min_k_ratio, min_k_match, max_results, 0, 0, nullptr, 0, 0, 0 };
+    return search_file_replicas(r, path, format, strict_scanner, f, chunk_seqs, chunk_bytes, in_flight, cb, user, total);
+}
+
+// the same with -pos (search.go:416,442-452) and -aln (search.go:483-494): `top` of the callback carries the chunk's bitmaps
+// (kaamer_batch_top_positions) and alignments (kaamer_batch_top_alignments)
+int kaamer_search_file_opts(kaamer_replicas *r, const char *path, int format, int strict_scanner, int32_t seq_type, double min_k_ratio,
+                            int64_t min_k_match, uint32_t max_results, int32_t want_positions, int32_t want_aln, const char *sub_matrix,
+                            int32_t gap_open, int32_t gap_extend, int32_t want_text, uint32_t chunk_seqs, uint64_t chunk_bytes, uint32_t in_flight,
+                            kaamer_chunk_cb cb, void *user, kaamer_counters *total)
+{
+    const StreamForm f = { seq_type, min_k_ratio, min_k_match, max_results, want_positions, want_aln, sub_matrix, gap_open, gap_extend, want_text };
+    return search_file_replicas(r, path, format, strict_scanner, f, chunk_seqs, chunk_bytes, in_flight, cb, user, total);
 }

@@ -88,7 +88,7 @@ struct ShardSet {
     uint64_t sa_us[3] = {0, 0, 0};              // its gather, assemble and alignment stages: the slowest device's, microseconds (timing on)
     uint64_t sa_stage[3] = {0, 0, 0};           // waves, slab bytes, long-subject waves: the largest over the owners
 };
-#define KAAMER_SHARDED_SETS 3   /* calls in flight per handle: the goroutines of search_fastq.go:60-66 against one handle */
+/* KAAMER_SHARDED_SETS (kaamer_hip.h): calls in flight per handle, the goroutines of search_fastq.go:60-66 against one handle */
 
 struct kaamer_sharded_index {
     uint32_t n = 0;
@@ -1066,8 +1066,9 @@ static void tas_first_caps(const kaamer_sharded_index *sx, kaamer_sharded_ticket
     else t->b.aln_cap = ((uint64_t)t->n_seqs / W + 1) * K * sizeof(kaamer_align_pair) + (t->aln.text ? 2 * K * t->seq_bytes / W : 0) + 4096;
 }
 
+// block = false: no waiting for a set (a stream must never wait for a set it holds itself): KAAMER_E_BUSY instead
 static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket *t,
-                          bool top_pos, const TopAlnRequest *aln = nullptr)
+                          bool top_pos, const TopAlnRequest *aln = nullptr, bool block = true)
 {
     ShardSet *set = nullptr;
     {
@@ -1076,6 +1077,7 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
             for (int k = 0; k < KAAMER_SHARDED_SETS && !set; k++)
                 if (!sx->sets[k].busy) set = &sx->sets[k];
             if (set) break;
+            if (!block) return kaamer_fail(KAAMER_E_BUSY, "all %d sets of the handle are busy: wait for / pop an earlier batch first", KAAMER_SHARDED_SETS);
             sx->cv.wait(lock);
         }
         // an aligning call takes its set while the table is there: kaamer_sharded_index_attach_proteins refuses to replace
@@ -1123,14 +1125,14 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
 }
 
 static int sharded_submit_top(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool top_pos, kaamer_sharded_ticket **ticket,
-                              const TopAlnRequest *aln = nullptr)
+                              const TopAlnRequest *aln = nullptr, bool block = true)
 {
     if (!sx || !in || !top || !ticket || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
         return kaamer_fail(KAAMER_E_ARG, "sharded_submit_batch_top: bad argument");
     *ticket = nullptr;
     kaamer_sharded_ticket *t = new (std::nothrow) kaamer_sharded_ticket();
     if (!t) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
-    const int rc = sharded_submit(sx, in, top, t, top_pos, aln);
+    const int rc = sharded_submit(sx, in, top, t, top_pos, aln, block);
     if (rc) { delete t; return rc; }
     *ticket = t;
     return KAAMER_OK;

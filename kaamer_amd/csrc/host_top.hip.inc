@@ -589,6 +589,8 @@ struct kaamer_stream {
     kaamer_topn_opts top;
     std::vector<kaamer_ticket *> *fifo;
     bool want_pos;
+    bool want_aln;       // kaamer_stream_open_aln_flat (host_top_align.hip.inc): every chunk is a TopAlnRequest
+    TopAlnRequest aln;
 };
 static void stream_set_positions(kaamer_stream *st) { st->want_pos = true; }
 
@@ -598,7 +600,7 @@ int kaamer_stream_open(kaamer_index *ix, int32_t seq_type, const kaamer_topn_opt
     *out = nullptr;
     kaamer_stream *st = new (std::nothrow) kaamer_stream();
     if (!st) return kaamer_fail(KAAMER_E_NOMEM, "stream");
-    st->ix = ix; st->seq_type = seq_type; st->top = *top; st->want_pos = false;
+    st->ix = ix; st->seq_type = seq_type; st->top = *top; st->want_pos = false; st->want_aln = false;
     st->fifo = new (std::nothrow) std::vector<kaamer_ticket *>();
     if (!st->fifo) { delete st; return kaamer_fail(KAAMER_E_NOMEM, "stream"); }
     *out = st;
@@ -613,7 +615,7 @@ int kaamer_stream_push(kaamer_stream *st, const uint8_t *seqs, const uint64_t *o
     in.seqs = seqs; in.offsets = offsets; in.n_seqs = n_seqs; in.seq_type = st->seq_type;
     kaamer_ticket *t = nullptr;
     // never block on a slot this stream itself holds: when every slot is busy the caller pops first
-    const int rc = top_submit(st->ix, &in, &st->top, st->fifo->empty(), &t, st->want_pos);
+    const int rc = top_submit(st->ix, &in, &st->top, st->fifo->empty(), &t, st->want_pos, st->want_aln ? &st->aln : nullptr);
     if (rc) return rc;
     st->fifo->push_back(t);
     return KAAMER_OK;

@@ -384,6 +384,23 @@ int kaamer_search_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, cons
     return kaamer_wait_batch_top(t, out);
 }
 
+// kaamer_stream_* with the alignment of every reported hit (FastqSearch / ProteinSearch with -aln over chunks,
+// search_fastq.go:60-136 + search.go:483-494): a push goes the way kaamer_submit_batch_top_aln_flat goes
+int kaamer_stream_open_aln_flat(kaamer_index *ix, int32_t seq_type, double min_k_ratio, int64_t min_k_match, uint32_t max_results,
+                                int32_t want_positions, const char *sub_matrix, int32_t gap_open, int32_t gap_extend, int32_t want_text,
+                                kaamer_stream **out)
+{
+    if (!ix || !sub_matrix || !out) return kaamer_fail(KAAMER_E_ARG, "stream_open_aln: bad argument");
+    *out = nullptr;
+    if (!ix->d_aln_raw) return kaamer_fail(KAAMER_E_ARG, "stream_open_aln: no protein table is attached to the index (kaamer_index_attach_proteins)");
+    const int rc = kaamer_stream_open_flat(ix, seq_type, min_k_ratio, min_k_match, max_results, out);
+    if (rc) return rc;
+    (*out)->want_pos = want_positions != 0;
+    (*out)->want_aln = true;
+    (*out)->aln = top_aln_request(sub_matrix, gap_open, gap_extend, want_text);
+    return KAAMER_OK;
+}
+
 int kaamer_batch_top_alignments(const kaamer_batch_top *out, const kaamer_alignment **items, const char **text)
 {
     if (items) *items = nullptr;

@@ -3524,6 +3524,7 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 #include "host_top_align.hip.inc"
 #include "host_sharded.hip.inc"
 #include "host_replicas.hip.inc"
+#include "host_sharded_stream.hip.inc"
 
 void kaamer_batch_free(kaamer_batch_out *out)
 {

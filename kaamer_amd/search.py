@@ -10,6 +10,8 @@ alignment of the reported hits runs inside the same call (kaamer_search_batch_to
 is the one below: FetchHitsInformation, then AlignHits.
 """
 import ctypes as C
+import queue
+import threading
 from dataclasses import dataclass
 
 import numpy as np
@@ -30,6 +32,8 @@ class SearchOptions:  # search.go:56-71 (the fields the hot path reads); default
     SubMatrix: str = "blosum62"   # api/server.go:149-151
     GapOpen: int = 11
     GapExtend: int = 1
+    ChunkSeqs: int = 1 << 20      # SearchFile only (no reference counterpart): records per chunk, chunks in flight (0: three)
+    InFlight: int = 0
 
 
 _EMPTY_ALN = {"Identity": 0.0, "Similarity": 0.0, "Length": 0, "Mismatches": 0, "GapOpenings": 0, "Raw": 0, "BitScore": 0.0,
@@ -182,6 +186,99 @@ def NucleotideSearch(index, fasta_text, options=None):
     for qr in out:
         qr["Query"]["Contig"] = qr["Query"]["Name"]  # search.go:305-306
     return out
+
+
+def _chunk_results(top, recs, o, seq_type, proteins, aligned):
+    """the QueryResult dicts of one chunk's TopResult, shaped as ProteinSearch / _orf_results shape theirs; recs: the
+    chunk's records (seq, name, size, plus).  PositionHits, when the block carries bitmaps, are those of the reported hits:
+    what the reference prints (search.go:520-522,540-543,591-594); for an ORF over the SizeInKmer as searched."""
+    out = []
+    for i in range(top.n_reported):
+        a, b = int(top.top_off[i]), int(top.top_off[i + 1])
+        if seq_type == abi.PROTEIN:
+            q = recs[int(top.rep_query[i])]
+            query = {"Sequence": q["seq"], "Name": q["name"], "SizeInKmer": q["size"], "Type": PROTEIN_QUERY,
+                     "Location": {"StartPosition": 1, "EndPosition": len(q["seq"]), "PlusStrand": q["plus"], "StartsAlternative": []},
+                     "Contig": ""}
+        else:
+            m = top.meta[i]
+            aa = bytes(top.orf_aa[int(m["aa_off"]):int(m["aa_off"]) + int(m["aa_len"])])  # already trimmed
+            name = recs[int(m["src_seq"])]["name"]
+            query = {"Sequence": aa.decode("latin-1"), "Name": name, "SizeInKmer": int(m["size_in_kmer"]), "Type": DNA_QUERY,
+                     "Location": {"StartPosition": int(m["start_position"]), "EndPosition": int(m["end_position"]),
+                                  "PlusStrand": bool(m["plus_strand"]), "StartsAlternative": []},
+                     "Contig": name if seq_type == abi.NUCLEOTIDE else ""}  # search.go:305-306
+        qr = {"Query": query,
+              "SearchResults": {"Hits": [{"Key": int(p), "Kmatch": int(k)} for p, k in zip(top.top_pid[a:b], top.top_kmatch[a:b])]}}
+        if top.pos_bits is not None:
+            qr["SearchResults"]["PositionHits"] = {p: bits.tolist() for p, bits in top.positions(i).items()}
+        if aligned:
+            _with_alignments(qr, top, i, proteins)
+        out.append(qr)
+    return out
+
+
+class _ConsumerGone(Exception):
+    """SearchFile's generator was closed before the file ended"""
+
+
+def SearchFile(handle, path, options=None, fmt=None):
+    """FastqSearch / ProteinSearch / NucleotideSearch (search_fastq.go:60-136, search_protein.go:40-118,
+    search_nucleotide.go:27-160) over a FILE of any size (gzip included) on an api.Replicas set or an api.ShardedIndex: a
+    generator of QueryResult dicts in file order, shaped as the text drivers above shape theirs (options.SequenceType
+    picks which; fmt: "fastq" / "fasta", default by SequenceType).  The file goes through kaamer_search_file_opts /
+    kaamer_sharded_search_file on a worker thread, a chunk at a time (options.ChunkSeqs records, default 1 << 20); at most
+    two converted chunks wait for the consumer.  ExtractPositions: PositionHits of the reported hits, from the block's
+    bitmaps.  Align with a table attached to the handle: HitEntries and every hit's Alignment, hits in BitScore order."""
+    o = options or SearchOptions(SequenceType=abi.READS)
+    seq_type = o.SequenceType
+    fmt = fmt or ("fastq" if seq_type == abi.READS else "fasta")
+    aln = _one_call(handle, o)
+    done, stop = object(), threading.Event()
+    q = queue.Queue(maxsize=2)
+
+    def put(item):
+        while not stop.is_set():
+            try:
+                q.put(item, timeout=0.1)
+                return
+            except queue.Full:
+                pass
+        raise _ConsumerGone()
+
+    def on_chunk(first, reads_h, top):
+        seqs, offs, size, names, noff, plus = api._reads_to_arrays(reads_h)
+        sb = bytes(seqs)
+        recs = [dict(seq=sb[int(offs[i]):int(offs[i + 1])].decode("latin-1"), name=names[int(noff[i]):int(noff[i + 1])].decode("latin-1"),
+                     size=int(size[i]), plus=bool(plus[i])) for i in range(len(size))]
+        put(_chunk_results(top, recs, o, seq_type, getattr(handle, "proteins", None), aln is not None))
+
+    def work():
+        try:
+            handle.search_file(path, fmt, seq_type=seq_type, min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
+                               chunk_seqs=int(getattr(o, "ChunkSeqs", 1 << 20)), in_flight=int(getattr(o, "InFlight", 0)), on_chunk=on_chunk,
+                               want_positions=bool(o.ExtractPositions), align=aln)
+            put(done)
+        except BaseException as e:  # noqa: BLE001  (handed to the consumer)
+            if not stop.is_set():
+                try:
+                    put(e)
+                except _ConsumerGone:
+                    pass
+
+    th = threading.Thread(target=work, daemon=True)
+    th.start()
+    try:
+        while True:
+            item = q.get()
+            if item is done:
+                return
+            if isinstance(item, BaseException):
+                raise item
+            yield from item
+    finally:
+        stop.set()   # (a consumer that leaves early: the callback stops the run at the next chunk)
+        th.join()
 
 
 def FetchHitsInformation(query_results, proteins):

@@ -1,7 +1,7 @@
 """Host-resident batches larger than one device batch (BASELINE configs[4]: reads streamed
 host -> GPU with double-buffered asynchronous copies).  The packed reads are cut into chunks of
 whole sequences and pushed through the library's streaming entry points (kaamer_stream_open /
-_push / _pop, include/kaamer_hip.h): chunk i + 1 is copied into pinned staging and on to the device
+_push / _pop and their replica and sharded forms, include/kaamer_hip.h): chunk i + 1 is copied into pinned staging and on to the device
 while chunk i is searched, and only what a caller reports comes back -- per ORF the hits that survive
 the device post-steps.  This module is a thin ctypes caller: chunking and result bookkeeping only."""
 import numpy as np
@@ -27,12 +27,14 @@ def chunk_bounds(offsets, max_seqs, max_bytes):
 
 class StreamingSearcher:
     def __init__(self, index, max_chunk_seqs, max_chunk_bytes, seq_type=abi.READS, n_buffers=2,
-                 min_k_ratio=0.05, min_k_match=10, max_results=10):
-        """n_buffers: chunks kept in flight (the library holds KAAMER_HOST_SLOTS slots, default 4)"""
+                 min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
+        """index: an api.Index, api.Replicas or api.ShardedIndex (kaamer_stream_* / kaamer_replica_stream_* /
+        kaamer_sharded_stream_*).  n_buffers: chunks kept in flight (the library holds KAAMER_HOST_SLOTS slots per index,
+        default 4, and KAAMER_SHARDED_SETS = 3 sets per sharded handle).  want_positions / align: as Index.stream's."""
         self.index, self.seq_type = index, seq_type
         self.max_seqs, self.max_bytes, self.k = max_chunk_seqs, max_chunk_bytes, max_results
         self.n_buffers = max(1, n_buffers)
-        self.stream = index.stream(seq_type, min_k_ratio, min_k_match, max_results)
+        self.stream = index.stream(seq_type, min_k_ratio, min_k_match, max_results, want_positions=want_positions, align=align)
 
     def run(self, buf, offsets, on_chunk=None):
         """Search every sequence of the packed host batch; `on_chunk(first_seq, n_seqs, top)` receives each chunk's
