@@ -13,6 +13,9 @@
 // lengths are, all memory round trips of a group overlap, and one compaction pass serves
 // up to 32 queries.  Counts are exact integers; a table that fills up sends its query to
 // the G tier (count_global_kernel), never a partial result.
+// The steps that turn one window of 64 positions into table adds (the window's query, the list head, the flatten, the run
+// add, the table add) are count_window.hip.inc's, shared with the ORF kernel (count_pack.hip.inc); what is here is the
+// group's own: layout, schedule, descriptors, the window pipelines of the three modes, compaction.
 
 #ifndef GRP_WAVES
 #define GRP_WAVES 8
@@ -33,13 +36,6 @@ static_assert((1u << GRP_SHIFT) == GRP_BUDGET, "GRP_BUDGET must be 1 << GRP_SHIF
 // slots of the arena a cycle can use: tables start at multiples of 64 within a window, none is larger than GRP_MAX_TABLE
 #define GRP_FIT (GRP_BUDGET - 64u + GRP_MAX_TABLE)
 #define GRP_NONE 0xFFFFFFFFu
-#define GRP_MAX_PROBES 96u   /* slots one table add may inspect before the query is handed to the G tier */
-#ifndef GRP_NWIN
-#define GRP_NWIN 1
-#endif
-#ifndef GRP_V2
-#define GRP_V2 1   /* round 4 skeleton: tables cleared by the compaction, compaction by stripes over all waves, no clear phase */
-#endif
 #ifndef GRP_LONG_UNROLL
 #define GRP_LONG_UNROLL 4u  /* chunks of 64 ids per round of the long-list path (registers: the kernel must stay at <= 80) */
 #endif
@@ -465,36 +461,6 @@ __global__ __launch_bounds__(LAY_THREADS) void prep_layout_schedule_kernel(PrepL
     }
 }
 
-// inclusive scan of a wave with DPP row shifts (VALU, ~10 cycles a step) instead of six dependent
-// ds_bpermute round trips (~100 cycles each); rows of 16 lanes, then row_bcast:15 / row_bcast:31
-// carry the row totals (gfx9 DPP controls).
-__device__ __forceinline__ uint32_t wave_inclusive_scan_dpp(uint32_t v)
-{
-#define KH_DPP_ADD(ctrl, rmask) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xf, false)
-    KH_DPP_ADD(0x111, 0xf);  // row_shr:1
-    KH_DPP_ADD(0x112, 0xf);  // row_shr:2
-    KH_DPP_ADD(0x114, 0xf);  // row_shr:4
-    KH_DPP_ADD(0x118, 0xf);  // row_shr:8
-    KH_DPP_ADD(0x142, 0xa);  // row_bcast:15 -> rows 1 and 3
-    KH_DPP_ADD(0x143, 0xc);  // row_bcast:31 -> rows 2 and 3
-#undef KH_DPP_ADD
-    return v;
-}
-
-// inclusive max-scan over the wave, same DPP steps (0 is the identity: lanes without a source read 0)
-__device__ __forceinline__ uint32_t wave_inclusive_max_dpp(uint32_t v)
-{
-#define KH_DPP_MAX(ctrl, rmask) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xf, false); v = v > t_ ? v : t_; }
-    KH_DPP_MAX(0x111, 0xf);  // row_shr:1
-    KH_DPP_MAX(0x112, 0xf);  // row_shr:2
-    KH_DPP_MAX(0x114, 0xf);  // row_shr:4
-    KH_DPP_MAX(0x118, 0xf);  // row_shr:8
-    KH_DPP_MAX(0x142, 0xa);  // row_bcast:15 -> rows 1 and 3
-    KH_DPP_MAX(0x143, 0xc);  // row_bcast:31 -> rows 2 and 3
-#undef KH_DPP_MAX
-    return v;
-}
-
 #ifdef KAAMER_PHASE_CLOCK  /* measurement build only (tools/phase_clock.sh): where a group's time goes, in 10 ns ticks */
 __device__ unsigned long long g_phase_clock[2048][16];  // per workgroup: summed on the host (global atomics would serialise)
 #define PHASE_T() wall_clock64()
@@ -514,7 +480,6 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
     constexpr uint32_t UQMAX = 2u * GRP_QMAX;   // queries of a unit
     constexpr uint32_t FIT = GRP_FIT;           // slots of the arena
     static_assert(UQMAX <= 256 && FIT <= 65535u, "query indices are bytes, table offsets 16-bit");
-    constexpr int NWIN = GRP_NWIN;
     constexpr int XIT = 2;
     __shared__ uint32_t a_keys[FIT];
     __shared__ uint32_t a_cnt[FIT];
@@ -531,13 +496,16 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
     __shared__ unsigned long long g_base[MODE == 1 ? UQMAX : 1];  // MODE 1: first bitmap word of the query
     __shared__ uint64_t g_aa[UQMAX];
     __shared__ uint32_t s_splitq;   // the unit's tables do not fit the arena: the first query of its second part (GRP_NONE: none)
-    __shared__ uint32_t s_pref[WAVES][NWIN * 64];
-    __shared__ uint8_t s_own[WAVES][XIT * 64];
+    constexpr bool FLATTENS = MODE != 2;   // (the merge adds one entry per position)
+    __shared__ uint32_t s_pref[FLATTENS ? WAVES : 1][FLATTENS ? 64 : 1];
+    __shared__ uint8_t s_own[FLATTENS ? WAVES : 1][FLATTENS ? XIT * 64 : 1];
     __shared__ uint32_t s_nq, s_slots, s_win;
     __shared__ uint8_t s_wq[2 * 64];  // query of the first position of every window
     __shared__ uint8_t s_sq[FIT / 64];  // query whose table holds 64-slot stripe s of the arena
     __shared__ uint32_t g_hits[UQMAX];    // distinct ids packed so far, per query (stripes are packed by any wave)
-    constexpr bool V2 = GRP_V2 != 0 && MODE != 1;
+    // the tables start clean and every compaction leaves the stripes it packs clean again: no clear phase (and no barrier
+    // after it) per group.  The positions pass does not compact: it clears the tables it fills.
+    constexpr bool TABLES_LEFT_CLEAN = MODE != 1;
     __shared__ unsigned long long s_efirst;  // E of the group's first table = first hit-list entry of the group
     __shared__ unsigned long long s_tot[8];
     enum { T_IN = 0, T_Q, T_POST, T_HITS, T_OVF, T_LISTS, T_LIDS };
@@ -555,11 +523,10 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
     const uint32_t n_groups = *p.d_n_groups;
     const uint32_t nq_total = *p.d_nq;
     if (tid < 8) s_tot[tid] = 0;
-    for (uint32_t i = tid; i < WAVES * XIT * 64; i += 64 * WAVES) (&s_own[0][0])[i] = 0;  // owner marks: clean between windows
+    if (FLATTENS)
+        for (uint32_t i = tid; i < WAVES * XIT * 64; i += 64 * WAVES) (&s_own[0][0])[i] = 0;  // owner marks: clean between windows
 
-    if (V2) {
-        // the tables start clean and every compaction leaves the stripes it packs clean again: no clear phase (and no
-        // barrier after it) per group
+    if (TABLES_LEFT_CLEAN) {
         for (uint32_t i = tid; i < FIT; i += 64 * WAVES) {
             a_keys[i] = KH_EMPTY_PID;
             a_cnt[i] = PACKED ? 0xFFFF0000u : 0u;
@@ -630,7 +597,7 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
             pc_t = t;
         }
 #endif
-        if (V2 && have_prev) {
+        if (TABLES_LEFT_CLEAN && have_prev) {
             if (wv == 0) epilogue();
             have_prev = false;
         }
@@ -690,7 +657,7 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
                             g_ovf[idx] = (PACKED && qi.size >= 65535) ? 1u : 0u;  // 16-bit counts and positions
                             g_pref[idx] = lo;
                             for (uint32_t w = (lo + 63u) >> 6; (w << 6) < hi && w < 128u; w++) s_wq[w] = (uint8_t)idx;
-                            if (V2) {
+                            if (TABLES_LEFT_CLEAN) {
                                 g_hits[idx] = 0u;
                                 for (uint32_t st = tab >> 6; st < ((tab + qi.slots) >> 6) && st < FIT / 64; st++) s_sq[st] = (uint8_t)idx;
                             }
@@ -729,7 +696,7 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
                 s_nq = d.nq;
                 s_slots = d.slots;
                 s_splitq = splitq;
-                if (V2 && MODE == 0) { s_tot[T_Q] += d.nq; s_tot[T_IN] += (unsigned long long)d.npos + 6ull * d.nq; }  // (only this lane writes these two)
+                if (TABLES_LEFT_CLEAN && MODE == 0) { s_tot[T_Q] += d.nq; s_tot[T_IN] += (unsigned long long)d.npos + 6ull * d.nq; }  // (only this lane writes these two)
             }
         }
         __syncthreads();
@@ -741,8 +708,8 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
         const uint32_t n_slots = s_slots < FIT ? s_slots : FIT;
         const uint32_t n_posn = g_pref[nq];
 
-        // ---- 2. clear the tables in use (V2: left clean by the previous compaction)
-        if (!V2) {
+        // ---- 2. clear the tables in use
+        if (!TABLES_LEFT_CLEAN) {
             for (uint32_t i = tid; i < n_slots; i += 64 * WAVES) {
                 a_keys[i] = KH_EMPTY_PID;
                 a_cnt[i] = PACKED ? 0xFFFF0000u : 0u;
@@ -764,7 +731,7 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
                 bool ok = true;
                 for (uint32_t i = lane; i < cnt; i += 64) {
                     const uint32_t pid = p.hit_pid[off + i];
-                    uint32_t hh = (uint32_t)(((uint64_t)(pid * 0x9E3779B1u) * cap) >> 32);
+                    uint32_t hh = table_home(pid, cap);
                     bool placed = false;
                     for (uint32_t t = 0; t < cap && !placed; t++) {
                         if (atomicCAS(&a_keys[base_slot + hh], KH_EMPTY_PID, pid) == KH_EMPTY_PID) { a_cnt[base_slot + hh] = i; placed = true; }
@@ -779,292 +746,65 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
             __syncthreads();
         }
 
-        // ---- 3. count: windows of 64 flat positions, software-pipelined per wave.
-        // A window needs three dependent loads: its probe results (vals), the 16-byte list heads,
-        // the ids beyond the three in a head.  Stage A(w+2), B(w+1) and the leftovers of w are issued
-        // in the same iteration, so one memory round trip per iteration is exposed instead of three.
-        uint32_t c_post = 0, c_lists = 0, c_lids = 0;
+        // ---- 3. count: windows of 64 flat positions, software-pipelined per wave (the steps of a window:
+        // count_window.hip.inc).  A window needs three dependent loads: its probe results (vals), the 16-byte list
+        // heads, the ids beyond the three in a head.  Stage A(w+2), B(w+1) and the leftovers of w are issued in the same
+        // iteration, so one memory round trip per iteration is exposed instead of three.
+        // Windows are taken from an LDS counter: a window costs anything from an empty bitmap word to a few hundred ids,
+        // and static striding left waves waiting at the barrier for a fifth of the kernel.  The first two windows of a
+        // wave are static (no round trip).
+        WorkCount work;
         const uint32_t n_win = (n_posn + 63u) >> 6;
-        uint32_t *const pref = s_pref[wv];  // LDS accesses stay ds_* (a generic/volatile pointer becomes FLAT)
-        uint8_t *const own = s_own[wv];
-        struct WinA { uint32_t v, j, ps; uint64_t a; };
-        // stage A: flat position -> (query, position in the query); its probe result
-        auto stage_a = [&](uint32_t w) {
-            WinA r;
-            r.v = 0u; r.j = 0u; r.ps = 0u; r.a = 0;
-            const uint32_t i = (w << 6) + lane;
-            if (w < n_win && i < n_posn) {
-                uint32_t j = 0;  // largest j with g_pref[j] <= i: at or shortly after the window's first
-                if (w < 128u) {
-                    j = s_wq[w];
-                    while (j + 1 < nq && g_pref[j + 1] <= i) j++;
-                } else {  // a group made of one very long query
-#pragma unroll
-                    for (uint32_t sft = UQMAX / 2; sft > 0; sft >>= 1)
-                        if (j + sft < nq && g_pref[j + sft] <= i) j += sft;
-                }
-                r.j = j;
-                r.ps = i - g_pref[j];
-                r.a = g_aa[j] + r.ps;
-                r.v = MODE == 2 ? KH_INLINE_BIT : p.vals[r.a];
-            }
-            return r;
-        };
-        // stage B: inline single id, or the list head {count, id0, id1, id2} from the arena
-        auto stage_b = [&](const WinA &w) {
-            uint4 h = make_uint4(0, 0, 0, 0);
-            if (MODE == 2) { if (w.v) h = make_uint4(1u, p.m_pid[w.a], p.m_km[w.a], FIRSTPOS ? p.m_fp[w.a] : 0u); }
-            else if (w.v & KH_INLINE_BIT) h = make_uint4(1u, w.v & ~KH_INLINE_BIT, 0, 0);
-            else if (w.v != 0u) h = reinterpret_cast<const uint4 *>(p.arena)[w.v];
-            return h;
-        };
+        auto valid_at = [&](uint32_t w) { return w < n_win && ((w << 6) + lane) < n_posn; };
+        auto pos_of = [&](uint32_t w) { return window_pos<UQMAX>(w, (w << 6) + lane, valid_at(w), s_wq, 128u, g_pref, nq); };
+        uint32_t w0 = wv, w1 = wv + WAVES;
+        uint32_t tk = 0;  // ticket in flight for the window after w1
+        if (lane == 0) tk = atomicAdd(&s_win, 1u);
 
-        // table add of this lane's own (query, position)
-        auto add_n = [&](uint32_t j, uint32_t pid, uint32_t pos, uint32_t n) {
-#ifdef KAAMER_ABL_NOADD
-            return;
-#endif
-            const uint32_t base = g_tab[j], cap = g_cap[j];
-            uint32_t hh = (uint32_t)(((uint64_t)(pid * 0x9E3779B1u) * cap) >> 32);
-            if (MODE == 1) {
-                if (g_ovf[j]) return;
-                for (uint32_t t = 0; t < cap; t++) {
-                    const uint32_t kk = __hip_atomic_load(&a_keys[base + hh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (kk == pid) {
-                        const uint32_t words = (g_size[j] + 63u) >> 6;
-                        unsigned long long *bm = p.pos_bits + g_base[j] + (unsigned long long)a_cnt[base + hh] * words;
-                        // positions pos .. pos+n-1 (n <= 64: at most two words)
-                        const uint32_t w0 = pos >> 6, b0 = pos & 63u;
-                        const uint32_t n0 = n < 64u - b0 ? n : 64u - b0;
-                        atomicOr(&bm[w0], (n0 == 64u ? ~0ull : ((1ull << n0) - 1ull)) << b0);
-                        if (n > n0) atomicOr(&bm[w0 + 1], (1ull << (n - n0)) - 1ull);
-                        return;
-                    }
-                    if (kk == KH_EMPTY_PID) return;  // not a hit of this query (cannot happen)
-                    hh = (hh + 1u == cap) ? 0u : hh + 1u;
-                }
-                return;
-            }
-            // At most GRP_MAX_PROBES slots are inspected: a table that crowded is as good as full, and walking all of
-            // a full 4096-slot table for every further id of the query (a query that meets a postings list of
-            // thousands of proteins) cost 170 us per add -- 0.4 s per batch on a skewed database.
-            const uint32_t tmax = cap < GRP_MAX_PROBES ? cap : GRP_MAX_PROBES;
-            for (uint32_t t = 0; t < tmax; t++) {
-#ifdef KAAMER_PROBE_READ_FIRST
-                uint32_t kk = __hip_atomic_load(&a_keys[base + hh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (kk == KH_EMPTY_PID) {
-                    const uint32_t old = atomicCAS(&a_keys[base + hh], KH_EMPTY_PID, pid);
-                    kk = old == KH_EMPTY_PID ? pid : old;
-                }
-#else
-                // ONE LDS round trip per slot inspected: the compare-and-swap is issued whatever the slot holds (it
-                // returns the occupant of a taken slot).  Reading first and swapping only an empty slot is two dependent
-                // round trips whenever any lane of the wave meets an empty slot -- nearly every iteration.
-                const uint32_t old = atomicCAS(&a_keys[base + hh], KH_EMPTY_PID, pid);
-                const uint32_t kk = old == KH_EMPTY_PID ? pid : old;
-#endif
-                if (kk == pid) {
-                    atomicAdd(&a_cnt[base + hh], n);
-                    if (PACKED) {  // the position is lowered rarely (windows are taken in order): a CAS loop
-                        uint32_t old = __hip_atomic_load(&a_cnt[base + hh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        while (pos < (old >> 16)) {
-                            const uint32_t seen = atomicCAS(&a_cnt[base + hh], old, (old & 0xFFFFu) | (pos << 16));
-                            if (seen == old) break;
-                            old = seen;
-                        }
-                    } else if (FIRSTPOS) {
-                        atomicMin(&a_min[base + hh], pos);
-                    }
-                    return;
-                }
-                hh = (hh + 1u == cap) ? 0u : hh + 1u;
-            }
-            g_ovf[j] = 1;  // table full: the query goes to the G tier
-        };
-        // runs of equal (query, id) in adjacent lanes are added once with their length
-        auto add_runs = [&](uint32_t j, uint32_t x, uint32_t pos) {
-            const uint32_t px = __shfl_up(x, 1, 64), pj = __shfl_up(j, 1, 64);
-            const bool change = (lane == 0) || px != x || pj != j;
-            const unsigned long long cm = __ballot(change);
-            if (change && x != KH_EMPTY_PID) {
-                const unsigned long long above = (lane == 63) ? 0ull : (cm >> (lane + 1));
-                const uint32_t len = above ? (uint32_t)__ffsll((long long)above) : 64u - lane;
-                add_n(j, x, pos, len);
-            }
-        };
-        // leftovers + all table adds of one window
-        auto process = [&](const WinA &w, const uint4 &h) {
-            const uint32_t lcnt = h.x;
-            if (MODE == 2) {
-                if (lcnt != 0u) add_n(w.j, h.y, h.w, h.z);  // (id, first position, count)
-                return;
-            }
-            // The first id of every lane is added directly.  All further ids of the window (about
-            // as many again, held by a minority of the lanes) are FLATTENED: item t belongs to the
-            // lane found by binary search in the prefix of (count - 1), so the adds run with dense
-            // lanes instead of once per list slot with a few lanes each.
-            // a postings list longer than the query's table can never fit it: the query goes to the G tier at once
-            // (expanding the list first, 64 ids at a time, only to find the table full was 60 us per window).
-            // A query already on its way there is only counted here (its ids are not expanded again)
-            if (MODE == 0 && lcnt > g_cap[w.j]) g_ovf[w.j] = 1u;
-            const bool dead = lcnt != 0u && g_ovf[w.j] != 0u;
-#ifdef KAAMER_ABL_NOEXTRA  /* timing experiment (tools/abl.sh): wrong results */
-            const uint32_t extra = 0u;
-#else
-            const uint32_t extra = (lcnt > 1u && !dead) ? lcnt - 1u : 0u;
-#endif
-            const uint32_t inc = wave_inclusive_scan_dpp(extra);
-            const uint32_t xtotal = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            uint32_t xid[XIT], xj[XIT], xps[XIT];
-            if (xtotal) {  // wave-uniform
-                pref[lane] = inc - extra;
-                // every owner marks its FIRST item with its lane number + 1; an item's owner is the highest mark at or
-                // before it (owners ascend with the items): one LDS store per owner and a max-scan per 64 items instead
-                // of a store per item in a divergent loop as long as the longest list of the window
-                if (extra != 0u && inc - extra < XIT * 64u) own[inc - extra] = (uint8_t)(lane + 1u);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                uint32_t carry = 0;
-#pragma unroll
-                for (int it = 0; it < XIT; it++) {
-                    xid[it] = KH_EMPTY_PID; xj[it] = 0; xps[it] = 0;
-                    if ((uint32_t)it * 64u >= xtotal) continue;  // wave-uniform
-                    const uint32_t t = (uint32_t)it * 64u + lane;
-                    const bool act = t < xtotal;
-                    uint32_t mk = own[t];
-                    own[t] = 0;  // the marks are left clean for the next window
-                    mk = wave_inclusive_max_dpp(mk > carry ? mk : carry);
-                    carry = (uint32_t)__builtin_amdgcn_readlane((int)mk, 63);
-                    const uint32_t lo = act ? mk - 1u : 0u;
-                    // executed by all lanes: the owner may be a lane that is idle in this round
-                    const uint32_t off = __shfl(w.v, (int)lo, 64);
-                    const uint32_t oz = __shfl(h.z, (int)lo, 64), ow = __shfl(h.w, (int)lo, 64);
-                    xj[it] = __shfl(w.j, (int)lo, 64);
-                    xps[it] = __shfl(w.ps, (int)lo, 64);
-                    if (act) {
-                        const uint32_t k = t - pref[lo];  // item k of the owner = id k+1 of its list
-                        xid[it] = k == 0u ? oz : k == 1u ? ow : p.arena[(uint64_t)off * 4 + 2 + k];
-                    }
-                }
-            }
-            if (lcnt != 0u) {
-                c_post += lcnt;
-                if (!(w.v & KH_INLINE_BIT)) { c_lists++; c_lids += lcnt; }
-            }
-#ifdef KAAMER_NO_RUNS
-            if (lcnt != 0u) add_n(w.j, h.y, w.ps, 1u);
-#else
-            add_runs(w.j, (lcnt > 0 && !dead) ? h.y : KH_EMPTY_PID, w.ps);
-#endif
-            if (xtotal) {
-#pragma unroll
-                for (int it = 0; it < XIT; it++)
-                    if (xid[it] != KH_EMPTY_PID) add_n(xj[it], xid[it], xps[it], 1u);
-                // very many ids in one window: more than XIT*64 beyond the first
-                for (uint32_t t0 = XIT * 64u; t0 < xtotal; t0 += 64) {
-                    const uint32_t t = t0 + lane;
-                    const bool act = t < xtotal;
-                    uint32_t lo = 0;
-                    if (act) {
-#pragma unroll
-                        for (int sft = 32; sft > 0; sft >>= 1)
-                            if (pref[lo + sft] <= t) lo += sft;
-                    }
-                    const uint32_t off = __shfl(w.v, (int)lo, 64);
-                    const uint32_t oz = __shfl(h.z, (int)lo, 64), ow = __shfl(h.w, (int)lo, 64);
-                    const uint32_t oj = __shfl(w.j, (int)lo, 64);
-                    const uint32_t op = __shfl(w.ps, (int)lo, 64);
-                    if (act && !g_ovf[oj]) {  // (a table that has just filled up is not walked again for every further id)
-                        const uint32_t k = t - pref[lo];
-                        add_n(oj, k == 0u ? oz : k == 1u ? ow : p.arena[(uint64_t)off * 4 + 2 + k], op, 1u);
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                __builtin_amdgcn_wave_barrier();  // pref is rewritten by the next window
-            }
-        };
-
-        if (MODE == 0) {
+        if constexpr (MODE == 0) {
             // The search's counting pass.  Every global load of the loop is issued UNCONDITIONALLY (idle lanes read
             // word 0 of their array; the arena's first 16 bytes are zero: "no list") and the probe results and list heads
             // are consumed an ITERATION AFTER they were issued, as raw loop-carried registers: the compiler's
             // s_waitcnt vmcnt(N) then counts exactly.  With the loads inside branches (as MODE 1 / 2 below still have
             // them) every wait of the loop was a vmcnt(0): a window's three dependent loads cost three exposed round
             // trips.  The ids beyond a head's three are loaded before the first ids are added and read after.
-            auto valid_at = [&](uint32_t w) { return w < n_win && ((w << 6) + lane) < n_posn; };
+            uint32_t *const pref = s_pref[wv];  // LDS accesses stay ds_* (a generic/volatile pointer becomes FLAT)
+            uint8_t *const own = s_own[wv];
+            auto add_n = [&](uint32_t j, uint32_t pid, uint32_t pos, uint32_t n) {
+                if constexpr (PACKED) table_add_packed(a_keys, a_cnt, g_tab, g_cap, g_ovf, j, pid, pos, n);
+                else table_add<FIRSTPOS>(a_keys, a_cnt, a_min, g_tab, g_cap, g_ovf, j, pid, pos, n);
+            };
             struct RawA { uint32_t vraw, j, ps; };
             auto issue_a = [&](uint32_t w) {
                 RawA r;
-                const uint32_t i = (w << 6) + lane;
-                const bool valid = w < n_win && i < n_posn;
-                uint32_t j = 0;
-                if (valid) {  // (LDS only)
-                    if (w < 128u) {
-                        j = s_wq[w];
-                        while (j + 1 < nq && g_pref[j + 1] <= i) j++;
-                    } else {
-#pragma unroll
-                        for (uint32_t sft = UQMAX / 2; sft > 0; sft >>= 1)
-                            if (j + sft < nq && g_pref[j + sft] <= i) j += sft;
-                    }
-                }
-                r.j = j;
-                r.ps = valid ? i - g_pref[j] : 0u;
-                r.vraw = p.vals[valid ? g_aa[j] + r.ps : 0ull];
+                const WinPos wp = pos_of(w);
+                r.j = wp.j;
+                r.ps = wp.ps;
+                r.vraw = p.vals[valid_at(w) ? g_aa[wp.j] + wp.ps : 0ull];
                 return r;
             };
-            auto issue_b = [&](uint32_t v) { return reinterpret_cast<const uint4 *>(p.arena)[(v & KH_INLINE_BIT) ? 0u : v]; };
             auto count_window = [&](uint32_t v, uint32_t wj, uint32_t wps, const uint4 &hv) {
-                // the head as the counting sees it: arithmetic on the raw load (a select would let the compiler sink the
-                // load into a branch again)
-                const uint32_t inl = (v & KH_INLINE_BIT) ? 0xFFFFFFFFu : 0u;
-                const uint32_t lcnt = hv.x | (inl & 1u), id0 = hv.y | (inl & v & ~KH_INLINE_BIT);
-                if (lcnt > g_cap[wj] && lcnt != 0u) g_ovf[wj] = 1u;
-                const bool dead = lcnt != 0u && g_ovf[wj] != 0u;
-                if (lcnt != 0u) {
-                    c_post += lcnt;
-                    if (!(v & KH_INLINE_BIT)) { c_lists++; c_lids += lcnt; }
-                }
-                const uint32_t extra = (lcnt > 1u && !dead) ? lcnt - 1u : 0u;
-                const uint32_t inc = wave_inclusive_scan_dpp(extra);
-                const uint32_t xtotal = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-                pref[lane] = inc - extra;
-                if (extra != 0u && inc - extra < XIT * 64u) own[inc - extra] = (uint8_t)(lane + 1u);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                const uint4 h = head_of(v, hv);
+                const LaneList ll = lane_list(h, wj, g_cap, g_ovf);
+                work.list(v, h.x);
+                const XWin xw = {v, h.z, h.w, wj, wps};
+                const uint32_t xtotal = flatten_begin<XIT>(lane, ll.extra, pref, own);
                 uint32_t carry = 0;
-                uint32_t xid[XIT], xld[XIT], xm[XIT], xj[XIT], xps[XIT];
+                XRound x[XIT];
 #pragma unroll
-                for (int it = 0; it < XIT; it++) {
-                    const uint32_t t = (uint32_t)it * 64u + lane;
-                    const bool act = t < xtotal;
-                    uint32_t mk = own[t];
-                    own[t] = 0;  // the marks are left clean for the next window
-                    mk = wave_inclusive_max_dpp(mk > carry ? mk : carry);
-                    carry = (uint32_t)__builtin_amdgcn_readlane((int)mk, 63);
-                    const uint32_t lo = act ? mk - 1u : 0u;
-                    const uint32_t off = __shfl(v, (int)lo, 64);
-                    const uint32_t oz = __shfl(hv.z, (int)lo, 64), ow = __shfl(hv.w, (int)lo, 64);
-                    xj[it] = __shfl(wj, (int)lo, 64);
-                    xps[it] = __shfl(wps, (int)lo, 64);
-                    const uint32_t k = act ? t - pref[lo] : 0u;  // item k of the owner = id k+1 of its list
-                    const bool from_arena = act && k >= 2u;
-                    xld[it] = p.arena[from_arena ? (uint64_t)off * 4 + 2 + k : 0ull];
-                    xm[it] = from_arena ? 0xFFFFFFFFu : 0u;
-                    xid[it] = !act ? KH_EMPTY_PID : k == 0u ? oz : ow;
-                }
+                for (int it = 0; it < XIT; it++) x[it] = flatten_round<true>(lane, (uint32_t)it, xtotal, carry, xw, pref, own, p.arena);
                 // the first ids are added while the loads above are in flight
-                add_runs(wj, (lcnt > 0 && !dead) ? id0 : KH_EMPTY_PID, wps);
+                add_runs(lane, wj, ll.first_id, wps, add_n);
 #pragma unroll
                 for (int it = 0; it < XIT; it++) {
-                    const uint32_t id = (xld[it] & xm[it]) | (xid[it] & ~xm[it]);
-                    if (id != KH_EMPTY_PID) add_n(xj[it], id, xps[it], 1u);
+                    const uint32_t id = xround_id(x[it]);
+                    if (id != KH_EMPTY_PID) add_n(x[it].j, id, x[it].ps, 1u);
                 }
                 if (xtotal > XIT * 64u) {
                     // very many ids in one window (a database with long postings lists: hundreds of ids behind one
                     // position): GRP_LONG_UNROLL chunks of 64 ids per round, their arena loads issued together
                     // (unconditionally, at clamped addresses) before the first add -- one dependent search -> load -> add
-                    // chain per chunk made this path 5 x the cost of the rest on a database with lists of ~1 000
+                    // chain per chunk (flatten_tail) made this path 5 x the cost of the rest on a database with lists of ~1 000
                     for (uint32_t t0 = XIT * 64u; t0 < xtotal; t0 += GRP_LONG_UNROLL * 64u) {
                         uint32_t lid[GRP_LONG_UNROLL], lj[GRP_LONG_UNROLL], lp[GRP_LONG_UNROLL];
 #pragma unroll
@@ -1072,18 +812,14 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
                             const uint32_t t = t0 + (uint32_t)u * 64u + lane;
                             const bool act = t < xtotal;
                             const uint32_t tt = act ? t : xtotal - 1u;
-                            uint32_t lo = 0;
-#pragma unroll
-                            for (int sft = 32; sft > 0; sft >>= 1)
-                                if (pref[lo + sft] <= tt) lo += sft;
-                            const uint32_t off = __shfl(v, (int)lo, 64);
-                            const uint32_t oz = __shfl(hv.z, (int)lo, 64), ow = __shfl(hv.w, (int)lo, 64);
-                            lj[u] = __shfl(wj, (int)lo, 64);
-                            lp[u] = __shfl(wps, (int)lo, 64);
+                            const uint32_t lo = flatten_owner(pref, tt);
+                            const XWin o = xwin_of(xw, lo);
+                            lj[u] = o.j;
+                            lp[u] = o.ps;
                             const uint32_t k = tt - pref[lo];
-                            const uint32_t ld = p.arena[k >= 2u ? (uint64_t)off * 4 + 2 + k : 0ull];
+                            const uint32_t ld = p.arena[k >= 2u ? (uint64_t)o.v * 4 + 2 + k : 0ull];
                             const uint32_t m = k >= 2u ? 0xFFFFFFFFu : 0u;
-                            const uint32_t idr = k == 0u ? oz : ow;
+                            const uint32_t idr = k == 0u ? o.z : o.w;
                             lid[u] = act ? ((ld & m) | (idr & ~m)) : KH_EMPTY_PID;
                         }
 #pragma unroll
@@ -1091,48 +827,116 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
                             if (lid[u] != KH_EMPTY_PID && !g_ovf[lj[u]]) add_n(lj[u], lid[u], lp[u], 1u);
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();  // pref is rewritten by the next window
+                flatten_end();
             };
-            uint32_t w0 = wv, w1 = wv + WAVES;
-            uint32_t tk = 0;  // ticket in flight for the window after w1
-            if (lane == 0) tk = atomicAdd(&s_win, 1u);
             RawA a0 = issue_a(w0), a1 = issue_a(w1);
             uint32_t v0 = valid_at(w0) ? a0.vraw : 0u;
-            uint4 hv0 = issue_b(v0);
-#ifdef KAAMER_ABL_NOCOUNT
-            w0 = n_win;
-#endif
+            uint4 hv0 = issue_head(p.arena, v0);
             while (w0 < n_win) {
                 const uint32_t w2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk) + 2 * WAVES;
                 if (lane == 0) tk = atomicAdd(&s_win, 1u);
                 const RawA a2 = issue_a(w2);
                 const uint32_t v1 = valid_at(w1) ? a1.vraw : 0u;
-                const uint4 hv1 = issue_b(v1);
+                const uint4 hv1 = issue_head(p.arena, v1);
                 count_window(v0, a0.j, a0.ps, hv0);
                 a0 = a1; v0 = v1; hv0 = hv1; a1 = a2;
                 w0 = w1; w1 = w2;
             }
         } else {
-            // windows are taken from an LDS counter: a window costs anything from an empty bitmap
-            // word to a few hundred ids, and static striding left waves waiting at the barrier for
-            // a fifth of the kernel.  The first two windows of a wave are static (no round trip).
-            uint32_t w0 = wv, w1 = wv + WAVES;
-            uint32_t tk = 0;  // ticket in flight for the window after w1
-            if (lane == 0) tk = atomicAdd(&s_win, 1u);
-            WinA a0 = stage_a(w0), a1 = stage_a(w1);
-            uint4 h0 = stage_b(a0);
-#ifdef KAAMER_ABL_NOCOUNT
-            w0 = n_win;
-#endif
-            while (w0 < n_win) {
-                const uint32_t w2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk) + 2 * WAVES;
-                if (lane == 0) tk = atomicAdd(&s_win, 1u);
-                const WinA a2 = stage_a(w2);
-                const uint4 h1 = stage_b(a1);
-                process(a0, h0);
-                a0 = a1; h0 = h1; a1 = a2;
-                w0 = w1; w1 = w2;
+            // MODE 1 and MODE 2: the same loop over their own three steps (loads inside branches: neither is the hot kernel)
+            struct WinA { uint32_t v, j, ps; uint64_t a; };   // v: the lane has a position (MODE 1: its probe result)
+            auto locate = [&](uint32_t w) {  // flat position -> (query, position in the query, index in the batch's arrays)
+                WinA r;
+                const WinPos wp = pos_of(w);
+                r.v = valid_at(w) ? 1u : 0u;
+                r.j = wp.j;
+                r.ps = wp.ps;
+                r.a = r.v ? g_aa[wp.j] + wp.ps : 0ull;
+                return r;
+            };
+            auto window_loop = [&](auto stage_a, auto stage_b, auto step) {
+                WinA a0 = stage_a(w0), a1 = stage_a(w1);
+                uint4 h0 = stage_b(a0);
+                while (w0 < n_win) {
+                    const uint32_t w2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk) + 2 * WAVES;
+                    if (lane == 0) tk = atomicAdd(&s_win, 1u);
+                    const WinA a2 = stage_a(w2);
+                    const uint4 h1 = stage_b(a1);
+                    step(a0, h0);
+                    a0 = a1; h0 = h1; a1 = a2;
+                    w0 = w1; w1 = w2;
+                }
+            };
+            if constexpr (MODE == 1) {
+                // The positions pass: the ids of a window, flattened as in the count, each set the bits of their positions
+                uint32_t *const pref = s_pref[wv];  // LDS accesses stay ds_* (a generic/volatile pointer becomes FLAT)
+                uint8_t *const own = s_own[wv];
+                auto stage_a = [&](uint32_t w) {
+                    WinA r = locate(w);
+                    if (r.v) r.v = p.vals[r.a];
+                    return r;
+                };
+                // inline single id, or the list head {count, id0, id1, id2} from the arena
+                auto stage_b = [&](const WinA &w) {
+                    uint4 h = make_uint4(0, 0, 0, 0);
+                    if (w.v & KH_INLINE_BIT) h = make_uint4(1u, w.v & ~KH_INLINE_BIT, 0, 0);
+                    else if (w.v != 0u) h = reinterpret_cast<const uint4 *>(p.arena)[w.v];
+                    return h;
+                };
+                // positions pos .. pos+n-1 (n <= 64: at most two words) of query j in the bitmap of its hit pid
+                auto set_bits = [&](uint32_t j, uint32_t pid, uint32_t pos, uint32_t n) {
+                    if (g_ovf[j]) return;
+                    const uint32_t base = g_tab[j], cap = g_cap[j];
+                    uint32_t hh = table_home(pid, cap);
+                    for (uint32_t t = 0; t < cap; t++) {
+                        const uint32_t kk = __hip_atomic_load(&a_keys[base + hh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (kk == pid) {
+                            const uint32_t words = (g_size[j] + 63u) >> 6;
+                            unsigned long long *bm = p.pos_bits + g_base[j] + (unsigned long long)a_cnt[base + hh] * words;
+                            const uint32_t w0 = pos >> 6, b0 = pos & 63u;
+                            const uint32_t n0 = n < 64u - b0 ? n : 64u - b0;
+                            atomicOr(&bm[w0], (n0 == 64u ? ~0ull : ((1ull << n0) - 1ull)) << b0);
+                            if (n > n0) atomicOr(&bm[w0 + 1], (1ull << (n - n0)) - 1ull);
+                            return;
+                        }
+                        if (kk == KH_EMPTY_PID) return;  // not a hit of this query (cannot happen)
+                        hh = (hh + 1u == cap) ? 0u : hh + 1u;
+                    }
+                };
+                auto set_bit = [&](uint32_t j, uint32_t pid, uint32_t pos) { set_bits(j, pid, pos, 1u); };
+                auto step = [&](const WinA &w, const uint4 &h) {
+                    const uint32_t lcnt = h.x;
+                    const bool dead = lcnt != 0u && g_ovf[w.j] != 0u;  // (its hit list came from the G tier, and so do its bits)
+                    const XWin xw = {w.v, h.z, h.w, w.j, w.ps};
+                    const uint32_t xtotal = flatten_begin<XIT>(lane, (lcnt > 1u && !dead) ? lcnt - 1u : 0u, pref, own);
+                    uint32_t carry = 0;
+                    XRound x[XIT];
+#pragma unroll
+                    for (int it = 0; it < XIT; it++)
+                        if ((uint32_t)it * 64u < xtotal)  // wave-uniform
+                            x[it] = flatten_round<false>(lane, (uint32_t)it, xtotal, carry, xw, pref, own, p.arena);
+                    add_runs(lane, w.j, (lcnt > 0 && !dead) ? h.y : KH_EMPTY_PID, w.ps, set_bits);
+                    if (xtotal) {  // wave-uniform
+#pragma unroll
+                        for (int it = 0; it < XIT; it++) {
+                            const uint32_t id = xround_id(x[it]);
+                            if (id != KH_EMPTY_PID) set_bit(x[it].j, id, x[it].ps);
+                        }
+                        flatten_tail(lane, XIT * 64u, xtotal, xw, pref, g_ovf, p.arena, set_bit);
+                        flatten_end();
+                    }
+                };
+                window_loop(stage_a, stage_b, step);
+            } else {
+                // The merge: a "position" is one partial entry (id, count, first position), and a window is one add per
+                // entry -- no list head, no flatten
+                auto stage_b = [&](const WinA &w) {
+                    return w.v ? make_uint4(1u, p.m_pid[w.a], p.m_km[w.a], FIRSTPOS ? p.m_fp[w.a] : 0u) : make_uint4(0, 0, 0, 0);
+                };
+                auto step = [&](const WinA &w, const uint4 &h) {
+                    if (h.x != 0u) table_add<FIRSTPOS>(a_keys, a_cnt, a_min, g_tab, g_cap, g_ovf, w.j, h.y, h.w, h.z);  // (id, first position, count)
+                };
+                window_loop(locate, stage_b, step);
             }
         }
 #ifdef KAAMER_PHASE_CLOCK
@@ -1144,8 +948,8 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
             if (wv == 0 && first1 != GRP_NONE && (uint64_t)first1 + lane < nq_total) { pre_qi = p.qinfo[first1 + lane]; pre_e = p.slot_off[first1 + lane]; }
         }
         if (tid == 0) s_ticket = ticket + gridDim.x;
-        if (MODE != 1) {
-            const uint32_t a = wave_total(c_post), b = wave_total(c_lists), c = wave_total(c_lids);
+        if (MODE == 0) {
+            const uint32_t a = wave_total(work.post), b = wave_total(work.lists), c = wave_total(work.lids);
             if (lane == 0) {
                 atomicAdd(&s_tot[T_POST], (unsigned long long)a);
                 atomicAdd(&s_tot[T_LISTS], (unsigned long long)b);
@@ -1170,94 +974,43 @@ __global__ __launch_bounds__(64 * GRP_WAVES) void count_group_kernel(CountParams
         // The list of query q lives at [E[q], E[q] + hits) of the hit arrays -- E is the table
         // layout, a table holds at most its capacity of distinct ids -- so nothing is allocated
         // and no pass has to count first.
-        if (V2) {
-            // a 64-slot stripe per wave and round, whatever query it belongs to (tables are multiples of 64 slots): all
-            // eight waves pack -- a wave per QUERY left half of them idle on a group of three or four queries and the
-            // longest table set the time; the position inside the query's list comes from a counter per query in LDS
-            // (the order of a hit list is free).  The stripe is left clean for the next group.
-            const uint32_t n_str = n_slots >> 6;
-            for (uint32_t st = wv; st < n_str; st += WAVES) {
-                const uint32_t slot = (st << 6) + lane;
-                const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_sq[st]);
-                const uint32_t k = a_keys[slot];
-                const uint32_t w = a_cnt[slot];
-                uint32_t mn = 0;
-                if (FIRSTPOS && !PACKED) { mn = a_min[slot]; a_min[slot] = 0xFFFFFFFFu; }
-                a_keys[slot] = KH_EMPTY_PID;
-                a_cnt[slot] = PACKED ? 0xFFFF0000u : 0u;
-                const unsigned long long base = s_efirst + g_tab[j];
-                const bool usable = g_ovf[j] == 0u && base + g_cap[j] <= p.hit_cap;
-#ifdef KAAMER_ABL_NOCOMPACT
-                const bool has = false;
-#else
-                const bool has = usable && k != KH_EMPTY_PID;
-#endif
-                const unsigned long long bm = __ballot(has);
-                if (bm) {  // wave-uniform
-                    uint32_t off = 0;
-                    if (lane == 0) {
-                        off = atomicAdd(&g_hits[j], (uint32_t)__popcll(bm));
-                        atomicAdd(&s_tot[T_HITS], (unsigned long long)__popcll(bm));
-                    }
-                    off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
-                    if (has) {
-                        const unsigned long long idx = base + off + (uint32_t)__popcll(bm & below);
-                        p.hit_pid[idx] = k;
-                        p.hit_km[idx] = PACKED ? (w & 0xFFFFu) : w;
-                        if (FIRSTPOS) p.hit_fp[idx] = PACKED ? (w >> 16) : mn;
-                    }
+        // a 64-slot stripe per wave and round, whatever query it belongs to (tables are multiples of 64 slots): all
+        // eight waves pack -- a wave per QUERY left half of them idle on a group of three or four queries and the
+        // longest table set the time; the position inside the query's list comes from a counter per query in LDS
+        // (the order of a hit list is free).  The stripe is left clean for the next group.
+        const uint32_t n_str = n_slots >> 6;
+        for (uint32_t st = wv; st < n_str; st += WAVES) {
+            const uint32_t slot = (st << 6) + lane;
+            const uint32_t j = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_sq[st]);
+            const uint32_t k = a_keys[slot];
+            const uint32_t w = a_cnt[slot];
+            uint32_t mn = 0;
+            if (FIRSTPOS && !PACKED) { mn = a_min[slot]; a_min[slot] = 0xFFFFFFFFu; }
+            a_keys[slot] = KH_EMPTY_PID;
+            a_cnt[slot] = PACKED ? 0xFFFF0000u : 0u;
+            const unsigned long long base = s_efirst + g_tab[j];
+            const bool usable = g_ovf[j] == 0u && base + g_cap[j] <= p.hit_cap;
+            const bool has = usable && k != KH_EMPTY_PID;
+            const unsigned long long bm = __ballot(has);
+            if (bm) {  // wave-uniform
+                uint32_t off = 0;
+                if (lane == 0) {
+                    off = atomicAdd(&g_hits[j], (uint32_t)__popcll(bm));
+                    atomicAdd(&s_tot[T_HITS], (unsigned long long)__popcll(bm));
+                }
+                off = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
+                if (has) {
+                    const unsigned long long idx = base + off + (uint32_t)__popcll(bm & below);
+                    p.hit_pid[idx] = k;
+                    p.hit_km[idx] = PACKED ? (w & 0xFFFFu) : w;
+                    if (FIRSTPOS) p.hit_fp[idx] = PACKED ? (w >> 16) : mn;
                 }
             }
-            have_prev = true;
-        } else {
-            uint32_t wave_hits = 0;
-            for (uint32_t j = wv; j < nq; j += WAVES) {
-                const uint32_t q = g_q[j], base_slot = g_tab[j], cap = g_cap[j];
-                if (lane == 0 && MODE == 0) { atomicAdd(&s_tot[T_Q], 1ull); atomicAdd(&s_tot[T_IN], (unsigned long long)g_size[j] + 6ull); }
-                if (g_ovf[j]) {
-                    if (lane == 0) {
-                        atomicAdd(&s_tot[T_OVF], 1ull);
-                        const uint32_t slot = atomicAdd(p.ovf_count, 1u);
-                        WorkItem wi;
-                        wi.q = q; wi.size = (int32_t)g_size[j]; wi.aa_off = g_aa[j];
-                        if (slot < p.list_cap) p.ovf_list[slot] = wi;
-                        else atomicOr(p.status, (uint32_t)ST_LIST_FULL);
-                        p.q_cnt[q] = 0;
-                        p.hit_off[q] = 0;
-                    }
-                    continue;
-                }
-                const unsigned long long base = s_efirst + base_slot;
-                const bool have = base + cap <= p.hit_cap;
-                if (!have && lane == 0) atomicOr(p.status, (uint32_t)ST_POOL_FULL);
-                uint32_t running = 0;
-#ifdef KAAMER_ABL_NOCOMPACT
-                if (false) {
-#else
-                if (have) {
-#endif
-                    for (uint32_t i0 = 0; i0 < cap; i0 += 64) {
-                        const uint32_t k = a_keys[base_slot + i0 + lane];
-                        const bool has = k != KH_EMPTY_PID;
-                        const unsigned long long bm = __ballot(has);
-                        if (has) {
-                            const uint32_t idx = running + (uint32_t)__popcll(bm & below);
-                            p.hit_pid[base + idx] = k;
-                            const uint32_t w = a_cnt[base_slot + i0 + lane];
-                            p.hit_km[base + idx] = PACKED ? (w & 0xFFFFu) : w;
-                            if (FIRSTPOS) p.hit_fp[base + idx] = PACKED ? (w >> 16) : a_min[base_slot + i0 + lane];
-                        }
-                        running += (uint32_t)__popcll(bm);
-                    }
-                }
-                if (lane == 0) { p.q_cnt[q] = running; p.hit_off[q] = have ? base : 0; }
-                wave_hits += running;
-            }
-            if (lane == 0 && wave_hits) atomicAdd(&s_tot[T_HITS], (unsigned long long)wave_hits);
         }
+        have_prev = true;
     }
     __syncthreads();
-    if (V2 && have_prev) {
+    if (TABLES_LEFT_CLEAN && have_prev) {
         if (wv == 0) epilogue();
         __syncthreads();
     }

@@ -23,6 +23,8 @@
 // PK_ARENA (template parameter): table slots per wave.  640 (5 KB of keys + counts, 24 waves per CU) for ORFs of reads,
 // whose tables are 64-128 slots; 1024 for longer ORFs (search.hip: PK_ARENA_ORF_LONG).  Counts and lowest positions
 // are always kept: the ORFs of nucleotide input carry PositionHits in the reference (search.go:416).
+// The steps of a window (its query, the list head, the flatten, the run add, the packed table add) are
+// count_window.hip.inc's, shared with the group kernel; the four-stage pipeline that runs them is this kernel's own.
 #define PK_QMAX 32u      /* queries of a pack: budget / 64 at most */
 #define PK_WHINT 64u     /* windows with a start hint (the rest search the prefix) */
 #define PK_TICKETS 64u   /* ticket counters (ranges of packs) */
@@ -74,7 +76,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
     fetch_desc(e_cur.y, pre_qi, pre_e);
 
     // work counters of this wave (lane-private partial sums; totals at the end)
-    uint32_t c_post = 0, c_lists = 0, c_lids = 0, c_hits = 0, c_q = 0, c_ovf = 0, c_big = 0;
+    WorkCount work;
+    uint32_t c_hits = 0, c_q = 0, c_ovf = 0, c_big = 0;
     unsigned long long c_in = 0;
 
     while (e_cur.x != 0xFFFFFFFFu) {  // (tickets of one counter ascend: after the first one past the range, all are)
@@ -160,12 +163,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
         __builtin_amdgcn_wave_barrier();
         const uint32_t n_win = (n_posn + 63u) >> 6;
         if (lane < PK_WHINT && (lane << 6) < n_posn) {  // the query that holds position 64 w, for the first windows
-            const uint32_t i = lane << 6;
-            uint32_t j = 0;
-#pragma unroll
-            for (uint32_t sft = PK_QMAX / 2; sft > 0; sft >>= 1)
-                if (j + sft < nq && g_pref[j + sft] <= i) j += sft;
-            s_wq[lane] = (uint8_t)j;
+            s_wq[lane] = (uint8_t)prefix_search<PK_QMAX>(g_pref, nq, lane << 6);
         }
         // ---- 2. clear the tables in use
         for (uint32_t i = lane; i < n_slots; i += 64) {
@@ -187,170 +185,55 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
             WinA r;
             const uint32_t i = (w << 6) + lane;
             const bool valid = i < n_posn;
-            uint32_t j = 0;
-            if (valid) {  // (LDS only)
-                if (w < PK_WHINT) {
-                    j = s_wq[w];
-                    while (j + 1 < nq && g_pref[j + 1] <= i) j++;
-                } else {
-#pragma unroll
-                    for (uint32_t sft = PK_QMAX / 2; sft > 0; sft >>= 1)
-                        if (j + sft < nq && g_pref[j + sft] <= i) j += sft;
-                }
-            }
-            r.j = j;
-            r.ps = valid ? i - g_pref[j] : 0u;
-            r.vraw = p.vals[valid ? g_aa[j] + r.ps : 0ull];
+            const WinPos wp = window_pos<PK_QMAX>(w, i, valid, s_wq, PK_WHINT, g_pref, nq);
+            r.j = wp.j;
+            r.ps = wp.ps;
+            r.vraw = p.vals[valid ? g_aa[wp.j] + wp.ps : 0ull];
             return r;
         };
-        // ISSUES the load of the list head {count, id0, id1, id2}; offset 0 (key absent, or a single inline id) reads zeros
-        auto stage_b = [&](uint32_t v) {
-            return reinterpret_cast<const uint4 *>(p.arena)[(v & KH_INLINE_BIT) ? 0u : v];
-        };
-        // the head as the counting sees it: arithmetic on the raw load (a select would let the compiler sink the load
-        // into a branch again)
-        auto head_of = [&](uint32_t v, const uint4 &hv) {
-            const uint32_t inl = (v & KH_INLINE_BIT) ? 0xFFFFFFFFu : 0u;
-            return make_uint4(hv.x | (inl & 1u), hv.y | (inl & v & ~KH_INLINE_BIT), hv.z, hv.w);
-        };
-        auto add_n = [&](uint32_t j, uint32_t pid, uint32_t pos, uint32_t n) {
-            const uint32_t base = g_tab[j], cap = g_cap[j];
-            uint32_t hh = (uint32_t)(((uint64_t)(pid * 0x9E3779B1u) * cap) >> 32);
-            // at most GRP_MAX_PROBES slots are inspected: a table that crowded is as good as full
-            const uint32_t tmax = cap < GRP_MAX_PROBES ? cap : GRP_MAX_PROBES;
-            for (uint32_t t = 0; t < tmax; t++) {
-#ifdef KAAMER_PROBE_READ_FIRST
-                uint32_t kk = __hip_atomic_load(&a_keys[base + hh], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (kk == KH_EMPTY_PID) {
-                    const uint32_t old = atomicCAS(&a_keys[base + hh], KH_EMPTY_PID, pid);
-                    kk = old == KH_EMPTY_PID ? pid : old;
-                }
-#else
-                // ONE LDS round trip per slot inspected: the compare-and-swap is issued whatever the slot holds (it
-                // returns the occupant of a taken slot).  Reading first and swapping only an empty slot is two dependent
-                // round trips whenever any lane of the wave meets an empty slot -- nearly every iteration.
-                const uint32_t old = atomicCAS(&a_keys[base + hh], KH_EMPTY_PID, pid);
-                const uint32_t kk = old == KH_EMPTY_PID ? pid : old;
-#endif
-                if (kk == pid) {
-                    // count += n and position = min(position, pos) in one word: the adds of a wave are serialised per
-                    // slot by the hardware, other waves never touch this arena
-                    uint32_t old = atomicAdd(&a_cnt[base + hh], n) + n;
-                    while (pos < (old >> 16)) {
-                        const uint32_t seen = atomicCAS(&a_cnt[base + hh], old, (old & 0xFFFFu) | (pos << 16));
-                        if (seen == old) break;
-                        old = seen;
-                    }
-                    return;
-                }
-                hh = (hh + 1u == cap) ? 0u : hh + 1u;
-            }
-            g_ovf[j] = 1;  // table full: the query goes to the G tier
-        };
-        auto add_runs = [&](uint32_t j, uint32_t x, uint32_t pos) {  // runs of equal (query, id) in adjacent lanes: one add
-            const uint32_t px = __shfl_up(x, 1, 64), pj = __shfl_up(j, 1, 64);
-            const bool change = (lane == 0) || px != x || pj != j;
-            const unsigned long long cm = __ballot(change);
-            if (change && x != KH_EMPTY_PID) {
-                const unsigned long long above = (lane == 63) ? 0ull : (cm >> (lane + 1));
-                const uint32_t len = above ? (uint32_t)__ffsll((long long)above) : 64u - lane;
-                add_n(j, x, pos, len);
-            }
-        };
-        // stage C: the ids beyond the first of every lane are FLATTENED over the lanes (item t belongs to the lane that
-        // marked the highest position at or before t); ids 1 and 2 come with the head, the rest are loaded here -- the
-        // loads are ISSUED here and read by stage D an iteration later (xld: raw)
-        struct XRound { uint32_t id, ld, j, ps, m; };  // (scalars, not arrays: a select between two array
-        struct WinX { XRound r0, r1; uint32_t first_id; };          //  elements became a scratch access by address)
+        // stage B ISSUES the load of the list head (issue_head); stage C reads it (head_of)
+        auto add_n = [&](uint32_t j, uint32_t pid, uint32_t pos, uint32_t n) { table_add_packed(a_keys, a_cnt, g_tab, g_cap, g_ovf, j, pid, pos, n); };
+        auto add_one = [&](uint32_t j, uint32_t pid, uint32_t pos) { add_n(j, pid, pos, 1u); };
+        // stage C: the ids beyond the first of every lane are flattened over the lanes; the arena loads of the rounds are
+        // ISSUED here and read by stage D an iteration later (XRound.ld: raw)
+        struct WinX { XRound r0, r1; uint32_t first_id; };
         static_assert(XIT == 2, "two flattened rounds per window are written out");
         auto stage_c = [&](uint32_t v, uint32_t wj, uint32_t wps, const uint4 &h) {
             WinX x;
-            const uint32_t lcnt = h.x;
-            // a postings list longer than the query's table can never fit it: the query goes to the G tier at once, and
-            // a query already on its way there is only counted, not expanded
-            if (lcnt > g_cap[wj] && lcnt != 0u) g_ovf[wj] = 1u;
-            const bool dead = lcnt != 0u && g_ovf[wj] != 0u;
-            x.first_id = (lcnt > 0 && !dead) ? h.y : KH_EMPTY_PID;
-            if (lcnt != 0u) {
-                c_post += lcnt;
-                if (!(v & KH_INLINE_BIT)) { c_lists++; c_lids += lcnt; }
-            }
-            const uint32_t extra = (lcnt > 1u && !dead) ? lcnt - 1u : 0u;
-            const uint32_t inc = wave_inclusive_scan_dpp(extra);
-            const uint32_t xtotal = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            pref[lane] = inc - extra;
-            if (extra != 0u && inc - extra < XIT * 64u) own[inc - extra] = (uint8_t)(lane + 1u);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            const LaneList ll = lane_list(h, wj, g_cap, g_ovf);
+            x.first_id = ll.first_id;
+            work.list(v, h.x);
+            const XWin xw = {v, h.z, h.w, wj, wps};
+            const uint32_t xtotal = flatten_begin<XIT>(lane, ll.extra, pref, own);
             uint32_t carry = 0;
-            auto round = [&](uint32_t it) {
-                XRound r;
-                const uint32_t t = it * 64u + lane;
-                const bool act = t < xtotal;
-                uint32_t mk = own[t];
-                own[t] = 0;  // the marks are left clean for the next window
-                mk = wave_inclusive_max_dpp(mk > carry ? mk : carry);
-                carry = (uint32_t)__builtin_amdgcn_readlane((int)mk, 63);
-                const uint32_t lo = act ? mk - 1u : 0u;
-                const uint32_t off = __shfl(v, (int)lo, 64);
-                const uint32_t oz = __shfl(h.z, (int)lo, 64), ow = __shfl(h.w, (int)lo, 64);
-                r.j = __shfl(wj, (int)lo, 64);
-                r.ps = __shfl(wps, (int)lo, 64);
-                const uint32_t k = act ? t - pref[lo] : 0u;  // item k of the owner = id k+1 of its list
-                const bool from_arena = act && k >= 2u;
-                r.m = from_arena ? 0xFFFFFFFFu : 0u;  // the id is (ld & m) | (id & ~m): arithmetic on the raw load
-                r.ld = p.arena[from_arena ? (uint64_t)off * 4 + 2 + k : 0ull];
-                r.id = !act ? KH_EMPTY_PID : k == 0u ? oz : ow;
-                return r;
-            };
-            x.r0 = round(0u);
-            x.r1 = round(1u);
-            if (xtotal > XIT * 64u) {  // very many ids in one window: the rest are added here, at once (rare)
-                for (uint32_t t0 = XIT * 64u; t0 < xtotal; t0 += 64) {
-                    const uint32_t t = t0 + lane;
-                    const bool act = t < xtotal;
-                    uint32_t lo = 0;
-                    if (act) {
-#pragma unroll
-                        for (int sft = 32; sft > 0; sft >>= 1)
-                            if (pref[lo + sft] <= t) lo += sft;
-                    }
-                    const uint32_t off = __shfl(v, (int)lo, 64);
-                    const uint32_t oz = __shfl(h.z, (int)lo, 64), ow = __shfl(h.w, (int)lo, 64);
-                    const uint32_t oj = __shfl(wj, (int)lo, 64);
-                    const uint32_t op = __shfl(wps, (int)lo, 64);
-                    if (act && !g_ovf[oj]) {
-                        const uint32_t k = t - pref[lo];
-                        add_n(oj, k == 0u ? oz : k == 1u ? ow : p.arena[(uint64_t)off * 4 + 2 + k], op, 1u);
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();  // pref is rewritten by the next window's stage C
+            x.r0 = flatten_round<true>(lane, 0u, xtotal, carry, xw, pref, own, p.arena);
+            x.r1 = flatten_round<true>(lane, 1u, xtotal, carry, xw, pref, own, p.arena);
+            flatten_tail(lane, XIT * 64u, xtotal, xw, pref, g_ovf, p.arena, add_one);  // (rare)
+            flatten_end();
             return x;
         };
         auto stage_d = [&](uint32_t wj, uint32_t wps, const WinX &x) {  // the table adds of one window
-            add_runs(wj, x.first_id, wps);
-            const uint32_t id0 = (x.r0.ld & x.r0.m) | (x.r0.id & ~x.r0.m);
-            if (id0 != KH_EMPTY_PID) add_n(x.r0.j, id0, x.r0.ps, 1u);
-            const uint32_t id1 = (x.r1.ld & x.r1.m) | (x.r1.id & ~x.r1.m);
-            if (id1 != KH_EMPTY_PID) add_n(x.r1.j, id1, x.r1.ps, 1u);
+            add_runs(lane, wj, x.first_id, wps, add_n);
+            const uint32_t id0 = xround_id(x.r0);
+            if (id0 != KH_EMPTY_PID) add_one(x.r0.j, id0, x.r0.ps);
+            const uint32_t id1 = xround_id(x.r1);
+            if (id1 != KH_EMPTY_PID) add_one(x.r1.j, id1, x.r1.ps);
         };
         {
             // iteration w: A(w+3) issued; B(w+2) issued on A(w+2)'s result; C(w+1) on B(w+1)'s; D(w) on C(w)'s -- every
             // load is read one iteration after it was issued
             WinA a1 = stage_a(0), a2 = stage_a(1), a3 = stage_a(2);
             uint32_t v1 = is_valid(0) ? a1.vraw : 0u;
-            uint4 hv1 = stage_b(v1);
+            uint4 hv1 = issue_head(p.arena, v1);
             uint32_t v2 = is_valid(1) ? a2.vraw : 0u;
-            uint4 hv2 = stage_b(v2);
+            uint4 hv2 = issue_head(p.arena, v2);
             uint32_t j0 = a1.j, ps0 = a1.ps;
             WinX x0 = stage_c(v1, a1.j, a1.ps, head_of(v1, hv1));
             // from here on: window w is (j0, ps0, x0); w+1 is (v2, a2, hv2); w+2 is a3 (raw)
             for (uint32_t w = 0; w < n_win; w++) {
                 const WinA a4 = stage_a(w + 3);
                 const uint32_t v3 = is_valid(w + 2) ? a3.vraw : 0u;
-                const uint4 hv3 = stage_b(v3);
+                const uint4 hv3 = issue_head(p.arena, v3);
                 const WinX x1 = stage_c(v2, a2.j, a2.ps, head_of(v2, hv2));
                 stage_d(j0, ps0, x0);
                 j0 = a2.j; ps0 = a2.ps; x0 = x1;
@@ -405,7 +288,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void co
     }
     // ---- totals of the wave -> the batch's counters (one replica per wave index)
     {
-        const uint32_t a = wave_total(c_post), b = wave_total(c_lists), c = wave_total(c_lids), d = wave_total(c_q), big = wave_total(c_big);
+        const uint32_t a = wave_total(work.post), b = wave_total(work.lists), c = wave_total(work.lids), d = wave_total(c_q), big = wave_total(c_big);
         unsigned long long in = c_in;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) in += __shfl_xor(in, o, 64);

@@ -788,6 +788,7 @@ __device__ __forceinline__ void mark_invalid_range(unsigned long long *invalid, 
     }
 }
 
+#include "count_window.hip.inc"
 #include "count_group.hip.inc"
 #ifndef PK_ARENA_ORF
 #define PK_ARENA_ORF 640u
