@@ -50,6 +50,26 @@ typedef enum {
 /* search.go:41-44 */
 enum { KAAMER_NUCLEOTIDE = 0, KAAMER_PROTEIN = 1, KAAMER_READS = 2 };
 
+/* The request's genetic code (SearchOptions.GeneticCode, search.go:60) rides in every `seq_type` argument and field:
+ * bits 0-7 are the sequence type above, bits 8-15 the code, every higher bit is 0.  Valid codes are the keys of
+ * search.GCodes (gcode.go:21-34): 1, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 14, 15.  Code 0 -- every seq_type value of
+ * before this macro -- is the reference's behaviour: GetORFs consults the bacterial table 11 whatever the request says
+ * (dna.go:106), and an explicit 11 gives exactly the same result.  The other codes are honoured where the reference
+ * ignores them: the 6-frame translation reads its start / stop / amino-acid classes from that table.  With
+ * KAAMER_PROTEIN a valid code is accepted and ignored (the reference sends GeneticCode: 11 on protein requests too).
+ * Any other code, or a bit above 15: KAAMER_E_ARG, and the message names the code, before anything is enqueued or a
+ * slot is taken.  The code belongs to the search call, or to the open call of a stream or file driver: workspaces, host
+ * slots and sharded sets are matched and sized by the sequence type alone (kaamer_workspace_create ignores the code
+ * bits) and keep no code from one batch to the next. */
+#define KAAMER_SEQ_TYPE(type, genetic_code) ((int32_t)((type) | ((genetic_code) << 8)))
+#define KAAMER_SEQ_TYPE_BASE(seq_type) ((int32_t)((seq_type) & 0xFF))
+#define KAAMER_SEQ_TYPE_GENETIC_CODE(seq_type) ((int32_t)(((seq_type) >> 8) & 0xFF))
+
+/* The library's own table of a genetic code, codons in t-c-a-g order (ttt, ttc, tta, ttg, tct, ...): aa[i] the amino-acid
+ * letter ('*': a stop codon), start[i] 'M' for a start codon and '-' otherwise; no terminator is written.  Code 0 returns
+ * table 11.  KAAMER_E_ARG for a code that is not a key of search.GCodes.  Host only. */
+int kaamer_genetic_code(int32_t code, char aa[64], char start[64]);
+
 const char *kaamer_last_error(void);
 int kaamer_abi_version(void);
 
@@ -253,7 +273,8 @@ typedef struct {
     const uint8_t *seqs;      /* packed sequences, caller-owned                */
     const uint64_t *offsets;  /* n_seqs + 1                                    */
     uint32_t n_seqs;
-    int32_t seq_type;         /* KAAMER_NUCLEOTIDE / PROTEIN / READS           */
+    int32_t seq_type;         /* KAAMER_NUCLEOTIDE / PROTEIN / READS, or       */
+                              /* KAAMER_SEQ_TYPE(type, genetic code)           */
     int32_t want_positions;   /* SearchOptions.ExtractPositions (search.go:64) */
 } kaamer_batch_in;
 
@@ -318,7 +339,9 @@ typedef struct {
     uint64_t g_tier_slots;   /* HBM counting-table slots for queries whose     */
                              /* distinct hits exceed the on-chip tiers; 0 = def*/
     int32_t seq_type;        /* KAAMER_PROTEIN, or KAAMER_NUCLEOTIDE / READS   */
-                             /* (adds the 6-frame translation buffers)         */
+                             /* (adds the 6-frame translation buffers); the    */
+                             /* genetic-code bits are ignored: the code is the */
+                             /* search call's (KAAMER_SEQ_TYPE)                */
     uint32_t first_pos;      /* hit_first_pos: 0 = as the reference fills      */
                              /* PositionHits (nucleotide/reads only,           */
                              /* search.go:416), 1 = always, 2 = never (zeros)  */

@@ -11,6 +11,34 @@ LIB_PATH = os.environ.get("KAAMER_LIB") or os.path.join(_HERE, "libkaamer_hip.so
 
 OK, E_ARG, E_IO, E_NOMEM, E_HIP, E_CAPACITY, E_FORMAT, E_BUSY = 0, -1, -2, -3, -4, -5, -6, -7
 NUCLEOTIDE, PROTEIN, READS = 0, 1, 2
+GENETIC_CODES = (1, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 14, 15)   # the keys of search.GCodes (gcode.go:21-34)
+
+
+def seq_type(base, genetic_code=0):
+    """KAAMER_SEQ_TYPE: the value every `seq_type` argument takes -- the sequence type in bits 0-7, the request's genetic
+    code in bits 8-15 (0: the reference's behaviour, table 11).  The library checks the code."""
+    return int(base) | (int(genetic_code) << 8)
+
+
+def seq_type_base(seq_type):
+    """KAAMER_SEQ_TYPE_BASE: NUCLEOTIDE / PROTEIN / READS"""
+    return int(seq_type) & 0xFF
+
+
+def seq_type_genetic_code(seq_type):
+    """KAAMER_SEQ_TYPE_GENETIC_CODE"""
+    return (int(seq_type) >> 8) & 0xFF
+
+
+def split_seq_type(seq_type):
+    return seq_type_base(seq_type), seq_type_genetic_code(seq_type)
+
+
+def genetic_code(code=0):
+    """kaamer_genetic_code: the library's table, codons in t-c-a-g order -> (amino-acid letters, 'M' / '-' start letters)"""
+    aa, start = C.create_string_buffer(64), C.create_string_buffer(64)
+    check(lib().kaamer_genetic_code(int(code), aa, start))
+    return aa.raw.decode("ascii"), start.raw.decode("ascii")
 
 
 class KaamerError(RuntimeError):
@@ -142,6 +170,7 @@ SYMBOLS = {
     "kaamer_last_error": (C.c_char_p, []),
     "kaamer_abi_version": (C.c_int, []),
     "kaamer_encode_kmer": (C.c_uint32, [C.c_char_p]),
+    "kaamer_genetic_code": (C.c_int, [C.c_int32, C.c_char_p, C.c_char_p]),
     "kaamer_shard_of": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "kaamer_image_build_pairs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double,
                                            C.POINTER(C.c_void_p)]),

@@ -88,6 +88,7 @@ static int replica_stream_open_form(kaamer_replicas *r, const StreamForm &f, kaa
 {
     if (!r || !r->ix || !out) return kaamer_fail(KAAMER_E_ARG, "replica_stream_open: bad argument");
     *out = nullptr;
+    SEQ_TYPE_CHK(f.seq_type, "replica_stream_open");
     kaamer_replica_stream *rs = new (std::nothrow) kaamer_replica_stream();
     if (!rs) return kaamer_fail(KAAMER_E_NOMEM, "replica stream");
     rs->st = new (std::nothrow) std::vector<kaamer_stream *>(r->ix->size(), nullptr);
@@ -248,6 +249,7 @@ static int search_file_replicas(kaamer_replicas *r, const char *path, int format
                                 uint64_t chunk_bytes, uint32_t in_flight, kaamer_chunk_cb cb, void *user, kaamer_counters *total)
 {
     if (!r || !path || chunk_seqs == 0 || (f.want_aln && !f.sub_matrix)) return kaamer_fail(KAAMER_E_ARG, "search_file: bad argument");
+    SEQ_TYPE_CHK(f.seq_type, "search_file");
     if (total) memset(total, 0, sizeof *total);
     if (in_flight < 1) in_flight = 3;
     kaamer_reader *rd = nullptr;

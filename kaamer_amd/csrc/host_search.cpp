@@ -8,6 +8,7 @@
 //
 // In the Go integration these stay the reference's own Go code.
 #include "kaamer_internal.h"
+#include "gcodes.h"
 
 #include <zlib.h>
 
@@ -438,6 +439,17 @@ const char *kaamer_reads_names(const kaamer_reads *r) { return r ? r->names.data
 const uint64_t *kaamer_reads_name_offsets(const kaamer_reads *r) { return r ? r->name_off.data() : nullptr; }
 const int32_t *kaamer_reads_plus_strand(const kaamer_reads *r) { return r ? r->plus_strand.data() : nullptr; }
 void kaamer_reads_free(kaamer_reads *r) { delete r; }
+
+// the library's own table of a genetic code (gcodes.h), as tests and a Go host see it; 0 = the reference's behaviour = table 11
+int kaamer_genetic_code(int32_t code, char aa[64], char start[64])
+{
+    if (!aa || !start) return kaamer_fail(KAAMER_E_ARG, "genetic_code: bad argument");
+    const int slot = kt_gcode_slot(code);
+    if (slot < 0) return kaamer_fail(KAAMER_E_ARG, "genetic_code: unknown genetic code %d (one of 1-6, 9-15; 0 = table 11)", (int)code);
+    memcpy(aa, kt_tables()[slot].aa, 64);
+    memcpy(start, kt_tables()[slot].start, 64);
+    return KAAMER_OK;
+}
 
 // SetBestStartCodon, dna.go:198-272.  hits must be in sortMapByValue order (Kmatch
 // descending; kaamer_sort_hits).  The reference scans PositionHits of the best hits; the only

@@ -389,6 +389,7 @@ static int tas_enqueue_align(kaamer_sharded_index *sx, const kaamer_sharded_tick
 static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq_bytes, uint32_t n_seqs, int32_t seq_type, const ShardBounds &b, uint32_t K)
 {
     HIPCHK(hipSetDevice(st.device));
+    seq_type = seq_base(seq_type);   // (the genetic code is the call's: every shard gets it with the batch, kaamer_search_device)
     const bool nucl = is_nucl(seq_type);
     const kaamer_workspace_opts &o = st.opts;
     const bool fits = st.ws && o.seq_type == seq_type && o.max_seq_bytes >= seq_bytes && o.max_seqs >= (n_seqs ? n_seqs : 1) &&
@@ -1070,6 +1071,7 @@ static void tas_first_caps(const kaamer_sharded_index *sx, kaamer_sharded_ticket
 static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, const kaamer_topn_opts *top, kaamer_sharded_ticket *t,
                           bool top_pos, const TopAlnRequest *aln = nullptr, bool block = true)
 {
+    SEQ_TYPE_CHK(in->seq_type, "sharded_submit_batch");
     ShardSet *set = nullptr;
     {
         std::unique_lock<std::mutex> lock(sx->mu);

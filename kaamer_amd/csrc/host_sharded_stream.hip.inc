@@ -21,6 +21,7 @@ static int sharded_stream_open(kaamer_sharded_index *sx, int32_t seq_type, doubl
 {
     if (!sx || !out || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "sharded_stream_open: bad argument");
     *out = nullptr;
+    SEQ_TYPE_CHK(seq_type, "sharded_stream_open");
     kaamer_sharded_stream *st = new (std::nothrow) kaamer_sharded_stream();
     if (!st) return kaamer_fail(KAAMER_E_NOMEM, "sharded stream");
     st->sx = sx; st->seq_type = seq_type; st->want_pos = want_pos;
@@ -111,6 +112,7 @@ int kaamer_sharded_search_file(kaamer_sharded_index *sx, const char *path, int f
                                uint32_t in_flight, kaamer_chunk_cb cb, void *user, kaamer_counters *total)
 {
     if (!sx || !path || chunk_seqs == 0 || (want_aln && !sub_matrix)) return kaamer_fail(KAAMER_E_ARG, "sharded_search_file: bad argument");
+    SEQ_TYPE_CHK(seq_type, "sharded_search_file");
     if (total) memset(total, 0, sizeof *total);
     if (in_flight < 1) in_flight = 3;
     if (in_flight > KAAMER_SHARDED_SETS) in_flight = KAAMER_SHARDED_SETS;

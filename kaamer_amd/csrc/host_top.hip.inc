@@ -299,7 +299,7 @@ static int top_enqueue(kaamer_ticket *t)
     o.max_seqs = t->n_seqs ? t->n_seqs : 1;
     o.max_hits = t->b.max_hits;
     o.g_tier_slots = t->b.g_slots;
-    o.seq_type = t->seq_type;
+    o.seq_type = seq_base(t->seq_type);
     o.first_pos = 0;  // as the reference fills PositionHits: nucleotide / reads input only (search.go:416)
     o.max_queries = t->b.max_queries;
     o.concurrent_batches = (uint32_t)ix->n_top;   // the slots exist so that batches overlap
@@ -333,6 +333,7 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
     if (!ix || !in || !top || !out || !in->offsets || (in->n_seqs && !in->seqs) || top->max_results < 1)
         return kaamer_fail(KAAMER_E_ARG, "submit_batch_top: bad argument");
     *out = nullptr;
+    SEQ_TYPE_CHK(in->seq_type, "submit_batch_top");
     int slot = -1;
     {
         std::unique_lock<std::mutex> lock(ix->pool_mu);
@@ -598,6 +599,7 @@ int kaamer_stream_open(kaamer_index *ix, int32_t seq_type, const kaamer_topn_opt
 {
     if (!ix || !top || !out || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "stream_open: bad argument");
     *out = nullptr;
+    SEQ_TYPE_CHK(seq_type, "stream_open");
     kaamer_stream *st = new (std::nothrow) kaamer_stream();
     if (!st) return kaamer_fail(KAAMER_E_NOMEM, "stream");
     st->ix = ix; st->seq_type = seq_type; st->top = *top; st->want_pos = false; st->want_aln = false;

@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "kaamer_internal.h"
+#include "gcodes.h"
 
 // ------------------------------------------------------------------------------------
 // error plumbing
@@ -84,7 +85,26 @@ struct HostSlot {
     bool busy = false;              // (under kaamer_index::pool_mu)
 };
 
-static inline bool is_nucl(int32_t seq_type) { return seq_type == KAAMER_NUCLEOTIDE || seq_type == KAAMER_READS; }
+// `seq_type` as every entry point takes it: the sequence type in bits 0-7, the request's genetic code in bits 8-15
+// (KAAMER_SEQ_TYPE).  Workspaces, host slots and sharded sets are matched and sized by the base type alone; the code goes
+// with the call into kaamer_search_device and no further.
+static inline int32_t seq_base(int32_t seq_type) { return KAAMER_SEQ_TYPE_BASE(seq_type); }
+static inline bool is_nucl(int32_t seq_type) { return seq_base(seq_type) == KAAMER_NUCLEOTIDE || seq_base(seq_type) == KAAMER_READS; }
+
+// the entry points' test, before anything is enqueued or a slot is taken
+static int check_seq_type(int32_t seq_type, const char *who)
+{
+    const int32_t base = seq_base(seq_type), code = KAAMER_SEQ_TYPE_GENETIC_CODE(seq_type);
+    if ((uint32_t)seq_type >> 16) return kaamer_fail(KAAMER_E_ARG, "%s: sequence type 0x%x has bits above 15 set", who, (unsigned)seq_type);
+    if (base != KAAMER_NUCLEOTIDE && base != KAAMER_PROTEIN && base != KAAMER_READS) return kaamer_fail(KAAMER_E_ARG, "%s: unknown sequence type %d", who, base);
+    if (kt_gcode_slot(code) < 0) return kaamer_fail(KAAMER_E_ARG, "%s: unknown genetic code %d (one of 1-6, 9-15; 0 = table 11)", who, code);
+    return KAAMER_OK;
+}
+#define SEQ_TYPE_CHK(seq_type, who)                        \
+    do {                                                   \
+        const int rc_ = check_seq_type((seq_type), (who)); \
+        if (rc_) return rc_;                               \
+    } while (0)
 
 // the data-dependent bounds of a host-buffer call (0: the library's default for the input size).  The hit count of a
 // batch is data dependent: a call starts from an estimate and, while the device reports KAAMER_E_CAPACITY (results are
@@ -1985,6 +2005,7 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     memset(ws, 0, sizeof *ws);
     ws->device = ix->device;
     ws->opts = *opts;
+    ws->opts.seq_type = seq_base(opts->seq_type);   // a workspace serves every genetic code: the code is the call's
     ws->nucleotide = is_nucl(opts->seq_type);
     ws->max_seqs = opts->max_seqs ? opts->max_seqs : 1;
     if (ws->nucleotide) {
@@ -2270,9 +2291,27 @@ struct QueryInput {
     uint32_t nq_bound;         // host-side bound of the number of queries
 };
 
+// the launches that see codon classes, once per GENERIC (translate.hip.inc): the long sequences' COUNT pass, then the reads'
+// kernel and the long sequences' WRITE pass
+extern "C++" {
+template <bool GENERIC>
+static void launch_translate_count(const TranslateParams &tp, int tgrid, hipStream_t s)
+{
+    hipLaunchKernelGGL((translate_kernel<false, GENERIC>), dim3(tgrid), dim3(256), 0, s, tp);
+}
+template <bool GENERIC>
+static void launch_translate_write(const TranslateParams &tp, bool wide_reads, int sgrid, int tgrid, hipStream_t s)
+{
+    if (wide_reads) hipLaunchKernelGGL((translate_reads_kernel<TS_MAX_WIDE, GENERIC>), dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
+    else hipLaunchKernelGGL((translate_reads_kernel<TS_MAX, GENERIC>), dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
+    hipLaunchKernelGGL((translate_kernel<true, GENERIC>), dim3(tgrid), dim3(256), 0, s, tp);
+}
+}  // extern "C++"
+
 // nucleotide batches: 6-frame translation -- count, scan, write, order (translate.hip.inc) -- and the ORFs' prep
+// gc_slot: the call's table (kt_gcode_slot); table 11 launches the kernels with compile-time classes
 static QueryInput enqueue_translate(kaamer_workspace *ws, const uint8_t *d_seqs, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t seq_bytes,
-                                    uint32_t *status, hipStream_t s)
+                                    int gc_slot, uint32_t *status, hipStream_t s)
 {
     const size_t cap6 = (size_t)ws->max_seqs * 6;
     TranslateParams tp;
@@ -2308,17 +2347,26 @@ static QueryInput enqueue_translate(kaamer_workspace *ws, const uint8_t *d_seqs,
     tp.epoch = next_epoch(ws->tr_epoch);
     tp.out_meta = ws->d_q; tp.d_nq = ws->d_nq; tp.d_n_pos = ws->d_n_pos;
     tp.w_off_orf = ws->d_off3; tp.w_off_aa = ws->d_off3 + (cap6 + 1); tp.w_off_sa = ws->d_off3 + 2 * (cap6 + 1);
+    const bool generic = gc_slot != KT_SLOT_DEFAULT;
+    if (generic) {
+        const KtTable &kt = kt_tables()[gc_slot];
+        tp.gc_slot = (uint32_t)gc_slot;
+        for (int i = 0; i < 64; i++) {
+            if (kt.start[i] == 'M') tp.gc_start_bits |= 1ull << i;
+            if (kt.aa[i] == '*') tp.gc_stop_bits |= 1ull << i;
+        }
+    }
     // long sequences first (listed, cut in pieces, counted: a wave per piece) -- a reads-only batch falls through
     // these launches; then everything of the reads and the output offsets of both kinds in one kernel
     hipLaunchKernelGGL(list_long_kernel, dim3((unsigned)(((uint64_t)n_seqs + LL_BLOCK - 1) / LL_BLOCK + (n_seqs ? 0 : 1))), dim3(LL_BLOCK), 0, s, tp);
     scan_u32_on(ws, ws->d_long_np, tp.n_long, n_long_bound, ws->d_piece_base, s);
     hipLaunchKernelGGL(piece_li_kernel, dim3((unsigned)((n_long_bound + 255) / 256)), dim3(256), 0, s, tp);
-    hipLaunchKernelGGL(translate_kernel<false>, dim3(tgrid), dim3(256), 0, s, tp);
+    if (generic) launch_translate_count<true>(tp, tgrid, s);
+    else launch_translate_count<false>(tp, tgrid, s);
     for (int a = 0; a < 3; a++) scan_u32_on(ws, ws->d_pcnt3 + a * mpi, ws->d_n_piece_items, piece_bound, ws->d_poff3 + a * (mpi + 1), s);
     hipLaunchKernelGGL(long_totals_kernel, dim3((unsigned)((n_long_bound * 6 + 255) / 256)), dim3(256), 0, s, tp);
-    if (wide_reads) hipLaunchKernelGGL(translate_reads_kernel<TS_MAX_WIDE>, dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
-    else hipLaunchKernelGGL(translate_reads_kernel<TS_MAX>, dim3(sgrid), dim3(64 * TS_WAVES), 0, s, tp);
-    hipLaunchKernelGGL(translate_kernel<true>, dim3(tgrid), dim3(256), 0, s, tp);
+    if (generic) launch_translate_write<true>(tp, wide_reads, sgrid, tgrid, s);
+    else launch_translate_write<false>(tp, wide_reads, sgrid, tgrid, s);
     hipLaunchKernelGGL(orf_order_long_kernel, dim3((unsigned)(n_long_bound < (uint64_t)ws->n_cu * 32 ? (n_long_bound + 3) / 4 + 1 : (uint64_t)ws->n_cu * 8)), dim3(256), 0, s,
                        ws->d_tmp_meta, tp.off_orf, ws->d_long_seq, tp.n_long, ws->d_q, ws->d_nq);
     hipLaunchKernelGGL(prep_orf_kernel, dim3(ws->n_cu * 4), dim3(256), 0, s, ws->d_q, ws->d_nq, ws->d_valid, ws->d_n_pos,
@@ -2431,8 +2479,8 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
 {
     if (!ix || !ws || !out || (n_seqs && (!d_seqs || !d_offsets))) return kaamer_fail(KAAMER_E_ARG, "search_device: bad argument");
     if (ix->device != ws->device) return kaamer_fail(KAAMER_E_ARG, "workspace belongs to another device");
+    SEQ_TYPE_CHK(seq_type, "search_device");
     const bool nucl = is_nucl(seq_type);
-    if (!nucl && seq_type != KAAMER_PROTEIN) return kaamer_fail(KAAMER_E_ARG, "search_device: unknown sequence type %d", seq_type);
     if (nucl != ws->nucleotide) return kaamer_fail(KAAMER_E_ARG, "workspace was created for %s input", ws->nucleotide ? "nucleotide" : "protein");
     if (n_seqs > ws->max_seqs) return kaamer_fail(KAAMER_E_CAPACITY, "batch of %u sequences exceeds workspace max_seqs %u", n_seqs, ws->max_seqs);
     if (ws->pos_cap > 0xFFFFFFF0ull) return kaamer_fail(KAAMER_E_CAPACITY, "a batch holds at most 2^32 residue positions");
@@ -2470,7 +2518,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     if (!nucl) {
         enqueue_protein_prep(ws, d_seqs, d_offsets, n_seqs, seq_bytes, status, s);
     } else {
-        qin = enqueue_translate(ws, d_seqs, d_offsets, n_seqs, seq_bytes, status, s);
+        qin = enqueue_translate(ws, d_seqs, d_offsets, n_seqs, seq_bytes, kt_gcode_slot(KAAMER_SEQ_TYPE_GENETIC_CODE(seq_type)), status, s);
         launch_layout(ws, qin.nq_bound, status, s, ws->pack_shift, false);
     }
     if (timed) HIPCHK(hipEventRecord(ev[1], s));
@@ -3315,7 +3363,7 @@ static int search_batch_enqueue(kaamer_index *ix, HostSlot &slot, const kaamer_b
     o.max_seqs = in->n_seqs ? in->n_seqs : 1;
     o.max_hits = b.max_hits;
     o.g_tier_slots = b.g_slots;
-    o.seq_type = in->seq_type;
+    o.seq_type = seq_base(in->seq_type);
     o.first_pos = 1;  // kaamer_batch_out always carries hit_first_pos
     o.want_positions = in->want_positions ? 1u : 0u;
     o.compact = 1u;  // the host form is CSR
@@ -3426,6 +3474,7 @@ struct kaamer_full_ticket {
 // a free slot (one whose workspace already serves this kind of batch, if there is one); callers beyond the slots wait
 static HostSlot *host_slot_take(kaamer_index *ix, int32_t seq_type)
 {
+    seq_type = seq_base(seq_type);
     HostSlot *slot = nullptr;
     std::unique_lock<std::mutex> lock(ix->pool_mu);
     for (;;) {
@@ -3449,6 +3498,7 @@ int kaamer_submit_batch_flat(kaamer_index *ix, const uint8_t *seqs, const uint64
 {
     if (!ix || !ticket || !offsets || (n_seqs && !seqs)) return kaamer_fail(KAAMER_E_ARG, "submit_batch: bad argument");
     *ticket = nullptr;
+    SEQ_TYPE_CHK(seq_type, "submit_batch");
     HIPCHK(hipSetDevice(ix->device));
     kaamer_full_ticket *t = new (std::nothrow) kaamer_full_ticket();
     if (!t) return kaamer_fail(KAAMER_E_NOMEM, "ticket");
@@ -3507,6 +3557,7 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 {
     if (!ix || !in || !out || !in->offsets || (in->n_seqs && !in->seqs)) return kaamer_fail(KAAMER_E_ARG, "search_batch: bad argument");
     *out = nullptr;
+    SEQ_TYPE_CHK(in->seq_type, "search_batch");
     HIPCHK(hipSetDevice(ix->device));
     HostSlot *slot = host_slot_take(ix, in->seq_type);
     struct Release {

@@ -1,9 +1,11 @@
 // translate.hip.inc — 6-frame translation and ORF segmentation on the device
 // (included by search.hip).
 //
-// Replaces GetORFs / GetFrame / ReverseComplement (pkg/search/dna.go:55-196) with the
+// Replaces GetORFs / GetFrame / ReverseComplement (pkg/search/dna.go:55-196).  By default with the
 // bacterial table gcodeBacteria (gcode.go:36-101; the geneticCode argument is ignored by
-// the reference, dna.go:106).  One wave walks one input sequence: six frames, 64 codons
+// the reference, dna.go:106); a request that names another of search.GCodes' tables gets that
+// table (a deliberate divergence: the codon classes are all that changes, see GENERIC below).
+// One wave walks one input sequence: six frames, 64 codons
 // at a time; codon classes are ballots (known / start / stop) and the reference's
 // per-codon state machine runs on those 64-bit masks:
 //
@@ -22,8 +24,19 @@
 // StartPosition on the minus strand; ties in emission order) by merging the six per-frame lists,
 // which are already monotonic.
 
-__constant__ char kt_aa[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";      // tcag order
-__constant__ char kt_start[65] = "---M---------------M------------MMMM---------------M------------";
+// the thirteen tables of search.GCodes (gcodes.h), tcag order; row KT_SLOT_DEFAULT is table 11
+#define KT_AA_(code_, aa_, start_) aa_,
+#define KT_START_(code_, aa_, start_) start_,
+__constant__ char kt_aa[KT_N_GCODES][65] = { KT_GCODES(KT_AA_) };
+__constant__ char kt_start[KT_N_GCODES][65] = { KT_GCODES(KT_START_) };
+#undef KT_AA_
+#undef KT_START_
+// Every translation kernel exists twice.  GENERIC = false is the reference's behaviour (code 0 or 11): table 11 and its
+// class masks are compile-time constants, and the kernels are instruction for instruction what they were before a
+// request could name a code (translate_reads_kernel<192> sits one register under the 4-waves-per-SIMD cliff).
+// GENERIC = true reads the table slot and the two class masks the host put into TranslateParams for this call.
+#define KT_START_BITS_DEFAULT 0x0008000F00080008ull  /* kt_start[KT_SLOT_DEFAULT] == 'M', bit = codon index */
+#define KT_STOP_BITS_DEFAULT 0x0000000000004C00ull   /* kt_aa[KT_SLOT_DEFAULT] == '*' */
 
 #define MIN_LEN_CDS 21  /* dna.go:26 */
 // Sequences up to TranslateParams::ts_max nucleotides (reads) take translate_reads_kernel<MAXNT>, which exists twice:
@@ -85,6 +98,10 @@ struct TranslateParams {
     uint32_t *d_nq;
     unsigned long long *d_n_pos;
     uint64_t *w_off_orf, *w_off_aa, *w_off_sa;  // off_* again, writable: the entries of the long sequences
+    // the call's genetic code (GENERIC kernels only; never kept in the workspace): row of kt_aa / kt_start, and its start /
+    // stop classes as masks over the codon index (wave-uniform: pass 1 of the lane-per-read kernels needs no table lookup)
+    uint32_t gc_slot;
+    unsigned long long gc_start_bits, gc_stop_bits;
 };
 
 __device__ __forceinline__ uint32_t nt_code(uint8_t c)
@@ -124,7 +141,7 @@ __device__ __forceinline__ void load_codon(const uint8_t *dna, int64_t len, int 
 // 2 400 of them instead of 6.  The (sequence, frame, piece) items of all long sequences are numbered
 // t = 6 * piece_base[li] + frame * np(li) + piece; their ORF / residue / start counts are scanned
 // (poff_*) and summed into the per-(sequence, frame) counts the rest of the pipeline uses.
-template <bool WRITE>
+template <bool WRITE, bool GENERIC>
 __global__ __launch_bounds__(256) void translate_kernel(TranslateParams p)
 {
     __shared__ uint8_t s_pend_aa_all[4][32];
@@ -147,7 +164,10 @@ __global__ __launch_bounds__(256) void translate_kernel(TranslateParams p)
         s_nt[0][threadIdx.x] = (uint8_t)c0_;
         s_nt[1][threadIdx.x] = (uint8_t)(c0_ < 4 ? c0_ ^ 2u : c0_);  // t<->a, c<->g
     }
-    if (threadIdx.x < 64) s_aa_tab[threadIdx.x] = (uint8_t)((uint8_t)kt_aa[threadIdx.x] | (kt_start[threadIdx.x] == 'M' ? 0x80u : 0u));
+    if (threadIdx.x < 64) {
+        const uint32_t slot = GENERIC ? p.gc_slot : (uint32_t)KT_SLOT_DEFAULT;
+        s_aa_tab[threadIdx.x] = (uint8_t)((uint8_t)kt_aa[slot][threadIdx.x] | (kt_start[slot][threadIdx.x] == 'M' ? 0x80u : 0u));
+    }
     __syncthreads();
     const unsigned long long below = (1ull << lane) - 1ull;
 
@@ -183,7 +203,7 @@ __global__ __launch_bounds__(256) void translate_kernel(TranslateParams p)
                 const uint32_t t_ = ((a | b | c) & 4u) ? 0u : (uint32_t)s_aa_tab[(a << 4) | (b << 2) | c];  // amino acid | 0x80: start codon
                 aa = t_ & 0x7Fu;
                 is_start = (t_ & 0x80u) != 0u;
-                is_stop = aa == (uint32_t)'*';
+                is_stop = aa == (uint32_t)'*';   // (in all thirteen tables Stop <=> amino acid '*')
             };
             // ---- where the state machine starts: after the last stop before the piece
             bool inside = true;             // dna.go:98 (no stop before: the first ORF of the frame)
@@ -433,7 +453,7 @@ __global__ __launch_bounds__(LL_BLOCK) void list_long_kernel(TranslateParams p)
 //           lane works out among its own <= 6 x TR_Q ORFs.
 // Longer sequences of the same batch have been counted by translate_kernel<false> before this kernel runs: their lane
 // puts those counts on the chain and leaves the offsets of their six frames for translate_kernel<true>.
-template <uint32_t MAXNT>
+template <uint32_t MAXNT, bool GENERIC>
 __global__ __launch_bounds__(64 * TS_WAVES, TsCfg<MAXNT>::MIN_WAVES) void translate_reads_kernel(TranslateParams p)
 {
     constexpr int TS_HALVES = TsCfg<MAXNT>::HALVES;
@@ -446,7 +466,10 @@ __global__ __launch_bounds__(64 * TS_WAVES, TsCfg<MAXNT>::MIN_WAVES) void transl
     __shared__ uint8_t s_aa_tab[64];  // amino acid of the codon (t c a g order) | 0x80 when it is a start codon
     __shared__ uint8_t s_ntc[256];    // byte -> nucleotide code (nt_code): one LDS read per base when the reads are staged
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    if (threadIdx.x < 64) s_aa_tab[threadIdx.x] = (uint8_t)((uint8_t)kt_aa[threadIdx.x] | (kt_start[threadIdx.x] == 'M' ? 0x80u : 0u));
+    if (threadIdx.x < 64) {
+        const uint32_t slot = GENERIC ? p.gc_slot : (uint32_t)KT_SLOT_DEFAULT;
+        s_aa_tab[threadIdx.x] = (uint8_t)((uint8_t)kt_aa[slot][threadIdx.x] | (kt_start[slot][threadIdx.x] == 'M' ? 0x80u : 0u));
+    }
     for (uint32_t i = threadIdx.x; i < 256; i += 64 * TS_WAVES) s_ntc[i] = (uint8_t)nt_code((uint8_t)i);
     __syncthreads();
     uint8_t *rd = s_read[wv];
@@ -523,9 +546,10 @@ __global__ __launch_bounds__(64 * TS_WAVES, TsCfg<MAXNT>::MIN_WAVES) void transl
             else idx = ((((c >> 8) & 3u) << 4) | ((c >> 2) & 12u) | (c & 3u)) ^ 42u;
             return idx | ((c & 0x444u) << 4);
         };
-        // the classes pass 1 needs, without a table lookup: start / stop codons of table 11 as bit masks over the index
-        // (kt_start == 'M' and kt_aa == '*'), known = all three bytes are a/c/g/t
-        constexpr unsigned long long START_BITS = 0x0008000F00080008ull, STOP_BITS = 0x0000000000004C00ull;
+        // the classes pass 1 needs, without a table lookup: start / stop codons of the table as bit masks over the index
+        // (kt_start == 'M' and kt_aa == '*'; constants for table 11, the call's otherwise), known = all three bytes are a/c/g/t
+        const unsigned long long START_BITS = GENERIC ? p.gc_start_bits : KT_START_BITS_DEFAULT;
+        const unsigned long long STOP_BITS = GENERIC ? p.gc_stop_bits : KT_STOP_BITS_DEFAULT;
         auto classify = [&](uint32_t f, uint32_t j, bool &known, bool &is_start, bool &is_stop) {
             const uint32_t ci = codon(f, j);
             known = ci < 64u;

@@ -32,6 +32,7 @@ class SearchOptions:  # search.go:56-71 (the fields the hot path reads); default
     SubMatrix: str = "blosum62"   # api/server.go:149-151
     GapOpen: int = 11
     GapExtend: int = 1
+    GeneticCode: int = 11         # search.go:60, api/server.go:142: the 6-frame translation's table (nucleotide / reads requests)
     ChunkSeqs: int = 1 << 20      # SearchFile only (no reference counterpart): records per chunk, chunks in flight (0: three)
     InFlight: int = 0
 
@@ -175,14 +176,14 @@ def FastqSearch(index, fastq_text, options=None):
     """search_fastq.go:27-154 (READS) -> list of QueryResult dicts, one per reported ORF"""
     o = options or SearchOptions(SequenceType=abi.READS)
     recs = api.parse_reads(fastq_text, "fastq")
-    return _orf_results(index, [r["seq"] for r in recs], [r["name"] for r in recs], o, abi.READS)
+    return _orf_results(index, [r["seq"] for r in recs], [r["name"] for r in recs], o, abi.seq_type(abi.READS, o.GeneticCode))
 
 
 def NucleotideSearch(index, fasta_text, options=None):
     """search_nucleotide.go:27-160 (contigs in FASTA) -> list of QueryResult dicts"""
     o = options or SearchOptions(SequenceType=abi.NUCLEOTIDE)
     recs = api.parse_reads(fasta_text, "fasta")
-    out = _orf_results(index, [r["seq"] for r in recs], [r["name"] for r in recs], o, abi.NUCLEOTIDE)
+    out = _orf_results(index, [r["seq"] for r in recs], [r["name"] for r in recs], o, abi.seq_type(abi.NUCLEOTIDE, o.GeneticCode))
     for qr in out:
         qr["Query"]["Contig"] = qr["Query"]["Name"]  # search.go:305-306
     return out
@@ -255,7 +256,7 @@ def SearchFile(handle, path, options=None, fmt=None):
 
     def work():
         try:
-            handle.search_file(path, fmt, seq_type=seq_type, min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
+            handle.search_file(path, fmt, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
                                chunk_seqs=int(getattr(o, "ChunkSeqs", 1 << 20)), in_flight=int(getattr(o, "InFlight", 0)), on_chunk=on_chunk,
                                want_positions=bool(o.ExtractPositions), align=aln)
             put(done)

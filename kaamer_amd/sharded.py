@@ -134,7 +134,7 @@ class ShardedSearcher:
         assert transport in ("rccl", "torch", "host")
         self.index, self.rank, self.world, self.group = index, rank, world, group
         self.transport = transport
-        self.nucl = seq_type in (abi.READS, abi.NUCLEOTIDE)
+        self.nucl = abi.seq_type_base(seq_type) in (abi.READS, abi.NUCLEOTIDE)
         self.want_positions = bool(want_positions)
         if first_pos is None:
             first_pos = self.nucl
