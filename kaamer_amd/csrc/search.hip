@@ -498,104 +498,6 @@ __device__ __forceinline__ unsigned long long tail_alloc(const CountParams &p, u
 }
 
 // counting tables: protein id -> (count, lowest matching position)
-template <int LOG2CAP, bool FIRSTPOS = true> struct LdsTable {
-    volatile uint32_t *keys;
-    uint32_t *cnt, *minpos, *nd;
-    static constexpr uint32_t CAP = 1u << LOG2CAP;
-    static constexpr uint32_t LIMIT = CAP - CAP / 4;  // keep 25 % free
-    // n matches of `pid`, the lowest of them at `pos`.  `nnew` counts the entries this lane
-    // created: the distinct-hit counter is updated once per wave, not once per insertion
-    // (64 lanes bumping one LDS word serialise).
-    __device__ __forceinline__ bool add_n(uint32_t pid, uint32_t pos, uint32_t n, uint32_t &nnew) const
-    {
-        constexpr uint32_t MASK = CAP - 1u;
-        uint32_t h = (pid * 0x9E3779B1u) >> (32 - LOG2CAP);
-        for (uint32_t t = 0; t <= MASK; t++) {
-            uint32_t k = keys[h];
-            if (k == KH_EMPTY_PID) {
-                const uint32_t old = atomicCAS((uint32_t *)&keys[h], KH_EMPTY_PID, pid);
-                if (old == KH_EMPTY_PID) { nnew++; k = pid; }
-                else k = old;
-            }
-            if (k == pid) {
-                atomicAdd(&cnt[h], n);
-                if (FIRSTPOS) atomicMin(&minpos[h], pos);
-                return true;
-            }
-            h = (h + 1u) & MASK;
-        }
-        return false;
-    }
-    __device__ __forceinline__ bool over_limit() const { return *(volatile uint32_t *)nd > LIMIT; }
-};
-
-// The G tier's first attempt: a table of 8192 slots in LDS (64 KB: protein id | count in the low and lowest position in the
-// high 16 bits of one word, so the query must be shorter than 65 535 k-mers).  A query of a skewed database that overflows
-// its group table typically has a few thousand distinct hits behind tens of thousands of postings: here those postings
-// are LDS atomics instead of line fills and write-backs of a multi-megabyte table in HBM.
-#define BIG_LOG2CAP 13
-struct BigLdsTable {
-    uint32_t *keys, *val, *nd;
-    static constexpr uint32_t CAP = 1u << BIG_LOG2CAP;
-    static constexpr uint32_t LIMIT = CAP - CAP / 4;  // keep 25 % free
-    __device__ __forceinline__ bool add_n(uint32_t pid, uint32_t pos, uint32_t n, uint32_t &nnew) const
-    {
-        uint32_t h = (pid * 0x9E3779B1u) >> (32 - BIG_LOG2CAP);
-        for (uint32_t t = 0; t < 128u; t++) {  // a table this crowded is handed to the HBM path
-            uint32_t k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (k == KH_EMPTY_PID) {
-                const uint32_t old = atomicCAS(&keys[h], KH_EMPTY_PID, pid);
-                // the distinct hits are counted as they come (at most 8192 bumps of one LDS word per query): the attempt is
-                // given up the moment the table is three quarters full, not after every further id has walked a full table
-                if (old == KH_EMPTY_PID) { k = pid; if (atomicAdd(nd, 1u) >= LIMIT) return false; }
-                else k = old;
-            }
-            if (k == pid) {
-                atomicAdd(&val[h], n);  // counts stay below 65 536: one per position of the query at most
-                uint32_t old = __hip_atomic_load(&val[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                while (pos < (old >> 16)) {
-                    const uint32_t seen = atomicCAS(&val[h], old, (old & 0xFFFFu) | (pos << 16));
-                    if (seen == old) break;
-                    old = seen;
-                }
-                return true;
-            }
-            h = (h + 1u) & (CAP - 1u);
-        }
-        return false;
-    }
-    __device__ __forceinline__ bool over_limit() const { return false; }
-};
-
-// A query with more distinct hits than the LDS table holds is partitioned by protein-id range (count_global_kernel):
-// these two "tables" take the place of a counting table in the postings sweep -- the first counts the items per range,
-// the second writes them to their range's bucket.  An item is (protein id, position | run length << 16).
-#define G_MAX_RANGES 64u
-__device__ __forceinline__ uint32_t g_range_of(uint32_t pid, uint32_t R) { return (uint32_t)(((uint64_t)(pid * 0x85EBCA6Bu) * R) >> 32); }
-struct RangeHist {
-    uint32_t *cnt, *nd;
-    uint32_t R;
-    __device__ __forceinline__ bool add_n(uint32_t pid, uint32_t, uint32_t, uint32_t &) const { atomicAdd(&cnt[g_range_of(pid, R)], 1u); return true; }
-    __device__ __forceinline__ bool over_limit() const { return false; }
-};
-struct RangeScatter {
-    uint32_t *cur, *nd;
-    uint2 *items;
-    uint32_t R;
-    const uint32_t *first;  // first item of every bucket
-    uint32_t cap;           // items a bucket holds (optimistic partition: the same for all; exact sizes: no limit)
-    uint32_t *ovf;          // set when a bucket is full
-    __device__ __forceinline__ bool add_n(uint32_t pid, uint32_t pos, uint32_t n, uint32_t &) const
-    {
-        const uint32_t r = g_range_of(pid, R);
-        const uint32_t at = atomicAdd(&cur[r], 1u);
-        if (at - first[r] < cap) items[at] = make_uint2(pid, pos | (n << 16));
-        else *ovf = 1u;
-        return true;
-    }
-    __device__ __forceinline__ bool over_limit() const { return false; }
-};
-
 // A slot is 16 bytes {protein id, count, lowest position, -}: one memory line per table add.  As three arrays an add
 // touched three random lines of a table that is megabytes large, and the tier ran at the speed of those line fills and
 // write-backs (14 ms per batch on the skewed database, 53 GB of traffic).
@@ -627,172 +529,7 @@ struct GlobalTable {
         }
         return false;
     }
-    __device__ __forceinline__ bool over_limit() const { return false; }
 };
-
-struct PostCtr {
-    uint32_t post, lists, lids;
-    __device__ void clear() { post = lists = lids = 0; }
-};
-
-// Adjacent positions of a query mostly hit the same proteins (a homologous stretch), so
-// lane i and lane i+1 usually carry the same id in the same head slot.  Sixty-four lanes
-// adding to one LDS word serialise; instead the first lane of every run of equal ids adds
-// the whole run at once (run length from a ballot of the change points).
-template <class Table>
-__device__ __forceinline__ bool add_runs(const Table &tab, uint32_t x, uint32_t pos, uint32_t &nnew)
-{
-    const uint32_t lane = lane_id();
-    const uint32_t prev = __shfl_up(x, 1, 64);
-    const bool change = (lane == 0) || (prev != x);
-    const unsigned long long cm = __ballot(change);
-    bool ok = true;
-    if (change && x != KH_EMPTY_PID) {
-        const unsigned long long above = (lane == 63) ? 0ull : (cm >> (lane + 1));
-        const uint32_t len = above ? (uint32_t)__ffsll((long long)above) : 64u - lane;
-        ok = tab.add_n(x, pos, len, nnew);
-    }
-    return ok;
-}
-
-// NWIN 64-position windows of one query, processed by one wave with all their memory
-// round trips overlapped: (1) the probe results of every window, (2) the 16-byte heads of
-// every postings list (count + first three ids), (3) the remaining ids of all lists,
-// spread evenly over the 64 lanes whatever the individual list lengths are (per-window
-// prefix sum of the leftovers, owner found by binary search in LDS), then the counter
-// increments (KCombStore.Get + the id loop of search.go:427-436).  Window k starts at
-// c0 + k*stride.  `s_pref` is 64 words of LDS private to the wave.  No workgroup
-// barriers inside.  COUNT_ONLY: only sum the postings (G tier sizing pass).
-// G tier: postings lists of more than LONG_LIST ids are not expanded by the wave that meets them: they go on a list in
-// LDS and the whole workgroup expands them afterwards, FLAT -- item t of all the lists together belongs to the list found
-// by binary search in the prefix of their lengths -- a thread per id.  One wave walking a 9 000-protein list 64 ids at a
-// time, for each of the 21 positions of a shared motif, is 3 000 dependent round trips while fifteen waves wait.
-#define LONG_LIST 8u
-#define LONG_SINK_CAP 960u   /* 15 entries per lane; with 1024 the kernel's LDS was 56 bytes over half a CU's: one workgroup per CU */
-#define LONG_SINK_LIFT 512u  /* first step of the binary lifting over the prefix: the largest power of two below the capacity */
-struct LongSink {
-    uint32_t n;
-    uint32_t off[LONG_SINK_CAP], pos[LONG_SINK_CAP], cnt[LONG_SINK_CAP];  // cnt becomes the exclusive prefix
-    uint32_t total;
-};
-
-template <class Table, int NWIN, bool COUNT_ONLY>
-__device__ __forceinline__ bool count_windows(const CountParams &p, const uint32_t *vals,
-                                              int32_t size, int32_t c0, int32_t stride, const Table &tab, PostCtr &c,
-                                              volatile uint32_t *s_pref, LongSink *sink = nullptr)
-{
-    const uint32_t lane = lane_id();
-    uint32_t v[NWIN];
-    uint4 h[NWIN];
-#pragma unroll
-    for (int k = 0; k < NWIN; k++) {
-        const int32_t pos = c0 + k * stride + (int32_t)lane;
-        v[k] = 0u;
-        h[k] = make_uint4(0, 0, 0, 0);
-        if (pos < size) {
-            v[k] = vals[pos];
-            if (v[k] & KH_INLINE_BIT) h[k] = make_uint4(1u, v[k] & ~KH_INLINE_BIT, 0, 0);
-            else if (v[k] != 0u) h[k] = reinterpret_cast<const uint4 *>(p.arena)[v[k]];  // {count, id0, id1, id2}
-        }
-        if (!COUNT_ONLY && sink && h[k].x > LONG_LIST) {
-            const uint32_t slot = atomicAdd(&sink->n, 1u);
-            if (slot < LONG_SINK_CAP) {  // (a full list: the wave expands it itself, below)
-                sink->off[slot] = v[k]; sink->pos[slot] = (uint32_t)pos; sink->cnt[slot] = h[k].x;
-                c.post += h[k].x; c.lists++; c.lids += h[k].x;
-                h[k] = make_uint4(0, 0, 0, 0);
-                v[k] = 0u;
-            }
-        }
-    }
-    bool ok = true;
-    uint32_t nnew = 0;
-    // leftovers (ids beyond the three that came with the head): all their loads are issued
-    // before anything is consumed
-    constexpr int XIT = 2;  // leftover rounds kept in registers per window (64 ids each)
-    uint32_t xid[NWIN][XIT], xpos[NWIN][XIT];
-    uint32_t xtotal[NWIN];
-    if (!COUNT_ONLY) {
-#pragma unroll
-        for (int k = 0; k < NWIN; k++) {
-            const uint32_t lcnt = h[k].x;
-            const uint32_t extra = lcnt > 3u ? lcnt - 3u : 0u;
-            uint32_t inc = extra;  // inclusive prefix over the wave
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t t = __shfl_up(inc, o, 64);
-                if ((int)lane >= o) inc += t;
-            }
-            xtotal[k] = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            s_pref[k * 64 + lane] = inc - extra;  // exclusive prefix
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < NWIN; k++) {
-            const volatile uint32_t *pref = s_pref + k * 64;
-#pragma unroll
-            for (int it = 0; it < XIT; it++) {
-                const uint32_t t = (uint32_t)it * 64u + lane;
-                const bool act = t < xtotal[k];
-                uint32_t lo = 0;
-                if (act) {  // largest lane with pref[lane] <= t owns leftover t
-#pragma unroll
-                    for (int sft = 32; sft > 0; sft >>= 1)
-                        if (pref[lo + sft] <= t) lo += sft;
-                }
-                // executed by all lanes: the owner may be a lane that is idle in this round
-                const uint32_t off = __shfl(v[k], (int)lo, 64);
-                xid[k][it] = KH_EMPTY_PID;
-                xpos[k][it] = (uint32_t)(c0 + k * stride) + lo;
-                if (act) xid[k][it] = p.arena[(uint64_t)off * 4 + 4 + (t - pref[lo])];
-            }
-        }
-        // very long lists (more than XIT*64 leftovers in one window): counted as they arrive
-#pragma unroll
-        for (int k = 0; k < NWIN; k++) {
-            const volatile uint32_t *pref = s_pref + k * 64;
-            for (uint32_t t0 = XIT * 64u; t0 < xtotal[k]; t0 += 64) {
-                const uint32_t t = t0 + lane;
-                const bool act = t < xtotal[k];
-                uint32_t lo = 0;
-                if (act) {
-#pragma unroll
-                    for (int sft = 32; sft > 0; sft >>= 1)
-                        if (pref[lo + sft] <= t) lo += sft;
-                }
-                const uint32_t off = __shfl(v[k], (int)lo, 64);
-                if (act) ok = ok && tab.add_n(p.arena[(uint64_t)off * 4 + 4 + (t - pref[lo])], (uint32_t)(c0 + k * stride) + lo, 1u, nnew);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    // heads: inline ids and the first three ids of every list
-#pragma unroll
-    for (int k = 0; k < NWIN; k++) {
-        const uint32_t pos = (uint32_t)(c0 + k * stride) + lane;
-        const uint32_t lcnt = h[k].x;
-        if (lcnt != 0u) {
-            c.post += lcnt;
-            if (!(v[k] & KH_INLINE_BIT)) { c.lists++; c.lids += lcnt; }
-        }
-        if (!COUNT_ONLY) {  // all lanes take part: run heads add for their whole run
-            ok = add_runs(tab, lcnt > 0 ? h[k].y : KH_EMPTY_PID, pos, nnew) && ok;
-            ok = add_runs(tab, lcnt > 1 ? h[k].z : KH_EMPTY_PID, pos, nnew) && ok;
-            ok = add_runs(tab, lcnt > 2 ? h[k].w : KH_EMPTY_PID, pos, nnew) && ok;
-        }
-    }
-    if (!COUNT_ONLY) {
-#pragma unroll
-        for (int k = 0; k < NWIN; k++)
-#pragma unroll
-            for (int it = 0; it < XIT; it++)
-                if (xid[k][it] != KH_EMPTY_PID) ok = ok && tab.add_n(xid[k][it], xpos[k][it], 1u, nnew);
-        const uint32_t wave_new = wave_total(nnew);
-        if (lane == 0 && wave_new) atomicAdd(tab.nd, wave_new);
-    }
-    return __all(ok);
-}
 
 // sets bits [b, e) of the not-a-k-mer-start bitmap
 __device__ __forceinline__ void mark_invalid_range(unsigned long long *invalid, uint64_t b, uint64_t e)
@@ -815,13 +552,6 @@ __device__ __forceinline__ void mark_invalid_range(unsigned long long *invalid, 
 #endif
 #define PK_ARENA_ORF_LONG 1024u  /* batches of longer sequences (mean > 200 nt): ORFs of a few hundred residues are common */
 #include "count_pack.hip.inc"
-
-// ---- G tier: counting table in HBM, sized from the query's exact postings count -------------------
-struct NullTable {
-    uint32_t *nd;
-    __device__ __forceinline__ bool add_n(uint32_t, uint32_t, uint32_t, uint32_t &) const { return true; }
-    __device__ __forceinline__ bool over_limit() const { return false; }
-};
 
 // Sums the counter replicas, publishes status, and leaves every piece of per-batch device
 // state zeroed for the next batch (no memsets in the steady state).  One workgroup.
@@ -883,527 +613,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
     }
 }
 
-#ifndef G_MIN_BLOCKS
-#define G_MIN_BLOCKS 1
-#endif
-#ifndef G_NWIN
-#define G_NWIN 2   /* windows of 64 positions a wave has in flight in the G tier's sweeps */
-#endif
-#ifdef KAAMER_PHASE_CLOCK
-__device__ unsigned long long g_gtier_clock[2048][16];
-#endif
-__global__ __launch_bounds__(64 * G_WAVES, G_MIN_BLOCKS) void count_global_kernel(CountParams p)
-{
-    constexpr int WAVES = G_WAVES;
-    __shared__ uint32_t s_nd, s_fail, s_cursor;
-    constexpr int NWIN = G_NWIN;
-    __shared__ uint32_t s_pref[WAVES][NWIN * 64];
-    __shared__ unsigned long long s_post, s_off, s_base, s_reserved;
-    __shared__ uint32_t s_roff[G_MAX_RANGES], s_rcur[G_MAX_RANGES], s_rtotal;  // buckets of a partitioned query
-    __shared__ LongSink s_long;
-    __shared__ uint32_t b_keys[BigLdsTable::CAP], b_val[BigLdsTable::CAP];
-
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const uint32_t n_items = *p.list_count < p.list_cap ? *p.list_count : p.list_cap;
-    // the grid is sized for a batch full of overflowing queries; most batches have none, and the workgroups beyond the
-    // items (all but one when there are none) leave at once -- they take no part in the completion count either
-    const uint32_t n_part = n_items < gridDim.x ? (n_items ? n_items : 1u) : gridDim.x;
-    if (blockIdx.x >= n_part) return;
-    unsigned long long tot_hits = 0, f_post = 0, f_lists = 0, f_lids = 0, mon_hits = 0;
-    uint32_t mon_q = 0;
-#ifdef KAAMER_PHASE_CLOCK   /* tools/phase_clock_gtier.py: where the G tier's time goes, per workgroup (thread 0) */
-    unsigned long long gq_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long gq_start = wall_clock64();
-#endif
-    PostCtr pc;
-    NullTable nt;
-    nt.nd = &s_nd;
-    // the long postings lists a sweep set aside, expanded by all threads into `tab`
-    auto expand_long = [&](const auto &tab) {
-        const uint32_t nl = s_long.n < LONG_SINK_CAP ? s_long.n : LONG_SINK_CAP;
-        if (wv == 0 && nl) {  // lengths -> exclusive prefix (16 entries per lane)
-            constexpr uint32_t PER = LONG_SINK_CAP / 64;
-            uint32_t sum = 0;
-            for (uint32_t i = 0; i < PER; i++) { const uint32_t e = lane * PER + i; sum += e < nl ? s_long.cnt[e] : 0u; }
-            uint32_t inc = sum;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t t = __shfl_up(inc, o, 64);
-                if ((int)lane >= o) inc += t;
-            }
-            uint32_t run = inc - sum;
-            for (uint32_t i = 0; i < PER; i++) {
-                const uint32_t e = lane * PER + i;
-                if (e < nl) { const uint32_t c = s_long.cnt[e]; s_long.cnt[e] = run; run += c; }
-            }
-            if (lane == 63) s_long.total = inc;
-        }
-        __syncthreads();
-        uint32_t nnew = 0;
-        bool ok = true;
-        const uint32_t total = nl ? s_long.total : 0u;
-        // Eight items per thread and round, their arena loads all issued before the first id is used, and the list of an
-        // item found from the previous item's (the next item of a thread is 512 further on: the same list, or the one
-        // after it) instead of a ten-step search in LDS per id.  One dependent (search -> load -> add) chain per id made
-        // a monster query's sweep ~1 500 cycles per id and thread: 0.6 ms for half a million postings, three sweeps per
-        // query, and the tier ended when the slowest workgroup had done two of them (4.5 ms per skewed batch).
-#ifndef G_EXPAND_UNROLL
-#define G_EXPAND_UNROLL 8  /* measured on the skewed batch: 4 -> 5.28 ms, 8 -> 4.36, 16 -> 4.42, 32 -> 4.55 */
-#endif
-        constexpr int EU = G_EXPAND_UNROLL;
-        uint32_t e = 0;  // largest e with prefix[e] <= the thread's current item
-        auto find_list = [&](uint32_t t) {
-            if (e + 1u < nl && s_long.cnt[e + 1u] <= t) {      // not in the current list any more
-                e++;
-                if (e + 1u < nl && s_long.cnt[e + 1u] <= t) {  // nor in the next one: search
-                    e = 0;
-#pragma unroll
-                    for (uint32_t sft = LONG_SINK_LIFT; sft > 0; sft >>= 1)
-                        if (e + sft < nl && s_long.cnt[e + sft] <= t) e += sft;
-                }
-            }
-        };
-        for (uint32_t t0 = tid; t0 < total; t0 += EU * 64 * WAVES) {
-            if (s_fail) break;  // (the table gave up: no point in the rest)
-            uint32_t ids[EU], pos_[EU];
-#pragma unroll
-            for (int u = 0; u < EU; u++) {
-                const uint32_t t = t0 + (uint32_t)u * 64 * WAVES;
-                const uint32_t tt = t < total ? t : total - 1u;  // (clamped: the load is issued whatever; used only if t < total)
-                find_list(tt);
-                ids[u] = p.arena[(uint64_t)s_long.off[e] * 4 + 1 + (tt - s_long.cnt[e])];
-                pos_[u] = s_long.pos[e];
-            }
-#pragma unroll
-            for (int u = 0; u < EU; u++)
-                if (t0 + (uint32_t)u * 64 * WAVES < total)
-                    if (!tab.add_n(ids[u], pos_[u], 1u, nnew)) { ok = false; s_fail = 1; }
-        }
-        const uint32_t wn = wave_total(nnew);
-        if (lane == 0 && wn) atomicAdd(&s_nd, wn);
-        if (!ok) s_fail = 1;
-    };
-
-    // items are handed out by ticket (after the first one): a query here costs anything from microseconds to
-    // milliseconds, and two expensive ones on the same workgroup's static share were the tier's tail
-    __shared__ uint32_t s_item;
-    for (uint32_t item = blockIdx.x; item < n_items;) {
-        const WorkItem wi = p.list[item];
-        const uint32_t q = wi.q;
-        // a negative size: the query was sent here unseen (its table does not fit a wave's arena, count_pack.hip.inc), so
-        // its postings have not been counted anywhere yet; otherwise it overflowed its table and they have
-        const bool fresh = wi.size < 0;
-        const int32_t size = fresh ? -wi.size : wi.size;
-        const uint32_t *vals = p.vals + wi.aa_off;
-        if (tid == 0) {
-            s_nd = 0; s_fail = 0; s_post = 0; s_cursor = 0; s_long.n = 0;
-            s_item = atomicAdd(p.queue_head + (SLOT_G_TICKET - SLOT_QUEUE_HEAD), 1u) + n_part;  // the next item of this workgroup
-        }
-        __syncthreads();
-        item = s_item;
-#ifdef KAAMER_PHASE_CLOCK
-        unsigned long long gq_t = wall_clock64();
-        const unsigned long long gq_t0 = gq_t;
-#define GQ_LAP(i) { if (tid == 0) { const unsigned long long t_ = wall_clock64(); gq_acc[i] += t_ - gq_t; gq_t = t_; } }
-#else
-#define GQ_LAP(i) { }
-#endif
-        // pass 1: exact number of postings (an upper bound of the distinct proteins)
-        pc.clear();
-        for (int32_t r0 = 0; r0 < size; r0 += 64 * WAVES * NWIN)
-            count_windows<NullTable, NWIN, true>(p, vals, size, r0 + 64 * (int32_t)wv, 64 * WAVES, nt, pc, s_pref[wv]);
-        {
-            const unsigned long long wp = wave_total(pc.post);
-            if (lane == 0 && wp) atomicAdd(&s_post, wp);
-            if (fresh) {
-                const uint32_t wl = wave_total(pc.lists), wi_ = wave_total(pc.lids);
-                if (lane == 0) { f_post += wp; f_lists += wl; f_lids += wi_; }
-            }
-        }
-        __syncthreads();
-        // ---- in LDS: the whole query in the big table first.  A query with more distinct hits than it holds (a skewed
-        // database: tens of thousands of proteins behind a few motifs) has its postings PARTITIONED by protein-id range
-        // (a hash of the id) into R buckets in the G arena -- one counting sweep for the bucket sizes, one sweep that
-        // scatters (id, position, run length) -- and then every bucket is counted in the LDS table on its own and its
-        // hits appended to the query's list (space for min(postings, proteins) entries is taken once).  Three sweeps of
-        // the query and sequential bucket reads instead of one random line fill and write-back per posting in a
-        // multi-megabyte table in HBM (6.5 of the skewed batch's 8.3 ms); counting the ranges by re-sweeping the whole
-        // query per range (tried first) costs R sweeps and lost for the monsters (profiles/r03_count_kernels.md).
-        if (size < 65535) {
-            BigLdsTable bt;
-            bt.keys = b_keys; bt.val = b_val; bt.nd = &s_nd;
-            bool q_done = false, give_up = false;
-            uint32_t written = 0;
-            if (tid == 0) s_base = ~0ull;
-            // counts bucket `r` (or, r == R: everything, straight from the postings) in the LDS table and appends its hits
-            auto count_bucket = [&](uint32_t R, uint32_t r, const uint2 *items) -> int {  // 0 ok, 1 table overflow, 2 no space
-                __syncthreads();
-                if (tid == 0) { s_nd = 0; s_fail = 0; s_cursor = 0; s_long.n = 0; }
-                for (uint32_t i = tid; i < BigLdsTable::CAP; i += 64 * WAVES) { b_keys[i] = KH_EMPTY_PID; b_val[i] = 0xFFFF0000u; }
-                __syncthreads();
-                if (R == 1u) {
-                    pc.clear();
-                    for (int32_t r0 = 0; r0 < size && !s_fail; r0 += 64 * WAVES * NWIN) {
-                        const bool ok = count_windows<BigLdsTable, NWIN, false>(p, vals, size, r0 + 64 * (int32_t)wv, 64 * WAVES, bt, pc,
-                                                                               s_pref[wv], &s_long);
-                        if (!ok) s_fail = 1;
-                    }
-                    __syncthreads();
-                    expand_long(bt);
-                } else {
-                    uint32_t nnew = 0;
-                    const uint32_t b0 = s_roff[r], b1 = s_rcur[r];   // (the scatter sweep left every cursor at its bucket's end)
-                    for (uint32_t i = b0 + tid; i < b1; i += 64 * WAVES) {
-                        if (s_fail) break;
-                        const uint2 it = items[i];
-                        if (!bt.add_n(it.x, it.y & 0xFFFFu, it.y >> 16, nnew)) s_fail = 1;
-                    }
-                }
-                __syncthreads();
-                const uint32_t total = s_nd;
-                if (s_fail != 0u || total > BigLdsTable::LIMIT) return 1;
-                if (s_base == ~0ull && total > 0) {  // (workgroup-uniform: read after a barrier)
-                    __syncthreads();
-                    if (tid == 0) {
-                        unsigned long long want = total;  // one bucket: exactly the hits; more: the bound
-                        if (R > 1u) want = s_post < p.n_proteins ? s_post : p.n_proteins;
-                        s_base = tail_alloc(p, (uint32_t)(want > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : want));
-                        s_reserved = want;
-                        if (s_base == ~0ull) s_fail = 2;
-                    }
-                    __syncthreads();
-                    if (s_fail == 2u) return 2;
-                }
-                const unsigned long long base = s_base;
-                if (total > 0) {
-                    if ((unsigned long long)written + total > s_reserved) { if (tid == 0) atomicOr(p.status, (uint32_t)ST_POOL_FULL); return 2; }
-                    for (uint32_t i0 = wv * 64u; i0 < BigLdsTable::CAP; i0 += 64 * WAVES) {
-                        const uint32_t k = b_keys[i0 + lane];
-                        const bool has = k != KH_EMPTY_PID;
-                        const unsigned long long bm = __ballot(has);
-                        uint32_t wbase = 0;
-                        if (lane == 0 && bm) wbase = atomicAdd(&s_cursor, (uint32_t)__popcll(bm));
-                        wbase = __shfl(wbase, 0, 64);
-                        if (has) {
-                            const unsigned long long idx = base + written + wbase + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
-                            const uint32_t v = b_val[i0 + lane];
-                            p.hit_pid[idx] = k;
-                            p.hit_km[idx] = v & 0xFFFFu;
-                            p.hit_fp[idx] = v >> 16;
-                        }
-                    }
-                    written += total;
-                }
-                return 0;
-            };
-            GQ_LAP(0);   // pass 1
-            int rc1 = count_bucket(1u, 0u, nullptr);
-            GQ_LAP(1);   // the whole query in the LDS table
-            if (rc1 == 0 || rc1 == 2) q_done = true;
-            if (rc1 == 1) {
-                // ---- partition: bucket sizes, offsets, scatter.  The sizes are GUESSED first: the ranges are a hash of the
-                // protein id, so every bucket gets postings / R items give or take a few per cent, and buckets of 5/4 of that
-                // (+ 2 048) spare the sweep that counts them -- one of a monster's three sweeps over hundreds of thousands
-                // of postings.  A bucket that is full after all (a few ids with very many positions in one range) sends the
-                // query through the exact sizes (attempt 1).
-                uint32_t R = (uint32_t)(s_post / 16384ull) + 2u;  // ~3 000 distinct ids per bucket when ids repeat ~6 times
-                if (R > G_MAX_RANGES) R = G_MAX_RANGES;
-                for (int attempt = 0; attempt < 2 && !q_done; attempt++) {
-                    uint32_t cap_items = 0xFFFFFFFFu;
-                    __syncthreads();
-                    if (tid == 0) { s_fail = 0; s_long.n = 0; s_cursor = 0; }   // (s_cursor: "a guessed bucket was full"; count_bucket resets it)
-                    if (attempt == 0) {
-                        const unsigned long long per = s_post / R;
-                        const unsigned long long c = per + per / 4ull + 2048ull;
-                        if (c * R > 0x7FFFFFFFull) continue;   // (workgroup-uniform) too many postings to guess: count them
-                        cap_items = (uint32_t)c;
-                        if (tid < G_MAX_RANGES) { s_roff[tid] = tid * cap_items; s_rcur[tid] = tid * cap_items; }
-                        if (tid == 0) s_rtotal = R * cap_items;
-                        __syncthreads();
-                    } else {
-                        if (tid < G_MAX_RANGES) s_roff[tid] = 0;
-                        __syncthreads();
-                        RangeHist rh;
-                        rh.cnt = s_roff; rh.nd = &s_nd; rh.R = R;
-                        pc.clear();
-                        for (int32_t r0 = 0; r0 < size; r0 += 64 * WAVES * NWIN)
-                            count_windows<RangeHist, NWIN, false>(p, vals, size, r0 + 64 * (int32_t)wv, 64 * WAVES, rh, pc, s_pref[wv], &s_long);
-                        __syncthreads();
-                        expand_long(rh);
-                        __syncthreads();
-                        if (wv == 0) {  // exclusive prefix of the bucket sizes (R <= 64: one lane each); cursors start at the offsets
-                            const uint32_t v = lane < R ? s_roff[lane] : 0u;
-                            uint32_t inc = v;
-#pragma unroll
-                            for (int o = 1; o < 64; o <<= 1) {
-                                const uint32_t t = __shfl_up(inc, o, 64);
-                                if ((int)lane >= o) inc += t;
-                            }
-                            s_roff[lane] = inc - v;
-                            s_rcur[lane] = inc - v;
-                            if (lane == 63) s_rtotal = inc;
-                        }
-                        __syncthreads();
-                    }
-                    const uint32_t n_items = s_rtotal;
-                    if (tid == 0) {  // 8 bytes per item: half a 16-byte slot of the arena
-                        const unsigned long long need = ((unsigned long long)n_items + 1ull) / 2ull + 1ull;
-                        const unsigned long long off = atomicAdd(p.g_cursor, need);
-                        if (off + need > p.g_slots) { atomicOr(p.status, (uint32_t)ST_G_ARENA_FULL); s_off = ~0ull; }
-                        else s_off = off;
-                        s_long.n = 0;
-                    }
-                    __syncthreads();
-                    if (s_off == ~0ull) { give_up = true; q_done = true; break; }
-                    uint2 *items = reinterpret_cast<uint2 *>(p.g_keys + 4ull * s_off);
-                    RangeScatter rsc;
-                    rsc.cur = s_rcur; rsc.items = items; rsc.nd = &s_nd; rsc.R = R;
-                    rsc.first = s_roff; rsc.cap = cap_items; rsc.ovf = &s_cursor;
-                    pc.clear();
-                    for (int32_t r0 = 0; r0 < size; r0 += 64 * WAVES * NWIN)
-                        count_windows<RangeScatter, NWIN, false>(p, vals, size, r0 + 64 * (int32_t)wv, 64 * WAVES, rsc, pc, s_pref[wv], &s_long);
-                    __syncthreads();
-                    expand_long(rsc);
-                    // the buckets were written by this workgroup's own stores into a region nobody has loaded from (g_cursor
-                    // never hands a region out twice within a launch): after the barrier (which drains vmcnt) the loads
-                    // below miss the L1 and find them in the L2
-                    __syncthreads();
-                    GQ_LAP(2);   // partition sweeps
-                    if (s_cursor != 0u) continue;   // (workgroup-uniform: read after a barrier) a guessed bucket was too small
-                    bool overflow = false;
-                    for (uint32_t r = 0; r < R && !q_done; r++) {
-                        const int rc = count_bucket(R, r, items);
-                        if (rc == 1) { overflow = true; break; }
-                        if (rc == 2) { q_done = true; give_up = true; }
-                    }
-                    GQ_LAP(3);   // buckets
-#ifdef KAAMER_PHASE_CLOCK
-                    if (tid == 0) { gq_acc[6] += 1; gq_acc[7] += s_post; }
-#endif
-                    if (!overflow) q_done = true;  // else: a bucket with more distinct ids than the table holds -> the table in HBM
-                    else { written = 0; }
-                    break;
-                }
-            }
-            __syncthreads();
-            if (q_done) {
-                const unsigned long long base = give_up ? ~0ull : s_base;
-                if (wv == 0 && base != ~0ull) {
-                    tot_hits += written;
-                    if (written > G_MONSTER_HITS) { mon_hits += written; mon_q++; }
-                }
-                if (tid == 0) { p.q_cnt[q] = (base != ~0ull) ? written : 0u; p.hit_off[q] = (base == ~0ull || written == 0) ? 0 : base; }
-                __syncthreads();
-#ifdef KAAMER_PHASE_CLOCK
-                if (tid == 0) { const unsigned long long d_ = wall_clock64() - gq_t0; gq_acc[5] += 1; if (d_ > gq_acc[8]) { gq_acc[8] = d_; gq_acc[9] = s_post; } }
-#endif
-                continue;
-            }
-            if (tid == 0) { s_nd = 0; s_fail = 0; s_cursor = 0; s_long.n = 0; }  // (a bucket overflowed: the table in HBM)
-            __syncthreads();
-        }
-        unsigned long long bound = s_post;
-        if (bound > p.n_proteins) bound = p.n_proteins;
-        uint32_t log2cap = 10;
-        while ((1ull << log2cap) < 2 * bound && log2cap < 31) log2cap++;
-        const unsigned long long cap = 1ull << log2cap;
-        if (tid == 0) {
-            const unsigned long long off = atomicAdd(p.g_cursor, cap);
-            if (off + cap > p.g_slots) { atomicOr(p.status, (uint32_t)ST_G_ARENA_FULL); s_off = ~0ull; }
-            else s_off = off;
-        }
-        __syncthreads();
-        const unsigned long long off = s_off;
-        if (off == ~0ull) {
-            if (tid == 0) { p.q_cnt[q] = 0; p.hit_off[q] = 0; }
-            __syncthreads();
-            continue;
-        }
-        GlobalTable gt;
-        gt.slots = p.g_keys + 4ull * off; gt.nd = &s_nd; gt.log2cap = log2cap;
-        // The table belongs to this workgroup alone (g_cursor never hands out a region twice within one launch) and is
-        // touched with plain 16-byte initialisation stores, workgroup-scope atomics and, at the end, plain read-out
-        // loads.  Nothing loads from it before the read-out, so no stale line can sit in the L1 (write-through, holds
-        // no line of the table); the atomics are performed in the XCD's L2, where the initialisation stores went.  A
-        // workgroup barrier (which drains vmcnt) between the phases is enough: no agent-scope fence -- a full L2
-        // write-back on this part.
-        for (unsigned long long i = tid; i < cap; i += 64 * WAVES)
-            reinterpret_cast<uint4 *>(gt.slots)[i] = make_uint4(KH_EMPTY_PID, 0u, 0xFFFFFFFFu, 0u);
-        __syncthreads();
-        // pass 2: count
-        pc.clear();
-        for (int32_t r0 = 0; r0 < size; r0 += 64 * WAVES * NWIN) {
-            const bool ok = count_windows<GlobalTable, NWIN, false>(p, vals, size, r0 + 64 * (int32_t)wv, 64 * WAVES, gt,
-                                                                   pc, s_pref[wv], &s_long);
-            if (!ok) s_fail = 1;
-        }
-        __syncthreads();
-        expand_long(gt);
-        __syncthreads();
-        // lookups, postings and queries were already counted by the group kernel
-        const uint32_t total = s_nd;
-        const bool failed = s_fail != 0;
-        if (tid == 0) {
-            if (failed) { atomicOr(p.status, (uint32_t)ST_G_TABLE_FULL); s_base = ~0ull; }
-            else if (total == 0) s_base = 0;
-            else s_base = tail_alloc(p, total);
-        }
-        __syncthreads();
-        const unsigned long long base = s_base;
-        if (base != ~0ull && total > 0) {
-            // four stripes of the table per round trip, a 16-byte slot per lane
-            for (unsigned long long i0 = (unsigned long long)wv * 64; i0 < cap; i0 += 4ull * 64 * WAVES) {
-                uint32_t k4[4], c4[4], m4[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned long long i = i0 + (unsigned long long)u * 64 * WAVES + lane;
-                    const uint4 sv = reinterpret_cast<const uint4 *>(gt.slots)[i < cap ? i : cap - 1];
-                    k4[u] = i < cap ? sv.x : KH_EMPTY_PID; c4[u] = sv.y; m4[u] = sv.z;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const bool has = k4[u] != KH_EMPTY_PID;
-                    const unsigned long long bm = __ballot(has);
-                    uint32_t wbase = 0;
-                    if (lane == 0 && bm) wbase = atomicAdd(&s_cursor, (uint32_t)__popcll(bm));
-                    wbase = __shfl(wbase, 0, 64);
-                    if (has) {
-                        const uint32_t idx = wbase + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull));
-                        p.hit_pid[base + idx] = k4[u];
-                        p.hit_km[base + idx] = c4[u];
-                        p.hit_fp[base + idx] = m4[u];
-                    }
-                }
-            }
-            if (wv == 0) {
-                tot_hits += total;
-                if (total > G_MONSTER_HITS) { mon_hits += total; mon_q++; }
-            }
-        }
-        if (tid == 0) { p.q_cnt[q] = (base != ~0ull) ? total : 0u; p.hit_off[q] = base == ~0ull ? 0 : base; }
-        __syncthreads();
-    }
-#ifdef KAAMER_PHASE_CLOCK
-    if (tid == 0 && blockIdx.x < 2048) {
-        gq_acc[4] = wall_clock64() - gq_start;
-        for (int i = 0; i < 8; i++) g_gtier_clock[blockIdx.x][i] += gq_acc[i];
-        if (gq_acc[8] > g_gtier_clock[blockIdx.x][8]) { g_gtier_clock[blockIdx.x][8] = gq_acc[8]; g_gtier_clock[blockIdx.x][9] = gq_acc[9]; }
-        if (gq_acc[4] > g_gtier_clock[blockIdx.x][10]) g_gtier_clock[blockIdx.x][10] = gq_acc[4];
-    }
-#endif
-    if (lane == 0) {
-        const uint32_t rep = blockIdx.x * WAVES + wv;
-        add_counter(p.counters, rep, CTR_HITS, tot_hits);
-        // (what the queries that left their LDS tables found, and the monsters among them: finalize_body works the next
-        // batch's table scale out without the ones or the others)
-        if (tot_hits) atomicAdd(p.queue_head + (SLOT_G_HITS16 - SLOT_QUEUE_HEAD), (uint32_t)((tot_hits + 15ull) >> 4 > 0x0FFFFFFFull ? 0x0FFFFFFFull : (tot_hits + 15ull) >> 4));
-        if (mon_q) {
-            atomicAdd(p.queue_head + (SLOT_G_MON_HITS16 - SLOT_QUEUE_HEAD), (uint32_t)((mon_hits + 15ull) >> 4 > 0x0FFFFFFFull ? 0x0FFFFFFFull : (mon_hits + 15ull) >> 4));
-            atomicAdd(p.queue_head + (SLOT_G_MONSTERS - SLOT_QUEUE_HEAD), mon_q);
-        }
-        add_counter(p.counters, rep, CTR_POST, f_post);
-        add_counter(p.counters, rep, CTR_LISTS, f_lists);
-        add_counter(p.counters, rep, CTR_LIST_IDS, f_lids);
-    }
-    if (p.fin_out) {
-        // the batch ends here: the last workgroup to arrive does the finalize step
-        __shared__ uint32_t s_last;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // this wave's counter atomics are done
-        __syncthreads();
-        // two levels: 512 workgroups bumping ONE word serialise at ~90 per microsecond (6 us of a 0.2 ms batch);
-        // eight sub-counters (workgroup index mod 8), and the last arrival of each bumps the top one
-        if (tid == 0) {
-            const uint32_t sub = blockIdx.x & 7u, n_sub = (n_part - sub + 7u) >> 3, n_top = n_part < 8u ? n_part : 8u;
-            s_last = 0;
-            if (atomicAdd(p.queue_head + (SLOT_QUEUE_SUB - SLOT_QUEUE_HEAD) + sub, 1u) == n_sub - 1u)
-                s_last = atomicAdd(p.queue_head, 1u) == n_top - 1u;
-        }
-        __syncthreads();
-        if (s_last) {
-            finalize_body<true>(p.counters, p.fin_out, p.fin_small, p.fin_status_out, p.fin_cursors, p.fin_slot_scale, p.fin_scale_cap, p.fin_scale_margin);
-        }
-    }
-}
-
-// PositionHits of the G-tier queries (search.go:442-452): the query's final hit list goes into a
-// table in HBM (id -> index in the list), then every (position, id) sets one bit of that hit's bitmap.
-struct BitsTable {
-    const uint32_t *slots;  // 4 words per slot: {protein id, index in the hit list, -, -}
-    uint32_t *nd;
-    uint32_t log2cap, words;
-    unsigned long long *bits;  // first bitmap of the query
-    __device__ __forceinline__ bool add_n(uint32_t pid, uint32_t pos, uint32_t n, uint32_t &) const
-    {
-        const uint32_t mask = (1u << log2cap) - 1u;
-        uint32_t h = (pid * 0x9E3779B1u) >> (32 - log2cap);
-        for (uint32_t t = 0; t <= mask; t++) {
-            const uint32_t k = __hip_atomic_load(&slots[4ull * h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == pid) {
-                unsigned long long *bm = bits + (unsigned long long)__hip_atomic_load(&slots[4ull * h + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * words;
-                const uint32_t w0 = pos >> 6, b0 = pos & 63u;
-                const uint32_t n0 = n < 64u - b0 ? n : 64u - b0;
-                atomicOr(&bm[w0], (n0 == 64u ? ~0ull : ((1ull << n0) - 1ull)) << b0);
-                if (n > n0) atomicOr(&bm[w0 + 1], (1ull << (n - n0)) - 1ull);
-                return true;
-            }
-            if (k == KH_EMPTY_PID) return false;  // cannot happen: every id of the postings is a hit
-            h = (h + 1u) & mask;
-        }
-        return false;
-    }
-    __device__ __forceinline__ bool over_limit() const { return false; }
-};
-
-__global__ __launch_bounds__(64 * G_WAVES) void positions_global_kernel(CountParams p)
-{
-    constexpr int WAVES = G_WAVES;
-    constexpr int NWIN = 2;
-    __shared__ uint32_t s_nd;
-    __shared__ uint32_t s_pref[WAVES][NWIN * 64];
-    __shared__ unsigned long long s_off;
-    const uint32_t tid = threadIdx.x, wv = tid >> 6;
-    const uint32_t n_items = *p.list_count < p.list_cap ? *p.list_count : p.list_cap;
-    PostCtr pc;
-    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const WorkItem wi = p.list[item];
-        const uint32_t q = wi.q, cnt = p.q_cnt[q];
-        const int32_t size = wi.size < 0 ? -wi.size : wi.size;  // (negative: sent to the G tier unseen, see count_global_kernel)
-        const unsigned long long hoff = p.hit_off[q];
-        uint32_t log2cap = 10;
-        while ((1ull << log2cap) < 2ull * cnt && log2cap < 31) log2cap++;
-        const unsigned long long cap = 1ull << log2cap;
-        if (tid == 0) {
-            s_nd = 0;
-            const unsigned long long off = atomicAdd(p.g_cursor, cap);
-            if (off + cap > p.g_slots) { atomicOr(p.status, (uint32_t)ST_G_ARENA_FULL); s_off = ~0ull; }
-            else s_off = off;
-        }
-        __syncthreads();
-        const unsigned long long off = s_off;
-        if (off == ~0ull || cnt == 0 || size <= 0) { __syncthreads(); continue; }
-        uint32_t *slots = p.g_keys + 4ull * off;
-        for (unsigned long long i = tid; i < cap; i += 64 * WAVES) __hip_atomic_store(&slots[4 * i], KH_EMPTY_PID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const uint32_t mask = (uint32_t)cap - 1u;
-        for (uint32_t i = tid; i < cnt; i += 64 * WAVES) {
-            const uint32_t pid = p.hit_pid[hoff + i];
-            uint32_t h = (pid * 0x9E3779B1u) >> (32 - log2cap);
-            while (atomicCAS(&slots[4ull * h], KH_EMPTY_PID, pid) != KH_EMPTY_PID) h = (h + 1u) & mask;  // ids are distinct, load <= 0.5
-            __hip_atomic_store(&slots[4ull * h + 1], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        BitsTable bt;
-        bt.slots = slots; bt.nd = &s_nd; bt.log2cap = log2cap;
-        bt.words = ((uint32_t)size + 63u) >> 6;
-        bt.bits = p.pos_bits + p.pos_base[q];
-        pc.clear();
-        bool ok = true;
-        for (int32_t r0 = 0; r0 < size; r0 += 64 * WAVES * NWIN)
-            ok = count_windows<BitsTable, NWIN, false>(p, p.vals + wi.aa_off, size, r0 + 64 * (int32_t)wv, 64 * WAVES, bt, pc, s_pref[wv]) && ok;
-        if (!ok && (tid & 63u) == 0) atomicOr(p.status, (uint32_t)ST_G_TABLE_FULL);
-        __syncthreads();
-    }
-}
+#include "count_global.hip.inc"
 
 #include "translate.hip.inc"
 #include "topn.hip.inc"
