@@ -142,6 +142,29 @@ void kaamer_image_free(kaamer_image *img);
 /* host-side point read of an image (builder self-check; not the search path):
  * returns the number of ids under `key`, copies up to cap of them */
 uint32_t kaamer_image_get(const kaamer_image *img, uint32_t key, uint32_t *ids, uint32_t cap);
+/* the load factor the image was built with (after the builders' own rule: outside (0.05, 0.95] it became 0.5) */
+double kaamer_image_load_factor(const kaamer_image *img);
+
+/* kaamer-db -merge: the union of images of the same shard (pkg/mergedb/mergedb.go:42-135, the kmer_store leg:
+ * MergeStores streams every version of every key into store 1; pkg/indexdb/indexdb.go:68-132 then collapses them).
+ * Per key the id set is the union of the inputs' sets, a pair present in two inputs is stored once, identical union sets
+ * share one list, and a key whose union is one id below 2^31 is inline.  An image does not record which window first
+ * referred to a list, so the layout is defined through kaamer_image_build_pairs, whose order is its input's:
+ *     merge(img_0 .. img_{n-1}) := kaamer_image_build_pairs(E(img_0) ++ .. ++ E(img_{n-1}), shard, n_shards, load_factor)
+ * where E(img) lists first the keys whose slot holds a list offset, by (offset, key) ascending, each as (key, id) for its
+ * ids in stored order, then the keys with an inline id by key ascending.  So the lists of img_0 keep their relative order
+ * and are followed by what img_1 adds; every counter of kaamer_image_stats equals that of one build over the union of the
+ * inputs' proteins at the same load factor (only the order of the lists in the arena differs); and the merge of ONE image
+ * built here, at its own load factor, is that image byte for byte (at another load factor: a re-bucketing).
+ * KAAMER_E_ARG: n == 0, a null entry, inputs that differ in shard / n_shards / kmer_size / version, a list offset or count
+ * that points outside its image's arena (checked before anything is dereferenced).  KAAMER_E_CAPACITY / the builders' own
+ * codes for their limits (2^32 - 1 pairs per shard, arena 32 GiB, buckets).  load_factor outside (0.05, 0.95] becomes 0.5. */
+int kaamer_image_merge(const kaamer_image *const *imgs, uint32_t n, double load_factor, kaamer_image **out);
+/* The same image, byte for byte, made on `device` (merge_device.hip): the inputs' buckets and arenas are uploaded, expanded
+ * to pairs there, and the build runs from the sort on as kaamer_image_build_proteins_device's does.  Peak device memory is
+ * that of a build over the same number of pairs (two 8-byte buffers of the enumerated pairs) plus the uploaded inputs. */
+int kaamer_image_merge_device(const kaamer_image *const *imgs, uint32_t n, double load_factor, int device,
+                              kaamer_image **out);
 
 /* ------------------------------------------------------------------------- */
 /* makedb — which proteins a database file contributes and under which ids      */
@@ -170,7 +193,15 @@ int kaamer_makedb_tsv(const char *text, uint64_t len, kaamer_proteins **out);
  *          " [organism]." removed), VERSION -> EntryId, ORGANISM -> Organism + FullTaxonomy, ORIGIN -> the sequence,
  *          upper-cased; names containing ", partial" and sequences shorter than 7 are dropped.
  *   Where the Go code would panic on a malformed entry (a tag line shorter than the column it slices at, an SQ
- *   length beyond the sequence) the entry is dropped; the split-build options -offset / -length are not reproduced. */
+ *   length beyond the sequence) the entry is dropped.
+ *   -offset / -length (kaamer_makedb_text_range below) follow the scan loops (inputFASTA.go:64-125, inputEMBL.go:66-119,
+ *   inputGBK.go:94-118): proteinNb counts '>' headers (FASTA) or "//" lines (EMBL, GBK), text is gathered only while
+ *   proteinNb >= offset, and at proteinNb >= offset + length (Go uint: 64 bits, wrapping) the pending entry is queued and
+ *   the scan ends.  Ids stay the loop's proteinNb: a FASTA range holds records offset .. offset + length - 1 under ids
+ *   k + 1, an EMBL / GBK range records offset + 1 .. offset + length under ids k, so consecutive ranges partition the file
+ *   and only the range that reaches the end of a FASTA file has two records share the last id.  (The FASTA loop leaves the
+ *   entry in place when it breaks, so its closing statement, :120-124, queues that record a second time under the same id:
+ *   reproduced; the record and the KStats counters count it twice.) */
 int kaamer_makedb_embl(const char *text, uint64_t len, kaamer_proteins **out);
 int kaamer_makedb_gbk(const char *text, uint64_t len, kaamer_proteins **out);
 /* The four readers behind one entry point (format: 0 FASTA, 1 TSV, 2 EMBL, 3 GBK), with the reference's scanner limit on
@@ -178,6 +209,17 @@ int kaamer_makedb_gbk(const char *text, uint64_t len, kaamer_proteins **out);
  * (inputFASTA.go:88-89 and the same two lines in the other readers): what was read before the line is processed as if the
  * file ended there.  strict_scanner = 0 (what the four functions above do) reads lines of any length. */
 int kaamer_makedb_text(const char *text, uint64_t len, int32_t format, int32_t strict_scanner, kaamer_proteins **out);
+/* kaamer_makedb_text with the scan loops' -offset / -length (cmd/kaamer-db/main.go:141-142; the rule is stated above).
+ * offset = 0, length = INT64_MAX (the flags' defaults) is kaamer_makedb_text; TSV ignores both (inputTSV.go:40-145 never
+ * reads them). */
+int kaamer_makedb_text_range(const char *text, uint64_t len, int32_t format, int32_t strict_scanner,
+                             uint64_t offset, uint64_t length, kaamer_proteins **out);
+/* kaamer-db -merge, the protein_store leg + KStats (mergedb.go:91-98): the records of every table in argument order; when
+ * an id occurs more than once the later record wins in kaamer_fetch_hits (store 2's Protein overwrites store 1's,
+ * mergedb.go:98); kaamer_proteins_stats is the SUM of the inputs' counters, duplicates included (mergedb.go:91-93).
+ * Divergence: the reference keeps the first database's KStats.Features; this table is dense per feature, so inputs whose
+ * feature names differ are refused (KAAMER_E_ARG).  n == 0 or a null entry: KAAMER_E_ARG. */
+int kaamer_proteins_merge(const kaamer_proteins *const *tables, uint32_t n, kaamer_proteins **out);
 uint32_t kaamer_proteins_count(const kaamer_proteins *p);           /* accepted proteins       */
 const uint32_t *kaamer_proteins_ids(const kaamer_proteins *p);      /* their protein ids       */
 const uint8_t *kaamer_proteins_seqs(const kaamer_proteins *p);      /* packed sequences        */

@@ -383,8 +383,16 @@ SYMBOLS = {
     "kaamer_sharded_search_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
                                              C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    # kaamer-db -merge and the split makedb runs (-offset / -length)
+    "kaamer_image_load_factor": (C.c_double, [C.c_void_p]),
+    "kaamer_image_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]),
+    "kaamer_image_merge_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
+    "kaamer_proteins_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_makedb_text_range": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
 }
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
+FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range
+MAKEDB_LENGTH_ALL = 2 ** 63 - 1      # the default of -length (cmd/kaamer-db/main.go:142: uint(MaxInt))
 
 _lib = None
 

@@ -60,6 +60,19 @@ class Image:
         return cls(h.value)
 
     @classmethod
+    def merge(cls, images, load_factor=0.5, device=None):
+        """kaamer-db -merge: the union of images of one shard (kaamer_image_merge).  device=None: on the host;
+        device=d: the same image made on GPU d (byte-identical)."""
+        images = list(images)
+        arr = (C.c_void_p * max(1, len(images)))(*[im._h for im in images])
+        h = C.c_void_p()
+        if device is None:
+            abi.check(abi.lib().kaamer_image_merge(arr, len(images), load_factor, C.byref(h)))
+        else:
+            abi.check(abi.lib().kaamer_image_merge_device(arr, len(images), load_factor, int(device), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
     def load(cls, path):
         h = C.c_void_p()
         abi.check(abi.lib().kaamer_image_load(str(path).encode(), C.byref(h)))
@@ -67,6 +80,10 @@ class Image:
 
     def save(self, path):
         abi.check(abi.lib().kaamer_image_save(self._h, str(path).encode()))
+
+    @property
+    def load_factor(self):
+        return float(abi.lib().kaamer_image_load_factor(self._h))
 
     def stats(self):
         s = abi.ImageStats()
@@ -121,6 +138,25 @@ class Proteins:
     @classmethod
     def from_gbk(cls, text):
         return cls._make(abi.lib().kaamer_makedb_gbk, text)
+
+    @classmethod
+    def from_text(cls, text, fmt, offset=0, length=None, strict_scanner=False):
+        """kaamer_makedb_text_range: fmt is abi.FASTA / TSV / EMBL / GBK; offset / length are kaamer-db -make's -offset / -length
+        (length=None: the flag's default, the rest of the file)."""
+        text = bytes(text)
+        h = C.c_void_p()
+        abi.check(abi.lib().kaamer_makedb_text_range(text, len(text), int(fmt), int(bool(strict_scanner)), int(offset),
+                                                     abi.MAKEDB_LENGTH_ALL if length is None else int(length), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def merge(cls, tables):
+        """kaamer-db -merge on the protein tables (kaamer_proteins_merge): records in argument order, a later record of an id wins"""
+        tables = list(tables)
+        arr = (C.c_void_p * max(1, len(tables)))(*[t._h for t in tables])
+        h = C.c_void_p()
+        abi.check(abi.lib().kaamer_proteins_merge(arr, len(tables), C.byref(h)))
+        return cls(h.value)
 
     @classmethod
     def load(cls, path):

@@ -469,6 +469,101 @@ int kaamer_image_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
     return rc;
 }
 
+}  // extern "C"
+
+// What both merge forms check before anything is dereferenced: the inputs agree on shard, n_shards, kmer_size and version,
+// and every list reference stays inside its image's arena.  n_pairs[i] = the number of pairs image i enumerates.
+int kaamer_merge_check(const kaamer_image *const *imgs, uint32_t n, uint64_t *n_pairs)
+{
+    if (!imgs || n == 0) return kaamer_fail(KAAMER_E_ARG, "image_merge: no input");
+    for (uint32_t i = 0; i < n; i++) {
+        if (!imgs[i] || !imgs[i]->buckets || !imgs[i]->arena) return kaamer_fail(KAAMER_E_ARG, "image_merge: input %u is null", i);
+        const kh_image_header &h = imgs[i]->hdr, &h0 = imgs[0]->hdr;
+        if (h.version != KH_IMAGE_VERSION || h.kmer_size != KAAMER_KMER_SIZE || h.n_shards == 0 || h.shard >= h.n_shards ||
+            h.n_buckets == 0 || h.n_buckets >= (1ull << 32) || h.arena_words < 4)
+            return kaamer_fail(KAAMER_E_ARG, "image_merge: input %u is not an image of this layout", i);
+        if (h.shard != h0.shard || h.n_shards != h0.n_shards || h.kmer_size != h0.kmer_size || h.version != h0.version)
+            return kaamer_fail(KAAMER_E_ARG, "image_merge: input %u is shard %u of %u, input 0 is shard %u of %u", i, h.shard, h.n_shards,
+                               h0.shard, h0.n_shards);
+        const uint64_t nb = h.n_buckets, aw = h.arena_words;
+        const unsigned nt = n_threads();
+        std::vector<uint64_t> part(nt, 0);
+        std::atomic<int> bad_ref(0);
+        parallel_for((size_t)nb, nt, [&](size_t b0, size_t b1, unsigned t) {
+            uint64_t c = 0;
+            for (size_t b = b0; b < b1; b++)
+                for (int s = 0; s < KH_SLOTS_PER_BUCKET; s++) {
+                    const kh_slot &sl = imgs[i]->buckets[b].s[s];
+                    if (sl.key == KH_EMPTY_KEY) continue;
+                    if (sl.val & KH_INLINE_BIT) { c++; continue; }
+                    const uint64_t off = (uint64_t)sl.val * 4;
+                    if (sl.val == 0 || off + 1 > aw || off + 1 + imgs[i]->arena[off] > aw) { bad_ref = 1; continue; }
+                    c += imgs[i]->arena[off];
+                }
+            part[t] += c;
+        });
+        if (bad_ref) return kaamer_fail(KAAMER_E_ARG, "image_merge: input %u: postings reference out of range", i);
+        n_pairs[i] = 0;
+        for (uint64_t c : part) n_pairs[i] += c;
+    }
+    return KAAMER_OK;
+}
+
+extern "C" {
+
+// mergedb.go:42-135 (kmer_store leg) + indexdb.go:68-132 over the union.  The merged image is
+// kaamer_image_build_pairs(E(img_0) ++ E(img_1) ++ ...): E(img) lists the keys that own a list by (offset, key) ascending,
+// each with its ids in stored order, then the keys with an inline id by key ascending.  An image does not record which
+// window first referred to a list, so the order of its arena is the only order a merge can keep.
+int kaamer_image_merge(const kaamer_image *const *imgs, uint32_t n, double load_factor, kaamer_image **out)
+{
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "image_merge: bad argument");
+    *out = nullptr;
+    std::vector<uint64_t> n_pairs(n ? n : 1, 0);
+    int rc = kaamer_merge_check(imgs, n, n_pairs.data());
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) total += n_pairs[i];
+    if (total >= 0xFFFFFFFFull) return kaamer_fail(KAAMER_E_CAPACITY, "image_merge: %llu pairs in one shard; use more shards", (unsigned long long)total);
+    uint64_t *p64 = (uint64_t *)malloc((total ? total : 1) * sizeof(uint64_t));
+    if (!p64) return kaamer_fail(KAAMER_E_NOMEM, "pairs buffer");
+    struct First { uint32_t key; uint64_t at; };   // a key of one input and the index of its first pair in the enumeration
+    std::vector<First> firsts;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const kaamer_image *img = imgs[i];
+        std::vector<uint64_t> lists, inl;   // offset << 32 | key;  key << 32 | id
+        for (uint64_t b = 0; b < img->hdr.n_buckets; b++)
+            for (int s = 0; s < KH_SLOTS_PER_BUCKET; s++) {
+                const kh_slot &sl = img->buckets[b].s[s];
+                if (sl.key == KH_EMPTY_KEY) continue;
+                if (sl.val & KH_INLINE_BIT) inl.push_back(((uint64_t)sl.key << 32) | (sl.val & ~KH_INLINE_BIT));
+                else lists.push_back(((uint64_t)sl.val << 32) | sl.key);
+            }
+        sort_u64(lists.data(), lists.size());
+        sort_u64(inl.data(), inl.size());
+        for (uint64_t w : lists) {
+            const uint32_t key = (uint32_t)w, *l = img->arena + (w >> 32) * 4;
+            firsts.push_back(First{ key, at });
+            for (uint32_t t = 0; t < l[0]; t++) p64[at++] = ((uint64_t)key << 32) | l[1 + t];
+        }
+        for (uint64_t w : inl) {
+            firsts.push_back(First{ (uint32_t)(w >> 32), at });
+            p64[at++] = w;
+        }
+    }
+    const RankFill by_enumeration = [&](const KeyIndex &ki, std::atomic<uint64_t> *rank) {
+        parallel_for(firsts.size(), n_threads(), [&](size_t b, size_t e, unsigned) {
+            for (size_t i = b; i < e; i++) atomic_min(rank[ki.find(firsts[i].key)], firsts[i].at);
+        });
+    };
+    rc = build_from_sorted_input(p64, total, imgs[0]->hdr.shard, imgs[0]->hdr.n_shards, load_factor, by_enumeration, out);
+    free(p64);
+    return rc;
+}
+
+double kaamer_image_load_factor(const kaamer_image *img) { return img ? img->hdr.load_factor : 0.0; }
+
 int kaamer_image_save(const kaamer_image *img, const char *path)
 {
     if (!img || !path) return kaamer_fail(KAAMER_E_ARG, "image_save: bad argument");

@@ -21,13 +21,19 @@
 //       c -> max(a, c + s).  WHICH ones is a merge along each run of buckets with a non-zero carry; runs are
 //       independent, one thread walks one run.
 // Sorting, scans and selections are rocPRIM (offline path); the kernels around them are below.
+// The build has two seams: where its pairs come from (here: the window kernel) and where a key's rank comes from (here:
+// the window kernel again).  Everything between and after them is bd_build_from_pairs, which the merge of images
+// (merge_device.hip.inc, kaamer_image_merge_device) calls with its own two sources.
 #include "kaamer_internal.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <new>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -494,6 +500,13 @@ __global__ __launch_bounds__(256) void bd_place_kernel(const uint64_t *__restric
 
 inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
+// Where the rank of a key comes from: launches what lowers fw.min_pos[key index] (preset to ~0) to the smallest index of a
+// window -- or, in a merge, of an enumerated pair -- that refers to the key; every index is below the build's no_rank.
+using RankSource = std::function<int(const FirstWindow &)>;
+
+int bd_build_from_pairs(DevMem &d_pairs, DevMem &d_pairs_alt, uint64_t n_emit, uint32_t shard, uint32_t n_shards, double load,
+                        BuildStats *st, Trace &tr, unsigned long long no_rank, const RankSource &first_windows, kaamer_device_image *out);
+
 }  // namespace
 
 // The whole build; on success *out owns two device allocations (hipFree).  Inputs are host buffers.
@@ -502,7 +515,6 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
 {
     out->d_buckets = nullptr;
     out->d_arena = nullptr;
-    if (!(load > 0.05 && load <= 0.95)) load = 0.5;
     for (uint32_t p = 0; p < n_proteins; p++) {
         if (offsets[p + 1] < offsets[p]) return kaamer_fail(KAAMER_E_ARG, "build_proteins: offsets decrease at %u", p);
         if (ids && ids[p] == KH_EMPTY_PID) return kaamer_fail(KAAMER_E_ARG, "protein id 0xFFFFFFFF is reserved");
@@ -550,6 +562,30 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
         if (hs.bad || hs.n_windows != n_emit) return kaamer_fail(KAAMER_E_HIP, "device build: the emit pass disagrees with the count pass");
         tr.lap("emit", n_emit);
     }
+    // the order of the arena: a second run of the window kernel takes, per key, the smallest window position
+    const RankSource by_walk = [&](const FirstWindow &fw) {
+        hipLaunchKernelGGL(bd_windows_kernel<BD_FIRST>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
+                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st, fw);
+        BD_HIP(hipGetLastError());
+        d_seqs.release(); d_off.release(); d_ids.release();   // (hipFree waits for the kernel)
+        return (int)KAAMER_OK;
+    };
+    return bd_build_from_pairs(d_pairs, d_pairs_alt, n_emit, shard, n_shards, load, st, tr, origin + total_res, by_walk, out);
+}
+
+namespace {
+
+// Everything from the emitted pairs on: sort, unique, keys, hash and share with the collision retry, the ranks' hand-over
+// to the representatives, the order of the arena, the lists and the placement.  The build and the merge differ in where
+// the pairs (d_pairs, n_emit of them, d_pairs_alt of the same size) and the ranks (first_windows) come from, in nothing else.
+int bd_build_from_pairs(DevMem &d_pairs, DevMem &d_pairs_alt, uint64_t n_emit, uint32_t shard, uint32_t n_shards, double load,
+                        BuildStats *st, Trace &tr, unsigned long long no_rank, const RankSource &first_windows, kaamer_device_image *out)
+{
+    out->d_buckets = nullptr;
+    out->d_arena = nullptr;
+    if (!(load > 0.05 && load <= 0.95)) load = 0.5;
+    BuildStats hs;
+    memset(&hs, 0, sizeof hs);
 
     // ---- sort + unique -------------------------------------------------------------------------------------
     DevMem d_tmp;
@@ -678,7 +714,7 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
             a.dkeys = d_run.as<uint32_t>();
             a.rank = (unsigned long long *)d_hv.p;
             a.order = d_hk.as<uint32_t>();
-            a.no_rank = origin + total_res;
+            a.no_rank = no_rank;
             uint32_t bits = 4;
             while (bits < 22 && (8ull << bits) < n_keys) bits++;
             const uint32_t n_dir = 1u << bits;
@@ -687,14 +723,14 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
             hipLaunchKernelGGL(bd_keys_kernel, dim3(kb), dim3(256), 0, 0, a);
             hipLaunchKernelGGL(bd_dir_kernel, dim3(blocks_for((uint64_t)n_dir + 1, 256)), dim3(256), 0, 0, a.dkeys, n_keys, 32u - bits, n_dir, d_dir.as<uint32_t>());
             BD_HIP(hipMemset(a.rank, 0xFF, (size_t)n_keys * 8));
-            hipLaunchKernelGGL(bd_windows_kernel<BD_FIRST>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
-                               d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st,
-                               FirstWindow{ a.dkeys, d_dir.as<uint32_t>(), 32u - bits, n_keys, a.rank });
+            {
+                const int rc = first_windows(FirstWindow{ a.dkeys, d_dir.as<uint32_t>(), 32u - bits, n_keys, a.rank });
+                if (rc) return rc;
+            }
             hipLaunchKernelGGL(bd_rank_share_kernel, dim3(kb), dim3(256), 0, 0, a);
             hipLaunchKernelGGL(bd_rank_keys_kernel, dim3(kb), dim3(256), 0, 0, a);
             BD_HIP(hipGetLastError());
             tr.lap("first windows", n_keys);
-            d_seqs.release(); d_off.release(); d_ids.release();
             uint32_t rank_bits = 1;
             while (rank_bits < 64 && (a.no_rank >> rank_bits)) rank_bits++;
             rocprim::double_buffer<unsigned long long> rb((unsigned long long *)d_hv.p, (unsigned long long *)d_hv_alt.p);
@@ -795,16 +831,10 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
     return KAAMER_OK;
 }
 
-extern "C" int kaamer_image_build_proteins_device(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids,
-                                                  uint32_t n_proteins, uint32_t shard, uint32_t n_shards, double load_factor,
-                                                  int device, kaamer_image **out)
+// the host copy of an image that was made on the device; di's two allocations are freed
+int bd_download(kaamer_device_image &di, kaamer_image **out)
 {
-    if (!out || !offsets || (!seqs && n_proteins) || n_shards == 0 || shard >= n_shards)
-        return kaamer_fail(KAAMER_E_ARG, "build_proteins_device: bad argument");
-    *out = nullptr;
-    kaamer_device_image di;
-    int rc = kaamer_build_on_device(seqs, offsets, ids, n_proteins, shard, n_shards, load_factor, device, &di);
-    if (rc) return rc;
+    int rc = KAAMER_OK;
     Trace tr;
     kaamer_image *img = new (std::nothrow) kaamer_image();
     if (!img) rc = kaamer_fail(KAAMER_E_NOMEM, "image alloc");
@@ -824,6 +854,40 @@ extern "C" int kaamer_image_build_proteins_device(const uint8_t *seqs, const uin
     tr.lap("download", di.hdr.n_buckets * 64 + di.hdr.arena_words * 4);
     *out = img;
     return KAAMER_OK;
+}
+
+#include "merge_device.hip.inc"
+
+}  // namespace
+
+extern "C" int kaamer_image_build_proteins_device(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids,
+                                                  uint32_t n_proteins, uint32_t shard, uint32_t n_shards, double load_factor,
+                                                  int device, kaamer_image **out)
+{
+    if (!out || !offsets || (!seqs && n_proteins) || n_shards == 0 || shard >= n_shards)
+        return kaamer_fail(KAAMER_E_ARG, "build_proteins_device: bad argument");
+    *out = nullptr;
+    kaamer_device_image di;
+    const int rc = kaamer_build_on_device(seqs, offsets, ids, n_proteins, shard, n_shards, load_factor, device, &di);
+    if (rc) return rc;
+    return bd_download(di, out);
+}
+
+// mergedb.go:42-135 (kmer_store leg) + indexdb.go:68-132 over the union, on the device: kaamer_image_merge's image, byte for byte
+extern "C" int kaamer_image_merge_device(const kaamer_image *const *imgs, uint32_t n, double load_factor, int device, kaamer_image **out)
+{
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "image_merge_device: bad argument");
+    *out = nullptr;
+    std::vector<uint64_t> n_pairs(n ? n : 1, 0);
+    int rc = kaamer_merge_check(imgs, n, n_pairs.data());   // (references are checked before anything is uploaded)
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) total += n_pairs[i];
+    if (total >= 0xFFFFFFFFull) return kaamer_fail(KAAMER_E_CAPACITY, "image_merge: %llu pairs in one shard; use more shards", (unsigned long long)total);
+    kaamer_device_image di;
+    rc = md_merge_on_device(imgs, n, n_pairs.data(), total, load_factor, device, &di);
+    if (rc) return rc;
+    return bd_download(di, out);
 }
 
 extern "C" int kaamer_image_build_makedb_device(const kaamer_proteins *p, uint32_t shard, uint32_t n_shards, double load_factor,

@@ -27,6 +27,9 @@ struct kaamer_device_image {
 };
 int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids, uint32_t n_proteins,
                            uint32_t shard, uint32_t n_shards, double load, int device, kaamer_device_image *out);
+// what kaamer_image_merge and kaamer_image_merge_device check before anything is dereferenced (builder.cpp);
+// n_pairs[i] = the pairs input i enumerates
+int kaamer_merge_check(const kaamer_image *const *imgs, uint32_t n, uint64_t *n_pairs);
 extern "C" void kaamer_proteins_raw(const kaamer_proteins *p, const uint8_t **seqs, const uint64_t **offsets, const uint32_t **ids, uint32_t *n);
 
 // The readers take the bytes of a file: when they start with the gzip signature (what http.DetectContentType calls

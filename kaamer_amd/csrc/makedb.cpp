@@ -13,6 +13,8 @@
 //                         (any case) are required; a row is accepted when its sequence has >= 7 characters and its
 //                         EntryId is not empty, and gets the next 0-based id; the sequence is NOT upper-cased;
 //                         every other column is a feature (inputTSV.go:184-190)
+//   kaamer_makedb_text_range   the scan loops' -offset / -length (inputFASTA.go:64-125, inputEMBL.go:66-119, inputGBK.go:94-118)
+//   kaamer_proteins_merge      mergedb's protein_store leg and KStats sum (mergedb.go:91-98)
 // Divergences (documented): an empty line makes the reference's FASTA reader panic (line[0:1]) — skipped here; a TSV
 // row with more columns than the header panics (features[i]) — the extra columns are ignored; bytes >= 0x80 are kept
 // as they are (Go's ToUpper would rewrite invalid UTF-8); files are taken as text already decompressed.
@@ -49,6 +51,14 @@ namespace {
 // (inputFASTA.go:88-89, inputTSV.go, inputEMBL.go, inputGBK.go alike): a line of 1 048 576 bytes or more ('\r' included,
 // '\n' not) fills the buffer without a token, Scan() returns false and the reader goes on as if the input had ended there
 thread_local bool g_strict_scanner = false;
+
+// -offset / -length of the scan loops (cmd/kaamer-db/main.go:141-142): `offset` and lastProtein = offset + length in Go's
+// uint (64 bits, wrapping).  The flag defaults, 0 and MaxInt, read the whole file.
+struct Range {
+    uint64_t offset = 0, last = (uint64_t)INT64_MAX;
+    Range() = default;
+    Range(uint64_t o, uint64_t l) : offset(o), last(o + l) {}
+};
 
 struct Lines {
     const char *p, *end;
@@ -117,11 +127,8 @@ void process_fasta_entry(kaamer_proteins *r, uint32_t id, const std::vector<std:
     add_protein(r, id, entry_id, seq, { name });
 }
 
-}  // namespace
-
-extern "C" {
-
-int kaamer_makedb_fasta(const char *text, uint64_t len, kaamer_proteins **out)
+// runFASTA's scan loop, inputFASTA.go:64-125
+int makedb_fasta(const char *text, uint64_t len, const Range &rg, kaamer_proteins **out)
 {
     if (!out || (!text && len)) return kaamer_fail(KAAMER_E_ARG, "makedb_fasta: bad argument");
     *out = nullptr;
@@ -130,23 +137,33 @@ int kaamer_makedb_fasta(const char *text, uint64_t len, kaamer_proteins **out)
     r->feature_names = { "ProteinName" };                                            // FASTA_DEF_FTS, inputFASTA.go:41
     Lines lr{ text, text + len };
     const char *b, *e;
-    uint32_t protein_nb = 0;                                                         // inputFASTA.go:65
+    uint64_t protein_nb = 0;                                                         // inputFASTA.go:65
     std::vector<std::pair<const char *, const char *>> entry;
     while (lr.next(b, e)) {
         if (e - b < 1) continue;                                                     // (the reference panics on an empty line)
         if (*b == '>') {                                                             // :98-112
             protein_nb++;
-            if (!entry.empty()) {
-                process_fasta_entry(r, protein_nb, entry);                           // queued under the NEW number
+            if (protein_nb >= rg.last) {                                             // :100-105: the entry is NOT cleared before the
+                if (!entry.empty()) process_fasta_entry(r, (uint32_t)protein_nb, entry);   // break, so :120-124 queues it once more
+                break;
+            }
+            if (protein_nb >= rg.offset && !entry.empty()) {
+                process_fasta_entry(r, (uint32_t)protein_nb, entry);                 // queued under the NEW number
                 entry.clear();
             }
         }
-        entry.emplace_back(b, e);                                                    // :114-117
+        if (protein_nb >= rg.offset) entry.emplace_back(b, e);                       // :114-117
     }
-    if (!entry.empty()) process_fasta_entry(r, protein_nb, entry);                   // :120-124
+    if (protein_nb >= rg.offset && !entry.empty()) process_fasta_entry(r, (uint32_t)protein_nb, entry);   // :120-124
     *out = r;
     return KAAMER_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int kaamer_makedb_fasta(const char *text, uint64_t len, kaamer_proteins **out) { return makedb_fasta(text, len, Range(), out); }
 
 int kaamer_makedb_tsv(const char *text, uint64_t len, kaamer_proteins **out)
 {
@@ -207,7 +224,8 @@ int kaamer_makedb_tsv(const char *text, uint64_t len, kaamer_proteins **out)
 // Both scan loops cut the file at lines that are exactly "//" (inputEMBL.go:95-113, inputGBK.go:94-112): every such
 // line bumps proteinNb, and the text gathered since the previous one -- if there is any -- is queued under that
 // number, so ids are the 1-based ordinal of the record's terminator (an empty record uses up a number).  Text after
-// the last "//" is never queued.  (offset / length, the split-build options, are not reproduced: one file, all of it.)
+// the last "//" is never queued.  -offset / -length (Range): text is gathered only while proteinNb >= offset, and at
+// proteinNb >= offset + length the pending entry is queued, empty or not, and the scan ends.
 namespace {
 
 const std::string *find_feat(const std::vector<std::pair<std::string, std::string>> &f, const char *k)
@@ -381,7 +399,7 @@ bool process_gbk_entry(const std::string &entry, std::string &entry_id, std::str
     return true;
 }
 
-int makedb_flat(const char *text, uint64_t len, bool gbk, kaamer_proteins **out)
+int makedb_flat(const char *text, uint64_t len, bool gbk, const Range &rg, kaamer_proteins **out)
 {
     if (!out || (!text && len)) return kaamer_fail(KAAMER_E_ARG, "makedb_%s: bad argument", gbk ? "gbk" : "embl");
     *out = nullptr;
@@ -397,30 +415,33 @@ int makedb_flat(const char *text, uint64_t len, bool gbk, kaamer_proteins **out)
     else r->feature_names = { "ProteinName", "GeneName", "EC", "GO", "KEGG_ID", "BioCyc_ID", "HAMAP", "Organism", "TaxId", "FullTaxonomy" };  // inputEMBL.go:43
     Lines lr{ text, text + len };
     const char *b, *e;
-    uint32_t protein_nb = 0;
+    uint64_t protein_nb = 0;
     std::string entry;
+    auto send = [&]() {                                                              // one queued entry (an empty one contributes nothing)
+        std::string entry_id, seq;
+        std::vector<std::pair<std::string, std::string>> feat;
+        bool keep = false;
+        size_t declared = std::string::npos;
+        try { keep = gbk ? process_gbk_entry(entry, entry_id, seq, feat) : process_embl_entry(entry, entry_id, seq, feat, declared); }
+        catch (const Skip &) { keep = false; }   // the reference process would have died here: the entry is dropped
+        if (!keep) return;
+        std::vector<std::string> vals;
+        for (auto &n : r->feature_names) { const std::string *v = find_feat(feat, n.c_str()); vals.push_back(v ? *v : std::string()); }
+        if (declared != std::string::npos && declared < seq.size()) {   // indexed: Sequence[:Length]; stored: all of it
+            r->full_seq[(uint32_t)r->ids.size()] = seq;
+            seq.resize(declared);
+        }
+        add_protein(r, (uint32_t)protein_nb, entry_id, seq, vals);
+    };
     while (lr.next(b, e)) {
         if (e - b == 2 && b[0] == '/' && b[1] == '/') {
             protein_nb++;
-            if (!entry.empty()) {
-                std::string entry_id, seq;
-                std::vector<std::pair<std::string, std::string>> feat;
-                bool keep = false;
-                size_t declared = std::string::npos;
-                try { keep = gbk ? process_gbk_entry(entry, entry_id, seq, feat) : process_embl_entry(entry, entry_id, seq, feat, declared); }
-                catch (const Skip &) { keep = false; }   // the reference process would have died here: the entry is dropped
-                if (keep) {
-                    std::vector<std::string> vals;
-                    for (auto &n : r->feature_names) { const std::string *v = find_feat(feat, n.c_str()); vals.push_back(v ? *v : std::string()); }
-                    if (declared != std::string::npos && declared < seq.size()) {   // indexed: Sequence[:Length]; stored: all of it
-                        r->full_seq[(uint32_t)r->ids.size()] = seq;
-                        seq.resize(declared);
-                    }
-                    add_protein(r, protein_nb, entry_id, seq, vals);
-                }
+            if (protein_nb >= rg.last) { send(); break; }                            // inputEMBL.go:102-105: sent even when empty
+            if (protein_nb >= rg.offset && !entry.empty()) {                         // :106-111
+                send();
                 entry.clear();
             }
-        } else {
+        } else if (protein_nb >= rg.offset) {                                        // :113-116
             entry.append(b, e);
             entry.push_back('\n');
         }
@@ -432,17 +453,61 @@ int makedb_flat(const char *text, uint64_t len, bool gbk, kaamer_proteins **out)
 }  // namespace
 
 extern "C" {
-int kaamer_makedb_embl(const char *text, uint64_t len, kaamer_proteins **out) { return makedb_flat(text, len, false, out); }
-int kaamer_makedb_gbk(const char *text, uint64_t len, kaamer_proteins **out) { return makedb_flat(text, len, true, out); }
+int kaamer_makedb_embl(const char *text, uint64_t len, kaamer_proteins **out) { return makedb_flat(text, len, false, Range(), out); }
+int kaamer_makedb_gbk(const char *text, uint64_t len, kaamer_proteins **out) { return makedb_flat(text, len, true, Range(), out); }
+
+// kaamer_makedb_text with the scan loops' -offset / -length; the TSV loop never reads them (inputTSV.go:40-145)
+int kaamer_makedb_text_range(const char *text, uint64_t len, int32_t format, int32_t strict_scanner, uint64_t offset, uint64_t length,
+                             kaamer_proteins **out)
+{
+    if (format < 0 || format > 3) return kaamer_fail(KAAMER_E_ARG, "makedb_text: format is 0 FASTA, 1 TSV, 2 EMBL, 3 GBK");
+    const Range rg(offset, length);
+    g_strict_scanner = strict_scanner != 0;
+    const int rc = format == 0 ? makedb_fasta(text, len, rg, out) : format == 1 ? kaamer_makedb_tsv(text, len, out)
+                 : makedb_flat(text, len, format == 3, rg, out);
+    g_strict_scanner = false;
+    return rc;
+}
 
 int kaamer_makedb_text(const char *text, uint64_t len, int32_t format, int32_t strict_scanner, kaamer_proteins **out)
 {
-    if (format < 0 || format > 3) return kaamer_fail(KAAMER_E_ARG, "makedb_text: format is 0 FASTA, 1 TSV, 2 EMBL, 3 GBK");
-    g_strict_scanner = strict_scanner != 0;
-    const int rc = format == 0 ? kaamer_makedb_fasta(text, len, out) : format == 1 ? kaamer_makedb_tsv(text, len, out)
-                 : format == 2 ? kaamer_makedb_embl(text, len, out) : kaamer_makedb_gbk(text, len, out);
-    g_strict_scanner = false;
-    return rc;
+    return kaamer_makedb_text_range(text, len, format, strict_scanner, 0, (uint64_t)INT64_MAX, out);
+}
+
+// mergedb.go:91-98, the protein_store leg: the records of every table in argument order (a later record of an id wins in
+// kaamer_fetch_hits, as store 2's Protein overwrites store 1's) and the sum of the KStats counters.  The reference keeps
+// the first database's KStats.Features; the table is dense per feature, so unequal feature columns are refused.
+int kaamer_proteins_merge(const kaamer_proteins *const *tables, uint32_t n, kaamer_proteins **out)
+{
+    if (!out || !tables || n == 0) return kaamer_fail(KAAMER_E_ARG, "proteins_merge: bad argument");
+    *out = nullptr;
+    for (uint32_t t = 0; t < n; t++) {
+        if (!tables[t]) return kaamer_fail(KAAMER_E_ARG, "proteins_merge: table %u is null", t);
+        if (tables[t]->feature_names != tables[0]->feature_names)
+            return kaamer_fail(KAAMER_E_ARG, "proteins_merge: table %u has other feature columns than table 0", t);
+    }
+    kaamer_proteins *r = new_proteins();
+    if (!r) return kaamer_fail(KAAMER_E_NOMEM, "proteins_merge");
+    r->feature_names = tables[0]->feature_names;
+    for (uint32_t t = 0; t < n; t++) {
+        const kaamer_proteins *p = tables[t];
+        const uint32_t base = (uint32_t)r->ids.size();
+        if ((uint64_t)base + p->ids.size() > 0xFFFFFFFFull) { delete r; return kaamer_fail(KAAMER_E_CAPACITY, "proteins_merge: more than 2^32 records"); }
+        const uint64_t s0 = r->seqs.size(), e0 = r->entry_ids.size(), f0 = r->features.size();
+        r->ids.insert(r->ids.end(), p->ids.begin(), p->ids.end());
+        r->seqs.insert(r->seqs.end(), p->seqs.begin(), p->seqs.end());
+        r->entry_ids.insert(r->entry_ids.end(), p->entry_ids.begin(), p->entry_ids.end());
+        r->features.insert(r->features.end(), p->features.begin(), p->features.end());
+        for (size_t i = 1; i < p->offsets.size(); i++) r->offsets.push_back(s0 + p->offsets[i]);
+        for (size_t i = 1; i < p->entry_off.size(); i++) r->entry_off.push_back(e0 + p->entry_off[i]);
+        for (size_t i = 1; i < p->feature_off.size(); i++) r->feature_off.push_back(f0 + p->feature_off[i]);
+        for (uint32_t i = 0; i < (uint32_t)p->ids.size(); i++) r->by_id[p->ids[i]] = base + i;
+        for (auto &kv : p->full_seq) r->full_seq[base + kv.first] = kv.second;
+        r->n_aa += p->n_aa;
+        r->n_kmers += p->n_kmers;
+    }
+    *out = r;
+    return KAAMER_OK;
 }
 }
 
