@@ -1162,6 +1162,91 @@ int kaamer_reader_done(const kaamer_reader *rd);
 uint64_t kaamer_reader_records(const kaamer_reader *rd);   /* records handed out so far */
 void kaamer_reader_close(kaamer_reader *rd);
 
+/* ------------------------------------------------------------------------- */
+/* FASTQ text parsed on the device — GetQueriesFastq (search.go:324-412) as a  */
+/* data-parallel job: raw text in, the reported hits out.  The host readers    */
+/* above remain the route for FASTA, strict_scanner, -pos / -aln and the       */
+/* sharded handle.                                                             */
+/* ------------------------------------------------------------------------- */
+/* The reader's rules, per line (search.go:370-410; the kernels in parse_text.hip.inc compute exactly this):
+ *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped (bufio.ScanLines)
+ *   class    X (ignored): empty after the '\r' drop.  H: the first byte is '@' (search.go:380).  S: every byte is one of
+ *            ATGCNatgcn (search.go:340,386).  X: anything else.  A quality line that starts with '@' is an H and one made
+ *            of those ten letters only is an S: both quirks of the reference are kept.
+ *   records  X lines are ignored.  A record is every S line whose next non-X line is an H, or that has no next non-X line
+ *            (of a run of S lines the last one wins: search.go:386-388).  Its sequence is that line's bytes, no case
+ *            change; its name is what follows the '@' of the nearest preceding H line, empty when no H precedes (the very
+ *            start of a file only); SizeInKmer = len - 6 (search.go:395,407).  PlusStrand is 1 on the file's first record
+ *            only (search.go:399): host bookkeeping, not part of the parse.
+ *   chunks   a text may be cut at any p with text[p-1] == '\n' and text[p] == '@': the pieces, parsed independently, give
+ *            the records of the whole text in order (kaamer_text_cut_fastq).
+ * Out of scope here: FASTA on the device (it needs the concatenation of TrimSpace'd lines and "upper-case every record but
+ * the last", and protein files are small), strict_scanner, -pos / -aln on the text forms, the sharded handle, inflating
+ * on the device, a reader thread. */
+typedef struct kaamer_text_parser kaamer_text_parser;
+typedef struct { uint32_t name_off, name_len, seq_off, seq_len; } kaamer_text_span;   /* into the text */
+typedef struct {
+    uint32_t n_records;
+    uint32_t reserved;
+    uint64_t n_lines;                   /* lines as the reader counts them */
+    uint64_t seq_bytes;                 /* = offsets[n_records] */
+    const uint8_t *d_seqs;              /* device: the records' sequences back to back: what kaamer_search_device takes */
+    const uint64_t *d_offsets;          /* device: n_records + 1 */
+    const kaamer_text_span *d_spans;    /* device: n_records */
+} kaamer_text_parse_result;
+/* A parser holds the device buffers for texts of up to max_text_bytes (at most 2^32 - 1: spans are 32-bit; longer texts
+ * are KAAMER_E_ARG -- cut them) with up to max_records records.  Lines are bounded by max_text_bytes / 16 +
+ * 4 max_records + 1024 (a FASTQ record is four lines).  A text beyond either bound sets a status word on the device:
+ * kaamer_text_parser_finish then returns KAAMER_E_CAPACITY, never a partial result, and the parser stays usable. */
+int kaamer_text_parser_create(int device, uint64_t max_text_bytes, uint32_t max_records, kaamer_text_parser **out);
+void kaamer_text_parser_free(kaamer_text_parser *p);
+/* Enqueues the parse of d_text[0, n_bytes) on `stream` (a hipStream_t; NULL: the default stream).  d_text stays the
+ * caller's, must start at a 16-byte boundary (any hipMalloc'd buffer does) and must not change before the parse is done.
+ * Bytes that start with the gzip signature are parsed as they are (text): inflate first. */
+int kaamer_parse_fastq_device(kaamer_text_parser *p, const uint8_t *d_text, uint64_t n_bytes, void *stream);
+/* Waits for the last parse enqueued on `stream`: the counts and the device pointers, valid until the next parse. */
+int kaamer_text_parser_finish(kaamer_text_parser *p, void *stream, kaamer_text_parse_result *out);
+/* What the kernels' tiling is made of (tests put their boundary cases there): out[0] bytes a lane reads at once, out[1]
+ * bytes a wave reads at once, out[2] bytes of text per workgroup, out[3] lines per workgroup of the record passes.
+ * Lines are classified and copied by position, not per line: there is no line length at which the code path changes. */
+void kaamer_text_parser_geometry(uint32_t out[4]);
+
+/* Host-buffer search that takes TEXT instead of a packed batch (search_fastq.go:60-136 with the reader inside): the text
+ * is uploaded to the slot, parsed on the slot's stream, then searched exactly as kaamer_submit_batch_top_flat searches the
+ * packed batch -- wait, the repeat of a batch beyond a bound (from the parsed buffers: the text is not parsed again),
+ * discard and the packed block are those of kaamer_ticket.  The submit call waits once for the two counts of the parse
+ * (records, sequence bytes: one small copy): kaamer_search_device takes n_seqs from the host, so this cannot be avoided.
+ * format: 1 (FASTQ); 0 (FASTA) is KAAMER_E_ARG -- use the host reader (kaamer_parse_fasta + kaamer_search_batch_top_flat).
+ * seq_type: base KAAMER_READS or KAAMER_NUCLEOTIDE (NucleotideSearch takes FASTQ too, search_nucleotide.go:38-39), the
+ * genetic code in bits 8-15 as on every call; KAAMER_PROTEIN is KAAMER_E_ARG.  Text that starts with the gzip signature is
+ * KAAMER_E_ARG: only kaamer_search_text_file inflates.  `text` is borrowed for the call (one pointer: cgo-safe).
+ * The slot's parser and text staging (pinned host + device) are allocated at the first text call on it: an index that
+ * never sees text allocates nothing for it.  rep_query / q[].src_seq of the result index the records of the text. */
+int kaamer_submit_text_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_ticket **ticket);
+int kaamer_search_text_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out);
+/* The spans of the text's records (16 bytes each; the caller holds the text): views into `out`, NULL / 0 for a result of
+ * a call that took a packed batch. */
+int kaamer_batch_top_text_spans(const kaamer_batch_top *out, const kaamer_text_span **spans, uint32_t *n_records);
+
+/* The greatest valid cut p in [1, len): text[p-1] == '\n' and text[p] == '@'; 0: none. */
+uint64_t kaamer_text_cut_fastq(const char *text, uint64_t len);
+/* FastqSearch over a FILE (search_fastq.go:60-136) with the reader on the device: raw bytes (plain, or gzip inflated
+ * incrementally by the byte source kaamer_reader_* uses, with its rules: every member, a broken stream reads as what
+ * inflated before, a first header that is no gzip header yields no records) are collected into chunks of about
+ * chunk_text_bytes, each cut at kaamer_text_cut_fastq with the tail carried into the next, dealt round-robin to the
+ * replicas with up to in_flight chunks per replica (0: three) and searched by kaamer_submit_text_top_flat.  cb is called
+ * once per chunk, in input order; `top` indexes the chunk's records from 0, first_seq is the chunk's first record in the
+ * file.  A chunk without a cut goes on reading up to 4 chunk_text_bytes; beyond that: KAAMER_E_CAPACITY (use
+ * kaamer_search_file).  Memory: in_flight x replicas chunks.  Errors drain the chunks in flight, counters are summed and
+ * a non-zero return of cb stops the run with KAAMER_E_ARG, as in kaamer_search_file (it is the same loop). */
+typedef int (*kaamer_text_chunk_cb)(void *user, uint64_t first_seq, const char *text, uint64_t len,
+                                    const kaamer_text_span *spans, uint32_t n_records, const kaamer_batch_top *top);
+int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio,
+                            int64_t min_k_match, uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight,
+                            kaamer_text_chunk_cb cb, void *user, kaamer_counters *total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,15 @@ class TopnPositions(C.Structure):
                 ("pos_words_capacity", C.c_uint64)]
 
 
+class TextSpan(C.Structure):   # kaamer_text_span: name and sequence of one record, as offsets into the text
+    _fields_ = [("name_off", C.c_uint32), ("name_len", C.c_uint32), ("seq_off", C.c_uint32), ("seq_len", C.c_uint32)]
+
+
+class TextParseResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("reserved", C.c_uint32), ("n_lines", C.c_uint64), ("seq_bytes", C.c_uint64),
+                ("d_seqs", C.c_void_p), ("d_offsets", C.c_void_p), ("d_spans", C.c_void_p)]
+
+
 # every symbol include/kaamer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "kaamer_last_error": (C.c_char_p, []),
@@ -389,6 +398,22 @@ SYMBOLS = {
     "kaamer_image_merge_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
     "kaamer_proteins_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
     "kaamer_makedb_text_range": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
+    # FASTQ text parsed on the device: the parser, the host-buffer calls that take text, the whole-file driver
+    "kaamer_text_parser_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_text_parser_free": (None, [C.c_void_p]),
+    "kaamer_parse_fastq_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_text_parser_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TextParseResult)]),
+    "kaamer_text_parser_geometry": (None, [C.POINTER(C.c_uint32)]),
+    # (handle, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, out)
+    "kaamer_submit_text_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                              C.POINTER(C.c_void_p)]),
+    "kaamer_search_text_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                              C.c_void_p]),
+    "kaamer_batch_top_text_spans": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(TextSpan)), C.POINTER(C.c_uint32)]),
+    "kaamer_text_cut_fastq": (C.c_uint64, [C.c_char_p, C.c_uint64]),
+    # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total)
+    "kaamer_search_text_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 }
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range

@@ -4,6 +4,7 @@ torch-owned device tensors (device memory and streams are torch's job here,
 nothing else).  All compute happens inside libkaamer_hip.so.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -239,10 +240,14 @@ META_DTYPE = np.dtype([("src_seq", "<u4"), ("size_in_kmer", "<i4"), ("start_posi
                        ("plus_strand", "<i4"), ("aa_len", "<u4"), ("aa_off", "<u8"), ("sa_off", "<u4"), ("sa_len", "<u4")])
 
 
+SPAN_DTYPE = np.dtype([("name_off", "<u4"), ("name_len", "<u4"), ("seq_off", "<u4"), ("seq_len", "<u4")])   # kaamer_text_span
+
+
 class TopResult:
     """Host view of one kaamer_batch_top (copied out, the C object is freed): the reported queries
     (`rep_query`, `meta`, `trim`, CSR `top_off` + `top_pid` / `top_kmatch` / `top_first_pos`, `orf_aa`),
-    plus dense per-query views for convenience (`top_cnt[n_queries]`, `dense()`)."""
+    plus dense per-query views for convenience (`top_cnt[n_queries]`, `dense()`).  `text_spans`: one SPAN_DTYPE item
+    per record of the text for a result of the text calls (kaamer_batch_top_text_spans), else None."""
 
     def __init__(self, out):
         o = out.contents
@@ -277,6 +282,12 @@ class TopResult:
         # the alignments of the reported hits (kaamer_batch_top_alignments): None unless the call asked for them; else one
         # dict per CSR entry (fields of kaamer_alignment; "aln": the three rows, None for a result without text), and the
         # CSR arrays above are in the reference's final order (BitScore descending)
+        self.text_spans = None
+        sp, ns = C.POINTER(abi.TextSpan)(), C.c_uint32()
+        abi.check(abi.lib().kaamer_batch_top_text_spans(out, C.byref(sp), C.byref(ns)))
+        if bool(sp):
+            self.text_spans = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint8)), shape=(ns.value * 16,)).copy().view(SPAN_DTYPE) \
+                if ns.value else np.zeros(0, SPAN_DTYPE)
         self.alignments = None
         items, text = C.POINTER(abi.Alignment)(), C.POINTER(C.c_char)()
         abi.check(abi.lib().kaamer_batch_top_alignments(out, C.byref(items), C.byref(text)))
@@ -535,6 +546,27 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
+    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq"):
+        """kaamer_search_text_top_flat: FASTQ text (bytes) in, the reported hits out -- the text is parsed on the device
+        (GetQueriesFastq) and searched as search_top searches the packed batch.  TopResult.text_spans: name and sequence of
+        every record as offsets into `text`; rep_query / meta["src_seq"] index the records."""
+        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        out = C.POINTER(abi.BatchTop)()
+        abi.check(abi.lib().kaamer_search_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
+                                                        min_k_match, max_results, C.byref(out)))
+        try:
+            return TopResult(out)
+        finally:
+            abi.lib().kaamer_batch_top_free(out)
+
+    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq"):
+        """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans)"""
+        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        t = C.c_void_p()
+        abi.check(abi.lib().kaamer_submit_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
+                                                        min_k_match, max_results, C.byref(t)))
+        return TopTicket(t)
+
     def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
         """kaamer_stream_open[_pos|_aln]_flat; align: as search_top's (needs attach_proteins)"""
         return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions, align)
@@ -787,6 +819,32 @@ class Replicas:
                                 chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, None, None)
         return _search_file(abi.lib().kaamer_search_file_opts, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
                             chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, want_positions, align)
+
+    TEXT_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(abi.BatchTop))
+
+    def search_text_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
+                         chunk_text_bytes=1 << 28, in_flight=0, on_chunk=None):
+        """kaamer_search_text_file: the file's FASTQ text (plain or gzip) is cut into chunks of about chunk_text_bytes, each
+        parsed and searched on a replica.  on_chunk(first_seq, text bytes, TopResult) per chunk, in input order; the
+        TopResult's text_spans index `text`, its rep_query counts from the chunk's first record.  -> summed counters"""
+        err = []
+
+        def cb(user, first, text, length, spans, n_records, top):
+            try:
+                if on_chunk is not None:
+                    on_chunk(int(first), C.string_at(text, length), TopResult(top))
+                return 0
+            except BaseException as e:  # noqa: BLE001  (must not propagate through the C frames)
+                err.append(e)
+                return 1
+        c = abi.Counters()
+        cfn = Replicas.TEXT_CHUNK_CB(cb)
+        rc = abi.lib().kaamer_search_text_file(self._h, str(path).encode(), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio, min_k_match,
+                                               max_results, int(chunk_text_bytes), in_flight, C.cast(cfn, C.c_void_p), None, C.byref(c))
+        if err:
+            raise err[0]
+        abi.check(rc)
+        return c.as_dict()
 
     def close(self):
         if self._h:
@@ -1161,6 +1219,89 @@ def parse_reads(text, fmt="fasta"):
                 for i in range(n)]
     finally:
         abi.lib().kaamer_reads_free(h)
+
+
+def text_parser_geometry():
+    """kaamer_text_parser_geometry -> dict(piece, wave_step, tile, lines): the tiling of the device parser's kernels"""
+    g = (C.c_uint32 * 4)()
+    abi.lib().kaamer_text_parser_geometry(g)
+    return dict(piece=int(g[0]), wave_step=int(g[1]), tile=int(g[2]), lines=int(g[3]))
+
+
+def text_cut_fastq(text):
+    """kaamer_text_cut_fastq: the greatest p in [1, len) with text[p-1] == '\\n' and text[p] == '@'; 0: none"""
+    data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    return int(abi.lib().kaamer_text_cut_fastq(data, len(data)))
+
+
+def _hip_runtime():
+    """the HIP runtime torch loaded (device copies of the tools below)"""
+    import torch
+    hip = C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return hip
+
+
+class TextParser:
+    """kaamer_text_parser_*: GetQueriesFastq on the device, for texts of up to max_text_bytes with up to max_records
+    records (None: as many as such a text can hold)"""
+
+    def __init__(self, max_text_bytes, max_records=None, device=0):
+        self.device = device
+        self.max_text_bytes = int(max_text_bytes)
+        if max_records is None:
+            max_records = self.max_text_bytes // 2 + 1
+        h = C.c_void_p()
+        abi.check(abi.lib().kaamer_text_parser_create(device, self.max_text_bytes, int(max_records), C.byref(h)))
+        self._h = h
+
+    def parse_device(self, d_text_ptr, n_bytes, stream=0):
+        """kaamer_parse_fastq_device + kaamer_text_parser_finish on a device buffer -> abi.TextParseResult"""
+        abi.check(abi.lib().kaamer_parse_fastq_device(self._h, d_text_ptr, n_bytes, stream))
+        r = abi.TextParseResult()
+        abi.check(abi.lib().kaamer_text_parser_finish(self._h, stream, C.byref(r)))
+        return r
+
+    def parse(self, text):
+        """text (bytes) -> dict(seqs u8, offsets u64, spans (SPAN_DTYPE), n_lines): uploaded, parsed, copied back"""
+        import torch
+        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        with torch.cuda.device(self.device):
+            d = torch.frombuffer(bytearray(data) if data else bytearray(1), dtype=torch.uint8).cuda()
+            torch.cuda.synchronize()
+            r = self.parse_device(d.data_ptr(), len(data))
+            hip = _hip_runtime()
+            n = int(r.n_records)
+            offs = np.empty(n + 1, np.uint64)
+            spans = np.empty(n, SPAN_DTYPE)
+            seqs = np.empty(int(r.seq_bytes), np.uint8)
+            for arr, ptr in ((offs, r.d_offsets), (spans, r.d_spans), (seqs, r.d_seqs)):
+                if arr.nbytes:
+                    assert hip.hipMemcpy(arr.ctypes.data, C.c_void_p(ptr), arr.nbytes, 2) == 0
+            del d
+        return dict(seqs=seqs, offsets=offs, spans=spans, n_lines=int(r.n_lines))
+
+    def close(self):
+        if self._h:
+            abi.lib().kaamer_text_parser_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_fastq_device(text, device=0):
+    """GetQueriesFastq on the device (tests and tools) -> dict(seqs, offsets, spans, n_lines) as numpy arrays; spans index
+    the text (SPAN_DTYPE: name_off, name_len, seq_off, seq_len)"""
+    data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    p = TextParser(len(data), device=device)
+    try:
+        return p.parse(data)
+    finally:
+        p.close()
 
 
 def align_pairs(seqs=None, packed=None, pairs=(), number_of_aa=0, sub_matrix="blosum62", gap_open=11, gap_extend=1, device=0):

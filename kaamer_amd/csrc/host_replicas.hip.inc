@@ -174,7 +174,64 @@ uint32_t kaamer_replica_stream_pending(const kaamer_replica_stream *rs) { return
 // max_pending chunks in flight, the callback once per chunk, in input order, with the chunk's records (names, sequences:
 // what QueryResultHandler needs next to the hits) and its reported hits.  first_seq = index of the chunk's first record in
 // the file.  A non-zero return of the callback ends the run with KAAMER_E_ARG.
-// The loop is written once, over what it needs of a FIFO of chunks: a replica stream or a sharded stream.
+// The loop is written once, over a source of chunks that also searches them (chunk_loop): records from kaamer_reader_*
+// through a replica stream or a sharded stream (ReadsSource over a ChunkFifo), or raw text through the replicas' text
+// call (host_text_file.hip.inc).  What it needs of a source:
+//   Chunk                      what is in flight and goes to the callback with its hits
+//   bool done()                the input is over
+//   int  next(Chunk **)        the next chunk (NULL with KAAMER_OK: none this time)
+//   int  push(Chunk *)         KAAMER_E_BUSY: pop first
+//   int  pop(top **)           the oldest chunk's result; a failed chunk is consumed too
+//   uint32_t pending()
+//   int  deliver(Chunk *, top) the callback (non-zero: stop)
+//   void drop(Chunk *)
+extern "C++" {
+template <class Src> static int chunk_loop(Src &src, uint32_t max_pending, kaamer_counters *total)
+{
+    int rc = KAAMER_OK;
+    std::vector<typename Src::Chunk *> fifo;   // the chunks in flight, oldest first (the callback gets the records with the hits)
+    auto pop_one = [&]() -> int {
+        kaamer_batch_top *top = nullptr;
+        int prc = src.pop(&top);
+        typename Src::Chunk *chunk = fifo.front();
+        fifo.erase(fifo.begin());
+        if (!prc) {
+            if (total) {
+                const kaamer_counters &c = top->counters;
+                total->n_in += c.n_in; total->n_queries += c.n_queries; total->n_lookup += c.n_lookup; total->n_probe += c.n_probe;
+                total->n_found += c.n_found; total->n_post += c.n_post; total->n_hits += c.n_hits; total->n_overflow += c.n_overflow;
+                total->n_lists += c.n_lists; total->n_list_ids += c.n_list_ids;
+            }
+            if (src.deliver(chunk, top) != 0) prc = kaamer_fail(KAAMER_E_ARG, "search_file: stopped by the callback");
+            kaamer_batch_top_free(top);
+        }
+        src.drop(chunk);
+        return prc;
+    };
+    while (!rc && !src.done()) {
+        typename Src::Chunk *chunk = nullptr;
+        rc = src.next(&chunk);
+        if (rc) break;
+        if (!chunk) continue;
+        for (;;) {
+            int prc = KAAMER_E_BUSY;
+            if (src.pending() < max_pending) prc = src.push(chunk);
+            if (prc == KAAMER_OK) break;
+            if (prc != KAAMER_E_BUSY || fifo.empty()) { rc = prc; break; }
+            rc = pop_one();
+            if (rc) break;
+        }
+        if (rc) { src.drop(chunk); break; }
+        fifo.push_back(chunk);
+    }
+    while (!fifo.empty()) {   // (after an error: the chunks in flight are drained and dropped)
+        const int prc = pop_one();
+        if (!rc) rc = prc;
+    }
+    return rc;
+}
+}  // extern "C++"
+
 struct ChunkFifo {
     void *st;
     int (*push)(void *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs);   // KAAMER_E_BUSY: pop first
@@ -183,58 +240,43 @@ struct ChunkFifo {
     uint32_t max_pending;
 };
 
+// records of a kaamer_reader, searched through a ChunkFifo
+struct ReadsChunk { kaamer_reads *reads; uint64_t first; };
+struct ReadsSource {
+    typedef ReadsChunk Chunk;
+    kaamer_reader *rd;
+    const ChunkFifo &q;
+    uint32_t chunk_seqs;
+    uint64_t chunk_bytes;
+    kaamer_chunk_cb cb;
+    void *user;
+    uint64_t n_seen;
+    bool done() const { return kaamer_reader_done(rd) != 0; }
+    int next(Chunk **out)
+    {
+        kaamer_reads *reads = nullptr;
+        const int rc = kaamer_reader_next(rd, chunk_seqs, chunk_bytes, &reads);
+        if (rc) return rc;
+        const uint32_t n = kaamer_reads_count(reads);
+        if (n == 0) { kaamer_reads_free(reads); return KAAMER_OK; }
+        Chunk *c = new (std::nothrow) Chunk{ reads, n_seen };
+        if (!c) { kaamer_reads_free(reads); return kaamer_fail(KAAMER_E_NOMEM, "search_file: chunk"); }
+        n_seen += n;
+        *out = c;
+        return KAAMER_OK;
+    }
+    int push(Chunk *c) { return q.push(q.st, kaamer_reads_seqs(c->reads), kaamer_reads_offsets(c->reads), kaamer_reads_count(c->reads)); }
+    int pop(kaamer_batch_top **top) { return q.pop(q.st, top); }
+    uint32_t pending() const { return q.pending(q.st); }
+    int deliver(Chunk *c, const kaamer_batch_top *top) { return cb ? cb(user, c->first, c->reads, top) : 0; }
+    void drop(Chunk *c) { kaamer_reads_free(c->reads); delete c; }
+};
+
 static int search_file_loop(kaamer_reader *rd, const ChunkFifo &q, uint32_t chunk_seqs, uint64_t chunk_bytes, kaamer_chunk_cb cb, void *user,
                             kaamer_counters *total)
 {
-    int rc = KAAMER_OK;
-    std::vector<kaamer_reads *> fifo;   // the chunks in flight, oldest first (the callback gets the records with the hits)
-    std::vector<uint64_t> first;
-    uint64_t n_seen = 0;
-    auto pop_one = [&]() -> int {
-        kaamer_batch_top *top = nullptr;
-        int prc = q.pop(q.st, &top);
-        kaamer_reads *chunk = fifo.front();
-        const uint64_t f0 = first.front();
-        fifo.erase(fifo.begin());
-        first.erase(first.begin());
-        if (!prc) {
-            if (total) {
-                const kaamer_counters &c = top->counters;
-                total->n_in += c.n_in; total->n_queries += c.n_queries; total->n_lookup += c.n_lookup; total->n_probe += c.n_probe;
-                total->n_found += c.n_found; total->n_post += c.n_post; total->n_hits += c.n_hits; total->n_overflow += c.n_overflow;
-                total->n_lists += c.n_lists; total->n_list_ids += c.n_list_ids;
-            }
-            if (cb && cb(user, f0, chunk, top) != 0) prc = kaamer_fail(KAAMER_E_ARG, "search_file: stopped by the callback");
-            kaamer_batch_top_free(top);
-        }
-        kaamer_reads_free(chunk);
-        return prc;
-    };
-    while (!rc && !kaamer_reader_done(rd)) {
-        kaamer_reads *chunk = nullptr;
-        rc = kaamer_reader_next(rd, chunk_seqs, chunk_bytes, &chunk);
-        if (rc) break;
-        const uint32_t n = kaamer_reads_count(chunk);
-        if (n == 0) { kaamer_reads_free(chunk); continue; }
-        for (;;) {
-            int prc = KAAMER_E_BUSY;
-            if (q.pending(q.st) < q.max_pending)
-                prc = q.push(q.st, kaamer_reads_seqs(chunk), kaamer_reads_offsets(chunk), n);
-            if (prc == KAAMER_OK) break;
-            if (prc != KAAMER_E_BUSY || fifo.empty()) { rc = prc; break; }
-            rc = pop_one();
-            if (rc) break;
-        }
-        if (rc) { kaamer_reads_free(chunk); break; }
-        fifo.push_back(chunk);
-        first.push_back(n_seen);
-        n_seen += n;
-    }
-    while (!fifo.empty()) {   // (after an error: the chunks in flight are drained and dropped)
-        const int prc = pop_one();
-        if (!rc) rc = prc;
-    }
-    return rc;
+    ReadsSource src = { rd, q, chunk_seqs, chunk_bytes, cb, user, 0 };
+    return chunk_loop(src, q.max_pending, total);
 }
 
 static int replica_fifo_push(void *st, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs)

@@ -236,23 +236,36 @@ int kaamer_parse_fastq(const char *text, uint64_t len, kaamer_reads **out)
     return parse_buffer(text, len, true, out);
 }
 
+// Where a FASTQ text may be cut so that its pieces, parsed one by one, give the records of the whole (the rules per line:
+// include/kaamer_hip.h): before an '@' that opens a line.  That line is an H whatever it holds, an H closes the record
+// pending before it and names whatever follows, so nothing of the reader's state crosses the cut -- a quality line that
+// starts with '@' is an H to the reader too (search.go:380), which is why it is as good a place as a header.
+uint64_t kaamer_text_cut_fastq(const char *text, uint64_t len)
+{
+    if (!text) return 0;
+    for (uint64_t p = len; p-- > 1;)
+        if (text[p] == '@' && text[p - 1] == '\n') return p;
+    return 0;
+}
+
 // ---- the same readers over a FILE, in chunks: search.go:240-283 opens the file, sniffs the first 32 bytes, wraps a
 // gzip.Reader around it when they carry the gzip signature and scans line by line; a 100 M-read file is never in
 // memory as a whole (configs[4]).  kaamer_reader_next hands out up to max_seqs records / about max_bytes of sequence
 // as a kaamer_reads (the accessors below), which goes straight into kaamer_stream_push.
-struct kaamer_reader {
+// The bytes of a query file as text, one copy for every reader of a file (kaamer_reader_* below, kaamer_search_text_file):
+// search.go:240-283 opens the file, sniffs the first 32 bytes and wraps a gzip.Reader around it when they carry the gzip
+// signature.  gzip: every member is read (gzip.Reader is multistream); a stream that breaks off or is damaged reads as
+// what inflated before (gzip.Reader returns the error and the scanner stops); a first header that is no gzip header
+// yields nothing.
+struct kaamer_bytes {
     int fd = -1;
-    bool own_fd = false;
-    bool gz = false, src_eof = false, ended = false, strict = false;
+    bool gz = false, eof = false;
     z_stream z;
     bool z_live = false;
     std::vector<uint8_t> raw;     // bytes as read from the file (gzip only)
     size_t raw_pos = 0, raw_len = 0;
-    std::vector<char> text;       // decoded text not yet split into lines
-    size_t text_pos = 0, text_len = 0;
-    std::string carry;            // a line that began in an earlier block
-    RecordParser ps;
-    uint64_t n_records = 0;
+    uint8_t head[32];             // the sniffed bytes
+    size_t n_head = 0, head_pos = 0;
 };
 
 static ssize_t fd_read(int fd, void *dst, size_t n)
@@ -264,49 +277,168 @@ static ssize_t fd_read(int fd, void *dst, size_t n)
     }
 }
 
-// fills rd->text with the next block of decoded text; false: the input is over (EOF, a gzip stream that broke off or is
-// damaged: what was read before stays -- gzip.Reader returns the error and the scanner stops)
-static bool reader_fill(kaamer_reader *rd)
+}  // extern "C"
+
+int kaamer_bytes_open_fd(int fd, kaamer_bytes **out)
 {
-    rd->text_pos = rd->text_len = 0;
-    if (rd->src_eof) return false;
-    if (!rd->gz) {
-        const ssize_t k = fd_read(rd->fd, rd->text.data(), rd->text.size());
-        if (k <= 0) { rd->src_eof = true; return false; }
-        rd->text_len = (size_t)k;
-        return true;
+    *out = nullptr;
+    kaamer_bytes *b = new (std::nothrow) kaamer_bytes();
+    if (!b) return kaamer_fail(KAAMER_E_NOMEM, "byte source");
+    b->fd = fd;
+    // the first 32 bytes decide how the file is read (http.DetectContentType, search.go:246-270)
+    while (b->n_head < sizeof b->head) {
+        const ssize_t k = fd_read(fd, b->head + b->n_head, sizeof b->head - b->n_head);
+        if (k <= 0) break;
+        b->n_head += (size_t)k;
     }
-    for (;;) {
-        if (rd->raw_pos == rd->raw_len) {
-            const ssize_t k = fd_read(rd->fd, rd->raw.data(), rd->raw.size());
-            rd->raw_pos = 0;
-            rd->raw_len = k > 0 ? (size_t)k : 0;
+    if (b->n_head == 0) b->eof = true;
+    if (kaamer_is_gzip((const char *)b->head, b->n_head)) {
+        b->gz = true;
+        b->raw.resize(1u << 20);
+        memcpy(b->raw.data(), b->head, b->n_head);
+        b->raw_len = b->n_head;
+        memset(&b->z, 0, sizeof b->z);
+        if (inflateInit2(&b->z, 16 + MAX_WBITS) != Z_OK) { delete b; return kaamer_fail(KAAMER_E_NOMEM, "gzip: inflateInit2"); }
+        b->z_live = true;
+    }
+    *out = b;
+    return KAAMER_OK;
+}
+
+const uint8_t *kaamer_bytes_head(const kaamer_bytes *b, size_t *n) { *n = b->n_head; return b->head; }
+bool kaamer_bytes_is_gzip(const kaamer_bytes *b) { return b->gz; }
+void kaamer_bytes_end(kaamer_bytes *b) { b->eof = true; }
+
+void kaamer_bytes_close(kaamer_bytes *b)
+{
+    if (!b) return;
+    if (b->z_live) inflateEnd(&b->z);
+    delete b;
+}
+
+// the next block of decoded text into dst[0, cap): its length; 0: the input is over (EOF, a gzip stream that broke off or
+// is damaged: what was read before stays)
+size_t kaamer_bytes_read(kaamer_bytes *b, char *dst, size_t cap)
+{
+    if (b->eof || cap == 0) return 0;
+    if (!b->gz) {
+        if (b->head_pos < b->n_head) {   // the sniffed bytes first
+            const size_t k = b->n_head - b->head_pos < cap ? b->n_head - b->head_pos : cap;
+            memcpy(dst, b->head + b->head_pos, k);
+            b->head_pos += k;
+            return k;
         }
-        const bool file_over = rd->raw_len == 0;
-        rd->z.next_in = rd->raw.data() + rd->raw_pos;
-        rd->z.avail_in = (uInt)(rd->raw_len - rd->raw_pos);
-        rd->z.next_out = (Bytef *)rd->text.data();
-        rd->z.avail_out = (uInt)rd->text.size();
-        const int rc = inflate(&rd->z, Z_NO_FLUSH);
-        rd->raw_pos = rd->raw_len - rd->z.avail_in;
-        const size_t got = rd->text.size() - rd->z.avail_out;
+        const ssize_t k = fd_read(b->fd, dst, cap);
+        if (k <= 0) { b->eof = true; return 0; }
+        return (size_t)k;
+    }
+    if (cap > (1u << 30)) cap = 1u << 30;
+    for (;;) {
+        if (b->raw_pos == b->raw_len) {
+            const ssize_t k = fd_read(b->fd, b->raw.data(), b->raw.size());
+            b->raw_pos = 0;
+            b->raw_len = k > 0 ? (size_t)k : 0;
+        }
+        const bool file_over = b->raw_len == 0;
+        b->z.next_in = b->raw.data() + b->raw_pos;
+        b->z.avail_in = (uInt)(b->raw_len - b->raw_pos);
+        b->z.next_out = (Bytef *)dst;
+        b->z.avail_out = (uInt)cap;
+        const int rc = inflate(&b->z, Z_NO_FLUSH);
+        b->raw_pos = b->raw_len - b->z.avail_in;
+        const size_t got = cap - b->z.avail_out;
         if (rc == Z_STREAM_END) {
             // another member may follow (gzip.Reader is multistream); bytes that are no gzip header end the text here
-            if (rd->raw_pos == rd->raw_len) {
-                const ssize_t k = fd_read(rd->fd, rd->raw.data(), rd->raw.size());
-                rd->raw_pos = 0;
-                rd->raw_len = k > 0 ? (size_t)k : 0;
+            if (b->raw_pos == b->raw_len) {
+                const ssize_t k = fd_read(b->fd, b->raw.data(), b->raw.size());
+                b->raw_pos = 0;
+                b->raw_len = k > 0 ? (size_t)k : 0;
             }
-            if (rd->raw_len == rd->raw_pos || inflateReset(&rd->z) != Z_OK) rd->src_eof = true;
-            if (got) { rd->text_len = got; return true; }
-            if (rd->src_eof) return false;
+            if (b->raw_len == b->raw_pos || inflateReset(&b->z) != Z_OK) b->eof = true;
+            if (got) return got;
+            if (b->eof) return 0;
             continue;
         }
-        if (rc != Z_OK && !(rc == Z_BUF_ERROR && !file_over && got == 0 && rd->z.avail_in == 0)) rd->src_eof = true;  // broke off / damaged
-        if (file_over && got == 0) rd->src_eof = true;
-        if (got) { rd->text_len = got; return true; }
-        if (rd->src_eof) return false;
+        if (rc != Z_OK && !(rc == Z_BUF_ERROR && !file_over && got == 0 && b->z.avail_in == 0)) b->eof = true;  // broke off / damaged
+        if (file_over && got == 0) b->eof = true;
+        if (got) return got;
+        if (b->eof) return 0;
     }
+}
+
+// The chunk reader of kaamer_search_text_file: text from a byte source in pieces of about `budget` bytes, each cut at
+// kaamer_text_cut_fastq, the tail behind the cut carried into the next.  *chunk comes in as a spare buffer (any size) and
+// goes out holding the chunk in its first *len bytes; *len = 0: the input is over.  A piece without a cut goes on reading
+// up to 4 budgets, then KAAMER_E_CAPACITY.
+struct kaamer_text_chunker {
+    kaamer_bytes *src = nullptr;
+    size_t budget = 0;
+    std::vector<char> acc;        // text read and not yet handed out: the tail behind the last cut, then what follows
+    size_t acc_len = 0;
+    bool over = false;            // the byte source is exhausted
+};
+
+kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget)
+{
+    kaamer_text_chunker *c = new (std::nothrow) kaamer_text_chunker();
+    if (c) { c->src = src; c->budget = (size_t)budget; }
+    return c;
+}
+
+void kaamer_text_chunker_free(kaamer_text_chunker *c) { delete c; }
+bool kaamer_text_chunker_done(const kaamer_text_chunker *c) { return c->over && c->acc_len == 0; }
+
+int kaamer_text_chunker_next(kaamer_text_chunker *c, std::vector<char> *chunk, size_t *len)
+{
+    *len = 0;
+    size_t want = c->budget, cut = 0;
+    for (;;) {
+        if (c->acc.size() < want) c->acc.resize(want);
+        while (!c->over && c->acc_len < want) {
+            const size_t got = kaamer_bytes_read(c->src, c->acc.data() + c->acc_len, want - c->acc_len);
+            if (!got) c->over = true;
+            else c->acc_len += got;
+        }
+        if (c->acc_len == 0) return KAAMER_OK;
+        if (c->over) { cut = c->acc_len; break; }   // the rest of the file
+        cut = (size_t)kaamer_text_cut_fastq(c->acc.data(), c->acc_len);
+        if (cut) break;
+        if (want >= 4 * c->budget)
+            return kaamer_fail(KAAMER_E_CAPACITY, "search_text_file: no line starts with '@' within %zu bytes of text (4 chunk_text_bytes): "
+                                                  "use kaamer_search_file, whose reader takes records of any length", want);
+        want += c->budget;
+    }
+    // the chunk takes the buffer, the tail moves to the front of the spare one
+    const size_t tail = c->acc_len - cut;
+    if (chunk->size() < c->budget) chunk->resize(c->budget);
+    if (chunk->size() < tail) chunk->resize(tail);
+    memcpy(chunk->data(), c->acc.data() + cut, tail);
+    chunk->swap(c->acc);
+    c->acc_len = tail;
+    *len = cut;
+    return KAAMER_OK;
+}
+
+extern "C" {
+
+struct kaamer_reader {
+    int fd = -1;
+    bool own_fd = false;
+    bool ended = false, strict = false;
+    kaamer_bytes *src = nullptr;  // plain or gzip: the file as text
+    std::vector<char> text;       // decoded text not yet split into lines
+    size_t text_pos = 0, text_len = 0;
+    std::string carry;            // a line that began in an earlier block
+    RecordParser ps;
+    uint64_t n_records = 0;
+};
+
+// fills rd->text with the next block of decoded text; false: the input is over
+static bool reader_fill(kaamer_reader *rd)
+{
+    rd->text_pos = 0;
+    rd->text_len = kaamer_bytes_read(rd->src, rd->text.data(), rd->text.size());
+    return rd->text_len != 0;
 }
 
 int kaamer_reader_open_fd(int fd, int format, int strict_scanner, kaamer_reader **out)
@@ -319,36 +451,20 @@ int kaamer_reader_open_fd(int fd, int format, int strict_scanner, kaamer_reader 
     rd->ps.fastq = format == 1;
     rd->strict = strict_scanner != 0;
     rd->text.resize(4u << 20);
-    // the first 32 bytes decide how the file is read (http.DetectContentType, search.go:246-270)
-    uint8_t head[32];
+    const int rc = kaamer_bytes_open_fd(fd, &rd->src);
+    if (rc) { delete rd; return rc; }
     size_t nh = 0;
-    while (nh < sizeof head) {
-        const ssize_t k = fd_read(fd, head + nh, sizeof head - nh);
-        if (k <= 0) break;
-        nh += (size_t)k;
-    }
-    if (nh == 0) { rd->src_eof = true; rd->ended = true; }   // (the reference exits on the read error of an empty file)
-    if (kaamer_is_gzip((const char *)head, nh)) {
-        rd->gz = true;
-        rd->raw.resize(1u << 20);
-        memcpy(rd->raw.data(), head, nh);
-        rd->raw_len = nh;
-        memset(&rd->z, 0, sizeof rd->z);
-        if (inflateInit2(&rd->z, 16 + MAX_WBITS) != Z_OK) { delete rd; return kaamer_fail(KAAMER_E_NOMEM, "gzip: inflateInit2"); }
-        rd->z_live = true;
-    } else {
-        if (rd->strict) {
-            // anything DetectContentType does not call "text/plain; charset=utf-8" yields no query (search.go:266-270):
-            // a UTF-16 / UTF-32 byte-order mark, or a byte the sniffer counts as binary among the first 32
-            bool text_utf8 = !(nh >= 2 && ((head[0] == 0xFE && head[1] == 0xFF) || (head[0] == 0xFF && head[1] == 0xFE)));
-            for (size_t i = 0; i < nh && text_utf8; i++) {
-                const uint8_t c = head[i];
-                if (c <= 0x08 || c == 0x0B || (c >= 0x0E && c <= 0x1A) || (c >= 0x1C && c <= 0x1F)) text_utf8 = false;
-            }
-            if (!text_utf8) { rd->src_eof = true; rd->ended = true; }
+    const uint8_t *head = kaamer_bytes_head(rd->src, &nh);
+    if (nh == 0) rd->ended = true;   // (the reference exits on the read error of an empty file)
+    if (!kaamer_bytes_is_gzip(rd->src) && rd->strict) {
+        // anything DetectContentType does not call "text/plain; charset=utf-8" yields no query (search.go:266-270):
+        // a UTF-16 / UTF-32 byte-order mark, or a byte the sniffer counts as binary among the first 32
+        bool text_utf8 = !(nh >= 2 && ((head[0] == 0xFE && head[1] == 0xFF) || (head[0] == 0xFF && head[1] == 0xFE)));
+        for (size_t i = 0; i < nh && text_utf8; i++) {
+            const uint8_t c = head[i];
+            if (c <= 0x08 || c == 0x0B || (c >= 0x0E && c <= 0x1A) || (c >= 0x1C && c <= 0x1F)) text_utf8 = false;
         }
-        memcpy(rd->text.data(), head, nh);
-        rd->text_len = nh;
+        if (!text_utf8) { kaamer_bytes_end(rd->src); rd->ended = true; }
     }
     *out = rd;
     return KAAMER_OK;
@@ -426,7 +542,7 @@ uint64_t kaamer_reader_records(const kaamer_reader *rd) { return rd ? rd->n_reco
 void kaamer_reader_close(kaamer_reader *rd)
 {
     if (!rd) return;
-    if (rd->z_live) inflateEnd(&rd->z);
+    kaamer_bytes_close(rd->src);
     if (rd->own_fd && rd->fd >= 0) close(rd->fd);
     delete rd;
 }

@@ -1,0 +1,167 @@
+// host_text.hip.inc — the host-buffer boundary for callers that hold TEXT (included by search.hip inside its extern "C"
+// block, after host_top.hip.inc): search_fastq.go:60-136 with the reader (search.go:324-412) on the device.
+//
+//   kaamer_submit_text_top_flat   takes a free slot, copies the caller's text into the slot's pinned staging, uploads it,
+//                                 parses it on the slot's stream (parse_text.hip.inc), waits for the two counts, then
+//                                 enqueues what kaamer_submit_batch_top_flat enqueues -- on the parser's buffers
+//   kaamer_wait_batch_top         as for every ticket; the result carries the records' spans
+// The slot's parser starts from an estimate of the record count and, as every other bound of these calls, grows when the
+// device reports KAAMER_E_CAPACITY: the text is on the device by then, only the parse is repeated.
+
+// a text holds at most one record per two bytes (an S line and its '\n'), and one line per byte
+static uint32_t text_hard_records(uint64_t len) { return (uint32_t)(len / 2 + 1); }
+
+// parser and staging of a slot for `len` bytes of text with the bounds (recs, lines)
+static int text_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t len, uint32_t recs, uint64_t lines)
+{
+    if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+    if (h.h_text_cap < len) {
+        HIPCHK(hipStreamSynchronize(h.stream));
+        if (h.h_text) (void)hipHostFree(h.h_text);
+        h.h_text = nullptr; h.h_text_cap = 0;
+        const size_t cap = (size_t)len + (size_t)len / 4 + 4096;
+        if (hipHostMalloc((void **)&h.h_text, cap, hipHostMallocDefault) != hipSuccess) return kaamer_fail(KAAMER_E_NOMEM, "pinned text staging (%zu bytes)", cap);
+        h.h_text_cap = cap;
+    }
+    if (h.d_text_cap < len) {
+        HIPCHK(hipStreamSynchronize(h.stream));
+        if (h.d_text) (void)hipFree(h.d_text);
+        h.d_text = nullptr; h.d_text_cap = 0;
+        const size_t cap = (size_t)len + (size_t)len / 4 + 4096;
+        const int rc = dev_alloc(&h.d_text, cap);
+        if (rc) return rc;
+        h.d_text_cap = cap;
+    }
+    if (!h.parser || h.parser_text < len || h.parser_recs < recs || h.parser_lines < lines) {
+        HIPCHK(hipStreamSynchronize(h.stream));
+        if (h.parser) kaamer_text_parser_free(h.parser);
+        h.parser = nullptr;
+        uint64_t text_cap = len + len / 4 + 4096;   // some headroom, as for the other buffers of a slot
+        if (text_cap > 0xFFFFFFFFull) text_cap = 0xFFFFFFFFull;
+        const int rc = text_parser_create_lines(ix->device, text_cap, recs, lines, &h.parser);
+        if (rc) { h.parser = nullptr; return rc; }
+        h.parser_text = text_cap; h.parser_recs = recs; h.parser_lines = lines;
+    }
+    return KAAMER_OK;
+}
+
+static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, const kaamer_topn_opts *top,
+                       bool blocking, kaamer_ticket **out)
+{
+    if (!ix || !top || !out || (!text && len) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: bad argument");
+    *out = nullptr;
+    if (format == 0)
+        return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTA is not parsed on the device: use the host reader (kaamer_parse_fasta, then kaamer_submit_batch_top_flat)");
+    if (format != 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: unknown format %d (1 = FASTQ)", (int)format);
+    SEQ_TYPE_CHK(seq_type, "submit_text_top");
+    if (!is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
+    if (kaamer_is_gzip(text, len))
+        return kaamer_fail(KAAMER_E_ARG, "submit_text_top: the text starts with the gzip signature: inflate it first (kaamer_search_text_file does)");
+    if (len > 0xFFFFFFFFull)
+        return kaamer_fail(KAAMER_E_ARG, "submit_text_top: a text holds at most 2^32 - 1 bytes (spans are 32-bit): cut it (kaamer_text_cut_fastq)");
+    int slot = -1;
+    const int src = top_slot_take(ix, blocking, &slot);
+    if (src) return src;
+    kaamer_ticket *t = new (std::nothrow) kaamer_ticket();
+    if (!t) { top_slot_release(ix, slot); return kaamer_fail(KAAMER_E_NOMEM, "ticket"); }
+    memset(t, 0, sizeof *t);
+    t->ix = ix; t->slot = slot; t->seq_type = seq_type; t->top = *top; t->text = true;
+    TopSlot &h = ix->top[slot];
+    int rc = KAAMER_OK;
+    hipError_t he = hipSetDevice(ix->device);
+    if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(he));
+    // where the bounds start: a record of a read set is a header, the read, '+' and as many quality bytes -- 32 bytes
+    // would be a 10-base read; four lines per record.  Kept when the slot's parser already holds more.
+    const uint32_t hard_recs = text_hard_records(len);
+    uint32_t recs = (uint32_t)(len / 32 + 1024);
+    if (recs > hard_recs) recs = hard_recs;
+    uint64_t lines = pt_default_line_cap(len, recs);
+    if (!rc && h.parser && h.parser_text >= len) {
+        if (h.parser_recs > recs) recs = h.parser_recs;
+        if (h.parser_lines > lines) lines = h.parser_lines;
+    }
+    kaamer_text_parse_result pr;
+    memset(&pr, 0, sizeof pr);
+    bool uploaded = false;
+    while (!rc) {
+        rc = text_slot_prepare(ix, h, len, recs, lines);
+        if (rc) break;
+        if (!uploaded) {
+            if (len) {
+                memcpy(h.h_text, text, (size_t)len);   // the caller's buffer is only borrowed for this call
+                he = hipMemcpyAsync(h.d_text, h.h_text, (size_t)len, hipMemcpyHostToDevice, h.stream);
+                if (he != hipSuccess) { rc = kaamer_fail(KAAMER_E_HIP, "H2D: %s", hipGetErrorString(he)); break; }
+            }
+            uploaded = true;
+        }
+        rc = kaamer_parse_fastq_device(h.parser, h.d_text, len, h.stream);
+        if (!rc) rc = kaamer_text_parser_finish(h.parser, h.stream, &pr);   // the one wait of the submit call: n_seqs comes from the host
+        if (rc != KAAMER_E_CAPACITY) break;
+        if (recs >= hard_recs && lines >= len + 1) break;   // (cannot happen: these bounds hold for any text)
+        recs = recs > hard_recs / 4 ? hard_recs : recs * 4;
+        lines = lines > (len + 1) / 4 ? len + 1 : lines * 4;
+        rc = KAAMER_OK;
+    }
+    if (!rc) {
+        t->n_seqs = pr.n_records; t->seq_bytes = pr.seq_bytes;
+        t->d_text_seqs = pr.d_seqs; t->d_text_off = pr.d_offsets;
+        t->h_spans = (kaamer_text_span *)pinned_get(((size_t)pr.n_records + 1) * sizeof(kaamer_text_span), &t->h_spans_cap);
+        if (!t->h_spans) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned spans (%u records)", pr.n_records);
+    }
+    if (!rc && pr.n_records) {
+        he = hipMemcpyAsync(t->h_spans, pr.d_spans, (size_t)pr.n_records * sizeof(kaamer_text_span), hipMemcpyDeviceToHost, h.stream);
+        if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(he));
+    }
+    if (!rc) rc = top_enqueue(t);
+    if (rc) {
+        if (h.stream) (void)hipStreamSynchronize(h.stream);
+        if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
+        if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
+        delete t;
+        top_slot_release(ix, slot);
+        return rc;
+    }
+    *out = t;
+    return KAAMER_OK;
+}
+
+int kaamer_submit_text_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                int64_t min_k_match, uint32_t max_results, kaamer_ticket **ticket)
+{
+    kaamer_topn_opts top;
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    return text_submit(ix, text, len, format, seq_type, &top, true, ticket);
+}
+
+int kaamer_search_text_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_text_top_flat(ix, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+int kaamer_batch_top_text_spans(const kaamer_batch_top *out, const kaamer_text_span **spans, uint32_t *n_records)
+{
+    if (spans) *spans = nullptr;
+    if (n_records) *n_records = 0;
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_text_spans: bad argument");
+    const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
+    if (!bo->spans) return KAAMER_OK;   // the call took a packed batch
+    if (spans) *spans = bo->spans;
+    if (n_records) *n_records = bo->n_spans;
+    return KAAMER_OK;
+}
+
+// a text chunk into the FIFO of a stream (kaamer_search_text_file): as kaamer_stream_push, never blocking on a slot the
+// stream itself holds
+static int stream_push_text(kaamer_stream *st, const char *text, uint64_t len)
+{
+    kaamer_ticket *t = nullptr;
+    const int rc = text_submit(st->ix, text, len, 1, st->seq_type, &st->top, st->fifo->empty(), &t);
+    if (rc) return rc;
+    st->fifo->push_back(t);
+    return KAAMER_OK;
+}

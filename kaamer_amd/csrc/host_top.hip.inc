@@ -27,6 +27,10 @@ struct batch_top_owner {
     bool has_aln = false, has_text = false;
     std::vector<kaamer_alignment> aln;
     std::vector<char> aln_text;
+    // the records of a text call (host_text.hip.inc): one span each, pinned
+    kaamer_text_span *spans = nullptr;
+    size_t spans_cap = 0;
+    uint32_t n_spans = 0;
 };
 
 // the alignment half of a request (kaamer_*_batch_top_aln_flat)
@@ -71,6 +75,12 @@ struct kaamer_ticket {
     TopAlnRequest aln;
     uint32_t max_query_len;   // batch_max_query_len
     uint64_t aln_cap;         // bytes the block's two sections may take
+    // a text call (host_text.hip.inc): the batch is what the slot's parser left on the device, nothing is uploaded
+    bool text;
+    const uint8_t *d_text_seqs;
+    const uint64_t *d_text_off;
+    kaamer_text_span *h_spans;   // pinned; goes to the result
+    size_t h_spans_cap;
 };
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
@@ -219,6 +229,9 @@ static void top_slot_free(TopSlot &h)
     if (h.d_off) (void)hipFree(h.d_off);
     if (h.d_block) (void)hipFree(h.d_block);
     if (h.h_in) (void)hipHostFree(h.h_in);
+    if (h.parser) kaamer_text_parser_free(h.parser);
+    if (h.h_text) (void)hipHostFree(h.h_text);
+    if (h.d_text) (void)hipFree(h.d_text);
     if (h.stream) (void)hipStreamDestroy(h.stream);
     h = TopSlot();
 }
@@ -305,26 +318,51 @@ static int top_enqueue(kaamer_ticket *t)
     o.concurrent_batches = (uint32_t)ix->n_top;   // the slots exist so that batches overlap
     const bool aligns = t->want_aln && t->aln.on;   // (without a matrix row nothing is aligned: the host marks every item)
     if (aligns && !t->aln_cap) t->aln_cap = ta_first_cap(t, h);
-    int rc = top_slot_prepare(ix, h, o, t->seq_bytes, t->n_seqs, t->top.max_results, t->want_pos, t->b.pos_scale, aligns ? t->aln_cap : 0);
+    // (a text call stages nothing: its batch is on the device already)
+    int rc = top_slot_prepare(ix, h, o, t->text ? 0 : t->seq_bytes, t->text ? 0 : t->n_seqs, t->top.max_results, t->want_pos, t->b.pos_scale,
+                              aligns ? t->aln_cap : 0);
     if (rc) return rc;
     hipStream_t s = h.stream;
-    const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
-    hipError_t e = hipSuccess;
-    if (t->seq_bytes) e = hipMemcpyAsync(h.d_seqs, h.h_in, (size_t)t->seq_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.d_off, h.h_in + off_at, ((size_t)t->n_seqs + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "H2D: %s", hipGetErrorString(e));
+    const uint8_t *d_seqs = h.d_seqs;
+    const uint64_t *d_off = h.d_off;
+    if (t->text) {
+        d_seqs = t->d_text_seqs; d_off = t->d_text_off;
+    } else {
+        const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
+        hipError_t e = hipSuccess;
+        if (t->seq_bytes) e = hipMemcpyAsync(h.d_seqs, h.h_in, (size_t)t->seq_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h.d_off, h.h_in + off_at, ((size_t)t->n_seqs + 1) * 8, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "H2D: %s", hipGetErrorString(e));
+    }
     kaamer_device_result dr;
     kaamer_topn_result tr;
     kaamer_topn_opts top = t->top;
     top.best_start_codon = nucl ? 1u : 0u;  // search_fastq.go:121, search_nucleotide.go:118; not in search_protein.go
     top.d_size_in_kmer = nullptr; top.orf_source = nullptr;
-    rc = kaamer_search_device(ix, h.ws, h.d_seqs, h.d_off, t->n_seqs, t->seq_bytes, t->seq_type, s, &dr);
+    rc = kaamer_search_device(ix, h.ws, d_seqs, d_off, t->n_seqs, t->seq_bytes, t->seq_type, s, &dr);
     if (!rc) rc = kaamer_topn_device(h.ws, &top, s, &tr);
     if (!rc) rc = topn_pack_block(h.ws, h.ws, 0u, 1u, &tr, s, h.d_block, h.block_use);
     if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
     if (!rc && aligns) rc = top_enqueue_alignments(t, h, &tr, s);
     if (rc) return rc;
     return rep_block_copy_guess(h.d_block, h.block_use, h.guess, &t->h_block, &t->h_block_cap, &t->copied, s);
+}
+
+// a free slot of the pool, marked busy; blocking: waits while all are busy, else KAAMER_E_BUSY
+static int top_slot_take(kaamer_index *ix, bool blocking, int *slot_out)
+{
+    int slot = -1;
+    std::unique_lock<std::mutex> lock(ix->pool_mu);
+    for (;;) {
+        for (int i = 0; i < ix->n_top; i++)
+            if (!ix->top[i].busy) { slot = i; break; }
+        if (slot >= 0) break;
+        if (!blocking) return kaamer_fail(KAAMER_E_BUSY, "all %d host slots are busy: wait for / pop an earlier batch first", ix->n_top);
+        ix->pool_cv.wait(lock);
+    }
+    ix->top[slot].busy = true;
+    *slot_out = slot;
+    return KAAMER_OK;
 }
 
 static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_topn_opts *top, bool blocking, kaamer_ticket **out,
@@ -335,17 +373,8 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
     *out = nullptr;
     SEQ_TYPE_CHK(in->seq_type, "submit_batch_top");
     int slot = -1;
-    {
-        std::unique_lock<std::mutex> lock(ix->pool_mu);
-        for (;;) {
-            for (int i = 0; i < ix->n_top; i++)
-                if (!ix->top[i].busy) { slot = i; break; }
-            if (slot >= 0) break;
-            if (!blocking) return kaamer_fail(KAAMER_E_BUSY, "all %d host slots are busy: wait for / pop an earlier batch first", ix->n_top);
-            ix->pool_cv.wait(lock);
-        }
-        ix->top[slot].busy = true;
-    }
+    const int src = top_slot_take(ix, blocking, &slot);
+    if (src) return src;
     kaamer_ticket *t = new (std::nothrow) kaamer_ticket();
     if (!t) { top_slot_release(ix, slot); return kaamer_fail(KAAMER_E_NOMEM, "ticket"); }
     memset(t, 0, sizeof *t);
@@ -443,12 +472,14 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         if (ix->top[t->slot].ws) ws_note_density(ix->top[t->slot].ws, bo->pub.counters);
         bo->pub.max_results = t->top.max_results;
         bo->has_pos = t->want_pos;
+        if (t->text) { bo->spans = t->h_spans; bo->spans_cap = t->h_spans_cap; bo->n_spans = t->n_seqs; t->h_spans = nullptr; }
         if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
         if (!nucl) bo->pub.orf_aa = nullptr;
         if (!rc) *out = &bo->pub;
         else kaamer_batch_top_free(&bo->pub);
     }
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
+    if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
     top_slot_release(ix, t->slot);
     delete t;
     return rc;
@@ -465,6 +496,7 @@ void kaamer_ticket_discard(kaamer_ticket *t)
     if (h.stream) (void)hipStreamSynchronize(h.stream);
     if (h.ws) h.ws->clean = false;  // its status was not looked at: the next batch starts from cleared per-batch state
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
+    if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
     top_slot_release(ix, t->slot);
     delete t;
 }
@@ -580,6 +612,7 @@ void kaamer_batch_top_free(kaamer_batch_top *out)
     if (!out) return;
     batch_top_owner *bo = reinterpret_cast<batch_top_owner *>(out);  // pub is the first member
     if (bo->block) { if (bo->pinned) pinned_put(bo->block, bo->block_cap); else free(bo->block); }
+    if (bo->spans) pinned_put(bo->spans, bo->spans_cap);
     delete bo;
 }
 

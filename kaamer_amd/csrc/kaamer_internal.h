@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/kaamer_hip.h"
 #include "kaamer_layout.h"
@@ -39,6 +40,22 @@ extern "C" void kaamer_proteins_raw(const kaamer_proteins *p, const uint8_t **se
 // Returns 0, or KAAMER_E_FORMAT when not even the first header is a gzip header (gzip.NewReader fails: no input).
 bool kaamer_is_gzip(const char *text, uint64_t len);
 int kaamer_gunzip(const char *text, uint64_t len, std::string *out);
+
+// The bytes of a query file as text (host_search.cpp): plain, or gzip inflated incrementally.  One copy for kaamer_reader_*
+// and kaamer_search_text_file.  The fd stays the caller's.
+struct kaamer_bytes;
+int kaamer_bytes_open_fd(int fd, kaamer_bytes **out);                     // sniffs the first 32 bytes (search.go:246-270)
+const uint8_t *kaamer_bytes_head(const kaamer_bytes *b, size_t *n);       // ... which are these
+bool kaamer_bytes_is_gzip(const kaamer_bytes *b);
+size_t kaamer_bytes_read(kaamer_bytes *b, char *dst, size_t cap);         // the next block of text; 0: the input is over
+void kaamer_bytes_end(kaamer_bytes *b);                                   // nothing more is handed out
+void kaamer_bytes_close(kaamer_bytes *b);
+// ... cut into chunks at kaamer_text_cut_fastq (the reader half of kaamer_search_text_file; the rules: host_search.cpp)
+struct kaamer_text_chunker;
+kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget);   // src stays the caller's
+int kaamer_text_chunker_next(kaamer_text_chunker *c, std::vector<char> *chunk, size_t *len);
+bool kaamer_text_chunker_done(const kaamer_text_chunker *c);
+void kaamer_text_chunker_free(kaamer_text_chunker *c);
 
 // The alignment step's shared statements (align.hip), for the stage that aligns the reported hits of a top-N call
 // (search.hip: top_align.hip.inc): the integers of one alignment as the device leaves them ...

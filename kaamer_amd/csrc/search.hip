@@ -33,6 +33,8 @@
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
+#include <fcntl.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cstdarg>
@@ -148,6 +150,12 @@ struct TopSlot {
     uint64_t pos_words = 0;    // bitmap words of that bound (calls that ask for PositionHits of the reported hits)
     size_t guess = 1u << 16;   // bytes of the block copied before its size is known (adapts to the previous call)
     uint64_t aln_guess = 0;    // bytes the alignment sections of the previous call needed, plus a quarter (0: none yet)
+    // the text calls (host_text.hip.inc), allocated at the slot's first one: the parser and the text's staging
+    kaamer_text_parser *parser = nullptr;
+    uint64_t parser_text = 0, parser_lines = 0;   // the bounds the parser was created for
+    uint32_t parser_recs = 0;
+    uint8_t *h_text = nullptr, *d_text = nullptr; // pinned / device
+    size_t h_text_cap = 0, d_text_cap = 0;
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
@@ -1059,6 +1067,8 @@ static void aln_table_free(kaamer_index *ix)
     ix->aln_host = nullptr; ix->aln_idmap_n = ix->aln_entries = ix->aln_max_ns = 0; ix->aln_bytes = ix->aln_number_of_aa = 0;
 }
 
+#include "parse_text.hip.inc"
+
 extern "C" {
 
 const char *kaamer_last_error(void) { return g_err; }
@@ -1570,11 +1580,12 @@ static QueryInput enqueue_translate(kaamer_workspace *ws, const uint8_t *d_seqs,
     // these launches; then everything of the reads and the output offsets of both kinds in one kernel
     hipLaunchKernelGGL(list_long_kernel, dim3((unsigned)(((uint64_t)n_seqs + LL_BLOCK - 1) / LL_BLOCK + (n_seqs ? 0 : 1))), dim3(LL_BLOCK), 0, s, tp);
     scan_u32_on(ws, ws->d_long_np, tp.n_long, n_long_bound, ws->d_piece_base, s);
-    hipLaunchKernelGGL(piece_li_kernel, dim3((unsigned)((n_long_bound + 255) / 256)), dim3(256), 0, s, tp);
+    // (an empty batch -- a text without a record -- still launches one workgroup of each, as list_long_kernel above)
+    hipLaunchKernelGGL(piece_li_kernel, dim3((unsigned)((n_long_bound + 255) / 256 + (n_long_bound ? 0 : 1))), dim3(256), 0, s, tp);
     if (generic) launch_translate_count<true>(tp, tgrid, s);
     else launch_translate_count<false>(tp, tgrid, s);
     for (int a = 0; a < 3; a++) scan_u32_on(ws, ws->d_pcnt3 + a * mpi, ws->d_n_piece_items, piece_bound, ws->d_poff3 + a * (mpi + 1), s);
-    hipLaunchKernelGGL(long_totals_kernel, dim3((unsigned)((n_long_bound * 6 + 255) / 256)), dim3(256), 0, s, tp);
+    hipLaunchKernelGGL(long_totals_kernel, dim3((unsigned)((n_long_bound * 6 + 255) / 256 + (n_long_bound ? 0 : 1))), dim3(256), 0, s, tp);
     if (generic) launch_translate_write<true>(tp, wide_reads, sgrid, tgrid, s);
     else launch_translate_write<false>(tp, wide_reads, sgrid, tgrid, s);
     hipLaunchKernelGGL(orf_order_long_kernel, dim3((unsigned)(n_long_bound < (uint64_t)ws->n_cu * 32 ? (n_long_bound + 3) / 4 + 1 : (uint64_t)ws->n_cu * 8)), dim3(256), 0, s,
@@ -2784,8 +2795,10 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 
 #include "host_top.hip.inc"
 #include "host_top_align.hip.inc"
+#include "host_text.hip.inc"
 #include "host_sharded.hip.inc"
 #include "host_replicas.hip.inc"
+#include "host_text_file.hip.inc"
 #include "host_sharded_stream.hip.inc"
 
 void kaamer_batch_free(kaamer_batch_out *out)

@@ -35,6 +35,7 @@ class SearchOptions:  # search.go:56-71 (the fields the hot path reads); default
     GeneticCode: int = 11         # search.go:60, api/server.go:142: the 6-frame translation's table (nucleotide / reads requests)
     ChunkSeqs: int = 1 << 20      # SearchFile only (no reference counterpart): records per chunk, chunks in flight (0: three)
     InFlight: int = 0
+    ChunkTextBytes: int = 1 << 28  # SearchFile(device_parse=True) only: bytes of text per chunk
 
 
 _EMPTY_ALN = {"Identity": 0.0, "Similarity": 0.0, "Length": 0, "Mismatches": 0, "GapOpenings": 0, "Raw": 0, "BitScore": 0.0,
@@ -223,17 +224,32 @@ class _ConsumerGone(Exception):
     """SearchFile's generator was closed before the file ended"""
 
 
-def SearchFile(handle, path, options=None, fmt=None):
+def SearchFile(handle, path, options=None, fmt=None, device_parse=False):
     """FastqSearch / ProteinSearch / NucleotideSearch (search_fastq.go:60-136, search_protein.go:40-118,
     search_nucleotide.go:27-160) over a FILE of any size (gzip included) on an api.Replicas set or an api.ShardedIndex: a
     generator of QueryResult dicts in file order, shaped as the text drivers above shape theirs (options.SequenceType
     picks which; fmt: "fastq" / "fasta", default by SequenceType).  The file goes through kaamer_search_file_opts /
     kaamer_sharded_search_file on a worker thread, a chunk at a time (options.ChunkSeqs records, default 1 << 20); at most
     two converted chunks wait for the consumer.  ExtractPositions: PositionHits of the reported hits, from the block's
-    bitmaps.  Align with a table attached to the handle: HitEntries and every hit's Alignment, hits in BitScore order."""
+    bitmaps.  Align with a table attached to the handle: HitEntries and every hit's Alignment, hits in BitScore order.
+    device_parse=True (FASTQ on an api.Replicas set, no ExtractPositions, no Align; anything else: ValueError): the file's
+    text is parsed on the device (kaamer_search_text_file, options.ChunkTextBytes of text per chunk) and the names are
+    sliced out of each chunk's text by span; the same dicts come out."""
     o = options or SearchOptions(SequenceType=abi.READS)
     seq_type = o.SequenceType
     fmt = fmt or ("fastq" if seq_type == abi.READS else "fasta")
+    if device_parse:
+        why = None
+        if fmt != "fastq":
+            why = "only FASTQ is parsed on the device"
+        elif seq_type not in (abi.READS, abi.NUCLEOTIDE):
+            why = "FASTQ text is READS or NUCLEOTIDE input"
+        elif o.ExtractPositions or o.Align:
+            why = "ExtractPositions and Align go through the host reader"
+        elif not hasattr(handle, "search_text_file"):
+            why = "the handle has no text driver (an api.Replicas set has)"
+        if why:
+            raise ValueError("SearchFile(device_parse=True): " + why)
     aln = _one_call(handle, o)
     done, stop = object(), threading.Event()
     q = queue.Queue(maxsize=2)
@@ -254,8 +270,20 @@ def SearchFile(handle, path, options=None, fmt=None):
                      size=int(size[i]), plus=bool(plus[i])) for i in range(len(size))]
         put(_chunk_results(top, recs, o, seq_type, getattr(handle, "proteins", None), aln is not None))
 
+    def on_text_chunk(first, text, top):
+        sp = top.text_spans   # names are sliced out of the chunk's text; nothing else of a record is reported for reads
+        recs = [dict(name=text[int(s["name_off"]):int(s["name_off"]) + int(s["name_len"])].decode("latin-1")) for s in sp]
+        put(_chunk_results(top, recs, o, seq_type, None, False))
+
     def work():
         try:
+            if device_parse:
+                handle.search_text_file(path, fmt, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio,
+                                        min_k_match=o.MinKMatch, max_results=o.MaxResults,
+                                        chunk_text_bytes=int(getattr(o, "ChunkTextBytes", 1 << 28)), in_flight=int(getattr(o, "InFlight", 0)),
+                                        on_chunk=on_text_chunk)
+                put(done)
+                return
             handle.search_file(path, fmt, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
                                chunk_seqs=int(getattr(o, "ChunkSeqs", 1 << 20)), in_flight=int(getattr(o, "InFlight", 0)), on_chunk=on_chunk,
                                want_positions=bool(o.ExtractPositions), align=aln)

@@ -1,0 +1,182 @@
+// text_cut_check — the host half of the device FASTQ reader under AddressSanitizer + UBSan, as a stand-alone program:
+// kaamer_text_cut_fastq and the chunk reader of kaamer_search_text_file (byte source -> chunks cut before an '@' that
+// opens a line) over hand cases and random texts, plain and gzip; every chunk is parsed with kaamer_parse_fastq and the
+// concatenation must equal kaamer_parse_fastq of the whole text.  CPU only.    make -C tools/text_cut_check test
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include <unistd.h>
+#include <zlib.h>
+
+#include "../../kaamer_amd/csrc/kaamer_internal.h"
+
+// the two symbols host_search.cpp takes from search.hip
+static char g_err[512] = "";
+int kaamer_fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+extern "C" const char *kaamer_last_error(void) { return g_err; }
+
+static int g_failed = 0;
+#define CHECK(cond, ...)                                        \
+    do {                                                        \
+        if (!(cond)) {                                          \
+            fprintf(stderr, "FAILED %s:%d: %s: ", __FILE__, __LINE__, #cond); \
+            fprintf(stderr, __VA_ARGS__);                       \
+            fprintf(stderr, "\n");                              \
+            g_failed++;                                         \
+        }                                                       \
+    } while (0)
+
+struct Records {
+    std::vector<std::string> seq, name;
+    std::vector<int32_t> size;
+    bool operator==(const Records &o) const { return seq == o.seq && name == o.name && size == o.size; }
+};
+
+static void parse_into(const std::string &text, Records *out)
+{
+    kaamer_reads *r = nullptr;
+    const int rc = kaamer_parse_fastq(text.data(), text.size(), &r);
+    CHECK(rc == KAAMER_OK, "parse_fastq: %d", rc);
+    if (rc) return;
+    const uint32_t n = kaamer_reads_count(r);
+    const uint64_t *off = kaamer_reads_offsets(r), *noff = kaamer_reads_name_offsets(r);
+    const char *seqs = (const char *)kaamer_reads_seqs(r), *names = kaamer_reads_names(r);
+    for (uint32_t i = 0; i < n; i++) {
+        out->seq.emplace_back(seqs + off[i], seqs + off[i + 1]);
+        out->name.emplace_back(names + noff[i], names + noff[i + 1]);
+        out->size.push_back(kaamer_reads_size_in_kmer(r)[i]);
+        // (PlusStrand is 1 on the first record of what was parsed: per FILE it is host bookkeeping, not compared here)
+    }
+    kaamer_reads_free(r);
+}
+
+static std::string gzip_members(const std::string &text, size_t split)
+{
+    std::string out;
+    const std::string parts[2] = { text.substr(0, split), text.substr(split) };
+    for (const std::string &p : parts) {
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (deflateInit2(&z, 1, Z_DEFLATED, 16 + MAX_WBITS, 8, Z_DEFAULT_STRATEGY) != Z_OK) abort();
+        std::vector<unsigned char> buf(deflateBound(&z, p.size()) + 64);
+        z.next_in = (Bytef *)p.data(); z.avail_in = (uInt)p.size();
+        z.next_out = buf.data(); z.avail_out = (uInt)buf.size();
+        if (deflate(&z, Z_FINISH) != Z_STREAM_END) abort();
+        out.append((const char *)buf.data(), buf.size() - z.avail_out);
+        deflateEnd(&z);
+    }
+    return out;
+}
+
+// the file's bytes through the byte source and the chunk reader; expect_rc: what the reader must end with
+static void through_chunker(const std::string &file_bytes, const std::string &text, size_t budget, int expect_rc, const char *what)
+{
+    FILE *f = tmpfile();
+    if (!f) { perror("tmpfile"); exit(2); }
+    if (!file_bytes.empty() && fwrite(file_bytes.data(), 1, file_bytes.size(), f) != file_bytes.size()) { perror("fwrite"); exit(2); }
+    fflush(f);
+    rewind(f);
+    kaamer_bytes *src = nullptr;
+    int rc = kaamer_bytes_open_fd(fileno(f), &src);
+    CHECK(rc == KAAMER_OK, "%s: bytes_open_fd %d", what, rc);
+    kaamer_text_chunker *ck = kaamer_text_chunker_new(src, budget);
+    Records got, whole;
+    std::string joined;
+    std::vector<char> spare;
+    size_t n_chunks = 0;
+    while (!rc && !kaamer_text_chunker_done(ck)) {
+        size_t len = 0;
+        rc = kaamer_text_chunker_next(ck, &spare, &len);
+        if (rc || !len) continue;
+        n_chunks++;
+        CHECK(len <= 4 * budget || kaamer_text_chunker_done(ck), "%s: a chunk of %zu bytes with budget %zu", what, len, budget);
+        CHECK(joined.empty() || spare[0] == '@', "%s: chunk %zu does not start with '@'", what, n_chunks);
+        CHECK(kaamer_text_chunker_done(ck) || spare[len - 1] == '\n', "%s: chunk %zu does not end with a newline", what, n_chunks);
+        const std::string piece(spare.data(), len);
+        joined += piece;
+        parse_into(piece, &got);
+    }
+    CHECK(rc == expect_rc, "%s: the reader ended with %d (%s), expected %d", what, rc, g_err, expect_rc);
+    if (!rc && !expect_rc) {
+        CHECK(joined == text, "%s: the chunks do not add up to the text (%zu of %zu bytes)", what, joined.size(), text.size());
+        parse_into(text, &whole);
+        CHECK(got == whole, "%s: %zu records piecewise, %zu at once (budget %zu, %zu chunks)", what, got.seq.size(), whole.seq.size(), budget, n_chunks);
+    }
+    kaamer_text_chunker_free(ck);
+    kaamer_bytes_close(src);
+    fclose(f);
+}
+
+// a text may hold a stretch without a cut that four budgets cannot hold (KAAMER_E_CAPACITY by design): such a text goes
+// through in one chunk
+static size_t budget_that_fits(const std::string &text, size_t budget)
+{
+    for (size_t at = 1, last_cut = 0; at <= text.size(); at++)
+        if (at == text.size() || (text[at] == '@' && text[at - 1] == '\n')) {
+            if (at - last_cut > 3 * budget) return text.size() + 1;
+            last_cut = at;
+        }
+    return budget;
+}
+
+int main()
+{
+    // kaamer_text_cut_fastq by hand
+    struct { const char *text; uint64_t cut; } hand[] = {
+        { "", 0 }, { "@r1 ACGT", 0 }, { "@r1\nACGT\n+\nIIII\n", 0 }, { "@a\nAC\r\n@b\nGT\n", 7 }, { "@a\nAC\n@", 6 },
+        { "@a\nAC@GT\n+\nII@I\n", 0 }, { "\n@", 1 }, { "@a\nAC\n+\n@@II\n@b\nGT\n", 13 }, { "@", 0 }, { "\n", 0 },
+    };
+    for (auto &h : hand) {
+        const std::string t(h.text);
+        // (an exact-size heap copy: a read past either end is the sanitizer's to find)
+        std::vector<char> exact(t.begin(), t.end());
+        const uint64_t cut = kaamer_text_cut_fastq(exact.data(), exact.size());
+        CHECK(cut == h.cut, "cut of the hand case \"%s\": %llu, expected %llu", h.text, (unsigned long long)cut, (unsigned long long)h.cut);
+        for (size_t budget : { (size_t)1, (size_t)3, (size_t)8, (size_t)64 }) through_chunker(t, t, budget_that_fits(t, budget), KAAMER_OK, "hand case");
+    }
+    CHECK(kaamer_text_cut_fastq(nullptr, 0) == 0, "NULL text");
+    // a record that no four budgets hold, and one they do
+    const std::string long_read = "@long\n" + std::string(8000, 'A') + "\n+\n" + std::string(8000, 'I') + "\n@next\nACGT\n+\nIIII\n@z\nAC\n";
+    through_chunker(long_read, long_read, 1000, KAAMER_E_CAPACITY, "long record, small budget");
+    through_chunker(long_read, long_read, 4100, KAAMER_OK, "long record, four budgets");
+    // 2 000 random texts over the alphabet of the tests, seed 20261003 (a 64-bit LCG: the texts need not be Python's)
+    const char alphabet[] = "@ACNax+\r\n!G";
+    const size_t n_alpha = sizeof alphabet - 1;
+    uint64_t state = 20261003ull;
+    auto rnd = [&](uint64_t n) { state = state * 6364136223846793005ull + 1442695040888963407ull; return (state >> 33) % n; };
+    for (int it = 0; it < 2000; it++) {
+        const size_t n = (size_t)rnd(400);
+        const uint64_t nl_weight = 1 + rnd(4), at_weight = 1 + rnd(2);
+        std::string text;
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t k = rnd(n_alpha + nl_weight + at_weight);
+            text += k < n_alpha ? alphabet[k] : (k < n_alpha + nl_weight ? '\n' : '@');
+        }
+        if (!text.empty() && (uint8_t)text[0] == 0x1F) text[0] = 'A';
+        const size_t budgets[] = { 1, 7, 16, 50 };
+        const size_t budget = budgets[rnd(4)];
+        const size_t use = budget_that_fits(text, budget);
+        through_chunker(text, text, use, KAAMER_OK, "random text");
+        if (it % 4 == 0) through_chunker(gzip_members(text, text.size() / 2), text, use, KAAMER_OK, "random text, two gzip members");
+    }
+    // the byte source's gzip rules: a stream that breaks off reads as what inflated before; a bad first header: nothing
+    const std::string two = "@a\nACGT\n+\nIIII\n@b\nGGCC\n+\nIIII\n";
+    std::string gz = gzip_members(two, 15);
+    through_chunker(gz + "trailing bytes that are no gzip header", two, 1 << 20, KAAMER_OK, "gzip with trailing garbage");
+    through_chunker(std::string("\x1f\x8b\x08\xff\xff\xff\xff", 7) + " no gzip header", "", 64, KAAMER_OK, "bad first gzip header");
+    through_chunker("", "", 64, KAAMER_OK, "empty file");
+    if (g_failed) { fprintf(stderr, "%d check(s) failed\n", g_failed); return 1; }
+    printf("text_cut_check: ok\n");
+    return 0;
+}
