@@ -1181,8 +1181,8 @@ void kaamer_reader_close(kaamer_reader *rd);
  *   chunks   a text may be cut at any p with text[p-1] == '\n' and text[p] == '@': the pieces, parsed independently, give
  *            the records of the whole text in order (kaamer_text_cut_fastq).
  * Out of scope here: FASTA on the device (it needs the concatenation of TrimSpace'd lines and "upper-case every record but
- * the last", and protein files are small), strict_scanner, -pos / -aln on the text forms, the sharded handle, inflating
- * on the device, a reader thread. */
+ * the last", and protein files are small), strict_scanner, -pos / -aln on the text forms, the sharded handle, a reader
+ * thread.  (Inflating on the device: the BGZF section below.) */
 typedef struct kaamer_text_parser kaamer_text_parser;
 typedef struct { uint32_t name_off, name_len, seq_off, seq_len; } kaamer_text_span;   /* into the text */
 typedef struct {
@@ -1219,7 +1219,8 @@ void kaamer_text_parser_geometry(uint32_t out[4]);
  * format: 1 (FASTQ); 0 (FASTA) is KAAMER_E_ARG -- use the host reader (kaamer_parse_fasta + kaamer_search_batch_top_flat).
  * seq_type: base KAAMER_READS or KAAMER_NUCLEOTIDE (NucleotideSearch takes FASTQ too, search_nucleotide.go:38-39), the
  * genetic code in bits 8-15 as on every call; KAAMER_PROTEIN is KAAMER_E_ARG.  Text that starts with the gzip signature is
- * KAAMER_E_ARG: only kaamer_search_text_file inflates.  `text` is borrowed for the call (one pointer: cgo-safe).
+ * KAAMER_E_ARG: kaamer_search_text_file inflates (zlib, on the host), and whole BGZF blocks have a call of their own
+ * (kaamer_search_bgzf_top_flat below).  `text` is borrowed for the call (one pointer: cgo-safe).
  * The slot's parser and text staging (pinned host + device) are allocated at the first text call on it: an index that
  * never sees text allocates nothing for it.  rep_query / q[].src_seq of the result index the records of the text. */
 int kaamer_submit_text_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
@@ -1246,6 +1247,92 @@ typedef int (*kaamer_text_chunk_cb)(void *user, uint64_t first_seq, const char *
 int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio,
                             int64_t min_k_match, uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight,
                             kaamer_text_chunk_cb cb, void *user, kaamer_counters *total);
+
+/* ------------------------------------------------------------------------- */
+/* BGZF inflated on the device.  BGZF (what bgzip, htslib and most sequencer  */
+/* pipelines write) is a run of independent gzip members of at most 64 KiB of */
+/* text each, every member's compressed size in its header and its inflated   */
+/* size and CRC-32 in its trailer: the host finds the blocks without          */
+/* inflating, every block is inflated by a wave of its own (inflate.hip.inc). */
+/* Ordinary single-member gzip, FASTA, -pos / -aln and the sharded handle     */
+/* stay with the host readers above.                                          */
+/* ------------------------------------------------------------------------- */
+/* One block: the deflate payload is bytes[comp_off, comp_off + comp_len) -- what lies between the member's header and
+ * its 8-byte trailer -- and inflates to isize bytes (at most 65536) with CRC-32 crc. */
+typedef struct { uint64_t comp_off; uint32_t comp_len, isize, crc, reserved; } kaamer_bgzf_block;
+/* CPU only.  Walks the member headers of bytes[0, len) without inflating: a BGZF header is 1f 8b 08, FLG exactly 4, and an
+ * extra field that holds (walked subfield by subfield) a subfield 'B' 'C' with SLEN 2, whose value is the member's size
+ * minus 1 (BSIZE).  Fills blocks[0, min(*n_blocks, cap)) and stops at the first member that is no BGZF block or is not whole
+ * in the buffer -- also one without the BC subfield, with BSIZE + 1 below header + trailer, or with ISIZE above 65536.
+ * *n_blocks: the whole blocks found (it may exceed cap: call again with more room); *consumed: where the walk stopped
+ * (== len: the buffer is whole BGZF blocks).  The 28-byte empty end-of-file block is an ordinary block with isize 0.
+ * blocks may be NULL when cap is 0. */
+int kaamer_bgzf_scan(const uint8_t *bytes, uint64_t len, kaamer_bgzf_block *blocks, uint64_t cap, uint64_t *n_blocks,
+                     uint64_t *consumed);
+
+typedef struct kaamer_inflater kaamer_inflater;
+typedef struct {
+    uint32_t n_bad;                     /* blocks whose status is not 0 */
+    uint32_t first_bad;                 /* the first of them (0xFFFFFFFF: none) */
+    uint64_t out_bytes;                 /* the sum of the blocks' isize */
+    uint32_t first_bad_status;          /* its status word (0: none) */
+    uint32_t reserved;
+    const uint32_t *d_status;           /* device: one word per block */
+} kaamer_inflate_result;
+/* An inflater holds the per-block device words for calls of up to max_blocks blocks and max_comp_bytes compressed bytes. */
+int kaamer_inflater_create(int device, uint64_t max_comp_bytes, uint32_t max_blocks, kaamer_inflater **out);
+void kaamer_inflater_free(kaamer_inflater *inf);
+/* Enqueues on `stream` the inflate of d_blocks[0, n_blocks) (device, 8-byte aligned; comp_off relative to d_comp, which
+ * holds comp_bytes bytes: a block whose payload is not inside them is status 4 and is not read): block b
+ * goes to d_out + (the sum of isize of the blocks before it) -- the text of the blocks back to back, at any alignment.
+ * Every block is a full RFC 1951 inflate (stored, fixed and dynamic blocks, any number of them) checked against isize and
+ * crc, and ends with a status word: 0 good; 1 bad block type, stored length mismatch or payload left behind the final
+ * block; 2 over-subscribed or incomplete code; 3 invalid symbol or distance (BGZF blocks share no window: a distance
+ * beyond the block's own output is invalid); 4 input exhausted; 5 more output than ISIZE (or than out_cap holds); 6 less
+ * output than ISIZE; 7 CRC-32 mismatch.  No input makes the kernel read outside a block's payload or write outside the
+ * block's isize bytes.  The bytes of a bad block's output are unspecified. */
+int kaamer_inflate_bgzf_device(kaamer_inflater *inf, const uint8_t *d_comp, uint64_t comp_bytes, const kaamer_bgzf_block *d_blocks,
+                               uint32_t n_blocks, uint8_t *d_out, uint64_t out_cap, void *stream);
+/* Waits for the last inflate enqueued on `stream`; d_status is valid until the next inflate. */
+int kaamer_inflater_finish(kaamer_inflater *inf, void *stream, kaamer_inflate_result *out);
+/* The tiling (tests put their boundary cases there): out[0] bytes of output per lane of the CRC, out[1] BGZF blocks (waves)
+ * per workgroup, out[2] bytes of text per workgroup of the cut kernel. */
+void kaamer_inflater_geometry(uint32_t out[3]);
+/* kaamer_text_cut_fastq of a text that lives on the device (the caller of the device inflate never holds it): waits. */
+int kaamer_text_cut_fastq_device(int device, const uint8_t *d_text, uint64_t n_bytes, void *stream, uint64_t *cut);
+
+/* kaamer_submit_text_top_flat / kaamer_search_text_top_flat for FASTQ that is BGZF-compressed: `bytes` must be whole BGZF
+ * blocks (kaamer_bgzf_scan consumes all of them; anything else -- ordinary gzip, plain text, a block cut short -- is
+ * KAAMER_E_ARG, and kaamer_submit_text_top_flat keeps refusing gzip bytes: this call is the opt-in).  The compressed bytes
+ * and the block table are uploaded to the slot (about a fifth of the text's bytes), then inflated, parsed and searched on
+ * the slot's stream.  A block that does not inflate is KAAMER_E_FORMAT, with the block's index and its status word in
+ * kaamer_last_error: hand such bytes to the host inflater.  The spans of kaamer_batch_top_text_spans index the INFLATED
+ * text, which is copied back with the result: kaamer_batch_top_text (a view into `out`; NULL / 0 for any other call's
+ * result).  `bytes` is borrowed for the call. */
+int kaamer_submit_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                int64_t min_k_match, uint32_t max_results, kaamer_ticket **ticket);
+int kaamer_search_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out);
+int kaamer_batch_top_text(const kaamer_batch_top *out, const char **text, uint64_t *len);
+
+/* kaamer_search_text_file with one more argument.  device_inflate = 0 is kaamer_search_text_file.  device_inflate = 1:
+ *   plain files   take that path too;
+ *   a gzip file   is read raw and scanned with kaamer_bgzf_scan; whole blocks are grouped until their ISIZEs reach
+ *                 chunk_text_bytes.  The device text of chunk k is the tail of chunk k-1 (a short plain upload) followed by
+ *                 its blocks' output (out offsets: the prefix sum of ISIZE behind the tail); it is cut on the device at
+ *                 kaamer_text_cut_fastq's place (the last chunk: at its end), [0, cut) is parsed and searched, [cut, end)
+ *                 comes back as the next tail.  A chunk without a cut takes one more budget of blocks, up to four, then
+ *                 fails with kaamer_search_text_file's KAAMER_E_CAPACITY.  The callback keeps its contract: text, len is
+ *                 the chunk's inflated text [0, cut) -- the copy brought back from the device -- with spans into it.
+ *   fallback      as soon as a chunk reports a bad block, the scan meets a member that is no BGZF block (ordinary gzip,
+ *                 FNAME set, ...) or the file ends inside a block, the file's position at that chunk's first block goes to
+ *                 the host inflater with the pending tail in front, and the rest of the file runs on the flag-0 route.
+ * The concatenated text the callbacks see is byte for byte the flag-0 run's, for every file; the chunk boundaries differ.
+ * The submit of a device chunk waits twice on the replica's stream (status words + cut, then the parse's counts: the
+ * parser takes the text's length from the host). */
+int kaamer_search_text_file_opts(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio,
+                                 int64_t min_k_match, uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight,
+                                 int32_t device_inflate, kaamer_text_chunk_cb cb, void *user, kaamer_counters *total);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,11 @@ class TextParseResult(C.Structure):
                 ("d_seqs", C.c_void_p), ("d_offsets", C.c_void_p), ("d_spans", C.c_void_p)]
 
 
+class InflateResult(C.Structure):   # kaamer_inflate_result
+    _fields_ = [("n_bad", C.c_uint32), ("first_bad", C.c_uint32), ("out_bytes", C.c_uint64), ("first_bad_status", C.c_uint32),
+                ("reserved", C.c_uint32), ("d_status", C.c_void_p)]
+
+
 # every symbol include/kaamer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "kaamer_last_error": (C.c_char_p, []),
@@ -414,6 +419,21 @@ SYMBOLS = {
     # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total)
     "kaamer_search_text_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    # BGZF inflated on the device: the host scan of the block headers, the inflater, the cut on the device
+    "kaamer_bgzf_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kaamer_inflater_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_inflater_free": (None, [C.c_void_p]),
+    "kaamer_inflate_bgzf_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_inflater_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(InflateResult)]),
+    "kaamer_inflater_geometry": (None, [C.POINTER(C.c_uint32)]),
+    "kaamer_text_cut_fastq_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    # (handle, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, out)
+    "kaamer_submit_bgzf_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_bgzf_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_void_p]),
+    "kaamer_batch_top_text": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, device_inflate, cb, user, total)
+    "kaamer_search_text_file_opts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 }
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range

@@ -288,6 +288,12 @@ class TopResult:
         if bool(sp):
             self.text_spans = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint8)), shape=(ns.value * 16,)).copy().view(SPAN_DTYPE) \
                 if ns.value else np.zeros(0, SPAN_DTYPE)
+        # the text a BGZF call inflated on the device (kaamer_batch_top_text): what text_spans index; None for other calls
+        self.text = None
+        tp, tn = C.c_void_p(), C.c_uint64()
+        abi.check(abi.lib().kaamer_batch_top_text(out, C.byref(tp), C.byref(tn)))
+        if tp.value:
+            self.text = C.string_at(tp.value, tn.value)
         self.alignments = None
         items, text = C.POINTER(abi.Alignment)(), C.POINTER(C.c_char)()
         abi.check(abi.lib().kaamer_batch_top_alignments(out, C.byref(items), C.byref(text)))
@@ -559,6 +565,25 @@ class Index:
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
+    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10):
+        """kaamer_search_bgzf_top_flat: whole BGZF blocks of FASTQ (bytes) in, the reported hits out -- the compressed bytes
+        are uploaded, inflated, parsed and searched on the device.  TopResult.text: the inflated text; text_spans index it.
+        Bytes that are not whole BGZF blocks: KaamerError E_ARG; a block that does not inflate: E_FORMAT."""
+        data = bytes(data)
+        out = C.POINTER(abi.BatchTop)()
+        abi.check(abi.lib().kaamer_search_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
+        try:
+            return TopResult(out)
+        finally:
+            abi.lib().kaamer_batch_top_free(out)
+
+    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10):
+        """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans)"""
+        data = bytes(data)
+        t = C.c_void_p()
+        abi.check(abi.lib().kaamer_submit_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
+        return TopTicket(t)
+
     def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq"):
         """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans)"""
         data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
@@ -823,10 +848,12 @@ class Replicas:
     TEXT_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(abi.BatchTop))
 
     def search_text_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
-                         chunk_text_bytes=1 << 28, in_flight=0, on_chunk=None):
+                         chunk_text_bytes=1 << 28, in_flight=0, on_chunk=None, device_inflate=False):
         """kaamer_search_text_file: the file's FASTQ text (plain or gzip) is cut into chunks of about chunk_text_bytes, each
         parsed and searched on a replica.  on_chunk(first_seq, text bytes, TopResult) per chunk, in input order; the
-        TopResult's text_spans index `text`, its rep_query counts from the chunk's first record.  -> summed counters"""
+        TopResult's text_spans index `text`, its rep_query counts from the chunk's first record.  -> summed counters
+        device_inflate (kaamer_search_text_file_opts): a BGZF file is inflated on the device, block by block; anything else
+        in a gzip file falls back to the host inflater from that chunk on.  The concatenated texts are the same."""
         err = []
 
         def cb(user, first, text, length, spans, n_records, top):
@@ -839,8 +866,11 @@ class Replicas:
                 return 1
         c = abi.Counters()
         cfn = Replicas.TEXT_CHUNK_CB(cb)
-        rc = abi.lib().kaamer_search_text_file(self._h, str(path).encode(), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio, min_k_match,
-                                               max_results, int(chunk_text_bytes), in_flight, C.cast(cfn, C.c_void_p), None, C.byref(c))
+        args = (self._h, str(path).encode(), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio, min_k_match, max_results, int(chunk_text_bytes), in_flight)
+        if device_inflate:
+            rc = abi.lib().kaamer_search_text_file_opts(*args, 1, C.cast(cfn, C.c_void_p), None, C.byref(c))
+        else:
+            rc = abi.lib().kaamer_search_text_file(*args, C.cast(cfn, C.c_void_p), None, C.byref(c))
         if err:
             raise err[0]
         abi.check(rc)
@@ -1302,6 +1332,95 @@ def parse_fastq_device(text, device=0):
         return p.parse(data)
     finally:
         p.close()
+
+
+BGZF_BLOCK_DTYPE = np.dtype([("comp_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4"), ("crc", "<u4"), ("reserved", "<u4")])   # kaamer_bgzf_block
+
+
+def bgzf_scan(data):
+    """kaamer_bgzf_scan (CPU): the BGZF blocks at the start of `data` (bytes), found without inflating ->
+    (blocks as a BGZF_BLOCK_DTYPE array, consumed).  consumed == len(data): the bytes are whole BGZF blocks."""
+    data = bytes(data)
+    n, used = C.c_uint64(), C.c_uint64()
+    L = abi.lib()
+    abi.check(L.kaamer_bgzf_scan(data, len(data), None, 0, C.byref(n), C.byref(used)))
+    blocks = np.zeros(int(n.value), BGZF_BLOCK_DTYPE)
+    if len(blocks):
+        abi.check(L.kaamer_bgzf_scan(data, len(data), blocks.ctypes.data, len(blocks), C.byref(n), C.byref(used)))
+    return blocks, int(used.value)
+
+
+def inflater_geometry():
+    """kaamer_inflater_geometry -> dict(crc_segment, blocks_per_workgroup, cut_tile)"""
+    g = (C.c_uint32 * 3)()
+    abi.lib().kaamer_inflater_geometry(g)
+    return dict(crc_segment=int(g[0]), blocks_per_workgroup=int(g[1]), cut_tile=int(g[2]))
+
+
+def text_cut_fastq_device(text, device=0):
+    """kaamer_text_cut_fastq_device of `text` (bytes), uploaded for the call (tests)"""
+    import torch
+    data = bytes(text)
+    with torch.cuda.device(device):
+        d = torch.frombuffer(bytearray(data) if data else bytearray(1), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        cut = C.c_uint64()
+        abi.check(abi.lib().kaamer_text_cut_fastq_device(device, d.data_ptr(), len(data), None, C.byref(cut)))
+        del d
+    return int(cut.value)
+
+
+class Inflater:
+    """kaamer_inflater_*: BGZF blocks inflated on the device, one wave per block, for calls of up to max_blocks blocks
+    within max_comp_bytes compressed bytes"""
+
+    def __init__(self, max_comp_bytes, max_blocks, device=0):
+        self.device = device
+        self.max_comp_bytes = int(max_comp_bytes)
+        self.max_blocks = int(max_blocks)
+        h = C.c_void_p()
+        abi.check(abi.lib().kaamer_inflater_create(device, self.max_comp_bytes, self.max_blocks, C.byref(h)))
+        self._h = h
+
+    def inflate_device(self, d_comp_ptr, comp_bytes, d_blocks_ptr, n_blocks, d_out_ptr, out_cap, stream=0):
+        """kaamer_inflate_bgzf_device + kaamer_inflater_finish on device buffers -> abi.InflateResult"""
+        abi.check(abi.lib().kaamer_inflate_bgzf_device(self._h, d_comp_ptr, comp_bytes, d_blocks_ptr, n_blocks, d_out_ptr, out_cap, stream))
+        r = abi.InflateResult()
+        abi.check(abi.lib().kaamer_inflater_finish(self._h, stream, C.byref(r)))
+        return r
+
+    def inflate(self, comp_tensor, blocks, out_offset=0):
+        """comp_tensor: the compressed bytes (a uint8 tensor on the device, or bytes: uploaded); blocks: BGZF_BLOCK_DTYPE
+        array (bgzf_scan).  The text goes to a fresh device buffer `out_offset` bytes behind its start.
+        -> dict(text u8 array, status u32 array, n_bad, first_bad, out_bytes)"""
+        import torch
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        total = int(blocks["isize"].astype(np.uint64).sum())
+        with torch.cuda.device(self.device):
+            comp_bytes = int(comp_tensor.numel()) if torch.is_tensor(comp_tensor) else len(bytes(comp_tensor))
+            if not torch.is_tensor(comp_tensor):
+                comp_tensor = torch.frombuffer(bytearray(bytes(comp_tensor)) or bytearray(1), dtype=torch.uint8).cuda()
+            d_blocks = torch.frombuffer(bytearray(blocks.tobytes()) or bytearray(24), dtype=torch.uint8).cuda()
+            d_out = torch.full((out_offset + total + 64,), 0xEE, dtype=torch.uint8, device="cuda")   # guard bytes on both sides
+            torch.cuda.synchronize()
+            r = self.inflate_device(comp_tensor.data_ptr(), comp_bytes, d_blocks.data_ptr(), len(blocks), d_out.data_ptr() + out_offset, total)
+            status = np.empty(len(blocks), np.uint32)
+            if len(blocks):
+                assert _hip_runtime().hipMemcpy(status.ctypes.data, C.c_void_p(r.d_status), status.nbytes, 2) == 0
+            whole = d_out.cpu().numpy()
+        return dict(text=whole[out_offset:out_offset + total].copy(), guard=(whole[:out_offset].copy(), whole[out_offset + total:].copy()),
+                    status=status, n_bad=int(r.n_bad), first_bad=int(r.first_bad), first_bad_status=int(r.first_bad_status), out_bytes=int(r.out_bytes))
+
+    def close(self):
+        if self._h:
+            abi.lib().kaamer_inflater_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def align_pairs(seqs=None, packed=None, pairs=(), number_of_aa=0, sub_matrix="blosum62", gap_open=11, gap_extend=1, device=0):

@@ -248,6 +248,46 @@ uint64_t kaamer_text_cut_fastq(const char *text, uint64_t len)
     return 0;
 }
 
+// The blocks of a BGZF stream, found without inflating (the rules: include/kaamer_hip.h).  A member is
+//   1f 8b 08 FLG=4 MTIME(4) XFL OS XLEN(2) | extra field of XLEN bytes: subfields SI1 SI2 SLEN(2) data | deflate | CRC32 ISIZE
+// and the subfield 'B' 'C' with SLEN 2 holds BSIZE = the member's size - 1.
+int kaamer_bgzf_scan(const uint8_t *bytes, uint64_t len, kaamer_bgzf_block *blocks, uint64_t cap, uint64_t *n_blocks, uint64_t *consumed)
+{
+    if (!n_blocks || !consumed || (!bytes && len) || (!blocks && cap)) return kaamer_fail(KAAMER_E_ARG, "bgzf_scan: bad argument");
+    uint64_t at = 0, n = 0;
+    auto u16 = [&](uint64_t p) { return (uint32_t)bytes[p] | (uint32_t)bytes[p + 1] << 8; };
+    auto u32 = [&](uint64_t p) { return u16(p) | u16(p + 2) << 16; };
+    while (len - at >= 12) {
+        if (bytes[at] != 0x1F || bytes[at + 1] != 0x8B || bytes[at + 2] != 0x08 || bytes[at + 3] != 4) break;
+        const uint64_t xlen = u16(at + 10), extra = at + 12;
+        if (len - extra < xlen) break;
+        uint64_t bsize1 = 0;   // BSIZE + 1; 0: no BC subfield
+        for (uint64_t f = 0; xlen - f >= 4;) {
+            const uint64_t slen = u16(extra + f + 2);
+            if (xlen - f - 4 < slen) break;   // a subfield that leaves the extra field
+            if (bytes[extra + f] == 'B' && bytes[extra + f + 1] == 'C' && slen == 2) { bsize1 = (uint64_t)u16(extra + f + 4) + 1; break; }
+            f += 4 + slen;
+        }
+        const uint64_t head = 12 + xlen;
+        if (!bsize1 || bsize1 < head + 8 || len - at < bsize1) break;
+        const uint32_t isize = u32(at + bsize1 - 4);
+        if (isize > 65536) break;
+        if (n < cap) {
+            kaamer_bgzf_block &b = blocks[n];
+            b.comp_off = at + head;
+            b.comp_len = (uint32_t)(bsize1 - head - 8);
+            b.isize = isize;
+            b.crc = u32(at + bsize1 - 8);
+            b.reserved = 0;
+        }
+        n++;
+        at += bsize1;
+    }
+    *n_blocks = n;
+    *consumed = at;
+    return KAAMER_OK;
+}
+
 // ---- the same readers over a FILE, in chunks: search.go:240-283 opens the file, sniffs the first 32 bytes, wraps a
 // gzip.Reader around it when they carry the gzip signature and scans line by line; a 100 M-read file is never in
 // memory as a whole (configs[4]).  kaamer_reader_next hands out up to max_seqs records / about max_bytes of sequence
@@ -386,6 +426,13 @@ kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget)
 }
 
 void kaamer_text_chunker_free(kaamer_text_chunker *c) { delete c; }
+// text that precedes what the byte source will give (a reader that takes over in the middle of a file)
+void kaamer_text_chunker_prime(kaamer_text_chunker *c, const char *text, size_t len)
+{
+    if (c->acc.size() < c->acc_len + len) c->acc.resize(c->acc_len + len);
+    if (len) memcpy(c->acc.data() + c->acc_len, text, len);
+    c->acc_len += len;
+}
 bool kaamer_text_chunker_done(const kaamer_text_chunker *c) { return c->over && c->acc_len == 0; }
 
 int kaamer_text_chunker_next(kaamer_text_chunker *c, std::vector<char> *chunk, size_t *len)

@@ -5,6 +5,9 @@
 //                                 parses it on the slot's stream (parse_text.hip.inc), waits for the two counts, then
 //                                 enqueues what kaamer_submit_batch_top_flat enqueues -- on the parser's buffers
 //   kaamer_wait_batch_top         as for every ticket; the result carries the records' spans
+//   kaamer_submit_bgzf_top_flat   the same call for whole BGZF blocks: the COMPRESSED bytes and the block table go up, the
+//                                 slot's inflater (inflate.hip.inc) writes the text where the upload would have put it, and
+//                                 the text comes back with the result (kaamer_batch_top_text), since the caller never had it
 // The slot's parser starts from an estimate of the record count and, as every other bound of these calls, grows when the
 // device reports KAAMER_E_CAPACITY: the text is on the device by then, only the parse is repeated.
 
@@ -12,10 +15,10 @@
 static uint32_t text_hard_records(uint64_t len) { return (uint32_t)(len / 2 + 1); }
 
 // parser and staging of a slot for `len` bytes of text with the bounds (recs, lines)
-static int text_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t len, uint32_t recs, uint64_t lines)
+static int text_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t len, uint32_t recs, uint64_t lines, bool host_staging = true)
 {
     if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-    if (h.h_text_cap < len) {
+    if (host_staging && h.h_text_cap < len) {
         HIPCHK(hipStreamSynchronize(h.stream));
         if (h.h_text) (void)hipHostFree(h.h_text);
         h.h_text = nullptr; h.h_text_cap = 0;
@@ -45,17 +48,83 @@ static int text_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t len, uint32_
     return KAAMER_OK;
 }
 
-static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, const kaamer_topn_opts *top,
-                       bool blocking, kaamer_ticket **out)
+// whole BGZF blocks as the input of a text call: `len` of text_submit is then the sum of the blocks' isize
+struct BgzfInput {
+    const uint8_t *bytes;
+    uint64_t len;
+    const std::vector<kaamer_bgzf_block> *blocks;
+    // the file form (host_text_file.hip.inc): the text on the device is `tail` (what the previous chunk left behind its cut)
+    // followed by the blocks' output; it is cut on the device (last: at its end) and only [0, cut) is parsed and searched
+    bool file = false, last = false;
+    const char *tail = nullptr;
+    uint64_t tail_len = 0;
+    std::vector<char> *tail_out = nullptr;   // the text behind the cut, for the next chunk
+    bool *no_cut = nullptr;                  // set with KAAMER_E_CAPACITY: no line of the text starts with '@'
+};
+
+// staging (pinned + device: the compressed bytes, then the block table at the next multiple of 8) and inflater of a slot
+static int bgzf_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t comp_len, size_t n_blocks)
 {
-    if (!ix || !top || !out || (!text && len) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: bad argument");
+    if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+    const size_t need = (size_t)((comp_len + 7) & ~7ull) + n_blocks * sizeof(kaamer_bgzf_block);
+    if (h.h_comp_cap < need || h.d_comp_cap < need) {
+        HIPCHK(hipStreamSynchronize(h.stream));
+        if (h.h_comp) (void)hipHostFree(h.h_comp);
+        if (h.d_comp) (void)hipFree(h.d_comp);
+        h.h_comp = nullptr; h.d_comp = nullptr; h.h_comp_cap = h.d_comp_cap = 0;
+        const size_t cap = need + need / 4 + 4096;
+        if (hipHostMalloc((void **)&h.h_comp, cap, hipHostMallocDefault) != hipSuccess) return kaamer_fail(KAAMER_E_NOMEM, "pinned BGZF staging (%zu bytes)", cap);
+        h.h_comp_cap = cap;
+        const int rc = dev_alloc(&h.d_comp, cap);
+        if (rc) return rc;
+        h.d_comp_cap = cap;
+    }
+    if (!h.inflater || h.inflater_comp < comp_len || h.inflater_blocks < n_blocks) {
+        HIPCHK(hipStreamSynchronize(h.stream));
+        if (h.inflater) kaamer_inflater_free(h.inflater);
+        h.inflater = nullptr;
+        const uint64_t comp_cap = comp_len + comp_len / 4 + 4096;
+        const uint32_t blocks_cap = (uint32_t)(n_blocks + n_blocks / 4 + 64);
+        const int rc = kaamer_inflater_create(ix->device, comp_cap, blocks_cap, &h.inflater);
+        if (rc) { h.inflater = nullptr; return rc; }
+        h.inflater_comp = comp_cap; h.inflater_blocks = blocks_cap;
+    }
+    return KAAMER_OK;
+}
+
+// compressed bytes and block table up, the text into h.d_text (behind the tail of the file form); waits once for the
+// status words' summary and, in the file form, the cut.  A bad block: KAAMER_E_FORMAT.
+static int bgzf_inflate_to_slot(TopSlot &h, const BgzfInput &bz, uint64_t text_len, uint64_t *cut)
+{
+    const size_t n = bz.blocks->size(), table_at = (size_t)((bz.len + 7) & ~7ull);
+    if (bz.len) memcpy(h.h_comp, bz.bytes, (size_t)bz.len);   // the caller's buffer is only borrowed for this call
+    if (n) memcpy(h.h_comp + table_at, bz.blocks->data(), n * sizeof(kaamer_bgzf_block));
+    if (table_at + n) HIPCHK(hipMemcpyAsync(h.d_comp, h.h_comp, table_at + n * sizeof(kaamer_bgzf_block), hipMemcpyHostToDevice, h.stream));
+    if (bz.tail_len) HIPCHK(hipMemcpyAsync(h.d_text, bz.tail, (size_t)bz.tail_len, hipMemcpyHostToDevice, h.stream));
+    const bool want_cut = bz.file && !bz.last;
+    int rc = inf_enqueue(h.inflater, h.d_comp, bz.len, reinterpret_cast<const kaamer_bgzf_block *>(h.d_comp + table_at), (uint32_t)n,
+                         h.d_text + bz.tail_len, text_len - bz.tail_len, h.d_text, want_cut ? text_len : 0, h.stream);
+    kaamer_inflate_result res;
+    if (!rc) rc = kaamer_inflater_finish(h.inflater, h.stream, &res);
+    if (rc) return rc;
+    if (res.n_bad)
+        return kaamer_fail(KAAMER_E_FORMAT, "search_bgzf_top: BGZF block %u does not inflate: status %u (%u bad of %zu blocks)", res.first_bad,
+                           res.first_bad_status, res.n_bad, n);
+    *cut = want_cut ? h.inflater->h_res[INF_R_CUT] : text_len;
+    return KAAMER_OK;
+}
+
+static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, const kaamer_topn_opts *top,
+                       bool blocking, kaamer_ticket **out, const BgzfInput *bz = nullptr)
+{
+    if (!ix || !top || !out || (!text && len && !bz) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: bad argument");
     *out = nullptr;
     if (format == 0)
         return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTA is not parsed on the device: use the host reader (kaamer_parse_fasta, then kaamer_submit_batch_top_flat)");
     if (format != 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: unknown format %d (1 = FASTQ)", (int)format);
     SEQ_TYPE_CHK(seq_type, "submit_text_top");
     if (!is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
-    if (kaamer_is_gzip(text, len))
+    if (!bz && kaamer_is_gzip(text, len))
         return kaamer_fail(KAAMER_E_ARG, "submit_text_top: the text starts with the gzip signature: inflate it first (kaamer_search_text_file does)");
     if (len > 0xFFFFFFFFull)
         return kaamer_fail(KAAMER_E_ARG, "submit_text_top: a text holds at most 2^32 - 1 bytes (spans are 32-bit): cut it (kaamer_text_cut_fastq)");
@@ -84,8 +153,27 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
     memset(&pr, 0, sizeof pr);
     bool uploaded = false;
     while (!rc) {
-        rc = text_slot_prepare(ix, h, len, recs, lines);
+        rc = text_slot_prepare(ix, h, len, recs, lines, !bz);
         if (rc) break;
+        if (!uploaded && bz) {
+            rc = bgzf_slot_prepare(ix, h, bz->len, bz->blocks->size());
+            uint64_t cut = len;
+            if (!rc) rc = bgzf_inflate_to_slot(h, *bz, len, &cut);
+            if (!rc && bz->file) {
+                if (cut == 0 && !bz->last && len) { *bz->no_cut = true; rc = KAAMER_E_CAPACITY; }   // (the source grows the chunk or gives up)
+                else {
+                    // the tail goes home with the wait for the parse's counts; from here on the text is [0, cut)
+                    bz->tail_out->resize((size_t)(len - cut));
+                    if (len > cut) {
+                        he = hipMemcpyAsync(bz->tail_out->data(), h.d_text + cut, (size_t)(len - cut), hipMemcpyDeviceToHost, h.stream);
+                        if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(he));
+                    }
+                    len = cut;
+                }
+            }
+            if (rc) break;
+            uploaded = true;
+        }
         if (!uploaded) {
             if (len) {
                 memcpy(h.h_text, text, (size_t)len);   // the caller's buffer is only borrowed for this call
@@ -112,11 +200,21 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
         he = hipMemcpyAsync(t->h_spans, pr.d_spans, (size_t)pr.n_records * sizeof(kaamer_text_span), hipMemcpyDeviceToHost, h.stream);
         if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(he));
     }
+    if (!rc && bz) {   // the caller never held the text: it rides back with the result
+        t->text_len = len;
+        t->h_text_out = (char *)pinned_get((size_t)len + 1, &t->h_text_out_cap);
+        if (!t->h_text_out) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned text (%llu bytes)", (unsigned long long)len);
+        if (!rc && len) {
+            he = hipMemcpyAsync(t->h_text_out, h.d_text, (size_t)len, hipMemcpyDeviceToHost, h.stream);
+            if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(he));
+        }
+    }
     if (!rc) rc = top_enqueue(t);
     if (rc) {
         if (h.stream) (void)hipStreamSynchronize(h.stream);
         if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
         if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
+        if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
         delete t;
         top_slot_release(ix, slot);
         return rc;
@@ -143,6 +241,54 @@ int kaamer_search_text_top_flat(kaamer_index *ix, const char *text, uint64_t len
     return kaamer_wait_batch_top(t, out);
 }
 
+// whole BGZF blocks: scanned on the host (no inflate), inflated, parsed and searched on the slot's stream
+int kaamer_submit_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                uint32_t max_results, kaamer_ticket **ticket)
+{
+    if (ticket) *ticket = nullptr;
+    if (!ix || !ticket || (!bytes && len)) return kaamer_fail(KAAMER_E_ARG, "submit_bgzf_top: bad argument");
+    std::vector<kaamer_bgzf_block> blocks;
+    uint64_t n = 0, used = 0;
+    int rc = kaamer_bgzf_scan(bytes, len, nullptr, 0, &n, &used);
+    if (rc) return rc;
+    if (used != len)
+        return kaamer_fail(KAAMER_E_ARG, "submit_bgzf_top: the bytes are not whole BGZF blocks (%llu blocks in the first %llu of %llu bytes): "
+                                         "ordinary gzip and plain text go through the host (kaamer_search_text_file, kaamer_search_text_top_flat)",
+                           (unsigned long long)n, (unsigned long long)used, (unsigned long long)len);
+    if (n > 0xFFFFFFF0ull) return kaamer_fail(KAAMER_E_ARG, "submit_bgzf_top: too many blocks");
+    blocks.resize((size_t)n);
+    rc = kaamer_bgzf_scan(bytes, len, blocks.data(), n, &n, &used);
+    if (rc) return rc;
+    uint64_t text_len = 0;
+    for (const kaamer_bgzf_block &b : blocks) text_len += b.isize;
+    kaamer_topn_opts top;
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    const BgzfInput bz = { bytes, len, &blocks };
+    return text_submit(ix, nullptr, text_len, 1, seq_type, &top, true, ticket, &bz);
+}
+
+int kaamer_search_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                uint32_t max_results, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_bgzf_top_flat(ix, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+int kaamer_batch_top_text(const kaamer_batch_top *out, const char **text, uint64_t *len)
+{
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_text: bad argument");
+    const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
+    if (!bo->text) return KAAMER_OK;   // the caller of any other call holds the text (or the batch) itself
+    if (text) *text = bo->text;
+    if (len) *len = bo->text_len;
+    return KAAMER_OK;
+}
+
 int kaamer_batch_top_text_spans(const kaamer_batch_top *out, const kaamer_text_span **spans, uint32_t *n_records)
 {
     if (spans) *spans = nullptr;
@@ -152,6 +298,16 @@ int kaamer_batch_top_text_spans(const kaamer_batch_top *out, const kaamer_text_s
     if (!bo->spans) return KAAMER_OK;   // the call took a packed batch
     if (spans) *spans = bo->spans;
     if (n_records) *n_records = bo->n_spans;
+    return KAAMER_OK;
+}
+
+// whole BGZF blocks of a file (with the tail in front) into the FIFO of a stream: as stream_push_text
+static int stream_push_bgzf(kaamer_stream *st, const BgzfInput &bz, uint64_t text_len)
+{
+    kaamer_ticket *t = nullptr;
+    const int rc = text_submit(st->ix, nullptr, text_len, 1, st->seq_type, &st->top, st->fifo->empty(), &t, &bz);
+    if (rc) return rc;
+    st->fifo->push_back(t);
     return KAAMER_OK;
 }
 

@@ -31,6 +31,10 @@ struct batch_top_owner {
     kaamer_text_span *spans = nullptr;
     size_t spans_cap = 0;
     uint32_t n_spans = 0;
+    // the text of a BGZF call, inflated on the device and brought back with the result (the spans index it): pinned
+    char *text = nullptr;
+    size_t text_cap = 0;
+    uint64_t text_len = 0;
 };
 
 // the alignment half of a request (kaamer_*_batch_top_aln_flat)
@@ -81,6 +85,9 @@ struct kaamer_ticket {
     const uint64_t *d_text_off;
     kaamer_text_span *h_spans;   // pinned; goes to the result
     size_t h_spans_cap;
+    char *h_text_out;            // a BGZF call: the inflated text, pinned; goes to the result
+    size_t h_text_out_cap;
+    uint64_t text_len;
 };
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
@@ -232,6 +239,9 @@ static void top_slot_free(TopSlot &h)
     if (h.parser) kaamer_text_parser_free(h.parser);
     if (h.h_text) (void)hipHostFree(h.h_text);
     if (h.d_text) (void)hipFree(h.d_text);
+    if (h.inflater) kaamer_inflater_free(h.inflater);
+    if (h.h_comp) (void)hipHostFree(h.h_comp);
+    if (h.d_comp) (void)hipFree(h.d_comp);
     if (h.stream) (void)hipStreamDestroy(h.stream);
     h = TopSlot();
 }
@@ -473,6 +483,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         bo->pub.max_results = t->top.max_results;
         bo->has_pos = t->want_pos;
         if (t->text) { bo->spans = t->h_spans; bo->spans_cap = t->h_spans_cap; bo->n_spans = t->n_seqs; t->h_spans = nullptr; }
+        if (t->h_text_out) { bo->text = t->h_text_out; bo->text_cap = t->h_text_out_cap; bo->text_len = t->text_len; t->h_text_out = nullptr; }
         if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
         if (!nucl) bo->pub.orf_aa = nullptr;
         if (!rc) *out = &bo->pub;
@@ -480,6 +491,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
     }
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
     if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
+    if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
     top_slot_release(ix, t->slot);
     delete t;
     return rc;
@@ -497,6 +509,7 @@ void kaamer_ticket_discard(kaamer_ticket *t)
     if (h.ws) h.ws->clean = false;  // its status was not looked at: the next batch starts from cleared per-batch state
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
     if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
+    if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
     top_slot_release(ix, t->slot);
     delete t;
 }
@@ -613,6 +626,7 @@ void kaamer_batch_top_free(kaamer_batch_top *out)
     batch_top_owner *bo = reinterpret_cast<batch_top_owner *>(out);  // pub is the first member
     if (bo->block) { if (bo->pinned) pinned_put(bo->block, bo->block_cap); else free(bo->block); }
     if (bo->spans) pinned_put(bo->spans, bo->spans_cap);
+    if (bo->text) pinned_put(bo->text, bo->text_cap);
     delete bo;
 }
 

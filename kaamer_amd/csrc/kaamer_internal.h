@@ -56,6 +56,7 @@ kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget)
 int kaamer_text_chunker_next(kaamer_text_chunker *c, std::vector<char> *chunk, size_t *len);
 bool kaamer_text_chunker_done(const kaamer_text_chunker *c);
 void kaamer_text_chunker_free(kaamer_text_chunker *c);
+void kaamer_text_chunker_prime(kaamer_text_chunker *c, const char *text, size_t len);   // text in front of the source's
 
 // The alignment step's shared statements (align.hip), for the stage that aligns the reported hits of a top-N call
 // (search.hip: top_align.hip.inc): the integers of one alignment as the device leaves them ...

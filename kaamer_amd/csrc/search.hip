@@ -37,6 +37,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -156,6 +157,13 @@ struct TopSlot {
     uint32_t parser_recs = 0;
     uint8_t *h_text = nullptr, *d_text = nullptr; // pinned / device
     size_t h_text_cap = 0, d_text_cap = 0;
+    // the BGZF call (kaamer_search_bgzf_top_flat), allocated at the slot's first one: compressed bytes, then (8-byte
+    // aligned) the block table -- pinned and device -- and the inflater
+    kaamer_inflater *inflater = nullptr;
+    uint64_t inflater_comp = 0;
+    uint32_t inflater_blocks = 0;
+    uint8_t *h_comp = nullptr, *d_comp = nullptr;
+    size_t h_comp_cap = 0, d_comp_cap = 0;
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
@@ -1068,6 +1076,7 @@ static void aln_table_free(kaamer_index *ix)
 }
 
 #include "parse_text.hip.inc"
+#include "inflate.hip.inc"
 
 extern "C" {
 

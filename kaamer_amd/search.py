@@ -224,7 +224,7 @@ class _ConsumerGone(Exception):
     """SearchFile's generator was closed before the file ended"""
 
 
-def SearchFile(handle, path, options=None, fmt=None, device_parse=False):
+def SearchFile(handle, path, options=None, fmt=None, device_parse=False, device_inflate=False):
     """FastqSearch / ProteinSearch / NucleotideSearch (search_fastq.go:60-136, search_protein.go:40-118,
     search_nucleotide.go:27-160) over a FILE of any size (gzip included) on an api.Replicas set or an api.ShardedIndex: a
     generator of QueryResult dicts in file order, shaped as the text drivers above shape theirs (options.SequenceType
@@ -234,10 +234,14 @@ def SearchFile(handle, path, options=None, fmt=None, device_parse=False):
     bitmaps.  Align with a table attached to the handle: HitEntries and every hit's Alignment, hits in BitScore order.
     device_parse=True (FASTQ on an api.Replicas set, no ExtractPositions, no Align; anything else: ValueError): the file's
     text is parsed on the device (kaamer_search_text_file, options.ChunkTextBytes of text per chunk) and the names are
-    sliced out of each chunk's text by span; the same dicts come out."""
+    sliced out of each chunk's text by span; the same dicts come out.  device_inflate=True (with device_parse only: else
+    ValueError): a BGZF file is also inflated on the device (kaamer_search_text_file_opts); whatever else a gzip file holds
+    falls back to the host inflater, the results are the same."""
     o = options or SearchOptions(SequenceType=abi.READS)
     seq_type = o.SequenceType
     fmt = fmt or ("fastq" if seq_type == abi.READS else "fasta")
+    if device_inflate and not device_parse:
+        raise ValueError("SearchFile(device_inflate=True) needs device_parse=True: the device inflates into the device reader's text buffer")
     if device_parse:
         why = None
         if fmt != "fastq":
@@ -281,7 +285,7 @@ def SearchFile(handle, path, options=None, fmt=None, device_parse=False):
                 handle.search_text_file(path, fmt, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio,
                                         min_k_match=o.MinKMatch, max_results=o.MaxResults,
                                         chunk_text_bytes=int(getattr(o, "ChunkTextBytes", 1 << 28)), in_flight=int(getattr(o, "InFlight", 0)),
-                                        on_chunk=on_text_chunk)
+                                        on_chunk=on_text_chunk, **({"device_inflate": True} if device_inflate else {}))
                 put(done)
                 return
             handle.search_file(path, fmt, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
