@@ -799,7 +799,7 @@ __global__ __launch_bounds__(64 * G_WAVES, G_MIN_BLOCKS) void count_global_kerne
         }
         __syncthreads();
         if (s.last) {
-            finalize_body<true>(p.counters, p.fin_out, p.fin_small, p.fin_status_out, p.fin_cursors, p.fin_slot_scale, p.fin_scale_cap, p.fin_scale_margin);
+            finalize_body<true>(p.counters, p.fin_out, p.fin_small, p.fin_status_out, p.fin_g_items, p.fin_cursors, p.fin_slot_scale, p.fin_scale_cap, p.fin_scale_margin);
         }
     }
 }

@@ -500,6 +500,7 @@ struct CountParams {
     // set when count_global_kernel is the last kernel of the batch: its last workgroup finalizes
     kaamer_counters *fin_out;
     uint32_t *fin_small, *fin_status_out;
+    uint32_t *fin_g_items;      // entries of LIST_G of this batch, kept for the host (g_tier_grid)
     unsigned long long *fin_cursors;
     uint32_t *fin_slot_scale;   // table capacity scale for the next batch (count_group.hip.inc: table_slots_for)
     uint32_t fin_scale_cap, fin_scale_margin;
@@ -575,10 +576,12 @@ __device__ __forceinline__ void mark_invalid_range(unsigned long long *invalid, 
 // with device-scope atomics (performed at the memory side), so device-scope atomic loads see
 // it without an agent-scope fence -- which on this part writes back the whole L2 (a fence per
 // workgroup made the kernel 30x slower).
+// g_items_out: a search leaves the entry count of LIST_G there before it is zeroed (kaamer_workspace_finish reads it
+// with the status: g_tier_grid); a merge passes nullptr and leaves the word alone.
 template <bool IN_FLIGHT>
 __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaamer_counters *out, uint32_t *small_state,
-                                              uint32_t *status_out, unsigned long long *cursors, uint32_t *slot_scale = nullptr,
-                                              uint32_t scale_cap = 16u, uint32_t margin_q4 = 30u)
+                                              uint32_t *status_out, uint32_t *g_items_out, unsigned long long *cursors,
+                                              uint32_t *slot_scale = nullptr, uint32_t scale_cap = 16u, uint32_t margin_q4 = 30u)
 {
     // 256 threads: lane <-> replica, wave w sums counters w, w+4, ...
     static_assert(CTR_REPLICAS == 64, "one replica per lane");
@@ -594,6 +597,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
     unsigned long long g_hits = 0, g_mon_hits = 0, g_monsters = 0;
     if (threadIdx.x == 0) {
         *status_out = IN_FLIGHT ? __hip_atomic_load(&small_state[SLOT_STATUS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : small_state[SLOT_STATUS];
+        if (g_items_out) *g_items_out = IN_FLIGHT ? __hip_atomic_load(&small_state[LIST_G], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : small_state[LIST_G];
         g_hits = 16ull * (IN_FLIGHT ? __hip_atomic_load(&small_state[SLOT_G_HITS16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : small_state[SLOT_G_HITS16]);
         g_mon_hits = 16ull * (IN_FLIGHT ? __hip_atomic_load(&small_state[SLOT_G_MON_HITS16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : small_state[SLOT_G_MON_HITS16]);
         g_monsters = IN_FLIGHT ? __hip_atomic_load(&small_state[SLOT_G_MONSTERS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : small_state[SLOT_G_MONSTERS];
@@ -777,9 +781,10 @@ __global__ __launch_bounds__(256) void gather_hits_kernel(const uint32_t *d_nq, 
 }
 
 __global__ void finalize_kernel(unsigned long long *replicas, kaamer_counters *out, uint32_t *small_state,
-                                uint32_t *status_out, unsigned long long *cursors, uint32_t *slot_scale, uint32_t scale_cap, uint32_t margin_q4)
+                                uint32_t *status_out, uint32_t *g_items_out, unsigned long long *cursors, uint32_t *slot_scale,
+                                uint32_t scale_cap, uint32_t margin_q4)
 {
-    finalize_body<false>(replicas, out, small_state, status_out, cursors, slot_scale, scale_cap, margin_q4);
+    finalize_body<false>(replicas, out, small_state, status_out, g_items_out, cursors, slot_scale, scale_cap, margin_q4);
 }
 
 // ------------------------------------------------------------------------------------
@@ -893,7 +898,9 @@ struct kaamer_workspace {
     unsigned long long *d_tr_chain;     // translate_reads_kernel: three words per 64-sequence chunk, tagged with tr_epoch
     uint32_t tr_epoch;
     uint32_t *d_list_counts;            // [N_LISTS] + queue head + status (zeroed by finalize)
-    uint32_t *d_status_out;             // status of the last finished batch
+    uint32_t *d_status_out;             // status of the last finished batch; the word after it: its LIST_G entries (a search's)
+    int64_t g_last;                     // LIST_G entries of the last batch kaamer_workspace_finish looked at, or G_LAST_UNKNOWN
+    int g_floor;                        // workgroups of a G-tier launch behind a batch that had none (g_tier_grid)
     bool clean;                         // per-batch device state is known to be zeroed
     bool firstpos;                      // track the lowest matching position per hit
     bool want_positions;                // full PositionHits bitmaps
@@ -913,6 +920,7 @@ struct kaamer_workspace {
     uint32_t n_timed, time_every, call_no;
 };
 #define EV_PER_CALL 5
+#define G_LAST_UNKNOWN (-1)
 
 template <class T> static int dev_alloc(T **p, size_t n)
 {
@@ -959,6 +967,7 @@ static void scan_u32_on(kaamer_workspace *ws, const uint32_t *cnt, const uint32_
 static int ws_reset_if_dirty(kaamer_workspace *ws, hipStream_t s)
 {
     if (ws->clean) return KAAMER_OK;
+    ws->g_last = G_LAST_UNKNOWN;   // (whatever ran last did not end as a batch does: it says nothing about the next one)
     HIPCHK(hipMemsetAsync(ws->d_pool_cursor, 0, (size_t)3 * CURSOR_STRIDE * sizeof(unsigned long long), s));
     HIPCHK(hipMemsetAsync(ws->d_list_counts, 0, N_SMALL_SLOTS * sizeof(uint32_t), s));
     HIPCHK(hipMemsetAsync(ws->d_counter_replicas, 0, sizeof(unsigned long long) * CTR_REPLICAS * CTR_N, s));
@@ -1005,10 +1014,21 @@ static int group_grid(const kaamer_workspace *ws, uint64_t nq, uint64_t items)
     return (int)(g > (uint64_t)ws->grp_grid ? (uint64_t)ws->grp_grid : g);
 }
 
-// workgroups of a G-tier launch: never more than queries
-static int g_tier_grid(const kaamer_workspace *ws, uint32_t nq_bound)
+// workgroups of a G-tier launch: never more than queries.
+// hinted (the G-tier launches of a search): behind a finished batch that sent nothing to the G tier the launch is cut to
+// g_floor workgroups (KAAMER_G_FLOOR, shipped: 1).  The kernels are exact at any grid (items go out by ticket, the
+// completion count is over the workgroups that take part); every workgroup of the grid has to be PLACED, 80 KB of LDS
+// and 8 waves each, and next to the neighbouring batches' kernels the last of them is placed late: with three protein
+// batches in flight on DB-SP the empty launch lasts 55-58 us at the full grid and at floors of 16, 32 and 64, 49.5 us at
+// 1 (6 us alone; the one workgroup still waits for its 80 KB), and the batch takes 0.1287 instead of 0.1309 ms
+// (profiles/r17_gtier_grid.md).  The price is a batch that overflows after a clean one: the floor's workgroups count
+// its items alone.  A --db zipf-mid batch (10 000 queries, 7 items) behind a clean one: 0.756 ms at floor 1 against
+// 0.605 ms at the full grid, once -- the batch after it is sized from a count above zero.
+static int g_tier_grid(const kaamer_workspace *ws, uint32_t nq_bound, bool hinted = false)
 {
-    return (uint32_t)ws->g_grid > nq_bound ? (nq_bound > 0 ? (int)nq_bound : 1) : ws->g_grid;
+    int g = ws->g_grid;
+    if (hinted && ws->g_last == 0 && ws->g_floor < g) g = ws->g_floor;
+    return (uint32_t)g > nq_bound ? (nq_bound > 0 ? (int)nq_bound : 1) : g;
 }
 
 // epochs of the chained-tile kernels: 24 bits, never 0
@@ -1030,6 +1050,7 @@ struct SearchKnobs {
     bool pack_long;                         // ORF batches always take the pack kernel's larger arena
     bool ws_trace;                          // a workspace prints its sizes when it is created
     int host_slots;                         // calls in flight through the host-buffer boundary
+    int g_floor;                            // G-tier workgroups behind a batch without G-tier items (0: the shipped 1)
 };
 
 static SearchKnobs read_knobs()
@@ -1053,6 +1074,8 @@ static SearchKnobs read_knobs()
     k.ws_trace = getenv("KAAMER_WS_TRACE") != nullptr;
     const int hs = num("KAAMER_HOST_SLOTS");
     k.host_slots = hs >= 1 && hs <= KAAMER_MAX_HOST_SLOTS ? hs : 4;
+    const int gf = num("KAAMER_G_FLOOR");
+    k.g_floor = gf >= 1 ? gf : 0;
     return k;
 }
 
@@ -1292,6 +1315,9 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
         int g_per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&g_per_cu, count_global_kernel, 64 * G_WAVES, 0) != hipSuccess || g_per_cu < 1) g_per_cu = 1;
         ws->g_grid = ws->n_cu * (g_per_cu > 2 ? 2 : g_per_cu);
+        ws->g_floor = knobs.g_floor ? knobs.g_floor : 1;
+        if (ws->g_floor > ws->g_grid) ws->g_floor = ws->g_grid;
+        ws->g_last = G_LAST_UNKNOWN;
     }
     ws->p_grid = ws->n_cu * p_per_cu;
     {
@@ -1357,7 +1383,8 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     if (!rc) rc = dev_alloc(&ws->d_pool_cursor, (size_t)3 * CURSOR_STRIDE);
     if (!rc) rc = dev_alloc(&ws->d_lists, (size_t)N_LISTS * ws->q_cap);
     if (!rc) rc = dev_alloc(&ws->d_list_counts, N_SMALL_SLOTS);
-    if (!rc) rc = dev_alloc(&ws->d_status_out, 1);
+    if (!rc) rc = dev_alloc(&ws->d_status_out, 2);
+    if (!rc && hipMemset(ws->d_status_out, 0, 2 * sizeof(uint32_t)) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset");
     if (!rc) rc = dev_alloc(&ws->d_qinfo, ws->q_cap);
     if (!rc) rc = dev_alloc(&ws->d_slots, ws->q_cap);
     if (!rc) rc = dev_alloc(&ws->d_slot_off, (size_t)ws->q_cap + 1);
@@ -1672,10 +1699,10 @@ static void enqueue_count(const kaamer_index *ix, kaamer_workspace *ws, bool nuc
     pg.list = ws_list(ws, LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
     if (fused_finalize(ws)) {
         pg.fin_out = ws->d_counters; pg.fin_small = ws->d_list_counts; pg.fin_status_out = ws->d_status_out;
-        pg.fin_cursors = ws->d_pool_cursor;
+        pg.fin_g_items = ws->d_status_out + 1; pg.fin_cursors = ws->d_pool_cursor;
         pg.fin_slot_scale = ws->d_slot_scale; pg.fin_scale_cap = ws->slot_scale_cap; pg.fin_scale_margin = ws->slot_scale_margin;
     }
-    hipLaunchKernelGGL(count_global_kernel, dim3(g_tier_grid(ws, nq_bound)), dim3(64 * G_WAVES), 0, s, pg);
+    hipLaunchKernelGGL(count_global_kernel, dim3(g_tier_grid(ws, nq_bound, true)), dim3(64 * G_WAVES), 0, s, pg);
     if (ws->compact) launch_compaction(ws, nq_bound, p.status, s);
 }
 
@@ -1700,7 +1727,7 @@ static void enqueue_positions(const kaamer_index *ix, kaamer_workspace *ws, uint
     pg2.pos_base = ws->d_pos_base;
     pg2.pos_bits = ws->d_pos_bits;
     pg2.g_cursor = ws->d_pool_cursor + 2 * CURSOR_STRIDE;
-    hipLaunchKernelGGL(positions_global_kernel, dim3(g_tier_grid(ws, nq_bound)), dim3(64 * G_WAVES), 0, s, pg2);
+    hipLaunchKernelGGL(positions_global_kernel, dim3(g_tier_grid(ws, nq_bound, true)), dim3(64 * G_WAVES), 0, s, pg2);
 }
 
 int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *d_seqs, const uint64_t *d_offsets,
@@ -1765,7 +1792,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     if (ws->want_positions) enqueue_positions(ix, ws, qin.nq_bound, qin.pos_bound, s);
     if (!fused_finalize(ws))
         hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, ws->d_counter_replicas, ws->d_counters, ws->d_list_counts,
-                           ws->d_status_out, ws->d_pool_cursor, ws->d_slot_scale, ws->slot_scale_cap, ws->slot_scale_margin);
+                           ws->d_status_out, ws->d_status_out + 1, ws->d_pool_cursor, ws->d_slot_scale, ws->slot_scale_cap, ws->slot_scale_margin);
     if (timed) HIPCHK(hipEventRecord(ev[4], s));
     HIPCHK(hipGetLastError());
     if (split) {
@@ -1839,7 +1866,8 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
         hipLaunchKernelGGL(x_or_bits_kernel, dim3(gb ? gb : 1), dim3(64), 0, s, *xpos);
     }
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, ws->d_counter_replicas, ws->d_counters, ws->d_list_counts,
-                       ws->d_status_out, ws->d_pool_cursor, (uint32_t *)nullptr, 16u, 16u);   // (a merge looks nothing up: the scale stays)
+                       ws->d_status_out, (uint32_t *)nullptr, ws->d_pool_cursor, (uint32_t *)nullptr, 16u, 16u);   // (a merge looks nothing up: the scale
+                                                                                                                  // stays, and so does the last search's G-tier count)
     HIPCHK(hipGetLastError());
     ws->clean = true;
     ws->last_was_merge = true;
@@ -2420,13 +2448,17 @@ int kaamer_workspace_finish(kaamer_workspace *ws, void *stream, kaamer_counters 
     HIPCHK(hipSetDevice(ws->device));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (ws->split_pending) HIPCHK(hipEventSynchronize(ws->ev_count));   // (the counting stage ran on the count stream)
-    uint32_t status = 0;
-    HIPCHK(hipMemcpy(&status, ws->d_status_out, sizeof status, hipMemcpyDeviceToHost));
+    uint32_t st_g[2] = { 0, 0 };   // status, LIST_G entries of the last search
+    HIPCHK(hipMemcpy(st_g, ws->d_status_out, sizeof st_g, hipMemcpyDeviceToHost));
+    const uint32_t status = st_g[0];
     kaamer_counters c;
     HIPCHK(hipMemcpy(&c, ws->d_counters, sizeof c, hipMemcpyDeviceToHost));
     if (out) *out = c;
-    if (!ws->last_was_merge) ws_note_density(ws, c);
-    if (status) ws->clean = false;  // an aborted batch may leave per-batch state behind
+    if (!ws->last_was_merge) {
+        ws_note_density(ws, c);
+        ws->g_last = st_g[1];   // sizes the next search's G-tier launches (g_tier_grid)
+    }
+    if (status) { ws->clean = false; ws->g_last = G_LAST_UNKNOWN; }  // an aborted batch may leave per-batch state behind
     if (status & ST_POOL_FULL) return kaamer_fail(KAAMER_E_CAPACITY, "hit pool exhausted: raise workspace max_hits (now %llu)", (unsigned long long)ws->hit_cap);
     if (status & ST_LIST_FULL) return kaamer_fail(KAAMER_E_CAPACITY, "tier work list exhausted");
     if (status & ST_CHAIN_TIMEOUT) return kaamer_fail(KAAMER_E_HIP, "table layout: a tile never published its total");
