@@ -1165,8 +1165,8 @@ void kaamer_reader_close(kaamer_reader *rd);
 /* ------------------------------------------------------------------------- */
 /* FASTQ text parsed on the device — GetQueriesFastq (search.go:324-412) as a  */
 /* data-parallel job: raw text in, the reported hits out.  The host readers    */
-/* above remain the route for FASTA, strict_scanner, -pos / -aln and the       */
-/* sharded handle.                                                             */
+/* above remain the route for strict_scanner, -pos / -aln and the sharded      */
+/* handle.  FASTA text has calls of its own: the last section of this file.    */
 /* ------------------------------------------------------------------------- */
 /* The reader's rules, per line (search.go:370-410; the kernels in parse_text.hip.inc compute exactly this):
  *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped (bufio.ScanLines)
@@ -1180,10 +1180,13 @@ void kaamer_reader_close(kaamer_reader *rd);
  *            only (search.go:399): host bookkeeping, not part of the parse.
  *   chunks   a text may be cut at any p with text[p-1] == '\n' and text[p] == '@': the pieces, parsed independently, give
  *            the records of the whole text in order (kaamer_text_cut_fastq).
- * Out of scope here: FASTA on the device (it needs the concatenation of TrimSpace'd lines and "upper-case every record but
- * the last", and protein files are small), strict_scanner, -pos / -aln on the text forms, the sharded handle, a reader
- * thread.  (Inflating on the device: the BGZF section below.) */
+ * Out of scope here: strict_scanner, -pos / -aln on the text forms, the sharded handle, a reader thread.  (Inflating on
+ * the device: the BGZF section below.  FASTA on the device: the section after it, with entry points of its own -- the
+ * calls of this section keep refusing format 0.) */
 typedef struct kaamer_text_parser kaamer_text_parser;
+/* name and sequence of one record as ranges of the text.  FASTQ: text[seq_off, seq_off + seq_len) IS the sequence.  FASTA:
+ * seq_off is the record's first kept byte and seq_len reaches to one past its last kept byte, so the range covers the line
+ * breaks and trimmed bytes in between (and no header line): the packed length is offsets[i + 1] - offsets[i], not seq_len. */
 typedef struct { uint32_t name_off, name_len, seq_off, seq_len; } kaamer_text_span;   /* into the text */
 typedef struct {
     uint32_t n_records;
@@ -1216,7 +1219,8 @@ void kaamer_text_parser_geometry(uint32_t out[4]);
  * packed batch -- wait, the repeat of a batch beyond a bound (from the parsed buffers: the text is not parsed again),
  * discard and the packed block are those of kaamer_ticket.  The submit call waits once for the two counts of the parse
  * (records, sequence bytes: one small copy): kaamer_search_device takes n_seqs from the host, so this cannot be avoided.
- * format: 1 (FASTQ); 0 (FASTA) is KAAMER_E_ARG -- use the host reader (kaamer_parse_fasta + kaamer_search_batch_top_flat).
+ * format: 1 (FASTQ); 0 (FASTA) is KAAMER_E_ARG -- use kaamer_submit_fasta_top_flat, or the host reader (kaamer_parse_fasta +
+ * kaamer_search_batch_top_flat).
  * seq_type: base KAAMER_READS or KAAMER_NUCLEOTIDE (NucleotideSearch takes FASTQ too, search_nucleotide.go:38-39), the
  * genetic code in bits 8-15 as on every call; KAAMER_PROTEIN is KAAMER_E_ARG.  Text that starts with the gzip signature is
  * KAAMER_E_ARG: kaamer_search_text_file inflates (zlib, on the host), and whole BGZF blocks have a call of their own
@@ -1254,8 +1258,8 @@ int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, in
 /* text each, every member's compressed size in its header and its inflated   */
 /* size and CRC-32 in its trailer: the host finds the blocks without          */
 /* inflating, every block is inflated by a wave of its own (inflate.hip.inc). */
-/* Ordinary single-member gzip, FASTA, -pos / -aln and the sharded handle     */
-/* stay with the host readers above.                                          */
+/* Ordinary single-member gzip, BGZF-compressed FASTA, -pos / -aln and the    */
+/* sharded handle stay with the host readers above.                           */
 /* ------------------------------------------------------------------------- */
 /* One block: the deflate payload is bytes[comp_off, comp_off + comp_len) -- what lies between the member's header and
  * its 8-byte trailer -- and inflates to isize bytes (at most 65536) with CRC-32 crc. */
@@ -1333,6 +1337,64 @@ int kaamer_batch_top_text(const kaamer_batch_top *out, const char **text, uint64
 int kaamer_search_text_file_opts(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio,
                                  int64_t min_k_match, uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight,
                                  int32_t device_inflate, kaamer_text_chunk_cb cb, void *user, kaamer_counters *total);
+
+/* ------------------------------------------------------------------------- */
+/* FASTA text parsed on the device — GetQueriesFasta (search.go:222-322), the  */
+/* reader of ProteinSearch and, for requests that are not FASTQ, of            */
+/* NucleotideSearch and FastqSearch (search_nucleotide.go, search_fastq.go).   */
+/* The FASTQ calls above keep refusing format 0: FASTA has these entry points. */
+/* ------------------------------------------------------------------------- */
+/* The reader's rules (the host's statement: kaamer_parse_fasta; the kernels in parse_fasta.hip.inc compute exactly this):
+ *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped (bufio.ScanLines)
+ *   trim     leading and trailing bytes out of ' ' \t \n \v \f \r are removed from a non-header line (search.go:309; ASCII
+ *            only: 0x85, 0xA0, 0x1C-0x1F, 0x00 and every byte >= 0x80 are ordinary bytes).  Interior whitespace is kept.
+ *   class    H: non-empty after the '\r' drop and the first byte is '>' -- tested before any trim, so " >x" is a sequence
+ *            line that contributes ">x".  S: any other line with a byte left after the trim.  X: empty and whitespace-only
+ *            lines (search.go:285-287).
+ *   records  X lines are ignored.  A record is a maximal run of S lines with no H line between them; its sequence is the
+ *            concatenation of their trimmed bytes.  Its name is what follows the '>' of the nearest preceding H line, the
+ *            '\r' dropped and nothing else trimmed; empty when no H precedes (the first record only).  Headers with no S
+ *            line before the next header produce nothing.
+ *   case     every record but the LAST of the input has a-z mapped to A-Z (search.go:295 against :313-320); the last is
+ *            copied as it is -- precisely: the record still pending at the end of the input.  A last record with a header
+ *            line behind it (">a\nacgt\n>b\n") was closed by that header and is upper-cased like the others, on the host
+ *            reader and here.  upper_last = 1: more input follows this text, the pending record is upper-cased too.
+ *   size     SizeInKmer (len - 6, minus 1 when the last byte is '*') is derived from the packed bytes by the search
+ *            kernels; the parser does not produce it.
+ *   spans    name_off / name_len as for FASTQ; seq_off / seq_len: see kaamer_text_span (the range spans line breaks).
+ *   chunks   kaamer_text_cut_fasta.
+ * Out of scope here: BGZF-compressed FASTA, -pos / -aln on the text forms, the sharded handle, strict_scanner. */
+/* kaamer_text_parser_create with a line bound of the caller's: max_lines below the FASTQ rule (max_text_bytes / 16 +
+ * 4 max_records + 1024) is raised to it.  FASTA at narrow line widths has more lines than that rule allows. */
+int kaamer_text_parser_create_lines(int device, uint64_t max_text_bytes, uint32_t max_records, uint64_t max_lines,
+                                    kaamer_text_parser **out);
+/* kaamer_parse_fastq_device for FASTA: the same parser object, kaamer_text_parser_finish and kaamer_text_parse_result,
+ * the same demands on d_text.  The per-line words only FASTA needs are allocated at the parser's first FASTA text. */
+int kaamer_parse_fasta_device(kaamer_text_parser *p, const uint8_t *d_text, uint64_t n_bytes, int32_t upper_last, void *stream);
+/* CPU only.  The greatest p in [1, len) with text[p-1] == '\n', text[p] == '>' and at least one S line, complete or not, in
+ * [p, len) (a partial last line counts when its first byte is not '>' and it holds a non-space byte); 0: none.  The S
+ * line guarantees that a record follows the cut: every piece in front of a cut is parsed with upper_last = 1, the piece
+ * at the end of the input with 0, and the pieces' records are the records of the whole. */
+uint64_t kaamer_text_cut_fasta(const char *text, uint64_t len);
+/* kaamer_submit_text_top_flat / kaamer_search_text_top_flat for FASTA text (search_protein.go:38-120, search_nucleotide.go,
+ * search_fastq.go with GetQueriesFasta inside): the same slot, ticket, wait, repeat beyond a bound (from the parsed
+ * buffers), discard and kaamer_batch_top_text_spans.  seq_type: base KAAMER_PROTEIN, KAAMER_NUCLEOTIDE or KAAMER_READS, the
+ * genetic code in bits 8-15.  Text that starts with the gzip signature is KAAMER_E_ARG; so is text above 2^32 - 1 bytes
+ * (cut it: kaamer_text_cut_fasta).  `text` is borrowed for the call (one pointer: cgo-safe).
+ * Against kaamer_parse_fasta + kaamer_search_batch_top_flat on the same text, one caller (profiles/r17_fasta_parse.md): 4.3x
+ * for 10 000 protein queries (3.7 MB of text: 0.76 against 3.23 ms), 8.5x for 1 M two-line reads, 7.7x for 300 MB of contigs;
+ * with four callers 3.7x to 4.0x.  No measured input is slower on the text route. */
+int kaamer_submit_fasta_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                 double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_ticket **ticket);
+int kaamer_search_fasta_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                 double min_k_ratio, int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out);
+/* ProteinSearch / NucleotideSearch / FastqSearch over a FASTA FILE: kaamer_search_text_file's byte source (plain or gzip,
+ * with its rules), chunk loop and callback, the chunks cut at kaamer_text_cut_fasta; every chunk but the file's last is
+ * parsed with upper_last = 1.  A chunk without a cut goes on reading up to 4 chunk_text_bytes; beyond that:
+ * KAAMER_E_CAPACITY (use kaamer_search_file).  An empty file, or a first header that is no gzip header: no chunk, no error. */
+int kaamer_search_fasta_file(kaamer_replicas *r, const char *path, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                             uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb,
+                             void *user, kaamer_counters *total);
 
 #ifdef __cplusplus
 }

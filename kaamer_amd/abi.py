@@ -434,6 +434,18 @@ SYMBOLS = {
     # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, device_inflate, cb, user, total)
     "kaamer_search_text_file_opts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    # FASTA text parsed on the device: the parse, the cut rule, the host-buffer calls, the whole-file driver
+    "kaamer_text_parser_create_lines": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "kaamer_parse_fasta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]),
+    "kaamer_text_cut_fasta": (C.c_uint64, [C.c_char_p, C.c_uint64]),
+    # (handle, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, out)
+    "kaamer_submit_fasta_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                               C.POINTER(C.c_void_p)]),
+    "kaamer_search_fasta_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                               C.c_void_p]),
+    # (handle, path, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total)
+    "kaamer_search_fasta_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 }
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range

@@ -592,6 +592,28 @@ class Index:
                                                         min_k_match, max_results, C.byref(t)))
         return TopTicket(t)
 
+    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10):
+        """kaamer_search_fasta_top_flat: FASTA text (bytes) in, the reported hits out -- the text is parsed on the device
+        (GetQueriesFasta) and searched as search_top searches the packed batch.  seq_type: PROTEIN, NUCLEOTIDE or READS
+        (with a genetic code).  upper_last: more input follows this text, its last record is upper-cased too.
+        TopResult.text_spans: name and sequence range of every record as offsets into `text`."""
+        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        out = C.POINTER(abi.BatchTop)()
+        abi.check(abi.lib().kaamer_search_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
+                                                         min_k_match, max_results, C.byref(out)))
+        try:
+            return TopResult(out)
+        finally:
+            abi.lib().kaamer_batch_top_free(out)
+
+    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10):
+        """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans)"""
+        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+        t = C.c_void_p()
+        abi.check(abi.lib().kaamer_submit_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
+                                                         min_k_match, max_results, C.byref(t)))
+        return TopTicket(t)
+
     def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
         """kaamer_stream_open[_pos|_aln]_flat; align: as search_top's (needs attach_proteins)"""
         return TopStream(self, seq_type, min_k_ratio, min_k_match, max_results, want_positions, align)
@@ -847,13 +869,10 @@ class Replicas:
 
     TEXT_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(abi.BatchTop))
 
-    def search_text_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
-                         chunk_text_bytes=1 << 28, in_flight=0, on_chunk=None, device_inflate=False):
-        """kaamer_search_text_file: the file's FASTQ text (plain or gzip) is cut into chunks of about chunk_text_bytes, each
-        parsed and searched on a replica.  on_chunk(first_seq, text bytes, TopResult) per chunk, in input order; the
-        TopResult's text_spans index `text`, its rep_query counts from the chunk's first record.  -> summed counters
-        device_inflate (kaamer_search_text_file_opts): a BGZF file is inflated on the device, block by block; anything else
-        in a gzip file falls back to the host inflater from that chunk on.  The concatenated texts are the same."""
+    @staticmethod
+    def _text_chunk_cb(on_chunk):
+        """the kaamer_text_chunk_cb of the text file drivers around on_chunk(first_seq, text bytes, TopResult) -> (the C
+        callback, the list that receives an exception of on_chunk)"""
         err = []
 
         def cb(user, first, text, length, spans, n_records, top):
@@ -864,13 +883,36 @@ class Replicas:
             except BaseException as e:  # noqa: BLE001  (must not propagate through the C frames)
                 err.append(e)
                 return 1
+        return Replicas.TEXT_CHUNK_CB(cb), err
+
+    def search_text_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
+                         chunk_text_bytes=1 << 28, in_flight=0, on_chunk=None, device_inflate=False):
+        """kaamer_search_text_file: the file's FASTQ text (plain or gzip) is cut into chunks of about chunk_text_bytes, each
+        parsed and searched on a replica.  on_chunk(first_seq, text bytes, TopResult) per chunk, in input order; the
+        TopResult's text_spans index `text`, its rep_query counts from the chunk's first record.  -> summed counters
+        device_inflate (kaamer_search_text_file_opts): a BGZF file is inflated on the device, block by block; anything else
+        in a gzip file falls back to the host inflater from that chunk on.  The concatenated texts are the same."""
         c = abi.Counters()
-        cfn = Replicas.TEXT_CHUNK_CB(cb)
+        cfn, err = Replicas._text_chunk_cb(on_chunk)
         args = (self._h, str(path).encode(), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio, min_k_match, max_results, int(chunk_text_bytes), in_flight)
         if device_inflate:
             rc = abi.lib().kaamer_search_text_file_opts(*args, 1, C.cast(cfn, C.c_void_p), None, C.byref(c))
         else:
             rc = abi.lib().kaamer_search_text_file(*args, C.cast(cfn, C.c_void_p), None, C.byref(c))
+        if err:
+            raise err[0]
+        abi.check(rc)
+        return c.as_dict()
+
+    def search_fasta_file(self, path, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, chunk_text_bytes=1 << 28,
+                          in_flight=0, on_chunk=None):
+        """kaamer_search_fasta_file: the file's FASTA text (plain or gzip) is cut into chunks of about chunk_text_bytes at
+        kaamer_text_cut_fasta, each parsed and searched on a replica (every chunk but the last with upper_last).
+        on_chunk(first_seq, text bytes, TopResult) per chunk, in input order, as search_text_file's.  -> summed counters"""
+        c = abi.Counters()
+        cfn, err = Replicas._text_chunk_cb(on_chunk)
+        rc = abi.lib().kaamer_search_fasta_file(self._h, str(path).encode(), seq_type, min_k_ratio, min_k_match, max_results,
+                                                int(chunk_text_bytes), in_flight, C.cast(cfn, C.c_void_p), None, C.byref(c))
         if err:
             raise err[0]
         abi.check(rc)
@@ -1264,6 +1306,13 @@ def text_cut_fastq(text):
     return int(abi.lib().kaamer_text_cut_fastq(data, len(data)))
 
 
+def text_cut_fasta(text):
+    """kaamer_text_cut_fasta: the greatest p in [1, len) with text[p-1] == '\\n', text[p] == '>' and a sequence line (complete
+    or not) in text[p:]; 0: none"""
+    data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    return int(abi.lib().kaamer_text_cut_fasta(data, len(data)))
+
+
 def _hip_runtime():
     """the HIP runtime torch loaded (device copies of the tools below)"""
     import torch
@@ -1273,33 +1322,44 @@ def _hip_runtime():
 
 
 class TextParser:
-    """kaamer_text_parser_*: GetQueriesFastq on the device, for texts of up to max_text_bytes with up to max_records
-    records (None: as many as such a text can hold)"""
+    """kaamer_text_parser_*: GetQueriesFastq / GetQueriesFasta on the device, for texts of up to max_text_bytes with up to
+    max_records records (None: as many as such a text can hold) and max_lines lines (None: the FASTQ rule,
+    max_text_bytes / 16 + 4 max_records + 1024; kaamer_text_parser_create_lines otherwise)"""
 
-    def __init__(self, max_text_bytes, max_records=None, device=0):
+    def __init__(self, max_text_bytes, max_records=None, device=0, max_lines=None):
         self.device = device
         self.max_text_bytes = int(max_text_bytes)
         if max_records is None:
             max_records = self.max_text_bytes // 2 + 1
         h = C.c_void_p()
-        abi.check(abi.lib().kaamer_text_parser_create(device, self.max_text_bytes, int(max_records), C.byref(h)))
+        if max_lines is None:
+            abi.check(abi.lib().kaamer_text_parser_create(device, self.max_text_bytes, int(max_records), C.byref(h)))
+        else:
+            abi.check(abi.lib().kaamer_text_parser_create_lines(device, self.max_text_bytes, int(max_records), int(max_lines), C.byref(h)))
         self._h = h
 
-    def parse_device(self, d_text_ptr, n_bytes, stream=0):
-        """kaamer_parse_fastq_device + kaamer_text_parser_finish on a device buffer -> abi.TextParseResult"""
-        abi.check(abi.lib().kaamer_parse_fastq_device(self._h, d_text_ptr, n_bytes, stream))
+    def parse_device(self, d_text_ptr, n_bytes, stream=0, fmt="fastq", upper_last=False):
+        """kaamer_parse_fastq_device (fmt "fasta": kaamer_parse_fasta_device) + kaamer_text_parser_finish on a device
+        buffer -> abi.TextParseResult"""
+        if fmt == "fasta":
+            abi.check(abi.lib().kaamer_parse_fasta_device(self._h, d_text_ptr, n_bytes, int(bool(upper_last)), stream))
+        elif fmt == "fastq":
+            abi.check(abi.lib().kaamer_parse_fastq_device(self._h, d_text_ptr, n_bytes, stream))
+        else:
+            raise ValueError("fmt is 'fastq' or 'fasta'")
         r = abi.TextParseResult()
         abi.check(abi.lib().kaamer_text_parser_finish(self._h, stream, C.byref(r)))
         return r
 
-    def parse(self, text):
-        """text (bytes) -> dict(seqs u8, offsets u64, spans (SPAN_DTYPE), n_lines): uploaded, parsed, copied back"""
+    def parse(self, text, fmt="fastq", upper_last=False):
+        """text (bytes) -> dict(seqs u8, offsets u64, spans (SPAN_DTYPE), n_lines): uploaded, parsed, copied back.
+        fmt "fasta": GetQueriesFasta; upper_last: more input follows the text, its last record is upper-cased too"""
         import torch
         data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
         with torch.cuda.device(self.device):
             d = torch.frombuffer(bytearray(data) if data else bytearray(1), dtype=torch.uint8).cuda()
             torch.cuda.synchronize()
-            r = self.parse_device(d.data_ptr(), len(data))
+            r = self.parse_device(d.data_ptr(), len(data), fmt=fmt, upper_last=upper_last)
             hip = _hip_runtime()
             n = int(r.n_records)
             offs = np.empty(n + 1, np.uint64)
@@ -1330,6 +1390,17 @@ def parse_fastq_device(text, device=0):
     p = TextParser(len(data), device=device)
     try:
         return p.parse(data)
+    finally:
+        p.close()
+
+
+def parse_fasta_device(text, upper_last=False, device=0):
+    """GetQueriesFasta on the device (tests and tools) -> dict(seqs, offsets, spans, n_lines) as numpy arrays.  A record's
+    span covers text[seq_off : seq_off + seq_len] from its first to its last kept byte, line breaks included"""
+    data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    p = TextParser(len(data), device=device)
+    try:
+        return p.parse(data, fmt="fasta", upper_last=upper_last)
     finally:
         p.close()
 

@@ -248,6 +248,30 @@ uint64_t kaamer_text_cut_fastq(const char *text, uint64_t len)
     return 0;
 }
 
+// Where a FASTA text may be cut (the rules: include/kaamer_hip.h): before a '>' that opens a line, provided an S line --
+// a line that does not start with '>' and holds a non-space byte, complete or not -- lies behind it.  The H closes the
+// record pending before it and names what follows, and the S line behind it guarantees that the piece in front does not
+// hold the input's last record: it is parsed with upper_last = 1.  One walk over the lines from the end.
+uint64_t kaamer_text_cut_fasta(const char *text, uint64_t len)
+{
+    if (!text) return 0;
+    bool has_s = false;
+    uint64_t le = len;   // the end of the line being looked at: the position of its '\n', or len
+    if (len && text[len - 1] == '\n') le = len - 1;
+    while (len) {
+        const char *nl = le ? (const char *)memrchr(text, '\n', (size_t)le) : nullptr;
+        const uint64_t ls = nl ? (uint64_t)(nl - text) + 1 : 0;
+        if (ls < le && text[ls] == '>') {
+            if (has_s && ls) return ls;
+        } else if (!has_s) {
+            for (uint64_t q = ls; q < le && !has_s; q++) has_s = !is_space(text[q]);
+        }
+        if (!ls) break;
+        le = ls - 1;
+    }
+    return 0;
+}
+
 // The blocks of a BGZF stream, found without inflating (the rules: include/kaamer_hip.h).  A member is
 //   1f 8b 08 FLG=4 MTIME(4) XFL OS XLEN(2) | extra field of XLEN bytes: subfields SI1 SI2 SLEN(2) data | deflate | CRC32 ISIZE
 // and the subfield 'B' 'C' with SLEN 2 holds BSIZE = the member's size - 1.
@@ -407,21 +431,31 @@ size_t kaamer_bytes_read(kaamer_bytes *b, char *dst, size_t cap)
 }
 
 // The chunk reader of kaamer_search_text_file: text from a byte source in pieces of about `budget` bytes, each cut at
-// kaamer_text_cut_fastq, the tail behind the cut carried into the next.  *chunk comes in as a spare buffer (any size) and
-// goes out holding the chunk in its first *len bytes; *len = 0: the input is over.  A piece without a cut goes on reading
+// the reader's cut rule (kaamer_text_cut_fastq or kaamer_text_cut_fasta), the tail behind the cut carried into the next.
+// *chunk comes in as a spare buffer (any size) and goes out holding the chunk in its first *len bytes; *len = 0: the input is over.  A piece without a cut goes on reading
 // up to 4 budgets, then KAAMER_E_CAPACITY.
+struct TextCutRule {
+    uint64_t (*cut)(const char *text, uint64_t len);
+    const char *driver, *no_cut;   // "<driver>: <no_cut> within N bytes of text ..."
+};
 struct kaamer_text_chunker {
     kaamer_bytes *src = nullptr;
     size_t budget = 0;
     std::vector<char> acc;        // text read and not yet handed out: the tail behind the last cut, then what follows
     size_t acc_len = 0;
     bool over = false;            // the byte source is exhausted
+    const TextCutRule *rule = nullptr;   // the cut rule of the text's format
 };
 
-kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget)
+kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget, bool fasta)
 {
+    // a format's cut rule, with what the reader says when four budgets hold no cut
+    static const TextCutRule rules[2] = {
+        { kaamer_text_cut_fastq, "search_text_file", "no line starts with '@'" },
+        { kaamer_text_cut_fasta, "search_fasta_file", "no record starts behind a '>' line (kaamer_text_cut_fasta)" },
+    };
     kaamer_text_chunker *c = new (std::nothrow) kaamer_text_chunker();
-    if (c) { c->src = src; c->budget = (size_t)budget; }
+    if (c) { c->src = src; c->budget = (size_t)budget; c->rule = &rules[fasta ? 1 : 0]; }
     return c;
 }
 
@@ -448,11 +482,11 @@ int kaamer_text_chunker_next(kaamer_text_chunker *c, std::vector<char> *chunk, s
         }
         if (c->acc_len == 0) return KAAMER_OK;
         if (c->over) { cut = c->acc_len; break; }   // the rest of the file
-        cut = (size_t)kaamer_text_cut_fastq(c->acc.data(), c->acc_len);
+        cut = (size_t)c->rule->cut(c->acc.data(), c->acc_len);
         if (cut) break;
         if (want >= 4 * c->budget)
-            return kaamer_fail(KAAMER_E_CAPACITY, "search_text_file: no line starts with '@' within %zu bytes of text (4 chunk_text_bytes): "
-                                                  "use kaamer_search_file, whose reader takes records of any length", want);
+            return kaamer_fail(KAAMER_E_CAPACITY, "%s: %s within %zu bytes of text (4 chunk_text_bytes): "
+                                                  "use kaamer_search_file, whose reader takes records of any length", c->rule->driver, c->rule->no_cut, want);
         want += c->budget;
     }
     // the chunk takes the buffer, the tail moves to the front of the spare one

@@ -114,20 +114,30 @@ static int bgzf_inflate_to_slot(TopSlot &h, const BgzfInput &bz, uint64_t text_l
     return KAAMER_OK;
 }
 
+// FASTA text as the input of a text call (kaamer_submit_fasta_top_flat, kaamer_search_fasta_file): the `format` of
+// text_submit is then not looked at, and PROTEIN is as good a sequence type as the other two
+struct FastaInput { bool upper_last; };
+
 static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, const kaamer_topn_opts *top,
-                       bool blocking, kaamer_ticket **out, const BgzfInput *bz = nullptr)
+                       bool blocking, kaamer_ticket **out, const BgzfInput *bz = nullptr, const FastaInput *fa = nullptr)
 {
-    if (!ix || !top || !out || (!text && len && !bz) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: bad argument");
+    const char *who = fa ? "submit_fasta_top" : "submit_text_top";
+    if (!ix || !top || !out || (!text && len && !bz) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "%s: bad argument", who);
     *out = nullptr;
-    if (format == 0)
-        return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTA is not parsed on the device: use the host reader (kaamer_parse_fasta, then kaamer_submit_batch_top_flat)");
-    if (format != 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: unknown format %d (1 = FASTQ)", (int)format);
-    SEQ_TYPE_CHK(seq_type, "submit_text_top");
-    if (!is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
+    if (!fa) {
+        if (format == 0)
+            return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTA is not parsed on the device by this call: use kaamer_submit_fasta_top_flat, or the host reader "
+                                             "(kaamer_parse_fasta, then kaamer_submit_batch_top_flat)");
+        if (format != 1) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: unknown format %d (1 = FASTQ)", (int)format);
+    }
+    SEQ_TYPE_CHK(seq_type, who);
+    if (!fa && !is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
     if (!bz && kaamer_is_gzip(text, len))
-        return kaamer_fail(KAAMER_E_ARG, "submit_text_top: the text starts with the gzip signature: inflate it first (kaamer_search_text_file does)");
+        return kaamer_fail(KAAMER_E_ARG, "%s: the text starts with the gzip signature: inflate it first (%s does)", who,
+                           fa ? "kaamer_search_fasta_file" : "kaamer_search_text_file");
     if (len > 0xFFFFFFFFull)
-        return kaamer_fail(KAAMER_E_ARG, "submit_text_top: a text holds at most 2^32 - 1 bytes (spans are 32-bit): cut it (kaamer_text_cut_fastq)");
+        return kaamer_fail(KAAMER_E_ARG, "%s: a text holds at most 2^32 - 1 bytes (spans are 32-bit): cut it (%s)", who,
+                           fa ? "kaamer_text_cut_fasta" : "kaamer_text_cut_fastq");
     int slot = -1;
     const int src = top_slot_take(ix, blocking, &slot);
     if (src) return src;
@@ -140,7 +150,8 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
     hipError_t he = hipSetDevice(ix->device);
     if (he != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(he));
     // where the bounds start: a record of a read set is a header, the read, '+' and as many quality bytes -- 32 bytes
-    // would be a 10-base read; four lines per record.  Kept when the slot's parser already holds more.
+    // would be a 10-base read; four lines per record.  Kept when the slot's parser already holds more.  (FASTA starts from
+    // the same figures: they hold for two-line reads and for 60-column files, and narrower ones grow them.)
     const uint32_t hard_recs = text_hard_records(len);
     uint32_t recs = (uint32_t)(len / 32 + 1024);
     if (recs > hard_recs) recs = hard_recs;
@@ -182,7 +193,8 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
             }
             uploaded = true;
         }
-        rc = kaamer_parse_fastq_device(h.parser, h.d_text, len, h.stream);
+        rc = fa ? kaamer_parse_fasta_device(h.parser, h.d_text, len, fa->upper_last ? 1 : 0, h.stream)
+                : kaamer_parse_fastq_device(h.parser, h.d_text, len, h.stream);
         if (!rc) rc = kaamer_text_parser_finish(h.parser, h.stream, &pr);   // the one wait of the submit call: n_seqs comes from the host
         if (rc != KAAMER_E_CAPACITY) break;
         if (recs >= hard_recs && lines >= len + 1) break;   // (cannot happen: these bounds hold for any text)
@@ -237,6 +249,27 @@ int kaamer_search_text_top_flat(kaamer_index *ix, const char *text, uint64_t len
     if (out) *out = nullptr;
     kaamer_ticket *t = nullptr;
     const int rc = kaamer_submit_text_top_flat(ix, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+// the text call for FASTA (search_protein.go / search_nucleotide.go / search_fastq.go with GetQueriesFasta inside): one more
+// caller of text_submit
+int kaamer_submit_fasta_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                 int64_t min_k_match, uint32_t max_results, kaamer_ticket **ticket)
+{
+    kaamer_topn_opts top;
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    const FastaInput fa = { upper_last != 0 };
+    return text_submit(ix, text, len, 0, seq_type, &top, true, ticket, nullptr, &fa);
+}
+
+int kaamer_search_fasta_top_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                 int64_t min_k_match, uint32_t max_results, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_fasta_top_flat(ix, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, &t);
     if (rc) return rc;
     return kaamer_wait_batch_top(t, out);
 }
@@ -313,10 +346,10 @@ static int stream_push_bgzf(kaamer_stream *st, const BgzfInput &bz, uint64_t tex
 
 // a text chunk into the FIFO of a stream (kaamer_search_text_file): as kaamer_stream_push, never blocking on a slot the
 // stream itself holds
-static int stream_push_text(kaamer_stream *st, const char *text, uint64_t len)
+static int stream_push_text(kaamer_stream *st, const char *text, uint64_t len, const FastaInput *fa = nullptr)
 {
     kaamer_ticket *t = nullptr;
-    const int rc = text_submit(st->ix, text, len, 1, st->seq_type, &st->top, st->fifo->empty(), &t);
+    const int rc = text_submit(st->ix, text, len, 1, st->seq_type, &st->top, st->fifo->empty(), &t, nullptr, fa);
     if (rc) return rc;
     st->fifo->push_back(t);
     return KAAMER_OK;

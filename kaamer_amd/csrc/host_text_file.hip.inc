@@ -4,14 +4,14 @@
 // chunk_loop; this file is the source it runs over.
 
 // chunk k -> replica k mod n, as kaamer_replica_stream_push deals packed chunks
-static int replica_stream_push_text(kaamer_replica_stream *rs, const char *text, uint64_t len)
+static int replica_stream_push_text(kaamer_replica_stream *rs, const char *text, uint64_t len, const FastaInput *fa = nullptr)
 {
-    const int rc = stream_push_text((*rs->st)[rs->pushed % rs->st->size()], text, len);
+    const int rc = stream_push_text((*rs->st)[rs->pushed % rs->st->size()], text, len, fa);
     if (rc == KAAMER_OK) rs->pushed++;
     return rc;
 }
 
-struct TextChunk { std::vector<char> text; size_t len; };
+struct TextChunk { std::vector<char> text; size_t len; bool last; };
 struct TextSource {
     typedef TextChunk Chunk;
     kaamer_text_chunker *reader;  // the file's text, cut into chunks (host_search.cpp)
@@ -20,6 +20,7 @@ struct TextSource {
     void *user;
     uint64_t n_seen;              // records delivered so far
     std::vector<std::vector<char>> pool;   // buffers of chunks that were delivered
+    bool fasta = false;           // kaamer_search_fasta_file: the chunks are FASTA, every one but the file's last with upper_last
 
     bool done() const { return kaamer_text_chunker_done(reader); }
     int next(Chunk **out)
@@ -29,10 +30,16 @@ struct TextSource {
         if (!pool.empty()) { c->text.swap(pool.back()); pool.pop_back(); }
         const int rc = kaamer_text_chunker_next(reader, &c->text, &c->len);
         if (rc || c->len == 0) { drop(c); return rc; }
+        c->last = kaamer_text_chunker_done(reader);   // (the reader hands out the rest of the input only once it has seen its end)
         *out = c;
         return KAAMER_OK;
     }
-    int push(Chunk *c) { return replica_stream_push_text(rs, c->text.data(), c->len); }
+    int push(Chunk *c)
+    {
+        if (!fasta) return replica_stream_push_text(rs, c->text.data(), c->len);
+        const FastaInput fa = { !c->last };
+        return replica_stream_push_text(rs, c->text.data(), c->len, &fa);
+    }
     int pop(kaamer_batch_top **top) { return kaamer_replica_stream_pop(rs, top); }
     uint32_t pending() const { return kaamer_replica_stream_pending(rs); }
     int deliver(Chunk *c, const kaamer_batch_top *top)
@@ -222,32 +229,26 @@ struct BgzfSource {
     void drop(Chunk *c) { delete c; }
 };
 
-int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
-                            uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
-                            kaamer_counters *total)
+// the plain / gzip file `path` through the chunk reader with the cut rule of its format, and chunk_loop over it
+static int text_file_run(kaamer_replicas *r, const char *path, bool fasta, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                         uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
+                         kaamer_counters *total)
 {
-    if (!r || !path || chunk_text_bytes == 0 || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "search_text_file: bad argument");
-    if (format == 0)
-        return kaamer_fail(KAAMER_E_ARG, "search_text_file: FASTA is not parsed on the device: use the host reader (kaamer_search_file)");
-    if (format != 1) return kaamer_fail(KAAMER_E_ARG, "search_text_file: unknown format %d (1 = FASTQ)", format);
-    SEQ_TYPE_CHK(seq_type, "search_text_file");
-    if (!is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "search_text_file: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
-    if (chunk_text_bytes > 0xFFFFFFFFull / 4)
-        return kaamer_fail(KAAMER_E_ARG, "search_text_file: chunk_text_bytes above 2^30 - 1 (a chunk may grow to four times that and spans are 32-bit)");
+    const char *who = fasta ? "search_fasta_file" : "search_text_file";
     if (total) memset(total, 0, sizeof *total);
     if (in_flight < 1) in_flight = 3;
     const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return kaamer_fail(KAAMER_E_IO, "search_text_file: cannot open %s", path);
+    if (fd < 0) return kaamer_fail(KAAMER_E_IO, "%s: cannot open %s", who, path);
     kaamer_bytes *bytes = nullptr;
     int rc = kaamer_bytes_open_fd(fd, &bytes);
     if (rc) { close(fd); return rc; }
     kaamer_replica_stream *rs = nullptr;
     rc = kaamer_replica_stream_open_flat(r, seq_type, min_k_ratio, min_k_match, max_results, &rs);
     if (!rc) {
-        kaamer_text_chunker *reader = kaamer_text_chunker_new(bytes, chunk_text_bytes);
-        if (!reader) rc = kaamer_fail(KAAMER_E_NOMEM, "search_text_file: chunk reader");
+        kaamer_text_chunker *reader = kaamer_text_chunker_new(bytes, chunk_text_bytes, fasta);
+        if (!reader) rc = kaamer_fail(KAAMER_E_NOMEM, "%s: chunk reader", who);
         if (!rc) {
-            TextSource src = { reader, rs, cb, user, 0, {} };
+            TextSource src = { reader, rs, cb, user, 0, {}, fasta };
             rc = chunk_loop(src, in_flight * kaamer_replicas_count(r), total);
         }
         kaamer_text_chunker_free(reader);
@@ -256,6 +257,34 @@ int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, in
     kaamer_bytes_close(bytes);
     close(fd);
     return rc;
+}
+
+// ProteinSearch / NucleotideSearch / FastqSearch over a FASTA file (search_protein.go, search_nucleotide.go, search_fastq.go:
+// each calls GetQueriesFasta when the request is not FASTQ) with the reader on the device
+int kaamer_search_fasta_file(kaamer_replicas *r, const char *path, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                             uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
+                             kaamer_counters *total)
+{
+    if (!r || !path || chunk_text_bytes == 0 || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "search_fasta_file: bad argument");
+    SEQ_TYPE_CHK(seq_type, "search_fasta_file");
+    if (chunk_text_bytes > 0xFFFFFFFFull / 4)
+        return kaamer_fail(KAAMER_E_ARG, "search_fasta_file: chunk_text_bytes above 2^30 - 1 (a chunk may grow to four times that and spans are 32-bit)");
+    return text_file_run(r, path, true, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total);
+}
+
+int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                            uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
+                            kaamer_counters *total)
+{
+    if (!r || !path || chunk_text_bytes == 0 || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "search_text_file: bad argument");
+    if (format == 0)
+        return kaamer_fail(KAAMER_E_ARG, "search_text_file: FASTA is not parsed on the device by this call: use kaamer_search_fasta_file, or the host reader (kaamer_search_file)");
+    if (format != 1) return kaamer_fail(KAAMER_E_ARG, "search_text_file: unknown format %d (1 = FASTQ)", format);
+    SEQ_TYPE_CHK(seq_type, "search_text_file");
+    if (!is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "search_text_file: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
+    if (chunk_text_bytes > 0xFFFFFFFFull / 4)
+        return kaamer_fail(KAAMER_E_ARG, "search_text_file: chunk_text_bytes above 2^30 - 1 (a chunk may grow to four times that and spans are 32-bit)");
+    return text_file_run(r, path, false, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total);
 }
 
 int kaamer_search_text_file_opts(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio, int64_t min_k_match,

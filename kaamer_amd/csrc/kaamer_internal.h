@@ -50,9 +50,12 @@ bool kaamer_bytes_is_gzip(const kaamer_bytes *b);
 size_t kaamer_bytes_read(kaamer_bytes *b, char *dst, size_t cap);         // the next block of text; 0: the input is over
 void kaamer_bytes_end(kaamer_bytes *b);                                   // nothing more is handed out
 void kaamer_bytes_close(kaamer_bytes *b);
-// ... cut into chunks at kaamer_text_cut_fastq (the reader half of kaamer_search_text_file; the rules: host_search.cpp)
+// ... cut into chunks by a cut rule, kaamer_text_cut_fastq or kaamer_text_cut_fasta (the reader half of kaamer_search_text_file
+// and kaamer_search_fasta_file; the rules: host_search.cpp).  Once kaamer_text_chunker_done is true, the chunk handed out
+// last was the rest of the input.
 struct kaamer_text_chunker;
-kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget);   // src stays the caller's
+// (fasta: the cut rule is kaamer_text_cut_fasta and the reader speaks as kaamer_search_fasta_file; else kaamer_text_cut_fastq)
+kaamer_text_chunker *kaamer_text_chunker_new(kaamer_bytes *src, uint64_t budget, bool fasta = false);   // src stays the caller's
 int kaamer_text_chunker_next(kaamer_text_chunker *c, std::vector<char> *chunk, size_t *len);
 bool kaamer_text_chunker_done(const kaamer_text_chunker *c);
 void kaamer_text_chunker_free(kaamer_text_chunker *c);

@@ -418,9 +418,11 @@ struct kaamer_text_parser {
     unsigned long long *d_u64 = nullptr;       // every u64 array
     uint8_t *d_seqs = nullptr;
     kaamer_text_span *d_spans = nullptr;
+    uint32_t *d_fa = nullptr;                  // what only FASTA needs (parse_fasta.hip.inc), allocated at the first FASTA text
     unsigned long long *h_res = nullptr;       // pinned
     PtParams p{};                              // the device pointers, laid out once
     bool parsed = false;
+    bool fasta = false;                        // the last parse was kaamer_parse_fasta_device
 };
 
 static uint64_t pt_default_line_cap(uint64_t max_text, uint32_t max_records)
@@ -441,6 +443,7 @@ void kaamer_text_parser_free(kaamer_text_parser *ps)
     if (ps->d_u64) (void)hipFree(ps->d_u64);
     if (ps->d_seqs) (void)hipFree(ps->d_seqs);
     if (ps->d_spans) (void)hipFree(ps->d_spans);
+    if (ps->d_fa) (void)hipFree(ps->d_fa);
     if (ps->h_res) (void)hipHostFree(ps->h_res);
     delete ps;
 }
@@ -538,6 +541,7 @@ int kaamer_parse_fastq_device(kaamer_text_parser *ps, const uint8_t *d_text, uin
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(ps->h_res, p.res, PT_R_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     ps->parsed = true;
+    ps->fasta = false;
     return KAAMER_OK;
 }
 
@@ -549,11 +553,12 @@ int kaamer_text_parser_finish(kaamer_text_parser *ps, void *stream, kaamer_text_
     HIPCHK(hipSetDevice(ps->device));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     const unsigned long long st = ps->h_res[PT_R_STATUS];
+    const char *who = ps->fasta ? "parse_fasta_device" : "parse_fastq_device";
     if (st & PT_ST_LINES)
-        return kaamer_fail(KAAMER_E_CAPACITY, "parse_fastq_device: %llu lines, the parser holds %u (max_records %u): create it for more records",
-                           ps->h_res[PT_R_NL], ps->line_cap, ps->rec_cap);
+        return kaamer_fail(KAAMER_E_CAPACITY, "%s: %llu lines, the parser holds %u (max_records %u): create it for more records%s", who,
+                           ps->h_res[PT_R_NL], ps->line_cap, ps->rec_cap, ps->fasta ? " or more lines (kaamer_text_parser_create_lines)" : "");
     if (st & PT_ST_RECORDS)
-        return kaamer_fail(KAAMER_E_CAPACITY, "parse_fastq_device: %llu records, the parser holds %u", ps->h_res[PT_R_RECORDS], ps->rec_cap);
+        return kaamer_fail(KAAMER_E_CAPACITY, "%s: %llu records, the parser holds %u", who, ps->h_res[PT_R_RECORDS], ps->rec_cap);
     out->n_records = (uint32_t)ps->h_res[PT_R_RECORDS];
     out->n_lines = ps->h_res[PT_R_LINES];
     out->seq_bytes = ps->h_res[PT_R_SEQ_BYTES];

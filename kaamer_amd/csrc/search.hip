@@ -1099,6 +1099,7 @@ static void aln_table_free(kaamer_index *ix)
 }
 
 #include "parse_text.hip.inc"
+#include "parse_fasta.hip.inc"
 #include "inflate.hip.inc"
 
 extern "C" {

@@ -224,7 +224,17 @@ class _ConsumerGone(Exception):
     """SearchFile's generator was closed before the file ended"""
 
 
-def SearchFile(handle, path, options=None, fmt=None, device_parse=False, device_inflate=False):
+_FASTA_SPACE = b" \t\n\v\f\r"
+
+
+def _fasta_span_seq(text, s, upper):
+    """the sequence of a FASTA record from its span: the range's lines, '\\r' dropped, trimmed and joined (the reader's rules)"""
+    rng = text[int(s["seq_off"]):int(s["seq_off"]) + int(s["seq_len"])]
+    seq = b"".join(ln.strip(_FASTA_SPACE) for ln in rng.split(b"\n"))
+    return (seq.upper() if upper else seq).decode("latin-1")   # (bytes.upper: a-z only, as the reader)
+
+
+def SearchFile(handle, path, options=None, fmt=None, device_parse=False, device_inflate=False, device_fasta=False):
     """FastqSearch / ProteinSearch / NucleotideSearch (search_fastq.go:60-136, search_protein.go:40-118,
     search_nucleotide.go:27-160) over a FILE of any size (gzip included) on an api.Replicas set or an api.ShardedIndex: a
     generator of QueryResult dicts in file order, shaped as the text drivers above shape theirs (options.SequenceType
@@ -236,9 +246,27 @@ def SearchFile(handle, path, options=None, fmt=None, device_parse=False, device_
     text is parsed on the device (kaamer_search_text_file, options.ChunkTextBytes of text per chunk) and the names are
     sliced out of each chunk's text by span; the same dicts come out.  device_inflate=True (with device_parse only: else
     ValueError): a BGZF file is also inflated on the device (kaamer_search_text_file_opts); whatever else a gzip file holds
-    falls back to the host inflater, the results are the same."""
+    falls back to the host inflater, the results are the same.
+    device_fasta=True (FASTA on an api.Replicas set, any of the three sequence types, no ExtractPositions, no Align;
+    anything else: ValueError): the file's FASTA text is parsed on the device (kaamer_search_fasta_file); names -- and for
+    PROTEIN the sequences -- are taken out of each chunk's text by span; the same dicts come out."""
     o = options or SearchOptions(SequenceType=abi.READS)
     seq_type = o.SequenceType
+    if device_fasta:
+        why = None
+        if device_parse or device_inflate:
+            why = "device_parse / device_inflate are the FASTQ route"
+        elif fmt not in (None, "fasta"):
+            why = "the file must be FASTA"
+        elif seq_type not in (abi.READS, abi.NUCLEOTIDE, abi.PROTEIN):
+            why = "unknown SequenceType"
+        elif o.ExtractPositions or o.Align:
+            why = "ExtractPositions and Align go through the host reader"
+        elif not hasattr(handle, "search_fasta_file"):
+            why = "the handle has no FASTA text driver (an api.Replicas set has)"
+        if why:
+            raise ValueError("SearchFile(device_fasta=True): " + why)
+        fmt = "fasta"
     fmt = fmt or ("fastq" if seq_type == abi.READS else "fasta")
     if device_inflate and not device_parse:
         raise ValueError("SearchFile(device_inflate=True) needs device_parse=True: the device inflates into the device reader's text buffer")
@@ -279,8 +307,42 @@ def SearchFile(handle, path, options=None, fmt=None, device_parse=False, device_
         recs = [dict(name=text[int(s["name_off"]):int(s["name_off"]) + int(s["name_len"])].decode("latin-1")) for s in sp]
         put(_chunk_results(top, recs, o, seq_type, None, False))
 
+    held = []   # device_fasta: the chunk that may hold the file's last record waits for its successor or the file's end
+
+    def fasta_chunk_out(first, text, top, last):
+        sp = top.text_spans
+        n = len(sp)
+        if seq_type == abi.PROTEIN:   # the reported queries carry their own sequence (search_protein.go)
+            recs = [None] * n
+            for i in set(int(x) for x in top.rep_query):
+                s = sp[i]
+                # the reader's case rule: only the record still pending at the end of the input keeps its case -- a last
+                # record with a header line behind it was closed by that header and is upper-cased like the others
+                end = int(s["seq_off"]) + int(s["seq_len"])
+                pending = last and i == n - 1 and b"\n>" not in text[end:]
+                seq = _fasta_span_seq(text, s, not pending)
+                recs[i] = dict(seq=seq, name=text[int(s["name_off"]):int(s["name_off"]) + int(s["name_len"])].decode("latin-1"),
+                               size=len(seq) - 6 - (1 if seq.endswith("*") else 0), plus=first == 0 and i == 0)
+        else:
+            recs = [dict(name=text[int(s["name_off"]):int(s["name_off"]) + int(s["name_len"])].decode("latin-1")) for s in sp]
+        put(_chunk_results(top, recs, o, seq_type, None, False))
+
+    def on_fasta_chunk(first, text, top):
+        if held:
+            fasta_chunk_out(*held.pop(), False)
+        held.append((first, text, top))
+
     def work():
         try:
+            if device_fasta:
+                handle.search_fasta_file(path, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio,
+                                         min_k_match=o.MinKMatch, max_results=o.MaxResults,
+                                         chunk_text_bytes=int(getattr(o, "ChunkTextBytes", 1 << 28)), in_flight=int(getattr(o, "InFlight", 0)),
+                                         on_chunk=on_fasta_chunk)
+                if held:
+                    fasta_chunk_out(*held.pop(), True)
+                put(done)
+                return
             if device_parse:
                 handle.search_text_file(path, fmt, seq_type=abi.seq_type(seq_type, getattr(o, "GeneticCode", 0)), min_k_ratio=o.MinKRatio,
                                         min_k_match=o.MinKMatch, max_results=o.MaxResults,

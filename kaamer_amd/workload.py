@@ -291,3 +291,19 @@ def fastq_text(reads):
     out[e] = 10; out[e + 1] = ord("+"); out[e + 2] = 10
     out[start[1:] - 1] = 10
     return out.tobytes()
+
+
+def fasta_text(packed, width=60):
+    """packed sequences -> FASTA text (numpy, no per-record Python): ">r\\n" and the sequence in lines of `width` per record."""
+    buf, offs = packed
+    offs = offs.astype(np.int64)
+    lens = offs[1:] - offs[:-1]
+    rec = 3 + lens + (lens + width - 1) // width
+    start = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(rec, out=start[1:])
+    out = np.full(int(start[-1]), 10, dtype=np.uint8)       # whatever is neither header nor residue is a line break
+    s0 = start[:-1]
+    out[s0] = ord(">"); out[s0 + 1] = ord("r")
+    j = np.arange(int(offs[-1]), dtype=np.int64) - np.repeat(offs[:-1], lens)
+    out[np.repeat(s0 + 3, lens) + j + j // width] = buf[:int(offs[-1])]
+    return out.tobytes()

@@ -1,7 +1,9 @@
-// text_cut_check — the host half of the device FASTQ reader under AddressSanitizer + UBSan, as a stand-alone program:
-// kaamer_text_cut_fastq and the chunk reader of kaamer_search_text_file (byte source -> chunks cut before an '@' that
-// opens a line) over hand cases and random texts, plain and gzip; every chunk is parsed with kaamer_parse_fastq and the
-// concatenation must equal kaamer_parse_fastq of the whole text.  CPU only.    make -C tools/text_cut_check test
+// text_cut_check — the host half of the device FASTQ and FASTA readers under AddressSanitizer + UBSan, as a stand-alone
+// program: kaamer_text_cut_fastq / kaamer_text_cut_fasta and the chunk reader of kaamer_search_text_file /
+// kaamer_search_fasta_file (byte source -> chunks cut before an '@' / a '>' that opens a line) over hand cases and random
+// texts, plain and gzip; every chunk is parsed with the host reader (FASTA: every chunk but the last with its last record
+// upper-cased, as upper_last = 1 does on the device) and the concatenation must equal the host parse of the whole text.
+// The FASTA cut is also held against a straight restatement of its rule.  CPU only.    make -C tools/text_cut_check test
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -43,11 +45,11 @@ struct Records {
     bool operator==(const Records &o) const { return seq == o.seq && name == o.name && size == o.size; }
 };
 
-static void parse_into(const std::string &text, Records *out)
+static void parse_into(const std::string &text, Records *out, bool fasta = false, bool upper_last = false)
 {
     kaamer_reads *r = nullptr;
-    const int rc = kaamer_parse_fastq(text.data(), text.size(), &r);
-    CHECK(rc == KAAMER_OK, "parse_fastq: %d", rc);
+    const int rc = fasta ? kaamer_parse_fasta(text.data(), text.size(), &r) : kaamer_parse_fastq(text.data(), text.size(), &r);
+    CHECK(rc == KAAMER_OK, "parse: %d", rc);
     if (rc) return;
     const uint32_t n = kaamer_reads_count(r);
     const uint64_t *off = kaamer_reads_offsets(r), *noff = kaamer_reads_name_offsets(r);
@@ -58,7 +60,50 @@ static void parse_into(const std::string &text, Records *out)
         out->size.push_back(kaamer_reads_size_in_kmer(r)[i]);
         // (PlusStrand is 1 on the first record of what was parsed: per FILE it is host bookkeeping, not compared here)
     }
+    if (upper_last && n)
+        for (char &c : out->seq.back())
+            if (c >= 'a' && c <= 'z') c = (char)(c - 32);
     kaamer_reads_free(r);
+}
+
+// ---- kaamer_text_cut_fasta, restated straight from its rule (quadratic: small texts only)
+static bool fa_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\v' || c == '\f' || c == '\r'; }
+// [p, len) holds a line, complete or not, that does not start with '>' and holds a non-space byte
+static bool fa_has_s_line(const std::string &t, size_t p)
+{
+    while (p < t.size()) {
+        size_t e = t.find('\n', p);
+        if (e == std::string::npos) e = t.size();
+        if (t[p] != '>')
+            for (size_t q = p; q < e; q++)
+                if (!fa_space(t[q])) return true;
+        p = e + 1;
+    }
+    return false;
+}
+static bool fa_valid_cut(const std::string &t, size_t p) { return p >= 1 && p < t.size() && t[p - 1] == '\n' && t[p] == '>' && fa_has_s_line(t, p); }
+static uint64_t fa_ref_cut(const std::string &t)
+{
+    for (size_t p = t.size(); p-- > 1;)
+        if (fa_valid_cut(t, p)) return p;
+    return 0;
+}
+// the chunk reader restated: a window of 1 to 4 budgets behind the last cut, cut at the greatest valid place INSIDE the
+// window (the S line must lie in it too); a window that reaches beyond the text is the rest of the text.  false: some window
+// of four budgets holds no cut (KAAMER_E_CAPACITY by design)
+static bool fa_ref_chunks(const std::string &t, size_t budget, std::vector<size_t> *lens)
+{
+    for (size_t a = 0; a < t.size();) {
+        size_t take = 0;
+        for (size_t w = budget; !take; w += budget) {
+            if (a + w > t.size()) { take = t.size() - a; break; }
+            take = (size_t)fa_ref_cut(t.substr(a, w));
+            if (!take && w >= 4 * budget) return false;
+        }
+        lens->push_back(take);
+        a += take;
+    }
+    return true;
 }
 
 static std::string gzip_members(const std::string &text, size_t split)
@@ -80,8 +125,10 @@ static std::string gzip_members(const std::string &text, size_t split)
 }
 
 // the file's bytes through the byte source and the chunk reader; expect_rc: what the reader must end with
-static void through_chunker(const std::string &file_bytes, const std::string &text, size_t budget, int expect_rc, const char *what)
+static void through_chunker(const std::string &file_bytes, const std::string &text, size_t budget, int expect_rc, const char *what,
+                            bool fasta = false, const std::vector<size_t> *want_lens = nullptr)
 {
+    std::vector<size_t> lens;
     FILE *f = tmpfile();
     if (!f) { perror("tmpfile"); exit(2); }
     if (!file_bytes.empty() && fwrite(file_bytes.data(), 1, file_bytes.size(), f) != file_bytes.size()) { perror("fwrite"); exit(2); }
@@ -90,7 +137,7 @@ static void through_chunker(const std::string &file_bytes, const std::string &te
     kaamer_bytes *src = nullptr;
     int rc = kaamer_bytes_open_fd(fileno(f), &src);
     CHECK(rc == KAAMER_OK, "%s: bytes_open_fd %d", what, rc);
-    kaamer_text_chunker *ck = kaamer_text_chunker_new(src, budget);
+    kaamer_text_chunker *ck = kaamer_text_chunker_new(src, budget, fasta);
     Records got, whole;
     std::string joined;
     std::vector<char> spare;
@@ -100,17 +147,20 @@ static void through_chunker(const std::string &file_bytes, const std::string &te
         rc = kaamer_text_chunker_next(ck, &spare, &len);
         if (rc || !len) continue;
         n_chunks++;
+        lens.push_back(len);
         CHECK(len <= 4 * budget || kaamer_text_chunker_done(ck), "%s: a chunk of %zu bytes with budget %zu", what, len, budget);
-        CHECK(joined.empty() || spare[0] == '@', "%s: chunk %zu does not start with '@'", what, n_chunks);
+        CHECK(joined.empty() || spare[0] == (fasta ? '>' : '@'), "%s: chunk %zu does not start with '%c'", what, n_chunks, fasta ? '>' : '@');
         CHECK(kaamer_text_chunker_done(ck) || spare[len - 1] == '\n', "%s: chunk %zu does not end with a newline", what, n_chunks);
         const std::string piece(spare.data(), len);
         joined += piece;
-        parse_into(piece, &got);
+        // FASTA: a chunk in front of a cut is parsed with upper_last = 1 -- a record follows it
+        parse_into(piece, &got, fasta, fasta && !kaamer_text_chunker_done(ck));
     }
     CHECK(rc == expect_rc, "%s: the reader ended with %d (%s), expected %d", what, rc, g_err, expect_rc);
     if (!rc && !expect_rc) {
         CHECK(joined == text, "%s: the chunks do not add up to the text (%zu of %zu bytes)", what, joined.size(), text.size());
-        parse_into(text, &whole);
+        CHECK(!want_lens || lens == *want_lens, "%s: %zu chunks, the restated reader cuts %zu (budget %zu)", what, lens.size(), want_lens->size(), budget);
+        parse_into(text, &whole, fasta);
         CHECK(got == whole, "%s: %zu records piecewise, %zu at once (budget %zu, %zu chunks)", what, got.seq.size(), whole.seq.size(), budget, n_chunks);
     }
     kaamer_text_chunker_free(ck);
@@ -170,6 +220,53 @@ int main()
         through_chunker(text, text, use, KAAMER_OK, "random text");
         if (it % 4 == 0) through_chunker(gzip_members(text, text.size() / 2), text, use, KAAMER_OK, "random text, two gzip members");
     }
+    // ---- FASTA: the cut by hand, against the restatement, and through the chunk reader
+    struct { const char *text; uint64_t cut; } fa_hand[] = {
+        { "", 0 }, { ">", 0 }, { "\n", 0 }, { "\n>", 0 }, { "ACGT\nACGT\n", 0 }, { "AC>GT\nA>C\n", 0 }, { ">a\nAC\n>b\n>c\n", 0 },
+        { ">a\nAC\n>b\n>c\nG\n", 9 }, { ">a\nAC\n>b\n \t\n\r\n\n", 0 }, { ">a\nAC\n>b\nGG\n>c", 6 }, { ">a\nAC\n>b\nG", 6 },
+        { ">a\nAC\n>b\n  ", 0 }, { ">a\r\nAC\r\n>b\r\nGG\r\n", 8 }, { "\n>a\nAC\n", 1 }, { ">a\nAC\n>b\n >x\n", 6 }, { ">a\nacgt\n>b\n", 0 },
+    };
+    for (auto &h : fa_hand) {
+        const std::string t(h.text);
+        std::vector<char> exact(t.begin(), t.end());
+        const uint64_t cut = kaamer_text_cut_fasta(exact.data(), exact.size());
+        CHECK(cut == h.cut, "FASTA cut of the hand case \"%s\": %llu, expected %llu", h.text, (unsigned long long)cut, (unsigned long long)h.cut);
+        CHECK(fa_ref_cut(t) == h.cut, "the restated FASTA cut of the hand case \"%s\"", h.text);
+        for (size_t budget : { (size_t)1, (size_t)3, (size_t)8, (size_t)64 }) {
+            std::vector<size_t> want;
+            const bool fits = fa_ref_chunks(t, budget, &want);
+            through_chunker(t, t, budget, fits ? KAAMER_OK : KAAMER_E_CAPACITY, "FASTA hand case", true, &want);
+        }
+    }
+    CHECK(kaamer_text_cut_fasta(nullptr, 0) == 0, "NULL text");
+    std::string long_rec = ">long\n";
+    for (int i = 0; i < 100; i++) long_rec += std::string(80, "ACgt"[i & 3]) + "\n";
+    long_rec += ">next\nacgt\n>z\nac\n";
+    through_chunker(long_rec, long_rec, 1000, KAAMER_E_CAPACITY, "long FASTA record, small budget", true);
+    through_chunker(long_rec, long_rec, 2100, KAAMER_OK, "long FASTA record, four budgets", true);
+    const char fa_alphabet[] = ">>AAcg*  \t\r\n\n\n\v\f";
+    const size_t n_fa = sizeof fa_alphabet - 1;
+    size_t fa_with_cut = 0, fa_fit = 0;
+    for (int it = 0; it < 2000; it++) {
+        const size_t n = (size_t)rnd(300);
+        std::string text;
+        for (size_t i = 0; i < n; i++) text += fa_alphabet[rnd(n_fa)];
+        std::vector<char> exact(text.begin(), text.end());
+        const uint64_t cut = kaamer_text_cut_fasta(exact.data(), exact.size()), want = fa_ref_cut(text);
+        CHECK(cut == want, "FASTA cut of random text %d: %llu, the rule says %llu", it, (unsigned long long)cut, (unsigned long long)want);
+        fa_with_cut += want != 0;
+        const size_t budgets[] = { 1, 7, 16, 50 };
+        const size_t use = 2 * budgets[rnd(4)] + 14;   // (16 to 114: records of this alphabet are longer than FASTQ's)
+        std::vector<size_t> want_lens;
+        const bool fits = fa_ref_chunks(text, use, &want_lens);
+        fa_fit += fits;
+        through_chunker(text, text, use, fits ? KAAMER_OK : KAAMER_E_CAPACITY, "random FASTA text", true, &want_lens);
+        if (it % 4 == 0)
+            through_chunker(gzip_members(text, text.size() / 2), text, use, fits ? KAAMER_OK : KAAMER_E_CAPACITY, "random FASTA text, two gzip members", true,
+                            &want_lens);
+    }
+    CHECK(fa_fit * 2 >= 2000, "only %zu of 2000 random FASTA texts go through the chunk reader", fa_fit);
+    CHECK(fa_with_cut * 4 >= 2000, "only %zu of 2000 random FASTA texts hold a cut", fa_with_cut);
     // the byte source's gzip rules: a stream that breaks off reads as what inflated before; a bad first header: nothing
     const std::string two = "@a\nACGT\n+\nIIII\n@b\nGGCC\n+\nIIII\n";
     std::string gz = gzip_members(two, 15);
