@@ -1,5 +1,5 @@
 // host_replicas.hip.inc — ONE process, the same database resident on several devices (included by search.hip inside
-// its extern "C" block, after host_sharded.hip.inc).
+// its extern "C" block, after host_sharded_collect.hip.inc).
 //
 // SURVEY 8e: a database that fits one device is not sharded, the QUERY stream is split -- "replicas only", no
 // collective.  The reference is one server process (api/server.go:47-65) whose FastqSearch takes a file

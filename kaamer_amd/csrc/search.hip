@@ -933,6 +933,18 @@ template <class T> static int dev_alloc(T **p, size_t n)
     return KAAMER_OK;
 }
 
+// a device buffer that lasts from call to call: made again, a quarter larger than asked for, when it is too small
+template <class T> static int dev_grow(T **p, size_t *cap, size_t need)
+{
+    if (*cap >= need) return KAAMER_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t want = need + need / 4 + 64;
+    const int rc = dev_alloc(p, want);
+    if (!rc) *cap = want;
+    return rc;
+}
+
 static void launch_group(const CountParams &p, int grid, bool firstpos, hipStream_t s)
 {
     if (firstpos) hipLaunchKernelGGL((count_group_kernel<true, 0>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);
@@ -2839,6 +2851,8 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 #include "host_top_align.hip.inc"
 #include "host_text.hip.inc"
 #include "host_sharded.hip.inc"
+#include "host_sharded_submit.hip.inc"
+#include "host_sharded_collect.hip.inc"
 #include "host_replicas.hip.inc"
 #include "host_text_file.hip.inc"
 #include "host_sharded_stream.hip.inc"
