@@ -914,7 +914,8 @@ void kaamer_sort_hits(const uint32_t *pid, const uint32_t *kmatch, int64_t n_hit
  * n_bits for a run that reaches the end; with_alignment adds KAAMER_KMER_SIZE - 1 to every end (the residues the last
  * k-mer covers).  Writes at most cap bytes into buf, NUL-terminated when cap > 0, and returns the length of the whole
  * string without the NUL: a return >= cap means buf was too short.  buf may be NULL with cap 0.  (The TSV writer's hit
- * count, strings.Count(posString, ","), is derived from the string by the caller.) */
+ * count, strings.Count(posString, ","), is derived from the string by the caller -- or the whole row is written by
+ * kaamer_format_tsv / the *_tsv_flat calls, at the end of this file.) */
 uint64_t kaamer_format_positions(const uint64_t *bits, int32_t n_bits, int32_t with_alignment, char *buf, uint64_t cap);
 
 /* SetBestStartCodon, dna.go:198-272: hits in sortMapByValue order with their first
@@ -1180,7 +1181,9 @@ void kaamer_reader_close(kaamer_reader *rd);
  *            only (search.go:399): host bookkeeping, not part of the parse.
  *   chunks   a text may be cut at any p with text[p-1] == '\n' and text[p] == '@': the pieces, parsed independently, give
  *            the records of the whole text in order (kaamer_text_cut_fastq).
- * Out of scope here: strict_scanner, -pos / -aln on the text forms, the sharded handle, a reader thread.  (Inflating on
+ * Out of scope here: strict_scanner, -pos / -aln on the text forms (the bitmaps of the reported hits do come with the
+ * calls that return TSV rows, kaamer_submit_text_top_tsv_flat at the end of this file), the sharded handle, a reader thread.
+ * The response rows of a text request are no longer the host's to write: same calls.  (Inflating on
  * the device: the BGZF section below.  FASTA on the device: the section after it, with entry points of its own -- the
  * calls of this section keep refusing format 0.) */
 typedef struct kaamer_text_parser kaamer_text_parser;
@@ -1395,6 +1398,143 @@ int kaamer_search_fasta_top_flat(kaamer_index *ix, const char *text, uint64_t le
 int kaamer_search_fasta_file(kaamer_replicas *r, const char *path, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                              uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb,
                              void *user, kaamer_counters *total);
+
+/* ------------------------------------------------------------------------- */
+/* The TSV response rows (QueryResultHandler, search.go:505-554, the form     */
+/* without alignment; header line: SetResponseFormatAndHeader,                 */
+/* search.go:636-662): one line per reported hit, reported queries ascending,  */
+/* hits in reporting order, fields separated by '\t', the line ended by '\n'.  */
+/*    1 QueryId          strings.Split(Query.Name, " ")[0]: the bytes before   */
+/*                       the first 0x20 (a tab is an ordinary byte); an ORF    */
+/*                       takes the name of record q[].src_seq                  */
+/*    2 SubjectId        HitEntries[Key].EntryId                               */
+/*    3 %KMatchIdentity  "%.2f" of float32(Kmatch) / float32(SizeInKmer) *     */
+/*                       float32(100): two float32 roundings, then the exact   */
+/*                       value rounded half-even at the second decimal         */
+/*    4 QueryKLength     SizeInKmer (an ORF's: after SetBestStartCodon)        */
+/*    5 KMatch                                                                 */
+/*    6 GapOpen          ExtractPositions: the ',' of field 11; else "N/A"     */
+/*  7 8 QStart QEnd      Location.StartPosition (after the trim), EndPosition  */
+/*    9 SStart           "1"                                                   */
+/*   10 SEnd             Annotations: Protein.Length; else "N/A"               */
+/*   11 QueryPositions   ExtractPositions only: kaamer_format_positions(bitmap,*/
+/*                       bits as searched, 0)                                  */
+/*  12.. one per KStats.Features name, Annotations only: the entry's value     */
+/* FetchHitsInformation stops a query's loop at the first id without an entry  */
+/* (search.go:461-463): from that hit on, in reporting order, every hit of the */
+/* query prints an empty SubjectId, 0 as Length and empty feature values.      */
+/* Out of scope: the -aln TSV form (its "%e" of a float64 EValue needs         */
+/* arbitrary-precision formatting), JSON, the file drivers and streams, the    */
+/* sharded handle and the packed-batch calls on the device -- those have the   */
+/* host formatter, and the device stage takes names as bytes + spans, so a     */
+/* packed form is host plumbing only.                                          */
+/* ------------------------------------------------------------------------- */
+/* SetResponseFormatAndHeader, search.go:645-660, Align = false.  proteins (its feature names) may be NULL without
+ * annotations.  The conventions of kaamer_format_positions: at most cap bytes, NUL-terminated when cap > 0, the return is
+ * the whole length without the NUL; need = f(NULL, 0). */
+uint64_t kaamer_format_tsv_header(int32_t extract_positions, int32_t annotations, const kaamer_proteins *proteins, char *buf,
+                                  uint64_t cap);
+/* The rows of any kaamer_batch_top (packed, _pos, sharded or text), on the caller's thread: what QueryResultHandler's
+ * `output += ...` per field does (search.go:505-554).  Names: record i of the input is name_bytes[name_spans[i].name_off,
+ * + name_len) -- a text result passes the caller's text and kaamer_batch_top_text_spans; n_names records (q[].src_seq beyond
+ * it prints an empty name).  proteins: the table kaamer_fetch_hits reads; NULL prints every entry as missing.
+ * line_off (may be NULL): top_off[n_reported] + 1 entries, the first byte of every row and the total.  Returns the whole
+ * length (buf and cap as above: need = f(NULL, 0)), or a negative code: KAAMER_E_ARG for a bad argument and for
+ * extract_positions on a result without bitmaps (kaamer_batch_top_positions gives NULL). */
+int64_t kaamer_format_tsv(const kaamer_batch_top *top, const char *name_bytes, uint64_t name_bytes_len,
+                          const kaamer_text_span *name_spans, uint32_t n_names, const kaamer_proteins *proteins,
+                          int32_t extract_positions, int32_t annotations, char *buf, uint64_t cap, uint64_t *line_off);
+/* The same on a result whose arrays the caller holds itself (one built by hand, or by another library): the three arrays
+ * of kaamer_batch_top_positions as arguments, all NULL without extract_positions.  Host only. */
+int64_t kaamer_format_tsv_arrays(const kaamer_batch_top *top, const int32_t *pos_bits_len, const uint64_t *pos_off,
+                                 const uint64_t *pos_bits, const char *name_bytes, uint64_t name_bytes_len,
+                                 const kaamer_text_span *name_spans, uint32_t n_names, const kaamer_proteins *proteins,
+                                 int32_t extract_positions, int32_t annotations, char *buf, uint64_t cap, uint64_t *line_off);
+
+/* What the rows need of the protein table, resident next to the index: every entry's EntryId bytes, its Length and its
+ * annotation columns pre-joined on the host ('\t' + value per KStats.Features name, in order: the device only copies
+ * bytes), with offsets and an id -> entry map that resolves ids as kaamer_fetch_hits does (shared with
+ * kaamer_index_attach_proteins' map when both are attached in that order; else one of its own).  The table is read during
+ * the call only.  A second attach replaces the first; KAAMER_E_BUSY with calls in flight; freed by kaamer_index_close. */
+int kaamer_index_attach_subject_text(kaamer_index *ix, const kaamer_proteins *proteins);
+/* out[0] HBM bytes, out[1] entries, out[2] the longest row suffix (EntryId + Length digits + annotation columns), out[3]
+ * feature names; zeros when nothing is attached */
+int kaamer_index_subject_text_info(const kaamer_index *ix, uint64_t out[4]);
+
+/* The rows on the device (tsv_rows.hip.inc), enqueued on `stream` behind kaamer_topn_device -- and behind
+ * kaamer_topn_positions_device with extract_positions.  Plain device arrays: a workspace's, or fabricated ones. */
+typedef struct {
+    kaamer_topn_result top;             /* max_results, d_top_cnt, d_top_pid, d_top_kmatch, d_start_position,          */
+                                        /* d_size_in_kmer (d_top_first_pos and d_trim are not read)                    */
+    const kaamer_query_meta *d_q;       /* src_seq and end_position of every query                                     */
+    const uint32_t *d_n_queries;        /* device scalar, as the workspace holds it                                    */
+    uint32_t n_queries_cap;             /* its bound: what the launches are sized by                                   */
+    uint32_t n_names;                   /* records the spans describe                                                  */
+    const uint8_t *d_name_bytes;        /* the text the spans index ...                                                */
+    uint64_t name_bytes_len;            /* ... and its length: a span beyond it prints an empty name                   */
+    const kaamer_text_span *d_spans;    /* name_off / name_len are read                                                */
+    const kaamer_topn_positions *pos;   /* NULL unless extract_positions                                               */
+    int32_t extract_positions, annotations;
+} kaamer_tsv_rows_in;
+typedef struct {
+    const uint64_t *d_line_off;         /* [lines + 1] first byte of every row in d_out, in CSR order; the total        */
+    const uint64_t *d_counts;           /* device: {lines, bytes}                                                       */
+    uint64_t line_off_capacity;         /* entries d_line_off holds                                                     */
+} kaamer_tsv_rows_result;
+/* The stage's own buffers (per-query sizes, their scan, the line offsets), for up to max_queries queries and max_lines
+ * rows; one stage serves one stream at a time. */
+typedef struct kaamer_tsv_stage kaamer_tsv_stage;
+int kaamer_tsv_stage_create(kaamer_index *ix, uint32_t max_queries, uint64_t max_lines, kaamer_tsv_stage **out);
+void kaamer_tsv_stage_free(kaamer_tsv_stage *st);
+/* A length pass (a lane per query: digits, field lengths, for field 11 the runs of the bitmap words), a 64-bit scan of
+ * the tiles' sizes, the rows' offsets, and the write pass.  The write pass works on tiles of out[0] consecutive queries, a
+ * lane per query: the tile's rows are one contiguous byte range of d_out, which the workgroup builds in LDS in windows of
+ * out[1] bytes (aligned to multiples of out[1] in d_out) -- names, ids and annotation values are byte copies at arbitrary
+ * alignment, and LDS takes those at no cost -- and stores with out[2] bytes per lane, consecutive lanes consecutive
+ * addresses.  d_out must start at a 16-byte boundary.  Rows beyond out_cap bytes or max_lines set a status word:
+ * kaamer_tsv_rows_finish then returns KAAMER_E_CAPACITY and nothing of d_out is to be read; the stage stays usable.
+ * KAAMER_E_ARG naming kaamer_index_attach_subject_text when nothing is attached. */
+int kaamer_tsv_rows_device(kaamer_tsv_stage *st, const kaamer_tsv_rows_in *in, char *d_out, uint64_t out_cap, void *stream,
+                           kaamer_tsv_rows_result *out);
+/* waits for `stream`; counts[0] rows, counts[1] bytes (also filled with what was needed on KAAMER_E_CAPACITY) */
+int kaamer_tsv_rows_finish(kaamer_tsv_stage *st, void *stream, uint64_t counts[2]);
+/* out[0] queries per tile, out[1] bytes per LDS window, out[2] bytes a lane stores at once, out[3] threads per workgroup */
+void kaamer_tsv_geometry(uint32_t out[4]);
+
+/* The text calls with the rows in the result: what a host shim calls instead of QueryResultHandler + QueryResultWriter's
+ * per-field `output += ...` (search.go:505-554) -- it writes the header (kaamer_format_tsv_header) and then the bytes of
+ * kaamer_batch_top_tsv to the response.  Arguments, slot, ticket, wait, discard, spans (and text, for BGZF) as
+ * kaamer_submit_text_top_flat / kaamer_submit_fasta_top_flat / kaamer_submit_bgzf_top_flat, plus SearchOptions.ExtractPositions
+ * and SearchOptions.Annotations.  The stage follows the packing of the block on the slot's stream; with extract_positions
+ * the ticket asks for the bitmaps as the _pos calls do, and kaamer_batch_top_positions gives them as well.  The structured
+ * result is that of the call without rows.  The rows and their line offsets have a buffer of their own next to the block
+ * (the block's format is unchanged: one more device-to-host copy); its two bounds, bytes and rows, start from what the
+ * slot's previous call needed plus a quarter, and a batch beyond them is repeated from the parsed buffers with what it
+ * reported to need.  KAAMER_E_ARG naming kaamer_index_attach_subject_text when nothing is attached. */
+int kaamer_submit_text_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                    double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                    int32_t annotations, kaamer_ticket **ticket);
+int kaamer_search_text_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                    double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                    int32_t annotations, kaamer_batch_top **out);
+int kaamer_submit_fasta_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                     int32_t annotations, kaamer_ticket **ticket);
+int kaamer_search_fasta_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                     int32_t annotations, kaamer_batch_top **out);
+int kaamer_submit_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                    int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                    kaamer_ticket **ticket);
+int kaamer_search_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                    int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                    kaamer_batch_top **out);
+/* The rows of a result: views that live as long as it does; line_off has top_off[n_reported] + 1 entries.  NULL / 0 for a
+ * result of any other call (format it on the host: kaamer_format_tsv). */
+int kaamer_batch_top_tsv(const kaamer_batch_top *out, const char **text, uint64_t *len, const uint64_t **line_off);
+/* The FIRST bounds of the rows (bytes, rows) on every slot of this index, for callers who know what their batches print;
+ * 0: the rule.  A batch beyond them is repeated as stated above.  KAAMER_E_BUSY with calls in flight. */
+int kaamer_index_set_tsv_bounds(kaamer_index *ix, uint64_t bytes, uint64_t lines);
 
 #ifdef __cplusplus
 }

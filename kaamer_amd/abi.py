@@ -179,6 +179,16 @@ class InflateResult(C.Structure):   # kaamer_inflate_result
                 ("reserved", C.c_uint32), ("d_status", C.c_void_p)]
 
 
+class TsvRowsIn(C.Structure):   # kaamer_tsv_rows_in
+    _fields_ = [("top", TopnResult), ("d_q", C.c_void_p), ("d_n_queries", C.c_void_p), ("n_queries_cap", C.c_uint32),
+                ("n_names", C.c_uint32), ("d_name_bytes", C.c_void_p), ("name_bytes_len", C.c_uint64), ("d_spans", C.c_void_p),
+                ("pos", C.POINTER(TopnPositions)), ("extract_positions", C.c_int32), ("annotations", C.c_int32)]
+
+
+class TsvRowsResult(C.Structure):   # kaamer_tsv_rows_result
+    _fields_ = [("d_line_off", C.c_void_p), ("d_counts", C.c_void_p), ("line_off_capacity", C.c_uint64)]
+
+
 # every symbol include/kaamer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "kaamer_last_error": (C.c_char_p, []),
@@ -446,6 +456,39 @@ SYMBOLS = {
     # (handle, path, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total)
     "kaamer_search_fasta_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    # the TSV response rows: the host formatter, the subject text on the device, the device stage, the text calls
+    # (extract_positions, annotations, proteins, buf, cap)
+    "kaamer_format_tsv_header": (C.c_uint64, [C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_uint64]),
+    # (top, name_bytes, name_bytes_len, name_spans, n_names, proteins, extract_positions, annotations, buf, cap, line_off)
+    "kaamer_format_tsv": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_uint64, C.c_void_p]),
+    # (top, pos_bits_len, pos_off, pos_bits, ...the same)
+    "kaamer_format_tsv_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_index_attach_subject_text": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kaamer_index_subject_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_tsv_stage_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "kaamer_tsv_stage_free": (None, [C.c_void_p]),
+    "kaamer_tsv_rows_device": (C.c_int, [C.c_void_p, C.POINTER(TsvRowsIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TsvRowsResult)]),
+    "kaamer_tsv_rows_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_tsv_geometry": (None, [C.POINTER(C.c_uint32)]),
+    # (handle, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, annotations, out)
+    "kaamer_submit_text_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                  C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_text_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                  C.c_int32, C.c_int32, C.c_void_p]),
+    # (handle, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, extract_positions, annotations, out)
+    "kaamer_submit_fasta_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                   C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_fasta_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                   C.c_int32, C.c_int32, C.c_void_p]),
+    # (handle, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, annotations, out)
+    "kaamer_submit_bgzf_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                                  C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_bgzf_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                                  C.c_int32, C.c_void_p]),
+    "kaamer_batch_top_tsv": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]),
+    "kaamer_index_set_tsv_bounds": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
 }
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range

@@ -294,6 +294,15 @@ class TopResult:
         abi.check(abi.lib().kaamer_batch_top_text(out, C.byref(tp), C.byref(tn)))
         if tp.value:
             self.text = C.string_at(tp.value, tn.value)
+        # the TSV rows of a call with tsv=... (kaamer_batch_top_tsv): bytes, and the first byte of every row + the total; None
+        # for other calls
+        self.tsv = self.tsv_line_off = None
+        if hasattr(abi.lib(), "kaamer_batch_top_tsv"):
+            vp, vn, vo = C.c_void_p(), C.c_uint64(), C.POINTER(C.c_uint64)()
+            abi.check(abi.lib().kaamer_batch_top_tsv(out, C.byref(vp), C.byref(vn), C.byref(vo)))
+            if bool(vo):
+                self.tsv = C.string_at(vp.value, vn.value) if vn.value else b""
+                self.tsv_line_off = np.ctypeslib.as_array(vo, shape=(ne + 1,)).copy()
         self.alignments = None
         items, text = C.POINTER(abi.Alignment)(), C.POINTER(C.c_char)()
         abi.check(abi.lib().kaamer_batch_top_alignments(out, C.byref(items), C.byref(text)))
@@ -552,64 +561,96 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
-    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq"):
+    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None):
         """kaamer_search_text_top_flat: FASTQ text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFastq) and searched as search_top searches the packed batch.  TopResult.text_spans: name and sequence of
-        every record as offsets into `text`; rep_query / meta["src_seq"] index the records."""
+        every record as offsets into `text`; rep_query / meta["src_seq"] index the records.
+        tsv=dict(positions=..., annotations=...): kaamer_search_text_top_tsv_flat -- the TSV rows of the reported hits are
+        written on the device too (needs attach_subject_text): TopResult.tsv, .tsv_line_off."""
         data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
         out = C.POINTER(abi.BatchTop)()
-        abi.check(abi.lib().kaamer_search_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
-                                                        min_k_match, max_results, C.byref(out)))
+        if tsv is not None:
+            abi.check(abi.lib().kaamer_search_text_top_tsv_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
+                                                                min_k_match, max_results, *_tsv_args(tsv), C.byref(out)))
+        else:
+            abi.check(abi.lib().kaamer_search_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
+                                                            min_k_match, max_results, C.byref(out)))
         try:
             return TopResult(out)
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10):
+    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
         """kaamer_search_bgzf_top_flat: whole BGZF blocks of FASTQ (bytes) in, the reported hits out -- the compressed bytes
         are uploaded, inflated, parsed and searched on the device.  TopResult.text: the inflated text; text_spans index it.
-        Bytes that are not whole BGZF blocks: KaamerError E_ARG; a block that does not inflate: E_FORMAT."""
+        Bytes that are not whole BGZF blocks: KaamerError E_ARG; a block that does not inflate: E_FORMAT.
+        tsv: as search_text_top's (kaamer_search_bgzf_top_tsv_flat)."""
         data = bytes(data)
         out = C.POINTER(abi.BatchTop)()
-        abi.check(abi.lib().kaamer_search_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
+        if tsv is not None:
+            abi.check(abi.lib().kaamer_search_bgzf_top_tsv_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results,
+                                                                *_tsv_args(tsv), C.byref(out)))
+        else:
+            abi.check(abi.lib().kaamer_search_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results,
+                                                            C.byref(out)))
         try:
             return TopResult(out)
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10):
-        """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans)"""
+    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
+        """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans); tsv: as
+        search_text_top's (kaamer_submit_bgzf_top_tsv_flat)"""
         data = bytes(data)
         t = C.c_void_p()
+        if tsv is not None:
+            abi.check(abi.lib().kaamer_submit_bgzf_top_tsv_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results,
+                                                                *_tsv_args(tsv), C.byref(t)))
+            return TopTicket(t)
         abi.check(abi.lib().kaamer_submit_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
         return TopTicket(t)
 
-    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq"):
-        """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans)"""
+    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None):
+        """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv: as
+        search_text_top's (kaamer_submit_text_top_tsv_flat)"""
         data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
         t = C.c_void_p()
+        if tsv is not None:
+            abi.check(abi.lib().kaamer_submit_text_top_tsv_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
+                                                                min_k_match, max_results, *_tsv_args(tsv), C.byref(t)))
+            return TopTicket(t)
         abi.check(abi.lib().kaamer_submit_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
                                                         min_k_match, max_results, C.byref(t)))
         return TopTicket(t)
 
-    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10):
+    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
         """kaamer_search_fasta_top_flat: FASTA text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFasta) and searched as search_top searches the packed batch.  seq_type: PROTEIN, NUCLEOTIDE or READS
         (with a genetic code).  upper_last: more input follows this text, its last record is upper-cased too.
-        TopResult.text_spans: name and sequence range of every record as offsets into `text`."""
+        TopResult.text_spans: name and sequence range of every record as offsets into `text`.
+        tsv: as search_text_top's (kaamer_search_fasta_top_tsv_flat)."""
         data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
         out = C.POINTER(abi.BatchTop)()
-        abi.check(abi.lib().kaamer_search_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
-                                                         min_k_match, max_results, C.byref(out)))
+        if tsv is not None:
+            abi.check(abi.lib().kaamer_search_fasta_top_tsv_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
+                                                                 min_k_match, max_results, *_tsv_args(tsv), C.byref(out)))
+        else:
+            abi.check(abi.lib().kaamer_search_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
+                                                             min_k_match, max_results, C.byref(out)))
         try:
             return TopResult(out)
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10):
-        """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans)"""
+    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
+        """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv: as
+        search_text_top's (kaamer_submit_fasta_top_tsv_flat)"""
         data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
         t = C.c_void_p()
+        if tsv is not None:
+            abi.check(abi.lib().kaamer_submit_fasta_top_tsv_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
+                                                                 min_k_match, max_results, *_tsv_args(tsv), C.byref(t)))
+            return TopTicket(t)
         abi.check(abi.lib().kaamer_submit_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
                                                          min_k_match, max_results, C.byref(t)))
         return TopTicket(t)
@@ -623,6 +664,21 @@ class Index:
         subjects of search_top(align=...)).  The table is borrowed by the library: the index keeps it alive."""
         abi.check(abi.lib().kaamer_index_attach_proteins(self._h, proteins._h))
         self.proteins = proteins
+
+    def attach_subject_text(self, proteins):
+        """kaamer_index_attach_subject_text: EntryId, Length and the annotation columns of every entry become resident
+        next to the index: what the TSV rows print of a hit (search_*_top(tsv=...), TsvStage)."""
+        abi.check(abi.lib().kaamer_index_attach_subject_text(self._h, proteins._h))
+
+    def subject_text_info(self):
+        """kaamer_index_subject_text_info -> dict"""
+        out = (C.c_uint64 * 4)()
+        abi.check(abi.lib().kaamer_index_subject_text_info(self._h, out))
+        return dict(zip(("table_bytes", "entries", "max_row_suffix", "features"), (int(v) for v in out)))
+
+    def set_tsv_bounds(self, nbytes, lines):
+        """kaamer_index_set_tsv_bounds: the first bounds (bytes, rows) of the tsv=... calls on every slot; 0: the rule"""
+        abi.check(abi.lib().kaamer_index_set_tsv_bounds(self._h, int(nbytes), int(lines)))
 
     def align_info(self):
         """kaamer_index_align_info -> dict"""
@@ -921,6 +977,112 @@ class Replicas:
     def close(self):
         if self._h:
             abi.lib().kaamer_replicas_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _tsv_args(tsv):
+    """tsv=dict(positions=..., annotations=...) -> (extract_positions, annotations)"""
+    return int(bool(tsv.get("positions"))), int(bool(tsv.get("annotations")))
+
+
+def format_tsv_header(positions=False, annotations=False, proteins=None):
+    """kaamer_format_tsv_header: the header line of the TSV response (search.go:645-660, no alignment) -> bytes"""
+    ph = proteins._h if proteins is not None else None
+    need = int(abi.lib().kaamer_format_tsv_header(int(bool(positions)), int(bool(annotations)), ph, None, 0))
+    buf = C.create_string_buffer(need + 1)
+    abi.lib().kaamer_format_tsv_header(int(bool(positions)), int(bool(annotations)), ph, buf, need + 1)
+    return buf.raw[:need]
+
+
+def format_tsv(top, names, spans, proteins=None, positions=False, annotations=False, cap=None):
+    """kaamer_format_tsv_arrays on a TopResult (or any object with its arrays: n_reported, meta, top_off, top_pid, top_kmatch
+    and, with positions, pos_bits_len / pos_off / pos_bits): the TSV rows of the reported hits, formatted on the host
+    (search.go:505-554) -> (bytes, line_off u64[entries + 1]).  names: the bytes the records' names lie in (the text of a
+    text call); spans: SPAN_DTYPE, one per input record (TopResult.text_spans).  cap: format into a buffer of that many
+    bytes instead of one of the needed size -> (bytes written without the NUL, the needed length)."""
+    names = names.encode("latin-1") if isinstance(names, str) else bytes(names)
+    spans = np.ascontiguousarray(spans, SPAN_DTYPE)
+    r = int(top.n_reported)
+    meta = np.ascontiguousarray(top.meta, META_DTYPE)
+    off = np.ascontiguousarray(top.top_off, np.uint64)
+    pid = np.ascontiguousarray(top.top_pid, np.uint32)
+    km = np.ascontiguousarray(top.top_kmatch, np.uint32)
+    bt = abi.BatchTop()
+    bt.n_queries, bt.n_reported, bt.max_results = int(getattr(top, "n_queries", r)), r, int(getattr(top, "max_results", 0))
+    bt.q = C.cast(meta.ctypes.data, C.POINTER(abi.QueryMeta))
+    bt.top_off = C.cast(off.ctypes.data, C.POINTER(C.c_uint64))
+    bt.top_pid = C.cast(pid.ctypes.data, C.POINTER(C.c_uint32))
+    bt.top_kmatch = C.cast(km.ctypes.data, C.POINTER(C.c_uint32))
+    pl = po = pb = None
+    if positions and getattr(top, "pos_bits", None) is not None:
+        pl = np.ascontiguousarray(top.pos_bits_len, np.int32)
+        po = np.ascontiguousarray(top.pos_off, np.uint64)
+        pb = np.ascontiguousarray(top.pos_bits, np.uint64) if len(top.pos_bits) else np.zeros(1, np.uint64)
+    ne = int(off[r]) if r else 0
+    line_off = np.zeros(ne + 1, np.uint64)
+    ph = proteins._h if proteins is not None else None
+
+    def call(buf, n):
+        rc = int(abi.lib().kaamer_format_tsv_arrays(
+            C.byref(bt), pl.ctypes.data if pl is not None else None, po.ctypes.data if po is not None else None,
+            pb.ctypes.data if pb is not None else None, names, len(names), spans.ctypes.data if len(spans) else None, len(spans), ph,
+            int(bool(positions)), int(bool(annotations)), buf, n, line_off.ctypes.data))
+        if rc < 0:
+            abi.check(rc)
+        return rc
+    need = call(None, 0)
+    if cap is not None:
+        buf = C.create_string_buffer(max(int(cap), 1))
+        call(buf if cap else None, int(cap))
+        return (buf.raw[:min(need, int(cap) - 1)] if cap else b""), need
+    buf = C.create_string_buffer(need + 1)
+    call(buf, need + 1)
+    return buf.raw[:need], line_off
+
+
+def tsv_geometry():
+    """kaamer_tsv_geometry -> dict(tile, window, store, threads): queries per tile of the write pass, bytes per LDS window
+    (windows lie on multiples of it in the output), bytes a lane stores at once, threads per workgroup"""
+    g = (C.c_uint32 * 4)()
+    abi.lib().kaamer_tsv_geometry(g)
+    return dict(tile=int(g[0]), window=int(g[1]), store=int(g[2]), threads=int(g[3]))
+
+
+class TsvStage:
+    """kaamer_tsv_stage_*: the buffers of the device stage that writes the TSV rows, for up to max_queries queries and
+    max_lines rows (needs Index.attach_subject_text)"""
+
+    def __init__(self, index, max_queries, max_lines):
+        self.index = index
+        h = C.c_void_p()
+        abi.check(abi.lib().kaamer_tsv_stage_create(index._h, int(max_queries), int(max_lines), C.byref(h)))
+        self._h = h
+
+    def rows_device(self, rows_in, d_out_ptr, out_cap, stream=0):
+        """kaamer_tsv_rows_device (rows_in: abi.TsvRowsIn of raw device addresses) -> abi.TsvRowsResult"""
+        r = abi.TsvRowsResult()
+        abi.check(abi.lib().kaamer_tsv_rows_device(self._h, C.byref(rows_in), C.c_void_p(d_out_ptr), int(out_cap), C.c_void_p(stream), C.byref(r)))
+        return r
+
+    def finish(self, stream=0):
+        """kaamer_tsv_rows_finish -> (rows, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did not fit"""
+        c = (C.c_uint64 * 2)()
+        rc = abi.lib().kaamer_tsv_rows_finish(self._h, C.c_void_p(stream), c)
+        if rc:
+            e = abi.KaamerError(rc, (abi.lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
+            e.counts = (int(c[0]), int(c[1]))
+            raise e
+        return int(c[0]), int(c[1])
+
+    def close(self):
+        if self._h:
+            abi.lib().kaamer_tsv_stage_free(self._h)
             self._h = None
 
     def __del__(self):

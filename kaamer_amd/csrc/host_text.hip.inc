@@ -117,13 +117,18 @@ static int bgzf_inflate_to_slot(TopSlot &h, const BgzfInput &bz, uint64_t text_l
 // FASTA text as the input of a text call (kaamer_submit_fasta_top_flat, kaamer_search_fasta_file): the `format` of
 // text_submit is then not looked at, and PROTEIN is as good a sequence type as the other two
 struct FastaInput { bool upper_last; };
+// the TSV rows of the reported hits as part of a text call (the *_tsv_flat calls, host_tsv.hip.inc)
+struct TsvRequest { bool positions, annotations; };
 
 static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, const kaamer_topn_opts *top,
-                       bool blocking, kaamer_ticket **out, const BgzfInput *bz = nullptr, const FastaInput *fa = nullptr)
+                       bool blocking, kaamer_ticket **out, const BgzfInput *bz = nullptr, const FastaInput *fa = nullptr,
+                       const TsvRequest *tsv = nullptr)
 {
     const char *who = fa ? "submit_fasta_top" : "submit_text_top";
     if (!ix || !top || !out || (!text && len && !bz) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "%s: bad argument", who);
     *out = nullptr;
+    if (tsv && !ix->d_st_bytes)
+        return kaamer_fail(KAAMER_E_ARG, "%s: TSV rows need the subject text on the device (kaamer_index_attach_subject_text)", who);
     if (!fa) {
         if (format == 0)
             return kaamer_fail(KAAMER_E_ARG, "submit_text_top: FASTA is not parsed on the device by this call: use kaamer_submit_fasta_top_flat, or the host reader "
@@ -145,6 +150,7 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
     if (!t) { top_slot_release(ix, slot); return kaamer_fail(KAAMER_E_NOMEM, "ticket"); }
     memset(t, 0, sizeof *t);
     t->ix = ix; t->slot = slot; t->seq_type = seq_type; t->top = *top; t->text = true;
+    if (tsv) { t->want_tsv = true; t->tsv_pos = tsv->positions; t->tsv_ann = tsv->annotations; t->want_pos = tsv->positions; }
     TopSlot &h = ix->top[slot];
     int rc = KAAMER_OK;
     hipError_t he = hipSetDevice(ix->device);
@@ -205,6 +211,7 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
     if (!rc) {
         t->n_seqs = pr.n_records; t->seq_bytes = pr.seq_bytes;
         t->d_text_seqs = pr.d_seqs; t->d_text_off = pr.d_offsets;
+        t->d_names = h.d_text; t->names_len = len; t->d_spans = pr.d_spans;
         t->h_spans = (kaamer_text_span *)pinned_get(((size_t)pr.n_records + 1) * sizeof(kaamer_text_span), &t->h_spans_cap);
         if (!t->h_spans) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned spans (%u records)", pr.n_records);
     }
@@ -227,6 +234,7 @@ static int text_submit(kaamer_index *ix, const char *text, uint64_t len, int32_t
         if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
         if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
         if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
+        if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
         delete t;
         top_slot_release(ix, slot);
         return rc;
@@ -275,8 +283,8 @@ int kaamer_search_fasta_top_flat(kaamer_index *ix, const char *text, uint64_t le
 }
 
 // whole BGZF blocks: scanned on the host (no inflate), inflated, parsed and searched on the slot's stream
-int kaamer_submit_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
-                                uint32_t max_results, kaamer_ticket **ticket)
+static int bgzf_submit(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                       uint32_t max_results, kaamer_ticket **ticket, const TsvRequest *tsv)
 {
     if (ticket) *ticket = nullptr;
     if (!ix || !ticket || (!bytes && len)) return kaamer_fail(KAAMER_E_ARG, "submit_bgzf_top: bad argument");
@@ -297,7 +305,13 @@ int kaamer_submit_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t
     kaamer_topn_opts top;
     flat_top(&top, min_k_ratio, min_k_match, max_results);
     const BgzfInput bz = { bytes, len, &blocks };
-    return text_submit(ix, nullptr, text_len, 1, seq_type, &top, true, ticket, &bz);
+    return text_submit(ix, nullptr, text_len, 1, seq_type, &top, true, ticket, &bz, nullptr, tsv);
+}
+
+int kaamer_submit_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                uint32_t max_results, kaamer_ticket **ticket)
+{
+    return bgzf_submit(ix, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, ticket, nullptr);
 }
 
 int kaamer_search_bgzf_top_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,

@@ -35,6 +35,11 @@ struct batch_top_owner {
     char *text = nullptr;
     size_t text_cap = 0;
     uint64_t text_len = 0;
+    // the TSV rows of a *_tsv_flat call (host_tsv.hip.inc), pinned: line_off[tsv_lines + 1], then the text
+    uint8_t *tsv = nullptr;
+    size_t tsv_cap = 0;
+    uint64_t tsv_lines = 0, tsv_len = 0;
+    const char *tsv_text = nullptr;
 };
 
 // the alignment half of a request (kaamer_*_batch_top_aln_flat)
@@ -88,7 +93,19 @@ struct kaamer_ticket {
     char *h_text_out;            // a BGZF call: the inflated text, pinned; goes to the result
     size_t h_text_out_cap;
     uint64_t text_len;
+    // a call that returns the TSV rows (host_tsv.hip.inc; text calls only): the request, the names on the device, the bounds
+    // of this attempt (0: the slot's guess) and the pinned buffer that goes to the result
+    bool want_tsv, tsv_pos, tsv_ann;
+    const uint8_t *d_names;
+    uint64_t names_len;
+    const kaamer_text_span *d_spans;
+    uint64_t tsv_bytes_cap, tsv_lines_cap;
+    uint8_t *h_tsv;
+    size_t h_tsv_cap;
 };
+static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
+static int tsv_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
+static void tsv_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
 static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h);
@@ -242,6 +259,8 @@ static void top_slot_free(TopSlot &h)
     if (h.inflater) kaamer_inflater_free(h.inflater);
     if (h.h_comp) (void)hipHostFree(h.h_comp);
     if (h.d_comp) (void)hipFree(h.d_comp);
+    if (h.tsv) kaamer_tsv_stage_free(h.tsv);
+    if (h.d_tsv) (void)hipFree(h.d_tsv);
     if (h.stream) (void)hipStreamDestroy(h.stream);
     h = TopSlot();
 }
@@ -354,6 +373,7 @@ static int top_enqueue(kaamer_ticket *t)
     if (!rc) rc = topn_pack_block(h.ws, h.ws, 0u, 1u, &tr, s, h.d_block, h.block_use);
     if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
     if (!rc && aligns) rc = top_enqueue_alignments(t, h, &tr, s);
+    if (!rc && t->want_tsv) rc = top_enqueue_tsv(t, h, &tr, s);
     if (rc) return rc;
     return rep_block_copy_guess(h.d_block, h.block_use, h.guess, &t->h_block, &t->h_block_cap, &t->copied, s);
 }
@@ -467,6 +487,13 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
             rc = top_enqueue(t);
             continue;
         }
+        if (t->want_tsv && tsv_needs_repeat(t, h, &rc)) {   // the rows' bounds were too small: once more, with what they needed
+            if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "TSV rows of the result"); break; }
+            t->attempt++;
+            rc = top_enqueue(t);
+            continue;
+        }
+        if (rc) break;
         rc = rep_block_fetch_rest(h.d_block, &h.guess, &t->h_block, &t->h_block_cap, &t->copied, h.stream);
         break;
     }
@@ -484,6 +511,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         bo->has_pos = t->want_pos;
         if (t->text) { bo->spans = t->h_spans; bo->spans_cap = t->h_spans_cap; bo->n_spans = t->n_seqs; t->h_spans = nullptr; }
         if (t->h_text_out) { bo->text = t->h_text_out; bo->text_cap = t->h_text_out_cap; bo->text_len = t->text_len; t->h_text_out = nullptr; }
+        if (t->want_tsv) tsv_finish_host(t, h, bo);
         if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
         if (!nucl) bo->pub.orf_aa = nullptr;
         if (!rc) *out = &bo->pub;
@@ -492,6 +520,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
     if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
     if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
+    if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
     top_slot_release(ix, t->slot);
     delete t;
     return rc;
@@ -510,6 +539,7 @@ void kaamer_ticket_discard(kaamer_ticket *t)
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
     if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
     if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
+    if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
     top_slot_release(ix, t->slot);
     delete t;
 }
@@ -627,6 +657,7 @@ void kaamer_batch_top_free(kaamer_batch_top *out)
     if (bo->block) { if (bo->pinned) pinned_put(bo->block, bo->block_cap); else free(bo->block); }
     if (bo->spans) pinned_put(bo->spans, bo->spans_cap);
     if (bo->text) pinned_put(bo->text, bo->text_cap);
+    if (bo->tsv) pinned_put(bo->tsv, bo->tsv_cap);
     delete bo;
 }
 

@@ -1,0 +1,371 @@
+// host_tsv.hip.inc — the host side of the TSV response rows (included by search.hip inside its extern "C" block, after
+// host_text.hip.inc; the kernels are in tsv_rows.hip.inc, the contract and the host formatter in tsv_format.cpp):
+//   kaamer_index_attach_subject_text  EntryId, Length and the annotation columns of every entry, resident next to the index
+//   kaamer_tsv_stage_* / kaamer_tsv_rows_device / kaamer_tsv_rows_finish   the stage on a stream
+//   kaamer_format_tsv                 the host formatter on a result of this library (its bitmaps come from the result)
+//   kaamer_*_top_tsv_flat             the text, FASTA and BGZF calls with the rows in the result; kaamer_batch_top_tsv
+
+int kaamer_index_attach_subject_text(kaamer_index *ix, const kaamer_proteins *p)
+{
+    if (!ix || !p) return kaamer_fail(KAAMER_E_ARG, "index_attach_subject_text: bad argument");
+    HIPCHK(hipSetDevice(ix->device));
+    std::vector<uint32_t> uniq;
+    std::vector<kaamer_protein_entry> ent;
+    int rc = proteins_distinct(p, uniq, ent);   // the entry order of kaamer_index_attach_proteins: one map serves both
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)uniq.size(), nf = kaamer_proteins_n_features(p);
+    const uint64_t map_n = n ? (uint64_t)uniq.back() + 1 : 0;
+    if (map_n > (1ull << 31)) return kaamer_fail(KAAMER_E_ARG, "index_attach_subject_text: protein ids up to %llu: the id map is dense", (unsigned long long)map_n);
+    std::vector<uint64_t> off((size_t)n + 1, 0);
+    std::vector<uint32_t> idlen((size_t)n + 1, 0), length((size_t)n + 1, 0);
+    std::vector<uint8_t> bytes;
+    uint64_t max_suffix = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const kaamer_protein_entry &e = ent[i];
+        off[i] = bytes.size();
+        idlen[i] = e.entry_id_len;
+        length[i] = e.length;
+        bytes.insert(bytes.end(), e.entry_id, e.entry_id + e.entry_id_len);
+        for (uint32_t f = 0; f < nf; f++) {   // '\t' + value per KStats.Features name: the device only copies bytes
+            bytes.push_back((uint8_t)'\t');
+            if (f < e.n_features) bytes.insert(bytes.end(), e.features + e.feature_off[f], e.features + e.feature_off[f + 1]);
+        }
+        uint64_t digits = 1;
+        for (uint32_t v = e.length; v >= 10; v /= 10) digits++;
+        const uint64_t suffix = bytes.size() - off[i] + digits;
+        if (suffix > max_suffix) max_suffix = suffix;
+    }
+    off[n] = bytes.size();
+    {   // nothing of the index may be running: the slots' streams are idle when no slot is busy
+        std::lock_guard<std::mutex> lock(ix->pool_mu);
+        for (int i = 0; i < ix->n_top; i++)
+            if (ix->top[i].busy) return kaamer_fail(KAAMER_E_BUSY, "index_attach_subject_text: calls are in flight on the index");
+    }
+    HIPCHK(hipDeviceSynchronize());
+    subject_text_free(ix);   // a second attach replaces the first
+    const bool share = ix->d_aln_idmap && ix->aln_host == p && ix->aln_entries == n && ix->aln_idmap_n == (uint32_t)map_n;
+    std::vector<uint32_t> idmap;
+    rc = dev_alloc(&ix->d_st_bytes, bytes.size() + 1);
+    if (!rc) rc = dev_alloc(&ix->d_st_off, off.size());
+    if (!rc) rc = dev_alloc(&ix->d_st_idlen, idlen.size());
+    if (!rc) rc = dev_alloc(&ix->d_st_length, length.size());
+    if (!rc && !share) {
+        idmap.assign((size_t)map_n + 1, TSV_NONE);
+        for (uint32_t i = 0; i < n; i++) idmap[uniq[i]] = i;
+        rc = dev_alloc(&ix->d_st_idmap, idmap.size());
+    }
+    if (rc) { subject_text_free(ix); return rc; }
+    hipError_t e = bytes.empty() ? hipSuccess : hipMemcpy(ix->d_st_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_st_off, off.data(), off.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_st_idlen, idlen.data(), idlen.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_st_length, length.data(), length.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !share) e = hipMemcpy(ix->d_st_idmap, idmap.data(), idmap.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { subject_text_free(ix); return kaamer_fail(KAAMER_E_HIP, "subject text upload: %s", hipGetErrorString(e)); }
+    if (share) { ix->d_st_idmap = ix->d_aln_idmap; ix->st_idmap_shared = true; }
+    ix->st_idmap_n = (uint32_t)map_n; ix->st_entries = n; ix->st_features = nf;
+    ix->st_max_suffix = max_suffix;
+    ix->st_bytes = bytes.size() + 1 + off.size() * 8 + idlen.size() * 4 + length.size() * 4 + (share ? 0 : idmap.size() * 4);
+    return KAAMER_OK;
+}
+
+int kaamer_index_subject_text_info(const kaamer_index *ix, uint64_t out[4])
+{
+    if (!ix || !out) return kaamer_fail(KAAMER_E_ARG, "index_subject_text_info: bad argument");
+    out[0] = ix->st_bytes; out[1] = ix->st_entries; out[2] = ix->st_max_suffix; out[3] = ix->st_features;
+    return KAAMER_OK;
+}
+
+void kaamer_tsv_geometry(uint32_t out[4])
+{
+    out[0] = TSV_TILE; out[1] = TSV_WINDOW; out[2] = 16; out[3] = TSV_TILE;
+}
+
+struct kaamer_tsv_stage {
+    kaamer_index *ix = nullptr;
+    uint32_t max_queries = 0;
+    uint64_t max_lines = 0;
+    unsigned long long *d_tile_bytes = nullptr, *d_tile_lines = nullptr, *d_line_off = nullptr, *d_counts = nullptr;
+    unsigned long long *h_counts = nullptr;   // pinned
+    uint64_t out_cap = 0;                     // of the last call
+};
+
+void kaamer_tsv_stage_free(kaamer_tsv_stage *st)
+{
+    if (!st) return;
+    if (st->ix) (void)hipSetDevice(st->ix->device);
+    void *bufs[] = { st->d_tile_bytes, st->d_tile_lines, st->d_line_off, st->d_counts };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    if (st->h_counts) (void)hipHostFree(st->h_counts);
+    delete st;
+}
+
+int kaamer_tsv_stage_create(kaamer_index *ix, uint32_t max_queries, uint64_t max_lines, kaamer_tsv_stage **out)
+{
+    if (!ix || !out) return kaamer_fail(KAAMER_E_ARG, "tsv_stage_create: bad argument");
+    *out = nullptr;
+    HIPCHK(hipSetDevice(ix->device));
+    kaamer_tsv_stage *st = new (std::nothrow) kaamer_tsv_stage();
+    if (!st) return kaamer_fail(KAAMER_E_NOMEM, "tsv stage");
+    st->ix = ix; st->max_queries = max_queries; st->max_lines = max_lines;
+    const size_t tiles = (size_t)max_queries / TSV_TILE + 1;
+    int rc = dev_alloc(&st->d_tile_bytes, tiles);
+    if (!rc) rc = dev_alloc(&st->d_tile_lines, tiles);
+    if (!rc) rc = dev_alloc(&st->d_line_off, (size_t)max_lines + 1);
+    if (!rc) rc = dev_alloc(&st->d_counts, (size_t)TSV_C_N);
+    if (!rc && hipHostMalloc((void **)&st->h_counts, TSV_C_N * 8, hipHostMallocDefault) != hipSuccess) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned tsv counts");
+    if (rc) { kaamer_tsv_stage_free(st); return rc; }
+    *out = st;
+    return KAAMER_OK;
+}
+
+// the four launches and the copy of the counts; d_line_off / line_cap: where the line offsets go; block: the packed
+// result block of the same batch (the host-buffer calls), see TsvParams
+static int tsv_enqueue(kaamer_tsv_stage *st, const kaamer_tsv_rows_in *in, char *d_out, uint64_t out_cap, unsigned long long *d_line_off,
+                       uint64_t line_cap, hipStream_t s, const uint8_t *block = nullptr)
+{
+    const kaamer_index *ix = st->ix;
+    if (!ix->d_st_bytes) return kaamer_fail(KAAMER_E_ARG, "tsv_rows: no subject text is attached to the index (kaamer_index_attach_subject_text)");
+    if (!in || !in->d_n_queries || !in->d_q || !in->top.d_top_cnt || !in->top.d_top_pid || !in->top.d_top_kmatch || !in->top.d_start_position ||
+        !in->top.d_size_in_kmer || in->top.max_results < 1 || (in->n_names && (!in->d_spans || !in->d_name_bytes)) || (!d_out && out_cap) ||
+        ((uintptr_t)d_out & 15u) || line_cap < 1)
+        return kaamer_fail(KAAMER_E_ARG, "tsv_rows: bad argument");
+    if (in->extract_positions && (!in->pos || !in->pos->d_pos_base || !in->pos->d_pos_bits_len || !in->pos->d_pos_bits))
+        return kaamer_fail(KAAMER_E_ARG, "tsv_rows: ExtractPositions without the bitmaps of the reported hits (kaamer_topn_positions_device)");
+    if (in->n_queries_cap > st->max_queries) return kaamer_fail(KAAMER_E_ARG, "tsv_rows: %u queries, the stage holds %u", in->n_queries_cap, st->max_queries);
+    TsvParams p;
+    memset(&p, 0, sizeof p);
+    p.d_nq = in->d_n_queries; p.nq_cap = in->n_queries_cap; p.q = in->d_q;
+    p.top_cnt = in->top.d_top_cnt; p.top_pid = in->top.d_top_pid; p.top_km = in->top.d_top_kmatch;
+    p.start_pos = in->top.d_start_position; p.size_out = in->top.d_size_in_kmer; p.K = in->top.max_results;
+    p.names = in->d_name_bytes; p.names_len = in->name_bytes_len; p.spans = in->d_spans; p.n_names = in->n_names;
+    p.positions = in->extract_positions ? 1 : 0; p.annotations = in->annotations ? 1 : 0;
+    if (p.positions) { p.pos_base = in->pos->d_pos_base; p.pos_len = in->pos->d_pos_bits_len; p.pos_bits = in->pos->d_pos_bits; }
+    p.st_bytes = ix->d_st_bytes; p.st_off = ix->d_st_off; p.st_idlen = ix->d_st_idlen; p.st_length = ix->d_st_length;
+    p.idmap = ix->d_st_idmap; p.idmap_n = ix->st_idmap_n; p.n_features = ix->st_features;
+    p.tile_bytes = st->d_tile_bytes; p.tile_lines = st->d_tile_lines;
+    p.line_off = d_line_off; p.line_cap = line_cap;
+    p.out = d_out; p.out_cap = out_cap;
+    p.counts = st->d_counts;
+    p.block = block;
+    st->out_cap = out_cap;
+    const uint32_t tiles = in->n_queries_cap / TSV_TILE + 1;
+    hipLaunchKernelGGL(tsv_len_kernel, dim3(tiles), dim3(TSV_TILE), 0, s, p);
+    hipLaunchKernelGGL(tsv_scan_kernel, dim3(1), dim3(TSV_TILE), 0, s, p);
+    hipLaunchKernelGGL(tsv_off_kernel, dim3(tiles), dim3(TSV_TILE), 0, s, p);
+    hipLaunchKernelGGL(tsv_write_kernel, dim3(tiles), dim3(TSV_TILE), 0, s, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(st->h_counts, st->d_counts, TSV_C_N * 8, hipMemcpyDeviceToHost, s));
+    return KAAMER_OK;
+}
+
+int kaamer_tsv_rows_device(kaamer_tsv_stage *st, const kaamer_tsv_rows_in *in, char *d_out, uint64_t out_cap, void *stream,
+                           kaamer_tsv_rows_result *out)
+{
+    if (!st || !out) return kaamer_fail(KAAMER_E_ARG, "tsv_rows_device: bad argument");
+    memset(out, 0, sizeof *out);
+    HIPCHK(hipSetDevice(st->ix->device));
+    const int rc = tsv_enqueue(st, in, d_out, out_cap, st->d_line_off, st->max_lines + 1, (hipStream_t)stream);
+    if (rc) return rc;
+    out->d_line_off = reinterpret_cast<const uint64_t *>(st->d_line_off);
+    out->d_counts = reinterpret_cast<const uint64_t *>(st->d_counts);
+    out->line_off_capacity = st->max_lines + 1;
+    return KAAMER_OK;
+}
+
+// the counts of the last enqueue, once its stream is done
+static int tsv_counts(const kaamer_tsv_stage *st, uint64_t counts[2])
+{
+    if (counts) { counts[0] = st->h_counts[TSV_C_LINES]; counts[1] = st->h_counts[TSV_C_BYTES]; }
+    const unsigned long long status = st->h_counts[TSV_C_STATUS];
+    if (status)
+        return kaamer_fail(KAAMER_E_CAPACITY, "tsv_rows: %llu rows of %llu bytes do not fit (%llu bytes, %llu rows)", st->h_counts[TSV_C_LINES],
+                           st->h_counts[TSV_C_BYTES], (unsigned long long)st->out_cap, (unsigned long long)st->max_lines);
+    return KAAMER_OK;
+}
+
+int kaamer_tsv_rows_finish(kaamer_tsv_stage *st, void *stream, uint64_t counts[2])
+{
+    if (!st) return kaamer_fail(KAAMER_E_ARG, "tsv_rows_finish: bad argument");
+    HIPCHK(hipSetDevice(st->ix->device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    return tsv_counts(st, counts);
+}
+
+int64_t kaamer_format_tsv(const kaamer_batch_top *top, const char *name_bytes, uint64_t name_bytes_len, const kaamer_text_span *name_spans,
+                          uint32_t n_names, const kaamer_proteins *proteins, int32_t extract_positions, int32_t annotations, char *buf, uint64_t cap,
+                          uint64_t *line_off)
+{
+    if (!top) return kaamer_fail(KAAMER_E_ARG, "format_tsv: bad argument");
+    const int32_t *len = nullptr;
+    const uint64_t *off = nullptr, *bits = nullptr;
+    if (extract_positions) {
+        const int rc = kaamer_batch_top_positions(top, &len, &off, &bits);
+        if (rc) return rc;
+    }
+    return kaamer_format_tsv_arrays(top, len, off, bits, name_bytes, name_bytes_len, name_spans, n_names, proteins, extract_positions, annotations,
+                                    buf, cap, line_off);
+}
+
+// ---- the rows as part of a text call (kaamer_*_top_tsv_flat): behind the packed block on the slot's stream ----------------
+// The rows and their line offsets have a buffer of their own next to the block (the block's format is unchanged): one
+// more device-to-host copy per call.  Both bounds -- bytes and rows -- start from what the slot's previous call needed plus
+// a quarter; a batch beyond them reports how much it needs, and is repeated from the parsed buffers with exactly that.
+
+static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s)
+{
+    kaamer_index *ix = t->ix;
+    const uint64_t hard_lines = (uint64_t)h.ws->q_cap * tr->max_results;
+    uint64_t lines = t->tsv_lines_cap ? t->tsv_lines_cap : (h.tsv_guess_lines ? h.tsv_guess_lines : (uint64_t)t->n_seqs + 1024);
+    if (lines > hard_lines) lines = hard_lines;
+    const uint64_t bytes = t->tsv_bytes_cap ? t->tsv_bytes_cap : (h.tsv_guess_bytes ? h.tsv_guess_bytes : lines * 64);
+    t->tsv_lines_cap = lines; t->tsv_bytes_cap = bytes;
+    if (!h.tsv || h.tsv_queries < h.ws->q_cap || h.tsv_lines < lines) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (h.tsv) kaamer_tsv_stage_free(h.tsv);
+        h.tsv = nullptr;
+        const int rc = kaamer_tsv_stage_create(ix, h.ws->q_cap, lines, &h.tsv);
+        if (rc) { h.tsv = nullptr; return rc; }
+        h.tsv_queries = h.ws->q_cap; h.tsv_lines = lines;
+    }
+    if (h.d_tsv_cap < bytes) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (h.d_tsv) (void)hipFree(h.d_tsv);
+        h.d_tsv = nullptr; h.d_tsv_cap = 0;
+        const int rc = dev_alloc(&h.d_tsv, (size_t)bytes + 16);
+        if (rc) return rc;
+        h.d_tsv_cap = (size_t)bytes;
+    }
+    const size_t off_bytes = ((size_t)lines + 1) * 8, need = off_bytes + (size_t)bytes;
+    if (t->h_tsv_cap < need) {
+        if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
+        t->h_tsv = (uint8_t *)pinned_get(need, &t->h_tsv_cap);
+        if (!t->h_tsv) { t->h_tsv_cap = 0; return kaamer_fail(KAAMER_E_NOMEM, "pinned TSV rows (%zu bytes)", need); }
+    }
+    kaamer_tsv_rows_in in;
+    memset(&in, 0, sizeof in);
+    in.top = *tr;
+    in.d_q = h.ws->d_q; in.d_n_queries = h.ws->d_nq; in.n_queries_cap = h.ws->q_cap;
+    in.n_names = t->n_seqs; in.d_name_bytes = t->d_names; in.name_bytes_len = t->names_len; in.d_spans = t->d_spans;
+    kaamer_topn_positions pos;
+    memset(&pos, 0, sizeof pos);
+    if (t->tsv_pos) {   // the bitmaps are in the block (topn_pack_positions); the per-query layout is the workspace's
+        pos.d_pos_base = h.ws->d_tp_base; pos.d_pos_bits_len = h.ws->d_tp_len;
+        pos.d_pos_bits = reinterpret_cast<const uint64_t *>(h.d_block);   // (replaced on the device by the block's section)
+        in.pos = &pos;
+    }
+    in.extract_positions = t->tsv_pos; in.annotations = t->tsv_ann;
+    int rc = tsv_enqueue(h.tsv, &in, h.d_tsv, bytes, h.tsv->d_line_off, lines + 1, s, h.d_block);
+    if (rc) return rc;
+    // the bounds are what the previous call needed plus a quarter: all of both goes home with the block
+    HIPCHK(hipMemcpyAsync(t->h_tsv, h.tsv->d_line_off, off_bytes, hipMemcpyDeviceToHost, s));
+    if (bytes) HIPCHK(hipMemcpyAsync(t->h_tsv + off_bytes, h.d_tsv, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    return KAAMER_OK;
+}
+
+// after the stream is done and the block was fine: 1 when the rows did not fit (the ticket's bounds are then what they need)
+static int tsv_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc)
+{
+    const unsigned long long status = h.tsv->h_counts[TSV_C_STATUS], lines = h.tsv->h_counts[TSV_C_LINES], bytes = h.tsv->h_counts[TSV_C_BYTES];
+    if (status & TSV_ST_UPSTREAM) { *rc = kaamer_fail(KAAMER_E_HIP, "tsv rows: the block carries no bitmaps"); return 0; }
+    if (!status) return 0;
+    t->tsv_lines_cap = lines + 1; t->tsv_bytes_cap = bytes + 16;
+    return 1;
+}
+
+static void tsv_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo)
+{
+    const uint64_t lines = h.tsv->h_counts[TSV_C_LINES], bytes = h.tsv->h_counts[TSV_C_BYTES];
+    h.tsv_guess_lines = lines + lines / 4 + 64; h.tsv_guess_bytes = bytes + bytes / 4 + 4096;
+    bo->tsv = t->h_tsv; bo->tsv_cap = t->h_tsv_cap;
+    bo->tsv_lines = lines; bo->tsv_len = bytes;
+    bo->tsv_text = reinterpret_cast<const char *>(t->h_tsv + ((size_t)t->tsv_lines_cap + 1) * 8);
+    t->h_tsv = nullptr;
+}
+
+int kaamer_batch_top_tsv(const kaamer_batch_top *out, const char **text, uint64_t *len, const uint64_t **line_off)
+{
+    if (text) *text = nullptr;
+    if (len) *len = 0;
+    if (line_off) *line_off = nullptr;
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_tsv: bad argument");
+    const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
+    if (!bo->tsv) return KAAMER_OK;   // any other call: format the rows on the host (kaamer_format_tsv)
+    if (text) *text = bo->tsv_text;
+    if (len) *len = bo->tsv_len;
+    if (line_off) *line_off = reinterpret_cast<const uint64_t *>(bo->tsv);
+    return KAAMER_OK;
+}
+
+int kaamer_submit_text_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                    int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                    kaamer_ticket **ticket)
+{
+    kaamer_topn_opts top;
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    const TsvRequest rq = { extract_positions != 0, annotations != 0 };
+    return text_submit(ix, text, len, format, seq_type, &top, true, ticket, nullptr, nullptr, &rq);
+}
+
+int kaamer_search_text_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                    int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                    kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_text_top_tsv_flat(ix, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, extract_positions,
+                                                   annotations, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+int kaamer_submit_fasta_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                     kaamer_ticket **ticket)
+{
+    kaamer_topn_opts top;
+    flat_top(&top, min_k_ratio, min_k_match, max_results);
+    const FastaInput fa = { upper_last != 0 };
+    const TsvRequest rq = { extract_positions != 0, annotations != 0 };
+    return text_submit(ix, text, len, 0, seq_type, &top, true, ticket, nullptr, &fa, &rq);
+}
+
+int kaamer_search_fasta_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                     kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_fasta_top_tsv_flat(ix, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, extract_positions,
+                                                    annotations, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+int kaamer_submit_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                    uint32_t max_results, int32_t extract_positions, int32_t annotations, kaamer_ticket **ticket)
+{
+    const TsvRequest rq = { extract_positions != 0, annotations != 0 };
+    return bgzf_submit(ix, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, ticket, &rq);
+}
+
+int kaamer_search_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                    uint32_t max_results, int32_t extract_positions, int32_t annotations, kaamer_batch_top **out)
+{
+    if (out) *out = nullptr;
+    kaamer_ticket *t = nullptr;
+    const int rc = kaamer_submit_bgzf_top_tsv_flat(ix, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, annotations, &t);
+    if (rc) return rc;
+    return kaamer_wait_batch_top(t, out);
+}
+
+// the first bounds of the rows on a slot that has not run a TSV call yet (tests: a first bound too small); 0: the rule
+int kaamer_index_set_tsv_bounds(kaamer_index *ix, uint64_t bytes, uint64_t lines)
+{
+    if (!ix) return kaamer_fail(KAAMER_E_ARG, "index_set_tsv_bounds: bad argument");
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    for (int i = 0; i < ix->n_top; i++) {
+        if (ix->top[i].busy) return kaamer_fail(KAAMER_E_BUSY, "index_set_tsv_bounds: calls are in flight on the index");
+        ix->top[i].tsv_guess_bytes = bytes; ix->top[i].tsv_guess_lines = lines;
+    }
+    return KAAMER_OK;
+}

@@ -164,6 +164,14 @@ struct TopSlot {
     uint32_t inflater_blocks = 0;
     uint8_t *h_comp = nullptr, *d_comp = nullptr;
     size_t h_comp_cap = 0, d_comp_cap = 0;
+    // the calls that return TSV rows (host_tsv.hip.inc), allocated at the slot's first one: the stage and the rows' buffer.
+    // Both bounds start from what the previous call needed, plus a quarter.
+    kaamer_tsv_stage *tsv = nullptr;
+    uint32_t tsv_queries = 0;       // the bounds the stage was created for
+    uint64_t tsv_lines = 0;
+    char *d_tsv = nullptr;
+    size_t d_tsv_cap = 0;
+    uint64_t tsv_guess_bytes = 0, tsv_guess_lines = 0;
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
@@ -194,6 +202,15 @@ struct kaamer_index {
     uint64_t aln_bytes = 0, aln_number_of_aa = 0;
     uint64_t aln_budget = 0;                     // kaamer_index_set_align_budget (0: the default)
     uint64_t aln_last[3] = {0, 0, 0};            // the last stage: resident waves, slab bytes, long waves
+    // kaamer_index_attach_subject_text: what a TSV row prints of a hit's entry (tsv_rows.hip.inc).  Entry i is
+    // d_st_bytes[d_st_off[i], d_st_off[i + 1]): EntryId (d_st_idlen[i] bytes), then the annotation columns.  The id map is
+    // the alignment table's while st_idmap_shared (same table, same entry order), else owned here.
+    uint8_t *d_st_bytes = nullptr;
+    uint64_t *d_st_off = nullptr;
+    uint32_t *d_st_idlen = nullptr, *d_st_length = nullptr, *d_st_idmap = nullptr;
+    bool st_idmap_shared = false;
+    uint32_t st_idmap_n = 0, st_entries = 0, st_features = 0;
+    uint64_t st_bytes = 0, st_max_suffix = 0;
 };
 
 enum { ST_POOL_FULL = 1u, ST_LIST_FULL = 2u, ST_QUERY_CAP = 4u, ST_AA_CAP = 8u, ST_G_ARENA_FULL = 16u, ST_G_TABLE_FULL = 32u,
@@ -639,6 +656,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
 #include "topn.hip.inc"
 #include "top_positions.hip.inc"
 #include "top_align.hip.inc"
+#include "tsv_rows.hip.inc"
 
 // ------------------------------------------------------------------------------------
 // exclusive scan of q_cnt[0..nq) -> hit_off[0..nq]
@@ -1104,10 +1122,22 @@ template <class T> static int ta_grow(T **buf, uint64_t *cap, uint64_t need, hip
 // the device copy of the attached Protein.Sequence table (kaamer_index_attach_proteins)
 static void aln_table_free(kaamer_index *ix)
 {
+    // (a subject text that shares the id map keeps it: it is the owner from here on)
+    if (ix->st_idmap_shared) { ix->st_idmap_shared = false; ix->d_aln_idmap = nullptr; }
     void *bufs[] = { ix->d_aln_raw, ix->d_aln_codes, ix->d_aln_bad, ix->d_aln_off, ix->d_aln_idmap, ix->d_aln_matrix };
     for (void *b : bufs) if (b) (void)hipFree(b);
     ix->d_aln_raw = ix->d_aln_codes = ix->d_aln_bad = nullptr; ix->d_aln_off = nullptr; ix->d_aln_idmap = nullptr; ix->d_aln_matrix = nullptr;
     ix->aln_host = nullptr; ix->aln_idmap_n = ix->aln_entries = ix->aln_max_ns = 0; ix->aln_bytes = ix->aln_number_of_aa = 0;
+}
+
+// the device copy of the attached subject text (kaamer_index_attach_subject_text)
+static void subject_text_free(kaamer_index *ix)
+{
+    void *bufs[] = { ix->d_st_bytes, ix->d_st_off, ix->d_st_idlen, ix->d_st_length, ix->st_idmap_shared ? nullptr : ix->d_st_idmap };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    ix->d_st_bytes = nullptr; ix->d_st_off = nullptr; ix->d_st_idlen = ix->d_st_length = ix->d_st_idmap = nullptr;
+    ix->st_idmap_shared = false;
+    ix->st_idmap_n = ix->st_entries = ix->st_features = 0; ix->st_bytes = ix->st_max_suffix = 0;
 }
 
 #include "parse_text.hip.inc"
@@ -1225,6 +1255,7 @@ void kaamer_index_close(kaamer_index *ix)
     if (ix->d_buckets) (void)hipFree(ix->d_buckets);
     if (ix->d_arena) (void)hipFree(ix->d_arena);
     aln_table_free(ix);
+    subject_text_free(ix);
     delete ix;
 }
 
@@ -2850,6 +2881,7 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 #include "host_top.hip.inc"
 #include "host_top_align.hip.inc"
 #include "host_text.hip.inc"
+#include "host_tsv.hip.inc"
 #include "host_sharded.hip.inc"
 #include "host_sharded_submit.hip.inc"
 #include "host_sharded_collect.hip.inc"

@@ -28,6 +28,7 @@ class SearchOptions:  # search.go:56-71 (the fields the hot path reads); default
     MinKMatch: int = 10
     MinKRatio: float = 0.05
     ExtractPositions: bool = False
+    Annotations: bool = False     # search.go:65: the TSV rows carry Protein.Length and one column per KStats.Features name
     Align: bool = False           # search.go:65; the alignment step: AlignHits below
     SubMatrix: str = "blosum62"   # api/server.go:149-151
     GapOpen: int = 11
@@ -374,6 +375,33 @@ def SearchFile(handle, path, options=None, fmt=None, device_parse=False, device_
     finally:
         stop.set()   # (a consumer that leaves early: the callback stops the run at the next chunk)
         th.join()
+
+
+def TextSearchTsv(index, text, options=None, fmt="fastq", proteins=None):
+    """The whole TSV response body of a request whose input is text (SetResponseFormatAndHeader + QueryResultHandler,
+    search.go:636-662,505-554, OutFormat "tsv" without Align): the header line, then one row per reported hit, written on the
+    device in the same call that parses and searches the text (Index.search_text_top / search_fasta_top / search_bgzf_top
+    with tsv=...; needs Index.attach_subject_text).  fmt: "fastq", "fasta" or "bgzf" (whole BGZF blocks of FASTQ).
+    proteins: the table, for the feature names of the header (default: index.proteins); needed with Annotations."""
+    o = options or SearchOptions(SequenceType=abi.READS)
+    if o.Align:
+        raise ValueError("the -aln form of the TSV response is not written on the device: AlignHits, then format on the host")
+    proteins = proteins if proteins is not None else getattr(index, "proteins", None)
+    if o.Annotations and proteins is None:
+        raise ValueError("Annotations: the header needs the table's feature names (proteins=...)")
+    base = abi.seq_type_base(o.SequenceType)
+    st = abi.seq_type(base, o.GeneticCode) if base != abi.PROTEIN else abi.PROTEIN
+    kw = dict(seq_type=st, min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
+              tsv=dict(positions=o.ExtractPositions, annotations=o.Annotations))
+    if fmt == "fastq":
+        top = index.search_text_top(text, **kw)
+    elif fmt == "fasta":
+        top = index.search_fasta_top(text, **kw)
+    elif fmt == "bgzf":
+        top = index.search_bgzf_top(text, **kw)
+    else:
+        raise ValueError("fmt is 'fastq', 'fasta' or 'bgzf'")
+    return api.format_tsv_header(o.ExtractPositions, o.Annotations, proteins) + top.tsv
 
 
 def FetchHitsInformation(query_results, proteins):
