@@ -561,67 +561,45 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
+    def _text_call(self, kind, data, extra, top, tsv, wait):
+        """kaamer_{search,submit}_{kind}_top[_tsv]_flat -- kind: text, fasta or bgzf; extra: the kind's arguments between the
+        data and the sequence type, and the sequence type; top: (min_k_ratio, min_k_match, max_results); wait: search
+        (-> TopResult), else submit (-> TopTicket)"""
+        data = data.encode("latin-1") if isinstance(data, str) else bytes(data)
+        fn = getattr(abi.lib(), "kaamer_%s_%s_top%s_flat" % ("search" if wait else "submit", kind, "_tsv" if tsv is not None else ""))
+        out = C.POINTER(abi.BatchTop)() if wait else C.c_void_p()
+        abi.check(fn(self._h, data, len(data), *extra, *top, *(_tsv_args(tsv) if tsv is not None else ()), C.byref(out)))
+        if not wait:
+            return TopTicket(out)
+        try:
+            return TopResult(out)
+        finally:
+            abi.lib().kaamer_batch_top_free(out)
+
     def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None):
         """kaamer_search_text_top_flat: FASTQ text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFastq) and searched as search_top searches the packed batch.  TopResult.text_spans: name and sequence of
         every record as offsets into `text`; rep_query / meta["src_seq"] index the records.
         tsv=dict(positions=..., annotations=...): kaamer_search_text_top_tsv_flat -- the TSV rows of the reported hits are
         written on the device too (needs attach_subject_text): TopResult.tsv, .tsv_line_off."""
-        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
-        out = C.POINTER(abi.BatchTop)()
-        if tsv is not None:
-            abi.check(abi.lib().kaamer_search_text_top_tsv_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
-                                                                min_k_match, max_results, *_tsv_args(tsv), C.byref(out)))
-        else:
-            abi.check(abi.lib().kaamer_search_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
-                                                            min_k_match, max_results, C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, True)
 
     def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
         """kaamer_search_bgzf_top_flat: whole BGZF blocks of FASTQ (bytes) in, the reported hits out -- the compressed bytes
         are uploaded, inflated, parsed and searched on the device.  TopResult.text: the inflated text; text_spans index it.
         Bytes that are not whole BGZF blocks: KaamerError E_ARG; a block that does not inflate: E_FORMAT.
         tsv: as search_text_top's (kaamer_search_bgzf_top_tsv_flat)."""
-        data = bytes(data)
-        out = C.POINTER(abi.BatchTop)()
-        if tsv is not None:
-            abi.check(abi.lib().kaamer_search_bgzf_top_tsv_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results,
-                                                                *_tsv_args(tsv), C.byref(out)))
-        else:
-            abi.check(abi.lib().kaamer_search_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results,
-                                                            C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, True)
 
     def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
         """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans); tsv: as
         search_text_top's (kaamer_submit_bgzf_top_tsv_flat)"""
-        data = bytes(data)
-        t = C.c_void_p()
-        if tsv is not None:
-            abi.check(abi.lib().kaamer_submit_bgzf_top_tsv_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results,
-                                                                *_tsv_args(tsv), C.byref(t)))
-            return TopTicket(t)
-        abi.check(abi.lib().kaamer_submit_bgzf_top_flat(self._h, data, len(data), seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
-        return TopTicket(t)
+        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, False)
 
     def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None):
         """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv: as
         search_text_top's (kaamer_submit_text_top_tsv_flat)"""
-        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
-        t = C.c_void_p()
-        if tsv is not None:
-            abi.check(abi.lib().kaamer_submit_text_top_tsv_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
-                                                                min_k_match, max_results, *_tsv_args(tsv), C.byref(t)))
-            return TopTicket(t)
-        abi.check(abi.lib().kaamer_submit_text_top_flat(self._h, data, len(data), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio,
-                                                        min_k_match, max_results, C.byref(t)))
-        return TopTicket(t)
+        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, False)
 
     def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
         """kaamer_search_fasta_top_flat: FASTA text (bytes) in, the reported hits out -- the text is parsed on the device
@@ -629,31 +607,12 @@ class Index:
         (with a genetic code).  upper_last: more input follows this text, its last record is upper-cased too.
         TopResult.text_spans: name and sequence range of every record as offsets into `text`.
         tsv: as search_text_top's (kaamer_search_fasta_top_tsv_flat)."""
-        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
-        out = C.POINTER(abi.BatchTop)()
-        if tsv is not None:
-            abi.check(abi.lib().kaamer_search_fasta_top_tsv_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
-                                                                 min_k_match, max_results, *_tsv_args(tsv), C.byref(out)))
-        else:
-            abi.check(abi.lib().kaamer_search_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
-                                                             min_k_match, max_results, C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, True)
 
     def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
         """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv: as
         search_text_top's (kaamer_submit_fasta_top_tsv_flat)"""
-        data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
-        t = C.c_void_p()
-        if tsv is not None:
-            abi.check(abi.lib().kaamer_submit_fasta_top_tsv_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
-                                                                 min_k_match, max_results, *_tsv_args(tsv), C.byref(t)))
-            return TopTicket(t)
-        abi.check(abi.lib().kaamer_submit_fasta_top_flat(self._h, data, len(data), seq_type, int(bool(upper_last)), min_k_ratio,
-                                                         min_k_match, max_results, C.byref(t)))
-        return TopTicket(t)
+        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, False)
 
     def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
         """kaamer_stream_open[_pos|_aln]_flat; align: as search_top's (needs attach_proteins)"""

@@ -1,27 +1,52 @@
 // host_text_file.hip.inc — FastqSearch over a FILE (search_fastq.go:60-136) with the reader on the device (included by
 // search.hip inside its extern "C" block, after host_replicas.hip.inc): raw bytes -> chunks cut at kaamer_text_cut_fastq ->
 // the replicas' text call, round-robin -> a callback per chunk, in input order.  The loop is host_replicas.hip.inc's
-// chunk_loop; this file is the source it runs over.
+// chunk_loop; this file holds the two sources it runs over (TextSource: text the host chunk reader cut, FASTQ or FASTA;
+// BgzfSource: whole BGZF blocks for the device's inflater), and what the three exported calls share:
+//   text_file_check    what a call refuses, under its own name
+//   text_file_run      open the file and the replica stream, chunk_loop over the source, close both
+//   text_file_deliver  a chunk's result to the callback
 
 // chunk k -> replica k mod n, as kaamer_replica_stream_push deals packed chunks
-static int replica_stream_push_text(kaamer_replica_stream *rs, const char *text, uint64_t len, const FastaInput *fa = nullptr)
+static int replica_stream_push_text(kaamer_replica_stream *rs, const TextRequest &rq)
 {
-    const int rc = stream_push_text((*rs->st)[rs->pushed % rs->st->size()], text, len, fa);
+    const int rc = stream_push_text((*rs->st)[rs->pushed % rs->st->size()], rq);
     if (rc == KAAMER_OK) rs->pushed++;
     return rc;
+}
+
+// the records of a chunk (`text`: what the spans index) and its hits to the callback; n_seen: records delivered so far
+static int text_file_deliver(kaamer_text_chunk_cb cb, void *user, uint64_t *n_seen, const char *text, uint64_t len, const kaamer_batch_top *top)
+{
+    const kaamer_text_span *spans = nullptr;
+    uint32_t n = 0;
+    (void)kaamer_batch_top_text_spans(top, &spans, &n);
+    const uint64_t first = *n_seen;
+    *n_seen += n;
+    return cb ? cb(user, first, text, len, spans, n, top) : 0;
 }
 
 struct TextChunk { std::vector<char> text; size_t len; bool last; };
 struct TextSource {
     typedef TextChunk Chunk;
-    kaamer_text_chunker *reader;  // the file's text, cut into chunks (host_search.cpp)
-    kaamer_replica_stream *rs;
+    uint64_t budget;
+    bool fasta;                   // kaamer_search_fasta_file: the chunks are FASTA, every one but the file's last with upper_last
     kaamer_text_chunk_cb cb;
     void *user;
-    uint64_t n_seen;              // records delivered so far
+    kaamer_replica_stream *rs = nullptr;
+    kaamer_bytes *bytes = nullptr;
+    kaamer_text_chunker *reader = nullptr;   // the file's text, cut into chunks (host_search.cpp)
+    uint64_t n_seen = 0;          // records delivered so far
     std::vector<std::vector<char>> pool;   // buffers of chunks that were delivered
-    bool fasta = false;           // kaamer_search_fasta_file: the chunks are FASTA, every one but the file's last with upper_last
 
+    ~TextSource() { if (reader) kaamer_text_chunker_free(reader); if (bytes) kaamer_bytes_close(bytes); }
+    int open(int fd)
+    {
+        const int rc = kaamer_bytes_open_fd(fd, &bytes);
+        if (rc) return rc;
+        reader = kaamer_text_chunker_new(bytes, budget, fasta);
+        return reader ? KAAMER_OK : kaamer_fail(KAAMER_E_NOMEM, "%s: chunk reader", fasta ? "search_fasta_file" : "search_text_file");
+    }
     bool done() const { return kaamer_text_chunker_done(reader); }
     int next(Chunk **out)
     {
@@ -36,21 +61,11 @@ struct TextSource {
     }
     int push(Chunk *c)
     {
-        if (!fasta) return replica_stream_push_text(rs, c->text.data(), c->len);
-        const FastaInput fa = { !c->last };
-        return replica_stream_push_text(rs, c->text.data(), c->len, &fa);
+        return replica_stream_push_text(rs, fasta ? fasta_request(c->text.data(), c->len, !c->last) : fastq_request(c->text.data(), c->len));
     }
     int pop(kaamer_batch_top **top) { return kaamer_replica_stream_pop(rs, top); }
     uint32_t pending() const { return kaamer_replica_stream_pending(rs); }
-    int deliver(Chunk *c, const kaamer_batch_top *top)
-    {
-        const kaamer_text_span *spans = nullptr;
-        uint32_t n = 0;
-        (void)kaamer_batch_top_text_spans(top, &spans, &n);
-        const uint64_t first = n_seen;
-        n_seen += n;
-        return cb ? cb(user, first, c->text.data(), c->len, spans, n, top) : 0;
-    }
+    int deliver(Chunk *c, const kaamer_batch_top *top) { return text_file_deliver(cb, user, &n_seen, c->text.data(), c->len, top); }
     void drop(Chunk *c)
     {
         if (pool.size() < 64) pool.emplace_back(std::move(c->text));
@@ -69,13 +84,6 @@ struct TextSource {
 // inflater (kaamer_bytes) with the pending tail in front, and the rest of the file runs on kaamer_search_text_file's
 // route.  Members are independent, so zlib started there yields what it yields there in a run from the file's start: the
 // device never has to imitate zlib on a damaged stream, and the concatenated text equals the flag-0 run's for every file.
-static int replica_stream_push_bgzf(kaamer_replica_stream *rs, const BgzfInput &bz, uint64_t text_len)
-{
-    const int rc = stream_push_bgzf((*rs->st)[rs->pushed % rs->st->size()], bz, text_len);
-    if (rc == KAAMER_OK) rs->pushed++;
-    return rc;
-}
-
 struct BgzfChunk {
     bool host = false;
     std::vector<char> text;                   // a host chunk (after the fallback)
@@ -87,11 +95,11 @@ struct BgzfChunk {
 };
 struct BgzfSource {
     typedef BgzfChunk Chunk;
-    int fd;
     uint64_t budget;
-    kaamer_replica_stream *rs;
     kaamer_text_chunk_cb cb;
     void *user;
+    kaamer_replica_stream *rs = nullptr;
+    int fd = -1;
     uint64_t n_seen = 0;
     std::vector<uint8_t> raw;                 // file bytes [raw_off, raw_off + raw_len); the next chunk starts at raw_pos
     size_t raw_pos = 0, raw_len = 0;
@@ -104,6 +112,7 @@ struct BgzfSource {
     std::vector<kaamer_bgzf_block> tab;
 
     ~BgzfSource() { if (reader) kaamer_text_chunker_free(reader); if (bytes) kaamer_bytes_close(bytes); }
+    int open(int file) { fd = file; return KAAMER_OK; }
     bool done() const { return reader ? kaamer_text_chunker_done(reader) : finished; }
 
     // at least `want` unread bytes in raw, or the file's end
@@ -182,14 +191,14 @@ struct BgzfSource {
     int push(Chunk *c)
     {
         for (;;) {
-            if (c->host) return replica_stream_push_text(rs, c->text.data(), c->len);
-            BgzfInput bz;
-            bz.bytes = raw.data() + raw_pos; bz.len = c->comp_len; bz.blocks = &c->blocks;
+            if (c->host) return replica_stream_push_text(rs, fastq_request(c->text.data(), c->len));
+            TextRequest bz = bgzf_request(raw.data() + raw_pos, c->comp_len);
+            bz.blocks = &c->blocks;
             bz.file = true; bz.last = c->last; bz.tail = tail.data(); bz.tail_len = tail.size();
             bz.tail_out = &next_tail; bz.no_cut = &no_cut;
             no_cut = false;
-            const uint64_t text_len = tail.size() + c->isize_sum;
-            int rc = replica_stream_push_bgzf(rs, bz, text_len);
+            const uint64_t text_len = bz.len = tail.size() + c->isize_sum;
+            int rc = replica_stream_push_text(rs, bz);
             if (rc == KAAMER_OK) {
                 raw_pos += c->comp_len;
                 tail.swap(next_tail);
@@ -216,48 +225,50 @@ struct BgzfSource {
     uint32_t pending() const { return kaamer_replica_stream_pending(rs); }
     int deliver(Chunk *c, const kaamer_batch_top *top)
     {
-        const kaamer_text_span *spans = nullptr;
-        uint32_t n = 0;
-        (void)kaamer_batch_top_text_spans(top, &spans, &n);
         const char *text = c->text.data();
         uint64_t len = c->len;
         if (!c->host) (void)kaamer_batch_top_text(top, &text, &len);   // the copy brought back from the device
-        const uint64_t first = n_seen;
-        n_seen += n;
-        return cb ? cb(user, first, text, len, spans, n, top) : 0;
+        return text_file_deliver(cb, user, &n_seen, text, len, top);
     }
     void drop(Chunk *c) { delete c; }
 };
 
-// the plain / gzip file `path` through the chunk reader with the cut rule of its format, and chunk_loop over it
-static int text_file_run(kaamer_replicas *r, const char *path, bool fasta, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
-                         uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
-                         kaamer_counters *total)
+// what the file calls refuse before they open anything (fasta: kaamer_search_fasta_file, which takes any sequence type)
+static int text_file_check(const char *who, bool fasta, kaamer_replicas *r, const char *path, int format, int32_t seq_type, uint32_t max_results,
+                           uint64_t chunk_text_bytes)
 {
-    const char *who = fasta ? "search_fasta_file" : "search_text_file";
+    if (!r || !path || chunk_text_bytes == 0 || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "%s: bad argument", who);
+    if (!fasta) {
+        if (format == 0)
+            return kaamer_fail(KAAMER_E_ARG, "%s: FASTA is not parsed on the device by this call: use kaamer_search_fasta_file, or the host reader (kaamer_search_file)", who);
+        if (format != 1) return kaamer_fail(KAAMER_E_ARG, "%s: unknown format %d (1 = FASTQ)", who, format);
+    }
+    SEQ_TYPE_CHK(seq_type, who);
+    if (!fasta && !is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "%s: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN", who);
+    if (chunk_text_bytes > 0xFFFFFFFFull / 4)
+        return kaamer_fail(KAAMER_E_ARG, "%s: chunk_text_bytes above 2^30 - 1 (a chunk may grow to four times that and spans are 32-bit)", who);
+    return KAAMER_OK;
+}
+
+// the file `path` and a replica stream opened, chunk_loop over `src` (a TextSource or a BgzfSource), both closed
+extern "C++" {
+template <class Src> static int text_file_run(Src &src, const char *who, kaamer_replicas *r, const char *path, int32_t seq_type, double min_k_ratio,
+                                              int64_t min_k_match, uint32_t max_results, uint32_t in_flight, kaamer_counters *total)
+{
     if (total) memset(total, 0, sizeof *total);
     if (in_flight < 1) in_flight = 3;
     const int fd = open(path, O_RDONLY | O_CLOEXEC);
     if (fd < 0) return kaamer_fail(KAAMER_E_IO, "%s: cannot open %s", who, path);
-    kaamer_bytes *bytes = nullptr;
-    int rc = kaamer_bytes_open_fd(fd, &bytes);
-    if (rc) { close(fd); return rc; }
-    kaamer_replica_stream *rs = nullptr;
-    rc = kaamer_replica_stream_open_flat(r, seq_type, min_k_ratio, min_k_match, max_results, &rs);
+    int rc = src.open(fd);
+    if (!rc) rc = kaamer_replica_stream_open_flat(r, seq_type, min_k_ratio, min_k_match, max_results, &src.rs);
     if (!rc) {
-        kaamer_text_chunker *reader = kaamer_text_chunker_new(bytes, chunk_text_bytes, fasta);
-        if (!reader) rc = kaamer_fail(KAAMER_E_NOMEM, "%s: chunk reader", who);
-        if (!rc) {
-            TextSource src = { reader, rs, cb, user, 0, {}, fasta };
-            rc = chunk_loop(src, in_flight * kaamer_replicas_count(r), total);
-        }
-        kaamer_text_chunker_free(reader);
-        kaamer_replica_stream_close(rs);
+        rc = chunk_loop(src, in_flight * kaamer_replicas_count(r), total);
+        kaamer_replica_stream_close(src.rs);
     }
-    kaamer_bytes_close(bytes);
     close(fd);
     return rc;
 }
+}  // extern "C++"
 
 // ProteinSearch / NucleotideSearch / FastqSearch over a FASTA file (search_protein.go, search_nucleotide.go, search_fastq.go:
 // each calls GetQueriesFasta when the request is not FASTQ) with the reader on the device
@@ -265,54 +276,36 @@ int kaamer_search_fasta_file(kaamer_replicas *r, const char *path, int32_t seq_t
                              uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
                              kaamer_counters *total)
 {
-    if (!r || !path || chunk_text_bytes == 0 || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "search_fasta_file: bad argument");
-    SEQ_TYPE_CHK(seq_type, "search_fasta_file");
-    if (chunk_text_bytes > 0xFFFFFFFFull / 4)
-        return kaamer_fail(KAAMER_E_ARG, "search_fasta_file: chunk_text_bytes above 2^30 - 1 (a chunk may grow to four times that and spans are 32-bit)");
-    return text_file_run(r, path, true, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total);
+    const int rc = text_file_check("search_fasta_file", true, r, path, 0, seq_type, max_results, chunk_text_bytes);
+    if (rc) return rc;
+    TextSource src = { chunk_text_bytes, true, cb, user };
+    return text_file_run(src, "search_fasta_file", r, path, seq_type, min_k_ratio, min_k_match, max_results, in_flight, total);
 }
 
 int kaamer_search_text_file(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                             uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, kaamer_text_chunk_cb cb, void *user,
                             kaamer_counters *total)
 {
-    if (!r || !path || chunk_text_bytes == 0 || max_results < 1) return kaamer_fail(KAAMER_E_ARG, "search_text_file: bad argument");
-    if (format == 0)
-        return kaamer_fail(KAAMER_E_ARG, "search_text_file: FASTA is not parsed on the device by this call: use kaamer_search_fasta_file, or the host reader (kaamer_search_file)");
-    if (format != 1) return kaamer_fail(KAAMER_E_ARG, "search_text_file: unknown format %d (1 = FASTQ)", format);
-    SEQ_TYPE_CHK(seq_type, "search_text_file");
-    if (!is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "search_text_file: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN");
-    if (chunk_text_bytes > 0xFFFFFFFFull / 4)
-        return kaamer_fail(KAAMER_E_ARG, "search_text_file: chunk_text_bytes above 2^30 - 1 (a chunk may grow to four times that and spans are 32-bit)");
-    return text_file_run(r, path, false, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total);
+    return kaamer_search_text_file_opts(r, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, 0, cb, user, total);
 }
 
+// device_inflate: a file that starts with the gzip signature goes through BgzfSource; flag 0, and plain files: TextSource
 int kaamer_search_text_file_opts(kaamer_replicas *r, const char *path, int format, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
                                  uint32_t max_results, uint64_t chunk_text_bytes, uint32_t in_flight, int32_t device_inflate,
                                  kaamer_text_chunk_cb cb, void *user, kaamer_counters *total)
 {
+    const int rc = text_file_check("search_text_file", false, r, path, format, seq_type, max_results, chunk_text_bytes);
+    if (rc) return rc;
     bool gz = false;
-    if (device_inflate && path && format == 1) {   // (every other argument is checked by the call below)
+    if (device_inflate) {
         const int fd = open(path, O_RDONLY | O_CLOEXEC);
         uint8_t head[3];
         if (fd >= 0) { gz = read(fd, head, 3) == 3 && kaamer_is_gzip((const char *)head, 3); close(fd); }
     }
-    // flag 0, and plain files: today's path
-    if (!gz || !r || chunk_text_bytes == 0 || max_results < 1 || chunk_text_bytes > 0xFFFFFFFFull / 4 || !is_nucl(seq_type))
-        return kaamer_search_text_file(r, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total);
-    SEQ_TYPE_CHK(seq_type, "search_text_file");
-    if (total) memset(total, 0, sizeof *total);
-    if (in_flight < 1) in_flight = 3;
-    const int fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fd < 0) return kaamer_fail(KAAMER_E_IO, "search_text_file: cannot open %s", path);
-    kaamer_replica_stream *rs = nullptr;
-    int rc = kaamer_replica_stream_open_flat(r, seq_type, min_k_ratio, min_k_match, max_results, &rs);
-    if (!rc) {
-        BgzfSource src;
-        src.fd = fd; src.budget = chunk_text_bytes; src.rs = rs; src.cb = cb; src.user = user;
-        rc = chunk_loop(src, in_flight * kaamer_replicas_count(r), total);
-        kaamer_replica_stream_close(rs);
+    if (gz) {
+        BgzfSource src = { chunk_text_bytes, cb, user };
+        return text_file_run(src, "search_text_file", r, path, seq_type, min_k_ratio, min_k_match, max_results, in_flight, total);
     }
-    close(fd);
-    return rc;
+    TextSource src = { chunk_text_bytes, false, cb, user };
+    return text_file_run(src, "search_text_file", r, path, seq_type, min_k_ratio, min_k_match, max_results, in_flight, total);
 }

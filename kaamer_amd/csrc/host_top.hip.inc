@@ -103,6 +103,14 @@ struct kaamer_ticket {
     uint8_t *h_tsv;
     size_t h_tsv_cap;
 };
+// the pinned buffers a ticket still holds (those that went to a result are NULL by then) back to the cache
+static void ticket_put_pinned(kaamer_ticket *t)
+{
+    if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
+    if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
+    if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
+    if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
+}
 static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static int tsv_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
 static void tsv_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
@@ -265,6 +273,13 @@ static void top_slot_free(TopSlot &h)
     h = TopSlot();
 }
 
+// the pinned staging of a packed batch: the sequences, then (8-byte aligned) the n_seqs + 1 offsets
+static int top_slot_staging(TopSlot &h, uint64_t seq_bytes, uint32_t n_seqs)
+{
+    const size_t in_need = (((size_t)seq_bytes + 7) & ~(size_t)7) + ((size_t)n_seqs + 1) * 8;
+    return slot_grow_pinned(h.stream, &h.h_in, &h.h_in_cap, in_need, "input staging");
+}
+
 // workspace, staging and result block of a slot: rebuilt only when the batch outgrows them
 static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace_opts &need, uint64_t seq_bytes, uint32_t n_seqs, uint32_t K,
                             bool want_pos = false, uint32_t pos_scale = 0, uint64_t aln_bytes = 0)
@@ -284,14 +299,8 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
         if (rc) { h.ws = nullptr; return rc; }
         h.opts = g;
     }
-    if (h.seq_cap < seq_bytes + 16) {
-        if (h.d_seqs) (void)hipFree(h.d_seqs);
-        h.d_seqs = nullptr; h.seq_cap = 0;
-        const size_t cap = (size_t)seq_bytes + (size_t)seq_bytes / 4 + 4096;
-        const int rc = dev_alloc(&h.d_seqs, cap);
-        if (rc) return rc;
-        h.seq_cap = cap;
-    }
+    int rc = slot_grow_dev(h.stream, &h.d_seqs, &h.seq_cap, (size_t)seq_bytes, 16);
+    if (rc) return rc;
     if (h.off_cap < (size_t)n_seqs + 1) {
         if (h.d_off) (void)hipFree(h.d_off);
         h.d_off = nullptr; h.off_cap = 0;
@@ -300,14 +309,8 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
         if (rc) return rc;
         h.off_cap = cap;
     }
-    const size_t in_need = (((size_t)seq_bytes + 7) & ~(size_t)7) + ((size_t)n_seqs + 1) * 8;
-    if (h.h_in_cap < in_need) {
-        if (h.h_in) (void)hipHostFree(h.h_in);
-        h.h_in = nullptr; h.h_in_cap = 0;
-        const size_t cap = in_need + in_need / 4 + 4096;
-        if (hipHostMalloc((void **)&h.h_in, cap, hipHostMallocDefault) != hipSuccess) return kaamer_fail(KAAMER_E_NOMEM, "pinned input staging (%zu bytes)", cap);
-        h.h_in_cap = cap;
-    }
+    rc = top_slot_staging(h, seq_bytes, n_seqs);
+    if (rc) return rc;
     // the bitmap bound (the rule next to kaamer_topn_positions_device); a first bound set on the index holds for the
     // first attempt only: the repeat of a batch that exceeded it takes the rule's
     h.pos_words = 0;
@@ -322,7 +325,7 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
     if (h.d_block_cap < bneed) {
         if (h.d_block) (void)hipFree(h.d_block);
         h.d_block = nullptr; h.d_block_cap = 0;
-        const int rc = dev_alloc(&h.d_block, bneed);
+        rc = dev_alloc(&h.d_block, bneed);
         if (rc) return rc;
         h.d_block_cap = bneed;
     }
@@ -423,15 +426,7 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
         // is part of top_slot_prepare, which needs the workspace options: a first pass with the default bounds.)
         TopSlot &h = ix->top[slot];
         const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
-        const size_t in_need = off_at + ((size_t)in->n_seqs + 1) * 8;
-        if (h.h_in_cap < in_need) {
-            if (h.stream) (void)hipStreamSynchronize(h.stream);
-            if (h.h_in) (void)hipHostFree(h.h_in);
-            h.h_in = nullptr; h.h_in_cap = 0;
-            const size_t cap = in_need + in_need / 4 + 4096;
-            if (hipHostMalloc((void **)&h.h_in, cap, hipHostMallocDefault) != hipSuccess) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned input staging (%zu bytes)", cap);
-            else h.h_in_cap = cap;
-        }
+        rc = top_slot_staging(h, t->seq_bytes, in->n_seqs);
         if (!rc) {
             if (t->seq_bytes) memcpy(h.h_in, in->seqs, (size_t)t->seq_bytes);
             memcpy(h.h_in + off_at, in->offsets, ((size_t)in->n_seqs + 1) * 8);
@@ -441,7 +436,7 @@ static int top_submit(kaamer_index *ix, const kaamer_batch_in *in, const kaamer_
     if (rc) {
         // part of the call may be on the slot's stream already (copies out of the pinned staging the next caller overwrites)
         if (ix->top[slot].stream) (void)hipStreamSynchronize(ix->top[slot].stream);
-        if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
+        ticket_put_pinned(t);
         delete t;
         top_slot_release(ix, slot);
         return rc;
@@ -517,10 +512,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         if (!rc) *out = &bo->pub;
         else kaamer_batch_top_free(&bo->pub);
     }
-    if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
-    if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
-    if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
-    if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
+    ticket_put_pinned(t);
     top_slot_release(ix, t->slot);
     delete t;
     return rc;
@@ -536,10 +528,7 @@ void kaamer_ticket_discard(kaamer_ticket *t)
     TopSlot &h = ix->top[t->slot];
     if (h.stream) (void)hipStreamSynchronize(h.stream);
     if (h.ws) h.ws->clean = false;  // its status was not looked at: the next batch starts from cleared per-batch state
-    if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
-    if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
-    if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
-    if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
+    ticket_put_pinned(t);
     top_slot_release(ix, t->slot);
     delete t;
 }

@@ -3,7 +3,8 @@
 //   kaamer_index_attach_subject_text  EntryId, Length and the annotation columns of every entry, resident next to the index
 //   kaamer_tsv_stage_* / kaamer_tsv_rows_device / kaamer_tsv_rows_finish   the stage on a stream
 //   kaamer_format_tsv                 the host formatter on a result of this library (its bitmaps come from the result)
-//   kaamer_*_top_tsv_flat             the text, FASTA and BGZF calls with the rows in the result; kaamer_batch_top_tsv
+//   top_enqueue_tsv / tsv_needs_repeat / tsv_finish_host   the rows as part of a text call (the kaamer_*_top_tsv_flat calls
+//                                     themselves stand next to their twins in host_text.hip.inc); kaamer_batch_top_tsv
 
 int kaamer_index_attach_subject_text(kaamer_index *ix, const kaamer_proteins *p)
 {
@@ -294,68 +295,6 @@ int kaamer_batch_top_tsv(const kaamer_batch_top *out, const char **text, uint64_
     if (len) *len = bo->tsv_len;
     if (line_off) *line_off = reinterpret_cast<const uint64_t *>(bo->tsv);
     return KAAMER_OK;
-}
-
-int kaamer_submit_text_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
-                                    int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
-                                    kaamer_ticket **ticket)
-{
-    kaamer_topn_opts top;
-    flat_top(&top, min_k_ratio, min_k_match, max_results);
-    const TsvRequest rq = { extract_positions != 0, annotations != 0 };
-    return text_submit(ix, text, len, format, seq_type, &top, true, ticket, nullptr, nullptr, &rq);
-}
-
-int kaamer_search_text_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
-                                    int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
-                                    kaamer_batch_top **out)
-{
-    if (out) *out = nullptr;
-    kaamer_ticket *t = nullptr;
-    const int rc = kaamer_submit_text_top_tsv_flat(ix, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, extract_positions,
-                                                   annotations, &t);
-    if (rc) return rc;
-    return kaamer_wait_batch_top(t, out);
-}
-
-int kaamer_submit_fasta_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
-                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
-                                     kaamer_ticket **ticket)
-{
-    kaamer_topn_opts top;
-    flat_top(&top, min_k_ratio, min_k_match, max_results);
-    const FastaInput fa = { upper_last != 0 };
-    const TsvRequest rq = { extract_positions != 0, annotations != 0 };
-    return text_submit(ix, text, len, 0, seq_type, &top, true, ticket, nullptr, &fa, &rq);
-}
-
-int kaamer_search_fasta_top_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
-                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
-                                     kaamer_batch_top **out)
-{
-    if (out) *out = nullptr;
-    kaamer_ticket *t = nullptr;
-    const int rc = kaamer_submit_fasta_top_tsv_flat(ix, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, extract_positions,
-                                                    annotations, &t);
-    if (rc) return rc;
-    return kaamer_wait_batch_top(t, out);
-}
-
-int kaamer_submit_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
-                                    uint32_t max_results, int32_t extract_positions, int32_t annotations, kaamer_ticket **ticket)
-{
-    const TsvRequest rq = { extract_positions != 0, annotations != 0 };
-    return bgzf_submit(ix, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, ticket, &rq);
-}
-
-int kaamer_search_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
-                                    uint32_t max_results, int32_t extract_positions, int32_t annotations, kaamer_batch_top **out)
-{
-    if (out) *out = nullptr;
-    kaamer_ticket *t = nullptr;
-    const int rc = kaamer_submit_bgzf_top_tsv_flat(ix, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, annotations, &t);
-    if (rc) return rc;
-    return kaamer_wait_batch_top(t, out);
 }
 
 // the first bounds of the rows on a slot that has not run a TSV call yet (tests: a first bound too small); 0: the rule

@@ -963,6 +963,30 @@ template <class T> static int dev_grow(T **p, size_t *cap, size_t need)
     return rc;
 }
 
+// The buffers of a host slot (TopSlot) that work on its stream: made again for `need` elements plus a quarter and 4096
+// when they hold fewer than need + pad, once the stream is done with the old one.
+static size_t slot_buf_cap(size_t need) { return need + need / 4 + 4096; }
+template <class T> static int slot_grow_dev(hipStream_t s, T **p, size_t *cap, size_t need, size_t pad = 0)
+{
+    if (*cap >= need + pad) return KAAMER_OK;
+    if (*p) { HIPCHK(hipStreamSynchronize(s)); (void)hipFree(*p); }
+    *p = nullptr; *cap = 0;
+    const int rc = dev_alloc(p, slot_buf_cap(need));
+    if (!rc) *cap = slot_buf_cap(need);
+    return rc;
+}
+// ... and its pinned staging (bytes); `what` names it in the refusal
+static int slot_grow_pinned(hipStream_t s, uint8_t **p, size_t *cap, size_t need, const char *what)
+{
+    if (*cap >= need) return KAAMER_OK;
+    if (*p) { HIPCHK(hipStreamSynchronize(s)); (void)hipHostFree(*p); }
+    *p = nullptr; *cap = 0;
+    if (hipHostMalloc((void **)p, slot_buf_cap(need), hipHostMallocDefault) != hipSuccess)
+        return kaamer_fail(KAAMER_E_NOMEM, "pinned %s (%zu bytes)", what, slot_buf_cap(need));
+    *cap = slot_buf_cap(need);
+    return KAAMER_OK;
+}
+
 static void launch_group(const CountParams &p, int grid, bool firstpos, hipStream_t s)
 {
     if (firstpos) hipLaunchKernelGGL((count_group_kernel<true, 0>), dim3(grid), dim3(64 * GRP_WAVES), 0, s, p);

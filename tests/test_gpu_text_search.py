@@ -97,3 +97,44 @@ def test_two_tickets_in_flight(setup):
     # a ticket nobody waits for gives its slot and its spans back
     ix.submit_text_top(a).discard()
     _same(ix.search_text_top(a), one_a)
+
+
+# ---- the record bound of a slot's first parse is exceeded: the parse is repeated with grown bounds ----------------------------
+@pytest.fixture(scope="module")
+def growth(setup, gpu_device):
+    """8 000 ten-byte records, then 200 ordinary reads: more records than the first bound of len / 32 + 1024.  Every call
+    runs on a fresh index: a used slot keeps its larger parser and would not grow."""
+    db = workload.make_db(1000)
+    reads = workload.make_reads(db, 200, seed=12)
+    text = b"@\nAC\n+\nII\n" * 8000 + bytes(workload.fastq_text(reads))
+    recs = api.parse_reads(text, "fastq")
+    assert len(recs) == 8200 and len(recs) > len(text) // 32 + 1024
+    img = api.Image.from_proteins(packed=db)
+    want = setup["ix"].search_top([r["seq"] for r in recs], seq_type=abi.READS)
+    ix = api.Index.from_image(img, gpu_device)
+    try:
+        got = ix.search_text_top(text)
+    finally:
+        ix.close()
+    return dict(img=img, text=text, recs=recs, want=want, got=got)
+
+
+def test_fastq_record_bound_grows(growth):
+    got = growth["got"]
+    assert got.n_reported > 0
+    _same(got, growth["want"])
+    _check_spans(got, growth["text"], growth["recs"])
+
+
+def test_record_bound_grows_on_inflated_text(growth, gpu_device):
+    """the same text as BGZF blocks: the repeated parse reads a text that was inflated on the device, not uploaded"""
+    import bgzfmake
+    ix = api.Index.from_image(growth["img"], gpu_device)
+    try:
+        got = ix.search_bgzf_top(bgzfmake.bgzf_file(growth["text"], 4096))
+    finally:
+        ix.close()
+    assert got.text == growth["text"]
+    _same(got, growth["got"])
+    assert got.text_spans.tobytes() == growth["got"].text_spans.tobytes()
+    _check_spans(got, growth["text"], growth["recs"])
