@@ -15,6 +15,7 @@
 //     [4] entries this block NEEDED (= [0] unless it overflowed)
 //     [5] the largest [4] over the sender's W blocks   [6], [7] zero (arrays = 4: see below)
 //     [8 .. 8+q_cap)             per owned query i (global query d + i W): number of entries
+//     (XWord and XStatus below name these words and bits; tests/blockfmt.py restates the format under the same names)
 //     then pid[e_cap], kmatch[e_cap], first_pos[e_cap]   (structure of arrays)
 // Blocks with PositionHits bitmaps (arrays = 4; search.go:442-452) add, after the counts, SizeInKmer[q_cap] (the entry
 // arrays follow it), and after the entry arrays, from the even word bits_off = 8 + 2 q_cap + 3 e_cap (rounded up), a
@@ -39,8 +40,15 @@
 #define X_BLOCK 1024
 #define X_ITEMS 8
 #define X_TILE (X_BLOCK * X_ITEMS)
-#define X_HDR 8u
 #define X_SMALL_TILES 4u  /* up to this many tiles per row a single workgroup per row scans them (one launch) */
+
+enum XWord : uint32_t {       // the header words of a block
+    X_ENTRIES = 0, X_STATUS, X_NQ, X_OWNED, X_NEED, X_NEED_MAX, X_BITS_NEED, X_BITS_NEED_MAX,
+    X_HDR                     // the header's length: the counts start here
+};
+enum XStatus : uint32_t {     // the bits of blk[X_STATUS]
+    XS_OVERFLOW = 1u, XS_FIRST_POS = 2u, XS_SENDER_FAILED = 4u, XS_SENDER_OVERFLOW = 8u, XS_BITMAPS = 16u
+};
 
 struct XParams {
     uint32_t world, rank, q_cap;
@@ -97,6 +105,13 @@ __device__ __forceinline__ uint32_t x_sat32(uint64_t v) { return v > 0xFFFFFFFFu
 
 __device__ __forceinline__ uint32_t *x_block(uint32_t *base, const XParams &p, uint32_t peer) { return base + (uint64_t)peer * p.block_words; }
 __device__ __forceinline__ const uint32_t *x_block(const uint32_t *base, const XParams &p, uint32_t peer) { return base + (uint64_t)peer * p.block_words; }
+// the per-query sections of a block: entry counts, and (arrays = 4) SizeInKmer
+__device__ __forceinline__ uint32_t *x_counts(uint32_t *blk) { return blk + X_HDR; }
+__device__ __forceinline__ const uint32_t *x_counts(const uint32_t *blk) { return blk + X_HDR; }
+__device__ __forceinline__ uint32_t *x_sizes(uint32_t *blk, const XParams &p) { return blk + X_HDR + p.q_cap; }
+__device__ __forceinline__ const uint32_t *x_sizes(const uint32_t *blk, const XParams &p) { return blk + X_HDR + p.q_cap; }
+// queries of a batch of nq that rank `peer` owns: peer, peer + W, ...
+__device__ __forceinline__ uint32_t x_owned_by(uint32_t nq, uint32_t peer, uint32_t world) { return nq > peer ? (nq - peer + world - 1) / world : 0u; }
 
 // exclusive scan of one tile of a block-wide loop (1024 threads, X_ITEMS each); returns the tile total
 __device__ __forceinline__ uint64_t x_tile_scan(const uint32_t (&v)[X_ITEMS], uint64_t (&ex)[X_ITEMS])
@@ -111,22 +126,22 @@ __device__ __forceinline__ uint64_t x_tile_scan(const uint32_t (&v)[X_ITEMS], ui
     return tot;
 }
 
-// Every source must describe the same batch: blk[2] (queries of the batch) equal in all blocks and blk[3] (queries this
-// rank owns) = ceil((nq - rank) / W) <= q_cap.  Otherwise nothing is unpacked (0 owned queries) and the batch fails.
+// Every source must describe the same batch: X_NQ equal in all blocks and X_OWNED (queries this rank owns) =
+// ceil((nq - rank) / W) <= q_cap.  Otherwise nothing is unpacked (0 owned queries) and the batch fails.
 __device__ __forceinline__ bool x_headers_agree(const XParams &p)
 {
-    const uint32_t nq = x_block(p.recv, p, 0)[2];
-    const uint32_t want = nq > p.rank ? (nq - p.rank + p.world - 1) / p.world : 0u;
+    const uint32_t nq = x_block(p.recv, p, 0)[X_NQ];
+    const uint32_t want = x_owned_by(nq, p.rank, p.world);
     bool ok = want <= p.q_cap;
     for (uint32_t t = 0; t < p.world; t++) {
         const uint32_t *b = x_block(p.recv, p, t);
-        ok = ok && b[2] == nq && b[3] == want;
+        ok = ok && b[X_NQ] == nq && b[X_OWNED] == want;
     }
     return ok;
 }
 __device__ __forceinline__ uint32_t x_owned_checked(const XParams &p)
 {
-    return x_headers_agree(p) ? x_block(p.recv, p, 0)[3] : 0u;
+    return x_headers_agree(p) ? x_block(p.recv, p, 0)[X_OWNED] : 0u;
 }
 
 // ---- scans over ROWS of per-query counts, tiled over the grid (a single workgroup per row took 5 ms for the 4.2 M ORFs
@@ -141,8 +156,7 @@ __device__ __forceinline__ uint32_t x_owned_checked(const XParams &p)
 template <int MODE> __device__ __forceinline__ uint32_t x_items(const XParams &p, uint32_t row)
 {
     if (MODE == 0 || MODE == 2) {
-        const uint32_t nq = *p.d_nq;
-        const uint32_t n = nq > row ? (nq - row + p.world - 1) / p.world : 0u;
+        const uint32_t n = x_owned_by(*p.d_nq, row, p.world);
         return n < p.q_cap ? n : p.q_cap;
     }
     return x_owned_checked(p);
@@ -158,14 +172,130 @@ template <int MODE> __device__ __forceinline__ uint32_t x_value(const XParams &p
         uint64_t v = 0;
         for (uint32_t t = (row < p.world ? row : 0u); t < (row < p.world ? row + 1u : p.world); t++) {
             const uint32_t *b = x_block(p.recv, p, t);
-            v += (uint64_t)b[X_HDR + idx] * x_words((int32_t)b[X_HDR + p.q_cap + idx]);
+            v += (uint64_t)x_counts(b)[idx] * x_words((int32_t)x_sizes(b, p)[idx]);
         }
         return x_sat32(v);
     }
-    if (row < p.world) return x_block(p.recv, p, row)[X_HDR + idx];
+    if (row < p.world) return x_counts(x_block(p.recv, p, row))[idx];
     uint32_t v = 0;
-    for (uint32_t t = 0; t < p.world; t++) v += x_block(p.recv, p, t)[X_HDR + idx];
+    for (uint32_t t = 0; t < p.world; t++) v += x_counts(x_block(p.recv, p, t))[idx];
     return v;
+}
+// item idx of a row and its exclusive offset o within the row: where the copy kernels will find the query's data
+template <int MODE> __device__ __forceinline__ void x_store(const XParams &p, uint32_t row, uint64_t idx, uint32_t v, uint64_t o)
+{
+    if (MODE == 0) {
+        x_counts(x_block(p.send, p, row))[idx] = v;
+        p.dst_off[(uint64_t)row * p.q_cap + idx] = x_sat32(o);
+    } else if (MODE == 2) {
+        x_sizes(x_block(p.send, p, row), p)[idx] = (uint32_t)p.qinfo[row + idx * p.world].size;
+        p.dst_boff[(uint64_t)row * p.q_cap + idx] = o;
+    } else if (row < p.world) {
+        if (MODE == 1) p.src_off[(uint64_t)row * p.q_cap + idx] = x_sat32(o);
+        else p.src_boff[(uint64_t)row * p.q_cap + idx] = o;
+    } else if (MODE == 1) {
+        p.ent_off[idx] = o;
+    } else {
+        p.ent_boff[idx] = o;
+        // all shards translate alike: every block must carry the same SizeInKmer, or they are not one batch
+        const uint32_t sz = x_sizes(x_block(p.recv, p, 0), p)[idx];
+        bool same = true;
+        for (uint32_t t = 1; t < p.world; t++) same = same && x_sizes(x_block(p.recv, p, t), p)[idx] == sz;
+        p.m_size[idx] = (int32_t)sz;
+        if (!same) { atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP); *p.d_nq_owned = 0u; }
+    }
+}
+// one tile of a row on top of `tbase`: the items' offsets stored; returns the tile's total
+template <int MODE> __device__ __forceinline__ uint64_t x_tile_apply(const XParams &p, uint32_t row, uint32_t n, uint64_t base, uint64_t tbase)
+{
+    uint32_t v[X_ITEMS];
+    uint64_t ex[X_ITEMS];
+#pragma unroll
+    for (int i = 0; i < X_ITEMS; i++) {
+        const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
+        v[i] = idx < n ? x_value<MODE>(p, row, idx) : 0u;
+    }
+    const uint64_t tot = x_tile_scan(v, ex);
+#pragma unroll
+    for (int i = 0; i < X_ITEMS; i++) {
+        const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
+        if (idx < n) x_store<MODE>(p, row, idx, v[i], tbase + ex[i]);
+    }
+    return tot;
+}
+
+// ---- what one thread writes once a row's total is known -----------------------------------------------------------------
+// pack: the header of destination d's block from its entry total.  (X_NEED_MAX: x_pack_copy_kernel, once all W blocks have
+// their X_NEED; the bitmap words: x_pack_bits_headers.)
+__device__ __forceinline__ void x_pack_header(const XParams &p, uint32_t d, uint64_t total)
+{
+    const uint32_t nq = *p.d_nq;
+    uint32_t n_owned = x_owned_by(nq, d, p.world);
+    uint32_t st = 0;
+    if (n_owned > p.q_cap) { n_owned = p.q_cap; st = XS_OVERFLOW; }
+    if (total > p.e_cap) st = XS_OVERFLOW;
+    uint32_t *blk = x_block(p.send, p, d);
+    blk[X_ENTRIES] = total > p.e_cap ? 0u : (uint32_t)total;
+    // a search that ran out of a workspace bound (hit pool, G-tier arena or table) has written empty lists for the
+    // queries it could not finish: every owner must know, or it would merge them into a result that looks complete
+    blk[X_STATUS] = st | (p.with_fp ? XS_FIRST_POS : 0u) | ((p.src_status && *p.src_status) ? XS_SENDER_FAILED : 0u);
+    blk[X_NQ] = nq;
+    blk[X_OWNED] = n_owned;
+    blk[X_NEED] = x_sat32(total);
+    blk[X_NEED_MAX] = blk[X_BITS_NEED] = blk[X_BITS_NEED_MAX] = 0u;
+}
+// pack, arrays = 4: the bitmap sections' words of all W headers from their totals; a section that does not fit sets the
+// overflow bit as the entries do (x_pack_copy_kernel spreads it to XS_SENDER_OVERFLOW in every block of this sender)
+__device__ __forceinline__ void x_pack_bits_headers(const XParams &p, const uint64_t *total)
+{
+    uint32_t mx = 0;
+    for (uint32_t d = 0; d < p.world; d++) {
+        uint32_t *blk = x_block(p.send, p, d);
+        blk[X_BITS_NEED] = x_sat32(total[d]);
+        blk[X_STATUS] |= XS_BITMAPS | (total[d] > p.p_cap ? XS_OVERFLOW : 0u);
+        mx = blk[X_BITS_NEED] > mx ? blk[X_BITS_NEED] : mx;
+    }
+    for (uint32_t d = 0; d < p.world; d++) x_block(p.send, p, d)[X_BITS_NEED_MAX] = mx;
+}
+// unpack: everything the owner derives from the W received headers and the entry total -- the statistics, the batch's
+// status, and how many owned queries the merge may read
+__device__ __forceinline__ void x_owner_verdict(const XParams &p, uint64_t total)
+{
+    const uint32_t n_owned = x_owned_checked(p);
+    p.ent_off[n_owned] = total;
+    uint32_t st = total > p.m_cap ? 1u : 0u, peer = 0u, need = 0;
+    for (uint32_t t = 0; t < p.world; t++) {
+        const uint32_t *bh = x_block(p.recv, p, t);
+        const uint32_t b1 = bh[X_STATUS];
+        if (b1 & (XS_OVERFLOW | XS_SENDER_OVERFLOW)) st = 1u;  // this block, or another block of the same sender, did not fit
+        peer |= b1 & XS_SENDER_FAILED;
+        need = bh[X_NEED_MAX] > need ? bh[X_NEED_MAX] : need;
+        if (p.with_fp && !(b1 & XS_FIRST_POS)) st = 1u;  // the owner wants first positions the sender did not pack: an error, not zeros
+    }
+    if (p.stats) { p.stats[0] = x_block(p.recv, p, 0)[X_NQ]; p.stats[1] = need; p.stats[2] = st; p.stats[3] = 0; }
+    if (!x_headers_agree(p)) st = 1u;  // ranks on different batches, or a stale / garbled block
+    if (st) atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP);
+    if (peer) atomicOr(p.status, (uint32_t)ST_PEER_FAILED);
+    // a block that overflowed carries counts without entries: nothing is merged (the batch fails with
+    // KAAMER_E_CAPACITY at kaamer_workspace_finish), and nothing may be read past the buffers
+    *p.d_nq_owned = (st | peer) ? 0u : n_owned;
+}
+// unpack, arrays = 4: the same over the bitmap words of the headers (after x_owner_verdict: it may only take d_nq_owned back)
+__device__ __forceinline__ void x_owner_verdict_bits(const XParams &p, uint64_t total)
+{
+    p.ent_boff[x_owned_checked(p)] = total;
+    uint32_t need = 0, povf = 0, bad = total > p.mb_cap ? 1u : 0u;
+    for (uint32_t t = 0; t < p.world; t++) {
+        const uint32_t *bh = x_block(p.recv, p, t);
+        need = bh[X_BITS_NEED_MAX] > need ? bh[X_BITS_NEED_MAX] : need;
+        if (bh[X_BITS_NEED] > p.p_cap || bh[X_BITS_NEED_MAX] > p.p_cap) povf = 1u;
+        if (!(bh[X_STATUS] & XS_BITMAPS)) bad = 1u;  // the owner wants bitmaps the sender did not pack: an error, not empty bitmaps
+    }
+    if (p.pstats) { p.pstats[0] = need; p.pstats[1] = povf; }
+    if (bad | povf) {
+        atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP);
+        *p.d_nq_owned = 0u;
+    }
 }
 
 template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_sums_kernel(XParams p)
@@ -208,82 +338,10 @@ template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_top_kernel
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
-    if (MODE == 2) {
-        // the bitmap sections: [6] = words this block needed, [7] = the largest [6] of the sender's W blocks, bit 4 =
-        // positions inside; a section that does not fit sets the overflow bit as the entries do (x_pack_copy_kernel
-        // spreads it to bit 3 of every block of this sender)
-        uint32_t mx = 0;
-        for (uint32_t d = 0; d < p.world; d++) {
-            uint32_t *blk = x_block(p.send, p, d);
-            const uint64_t need = s_total[d];
-            blk[6] = x_sat32(need);
-            blk[1] |= 16u | (need > p.p_cap ? 1u : 0u);
-            mx = blk[6] > mx ? blk[6] : mx;
-        }
-        for (uint32_t d = 0; d < p.world; d++) x_block(p.send, p, d)[7] = mx;
-        return;
-    }
-    if (MODE == 3) {
-        const uint32_t W = p.world;
-        const uint32_t n_owned = x_owned_checked(p);
-        const uint64_t carry = s_total[W];
-        p.ent_boff[n_owned] = carry;
-        uint32_t need = 0, povf = 0, bad = carry > p.mb_cap ? 1u : 0u;
-        for (uint32_t t = 0; t < W; t++) {
-            const uint32_t *bh = x_block(p.recv, p, t);
-            need = bh[7] > need ? bh[7] : need;
-            if (bh[6] > p.p_cap || bh[7] > p.p_cap) povf = 1u;
-            if (!(bh[1] & 16u)) bad = 1u;  // the owner wants bitmaps the sender did not pack: an error, not empty bitmaps
-        }
-        if (p.pstats) { p.pstats[0] = need; p.pstats[1] = povf; }
-        if (bad | povf) {
-            atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP);
-            *p.d_nq_owned = 0u;
-        }
-        return;
-    }
-    if (MODE == 0) {
-        const uint32_t nq = *p.d_nq;
-        for (uint32_t d = 0; d < p.world; d++) {
-            const uint64_t carry = s_total[d];
-            uint32_t n_owned = nq > d ? (nq - d + p.world - 1) / p.world : 0u;
-            uint32_t st = 0;
-            if (n_owned > p.q_cap) { n_owned = p.q_cap; st = 1; }
-            if (carry > p.e_cap) st = 1;
-            uint32_t *blk = x_block(p.send, p, d);
-            blk[0] = carry > p.e_cap ? 0u : (uint32_t)carry;
-            // a search that ran out of a workspace bound (hit pool, G-tier arena or table) has written empty lists for the
-            // queries it could not finish: every owner must know, or it would merge them into a result that looks complete
-            blk[1] = st | (p.with_fp ? 2u : 0u) | ((p.src_status && *p.src_status) ? 4u : 0u);
-            blk[2] = nq;
-            blk[3] = n_owned;
-            blk[4] = carry > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry;
-            blk[5] = blk[6] = blk[7] = 0u;  // [5]: x_pack_copy_kernel, once all W blocks have their [4]
-        }
-    } else {
-        const uint32_t W = p.world;
-        const uint32_t n_owned = x_owned_checked(p);
-        const uint64_t carry = s_total[W];
-        p.ent_off[n_owned] = carry;
-        uint32_t st = carry > p.m_cap ? 1u : 0u, peer = 0u;
-        uint32_t need = 0;
-        for (uint32_t t = 0; t < W; t++) {
-            const uint32_t *bh = x_block(p.recv, p, t);
-            const uint32_t b1 = bh[1];
-            st |= (b1 & 1u) | ((b1 >> 3) & 1u);  // this block, or another block of the same sender, did not fit
-            peer |= b1 & 4u;
-            need = bh[5] > need ? bh[5] : need;
-            if (p.with_fp && !(b1 & 2u)) st |= 1u;  // the owner wants first positions the sender did not pack: an error, not zeros
-        }
-        if (p.stats) { p.stats[0] = x_block(p.recv, p, 0)[2]; p.stats[1] = need; p.stats[2] = st; p.stats[3] = 0; }
-        if (!x_headers_agree(p)) st |= 1u;  // ranks on different batches, or a stale / garbled block
-        if (st) atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP);
-        if (peer) atomicOr(p.status, (uint32_t)ST_PEER_FAILED);
-        st |= peer;
-        // a block that overflowed carries counts without entries: nothing is merged (the batch fails with
-        // KAAMER_E_CAPACITY at kaamer_workspace_finish), and nothing may be read past the buffers
-        *p.d_nq_owned = st ? 0u : n_owned;
-    }
+    if (MODE == 0) for (uint32_t d = 0; d < p.world; d++) x_pack_header(p, d, s_total[d]);
+    if (MODE == 1) x_owner_verdict(p, s_total[p.world]);
+    if (MODE == 2) x_pack_bits_headers(p, s_total);
+    if (MODE == 3) x_owner_verdict_bits(p, s_total[p.world]);
 }
 
 template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_apply_kernel(XParams p)
@@ -291,92 +349,24 @@ template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_apply_kern
     const uint32_t row = blockIdx.y, tile = blockIdx.x;
     const uint32_t n = x_items<MODE>(p, row);
     const uint64_t base = (uint64_t)tile * X_TILE;
-    if (base >= n) return;
-    uint32_t v[X_ITEMS];
-    uint64_t ex[X_ITEMS];
-#pragma unroll
-    for (int i = 0; i < X_ITEMS; i++) {
-        const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
-        v[i] = idx < n ? x_value<MODE>(p, row, idx) : 0u;
-    }
-    x_tile_scan(v, ex);
-    const uint64_t tbase = p.tile_sum[(uint64_t)row * p.n_tiles + tile];
-#pragma unroll
-    for (int i = 0; i < X_ITEMS; i++) {
-        const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
-        if (idx >= n) continue;
-        const uint64_t o = tbase + ex[i];
-        if (MODE == 2) {
-            const uint64_t q = row + idx * p.world;
-            x_block(p.send, p, row)[X_HDR + p.q_cap + idx] = (uint32_t)p.qinfo[q].size;
-            p.dst_boff[(uint64_t)row * p.q_cap + idx] = o;
-        } else if (MODE == 3) {
-            if (row < p.world) {
-                p.src_boff[(uint64_t)row * p.q_cap + idx] = o;
-            } else {
-                p.ent_boff[idx] = o;
-                // all shards translate alike: every block must carry the same SizeInKmer, or they are not one batch
-                const uint32_t sz = x_block(p.recv, p, 0)[X_HDR + p.q_cap + idx];
-                bool same = true;
-                for (uint32_t t = 1; t < p.world; t++) same = same && x_block(p.recv, p, t)[X_HDR + p.q_cap + idx] == sz;
-                p.m_size[idx] = (int32_t)sz;
-                if (!same) { atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP); *p.d_nq_owned = 0u; }
-            }
-        } else if (MODE == 0) {
-            x_block(p.send, p, row)[X_HDR + idx] = v[i];
-            p.dst_off[(uint64_t)row * p.q_cap + idx] = o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o;
-        } else if (row < p.world) {
-            p.src_off[(uint64_t)row * p.q_cap + idx] = o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o;
-        } else {
-            p.ent_off[idx] = o;
-        }
-    }
+    if (base < n) x_tile_apply<MODE>(p, row, n, base, p.tile_sum[(uint64_t)row * p.n_tiles + tile]);
 }
 
-// small batches (a few tiles): one workgroup per destination rank walks its tiles with a carry -- one launch instead of three
-__global__ __launch_bounds__(X_BLOCK) void x_pack_scan_small_kernel(XParams p)
+// small batches (up to X_SMALL_TILES tiles per row), modes 0 and 1: one workgroup per row walks its tiles with a carry --
+// one launch instead of three
+template <int MODE> __global__ __launch_bounds__(X_BLOCK) void x_scan_small_kernel(XParams p)
 {
     static_assert(SCAN_BLOCK == X_BLOCK, "block_exclusive_scan is written for 1024 threads");
-    const uint32_t d = blockIdx.x, W = p.world;
-    const uint32_t nq = *p.d_nq;
-    uint32_t n_owned = nq > d ? (nq - d + W - 1) / W : 0u;
-    uint32_t st = 0;
-    if (n_owned > p.q_cap) { n_owned = p.q_cap; st = 1; }
-    uint32_t *blk = x_block(p.send, p, d);
-    uint32_t *doff = p.dst_off + (uint64_t)d * p.q_cap;
+    const uint32_t row = blockIdx.x;
+    const uint32_t n = x_items<MODE>(p, row);
     uint64_t carry = 0;
-    for (uint64_t base = 0; base < n_owned; base += X_TILE) {
-        uint32_t v[X_ITEMS];
-        uint64_t ex[X_ITEMS];
-#pragma unroll
-        for (int i = 0; i < X_ITEMS; i++) {
-            const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
-            v[i] = idx < n_owned ? p.hit_cnt[d + idx * W] : 0u;
-        }
-        const uint64_t tot = x_tile_scan(v, ex);
-#pragma unroll
-        for (int i = 0; i < X_ITEMS; i++) {
-            const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
-            if (idx < n_owned) {
-                blk[X_HDR + idx] = v[i];
-                const uint64_t o = carry + ex[i];
-                doff[idx] = o > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)o;
-            }
-        }
-        carry += tot;
+    for (uint64_t base = 0; base < n; base += X_TILE) {
+        carry += x_tile_apply<MODE>(p, row, n, base, carry);
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        if (carry > p.e_cap) st = 1;
-        blk[0] = carry > p.e_cap ? 0u : (uint32_t)carry;
-        // a search that ran out of a workspace bound (hit pool, G-tier arena or table) has written empty lists for the queries
-        // it could not finish: every owner must know, or it would merge them into a result that looks complete
-        blk[1] = st | (p.with_fp ? 2u : 0u) | ((p.src_status && *p.src_status) ? 4u : 0u);
-        blk[2] = nq;
-        blk[3] = n_owned;
-        blk[4] = carry > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry;
-        blk[5] = blk[6] = blk[7] = 0u;  // [5]: x_pack_copy_kernel, once all W blocks have their [4]
-    }
+    if (threadIdx.x != 0) return;
+    if (MODE == 0) x_pack_header(p, row, carry);
+    else if (row == p.world) x_owner_verdict(p, carry);
 }
 
 // X_GROUP lanes per query: its hit list into the block of its owner.  (A whole wave per query left 49 of 64 lanes
@@ -386,29 +376,38 @@ __global__ __launch_bounds__(X_BLOCK) void x_pack_scan_small_kernel(XParams p)
 #define X_GROUP 16u
 #define X_GROUP_WIDE 64u
 #define X_WIDE_QUERIES 262144u   /* batches of at most this many queries use the wide form */
-template <uint32_t X_GROUP_T>
-__global__ __launch_bounds__(256) void x_pack_copy_kernel(XParams p)
+#define X_COPY_BLOCK 256
+// this thread's place in a copy kernel: the first query of its group of LANES lanes, the stride to the group's next
+// query, and its lane within the group
+template <uint32_t LANES> struct XLanes {
+    uint64_t first, stride;
+    uint32_t lane;
+    __device__ __forceinline__ XLanes()
+        : first(((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES), stride(((uint64_t)gridDim.x * blockDim.x) / LANES),
+          lane(threadIdx.x & (LANES - 1u)) {}
+};
+
+template <uint32_t LANES>
+__global__ __launch_bounds__(X_COPY_BLOCK) void x_pack_copy_kernel(XParams p)
 {
-    constexpr uint32_t X_GROUP_ = X_GROUP_T;
-    const uint32_t nq = *p.d_nq, W = p.world, gl = threadIdx.x & (X_GROUP_ - 1u);
+    const uint32_t nq = *p.d_nq, W = p.world;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // the scans (earlier launches) have left every block's need in [4]: the sender's largest goes into every header,
+        // the scans (earlier launches) have left every block's need in X_NEED: the sender's largest goes into every header,
         // and so does the fact that one of its blocks did not fit (no thread of this kernel reads these words)
         uint32_t mx = 0, any = 0;
         for (uint32_t d = 0; d < W; d++) {
             const uint32_t *b = x_block(p.send, p, d);
-            mx = b[4] > mx ? b[4] : mx;
-            any |= b[1] & 1u;
+            mx = b[X_NEED] > mx ? b[X_NEED] : mx;
+            any |= b[X_STATUS] & XS_OVERFLOW;
         }
         for (uint32_t d = 0; d < W; d++) {
             uint32_t *b = x_block(p.send, p, d);
-            b[5] = mx;
-            if (any) b[1] |= 8u;
+            b[X_NEED_MAX] = mx;
+            if (any) b[X_STATUS] |= XS_SENDER_OVERFLOW;
         }
     }
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / X_GROUP_;
-    const uint64_t n_grp = ((uint64_t)gridDim.x * blockDim.x) / X_GROUP_;
-    for (uint64_t q = grp; q < nq; q += n_grp) {
+    const XLanes<LANES> g;
+    for (uint64_t q = g.first; q < nq; q += g.stride) {
         const uint32_t d = (uint32_t)(q % W);
         const uint64_t i = q / W;
         if (i >= p.q_cap) continue;
@@ -418,7 +417,7 @@ __global__ __launch_bounds__(256) void x_pack_copy_kernel(XParams p)
         if (o + n > p.e_cap) continue;  // over capacity: flagged by the scan kernel
         const uint64_t s = p.hit_off[q];
         uint32_t *blk = x_block(p.send, p, d) + p.ent_base;
-        for (uint32_t t = gl; t < n; t += X_GROUP_) {
+        for (uint32_t t = g.lane; t < n; t += LANES) {
             blk[o + t] = p.pid[s + t];
             blk[p.e_cap + o + t] = p.km[s + t];
             if (p.with_fp) blk[2 * p.e_cap + o + t] = p.fp[s + t];
@@ -426,78 +425,22 @@ __global__ __launch_bounds__(256) void x_pack_copy_kernel(XParams p)
     }
 }
 
-// workgroups 0..W-1: per source, where each owned query's entries start inside that source's block;
-// workgroup W: entries per owned query over all sources -> ent_off (what the merge reads)
-__global__ __launch_bounds__(X_BLOCK) void x_unpack_scan_small_kernel(XParams p)
-{
-    const uint32_t s = blockIdx.x, W = p.world;
-    const uint32_t n_owned = x_owned_checked(p);
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n_owned; base += X_TILE) {
-        uint32_t v[X_ITEMS];
-        uint64_t ex[X_ITEMS];
-#pragma unroll
-        for (int i = 0; i < X_ITEMS; i++) {
-            const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
-            v[i] = 0u;
-            if (idx < n_owned) {
-                if (s < W) v[i] = x_block(p.recv, p, s)[X_HDR + idx];
-                else for (uint32_t t = 0; t < W; t++) v[i] += x_block(p.recv, p, t)[X_HDR + idx];
-            }
-        }
-        const uint64_t tot = x_tile_scan(v, ex);
-#pragma unroll
-        for (int i = 0; i < X_ITEMS; i++) {
-            const uint64_t idx = base + (uint64_t)threadIdx.x * X_ITEMS + i;
-            if (idx < n_owned) {
-                if (s < W) p.src_off[(uint64_t)s * p.q_cap + idx] = (uint32_t)(carry + ex[i]);
-                else p.ent_off[idx] = carry + ex[i];
-            }
-        }
-        carry += tot;
-        __syncthreads();
-    }
-    if (s == W && threadIdx.x == 0) {
-        p.ent_off[n_owned] = carry;
-        uint32_t st = carry > p.m_cap ? 1u : 0u, peer = 0u;
-        uint32_t need = 0;
-        for (uint32_t t = 0; t < W; t++) {
-            const uint32_t *bh = x_block(p.recv, p, t);
-            const uint32_t b1 = bh[1];
-            st |= (b1 & 1u) | ((b1 >> 3) & 1u);  // this block, or another block of the same sender, did not fit
-            peer |= b1 & 4u;
-            need = bh[5] > need ? bh[5] : need;
-            if (p.with_fp && !(b1 & 2u)) st |= 1u;  // the owner wants first positions the sender did not pack: an error, not zeros
-        }
-        if (p.stats) { p.stats[0] = x_block(p.recv, p, 0)[2]; p.stats[1] = need; p.stats[2] = st; p.stats[3] = 0; }
-        if (!x_headers_agree(p)) st |= 1u;  // ranks on different batches, or a stale / garbled block
-        if (st) atomicOr(p.status, (uint32_t)ST_EXCHANGE_CAP);
-        if (peer) atomicOr(p.status, (uint32_t)ST_PEER_FAILED);
-        st |= peer;
-        // a block that overflowed carries counts without entries: nothing is merged (the batch fails with
-        // KAAMER_E_CAPACITY at kaamer_workspace_finish), and nothing may be read past the buffers
-        *p.d_nq_owned = st ? 0u : n_owned;
-    }
-}
-
 // X_GROUP lanes per owned query: the entries of all sources, source after source
-template <uint32_t X_GROUP_T>
-__global__ __launch_bounds__(256) void x_unpack_copy_kernel(XParams p)
+template <uint32_t LANES>
+__global__ __launch_bounds__(X_COPY_BLOCK) void x_unpack_copy_kernel(XParams p)
 {
-    constexpr uint32_t X_GROUP_ = X_GROUP_T;
-    const uint32_t W = p.world, gl = threadIdx.x & (X_GROUP_ - 1u);
+    const uint32_t W = p.world;
     const uint32_t n_owned = x_owned_checked(p);
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / X_GROUP_;
-    const uint64_t n_grp = ((uint64_t)gridDim.x * blockDim.x) / X_GROUP_;
-    for (uint64_t i = grp; i < n_owned; i += n_grp) {
+    const XLanes<LANES> g;
+    for (uint64_t i = g.first; i < n_owned; i += g.stride) {
         uint64_t dst = p.ent_off[i];
         for (uint32_t s = 0; s < W; s++) {
             const uint32_t *blk = x_block(p.recv, p, s);
-            const uint32_t n = blk[X_HDR + i];
+            const uint32_t n = x_counts(blk)[i];
             const uint64_t o = p.src_off[(uint64_t)s * p.q_cap + i];
             if (o + n > p.e_cap || dst + n > p.m_cap) break;  // flagged by the scan kernel
             const uint32_t *ent = blk + p.ent_base;
-            for (uint32_t t = gl; t < n; t += X_GROUP_) {
+            for (uint32_t t = g.lane; t < n; t += LANES) {
                 p.m_pid[dst + t] = ent[o + t];
                 p.m_km[dst + t] = ent[p.e_cap + o + t];
                 if (p.with_fp) p.m_fp[dst + t] = ent[2 * p.e_cap + o + t];
@@ -511,17 +454,15 @@ __global__ __launch_bounds__(256) void x_unpack_copy_kernel(XParams p)
 // X_GROUP lanes per query: the bitmaps of its hits, in hit-list order, after the bitmaps of the query before it in the
 // block (hit j of owned query i at dst_boff[i] + j * ceil(SizeInKmer_i / 64)).  The search laid a query's bitmaps out at
 // pos_off[hit], words = ceil(QInfo.size / 64).
-template <uint32_t X_GROUP_T>
-__global__ __launch_bounds__(256) void x_pack_bits_kernel(XParams p)
+template <uint32_t LANES>
+__global__ __launch_bounds__(X_COPY_BLOCK) void x_pack_bits_kernel(XParams p)
 {
-    constexpr uint32_t X_GROUP_ = X_GROUP_T;
     // a search that failed (its bitmap storage included: then pos_off was never laid out) sends no bitmaps; its blocks
-    // carry status bit 2 and the batch fails on every rank
+    // carry XS_SENDER_FAILED and the batch fails on every rank
     if (p.src_status && *p.src_status) return;
-    const uint32_t nq = *p.d_nq, W = p.world, gl = threadIdx.x & (X_GROUP_ - 1u);
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / X_GROUP_;
-    const uint64_t n_grp = ((uint64_t)gridDim.x * blockDim.x) / X_GROUP_;
-    for (uint64_t q = grp; q < nq; q += n_grp) {
+    const uint32_t nq = *p.d_nq, W = p.world;
+    const XLanes<LANES> g;
+    for (uint64_t q = g.first; q < nq; q += g.stride) {
         const uint32_t d = (uint32_t)(q % W);
         const uint64_t i = q / W;
         if (i >= p.q_cap) continue;
@@ -532,7 +473,7 @@ __global__ __launch_bounds__(256) void x_pack_bits_kernel(XParams p)
         if (o + tot > p.p_cap) continue;  // over capacity: flagged by the scan kernel
         const uint64_t s = p.hit_off[q];
         unsigned long long *dst = x_bits(x_block(p.send, p, d), p) + o;
-        for (uint64_t t = gl; t < tot; t += X_GROUP_) {
+        for (uint64_t t = g.lane; t < tot; t += LANES) {
             const uint64_t h = t / w;
             dst[t] = p.pos_bits[p.pos_off[s + h] + (t - h * w)];
         }
@@ -542,24 +483,22 @@ __global__ __launch_bounds__(256) void x_pack_bits_kernel(XParams p)
 // X_GROUP lanes per owned query: the bitmaps of all sources, source after source -- entry k of the query's unpacked
 // entries (ent_off) has its bitmap at ent_boff[i] + k * words.  Nothing when the headers, the sizes or a section failed
 // (d_nq_owned = 0).
-template <uint32_t X_GROUP_T>
-__global__ __launch_bounds__(256) void x_unpack_bits_kernel(XParams p)
+template <uint32_t LANES>
+__global__ __launch_bounds__(X_COPY_BLOCK) void x_unpack_bits_kernel(XParams p)
 {
-    constexpr uint32_t X_GROUP_ = X_GROUP_T;
-    const uint32_t W = p.world, gl = threadIdx.x & (X_GROUP_ - 1u);
+    const uint32_t W = p.world;
     const uint32_t n_owned = *p.d_nq_owned;
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / X_GROUP_;
-    const uint64_t n_grp = ((uint64_t)gridDim.x * blockDim.x) / X_GROUP_;
-    for (uint64_t i = grp; i < n_owned; i += n_grp) {
+    const XLanes<LANES> g;
+    for (uint64_t i = g.first; i < n_owned; i += g.stride) {
         const uint32_t w = x_words(p.m_size[i]);
         uint64_t dst = p.ent_boff[i];
         for (uint32_t s = 0; s < W && w; s++) {
             const uint32_t *blk = x_block(p.recv, p, s);
-            const uint64_t tot = (uint64_t)blk[X_HDR + i] * w;
+            const uint64_t tot = (uint64_t)x_counts(blk)[i] * w;
             const uint64_t o = p.src_boff[(uint64_t)s * p.q_cap + i];
             if (o + tot > p.p_cap || dst + tot > p.mb_cap) break;  // flagged by the scan kernel
             const unsigned long long *src = x_bits(blk, p) + o;
-            for (uint64_t t = gl; t < tot; t += X_GROUP_) p.m_bits[dst + t] = src[t];
+            for (uint64_t t = g.lane; t < tot; t += LANES) p.m_bits[dst + t] = src[t];
             dst += tot;
         }
     }
@@ -651,4 +590,40 @@ __global__ __launch_bounds__(64) void x_or_bits_kernel(XParams p)
         }
         __syncthreads();
     }
+}
+
+// ---- the step's state in a workspace (host): what XParams points at, allocated on first use ------------------------------
+// The block layout may change from batch to batch within the buffers' capacity, so the buffers only ever grow.
+template <class T> struct XBuf { T *p; size_t cap; };
+struct XStatsSlot {             // what the W headers of one merge said, as kaamer_exchange_stats(_positions) return it
+    unsigned long long stats[4];   // {queries of the batch, largest block any pair of ranks needed, a block overflowed, 0}
+    unsigned long long pstats[2];  // {largest bitmap need between any pair of ranks, a bitmap section overflowed}
+};
+struct XState {
+    // pack: where each query's entries / bitmaps start inside its block
+    XBuf<uint32_t> dst_off;
+    XBuf<uint64_t> dst_boff;
+    // unpack: offsets per (source, owned query), the owned queries' entries in one piece, the header statistics
+    XBuf<uint32_t> src_off, nq_owned, pid, km, fp;
+    XBuf<uint64_t> ent_off;
+    XBuf<unsigned long long> stats;
+    // unpack with bitmaps: offsets, sizes, the bitmaps, the OR-merge's scratch
+    XBuf<uint64_t> src_boff, ent_boff, mdst;
+    XBuf<int32_t> msize;
+    XBuf<unsigned long long> mbits, gtab, pstats;
+    XBuf<uint64_t> tiles;       // tile sums of the tiled scans
+    XStatsSlot *h_stats;        // pinned: two slots, slot = merge sequence number & 1
+    hipEvent_t ev_stats[2];
+    uint64_t merge_seq;         // merges enqueued on this workspace
+};
+static void x_state_free(XState &x)
+{
+    void *bufs[] = { x.dst_off.p, x.dst_boff.p, x.src_off.p, x.nq_owned.p, x.pid.p, x.km.p, x.fp.p, x.ent_off.p, x.stats.p,
+                     x.src_boff.p, x.ent_boff.p, x.mdst.p, x.msize.p, x.mbits.p, x.gtab.p, x.pstats.p, x.tiles.p };
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    if (x.h_stats) {
+        (void)hipHostFree(x.h_stats);
+        for (hipEvent_t e : x.ev_stats) if (e) (void)hipEventDestroy(e);
+    }
+    x = XState{};
 }

@@ -888,23 +888,7 @@ struct kaamer_workspace {
     uint8_t *d_ta_dirs, *d_ta_ops, *d_ta_ldirs, *d_ta_lops;   // per resident wave: direction slab, operations (wave / long form)
     int *d_ta_lbnd;
     uint64_t ta_dirs_cap, ta_ops_cap, ta_ldirs_cap, ta_lops_cap, ta_lbnd_cap;
-    // exchange step of the sharded index (kaamer_exchange_pack / _merge), allocated on first use
-    // exchange scratch: grow-only (the block layout may change from batch to batch within the buffers' capacity)
-    size_t x_dst_cap, x_src_cap, x_ent_cap, x_m_cap;
-    unsigned long long *d_x_stats;      // {queries, largest block needed, overflow, -} of the last merge's headers
-    unsigned long long *h_x_stats;      // pinned: two slots of 4 words, slot = merge sequence number & 1
-    hipEvent_t ev_x_stats[2];
-    uint64_t x_merge_seq;               // merges enqueued on this workspace
-    uint32_t *d_x_dst_off, *d_x_src_off, *d_x_nq_owned, *d_x_pid, *d_x_km, *d_x_fp;
-    uint64_t *d_x_ent_off;
-    uint64_t *d_x_tiles;                // tile sums of the exchange's tiled scans
-    size_t x_tiles_cap;
-    // blocks with PositionHits bitmaps (arrays = 4): pack offsets; unpack offsets, sizes, bitmaps, OR-merge scratch
-    size_t x_dstb_cap, x_pq_cap, x_pb_cap, x_pbits_cap;
-    uint64_t *d_x_dst_boff, *d_x_src_boff, *d_x_ent_boff, *d_x_mdst;
-    int32_t *d_x_msize;
-    unsigned long long *d_x_mbits, *d_x_gtab;
-    unsigned long long *d_x_pstats;     // {largest bitmap need, a bitmap section overflowed} of the last merge's headers
+    XState x;                           // exchange step of the sharded index (kaamer_exchange_pack / _merge; exchange.hip.inc)
     // reported-only packing of the top-N results (kaamer_search_batch_top), allocated on first use
     uint32_t rep_k;
     uint32_t *d_rep_flag, *d_rep_aalen, *d_rep_query, *d_rep_pid, *d_rep_km, *d_rep_fp;
@@ -1299,21 +1283,19 @@ void kaamer_workspace_free(kaamer_workspace *ws)
                      ws->d_pool_cursor, ws->d_lists, ws->d_list_counts, ws->d_status_out, ws->d_qinfo, ws->d_slots,
                      ws->d_slot_off, ws->d_group_first, ws->d_n_groups, ws->d_pos_words, ws->d_pos_base, ws->d_pos_off, ws->d_pos_bits, ws->d_g_keys,
                      ws->d_counter_replicas, ws->d_counters, ws->d_bsum, ws->d_chain, ws->d_tr_chain, ws->d_sched, ws->d_n_sched, ws->d_group_start, ws->d_lay_total, ws->d_slot_scale, ws->d_top_cnt, ws->d_top_pid, ws->d_top_km, ws->d_top_fp, ws->d_top_trim, ws->d_top_start, ws->d_top_size, ws->d_rep_flag, ws->d_rep_aalen, ws->d_rep_query, ws->d_rep_pid, ws->d_rep_km, ws->d_rep_fp, ws->d_rep_trim, ws->d_rep_rank, ws->d_rep_eoff, ws->d_rep_aoff, ws->d_rep_off, ws->d_rep_q, ws->d_rep_aa, ws->d_hit_off,
-                     ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp, ws->d_x_dst_off, ws->d_x_src_off, ws->d_x_nq_owned, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, ws->d_x_ent_off, ws->d_x_tiles, ws->d_x_stats,
-                     ws->d_x_dst_boff, ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_mdst, ws->d_x_msize, ws->d_x_mbits, ws->d_x_gtab, ws->d_x_pstats,
+                     ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp,
                      ws->d_tp_words, ws->d_tp_len, ws->d_tp_base, ws->d_tp_bits,
                      ws->d_ta_qcodes, ws->d_ta_lay, ws->d_ta_ctr, ws->d_ta_eoff, ws->d_ta_items, ws->d_ta_dirs, ws->d_ta_ops, ws->d_ta_ldirs, ws->d_ta_lops, ws->d_ta_lbnd };
     for (void *b : bufs) if (b) (void)hipFree(b);
-    if (ws->h_x_stats) {
-        (void)hipHostFree(ws->h_x_stats);
-        for (hipEvent_t e : ws->ev_x_stats) if (e) (void)hipEventDestroy(e);
-    }
+    x_state_free(ws->x);
     if (ws->ev) {
         for (hipEvent_t e : *ws->ev) (void)hipEventDestroy(e);
         delete ws->ev;
     }
     delete ws;
 }
+
+uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws) { return ws ? ws->q_cap : 0u; }
 
 int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts, kaamer_workspace **out)
 {
@@ -1525,6 +1507,14 @@ static void launch_layout(kaamer_workspace *ws, uint32_t nq_bound, uint32_t *sta
                            ws->d_nq, ws->d_sched, ws->d_n_sched, cshift);
 }
 
+// the hit arrays of the workspace's current result form: CSR in query order (opts.compact), or the sparse arrays
+struct WsHits { const uint64_t *off; const uint32_t *pid, *km, *fp; };
+static WsHits ws_hits(const kaamer_workspace *ws)
+{
+    if (ws->compact) return { ws->d_csr_off, ws->d_c_pid, ws->d_c_km, ws->d_c_fp };
+    return { ws->d_hit_off, ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp };
+}
+
 // PositionHits layout of the final hit lists: words per query, their scan (d_pos_base), pos_off per hit, bitmaps zeroed.
 // sizes: NULL = the search's own QInfo.size; a merge passes the owned queries' SizeInKmer
 static void launch_pos_layout(kaamer_workspace *ws, uint32_t nq_bound, const int32_t *sizes, uint32_t *status, hipStream_t s)
@@ -1535,7 +1525,7 @@ static void launch_pos_layout(kaamer_workspace *ws, uint32_t nq_bound, const int
     hipLaunchKernelGGL(pos_words_kernel, dim3(gb), dim3(256), 0, s, ws->d_qinfo, sizes, ws->d_q_cnt, ws->d_nq, ws->d_pos_words);
     scan_u32_on(ws, ws->d_pos_words, ws->d_nq, nq_bound, ws->d_pos_base, s);
     hipLaunchKernelGGL(pos_layout_kernel, dim3(ws->n_cu * 8), dim3(256), 0, s, ws->d_qinfo, sizes, ws->d_q_cnt,
-                       ws->compact ? ws->d_csr_off : ws->d_hit_off,
+                       ws_hits(ws).off,
                        ws->d_pos_base, ws->d_nq, ws->d_pos_off, ws->d_pos_bits, ws->bits_cap, status);
 }
 
@@ -1554,10 +1544,11 @@ static void fill_result_hits(const kaamer_workspace *ws, kaamer_device_result *o
 {
     out->d_hit_cnt = ws->d_q_cnt;
     out->hit_capacity = ws->compact ? ws->hit_cap : ws->sparse_cap;
-    out->d_hit_off = ws->compact ? ws->d_csr_off : ws->d_hit_off;
-    out->d_hit_pid = ws->compact ? ws->d_c_pid : ws->d_hit_pid;
-    out->d_hit_kmatch = ws->compact ? ws->d_c_km : ws->d_hit_km;
-    out->d_hit_first_pos = ws->compact ? ws->d_c_fp : ws->d_hit_fp;
+    const WsHits h = ws_hits(ws);
+    out->d_hit_off = h.off;
+    out->d_hit_pid = h.pid;
+    out->d_hit_kmatch = h.km;
+    out->d_hit_first_pos = h.fp;
 }
 
 // whoever consumes the workspace's last search on `stream` first waits for its counting stage, if that ran elsewhere
@@ -1885,18 +1876,16 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     return KAAMER_OK;
 }
 
+// ---- merge of partial hit lists, in two phases: an exchange merge lays out and ORs its bitmaps between them, so that a
+// bitmap bound is reported by the finalize step like every other
 // n_queries / n_entries are host-side bounds when d_n_queries (a device scalar) gives the actual number of queries
-// xpos: an exchange merge of blocks with bitmaps (arrays = 4) -- the merged bitmaps are laid out and ORed together before
-// the finalize step, so that a bitmap bound is reported like every other
-static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, const uint32_t *d_pid, const uint32_t *d_km,
-                             const uint32_t *d_fp, uint32_t n_queries, const uint32_t *d_n_queries, uint64_t n_entries, void *stream,
-                             kaamer_device_result *out, XParams *xpos = nullptr)
+static int merge_enqueue(kaamer_workspace *ws, const uint64_t *d_ent_off, const uint32_t *d_pid, const uint32_t *d_km, const uint32_t *d_fp,
+                         uint32_t n_queries, const uint32_t *d_n_queries, uint64_t n_entries, hipStream_t s)
 {
-    if (!ws || !out || (n_queries && !d_ent_off) || (n_entries && (!d_pid || !d_km || !d_fp)))
+    if (!ws || (n_queries && !d_ent_off) || (n_entries && (!d_pid || !d_km || !d_fp)))
         return kaamer_fail(KAAMER_E_ARG, "merge_device: bad argument");
     if (n_queries > ws->q_cap) return kaamer_fail(KAAMER_E_CAPACITY, "merge of %u queries exceeds the workspace (%u)", n_queries, ws->q_cap);
     if (n_entries > ws->hit_cap) return kaamer_fail(KAAMER_E_CAPACITY, "merge of %llu entries exceeds workspace max_hits", (unsigned long long)n_entries);
-    hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ws->device));
     {
         const int rrc = ws_reset_if_dirty(ws, s);
@@ -1920,19 +1909,12 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
     pg.list = ws_list(ws, LIST_G); pg.list_count = ws->d_list_counts + LIST_G;
     hipLaunchKernelGGL(merge_global_kernel, dim3(g_tier_grid(ws, nq_bound)), dim3(256), 0, s, pg);
     if (ws->compact) launch_compaction(ws, nq_bound, status, s);
-    if (xpos) {
-        launch_pos_layout(ws, nq_bound, xpos->m_size, status, s);
-        xpos->r_nq = ws->d_nq;
-        xpos->r_cnt = ws->d_q_cnt;
-        xpos->r_off = ws->compact ? ws->d_csr_off : ws->d_hit_off;
-        xpos->r_pid = ws->compact ? ws->d_c_pid : ws->d_hit_pid;
-        xpos->r_pos_off = ws->d_pos_off;
-        xpos->r_pos_base = ws->d_pos_base;
-        xpos->r_pos_bits = ws->d_pos_bits;
-        xpos->r_bits_cap = ws->bits_cap;
-        uint32_t gb = nq_bound < (uint32_t)ws->n_cu * 16 ? nq_bound : (uint32_t)ws->n_cu * 16;
-        hipLaunchKernelGGL(x_or_bits_kernel, dim3(gb ? gb : 1), dim3(64), 0, s, *xpos);
-    }
+    return KAAMER_OK;
+}
+
+// the finalize step and the result; with_positions: the caller has laid the merged bitmaps out behind merge_enqueue
+static int merge_finish(kaamer_workspace *ws, hipStream_t s, bool with_positions, kaamer_device_result *out)
+{
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, s, ws->d_counter_replicas, ws->d_counters, ws->d_list_counts,
                        ws->d_status_out, (uint32_t *)nullptr, ws->d_pool_cursor, (uint32_t *)nullptr, 16u, 16u);   // (a merge looks nothing up: the scale
                                                                                                                   // stays, and so does the last search's G-tier count)
@@ -1944,7 +1926,7 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
     out->d_n_queries = ws->d_nq;
     fill_result_hits(ws, out);
     out->d_counters = ws->d_counters;
-    if (xpos) {
+    if (with_positions) {
         out->d_pos_off = ws->d_pos_off;
         out->d_pos_bits = (const uint64_t *)ws->d_pos_bits;
         out->d_pos_base = ws->d_pos_base;
@@ -1955,365 +1937,12 @@ static int merge_device_impl(kaamer_workspace *ws, const uint64_t *d_ent_off, co
 int kaamer_merge_device(kaamer_workspace *ws, const uint64_t *d_ent_off, const uint32_t *d_pid, const uint32_t *d_km,
                         const uint32_t *d_fp, uint32_t n_queries, uint64_t n_entries, void *stream, kaamer_device_result *out)
 {
-    return merge_device_impl(ws, d_ent_off, d_pid, d_km, d_fp, n_queries, nullptr, n_entries, stream, out);
+    if (!out) return kaamer_fail(KAAMER_E_ARG, "merge_device: bad argument");
+    const int rc = merge_enqueue(ws, d_ent_off, d_pid, d_km, d_fp, n_queries, nullptr, n_entries, (hipStream_t)stream);
+    return rc ? rc : merge_finish(ws, (hipStream_t)stream, false, out);
 }
 
-// ---- the exchange step of the sharded index (exchange.hip.inc) --------------------------------------
-int kaamer_exchange_layout_init(uint32_t world, uint32_t rank, uint32_t max_queries, uint64_t max_entries_per_peer,
-                                kaamer_exchange_layout *out)
-{
-    if (!out || world == 0 || world > 64 || rank >= world || max_entries_per_peer == 0 || max_entries_per_peer > 0xFFFFFFF0ull)
-        return kaamer_fail(KAAMER_E_ARG, "exchange_layout_init: bad argument (1 <= world <= 64, rank < world, 0 < entries < 2^32)");
-    memset(out, 0, sizeof *out);
-    out->world = world;
-    out->rank = rank;
-    out->q_cap = (max_queries + world - 1) / world + 1;
-    out->arrays = 3;
-    out->e_cap = (max_entries_per_peer + 3) & ~3ull;
-    out->block_words = (X_HDR + (uint64_t)out->q_cap + 3 * out->e_cap + 3) & ~3ull;
-    return KAAMER_OK;
-}
-
-// blocks with bitmaps (arrays = 4): the section starts at the even word after the three entry arrays, and what is left of
-// the block is its capacity: p_cap = (block_words - bits_off) / 2 u64 words
-static uint64_t x_bits_off(const kaamer_exchange_layout *L) { return (X_HDR + 2ull * L->q_cap + 3ull * L->e_cap + 1) & ~1ull; }
-static uint64_t x_p_cap(const kaamer_exchange_layout *L)
-{
-    const uint64_t o = x_bits_off(L);
-    return L->arrays == 4 && L->block_words > o ? (L->block_words - o) / 2 : 0;
-}
-
-int kaamer_exchange_layout_init_positions(uint32_t world, uint32_t rank, uint32_t max_queries, uint64_t max_entries_per_peer,
-                                          uint64_t max_pos_words_per_peer, kaamer_exchange_layout *out)
-{
-    if (!out || max_pos_words_per_peer == 0 || max_pos_words_per_peer > 0xFFFFFFF0ull)
-        return kaamer_fail(KAAMER_E_ARG, "exchange_layout_init_positions: bad argument (0 < pos words < 2^32)");
-    const int rc = kaamer_exchange_layout_init(world, rank, max_queries, max_entries_per_peer, out);
-    if (rc) return rc;
-    out->arrays = 4;
-    out->block_words = (x_bits_off(out) + 2 * max_pos_words_per_peer + 3) & ~3ull;
-    return KAAMER_OK;
-}
-
-int kaamer_exchange_layout_fit_positions(const kaamer_exchange_layout *cap, uint32_t n_queries, uint64_t entries_per_block,
-                                         uint64_t pos_words_per_block, kaamer_exchange_layout *out)
-{
-    if (!cap || !out || cap->world == 0 || cap->arrays != 4)
-        return kaamer_fail(KAAMER_E_ARG, "exchange_layout_fit_positions: bad argument (a capacity layout of kaamer_exchange_layout_init_positions)");
-    kaamer_exchange_layout L = *cap;
-    const uint64_t q = ((uint64_t)n_queries + cap->world - 1) / cap->world + 1;
-    if (q < L.q_cap) L.q_cap = (uint32_t)q;
-    uint64_t e = (entries_per_block + 3) & ~3ull;
-    if (e < 4) e = 4;
-    if (e < L.e_cap) L.e_cap = e;
-    uint64_t pw = pos_words_per_block < 2 ? 2 : pos_words_per_block;
-    const uint64_t pc = x_p_cap(cap);
-    if (pw > pc) pw = pc;
-    L.block_words = (x_bits_off(&L) + 2 * pw + 3) & ~3ull;
-    if (L.block_words > cap->block_words) L = *cap;   // never beyond what the buffers hold
-    *out = L;
-    return KAAMER_OK;
-}
-
-// scratch of the tiled scans: (world + 1) rows of tile sums
-static int x_tiles(kaamer_workspace *ws, const kaamer_exchange_layout *L, XParams *x)
-{
-    const uint32_t n_tiles = (uint32_t)(((uint64_t)L->q_cap + X_TILE - 1) / X_TILE);
-    const size_t need = (size_t)(L->world + 1) * n_tiles;
-    if (ws->x_tiles_cap < need) {
-        if (ws->d_x_tiles) (void)hipFree(ws->d_x_tiles);
-        ws->d_x_tiles = nullptr; ws->x_tiles_cap = 0;
-        const int rc = dev_alloc(&ws->d_x_tiles, need);
-        if (rc) return rc;
-        ws->x_tiles_cap = need;
-    }
-    x->tile_sum = ws->d_x_tiles;
-    x->n_tiles = n_tiles;
-    return KAAMER_OK;
-}
-
-static void x_fill(XParams &x, const kaamer_exchange_layout *L)
-{
-    memset(&x, 0, sizeof x);
-    x.world = L->world; x.rank = L->rank; x.q_cap = L->q_cap; x.e_cap = L->e_cap; x.block_words = L->block_words;
-    x.ent_base = X_HDR + L->q_cap;
-    if (L->arrays == 4) { x.ent_base += L->q_cap; x.bits_off = x_bits_off(L); x.p_cap = x_p_cap(L); }
-}
-
-int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, uint32_t *d_send, void *stream)
-{
-    if (!ws || !L || !d_send || L->world == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_pack: bad argument");
-    if (L->arrays == 2 && ws->firstpos) return kaamer_fail(KAAMER_E_ARG, "exchange_pack: the layout has no room for the first positions this workspace computes");
-    const bool pos = L->arrays == 4;
-    if (pos && (!ws->want_positions || !ws->firstpos))
-        return kaamer_fail(KAAMER_E_ARG, "exchange_pack: blocks with bitmaps need a search workspace with want_positions = 1 and first_pos = 1");
-    if (pos && x_p_cap(L) == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_pack: the layout has no bitmap section");
-    // (a layout fitted to fewer queries than the batch turns out to have is an overflow like any other: flagged in the
-    // block headers by the scan, reported by every owner)
-    HIPCHK(hipSetDevice(ws->device));
-    { const int jrc = ws_join(ws, (hipStream_t)stream); if (jrc) return jrc; }
-    if (ws->x_dst_cap < (size_t)L->world * L->q_cap) {
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        if (ws->d_x_dst_off) (void)hipFree(ws->d_x_dst_off);
-        ws->d_x_dst_off = nullptr; ws->x_dst_cap = 0;
-        const int rc = dev_alloc(&ws->d_x_dst_off, (size_t)L->world * L->q_cap);
-        if (rc) return rc;
-        ws->x_dst_cap = (size_t)L->world * L->q_cap;
-    }
-    if (pos && ws->x_dstb_cap < (size_t)L->world * L->q_cap) {
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        if (ws->d_x_dst_boff) (void)hipFree(ws->d_x_dst_boff);
-        ws->d_x_dst_boff = nullptr; ws->x_dstb_cap = 0;
-        const int rc = dev_alloc(&ws->d_x_dst_boff, (size_t)L->world * L->q_cap);
-        if (rc) return rc;
-        ws->x_dstb_cap = (size_t)L->world * L->q_cap;
-    }
-    XParams x;
-    x_fill(x, L);
-    x.d_nq = ws->d_nq;
-    x.src_status = ws->d_status_out;  // written by the search's finalize step, earlier on this stream
-    x.hit_off = ws->compact ? ws->d_csr_off : ws->d_hit_off;
-    x.hit_cnt = ws->d_q_cnt;
-    x.pid = ws->compact ? ws->d_c_pid : ws->d_hit_pid;
-    x.km = ws->compact ? ws->d_c_km : ws->d_hit_km;
-    x.fp = ws->compact ? ws->d_c_fp : ws->d_hit_fp;
-    x.with_fp = ws->firstpos ? 1u : 0u;
-    x.send = d_send;
-    x.dst_off = ws->d_x_dst_off;
-    hipStream_t s = (hipStream_t)stream;
-    {
-        const int rc = x_tiles(ws, L, &x);
-        if (rc) return rc;
-    }
-    if (x.n_tiles <= X_SMALL_TILES) {
-        hipLaunchKernelGGL(x_pack_scan_small_kernel, dim3(L->world), dim3(X_BLOCK), 0, s, x);
-    } else {
-        hipLaunchKernelGGL(x_scan_sums_kernel<0>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_top_kernel<0>, dim3(1), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_apply_kernel<0>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
-    }
-    if (pos) {   // the bitmap sections: SizeInKmer per owned query, where each query's bitmaps start, header words [6], [7]
-        x.qinfo = ws->d_qinfo;
-        x.pos_off = ws->d_pos_off;
-        x.pos_bits = ws->d_pos_bits;
-        x.dst_boff = ws->d_x_dst_boff;
-        hipLaunchKernelGGL(x_scan_sums_kernel<2>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_top_kernel<2>, dim3(1), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_apply_kernel<2>, dim3(x.n_tiles, L->world), dim3(X_BLOCK), 0, s, x);
-    }
-    const bool wide = ws->q_cap <= X_WIDE_QUERIES;   // few queries with long lists: a wave per query
-    uint32_t gb = wide ? (ws->q_cap + 3) / 4 : (ws->q_cap + 15) / 16;  // 4 / 16 queries per 256-thread block
-    if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
-    if (gb < 1) gb = 1;
-    if (wide) hipLaunchKernelGGL(x_pack_copy_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
-    else hipLaunchKernelGGL(x_pack_copy_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
-    if (pos) {
-        if (wide) hipLaunchKernelGGL(x_pack_bits_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
-        else hipLaunchKernelGGL(x_pack_bits_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
-    }
-    HIPCHK(hipGetLastError());
-    return KAAMER_OK;
-}
-
-int kaamer_exchange_merge(kaamer_workspace *ws, const kaamer_exchange_layout *L, const uint32_t *d_recv, void *stream,
-                          kaamer_device_result *out)
-{
-    if (!ws || !L || !d_recv || !out || L->world == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_merge: bad argument");
-    if (L->arrays == 2 && ws->firstpos) return kaamer_fail(KAAMER_E_ARG, "exchange_merge: the layout has no room for the first positions this workspace wants");
-    const bool pos = L->arrays == 4;
-    if (pos && (!ws->want_positions || !ws->firstpos))
-        return kaamer_fail(KAAMER_E_ARG, "exchange_merge: blocks with bitmaps need a merge workspace with want_positions = 1 and first_pos = 1");
-    if (pos && x_p_cap(L) == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_merge: the layout has no bitmap section");
-    if (L->q_cap > ws->q_cap) return kaamer_fail(KAAMER_E_CAPACITY, "exchange_merge: %u owned queries exceed the merge workspace (%u)", L->q_cap, ws->q_cap);
-    const uint64_t m_cap = (uint64_t)L->world * L->e_cap;
-    if (m_cap > ws->hit_cap) return kaamer_fail(KAAMER_E_CAPACITY, "exchange_merge: %llu entries exceed the merge workspace's max_hits (%llu)",
-                                                 (unsigned long long)m_cap, (unsigned long long)ws->hit_cap);
-    HIPCHK(hipSetDevice(ws->device));
-    if (ws->x_src_cap < (size_t)L->world * L->q_cap || ws->x_ent_cap < (size_t)L->q_cap + 1 || ws->x_m_cap < (size_t)m_cap || !ws->d_x_nq_owned) {
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        void *bufs[] = { ws->d_x_src_off, ws->d_x_nq_owned, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, ws->d_x_ent_off, ws->d_x_stats };
-        for (void *b : bufs) if (b) (void)hipFree(b);
-        ws->d_x_src_off = ws->d_x_nq_owned = ws->d_x_pid = ws->d_x_km = ws->d_x_fp = nullptr;
-        ws->d_x_ent_off = nullptr; ws->d_x_stats = nullptr;
-        ws->x_src_cap = ws->x_ent_cap = ws->x_m_cap = 0;
-        int rc = dev_alloc(&ws->d_x_src_off, (size_t)L->world * L->q_cap);
-        if (!rc) rc = dev_alloc(&ws->d_x_nq_owned, 1);
-        if (!rc) rc = dev_alloc(&ws->d_x_ent_off, (size_t)L->q_cap + 1);
-        if (!rc) rc = dev_alloc(&ws->d_x_pid, (size_t)m_cap);
-        if (!rc) rc = dev_alloc(&ws->d_x_km, (size_t)m_cap);
-        if (!rc) rc = dev_alloc(&ws->d_x_fp, (size_t)m_cap);
-        if (!rc) rc = dev_alloc(&ws->d_x_stats, 4);
-        if (rc) return rc;
-        ws->x_src_cap = (size_t)L->world * L->q_cap; ws->x_ent_cap = (size_t)L->q_cap + 1; ws->x_m_cap = (size_t)m_cap;
-    }
-    const uint64_t mb_cap = pos ? (uint64_t)L->world * x_p_cap(L) : 0;
-    const size_t pq = (size_t)L->world * L->q_cap + 1;   // per (source, owned query); also bounds the per-query arrays
-    if (pos && (ws->x_pq_cap < pq || ws->x_pb_cap < (size_t)m_cap || ws->x_pbits_cap < (size_t)mb_cap)) {
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        void *bufs[] = { ws->d_x_src_boff, ws->d_x_ent_boff, ws->d_x_msize, ws->d_x_mdst, ws->d_x_gtab, ws->d_x_mbits };
-        for (void *b : bufs) if (b) (void)hipFree(b);
-        ws->d_x_src_boff = ws->d_x_ent_boff = ws->d_x_mdst = nullptr; ws->d_x_msize = nullptr; ws->d_x_gtab = ws->d_x_mbits = nullptr;
-        ws->x_pq_cap = ws->x_pb_cap = ws->x_pbits_cap = 0;
-        int rc = dev_alloc(&ws->d_x_src_boff, pq);
-        if (!rc) rc = dev_alloc(&ws->d_x_ent_boff, pq);
-        if (!rc) rc = dev_alloc(&ws->d_x_msize, pq);
-        if (!rc) rc = dev_alloc(&ws->d_x_mdst, (size_t)m_cap);
-        if (!rc) rc = dev_alloc(&ws->d_x_gtab, 2 * (size_t)m_cap);
-        if (!rc) rc = dev_alloc(&ws->d_x_mbits, (size_t)mb_cap);
-        if (rc) return rc;
-        ws->x_pq_cap = pq; ws->x_pb_cap = (size_t)m_cap; ws->x_pbits_cap = (size_t)mb_cap;
-    }
-    if (!ws->d_x_pstats) {
-        const int rc = dev_alloc(&ws->d_x_pstats, 2);
-        if (rc) return rc;
-    }
-    if (!ws->h_x_stats) {
-        // slots 0, 1: kaamer_exchange_stats (4 words each); then kaamer_exchange_stats_positions (2 words each)
-        if (hipHostMalloc((void **)&ws->h_x_stats, 12 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-            return kaamer_fail(KAAMER_E_NOMEM, "exchange_merge: pinned statistics");
-        memset(ws->h_x_stats, 0, 12 * sizeof(unsigned long long));
-        for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&ws->ev_x_stats[i], hipEventDisableTiming));
-    }
-    hipStream_t s = (hipStream_t)stream;
-    {   // the status word the unpack kernels may set must start from zero
-        const int rrc = ws_reset_if_dirty(ws, s);
-        if (rrc) return rrc;
-        ws->clean = true;
-    }
-    XParams x;
-    x_fill(x, L);
-    x.recv = d_recv;
-    x.src_off = ws->d_x_src_off;
-    x.ent_off = ws->d_x_ent_off;
-    x.d_nq_owned = ws->d_x_nq_owned;
-    x.m_pid = ws->d_x_pid; x.m_km = ws->d_x_km; x.m_fp = ws->d_x_fp;
-    x.with_fp = ws->firstpos ? 1u : 0u;
-    x.m_cap = m_cap;
-    x.stats = ws->d_x_stats;
-    x.status = ws->d_list_counts + SLOT_STATUS;
-    {
-        const int rc = x_tiles(ws, L, &x);
-        if (rc) return rc;
-    }
-    if (x.n_tiles <= X_SMALL_TILES) {
-        hipLaunchKernelGGL(x_unpack_scan_small_kernel, dim3(L->world + 1), dim3(X_BLOCK), 0, s, x);
-    } else {
-        hipLaunchKernelGGL(x_scan_sums_kernel<1>, dim3(x.n_tiles, L->world + 1), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_top_kernel<1>, dim3(1), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_apply_kernel<1>, dim3(x.n_tiles, L->world + 1), dim3(X_BLOCK), 0, s, x);
-    }
-    const bool wide = (uint64_t)L->q_cap * L->world <= X_WIDE_QUERIES;
-    uint32_t gb = wide ? (L->q_cap + 3) / 4 : (L->q_cap + 15) / 16;
-    if (gb > (uint32_t)ws->n_cu * 8) gb = (uint32_t)ws->n_cu * 8;
-    if (gb < 1) gb = 1;
-    if (wide) hipLaunchKernelGGL(x_unpack_copy_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
-    else hipLaunchKernelGGL(x_unpack_copy_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
-    if (pos) {   // the bitmap sections: sizes checked alike in all blocks, offsets per source and per owned query, copy
-        x.src_boff = ws->d_x_src_boff;
-        x.ent_boff = ws->d_x_ent_boff;
-        x.m_size = ws->d_x_msize;
-        x.m_bits = ws->d_x_mbits;
-        x.mb_cap = mb_cap;
-        x.pstats = ws->d_x_pstats;
-        x.m_dst = ws->d_x_mdst;
-        x.g_tab = ws->d_x_gtab;
-        hipLaunchKernelGGL(x_scan_sums_kernel<3>, dim3(x.n_tiles, L->world + 1), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_top_kernel<3>, dim3(1), dim3(X_BLOCK), 0, s, x);
-        hipLaunchKernelGGL(x_scan_apply_kernel<3>, dim3(x.n_tiles, L->world + 1), dim3(X_BLOCK), 0, s, x);
-        if (wide) hipLaunchKernelGGL(x_unpack_bits_kernel<X_GROUP_WIDE>, dim3(gb), dim3(256), 0, s, x);
-        else hipLaunchKernelGGL(x_unpack_bits_kernel<X_GROUP>, dim3(gb), dim3(256), 0, s, x);
-    } else {
-        HIPCHK(hipMemsetAsync(ws->d_x_pstats, 0, 2 * sizeof(unsigned long long), s));
-    }
-    HIPCHK(hipGetLastError());
-    {   // what the W headers said, to the host: read by kaamer_exchange_stats without waiting for the merge itself
-        const int slot = (int)(ws->x_merge_seq & 1u);
-        HIPCHK(hipMemcpyAsync(ws->h_x_stats + 4 * slot, ws->d_x_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(ws->h_x_stats + 8 + 2 * slot, ws->d_x_pstats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ws->ev_x_stats[slot], s));
-        ws->x_merge_seq++;
-    }
-    return merge_device_impl(ws, ws->d_x_ent_off, ws->d_x_pid, ws->d_x_km, ws->d_x_fp, L->q_cap, ws->d_x_nq_owned, m_cap, stream, out,
-                             pos ? &x : nullptr);
-}
-
-uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws) { return ws ? ws->q_cap : 0u; }
-
-int kaamer_exchange_layout_fit(const kaamer_exchange_layout *cap, uint32_t n_queries, uint64_t entries_per_block, int32_t with_first_pos,
-                               kaamer_exchange_layout *out)
-{
-    if (!cap || !out || cap->world == 0) return kaamer_fail(KAAMER_E_ARG, "exchange_layout_fit: bad argument");
-    kaamer_exchange_layout L = *cap;
-    L.arrays = with_first_pos ? 3u : 2u;   // a protein search without -pos sends no first positions: no room for them either
-    const uint64_t q = ((uint64_t)n_queries + cap->world - 1) / cap->world + 1;
-    if (q < L.q_cap) L.q_cap = (uint32_t)q;
-    uint64_t e = (entries_per_block + 3) & ~3ull;
-    if (e < 4) e = 4;
-    if (e < L.e_cap) L.e_cap = e;
-    L.block_words = (X_HDR + (uint64_t)L.q_cap + (uint64_t)L.arrays * L.e_cap + 3) & ~3ull;
-    if (L.block_words > cap->block_words) L = *cap;   // never beyond what the buffers hold
-    *out = L;
-    return KAAMER_OK;
-}
-
-int kaamer_exchange_stats(kaamer_workspace *ws, uint32_t back, uint64_t out[4])
-{
-    if (!ws || !out || back > 1) return kaamer_fail(KAAMER_E_ARG, "exchange_stats: bad argument (back is 0 or 1)");
-    if (ws->x_merge_seq <= back || !ws->h_x_stats) return kaamer_fail(KAAMER_E_ARG, "exchange_stats: no such merge yet");
-    const uint64_t seq = ws->x_merge_seq - 1 - back;
-    const int slot = (int)(seq & 1u);
-    HIPCHK(hipSetDevice(ws->device));
-    HIPCHK(hipEventSynchronize(ws->ev_x_stats[slot]));
-    out[0] = seq;
-    out[1] = ws->h_x_stats[4 * slot + 0];
-    out[2] = ws->h_x_stats[4 * slot + 1];
-    out[3] = ws->h_x_stats[4 * slot + 2];
-    return KAAMER_OK;
-}
-
-// grouped ncclSend / ncclRecv of equal blocks, for hosts that own an RCCL communicator and nothing else to drive it
-// (the library does not link RCCL: the symbols are looked up in the process at first use)
-int kaamer_exchange_stats_positions(kaamer_workspace *ws, uint32_t back, uint64_t out[2])
-{
-    if (!ws || !out || back > 1) return kaamer_fail(KAAMER_E_ARG, "exchange_stats_positions: bad argument (back is 0 or 1)");
-    if (ws->x_merge_seq <= back || !ws->h_x_stats) return kaamer_fail(KAAMER_E_ARG, "exchange_stats_positions: no such merge yet");
-    const int slot = (int)((ws->x_merge_seq - 1 - back) & 1u);
-    HIPCHK(hipSetDevice(ws->device));
-    HIPCHK(hipEventSynchronize(ws->ev_x_stats[slot]));
-    out[0] = ws->h_x_stats[8 + 2 * slot + 0];
-    out[1] = ws->h_x_stats[8 + 2 * slot + 1];
-    return KAAMER_OK;
-}
-
-int kaamer_rccl_alltoall(void *nccl_comm, const void *d_send, void *d_recv, uint64_t bytes_per_peer, uint32_t world, void *stream)
-{
-    typedef int (*grp_t)(void);
-    typedef int (*send_t)(const void *, size_t, int, int, void *, void *);
-    typedef int (*recv_t)(void *, size_t, int, int, void *, void *);
-    static grp_t g_start = nullptr, g_end = nullptr;
-    static send_t g_send = nullptr;
-    static recv_t g_recv = nullptr;
-    if (!nccl_comm || !d_send || !d_recv || world == 0) return kaamer_fail(KAAMER_E_ARG, "rccl_alltoall: bad argument");
-    if (!g_send) {
-        void *h = dlopen(nullptr, RTLD_NOW);
-        void *sym = h ? dlsym(h, "ncclSend") : nullptr;
-        if (!sym) { h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL); if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL); }
-        if (!h) return kaamer_fail(KAAMER_E_HIP, "rccl_alltoall: librccl is not loaded and cannot be opened");
-        g_start = (grp_t)dlsym(h, "ncclGroupStart"); g_end = (grp_t)dlsym(h, "ncclGroupEnd");
-        g_recv = (recv_t)dlsym(h, "ncclRecv");
-        g_send = (send_t)dlsym(h, "ncclSend");
-        if (!g_start || !g_end || !g_send || !g_recv) { g_send = nullptr; return kaamer_fail(KAAMER_E_HIP, "rccl_alltoall: RCCL symbols not found"); }
-    }
-    const int nccl_uint8 = 1;  // ncclUint8 (nccl.h: ncclInt8 = 0, ncclUint8 = 1)
-    int rc = g_start();
-    for (uint32_t peer = 0; peer < world && rc == 0; peer++) {
-        rc = g_send((const char *)d_send + (size_t)peer * bytes_per_peer, (size_t)bytes_per_peer, nccl_uint8, (int)peer, nccl_comm, stream);
-        if (rc == 0) rc = g_recv((char *)d_recv + (size_t)peer * bytes_per_peer, (size_t)bytes_per_peer, nccl_uint8, (int)peer, nccl_comm, stream);
-    }
-    const int rc2 = g_end();
-    if (rc || rc2) return kaamer_fail(KAAMER_E_HIP, "rccl_alltoall: RCCL error %d", rc ? rc : rc2);
-    return KAAMER_OK;
-}
+#include "exchange_host.hip.inc"
 
 // FilterResults / top-N (and SetBestStartCodon for nucleotide input) of the workspace's last
 // search or merge, on the device; see topn.hip.inc.
@@ -2355,11 +1984,12 @@ int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void 
     p.q_stride = opts->orf_source ? (opts->q_stride ? opts->q_stride : 1u) : 1u;
     p.size_in = opts->d_size_in_kmer;
     p.hit_cnt = ws->d_q_cnt;
-    p.hit_off = ws->compact ? ws->d_csr_off : ws->d_hit_off;
-    p.pid = ws->compact ? ws->d_c_pid : ws->d_hit_pid;
-    p.km = ws->compact ? ws->d_c_km : ws->d_hit_km;
+    const WsHits h = ws_hits(ws);
+    p.hit_off = h.off;
+    p.pid = h.pid;
+    p.km = h.km;
     // without first positions top_first_pos is zeros (kaamer_hip.h), whatever the counting tiers left in the hit arrays
-    p.fp = !ws->firstpos ? nullptr : ws->compact ? ws->d_c_fp : ws->d_hit_fp;
+    p.fp = ws->firstpos ? h.fp : nullptr;
     p.orf_aa = src->d_orf_aa;
     p.starts_alt = src->d_starts_alt;
     p.min_k_ratio = opts->min_k_ratio;
