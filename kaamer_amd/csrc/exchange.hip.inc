@@ -594,36 +594,24 @@ __global__ __launch_bounds__(64) void x_or_bits_kernel(XParams p)
 
 // ---- the step's state in a workspace (host): what XParams points at, allocated on first use ------------------------------
 // The block layout may change from batch to batch within the buffers' capacity, so the buffers only ever grow.
-template <class T> struct XBuf { T *p; size_t cap; };
 struct XStatsSlot {             // what the W headers of one merge said, as kaamer_exchange_stats(_positions) return it
     unsigned long long stats[4];   // {queries of the batch, largest block any pair of ranks needed, a block overflowed, 0}
     unsigned long long pstats[2];  // {largest bitmap need between any pair of ranks, a bitmap section overflowed}
 };
 struct XState {
     // pack: where each query's entries / bitmaps start inside its block
-    XBuf<uint32_t> dst_off;
-    XBuf<uint64_t> dst_boff;
+    DevBuf<uint32_t> dst_off;
+    DevBuf<uint64_t> dst_boff;
     // unpack: offsets per (source, owned query), the owned queries' entries in one piece, the header statistics
-    XBuf<uint32_t> src_off, nq_owned, pid, km, fp;
-    XBuf<uint64_t> ent_off;
-    XBuf<unsigned long long> stats;
+    DevBuf<uint32_t> src_off, nq_owned, pid, km, fp;
+    DevBuf<uint64_t> ent_off;
+    DevBuf<unsigned long long> stats;
     // unpack with bitmaps: offsets, sizes, the bitmaps, the OR-merge's scratch
-    XBuf<uint64_t> src_boff, ent_boff, mdst;
-    XBuf<int32_t> msize;
-    XBuf<unsigned long long> mbits, gtab, pstats;
-    XBuf<uint64_t> tiles;       // tile sums of the tiled scans
-    XStatsSlot *h_stats;        // pinned: two slots, slot = merge sequence number & 1
-    hipEvent_t ev_stats[2];
-    uint64_t merge_seq;         // merges enqueued on this workspace
+    DevBuf<uint64_t> src_boff, ent_boff, mdst;
+    DevBuf<int32_t> msize;
+    DevBuf<unsigned long long> mbits, gtab, pstats;
+    DevBuf<uint64_t> tiles;           // tile sums of the tiled scans
+    PinnedBuf<XStatsSlot> h_stats;    // two slots, slot = merge sequence number & 1
+    DevEvent ev_stats[2];
+    uint64_t merge_seq = 0;           // merges enqueued on this workspace
 };
-static void x_state_free(XState &x)
-{
-    void *bufs[] = { x.dst_off.p, x.dst_boff.p, x.src_off.p, x.nq_owned.p, x.pid.p, x.km.p, x.fp.p, x.ent_off.p, x.stats.p,
-                     x.src_boff.p, x.ent_boff.p, x.mdst.p, x.msize.p, x.mbits.p, x.gtab.p, x.pstats.p, x.tiles.p };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    if (x.h_stats) {
-        (void)hipHostFree(x.h_stats);
-        for (hipEvent_t e : x.ev_stats) if (e) (void)hipEventDestroy(e);
-    }
-    x = XState{};
-}

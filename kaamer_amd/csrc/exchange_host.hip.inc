@@ -100,29 +100,9 @@ static int x_check(const kaamer_workspace *ws, const kaamer_exchange_layout *L, 
     return KAAMER_OK;
 }
 
-// The growth rule of the step's buffers: when one buffer of a group holds less than asked, the whole group is made again,
-// every buffer exactly as large as asked (the capacity layout of a searcher does not change: a margin would only cost
-// memory), once the stream is done with the old ones.
-struct XWant { void **p; size_t *cap; size_t n, elem; };
-extern "C++" template <class T> static XWant x_want(XBuf<T> &b, size_t n) { return { (void **)&b.p, &b.cap, n, sizeof(T) }; }
-static int x_grow(hipStream_t s, std::initializer_list<XWant> group)
-{
-    bool fits = true, used = false;
-    for (const XWant &w : group) { fits = fits && *w.p && *w.cap >= w.n; used = used || *w.p; }
-    if (fits) return KAAMER_OK;
-    if (used) HIPCHK(hipStreamSynchronize(s));
-    for (const XWant &w : group) {
-        if (*w.p) (void)hipFree(*w.p);
-        *w.p = nullptr; *w.cap = 0;
-    }
-    for (const XWant &w : group) {
-        uint8_t *b = nullptr;
-        const int rc = dev_alloc(&b, (w.n ? w.n : 1) * w.elem);
-        if (rc) return rc;
-        *w.p = b; *w.cap = w.n;
-    }
-    return KAAMER_OK;
-}
+// The growth rule of the step's buffers (reserve_group, GROW_EXACT): when one buffer of a group holds less than asked, the
+// whole group is made again, every buffer exactly as large as asked (the capacity layout of a searcher does not change: a
+// margin would only cost memory), once the stream is done with the old ones.
 
 // the block geometry of a layout, and the tile sums its scans need: (world + 1) rows of n_tiles
 static int x_params(kaamer_workspace *ws, const kaamer_exchange_layout *L, hipStream_t s, XParams *x)
@@ -133,8 +113,8 @@ static int x_params(kaamer_workspace *ws, const kaamer_exchange_layout *L, hipSt
     if (L->arrays == 4) { x->ent_base += L->q_cap; x->bits_off = x_bits_off(L); x->p_cap = x_p_cap(L); }
     x->with_fp = ws->firstpos ? 1u : 0u;
     x->n_tiles = (uint32_t)(((uint64_t)L->q_cap + X_TILE - 1) / X_TILE);
-    const int rc = x_grow(s, { x_want(ws->x.tiles, (size_t)(L->world + 1) * x->n_tiles) });
-    x->tile_sum = ws->x.tiles.p;
+    const int rc = reserve_group(s, GROW_EXACT, { want(ws->x.tiles, (size_t)(L->world + 1) * x->n_tiles) });
+    x->tile_sum = ws->x.tiles;
     return rc;
 }
 
@@ -184,8 +164,8 @@ int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, 
     { const int jrc = ws_join(ws, s); if (jrc) return jrc; }
     XState &xs = ws->x;
     const size_t per_query = (size_t)L->world * L->q_cap;
-    int rc = x_grow(s, { x_want(xs.dst_off, per_query) });
-    if (!rc && pos) rc = x_grow(s, { x_want(xs.dst_boff, per_query) });
+    int rc = reserve_group(s, GROW_EXACT, { want(xs.dst_off, per_query) });
+    if (!rc && pos) rc = reserve_group(s, GROW_EXACT, { want(xs.dst_boff, per_query) });
     XParams x;
     if (!rc) rc = x_params(ws, L, s, &x);
     if (rc) return rc;
@@ -194,12 +174,12 @@ int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, 
     x.src_status = ws->d_status_out;  // written by the search's finalize step, earlier on this stream
     x.hit_off = h.off; x.hit_cnt = ws->d_q_cnt; x.pid = h.pid; x.km = h.km; x.fp = h.fp;
     x.send = d_send;
-    x.dst_off = xs.dst_off.p;
+    x.dst_off = xs.dst_off;
     if (pos) {   // the bitmap sections: SizeInKmer per owned query, where each query's bitmaps start, header words [6], [7]
         x.qinfo = ws->d_qinfo;
         x.pos_off = ws->d_pos_off;
         x.pos_bits = ws->d_pos_bits;
-        x.dst_boff = xs.dst_boff.p;
+        x.dst_boff = xs.dst_boff;
     }
     x_enqueue_scan<0>(x, L->world, s);
     if (pos) x_enqueue_scan<2>(x, L->world, s);
@@ -214,18 +194,18 @@ int kaamer_exchange_pack(kaamer_workspace *ws, const kaamer_exchange_layout *L, 
 // the unpack buffers for L: entries of all sources (m_cap), and with bitmaps their words (mb_cap); the statistics' slots
 static int x_grow_unpack(XState &xs, const kaamer_exchange_layout *L, uint64_t m_cap, uint64_t mb_cap, hipStream_t s)
 {
-    int rc = x_grow(s, { x_want(xs.src_off, (size_t)L->world * L->q_cap), x_want(xs.nq_owned, 1), x_want(xs.ent_off, (size_t)L->q_cap + 1),
-                         x_want(xs.pid, (size_t)m_cap), x_want(xs.km, (size_t)m_cap), x_want(xs.fp, (size_t)m_cap), x_want(xs.stats, 4) });
+    int rc = reserve_group(s, GROW_EXACT, { want(xs.src_off, (size_t)L->world * L->q_cap), want(xs.nq_owned, 1), want(xs.ent_off, (size_t)L->q_cap + 1),
+                         want(xs.pid, (size_t)m_cap), want(xs.km, (size_t)m_cap), want(xs.fp, (size_t)m_cap), want(xs.stats, 4) });
     const size_t pq = (size_t)L->world * L->q_cap + 1;   // per (source, owned query); also bounds the per-query arrays
     if (!rc && L->arrays == 4)
-        rc = x_grow(s, { x_want(xs.src_boff, pq), x_want(xs.ent_boff, pq), x_want(xs.msize, pq), x_want(xs.mdst, (size_t)m_cap),
-                         x_want(xs.gtab, 2 * (size_t)m_cap), x_want(xs.mbits, (size_t)mb_cap) });
-    if (!rc) rc = x_grow(s, { x_want(xs.pstats, 2) });
-    if (rc || xs.h_stats) return rc;
-    if (hipHostMalloc((void **)&xs.h_stats, 2 * sizeof(XStatsSlot), hipHostMallocDefault) != hipSuccess)
-        return kaamer_fail(KAAMER_E_NOMEM, "exchange_merge: pinned statistics");
+        rc = reserve_group(s, GROW_EXACT, { want(xs.src_boff, pq), want(xs.ent_boff, pq), want(xs.msize, pq), want(xs.mdst, (size_t)m_cap),
+                         want(xs.gtab, 2 * (size_t)m_cap), want(xs.mbits, (size_t)mb_cap) });
+    if (!rc) rc = reserve_group(s, GROW_EXACT, { want(xs.pstats, 2) });
+    if (rc || xs.ev_stats[1]) return rc;   // (the statistics' pinned slots and their events are there)
+    rc = reserve(xs.h_stats, 2, GROW_EXACT, s);
+    if (rc) return rc;
     memset(xs.h_stats, 0, 2 * sizeof(XStatsSlot));
-    for (hipEvent_t &e : xs.ev_stats) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (DevEvent &e : xs.ev_stats) if (!e) HIPCHK(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
     return KAAMER_OK;
 }
 
@@ -234,8 +214,8 @@ static int x_stats_to_host(XState &xs, hipStream_t s)
 {
     const int i = (int)(xs.merge_seq & 1u);
     XStatsSlot &slot = xs.h_stats[i];
-    HIPCHK(hipMemcpyAsync(slot.stats, xs.stats.p, sizeof slot.stats, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(slot.pstats, xs.pstats.p, sizeof slot.pstats, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(slot.stats, xs.stats, sizeof slot.stats, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(slot.pstats, xs.pstats, sizeof slot.pstats, hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(xs.ev_stats[i], s));
     xs.merge_seq++;
     return KAAMER_OK;
@@ -279,33 +259,33 @@ int kaamer_exchange_merge(kaamer_workspace *ws, const kaamer_exchange_layout *L,
     if (rc) return rc;
     ws->clean = true;
     x.recv = d_recv;
-    x.src_off = xs.src_off.p;
-    x.ent_off = xs.ent_off.p;
-    x.d_nq_owned = xs.nq_owned.p;
-    x.m_pid = xs.pid.p; x.m_km = xs.km.p; x.m_fp = xs.fp.p;
+    x.src_off = xs.src_off;
+    x.ent_off = xs.ent_off;
+    x.d_nq_owned = xs.nq_owned;
+    x.m_pid = xs.pid; x.m_km = xs.km; x.m_fp = xs.fp;
     x.m_cap = m_cap;
-    x.stats = xs.stats.p;
+    x.stats = xs.stats;
     x.status = ws->d_list_counts + SLOT_STATUS;
     x_enqueue_scan<1>(x, L->world + 1, s);
     const XCopy c = x_copy_form(ws, (uint64_t)L->q_cap * L->world, L->q_cap);
     X_LAUNCH_COPY(x_unpack_copy_kernel, c, s, x);
     if (pos) {   // the bitmap sections: sizes checked alike in all blocks, offsets per source and per owned query, copy
-        x.src_boff = xs.src_boff.p;
-        x.ent_boff = xs.ent_boff.p;
-        x.m_size = xs.msize.p;
-        x.m_bits = xs.mbits.p;
+        x.src_boff = xs.src_boff;
+        x.ent_boff = xs.ent_boff;
+        x.m_size = xs.msize;
+        x.m_bits = xs.mbits;
         x.mb_cap = mb_cap;
-        x.pstats = xs.pstats.p;
-        x.m_dst = xs.mdst.p;
-        x.g_tab = xs.gtab.p;
+        x.pstats = xs.pstats;
+        x.m_dst = xs.mdst;
+        x.g_tab = xs.gtab;
         x_enqueue_scan<3>(x, L->world + 1, s);
         X_LAUNCH_COPY(x_unpack_bits_kernel, c, s, x);
     } else {
-        HIPCHK(hipMemsetAsync(xs.pstats.p, 0, 2 * sizeof(unsigned long long), s));
+        HIPCHK(hipMemsetAsync(xs.pstats, 0, 2 * sizeof(unsigned long long), s));
     }
     HIPCHK(hipGetLastError());
     rc = x_stats_to_host(xs, s);
-    if (!rc) rc = merge_enqueue(ws, xs.ent_off.p, xs.pid.p, xs.km.p, xs.fp.p, L->q_cap, xs.nq_owned.p, m_cap, s);
+    if (!rc) rc = merge_enqueue(ws, xs.ent_off, xs.pid, xs.km, xs.fp, L->q_cap, xs.nq_owned, m_cap, s);
     if (rc) return rc;
     if (pos) x_enqueue_or_merge(ws, x, L->q_cap, s);
     return merge_finish(ws, s, pos, out);

@@ -28,7 +28,23 @@
 // host_sharded_submit.hip.inc: a set made ready and the phases above enqueued (sharded_enqueue).
 // host_sharded_collect.hip.inc: the attempt waited for, checked and interleaved (sharded_collect), the retry, discard.
 
-struct ShardState {
+// top calls with the PositionHits of the reported hits (top_positions_sharded.hip.inc): a shard's buffers
+struct ShardTps {
+    DevBuf<uint32_t> d_ids, d_ids_recv;                   // the owner's ids block; the W owners' blocks as pulled
+    DevBuf<unsigned long long> d_seg_send, d_seg_recv;    // W segments each (one header word + the bitmap words)
+    DevBuf<uint32_t> d_tps_words, d_tps_n;                // [rq_cap]; per owner {reported queries, status}
+    DevBuf<uint64_t> d_tps_base;                          // [W][rq_cap + 1] word offsets per owner
+};
+// top calls that align the reported hits (top_align_sharded.hip.inc): a shard's buffers and what they hold
+struct ShardSa {
+    TasLayout sa_cap{};                                   // a (holder -> owner) subject segment: capacity
+    DevBuf<uint8_t> d_sa_send, d_sa_recv, d_sa_codes;     // W segments each; the letter codes of the received ones
+    DevBuf<uint32_t> d_sa_qbytes, d_sa_n;                 // [rq_cap + 1]; per owner {reported queries, status}
+    DevBuf<uint64_t> d_sa_off;                            // owner: per pair, where its subject lies in d_sa_recv
+    DevBuf<unsigned long long> d_sa_need;                 // holder: per owner {payload bytes needed, status}
+};
+
+struct ShardState : ShardTps, ShardSa {
     kaamer_index *ix = nullptr;
     int device = 0;
     kaamer_workspace *ws = nullptr, *mws = nullptr;
@@ -38,31 +54,22 @@ struct ShardState {
     uint64_t e_cap = 0;
     uint64_t p_cap = 0;                // bitmap words a block can hold (full calls with positions)
     bool full = false;                 // workspaces of a full call (kaamer_sharded_search_batch): first_pos = 1, CSR merge
-    uint32_t *d_send = nullptr, *d_recv = nullptr;
-    size_t x_words = 0;
+    DevBuf<uint32_t> d_send, d_recv;
     hipStream_t stream = nullptr;
     hipEvent_t ev_packed = nullptr;
-    uint8_t *d_seqs = nullptr;
-    uint64_t *d_off = nullptr;
-    size_t seq_cap = 0, off_cap = 0;
-    uint8_t *d_block = nullptr, *h_block = nullptr;
-    size_t d_block_cap = 0, h_block_cap = 0, guess = 1u << 16, copied = 0;
-    // top calls with the PositionHits of the reported hits (top_positions_sharded.hip.inc)
+    DevBuf<uint8_t> d_seqs;
+    DevBuf<uint64_t> d_off;
+    DevBuf<uint8_t> d_block;
+    uint8_t *h_block = nullptr;        // a block of the pinned cache (pinned_get)
+    size_t h_block_cap = 0, guess = 1u << 16, copied = 0;
+    // top calls with the PositionHits of the reported hits (ShardTps)
     bool tpos = false;                 // workspaces and buffers of such a call
     uint32_t tp_k = 0, tp_scale = 0;   // MaxResults and BatchBounds::pos_scale the capacities below were made for
     TpsIdsLayout ids_cap{}, ids_wire{};   // the ids block: capacity, and as it travels for the batch in flight
     uint64_t tp_cap = 0, tp_wire = 0;     // bitmap words of one (shard -> owner) segment: capacity, as it travels
-    uint32_t *d_ids = nullptr, *d_ids_recv = nullptr;                   // the owner's ids block; the W owners' blocks as pulled
-    unsigned long long *d_seg_send = nullptr, *d_seg_recv = nullptr;    // W segments each (one header word + the bitmap words)
-    uint32_t *d_tps_words = nullptr, *d_tps_n = nullptr;                // [rq_cap]; per owner {reported queries, status}
-    uint64_t *d_tps_base = nullptr;                                     // [W][rq_cap + 1] word offsets per owner
     hipEvent_t ev_ids = nullptr, ev_bits = nullptr;   // the owner's ids block is packed; the shard's segments (bitmaps, subjects) are made
-    // top calls that align the reported hits (top_align_sharded.hip.inc)
-    TasLayout sa_cap{}, sa_wire{};     // a (holder -> owner) subject segment: capacity, and as it travels for the batch in flight
-    uint8_t *d_sa_send = nullptr, *d_sa_recv = nullptr, *d_sa_codes = nullptr;   // W segments each; the letter codes of the received ones
-    uint32_t *d_sa_qbytes = nullptr, *d_sa_n = nullptr;                          // [rq_cap + 1]; per owner {reported queries, status}
-    uint64_t *d_sa_off = nullptr;                                                // owner: per pair, where its subject lies in d_sa_recv
-    unsigned long long *d_sa_need = nullptr;                                     // holder: per owner {payload bytes needed, status}
+    // top calls that align the reported hits (ShardSa)
+    TasLayout sa_wire{};               // a subject segment as it travels for the batch in flight (<= sa_cap)
     uint64_t aln_guess = 0;            // bytes the alignment sections of this owner's previous block needed, plus a quarter
     uint64_t sa_stage[3] = {0, 0, 0};  // the owner's last alignment stage: resident waves, slab bytes, long-subject waves
     hipEvent_t ev_t[5] = {};           // kaamer_sharded_index_set_align_timing: gather begin / end, assemble begin, alignment begin / end
@@ -72,8 +79,7 @@ struct ShardState {
 // everything one call in flight needs on every shard (the indices themselves are shared by all sets)
 struct ShardSet {
     std::vector<ShardState> sh;
-    uint8_t *h_in = nullptr;
-    size_t h_in_cap = 0;
+    Buf<uint8_t, Mem::PINNED_PORTABLE> h_in;   // the caller's batch: every device copies from it
     bool busy = false;
     uint64_t need_entries = 0;   // what the largest (shard -> owner) block of the previous batch on this set needed
     uint32_t need_queries = 0;   // its queries (ORFs)
@@ -103,10 +109,10 @@ struct kaamer_sharded_index {
     std::condition_variable cv;
     // kaamer_sharded_index_attach_proteins: the Protein.Sequence table, partitioned over the devices by id mod W
     struct AlnPart {
-        uint8_t *d_raw = nullptr;      // the stored bytes of the entries this device holds
-        uint64_t *d_off = nullptr;     // entries + 1
-        uint32_t *d_idmap = nullptr;   // id / W -> entry, TA_NONE: no entry
-        int *d_matrix = nullptr;
+        DevBuf<uint8_t> d_raw;         // the stored bytes of the entries this device holds
+        DevBuf<uint64_t> d_off;        // entries + 1
+        DevBuf<uint32_t> d_idmap;      // id / W -> entry, TA_NONE: no entry
+        DevBuf<int> d_matrix;
         uint32_t idmap_n = 0, entries = 0;
         uint64_t bytes = 0;
     };
@@ -119,30 +125,16 @@ struct kaamer_sharded_index {
     bool aln_timing = false;                     // kaamer_sharded_index_set_align_timing
 };
 
-static void shard_tps_free(ShardState &s)
-{
-    void *bufs[] = { s.d_ids, s.d_ids_recv, s.d_seg_send, s.d_seg_recv, s.d_tps_words, s.d_tps_n, s.d_tps_base };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    s.d_ids = s.d_ids_recv = nullptr; s.d_seg_send = s.d_seg_recv = nullptr;
-    s.d_tps_words = s.d_tps_n = nullptr; s.d_tps_base = nullptr;
-}
-
-static void shard_sa_free(ShardState &s)
-{
-    void *bufs[] = { s.d_sa_send, s.d_sa_recv, s.d_sa_codes, s.d_sa_qbytes, s.d_sa_n, s.d_sa_off, s.d_sa_need };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    s.d_sa_send = s.d_sa_recv = s.d_sa_codes = nullptr; s.d_sa_qbytes = s.d_sa_n = nullptr; s.d_sa_off = nullptr; s.d_sa_need = nullptr;
-    s.sa_cap = TasLayout();
-}
+// (the shard's device is selected)
+static void shard_tps_free(ShardState &s) { static_cast<ShardTps &>(s) = ShardTps(); }
+static void shard_sa_free(ShardState &s) { static_cast<ShardSa &>(s) = ShardSa(); }
 
 static void sharded_aln_free(kaamer_sharded_index *sx)
 {
     if (!sx->aln) return;
     for (uint32_t s = 0; s < sx->n; s++) {
-        kaamer_sharded_index::AlnPart &a = (*sx->aln)[s];
         (void)hipSetDevice((*sx->dev)[s]);
-        void *bufs[] = { a.d_raw, a.d_off, a.d_idmap, a.d_matrix };
-        for (void *b : bufs) if (b) (void)hipFree(b);
+        (*sx->aln)[s] = kaamer_sharded_index::AlnPart();
     }
     delete sx->aln;
     sx->aln = nullptr; sx->aln_host = nullptr;
@@ -155,17 +147,13 @@ static void shard_state_free(ShardState &s)
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.ws) kaamer_workspace_free(s.ws);
     if (s.mws) kaamer_workspace_free(s.mws);
-    void *bufs[] = { s.d_send, s.d_recv, s.d_seqs, s.d_off, s.d_block };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    shard_tps_free(s);
-    shard_sa_free(s);
     if (s.h_block) pinned_put(s.h_block, s.h_block_cap);
     if (s.ev_packed) (void)hipEventDestroy(s.ev_packed);
     if (s.ev_ids) (void)hipEventDestroy(s.ev_ids);
     if (s.ev_bits) (void)hipEventDestroy(s.ev_bits);
     for (hipEvent_t e : s.ev_t) if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
-    s = ShardState();   // (the index belongs to the handle)
+    s = ShardState();   // its buffers go here, on its device (the index belongs to the handle)
 }
 
 void kaamer_sharded_index_close(kaamer_sharded_index *sx)
@@ -174,9 +162,8 @@ void kaamer_sharded_index_close(kaamer_sharded_index *sx)
     if (sx->sets) {
         for (int k = 0; k < KAAMER_SHARDED_SETS; k++) {
             for (ShardState &s : sx->sets[k].sh) shard_state_free(s);
-            if (sx->sets[k].h_in) (void)hipHostFree(sx->sets[k].h_in);
         }
-        delete[] sx->sets;
+        delete[] sx->sets;   // (with each set's pinned staging)
     }
     if (sx->dev) sharded_aln_free(sx);
     if (sx->ix) {
@@ -300,10 +287,8 @@ int kaamer_sharded_index_attach_proteins(kaamer_sharded_index *sx, const kaamer_
         raw.resize(raw.size() + 16, 0);
         hipError_t e = hipSetDevice((*sx->dev)[s]);
         if (e != hipSuccess) { rc = kaamer_fail(KAAMER_E_HIP, "hipSetDevice: %s", hipGetErrorString(e)); break; }
-        rc = dev_alloc(&a.d_raw, raw.size());
-        if (!rc) rc = dev_alloc(&a.d_off, off.size());
-        if (!rc) rc = dev_alloc(&a.d_idmap, idmap.size());
-        if (!rc) rc = dev_alloc(&a.d_matrix, (size_t)ALN_NL * ALN_NL);
+        rc = reserve_group(nullptr, GROW_EXACT, { want(a.d_raw, raw.size()), want(a.d_off, off.size()), want(a.d_idmap, idmap.size()),
+                                                  want(a.d_matrix, (size_t)ALN_NL * ALN_NL) });
         if (rc) break;
         e = hipMemcpy(a.d_raw, raw.data(), raw.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(a.d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice);

@@ -193,7 +193,7 @@ static int tas_enqueue_align(kaamer_sharded_index *sx, const kaamer_sharded_tick
     p.tab.raw = ow.d_sa_recv; p.tab.codes = ow.d_sa_codes; p.tab.off = ow.d_sa_off;   // (bad, idmap: ta_pairs_kernel's, not read here)
     p.matrix = part.d_matrix;
     p.gap_open = t->aln.gap_open; p.gap_extend = t->aln.gap_extend;
-    p.block = ow.d_block; p.block_cap = ow.d_block_cap; p.aln_cap = t->b.aln_cap; p.want_text = t->aln.text ? 1 : 0;
+    p.block = ow.d_block; p.block_cap = ow.d_block.capacity(); p.aln_cap = t->b.aln_cap; p.want_text = t->aln.text ? 1 : 0;
     p.status = mws->d_status_out;
     return ta_stage(ws, p, budget, sx->aln_max_ns, t->max_query_len, &sp, ow.stream, ow.sa_stage, ow.timed ? ow.ev_t + 2 : nullptr);
 }
@@ -249,15 +249,8 @@ static int shard_prepare_workspaces(ShardState &st, uint32_t W, uint32_t rank, u
     rc = kaamer_workspace_create(st.ix, &m, &st.mws);
     if (rc) { st.mws = nullptr; return rc; }
     const size_t words = (size_t)W * st.layout.block_words;
-    if (st.x_words < words) {
-        if (st.d_send) (void)hipFree(st.d_send);
-        if (st.d_recv) (void)hipFree(st.d_recv);
-        st.d_send = st.d_recv = nullptr; st.x_words = 0;
-        rc = dev_alloc(&st.d_send, words);
-        if (!rc) rc = dev_alloc(&st.d_recv, words);
-        if (rc) return rc;
-        st.x_words = words;
-    }
+    rc = reserve_group(st.stream, GROW_EXACT, { want(st.d_send, words), want(st.d_recv, words) });
+    if (rc) return rc;
     shard_tps_free(st);   // (sized from the workspaces: shard_prepare_ids makes them again)
     st.tpos = b.tpos;
     st.tp_k = 0; st.tp_scale = 0;
@@ -282,13 +275,10 @@ static int shard_prepare_ids(ShardState &st, uint32_t W, bool nucl, const ShardB
     st.ids_cap.rq_cap = (uint32_t)oq;
     st.ids_cap.ent_cap = (e > e_hard ? e_hard : e) + 64;
     const size_t iw = (size_t)tps_ids_words(st.ids_cap), sw = (size_t)st.tp_cap + 1;
-    int rc = dev_alloc(&st.d_ids, iw);
-    if (!rc) rc = dev_alloc(&st.d_ids_recv, (size_t)W * iw);
-    if (!rc && b.tpos) rc = dev_alloc(&st.d_seg_send, (size_t)W * sw);
-    if (!rc && b.tpos) rc = dev_alloc(&st.d_seg_recv, (size_t)W * sw);
-    if (!rc && b.tpos) rc = dev_alloc(&st.d_tps_words, (size_t)oq + 1);
-    if (!rc && b.tpos) rc = dev_alloc(&st.d_tps_n, (size_t)2 * W);
-    if (!rc && b.tpos) rc = dev_alloc(&st.d_tps_base, (size_t)W * (oq + 1));
+    int rc = reserve_group(st.stream, GROW_EXACT, { want(st.d_ids, iw), want(st.d_ids_recv, (size_t)W * iw) });
+    if (!rc && b.tpos)
+        rc = reserve_group(st.stream, GROW_EXACT, { want(st.d_seg_send, (size_t)W * sw), want(st.d_seg_recv, (size_t)W * sw), want(st.d_tps_words, (size_t)oq + 1),
+                                                    want(st.d_tps_n, (size_t)2 * W), want(st.d_tps_base, (size_t)W * (oq + 1)) });
     if (rc) { shard_tps_free(st); st.tp_k = 0; st.tp_scale = 0; return rc; }
     st.tp_k = K; st.tp_scale = scale;
     return KAAMER_OK;
@@ -305,14 +295,10 @@ static int shard_prepare_subjects(ShardState &st, uint32_t W, const ShardBounds 
     L.byte_cap = st.sa_cap.byte_cap > b.sa_bytes ? st.sa_cap.byte_cap : b.sa_bytes;
     shard_sa_free(st);
     const size_t sb = (size_t)tas_seg_bytes(L);
-    int rc = dev_alloc(&st.d_sa_send, (size_t)W * sb);
-    if (!rc) rc = dev_alloc(&st.d_sa_recv, (size_t)W * sb);
-    if (!rc) rc = dev_alloc(&st.d_sa_codes, (size_t)W * sb);
-    if (!rc) rc = dev_alloc(&st.d_sa_qbytes, (size_t)L.rq_cap + 1);
-    if (!rc) rc = dev_alloc(&st.d_sa_n, (size_t)2 * W);
-    if (!rc) rc = dev_alloc(&st.d_sa_off, (size_t)L.ent_cap + 1);
-    if (!rc) rc = dev_alloc(&st.d_sa_need, (size_t)2 * W);
-    if (rc) { shard_sa_free(st); return rc; }
+    const int rc = reserve_group(st.stream, GROW_EXACT, { want(st.d_sa_send, (size_t)W * sb), want(st.d_sa_recv, (size_t)W * sb), want(st.d_sa_codes, (size_t)W * sb),
+                                                          want(st.d_sa_qbytes, (size_t)L.rq_cap + 1), want(st.d_sa_n, (size_t)2 * W),
+                                                          want(st.d_sa_off, (size_t)L.ent_cap + 1), want(st.d_sa_need, (size_t)2 * W) });
+    if (rc) return rc;
     st.sa_cap = L;
     return KAAMER_OK;
 }
@@ -324,9 +310,9 @@ static int shard_prepare(ShardState &st, uint32_t W, uint32_t rank, uint64_t seq
     int rc = shard_prepare_workspaces(st, W, rank, seq_bytes, n_seqs, seq_type, b);
     if (!rc) rc = shard_prepare_ids(st, W, is_nucl(seq_type), b, K);
     if (!rc) rc = shard_prepare_subjects(st, W, b);
-    if (!rc) rc = dev_grow(&st.d_seqs, &st.seq_cap, (size_t)seq_bytes + 16);
-    if (!rc) rc = dev_grow(&st.d_off, &st.off_cap, (size_t)n_seqs + 1);
-    if (!rc && !b.full) rc = dev_grow(&st.d_block, &st.d_block_cap, rep_block_bound(st.mws, st.ws, K, b.tpos ? st.tp_cap : 0) + (b.aln ? (size_t)b.aln_cap + 64 : 0));
+    if (!rc) rc = reserve(st.d_seqs, (size_t)seq_bytes + 16, GROW_CALL, st.stream);
+    if (!rc) rc = reserve(st.d_off, (size_t)n_seqs + 1, GROW_CALL, st.stream);
+    if (!rc && !b.full) rc = reserve(st.d_block, rep_block_bound(st.mws, st.ws, K, b.tpos ? st.tp_cap : 0) + (b.aln ? (size_t)b.aln_cap + 64 : 0), GROW_CALL, st.stream);
     return rc;
 }
 
@@ -413,7 +399,7 @@ template <class Copy> static int pull_from_all(std::vector<ShardState> &sh, uint
 // the speculative copy of an owner's result block
 static int sharded_copy_back(ShardState &ow)
 {
-    return rep_block_copy_guess(ow.d_block, ow.d_block_cap, ow.guess, &ow.h_block, &ow.h_block_cap, &ow.copied, ow.stream);
+    return rep_block_copy_guess(ow.d_block, ow.d_block.capacity(), ow.guess, &ow.h_block, &ow.h_block_cap, &ow.copied, ow.stream);
 }
 
 // ---- every shard: the whole batch against its keys, partial hit lists packed per owner
@@ -456,10 +442,10 @@ static int enqueue_merge_topn(kaamer_sharded_ticket *t, uint32_t seq, std::vecto
         tt.d_size_in_kmer = nullptr;
         tt.orf_source = ow.ws; tt.q_first = d; tt.q_stride = W;
         rc = kaamer_topn_device(ow.mws, &tt, ow.stream, &trs[d]);
-        if (!rc) rc = topn_pack_block(ow.mws, ow.ws, d, W, &trs[d], ow.stream, ow.d_block, ow.d_block_cap);
+        if (!rc) rc = topn_pack_block(ow.mws, ow.ws, d, W, &trs[d], ow.stream, ow.d_block, ow.d_block.capacity());
         if (rc) return rc;
         if (tpos_or_aln(t)) {   // the result block waits for its bitmaps and alignments (the second round trip)
-            rc = tps_enqueue_ids_pack(ow.mws, &trs[d], ow.d_block, ow.d_block_cap, ow.d_ids, ow.ids_wire, d, W, seq, ow.stream);
+            rc = tps_enqueue_ids_pack(ow.mws, &trs[d], ow.d_block, ow.d_block.capacity(), ow.d_ids, ow.ids_wire, d, W, seq, ow.stream);
             if (rc) return rc;
             HIPCHK(hipEventRecord(ow.ev_ids, ow.stream));
             continue;
@@ -526,7 +512,7 @@ static int enqueue_ids_round_owners(kaamer_sharded_ticket *t, uint32_t seq, cons
             if (e == hipSuccess && aln) e = peer_pull_async(ow.d_sa_recv + (size_t)s * ab, ow.device, src.d_sa_send + (size_t)d * ab, src.device, ab, ow.stream);
             return e;
         });
-        if (!rc && tpos) rc = tps_enqueue_or(ow.ix, ow.mws, ow.ws, ow.d_block, ow.d_block_cap, ow.d_ids_recv + (size_t)d * iw, ow.ids_wire, d, W, seq,
+        if (!rc && tpos) rc = tps_enqueue_or(ow.ix, ow.mws, ow.ws, ow.d_block, ow.d_block.capacity(), ow.d_ids_recv + (size_t)d * iw, ow.ids_wire, d, W, seq,
                                              ow.d_tps_n + 2 * d, ow.d_tps_base + (size_t)d * bw, ow.d_seg_recv, sw, ow.tp_wire, ow.stream);
         if (!rc && aln) rc = tas_enqueue_align(t->sx, t, ow, &trs[d], d, W, seq, budget);
         if (!rc) rc = sharded_copy_back(ow);
@@ -625,14 +611,7 @@ static int sharded_submit(kaamer_sharded_index *sx, const kaamer_batch_in *in, c
     // the caller's buffers -> pinned staging, once; every device copies from there (and a retry runs from there)
     const size_t off_at = ((size_t)t->seq_bytes + 7) & ~(size_t)7;
     const size_t in_need = off_at + ((size_t)in->n_seqs + 1) * 8;
-    int rc = KAAMER_OK;
-    if (set->h_in_cap < in_need) {
-        if (set->h_in) (void)hipHostFree(set->h_in);
-        set->h_in = nullptr; set->h_in_cap = 0;
-        const size_t cap = in_need + in_need / 4 + 4096;
-        if (hipHostMalloc((void **)&set->h_in, cap, hipHostMallocPortable) != hipSuccess) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned input staging (%zu bytes)", cap);
-        else set->h_in_cap = cap;
-    }
+    int rc = reserve(set->h_in, in_need, GROW_SLOT, nullptr);   // (the set is this call's alone: nothing reads the old staging)
     if (!rc) {
         if (t->seq_bytes) memcpy(set->h_in, in->seqs, (size_t)t->seq_bytes);
         memcpy(set->h_in + off_at, in->offsets, ((size_t)in->n_seqs + 1) * 8);

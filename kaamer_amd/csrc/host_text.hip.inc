@@ -85,14 +85,14 @@ static uint32_t text_hard_records(uint64_t len) { return (uint32_t)(len / 2 + 1)
 static int text_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t len, uint32_t recs, uint64_t lines, bool host_staging)
 {
     if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-    int rc = host_staging ? slot_grow_pinned(h.stream, &h.h_text, &h.h_text_cap, (size_t)len, "text staging") : KAAMER_OK;
-    if (!rc) rc = slot_grow_dev(h.stream, &h.d_text, &h.d_text_cap, (size_t)len);
+    int rc = host_staging ? reserve(h.h_text, (size_t)len, GROW_SLOT, h.stream) : KAAMER_OK;
+    if (!rc) rc = reserve(h.d_text, (size_t)len, GROW_SLOT, h.stream);
     if (rc) return rc;
     if (!h.parser || h.parser_text < len || h.parser_recs < recs || h.parser_lines < lines) {
         HIPCHK(hipStreamSynchronize(h.stream));
         if (h.parser) kaamer_text_parser_free(h.parser);
         h.parser = nullptr;
-        uint64_t text_cap = slot_buf_cap(len);   // some headroom, as for the other buffers of a slot
+        uint64_t text_cap = grow_capacity(GROW_SLOT, len);   // some headroom, as for the other buffers of a slot
         if (text_cap > 0xFFFFFFFFull) text_cap = 0xFFFFFFFFull;
         rc = text_parser_create_lines(ix->device, text_cap, recs, lines, &h.parser);
         if (rc) { h.parser = nullptr; return rc; }
@@ -106,14 +106,14 @@ static int bgzf_slot_prepare(kaamer_index *ix, TopSlot &h, uint64_t comp_len, si
 {
     if (!h.stream) HIPCHK(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
     const size_t need = (size_t)((comp_len + 7) & ~7ull) + n_blocks * sizeof(kaamer_bgzf_block);
-    int rc = slot_grow_pinned(h.stream, &h.h_comp, &h.h_comp_cap, need, "BGZF staging");
-    if (!rc) rc = slot_grow_dev(h.stream, &h.d_comp, &h.d_comp_cap, need);
+    int rc = reserve(h.h_comp, need, GROW_SLOT, h.stream);
+    if (!rc) rc = reserve(h.d_comp, need, GROW_SLOT, h.stream);
     if (rc) return rc;
     if (!h.inflater || h.inflater_comp < comp_len || h.inflater_blocks < n_blocks) {
         HIPCHK(hipStreamSynchronize(h.stream));
         if (h.inflater) kaamer_inflater_free(h.inflater);
         h.inflater = nullptr;
-        const uint64_t comp_cap = slot_buf_cap(comp_len);
+        const uint64_t comp_cap = grow_capacity(GROW_SLOT, comp_len);
         const uint32_t blocks_cap = (uint32_t)(n_blocks + n_blocks / 4 + 64);
         rc = kaamer_inflater_create(ix->device, comp_cap, blocks_cap, &h.inflater);
         if (rc) { h.inflater = nullptr; return rc; }

@@ -134,12 +134,10 @@ static size_t rep_block_bound(const kaamer_workspace *ws, const kaamer_workspace
 static int topn_pack_block(kaamer_workspace *ws, const kaamer_workspace *src, uint32_t q_first, uint32_t q_stride,
                            const kaamer_topn_result *tr, hipStream_t s, uint8_t *d_block, size_t block_cap)
 {
-    if (!ws->d_rep_flag) {
-        int rc = dev_alloc(&ws->d_rep_flag, ws->q_cap);
-        if (!rc) rc = dev_alloc(&ws->d_rep_aalen, ws->q_cap);
-        if (!rc) rc = dev_alloc(&ws->d_rep_rank, (size_t)ws->q_cap + 1);
-        if (!rc) rc = dev_alloc(&ws->d_rep_eoff, (size_t)ws->q_cap + 1);
-        if (!rc) rc = dev_alloc(&ws->d_rep_aoff, (size_t)ws->q_cap + 1);
+    {   // (q_cap is fixed per workspace: the group is made at the first call)
+        const size_t qc = ws->q_cap;
+        const int rc = reserve_group(s, GROW_EXACT, { want(ws->d_rep_flag, qc), want(ws->d_rep_aalen, qc), want(ws->d_rep_rank, qc + 1),
+                                                      want(ws->d_rep_eoff, qc + 1), want(ws->d_rep_aoff, qc + 1) });
         if (rc) return rc;
     }
     RepParams p;
@@ -257,27 +255,18 @@ static void top_slot_release(kaamer_index *ix, int slot)
 static void top_slot_free(TopSlot &h)
 {
     if (h.ws) kaamer_workspace_free(h.ws);
-    if (h.d_seqs) (void)hipFree(h.d_seqs);
-    if (h.d_off) (void)hipFree(h.d_off);
-    if (h.d_block) (void)hipFree(h.d_block);
-    if (h.h_in) (void)hipHostFree(h.h_in);
     if (h.parser) kaamer_text_parser_free(h.parser);
-    if (h.h_text) (void)hipHostFree(h.h_text);
-    if (h.d_text) (void)hipFree(h.d_text);
     if (h.inflater) kaamer_inflater_free(h.inflater);
-    if (h.h_comp) (void)hipHostFree(h.h_comp);
-    if (h.d_comp) (void)hipFree(h.d_comp);
     if (h.tsv) kaamer_tsv_stage_free(h.tsv);
-    if (h.d_tsv) (void)hipFree(h.d_tsv);
     if (h.stream) (void)hipStreamDestroy(h.stream);
-    h = TopSlot();
+    h = TopSlot();   // (its buffers go here)
 }
 
 // the pinned staging of a packed batch: the sequences, then (8-byte aligned) the n_seqs + 1 offsets
 static int top_slot_staging(TopSlot &h, uint64_t seq_bytes, uint32_t n_seqs)
 {
     const size_t in_need = (((size_t)seq_bytes + 7) & ~(size_t)7) + ((size_t)n_seqs + 1) * 8;
-    return slot_grow_pinned(h.stream, &h.h_in, &h.h_in_cap, in_need, "input staging");
+    return reserve(h.h_in, in_need, GROW_SLOT, h.stream);
 }
 
 // workspace, staging and result block of a slot: rebuilt only when the batch outgrows them
@@ -299,17 +288,9 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
         if (rc) { h.ws = nullptr; return rc; }
         h.opts = g;
     }
-    int rc = slot_grow_dev(h.stream, &h.d_seqs, &h.seq_cap, (size_t)seq_bytes, 16);
-    if (rc) return rc;
-    if (h.off_cap < (size_t)n_seqs + 1) {
-        if (h.d_off) (void)hipFree(h.d_off);
-        h.d_off = nullptr; h.off_cap = 0;
-        const size_t cap = (size_t)n_seqs + (size_t)n_seqs / 4 + 16;
-        const int rc = dev_alloc(&h.d_off, cap);
-        if (rc) return rc;
-        h.off_cap = cap;
-    }
-    rc = top_slot_staging(h, seq_bytes, n_seqs);
+    int rc = reserve(h.d_seqs, (size_t)seq_bytes, GROW_SLOT_SEQS, h.stream);
+    if (!rc) rc = reserve(h.d_off, (size_t)n_seqs, GROW_SLOT_OFF, h.stream);
+    if (!rc) rc = top_slot_staging(h, seq_bytes, n_seqs);
     if (rc) return rc;
     // the bitmap bound (the rule next to kaamer_topn_positions_device); a first bound set on the index holds for the
     // first attempt only: the repeat of a batch that exceeded it takes the rule's
@@ -322,14 +303,7 @@ static int top_slot_prepare(kaamer_index *ix, TopSlot &h, const kaamer_workspace
     }
     const size_t bneed = rep_block_bound(h.ws, h.ws, K, h.pos_words) + (aln_bytes ? (size_t)aln_bytes + 64 : 0);
     h.block_use = bneed;
-    if (h.d_block_cap < bneed) {
-        if (h.d_block) (void)hipFree(h.d_block);
-        h.d_block = nullptr; h.d_block_cap = 0;
-        rc = dev_alloc(&h.d_block, bneed);
-        if (rc) return rc;
-        h.d_block_cap = bneed;
-    }
-    return KAAMER_OK;
+    return reserve(h.d_block, bneed, GROW_EXACT, h.stream);
 }
 
 // everything of one call onto the slot's stream; the inputs are in the slot's pinned staging

@@ -61,12 +61,9 @@ int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p)
     const uint64_t budget = ix->aln_budget;
     aln_table_free(ix);   // a second attach replaces the first
     ix->aln_budget = budget;
-    rc = dev_alloc(&ix->d_aln_raw, raw.size());
-    if (!rc) rc = dev_alloc(&ix->d_aln_codes, codes.size());
-    if (!rc) rc = dev_alloc(&ix->d_aln_bad, bad.size());
-    if (!rc) rc = dev_alloc(&ix->d_aln_off, off.size());
-    if (!rc) rc = dev_alloc(&ix->d_aln_idmap, idmap.size());
-    if (!rc) rc = dev_alloc(&ix->d_aln_matrix, (size_t)ALN_NL * ALN_NL);
+    rc = reserve_group(nullptr, GROW_EXACT, { want(ix->d_aln_raw, raw.size()), want(ix->d_aln_codes, codes.size()), want(ix->d_aln_bad, bad.size()),
+                                              want(ix->d_aln_off, off.size()), want(ix->d_aln_idmap, idmap.size()),
+                                              want(ix->d_aln_matrix, (size_t)ALN_NL * ALN_NL) });
     if (rc) { aln_table_free(ix); return rc; }
     kaamer_align_matrix(ix->aln_matrix);
     hipError_t e = hipMemcpy(ix->d_aln_raw, raw.data(), raw.size(), hipMemcpyHostToDevice);
@@ -119,11 +116,8 @@ static int ta_check(const kaamer_index *ix, const kaamer_workspace *ws, const ka
 static int ta_stage(kaamer_workspace *ws, TaParams p, uint64_t budget, uint32_t table_max_ns, uint32_t max_query_len, const TasParams *sharded,
                     hipStream_t s, uint64_t info[3], const hipEvent_t *marks = nullptr)
 {
-    {   // first use; each buffer on its own, so that a failed allocation is tried again by the next call
-        int rc = KAAMER_OK;
-        if (!ws->d_ta_lay) rc = dev_alloc(&ws->d_ta_lay, 1);
-        if (!rc && !ws->d_ta_ctr) rc = dev_alloc(&ws->d_ta_ctr, 4);
-        if (!rc && !ws->d_ta_qcodes) rc = dev_alloc(&ws->d_ta_qcodes, (size_t)ws->pos_cap + 64);   // (pos_cap is fixed per workspace)
+    {   // first use (pos_cap is fixed per workspace)
+        const int rc = reserve_group(s, GROW_EXACT, { want(ws->d_ta_lay, 1), want(ws->d_ta_ctr, 4), want(ws->d_ta_qcodes, (size_t)ws->pos_cap + 64) });
         if (rc) return rc;
     }
     // slabs: the batch's longest query against the table's longest subject, capped at the wave kernel's LDS row
@@ -133,17 +127,18 @@ static int ta_stage(kaamer_workspace *ws, TaParams p, uint64_t budget, uint32_t 
     uint64_t n_waves = budget / (slab + opsb);
     const uint64_t resident = (uint64_t)ws->n_cu * TA_WAVES_PER_CU;
     n_waves = n_waves < 1 ? 1 : (n_waves > resident ? resident : n_waves);
-    int rc = ta_grow(&ws->d_ta_dirs, &ws->ta_dirs_cap, n_waves * slab, s);
-    if (!rc) rc = ta_grow(&ws->d_ta_ops, &ws->ta_ops_cap, n_waves * opsb, s);
+    // (grow-only, each on its own: a buffer that is large enough stays as large as it is)
+    int rc = reserve(ws->d_ta_dirs, (size_t)(n_waves * slab), GROW_EXACT, s);
+    if (!rc) rc = reserve(ws->d_ta_ops, (size_t)(n_waves * opsb), GROW_EXACT, s);
     uint64_t n_long = 0, lslab = 0, lops = 0, lbnd = 0;
     if (!rc && table_max_ns > ALN_WAVE_NS) {   // the table holds subjects beyond the LDS row: slabs of its longest one
         const uint64_t ns = table_max_ns;
         lslab = strips * (ns + 63) * 64; lops = (mq + ns + 63) & ~63ull; lbnd = 3 * (ns + 1);
         n_long = budget / (lslab + lops + 4 * lbnd);
         n_long = n_long < 1 ? 1 : (n_long > TA_LONG_WAVES_MAX ? TA_LONG_WAVES_MAX : n_long);
-        rc = ta_grow(&ws->d_ta_ldirs, &ws->ta_ldirs_cap, n_long * lslab, s);
-        if (!rc) rc = ta_grow(&ws->d_ta_lops, &ws->ta_lops_cap, n_long * lops, s);
-        if (!rc) rc = ta_grow(&ws->d_ta_lbnd, &ws->ta_lbnd_cap, n_long * lbnd, s);
+        rc = reserve(ws->d_ta_ldirs, (size_t)(n_long * lslab), GROW_EXACT, s);
+        if (!rc) rc = reserve(ws->d_ta_lops, (size_t)(n_long * lops), GROW_EXACT, s);
+        if (!rc) rc = reserve(ws->d_ta_lbnd, (size_t)(n_long * lbnd), GROW_EXACT, s);
     }
     if (rc) return rc;
     p.qcodes = ws->d_ta_qcodes;
@@ -217,8 +212,8 @@ int kaamer_topn_align_device(kaamer_index *ix, kaamer_workspace *ws, const kaame
     hipStream_t s = on_count_stream ? ws->count_stream : (hipStream_t)stream;
     uint64_t cap = opts->max_pairs;
     if (!cap) { cap = (uint64_t)ws->q_cap * top->max_results; if (ws->hit_cap && ws->hit_cap < cap) cap = ws->hit_cap; }
-    if (!ws->d_ta_eoff) rc = dev_alloc(&ws->d_ta_eoff, (size_t)ws->q_cap + 1);   // (q_cap is fixed per workspace)
-    if (!rc) rc = ta_grow(&ws->d_ta_items, &ws->ta_items_cap, cap, s);
+    rc = reserve(ws->d_ta_eoff, (size_t)ws->q_cap + 1, GROW_EXACT, s);   // (q_cap is fixed per workspace)
+    if (!rc) rc = reserve(ws->d_ta_items, (size_t)cap, GROW_EXACT, s);
     if (rc) return rc;
     scan_u32_on(ws, top->d_top_cnt, ws->d_nq, ws->q_cap, ws->d_ta_eoff, s);
     uint64_t mq = opts->max_query_len ? opts->max_query_len : ws->opts.max_seq_bytes;

@@ -46,23 +46,21 @@ int kaamer_index_attach_subject_text(kaamer_index *ix, const kaamer_proteins *p)
     subject_text_free(ix);   // a second attach replaces the first
     const bool share = ix->d_aln_idmap && ix->aln_host == p && ix->aln_entries == n && ix->aln_idmap_n == (uint32_t)map_n;
     std::vector<uint32_t> idmap;
-    rc = dev_alloc(&ix->d_st_bytes, bytes.size() + 1);
-    if (!rc) rc = dev_alloc(&ix->d_st_off, off.size());
-    if (!rc) rc = dev_alloc(&ix->d_st_idlen, idlen.size());
-    if (!rc) rc = dev_alloc(&ix->d_st_length, length.size());
+    rc = reserve_group(nullptr, GROW_EXACT, { want(ix->d_st_bytes, bytes.size() + 1), want(ix->d_st_off, off.size()), want(ix->d_st_idlen, idlen.size()),
+                                              want(ix->d_st_length, length.size()) });
     if (!rc && !share) {
         idmap.assign((size_t)map_n + 1, TSV_NONE);
         for (uint32_t i = 0; i < n; i++) idmap[uniq[i]] = i;
-        rc = dev_alloc(&ix->d_st_idmap, idmap.size());
+        rc = reserve(ix->d_st_idmap_own, idmap.size(), GROW_EXACT, nullptr);
     }
     if (rc) { subject_text_free(ix); return rc; }
     hipError_t e = bytes.empty() ? hipSuccess : hipMemcpy(ix->d_st_bytes, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_st_off, off.data(), off.size() * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_st_idlen, idlen.data(), idlen.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_st_length, length.data(), length.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !share) e = hipMemcpy(ix->d_st_idmap, idmap.data(), idmap.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !share) e = hipMemcpy(ix->d_st_idmap_own, idmap.data(), idmap.size() * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) { subject_text_free(ix); return kaamer_fail(KAAMER_E_HIP, "subject text upload: %s", hipGetErrorString(e)); }
-    if (share) { ix->d_st_idmap = ix->d_aln_idmap; ix->st_idmap_shared = true; }
+    ix->d_st_idmap = share ? ix->d_aln_idmap.get() : ix->d_st_idmap_own.get();   // (borrowed: aln_table_free hands it over)
     ix->st_idmap_n = (uint32_t)map_n; ix->st_entries = n; ix->st_features = nf;
     ix->st_max_suffix = max_suffix;
     ix->st_bytes = bytes.size() + 1 + off.size() * 8 + idlen.size() * 4 + length.size() * 4 + (share ? 0 : idmap.size() * 4);
@@ -85,20 +83,13 @@ struct kaamer_tsv_stage {
     kaamer_index *ix = nullptr;
     uint32_t max_queries = 0;
     uint64_t max_lines = 0;
-    unsigned long long *d_tile_bytes = nullptr, *d_tile_lines = nullptr, *d_line_off = nullptr, *d_counts = nullptr;
-    unsigned long long *h_counts = nullptr;   // pinned
+    DevBuf<unsigned long long> d_tile_bytes, d_tile_lines, d_line_off, d_counts;
+    PinnedBuf<unsigned long long> h_counts;
     uint64_t out_cap = 0;                     // of the last call
+    ~kaamer_tsv_stage() { if (ix) (void)hipSetDevice(ix->device); }   // (before the buffers go)
 };
 
-void kaamer_tsv_stage_free(kaamer_tsv_stage *st)
-{
-    if (!st) return;
-    if (st->ix) (void)hipSetDevice(st->ix->device);
-    void *bufs[] = { st->d_tile_bytes, st->d_tile_lines, st->d_line_off, st->d_counts };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    if (st->h_counts) (void)hipHostFree(st->h_counts);
-    delete st;
-}
+void kaamer_tsv_stage_free(kaamer_tsv_stage *st) { delete st; }
 
 int kaamer_tsv_stage_create(kaamer_index *ix, uint32_t max_queries, uint64_t max_lines, kaamer_tsv_stage **out)
 {
@@ -109,12 +100,9 @@ int kaamer_tsv_stage_create(kaamer_index *ix, uint32_t max_queries, uint64_t max
     if (!st) return kaamer_fail(KAAMER_E_NOMEM, "tsv stage");
     st->ix = ix; st->max_queries = max_queries; st->max_lines = max_lines;
     const size_t tiles = (size_t)max_queries / TSV_TILE + 1;
-    int rc = dev_alloc(&st->d_tile_bytes, tiles);
-    if (!rc) rc = dev_alloc(&st->d_tile_lines, tiles);
-    if (!rc) rc = dev_alloc(&st->d_line_off, (size_t)max_lines + 1);
-    if (!rc) rc = dev_alloc(&st->d_counts, (size_t)TSV_C_N);
-    if (!rc && hipHostMalloc((void **)&st->h_counts, TSV_C_N * 8, hipHostMallocDefault) != hipSuccess) rc = kaamer_fail(KAAMER_E_NOMEM, "pinned tsv counts");
-    if (rc) { kaamer_tsv_stage_free(st); return rc; }
+    const int rc = reserve_group(nullptr, GROW_EXACT, { want(st->d_tile_bytes, tiles), want(st->d_tile_lines, tiles), want(st->d_line_off, (size_t)max_lines + 1),
+                                                        want(st->d_counts, (size_t)TSV_C_N), want(st->h_counts, (size_t)TSV_C_N) });
+    if (rc) { delete st; return rc; }
     *out = st;
     return KAAMER_OK;
 }
@@ -167,8 +155,8 @@ int kaamer_tsv_rows_device(kaamer_tsv_stage *st, const kaamer_tsv_rows_in *in, c
     HIPCHK(hipSetDevice(st->ix->device));
     const int rc = tsv_enqueue(st, in, d_out, out_cap, st->d_line_off, st->max_lines + 1, (hipStream_t)stream);
     if (rc) return rc;
-    out->d_line_off = reinterpret_cast<const uint64_t *>(st->d_line_off);
-    out->d_counts = reinterpret_cast<const uint64_t *>(st->d_counts);
+    out->d_line_off = reinterpret_cast<const uint64_t *>(st->d_line_off.get());
+    out->d_counts = reinterpret_cast<const uint64_t *>(st->d_counts.get());
     out->line_off_capacity = st->max_lines + 1;
     return KAAMER_OK;
 }
@@ -228,14 +216,7 @@ static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_resul
         if (rc) { h.tsv = nullptr; return rc; }
         h.tsv_queries = h.ws->q_cap; h.tsv_lines = lines;
     }
-    if (h.d_tsv_cap < bytes) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (h.d_tsv) (void)hipFree(h.d_tsv);
-        h.d_tsv = nullptr; h.d_tsv_cap = 0;
-        const int rc = dev_alloc(&h.d_tsv, (size_t)bytes + 16);
-        if (rc) return rc;
-        h.d_tsv_cap = (size_t)bytes;
-    }
+    { const int rc = reserve(h.d_tsv, (size_t)bytes + 16, GROW_EXACT, s); if (rc) return rc; }
     const size_t off_bytes = ((size_t)lines + 1) * 8, need = off_bytes + (size_t)bytes;
     if (t->h_tsv_cap < need) {
         if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
@@ -251,7 +232,7 @@ static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_resul
     memset(&pos, 0, sizeof pos);
     if (t->tsv_pos) {   // the bitmaps are in the block (topn_pack_positions); the per-query layout is the workspace's
         pos.d_pos_base = h.ws->d_tp_base; pos.d_pos_bits_len = h.ws->d_tp_len;
-        pos.d_pos_bits = reinterpret_cast<const uint64_t *>(h.d_block);   // (replaced on the device by the block's section)
+        pos.d_pos_bits = reinterpret_cast<const uint64_t *>(h.d_block.get());   // (replaced on the device by the block's section)
         in.pos = &pos;
     }
     in.extract_positions = t->tsv_pos; in.annotations = t->tsv_ann;

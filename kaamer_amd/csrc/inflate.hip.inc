@@ -527,10 +527,11 @@ struct kaamer_inflater {
     int device = 0;
     uint64_t max_comp = 0;
     uint32_t max_blocks = 0;
-    unsigned long long *d_out_off = nullptr;   // max_blocks + 1, then INF_R_N result words
-    uint32_t *d_status = nullptr;              // max_blocks, then the CRC table (256) and the shift matrix (32)
-    unsigned long long *h_res = nullptr;       // pinned
+    DevBuf<unsigned long long> d_out_off;      // max_blocks + 1, then INF_R_N result words
+    DevBuf<uint32_t> d_status;                 // max_blocks, then the CRC table (256) and the shift matrix (32)
+    PinnedBuf<unsigned long long> h_res;
     bool queued = false;
+    ~kaamer_inflater() { (void)hipSetDevice(device); }   // (before the buffers go)
 };
 
 static void inf_launch_cut(const uint8_t *d_text, uint64_t n, unsigned long long *d_cut, hipStream_t s)
@@ -541,15 +542,7 @@ static void inf_launch_cut(const uint8_t *d_text, uint64_t n, unsigned long long
 
 extern "C" {
 
-void kaamer_inflater_free(kaamer_inflater *inf)
-{
-    if (!inf) return;
-    (void)hipSetDevice(inf->device);
-    if (inf->d_out_off) (void)hipFree(inf->d_out_off);
-    if (inf->d_status) (void)hipFree(inf->d_status);
-    if (inf->h_res) (void)hipHostFree(inf->h_res);
-    delete inf;
-}
+void kaamer_inflater_free(kaamer_inflater *inf) { delete inf; }
 
 int kaamer_inflater_create(int device, uint64_t max_comp_bytes, uint32_t max_blocks, kaamer_inflater **out)
 {
@@ -559,17 +552,15 @@ int kaamer_inflater_create(int device, uint64_t max_comp_bytes, uint32_t max_blo
     kaamer_inflater *inf = new (std::nothrow) kaamer_inflater();
     if (!inf) return kaamer_fail(KAAMER_E_NOMEM, "inflater");
     inf->device = device; inf->max_comp = max_comp_bytes; inf->max_blocks = max_blocks;
-    int rc = dev_alloc(&inf->d_out_off, (size_t)max_blocks + 1 + INF_R_N);
-    if (!rc) rc = dev_alloc(&inf->d_status, (size_t)max_blocks + 256 + 32);
-    if (!rc && hipHostMalloc((void **)&inf->h_res, INF_R_N * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-        rc = kaamer_fail(KAAMER_E_NOMEM, "inflater: pinned result words");
+    int rc = reserve_group(nullptr, GROW_EXACT, { want(inf->d_out_off, (size_t)max_blocks + 1 + INF_R_N), want(inf->d_status, (size_t)max_blocks + 256 + 32),
+                                                  want(inf->h_res, (size_t)INF_R_N) });
     if (!rc) {
         uint32_t tabs[256 + 32];
         inf_crc_tables(tabs, tabs + 256);
         const hipError_t e = hipMemcpy(inf->d_status + max_blocks, tabs, sizeof tabs, hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "inflater: H2D: %s", hipGetErrorString(e));
     }
-    if (rc) { kaamer_inflater_free(inf); return rc; }
+    if (rc) { delete inf; return rc; }
     *out = inf;
     return KAAMER_OK;
 }
@@ -641,15 +632,14 @@ int kaamer_text_cut_fastq_device(int device, const uint8_t *d_text, uint64_t n_b
     *cut = 0;
     HIPCHK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *d_cut = nullptr;
-    const int rc = dev_alloc(&d_cut, 1);
+    DevBuf<unsigned long long> d_cut;   // the call's scratch: goes when the call returns (the stream is waited for below)
+    const int rc = reserve(d_cut, 1, GROW_EXACT, s);
     if (rc) return rc;
     unsigned long long h = 0;
     hipError_t e = hipMemsetAsync(d_cut, 0, sizeof h, s);
     if (e == hipSuccess) { inf_launch_cut(d_text, n_bytes, d_cut, s); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(&h, d_cut, sizeof h, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_cut);
     if (e != hipSuccess) return kaamer_fail(KAAMER_E_HIP, "text_cut_fastq_device: %s", hipGetErrorString(e));
     *cut = h;
     return KAAMER_OK;

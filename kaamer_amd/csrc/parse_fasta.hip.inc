@@ -312,11 +312,11 @@ int kaamer_parse_fasta_device(kaamer_text_parser *ps, const uint8_t *d_text, uin
     if ((uintptr_t)d_text & (PT_PIECE - 1)) return kaamer_fail(KAAMER_E_ARG, "parse_fasta_device: the text must start at a 16-byte boundary (any hipMalloc'd buffer does)");
     HIPCHK(hipSetDevice(ps->device));
     const size_t lc = ps->line_cap;
-    if (!ps->d_fa) {   // the words only FASTA needs, at the parser's first FASTA text
-        const int rc = dev_alloc(&ps->d_fa, 2 * (lc + 2) + (size_t)ps->rec_cap + 1 + 1);
+    hipStream_t s = (hipStream_t)stream;
+    {   // the words only FASTA needs, at the parser's first FASTA text
+        const int rc = reserve(ps->d_fa, 2 * (lc + 2) + (size_t)ps->rec_cap + 1 + 1, GROW_EXACT, s);
         if (rc) return rc;
     }
-    hipStream_t s = (hipStream_t)stream;
     PfParams f;
     f.pt = ps->p;
     PtParams &p = f.pt;

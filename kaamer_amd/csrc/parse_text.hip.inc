@@ -414,15 +414,16 @@ struct kaamer_text_parser {
     uint64_t max_text = 0;
     uint32_t rec_cap = 0, line_cap = 0, n_tiles_cap = 0, n_blk_cap = 0;
     int n_cu = 0;
-    uint32_t *d_u32 = nullptr;                 // every u32 array, one allocation
-    unsigned long long *d_u64 = nullptr;       // every u64 array
-    uint8_t *d_seqs = nullptr;
-    kaamer_text_span *d_spans = nullptr;
-    uint32_t *d_fa = nullptr;                  // what only FASTA needs (parse_fasta.hip.inc), allocated at the first FASTA text
-    unsigned long long *h_res = nullptr;       // pinned
+    DevBuf<uint32_t> d_u32;                    // every u32 array, one allocation
+    DevBuf<unsigned long long> d_u64;          // every u64 array
+    DevBuf<uint8_t> d_seqs;
+    DevBuf<kaamer_text_span> d_spans;
+    DevBuf<uint32_t> d_fa;                     // what only FASTA needs (parse_fasta.hip.inc), allocated at the first FASTA text
+    PinnedBuf<unsigned long long> h_res;
     PtParams p{};                              // the device pointers, laid out once
     bool parsed = false;
     bool fasta = false;                        // the last parse was kaamer_parse_fasta_device
+    ~kaamer_text_parser() { (void)hipSetDevice(device); }   // (before the buffers go)
 };
 
 static uint64_t pt_default_line_cap(uint64_t max_text, uint32_t max_records)
@@ -435,18 +436,7 @@ static uint64_t pt_default_line_cap(uint64_t max_text, uint32_t max_records)
 
 extern "C" {
 
-void kaamer_text_parser_free(kaamer_text_parser *ps)
-{
-    if (!ps) return;
-    (void)hipSetDevice(ps->device);
-    if (ps->d_u32) (void)hipFree(ps->d_u32);
-    if (ps->d_u64) (void)hipFree(ps->d_u64);
-    if (ps->d_seqs) (void)hipFree(ps->d_seqs);
-    if (ps->d_spans) (void)hipFree(ps->d_spans);
-    if (ps->d_fa) (void)hipFree(ps->d_fa);
-    if (ps->h_res) (void)hipHostFree(ps->h_res);
-    delete ps;
-}
+void kaamer_text_parser_free(kaamer_text_parser *ps) { delete ps; }
 
 static int text_parser_create_lines(int device, uint64_t max_text_bytes, uint32_t max_records, uint64_t line_cap, kaamer_text_parser **out)
 {
@@ -471,13 +461,9 @@ static int text_parser_create_lines(int device, uint64_t max_text_bytes, uint32_
     const size_t lc = ps->line_cap, nb = (size_t)ps->n_blk_cap + 1, nt = (size_t)ps->n_tiles_cap + 1;
     const size_t n32 = nt + (lc + 2) + (lc + 1) + 6 * nb;
     const size_t n64 = 3 * nb + ((size_t)max_records + 1) + PT_R_N;
-    int rc = dev_alloc(&ps->d_u32, n32);
-    if (!rc) rc = dev_alloc(&ps->d_u64, n64);
-    if (!rc) rc = dev_alloc(&ps->d_seqs, (size_t)max_text_bytes + 2 * PT_PIECE);
-    if (!rc) rc = dev_alloc(&ps->d_spans, (size_t)max_records + 1);
-    if (!rc && hipHostMalloc((void **)&ps->h_res, PT_R_N * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-        rc = kaamer_fail(KAAMER_E_NOMEM, "text parser: pinned result words");
-    if (rc) { kaamer_text_parser_free(ps); return rc; }
+    const int rc = reserve_group(nullptr, GROW_EXACT, { want(ps->d_u32, n32), want(ps->d_u64, n64), want(ps->d_seqs, (size_t)max_text_bytes + 2 * PT_PIECE),
+                                                        want(ps->d_spans, (size_t)max_records + 1), want(ps->h_res, (size_t)PT_R_N) });
+    if (rc) { delete ps; return rc; }
     PtParams &p = ps->p;
     uint32_t *a = ps->d_u32;
     p.tile_nl = a; a += nt;

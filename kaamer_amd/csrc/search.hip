@@ -72,6 +72,36 @@ int kaamer_fail(int code, const char *fmt, ...)
             return kaamer_fail(KAAMER_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// what devbuf.h reports: a refused allocation of `bytes` (0: the stream wait before a regrow failed)
+static int devbuf_fail(hipError_t e, size_t bytes)
+{
+    (void)hipGetLastError();   // a refused allocation is reported here, not by the next launch check on this thread
+    if (!bytes) return kaamer_fail(KAAMER_E_HIP, "hipStreamSynchronize before a regrow failed: %s", hipGetErrorString(e));
+    return kaamer_fail(KAAMER_E_NOMEM, "allocation of %zu bytes: %s", bytes, hipGetErrorString(e));
+}
+#include "devbuf.h"
+
+// an event that is destroyed with its owner
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(DevEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+    DevEvent &operator=(DevEvent &&o) noexcept
+    {
+        if (this != &o) { reset(); e = o.e; o.e = nullptr; }
+        return *this;
+    }
+    ~DevEvent() { reset(); }
+    void reset() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    operator hipEvent_t() const { return e; }
+};
+
+// the growth rules of the buffers that last from call to call
+static constexpr GrowRule GROW_CALL = grow_quarter(64);            // a shard's sequences, offsets and result block (sharded handle)
+static constexpr GrowRule GROW_SLOT = grow_quarter(4096);          // a host slot's staging, text and compressed bytes
+static constexpr GrowRule GROW_SLOT_SEQS = grow_quarter(4096, 16); // ... its sequences (the kernels read 16 bytes past the end)
+static constexpr GrowRule GROW_SLOT_OFF = grow_quarter(16, 1);     // ... its n_seqs + 1 offsets, asked for as n_seqs
+
 // ------------------------------------------------------------------------------------
 // device-side structures
 // ------------------------------------------------------------------------------------
@@ -81,9 +111,8 @@ struct kaamer_workspace;
 struct HostSlot {
     kaamer_workspace *ws = nullptr;
     kaamer_workspace_opts opts{};
-    uint8_t *d_seqs = nullptr;
-    uint64_t *d_off = nullptr;
-    size_t seq_cap = 0, off_cap = 0;
+    DevBuf<uint8_t> d_seqs;
+    DevBuf<uint64_t> d_off;
     hipStream_t stream = nullptr;   // every slot works on its own stream
     bool busy = false;              // (under kaamer_index::pool_mu)
 };
@@ -140,14 +169,11 @@ struct TopSlot {
     kaamer_workspace *ws = nullptr;
     kaamer_workspace_opts opts{};
     hipStream_t stream = nullptr;
-    uint8_t *d_seqs = nullptr;
-    uint64_t *d_off = nullptr;
-    size_t seq_cap = 0, off_cap = 0;
-    uint8_t *h_in = nullptr;   // pinned: the caller's sequences, then (8-byte aligned) its offsets
-    size_t h_in_cap = 0;
-    uint8_t *d_block = nullptr;
-    size_t d_block_cap = 0;
-    size_t block_use = 0;      // bytes of d_block this call may fill: its bound (<= d_block_cap)
+    DevBuf<uint8_t> d_seqs;
+    DevBuf<uint64_t> d_off;
+    PinnedBuf<uint8_t> h_in;   // the caller's sequences, then (8-byte aligned) its offsets
+    DevBuf<uint8_t> d_block;
+    size_t block_use = 0;      // bytes of d_block this call may fill: its bound (<= its capacity)
     uint64_t pos_words = 0;    // bitmap words of that bound (calls that ask for PositionHits of the reported hits)
     size_t guess = 1u << 16;   // bytes of the block copied before its size is known (adapts to the previous call)
     uint64_t aln_guess = 0;    // bytes the alignment sections of the previous call needed, plus a quarter (0: none yet)
@@ -155,32 +181,54 @@ struct TopSlot {
     kaamer_text_parser *parser = nullptr;
     uint64_t parser_text = 0, parser_lines = 0;   // the bounds the parser was created for
     uint32_t parser_recs = 0;
-    uint8_t *h_text = nullptr, *d_text = nullptr; // pinned / device
-    size_t h_text_cap = 0, d_text_cap = 0;
+    PinnedBuf<uint8_t> h_text;
+    DevBuf<uint8_t> d_text;
     // the BGZF call (kaamer_search_bgzf_top_flat), allocated at the slot's first one: compressed bytes, then (8-byte
     // aligned) the block table -- pinned and device -- and the inflater
     kaamer_inflater *inflater = nullptr;
     uint64_t inflater_comp = 0;
     uint32_t inflater_blocks = 0;
-    uint8_t *h_comp = nullptr, *d_comp = nullptr;
-    size_t h_comp_cap = 0, d_comp_cap = 0;
+    PinnedBuf<uint8_t> h_comp;
+    DevBuf<uint8_t> d_comp;
     // the calls that return TSV rows (host_tsv.hip.inc), allocated at the slot's first one: the stage and the rows' buffer.
     // Both bounds start from what the previous call needed, plus a quarter.
     kaamer_tsv_stage *tsv = nullptr;
     uint32_t tsv_queries = 0;       // the bounds the stage was created for
     uint64_t tsv_lines = 0;
-    char *d_tsv = nullptr;
-    size_t d_tsv_cap = 0;
+    DevBuf<char> d_tsv;            // 16 bytes more than the rows may take
     uint64_t tsv_guess_bytes = 0, tsv_guess_lines = 0;
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
 static void top_slot_free(TopSlot &h);
 
-struct kaamer_index {
+// kaamer_index_attach_proteins: the device copy of the Protein.Sequence table next to the index (top_align.hip.inc)
+struct AlnTable {
+    const kaamer_proteins *aln_host = nullptr;   // borrowed: the rows of a result with text read the subjects from it
+    DevBuf<uint8_t> d_aln_raw, d_aln_codes, d_aln_bad;
+    DevBuf<uint64_t> d_aln_off;
+    DevBuf<uint32_t> d_aln_idmap;
+    DevBuf<int> d_aln_matrix;
+    uint32_t aln_idmap_n = 0, aln_entries = 0, aln_max_ns = 0;
+    uint64_t aln_bytes = 0, aln_number_of_aa = 0;
+};
+// kaamer_index_attach_subject_text: what a TSV row prints of a hit's entry (tsv_rows.hip.inc).  Entry i is
+// d_st_bytes[d_st_off[i], d_st_off[i + 1]): EntryId (d_st_idlen[i] bytes), then the annotation columns.  The id map is
+// borrowed from the alignment table when that holds the same table in the same entry order, else owned here.
+struct SubjectText {
+    DevBuf<uint8_t> d_st_bytes;
+    DevBuf<uint64_t> d_st_off;
+    DevBuf<uint32_t> d_st_idlen, d_st_length;
+    DevBuf<uint32_t> d_st_idmap_own;             // its own id map, or the alignment table's once that table is gone
+    const uint32_t *d_st_idmap = nullptr;        // the map in use: d_st_idmap_own, or AlnTable::d_aln_idmap
+    uint32_t st_idmap_n = 0, st_entries = 0, st_features = 0;
+    uint64_t st_bytes = 0, st_max_suffix = 0;
+};
+
+struct kaamer_index : AlnTable, SubjectText {
     int device;
     kh_image_header hdr;
-    kh_bucket *d_buckets;
+    kh_bucket *d_buckets;         // raw: taken over from the device build, or uploaded from an image
     uint32_t *d_arena;
     // kaamer_search_batch (full hit lists): a call takes a free slot (workspace + staging + stream) and gives it back;
     // callers beyond the slots wait for one.  Same pool lock as the slots below.
@@ -191,26 +239,9 @@ struct kaamer_index {
     TopSlot top[KAAMER_MAX_HOST_SLOTS];
     int n_top;
     uint64_t top_pos_words = 0;   // kaamer_index_set_top_positions_bound: first bitmap bound of the host calls (0: the rule)
-    // kaamer_index_attach_proteins: the Protein.Sequence table next to the index (top_align.hip.inc)
-    const kaamer_proteins *aln_host = nullptr;   // borrowed: the rows of a result with text read the subjects from it
-    uint8_t *d_aln_raw = nullptr, *d_aln_codes = nullptr, *d_aln_bad = nullptr;
-    uint64_t *d_aln_off = nullptr;
-    uint32_t *d_aln_idmap = nullptr;
-    int *d_aln_matrix = nullptr;
     int aln_matrix[26 * 26];
-    uint32_t aln_idmap_n = 0, aln_entries = 0, aln_max_ns = 0;
-    uint64_t aln_bytes = 0, aln_number_of_aa = 0;
     uint64_t aln_budget = 0;                     // kaamer_index_set_align_budget (0: the default)
     uint64_t aln_last[3] = {0, 0, 0};            // the last stage: resident waves, slab bytes, long waves
-    // kaamer_index_attach_subject_text: what a TSV row prints of a hit's entry (tsv_rows.hip.inc).  Entry i is
-    // d_st_bytes[d_st_off[i], d_st_off[i + 1]): EntryId (d_st_idlen[i] bytes), then the annotation columns.  The id map is
-    // the alignment table's while st_idmap_shared (same table, same entry order), else owned here.
-    uint8_t *d_st_bytes = nullptr;
-    uint64_t *d_st_off = nullptr;
-    uint32_t *d_st_idlen = nullptr, *d_st_length = nullptr, *d_st_idmap = nullptr;
-    bool st_idmap_shared = false;
-    uint32_t st_idmap_n = 0, st_entries = 0, st_features = 0;
-    uint64_t st_bytes = 0, st_max_suffix = 0;
 };
 
 enum { ST_POOL_FULL = 1u, ST_LIST_FULL = 2u, ST_QUERY_CAP = 4u, ST_AA_CAP = 8u, ST_G_ARENA_FULL = 16u, ST_G_TABLE_FULL = 32u,
@@ -809,167 +840,120 @@ __global__ void finalize_kernel(unsigned long long *replicas, kaamer_counters *o
 // workspace
 // ------------------------------------------------------------------------------------
 struct kaamer_workspace {
-    int device;
-    kaamer_workspace_opts opts;
-    uint32_t q_cap;
-    uint64_t hit_cap, sparse_cap, g_slots, pos_cap;
-    bool compact;                       // finish with CSR in query order (scan + gather pass)
-    uint64_t *d_csr_off;                // compact form: CSR offsets
-    uint32_t *d_c_pid, *d_c_km, *d_c_fp;
-    int g_grid, p_grid, n_cu, pack_grid, pack_grid_long;
-    uint32_t pack_shift;                // log2 of the group / pack window (slots) of a search: 12 for protein, 9 for ORF batches
-    int wide_reads;                     // lane-per-read kernel: 1 the wide one, 0 the narrow one, -1 picked from the mean read length
-    bool pack_long;                     // ORF batches always take the pack kernel's larger arena
+    int device = 0;
+    kaamer_workspace_opts opts{};
+    uint32_t q_cap = 0;
+    uint64_t hit_cap = 0, sparse_cap = 0, g_slots = 0, pos_cap = 0;
+    bool compact = false;               // finish with CSR in query order (scan + gather pass)
+    DevBuf<uint64_t> d_csr_off;         // compact form: CSR offsets
+    DevBuf<uint32_t> d_c_pid, d_c_km, d_c_fp;
+    int g_grid = 0, p_grid = 0, n_cu = 0, pack_grid = 0, pack_grid_long = 0;
+    uint32_t pack_shift = 0;            // log2 of the group / pack window (slots) of a search: 12 for protein, 9 for ORF batches
+    int wide_reads = 0;                 // lane-per-read kernel: 1 the wide one, 0 the narrow one, -1 picked from the mean read length
+    bool pack_long = false;             // ORF batches always take the pack kernel's larger arena
     // device buffers
-    kaamer_query_meta *d_q;
-    uint32_t *d_nq;
-    unsigned long long *d_n_pos;
-    unsigned long long *d_valid;        // one bit per residue position
-    uint32_t *d_vals;                   // probe result per residue position
-    uint32_t *d_q_cnt;
-    unsigned long long *d_pool_cursor;  // CURSOR_STRIDE apart: G-tier tail cursor, G arena cursor (count), G arena cursor (positions)
-    WorkItem *d_lists;                  // [N_LISTS][q_cap] (only the G tier's overflow list is used)
-    QInfo *d_qinfo;
-    uint32_t *d_slots;
-    uint64_t *d_slot_off;
-    uint32_t *d_group_first;
-    uint32_t *d_n_groups;
-    uint32_t groups_cap;
+    DevBuf<kaamer_query_meta> d_q;
+    DevBuf<uint32_t> d_nq;
+    DevBuf<unsigned long long> d_n_pos;
+    DevBuf<unsigned long long> d_valid;        // one bit per residue position
+    DevBuf<uint32_t> d_vals;                   // probe result per residue position
+    DevBuf<uint32_t> d_q_cnt;
+    DevBuf<unsigned long long> d_pool_cursor;  // CURSOR_STRIDE apart: G-tier tail cursor, G arena cursor (count), G arena cursor (positions)
+    DevBuf<WorkItem> d_lists;                  // [N_LISTS][q_cap] (only the G tier's overflow list is used)
+    DevBuf<QInfo> d_qinfo;
+    DevBuf<uint32_t> d_slots;
+    DevBuf<uint64_t> d_slot_off;
+    DevBuf<uint32_t> d_group_first;
+    DevBuf<uint32_t> d_n_groups;
+    uint32_t groups_cap = 0;
     // the counting stage on a stream of its own (kaamer_workspace_set_count_stream): the caller's stream then carries
     // prep + probe only, so that the probe kernel of batch i + 1 starts while batch i is still counting
-    hipStream_t count_stream;
-    hipEvent_t ev_probe, ev_count;
-    bool split_pending;                 // the last search's counting stage is on count_stream: consumers wait for ev_count
-    int grp_grid;
+    hipStream_t count_stream = nullptr;
+    DevEvent ev_probe, ev_count;
+    bool split_pending = false;         // the last search's counting stage is on count_stream: consumers wait for ev_count
+    int grp_grid = 0;
     // nucleotide / reads input: 6-frame translation products
-    bool nucleotide;
-    uint64_t aa_cap, sa_cap;
-    uint32_t *d_cnt3;                   // [3][6*max_seqs] ORF / aa / starts counts per (sequence, frame)
-    uint64_t *d_off3;                   // [3][6*max_seqs+1] their exclusive scans
-    uint32_t *d_n6;                     // device scalar 6*n_seqs
+    bool nucleotide = false;
+    uint64_t aa_cap = 0, sa_cap = 0;
+    DevBuf<uint32_t> d_cnt3;            // [3][6*max_seqs] ORF / aa / starts counts per (sequence, frame)
+    DevBuf<uint64_t> d_off3;            // [3][6*max_seqs+1] their exclusive scans
+    DevBuf<uint32_t> d_n6;              // device scalar 6*n_seqs
     // long sequences (> TS_MAX nt) are translated piece-wise: list, pieces per frame, per-piece counts and their scans
-    uint32_t max_long;
-    uint64_t max_piece_items;
-    uint32_t *d_long_seq, *d_long_np, *d_pcnt3, *d_n_piece_items, *d_piece_li;
-    uint64_t *d_piece_base, *d_poff3;
-    kaamer_query_meta *d_tmp_meta;
-    uint8_t *d_orf_aa;
-    int32_t *d_starts_alt;
-    uint32_t max_seqs;
-    unsigned long long *d_chain;        // layout_kernel: one word per tile, tagged with the batch epoch
-    uint2 *d_sched;                     // schedule_kernel: ticket -> (group, first query)
-    uint64_t *d_group_start;            // layout_kernel: slot at which the group's first table starts
-    unsigned long long *d_lay_total;    // total table slots of the batch
-    uint32_t *d_slot_scale;             // table capacity scale of the next batch, sixteenths (finalize_body)
-    uint32_t slot_scale_cap;            // ceiling of the scale (8: beyond it the tables leave the pack kernel's arena)
-    unsigned long long table_room;      // slots of the hit arrays a batch's tables may take (the G tier's lists come after them)
-    uint32_t slot_scale_margin;         // sixteenths: tables of (hits per k-mer) x this
-    bool dense_tables;                  // the last finished batch left a table scale of 2 or more: ORF packs take the larger arena
-    uint32_t *d_n_sched;
+    uint32_t max_long = 0;
+    uint64_t max_piece_items = 0;
+    DevBuf<uint32_t> d_long_seq, d_long_np, d_pcnt3, d_n_piece_items, d_piece_li;
+    DevBuf<uint64_t> d_piece_base, d_poff3;
+    DevBuf<kaamer_query_meta> d_tmp_meta;
+    DevBuf<uint8_t> d_orf_aa;
+    DevBuf<int32_t> d_starts_alt;
+    uint32_t max_seqs = 0;
+    DevBuf<unsigned long long> d_chain;        // layout_kernel: one word per tile, tagged with the batch epoch
+    DevBuf<uint2> d_sched;                     // schedule_kernel: ticket -> (group, first query)
+    DevBuf<uint64_t> d_group_start;            // layout_kernel: slot at which the group's first table starts
+    DevBuf<unsigned long long> d_lay_total;    // total table slots of the batch
+    DevBuf<uint32_t> d_slot_scale;             // table capacity scale of the next batch, sixteenths (finalize_body)
+    uint32_t slot_scale_cap = 0;        // ceiling of the scale (8: beyond it the tables leave the pack kernel's arena)
+    unsigned long long table_room = 0;  // slots of the hit arrays a batch's tables may take (the G tier's lists come after them)
+    uint32_t slot_scale_margin = 0;     // sixteenths: tables of (hits per k-mer) x this
+    bool dense_tables = false;          // the last finished batch left a table scale of 2 or more: ORF packs take the larger arena
+    DevBuf<uint32_t> d_n_sched;
     // post-steps (kaamer_topn_device), allocated on first use
-    uint32_t topn_k;
-    uint32_t *d_top_cnt, *d_top_pid, *d_top_km, *d_top_fp;
-    int32_t *d_top_trim, *d_top_start, *d_top_size;
-    bool last_was_merge;
+    uint32_t topn_k = 0;
+    DevBuf<uint32_t> d_top_cnt, d_top_pid, d_top_km, d_top_fp;
+    DevBuf<int32_t> d_top_trim, d_top_start, d_top_size;
+    bool last_was_merge = false;
     // PositionHits of the reported hits (kaamer_topn_positions_device), allocated on first use
-    uint32_t *d_tp_words;
-    int32_t *d_tp_len;
-    uint64_t *d_tp_base;
-    unsigned long long *d_tp_bits;
-    uint64_t tp_alloc;                  // words d_tp_bits holds (grow-only)
+    DevBuf<uint32_t> d_tp_words;
+    DevBuf<int32_t> d_tp_len;
+    DevBuf<uint64_t> d_tp_base;
+    DevBuf<unsigned long long> d_tp_bits;      // grow-only
     // alignment of the reported hits (top_align.hip.inc), allocated on first use, grow-only
-    const uint8_t *last_seqs;           // the batch input of the last search (protein queries are aligned from it)
-    uint8_t *d_ta_qcodes;               // the queries' letter codes, by residue position
-    TaLayout *d_ta_lay;
-    unsigned long long *d_ta_ctr;
-    uint64_t *d_ta_eoff;                // device-resident form: its own scan of top_cnt
-    kaamer_align_pair *d_ta_items;      // ... and its pair records
-    uint64_t ta_items_cap;
-    uint8_t *d_ta_dirs, *d_ta_ops, *d_ta_ldirs, *d_ta_lops;   // per resident wave: direction slab, operations (wave / long form)
-    int *d_ta_lbnd;
-    uint64_t ta_dirs_cap, ta_ops_cap, ta_ldirs_cap, ta_lops_cap, ta_lbnd_cap;
+    const uint8_t *last_seqs = nullptr; // the batch input of the last search (protein queries are aligned from it)
+    DevBuf<uint8_t> d_ta_qcodes;        // the queries' letter codes, by residue position
+    DevBuf<TaLayout> d_ta_lay;
+    DevBuf<unsigned long long> d_ta_ctr;
+    DevBuf<uint64_t> d_ta_eoff;         // device-resident form: its own scan of top_cnt
+    DevBuf<kaamer_align_pair> d_ta_items;      // ... and its pair records
+    DevBuf<uint8_t> d_ta_dirs, d_ta_ops, d_ta_ldirs, d_ta_lops;   // per resident wave: direction slab, operations (wave / long form)
+    DevBuf<int> d_ta_lbnd;
     XState x;                           // exchange step of the sharded index (kaamer_exchange_pack / _merge; exchange.hip.inc)
     // reported-only packing of the top-N results (kaamer_search_batch_top), allocated on first use
-    uint32_t rep_k;
-    uint32_t *d_rep_flag, *d_rep_aalen, *d_rep_query, *d_rep_pid, *d_rep_km, *d_rep_fp;
-    int32_t *d_rep_trim;
-    uint64_t *d_rep_rank, *d_rep_eoff, *d_rep_aoff, *d_rep_off;
-    kaamer_query_meta *d_rep_q;
-    uint8_t *d_rep_aa;
-    uint32_t lay_epoch;
-    unsigned long long *d_tr_chain;     // translate_reads_kernel: three words per 64-sequence chunk, tagged with tr_epoch
-    uint32_t tr_epoch;
-    uint32_t *d_list_counts;            // [N_LISTS] + queue head + status (zeroed by finalize)
-    uint32_t *d_status_out;             // status of the last finished batch; the word after it: its LIST_G entries (a search's)
-    int64_t g_last;                     // LIST_G entries of the last batch kaamer_workspace_finish looked at, or G_LAST_UNKNOWN
-    int g_floor;                        // workgroups of a G-tier launch behind a batch that had none (g_tier_grid)
-    bool clean;                         // per-batch device state is known to be zeroed
-    bool firstpos;                      // track the lowest matching position per hit
-    bool want_positions;                // full PositionHits bitmaps
-    uint64_t bits_cap;                  // u64 words of bitmap storage
-    uint32_t *d_pos_words;              // per query: hits x words per hit
-    uint64_t *d_pos_base;               // exclusive scan of the above
-    uint64_t *d_pos_off;                // per hit: first word of its bitmap
-    unsigned long long *d_pos_bits;
-    uint32_t *d_g_keys;
-    unsigned long long *d_counter_replicas;
-    kaamer_counters *d_counters;
-    uint64_t *d_bsum;
-    uint32_t n_scan_blocks;
-    uint64_t *d_hit_off;
-    uint32_t *d_hit_pid, *d_hit_km, *d_hit_fp;
-    std::vector<hipEvent_t> *ev;  // 5 events per timed call: total0, probe0, probe1(=count0), count1, total1
-    uint32_t n_timed, time_every, call_no;
+    DevBuf<uint32_t> d_rep_flag, d_rep_aalen;
+    DevBuf<uint64_t> d_rep_rank, d_rep_eoff, d_rep_aoff;
+    uint32_t lay_epoch = 0;
+    DevBuf<unsigned long long> d_tr_chain;     // translate_reads_kernel: three words per 64-sequence chunk, tagged with tr_epoch
+    uint32_t tr_epoch = 0;
+    DevBuf<uint32_t> d_list_counts;     // [N_LISTS] + queue head + status (zeroed by finalize)
+    DevBuf<uint32_t> d_status_out;      // status of the last finished batch; the word after it: its LIST_G entries (a search's)
+    int64_t g_last = 0;                 // LIST_G entries of the last batch kaamer_workspace_finish looked at, or G_LAST_UNKNOWN
+    int g_floor = 0;                    // workgroups of a G-tier launch behind a batch that had none (g_tier_grid)
+    bool clean = false;                 // per-batch device state is known to be zeroed
+    bool firstpos = false;              // track the lowest matching position per hit
+    bool want_positions = false;        // full PositionHits bitmaps
+    uint64_t bits_cap = 0;              // u64 words of bitmap storage
+    DevBuf<uint32_t> d_pos_words;       // per query: hits x words per hit
+    DevBuf<uint64_t> d_pos_base;        // exclusive scan of the above
+    DevBuf<uint64_t> d_pos_off;         // per hit: first word of its bitmap
+    DevBuf<unsigned long long> d_pos_bits;
+    DevBuf<uint32_t> d_g_keys;
+    DevBuf<unsigned long long> d_counter_replicas;
+    DevBuf<kaamer_counters> d_counters;
+    DevBuf<uint64_t> d_bsum;
+    uint32_t n_scan_blocks = 0;
+    DevBuf<uint64_t> d_hit_off;
+    DevBuf<uint32_t> d_hit_pid, d_hit_km, d_hit_fp;
+    std::vector<hipEvent_t> ev;  // 5 events per timed call: total0, probe0, probe1(=count0), count1, total1
+    uint32_t n_timed = 0, time_every = 0, call_no = 0;
+
+    // the device is selected before any member goes (a destructor's body runs before its members' destructors)
+    ~kaamer_workspace()
+    {
+        (void)hipSetDevice(device);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
 };
 #define EV_PER_CALL 5
 #define G_LAST_UNKNOWN (-1)
-
-template <class T> static int dev_alloc(T **p, size_t n)
-{
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, (n ? n : 1) * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // a refused allocation is reported here, not by the next launch check on this thread
-        return kaamer_fail(KAAMER_E_NOMEM, "hipMalloc(%zu bytes): %s", n * sizeof(T), hipGetErrorString(e));
-    }
-    return KAAMER_OK;
-}
-
-// a device buffer that lasts from call to call: made again, a quarter larger than asked for, when it is too small
-template <class T> static int dev_grow(T **p, size_t *cap, size_t need)
-{
-    if (*cap >= need) return KAAMER_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t want = need + need / 4 + 64;
-    const int rc = dev_alloc(p, want);
-    if (!rc) *cap = want;
-    return rc;
-}
-
-// The buffers of a host slot (TopSlot) that work on its stream: made again for `need` elements plus a quarter and 4096
-// when they hold fewer than need + pad, once the stream is done with the old one.
-static size_t slot_buf_cap(size_t need) { return need + need / 4 + 4096; }
-template <class T> static int slot_grow_dev(hipStream_t s, T **p, size_t *cap, size_t need, size_t pad = 0)
-{
-    if (*cap >= need + pad) return KAAMER_OK;
-    if (*p) { HIPCHK(hipStreamSynchronize(s)); (void)hipFree(*p); }
-    *p = nullptr; *cap = 0;
-    const int rc = dev_alloc(p, slot_buf_cap(need));
-    if (!rc) *cap = slot_buf_cap(need);
-    return rc;
-}
-// ... and its pinned staging (bytes); `what` names it in the refusal
-static int slot_grow_pinned(hipStream_t s, uint8_t **p, size_t *cap, size_t need, const char *what)
-{
-    if (*cap >= need) return KAAMER_OK;
-    if (*p) { HIPCHK(hipStreamSynchronize(s)); (void)hipHostFree(*p); }
-    *p = nullptr; *cap = 0;
-    if (hipHostMalloc((void **)p, slot_buf_cap(need), hipHostMallocDefault) != hipSuccess)
-        return kaamer_fail(KAAMER_E_NOMEM, "pinned %s (%zu bytes)", what, slot_buf_cap(need));
-    *cap = slot_buf_cap(need);
-    return KAAMER_OK;
-}
 
 static void launch_group(const CountParams &p, int grid, bool firstpos, hipStream_t s)
 {
@@ -1117,36 +1101,16 @@ static SearchKnobs read_knobs()
     return k;
 }
 
-// a grow-only device buffer of the workspace; whatever still reads the old one is on `s`
-template <class T> static int ta_grow(T **buf, uint64_t *cap, uint64_t need, hipStream_t s)
-{
-    if (*buf && *cap >= need) return KAAMER_OK;
-    if (*buf) { HIPCHK(hipStreamSynchronize(s)); (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
-    const int rc = dev_alloc(buf, (size_t)need);
-    if (!rc) *cap = need;
-    return rc;
-}
-
-// the device copy of the attached Protein.Sequence table (kaamer_index_attach_proteins)
+// the attached Protein.Sequence table goes (kaamer_index_attach_proteins, kaamer_index_close; the device is selected)
 static void aln_table_free(kaamer_index *ix)
 {
-    // (a subject text that shares the id map keeps it: it is the owner from here on)
-    if (ix->st_idmap_shared) { ix->st_idmap_shared = false; ix->d_aln_idmap = nullptr; }
-    void *bufs[] = { ix->d_aln_raw, ix->d_aln_codes, ix->d_aln_bad, ix->d_aln_off, ix->d_aln_idmap, ix->d_aln_matrix };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    ix->d_aln_raw = ix->d_aln_codes = ix->d_aln_bad = nullptr; ix->d_aln_off = nullptr; ix->d_aln_idmap = nullptr; ix->d_aln_matrix = nullptr;
-    ix->aln_host = nullptr; ix->aln_idmap_n = ix->aln_entries = ix->aln_max_ns = 0; ix->aln_bytes = ix->aln_number_of_aa = 0;
+    // (a subject text that borrows the id map takes it over: it is the owner from here on)
+    if (ix->d_aln_idmap && ix->d_st_idmap == ix->d_aln_idmap) ix->d_st_idmap_own = std::move(ix->d_aln_idmap);
+    static_cast<AlnTable &>(*ix) = AlnTable();
 }
 
-// the device copy of the attached subject text (kaamer_index_attach_subject_text)
-static void subject_text_free(kaamer_index *ix)
-{
-    void *bufs[] = { ix->d_st_bytes, ix->d_st_off, ix->d_st_idlen, ix->d_st_length, ix->st_idmap_shared ? nullptr : ix->d_st_idmap };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    ix->d_st_bytes = nullptr; ix->d_st_off = nullptr; ix->d_st_idlen = ix->d_st_length = ix->d_st_idmap = nullptr;
-    ix->st_idmap_shared = false;
-    ix->st_idmap_n = ix->st_entries = ix->st_features = 0; ix->st_bytes = ix->st_max_suffix = 0;
-}
+// ... and the attached subject text (kaamer_index_attach_subject_text)
+static void subject_text_free(kaamer_index *ix) { static_cast<SubjectText &>(*ix) = SubjectText(); }
 
 #include "parse_text.hip.inc"
 #include "parse_fasta.hip.inc"
@@ -1190,10 +1154,12 @@ int kaamer_index_open_image(const kaamer_image *img, int device, kaamer_index **
     ix->device = device;
     ix->n_top = read_knobs().host_slots;
     ix->hdr = img->hdr;
-    ix->d_buckets = nullptr;
-    ix->d_arena = nullptr;
-    int rc = dev_alloc(&ix->d_buckets, (size_t)img->hdr.n_buckets);
-    if (!rc) rc = dev_alloc(&ix->d_arena, (size_t)(img->hdr.arena_words < 4 ? 4 : img->hdr.arena_words));
+    DevBuf<kh_bucket> buckets;
+    DevBuf<uint32_t> arena;
+    const int rc = reserve_group(nullptr, GROW_EXACT, { want(buckets, (size_t)img->hdr.n_buckets),
+                                                        want(arena, (size_t)(img->hdr.arena_words < 4 ? 4 : img->hdr.arena_words)) });
+    ix->d_buckets = buckets.release();
+    ix->d_arena = arena.release();
     if (rc) { kaamer_index_close(ix); return rc; }
     hipError_t e = hipMemcpy(ix->d_buckets, img->buckets, (size_t)img->hdr.n_buckets * sizeof(kh_bucket), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_arena, img->arena, (size_t)img->hdr.arena_words * 4, hipMemcpyHostToDevice);
@@ -1256,15 +1222,11 @@ void kaamer_index_close(kaamer_index *ix)
         if (h.stream) (void)hipStreamSynchronize(h.stream);
         if (h.stream) (void)hipStreamDestroy(h.stream);
         if (h.ws) kaamer_workspace_free(h.ws);
-        if (h.d_seqs) (void)hipFree(h.d_seqs);
-        if (h.d_off) (void)hipFree(h.d_off);
     }
     for (TopSlot &h : ix->top) top_slot_free(h);
-    if (ix->d_buckets) (void)hipFree(ix->d_buckets);
+    if (ix->d_buckets) (void)hipFree(ix->d_buckets);   // (raw: see kaamer_index)
     if (ix->d_arena) (void)hipFree(ix->d_arena);
-    aln_table_free(ix);
-    subject_text_free(ix);
-    delete ix;
+    delete ix;   // the slots' buffers and the attached tables go with it: the device is still selected
 }
 
 int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out)
@@ -1274,26 +1236,7 @@ int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out)
     return KAAMER_OK;
 }
 
-void kaamer_workspace_free(kaamer_workspace *ws)
-{
-    if (!ws) return;
-    (void)hipSetDevice(ws->device);
-    void *bufs[] = { ws->d_q, ws->d_nq, ws->d_n_pos, ws->d_valid, ws->d_vals, ws->d_cnt3, ws->d_off3, ws->d_n6, ws->d_long_seq, ws->d_long_np, ws->d_pcnt3, ws->d_n_piece_items, ws->d_piece_li, ws->d_piece_base, ws->d_poff3,
-                     ws->d_tmp_meta, ws->d_orf_aa, ws->d_starts_alt, ws->d_q_cnt, ws->d_csr_off, ws->d_c_pid, ws->d_c_km, ws->d_c_fp,
-                     ws->d_pool_cursor, ws->d_lists, ws->d_list_counts, ws->d_status_out, ws->d_qinfo, ws->d_slots,
-                     ws->d_slot_off, ws->d_group_first, ws->d_n_groups, ws->d_pos_words, ws->d_pos_base, ws->d_pos_off, ws->d_pos_bits, ws->d_g_keys,
-                     ws->d_counter_replicas, ws->d_counters, ws->d_bsum, ws->d_chain, ws->d_tr_chain, ws->d_sched, ws->d_n_sched, ws->d_group_start, ws->d_lay_total, ws->d_slot_scale, ws->d_top_cnt, ws->d_top_pid, ws->d_top_km, ws->d_top_fp, ws->d_top_trim, ws->d_top_start, ws->d_top_size, ws->d_rep_flag, ws->d_rep_aalen, ws->d_rep_query, ws->d_rep_pid, ws->d_rep_km, ws->d_rep_fp, ws->d_rep_trim, ws->d_rep_rank, ws->d_rep_eoff, ws->d_rep_aoff, ws->d_rep_off, ws->d_rep_q, ws->d_rep_aa, ws->d_hit_off,
-                     ws->d_hit_pid, ws->d_hit_km, ws->d_hit_fp,
-                     ws->d_tp_words, ws->d_tp_len, ws->d_tp_base, ws->d_tp_bits,
-                     ws->d_ta_qcodes, ws->d_ta_lay, ws->d_ta_ctr, ws->d_ta_eoff, ws->d_ta_items, ws->d_ta_dirs, ws->d_ta_ops, ws->d_ta_ldirs, ws->d_ta_lops, ws->d_ta_lbnd };
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    x_state_free(ws->x);
-    if (ws->ev) {
-        for (hipEvent_t e : *ws->ev) (void)hipEventDestroy(e);
-        delete ws->ev;
-    }
-    delete ws;
-}
+void kaamer_workspace_free(kaamer_workspace *ws) { delete ws; }
 
 uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws) { return ws ? ws->q_cap : 0u; }
 
@@ -1304,7 +1247,6 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
     HIPCHK(hipSetDevice(ix->device));
     kaamer_workspace *ws = new (std::nothrow) kaamer_workspace();
     if (!ws) return kaamer_fail(KAAMER_E_NOMEM, "workspace alloc");
-    memset(ws, 0, sizeof *ws);
     ws->device = ix->device;
     ws->opts = *opts;
     ws->opts.seq_type = seq_base(opts->seq_type);   // a workspace serves every genetic code: the code is the call's
@@ -1405,44 +1347,23 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
         }
         ws->n_scan_blocks = (uint32_t)((n + 1 + SCAN_TILE - 1) / SCAN_TILE);
     }
-    rc = dev_alloc(&ws->d_q, ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_nq, 1);
-    if (!rc) rc = dev_alloc(&ws->d_n_pos, 1);
-    if (!rc) rc = dev_alloc(&ws->d_valid, (size_t)(ws->pos_cap / 64 + 2));
-    if (!rc) rc = dev_alloc(&ws->d_vals, (size_t)ws->pos_cap);
-    if (!rc && ws->nucleotide) {
-        const size_t n6 = (size_t)ws->max_seqs * 6;
-        rc = dev_alloc(&ws->d_cnt3, 3 * n6);
-        if (!rc) rc = dev_alloc(&ws->d_off3, 3 * (n6 + 1));
-        if (!rc) rc = dev_alloc(&ws->d_n6, 1);
-        if (!rc) rc = dev_alloc(&ws->d_long_seq, (size_t)ws->max_long + 1);
-        if (!rc) rc = dev_alloc(&ws->d_piece_li, (size_t)ws->max_piece_items / 6 + 2);
-        if (!rc) rc = dev_alloc(&ws->d_long_np, (size_t)ws->max_long + 1);
-        if (!rc) rc = dev_alloc(&ws->d_piece_base, (size_t)ws->max_long + 2);
-        if (!rc) rc = dev_alloc(&ws->d_pcnt3, 3 * (size_t)ws->max_piece_items);
-        if (!rc) rc = dev_alloc(&ws->d_poff3, 3 * ((size_t)ws->max_piece_items + 1));
-        if (!rc) rc = dev_alloc(&ws->d_n_piece_items, 1);
-        if (!rc) rc = dev_alloc(&ws->d_tmp_meta, ws->q_cap);
-        const size_t tcw = 3 * ((size_t)ws->max_seqs / 64 + 2);
-        if (!rc) rc = dev_alloc(&ws->d_tr_chain, tcw);
-        if (!rc && hipMemset(ws->d_tr_chain, 0, tcw * sizeof(unsigned long long)) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset");
-        if (!rc) rc = dev_alloc(&ws->d_orf_aa, (size_t)ws->aa_cap + 64);
-        if (!rc) rc = dev_alloc(&ws->d_starts_alt, (size_t)ws->sa_cap + 64);
-    }
-    if (!rc) rc = dev_alloc(&ws->d_q_cnt, ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_pool_cursor, (size_t)3 * CURSOR_STRIDE);
-    if (!rc) rc = dev_alloc(&ws->d_lists, (size_t)N_LISTS * ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_list_counts, N_SMALL_SLOTS);
-    if (!rc) rc = dev_alloc(&ws->d_status_out, 2);
-    if (!rc && hipMemset(ws->d_status_out, 0, 2 * sizeof(uint32_t)) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset");
-    if (!rc) rc = dev_alloc(&ws->d_qinfo, ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_slots, ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_slot_off, (size_t)ws->q_cap + 1);
-    if (!rc) rc = dev_alloc(&ws->d_group_first, ws->groups_cap);
-    if (!rc) rc = dev_alloc(&ws->d_sched, ws->groups_cap);
-    if (!rc) rc = dev_alloc(&ws->d_group_start, ws->groups_cap);
-    if (!rc) rc = dev_alloc(&ws->d_lay_total, 1);
-    if (!rc) rc = dev_alloc(&ws->d_slot_scale, 4);
+    auto zero = [&rc](void *p, size_t bytes) { if (!rc && hipMemset(p, 0, bytes) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset"); };
+    const size_t qc = ws->q_cap;
+    // every batch: queries, probe results, table layout and schedule, counters, the sparse hit arrays
+    rc = reserve_group(nullptr, GROW_EXACT, {
+        want(ws->d_q, qc), want(ws->d_nq, 1), want(ws->d_n_pos, 1), want(ws->d_valid, (size_t)(ws->pos_cap / 64 + 2)), want(ws->d_vals, (size_t)ws->pos_cap),
+        want(ws->d_q_cnt, qc), want(ws->d_pool_cursor, (size_t)3 * CURSOR_STRIDE), want(ws->d_lists, (size_t)N_LISTS * qc),
+        want(ws->d_list_counts, N_SMALL_SLOTS), want(ws->d_status_out, 2), want(ws->d_qinfo, qc), want(ws->d_slots, qc), want(ws->d_slot_off, qc + 1),
+        want(ws->d_group_first, ws->groups_cap), want(ws->d_sched, ws->groups_cap), want(ws->d_group_start, ws->groups_cap), want(ws->d_lay_total, 1),
+        want(ws->d_slot_scale, 4), want(ws->d_n_sched, 1), want(ws->d_n_groups, 1),
+        want(ws->d_g_keys, (size_t)(4 * ws->g_slots)),  // 16-byte slots {id, count, lowest position, -}
+        want(ws->d_counter_replicas, (size_t)CTR_REPLICAS * CTR_N), want(ws->d_counters, 1), want(ws->d_bsum, ws->n_scan_blocks),
+        want(ws->d_chain, qc / PL_TILE + 2), want(ws->d_hit_off, qc + 1),
+        want(ws->d_hit_pid, (size_t)ws->sparse_cap), want(ws->d_hit_km, (size_t)ws->sparse_cap), want(ws->d_hit_fp, (size_t)ws->sparse_cap) });
+    zero(ws->d_status_out, 2 * sizeof(uint32_t));
+    zero(ws->d_chain, (qc / PL_TILE + 2) * sizeof(unsigned long long));
+    // first positions are written only when asked for; otherwise the array reads as zeros
+    if (!ws->firstpos) zero(ws->d_hit_fp, ws->sparse_cap * sizeof(uint32_t));
     if (!rc) {
         const uint32_t one = SLOT_SCALE_ONE;
         if (hipMemcpy(ws->d_slot_scale, &one, 4, hipMemcpyHostToDevice) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "workspace init");
@@ -1457,40 +1378,29 @@ int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts,
             fprintf(stderr, "[kaamer workspace] pos_cap %llu q_cap %u hit_cap %llu sparse_cap %llu table_room %llu slot_scale_cap %u/16\n", (unsigned long long)ws->pos_cap,
                     ws->q_cap, (unsigned long long)ws->hit_cap, (unsigned long long)ws->sparse_cap, ws->table_room, ws->slot_scale_cap);
     }
-    if (!rc) rc = dev_alloc(&ws->d_n_sched, 1);
-    if (!rc) rc = dev_alloc(&ws->d_n_groups, 1);
-
+    if (!rc && ws->nucleotide) {   // the products of the 6-frame translation
+        const size_t n6 = (size_t)ws->max_seqs * 6, ml = ws->max_long, mp = (size_t)ws->max_piece_items;
+        const size_t tcw = 3 * ((size_t)ws->max_seqs / 64 + 2);
+        rc = reserve_group(nullptr, GROW_EXACT, {
+            want(ws->d_cnt3, 3 * n6), want(ws->d_off3, 3 * (n6 + 1)), want(ws->d_n6, 1), want(ws->d_long_seq, ml + 1), want(ws->d_piece_li, mp / 6 + 2),
+            want(ws->d_long_np, ml + 1), want(ws->d_piece_base, ml + 2), want(ws->d_pcnt3, 3 * mp), want(ws->d_poff3, 3 * (mp + 1)),
+            want(ws->d_n_piece_items, 1), want(ws->d_tmp_meta, qc), want(ws->d_tr_chain, tcw),
+            want(ws->d_orf_aa, (size_t)ws->aa_cap + 64), want(ws->d_starts_alt, (size_t)ws->sa_cap + 64) });
+        zero(ws->d_tr_chain, tcw * sizeof(unsigned long long));
+    }
     ws->want_positions = opts->want_positions != 0;
-    if (!rc && ws->want_positions) {
+    if (!rc && ws->want_positions) {   // full PositionHits bitmaps
         ws->bits_cap = opts->max_pos_words ? opts->max_pos_words : ws->hit_cap * 8;
-        rc = dev_alloc(&ws->d_pos_words, ws->q_cap);
-        if (!rc) rc = dev_alloc(&ws->d_pos_base, (size_t)ws->q_cap + 1);
-        if (!rc) rc = dev_alloc(&ws->d_pos_off, ws->sparse_cap);
-        if (!rc) rc = dev_alloc(&ws->d_pos_bits, ws->bits_cap);
+        rc = reserve_group(nullptr, GROW_EXACT, { want(ws->d_pos_words, qc), want(ws->d_pos_base, qc + 1), want(ws->d_pos_off, (size_t)ws->sparse_cap),
+                                                  want(ws->d_pos_bits, (size_t)ws->bits_cap) });
     }
-    if (!rc) rc = dev_alloc(&ws->d_g_keys, 4 * ws->g_slots);  // 16-byte slots {id, count, lowest position, -}
-    if (!rc) rc = dev_alloc(&ws->d_counter_replicas, (size_t)CTR_REPLICAS * CTR_N);
-    if (!rc) rc = dev_alloc(&ws->d_counters, 1);
-    if (!rc) rc = dev_alloc(&ws->d_bsum, ws->n_scan_blocks);
-    if (!rc) rc = dev_alloc(&ws->d_chain, (size_t)ws->q_cap / PL_TILE + 2);
-    if (!rc && hipMemset(ws->d_chain, 0, ((size_t)ws->q_cap / PL_TILE + 2) * sizeof(unsigned long long)) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset");
-    if (!rc) rc = dev_alloc(&ws->d_hit_off, (size_t)ws->q_cap + 1);
     ws->compact = opts->compact != 0;
-    if (!rc) rc = dev_alloc(&ws->d_hit_pid, ws->sparse_cap);
-    if (!rc) rc = dev_alloc(&ws->d_hit_km, ws->sparse_cap);
-    if (!rc) rc = dev_alloc(&ws->d_hit_fp, ws->sparse_cap);
-    // first positions are written only when asked for; otherwise the array reads as zeros
-    if (!rc && !ws->firstpos && hipMemset(ws->d_hit_fp, 0, ws->sparse_cap * sizeof(uint32_t)) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset");
-    if (!rc && ws->compact) {
-        rc = dev_alloc(&ws->d_csr_off, (size_t)ws->q_cap + 1);
-        if (!rc) rc = dev_alloc(&ws->d_c_pid, ws->hit_cap);
-        if (!rc) rc = dev_alloc(&ws->d_c_km, ws->hit_cap);
-        if (!rc) rc = dev_alloc(&ws->d_c_fp, ws->hit_cap);
-        if (!rc && !ws->firstpos && hipMemset(ws->d_c_fp, 0, ws->hit_cap * sizeof(uint32_t)) != hipSuccess) rc = kaamer_fail(KAAMER_E_HIP, "memset");
+    if (!rc && ws->compact) {   // CSR in query order
+        rc = reserve_group(nullptr, GROW_EXACT, { want(ws->d_csr_off, qc + 1), want(ws->d_c_pid, (size_t)ws->hit_cap), want(ws->d_c_km, (size_t)ws->hit_cap),
+                                                  want(ws->d_c_fp, (size_t)ws->hit_cap) });
+        if (!ws->firstpos) zero(ws->d_c_fp, ws->hit_cap * sizeof(uint32_t));
     }
-    if (rc) { kaamer_workspace_free(ws); return rc; }
-    ws->ev = new (std::nothrow) std::vector<hipEvent_t>();
-    if (!ws->ev) { kaamer_workspace_free(ws); return kaamer_fail(KAAMER_E_NOMEM, "event ring"); }
+    if (rc) { delete ws; return rc; }
     *out = ws;
     return KAAMER_OK;
 }
@@ -1566,8 +1476,8 @@ int kaamer_workspace_set_count_stream(kaamer_workspace *ws, void *stream)
     ws->split_pending = false;
     ws->count_stream = (hipStream_t)stream;
     if (stream && !ws->ev_probe) {
-        HIPCHK(hipEventCreateWithFlags(&ws->ev_probe, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ws->ev_count, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ws->ev_probe.e, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ws->ev_count.e, hipEventDisableTiming));
     }
     return KAAMER_OK;
 }
@@ -1814,12 +1724,12 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     hipEvent_t *ev = nullptr;
     if (timed) {
         if (ws->n_timed >= MAX_TIMED_CALLS) ws->n_timed = 0;
-        while (ws->ev->size() < (size_t)(ws->n_timed + 1) * EV_PER_CALL) {
+        while (ws->ev.size() < (size_t)(ws->n_timed + 1) * EV_PER_CALL) {
             hipEvent_t e;
             HIPCHK(hipEventCreate(&e));
-            ws->ev->push_back(e);
+            ws->ev.push_back(e);
         }
-        ev = ws->ev->data() + (size_t)ws->n_timed * EV_PER_CALL;
+        ev = ws->ev.data() + (size_t)ws->n_timed * EV_PER_CALL;
         HIPCHK(hipEventRecord(ev[0], s));
     }
     {
@@ -1871,7 +1781,7 @@ int kaamer_search_device(kaamer_index *ix, kaamer_workspace *ws, const uint8_t *
     out->d_starts_alt = nucl ? ws->d_starts_alt : nullptr;
     out->d_counters = ws->d_counters;
     out->d_pos_off = ws->want_positions ? ws->d_pos_off : nullptr;
-    out->d_pos_bits = ws->want_positions ? (const uint64_t *)ws->d_pos_bits : nullptr;
+    out->d_pos_bits = ws->want_positions ? (const uint64_t *)ws->d_pos_bits.get() : nullptr;
     out->d_pos_base = ws->want_positions ? ws->d_pos_base : nullptr;
     return KAAMER_OK;
 }
@@ -1928,7 +1838,7 @@ static int merge_finish(kaamer_workspace *ws, hipStream_t s, bool with_positions
     out->d_counters = ws->d_counters;
     if (with_positions) {
         out->d_pos_off = ws->d_pos_off;
-        out->d_pos_bits = (const uint64_t *)ws->d_pos_bits;
+        out->d_pos_bits = (const uint64_t *)ws->d_pos_bits.get();
         out->d_pos_base = ws->d_pos_base;
     }
     return KAAMER_OK;
@@ -1958,22 +1868,16 @@ int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void 
         return kaamer_fail(KAAMER_E_ARG, "topn_device: merged results need d_size_in_kmer or orf_source (the owner's queries)");
     if (best_start && !ws->firstpos) return kaamer_fail(KAAMER_E_ARG, "topn_device: SetBestStartCodon needs first positions (first_pos != 2)");
     HIPCHK(hipSetDevice(ws->device));
-    if (ws->topn_k < opts->max_results) {
-        uint32_t **bufs[] = { &ws->d_top_pid, &ws->d_top_km, &ws->d_top_fp };
-        for (uint32_t **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-        int rc = 0;
-        const size_t n = (size_t)ws->q_cap * opts->max_results;
-        rc = dev_alloc(&ws->d_top_pid, n);
-        if (!rc) rc = dev_alloc(&ws->d_top_km, n);
-        if (!rc) rc = dev_alloc(&ws->d_top_fp, n);
-        if (!rc && !ws->d_top_cnt) {
-            rc = dev_alloc(&ws->d_top_cnt, ws->q_cap);
-            if (!rc) rc = dev_alloc(&ws->d_top_trim, ws->q_cap);
-            if (!rc) rc = dev_alloc(&ws->d_top_start, ws->q_cap);
-            if (!rc) rc = dev_alloc(&ws->d_top_size, ws->q_cap);
-        }
+    // a search whose counting stage ran on the count stream: the post-steps follow it there (the caller's stream is the probe
+    // stream of the next batches), and consumers keep waiting for ev_count
+    const bool on_count_stream = ws->split_pending && ws->count_stream;
+    hipStream_t ts = on_count_stream ? ws->count_stream : (hipStream_t)stream;
+    {   // the result arrays: q_cap rows of the largest max_results so far, and the per-query ones
+        const size_t n = (size_t)ws->q_cap * opts->max_results, qc = ws->q_cap;
+        int rc = reserve_group(ts, GROW_EXACT, { want(ws->d_top_pid, n), want(ws->d_top_km, n), want(ws->d_top_fp, n) });
+        if (!rc) rc = reserve_group(ts, GROW_EXACT, { want(ws->d_top_cnt, qc), want(ws->d_top_trim, qc), want(ws->d_top_start, qc), want(ws->d_top_size, qc) });
         if (rc) { ws->topn_k = 0; return rc; }
-        ws->topn_k = opts->max_results;
+        if (ws->topn_k < opts->max_results) ws->topn_k = opts->max_results;
     }
     TopnParams p;
     memset(&p, 0, sizeof p);
@@ -1999,10 +1903,6 @@ int kaamer_topn_device(kaamer_workspace *ws, const kaamer_topn_opts *opts, void 
     p.top_cnt = ws->d_top_cnt; p.top_pid = ws->d_top_pid; p.top_km = ws->d_top_km; p.top_fp = ws->d_top_fp;
     p.trim = ws->d_top_trim; p.start_pos = ws->d_top_start; p.size_out = ws->d_top_size;
     // lanes per query: a protein query has ~190 hits (a wave), an ORF ~15 (16 lanes: four ORFs per wave)
-    // a search whose counting stage ran on the count stream: the post-steps follow it there (the caller's stream is the probe
-    // stream of the next batches), and consumers keep waiting for ev_count
-    const bool on_count_stream = ws->split_pending && ws->count_stream;
-    hipStream_t ts = on_count_stream ? ws->count_stream : (hipStream_t)stream;
     if (src->nucleotide) hipLaunchKernelGGL(topn_kernel<16>, dim3(ws->n_cu * 8), dim3(256), 0, ts, p);
     else hipLaunchKernelGGL(topn_kernel<64>, dim3(ws->n_cu * 8), dim3(256), 0, ts, p);
     if (on_count_stream) HIPCHK(hipEventRecord(ws->ev_count, ts));
@@ -2042,16 +1942,8 @@ static uint64_t tp_default_words(const kaamer_workspace *ws, uint32_t K, uint32_
 
 static int tp_prepare(kaamer_workspace *ws)
 {
-    if (ws->d_tp_words) return KAAMER_OK;
-    int rc = dev_alloc(&ws->d_tp_words, ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_tp_len, ws->q_cap);
-    if (!rc) rc = dev_alloc(&ws->d_tp_base, (size_t)ws->q_cap + 1);
-    if (rc) {
-        void *bufs[] = { ws->d_tp_words, ws->d_tp_len, ws->d_tp_base };
-        for (void *b : bufs) if (b) (void)hipFree(b);
-        ws->d_tp_words = nullptr; ws->d_tp_len = nullptr; ws->d_tp_base = nullptr;
-    }
-    return rc;
+    const size_t qc = ws->q_cap;   // (fixed per workspace: nothing to wait for, the group is made once)
+    return reserve_group(nullptr, GROW_EXACT, { want(ws->d_tp_words, qc), want(ws->d_tp_len, qc), want(ws->d_tp_base, qc + 1) });
 }
 
 static TopPosParams tp_params(const kaamer_index *ix, const kaamer_workspace *ws, const kaamer_topn_result *top)
@@ -2099,16 +1991,8 @@ int kaamer_topn_positions_device(kaamer_index *ix, kaamer_workspace *ws, const k
     hipStream_t s = on_count_stream ? ws->count_stream : (hipStream_t)stream;
     rc = tp_prepare(ws);
     if (rc) return rc;
-    if (ws->tp_alloc < cap) {
-        if (ws->d_tp_bits) {   // an earlier batch may still be writing it
-            HIPCHK(hipStreamSynchronize(s));
-            (void)hipFree(ws->d_tp_bits);
-            ws->d_tp_bits = nullptr; ws->tp_alloc = 0;
-        }
-        rc = dev_alloc(&ws->d_tp_bits, (size_t)cap);
-        if (rc) return rc;
-        ws->tp_alloc = cap;
-    }
+    rc = reserve(ws->d_tp_bits, (size_t)cap, GROW_EXACT, s);   // (an earlier batch may still be writing it)
+    if (rc) return rc;
     TopPosParams p = tp_params(ix, ws, top);
     p.bits = ws->d_tp_bits; p.cap = cap;
     tp_enqueue_layout(ws, p, s);
@@ -2117,7 +2001,7 @@ int kaamer_topn_positions_device(kaamer_index *ix, kaamer_workspace *ws, const k
     HIPCHK(hipGetLastError());
     out->d_pos_base = ws->d_tp_base;
     out->d_pos_bits_len = ws->d_tp_len;
-    out->d_pos_bits = (const uint64_t *)ws->d_tp_bits;
+    out->d_pos_bits = (const uint64_t *)ws->d_tp_bits.get();
     out->pos_words_capacity = cap;
     return KAAMER_OK;
 }
@@ -2179,7 +2063,7 @@ int kaamer_workspace_kernel_ms_sum(kaamer_workspace *ws, double *probe_ms, doubl
     HIPCHK(hipSetDevice(ws->device));
     double a = 0, b = 0, c = 0;
     for (uint32_t i = 0; i < ws->n_timed; i++) {
-        hipEvent_t *ev = ws->ev->data() + (size_t)i * EV_PER_CALL;
+        hipEvent_t *ev = ws->ev.data() + (size_t)i * EV_PER_CALL;
         float x = 0, y = 0, z = 0;
         HIPCHK(hipEventElapsedTime(&x, ev[1], ev[2]));
         HIPCHK(hipEventElapsedTime(&y, ev[2], ev[3]));
@@ -2294,23 +2178,8 @@ static int host_slot_acquire(kaamer_index *ix, HostSlot &h, const kaamer_workspa
         if (rc) { h.ws = nullptr; return rc; }
         h.opts = g;
     }
-    if (h.seq_cap < seq_bytes + 16) {
-        if (h.d_seqs) (void)hipFree(h.d_seqs);
-        h.d_seqs = nullptr; h.seq_cap = 0;
-        const size_t cap = (size_t)seq_bytes + (size_t)seq_bytes / 4 + 4096;
-        const int rc = dev_alloc(&h.d_seqs, cap);
-        if (rc) return rc;
-        h.seq_cap = cap;
-    }
-    if (h.off_cap < (size_t)n_seqs + 1) {
-        if (h.d_off) (void)hipFree(h.d_off);
-        h.d_off = nullptr; h.off_cap = 0;
-        const size_t cap = (size_t)n_seqs + (size_t)n_seqs / 4 + 16;
-        const int rc = dev_alloc(&h.d_off, cap);
-        if (rc) return rc;
-        h.off_cap = cap;
-    }
-    return KAAMER_OK;
+    const int rc = reserve(h.d_seqs, (size_t)seq_bytes, GROW_SLOT_SEQS, h.stream);
+    return rc ? rc : reserve(h.d_off, (size_t)n_seqs, GROW_SLOT_OFF, h.stream);
 }
 
 // host buffers -> device, search enqueued on the slot's stream; nothing is waited for
