@@ -44,7 +44,8 @@ typedef enum {
     KAAMER_E_HIP = -4,       /* a HIP runtime call failed (no device, ...)     */
     KAAMER_E_CAPACITY = -5,  /* a workspace bound was exceeded; enlarge, retry */
     KAAMER_E_FORMAT = -6,    /* index image/version mismatch                   */
-    KAAMER_E_BUSY = -7       /* every host slot holds a batch: wait / pop first */
+    KAAMER_E_BUSY = -7,      /* every host slot holds a batch: wait / pop first */
+    KAAMER_E_RANGE = -8      /* a value outside what a device stage tabulates: take the host route (kaamer_tsv_rows_finish) */
 } kaamer_status;
 
 /* search.go:41-44 */
@@ -1070,6 +1071,11 @@ int kaamer_submit_batch_top_aln_flat(kaamer_index *ix, const uint8_t *seqs, cons
  * (three rows of `length` bytes), which is NULL for a result without text.  Both NULL for a result of a call without
  * alignments.  They live as long as the result does. */
 int kaamer_batch_top_alignments(const kaamer_batch_top *out, const kaamer_alignment **items, const char **text);
+/* Test and measurement entry: the floats and coordinates of such a result for pair records the caller holds (read back behind
+ * kaamer_topn_align_device, or built by hand): out[i] is what the items above would carry for pairs[i] -- status != 0
+ * keeps the empty AlignmentResult, options without a row in AllMatrixScores give status 1 -- aln_off 0.  Host only. */
+int kaamer_align_finish_pairs(const kaamer_align_pair *pairs, uint64_t n, uint64_t number_of_aa, const char *sub_matrix,
+                              int32_t gap_open, int32_t gap_extend, kaamer_alignment *out);
 
 /* The same on the one-process sharded handle (kaamer_index_open_sharded): replaces search.go:454-470 + :483-494 for a
  * database larger than one device.  The reported hits of a query are known at its owner (device q mod W) only; the
@@ -1423,11 +1429,11 @@ int kaamer_search_fasta_file(kaamer_replicas *r, const char *path, int32_t seq_t
 /* FetchHitsInformation stops a query's loop at the first id without an entry  */
 /* (search.go:461-463): from that hit on, in reporting order, every hit of the */
 /* query prints an empty SubjectId, 0 as Length and empty feature values.      */
-/* Out of scope: the -aln TSV form (its "%e" of a float64 EValue needs         */
-/* arbitrary-precision formatting), JSON, the file drivers and streams, the    */
-/* sharded handle and the packed-batch calls on the device -- those have the   */
-/* host formatter, and the device stage takes names as bytes + spans, so a     */
-/* packed form is host plumbing only.                                          */
+/* The -aln form has its own section below (host formatter and device stage).  */
+/* Out of scope: JSON, the file drivers and streams, the sharded handle and    */
+/* the packed-batch calls on the device -- those have the host formatter, and  */
+/* the device stage takes names as bytes + spans, so a packed form is host     */
+/* plumbing only.                                                              */
 /* ------------------------------------------------------------------------- */
 /* SetResponseFormatAndHeader, search.go:645-660, Align = false.  proteins (its feature names) may be NULL without
  * annotations.  The conventions of kaamer_format_positions: at most cap bytes, NUL-terminated when cap > 0, the return is
@@ -1450,6 +1456,59 @@ int64_t kaamer_format_tsv_arrays(const kaamer_batch_top *top, const int32_t *pos
                                  const uint64_t *pos_bits, const char *name_bytes, uint64_t name_bytes_len,
                                  const kaamer_text_span *name_spans, uint32_t n_names, const kaamer_proteins *proteins,
                                  int32_t extract_positions, int32_t annotations, char *buf, uint64_t cap, uint64_t *line_off);
+
+/* ------------------------------------------------------------------------- */
+/* The -aln TSV rows (QueryResultHandler, search.go:556-604; header line       */
+/* search.go:649 + :651-660): one line per reported hit of a result that        */
+/* carries alignments, in the result's own order (BitScore descending, ties in  */
+/* sortMapByValue order).                                                       */
+/*    1 QueryId, 2 SubjectId   as above.  FetchHitsInformation stops BEFORE the  */
+/*                     sort, so the hits without an entry are those with status  */
+/*                     4 (and, in a result that was not aligned -- status 1,     */
+/*                     sortMapByValue order -- those behind a missing id)        */
+/*    3 %Identity      "%.2f" of the float32 Alignment.Identity: its exact      */
+/*                     value, half-even at the second decimal; NaN when the      */
+/*                     alignment has no columns                                  */
+/*  4 5 6 AlnLength Mismatches GapOpen   Alignment.Length / .Mismatches /        */
+/*                     .GapOpenings                                              */
+/*  7 8 QStart QEnd    base sequence type PROTEIN: Alignment.QueryStart /        */
+/*                     QueryEnd; else Location.StartPosition / EndPosition       */
+/* 9 10 SStart SEnd    Alignment.SubjectStart / SubjectEnd                       */
+/*   11 Evalue         "%e" of the float64 Alignment.EValue: d.dddddde+XX, its   */
+/*                     exact value rounded half-even at the sixth decimal, the    */
+/*                     exponent with at least two digits                          */
+/*   12 Bitscore       "%.2f" of the float64 Alignment.BitScore                  */
+/*   13 QueryPositions ExtractPositions only: kaamer_format_positions(bitmap,    */
+/*                     bits as searched, 1)                                      */
+/*  14.. the annotation columns, Annotations only                                */
+/* The floats print as strconv prints them: every finite value exactly,          */
+/* subnormals included; "NaN", "+Inf", "-Inf".  A hit with the empty             */
+/* AlignmentResult (kaamer_alignment.status != 0) prints its zeros:              */
+/* 0.00 0 0 0 <QStart> <QEnd> 0 0 0.000000e+00 0.00.                             */
+/* Out of scope: JSON and AlnString.  The device stage (below) serves device-    */
+/* resident pair records and the text calls (kaamer_*_top_aln_tsv_flat); the     */
+/* sharded handle, streams, file drivers and the packed-batch calls format these */
+/* rows with the host formatter.                                                 */
+/* ------------------------------------------------------------------------- */
+uint64_t kaamer_format_tsv_aln_header(int32_t extract_positions, int32_t annotations, const kaamer_proteins *proteins, char *buf,
+                                      uint64_t cap);
+/* The rows of any kaamer_batch_top that carries alignments (kaamer_batch_top_alignments gives them), on the caller's
+ * thread.  Arguments and conventions as kaamer_format_tsv; seq_type: the request's (its base decides fields 7 and 8).
+ * KAAMER_E_ARG on a result without alignments, and for extract_positions on a result without bitmaps. */
+int64_t kaamer_format_tsv_aln(const kaamer_batch_top *top, const char *name_bytes, uint64_t name_bytes_len,
+                              const kaamer_text_span *name_spans, uint32_t n_names, const kaamer_proteins *proteins,
+                              int32_t seq_type, int32_t extract_positions, int32_t annotations, char *buf, uint64_t cap,
+                              uint64_t *line_off);
+/* The same on a result whose arrays the caller holds itself: alns[e] belongs to entry e of the CSR arrays (NULL:
+ * KAAMER_E_ARG), the three arrays of kaamer_batch_top_positions all NULL without extract_positions.  top_kmatch is not
+ * read.  Host only. */
+int64_t kaamer_format_tsv_aln_arrays(const kaamer_batch_top *top, const kaamer_alignment *alns, const int32_t *pos_bits_len,
+                                     const uint64_t *pos_off, const uint64_t *pos_bits, const char *name_bytes,
+                                     uint64_t name_bytes_len, const kaamer_text_span *name_spans, uint32_t n_names,
+                                     const kaamer_proteins *proteins, int32_t seq_type, int32_t extract_positions,
+                                     int32_t annotations, char *buf, uint64_t cap, uint64_t *line_off);
+/* Test entry: one float64 as fields 11 (mode 0: "%e") and 12 (mode 1: "%.2f") print it; buf / cap / the return as above. */
+uint64_t kaamer_format_double(double value, int32_t mode, char *buf, uint64_t cap);
 
 /* What the rows need of the protein table, resident next to the index: every entry's EntryId bytes, its Length and its
  * annotation columns pre-joined on the host ('\t' + value per KStats.Features name, in order: the device only copies
@@ -1496,10 +1555,46 @@ void kaamer_tsv_stage_free(kaamer_tsv_stage *st);
  * KAAMER_E_ARG naming kaamer_index_attach_subject_text when nothing is attached. */
 int kaamer_tsv_rows_device(kaamer_tsv_stage *st, const kaamer_tsv_rows_in *in, char *d_out, uint64_t out_cap, void *stream,
                            kaamer_tsv_rows_result *out);
-/* waits for `stream`; counts[0] rows, counts[1] bytes (also filled with what was needed on KAAMER_E_CAPACITY) */
+/* waits for `stream`; counts[0] rows, counts[1] bytes (also filled with what was needed on KAAMER_E_CAPACITY).  Serves
+ * both forms; after kaamer_tsv_aln_rows_device also KAAMER_E_RANGE (see there). */
 int kaamer_tsv_rows_finish(kaamer_tsv_stage *st, void *stream, uint64_t counts[2]);
 /* out[0] queries per tile, out[1] bytes per LDS window, out[2] bytes a lane stores at once, out[3] threads per workgroup */
 void kaamer_tsv_geometry(uint32_t out[4]);
+
+/* The -aln rows on the device (tsv_aln_rows.hip.inc), enqueued on `stream` behind kaamer_topn_align_device (and behind
+ * kaamer_topn_positions_device with extract_positions): stage, in, d_out, out_cap and the result as
+ * kaamer_tsv_rows_device takes and gives them (in->top.d_top_kmatch and d_size_in_kmer are not read); alns: the pair
+ * records of the same batch; opts: the request's matrix options -- those the alignment stage ran with -- and its sequence
+ * type, whose base decides fields 7 and 8.  Needs both attaches: kaamer_index_attach_subject_text, and
+ * kaamer_index_attach_proteins for NumberOfAA (KAAMER_E_ARG names the missing one).  max_results up to 65535.
+ *   order    a lane per query sorts its hits by BitScore, descending and stable, once; the three passes read that order.
+ *            The missing-entry rule is the host formatter's: the hits it covers carry status 4.
+ *   floats   Identity, BitScore and EValue are kaamer_align_finish's, bit for bit.  BitScore and 2^BitScore come from a
+ *            table per raw score that the host fills with that function's own arithmetic for the call's options (kept by
+ *            the stage while the options stay); the remaining operations are IEEE-rounded on the device.  The table
+ *            holds the raw scores -65536 .. 65535 (the reference's tally with the request's gap penalties goes below 0 on
+ *            alignments with long gaps).  A pair with a raw score outside it is never printed: the stage counts
+ *            such pairs, kaamer_tsv_rows_finish returns KAAMER_E_RANGE and nothing of d_out is to be read -- that batch's
+ *            rows are the host formatter's (kaamer_format_tsv_aln).  The stage keeps ONE table: callers that alternate
+ *            option sets on one stage refill it (131072 evaluations and a wait for the stream) at every change.
+ *   numbers  "%e" and "%.2f" print every finite double exactly (a multi-word routine whose limbs live in LDS).
+ * The capacity rule is kaamer_tsv_rows_device's. */
+typedef struct {
+    char sub_matrix[16];          /* SearchOptions.SubMatrix / GapOpen / GapExtend                                       */
+    int32_t gap_open, gap_extend;
+    int32_t seq_type;             /* the request's                                                                        */
+    int32_t reserved;
+} kaamer_tsv_aln_opts;
+int kaamer_tsv_aln_rows_device(kaamer_tsv_stage *st, const kaamer_tsv_rows_in *in, const kaamer_topn_alignments *alns,
+                               const kaamer_tsv_aln_opts *opts, char *d_out, uint64_t out_cap, void *stream,
+                               kaamer_tsv_rows_result *out);
+/* of the stage's last -aln call, after kaamer_tsv_rows_finish: out[0] pairs with a raw score outside the table, out[1]
+ * raw scores the table holds, out[2] tables the stage has filled so far */
+int kaamer_tsv_aln_info(const kaamer_tsv_stage *st, uint64_t out[4]);
+/* Test entry: n doubles on the current device, each printed as field 11 (mode 0: "%e") or field 12 (mode 1: "%.2f")
+ * prints it, by the device functions the stage uses, into a 32-byte slot of d_out, NUL-padded (a longer text -- "%.2f"
+ * of 1e29 and beyond -- is cut at 31 bytes).  Waits for the device. */
+int kaamer_tsv_format_doubles_device(const double *d_values, uint64_t n, int32_t mode, char *d_out);
 
 /* The text calls with the rows in the result: what a host shim calls instead of QueryResultHandler + QueryResultWriter's
  * per-field `output += ...` (search.go:505-554) -- it writes the header (kaamer_format_tsv_header) and then the bytes of
@@ -1529,6 +1624,47 @@ int kaamer_submit_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint
 int kaamer_search_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
                                     kaamer_batch_top **out);
+/* The same three calls with the alignment of the reported hits in between (`-aln -fmt tsv` in one call, search.go:483-494
+ * + :556-604): arguments as their _tsv_ twins plus SearchOptions.SubMatrix / GapOpen / GapExtend.  The alignment stage
+ * (kaamer_search_batch_top_aln_flat's, want_text = 0) follows the packing of the block on the slot's stream and the -aln
+ * rows (kaamer_tsv_aln_rows_device's kernels) follow it, on the pair records in the block.  The structured result is that
+ * of the _aln_flat call with want_text = 0 -- numbers only: the TSV form has no AlnString and a text call keeps no host
+ * copy of the queries -- read with kaamer_batch_top_alignments (and kaamer_batch_top_positions with extract_positions);
+ * kaamer_batch_top_tsv gives the rows, in the result's own order.  Both stages keep their repeat-on-too-small-bounds
+ * rule.  Options without a row in AllMatrixScores (or a matrix other than BLOSUM62): every item has status 1 and every
+ * row prints the zeros, in sortMapByValue order.  A batch with a raw score outside the stage's table is printed by the
+ * host formatter inside kaamer_wait_batch_top, from the finished result and the table of kaamer_index_attach_proteins
+ * (attach the same table twice): the same bytes, counted in kaamer_index_tsv_aln_info.  KAAMER_E_ARG naming
+ * kaamer_index_attach_proteins or kaamer_index_attach_subject_text when that attach is missing.  The alignment stage
+ * sizes its slabs by the longest record, which a text call learns from the spans: one more wait at submit. */
+int kaamer_submit_text_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                        double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                        int32_t annotations, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                        kaamer_ticket **ticket);
+int kaamer_search_text_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                        double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                        int32_t annotations, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                        kaamer_batch_top **out);
+int kaamer_submit_fasta_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                         double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                         int32_t annotations, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                         kaamer_ticket **ticket);
+int kaamer_search_fasta_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                         double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                         int32_t annotations, const char *sub_matrix, int32_t gap_open, int32_t gap_extend,
+                                         kaamer_batch_top **out);
+int kaamer_submit_bgzf_top_aln_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                        int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                        const char *sub_matrix, int32_t gap_open, int32_t gap_extend, kaamer_ticket **ticket);
+int kaamer_search_bgzf_top_aln_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                        int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                        const char *sub_matrix, int32_t gap_open, int32_t gap_extend, kaamer_batch_top **out);
+/* out[0] batches of those calls whose rows the host printed (a raw score outside the table), out[1] raw scores the table
+ * holds.  Test entry: kaamer_index_set_tsv_aln_raw_count makes the table of every stage of the index hold only the first n
+ * raw scores from -65536 on (0: all), so that the host path can be reached with ordinary scores; KAAMER_E_BUSY with calls
+ * in flight. */
+int kaamer_index_tsv_aln_info(kaamer_index *ix, uint64_t out[2]);
+int kaamer_index_set_tsv_aln_raw_count(kaamer_index *ix, uint32_t n);
 /* The rows of a result: views that live as long as it does; line_off has top_off[n_reported] + 1 entries.  NULL / 0 for a
  * result of any other call (format it on the host: kaamer_format_tsv). */
 int kaamer_batch_top_tsv(const kaamer_batch_top *out, const char **text, uint64_t *len, const uint64_t **line_off);

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # KAAMER_LIB points at an alternative build of the same library (tuning experiments only)
 LIB_PATH = os.environ.get("KAAMER_LIB") or os.path.join(_HERE, "libkaamer_hip.so")
 
-OK, E_ARG, E_IO, E_NOMEM, E_HIP, E_CAPACITY, E_FORMAT, E_BUSY = 0, -1, -2, -3, -4, -5, -6, -7
+OK, E_ARG, E_IO, E_NOMEM, E_HIP, E_CAPACITY, E_FORMAT, E_BUSY, E_RANGE = 0, -1, -2, -3, -4, -5, -6, -7, -8
 NUCLEOTIDE, PROTEIN, READS = 0, 1, 2
 GENETIC_CODES = (1, 2, 3, 4, 5, 6, 9, 10, 11, 12, 13, 14, 15)   # the keys of search.GCodes (gcode.go:21-34)
 
@@ -187,6 +187,11 @@ class TsvRowsIn(C.Structure):   # kaamer_tsv_rows_in
 
 class TsvRowsResult(C.Structure):   # kaamer_tsv_rows_result
     _fields_ = [("d_line_off", C.c_void_p), ("d_counts", C.c_void_p), ("line_off_capacity", C.c_uint64)]
+
+
+class TsvAlnOpts(C.Structure):   # kaamer_tsv_aln_opts
+    _fields_ = [("sub_matrix", C.c_char * 16), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("seq_type", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 # every symbol include/kaamer_hip.h declares: name -> (restype, argtypes)
@@ -371,6 +376,7 @@ SYMBOLS = {
                                                    C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
                                                    C.POINTER(C.c_void_p)]),
     "kaamer_batch_top_alignments": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Alignment)), C.POINTER(C.POINTER(C.c_char))]),
+    "kaamer_align_finish_pairs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
     # ... and on the sharded handle
     "kaamer_sharded_index_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kaamer_sharded_index_set_align_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
@@ -465,6 +471,19 @@ SYMBOLS = {
     # (top, pos_bits_len, pos_off, pos_bits, ...the same)
     "kaamer_format_tsv_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    # the -aln rows: (extract_positions, annotations, proteins, buf, cap)
+    "kaamer_format_tsv_aln_header": (C.c_uint64, [C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_uint64]),
+    # (top, name_bytes, name_bytes_len, name_spans, n_names, proteins, seq_type, extract_positions, annotations, buf, cap, line_off)
+    "kaamer_format_tsv_aln": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_uint64, C.c_void_p]),
+    # (top, alns, pos_bits_len, pos_off, pos_bits, ...the same)
+    "kaamer_format_tsv_aln_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                 C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_format_double": (C.c_uint64, [C.c_double, C.c_int32, C.c_char_p, C.c_uint64]),
+    "kaamer_tsv_aln_rows_device": (C.c_int, [C.c_void_p, C.POINTER(TsvRowsIn), C.POINTER(TopnAlignments), C.POINTER(TsvAlnOpts), C.c_void_p,
+                                             C.c_uint64, C.c_void_p, C.POINTER(TsvRowsResult)]),
+    "kaamer_tsv_aln_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_tsv_format_doubles_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]),
     "kaamer_index_attach_subject_text": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kaamer_index_subject_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_tsv_stage_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
@@ -487,6 +506,21 @@ SYMBOLS = {
                                                   C.c_int32, C.POINTER(C.c_void_p)]),
     "kaamer_search_bgzf_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
                                                   C.c_int32, C.c_void_p]),
+    # the _tsv_ calls with the alignment in between: ... extract_positions, annotations, sub_matrix, gap_open, gap_extend, out
+    "kaamer_submit_text_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                      C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_text_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                      C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "kaamer_submit_fasta_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                       C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_fasta_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                       C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "kaamer_submit_bgzf_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                                      C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_bgzf_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                                      C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "kaamer_index_tsv_aln_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_index_set_tsv_aln_raw_count": (C.c_int, [C.c_void_p, C.c_uint32]),
     "kaamer_batch_top_tsv": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]),
     "kaamer_index_set_tsv_bounds": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
 }

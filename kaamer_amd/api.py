@@ -561,14 +561,18 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
-    def _text_call(self, kind, data, extra, top, tsv, wait):
-        """kaamer_{search,submit}_{kind}_top[_tsv]_flat -- kind: text, fasta or bgzf; extra: the kind's arguments between the
-        data and the sequence type, and the sequence type; top: (min_k_ratio, min_k_match, max_results); wait: search
-        (-> TopResult), else submit (-> TopTicket)"""
+    def _text_call(self, kind, data, extra, top, tsv, wait, align=None):
+        """kaamer_{search,submit}_{kind}_top[_tsv|_aln_tsv]_flat -- kind: text, fasta or bgzf; extra: the kind's arguments
+        between the data and the sequence type, and the sequence type; top: (min_k_ratio, min_k_match, max_results); wait:
+        search (-> TopResult), else submit (-> TopTicket)"""
         data = data.encode("latin-1") if isinstance(data, str) else bytes(data)
-        fn = getattr(abi.lib(), "kaamer_%s_%s_top%s_flat" % ("search" if wait else "submit", kind, "_tsv" if tsv is not None else ""))
+        if align is not None and tsv is None:
+            raise ValueError("align=... on a text call comes with tsv=...: the call returns the -aln rows")
+        form = "" if tsv is None else "_tsv" if align is None else "_aln_tsv"
+        fn = getattr(abi.lib(), "kaamer_%s_%s_top%s_flat" % ("search" if wait else "submit", kind, form))
         out = C.POINTER(abi.BatchTop)() if wait else C.c_void_p()
-        abi.check(fn(self._h, data, len(data), *extra, *top, *(_tsv_args(tsv) if tsv is not None else ()), C.byref(out)))
+        more = (_tsv_args(tsv) if tsv is not None else ()) + (_align_args(align)[:3] if align is not None else ())
+        abi.check(fn(self._h, data, len(data), *extra, *top, *more, C.byref(out)))
         if not wait:
             return TopTicket(out)
         try:
@@ -576,43 +580,57 @@ class Index:
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None):
+    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None):
         """kaamer_search_text_top_flat: FASTQ text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFastq) and searched as search_top searches the packed batch.  TopResult.text_spans: name and sequence of
         every record as offsets into `text`; rep_query / meta["src_seq"] index the records.
         tsv=dict(positions=..., annotations=...): kaamer_search_text_top_tsv_flat -- the TSV rows of the reported hits are
-        written on the device too (needs attach_subject_text): TopResult.tsv, .tsv_line_off."""
-        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, True)
+        written on the device too (needs attach_subject_text): TopResult.tsv, .tsv_line_off.
+        align=dict(sub_matrix=..., gap_open=..., gap_extend=...) with tsv: kaamer_search_text_top_aln_tsv_flat -- the reported
+        hits are aligned in between (needs attach_proteins too) and the rows are the -aln form; TopResult.alignments carries
+        the numbers (no text), the hits are in BitScore order."""
+        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, True, align)
 
-    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
+    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
         """kaamer_search_bgzf_top_flat: whole BGZF blocks of FASTQ (bytes) in, the reported hits out -- the compressed bytes
         are uploaded, inflated, parsed and searched on the device.  TopResult.text: the inflated text; text_spans index it.
         Bytes that are not whole BGZF blocks: KaamerError E_ARG; a block that does not inflate: E_FORMAT.
-        tsv: as search_text_top's (kaamer_search_bgzf_top_tsv_flat)."""
-        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, True)
+        tsv, align: as search_text_top's (kaamer_search_bgzf_top_tsv_flat / _aln_tsv_flat)."""
+        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, True, align)
 
-    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
-        """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans); tsv: as
-        search_text_top's (kaamer_submit_bgzf_top_tsv_flat)"""
-        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, False)
+    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
+        """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans); tsv, align:
+        as search_text_top's"""
+        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, False, align)
 
-    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None):
-        """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv: as
-        search_text_top's (kaamer_submit_text_top_tsv_flat)"""
-        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, False)
+    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None):
+        """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv, align: as
+        search_text_top's"""
+        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, False, align)
 
-    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
+    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
         """kaamer_search_fasta_top_flat: FASTA text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFasta) and searched as search_top searches the packed batch.  seq_type: PROTEIN, NUCLEOTIDE or READS
         (with a genetic code).  upper_last: more input follows this text, its last record is upper-cased too.
         TopResult.text_spans: name and sequence range of every record as offsets into `text`.
-        tsv: as search_text_top's (kaamer_search_fasta_top_tsv_flat)."""
-        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, True)
+        tsv, align: as search_text_top's (kaamer_search_fasta_top_tsv_flat / _aln_tsv_flat)."""
+        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, True, align)
 
-    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None):
-        """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv: as
-        search_text_top's (kaamer_submit_fasta_top_tsv_flat)"""
-        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, False)
+    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
+        """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv, align: as
+        search_text_top's"""
+        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, False, align)
+
+    def tsv_aln_info(self):
+        """kaamer_index_tsv_aln_info -> dict(host_batches: batches of the align + tsv text calls whose rows the host printed,
+        raw_count: raw scores the stages' table holds)"""
+        c = (C.c_uint64 * 2)()
+        abi.check(abi.lib().kaamer_index_tsv_aln_info(self._h, c))
+        return dict(host_batches=int(c[0]), raw_count=int(c[1]))
+
+    def set_tsv_aln_raw_count(self, n):
+        """kaamer_index_set_tsv_aln_raw_count (a test entry): the stages' table holds the first n raw scores only; 0: all"""
+        abi.check(abi.lib().kaamer_index_set_tsv_aln_raw_count(self._h, int(n)))
 
     def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
         """kaamer_stream_open[_pos|_aln]_flat; align: as search_top's (needs attach_proteins)"""
@@ -950,21 +968,26 @@ def _tsv_args(tsv):
     return int(bool(tsv.get("positions"))), int(bool(tsv.get("annotations")))
 
 
-def format_tsv_header(positions=False, annotations=False, proteins=None):
-    """kaamer_format_tsv_header: the header line of the TSV response (search.go:645-660, no alignment) -> bytes"""
+def format_tsv_header(positions=False, annotations=False, proteins=None, align=False):
+    """kaamer_format_tsv_header, or with align kaamer_format_tsv_aln_header: the header line of the TSV response
+    (search.go:645-660) -> bytes"""
+    fn = abi.lib().kaamer_format_tsv_aln_header if align else abi.lib().kaamer_format_tsv_header
     ph = proteins._h if proteins is not None else None
-    need = int(abi.lib().kaamer_format_tsv_header(int(bool(positions)), int(bool(annotations)), ph, None, 0))
+    need = int(fn(int(bool(positions)), int(bool(annotations)), ph, None, 0))
     buf = C.create_string_buffer(need + 1)
-    abi.lib().kaamer_format_tsv_header(int(bool(positions)), int(bool(annotations)), ph, buf, need + 1)
+    fn(int(bool(positions)), int(bool(annotations)), ph, buf, need + 1)
     return buf.raw[:need]
 
 
-def format_tsv(top, names, spans, proteins=None, positions=False, annotations=False, cap=None):
+def format_tsv(top, names, spans, proteins=None, positions=False, annotations=False, cap=None, align=False, seq_type=abi.PROTEIN):
     """kaamer_format_tsv_arrays on a TopResult (or any object with its arrays: n_reported, meta, top_off, top_pid, top_kmatch
     and, with positions, pos_bits_len / pos_off / pos_bits): the TSV rows of the reported hits, formatted on the host
     (search.go:505-554) -> (bytes, line_off u64[entries + 1]).  names: the bytes the records' names lie in (the text of a
     text call); spans: SPAN_DTYPE, one per input record (TopResult.text_spans).  cap: format into a buffer of that many
-    bytes instead of one of the needed size -> (bytes written without the NUL, the needed length)."""
+    bytes instead of one of the needed size -> (bytes written without the NUL, the needed length).
+    align: the -aln rows (search.go:556-604), kaamer_format_tsv_aln_arrays -- top.alignments: one per entry, as ALN_DTYPE
+    records or dicts with its fields (TopResult.alignments; None: KaamerError E_ARG); seq_type: the request's, whose base
+    decides QStart / QEnd."""
     names = names.encode("latin-1") if isinstance(names, str) else bytes(names)
     spans = np.ascontiguousarray(spans, SPAN_DTYPE)
     r = int(top.n_reported)
@@ -986,12 +1009,19 @@ def format_tsv(top, names, spans, proteins=None, positions=False, annotations=Fa
     ne = int(off[r]) if r else 0
     line_off = np.zeros(ne + 1, np.uint64)
     ph = proteins._h if proteins is not None else None
+    alns = None
+    if align and getattr(top, "alignments", None) is not None:
+        alns = aln_records(top.alignments, ne)
+    bitmaps = (pl.ctypes.data if pl is not None else None, po.ctypes.data if po is not None else None, pb.ctypes.data if pb is not None else None)
+    name_args = (names, len(names), spans.ctypes.data if len(spans) else None, len(spans), ph)
 
     def call(buf, n):
-        rc = int(abi.lib().kaamer_format_tsv_arrays(
-            C.byref(bt), pl.ctypes.data if pl is not None else None, po.ctypes.data if po is not None else None,
-            pb.ctypes.data if pb is not None else None, names, len(names), spans.ctypes.data if len(spans) else None, len(spans), ph,
-            int(bool(positions)), int(bool(annotations)), buf, n, line_off.ctypes.data))
+        if align:
+            rc = int(abi.lib().kaamer_format_tsv_aln_arrays(C.byref(bt), alns.ctypes.data if alns is not None else None, *bitmaps, *name_args, int(seq_type),
+                                                            int(bool(positions)), int(bool(annotations)), buf, n, line_off.ctypes.data))
+        else:
+            rc = int(abi.lib().kaamer_format_tsv_arrays(C.byref(bt), *bitmaps, *name_args, int(bool(positions)), int(bool(annotations)), buf, n,
+                                                        line_off.ctypes.data))
         if rc < 0:
             abi.check(rc)
         return rc
@@ -1003,6 +1033,58 @@ def format_tsv(top, names, spans, proteins=None, positions=False, annotations=Fa
     buf = C.create_string_buffer(need + 1)
     call(buf, need + 1)
     return buf.raw[:need], line_off
+
+
+# kaamer_alignment as a numpy record
+ALN_DTYPE = np.dtype([("identity", np.float32), ("similarity", np.float32), ("length", np.int32), ("mismatches", np.int32),
+                      ("gap_openings", np.int32), ("raw", np.int32), ("bitscore", np.float64), ("evalue", np.float64),
+                      ("query_start", np.int32), ("query_end", np.int32), ("subject_start", np.int32), ("subject_end", np.int32),
+                      ("aln_off", np.uint64), ("status", np.int32), ("reserved", np.int32)])
+assert ALN_DTYPE.itemsize == C.sizeof(abi.Alignment)
+
+
+def aln_records(alignments, n):
+    """n kaamer_alignment records from ALN_DTYPE records, or from dicts with (some of) its fields"""
+    if isinstance(alignments, np.ndarray) and alignments.dtype == ALN_DTYPE:
+        out = np.ascontiguousarray(alignments)
+    else:
+        out = np.zeros(max(len(alignments), 1), ALN_DTYPE)
+        for i, a in enumerate(alignments):
+            for k in ALN_DTYPE.names:
+                if k in a:
+                    out[i][k] = a[k]
+    assert len(out) >= n, "%d alignments for %d entries" % (len(out), n)
+    return out
+
+
+PAIR_DTYPE = np.dtype([(k, np.int32) for k in ("status", "n_ops", "start_i", "start_j", "end_i", "end_j", "identical", "similar", "mismatches",
+                                                "gap_openings", "raw")] + [("query_len", np.uint32), ("off", np.uint64), ("entry", np.uint32),
+                                                                           ("subject_len", np.uint32)])
+assert PAIR_DTYPE.itemsize == C.sizeof(abi.AlignPair)
+
+
+def align_finish_pairs(pairs, number_of_aa, sub_matrix="blosum62", gap_open=11, gap_extend=1):
+    """kaamer_align_finish_pairs: PAIR_DTYPE records (kaamer_align_pair) -> ALN_DTYPE records, the floats and coordinates a
+    result of the aligning calls carries for them"""
+    pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+    out = np.zeros(max(len(pairs), 1), ALN_DTYPE)
+    abi.check(abi.lib().kaamer_align_finish_pairs(pairs.ctypes.data if len(pairs) else None, len(pairs), int(number_of_aa), sub_matrix.encode(),
+                                                  int(gap_open), int(gap_extend), out.ctypes.data))
+    return out[:len(pairs)]
+
+
+def format_double(value, mode):
+    """kaamer_format_double: a float64 as the -aln rows print EValue (mode 0: "%e") or BitScore (mode 1: "%.2f") -> bytes"""
+    need = int(abi.lib().kaamer_format_double(float(value), int(mode), None, 0))
+    buf = C.create_string_buffer(need + 1)
+    abi.lib().kaamer_format_double(float(value), int(mode), buf, need + 1)
+    return buf.raw[:need]
+
+
+def format_doubles_device(d_values_ptr, n, mode, d_out_ptr):
+    """kaamer_tsv_format_doubles_device: n float64 at a device address, printed by the device functions of the -aln stage
+    into 32-byte slots at d_out_ptr"""
+    abi.check(abi.lib().kaamer_tsv_format_doubles_device(C.c_void_p(d_values_ptr), int(n), int(mode), C.c_void_p(d_out_ptr)))
 
 
 def tsv_geometry():
@@ -1029,8 +1111,28 @@ class TsvStage:
         abi.check(abi.lib().kaamer_tsv_rows_device(self._h, C.byref(rows_in), C.c_void_p(d_out_ptr), int(out_cap), C.c_void_p(stream), C.byref(r)))
         return r
 
+    def aln_rows_device(self, rows_in, alns, d_out_ptr, out_cap, sub_matrix="blosum62", gap_open=11, gap_extend=1, seq_type=abi.PROTEIN,
+                        stream=0):
+        """kaamer_tsv_aln_rows_device (rows_in: abi.TsvRowsIn, alns: abi.TopnAlignments, both of raw device addresses)
+        -> abi.TsvRowsResult"""
+        o = abi.TsvAlnOpts()
+        o.sub_matrix = sub_matrix.encode() if isinstance(sub_matrix, str) else sub_matrix
+        o.gap_open, o.gap_extend, o.seq_type = int(gap_open), int(gap_extend), int(seq_type)
+        r = abi.TsvRowsResult()
+        abi.check(abi.lib().kaamer_tsv_aln_rows_device(self._h, C.byref(rows_in), C.byref(alns), C.byref(o), C.c_void_p(d_out_ptr), int(out_cap),
+                                                       C.c_void_p(stream), C.byref(r)))
+        return r
+
+    def aln_info(self):
+        """kaamer_tsv_aln_info -> dict(outside: pairs of the last -aln call with a raw score outside the table, table: raw
+        scores it holds, tables: tables filled so far)"""
+        c = (C.c_uint64 * 4)()
+        abi.check(abi.lib().kaamer_tsv_aln_info(self._h, c))
+        return dict(outside=int(c[0]), table=int(c[1]), tables=int(c[2]))
+
     def finish(self, stream=0):
-        """kaamer_tsv_rows_finish -> (rows, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did not fit"""
+        """kaamer_tsv_rows_finish -> (rows, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did not
+        fit, E_RANGE after aln_rows_device when a raw score lies outside the table (the batch is the host formatter's)"""
         c = (C.c_uint64 * 2)()
         rc = abi.lib().kaamer_tsv_rows_finish(self._h, C.c_void_p(stream), c)
         if rc:

@@ -281,6 +281,8 @@ bool kaamer_align_options(const char *sub_matrix, int gap_open, int gap_extend, 
     for (char &c : mlow) if (c >= 'A' && c <= 'Z') c = (char)(c + 32);
     return matrix_scores(sub_matrix, gap_open, gap_extend, lambda, k) && mlow == "blosum62";
 }
+// math.Pow(2, BitScore), align.go:142 (kept out of line: kaamer_align_finish and the table of the device rows get one code)
+__attribute__((noinline)) double kaamer_align_pow2(double bitscore) { return std::pow(2.0, bitscore); }
 // align.go:101-102,137,142,153-156 from the integers of one alignment (query_len = len(Query.Sequence))
 void kaamer_align_finish(kaamer_alignment *a, const kaamer_align_ints *t, uint64_t query_len, uint64_t number_of_aa, double lambda, double kk)
 {
@@ -296,7 +298,7 @@ void kaamer_align_finish(kaamer_alignment *a, const kaamer_align_ints *t, uint64
     a->gap_openings = t->gap_openings;
     a->raw = t->raw;
     a->bitscore = ((lambda * (double)t->raw) - std::log(kk)) / std::log(2.0);           // align.go:137
-    a->evalue = (double)query_len * (double)number_of_aa / std::pow(2.0, a->bitscore);  // align.go:142
+    a->evalue = (double)query_len * (double)number_of_aa / kaamer_align_pow2(a->bitscore);  // align.go:142
     a->query_start = len ? t->start_i + 1 : 1;                                          // align.go:153-156
     a->query_end = len ? t->end_i : 0;
     a->subject_start = len ? t->start_j + 1 : 1;

@@ -41,6 +41,9 @@ struct TextRequest {
     bool fasta = false, upper_last = false;
     // the TSV rows of the reported hits come back with the result (the *_tsv_flat calls, host_tsv.hip.inc)
     bool tsv = false, tsv_positions = false, tsv_annotations = false;
+    // ... behind the alignment of the reported hits, as the -aln rows (the *_aln_tsv_flat calls): numbers only, no operations
+    bool aln = false;
+    TopAlnRequest aln_rq;
 };
 
 static TextRequest fastq_request(const char *text, uint64_t len, int32_t format = 1)
@@ -66,6 +69,13 @@ static TextRequest bgzf_request(const uint8_t *comp, uint64_t comp_len)
 static TextRequest with_rows(TextRequest rq, int32_t extract_positions, int32_t annotations)
 {
     rq.tsv = true; rq.tsv_positions = extract_positions != 0; rq.tsv_annotations = annotations != 0;
+    return rq;
+}
+
+static TextRequest with_alignment(TextRequest rq, const char *sub_matrix, int32_t gap_open, int32_t gap_extend)
+{
+    rq.aln = true;
+    rq.aln_rq = top_aln_request(sub_matrix ? sub_matrix : "", gap_open, gap_extend, 0);
     return rq;
 }
 
@@ -158,6 +168,8 @@ static int text_check(kaamer_index *ix, const TextRequest &rq, int32_t seq_type,
                                              "(kaamer_parse_fasta, then kaamer_submit_batch_top_flat)", who);
         if (rq.format != 1) return kaamer_fail(KAAMER_E_ARG, "%s: unknown format %d (1 = FASTQ)", who, (int)rq.format);
     }
+    if (rq.aln && !ix->d_aln_raw)
+        return kaamer_fail(KAAMER_E_ARG, "%s: the -aln rows need the protein table on the device (kaamer_index_attach_proteins)", who);
     SEQ_TYPE_CHK(seq_type, who);
     if (!rq.fasta && !is_nucl(seq_type)) return kaamer_fail(KAAMER_E_ARG, "%s: FASTQ text is READS or NUCLEOTIDE input, not PROTEIN", who);
     if (!rq.bgzf && kaamer_is_gzip(rq.text, rq.len))
@@ -179,6 +191,7 @@ static int text_take_ticket(kaamer_index *ix, const TextRequest &rq, int32_t seq
     memset(t, 0, sizeof *t);
     t->ix = ix; t->slot = slot; t->seq_type = seq_type; t->top = *top; t->text = true;
     if (rq.tsv) { t->want_tsv = true; t->tsv_pos = rq.tsv_positions; t->tsv_ann = rq.tsv_annotations; t->want_pos = rq.tsv_positions; }
+    if (rq.aln) { t->want_aln = true; t->aln = rq.aln_rq; }
     *out = t;
     return KAAMER_OK;
 }
@@ -272,6 +285,19 @@ static int text_attach_results(kaamer_ticket *t, TopSlot &h, const TextRequest &
     return he == hipSuccess ? KAAMER_OK : kaamer_fail(KAAMER_E_HIP, "D2H: %s", hipGetErrorString(he));
 }
 
+// The alignment stage sizes its direction slabs by the batch's longest query.  A text call learns the records' lengths
+// from the spans, which are on their way home: one more wait, in the aligning calls only.
+static int text_max_query_len(kaamer_ticket *t, TopSlot &h)
+{
+    HIPCHK(hipStreamSynchronize(h.stream));
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < t->n_seqs; i++)
+        if (t->h_spans[i].seq_len > longest) longest = t->h_spans[i].seq_len;
+    if (is_nucl(t->seq_type)) longest = longest / 3 + 2;   // an ORF holds at most a frame's codons
+    t->max_query_len = longest > 0x3FFFFFFFull ? 0x3FFFFFFFu : (uint32_t)longest;
+    return KAAMER_OK;
+}
+
 // part of the call may be on the slot's stream already
 static int text_submit_failed(kaamer_ticket *t, int rc)
 {
@@ -298,6 +324,7 @@ static int text_submit(kaamer_index *ix, const TextRequest &rq, int32_t seq_type
     rc = text_stage(ix, h, rq, ps);
     if (!rc) rc = text_parse_growing(ix, h, rq, ps);
     if (!rc) rc = text_attach_results(t, h, rq, ps);
+    if (!rc && rq.aln) rc = text_max_query_len(t, h);
     if (!rc) rc = top_enqueue(t);
     if (rc) return text_submit_failed(t, rc);
     *out = t;
@@ -426,6 +453,55 @@ int kaamer_search_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint
                                     uint32_t max_results, int32_t extract_positions, int32_t annotations, kaamer_batch_top **out)
 {
     const TextRequest rq = with_rows(bgzf_request(bytes, len), extract_positions, annotations);
+    return flat_search(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, out);
+}
+
+// ... and with the alignment of the reported hits, the rows in the -aln form (search.go:556-604)
+int kaamer_submit_text_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                        int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                        const char *sub_matrix, int32_t gap_open, int32_t gap_extend, kaamer_ticket **ticket)
+{
+    const TextRequest rq = with_alignment(with_rows(fastq_request(text, len, format), extract_positions, annotations), sub_matrix, gap_open, gap_extend);
+    return flat_submit(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, ticket);
+}
+
+int kaamer_search_text_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                        int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                        const char *sub_matrix, int32_t gap_open, int32_t gap_extend, kaamer_batch_top **out)
+{
+    const TextRequest rq = with_alignment(with_rows(fastq_request(text, len, format), extract_positions, annotations), sub_matrix, gap_open, gap_extend);
+    return flat_search(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, out);
+}
+
+int kaamer_submit_fasta_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                         int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                         const char *sub_matrix, int32_t gap_open, int32_t gap_extend, kaamer_ticket **ticket)
+{
+    const TextRequest rq = with_alignment(with_rows(fasta_request(text, len, upper_last != 0), extract_positions, annotations), sub_matrix, gap_open, gap_extend);
+    return flat_submit(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, ticket);
+}
+
+int kaamer_search_fasta_top_aln_tsv_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                         int64_t min_k_match, uint32_t max_results, int32_t extract_positions, int32_t annotations,
+                                         const char *sub_matrix, int32_t gap_open, int32_t gap_extend, kaamer_batch_top **out)
+{
+    const TextRequest rq = with_alignment(with_rows(fasta_request(text, len, upper_last != 0), extract_positions, annotations), sub_matrix, gap_open, gap_extend);
+    return flat_search(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, out);
+}
+
+int kaamer_submit_bgzf_top_aln_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                        uint32_t max_results, int32_t extract_positions, int32_t annotations, const char *sub_matrix, int32_t gap_open,
+                                        int32_t gap_extend, kaamer_ticket **ticket)
+{
+    const TextRequest rq = with_alignment(with_rows(bgzf_request(bytes, len), extract_positions, annotations), sub_matrix, gap_open, gap_extend);
+    return flat_submit(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, ticket);
+}
+
+int kaamer_search_bgzf_top_aln_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                        uint32_t max_results, int32_t extract_positions, int32_t annotations, const char *sub_matrix, int32_t gap_open,
+                                        int32_t gap_extend, kaamer_batch_top **out)
+{
+    const TextRequest rq = with_alignment(with_rows(bgzf_request(bytes, len), extract_positions, annotations), sub_matrix, gap_open, gap_extend);
     return flat_search(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, out);
 }
 

@@ -114,6 +114,7 @@ static void ticket_put_pinned(kaamer_ticket *t)
 static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static int tsv_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
 static void tsv_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
+static int tsv_aln_host_rows(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
 static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h);
@@ -482,6 +483,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         if (t->h_text_out) { bo->text = t->h_text_out; bo->text_cap = t->h_text_out_cap; bo->text_len = t->text_len; t->h_text_out = nullptr; }
         if (t->want_tsv) tsv_finish_host(t, h, bo);
         if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
+        if (!rc && t->want_aln && t->want_tsv) rc = tsv_aln_host_rows(t, h, bo);   // (only a batch the stage flagged)
         if (!nucl) bo->pub.orf_aa = nullptr;
         if (!rc) *out = &bo->pub;
         else kaamer_batch_top_free(&bo->pub);

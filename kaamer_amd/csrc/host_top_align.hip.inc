@@ -337,6 +337,28 @@ static int ta_finish_rows(const TaFinish &f, batch_top_owner *bo, const kaamer_a
     return KAAMER_OK;
 }
 
+// the floats and coordinates of ta_finish_rows on pair records the caller holds (read back from kaamer_topn_align_device, or
+// built by hand): out[i] is what a result would carry for pairs[i]
+int kaamer_align_finish_pairs(const kaamer_align_pair *pairs, uint64_t n, uint64_t number_of_aa, const char *sub_matrix, int32_t gap_open,
+                              int32_t gap_extend, kaamer_alignment *out)
+{
+    if ((n && (!pairs || !out)) || !sub_matrix) return kaamer_fail(KAAMER_E_ARG, "align_finish_pairs: bad argument");
+    double lambda = 0, kk = 0;
+    const bool on = kaamer_align_options(sub_matrix, gap_open, gap_extend, &lambda, &kk);
+    for (uint64_t e = 0; e < n; e++) {
+        const kaamer_align_pair &it = pairs[e];
+        kaamer_alignment &al = out[e];
+        memset(&al, 0, sizeof al);
+        if (!on) { al.status = 1; continue; }
+        if (it.status != 0) { al.status = it.status; continue; }   // the empty AlignmentResult (BitScore 0)
+        kaamer_align_ints ti;
+        ti.n_ops = it.n_ops; ti.start_i = it.start_i; ti.start_j = it.start_j; ti.end_i = it.end_i; ti.end_j = it.end_j;
+        ti.identical = it.identical; ti.similar = it.similar; ti.mismatches = it.mismatches; ti.gap_openings = it.gap_openings; ti.raw = it.raw;
+        kaamer_align_finish(&al, &ti, it.query_len, number_of_aa, lambda, kk);
+    }
+    return KAAMER_OK;
+}
+
 // the finish of a one-device result (bo's block is complete; the slot is still the ticket's)
 static int ta_finish_host(const kaamer_ticket *t, const TopSlot &h, batch_top_owner *bo)
 {

@@ -73,6 +73,8 @@ void kaamer_align_matrix(int *m676);        // BLOSUM62 in AAPosInMatrix order, 
 bool kaamer_align_options(const char *sub_matrix, int gap_open, int gap_extend, double *lambda, double *k);
 // ... the floats of align.go:101-102,137,142 and the coordinates of :153-156 from them (aln_off is left alone)
 void kaamer_align_finish(kaamer_alignment *a, const kaamer_align_ints *t, uint64_t query_len, uint64_t number_of_aa, double lambda, double kk);
+// ... the 2^BitScore of align.go:142 as kaamer_align_finish computes it (one statement: the device rows tabulate it per raw score)
+double kaamer_align_pow2(double bitscore);
 // ... and the three rows from the operations (in reverse) and the raw letters; t (may be NULL) receives the tallies
 void kaamer_align_rows(const uint8_t *ops_rev, int len, const uint8_t *q, const uint8_t *s, int start_i, int start_j, const int *matrix,
                        int gap_open, int gap_extend, char *rows, kaamer_align_ints *t);

@@ -211,6 +211,10 @@ struct AlnTable {
     DevBuf<int> d_aln_matrix;
     uint32_t aln_idmap_n = 0, aln_entries = 0, aln_max_ns = 0;
     uint64_t aln_bytes = 0, aln_number_of_aa = 0;
+    // the *_aln_tsv_flat calls (host_tsv.hip.inc): batches whose rows the host printed because a raw score lay outside the
+    // stage's table; raw scores that table holds (0: all of TSV_ALN_RAW_N -- a smaller count is for tests of that path)
+    uint64_t tsv_aln_host_batches = 0;
+    uint32_t tsv_aln_raw_count = 0;
 };
 // kaamer_index_attach_subject_text: what a TSV row prints of a hit's entry (tsv_rows.hip.inc).  Entry i is
 // d_st_bytes[d_st_off[i], d_st_off[i + 1]): EntryId (d_st_idlen[i] bytes), then the annotation columns.  The id map is
@@ -688,6 +692,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
 #include "top_positions.hip.inc"
 #include "top_align.hip.inc"
 #include "tsv_rows.hip.inc"
+#include "tsv_aln_rows.hip.inc"
 
 // ------------------------------------------------------------------------------------
 // exclusive scan of q_cnt[0..nq) -> hit_off[0..nq]

@@ -25,7 +25,7 @@
 #define TSV_TILE 256u
 #define TSV_WINDOW 16384u
 #define TSV_NONE 0xFFFFFFFFu
-enum { TSV_C_LINES = 0, TSV_C_BYTES = 1, TSV_C_STATUS = 2, TSV_C_N = 4 };
+enum { TSV_C_LINES = 0, TSV_C_BYTES = 1, TSV_C_STATUS = 2, TSV_C_RAW = 3 /* tsv_aln_rows.hip.inc */, TSV_C_N = 4 };
 enum { TSV_ST_OUT_CAP = 1u, TSV_ST_LINE_CAP = 2u, TSV_ST_UPSTREAM = 4u /* the batch's own status, or no bitmaps in its block */ };
 
 struct TsvParams {
@@ -172,7 +172,8 @@ __device__ __forceinline__ uint32_t tsv_runs(const uint64_t *bits, uint32_t n)
 
 // FormatPositionsToString(bitmap, false), search.go:694-742, as kaamer_format_positions prints it: "start-end" per run,
 // start = first set position + 1, end = the first unset position + 1, or n for a run that reaches the end
-template <class Sink> __device__ __forceinline__ void tsv_put_positions(Sink &o, const uint64_t *bits, uint32_t n)
+// (ADD: what every run's end gains -- 0 here, KMER_SIZE - 1 in the -aln form, FormatPositionsToString(bitmap, true))
+template <uint32_t ADD, class Sink> __device__ __forceinline__ void tsv_put_positions_add(Sink &o, const uint64_t *bits, uint32_t n)
 {
     bool in_run = false, first = true;
     uint32_t start = 0;
@@ -189,7 +190,7 @@ template <class Sink> __device__ __forceinline__ void tsv_put_positions(Sink &o,
             first = false;
             o.put_u32(start + 1u);
             o.put('-');
-            o.put_u32(at >= n ? n : at + 1u);
+            o.put_u32((at >= n ? n : at + 1u) + ADD);
             in_run = false;
         }
     }
@@ -197,14 +198,40 @@ template <class Sink> __device__ __forceinline__ void tsv_put_positions(Sink &o,
         if (!first) o.put(',');
         o.put_u32(start + 1u);
         o.put('-');
-        o.put_u32(n);
+        o.put_u32(n + ADD);
     }
+}
+
+template <class Sink> __device__ __forceinline__ void tsv_put_positions(Sink &o, const uint64_t *bits, uint32_t n)
+{
+    tsv_put_positions_add<0u>(o, bits, n);
 }
 
 // the id -> entry map, as kaamer_fetch_hits resolves an id
 __device__ __forceinline__ uint32_t tsv_entry(const TsvParams &p, uint32_t pid)
 {
     return pid < p.idmap_n ? p.idmap[pid] : TSV_NONE;
+}
+
+// the bytes of a name before its first 0x20
+__device__ __forceinline__ uint32_t tsv_query_id_len(const uint8_t *name, uint32_t name_len)
+{
+    uint32_t len = 0;
+    bool found = false;
+    while (len < name_len && !found) {   // eight bytes at a time: one wait per eight loads, not one per byte
+        const uint32_t n = name_len - len < 8u ? name_len - len : 8u;
+        uint8_t t[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) t[k] = k < n ? name[len + k] : (uint8_t)' ';
+        uint32_t take = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) {
+            found = found || t[k] == (uint8_t)' ';
+            take += found ? 0u : 1u;
+        }
+        len += take;
+    }
+    return len;
 }
 
 // row r of query q; ent: the hit's entry, TSV_NONE from the query's first missing entry on
@@ -215,22 +242,7 @@ template <class Sink> __device__ __forceinline__ void tsv_row(const TsvParams &p
         const kaamer_text_span sp = p.spans[m.src_seq];
         if ((uint64_t)sp.name_off + sp.name_len <= p.names_len) {
             const uint8_t *name = p.names + sp.name_off;
-            uint32_t len = 0;
-            bool found = false;
-            while (len < sp.name_len && !found) {   // eight bytes at a time: one wait per eight loads, not one per byte
-                const uint32_t n = sp.name_len - len < 8u ? sp.name_len - len : 8u;
-                uint8_t t[8];
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++) t[k] = k < n ? name[len + k] : (uint8_t)' ';
-                uint32_t take = 0;
-#pragma unroll
-                for (uint32_t k = 0; k < 8; k++) {
-                    found = found || t[k] == (uint8_t)' ';
-                    take += found ? 0u : 1u;
-                }
-                len += take;
-            }
-            o.copy(name, len);
+            o.copy(name, tsv_query_id_len(name, sp.name_len));
         }
     }
     o.put('\t');
@@ -398,6 +410,21 @@ __global__ __launch_bounds__(TSV_TILE) void tsv_off_kernel(TsvParams p)
     for (uint32_t r = 0; r < cnt; r++) p.line_off[e0 + r] += q0;
 }
 
+// [lo, hi) of the output from the LDS window that starts at `w`, by the whole workgroup: 16 bytes per lane, consecutive
+// lanes consecutive addresses; a chunk the range covers only in part goes out in bytes
+__device__ __forceinline__ void tsv_store_window(char *out, const char *win, unsigned long long w, unsigned long long lo, unsigned long long hi)
+{
+    for (unsigned long long c = (lo - w) / 16ull + threadIdx.x; c * 16ull < hi - w; c += TSV_TILE) {
+        const unsigned long long at = w + c * 16ull;
+        if (at >= lo && at + 16ull <= hi) {
+            *reinterpret_cast<uint4 *>(out + at) = *reinterpret_cast<const uint4 *>(win + c * 16ull);
+        } else {
+            const unsigned long long a = at > lo ? at : lo, b = at + 16ull < hi ? at + 16ull : hi;
+            for (unsigned long long i = a; i < b; i++) out[i] = win[i - w];
+        }
+    }
+}
+
 __global__ __launch_bounds__(TSV_TILE) void tsv_write_kernel(TsvParams p)
 {
     __shared__ unsigned long long sh[TSV_TILE];
@@ -432,16 +459,7 @@ __global__ __launch_bounds__(TSV_TILE) void tsv_write_kernel(TsvParams p)
             }
         }
         __syncthreads();
-        // 16 bytes per lane, consecutive lanes consecutive addresses; a chunk the range covers only in part goes out in bytes
-        for (unsigned long long c = (lo - w) / 16ull + threadIdx.x; c * 16ull < hi - w; c += TSV_TILE) {
-            const unsigned long long at = w + c * 16ull;
-            if (at >= lo && at + 16ull <= hi) {
-                *reinterpret_cast<uint4 *>(p.out + at) = *reinterpret_cast<const uint4 *>(win + c * 16ull);
-            } else {
-                const unsigned long long a = at > lo ? at : lo, b = at + 16ull < hi ? at + 16ull : hi;
-                for (unsigned long long i = a; i < b; i++) p.out[i] = win[i - w];
-            }
-        }
+        tsv_store_window(p.out, win, w, lo, hi);
         __syncthreads();
     }
 }

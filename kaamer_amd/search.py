@@ -384,8 +384,6 @@ def TextSearchTsv(index, text, options=None, fmt="fastq", proteins=None):
     with tsv=...; needs Index.attach_subject_text).  fmt: "fastq", "fasta" or "bgzf" (whole BGZF blocks of FASTQ).
     proteins: the table, for the feature names of the header (default: index.proteins); needed with Annotations."""
     o = options or SearchOptions(SequenceType=abi.READS)
-    if o.Align:
-        raise ValueError("the -aln form of the TSV response is not written on the device: AlignHits, then format on the host")
     proteins = proteins if proteins is not None else getattr(index, "proteins", None)
     if o.Annotations and proteins is None:
         raise ValueError("Annotations: the header needs the table's feature names (proteins=...)")
@@ -393,6 +391,8 @@ def TextSearchTsv(index, text, options=None, fmt="fastq", proteins=None):
     st = abi.seq_type(base, o.GeneticCode) if base != abi.PROTEIN else abi.PROTEIN
     kw = dict(seq_type=st, min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults,
               tsv=dict(positions=o.ExtractPositions, annotations=o.Annotations))
+    if o.Align:   # the -aln form (search.go:556-604): the hits aligned in the same call (needs Index.attach_proteins too)
+        kw["align"] = dict(sub_matrix=o.SubMatrix, gap_open=o.GapOpen, gap_extend=o.GapExtend)
     if fmt == "fastq":
         top = index.search_text_top(text, **kw)
     elif fmt == "fasta":
@@ -401,7 +401,7 @@ def TextSearchTsv(index, text, options=None, fmt="fastq", proteins=None):
         top = index.search_bgzf_top(text, **kw)
     else:
         raise ValueError("fmt is 'fastq', 'fasta' or 'bgzf'")
-    return api.format_tsv_header(o.ExtractPositions, o.Annotations, proteins) + top.tsv
+    return api.format_tsv_header(o.ExtractPositions, o.Annotations, proteins, align=bool(o.Align)) + top.tsv
 
 
 def FetchHitsInformation(query_results, proteins):
