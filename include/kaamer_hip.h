@@ -1430,10 +1430,10 @@ int kaamer_search_fasta_file(kaamer_replicas *r, const char *path, int32_t seq_t
 /* (search.go:461-463): from that hit on, in reporting order, every hit of the */
 /* query prints an empty SubjectId, 0 as Length and empty feature values.      */
 /* The -aln form has its own section below (host formatter and device stage).  */
-/* Out of scope: JSON, the file drivers and streams, the sharded handle and    */
-/* the packed-batch calls on the device -- those have the host formatter, and  */
-/* the device stage takes names as bytes + spans, so a packed form is host     */
-/* plumbing only.                                                              */
+/* Out of scope: the file drivers and streams, the sharded handle and the      */
+/* packed-batch calls on the device -- those have the host formatter, and the  */
+/* device stage takes names as bytes + spans, so a packed form is host         */
+/* plumbing only.  (-fmt json: the JSON section at the end of this file.)      */
 /* ------------------------------------------------------------------------- */
 /* SetResponseFormatAndHeader, search.go:645-660, Align = false.  proteins (its feature names) may be NULL without
  * annotations.  The conventions of kaamer_format_positions: at most cap bytes, NUL-terminated when cap > 0, the return is
@@ -1485,10 +1485,11 @@ int64_t kaamer_format_tsv_arrays(const kaamer_batch_top *top, const int32_t *pos
 /* subnormals included; "NaN", "+Inf", "-Inf".  A hit with the empty             */
 /* AlignmentResult (kaamer_alignment.status != 0) prints its zeros:              */
 /* 0.00 0 0 0 <QStart> <QEnd> 0 0 0.000000e+00 0.00.                             */
-/* Out of scope: JSON and AlnString.  The device stage (below) serves device-    */
-/* resident pair records and the text calls (kaamer_*_top_aln_tsv_flat); the     */
-/* sharded handle, streams, file drivers and the packed-batch calls format these */
-/* rows with the host formatter.                                                 */
+/* Out of scope: AlnString, and -aln JSON (the JSON section at the end of this   */
+/* file writes results without alignments).  The device stage (below) serves     */
+/* device-resident pair records and the text calls (kaamer_*_top_aln_tsv_flat);  */
+/* the sharded handle, streams, file drivers and the packed-batch calls format   */
+/* these rows with the host formatter.                                           */
 /* ------------------------------------------------------------------------- */
 uint64_t kaamer_format_tsv_aln_header(int32_t extract_positions, int32_t annotations, const kaamer_proteins *proteins, char *buf,
                                       uint64_t cap);
@@ -1671,6 +1672,177 @@ int kaamer_batch_top_tsv(const kaamer_batch_top *out, const char **text, uint64_
 /* The FIRST bounds of the rows (bytes, rows) on every slot of this index, for callers who know what their batches print;
  * 0: the rule.  A batch beyond them is repeated as stated above.  KAAMER_E_BUSY with calls in flight. */
 int kaamer_index_set_tsv_bounds(kaamer_index *ix, uint64_t bytes, uint64_t lines);
+
+/* ------------------------------------------------------------------------- */
+/* The JSON response (-fmt json: QueryResultHandler, search.go:497-503, one    */
+/* json.Marshal(QueryResult) per reported query, Align = false; the opening    */
+/* bytes: SetResponseFormatAndHeader, search.go:672-688; the closing bytes:    */
+/* search.go:629-632).  An object is Go's struct field order, no whitespace:   */
+/*  {"Query":{"Sequence":s,"Name":s,"SizeInKmer":n,"Type":s,                   */
+/*            "Location":{"StartPosition":n,"EndPosition":n,"PlusStrand":b,    */
+/*                        "StartsAlternative":a},"Contig":s},                  */
+/*   "SearchResults":{"Counter":{},"Hits":[...],"PositionHits":{...}},         */
+/*   "HitEntries":{...}}                                                       */
+/*  Query     a protein request: Type "Protein Query", Sequence the record as   */
+/*            searched (the last record's case rule included), StartPosition   */
+/*            1, PlusStrand false -- the zero value (search.go:297-303) --,    */
+/*            StartsAlternative null (a nil slice), Contig "".  An ORF         */
+/*            (nucleotide / reads): Type "DNA Query", Sequence the residues    */
+/*            after the trim, Location as after SetBestStartCodon,             */
+/*            StartsAlternative [] (dna.go:270), Contig "" for FASTQ records   */
+/*            and the record's name for FASTA records (search.go:304-307).     */
+/*            Name is the record's whole name (the TSV cuts it at a space).    */
+/*  Counter   {}: docs/client.md:147.  The counters library is not part of     */
+/*            the reference tree; its marshalled form is taken from there.     */
+/*  Hits      [{"Key":id,"Kmatch":n,"Alignment":{...}}] in reporting order;    */
+/*            Alignment is the empty AlignmentResult (search.go:144): the      */
+/*            thirteen fields of align.go:17-31, zeros as 0, AlnString "".     */
+/*  PositionHits  {} for a protein request without ExtractPositions; else one  */
+/*            member per reported hit (FilterResults deletes the others,       */
+/*            search.go:216-218): the bitmap as searched with the first `trim` */
+/*            bits dropped (dna.go:260-262) as [true,false,...]; no bit left:  */
+/*            [].                                                              */
+/*  HitEntries  one member per reported hit up to, not including, the first id */
+/*            without an entry (FetchHitsInformation returns there,            */
+/*            search.go:461-463): the Protein with its omitempty tags          */
+/*            (protein.pb.go:24-27) -- EntryId, Sequence, Length left out when */
+/*            empty or 0, Features when it has no members; an empty feature    */
+/*            value is kept; feature names in byte order (Go's map-key order). */
+/*  map keys  of PositionHits and HitEntries: the ids as decimal strings,      */
+/*            sorted AS STRINGS ("10" < "100" < "9": encoding/json's rule).    */
+/*  strings   as encoding/json escapes them with HTML escaping on: '"' and '\' */
+/*            get a backslash; \n \r \t; every other byte below 0x20 is        */
+/*            \u00XX in lower-case hex -- 0x08 and 0x0c too: the Go release    */
+/*            go.mod names has no \b / \f forms, and this library follows it;  */
+/*            '<' '>' '&' are \u003c \u003e \u0026; 0x7f is copied.  Bytes   */
+/*            from 0x80 up are decoded by utf8.DecodeRune's rules: an invalid*/
+/*            byte (a stray continuation, a truncated sequence, an overlong  */
+/*            form, a surrogate, a value beyond U+10FFFF) prints \ufffd, one */
+/*            per byte; U+2028 / U+2029 print \u2028 / \u2029; every other   */
+/*            rune is copied.                                                  */
+/* Objects are joined by one ',' (none before the first, none after the last); */
+/* a shim writes the header, the bytes of every non-empty batch with ','       */
+/* between them, and the trailer.  Objects come in reported-query order (the   */
+/* reference's order across its handler goroutines is not deterministic).      */
+/* Out of scope: -aln JSON (shortest-round-trip floats and AlnString): a       */
+/* result that carries alignments is refused with KAAMER_E_ARG.  The file      */
+/* drivers, streams, the sharded handle and the packed-batch calls have the    */
+/* host formatter; the device stage serves the text calls.                     */
+/* ------------------------------------------------------------------------- */
+/* {"dbProteinFeatures":[ + the KStats.Features names, each in quotes, comma-separated and NOT escaped (search.go:672-688
+ * writes them so), with annotations only + ],"results":[ .  buf / cap / the return as kaamer_format_tsv_header. */
+uint64_t kaamer_format_json_header(int32_t annotations, const kaamer_proteins *proteins, char *buf, uint64_t cap);
+/* ]} */
+uint64_t kaamer_format_json_trailer(char *buf, uint64_t cap);
+/* The objects of any kaamer_batch_top without alignments (packed, _pos, sharded or text), on the caller's thread.
+ * seqs / offsets / n_seqs: the packed input of a protein request (record i is seqs[offsets[i], offsets[i + 1]); a text
+ * result: what kaamer_parse_fasta gives for the text) -- NULL / 0 for nucleotide / reads, whose Sequence is the result's
+ * orf_aa; a record beyond n_seqs prints "".  Names as kaamer_format_tsv takes them.  text_format: 0 FASTA records (Contig
+ * is the name), 1 FASTQ records (Contig is "").  The bitmaps are required -- KAAMER_E_ARG on a result without -- when the
+ * base of seq_type is not KAAMER_PROTEIN or extract_positions is set.  obj_off (may be NULL): n_reported + 1 entries, the
+ * '{' of every object and the total.  Returns the whole length (need = f(NULL, 0)) or a negative code. */
+int64_t kaamer_format_json(const kaamer_batch_top *top, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_seqs,
+                           const char *name_bytes, uint64_t name_bytes_len, const kaamer_text_span *name_spans, uint32_t n_names,
+                           const kaamer_proteins *proteins, int32_t seq_type, int32_t text_format, int32_t extract_positions,
+                           char *buf, uint64_t cap, uint64_t *obj_off);
+/* The same on a result whose arrays the caller holds itself: alns must be NULL (KAAMER_E_ARG otherwise), the three arrays
+ * of kaamer_batch_top_positions all NULL when no bitmaps are required.  Host only. */
+int64_t kaamer_format_json_arrays(const kaamer_batch_top *top, const kaamer_alignment *alns, const int32_t *pos_bits_len,
+                                  const uint64_t *pos_off, const uint64_t *pos_bits, const uint8_t *seqs, const uint64_t *offsets,
+                                  uint32_t n_seqs, const char *name_bytes, uint64_t name_bytes_len,
+                                  const kaamer_text_span *name_spans, uint32_t n_names, const kaamer_proteins *proteins,
+                                  int32_t seq_type, int32_t text_format, int32_t extract_positions, char *buf, uint64_t cap,
+                                  uint64_t *obj_off);
+/* Test entry: the bytes of one string as they stand between its quotes; buf / cap / the return as above. */
+uint64_t kaamer_json_escape(const uint8_t *bytes, uint64_t len, char *buf, uint64_t cap);
+/* Test entry: one HitEntries value, json.Marshal(Protein) of an entry the caller may have built by hand (`found` is not
+ * read); feature_names: entry->n_features of them, NUL-terminated (NULL: Features is left out). */
+uint64_t kaamer_json_protein_value(const kaamer_protein_entry *entry, const char *const *feature_names, char *buf, uint64_t cap);
+
+/* What the objects need of the protein table, resident next to the index: every entry's HitEntries value (the Protein
+ * object, sequence and annotations included), rendered once on the host by the formatter's own code -- the device only
+ * copies -- each at a 16-byte boundary, with offsets and the id -> entry map of kaamer_index_attach_subject_text (shared
+ * with it, or with kaamer_index_attach_proteins, when one of them holds the same table; else one of its own).  HBM cost:
+ * about the database's residues plus its annotations plus 40 bytes per entry.  A second attach replaces the first;
+ * KAAMER_E_BUSY with calls in flight; freed by kaamer_index_close. */
+int kaamer_index_attach_subject_json(kaamer_index *ix, const kaamer_proteins *proteins);
+/* out[0] HBM bytes, out[1] entries, out[2] the longest entry's bytes, out[3] 0; zeros when nothing is attached */
+int kaamer_index_subject_json_info(const kaamer_index *ix, uint64_t out[4]);
+
+/* The objects on the device (json_rows.hip.inc), enqueued on `stream` behind kaamer_topn_device and -- where bitmaps are
+ * required -- kaamer_topn_positions_device.  Plain device arrays: a workspace's, or fabricated ones. */
+typedef struct {
+    kaamer_tsv_rows_in rows;            /* as the TSV stage takes it; also read: top.d_trim (NULL: no trim), d_q[].aa_off / */
+                                        /* aa_len / plus_strand (the UNTRIMMED window: the stage drops top.d_trim[q]        */
+                                        /* residues itself); annotations is not read; extract_positions: PROTEIN only        */
+    const uint8_t *d_aa;                /* what aa_off indexes: the packed sequences (protein) / the ORF residues            */
+    uint64_t aa_len;                    /* its length: a window beyond it prints ""                                          */
+    int32_t seq_type;                   /* the request's                                                                     */
+    int32_t text_format;                /* 0 FASTA records, 1 FASTQ records (Contig)                                         */
+} kaamer_json_rows_in;
+typedef struct {
+    const uint64_t *d_obj_off;          /* [objects + 1] the '{' of every object in d_out; the total                         */
+    const uint64_t *d_counts;           /* device: {objects, bytes}                                                          */
+    uint64_t obj_off_capacity;          /* entries d_obj_off holds                                                           */
+} kaamer_json_rows_result;
+/* The stage's own buffers (per-query lengths, key orders, tile sums, object offsets) for up to max_queries queries and
+ * max_objects objects; one stage serves one stream at a time. */
+typedef struct kaamer_json_stage kaamer_json_stage;
+int kaamer_json_stage_create(kaamer_index *ix, uint32_t max_queries, uint64_t max_objects, kaamer_json_stage **out);
+void kaamer_json_stage_free(kaamer_json_stage *st);
+/* Three kernels: lengths, a 64-bit scan, the write pass.  Queries are taken in tiles of out[0]; a WAVE takes one reported
+ * query of its tile at a time, so the 64 lanes share every piece of an object: a string is escaped 64 bytes per step
+ * (per-lane expansion lengths, a wave prefix sum), a bitmap is expanded 64 bits per step (the trim shifts the bit origin
+ * off the word boundary: two words are funnelled), entries and literals are copied 16 bytes per lane.  The keys of a
+ * query are ordered once, in the length pass (rank by comparison, max_results^2 / 64 steps per reported query;
+ * max_results up to 65535), and the write pass reads that order.  One function, json_object, serves both passes.  A wave
+ * builds its object in an LDS buffer of out[1] bytes and stores it in runs aligned to 16 bytes in d_out, out[2] bytes per
+ * lane, consecutive lanes consecutive addresses; only the first and last bytes of an object, which share a 16-byte chunk
+ * with its neighbours, go out as single bytes.  d_out must start at a 16-byte boundary.  The capacity rule is
+ * kaamer_tsv_rows_device's: objects beyond out_cap bytes or max_objects set a status word, kaamer_json_rows_finish
+ * returns KAAMER_E_CAPACITY with what was needed, nothing of d_out is to be read, the stage stays usable.  KAAMER_E_ARG
+ * naming kaamer_index_attach_subject_json when nothing is attached. */
+int kaamer_json_rows_device(kaamer_json_stage *st, const kaamer_json_rows_in *in, char *d_out, uint64_t out_cap, void *stream,
+                            kaamer_json_rows_result *out);
+/* waits for `stream`; counts[0] objects, counts[1] bytes (also filled with what was needed on KAAMER_E_CAPACITY) */
+int kaamer_json_rows_finish(kaamer_json_stage *st, void *stream, uint64_t counts[2]);
+/* out[0] queries per tile, out[1] bytes of a wave's LDS buffer, out[2] bytes a lane stores at once, out[3] threads per
+ * workgroup */
+void kaamer_json_geometry(uint32_t out[4]);
+
+/* The text calls with the objects in the result: what a host shim calls instead of QueryResultHandler's json.Marshal
+ * (search.go:497-503) -- it writes the header (kaamer_format_json_header), the bytes of kaamer_batch_top_json of every
+ * non-empty batch with ',' between them, and the trailer.  Arguments, slot, ticket, wait, discard, spans (and text, for BGZF)
+ * as the _tsv_ twins take them, without `annotations` (an object always carries its entries).  extract_positions matters for
+ * KAAMER_PROTEIN only: KAAMER_READS / KAAMER_NUCLEOTIDE requests always ask for the bitmaps, as the _pos calls do
+ * (search.go:416), and kaamer_batch_top_positions gives them as well.  Contig is the record's name for the FASTA call and ""
+ * for the FASTQ and BGZF calls.  The stage follows the packing of the block on the slot's stream; the structured result is
+ * that of the call without objects.  The objects and their offsets have a buffer of their own next to the block (the
+ * block's format is unchanged: one more device-to-host copy); its two bounds, bytes and objects, start from what the slot's
+ * previous call needed plus a quarter, and a batch beyond them is repeated from the parsed buffers with what it reported to
+ * need.  KAAMER_E_ARG naming kaamer_index_attach_subject_json when nothing is attached. */
+int kaamer_submit_text_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                     kaamer_ticket **ticket);
+int kaamer_search_text_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type,
+                                     double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                     kaamer_batch_top **out);
+int kaamer_submit_fasta_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                      double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                      kaamer_ticket **ticket);
+int kaamer_search_fasta_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last,
+                                      double min_k_ratio, int64_t min_k_match, uint32_t max_results, int32_t extract_positions,
+                                      kaamer_batch_top **out);
+int kaamer_submit_bgzf_top_json_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, kaamer_ticket **ticket);
+int kaamer_search_bgzf_top_json_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio,
+                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, kaamer_batch_top **out);
+/* The objects of a result: views that live as long as it does; obj_off has n_reported + 1 entries.  NULL / 0 for a result of
+ * any other call (format it on the host: kaamer_format_json); kaamer_batch_top_tsv gives NULL for a result of these. */
+int kaamer_batch_top_json(const kaamer_batch_top *out, const char **text, uint64_t *len, const uint64_t **obj_off);
+/* The FIRST bounds of the objects (bytes, objects) on every slot of this index, for callers who know what their batches
+ * print; 0: the rule.  A batch beyond them is repeated as stated above.  KAAMER_E_BUSY with calls in flight. */
+int kaamer_index_set_json_bounds(kaamer_index *ix, uint64_t bytes, uint64_t objects);
 
 #ifdef __cplusplus
 }

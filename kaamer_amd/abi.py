@@ -189,6 +189,14 @@ class TsvRowsResult(C.Structure):   # kaamer_tsv_rows_result
     _fields_ = [("d_line_off", C.c_void_p), ("d_counts", C.c_void_p), ("line_off_capacity", C.c_uint64)]
 
 
+class JsonRowsIn(C.Structure):   # kaamer_json_rows_in
+    _fields_ = [("rows", TsvRowsIn), ("d_aa", C.c_void_p), ("aa_len", C.c_uint64), ("seq_type", C.c_int32), ("text_format", C.c_int32)]
+
+
+class JsonRowsResult(C.Structure):   # kaamer_json_rows_result
+    _fields_ = [("d_obj_off", C.c_void_p), ("d_counts", C.c_void_p), ("obj_off_capacity", C.c_uint64)]
+
+
 class TsvAlnOpts(C.Structure):   # kaamer_tsv_aln_opts
     _fields_ = [("sub_matrix", C.c_char * 16), ("gap_open", C.c_int32), ("gap_extend", C.c_int32), ("seq_type", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -523,6 +531,44 @@ SYMBOLS = {
     "kaamer_index_set_tsv_aln_raw_count": (C.c_int, [C.c_void_p, C.c_uint32]),
     "kaamer_batch_top_tsv": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]),
     "kaamer_index_set_tsv_bounds": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    # the JSON response: the host formatter, the subject entries on the device, the device stage, the text calls
+    # (annotations, proteins, buf, cap)
+    "kaamer_format_json_header": (C.c_uint64, [C.c_int32, C.c_void_p, C.c_char_p, C.c_uint64]),
+    "kaamer_format_json_trailer": (C.c_uint64, [C.c_char_p, C.c_uint64]),
+    # (top, seqs, offsets, n_seqs, name_bytes, name_bytes_len, name_spans, n_names, proteins, seq_type, text_format,
+    #  extract_positions, buf, cap, obj_off)
+    "kaamer_format_json": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    # (top, alns, pos_bits_len, pos_off, pos_bits, ...the same from seqs on)
+    "kaamer_format_json_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_json_escape": (C.c_uint64, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "kaamer_json_protein_value": (C.c_uint64, [C.POINTER(ProteinEntry), C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64]),
+    "kaamer_index_attach_subject_json": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kaamer_index_subject_json_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_json_stage_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "kaamer_json_stage_free": (None, [C.c_void_p]),
+    "kaamer_json_rows_device": (C.c_int, [C.c_void_p, C.POINTER(JsonRowsIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(JsonRowsResult)]),
+    "kaamer_json_rows_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kaamer_json_geometry": (None, [C.POINTER(C.c_uint32)]),
+    # (handle, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, out)
+    "kaamer_submit_text_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                   C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_text_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                   C.c_int32, C.c_void_p]),
+    # (handle, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, extract_positions, out)
+    "kaamer_submit_fasta_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                    C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_search_fasta_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
+                                                    C.c_int32, C.c_void_p]),
+    # (handle, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, out)
+    "kaamer_submit_bgzf_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                                   C.POINTER(C.c_void_p)]),
+    "kaamer_search_bgzf_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
+                                                   C.c_void_p]),
+    "kaamer_batch_top_json": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]),
+    "kaamer_index_set_json_bounds": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
 }
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range

@@ -303,6 +303,14 @@ class TopResult:
             if bool(vo):
                 self.tsv = C.string_at(vp.value, vn.value) if vn.value else b""
                 self.tsv_line_off = np.ctypeslib.as_array(vo, shape=(ne + 1,)).copy()
+        # the JSON objects of a call with json=... (kaamer_batch_top_json): bytes, and the '{' of every object + the total
+        self.json = self.json_obj_off = None
+        if hasattr(abi.lib(), "kaamer_batch_top_json"):
+            vp, vn, vo = C.c_void_p(), C.c_uint64(), C.POINTER(C.c_uint64)()
+            abi.check(abi.lib().kaamer_batch_top_json(out, C.byref(vp), C.byref(vn), C.byref(vo)))
+            if bool(vo):
+                self.json = C.string_at(vp.value, vn.value) if vn.value else b""
+                self.json_obj_off = np.ctypeslib.as_array(vo, shape=(r + 1,)).copy()
         self.alignments = None
         items, text = C.POINTER(abi.Alignment)(), C.POINTER(C.c_char)()
         abi.check(abi.lib().kaamer_batch_top_alignments(out, C.byref(items), C.byref(text)))
@@ -561,17 +569,21 @@ class Index:
             abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
         return TopTicket(t)
 
-    def _text_call(self, kind, data, extra, top, tsv, wait, align=None):
+    def _text_call(self, kind, data, extra, top, tsv, wait, align=None, json=None):
         """kaamer_{search,submit}_{kind}_top[_tsv|_aln_tsv]_flat -- kind: text, fasta or bgzf; extra: the kind's arguments
         between the data and the sequence type, and the sequence type; top: (min_k_ratio, min_k_match, max_results); wait:
         search (-> TopResult), else submit (-> TopTicket)"""
         data = data.encode("latin-1") if isinstance(data, str) else bytes(data)
         if align is not None and tsv is None:
             raise ValueError("align=... on a text call comes with tsv=...: the call returns the -aln rows")
-        form = "" if tsv is None else "_tsv" if align is None else "_aln_tsv"
+        if json is not None and (tsv is not None or align is not None):
+            raise ValueError("json=... comes alone: one response format per call, and -aln JSON is not written")
+        form = "_json" if json is not None else "" if tsv is None else "_tsv" if align is None else "_aln_tsv"
         fn = getattr(abi.lib(), "kaamer_%s_%s_top%s_flat" % ("search" if wait else "submit", kind, form))
         out = C.POINTER(abi.BatchTop)() if wait else C.c_void_p()
         more = (_tsv_args(tsv) if tsv is not None else ()) + (_align_args(align)[:3] if align is not None else ())
+        if json is not None:
+            more = (int(bool(json.get("positions"))),)
         abi.check(fn(self._h, data, len(data), *extra, *top, *more, C.byref(out)))
         if not wait:
             return TopTicket(out)
@@ -580,7 +592,7 @@ class Index:
         finally:
             abi.lib().kaamer_batch_top_free(out)
 
-    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None):
+    def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None, json=None):
         """kaamer_search_text_top_flat: FASTQ text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFastq) and searched as search_top searches the packed batch.  TopResult.text_spans: name and sequence of
         every record as offsets into `text`; rep_query / meta["src_seq"] index the records.
@@ -588,38 +600,40 @@ class Index:
         written on the device too (needs attach_subject_text): TopResult.tsv, .tsv_line_off.
         align=dict(sub_matrix=..., gap_open=..., gap_extend=...) with tsv: kaamer_search_text_top_aln_tsv_flat -- the reported
         hits are aligned in between (needs attach_proteins too) and the rows are the -aln form; TopResult.alignments carries
-        the numbers (no text), the hits are in BitScore order."""
-        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, True, align)
+        the numbers (no text), the hits are in BitScore order.
+        json=dict(positions=...): kaamer_search_text_top_json_flat -- the JSON objects of the reported queries are written on
+        the device too (needs attach_subject_json): TopResult.json, .json_obj_off; positions matters for PROTEIN only."""
+        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, True, align, json)
 
-    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
+    def search_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None, json=None):
         """kaamer_search_bgzf_top_flat: whole BGZF blocks of FASTQ (bytes) in, the reported hits out -- the compressed bytes
         are uploaded, inflated, parsed and searched on the device.  TopResult.text: the inflated text; text_spans index it.
         Bytes that are not whole BGZF blocks: KaamerError E_ARG; a block that does not inflate: E_FORMAT.
         tsv, align: as search_text_top's (kaamer_search_bgzf_top_tsv_flat / _aln_tsv_flat)."""
-        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, True, align)
+        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, True, align, json)
 
-    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
+    def submit_bgzf_top(self, data, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None, json=None):
         """kaamer_submit_bgzf_top_flat -> a ticket whose wait() returns the TopResult (with text and text_spans); tsv, align:
         as search_text_top's"""
-        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, False, align)
+        return self._text_call("bgzf", bytes(data), (seq_type,), (min_k_ratio, min_k_match, max_results), tsv, False, align, json)
 
-    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None):
+    def submit_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None, json=None):
         """kaamer_submit_text_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv, align: as
         search_text_top's"""
-        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, False, align)
+        return self._text_call("text", text, (1 if fmt == "fastq" else 0, seq_type), (min_k_ratio, min_k_match, max_results), tsv, False, align, json)
 
-    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
+    def search_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None, json=None):
         """kaamer_search_fasta_top_flat: FASTA text (bytes) in, the reported hits out -- the text is parsed on the device
         (GetQueriesFasta) and searched as search_top searches the packed batch.  seq_type: PROTEIN, NUCLEOTIDE or READS
         (with a genetic code).  upper_last: more input follows this text, its last record is upper-cased too.
         TopResult.text_spans: name and sequence range of every record as offsets into `text`.
         tsv, align: as search_text_top's (kaamer_search_fasta_top_tsv_flat / _aln_tsv_flat)."""
-        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, True, align)
+        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, True, align, json)
 
-    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None):
+    def submit_fasta_top(self, text, seq_type=abi.PROTEIN, upper_last=False, min_k_ratio=0.05, min_k_match=10, max_results=10, tsv=None, align=None, json=None):
         """kaamer_submit_fasta_top_flat -> a ticket whose wait() returns the TopResult (with text_spans); tsv, align: as
         search_text_top's"""
-        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, False, align)
+        return self._text_call("fasta", text, (seq_type, int(bool(upper_last))), (min_k_ratio, min_k_match, max_results), tsv, False, align, json)
 
     def tsv_aln_info(self):
         """kaamer_index_tsv_aln_info -> dict(host_batches: batches of the align + tsv text calls whose rows the host printed,
@@ -647,11 +661,26 @@ class Index:
         next to the index: what the TSV rows print of a hit (search_*_top(tsv=...), TsvStage)."""
         abi.check(abi.lib().kaamer_index_attach_subject_text(self._h, proteins._h))
 
+    def attach_subject_json(self, proteins):
+        """kaamer_index_attach_subject_json: every entry's HitEntries value (the Protein object as JSON) becomes resident
+        next to the index; what the calls that return JSON objects read"""
+        abi.check(abi.lib().kaamer_index_attach_subject_json(self._h, proteins._h))
+
+    def subject_json_info(self):
+        """kaamer_index_subject_json_info -> dict(table_bytes, entries, max_entry)"""
+        out = (C.c_uint64 * 4)()
+        abi.check(abi.lib().kaamer_index_subject_json_info(self._h, out))
+        return dict(table_bytes=int(out[0]), entries=int(out[1]), max_entry=int(out[2]))
+
     def subject_text_info(self):
         """kaamer_index_subject_text_info -> dict"""
         out = (C.c_uint64 * 4)()
         abi.check(abi.lib().kaamer_index_subject_text_info(self._h, out))
         return dict(zip(("table_bytes", "entries", "max_row_suffix", "features"), (int(v) for v in out)))
+
+    def set_json_bounds(self, nbytes, objects):
+        """kaamer_index_set_json_bounds: the first bounds (bytes, objects) of the json=... calls on every slot; 0: the rule"""
+        abi.check(abi.lib().kaamer_index_set_json_bounds(self._h, int(nbytes), int(objects)))
 
     def set_tsv_bounds(self, nbytes, lines):
         """kaamer_index_set_tsv_bounds: the first bounds (bytes, rows) of the tsv=... calls on every slot; 0: the rule"""
@@ -1035,8 +1064,112 @@ def format_tsv(top, names, spans, proteins=None, positions=False, annotations=Fa
     return buf.raw[:need], line_off
 
 
+def _sized(fn, *args):
+    """need = f(NULL, 0), then the bytes: the convention of the host formatters that cannot fail"""
+    need = int(fn(*args, None, 0))
+    buf = C.create_string_buffer(need + 1)
+    fn(*args, buf, need + 1)
+    return buf.raw[:need]
+
+
+def format_json_header(annotations=False, proteins=None):
+    """kaamer_format_json_header: the opening bytes of the JSON response (search.go:672-688) -> bytes"""
+    return _sized(abi.lib().kaamer_format_json_header, int(bool(annotations)), proteins._h if proteins is not None else None)
+
+
+def format_json_trailer():
+    """kaamer_format_json_trailer: the closing bytes of the JSON response (search.go:629-632) -> bytes"""
+    return _sized(abi.lib().kaamer_format_json_trailer)
+
+
+def json_escape(data):
+    """kaamer_json_escape: the bytes of a string between its quotes, as encoding/json writes them -> bytes"""
+    data = bytes(data)
+    return _sized(abi.lib().kaamer_json_escape, data, len(data))
+
+
+def json_protein_value(entry_id=b"", sequence=b"", length=0, features=()):
+    """kaamer_json_protein_value: json.Marshal(Protein) of a hand-built entry; features: [(name, value)] -> bytes"""
+    names = [bytes(k) for k, _ in features]
+    values = b"".join(bytes(v) for _, v in features)
+    off = np.zeros(len(names) + 1, np.uint64)
+    off[1:] = np.cumsum([len(v) for _, v in features]) if names else 0
+    eid, seq = C.create_string_buffer(bytes(entry_id), len(entry_id) + 1), C.create_string_buffer(bytes(sequence), len(sequence) + 1)
+    vals = C.create_string_buffer(values, len(values) + 1)
+    e = abi.ProteinEntry()
+    e.found, e.length = 1, int(length)
+    e.entry_id, e.entry_id_len = C.addressof(eid), len(entry_id)
+    e.sequence, e.sequence_len = C.addressof(seq), len(sequence)
+    e.n_features, e.features = len(names), C.addressof(vals)
+    e.feature_off = C.cast(off.ctypes.data, C.POINTER(C.c_uint64))
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    return _sized(abi.lib().kaamer_json_protein_value, C.byref(e), arr if names else None)
+
+
+def format_json(top, names, spans, proteins=None, seqs=None, offsets=None, seq_type=abi.PROTEIN, text_format=0, positions=False, cap=None):
+    """kaamer_format_json_arrays on a TopResult (or any object with its arrays: n_reported, meta, trim, top_off, top_pid,
+    top_kmatch, orf_aa and, where bitmaps are required, pos_bits_len / pos_off / pos_bits): the JSON objects of the reported
+    queries, formatted on the host (search.go:497-503) -> (bytes, obj_off u64[n_reported + 1]).  names / spans: as
+    format_tsv takes them.  seqs / offsets: the packed records of a protein request (bytes / u8 array and u64[n + 1]).
+    seq_type: the request's; text_format: 0 FASTA records, 1 FASTQ records (Contig); positions: ExtractPositions (protein
+    requests only: nucleotide / reads always print them).  top.alignments not None: KaamerError E_ARG.  cap: format into a
+    buffer of that many bytes -> (bytes written without the NUL, the needed length)."""
+    names = names.encode("latin-1") if isinstance(names, str) else bytes(names)
+    spans = np.ascontiguousarray(spans, SPAN_DTYPE)
+    r = int(top.n_reported)
+    meta = np.ascontiguousarray(top.meta, META_DTYPE)
+    off = np.ascontiguousarray(top.top_off, np.uint64)
+    pid = np.ascontiguousarray(top.top_pid, np.uint32)
+    km = np.ascontiguousarray(top.top_kmatch, np.uint32)
+    trim = np.ascontiguousarray(top.trim, np.int32) if getattr(top, "trim", None) is not None and len(top.trim) else None
+    orf = np.ascontiguousarray(top.orf_aa, np.uint8) if getattr(top, "orf_aa", None) is not None else np.zeros(0, np.uint8)
+    orf = orf if len(orf) else np.zeros(1, np.uint8)
+    bt = abi.BatchTop()
+    bt.n_queries, bt.n_reported, bt.max_results = int(getattr(top, "n_queries", r)), r, int(getattr(top, "max_results", 0))
+    bt.q = C.cast(meta.ctypes.data, C.POINTER(abi.QueryMeta))
+    bt.top_off = C.cast(off.ctypes.data, C.POINTER(C.c_uint64))
+    bt.top_pid = C.cast(pid.ctypes.data, C.POINTER(C.c_uint32))
+    bt.top_kmatch = C.cast(km.ctypes.data, C.POINTER(C.c_uint32))
+    bt.orf_aa = C.cast(orf.ctypes.data, C.POINTER(C.c_uint8))
+    if trim is not None:
+        bt.trim = C.cast(trim.ctypes.data, C.POINTER(C.c_int32))
+    pl = po = pb = None
+    if getattr(top, "pos_bits", None) is not None:
+        pl = np.ascontiguousarray(top.pos_bits_len, np.int32)
+        po = np.ascontiguousarray(top.pos_off, np.uint64)
+        pb = np.ascontiguousarray(top.pos_bits, np.uint64) if len(top.pos_bits) else np.zeros(1, np.uint64)
+    ne = int(off[r]) if r else 0
+    alns = aln_records(top.alignments, ne) if getattr(top, "alignments", None) is not None else None
+    n_seqs = 0
+    if seqs is not None:
+        seqs = np.frombuffer(bytes(seqs), np.uint8) if isinstance(seqs, (bytes, bytearray)) else np.ascontiguousarray(seqs, np.uint8)
+        seqs = seqs if len(seqs) else np.zeros(1, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        n_seqs = len(offsets) - 1
+    obj_off = np.zeros(r + 1, np.uint64)
+    args = (C.byref(bt), alns.ctypes.data if alns is not None else None, pl.ctypes.data if pl is not None else None,
+            po.ctypes.data if po is not None else None, pb.ctypes.data if pb is not None else None,
+            seqs.ctypes.data if n_seqs else None, offsets.ctypes.data if n_seqs else None, n_seqs, names, len(names),
+            spans.ctypes.data if len(spans) else None, len(spans), proteins._h if proteins is not None else None, int(seq_type),
+            int(text_format), int(bool(positions)))
+
+    def call(buf, n):
+        rc = int(abi.lib().kaamer_format_json_arrays(*args, buf, n, obj_off.ctypes.data))
+        if rc < 0:
+            abi.check(rc)
+        return rc
+    need = call(None, 0)
+    if cap is not None:
+        buf = C.create_string_buffer(max(int(cap), 1))
+        call(buf if cap else None, int(cap))
+        return (buf.raw[:min(need, int(cap) - 1)] if cap else b""), need
+    buf = C.create_string_buffer(need + 1)
+    call(buf, need + 1)
+    return buf.raw[:need], obj_off
+
+
 # kaamer_alignment as a numpy record
-ALN_DTYPE = np.dtype([("identity", np.float32), ("similarity", np.float32), ("length", np.int32), ("mismatches", np.int32),
+ALN_DTYPE =np.dtype([("identity", np.float32), ("similarity", np.float32), ("length", np.int32), ("mismatches", np.int32),
                       ("gap_openings", np.int32), ("raw", np.int32), ("bitscore", np.float64), ("evalue", np.float64),
                       ("query_start", np.int32), ("query_end", np.int32), ("subject_start", np.int32), ("subject_end", np.int32),
                       ("aln_off", np.uint64), ("status", np.int32), ("reserved", np.int32)])
@@ -1144,6 +1277,53 @@ class TsvStage:
     def close(self):
         if self._h:
             abi.lib().kaamer_tsv_stage_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def json_geometry():
+    """kaamer_json_geometry -> dict(tile, window, store, threads): queries per tile, bytes of a wave's LDS buffer, bytes a lane
+    stores at once, threads per workgroup"""
+    g = (C.c_uint32 * 4)()
+    abi.lib().kaamer_json_geometry(g)
+    return dict(tile=int(g[0]), window=int(g[1]), store=int(g[2]), threads=int(g[3]))
+
+
+class JsonStage:
+    """kaamer_json_stage_*: the buffers of the device stage that writes the JSON objects, for up to max_queries queries and
+    max_objects objects (needs Index.attach_subject_json)"""
+
+    def __init__(self, index, max_queries, max_objects):
+        self.index = index
+        h = C.c_void_p()
+        abi.check(abi.lib().kaamer_json_stage_create(index._h, int(max_queries), int(max_objects), C.byref(h)))
+        self._h = h
+
+    def rows_device(self, rows_in, d_out_ptr, out_cap, stream=0):
+        """kaamer_json_rows_device (rows_in: abi.JsonRowsIn of raw device addresses) -> abi.JsonRowsResult"""
+        r = abi.JsonRowsResult()
+        abi.check(abi.lib().kaamer_json_rows_device(self._h, C.byref(rows_in), C.c_void_p(d_out_ptr), int(out_cap), C.c_void_p(stream), C.byref(r)))
+        return r
+
+    def finish(self, stream=0):
+        """kaamer_json_rows_finish -> (objects, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did
+        not fit"""
+        c = (C.c_uint64 * 2)()
+        rc = abi.lib().kaamer_json_rows_finish(self._h, C.c_void_p(stream), c)
+        if rc:
+            e = abi.KaamerError(rc, (abi.lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
+            e.counts = (int(c[0]), int(c[1]))
+            raise e
+        return int(c[0]), int(c[1])
+
+    def close(self):
+        if self._h:
+            abi.lib().kaamer_json_stage_free(self._h)
             self._h = None
 
     def __del__(self):

@@ -41,6 +41,8 @@ struct TextRequest {
     bool fasta = false, upper_last = false;
     // the TSV rows of the reported hits come back with the result (the *_tsv_flat calls, host_tsv.hip.inc)
     bool tsv = false, tsv_positions = false, tsv_annotations = false;
+    // ... or the JSON objects of the reported queries (the *_json_flat calls, host_json.hip.inc); tsv_positions is ExtractPositions
+    bool json = false;
     // ... behind the alignment of the reported hits, as the -aln rows (the *_aln_tsv_flat calls): numbers only, no operations
     bool aln = false;
     TopAlnRequest aln_rq;
@@ -69,6 +71,12 @@ static TextRequest bgzf_request(const uint8_t *comp, uint64_t comp_len)
 static TextRequest with_rows(TextRequest rq, int32_t extract_positions, int32_t annotations)
 {
     rq.tsv = true; rq.tsv_positions = extract_positions != 0; rq.tsv_annotations = annotations != 0;
+    return rq;
+}
+
+static TextRequest with_objects(TextRequest rq, int32_t extract_positions)
+{
+    rq.json = true; rq.tsv_positions = extract_positions != 0;
     return rq;
 }
 
@@ -162,6 +170,8 @@ static int text_check(kaamer_index *ix, const TextRequest &rq, int32_t seq_type,
     *out = nullptr;
     if (rq.tsv && !ix->d_st_bytes)
         return kaamer_fail(KAAMER_E_ARG, "%s: TSV rows need the subject text on the device (kaamer_index_attach_subject_text)", who);
+    if (rq.json && !ix->d_sj_bytes)
+        return kaamer_fail(KAAMER_E_ARG, "%s: JSON objects need the subject entries on the device (kaamer_index_attach_subject_json)", who);
     if (!rq.fasta) {
         if (rq.format == 0)
             return kaamer_fail(KAAMER_E_ARG, "%s: FASTA is not parsed on the device by this call: use kaamer_submit_fasta_top_flat, or the host reader "
@@ -191,6 +201,9 @@ static int text_take_ticket(kaamer_index *ix, const TextRequest &rq, int32_t seq
     memset(t, 0, sizeof *t);
     t->ix = ix; t->slot = slot; t->seq_type = seq_type; t->top = *top; t->text = true;
     if (rq.tsv) { t->want_tsv = true; t->tsv_pos = rq.tsv_positions; t->tsv_ann = rq.tsv_annotations; t->want_pos = rq.tsv_positions; }
+    if (rq.json) {   // nucleotide / reads requests always print PositionHits (search.go:416)
+        t->want_json = true; t->json_fasta = rq.fasta; t->tsv_pos = rq.tsv_positions || is_nucl(seq_type); t->want_pos = t->tsv_pos;
+    }
     if (rq.aln) { t->want_aln = true; t->aln = rq.aln_rq; }
     *out = t;
     return KAAMER_OK;
@@ -454,6 +467,43 @@ int kaamer_search_bgzf_top_tsv_flat(kaamer_index *ix, const uint8_t *bytes, uint
 {
     const TextRequest rq = with_rows(bgzf_request(bytes, len), extract_positions, annotations);
     return flat_search(ix, rq, seq_type, min_k_ratio, min_k_match, max_results, out);
+}
+
+// ... and the three with the JSON objects of the reported queries (-fmt json, search.go:497-503)
+int kaamer_submit_text_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, kaamer_ticket **ticket)
+{
+    return flat_submit(ix, with_objects(fastq_request(text, len, format), extract_positions), seq_type, min_k_ratio, min_k_match, max_results, ticket);
+}
+
+int kaamer_search_text_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t format, int32_t seq_type, double min_k_ratio,
+                                     int64_t min_k_match, uint32_t max_results, int32_t extract_positions, kaamer_batch_top **out)
+{
+    return flat_search(ix, with_objects(fastq_request(text, len, format), extract_positions), seq_type, min_k_ratio, min_k_match, max_results, out);
+}
+
+int kaamer_submit_fasta_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                      int64_t min_k_match, uint32_t max_results, int32_t extract_positions, kaamer_ticket **ticket)
+{
+    return flat_submit(ix, with_objects(fasta_request(text, len, upper_last != 0), extract_positions), seq_type, min_k_ratio, min_k_match, max_results, ticket);
+}
+
+int kaamer_search_fasta_top_json_flat(kaamer_index *ix, const char *text, uint64_t len, int32_t seq_type, int32_t upper_last, double min_k_ratio,
+                                      int64_t min_k_match, uint32_t max_results, int32_t extract_positions, kaamer_batch_top **out)
+{
+    return flat_search(ix, with_objects(fasta_request(text, len, upper_last != 0), extract_positions), seq_type, min_k_ratio, min_k_match, max_results, out);
+}
+
+int kaamer_submit_bgzf_top_json_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                     uint32_t max_results, int32_t extract_positions, kaamer_ticket **ticket)
+{
+    return flat_submit(ix, with_objects(bgzf_request(bytes, len), extract_positions), seq_type, min_k_ratio, min_k_match, max_results, ticket);
+}
+
+int kaamer_search_bgzf_top_json_flat(kaamer_index *ix, const uint8_t *bytes, uint64_t len, int32_t seq_type, double min_k_ratio, int64_t min_k_match,
+                                     uint32_t max_results, int32_t extract_positions, kaamer_batch_top **out)
+{
+    return flat_search(ix, with_objects(bgzf_request(bytes, len), extract_positions), seq_type, min_k_ratio, min_k_match, max_results, out);
 }
 
 // ... and with the alignment of the reported hits, the rows in the -aln form (search.go:556-604)

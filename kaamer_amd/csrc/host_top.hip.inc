@@ -40,6 +40,7 @@ struct batch_top_owner {
     size_t tsv_cap = 0;
     uint64_t tsv_lines = 0, tsv_len = 0;
     const char *tsv_text = nullptr;
+    bool json = false;   // ... or the JSON objects of a *_json_flat call (host_json.hip.inc): obj_off[tsv_lines + 1], then the text
 };
 
 // the alignment half of a request (kaamer_*_batch_top_aln_flat)
@@ -96,6 +97,8 @@ struct kaamer_ticket {
     // a call that returns the TSV rows (host_tsv.hip.inc; text calls only): the request, the names on the device, the bounds
     // of this attempt (0: the slot's guess) and the pinned buffer that goes to the result
     bool want_tsv, tsv_pos, tsv_ann;
+    // ... or the JSON objects (host_json.hip.inc): the same bounds and buffer (bytes, objects); tsv_pos is ExtractPositions
+    bool want_json, json_fasta;
     const uint8_t *d_names;
     uint64_t names_len;
     const kaamer_text_span *d_spans;
@@ -115,6 +118,10 @@ static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_resul
 static int tsv_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
 static void tsv_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
 static int tsv_aln_host_rows(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
+static int top_enqueue_json(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
+static int json_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
+static void json_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
+extern "C" void kaamer_json_stage_free(kaamer_json_stage *st);
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
 static int ta_needs_repeat(kaamer_ticket *t, TopSlot &h);
@@ -259,6 +266,7 @@ static void top_slot_free(TopSlot &h)
     if (h.parser) kaamer_text_parser_free(h.parser);
     if (h.inflater) kaamer_inflater_free(h.inflater);
     if (h.tsv) kaamer_tsv_stage_free(h.tsv);
+    if (h.json) kaamer_json_stage_free(h.json);
     if (h.stream) (void)hipStreamDestroy(h.stream);
     h = TopSlot();   // (its buffers go here)
 }
@@ -352,6 +360,7 @@ static int top_enqueue(kaamer_ticket *t)
     if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
     if (!rc && aligns) rc = top_enqueue_alignments(t, h, &tr, s);
     if (!rc && t->want_tsv) rc = top_enqueue_tsv(t, h, &tr, s);
+    if (!rc && t->want_json) rc = top_enqueue_json(t, h, &tr, s);
     if (rc) return rc;
     return rep_block_copy_guess(h.d_block, h.block_use, h.guess, &t->h_block, &t->h_block_cap, &t->copied, s);
 }
@@ -463,6 +472,12 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
             rc = top_enqueue(t);
             continue;
         }
+        if (t->want_json && json_needs_repeat(t, h, &rc)) {   // the objects' bounds were too small: once more, with what they needed
+            if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "JSON objects of the result"); break; }
+            t->attempt++;
+            rc = top_enqueue(t);
+            continue;
+        }
         if (rc) break;
         rc = rep_block_fetch_rest(h.d_block, &h.guess, &t->h_block, &t->h_block_cap, &t->copied, h.stream);
         break;
@@ -482,6 +497,7 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         if (t->text) { bo->spans = t->h_spans; bo->spans_cap = t->h_spans_cap; bo->n_spans = t->n_seqs; t->h_spans = nullptr; }
         if (t->h_text_out) { bo->text = t->h_text_out; bo->text_cap = t->h_text_out_cap; bo->text_len = t->text_len; t->h_text_out = nullptr; }
         if (t->want_tsv) tsv_finish_host(t, h, bo);
+        if (t->want_json) json_finish_host(t, h, bo);
         if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
         if (!rc && t->want_aln && t->want_tsv) rc = tsv_aln_host_rows(t, h, bo);   // (only a batch the stage flagged)
         if (!nucl) bo->pub.orf_aa = nullptr;

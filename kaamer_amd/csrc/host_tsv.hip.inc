@@ -66,6 +66,7 @@ int kaamer_index_attach_subject_text(kaamer_index *ix, const kaamer_proteins *p)
     ix->d_st_idmap = share ? ix->d_aln_idmap.get() : ix->d_st_idmap_own.get();   // (borrowed: aln_table_free hands it over)
     ix->st_idmap_n = (uint32_t)map_n; ix->st_entries = n; ix->st_features = nf;
     ix->st_max_suffix = max_suffix;
+    ix->st_host = p;
     ix->st_bytes = bytes.size() + 1 + off.size() * 8 + idlen.size() * 4 + length.size() * 4 + (share ? 0 : idmap.size() * 4);
     return KAAMER_OK;
 }
@@ -481,7 +482,7 @@ int kaamer_batch_top_tsv(const kaamer_batch_top *out, const char **text, uint64_
     if (line_off) *line_off = nullptr;
     if (!out) return kaamer_fail(KAAMER_E_ARG, "batch_top_tsv: bad argument");
     const batch_top_owner *bo = reinterpret_cast<const batch_top_owner *>(out);  // pub is the first member
-    if (!bo->tsv) return KAAMER_OK;   // any other call: format the rows on the host (kaamer_format_tsv)
+    if (!bo->tsv || bo->json) return KAAMER_OK;   // any other call: format the rows on the host (kaamer_format_tsv)
     if (text) *text = bo->tsv_text;
     if (len) *len = bo->tsv_len;
     if (line_off) *line_off = reinterpret_cast<const uint64_t *>(bo->tsv);

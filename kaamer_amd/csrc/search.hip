@@ -164,6 +164,7 @@ static void bounds_grow(BatchBounds &b, uint64_t seq_bytes, uint32_t n_seqs, boo
     bounds_grow_positions(b);
 }
 
+struct kaamer_json_stage;
 // one in-flight call of the pipelined host-buffer boundary (host_top.hip.inc)
 struct TopSlot {
     kaamer_workspace *ws = nullptr;
@@ -197,6 +198,12 @@ struct TopSlot {
     uint64_t tsv_lines = 0;
     DevBuf<char> d_tsv;            // 16 bytes more than the rows may take
     uint64_t tsv_guess_bytes = 0, tsv_guess_lines = 0;
+    // the calls that return JSON objects (host_json.hip.inc): the same, bytes and objects
+    kaamer_json_stage *json = nullptr;
+    uint32_t json_queries = 0;
+    uint64_t json_objects = 0;
+    DevBuf<char> d_json;
+    uint64_t json_guess_bytes = 0, json_guess_objects = 0;
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
@@ -227,9 +234,23 @@ struct SubjectText {
     const uint32_t *d_st_idmap = nullptr;        // the map in use: d_st_idmap_own, or AlnTable::d_aln_idmap
     uint32_t st_idmap_n = 0, st_entries = 0, st_features = 0;
     uint64_t st_bytes = 0, st_max_suffix = 0;
+    const kaamer_proteins *st_host = nullptr;    // the table it was made from (compared, never read: who may share the map)
+};
+// kaamer_index_attach_subject_json: what a JSON object prints of a hit's entry (json_rows.hip.inc).  Entry i is
+// d_sj_bytes[d_sj_off[i], + d_sj_len[i]), its HitEntries value, at a 16-byte boundary.  The id map is borrowed from the
+// subject text or the alignment table when one of them holds the same table, else owned here; a lender that goes hands
+// its map to the borrower (aln_table_free, subject_text_free).
+struct SubjectJson {
+    DevBuf<uint8_t> d_sj_bytes;
+    DevBuf<uint64_t> d_sj_off;
+    DevBuf<uint32_t> d_sj_len;
+    DevBuf<uint32_t> d_sj_idmap_own;
+    const uint32_t *d_sj_idmap = nullptr;
+    uint32_t sj_idmap_n = 0, sj_entries = 0;
+    uint64_t sj_bytes = 0, sj_max_entry = 0;
 };
 
-struct kaamer_index : AlnTable, SubjectText {
+struct kaamer_index : AlnTable, SubjectText, SubjectJson {
     int device;
     kh_image_header hdr;
     kh_bucket *d_buckets;         // raw: taken over from the device build, or uploaded from an image
@@ -693,6 +714,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
 #include "top_align.hip.inc"
 #include "tsv_rows.hip.inc"
 #include "tsv_aln_rows.hip.inc"
+#include "json_rows.hip.inc"
 
 // ------------------------------------------------------------------------------------
 // exclusive scan of q_cnt[0..nq) -> hit_off[0..nq]
@@ -1111,11 +1133,19 @@ static void aln_table_free(kaamer_index *ix)
 {
     // (a subject text that borrows the id map takes it over: it is the owner from here on)
     if (ix->d_aln_idmap && ix->d_st_idmap == ix->d_aln_idmap) ix->d_st_idmap_own = std::move(ix->d_aln_idmap);
+    else if (ix->d_aln_idmap && ix->d_sj_idmap == ix->d_aln_idmap) ix->d_sj_idmap_own = std::move(ix->d_aln_idmap);
     static_cast<AlnTable &>(*ix) = AlnTable();
 }
 
 // ... and the attached subject text (kaamer_index_attach_subject_text)
-static void subject_text_free(kaamer_index *ix) { static_cast<SubjectText &>(*ix) = SubjectText(); }
+static void subject_text_free(kaamer_index *ix)
+{
+    if (ix->d_st_idmap_own && ix->d_sj_idmap == ix->d_st_idmap_own) ix->d_sj_idmap_own = std::move(ix->d_st_idmap_own);
+    static_cast<SubjectText &>(*ix) = SubjectText();
+}
+
+// ... and the attached subject entries in JSON form (kaamer_index_attach_subject_json)
+static void subject_json_free(kaamer_index *ix) { static_cast<SubjectJson &>(*ix) = SubjectJson(); }
 
 #include "parse_text.hip.inc"
 #include "parse_fasta.hip.inc"
@@ -2410,6 +2440,7 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 #include "host_top_align.hip.inc"
 #include "host_text.hip.inc"
 #include "host_tsv.hip.inc"
+#include "host_json.hip.inc"
 #include "host_sharded.hip.inc"
 #include "host_sharded_submit.hip.inc"
 #include "host_sharded_collect.hip.inc"

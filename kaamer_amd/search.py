@@ -404,6 +404,33 @@ def TextSearchTsv(index, text, options=None, fmt="fastq", proteins=None):
     return api.format_tsv_header(o.ExtractPositions, o.Annotations, proteins, align=bool(o.Align)) + top.tsv
 
 
+def TextSearchJson(index, text, options=None, fmt="fastq", proteins=None):
+    """The whole JSON response body of a request whose input is text (SetResponseFormatAndHeader, search.go:672-688; one
+    json.Marshal(QueryResult) per reported query, search.go:497-503; the closing bytes, search.go:629-632), OutFormat "json"
+    without Align: the objects are written on the device in the same call that parses and searches the text
+    (Index.search_text_top / search_fasta_top / search_bgzf_top with json=...; needs Index.attach_subject_json).  fmt:
+    "fastq", "fasta" or "bgzf".  proteins: the table, for the feature names of the header (default: index.proteins); needed
+    with Annotations."""
+    o = options or SearchOptions(SequenceType=abi.READS)
+    if o.Align:
+        raise ValueError("-aln JSON is not written")
+    proteins = proteins if proteins is not None else getattr(index, "proteins", None)
+    if o.Annotations and proteins is None:
+        raise ValueError("Annotations: the header needs the table's feature names (proteins=...)")
+    base = abi.seq_type_base(o.SequenceType)
+    st = abi.seq_type(base, o.GeneticCode) if base != abi.PROTEIN else abi.PROTEIN
+    kw = dict(seq_type=st, min_k_ratio=o.MinKRatio, min_k_match=o.MinKMatch, max_results=o.MaxResults, json=dict(positions=o.ExtractPositions))
+    if fmt == "fastq":
+        top = index.search_text_top(text, **kw)
+    elif fmt == "fasta":
+        top = index.search_fasta_top(text, **kw)
+    elif fmt == "bgzf":
+        top = index.search_bgzf_top(text, **kw)
+    else:
+        raise ValueError("fmt is 'fastq', 'fasta' or 'bgzf'")
+    return api.format_json_header(o.Annotations, proteins) + top.json + api.format_json_trailer()
+
+
 def FetchHitsInformation(query_results, proteins):
     """search.go:454-470 for a list of QueryResult dicts: HitEntries[Key] = the Protein entry (protein.proto:
     EntryId, Sequence, Length, Features) of every reported hit, from the protein table makedb built
