@@ -1220,23 +1220,56 @@ def format_doubles_device(d_values_ptr, n, mode, d_out_ptr):
     abi.check(abi.lib().kaamer_tsv_format_doubles_device(C.c_void_p(d_values_ptr), int(n), int(mode), C.c_void_p(d_out_ptr)))
 
 
-def tsv_geometry():
-    """kaamer_tsv_geometry -> dict(tile, window, store, threads): queries per tile of the write pass, bytes per LDS window
-    (windows lie on multiples of it in the output), bytes a lane stores at once, threads per workgroup"""
+def _geometry(fn):
     g = (C.c_uint32 * 4)()
-    abi.lib().kaamer_tsv_geometry(g)
+    fn(g)
     return dict(tile=int(g[0]), window=int(g[1]), store=int(g[2]), threads=int(g[3]))
 
 
-class TsvStage:
-    """kaamer_tsv_stage_*: the buffers of the device stage that writes the TSV rows, for up to max_queries queries and
-    max_lines rows (needs Index.attach_subject_text)"""
+def tsv_geometry():
+    """kaamer_tsv_geometry -> dict(tile, window, store, threads): queries per tile of the write pass, bytes per LDS window
+    (windows lie on multiples of it in the output), bytes a lane stores at once, threads per workgroup"""
+    return _geometry(abi.lib().kaamer_tsv_geometry)
 
-    def __init__(self, index, max_queries, max_lines):
+
+class _RowsStage:
+    """what TsvStage and JsonStage share: kaamer_{_KIND}_stage_create / _free and kaamer_{_KIND}_rows_finish"""
+    _KIND = None
+
+    def __init__(self, index, max_queries, max_units):
         self.index = index
         h = C.c_void_p()
-        abi.check(abi.lib().kaamer_tsv_stage_create(index._h, int(max_queries), int(max_lines), C.byref(h)))
+        abi.check(getattr(abi.lib(), "kaamer_%s_stage_create" % self._KIND)(index._h, int(max_queries), int(max_units), C.byref(h)))
         self._h = h
+
+    def finish(self, stream=0):
+        c = (C.c_uint64 * 2)()
+        rc = getattr(abi.lib(), "kaamer_%s_rows_finish" % self._KIND)(self._h, C.c_void_p(stream), c)
+        if rc:
+            e = abi.KaamerError(rc, (abi.lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
+            e.counts = (int(c[0]), int(c[1]))
+            raise e
+        return int(c[0]), int(c[1])
+
+    def close(self):
+        if self._h:
+            getattr(abi.lib(), "kaamer_%s_stage_free" % self._KIND)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TsvStage(_RowsStage):
+    """kaamer_tsv_stage_*: the buffers of the device stage that writes the TSV rows, for up to max_queries queries and
+    max_lines rows (needs Index.attach_subject_text)"""
+    _KIND = "tsv"
+
+    def __init__(self, index, max_queries, max_lines):
+        super().__init__(index, max_queries, max_lines)
 
     def rows_device(self, rows_in, d_out_ptr, out_cap, stream=0):
         """kaamer_tsv_rows_device (rows_in: abi.TsvRowsIn of raw device addresses) -> abi.TsvRowsResult"""
@@ -1266,43 +1299,22 @@ class TsvStage:
     def finish(self, stream=0):
         """kaamer_tsv_rows_finish -> (rows, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did not
         fit, E_RANGE after aln_rows_device when a raw score lies outside the table (the batch is the host formatter's)"""
-        c = (C.c_uint64 * 2)()
-        rc = abi.lib().kaamer_tsv_rows_finish(self._h, C.c_void_p(stream), c)
-        if rc:
-            e = abi.KaamerError(rc, (abi.lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
-            e.counts = (int(c[0]), int(c[1]))
-            raise e
-        return int(c[0]), int(c[1])
-
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_tsv_stage_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().finish(stream)
 
 
 def json_geometry():
     """kaamer_json_geometry -> dict(tile, window, store, threads): queries per tile, bytes of a wave's LDS buffer, bytes a lane
     stores at once, threads per workgroup"""
-    g = (C.c_uint32 * 4)()
-    abi.lib().kaamer_json_geometry(g)
-    return dict(tile=int(g[0]), window=int(g[1]), store=int(g[2]), threads=int(g[3]))
+    return _geometry(abi.lib().kaamer_json_geometry)
 
 
-class JsonStage:
+class JsonStage(_RowsStage):
     """kaamer_json_stage_*: the buffers of the device stage that writes the JSON objects, for up to max_queries queries and
     max_objects objects (needs Index.attach_subject_json)"""
+    _KIND = "json"
 
     def __init__(self, index, max_queries, max_objects):
-        self.index = index
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_json_stage_create(index._h, int(max_queries), int(max_objects), C.byref(h)))
-        self._h = h
+        super().__init__(index, max_queries, max_objects)
 
     def rows_device(self, rows_in, d_out_ptr, out_cap, stream=0):
         """kaamer_json_rows_device (rows_in: abi.JsonRowsIn of raw device addresses) -> abi.JsonRowsResult"""
@@ -1313,24 +1325,7 @@ class JsonStage:
     def finish(self, stream=0):
         """kaamer_json_rows_finish -> (objects, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did
         not fit"""
-        c = (C.c_uint64 * 2)()
-        rc = abi.lib().kaamer_json_rows_finish(self._h, C.c_void_p(stream), c)
-        if rc:
-            e = abi.KaamerError(rc, (abi.lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
-            e.counts = (int(c[0]), int(c[1]))
-            raise e
-        return int(c[0]), int(c[1])
-
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_json_stage_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return super().finish(stream)
 
 
 def _align_args(align):

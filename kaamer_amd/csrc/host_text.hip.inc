@@ -3,7 +3,7 @@
 //
 // Every text call is a TextRequest -- where the text comes from (the caller's buffer, or BGZF blocks that the slot's
 // inflater, inflate.hip.inc, turns into text on the device), which parser reads it (parse_text.hip.inc, parse_fasta.hip.inc)
-// and whether the TSV rows of the reported hits come back too (host_tsv.hip.inc) -- handed to text_submit, whose phases are
+// and whether the TSV rows of the reported hits come back too (host_out_text.hip.inc) -- handed to text_submit, whose phases are
 //   text_check            what is refused, before anything is taken
 //   text_take_ticket      a free slot and the ticket that holds it
 //   text_first_bounds     records and lines the slot's parser starts with
@@ -39,9 +39,9 @@ struct TextRequest {
     // sequence type as the other two)
     int32_t format = 1;
     bool fasta = false, upper_last = false;
-    // the TSV rows of the reported hits come back with the result (the *_tsv_flat calls, host_tsv.hip.inc)
+    // the TSV rows of the reported hits come back with the result (the *_tsv_flat calls, host_out_text.hip.inc)
     bool tsv = false, tsv_positions = false, tsv_annotations = false;
-    // ... or the JSON objects of the reported queries (the *_json_flat calls, host_json.hip.inc); tsv_positions is ExtractPositions
+    // ... or the JSON objects of the reported queries (the *_json_flat calls); tsv_positions is ExtractPositions
     bool json = false;
     // ... behind the alignment of the reported hits, as the -aln rows (the *_aln_tsv_flat calls): numbers only, no operations
     bool aln = false;
@@ -168,9 +168,9 @@ static int text_check(kaamer_index *ix, const TextRequest &rq, int32_t seq_type,
     const char *who = rq.who;
     if (!ix || !top || !out || (!rq.text && rq.len && !rq.bgzf) || top->max_results < 1) return kaamer_fail(KAAMER_E_ARG, "%s: bad argument", who);
     *out = nullptr;
-    if (rq.tsv && !ix->d_st_bytes)
+    if (rq.tsv && !ix->st.d_bytes)
         return kaamer_fail(KAAMER_E_ARG, "%s: TSV rows need the subject text on the device (kaamer_index_attach_subject_text)", who);
-    if (rq.json && !ix->d_sj_bytes)
+    if (rq.json && !ix->sj.d_bytes)
         return kaamer_fail(KAAMER_E_ARG, "%s: JSON objects need the subject entries on the device (kaamer_index_attach_subject_json)", who);
     if (!rq.fasta) {
         if (rq.format == 0)
@@ -200,9 +200,9 @@ static int text_take_ticket(kaamer_index *ix, const TextRequest &rq, int32_t seq
     if (!t) { top_slot_release(ix, slot); return kaamer_fail(KAAMER_E_NOMEM, "ticket"); }
     memset(t, 0, sizeof *t);
     t->ix = ix; t->slot = slot; t->seq_type = seq_type; t->top = *top; t->text = true;
-    if (rq.tsv) { t->want_tsv = true; t->tsv_pos = rq.tsv_positions; t->tsv_ann = rq.tsv_annotations; t->want_pos = rq.tsv_positions; }
+    if (rq.tsv) { t->out_fmt = OUT_TSV; t->out_pos = rq.tsv_positions; t->out_ann = rq.tsv_annotations; t->want_pos = rq.tsv_positions; }
     if (rq.json) {   // nucleotide / reads requests always print PositionHits (search.go:416)
-        t->want_json = true; t->json_fasta = rq.fasta; t->tsv_pos = rq.tsv_positions || is_nucl(seq_type); t->want_pos = t->tsv_pos;
+        t->out_fmt = OUT_JSON; t->json_fasta = rq.fasta; t->out_pos = rq.tsv_positions || is_nucl(seq_type); t->want_pos = t->out_pos;
     }
     if (rq.aln) { t->want_aln = true; t->aln = rq.aln_rq; }
     *out = t;

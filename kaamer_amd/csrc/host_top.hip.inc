@@ -35,12 +35,13 @@ struct batch_top_owner {
     char *text = nullptr;
     size_t text_cap = 0;
     uint64_t text_len = 0;
-    // the TSV rows of a *_tsv_flat call (host_tsv.hip.inc), pinned: line_off[tsv_lines + 1], then the text
-    uint8_t *tsv = nullptr;
-    size_t tsv_cap = 0;
-    uint64_t tsv_lines = 0, tsv_len = 0;
-    const char *tsv_text = nullptr;
-    bool json = false;   // ... or the JSON objects of a *_json_flat call (host_json.hip.inc): obj_off[tsv_lines + 1], then the text
+    // the response text of a *_tsv_flat / *_json_flat call (host_out_text.hip.inc), pinned: the offsets of its rows or objects
+    // (out_units + 1 of them), then the text
+    OutFormat out_fmt = OUT_PLAIN;
+    uint8_t *out = nullptr;
+    size_t out_cap = 0;
+    uint64_t out_units = 0, out_len = 0;
+    const char *out_text = nullptr;
 };
 
 // the alignment half of a request (kaamer_*_batch_top_aln_flat)
@@ -94,17 +95,17 @@ struct kaamer_ticket {
     char *h_text_out;            // a BGZF call: the inflated text, pinned; goes to the result
     size_t h_text_out_cap;
     uint64_t text_len;
-    // a call that returns the TSV rows (host_tsv.hip.inc; text calls only): the request, the names on the device, the bounds
-    // of this attempt (0: the slot's guess) and the pinned buffer that goes to the result
-    bool want_tsv, tsv_pos, tsv_ann;
-    // ... or the JSON objects (host_json.hip.inc): the same bounds and buffer (bytes, objects); tsv_pos is ExtractPositions
-    bool want_json, json_fasta;
+    // a call that returns response text (host_out_text.hip.inc; text calls only): the format and the request (out_pos:
+    // ExtractPositions, out_ann: Annotations, json_fasta: the records are FASTA), the names on the device, the bounds of this
+    // attempt (bytes; rows or objects; 0: the slot's guess) and the pinned buffer that goes to the result
+    OutFormat out_fmt;
+    bool out_pos, out_ann, json_fasta;
     const uint8_t *d_names;
     uint64_t names_len;
     const kaamer_text_span *d_spans;
-    uint64_t tsv_bytes_cap, tsv_lines_cap;
-    uint8_t *h_tsv;
-    size_t h_tsv_cap;
+    uint64_t out_bytes_cap, out_units_cap;
+    uint8_t *h_out;
+    size_t h_out_cap;
 };
 // the pinned buffers a ticket still holds (those that went to a result are NULL by then) back to the cache
 static void ticket_put_pinned(kaamer_ticket *t)
@@ -112,15 +113,12 @@ static void ticket_put_pinned(kaamer_ticket *t)
     if (t->h_block) pinned_put(t->h_block, t->h_block_cap);
     if (t->h_spans) pinned_put(t->h_spans, t->h_spans_cap);
     if (t->h_text_out) pinned_put(t->h_text_out, t->h_text_out_cap);
-    if (t->h_tsv) pinned_put(t->h_tsv, t->h_tsv_cap);
+    if (t->h_out) pinned_put(t->h_out, t->h_out_cap);
 }
-static int top_enqueue_tsv(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
-static int tsv_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
-static void tsv_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
+static int top_enqueue_out(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
+static int out_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
+static void out_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
 static int tsv_aln_host_rows(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
-static int top_enqueue_json(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
-static int json_needs_repeat(kaamer_ticket *t, TopSlot &h, int *rc);
-static void json_finish_host(kaamer_ticket *t, TopSlot &h, batch_top_owner *bo);
 extern "C" void kaamer_json_stage_free(kaamer_json_stage *st);
 static int top_enqueue_alignments(kaamer_ticket *t, TopSlot &h, const kaamer_topn_result *tr, hipStream_t s);
 static uint64_t ta_first_cap(const kaamer_ticket *t, const TopSlot &h);
@@ -359,8 +357,7 @@ static int top_enqueue(kaamer_ticket *t)
     if (!rc) rc = topn_pack_block(h.ws, h.ws, 0u, 1u, &tr, s, h.d_block, h.block_use);
     if (!rc && t->want_pos) rc = topn_pack_positions(ix, h.ws, &tr, s, h.d_block, h.block_use, h.pos_words);
     if (!rc && aligns) rc = top_enqueue_alignments(t, h, &tr, s);
-    if (!rc && t->want_tsv) rc = top_enqueue_tsv(t, h, &tr, s);
-    if (!rc && t->want_json) rc = top_enqueue_json(t, h, &tr, s);
+    if (!rc && t->out_fmt) rc = top_enqueue_out(t, h, &tr, s);
     if (rc) return rc;
     return rep_block_copy_guess(h.d_block, h.block_use, h.guess, &t->h_block, &t->h_block_cap, &t->copied, s);
 }
@@ -466,14 +463,8 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
             rc = top_enqueue(t);
             continue;
         }
-        if (t->want_tsv && tsv_needs_repeat(t, h, &rc)) {   // the rows' bounds were too small: once more, with what they needed
-            if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "TSV rows of the result"); break; }
-            t->attempt++;
-            rc = top_enqueue(t);
-            continue;
-        }
-        if (t->want_json && json_needs_repeat(t, h, &rc)) {   // the objects' bounds were too small: once more, with what they needed
-            if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "JSON objects of the result"); break; }
+        if (t->out_fmt && out_needs_repeat(t, h, &rc)) {   // the response text's bounds were too small: once more, with what it needed
+            if (t->attempt >= MAX_BOUND_RETRIES + 2) { rc = kaamer_fail(KAAMER_E_CAPACITY, "%s of the result", t->out_fmt == OUT_TSV ? "TSV rows" : "JSON objects"); break; }
             t->attempt++;
             rc = top_enqueue(t);
             continue;
@@ -496,10 +487,9 @@ int kaamer_wait_batch_top(kaamer_ticket *t, kaamer_batch_top **out)
         bo->has_pos = t->want_pos;
         if (t->text) { bo->spans = t->h_spans; bo->spans_cap = t->h_spans_cap; bo->n_spans = t->n_seqs; t->h_spans = nullptr; }
         if (t->h_text_out) { bo->text = t->h_text_out; bo->text_cap = t->h_text_out_cap; bo->text_len = t->text_len; t->h_text_out = nullptr; }
-        if (t->want_tsv) tsv_finish_host(t, h, bo);
-        if (t->want_json) json_finish_host(t, h, bo);
+        if (t->out_fmt) out_finish_host(t, h, bo);
         if (t->want_aln) rc = ta_finish_host(t, h, bo);   // (reads protein queries from the slot's staging: before the release)
-        if (!rc && t->want_aln && t->want_tsv) rc = tsv_aln_host_rows(t, h, bo);   // (only a batch the stage flagged)
+        if (!rc && t->want_aln && t->out_fmt == OUT_TSV) rc = tsv_aln_host_rows(t, h, bo);   // (only a batch the stage flagged)
         if (!nucl) bo->pub.orf_aa = nullptr;
         if (!rc) *out = &bo->pub;
         else kaamer_batch_top_free(&bo->pub);
@@ -638,7 +628,7 @@ void kaamer_batch_top_free(kaamer_batch_top *out)
     if (bo->block) { if (bo->pinned) pinned_put(bo->block, bo->block_cap); else free(bo->block); }
     if (bo->spans) pinned_put(bo->spans, bo->spans_cap);
     if (bo->text) pinned_put(bo->text, bo->text_cap);
-    if (bo->tsv) pinned_put(bo->tsv, bo->tsv_cap);
+    if (bo->out) pinned_put(bo->out, bo->out_cap);
     delete bo;
 }
 

@@ -23,6 +23,36 @@ static int proteins_distinct(const kaamer_proteins *p, std::vector<uint32_t> &un
     return kaamer_fetch_hits(p, uniq.data(), (uint32_t)uniq.size(), ent.data());
 }
 
+static_assert(TA_NONE == OUT_NONE, "one id map serves the alignment stage and the response writers");
+
+// a new map for the distinct ids of table p (uniq, ascending; map_n ids), on the device; NULL: *rc.  what: the attach, for
+// the error text
+static std::shared_ptr<IdMap> idmap_build(const kaamer_proteins *p, const std::vector<uint32_t> &uniq, uint64_t map_n, const char *what, int *rc)
+{
+    std::shared_ptr<IdMap> m(new (std::nothrow) IdMap());
+    if (!m) { *rc = kaamer_fail(KAAMER_E_NOMEM, "id map"); return nullptr; }
+    std::vector<uint32_t> host((size_t)map_n + 1, OUT_NONE);
+    for (size_t i = 0; i < uniq.size(); i++) host[uniq[i]] = (uint32_t)i;
+    *rc = reserve(m->d, host.size(), GROW_EXACT, nullptr);
+    if (*rc) return nullptr;
+    const hipError_t e = hipMemcpy(m->d, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { *rc = kaamer_fail(KAAMER_E_HIP, "%s upload: %s", what, hipGetErrorString(e)); return nullptr; }
+    m->n = (uint32_t)map_n; m->host = p; m->entries = (uint32_t)uniq.size();
+    return m;
+}
+
+// nothing of the index may be running when an attach changes: the slots' streams are idle when no slot is busy
+static int index_idle(kaamer_index *ix, const char *who)
+{
+    {
+        std::lock_guard<std::mutex> lock(ix->pool_mu);
+        for (int i = 0; i < ix->n_top; i++)
+            if (ix->top[i].busy) return kaamer_fail(KAAMER_E_BUSY, "%s: calls are in flight on the index", who);
+    }
+    HIPCHK(hipDeviceSynchronize());
+    return KAAMER_OK;
+}
+
 int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p)
 {
     if (!ix || !p) return kaamer_fail(KAAMER_E_ARG, "index_attach_proteins: bad argument");
@@ -37,10 +67,8 @@ int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p)
     std::vector<uint64_t> off((size_t)n + 1, 0);
     for (uint32_t i = 0; i < n; i++) off[i + 1] = off[i] + ent[i].sequence_len;
     std::vector<uint8_t> raw((size_t)off[n] + 1, 0), codes((size_t)off[n] + 1, 0), bad((size_t)n + 1, 0);
-    std::vector<uint32_t> idmap((size_t)map_n + 1, TA_NONE);
     uint32_t max_ns = 0;
     for (uint32_t i = 0; i < n; i++) {
-        idmap[uniq[i]] = i;
         if (ent[i].sequence_len > max_ns) max_ns = ent[i].sequence_len;
         for (uint32_t j = 0; j < ent[i].sequence_len; j++) {
             const int c = ent[i].sequence[j];
@@ -52,31 +80,26 @@ int kaamer_index_attach_proteins(kaamer_index *ix, const kaamer_proteins *p)
     }
     uint64_t st[3] = {0, 0, 0};
     kaamer_proteins_stats(p, st);
-    {   // nothing of the index may be running: the slots' streams are idle when no slot is busy
-        std::lock_guard<std::mutex> lock(ix->pool_mu);
-        for (int i = 0; i < ix->n_top; i++)
-            if (ix->top[i].busy) return kaamer_fail(KAAMER_E_BUSY, "index_attach_proteins: calls are in flight on the index");
-    }
-    HIPCHK(hipDeviceSynchronize());
+    rc = index_idle(ix, "index_attach_proteins");
+    if (rc) return rc;
     const uint64_t budget = ix->aln_budget;
     aln_table_free(ix);   // a second attach replaces the first
     ix->aln_budget = budget;
     rc = reserve_group(nullptr, GROW_EXACT, { want(ix->d_aln_raw, raw.size()), want(ix->d_aln_codes, codes.size()), want(ix->d_aln_bad, bad.size()),
-                                              want(ix->d_aln_off, off.size()), want(ix->d_aln_idmap, idmap.size()),
-                                              want(ix->d_aln_matrix, (size_t)ALN_NL * ALN_NL) });
+                                              want(ix->d_aln_off, off.size()), want(ix->d_aln_matrix, (size_t)ALN_NL * ALN_NL) });
+    if (!rc) ix->aln_idmap = idmap_build(p, uniq, map_n, "protein table", &rc);   // (always its own: the subject attaches take it over)
     if (rc) { aln_table_free(ix); return rc; }
     kaamer_align_matrix(ix->aln_matrix);
     hipError_t e = hipMemcpy(ix->d_aln_raw, raw.data(), raw.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_aln_codes, codes.data(), codes.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_aln_bad, bad.data(), bad.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_aln_off, off.data(), off.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ix->d_aln_idmap, idmap.data(), idmap.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(ix->d_aln_matrix, ix->aln_matrix, sizeof ix->aln_matrix, hipMemcpyHostToDevice);
     if (e != hipSuccess) { aln_table_free(ix); return kaamer_fail(KAAMER_E_HIP, "protein table upload: %s", hipGetErrorString(e)); }
     ix->aln_host = p;
-    ix->aln_idmap_n = (uint32_t)map_n; ix->aln_entries = n; ix->aln_max_ns = max_ns;
+    ix->aln_entries = n; ix->aln_max_ns = max_ns;
     ix->aln_number_of_aa = st[1];
-    ix->aln_bytes = raw.size() + codes.size() + bad.size() + off.size() * 8 + idmap.size() * 4 + sizeof ix->aln_matrix;
+    ix->aln_bytes = raw.size() + codes.size() + bad.size() + off.size() * 8 + ((size_t)map_n + 1) * 4 + sizeof ix->aln_matrix;
     return KAAMER_OK;
 }
 
@@ -183,7 +206,7 @@ static int ta_enqueue(kaamer_index *ix, kaamer_workspace *ws, const kaamer_topn_
     p.eoff = eoff;
     p.qraw = ws->nucleotide ? ws->d_orf_aa : ws->last_seqs;
     p.tab.raw = ix->d_aln_raw; p.tab.codes = ix->d_aln_codes; p.tab.off = ix->d_aln_off; p.tab.bad = ix->d_aln_bad;
-    p.tab.idmap = ix->d_aln_idmap; p.tab.idmap_n = ix->aln_idmap_n;
+    p.tab.idmap = ix->aln_idmap->d; p.tab.idmap_n = ix->aln_idmap->n;
     p.matrix = ix->d_aln_matrix;
     p.gap_open = gap_open; p.gap_extend = gap_extend;
     p.block = block; p.block_cap = block_cap; p.aln_cap = aln_cap; p.want_text = want_text ? 1 : 0;

@@ -1,5 +1,6 @@
 // json_rows.hip.inc — the JSON objects of the reported queries, written on the device (included by search.hip after
-// tsv_aln_rows.hip.inc; the host side is host_json.hip.inc, the contract and the host formatter are in json_format.cpp).
+// tsv_aln_rows.hip.inc; tiles, scans, counts and the scan kernel are out_rows.hip.inc's; the host side is host_json.hip.inc,
+// the contract and the host formatter are in json_format.cpp).
 //
 // json.Marshal(QueryResult) (search.go:497-503) needs what the TSV rows need plus the query's residues, the trim and every
 // hit's whole entry (kaamer_index_attach_subject_json: the HitEntries values, rendered on the host).  A row is short and a
@@ -11,28 +12,21 @@
 //   bitmaps    64 bits per step, funnelled out of two words (the trim moves the bit origin off the word boundary); lane i
 //              writes "true," or "false," at 6 i - popcount(bits below i)
 //   entries, literals   byte copies, 16 bytes per lane and step
-//   json_len_kernel    a workgroup per tile of JSON_TILE queries: the reported ones are listed, the waves take them in turn;
+//   json_len_kernel    a workgroup per tile of OUT_TILE queries: the reported ones are listed, the waves take them in turn;
 //                      json_object into a counting sink; the order of the query's keys (as decimal strings) is ranked here,
 //                      once, and kept for the write pass; lengths per query, sums per tile
-//   json_scan_kernel   one workgroup: the tiles' bytes and objects, scanned in 64 bits; the totals, the capacity check
+//   out_scan_kernel    (out_rows.hip.inc), one separator byte per object: the comma between two objects
 //   json_write_kernel  the same tiles and turns; json_object into a sink that builds the object in the wave's LDS buffer and
 //                      stores it in runs aligned to 16 bytes in the output, 16 bytes per lane, consecutive lanes consecutive
 //                      addresses; the bytes an object shares a 16-byte chunk with its neighbours in go out one by one
 // The same json_object serves both passes, so they cannot disagree about an object; should they ever, nothing is stored
 // beyond the object's counted end and the status word says so.
-#define JSON_TILE 256u
-#define JSON_WAVES (JSON_TILE / 64u)
+#define JSON_WAVES (OUT_TILE / 64u)
 #define JSON_WIN 4096u     /* bytes of a wave's LDS buffer */
 #define JSON_STEP 1024u    /* the most one step appends */
-enum { JSON_C_OBJECTS = 0, JSON_C_BYTES = 1, JSON_C_STATUS = 2, JSON_C_N = 4 };
-enum { JSON_ST_OUT_CAP = 1u, JSON_ST_OBJ_CAP = 2u, JSON_ST_UPSTREAM = 4u, JSON_ST_OBJECT = 8u /* an object of 4 GB */,
-       JSON_ST_MISMATCH = 16u /* the passes disagreed */ };
 #define JSON_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
-struct JsonParams {
-    // queries, hits, names, bitmaps (positions: they are printed), the block, the id map, tile sums (tile_lines: objects),
-    // line_off / line_cap (the objects' offsets), out / out_cap, counts (JSON_C_*): as the TSV rows name them
-    TsvParams t;
+struct JsonParams : OutParams {    // positions: the bitmaps are printed; a unit is an object
     const int32_t *trim;           // NULL: none
     const uint8_t *aa;             // what q[].aa_off indexes
     uint64_t aa_len;
@@ -115,7 +109,7 @@ struct JsonCount {
     static constexpr bool ORDERED = false;   // members of a map in any order: the count is the same (the order is not ranked yet)
     unsigned long long n = 0;
     __device__ __forceinline__ void lit(const char *, uint32_t len) { n += len; }
-    __device__ __forceinline__ void put_u32(uint32_t v) { n += tsv_digits(v); }
+    __device__ __forceinline__ void put_u32(uint32_t v) { n += out_digits(v); }
     __device__ __forceinline__ void copy(const uint8_t *, uint64_t len) { n += len; }
     __device__ __forceinline__ void escaped(const uint8_t *s, uint64_t len)
     {
@@ -179,7 +173,7 @@ struct JsonWrite {
     }
     __device__ __forceinline__ void put_u32(uint32_t v)
     {
-        const uint32_t at = room(), d = tsv_digits(v), lane = lane_id();
+        const uint32_t at = room(), d = out_digits(v), lane = lane_id();
         if (lane < d) {
             uint32_t div = 1;
             for (uint32_t k = lane + 1; k < d; k++) div *= 10u;
@@ -280,7 +274,7 @@ template <class Sink> __device__ __forceinline__ void json_put_bits(Sink &o, con
 // scaled to the other's digits: equal then means it is a prefix of the other
 __device__ __forceinline__ bool json_key_less(uint32_t a, uint32_t b)
 {
-    const uint32_t da = tsv_digits(a), db = tsv_digits(b);
+    const uint32_t da = out_digits(a), db = out_digits(b);
     unsigned long long x = a, y = b;
     for (uint32_t k = da; k < db; k++) x *= 10ull;
     for (uint32_t k = db; k < da; k++) y *= 10ull;
@@ -290,7 +284,7 @@ __device__ __forceinline__ bool json_key_less(uint32_t a, uint32_t b)
 // order[q * K + k] = the hit of query q whose key is k-th; by the wave: a lane ranks a hit against all the others
 __device__ __forceinline__ void json_order(const JsonParams &p, uint64_t q, uint32_t cnt)
 {
-    const uint32_t *pid = p.t.top_pid + q * p.t.K;
+    const uint32_t *pid = p.top_pid + q * p.K;
     for (uint32_t r = lane_id(); r < cnt; r += 64u) {
         const uint32_t mine = pid[r];
         uint32_t rank = 0;
@@ -298,19 +292,19 @@ __device__ __forceinline__ void json_order(const JsonParams &p, uint64_t q, uint
             const uint32_t other = pid[j];
             rank += (other != mine ? json_key_less(other, mine) : j < r) ? 1u : 0u;
         }
-        p.order[q * p.t.K + rank] = (uint16_t)r;
+        p.order[q * p.K + rank] = (uint16_t)r;
     }
 }
 
 // the object of query q with its cnt reported hits
 template <class Sink> __device__ __forceinline__ void json_object(const JsonParams &p, Sink &o, uint64_t q, uint32_t cnt)
 {
-    const kaamer_query_meta m = p.t.q[q];
+    const kaamer_query_meta m = p.q[q];
     const uint8_t *name = nullptr;
     uint32_t name_len = 0;
-    if (m.src_seq < p.t.n_names) {
-        const kaamer_text_span sp = p.t.spans[m.src_seq];
-        if ((uint64_t)sp.name_off + sp.name_len <= p.t.names_len) { name = p.t.names + sp.name_off; name_len = sp.name_len; }
+    if (m.src_seq < p.n_names) {
+        const kaamer_text_span sp = p.spans[m.src_seq];
+        if ((uint64_t)sp.name_off + sp.name_len <= p.names_len) { name = p.names + sp.name_off; name_len = sp.name_len; }
     }
     int32_t trim = p.trim ? p.trim[q] : 0;
     if (trim < 0) trim = 0;
@@ -319,10 +313,10 @@ template <class Sink> __device__ __forceinline__ void json_object(const JsonPara
     JL(o, "\",\"Name\":\"");
     o.escaped(name, name_len);
     JL(o, "\",\"SizeInKmer\":");
-    json_put_i32(o, p.t.size_out[q]);
+    json_put_i32(o, p.size_out[q]);
     if (p.protein) JL(o, ",\"Type\":\"Protein Query\",\"Location\":{\"StartPosition\":");
     else JL(o, ",\"Type\":\"DNA Query\",\"Location\":{\"StartPosition\":");
-    json_put_i32(o, p.t.start_pos[q]);
+    json_put_i32(o, p.start_pos[q]);
     JL(o, ",\"EndPosition\":");
     json_put_i32(o, m.end_position);
     if (p.protein) JL(o, ",\"PlusStrand\":false,\"StartsAlternative\":null},\"Contig\":\"");
@@ -330,13 +324,13 @@ template <class Sink> __device__ __forceinline__ void json_object(const JsonPara
     else JL(o, ",\"PlusStrand\":false,\"StartsAlternative\":[]},\"Contig\":\"");
     if (!p.protein && p.fasta) o.escaped(name, name_len);
     JL(o, "\"},\"SearchResults\":{\"Counter\":{},\"Hits\":[");
-    const uint32_t *pid = p.t.top_pid + q * p.t.K, *km = p.t.top_km + q * p.t.K;
+    const uint32_t *pid = p.top_pid + q * p.K, *km = p.top_km + q * p.K;
     uint32_t found = cnt;   // FetchHitsInformation returns at the first id without an entry (search.go:461-463)
     for (uint32_t r = 0; r < cnt; r++) {
         if (r) JL(o, ",{\"Key\":");
         else JL(o, "{\"Key\":");
         const uint32_t id = pid[r];
-        if (found == cnt && tsv_entry(p.t, id) == TSV_NONE) found = r;
+        if (found == cnt && out_entry(p, id) == OUT_NONE) found = r;
         o.put_u32(id);
         JL(o, ",\"Kmatch\":");
         o.put_u32(km[r]);
@@ -344,9 +338,9 @@ template <class Sink> __device__ __forceinline__ void json_object(const JsonPara
               "\"QueryStart\":0,\"QueryEnd\":0,\"SubjectStart\":0,\"SubjectEnd\":0}}");
     }
     JL(o, "],\"PositionHits\":{");
-    const uint16_t *order = p.order + q * p.t.K;
-    if (p.t.positions) {
-        const int32_t n = p.t.pos_len[q];
+    const uint16_t *order = p.order + q * p.K;
+    if (p.positions) {
+        const int32_t n = p.pos_len[q];
         const uint32_t n_bits = n > 0 ? (uint32_t)n : 0u, words = (n_bits + 63u) >> 6;
         const uint32_t first = (uint32_t)trim < n_bits ? (uint32_t)trim : n_bits;   // dna.go:260-262
         bool any = false;
@@ -358,7 +352,7 @@ template <class Sink> __device__ __forceinline__ void json_object(const JsonPara
             any = true;
             o.put_u32(pid[r]);
             JL(o, "\":[");
-            json_put_bits(o, p.t.pos_bits + p.t.pos_base[q] + (uint64_t)r * words, n_bits, first);
+            json_put_bits(o, p.pos_bits + p.pos_base[q] + (uint64_t)r * words, n_bits, first);
             JL(o, "]");
         }
     }
@@ -372,7 +366,7 @@ template <class Sink> __device__ __forceinline__ void json_object(const JsonPara
         any = true;
         o.put_u32(pid[r]);
         JL(o, "\":");
-        const uint32_t ent = tsv_entry(p.t, pid[r]);
+        const uint32_t ent = out_entry(p, pid[r]);
         o.copy(p.sj_bytes + p.sj_off[ent], p.sj_len[ent]);
     }
     JL(o, "}}");
@@ -382,14 +376,14 @@ template <class Sink> __device__ __forceinline__ void json_object(const JsonPara
 // gets its own query's hit count and its rank among the reported ones, *total how many there are
 __device__ __forceinline__ uint32_t json_tile_list(const JsonParams &p, uint32_t nq, unsigned long long *sh, uint32_t *list, uint32_t *rank, uint32_t *total)
 {
-    const uint64_t q = (uint64_t)blockIdx.x * JSON_TILE + threadIdx.x;
+    const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
     uint32_t cnt = 0;
     if (q < nq) {
-        cnt = p.t.top_cnt[q];
-        if (cnt > p.t.K) cnt = p.t.K;
+        cnt = p.top_cnt[q];
+        if (cnt > p.K) cnt = p.K;
     }
     unsigned long long n = 0;
-    const unsigned long long incl = tsv_block_scan(cnt ? 1ull : 0ull, sh, &n);
+    const unsigned long long incl = out_block_scan(cnt ? 1ull : 0ull, sh, &n);
     if (cnt) list[incl - 1ull] = threadIdx.x;
     *rank = (uint32_t)incl - (cnt ? 1u : 0u);
     *total = (uint32_t)n;
@@ -397,99 +391,70 @@ __device__ __forceinline__ uint32_t json_tile_list(const JsonParams &p, uint32_t
     return cnt;
 }
 
-__global__ __launch_bounds__(JSON_TILE) void json_len_kernel(JsonParams p)
+__global__ __launch_bounds__(OUT_TILE) void json_len_kernel(JsonParams p)
 {
-    __shared__ unsigned long long sh[JSON_TILE];
-    __shared__ uint32_t list[JSON_TILE], lens[JSON_TILE];
-    const uint32_t nq = tsv_nq(p.t);
-    if ((uint64_t)blockIdx.x * JSON_TILE >= nq || !tsv_upstream(p.t)) return;
+    __shared__ unsigned long long sh[OUT_TILE];
+    __shared__ uint32_t list[OUT_TILE], lens[OUT_TILE];
+    const uint32_t nq = out_nq(p);
+    if ((uint64_t)blockIdx.x * OUT_TILE >= nq || !out_upstream(p)) return;
     uint32_t rank, total;
     (void)json_tile_list(p, nq, sh, list, &rank, &total);
     lens[threadIdx.x] = 0;
     __syncthreads();
     for (uint32_t i = threadIdx.x >> 6; i < total; i += JSON_WAVES) {
         const uint32_t t = list[i];
-        const uint64_t q = (uint64_t)blockIdx.x * JSON_TILE + t;
-        uint32_t cnt = p.t.top_cnt[q];
-        if (cnt > p.t.K) cnt = p.t.K;
+        const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + t;
+        uint32_t cnt = p.top_cnt[q];
+        if (cnt > p.K) cnt = p.K;
         JsonCount o;
         json_object(p, o, q, cnt);
         json_order(p, q, cnt);
         if (lane_id() == 0) {
-            if (o.n > 0xFFFFFFF0ull) { atomicOr(&p.t.counts[JSON_C_STATUS], (unsigned long long)JSON_ST_OBJECT); o.n = 0; }
+            if (o.n > 0xFFFFFFF0ull) { atomicOr(&p.counts[OUT_C_STATUS], (unsigned long long)OUT_ST_OBJECT); o.n = 0; }
             lens[t] = (uint32_t)o.n;
         }
     }
     __syncthreads();
-    const uint64_t q = (uint64_t)blockIdx.x * JSON_TILE + threadIdx.x;
+    const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
     if (q < nq) p.obj_len[q] = lens[threadIdx.x];
     unsigned long long bytes = 0;
-    (void)tsv_block_scan(lens[threadIdx.x], sh, &bytes);
-    if (threadIdx.x == 0) { p.t.tile_bytes[blockIdx.x] = bytes; p.t.tile_lines[blockIdx.x] = total; }
+    (void)out_block_scan(lens[threadIdx.x], sh, &bytes);
+    if (threadIdx.x == 0) { p.tile_bytes[blockIdx.x] = bytes; p.tile_units[blockIdx.x] = total; }
 }
 
-// one workgroup: exclusive scan of the tiles' two sums in place; totals (one comma between two objects) and status
-__global__ __launch_bounds__(JSON_TILE) void json_scan_kernel(JsonParams p)
+__global__ __launch_bounds__(OUT_TILE) void json_write_kernel(JsonParams p)
 {
-    __shared__ unsigned long long sh[JSON_TILE];
-    if (!tsv_upstream(p.t)) {
-        if (threadIdx.x == 0) { p.t.counts[JSON_C_OBJECTS] = 0; p.t.counts[JSON_C_BYTES] = 0; p.t.counts[JSON_C_STATUS] = JSON_ST_UPSTREAM; }
-        return;
-    }
-    const uint32_t nq = tsv_nq(p.t);
-    const uint32_t tiles = (nq + JSON_TILE - 1u) / JSON_TILE;
-    unsigned long long base_b = 0, base_l = 0;
-    for (uint32_t t0 = 0; t0 < tiles; t0 += JSON_TILE) {
-        const uint32_t t = t0 + threadIdx.x;
-        const unsigned long long b = t < tiles ? p.t.tile_bytes[t] : 0ull, l = t < tiles ? p.t.tile_lines[t] : 0ull;
-        unsigned long long tb = 0, tl = 0;
-        const unsigned long long ib = tsv_block_scan(b, sh, &tb), il = tsv_block_scan(l, sh, &tl);
-        if (t < tiles) { p.t.tile_bytes[t] = base_b + ib - b; p.t.tile_lines[t] = base_l + il - l; }
-        base_b += tb; base_l += tl;
-    }
-    if (threadIdx.x == 0) {
-        const unsigned long long bytes = base_b + (base_l ? base_l - 1ull : 0ull);
-        unsigned long long st = p.t.counts[JSON_C_STATUS];   // (the length pass may have set JSON_ST_OBJECT)
-        if (bytes > p.t.out_cap) st |= JSON_ST_OUT_CAP;
-        if (base_l + 1ull > p.t.line_cap) st |= JSON_ST_OBJ_CAP;
-        p.t.counts[JSON_C_OBJECTS] = base_l; p.t.counts[JSON_C_BYTES] = bytes; p.t.counts[JSON_C_STATUS] = st;
-        if (!st) p.t.line_off[base_l] = bytes;
-    }
-}
-
-__global__ __launch_bounds__(JSON_TILE) void json_write_kernel(JsonParams p)
-{
-    __shared__ unsigned long long sh[JSON_TILE], start[JSON_TILE];
-    __shared__ uint32_t list[JSON_TILE];
+    __shared__ unsigned long long sh[OUT_TILE], start[OUT_TILE];
+    __shared__ uint32_t list[OUT_TILE];
     __shared__ __attribute__((aligned(16))) char win[JSON_WAVES * JSON_WIN];
-    const uint32_t nq = tsv_nq(p.t);
-    if ((uint64_t)blockIdx.x * JSON_TILE >= nq) return;
-    if (p.t.counts[JSON_C_STATUS]) return;   // (uniform: written by the scan kernel before this one started)
-    (void)tsv_upstream(p.t);
+    const uint32_t nq = out_nq(p);
+    if ((uint64_t)blockIdx.x * OUT_TILE >= nq) return;
+    if (p.counts[OUT_C_STATUS]) return;   // (uniform: written by the scan kernel before this one started)
+    (void)out_upstream(p);
     uint32_t rank, total;
     const uint32_t my_cnt = json_tile_list(p, nq, sh, list, &rank, &total);
-    const uint64_t my_q = (uint64_t)blockIdx.x * JSON_TILE + threadIdx.x;
+    const uint64_t my_q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
     const unsigned long long my_len = my_q < nq ? p.obj_len[my_q] : 0ull;
     unsigned long long tile_bytes = 0;
-    const unsigned long long before = tsv_block_scan(my_len, sh, &tile_bytes) - my_len;
+    const unsigned long long before = out_block_scan(my_len, sh, &tile_bytes) - my_len;
     // object number r of the batch starts behind the r objects and the r commas in front of it
-    const unsigned long long first_obj = p.t.tile_lines[blockIdx.x];
+    const unsigned long long first_obj = p.tile_units[blockIdx.x];
     if (my_cnt) {
-        const unsigned long long at = p.t.tile_bytes[blockIdx.x] + before + first_obj + rank;
+        const unsigned long long at = p.tile_bytes[blockIdx.x] + before + first_obj + rank;
         start[rank] = at;
-        p.t.line_off[first_obj + rank] = at;
+        p.unit_off[first_obj + rank] = at;
     }
     __syncthreads();
     for (uint32_t i = threadIdx.x >> 6; i < total; i += JSON_WAVES) {
         const uint32_t t = list[i];
-        const uint64_t q = (uint64_t)blockIdx.x * JSON_TILE + t;
-        uint32_t cnt = p.t.top_cnt[q];
-        if (cnt > p.t.K) cnt = p.t.K;
+        const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + t;
+        uint32_t cnt = p.top_cnt[q];
+        if (cnt > p.K) cnt = p.K;
         const unsigned long long at = start[i], first = at - (first_obj + i ? 1ull : 0ull);
-        JsonWrite o = { win + (threadIdx.x >> 6) * JSON_WIN, p.t.out, first, first & ~15ull, first, at + p.obj_len[q] };
+        JsonWrite o = { win + (threadIdx.x >> 6) * JSON_WIN, p.out, first, first & ~15ull, first, at + p.obj_len[q] };
         if (first != at) JL(o, ",");
         json_object(p, o, q, cnt);
-        if (lane_id() == 0 && o.pos != o.end) atomicOr(&p.t.counts[JSON_C_STATUS], (unsigned long long)JSON_ST_MISMATCH);
+        if (lane_id() == 0 && o.pos != o.end) atomicOr(&p.counts[OUT_C_STATUS], (unsigned long long)OUT_ST_MISMATCH);
         o.flush(true);
     }
 }

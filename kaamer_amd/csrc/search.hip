@@ -26,6 +26,9 @@
 //   [positions pass]      PositionHits bitmaps when asked for
 //   [topn_kernel]         kaamer_topn_device: sortMapByValue order, SetBestStartCodon,
 //                         FilterResults (topn.hip.inc)
+//   [response text]       behind top-N: the TSV rows, the -aln TSV rows, the JSON objects (the shared
+//                         part in out_rows.hip.inc, then tsv_rows, tsv_aln_rows, json_rows.hip.inc; host
+//                         side: host_out, host_tsv, host_json, host_out_text.hip.inc)
 //
 // This is integer hashing/indexing: no MFMA.  The probe is bound by the memory system's
 // random-request rate (~51e9 requests/s on MI355X whatever the size up to 128 B,
@@ -164,7 +167,10 @@ static void bounds_grow(BatchBounds &b, uint64_t seq_bytes, uint32_t n_seqs, boo
     bounds_grow_positions(b);
 }
 
+struct kaamer_tsv_stage;
 struct kaamer_json_stage;
+// the response text a text call brings back with its result (host_out_text.hip.inc); 0: none
+enum OutFormat { OUT_PLAIN = 0, OUT_TSV = 1, OUT_JSON = 2, OUT_FORMATS = 3 };
 // one in-flight call of the pipelined host-buffer boundary (host_top.hip.inc)
 struct TopSlot {
     kaamer_workspace *ws = nullptr;
@@ -191,66 +197,62 @@ struct TopSlot {
     uint32_t inflater_blocks = 0;
     PinnedBuf<uint8_t> h_comp;
     DevBuf<uint8_t> d_comp;
-    // the calls that return TSV rows (host_tsv.hip.inc), allocated at the slot's first one: the stage and the rows' buffer.
-    // Both bounds start from what the previous call needed, plus a quarter.
+    // the calls that return response text (host_out_text.hip.inc), allocated at the slot's first one of a kind: the stages
+    // with the bounds they were created for, one output buffer (16 bytes more than the text may take), and per format
+    // (OutFormat) the bounds the next call starts from: what the previous one needed plus a quarter
     kaamer_tsv_stage *tsv = nullptr;
-    uint32_t tsv_queries = 0;       // the bounds the stage was created for
-    uint64_t tsv_lines = 0;
-    DevBuf<char> d_tsv;            // 16 bytes more than the rows may take
-    uint64_t tsv_guess_bytes = 0, tsv_guess_lines = 0;
-    // the calls that return JSON objects (host_json.hip.inc): the same, bytes and objects
     kaamer_json_stage *json = nullptr;
-    uint32_t json_queries = 0;
-    uint64_t json_objects = 0;
-    DevBuf<char> d_json;
-    uint64_t json_guess_bytes = 0, json_guess_objects = 0;
+    uint32_t stage_queries[OUT_FORMATS] = {};
+    uint64_t stage_units[OUT_FORMATS] = {};
+    DevBuf<char> d_out;
+    uint64_t guess_bytes[OUT_FORMATS] = {}, guess_units[OUT_FORMATS] = {};
     bool busy = false;
 };
 #define KAAMER_MAX_HOST_SLOTS 8
 static void top_slot_free(TopSlot &h);
+
+// protein id -> entry of an attached table (OUT_NONE, TA_NONE: no entry), dense.  The three attaches of one table share one
+// map: attach_proteins always builds its own, the subject text takes the alignment table's, the JSON entries the subject
+// text's or else the alignment table's -- when that attach holds the same table (host, entries) at that moment.  The buffer
+// goes with its last holder, so the last reference must be dropped with the index's device selected, as aln_table_free,
+// subject_free and kaamer_index_close arrange.
+struct IdMap {
+    DevBuf<uint32_t> d;
+    uint32_t n = 0;                              // ids the map covers
+    const kaamer_proteins *host = nullptr;       // the table it was built from (compared, never read)
+    uint32_t entries = 0;
+    bool serves(const kaamer_proteins *p, uint32_t n_entries, uint64_t map_n) const { return host == p && entries == n_entries && n == (uint32_t)map_n; }
+};
 
 // kaamer_index_attach_proteins: the device copy of the Protein.Sequence table next to the index (top_align.hip.inc)
 struct AlnTable {
     const kaamer_proteins *aln_host = nullptr;   // borrowed: the rows of a result with text read the subjects from it
     DevBuf<uint8_t> d_aln_raw, d_aln_codes, d_aln_bad;
     DevBuf<uint64_t> d_aln_off;
-    DevBuf<uint32_t> d_aln_idmap;
+    std::shared_ptr<IdMap> aln_idmap;
     DevBuf<int> d_aln_matrix;
-    uint32_t aln_idmap_n = 0, aln_entries = 0, aln_max_ns = 0;
+    uint32_t aln_entries = 0, aln_max_ns = 0;
     uint64_t aln_bytes = 0, aln_number_of_aa = 0;
     // the *_aln_tsv_flat calls (host_tsv.hip.inc): batches whose rows the host printed because a raw score lay outside the
     // stage's table; raw scores that table holds (0: all of TSV_ALN_RAW_N -- a smaller count is for tests of that path)
     uint64_t tsv_aln_host_batches = 0;
     uint32_t tsv_aln_raw_count = 0;
 };
-// kaamer_index_attach_subject_text: what a TSV row prints of a hit's entry (tsv_rows.hip.inc).  Entry i is
-// d_st_bytes[d_st_off[i], d_st_off[i + 1]): EntryId (d_st_idlen[i] bytes), then the annotation columns.  The id map is
-// borrowed from the alignment table when that holds the same table in the same entry order, else owned here.
-struct SubjectText {
-    DevBuf<uint8_t> d_st_bytes;
-    DevBuf<uint64_t> d_st_off;
-    DevBuf<uint32_t> d_st_idlen, d_st_length;
-    DevBuf<uint32_t> d_st_idmap_own;             // its own id map, or the alignment table's once that table is gone
-    const uint32_t *d_st_idmap = nullptr;        // the map in use: d_st_idmap_own, or AlnTable::d_aln_idmap
-    uint32_t st_idmap_n = 0, st_entries = 0, st_features = 0;
-    uint64_t st_bytes = 0, st_max_suffix = 0;
-    const kaamer_proteins *st_host = nullptr;    // the table it was made from (compared, never read: who may share the map)
-};
-// kaamer_index_attach_subject_json: what a JSON object prints of a hit's entry (json_rows.hip.inc).  Entry i is
-// d_sj_bytes[d_sj_off[i], + d_sj_len[i]), its HitEntries value, at a 16-byte boundary.  The id map is borrowed from the
-// subject text or the alignment table when one of them holds the same table, else owned here; a lender that goes hands
-// its map to the borrower (aln_table_free, subject_text_free).
-struct SubjectJson {
-    DevBuf<uint8_t> d_sj_bytes;
-    DevBuf<uint64_t> d_sj_off;
-    DevBuf<uint32_t> d_sj_len;
-    DevBuf<uint32_t> d_sj_idmap_own;
-    const uint32_t *d_sj_idmap = nullptr;
-    uint32_t sj_idmap_n = 0, sj_entries = 0;
-    uint64_t sj_bytes = 0, sj_max_entry = 0;
+// kaamer_index_attach_subject_text / _json: what a TSV row or a JSON object prints of a hit's entry (tsv_rows.hip.inc,
+// json_rows.hip.inc), rendered on the host (host_out.hip.inc).  Entry i is d_bytes[d_off[i], ...):
+//   text   up to d_off[i + 1]: EntryId (d_len[i] bytes), then the annotation columns; d_plen[i]: Protein.Length
+//   JSON   d_len[i] bytes at a 16-byte boundary: the entry's HitEntries value
+struct SubjectTable {
+    DevBuf<uint8_t> d_bytes;
+    DevBuf<uint64_t> d_off;
+    DevBuf<uint32_t> d_len, d_plen;
+    std::shared_ptr<IdMap> idmap;
+    uint32_t entries = 0, features = 0;
+    uint64_t table_bytes = 0, longest = 0;       // longest: the info calls' max_row_suffix / max_entry
 };
 
-struct kaamer_index : AlnTable, SubjectText, SubjectJson {
+struct kaamer_index : AlnTable {
+    SubjectTable st, sj;          // the subject text, the subject entries in JSON form
     int device;
     kh_image_header hdr;
     kh_bucket *d_buckets;         // raw: taken over from the device build, or uploaded from an image
@@ -712,6 +714,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
 #include "topn.hip.inc"
 #include "top_positions.hip.inc"
 #include "top_align.hip.inc"
+#include "out_rows.hip.inc"
 #include "tsv_rows.hip.inc"
 #include "tsv_aln_rows.hip.inc"
 #include "json_rows.hip.inc"
@@ -1129,23 +1132,10 @@ static SearchKnobs read_knobs()
 }
 
 // the attached Protein.Sequence table goes (kaamer_index_attach_proteins, kaamer_index_close; the device is selected)
-static void aln_table_free(kaamer_index *ix)
-{
-    // (a subject text that borrows the id map takes it over: it is the owner from here on)
-    if (ix->d_aln_idmap && ix->d_st_idmap == ix->d_aln_idmap) ix->d_st_idmap_own = std::move(ix->d_aln_idmap);
-    else if (ix->d_aln_idmap && ix->d_sj_idmap == ix->d_aln_idmap) ix->d_sj_idmap_own = std::move(ix->d_aln_idmap);
-    static_cast<AlnTable &>(*ix) = AlnTable();
-}
+static void aln_table_free(kaamer_index *ix) { static_cast<AlnTable &>(*ix) = AlnTable(); }
 
-// ... and the attached subject text (kaamer_index_attach_subject_text)
-static void subject_text_free(kaamer_index *ix)
-{
-    if (ix->d_st_idmap_own && ix->d_sj_idmap == ix->d_st_idmap_own) ix->d_sj_idmap_own = std::move(ix->d_st_idmap_own);
-    static_cast<SubjectText &>(*ix) = SubjectText();
-}
-
-// ... and the attached subject entries in JSON form (kaamer_index_attach_subject_json)
-static void subject_json_free(kaamer_index *ix) { static_cast<SubjectJson &>(*ix) = SubjectJson(); }
+// ... and an attached subject table (ix->st, ix->sj)
+static void subject_free(SubjectTable &t) { t = SubjectTable(); }
 
 #include "parse_text.hip.inc"
 #include "parse_fasta.hip.inc"
@@ -2439,8 +2429,10 @@ int kaamer_search_batch(kaamer_index *ix, const kaamer_batch_in *in, kaamer_batc
 #include "host_top.hip.inc"
 #include "host_top_align.hip.inc"
 #include "host_text.hip.inc"
+#include "host_out.hip.inc"
 #include "host_tsv.hip.inc"
 #include "host_json.hip.inc"
+#include "host_out_text.hip.inc"
 #include "host_sharded.hip.inc"
 #include "host_sharded_submit.hip.inc"
 #include "host_sharded_collect.hip.inc"

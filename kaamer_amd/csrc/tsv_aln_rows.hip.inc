@@ -1,5 +1,5 @@
 // tsv_aln_rows.hip.inc — the -aln TSV rows of the reported hits, written on the device (included by search.hip after
-// tsv_rows.hip.inc, whose sinks, scans, tile and window machinery and scan kernel it uses; the host side is in
+// tsv_rows.hip.inc: the row form TsvAln for that file's passes, over its sinks, row head and row tail; the host side is in
 // host_tsv.hip.inc, the contract and the host formatter in tsv_format.cpp, the two number formats in fmt_double.h).
 //
 // QueryResultHandler aligns every reported hit, sorts a query's hits by BitScore and prints a row per hit
@@ -9,9 +9,8 @@
 //   tsv_aln_order_kernel   a lane per query: the order of its hits by BitScore descending, stable (insertion: a query has
 //                          at most max_results hits), kept as order[q * K + row] = hit; counts the pairs whose raw score lies
 //                          outside the table (the batch is then the host formatter's: nothing of the rows is to be read)
-//   tsv_aln_len_kernel, tsv_scan_kernel (tsv_rows.hip.inc), tsv_aln_off_kernel, tsv_aln_write_kernel
-//                          the four passes of the plain rows over tsv_aln_row; the -aln row has kernels of its own (two row
-//                          bodies in one kernel cost scratch there)
+//   tsv_len_kernel<TsvAln>, out_scan_kernel, tsv_off_kernel<TsvAln>, tsv_write_kernel<TsvAln>
+//                          the four passes of the rows (tsv_rows.hip.inc) over this form
 //
 // Floats.  Identity is float32(identical) / float32(columns) * 100, each step IEEE-rounded.  BitScore is a function of the
 // raw score alone and EValue = len(query) * NumberOfAA / 2^BitScore: the device's pow is not the host's, so BitScore and
@@ -19,7 +18,7 @@
 // (lambda, K); the product and the quotient are IEEE-rounded here as they are there.
 // Numbers.  "%.2f" of Identity and BitScore is 64-bit integer arithmetic (the table holds no BitScore of 2^63 or more);
 // "%e" of EValue is exact for every double (fmt_double.h), its limbs in LDS, limb-major: lane t's limb i is word
-// i * TSV_TILE + t, consecutive lanes in consecutive banks.
+// i * OUT_TILE + t, consecutive lanes in consecutive banks.
 #include "fmt_double.h"
 
 // The raw score is the reference's own tally with the request's gap penalties over an alignment made with the aligner's
@@ -27,8 +26,7 @@
 #define TSV_ALN_RAW_N (1u << 17)    /* raw scores the table holds: [TSV_ALN_RAW_MIN, TSV_ALN_RAW_MIN + TSV_ALN_RAW_N) */
 #define TSV_ALN_RAW_MIN (-65536)
 
-struct TsvAlnParams {
-    TsvParams base;                // top_km and size_out are not read
+struct TsvAlnParams : TsvParams {    // top_km and size_out are not read
     const uint64_t *pair_off;      // kaamer_topn_alignments
     const kaamer_align_pair *pairs;
     uint64_t pair_cap;
@@ -47,8 +45,8 @@ struct TsvAlnParams {
 // a lane's limbs in LDS
 struct TsvLimbs {
     uint32_t *base;
-    __device__ __forceinline__ uint32_t get(uint32_t i) const { return base[i * TSV_TILE]; }
-    __device__ __forceinline__ void set(uint32_t i, uint32_t v) { base[i * TSV_TILE] = v; }
+    __device__ __forceinline__ uint32_t get(uint32_t i) const { return base[i * OUT_TILE]; }
+    __device__ __forceinline__ void set(uint32_t i, uint32_t v) { base[i * OUT_TILE] = v; }
 };
 
 // Every thread computes the same: where the pair records are.
@@ -98,19 +96,19 @@ __device__ __forceinline__ double tsv_aln_bits(const TsvAlnParams &p, uint64_t q
 __device__ __forceinline__ uint32_t tsv_aln_cnt(const TsvAlnParams &p, uint64_t q, uint32_t nq)
 {
     if (q >= nq) return 0u;
-    uint32_t cnt = p.base.top_cnt[q];
-    if (cnt > p.base.K) cnt = p.base.K;
+    uint32_t cnt = p.top_cnt[q];
+    if (cnt > p.K) cnt = p.K;
     return p.unaligned || p.pair_off[q] + cnt <= p.pair_cap ? cnt : 0u;
 }
 
-__global__ __launch_bounds__(TSV_TILE) void tsv_aln_order_kernel(TsvAlnParams p)
+__global__ __launch_bounds__(OUT_TILE) void tsv_aln_order_kernel(TsvAlnParams p)
 {
     tsv_aln_setup(p);
-    const uint32_t nq = tsv_nq(p.base);
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
+    const uint32_t nq = out_nq(p);
+    const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
     const uint32_t cnt = tsv_aln_cnt(p, q, nq);
     if (!cnt) return;
-    uint16_t *order = p.order + q * p.base.K;
+    uint16_t *order = p.order + q * p.K;
     uint32_t outside = 0;
     for (uint32_t r = 0; r < cnt; r++) {
         outside += tsv_aln_in_table(p, tsv_aln_pair(p, q, r)) ? 0u : 1u;
@@ -123,26 +121,14 @@ __global__ __launch_bounds__(TSV_TILE) void tsv_aln_order_kernel(TsvAlnParams p)
         }
         order[j] = (uint16_t)r;
     }
-    if (outside) atomicAdd(&p.base.counts[TSV_C_RAW], (unsigned long long)outside);
+    if (outside) atomicAdd(&p.counts[OUT_C_RAW], (unsigned long long)outside);
 }
 
-// a row of query q: hit h = order[row] of its reported hits; ent: the hit's entry or TSV_NONE (tsv_aln_entry)
+// a row of query q: hit h = order[row] of its reported hits; ent: the hit's entry or OUT_NONE (tsv_aln_entry)
 template <class Sink> __device__ __forceinline__ void tsv_aln_row(const TsvAlnParams &p, Sink &o, uint32_t q, uint32_t h, uint32_t ent, TsvLimbs &X)
 {
-    const TsvParams &b = p.base;
-    const kaamer_query_meta m = b.q[q];
-    if (m.src_seq < b.n_names) {   // strings.Split(Query.Name, " ")[0]
-        const kaamer_text_span sp = b.spans[m.src_seq];
-        if ((uint64_t)sp.name_off + sp.name_len <= b.names_len) {
-            const uint8_t *name = b.names + sp.name_off;
-            o.copy(name, tsv_query_id_len(name, sp.name_len));
-        }
-    }
-    o.put('\t');
-    const uint64_t s0 = ent != TSV_NONE ? b.st_off[ent] : 0, s1 = ent != TSV_NONE ? b.st_off[ent + 1] : 0;
-    const uint32_t idlen = ent != TSV_NONE ? b.st_idlen[ent] : 0;
-    o.copy(b.st_bytes + s0, idlen);
-    o.put('\t');
+    const kaamer_query_meta m = p.q[q];
+    const TsvEntry e = tsv_row_head(p, o, m, ent);
     const kaamer_align_pair it = tsv_aln_pair(p, q, h);
     const bool ok = it.status == 0;                 // else the empty AlignmentResult: zeros
     const bool cols = ok && it.n_ops != 0;
@@ -155,7 +141,7 @@ template <class Sink> __device__ __forceinline__ void tsv_aln_row(const TsvAlnPa
     o.put('\t');
     tsv_put_i32(o, ok ? it.gap_openings : 0);
     o.put('\t');
-    tsv_put_i32(o, p.protein ? (cols ? it.start_i + 1 : (ok ? 1 : 0)) : b.start_pos[q]);   // align.go:153-156
+    tsv_put_i32(o, p.protein ? (cols ? it.start_i + 1 : (ok ? 1 : 0)) : p.start_pos[q]);   // align.go:153-156
     o.put('\t');
     tsv_put_i32(o, p.protein ? (cols ? it.end_i : 0) : m.end_position);
     o.put('\t');
@@ -170,17 +156,7 @@ template <class Sink> __device__ __forceinline__ void tsv_aln_row(const TsvAlnPa
     kfmt_exp6(o, evalue, X);
     o.put('\t');
     (void)kfmt_fixed2_small(o, bits);
-    if (b.positions) {
-        const int32_t n = b.pos_len[q];
-        const uint32_t n_bits = n > 0 ? (uint32_t)n : 0u;
-        o.put('\t');
-        tsv_put_positions_add<(uint32_t)KAAMER_KMER_SIZE - 1u>(o, b.pos_bits + b.pos_base[q] + (uint64_t)h * ((n_bits + 63u) >> 6), n_bits);
-    }
-    if (b.annotations) {
-        if (ent != TSV_NONE) o.copy(b.st_bytes + s0 + idlen, s1 - s0 - idlen);
-        else o.fill('\t', b.n_features);
-    }
-    o.put('\n');
+    tsv_row_tail<(uint32_t)KAAMER_KMER_SIZE - 1u>(p, o, q, h, ent, e);   // FormatPositionsToString(bitmap, true)
 }
 
 // The entry of hit h of query q.  FetchHitsInformation stops at a missing id BEFORE the sort (search.go:461-463): the hits
@@ -190,101 +166,32 @@ template <class Sink> __device__ __forceinline__ void tsv_aln_row(const TsvAlnPa
 __device__ __forceinline__ uint32_t tsv_aln_entry(const TsvAlnParams &p, uint64_t q, uint32_t h, bool gone)
 {
     const int32_t status = p.unaligned ? 1 : p.pairs[p.pair_off[q] + h].status;
-    if (status == 4 || (gone && status == 1)) return TSV_NONE;
-    return tsv_entry(p.base, p.base.top_pid[q * p.base.K + h]);
+    if (status == 4 || (gone && status == 1)) return OUT_NONE;
+    return out_entry(p, p.top_pid[q * p.K + h]);
 }
 
-__global__ __launch_bounds__(TSV_TILE) void tsv_aln_len_kernel(TsvAlnParams p)
-{
-    __shared__ unsigned long long sh[TSV_TILE];
-    __shared__ uint32_t limbs[KFMT_LIMBS * TSV_TILE];
-    tsv_aln_setup(p);
-    const uint32_t nq = tsv_nq(p.base);
-    if ((uint64_t)blockIdx.x * TSV_TILE >= nq || !tsv_upstream(p.base)) return;
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
-    const uint32_t cnt = tsv_aln_cnt(p, q, nq);
-    TsvLimbs X = { limbs + threadIdx.x };
-    TsvCount o;
-    bool gone = false;
-    for (uint32_t r = 0; r < cnt; r++) {
-        const uint32_t h = p.order[q * p.base.K + r];
+// the -aln rows as a form of the passes in tsv_rows.hip.inc: the hits in BitScore order, the write passes return on a raw
+// score outside the table too
+struct TsvAln {
+    using Params = TsvAlnParams;
+    struct Lds { uint32_t limbs[KFMT_LIMBS * OUT_TILE]; };
+    using Lane = TsvLimbs;
+    static __device__ __forceinline__ void setup(Params &p) { tsv_aln_setup(p); }
+    static __device__ __forceinline__ Lane lane(Lds &lds) { return Lane{ lds.limbs + threadIdx.x }; }
+    static __device__ __forceinline__ uint32_t count(const Params &p, uint64_t q, uint32_t nq) { return tsv_aln_cnt(p, q, nq); }
+    static __device__ __forceinline__ uint32_t hit(const Params &p, uint64_t q, uint32_t r) { return p.order[q * p.K + r]; }
+    static __device__ __forceinline__ uint32_t entry(const Params &p, uint64_t q, uint32_t h, bool &gone)
+    {
         const uint32_t ent = tsv_aln_entry(p, q, h, gone);
-        gone = gone || ent == TSV_NONE;
-        tsv_aln_row(p, o, (uint32_t)q, h, ent, X);
+        gone = gone || ent == OUT_NONE;
+        return ent;
     }
-    unsigned long long bytes = 0, lines = 0;
-    (void)tsv_block_scan(o.n, sh, &bytes);
-    (void)tsv_block_scan(cnt, sh, &lines);
-    if (threadIdx.x == 0) { p.base.tile_bytes[blockIdx.x] = bytes; p.base.tile_lines[blockIdx.x] = lines; }
-}
-
-__global__ __launch_bounds__(TSV_TILE) void tsv_aln_off_kernel(TsvAlnParams p)
-{
-    __shared__ unsigned long long sh[TSV_TILE];
-    __shared__ uint32_t limbs[KFMT_LIMBS * TSV_TILE];
-    tsv_aln_setup(p);
-    const uint32_t nq = tsv_nq(p.base);
-    if ((uint64_t)blockIdx.x * TSV_TILE >= nq) return;
-    if (p.base.counts[TSV_C_STATUS] || p.base.counts[TSV_C_RAW]) return;   // (uniform: written before this kernel started)
-    (void)tsv_upstream(p.base);
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
-    const uint32_t cnt = tsv_aln_cnt(p, q, nq);
-    TsvLimbs X = { limbs + threadIdx.x };
-    unsigned long long tile_total = 0;
-    const unsigned long long e0 = p.base.tile_lines[blockIdx.x] + tsv_block_scan(cnt, sh, &tile_total) - cnt;
-    unsigned long long mine = 0;
-    bool gone = false;
-    for (uint32_t r = 0; r < cnt; r++) {
-        const uint32_t h = p.order[q * p.base.K + r];
-        const uint32_t ent = tsv_aln_entry(p, q, h, gone);
-        gone = gone || ent == TSV_NONE;
-        TsvCount o;
-        tsv_aln_row(p, o, (uint32_t)q, h, ent, X);
-        p.base.line_off[e0 + r] = mine;   // relative to the query's first byte for now
-        mine += o.n;
+    static __device__ __forceinline__ bool refused(const Params &p) { return p.counts[OUT_C_STATUS] || p.counts[OUT_C_RAW]; }
+    template <class Sink> static __device__ __forceinline__ void row(const Params &p, Sink &o, uint32_t q, uint32_t h, uint32_t ent, Lane &X)
+    {
+        tsv_aln_row(p, o, q, h, ent, X);
     }
-    const unsigned long long q0 = p.base.tile_bytes[blockIdx.x] + tsv_block_scan(mine, sh, &tile_total) - mine;
-    for (uint32_t r = 0; r < cnt; r++) p.base.line_off[e0 + r] += q0;
-}
-
-__global__ __launch_bounds__(TSV_TILE) void tsv_aln_write_kernel(TsvAlnParams p)
-{
-    __shared__ unsigned long long sh[TSV_TILE];
-    __shared__ uint32_t limbs[KFMT_LIMBS * TSV_TILE];
-    __shared__ __attribute__((aligned(16))) char win[TSV_WINDOW];
-    tsv_aln_setup(p);
-    const uint32_t nq = tsv_nq(p.base);
-    if ((uint64_t)blockIdx.x * TSV_TILE >= nq) return;
-    if (p.base.counts[TSV_C_STATUS] || p.base.counts[TSV_C_RAW]) return;   // (uniform: written before this kernel started)
-    (void)tsv_upstream(p.base);
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
-    const uint32_t cnt = tsv_aln_cnt(p, q, nq);
-    TsvLimbs X = { limbs + threadIdx.x };
-    unsigned long long tile_total = 0;
-    const unsigned long long e0 = p.base.tile_lines[blockIdx.x] + tsv_block_scan(cnt, sh, &tile_total) - cnt;
-    // the tile's rows are [b0, b1) of the output; line_off[lines] is the total, so every row's end is the next entry
-    const unsigned long long b0 = p.base.tile_bytes[blockIdx.x], b1 = p.base.line_off[p.base.tile_lines[blockIdx.x] + tile_total];
-    const unsigned long long q0 = cnt ? p.base.line_off[e0] : 0ull, q1 = cnt ? p.base.line_off[e0 + cnt] : 0ull;
-    for (unsigned long long w = b0 - b0 % TSV_WINDOW; w < b1; w += TSV_WINDOW) {
-        const unsigned long long lo = w > b0 ? w : b0, hi = w + TSV_WINDOW < b1 ? w + TSV_WINDOW : b1;
-        if (q0 < hi && q1 > lo) {
-            bool gone = false;
-            for (uint32_t r = 0; r < cnt; r++) {
-                const uint32_t h = p.order[q * p.base.K + r];
-                const uint32_t ent = tsv_aln_entry(p, q, h, gone);
-                gone = gone || ent == TSV_NONE;
-                const unsigned long long s = p.base.line_off[e0 + r], e = p.base.line_off[e0 + r + 1];
-                if (e <= lo) continue;
-                if (s >= hi) break;
-                TsvWindow o = { win, s, w, lo, hi };
-                tsv_aln_row(p, o, (uint32_t)q, h, ent, X);
-            }
-        }
-        __syncthreads();
-        tsv_store_window(p.base.out, win, w, lo, hi);
-        __syncthreads();
-    }
-}
+};
 
 // kaamer_tsv_format_doubles_device: a lane per value, its text into a 32-byte slot (NUL-padded; a longer text is cut at 31
 // bytes) through the device functions the rows use
@@ -294,10 +201,10 @@ struct TsvSlot {
     __device__ __forceinline__ void put(char c) { if (n < 31u) p[n] = c; n++; }
 };
 
-__global__ __launch_bounds__(TSV_TILE) void tsv_format_doubles_kernel(const double *values, uint64_t n, int mode, char *out)
+__global__ __launch_bounds__(OUT_TILE) void tsv_format_doubles_kernel(const double *values, uint64_t n, int mode, char *out)
 {
-    __shared__ uint32_t limbs[KFMT_LIMBS * TSV_TILE];
-    const uint64_t i = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
+    __shared__ uint32_t limbs[KFMT_LIMBS * OUT_TILE];
+    const uint64_t i = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
     if (i >= n) return;
     TsvLimbs X = { limbs + threadIdx.x };
     TsvSlot o = { out + i * 32ull, 0u };

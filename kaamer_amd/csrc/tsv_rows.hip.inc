@@ -1,72 +1,46 @@
 // tsv_rows.hip.inc — the TSV response rows of the reported hits, written on the device (included by search.hip after
-// top_align.hip.inc; the host side is host_tsv.hip.inc, the contract and the host formatter are in tsv_format.cpp).
+// out_rows.hip.inc, whose tiles, scans, scan kernel and window store it uses; the -aln rows are tsv_aln_rows.hip.inc, the host
+// side is host_tsv.hip.inc, the contract and the host formatter are in tsv_format.cpp).
 //
 // QueryResultHandler builds a row with `output += ...` per field (search.go:505-554).  Behind kaamer_topn_device all a row
 // needs is resident: the text with the records' name spans, the reported hits, SizeInKmer / StartPosition after
 // SetBestStartCodon, the bitmaps of the reported hits and the subject text (kaamer_index_attach_subject_text).
 //
-//   tsv_len_kernel     a lane per query: the bytes of its rows (tsv_row into a counting sink: digits, field lengths, for
-//                      field 11 the runs of the bitmap words), summed per tile of TSV_TILE queries
-//   tsv_scan_kernel    one workgroup: the tiles' bytes and rows, scanned in 64 bits; the totals, the capacity check
-//   tsv_off_kernel     a workgroup per tile, a lane per query: the first byte of every row (line_off, in CSR order), from the
+// The passes are written once, over a row FORM (TsvPlain here, TsvAln in tsv_aln_rows.hip.inc); every instantiation is a
+// kernel of its own:
+//   tsv_len_kernel     a lane per query: the bytes of its rows (the form's row into a counting sink: digits, field lengths,
+//                      the runs of the bitmap words), summed per tile of OUT_TILE queries
+//   out_scan_kernel    (out_rows.hip.inc)
+//   tsv_off_kernel     a workgroup per tile, a lane per query: the first byte of every row (unit_off, in CSR order), from the
 //                      tiles' prefixes, a scan inside the tile and the rows' lengths once more (nothing per row is kept
 //                      between the passes: a batch has up to max_results rows per query, nearly all of them absent)
 //   tsv_write_kernel   a workgroup per tile, a lane per query.  The rows of a tile are one contiguous byte range of the
 //                      output.  Rows are short, many and uneven, and names, ids and annotation values are byte copies at
 //                      arbitrary alignment, so no lane writes a row to memory itself: the workgroup builds the range in LDS,
 //                      TSV_WINDOW bytes at a time (windows lie on multiples of TSV_WINDOW in the output), every lane putting
-//                      the part of its rows that falls into the window (tsv_row into a clipping sink), and then stores the
+//                      the part of its rows that falls into the window (the row into a clipping sink), and then stores the
 //                      window with 16 bytes per lane, consecutive lanes at consecutive addresses.  Only the first and the last
 //                      16 bytes of a tile's range, which it may share with its neighbours, go out as single bytes.
-// The same tsv_row serves the length passes and the write pass, so they cannot disagree about a row.  (Two kernels instead
-// of one behind the scan: with both instances of tsv_row in one kernel the compiler needed scratch memory for scalar
-// registers; apart they need none.)
-// Nothing is written beyond out_cap or line_cap: the scan kernel sets the status word and the write kernel returns.
-#define TSV_TILE 256u
+// The same row body serves the length passes and the write pass, so they cannot disagree about a row.  (Two kernels instead
+// of one behind the scan, and a kernel per form: with two row bodies in one kernel the compiler needed scratch memory for
+// scalar registers; apart they need none.)
+// Nothing is written beyond out_cap or unit_cap: the scan kernel sets the status word and the write kernel returns.
+//
+// A form supplies: Params (a TsvParams) and setup(p) (what every thread derives from it first); Lds and Lane, the form's
+// per-workgroup LDS and a lane's handle on it; count(p, q, nq), the rows of a query; hit(p, q, r), the hit printed r-th;
+// entry(p, q, h, gone), the hit's entry under the missing-entry rule, with `gone` carried from row to row; refused(p),
+// whether the write passes return; row(p, o, q, h, ent, X), the row itself.
 #define TSV_WINDOW 16384u
-#define TSV_NONE 0xFFFFFFFFu
-enum { TSV_C_LINES = 0, TSV_C_BYTES = 1, TSV_C_STATUS = 2, TSV_C_RAW = 3 /* tsv_aln_rows.hip.inc */, TSV_C_N = 4 };
-enum { TSV_ST_OUT_CAP = 1u, TSV_ST_LINE_CAP = 2u, TSV_ST_UPSTREAM = 4u /* the batch's own status, or no bitmaps in its block */ };
 
-struct TsvParams {
-    const uint32_t *d_nq;
-    uint32_t nq_cap;
-    const kaamer_query_meta *q;
-    const uint32_t *top_cnt, *top_pid, *top_km;
-    const int32_t *start_pos, *size_out;
-    uint32_t K;
-    const uint8_t *names;
-    uint64_t names_len;
-    const kaamer_text_span *spans;
-    uint32_t n_names;
-    const uint64_t *pos_base;      // the three of kaamer_topn_positions; NULL unless positions
-    const int32_t *pos_len;
-    const uint64_t *pos_bits;
-    int positions, annotations;
-    // the host-buffer calls: the packed result block of the same batch (topn.hip.inc).  A block whose status word is set is
-    // refused by the host whatever follows, so the stage writes nothing; with positions the bitmaps are the block's section
-    // (top_positions.hip.inc: per query at pos_base[q], as in the workspace's own storage)
-    const uint8_t *block;
-    // the subject text: entry i is st_bytes[st_off[i], st_off[i + 1]), its first st_idlen[i] bytes the EntryId, the rest the
-    // annotation columns ('\t' + value each)
+// the rows' own: the subject text.  Entry i is st_bytes[st_off[i], st_off[i + 1]), its first st_idlen[i] bytes the EntryId,
+// the rest the annotation columns ('\t' + value each)
+struct TsvParams : OutParams {
+    int annotations;
     const uint8_t *st_bytes;
     const uint64_t *st_off;
-    const uint32_t *st_idlen, *st_length, *idmap;
-    uint32_t idmap_n, n_features;
-    // the stage's own
-    unsigned long long *tile_bytes, *tile_lines;   // per tile: sums, then exclusive prefixes
-    unsigned long long *line_off;
-    uint64_t line_cap;
-    char *out;
-    uint64_t out_cap;
-    unsigned long long *counts;    // TSV_C_*
+    const uint32_t *st_idlen, *st_length;
+    uint32_t n_features;
 };
-
-__device__ __forceinline__ uint32_t tsv_digits(uint32_t v)
-{
-    return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u
-         : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
-}
 
 // counts the bytes of a row
 struct TsvCount {
@@ -74,7 +48,7 @@ struct TsvCount {
     __device__ __forceinline__ void put(char) { n++; }
     __device__ __forceinline__ void copy(const uint8_t *, uint64_t len) { n += len; }
     __device__ __forceinline__ void fill(char, uint32_t len) { n += len; }
-    __device__ __forceinline__ void put_u32(uint32_t v) { n += tsv_digits(v); }
+    __device__ __forceinline__ void put_u32(uint32_t v) { n += out_digits(v); }
 };
 
 // puts the bytes of a row that fall into [lo, hi) of the output into the LDS window that starts at `w`
@@ -109,7 +83,7 @@ struct TsvWindow {
     __device__ __forceinline__ void put_u32(uint32_t v)
     {
         uint32_t div = 1;
-        for (uint32_t d = tsv_digits(v); d > 1; d--) div *= 10u;
+        for (uint32_t d = out_digits(v); d > 1; d--) div *= 10u;
         for (; div; div /= 10u) { put((char)('0' + v / div)); v %= div; }
     }
 };
@@ -207,12 +181,6 @@ template <class Sink> __device__ __forceinline__ void tsv_put_positions(Sink &o,
     tsv_put_positions_add<0u>(o, bits, n);
 }
 
-// the id -> entry map, as kaamer_fetch_hits resolves an id
-__device__ __forceinline__ uint32_t tsv_entry(const TsvParams &p, uint32_t pid)
-{
-    return pid < p.idmap_n ? p.idmap[pid] : TSV_NONE;
-}
-
 // the bytes of a name before its first 0x20
 __device__ __forceinline__ uint32_t tsv_query_id_len(const uint8_t *name, uint32_t name_len)
 {
@@ -234,11 +202,18 @@ __device__ __forceinline__ uint32_t tsv_query_id_len(const uint8_t *name, uint32
     return len;
 }
 
-// row r of query q; ent: the hit's entry, TSV_NONE from the query's first missing entry on
-template <class Sink> __device__ __forceinline__ void tsv_row(const TsvParams &p, Sink &o, uint32_t q, uint32_t r, uint32_t ent)
+
+// where an entry's bytes are; OUT_NONE: nowhere, every length 0
+struct TsvEntry {
+    uint64_t s0, s1;
+    uint32_t idlen;
+};
+
+// the head of a row of either form: the query's id (strings.Split(Query.Name, " ")[0]) and the hit's EntryId, a tab behind
+// each -> where the entry's bytes are, for the tail
+template <class Sink> __device__ __forceinline__ TsvEntry tsv_row_head(const TsvParams &p, Sink &o, const kaamer_query_meta &m, uint32_t ent)
 {
-    const kaamer_query_meta m = p.q[q];
-    if (m.src_seq < p.n_names) {   // strings.Split(Query.Name, " ")[0]
+    if (m.src_seq < p.n_names) {
         const kaamer_text_span sp = p.spans[m.src_seq];
         if ((uint64_t)sp.name_off + sp.name_len <= p.names_len) {
             const uint8_t *name = p.names + sp.name_off;
@@ -246,220 +221,179 @@ template <class Sink> __device__ __forceinline__ void tsv_row(const TsvParams &p
         }
     }
     o.put('\t');
-    const uint64_t s0 = ent != TSV_NONE ? p.st_off[ent] : 0, s1 = ent != TSV_NONE ? p.st_off[ent + 1] : 0;
-    const uint32_t idlen = ent != TSV_NONE ? p.st_idlen[ent] : 0;
-    o.copy(p.st_bytes + s0, idlen);
+    TsvEntry e;
+    e.s0 = ent != OUT_NONE ? p.st_off[ent] : 0; e.s1 = ent != OUT_NONE ? p.st_off[ent + 1] : 0;
+    e.idlen = ent != OUT_NONE ? p.st_idlen[ent] : 0;
+    o.copy(p.st_bytes + e.s0, e.idlen);
     o.put('\t');
-    const uint32_t km = p.top_km[(uint64_t)q * p.K + r];
-    const int32_t size = p.size_out[q];
-    tsv_put_identity(o, km, size);
-    o.put('\t');
-    tsv_put_i32(o, size);
-    o.put('\t');
-    o.put_u32(km);
-    o.put('\t');
-    const uint64_t *bits = nullptr;
-    uint32_t n_bits = 0;
+    return e;
+}
+
+// the bitmap of hit h of query q -> its bits
+__device__ __forceinline__ const uint64_t *tsv_hit_bits(const TsvParams &p, uint32_t q, uint32_t h, uint32_t *n_bits)
+{
+    const int32_t n = p.pos_len[q];
+    *n_bits = n > 0 ? (uint32_t)n : 0u;
+    return p.pos_bits + p.pos_base[q] + (uint64_t)h * ((*n_bits + 63u) >> 6);
+}
+
+// the tail of a row of either form: with positions the runs of hit h's bitmap behind a tab (ADD: tsv_put_positions_add),
+// with annotations the entry's columns (a tab each for a hit without entry), the newline
+template <uint32_t ADD, class Sink> __device__ __forceinline__ void tsv_row_tail(const TsvParams &p, Sink &o, uint32_t q, uint32_t h, uint32_t ent, const TsvEntry &e)
+{
     if (p.positions) {
-        const int32_t n = p.pos_len[q];
-        n_bits = n > 0 ? (uint32_t)n : 0u;
-        bits = p.pos_bits + p.pos_base[q] + (uint64_t)r * ((n_bits + 63u) >> 6);
-        const uint32_t runs = tsv_runs(bits, n_bits);
-        o.put_u32(runs ? runs - 1u : 0u);   // strings.Count(posString, ",")
-    } else {
-        o.put('N'); o.put('/'); o.put('A');
-    }
-    o.put('\t');
-    tsv_put_i32(o, p.start_pos[q]);
-    o.put('\t');
-    tsv_put_i32(o, m.end_position);
-    o.put('\t'); o.put('1'); o.put('\t');
-    if (p.annotations) o.put_u32(ent != TSV_NONE ? p.st_length[ent] : 0u);
-    else { o.put('N'); o.put('/'); o.put('A'); }
-    if (p.positions) {
+        uint32_t n_bits;
+        const uint64_t *bits = tsv_hit_bits(p, q, h, &n_bits);
         o.put('\t');
-        tsv_put_positions(o, bits, n_bits);
+        tsv_put_positions_add<ADD>(o, bits, n_bits);
     }
     if (p.annotations) {
-        if (ent != TSV_NONE) o.copy(p.st_bytes + s0 + idlen, s1 - s0 - idlen);
+        if (ent != OUT_NONE) o.copy(p.st_bytes + e.s0 + e.idlen, e.s1 - e.s0 - e.idlen);
         else o.fill('\t', p.n_features);
     }
     o.put('\n');
 }
 
-// inclusive scan of one value per thread of a TSV_TILE-thread workgroup (sh: TSV_TILE words); every thread gets its own
-// inclusive prefix, *total the workgroup's sum
-__device__ __forceinline__ unsigned long long tsv_block_scan(unsigned long long v, unsigned long long *sh, unsigned long long *total)
-{
-    const uint32_t t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < TSV_TILE; o <<= 1) {
-        const unsigned long long add = t >= o ? sh[t - o] : 0ull;
-        __syncthreads();
-        sh[t] += add;
-        __syncthreads();
+// the plain rows (search.go:505-554): the hits in reporting order
+struct TsvPlain {
+    using Params = TsvParams;
+    struct Lds {};
+    struct Lane {};
+    static __device__ __forceinline__ void setup(Params &) {}
+    static __device__ __forceinline__ Lane lane(Lds &) { return Lane(); }
+    static __device__ __forceinline__ uint32_t count(const Params &p, uint64_t q, uint32_t nq)
+    {
+        if (q >= nq) return 0u;
+        const uint32_t cnt = p.top_cnt[q];
+        return cnt > p.K ? p.K : cnt;
     }
-    const unsigned long long mine = sh[t];
-    *total = sh[TSV_TILE - 1];
-    __syncthreads();
-    return mine;
-}
-
-__device__ __forceinline__ uint32_t tsv_nq(const TsvParams &p)
-{
-    const uint32_t nq = *p.d_nq;
-    return nq < p.nq_cap ? nq : p.nq_cap;
-}
-
-// false: the batch's block is flagged (or holds no bitmaps although they are wanted) -- nothing of the batch is read;
-// else, with positions, the bitmaps are taken from the block.  Every thread computes the same.
-__device__ __forceinline__ bool tsv_upstream(TsvParams &p)
-{
-    if (!p.block) return true;
-    const RepBlockHdr *hdr = reinterpret_cast<const RepBlockHdr *>(p.block);
-    if (hdr->status) return false;
-    if (p.positions) {
-        const uint64_t at = rep_pos_ext(hdr)->off_pos_bits;
-        if (!at) return false;
-        p.pos_bits = reinterpret_cast<const uint64_t *>(p.block + at);
+    static __device__ __forceinline__ uint32_t hit(const Params &, uint64_t, uint32_t r) { return r; }
+    // OUT_NONE from the query's first missing entry on
+    static __device__ __forceinline__ uint32_t entry(const Params &p, uint64_t q, uint32_t h, bool &gone)
+    {
+        const uint32_t ent = gone ? OUT_NONE : out_entry(p, p.top_pid[q * p.K + h]);
+        gone = ent == OUT_NONE;
+        return ent;
     }
-    return true;
-}
-
-__global__ __launch_bounds__(TSV_TILE) void tsv_len_kernel(TsvParams p)
-{
-    __shared__ unsigned long long sh[TSV_TILE];
-    const uint32_t nq = tsv_nq(p);
-    if ((uint64_t)blockIdx.x * TSV_TILE >= nq || !tsv_upstream(p)) return;
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
-    TsvCount o;
-    uint32_t cnt = 0;
-    if (q < nq) {
-        cnt = p.top_cnt[q];
-        if (cnt > p.K) cnt = p.K;
-        bool gone = false;
-        for (uint32_t r = 0; r < cnt; r++) {
-            const uint32_t ent = gone ? TSV_NONE : tsv_entry(p, p.top_pid[q * p.K + r]);
-            gone = ent == TSV_NONE;
-            tsv_row(p, o, (uint32_t)q, r, ent);
+    static __device__ __forceinline__ bool refused(const Params &p) { return p.counts[OUT_C_STATUS] != 0; }
+    template <class Sink> static __device__ __forceinline__ void row(const Params &p, Sink &o, uint32_t q, uint32_t r, uint32_t ent, Lane &)
+    {
+        const kaamer_query_meta m = p.q[q];
+        const TsvEntry e = tsv_row_head(p, o, m, ent);
+        const uint32_t km = p.top_km[(uint64_t)q * p.K + r];
+        const int32_t size = p.size_out[q];
+        tsv_put_identity(o, km, size);
+        o.put('\t');
+        tsv_put_i32(o, size);
+        o.put('\t');
+        o.put_u32(km);
+        o.put('\t');
+        if (p.positions) {
+            uint32_t n_bits;
+            const uint64_t *bits = tsv_hit_bits(p, q, r, &n_bits);
+            const uint32_t runs = tsv_runs(bits, n_bits);
+            o.put_u32(runs ? runs - 1u : 0u);   // strings.Count(posString, ",")
+        } else {
+            o.put('N'); o.put('/'); o.put('A');
         }
+        o.put('\t');
+        tsv_put_i32(o, p.start_pos[q]);
+        o.put('\t');
+        tsv_put_i32(o, m.end_position);
+        o.put('\t'); o.put('1'); o.put('\t');
+        if (p.annotations) o.put_u32(ent != OUT_NONE ? p.st_length[ent] : 0u);
+        else { o.put('N'); o.put('/'); o.put('A'); }
+        tsv_row_tail<0u>(p, o, q, r, ent, e);
+    }
+};
+
+template <class Form> __global__ __launch_bounds__(OUT_TILE) void tsv_len_kernel(typename Form::Params p)
+{
+    __shared__ unsigned long long sh[OUT_TILE];
+    __shared__ typename Form::Lds lds;
+    Form::setup(p);
+    const uint32_t nq = out_nq(p);
+    if ((uint64_t)blockIdx.x * OUT_TILE >= nq || !out_upstream(p)) return;
+    const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
+    const uint32_t cnt = Form::count(p, q, nq);
+    typename Form::Lane X = Form::lane(lds);
+    TsvCount o;
+    bool gone = false;
+    for (uint32_t r = 0; r < cnt; r++) {
+        const uint32_t h = Form::hit(p, q, r);
+        const uint32_t ent = Form::entry(p, q, h, gone);
+        Form::row(p, o, (uint32_t)q, h, ent, X);
     }
     unsigned long long bytes = 0, lines = 0;
-    (void)tsv_block_scan(o.n, sh, &bytes);
-    (void)tsv_block_scan(cnt, sh, &lines);
-    if (threadIdx.x == 0) { p.tile_bytes[blockIdx.x] = bytes; p.tile_lines[blockIdx.x] = lines; }
-}
-
-// one workgroup: exclusive scan of the tiles' two sums in place, TSV_TILE tiles per round; totals and status
-__global__ __launch_bounds__(TSV_TILE) void tsv_scan_kernel(TsvParams p)
-{
-    __shared__ unsigned long long sh[TSV_TILE];
-    if (!tsv_upstream(p)) {
-        if (threadIdx.x == 0) { p.counts[TSV_C_LINES] = 0; p.counts[TSV_C_BYTES] = 0; p.counts[TSV_C_STATUS] = TSV_ST_UPSTREAM; }
-        return;
-    }
-    const uint32_t nq = tsv_nq(p);
-    const uint32_t tiles = (nq + TSV_TILE - 1u) / TSV_TILE;
-    unsigned long long base_b = 0, base_l = 0;
-    for (uint32_t t0 = 0; t0 < tiles; t0 += TSV_TILE) {
-        const uint32_t t = t0 + threadIdx.x;
-        const unsigned long long b = t < tiles ? p.tile_bytes[t] : 0ull, l = t < tiles ? p.tile_lines[t] : 0ull;
-        unsigned long long tb = 0, tl = 0;
-        const unsigned long long ib = tsv_block_scan(b, sh, &tb), il = tsv_block_scan(l, sh, &tl);
-        if (t < tiles) { p.tile_bytes[t] = base_b + ib - b; p.tile_lines[t] = base_l + il - l; }
-        base_b += tb; base_l += tl;
-    }
-    if (threadIdx.x == 0) {
-        unsigned long long st = 0;
-        if (base_b > p.out_cap) st |= TSV_ST_OUT_CAP;
-        if (base_l + 1ull > p.line_cap) st |= TSV_ST_LINE_CAP;
-        p.counts[TSV_C_LINES] = base_l; p.counts[TSV_C_BYTES] = base_b; p.counts[TSV_C_STATUS] = st;
-        if (!st) p.line_off[base_l] = base_b;
-    }
+    (void)out_block_scan(o.n, sh, &bytes);
+    (void)out_block_scan(cnt, sh, &lines);
+    if (threadIdx.x == 0) { p.tile_bytes[blockIdx.x] = bytes; p.tile_units[blockIdx.x] = lines; }
 }
 
 // a workgroup per tile, a lane per query: where every row starts (the tiles' prefixes, a scan of the queries' rows and bytes
 // inside the tile, the rows' lengths once more)
-__global__ __launch_bounds__(TSV_TILE) void tsv_off_kernel(TsvParams p)
+template <class Form> __global__ __launch_bounds__(OUT_TILE) void tsv_off_kernel(typename Form::Params p)
 {
-    __shared__ unsigned long long sh[TSV_TILE];
-    const uint32_t nq = tsv_nq(p);
-    if ((uint64_t)blockIdx.x * TSV_TILE >= nq) return;
-    if (p.counts[TSV_C_STATUS]) return;   // (uniform: written by the scan kernel before this one started)
-    (void)tsv_upstream(p);
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
-    uint32_t cnt = 0;
-    if (q < nq) {
-        cnt = p.top_cnt[q];
-        if (cnt > p.K) cnt = p.K;
-    }
+    __shared__ unsigned long long sh[OUT_TILE];
+    __shared__ typename Form::Lds lds;
+    Form::setup(p);
+    const uint32_t nq = out_nq(p);
+    if ((uint64_t)blockIdx.x * OUT_TILE >= nq) return;
+    if (Form::refused(p)) return;   // (uniform: written before this kernel started)
+    (void)out_upstream(p);
+    const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
+    const uint32_t cnt = Form::count(p, q, nq);
+    typename Form::Lane X = Form::lane(lds);
     unsigned long long tile_total = 0;
-    const unsigned long long e0 = p.tile_lines[blockIdx.x] + tsv_block_scan(cnt, sh, &tile_total) - cnt;
+    const unsigned long long e0 = p.tile_units[blockIdx.x] + out_block_scan(cnt, sh, &tile_total) - cnt;
     unsigned long long mine = 0;
     bool gone = false;
     for (uint32_t r = 0; r < cnt; r++) {
-        const uint32_t ent = gone ? TSV_NONE : tsv_entry(p, p.top_pid[q * p.K + r]);
-        gone = ent == TSV_NONE;
+        const uint32_t h = Form::hit(p, q, r);
+        const uint32_t ent = Form::entry(p, q, h, gone);
         TsvCount o;
-        tsv_row(p, o, (uint32_t)q, r, ent);
-        p.line_off[e0 + r] = mine;   // relative to the query's first byte for now
+        Form::row(p, o, (uint32_t)q, h, ent, X);
+        p.unit_off[e0 + r] = mine;   // relative to the query's first byte for now
         mine += o.n;
     }
-    const unsigned long long q0 = p.tile_bytes[blockIdx.x] + tsv_block_scan(mine, sh, &tile_total) - mine;
-    for (uint32_t r = 0; r < cnt; r++) p.line_off[e0 + r] += q0;
+    const unsigned long long q0 = p.tile_bytes[blockIdx.x] + out_block_scan(mine, sh, &tile_total) - mine;
+    for (uint32_t r = 0; r < cnt; r++) p.unit_off[e0 + r] += q0;
 }
 
-// [lo, hi) of the output from the LDS window that starts at `w`, by the whole workgroup: 16 bytes per lane, consecutive
-// lanes consecutive addresses; a chunk the range covers only in part goes out in bytes
-__device__ __forceinline__ void tsv_store_window(char *out, const char *win, unsigned long long w, unsigned long long lo, unsigned long long hi)
+template <class Form> __global__ __launch_bounds__(OUT_TILE) void tsv_write_kernel(typename Form::Params p)
 {
-    for (unsigned long long c = (lo - w) / 16ull + threadIdx.x; c * 16ull < hi - w; c += TSV_TILE) {
-        const unsigned long long at = w + c * 16ull;
-        if (at >= lo && at + 16ull <= hi) {
-            *reinterpret_cast<uint4 *>(out + at) = *reinterpret_cast<const uint4 *>(win + c * 16ull);
-        } else {
-            const unsigned long long a = at > lo ? at : lo, b = at + 16ull < hi ? at + 16ull : hi;
-            for (unsigned long long i = a; i < b; i++) out[i] = win[i - w];
-        }
-    }
-}
-
-__global__ __launch_bounds__(TSV_TILE) void tsv_write_kernel(TsvParams p)
-{
-    __shared__ unsigned long long sh[TSV_TILE];
+    __shared__ unsigned long long sh[OUT_TILE];
+    __shared__ typename Form::Lds lds;
     __shared__ __attribute__((aligned(16))) char win[TSV_WINDOW];
-    const uint32_t nq = tsv_nq(p);
-    if ((uint64_t)blockIdx.x * TSV_TILE >= nq) return;
-    if (p.counts[TSV_C_STATUS]) return;   // (uniform: written by the scan kernel before this one started)
-    (void)tsv_upstream(p);
-    const uint64_t q = (uint64_t)blockIdx.x * TSV_TILE + threadIdx.x;
-    uint32_t cnt = 0;
-    if (q < nq) {
-        cnt = p.top_cnt[q];
-        if (cnt > p.K) cnt = p.K;
-    }
+    Form::setup(p);
+    const uint32_t nq = out_nq(p);
+    if ((uint64_t)blockIdx.x * OUT_TILE >= nq) return;
+    if (Form::refused(p)) return;   // (uniform: written before this kernel started)
+    (void)out_upstream(p);
+    const uint64_t q = (uint64_t)blockIdx.x * OUT_TILE + threadIdx.x;
+    const uint32_t cnt = Form::count(p, q, nq);
+    typename Form::Lane X = Form::lane(lds);
     unsigned long long tile_total = 0;
-    const unsigned long long e0 = p.tile_lines[blockIdx.x] + tsv_block_scan(cnt, sh, &tile_total) - cnt;
-    // the tile's rows are [b0, b1) of the output; line_off[lines] is the total, so every row's end is the next entry
-    const unsigned long long b0 = p.tile_bytes[blockIdx.x], b1 = p.line_off[p.tile_lines[blockIdx.x] + tile_total];
-    const unsigned long long q0 = cnt ? p.line_off[e0] : 0ull, q1 = cnt ? p.line_off[e0 + cnt] : 0ull;
+    const unsigned long long e0 = p.tile_units[blockIdx.x] + out_block_scan(cnt, sh, &tile_total) - cnt;
+    // the tile's rows are [b0, b1) of the output; unit_off[rows] is the total, so every row's end is the next entry
+    const unsigned long long b0 = p.tile_bytes[blockIdx.x], b1 = p.unit_off[p.tile_units[blockIdx.x] + tile_total];
+    const unsigned long long q0 = cnt ? p.unit_off[e0] : 0ull, q1 = cnt ? p.unit_off[e0 + cnt] : 0ull;
     for (unsigned long long w = b0 - b0 % TSV_WINDOW; w < b1; w += TSV_WINDOW) {
         const unsigned long long lo = w > b0 ? w : b0, hi = w + TSV_WINDOW < b1 ? w + TSV_WINDOW : b1;
         if (q0 < hi && q1 > lo) {
             bool gone = false;
             for (uint32_t r = 0; r < cnt; r++) {
-                const uint32_t ent = gone ? TSV_NONE : tsv_entry(p, p.top_pid[q * p.K + r]);
-                gone = ent == TSV_NONE;
-                const unsigned long long s = p.line_off[e0 + r], e = p.line_off[e0 + r + 1];
+                const uint32_t h = Form::hit(p, q, r);
+                const uint32_t ent = Form::entry(p, q, h, gone);
+                const unsigned long long s = p.unit_off[e0 + r], e = p.unit_off[e0 + r + 1];
                 if (e <= lo) continue;
                 if (s >= hi) break;
                 TsvWindow o = { win, s, w, lo, hi };
-                tsv_row(p, o, (uint32_t)q, r, ent);
+                Form::row(p, o, (uint32_t)q, h, ent, X);
             }
         }
         __syncthreads();
-        tsv_store_window(p.out, win, w, lo, hi);
+        out_store_window(p.out, win, w, lo, hi);
         __syncthreads();
     }
 }

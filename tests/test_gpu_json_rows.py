@@ -78,6 +78,7 @@ def run_stage(ix, c, out_cap, stage=None, max_objects=None, K=None):
         assert objects == n_objects and nbytes <= out_cap
         home = out.cpu().numpy().tobytes()
         off = _home(res.d_obj_off, objects + 1, np.uint64)
+        run_stage.counts = _home(res.d_counts, 4, np.uint64).tolist()      # objects, bytes, status, (unused)
         return home[:nbytes], off, home[nbytes:]
     finally:
         if own:
@@ -128,6 +129,21 @@ def test_hand_built_cases(setup, name):
 @pytest.mark.parametrize("n,seed", [(1, 1), (63, 2), (64, 3), (65, 4), (257, 5), (700, 6)])
 def test_many_queries_with_empty_ones_between(setup, n, seed):
     check(setup, jsoncases.many_queries(n, seed))
+
+
+def test_no_queries(setup):
+    _attach(setup, "std")
+    got, off, rest = run_stage(setup["ix"], jsoncases.standard_cases()["empty"], 64)
+    assert got == b"" and off.tolist() == [0] and rest == b"\x55" * len(rest) and run_stage.counts == [0, 0, 0, 0]
+
+
+def test_more_tiles_than_one_round_of_the_scan(setup):
+    """65 537 queries are 257 tiles: the scan kernel, one workgroup of 256 threads, goes round twice; objects on the first and
+    the last query of the first tile, the first of the second, and on either side of the second round's first tile"""
+    hit = (0, 255, 256, 65535, 65536)
+    qs = [jsoncases.query(0, [(5 + i % 9, 3)] if i in hit else []) for i in range(65537)]
+    got = check(setup, jsoncases.case("std", True, 0, False, [b"sweep of tiles"], qs, [jsoncases.residues(20)]))
+    assert got.count(b'{"Query"') == len(hit) and run_stage.counts[:1] + run_stage.counts[2:] == [len(hit), 0, 0]
 
 
 def test_objects_at_every_alignment_and_around_every_flush(setup):

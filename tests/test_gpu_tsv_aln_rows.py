@@ -86,6 +86,7 @@ def run_stage(setup, names, queries, K, positions, annotations, seq_type, out_ca
         assert lines == n_lines and nbytes <= out_cap
         home = out.cpu().numpy().tobytes()
         off = _home(res.d_line_off, lines + 1, np.uint64)
+        run_stage.counts = _home(res.d_counts, 4, np.uint64).tolist()      # rows, bytes, status, raw scores outside the table
         return home[:nbytes], off, home[nbytes:]
     finally:
         if own:
@@ -119,6 +120,20 @@ def test_hand_built_batches(setup, positions, annotations, seq_type):
         got = check(setup, names, queries, K, positions, annotations, seq_type, slack=0 if name != "order" else 5)
         if K < 10:
             assert check(setup, names, queries, 10, positions, annotations, seq_type) == got
+
+
+def test_no_queries(setup):
+    got, off, rest = run_stage(setup, [], [], 1, True, True, abi.READS, 64)
+    assert got == b"" and off.tolist() == [0] and rest == b"\x55" * len(rest) and run_stage.counts == [0, 0, 0, 0]
+
+
+def test_more_tiles_than_one_round_of_the_scan(setup):
+    """65 537 queries are 257 tiles: the scan kernel, one workgroup of 256 threads, goes round twice; hits on the first and
+    the last query of the first tile, the first of the second, and on either side of the second round's first tile"""
+    hit = (0, 255, 256, 65535, 65536)
+    queries = [tsvalncases.aquery(0, [(i % tsvcases.N_ENTRIES, tsvalncases.aligned(40 + i % 7, shift=i % 5))] if i in hit else []) for i in range(65537)]
+    got = check(setup, [b"sweep of tiles"], queries, 1, False, True, abi.PROTEIN)
+    assert got.count(b"\n") == len(hit) and run_stage.counts[:1] + run_stage.counts[2:] == [len(hit), 0, 0]
 
 
 def test_counts_above_max_results_are_clipped(setup):

@@ -66,6 +66,7 @@ def run_stage(ix, names, queries, K, positions, annotations, out_cap, stage=None
         assert lines == n_lines and nbytes <= out_cap
         home = out.cpu().numpy().tobytes()
         off = _home(res.d_line_off, lines + 1, np.uint64)
+        run_stage.counts = _home(res.d_counts, 4, np.uint64).tolist()      # rows, bytes, status, raw scores outside the table
         return home[:nbytes], off, home[nbytes:]
     finally:
         if own:
@@ -95,6 +96,11 @@ def test_geometry_and_info(setup):
     longest = max(len(e["EntryId"]) + len(str(e["Length"])) + sum(1 + len(v) for v in e["Features"].values()) for e in ent.values())
     assert (info["entries"], info["features"], info["max_row_suffix"]) == (len(ent), 3, longest)
     assert info["table_bytes"] > sum(len(e["EntryId"]) for e in ent.values())
+
+
+def test_no_queries(setup):
+    got, off, rest = run_stage(setup["ix"], [], [], 1, True, True, 64)
+    assert got == b"" and off.tolist() == [0] and rest == b"\x55" * len(rest) and run_stage.counts == [0, 0, 0, 0]
 
 
 def test_float_sweep_in_one_launch(setup):
