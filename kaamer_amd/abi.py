@@ -202,31 +202,51 @@ class TsvAlnOpts(C.Structure):   # kaamer_tsv_aln_opts
                 ("reserved", C.c_int32)]
 
 
-# every symbol include/kaamer_hip.h declares: name -> (restype, argtypes)
+# The argument groups that recur in the prototypes below, each named once
+HANDLE = [C.c_void_p]                                   # an index, a sharded index, a replica set, a stream, a ticket, a stage
+BATCH = [C.c_void_p, C.c_void_p, C.c_uint32]            # the packed batch: (seqs, offsets, n_seqs)
+SEQ_TYPE = [C.c_int32]                                  # seq_type()
+TOP = [C.c_double, C.c_int64, C.c_uint32]               # the top options: (min_k_ratio, min_k_match, max_results)
+ALIGN = [C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32]   # (want_positions, sub_matrix, gap_open, gap_extend, want_text)
+ALIGN_TEXT = ALIGN[1:4]                                 # ... of the text calls: (sub_matrix, gap_open, gap_extend)
+ALIGN_FILE = ALIGN[:1] + [C.c_int32] + ALIGN[1:]        # ... of the file drivers: want_aln after want_positions
+ROWS = [C.c_int32, C.c_int32]                           # the rows group: (extract_positions, annotations)
+TEXT_IN = [C.c_char_p, C.c_uint64]                      # (text, len)
+TEXT_HEAD = {"text": TEXT_IN + [C.c_int32] + SEQ_TYPE,  # (text, len, format, seq_type)
+             "fasta": TEXT_IN + SEQ_TYPE + [C.c_int32],  # (text, len, seq_type, upper_last)
+             "bgzf": TEXT_IN + SEQ_TYPE}                # (bytes, len, seq_type)
+TEXT_TAIL = {"": [], "_tsv": ROWS, "_aln_tsv": ROWS + ALIGN_TEXT, "_json": ROWS[:1]}   # what a response format adds behind TOP
+OUT = {"search": [C.c_void_p], "submit": [C.POINTER(C.c_void_p)]}   # the two `out` kinds: a kaamer_batch_top **, a ticket *
+NEW = [C.POINTER(C.c_void_p)]                           # the handle a create / open / parse call makes
+FULL_OUT = [C.POINTER(C.POINTER(BatchOut))]
+FILE_IN = [C.c_char_p, C.c_int, C.c_int]                # (path, format, strict_scanner)
+CHUNKS = [C.c_uint32, C.c_uint64, C.c_uint32]           # (chunk_seqs, chunk_bytes, in_flight)
+TEXT_CHUNKS = [C.c_uint64, C.c_uint32]                  # (chunk_text_bytes, in_flight)
+CB = [C.c_void_p, C.c_void_p, C.POINTER(Counters)]      # (cb, user, total)
+INFO = (C.c_int, HANDLE + [C.POINTER(C.c_uint64)])      # an info getter: (handle, u64 out[])
+ATTACH = (C.c_int, HANDLE + [C.c_void_p])               # (handle, proteins)
+
+# every symbol include/kaamer_hip.h declares: name -> (restype, argtypes).  First the symbols that stand alone, then the
+# families, built from the groups above
 SYMBOLS = {
     "kaamer_last_error": (C.c_char_p, []),
     "kaamer_abi_version": (C.c_int, []),
     "kaamer_encode_kmer": (C.c_uint32, [C.c_char_p]),
     "kaamer_genetic_code": (C.c_int, [C.c_int32, C.c_char_p, C.c_char_p]),
     "kaamer_shard_of": (C.c_uint32, [C.c_uint32, C.c_uint32]),
-    "kaamer_image_build_pairs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double,
-                                           C.POINTER(C.c_void_p)]),
-    "kaamer_image_build_proteins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                              C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]),
-    "kaamer_image_build_proteins_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                     C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
-    "kaamer_index_build_proteins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                              C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
+    "kaamer_image_build_pairs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double] + NEW),
+    # (seqs, offsets, ids, n_proteins, shard, n_shards, load_factor[, device], out)
+    "kaamer_image_build_proteins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double] + NEW),
+    "kaamer_image_build_proteins_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+                                                     C.c_int] + NEW),
+    "kaamer_index_build_proteins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+                                              C.c_int] + NEW),
     "kaamer_image_save": (C.c_int, [C.c_void_p, C.c_char_p]),
-    "kaamer_image_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "kaamer_image_load": (C.c_int, [C.c_char_p] + NEW),
     "kaamer_image_get_stats": (C.c_int, [C.c_void_p, C.POINTER(ImageStats)]),
     "kaamer_image_free": (None, [C.c_void_p]),
     "kaamer_image_get": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
-    "kaamer_makedb_fasta": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_makedb_tsv": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_makedb_embl": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_makedb_gbk": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_makedb_text": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "kaamer_makedb_text": (C.c_int, TEXT_IN + [C.c_int32, C.c_int32] + NEW),
     "kaamer_proteins_count": (C.c_uint32, [C.c_void_p]),
     "kaamer_proteins_ids": (C.POINTER(C.c_uint32), [C.c_void_p]),
     "kaamer_proteins_seqs": (C.POINTER(C.c_uint8), [C.c_void_p]),
@@ -235,22 +255,18 @@ SYMBOLS = {
     "kaamer_proteins_feature_name": (C.c_char_p, [C.c_void_p, C.c_uint32]),
     "kaamer_proteins_stats": (None, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_proteins_save": (C.c_int, [C.c_void_p, C.c_char_p]),
-    "kaamer_proteins_load": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "kaamer_proteins_load": (C.c_int, [C.c_char_p] + NEW),
     "kaamer_proteins_free": (None, [C.c_void_p]),
-    "kaamer_image_build_makedb": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]),
-    "kaamer_image_build_makedb_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_int,
-                                                   C.POINTER(C.c_void_p)]),
+    "kaamer_image_build_makedb": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double] + NEW),
+    "kaamer_image_build_makedb_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_int] + NEW),
     "kaamer_fetch_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ProteinEntry)]),
-    "kaamer_index_open_image": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
-    "kaamer_index_open": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "kaamer_index_open_image": (C.c_int, [C.c_void_p, C.c_int] + NEW),
+    "kaamer_index_open": (C.c_int, [C.c_char_p, C.c_int] + NEW),
     "kaamer_index_close": (None, [C.c_void_p]),
     "kaamer_index_get_stats": (C.c_int, [C.c_void_p, C.POINTER(ImageStats)]),
-    "kaamer_search_batch": (C.c_int, [C.c_void_p, C.POINTER(BatchIn), C.POINTER(C.POINTER(BatchOut))]),
     "kaamer_batch_free": (None, [C.POINTER(BatchOut)]),
-    "kaamer_submit_batch_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_wait_batch": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(BatchOut))]),
-    "kaamer_full_ticket_discard": (None, [C.c_void_p]),
-    "kaamer_workspace_create": (C.c_int, [C.c_void_p, C.POINTER(WorkspaceOpts), C.POINTER(C.c_void_p)]),
+    "kaamer_batch_top_free": (None, [C.c_void_p]),
+    "kaamer_workspace_create": (C.c_int, [C.c_void_p, C.POINTER(WorkspaceOpts)] + NEW),
     "kaamer_workspace_free": (None, [C.c_void_p]),
     "kaamer_workspace_set_count_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kaamer_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -268,45 +284,12 @@ SYMBOLS = {
     "kaamer_workspace_kernel_ms_sum": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                  C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "kaamer_topn_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "kaamer_search_batch_top": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "kaamer_batch_top_free": (None, [C.c_void_p]),
-    "kaamer_index_open_sharded": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_index_open_sharded_images": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_index_open_sharded": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_uint32] + NEW),
+    "kaamer_index_open_sharded_images": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_uint32] + NEW),
     "kaamer_sharded_index_shards": (C.c_uint32, [C.c_void_p]),
     "kaamer_sharded_index_close": (None, [C.c_void_p]),
-    "kaamer_sharded_search_batch_top": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "kaamer_submit_batch_top": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "kaamer_wait_batch_top": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_stream_open": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "kaamer_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "kaamer_stream_pop": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_stream_pending": (C.c_uint32, [C.c_void_p]),
-    "kaamer_stream_close": (None, [C.c_void_p]),
-    "kaamer_ticket_discard": (None, [C.c_void_p]),
-    # cgo-safe forms: (handle, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results, out)
-    "kaamer_search_batch_top_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                               C.c_int64, C.c_uint32, C.c_void_p]),
-    "kaamer_submit_batch_top_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                               C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_batch_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
-                                           C.POINTER(C.POINTER(BatchOut))]),
-    "kaamer_stream_open_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_submit_batch_top": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_wait_batch_top": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_sharded_ticket_discard": (None, [C.c_void_p]),
-    "kaamer_sharded_search_batch_top_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                                       C.c_int64, C.c_uint32, C.c_void_p]),
-    "kaamer_sharded_submit_batch_top_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                                       C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_exchange_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
-    # full hit lists (PositionHits included) on the sharded handle, and the exchange blocks that carry bitmaps
-    "kaamer_sharded_search_batch": (C.c_int, [C.c_void_p, C.POINTER(BatchIn), C.POINTER(C.POINTER(BatchOut))]),
-    "kaamer_sharded_search_batch_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
-                                                   C.POINTER(C.POINTER(BatchOut))]),
-    "kaamer_sharded_submit_batch_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
-                                                   C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_wait_batch": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(BatchOut))]),
-    "kaamer_sharded_full_ticket_discard": (None, [C.c_void_p]),
+    "kaamer_stream_open": (C.c_int, HANDLE + SEQ_TYPE + [C.c_void_p] + NEW),   # the struct form: (index, seq_type, topn_opts, out)
+    # the exchange blocks that carry bitmaps
     "kaamer_exchange_layout_init_positions": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                                         C.POINTER(ExchangeLayout)]),
     "kaamer_exchange_layout_fit_positions": (C.c_int, [C.POINTER(ExchangeLayout), C.c_uint32, C.c_uint64, C.c_uint64,
@@ -318,8 +301,6 @@ SYMBOLS = {
     "kaamer_sort_hits": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "kaamer_set_best_start_codon": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                                 C.c_char_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "kaamer_parse_fasta": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_parse_fastq": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "kaamer_reads_count": (C.c_uint32, [C.c_void_p]),
     "kaamer_reads_seqs": (C.POINTER(C.c_uint8), [C.c_void_p]),
     "kaamer_reads_offsets": (C.POINTER(C.c_uint64), [C.c_void_p]),
@@ -328,248 +309,171 @@ SYMBOLS = {
     "kaamer_reads_name_offsets": (C.POINTER(C.c_uint64), [C.c_void_p]),
     "kaamer_reads_plus_strand": (C.POINTER(C.c_int32), [C.c_void_p]),
     "kaamer_reads_free": (None, [C.c_void_p]),
-    "kaamer_index_open_replicas": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_index_open_replicas_image": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_index_open_replicas": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.c_uint32] + NEW),
+    "kaamer_index_open_replicas_image": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_uint32] + NEW),
     "kaamer_replicas_count": (C.c_uint32, [C.c_void_p]),
     "kaamer_replicas_index": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "kaamer_replicas_close": (None, [C.c_void_p]),
-    "kaamer_replica_stream_open_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_replica_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "kaamer_replica_stream_pop": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_replica_stream_pending": (C.c_uint32, [C.c_void_p]),
-    "kaamer_replica_stream_close": (None, [C.c_void_p]),
-    "kaamer_search_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint32,
-                                     C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
-    "kaamer_align_pairs": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
-                                     C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    # (device, seqs, offsets, n_seqs, pair_query, pair_subject, n_pairs, number_of_aa, sub_matrix, gap_open, gap_extend, out)
+    "kaamer_align_pairs": (C.c_int, [C.c_int] + BATCH + [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64] + ALIGN_TEXT + NEW),
     "kaamer_alignments_count": (C.c_uint32, [C.c_void_p]),
     "kaamer_alignments_items": (C.POINTER(Alignment), [C.c_void_p]),
     "kaamer_alignments_text": (C.POINTER(C.c_char), [C.c_void_p]),
     "kaamer_alignments_free": (None, [C.c_void_p]),
     "kaamer_align_matrix_scores": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "kaamer_align_matrix_entry": (C.c_int32, [C.c_int32, C.c_int32]),
-    "kaamer_reader_open": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
-    "kaamer_reader_open_fd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
-    "kaamer_reader_next": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "kaamer_reader_open": (C.c_int, FILE_IN + NEW),
+    "kaamer_reader_open_fd": (C.c_int, [C.c_int, C.c_int, C.c_int] + NEW),
+    "kaamer_reader_next": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64] + NEW),
     "kaamer_reader_done": (C.c_int, [C.c_void_p]),
     "kaamer_reader_records": (C.c_uint64, [C.c_void_p]),
     "kaamer_reader_close": (None, [C.c_void_p]),
     # PositionHits bitmaps of the reported hits on the top-N calls
     "kaamer_topn_positions_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TopnResult), C.c_uint64, C.c_void_p,
                                                C.POINTER(TopnPositions)]),
-    "kaamer_search_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                                   C.c_int64, C.c_uint32, C.c_void_p]),
-    "kaamer_submit_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                                   C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_stream_open_pos_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "kaamer_batch_top_positions": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_uint64)),
                                              C.POINTER(C.POINTER(C.c_uint64))]),
     "kaamer_index_set_top_positions_bound": (C.c_int, [C.c_void_p, C.c_uint64]),
-    # ... and on the sharded handle
-    "kaamer_sharded_search_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                                           C.c_int64, C.c_uint32, C.c_void_p]),
-    "kaamer_sharded_submit_batch_top_pos_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double,
-                                                           C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_positions_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_format_positions": (C.c_uint64, [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_uint64]),
     # the alignment of the reported hits inside the top-N call
-    "kaamer_index_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_index_align_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_index_set_align_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "kaamer_sharded_index_set_align_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "kaamer_sharded_index_set_align_timing": (C.c_int, [C.c_void_p, C.c_int32]),
     "kaamer_topn_align_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TopnResult), C.POINTER(TopnAlignOpts), C.c_void_p,
                                            C.POINTER(TopnAlignments)]),
-    "kaamer_search_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
-                                                   C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "kaamer_submit_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
-                                                   C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
-                                                   C.POINTER(C.c_void_p)]),
     "kaamer_batch_top_alignments": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(Alignment)), C.POINTER(C.POINTER(C.c_char))]),
-    "kaamer_align_finish_pairs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
-    # ... and on the sharded handle
-    "kaamer_sharded_index_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_sharded_index_set_align_budget": (C.c_int, [C.c_void_p, C.c_uint64]),
-    "kaamer_sharded_align_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
-    "kaamer_sharded_index_set_align_timing": (C.c_int, [C.c_void_p, C.c_int32]),
-    "kaamer_sharded_align_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
-    "kaamer_sharded_search_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
-                                                           C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "kaamer_sharded_submit_batch_top_aln_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_double, C.c_int64,
-                                                           C.c_uint32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32,
-                                                           C.POINTER(C.c_void_p)]),
-    # streams and whole-file drivers with the bitmaps / alignments of the reported hits, on all three handle kinds
-    # stream open forms: (handle, seq_type, min_k_ratio, min_k_match, max_results[, want_positions, sub_matrix, gap_open, gap_extend,
-    # want_text], out)
-    "kaamer_stream_open_aln_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32, C.c_char_p, C.c_int32,
-                                              C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_replicas_attach_proteins": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_replica_stream_open_pos_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_replica_stream_open_aln_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32, C.c_char_p,
-                                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_stream_open_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_stream_open_pos_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_stream_open_aln_flat": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32, C.c_char_p,
-                                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_sharded_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "kaamer_sharded_stream_pop": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_sharded_stream_pending": (C.c_uint32, [C.c_void_p]),
-    "kaamer_sharded_stream_close": (None, [C.c_void_p]),
-    # (handle, path, format, strict_scanner, seq_type, min_k_ratio, min_k_match, max_results, want_positions, want_aln, sub_matrix,
-    #  gap_open, gap_extend, want_text, chunk_seqs, chunk_bytes, in_flight, cb, user, total)
-    "kaamer_search_file_opts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                          C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32,
-                                          C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
-    "kaamer_sharded_search_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                             C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32,
-                                             C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    "kaamer_align_finish_pairs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64] + ALIGN_TEXT + [C.c_void_p]),
+    # the whole-file driver: (handle, path, format, strict_scanner, seq_type, min_k_ratio, min_k_match, max_results, chunk_seqs,
+    # chunk_bytes, in_flight, cb, user, total)
+    "kaamer_search_file": (C.c_int, HANDLE + FILE_IN + SEQ_TYPE + TOP + CHUNKS + CB),
     # kaamer-db -merge and the split makedb runs (-offset / -length)
     "kaamer_image_load_factor": (C.c_double, [C.c_void_p]),
-    "kaamer_image_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]),
-    "kaamer_image_merge_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
-    "kaamer_proteins_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_makedb_text_range": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
-    # FASTQ text parsed on the device: the parser, the host-buffer calls that take text, the whole-file driver
-    "kaamer_text_parser_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_image_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double] + NEW),
+    "kaamer_image_merge_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_double, C.c_int] + NEW),
+    "kaamer_proteins_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32] + NEW),
+    "kaamer_makedb_text_range": (C.c_int, TEXT_IN + [C.c_int32, C.c_int32, C.c_uint64, C.c_uint64] + NEW),
+    # FASTQ / FASTA text parsed on the device: the parser, the cut rules, the whole-file drivers
+    "kaamer_text_parser_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32] + NEW),
+    "kaamer_text_parser_create_lines": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64] + NEW),
     "kaamer_text_parser_free": (None, [C.c_void_p]),
     "kaamer_parse_fastq_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_parse_fasta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]),
     "kaamer_text_parser_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TextParseResult)]),
     "kaamer_text_parser_geometry": (None, [C.POINTER(C.c_uint32)]),
-    # (handle, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, out)
-    "kaamer_submit_text_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                              C.POINTER(C.c_void_p)]),
-    "kaamer_search_text_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                              C.c_void_p]),
     "kaamer_batch_top_text_spans": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(TextSpan)), C.POINTER(C.c_uint32)]),
-    "kaamer_text_cut_fastq": (C.c_uint64, [C.c_char_p, C.c_uint64]),
-    # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total)
-    "kaamer_search_text_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
-                                          C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    "kaamer_text_cut_fastq": (C.c_uint64, TEXT_IN),
+    "kaamer_text_cut_fasta": (C.c_uint64, TEXT_IN),
+    # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight[, device_inflate], cb, user,
+    # total); the FASTA driver has no format
+    "kaamer_search_text_file": (C.c_int, HANDLE + [C.c_char_p, C.c_int] + SEQ_TYPE + TOP + TEXT_CHUNKS + CB),
+    "kaamer_search_text_file_opts": (C.c_int, HANDLE + [C.c_char_p, C.c_int] + SEQ_TYPE + TOP + TEXT_CHUNKS + [C.c_int32] + CB),
+    "kaamer_search_fasta_file": (C.c_int, HANDLE + [C.c_char_p] + SEQ_TYPE + TOP + TEXT_CHUNKS + CB),
     # BGZF inflated on the device: the host scan of the block headers, the inflater, the cut on the device
     "kaamer_bgzf_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    "kaamer_inflater_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "kaamer_inflater_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32] + NEW),
     "kaamer_inflater_free": (None, [C.c_void_p]),
     "kaamer_inflate_bgzf_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "kaamer_inflater_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(InflateResult)]),
     "kaamer_inflater_geometry": (None, [C.POINTER(C.c_uint32)]),
     "kaamer_text_cut_fastq_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
-    # (handle, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, out)
-    "kaamer_submit_bgzf_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_bgzf_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_void_p]),
     "kaamer_batch_top_text": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
-    # (handle, path, format, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, device_inflate, cb, user, total)
-    "kaamer_search_text_file_opts": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
-                                               C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
-    # FASTA text parsed on the device: the parse, the cut rule, the host-buffer calls, the whole-file driver
-    "kaamer_text_parser_create_lines": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_parse_fasta_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]),
-    "kaamer_text_cut_fasta": (C.c_uint64, [C.c_char_p, C.c_uint64]),
-    # (handle, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, out)
-    "kaamer_submit_fasta_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                               C.POINTER(C.c_void_p)]),
-    "kaamer_search_fasta_top_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                               C.c_void_p]),
-    # (handle, path, seq_type, min_k_ratio, min_k_match, max_results, chunk_text_bytes, in_flight, cb, user, total)
-    "kaamer_search_fasta_file": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_uint64, C.c_uint32,
-                                           C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
-    # the TSV response rows: the host formatter, the subject text on the device, the device stage, the text calls
-    # (extract_positions, annotations, proteins, buf, cap)
-    "kaamer_format_tsv_header": (C.c_uint64, [C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_uint64]),
-    # (top, name_bytes, name_bytes_len, name_spans, n_names, proteins, extract_positions, annotations, buf, cap, line_off)
-    "kaamer_format_tsv": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32,
-                                      C.c_void_p, C.c_uint64, C.c_void_p]),
-    # (top, pos_bits_len, pos_off, pos_bits, ...the same)
+    # the TSV response rows on the host: (extract_positions, annotations, proteins, buf, cap)
+    "kaamer_format_tsv_header": (C.c_uint64, ROWS + [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "kaamer_format_tsv_aln_header": (C.c_uint64, ROWS + [C.c_void_p, C.c_char_p, C.c_uint64]),
+    # (top, name_bytes, name_bytes_len, name_spans, n_names, proteins[, seq_type], extract_positions, annotations, buf, cap, line_off)
+    "kaamer_format_tsv": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p] + ROWS
+                          + [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_format_tsv_aln": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p] + SEQ_TYPE + ROWS
+                              + [C.c_void_p, C.c_uint64, C.c_void_p]),
+    # (top[, alns], pos_bits_len, pos_off, pos_bits, ...the same)
     "kaamer_format_tsv_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
-                                             C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
-    # the -aln rows: (extract_positions, annotations, proteins, buf, cap)
-    "kaamer_format_tsv_aln_header": (C.c_uint64, [C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_uint64]),
-    # (top, name_bytes, name_bytes_len, name_spans, n_names, proteins, seq_type, extract_positions, annotations, buf, cap, line_off)
-    "kaamer_format_tsv_aln": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                          C.c_void_p, C.c_uint64, C.c_void_p]),
-    # (top, alns, pos_bits_len, pos_off, pos_bits, ...the same)
+                                             C.c_void_p] + ROWS + [C.c_void_p, C.c_uint64, C.c_void_p]),
     "kaamer_format_tsv_aln_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                 C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
+                                                 C.c_uint32, C.c_void_p] + SEQ_TYPE + ROWS + [C.c_void_p, C.c_uint64, C.c_void_p]),
     "kaamer_format_double": (C.c_uint64, [C.c_double, C.c_int32, C.c_char_p, C.c_uint64]),
     "kaamer_tsv_aln_rows_device": (C.c_int, [C.c_void_p, C.POINTER(TsvRowsIn), C.POINTER(TopnAlignments), C.POINTER(TsvAlnOpts), C.c_void_p,
                                              C.c_uint64, C.c_void_p, C.POINTER(TsvRowsResult)]),
-    "kaamer_tsv_aln_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_tsv_format_doubles_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]),
-    "kaamer_index_attach_subject_text": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_index_subject_text_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
-    "kaamer_tsv_stage_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_tsv_stage_free": (None, [C.c_void_p]),
-    "kaamer_tsv_rows_device": (C.c_int, [C.c_void_p, C.POINTER(TsvRowsIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(TsvRowsResult)]),
-    "kaamer_tsv_rows_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
-    "kaamer_tsv_geometry": (None, [C.POINTER(C.c_uint32)]),
-    # (handle, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, annotations, out)
-    "kaamer_submit_text_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                  C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_text_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                  C.c_int32, C.c_int32, C.c_void_p]),
-    # (handle, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, extract_positions, annotations, out)
-    "kaamer_submit_fasta_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                   C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_fasta_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                   C.c_int32, C.c_int32, C.c_void_p]),
-    # (handle, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, annotations, out)
-    "kaamer_submit_bgzf_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                                  C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_bgzf_top_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                                  C.c_int32, C.c_void_p]),
-    # the _tsv_ calls with the alignment in between: ... extract_positions, annotations, sub_matrix, gap_open, gap_extend, out
-    "kaamer_submit_text_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                      C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_text_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                      C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "kaamer_submit_fasta_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                       C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_fasta_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                       C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "kaamer_submit_bgzf_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                                      C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_bgzf_top_aln_tsv_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                                      C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "kaamer_index_tsv_aln_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "kaamer_index_set_tsv_aln_raw_count": (C.c_int, [C.c_void_p, C.c_uint32]),
-    "kaamer_batch_top_tsv": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]),
-    "kaamer_index_set_tsv_bounds": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
-    # the JSON response: the host formatter, the subject entries on the device, the device stage, the text calls
-    # (annotations, proteins, buf, cap)
+    # the JSON response on the host: (annotations, proteins, buf, cap)
     "kaamer_format_json_header": (C.c_uint64, [C.c_int32, C.c_void_p, C.c_char_p, C.c_uint64]),
     "kaamer_format_json_trailer": (C.c_uint64, [C.c_char_p, C.c_uint64]),
     # (top, seqs, offsets, n_seqs, name_bytes, name_bytes_len, name_spans, n_names, proteins, seq_type, text_format,
     #  extract_positions, buf, cap, obj_off)
-    "kaamer_format_json": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
-                                       C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_format_json": (C.c_int64, [C.c_void_p] + BATCH + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]),
     # (top, alns, pos_bits_len, pos_off, pos_bits, ...the same from seqs on)
-    "kaamer_format_json_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
-                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                              C.c_void_p, C.c_uint64, C.c_void_p]),
-    "kaamer_json_escape": (C.c_uint64, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "kaamer_format_json_arrays": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + BATCH
+                                  + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kaamer_json_escape": (C.c_uint64, TEXT_IN + [C.c_char_p, C.c_uint64]),
     "kaamer_json_protein_value": (C.c_uint64, [C.POINTER(ProteinEntry), C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64]),
-    "kaamer_index_attach_subject_json": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "kaamer_index_subject_json_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
-    "kaamer_json_stage_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
-    "kaamer_json_stage_free": (None, [C.c_void_p]),
-    "kaamer_json_rows_device": (C.c_int, [C.c_void_p, C.POINTER(JsonRowsIn), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(JsonRowsResult)]),
-    "kaamer_json_rows_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
-    "kaamer_json_geometry": (None, [C.POINTER(C.c_uint32)]),
-    # (handle, text, len, format, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, out)
-    "kaamer_submit_text_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                   C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_text_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                   C.c_int32, C.c_void_p]),
-    # (handle, text, len, seq_type, upper_last, min_k_ratio, min_k_match, max_results, extract_positions, out)
-    "kaamer_submit_fasta_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                    C.c_int32, C.POINTER(C.c_void_p)]),
-    "kaamer_search_fasta_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_int64, C.c_uint32,
-                                                    C.c_int32, C.c_void_p]),
-    # (handle, bytes, len, seq_type, min_k_ratio, min_k_match, max_results, extract_positions, out)
-    "kaamer_submit_bgzf_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                                   C.POINTER(C.c_void_p)]),
-    "kaamer_search_bgzf_top_json_flat": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_double, C.c_int64, C.c_uint32, C.c_int32,
-                                                   C.c_void_p]),
-    "kaamer_batch_top_json": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))]),
-    "kaamer_index_set_json_bounds": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
 }
+
+# a database or query text parsed on the host: (text, len, out)
+for _name in ("makedb_fasta", "makedb_tsv", "makedb_embl", "makedb_gbk", "parse_fasta", "parse_fastq"):
+    SYMBOLS["kaamer_" + _name] = (C.c_int, TEXT_IN + NEW)
+
+# the packed-batch calls of an index and of a sharded index; search fills a result, submit a ticket for wait / discard
+for _p in ("", "sharded_"):
+    # the reported hits, cgo-safe forms: (handle, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results[,
+    # want_positions, sub_matrix, gap_open, gap_extend, want_text], out)
+    for _verb, _out in OUT.items():
+        for _form, _mid in (("", []), ("_pos", []), ("_aln", ALIGN)):
+            SYMBOLS["kaamer_%s%s_batch_top%s_flat" % (_p, _verb, _form)] = (C.c_int, HANDLE + BATCH + SEQ_TYPE + TOP + _mid + _out)
+    # ... their struct forms: (handle, batch_in, topn_opts, out)
+    SYMBOLS["kaamer_%ssearch_batch_top" % _p] = (C.c_int, HANDLE + [C.c_void_p, C.c_void_p] + OUT["search"])
+    SYMBOLS["kaamer_%ssubmit_batch_top" % _p] = (C.c_int, HANDLE + [C.c_void_p, C.c_void_p] + OUT["submit"])
+    SYMBOLS["kaamer_%swait_batch_top" % _p] = (C.c_int, HANDLE + OUT["search"])
+    SYMBOLS["kaamer_%sticket_discard" % _p] = (None, HANDLE)
+    # the full hit lists (PositionHits included): (handle, seqs, offsets, n_seqs, seq_type, want_positions, out)
+    SYMBOLS["kaamer_%ssearch_batch_flat" % _p] = (C.c_int, HANDLE + BATCH + SEQ_TYPE + [C.c_int32] + FULL_OUT)
+    SYMBOLS["kaamer_%ssubmit_batch_flat" % _p] = (C.c_int, HANDLE + BATCH + SEQ_TYPE + [C.c_int32] + OUT["submit"])
+    SYMBOLS["kaamer_%ssearch_batch" % _p] = (C.c_int, HANDLE + [C.POINTER(BatchIn)] + FULL_OUT)
+    SYMBOLS["kaamer_%swait_batch" % _p] = (C.c_int, HANDLE + FULL_OUT)
+    SYMBOLS["kaamer_%sfull_ticket_discard" % _p] = (None, HANDLE)
+
+# the streams on the three handle kinds; open forms: (handle, seq_type, min_k_ratio, min_k_match, max_results[, want_positions,
+# sub_matrix, gap_open, gap_extend, want_text], out)
+for _kind in ("stream", "replica_stream", "sharded_stream"):
+    for _form, _mid in (("", []), ("_pos", []), ("_aln", ALIGN)):
+        SYMBOLS["kaamer_%s_open%s_flat" % (_kind, _form)] = (C.c_int, HANDLE + SEQ_TYPE + TOP + _mid + NEW)
+    SYMBOLS["kaamer_%s_push" % _kind] = (C.c_int, HANDLE + BATCH)
+    SYMBOLS["kaamer_%s_pop" % _kind] = (C.c_int, HANDLE + OUT["search"])
+    SYMBOLS["kaamer_%s_pending" % _kind] = (C.c_uint32, HANDLE)
+    SYMBOLS["kaamer_%s_close" % _kind] = (None, HANDLE)
+
+# the whole-file drivers with the bitmaps / alignments of the reported hits: (handle, path, format, strict_scanner, seq_type,
+# min_k_ratio, min_k_match, max_results, want_positions, want_aln, sub_matrix, gap_open, gap_extend, want_text, chunk_seqs,
+# chunk_bytes, in_flight, cb, user, total)
+for _name in ("kaamer_search_file_opts", "kaamer_sharded_search_file"):
+    SYMBOLS[_name] = (C.c_int, HANDLE + FILE_IN + SEQ_TYPE + TOP + ALIGN_FILE + CHUNKS + CB)
+
+# the calls that take query text (FASTQ or FASTA text, BGZF blocks of FASTQ) and may write the response on the device:
+# (handle, <the kind's head>, min_k_ratio, min_k_match, max_results, <what the format adds>, out)
+for _kind, _head in TEXT_HEAD.items():
+    for _verb, _out in OUT.items():
+        for _form, _tail in TEXT_TAIL.items():
+            SYMBOLS["kaamer_%s_%s_top%s_flat" % (_verb, _kind, _form)] = (C.c_int, HANDLE + _head + TOP + _tail + _out)
+
+# the device stages that write the TSV rows / the JSON objects, and what the text calls return of them
+for _kind, _in, _res in (("tsv", TsvRowsIn, TsvRowsResult), ("json", JsonRowsIn, JsonRowsResult)):
+    SYMBOLS["kaamer_%s_stage_create" % _kind] = (C.c_int, HANDLE + [C.c_uint32, C.c_uint64] + NEW)
+    SYMBOLS["kaamer_%s_stage_free" % _kind] = (None, HANDLE)
+    # (stage, rows_in, d_out, out_cap, stream, result)
+    SYMBOLS["kaamer_%s_rows_device" % _kind] = (C.c_int, HANDLE + [C.POINTER(_in), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(_res)])
+    SYMBOLS["kaamer_%s_rows_finish" % _kind] = (C.c_int, HANDLE + [C.c_void_p, C.POINTER(C.c_uint64)])
+    SYMBOLS["kaamer_%s_geometry" % _kind] = (None, [C.POINTER(C.c_uint32)])
+    SYMBOLS["kaamer_batch_top_%s" % _kind] = (C.c_int, HANDLE + [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64))])
+    SYMBOLS["kaamer_index_set_%s_bounds" % _kind] = (C.c_int, HANDLE + [C.c_uint64, C.c_uint64])
+
+for _name in ("sharded_exchange_info", "sharded_positions_info", "index_align_info", "sharded_align_info", "sharded_align_stage_info",
+              "tsv_aln_info", "index_tsv_aln_info", "index_subject_text_info", "index_subject_json_info"):
+    SYMBOLS["kaamer_" + _name] = INFO
+for _name in ("index_attach_proteins", "sharded_index_attach_proteins", "replicas_attach_proteins", "index_attach_subject_text",
+              "index_attach_subject_json"):
+    SYMBOLS["kaamer_" + _name] = ATTACH
+
 SHARDED_SETS = 3   # KAAMER_SHARDED_SETS
 FASTA, TSV, EMBL, GBK = 0, 1, 2, 3   # the `format` of kaamer_makedb_text / _range
 MAKEDB_LENGTH_ALL = 2 ** 63 - 1      # the default of -length (cmd/kaamer-db/main.go:142: uint(MaxInt))
@@ -602,6 +506,11 @@ def lib():
     return L
 
 
+def error(rc):
+    """the KaamerError of a return code, with the message the library kept for it"""
+    return KaamerError(rc, (lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
+
+
 def check(rc):
     if rc != OK:
-        raise KaamerError(rc, (lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
+        raise error(rc)

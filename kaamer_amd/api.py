@@ -21,11 +21,67 @@ def pack_sequences(seqs):
     return buf, offs
 
 
-class Image:
-    """Host copy of one shard's table (the builder's output)."""
+def packed_batch(seqs=None, packed=None):
+    """seqs, or packed=(buf, offs) -> (buf u8, offs u64, (seqs pointer or None, offsets pointer, n_seqs)): the contiguous
+    arrays, which the caller holds across the call, and the packed-batch arguments that point into them"""
+    buf, offs = packed if packed is not None else pack_sequences(seqs)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    return buf, offs, (buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1)
+
+
+def _proteins_args(seqs, packed, ids):
+    """the builders' (seqs, offsets, ids, n_proteins) -> (what keeps the arrays alive, the four arguments)"""
+    buf, offs, batch = packed_batch(seqs, packed)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32) if ids is not None else None
+    return (buf, offs, ids), (buf.ctypes.data, batch[1], ids.ctypes.data if ids is not None else None, batch[2])
+
+
+def _new(fn, *args):
+    """fn(*args, &handle), checked -> the handle"""
+    h = C.c_void_p()
+    abi.check(fn(*args, C.byref(h)))
+    return h
+
+
+def _u64s(fn, n, *args):
+    """fn(*args, out) with out a u64 array of n, checked -> the n values"""
+    out = (C.c_uint64 * n)()
+    abi.check(fn(*args, out))
+    return [int(v) for v in out]
+
+
+def _info(fn, handle, n, names):
+    """an info getter of the library, which fills n u64 -> dict of the first len(names) of them"""
+    return dict(zip(names, _u64s(fn, n, handle)))
+
+
+class _Handle:
+    """One object of the library behind `_h`: close() frees it through the function _FREE names, once, and __del__ closes
+    what was not closed without ever raising."""
+    _FREE = None
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
+        self._h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+
+    def _free(self, h):
+        getattr(abi.lib(), self._FREE)(h)
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            self._free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Image(_Handle):
+    """Host copy of one shard's table (the builder's output)."""
+    _FREE = "kaamer_image_free"
 
     @classmethod
     def from_pairs(cls, keys, ids, shard=0, n_shards=1, load_factor=0.5):
@@ -34,31 +90,15 @@ class Image:
         pairs = np.empty((len(keys), 2), dtype=np.uint32)
         pairs[:, 0] = keys
         pairs[:, 1] = ids
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_image_build_pairs(pairs.ctypes.data, len(keys), shard, n_shards,
-                                                     load_factor, C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_image_build_pairs, pairs.ctypes.data, len(keys), shard, n_shards, load_factor))
 
     @classmethod
     def from_proteins(cls, seqs=None, ids=None, packed=None, shard=0, n_shards=1, load_factor=0.5, device=None):
         """device=None: the host builder; device=d: the same image built on GPU d (byte-identical)."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        idp = None
-        if ids is not None:
-            ids = np.ascontiguousarray(ids, dtype=np.uint32)
-            idp = ids.ctypes.data
-        h = C.c_void_p()
+        keep, proteins = _proteins_args(seqs, packed, ids)
         if device is None:
-            abi.check(abi.lib().kaamer_image_build_proteins(buf.ctypes.data, offs.ctypes.data, idp,
-                                                            len(offs) - 1, shard, n_shards, load_factor,
-                                                            C.byref(h)))
-        else:
-            abi.check(abi.lib().kaamer_image_build_proteins_device(buf.ctypes.data, offs.ctypes.data, idp,
-                                                                   len(offs) - 1, shard, n_shards, load_factor,
-                                                                   int(device), C.byref(h)))
-        return cls(h.value)
+            return cls(_new(abi.lib().kaamer_image_build_proteins, *proteins, shard, n_shards, load_factor))
+        return cls(_new(abi.lib().kaamer_image_build_proteins_device, *proteins, shard, n_shards, load_factor, int(device)))
 
     @classmethod
     def merge(cls, images, load_factor=0.5, device=None):
@@ -66,18 +106,13 @@ class Image:
         device=d: the same image made on GPU d (byte-identical)."""
         images = list(images)
         arr = (C.c_void_p * max(1, len(images)))(*[im._h for im in images])
-        h = C.c_void_p()
         if device is None:
-            abi.check(abi.lib().kaamer_image_merge(arr, len(images), load_factor, C.byref(h)))
-        else:
-            abi.check(abi.lib().kaamer_image_merge_device(arr, len(images), load_factor, int(device), C.byref(h)))
-        return cls(h.value)
+            return cls(_new(abi.lib().kaamer_image_merge, arr, len(images), load_factor))
+        return cls(_new(abi.lib().kaamer_image_merge_device, arr, len(images), load_factor, int(device)))
 
     @classmethod
     def load(cls, path):
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_image_load(str(path).encode(), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_image_load, str(path).encode()))
 
     def save(self, path):
         abi.check(abi.lib().kaamer_image_save(self._h, str(path).encode()))
@@ -98,31 +133,16 @@ class Image:
             abi.lib().kaamer_image_get(self._h, int(key), out.ctypes.data, n)
         return out
 
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_image_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Proteins:
+class Proteins(_Handle):
     """What makedb accepts from a database file (ids, sequences, annotations): kaamer_makedb_fasta / _tsv
     (pkg/makedb/inputFASTA.go, inputTSV.go) and the table kaamer_fetch_hits reads (search.go:454-470)."""
-
-    def __init__(self, handle):
-        self._h = C.c_void_p(handle)
+    _FREE = "kaamer_proteins_free"
 
     @classmethod
     def _make(cls, fn, text):
         text = bytes(text)
-        h = C.c_void_p()
-        abi.check(fn(text, len(text), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(fn, text, len(text)))
 
     @classmethod
     def from_fasta(cls, text):
@@ -145,25 +165,19 @@ class Proteins:
         """kaamer_makedb_text_range: fmt is abi.FASTA / TSV / EMBL / GBK; offset / length are kaamer-db -make's -offset / -length
         (length=None: the flag's default, the rest of the file)."""
         text = bytes(text)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_makedb_text_range(text, len(text), int(fmt), int(bool(strict_scanner)), int(offset),
-                                                     abi.MAKEDB_LENGTH_ALL if length is None else int(length), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_makedb_text_range, text, len(text), int(fmt), int(bool(strict_scanner)), int(offset),
+                        abi.MAKEDB_LENGTH_ALL if length is None else int(length)))
 
     @classmethod
     def merge(cls, tables):
         """kaamer-db -merge on the protein tables (kaamer_proteins_merge): records in argument order, a later record of an id wins"""
         tables = list(tables)
         arr = (C.c_void_p * max(1, len(tables)))(*[t._h for t in tables])
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_proteins_merge(arr, len(tables), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_proteins_merge, arr, len(tables)))
 
     @classmethod
     def load(cls, path):
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_proteins_load(str(path).encode(), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_proteins_load, str(path).encode()))
 
     def save(self, path):
         abi.check(abi.lib().kaamer_proteins_save(self._h, str(path).encode()))
@@ -195,12 +209,9 @@ class Proteins:
         return dict(NumberOfProteins=out[0], NumberOfAA=out[1], NumberOfKmers=out[2], Features=self.feature_names)
 
     def image(self, shard=0, n_shards=1, load_factor=0.5, device=None):
-        h = C.c_void_p()
         if device is None:
-            abi.check(abi.lib().kaamer_image_build_makedb(self._h, shard, n_shards, load_factor, C.byref(h)))
-        else:
-            abi.check(abi.lib().kaamer_image_build_makedb_device(self._h, shard, n_shards, load_factor, int(device), C.byref(h)))
-        return Image(h.value)
+            return Image(_new(abi.lib().kaamer_image_build_makedb, self._h, shard, n_shards, load_factor))
+        return Image(_new(abi.lib().kaamer_image_build_makedb_device, self._h, shard, n_shards, load_factor, int(device)))
 
     def fetch_hits(self, ids):
         """[None | dict(EntryId, Sequence, Length, Features)] per protein id (protein.proto)"""
@@ -219,17 +230,6 @@ class Proteins:
                             Length=e.length,
                             Features={names[i]: blob[fo[i] - fo[0]:fo[i + 1] - fo[0]] for i in range(e.n_features)}))
         return out
-
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_proteins_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def build_image_from_proteins(seqs, ids=None, **kw):
@@ -442,40 +442,69 @@ class BatchResult:
         return dict(zip(self.hit_pid[a:b].tolist(), self.hit_first_pos[a:b].tolist()))
 
 
-class Index:
+def _take_top(out):
+    """a kaamer_batch_top the caller owns -> its TopResult (copied out); the C object is freed"""
+    try:
+        return TopResult(out)
+    finally:
+        abi.lib().kaamer_batch_top_free(out)
+
+
+def _batch_call(ix, wait, seqs, packed, seq_type, want_positions, flat=True):
+    """kaamer_[sharded_]{search,submit}_batch[_flat]: the full hit lists of a packed batch on an Index or a ShardedIndex.
+    wait: search (-> BatchResult), else submit (-> FullTicket)"""
+    buf, offs, batch = packed_batch(seqs, packed)
+    stem = "kaamer_%s%s_batch" % (ix._PREFIX, "search" if wait else "submit")
+    out = C.POINTER(abi.BatchOut)() if wait else C.c_void_p()
+    if flat:
+        abi.check(getattr(abi.lib(), stem + "_flat")(ix._h, *batch, seq_type, int(want_positions), C.byref(out)))
+    else:
+        bi = abi.BatchIn(*batch, seq_type, int(want_positions))
+        abi.check(getattr(abi.lib(), stem)(ix._h, C.byref(bi), C.byref(out)))
+    return BatchResult(out) if wait else FullTicket(out, sharded=bool(ix._PREFIX))
+
+
+def _batch_top_call(ix, wait, seqs, packed, seq_type, top, want_positions, align, flat=True):
+    """kaamer_[sharded_]{search,submit}_batch_top[_aln_flat|_pos_flat|_flat]: the reported hits of a packed batch on an Index
+    or a ShardedIndex.  top: (min_k_ratio, min_k_match, max_results); the form is `align`'s, else want_positions', else the
+    flat or the struct one.  wait: search (-> TopResult), else submit (-> TopTicket)"""
+    buf, offs, batch = packed_batch(seqs, packed)
+    stem = "kaamer_%s%s_batch_top" % (ix._PREFIX, "search" if wait else "submit")
+    out = C.POINTER(abi.BatchTop)() if wait else C.c_void_p()
+    if align is not None:
+        abi.check(getattr(abi.lib(), stem + "_aln_flat")(ix._h, *batch, seq_type, *top, int(bool(want_positions)), *_align_args(align),
+                                                         C.byref(out)))
+    elif want_positions or flat:
+        abi.check(getattr(abi.lib(), stem + ("_pos_flat" if want_positions else "_flat"))(ix._h, *batch, seq_type, *top, C.byref(out)))
+    else:
+        bi = abi.BatchIn(*batch, seq_type, 0)
+        to = abi.TopnOpts(*top, 0, None, None, 0, 0)
+        abi.check(getattr(abi.lib(), stem)(ix._h, C.byref(bi), C.byref(to), C.byref(out)))
+    return _take_top(out) if wait else TopTicket(out, sharded=bool(ix._PREFIX))
+
+
+class Index(_Handle):
     """The table resident in one device's HBM."""
+    _FREE, _PREFIX, _STREAM = "kaamer_index_close", "", "stream"
 
     def __init__(self, handle, device):
-        self._h = C.c_void_p(handle)
+        super().__init__(handle)
         self.device = device
         self.proteins = None   # attach_proteins
 
     @classmethod
     def from_image(cls, image, device=0):
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_open_image(image._h, device, C.byref(h)))
-        return cls(h.value, device)
+        return cls(_new(abi.lib().kaamer_index_open_image, image._h, device), device)
 
     @classmethod
     def from_proteins(cls, seqs=None, ids=None, packed=None, shard=0, n_shards=1, load_factor=0.5, device=0):
         """The table built on the device it is searched on (kaamer_index_build_proteins): no image in between."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        idp = None
-        if ids is not None:
-            ids = np.ascontiguousarray(ids, dtype=np.uint32)
-            idp = ids.ctypes.data
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_build_proteins(buf.ctypes.data, offs.ctypes.data, idp, len(offs) - 1, shard,
-                                                        n_shards, load_factor, int(device), C.byref(h)))
-        return cls(h.value, device)
+        keep, proteins = _proteins_args(seqs, packed, ids)
+        return cls(_new(abi.lib().kaamer_index_build_proteins, *proteins, shard, n_shards, load_factor, int(device)), device)
 
     @classmethod
     def open(cls, path, device=0):
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_open(str(path).encode(), device, C.byref(h)))
-        return cls(h.value, device)
+        return cls(_new(abi.lib().kaamer_index_open, str(path).encode(), device), device)
 
     def stats(self):
         s = abi.ImageStats()
@@ -485,28 +514,11 @@ class Index:
     def search(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False, flat=True):
         """Host-buffer form (kaamer_search_batch_flat: the entry point a cgo shim binds; flat=False: the struct form
         kaamer_search_batch)."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = C.POINTER(abi.BatchOut)()
-        if flat:
-            abi.check(abi.lib().kaamer_search_batch_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                         len(offs) - 1, seq_type, int(want_positions), C.byref(out)))
-        else:
-            bi = abi.BatchIn(buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type,
-                             int(want_positions))
-            abi.check(abi.lib().kaamer_search_batch(self._h, C.byref(bi), C.byref(out)))
-        return BatchResult(out)
+        return _batch_call(self, True, seqs, packed, seq_type, want_positions, flat)
 
     def submit(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False):
         """kaamer_submit_batch_flat -> a ticket whose wait() returns the BatchResult (full hit lists)"""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        t = C.c_void_p()
-        abi.check(abi.lib().kaamer_submit_batch_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1,
-                                                     seq_type, int(want_positions), C.byref(t)))
-        return FullTicket(t)
+        return _batch_call(self, False, seqs, packed, seq_type, want_positions)
 
     def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
                    want_positions=False, align=None):
@@ -517,29 +529,7 @@ class Index:
         align: dict(sub_matrix="blosum62", gap_open=11, gap_extend=1, text=True) -- every reported hit aligned with its
         query in the same call (kaamer_search_batch_top_aln_flat; needs attach_proteins): TopResult.alignments, hits in
         BitScore order."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = C.POINTER(abi.BatchTop)()
-        if align is not None:
-            abi.check(abi.lib().kaamer_search_batch_top_aln_flat(
-                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
-                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
-                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(out)))
-        elif want_positions:
-            abi.check(abi.lib().kaamer_search_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                                 len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
-        elif flat:
-            abi.check(abi.lib().kaamer_search_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                             len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
-        else:
-            bi = abi.BatchIn(buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, 0)
-            to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
-            abi.check(abi.lib().kaamer_search_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return _batch_top_call(self, True, seqs, packed, seq_type, (min_k_ratio, min_k_match, max_results), want_positions, align, flat)
 
     def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
                    want_positions=False, align=None):
@@ -548,26 +538,7 @@ class Index:
         want_positions: kaamer_submit_batch_top_pos_flat (the bitmaps of the reported hits come along).
         align: as search_top's -- kaamer_submit_batch_top_aln_flat: the reported hits aligned with their queries in the
         same call (needs attach_proteins); the ticket's TopResult carries `alignments`, hits in BitScore order."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        t = C.c_void_p()
-        if align is not None:   # kaamer_submit_batch_top_aln_flat (search_top's `align`)
-            abi.check(abi.lib().kaamer_submit_batch_top_aln_flat(
-                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
-                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
-                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(t)))
-        elif want_positions:
-            abi.check(abi.lib().kaamer_submit_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                                 len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
-        elif flat:
-            abi.check(abi.lib().kaamer_submit_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                             len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(t)))
-        else:
-            bi = abi.BatchIn(buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, 0)
-            to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
-            abi.check(abi.lib().kaamer_submit_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(t)))
-        return TopTicket(t)
+        return _batch_top_call(self, False, seqs, packed, seq_type, (min_k_ratio, min_k_match, max_results), want_positions, align, flat)
 
     def _text_call(self, kind, data, extra, top, tsv, wait, align=None, json=None):
         """kaamer_{search,submit}_{kind}_top[_tsv|_aln_tsv]_flat -- kind: text, fasta or bgzf; extra: the kind's arguments
@@ -585,12 +556,7 @@ class Index:
         if json is not None:
             more = (int(bool(json.get("positions"))),)
         abi.check(fn(self._h, data, len(data), *extra, *top, *more, C.byref(out)))
-        if not wait:
-            return TopTicket(out)
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return _take_top(out) if wait else TopTicket(out)
 
     def search_text_top(self, text, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, fmt="fastq", tsv=None, align=None, json=None):
         """kaamer_search_text_top_flat: FASTQ text (bytes) in, the reported hits out -- the text is parsed on the device
@@ -638,9 +604,7 @@ class Index:
     def tsv_aln_info(self):
         """kaamer_index_tsv_aln_info -> dict(host_batches: batches of the align + tsv text calls whose rows the host printed,
         raw_count: raw scores the stages' table holds)"""
-        c = (C.c_uint64 * 2)()
-        abi.check(abi.lib().kaamer_index_tsv_aln_info(self._h, c))
-        return dict(host_batches=int(c[0]), raw_count=int(c[1]))
+        return _info(abi.lib().kaamer_index_tsv_aln_info, self._h, 2, ("host_batches", "raw_count"))
 
     def set_tsv_aln_raw_count(self, n):
         """kaamer_index_set_tsv_aln_raw_count (a test entry): the stages' table holds the first n raw scores only; 0: all"""
@@ -668,15 +632,11 @@ class Index:
 
     def subject_json_info(self):
         """kaamer_index_subject_json_info -> dict(table_bytes, entries, max_entry)"""
-        out = (C.c_uint64 * 4)()
-        abi.check(abi.lib().kaamer_index_subject_json_info(self._h, out))
-        return dict(table_bytes=int(out[0]), entries=int(out[1]), max_entry=int(out[2]))
+        return _info(abi.lib().kaamer_index_subject_json_info, self._h, 4, ("table_bytes", "entries", "max_entry"))
 
     def subject_text_info(self):
         """kaamer_index_subject_text_info -> dict"""
-        out = (C.c_uint64 * 4)()
-        abi.check(abi.lib().kaamer_index_subject_text_info(self._h, out))
-        return dict(zip(("table_bytes", "entries", "max_row_suffix", "features"), (int(v) for v in out)))
+        return _info(abi.lib().kaamer_index_subject_text_info, self._h, 4, ("table_bytes", "entries", "max_row_suffix", "features"))
 
     def set_json_bounds(self, nbytes, objects):
         """kaamer_index_set_json_bounds: the first bounds (bytes, objects) of the json=... calls on every slot; 0: the rule"""
@@ -688,10 +648,8 @@ class Index:
 
     def align_info(self):
         """kaamer_index_align_info -> dict"""
-        out = (C.c_uint64 * 8)()
-        abi.check(abi.lib().kaamer_index_align_info(self._h, out))
-        return dict(zip(("table_bytes", "entries", "max_subject_len", "number_of_aa", "budget_bytes", "waves", "slab_bytes", "long_waves"),
-                        (int(v) for v in out)))
+        return _info(abi.lib().kaamer_index_align_info, self._h, 8,
+                     ("table_bytes", "entries", "max_subject_len", "number_of_aa", "budget_bytes", "waves", "slab_bytes", "long_waves"))
 
     def set_align_budget(self, nbytes):
         """kaamer_index_set_align_budget: bytes of direction array one call's alignment stage may hold; 0: the default"""
@@ -701,43 +659,27 @@ class Index:
         """kaamer_index_set_top_positions_bound: the first bitmap bound (u64 words) of the want_positions calls; 0: the rule"""
         abi.check(abi.lib().kaamer_index_set_top_positions_bound(self._h, int(words)))
 
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_index_close(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ShardedIndex:
+class ShardedIndex(_Handle):
     """kaamer_index_open_sharded*: one handle over W hash-prefix shards, each resident on its own device, driven from
     one process (no communicator)."""
+    _FREE, _PREFIX, _STREAM = "kaamer_sharded_index_close", "sharded_", "sharded_stream"
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
+        super().__init__(handle)
         self.proteins = None   # attach_proteins
 
     @classmethod
     def from_images(cls, images, devices):
         n = len(images)
         arr = (C.c_void_p * n)(*[im._h for im in images])
-        dev = (C.c_int * n)(*devices)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_open_sharded_images(arr, dev, n, C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_index_open_sharded_images, arr, (C.c_int * n)(*devices), n))
 
     @classmethod
     def open(cls, paths, devices):
         n = len(paths)
         arr = (C.c_char_p * n)(*[str(p).encode() for p in paths])
-        dev = (C.c_int * n)(*devices)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_open_sharded(arr, dev, n, C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_index_open_sharded, arr, (C.c_int * n)(*devices), n))
 
     def search_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, flat=True,
                    want_positions=False, align=None):
@@ -745,50 +687,14 @@ class ShardedIndex:
         bitmaps of the reported hits come along (kaamer_sharded_search_batch_top_pos_flat; TopResult.positions).
         align: as Index.search_top's -- every reported hit aligned with its query in the same call
         (kaamer_sharded_search_batch_top_aln_flat; needs attach_proteins): TopResult.alignments, hits in BitScore order."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = C.POINTER(abi.BatchTop)()
-        if align is not None:
-            abi.check(abi.lib().kaamer_sharded_search_batch_top_aln_flat(
-                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
-                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
-                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(out)))
-        elif want_positions:
-            abi.check(abi.lib().kaamer_sharded_search_batch_top_pos_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                                         len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results,
-                                                                         C.byref(out)))
-        elif flat:
-            abi.check(abi.lib().kaamer_sharded_search_batch_top_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                                     len(offs) - 1, seq_type, min_k_ratio, min_k_match, max_results, C.byref(out)))
-        else:
-            bi = abi.BatchIn(buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, 0)
-            to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
-            abi.check(abi.lib().kaamer_sharded_search_batch_top(self._h, C.byref(bi), C.byref(to), C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return _batch_top_call(self, True, seqs, packed, seq_type, (min_k_ratio, min_k_match, max_results), want_positions, align, flat)
 
     def submit_top(self, seqs=None, packed=None, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10,
                    want_positions=False, align=None):
         """kaamer_sharded_submit_batch_top_flat -> a ticket (wait() -> TopResult); up to three calls in flight per handle.
         want_positions: kaamer_sharded_submit_batch_top_pos_flat (the bitmaps of the reported hits come along).
         align: as search_top's (kaamer_sharded_submit_batch_top_aln_flat)."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        t = C.c_void_p()
-        if align is not None:
-            abi.check(abi.lib().kaamer_sharded_submit_batch_top_aln_flat(
-                self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
-                max_results, int(bool(want_positions)), str(align.get("sub_matrix", "blosum62")).encode(), int(align.get("gap_open", 11)),
-                int(align.get("gap_extend", 1)), int(bool(align.get("text", True))), C.byref(t)))
-            return TopTicket(t, sharded=True)
-        fn = abi.lib().kaamer_sharded_submit_batch_top_pos_flat if want_positions else abi.lib().kaamer_sharded_submit_batch_top_flat
-        abi.check(fn(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type, min_k_ratio, min_k_match,
-                     max_results, C.byref(t)))
-        return TopTicket(t, sharded=True)
+        return _batch_top_call(self, False, seqs, packed, seq_type, (min_k_ratio, min_k_match, max_results), want_positions, align)
 
     def attach_proteins(self, proteins):
         """kaamer_sharded_index_attach_proteins: the table's Protein.Sequence entries become resident on the handle's
@@ -799,10 +705,8 @@ class ShardedIndex:
 
     def align_info(self):
         """kaamer_sharded_align_info -> dict"""
-        out = (C.c_uint64 * 8)()
-        abi.check(abi.lib().kaamer_sharded_align_info(self._h, out))
-        return dict(zip(("table_bytes", "largest_share", "entries", "max_subject_len", "number_of_aa", "segment_bytes", "need_bytes",
-                         "attempts"), (int(v) for v in out)))
+        return _info(abi.lib().kaamer_sharded_align_info, self._h, 8,
+                     ("table_bytes", "largest_share", "entries", "max_subject_len", "number_of_aa", "segment_bytes", "need_bytes", "attempts"))
 
     def set_align_timing(self, on=True):
         """kaamer_sharded_index_set_align_timing: HIP events around the gather, assemble and alignment stages of later calls"""
@@ -810,10 +714,8 @@ class ShardedIndex:
 
     def align_stage_info(self):
         """kaamer_sharded_align_stage_info -> dict (stage times in microseconds: zeros unless set_align_timing)"""
-        out = (C.c_uint64 * 8)()
-        abi.check(abi.lib().kaamer_sharded_align_stage_info(self._h, out))
-        return dict(zip(("timing", "gather_us", "assemble_us", "align_us", "ids_block_bytes", "waves", "slab_bytes", "long_waves"),
-                        (int(v) for v in out)))
+        return _info(abi.lib().kaamer_sharded_align_stage_info, self._h, 8,
+                     ("timing", "gather_us", "assemble_us", "align_us", "ids_block_bytes", "waves", "slab_bytes", "long_waves"))
 
     def set_align_budget(self, nbytes):
         """kaamer_sharded_index_set_align_budget: bytes of direction array each owner's alignment stage may hold; 0: the default"""
@@ -822,35 +724,16 @@ class ShardedIndex:
     def positions_info(self):
         """-> dict(ids_block_bytes, segment_bytes, need_words, attempts) of the last finished call with positions on the
         handle's first set (kaamer_sharded_positions_info)"""
-        out = (C.c_uint64 * 4)()
-        abi.check(abi.lib().kaamer_sharded_positions_info(self._h, out))
-        return {"ids_block_bytes": int(out[0]), "segment_bytes": int(out[1]), "need_words": int(out[2]), "attempts": int(out[3])}
+        return _info(abi.lib().kaamer_sharded_positions_info, self._h, 4, ("ids_block_bytes", "segment_bytes", "need_words", "attempts"))
 
     def search(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False, flat=True):
         """The full hit lists (PositionHits bitmaps with want_positions): what Index.search returns on an unsharded index
         of the whole database (kaamer_sharded_search_batch_flat; flat=False: the struct form)."""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        out = C.POINTER(abi.BatchOut)()
-        if flat:
-            abi.check(abi.lib().kaamer_sharded_search_batch_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                                 len(offs) - 1, seq_type, int(want_positions), C.byref(out)))
-        else:
-            bi = abi.BatchIn(buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1, seq_type,
-                             int(want_positions))
-            abi.check(abi.lib().kaamer_sharded_search_batch(self._h, C.byref(bi), C.byref(out)))
-        return BatchResult(out)
+        return _batch_call(self, True, seqs, packed, seq_type, want_positions, flat)
 
     def submit(self, seqs=None, packed=None, seq_type=abi.PROTEIN, want_positions=False):
         """kaamer_sharded_submit_batch_flat -> a ticket whose wait() returns the BatchResult (full hit lists)"""
-        buf, offs = packed if packed is not None else pack_sequences(seqs)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        t = C.c_void_p()
-        abi.check(abi.lib().kaamer_sharded_submit_batch_flat(self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data,
-                                                             len(offs) - 1, seq_type, int(want_positions), C.byref(t)))
-        return FullTicket(t, sharded=True)
+        return _batch_call(self, False, seqs, packed, seq_type, want_positions)
 
     def stream(self, seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10, want_positions=False, align=None):
         """kaamer_sharded_stream_open[_pos|_aln]_flat: a FIFO of at most abi.SHARDED_SETS chunks on the handle"""
@@ -859,50 +742,34 @@ class ShardedIndex:
     def search_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
                     chunk_seqs=1 << 20, chunk_bytes=1 << 28, in_flight=0, strict=False, on_chunk=None, want_positions=False, align=None):
         """kaamer_sharded_search_file: Replicas.search_file on the sharded handle (in_flight: chunks per handle)"""
-        return _search_file(abi.lib().kaamer_sharded_search_file, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
-                            chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, want_positions, align)
+        return _search_file(self, path, fmt, seq_type, (min_k_ratio, min_k_match, max_results), chunk_seqs, chunk_bytes, in_flight, strict,
+                            on_chunk, want_positions, align)
 
     def exchange_info(self):
         """-> dict(block_bytes, need_entries, queries, adaptive) of the last finished call on the handle's first set"""
-        out = (C.c_uint64 * 4)()
-        abi.check(abi.lib().kaamer_sharded_exchange_info(self._h, out))
-        return {"block_bytes": int(out[0]), "need_entries": int(out[1]), "queries": int(out[2]), "adaptive": bool(out[3])}
-
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_sharded_index_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        info = _info(abi.lib().kaamer_sharded_exchange_info, self._h, 4, ("block_bytes", "need_entries", "queries", "adaptive"))
+        info["adaptive"] = bool(info["adaptive"])
+        return info
 
 
-class Replicas:
+class Replicas(_Handle):
     """kaamer_index_open_replicas*: the same database resident on several devices of ONE process; chunks of a read set are
     dealt round-robin (kaamer_replica_stream_*), or a whole file is searched (kaamer_search_file)."""
+    _FREE, _STREAM = "kaamer_replicas_close", "replica_stream"
 
     CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(abi.BatchTop))
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
+        super().__init__(handle)
         self.proteins = None   # attach_proteins
 
     @classmethod
     def from_image(cls, image, devices):
-        dev = (C.c_int * len(devices))(*devices)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_open_replicas_image(image._h, dev, len(devices), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_index_open_replicas_image, image._h, (C.c_int * len(devices))(*devices), len(devices)))
 
     @classmethod
     def open(cls, path, devices):
-        dev = (C.c_int * len(devices))(*devices)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_index_open_replicas(str(path).encode(), dev, len(devices), C.byref(h)))
-        return cls(h.value)
+        return cls(_new(abi.lib().kaamer_index_open_replicas, str(path).encode(), (C.c_int * len(devices))(*devices), len(devices)))
 
     def __len__(self):
         return int(abi.lib().kaamer_replicas_count(self._h))
@@ -923,29 +790,15 @@ class Replicas:
         valid during the call: kaamer_reads_* accessors / api._reads_to_arrays).  -> summed counters
         want_positions / align (as Index.search_top's; align needs attach_proteins): kaamer_search_file_opts -- the
         TopResult of every chunk carries the bitmaps / the alignments of its reported hits."""
-        if not want_positions and align is None:
-            return _search_file(abi.lib().kaamer_search_file, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
-                                chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, None, None)
-        return _search_file(abi.lib().kaamer_search_file_opts, self._h, path, fmt, seq_type, min_k_ratio, min_k_match, max_results,
-                            chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, want_positions, align)
+        return _search_file(self, path, fmt, seq_type, (min_k_ratio, min_k_match, max_results), chunk_seqs, chunk_bytes, in_flight, strict,
+                            on_chunk, want_positions, align)
 
     TEXT_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(abi.BatchTop))
 
     @staticmethod
-    def _text_chunk_cb(on_chunk):
-        """the kaamer_text_chunk_cb of the text file drivers around on_chunk(first_seq, text bytes, TopResult) -> (the C
-        callback, the list that receives an exception of on_chunk)"""
-        err = []
-
-        def cb(user, first, text, length, spans, n_records, top):
-            try:
-                if on_chunk is not None:
-                    on_chunk(int(first), C.string_at(text, length), TopResult(top))
-                return 0
-            except BaseException as e:  # noqa: BLE001  (must not propagate through the C frames)
-                err.append(e)
-                return 1
-        return Replicas.TEXT_CHUNK_CB(cb), err
+    def _text_chunk(first, text, length, spans, n_records, top):
+        """what a kaamer_text_chunk_cb receives behind `user` -> on_chunk's (first_seq, text bytes, TopResult)"""
+        return int(first), C.string_at(text, length), TopResult(top)
 
     def search_text_file(self, path, fmt="fastq", seq_type=abi.READS, min_k_ratio=0.05, min_k_match=10, max_results=10,
                          chunk_text_bytes=1 << 28, in_flight=0, on_chunk=None, device_inflate=False):
@@ -954,42 +807,18 @@ class Replicas:
         TopResult's text_spans index `text`, its rep_query counts from the chunk's first record.  -> summed counters
         device_inflate (kaamer_search_text_file_opts): a BGZF file is inflated on the device, block by block; anything else
         in a gzip file falls back to the host inflater from that chunk on.  The concatenated texts are the same."""
-        c = abi.Counters()
-        cfn, err = Replicas._text_chunk_cb(on_chunk)
         args = (self._h, str(path).encode(), 1 if fmt == "fastq" else 0, seq_type, min_k_ratio, min_k_match, max_results, int(chunk_text_bytes), in_flight)
         if device_inflate:
-            rc = abi.lib().kaamer_search_text_file_opts(*args, 1, C.cast(cfn, C.c_void_p), None, C.byref(c))
-        else:
-            rc = abi.lib().kaamer_search_text_file(*args, C.cast(cfn, C.c_void_p), None, C.byref(c))
-        if err:
-            raise err[0]
-        abi.check(rc)
-        return c.as_dict()
+            return _drive_file(abi.lib().kaamer_search_text_file_opts, args + (1,), Replicas.TEXT_CHUNK_CB, Replicas._text_chunk, on_chunk)
+        return _drive_file(abi.lib().kaamer_search_text_file, args, Replicas.TEXT_CHUNK_CB, Replicas._text_chunk, on_chunk)
 
     def search_fasta_file(self, path, seq_type=abi.PROTEIN, min_k_ratio=0.05, min_k_match=10, max_results=10, chunk_text_bytes=1 << 28,
                           in_flight=0, on_chunk=None):
         """kaamer_search_fasta_file: the file's FASTA text (plain or gzip) is cut into chunks of about chunk_text_bytes at
         kaamer_text_cut_fasta, each parsed and searched on a replica (every chunk but the last with upper_last).
         on_chunk(first_seq, text bytes, TopResult) per chunk, in input order, as search_text_file's.  -> summed counters"""
-        c = abi.Counters()
-        cfn, err = Replicas._text_chunk_cb(on_chunk)
-        rc = abi.lib().kaamer_search_fasta_file(self._h, str(path).encode(), seq_type, min_k_ratio, min_k_match, max_results,
-                                                int(chunk_text_bytes), in_flight, C.cast(cfn, C.c_void_p), None, C.byref(c))
-        if err:
-            raise err[0]
-        abi.check(rc)
-        return c.as_dict()
-
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_replicas_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        args = (self._h, str(path).encode(), seq_type, min_k_ratio, min_k_match, max_results, int(chunk_text_bytes), in_flight)
+        return _drive_file(abi.lib().kaamer_search_fasta_file, args, Replicas.TEXT_CHUNK_CB, Replicas._text_chunk, on_chunk)
 
 
 def _tsv_args(tsv):
@@ -1001,11 +830,7 @@ def format_tsv_header(positions=False, annotations=False, proteins=None, align=F
     """kaamer_format_tsv_header, or with align kaamer_format_tsv_aln_header: the header line of the TSV response
     (search.go:645-660) -> bytes"""
     fn = abi.lib().kaamer_format_tsv_aln_header if align else abi.lib().kaamer_format_tsv_header
-    ph = proteins._h if proteins is not None else None
-    need = int(fn(int(bool(positions)), int(bool(annotations)), ph, None, 0))
-    buf = C.create_string_buffer(need + 1)
-    fn(int(bool(positions)), int(bool(annotations)), ph, buf, need + 1)
-    return buf.raw[:need]
+    return _sized(fn, int(bool(positions)), int(bool(annotations)), proteins._h if proteins is not None else None)
 
 
 def format_tsv(top, names, spans, proteins=None, positions=False, annotations=False, cap=None, align=False, seq_type=abi.PROTEIN):
@@ -1208,10 +1033,7 @@ def align_finish_pairs(pairs, number_of_aa, sub_matrix="blosum62", gap_open=11, 
 
 def format_double(value, mode):
     """kaamer_format_double: a float64 as the -aln rows print EValue (mode 0: "%e") or BitScore (mode 1: "%.2f") -> bytes"""
-    need = int(abi.lib().kaamer_format_double(float(value), int(mode), None, 0))
-    buf = C.create_string_buffer(need + 1)
-    abi.lib().kaamer_format_double(float(value), int(mode), buf, need + 1)
-    return buf.raw[:need]
+    return _sized(abi.lib().kaamer_format_double, float(value), int(mode))
 
 
 def format_doubles_device(d_values_ptr, n, mode, d_out_ptr):
@@ -1220,10 +1042,11 @@ def format_doubles_device(d_values_ptr, n, mode, d_out_ptr):
     abi.check(abi.lib().kaamer_tsv_format_doubles_device(C.c_void_p(d_values_ptr), int(n), int(mode), C.c_void_p(d_out_ptr)))
 
 
-def _geometry(fn):
-    g = (C.c_uint32 * 4)()
+def _geometry(fn, names=("tile", "window", "store", "threads")):
+    """a geometry getter of the library, which fills len(names) u32 -> dict"""
+    g = (C.c_uint32 * len(names))()
     fn(g)
-    return dict(tile=int(g[0]), window=int(g[1]), store=int(g[2]), threads=int(g[3]))
+    return dict(zip(names, (int(v) for v in g)))
 
 
 def tsv_geometry():
@@ -1232,35 +1055,23 @@ def tsv_geometry():
     return _geometry(abi.lib().kaamer_tsv_geometry)
 
 
-class _RowsStage:
+class _RowsStage(_Handle):
     """what TsvStage and JsonStage share: kaamer_{_KIND}_stage_create / _free and kaamer_{_KIND}_rows_finish"""
     _KIND = None
 
     def __init__(self, index, max_queries, max_units):
         self.index = index
-        h = C.c_void_p()
-        abi.check(getattr(abi.lib(), "kaamer_%s_stage_create" % self._KIND)(index._h, int(max_queries), int(max_units), C.byref(h)))
-        self._h = h
+        self._FREE = "kaamer_%s_stage_free" % self._KIND
+        super().__init__(_new(getattr(abi.lib(), "kaamer_%s_stage_create" % self._KIND), index._h, int(max_queries), int(max_units)))
 
     def finish(self, stream=0):
         c = (C.c_uint64 * 2)()
         rc = getattr(abi.lib(), "kaamer_%s_rows_finish" % self._KIND)(self._h, C.c_void_p(stream), c)
         if rc:
-            e = abi.KaamerError(rc, (abi.lib().kaamer_last_error() or b"").decode("utf-8", "replace"))
+            e = abi.error(rc)
             e.counts = (int(c[0]), int(c[1]))
             raise e
         return int(c[0]), int(c[1])
-
-    def close(self):
-        if self._h:
-            getattr(abi.lib(), "kaamer_%s_stage_free" % self._KIND)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class TsvStage(_RowsStage):
@@ -1292,9 +1103,7 @@ class TsvStage(_RowsStage):
     def aln_info(self):
         """kaamer_tsv_aln_info -> dict(outside: pairs of the last -aln call with a raw score outside the table, table: raw
         scores it holds, tables: tables filled so far)"""
-        c = (C.c_uint64 * 4)()
-        abi.check(abi.lib().kaamer_tsv_aln_info(self._h, c))
-        return dict(outside=int(c[0]), table=int(c[1]), tables=int(c[2]))
+        return _info(abi.lib().kaamer_tsv_aln_info, self._h, 4, ("outside", "table", "tables"))
 
     def finish(self, stream=0):
         """kaamer_tsv_rows_finish -> (rows, bytes); KaamerError E_CAPACITY (with .counts = what was needed) when they did not
@@ -1334,118 +1143,104 @@ def _align_args(align):
             int(bool(align.get("text", True))))
 
 
-def _search_file(fn, handle, path, fmt, seq_type, min_k_ratio, min_k_match, max_results, chunk_seqs, chunk_bytes, in_flight, strict, on_chunk,
-                 want_positions, align):
-    """the three whole-file calls behind one callback wrapper; want_positions is None for kaamer_search_file, which has no
-    such arguments"""
+def _drive_file(fn, args, cb_type, chunk_args, on_chunk):
+    """one whole-file driver: fn(*args, cb, user, total), its callback (a cb_type) wrapped around on_chunk -> summed counters.
+    chunk_args: what the callback receives behind `user` -> on_chunk's arguments.  An exception of on_chunk stops the run and
+    is raised here"""
     err = []
 
-    def cb(user, first, reads, top):
+    def cb(user, *chunk):
         try:
             if on_chunk is not None:
-                on_chunk(int(first), C.c_void_p(reads), TopResult(top))
+                on_chunk(*chunk_args(*chunk))
             return 0
         except BaseException as e:  # noqa: BLE001  (must not propagate through the C frames)
             err.append(e)
             return 1
     c = abi.Counters()
-    cfn = Replicas.CHUNK_CB(cb)
-    head = (handle, str(path).encode(), 1 if fmt == "fastq" else 0, int(strict), seq_type, min_k_ratio, min_k_match, max_results)
-    tail = (chunk_seqs, chunk_bytes, in_flight, C.cast(cfn, C.c_void_p), None, C.byref(c))
-    if want_positions is None:
-        rc = fn(*(head + tail))
-    else:
-        aln = _align_args(align) if align is not None else (None, 0, 0, 0)
-        rc = fn(*(head + (int(bool(want_positions)), int(align is not None)) + aln + tail))
+    cfn = cb_type(cb)
+    rc = fn(*args, C.cast(cfn, C.c_void_p), None, C.byref(c))
     if err:
         raise err[0]
     abi.check(rc)
     return c.as_dict()
 
 
-class FullTicket:
+def _search_file(ix, path, fmt, seq_type, top, chunk_seqs, chunk_bytes, in_flight, strict, on_chunk, want_positions, align):
+    """the three whole-file calls of the host reader: kaamer_sharded_search_file on a ShardedIndex; on a Replicas set
+    kaamer_search_file_opts, or kaamer_search_file, which has no such arguments, when neither bitmaps nor alignments are asked
+    for.  on_chunk(first_seq, reads_handle, TopResult)"""
+    opts = (int(bool(want_positions)), int(align is not None)) + (_align_args(align) if align is not None else (None, 0, 0, 0))
+    if isinstance(ix, ShardedIndex):
+        fn = abi.lib().kaamer_sharded_search_file
+    elif want_positions or align is not None:
+        fn = abi.lib().kaamer_search_file_opts
+    else:
+        fn, opts = abi.lib().kaamer_search_file, ()
+    args = (ix._h, str(path).encode(), 1 if fmt == "fastq" else 0, int(strict), seq_type, *top, *opts, chunk_seqs, chunk_bytes, in_flight)
+    return _drive_file(fn, args, Replicas.CHUNK_CB, lambda first, reads, top_: (int(first), C.c_void_p(reads), TopResult(top_)), on_chunk)
+
+
+class _Ticket(_Handle):
+    """One batch in flight on an Index or (sharded=True) a ShardedIndex: wait() exactly once -- the ticket is empty after it,
+    even if it raises -- and a ticket dropped unwaited is discarded: its slot goes back to the pool instead of staying busy
+    for good.  A subclass names its wait and discard symbols, the result's C type and what takes it."""
+    _WAIT = _DISCARD = _OUT = _take = None
+
+    def __init__(self, handle, sharded=False):
+        super().__init__(handle)
+        self._sharded = sharded
+
+    def _symbol(self, name):
+        return getattr(abi.lib(), "kaamer_%s%s" % ("sharded_" if self._sharded else "", name))
+
+    def wait(self):
+        out = C.POINTER(self._OUT)()
+        h, self._h = self._h, None
+        abi.check(self._symbol(self._WAIT)(h, C.byref(out)))
+        return self._take(out)
+
+    def _free(self, h):
+        self._symbol(self._DISCARD)(h)
+
+    discard = _Handle.close
+
+
+class FullTicket(_Ticket):
     """one full-hit-list batch in flight (kaamer_full_ticket / kaamer_sharded_full_ticket); wait() exactly once,
     discarded when dropped"""
-
-    def __init__(self, handle, sharded=False):
-        self._h, self._sharded = handle, sharded
-
-    def wait(self):
-        out = C.POINTER(abi.BatchOut)()
-        h, self._h = self._h, None
-        L = abi.lib()
-        abi.check((L.kaamer_sharded_wait_batch if self._sharded else L.kaamer_wait_batch)(h, C.byref(out)))
-        return BatchResult(out)
-
-    def discard(self):
-        h, self._h = self._h, None
-        if h:
-            L = abi.lib()
-            (L.kaamer_sharded_full_ticket_discard if self._sharded else L.kaamer_full_ticket_discard)(h)
-
-    def __del__(self):
-        try:
-            self.discard()
-        except Exception:
-            pass
+    _WAIT, _DISCARD, _OUT, _take = "wait_batch", "full_ticket_discard", abi.BatchOut, staticmethod(BatchResult)
 
 
-class TopTicket:
+class TopTicket(_Ticket):
     """one batch in flight (kaamer_ticket / kaamer_sharded_ticket); wait() exactly once.  A ticket dropped unwaited is
     discarded (kaamer_ticket_discard): its slot goes back to the pool instead of staying busy for good."""
-
-    def __init__(self, handle, sharded=False):
-        self._h, self._sharded = handle, sharded
-
-    def wait(self):
-        out = C.POINTER(abi.BatchTop)()
-        h, self._h = self._h, None
-        L = abi.lib()
-        abi.check((L.kaamer_sharded_wait_batch_top if self._sharded else L.kaamer_wait_batch_top)(h, C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            L.kaamer_batch_top_free(out)
-
-    def discard(self):
-        h, self._h = self._h, None
-        if h:
-            L = abi.lib()
-            (L.kaamer_sharded_ticket_discard if self._sharded else L.kaamer_ticket_discard)(h)
-
-    def __del__(self):
-        try:
-            self.discard()
-        except Exception:
-            pass
+    _WAIT, _DISCARD, _OUT, _take = "wait_batch_top", "ticket_discard", abi.BatchTop, staticmethod(_take_top)
 
 
-class TopStream:
+class TopStream(_Handle):
     """kaamer_stream_* / kaamer_replica_stream_* / kaamer_sharded_stream_*: a FIFO of batches with fixed options (push
     chunk i + 1 while chunk i is searched) on an Index, a Replicas set or a ShardedIndex"""
 
     def __init__(self, index, seq_type, min_k_ratio, min_k_match, max_results, want_positions=False, align=None):
-        L = abi.lib()
-        kind = "sharded_stream" if isinstance(index, ShardedIndex) else "replica_stream" if isinstance(index, Replicas) else "stream"
+        L, kind, top = abi.lib(), index._STREAM, (min_k_ratio, min_k_match, max_results)
         self._fn = {k: getattr(L, "kaamer_%s_%s" % (kind, k)) for k in ("push", "pop", "pending", "close")}
-        h = C.c_void_p()
+        self.index = index
         if align is not None:
-            abi.check(getattr(L, "kaamer_%s_open_aln_flat" % kind)(index._h, seq_type, min_k_ratio, min_k_match, max_results,
-                                                                   int(bool(want_positions)), *(_align_args(align) + (C.byref(h),))))
+            h = _new(getattr(L, "kaamer_%s_open_aln_flat" % kind), index._h, seq_type, *top, int(bool(want_positions)), *_align_args(align))
         elif want_positions:
-            abi.check(getattr(L, "kaamer_%s_open_pos_flat" % kind)(index._h, seq_type, min_k_ratio, min_k_match, max_results, C.byref(h)))
-        elif kind == "stream":
-            to = abi.TopnOpts(min_k_ratio, min_k_match, max_results, 0, None, None, 0, 0)
-            abi.check(L.kaamer_stream_open(index._h, seq_type, C.byref(to), C.byref(h)))
+            h = _new(getattr(L, "kaamer_%s_open_pos_flat" % kind), index._h, seq_type, *top)
+        elif kind == "stream":   # the struct form
+            to = abi.TopnOpts(*top, 0, None, None, 0, 0)
+            h = _new(L.kaamer_stream_open, index._h, seq_type, C.byref(to))
         else:
-            abi.check(getattr(L, "kaamer_%s_open_flat" % kind)(index._h, seq_type, min_k_ratio, min_k_match, max_results, C.byref(h)))
-        self._h, self.index = h, index
+            h = _new(getattr(L, "kaamer_%s_open_flat" % kind), index._h, seq_type, *top)
+        super().__init__(h)
 
     def push(self, buf, offs):
         """-> False when every slot (set) is busy with this stream's own chunks (pop first), True when the chunk was taken"""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        rc = self._fn["push"](self._h, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1)
+        buf, offs, batch = packed_batch(packed=(buf, offs))
+        rc = self._fn["push"](self._h, *batch)
         if rc == abi.E_BUSY:
             return False
         abi.check(rc)
@@ -1454,29 +1249,19 @@ class TopStream:
     def pop(self):
         out = C.POINTER(abi.BatchTop)()
         abi.check(self._fn["pop"](self._h, C.byref(out)))
-        try:
-            return TopResult(out)
-        finally:
-            abi.lib().kaamer_batch_top_free(out)
+        return _take_top(out)
 
     @property
     def pending(self):
         return int(self._fn["pending"](self._h))
 
-    def close(self):
-        if self._h:
-            self._fn["close"](self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _free(self, h):
+        self._fn["close"](h)
 
 
-class Workspace:
+class Workspace(_Handle):
     """Reusable device buffers for the device-resident call."""
+    _FREE = "kaamer_workspace_free"
 
     def __init__(self, index, max_seq_bytes, max_seqs, max_queries=0, max_hits=0, g_tier_slots=0, seq_type=abi.PROTEIN,
                  first_pos=0, want_positions=False, max_pos_words=0, compact=False, concurrent_batches=0):
@@ -1485,9 +1270,7 @@ class Workspace:
         o = abi.WorkspaceOpts(max_seq_bytes, max_seqs, max_queries, max_hits,
                               g_tier_slots, seq_type, first_pos, int(want_positions), int(compact), max_pos_words,
                               int(concurrent_batches), 0)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_workspace_create(index._h, C.byref(o), C.byref(h)))
-        self._h = h
+        super().__init__(_new(abi.lib().kaamer_workspace_create, index._h, C.byref(o)))
 
     def search_device(self, d_seqs_ptr, d_offsets_ptr, n_seqs, seq_bytes, seq_type=None, stream=0):
         """Enqueue one batch; pointers are raw device addresses (e.g. tensor.data_ptr()),
@@ -1547,16 +1330,12 @@ class Workspace:
     def exchange_stats_positions(self, back=0):
         """-> (bitmap words the largest block between any pair of ranks needed, a bitmap section overflowed) of the merge
         `back` calls ago on this workspace (kaamer_exchange_stats_positions)"""
-        out = (C.c_uint64 * 2)()
-        abi.check(abi.lib().kaamer_exchange_stats_positions(self._h, back, out))
-        return int(out[0]), int(out[1])
+        return tuple(_u64s(abi.lib().kaamer_exchange_stats_positions, 2, self._h, back))
 
     def exchange_stats(self, back=0):
         """-> (merge sequence number, queries of the batch, entries the largest block any pair of ranks needed, overflow)
         of the merge `back` calls ago on this workspace; the same figures on every rank"""
-        out = (C.c_uint64 * 4)()
-        abi.check(abi.lib().kaamer_exchange_stats(self._h, back, out))
-        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+        return tuple(_u64s(abi.lib().kaamer_exchange_stats, 4, self._h, back))
 
     def exchange_merge(self, layout, d_recv_ptr, stream=0):
         r = abi.DeviceResult()
@@ -1581,17 +1360,6 @@ class Workspace:
         """0: no kernel timers (default); k: HIP events around the kernels of every k-th call"""
         abi.lib().kaamer_workspace_set_timing(self._h, int(every))
 
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_workspace_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _reads_to_arrays(h):
     """a kaamer_reads handle -> (seqs u8, offsets u64, size_in_kmer, names bytes, name offsets, plus_strand), copied"""
@@ -1606,22 +1374,20 @@ def _reads_to_arrays(h):
     return seqs, offs, size, names, noff, plus
 
 
-class Reader:
+class Reader(_Handle):
     """kaamer_reader_*: GetQueriesFasta / GetQueriesFastq over a file in chunks (gzip inflated incrementally)"""
+    _FREE = "kaamer_reader_close"
 
     def __init__(self, path=None, fmt="fastq", strict=False, fd=None):
-        h = C.c_void_p()
         f = 1 if fmt == "fastq" else 0
         if fd is not None:
-            abi.check(abi.lib().kaamer_reader_open_fd(fd, f, int(strict), C.byref(h)))
+            super().__init__(_new(abi.lib().kaamer_reader_open_fd, fd, f, int(strict)))
         else:
-            abi.check(abi.lib().kaamer_reader_open(str(path).encode(), f, int(strict), C.byref(h)))
-        self._h = h
+            super().__init__(_new(abi.lib().kaamer_reader_open, str(path).encode(), f, int(strict)))
 
     def next_handle(self, max_seqs, max_bytes):
         """-> a raw kaamer_reads handle (free with kaamer_reads_free), or None at the end"""
-        r = C.c_void_p()
-        abi.check(abi.lib().kaamer_reader_next(self._h, max_seqs, max_bytes, C.byref(r)))
+        r = _new(abi.lib().kaamer_reader_next, self._h, max_seqs, max_bytes)
         if abi.lib().kaamer_reads_count(r) == 0 and self.done:
             abi.lib().kaamer_reads_free(r)
             return None
@@ -1652,50 +1418,30 @@ class Reader:
             c = self.next(max_seqs, max_bytes)
             if c is None:
                 return out
-            seqs, offs, size, names, noff, plus = c
-            sb = bytes(seqs)
-            out += [dict(seq=sb[int(offs[i]):int(offs[i + 1])].decode("latin-1"), name=names[int(noff[i]):int(noff[i + 1])].decode("latin-1"),
-                         size=int(size[i]), plus=bool(plus[i])) for i in range(len(size))]
+            out += _read_records(c)
 
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_reader_close(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _read_records(arrays):
+    """what _reads_to_arrays returns -> list of dict(seq, name, size, plus)"""
+    seqs, offs, size, names, noff, plus = arrays
+    sb = bytes(seqs)
+    return [dict(seq=sb[int(offs[i]):int(offs[i + 1])].decode("latin-1"), name=names[int(noff[i]):int(noff[i + 1])].decode("latin-1"),
+                 size=int(size[i]), plus=bool(plus[i])) for i in range(len(size))]
 
 
 def parse_reads(text, fmt="fasta"):
     """GetQueriesFasta / GetQueriesFastq on a text buffer -> list of dict(seq, name, size, plus)"""
     data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
-    h = C.c_void_p()
-    f = abi.lib().kaamer_parse_fasta if fmt == "fasta" else abi.lib().kaamer_parse_fastq
-    abi.check(f(data, len(data), C.byref(h)))
+    h = _new(abi.lib().kaamer_parse_fasta if fmt == "fasta" else abi.lib().kaamer_parse_fastq, data, len(data))
     try:
-        L = abi.lib()
-        n = L.kaamer_reads_count(h)
-        offs = np.ctypeslib.as_array(L.kaamer_reads_offsets(h), shape=(n + 1,)).copy()
-        noff = np.ctypeslib.as_array(L.kaamer_reads_name_offsets(h), shape=(n + 1,)).copy()
-        seqs = bytes(np.ctypeslib.as_array(L.kaamer_reads_seqs(h), shape=(int(offs[n]),))) if offs[n] else b""
-        names = bytes(np.ctypeslib.as_array(C.cast(L.kaamer_reads_names(h), C.POINTER(C.c_uint8)), shape=(int(noff[n]),))) if noff[n] else b""
-        size = np.ctypeslib.as_array(L.kaamer_reads_size_in_kmer(h), shape=(n,)).copy() if n else np.zeros(0, np.int32)
-        plus = np.ctypeslib.as_array(L.kaamer_reads_plus_strand(h), shape=(n,)).copy() if n else np.zeros(0, np.int32)
-        return [dict(seq=seqs[int(offs[i]):int(offs[i + 1])].decode("latin-1"),
-                     name=names[int(noff[i]):int(noff[i + 1])].decode("latin-1"), size=int(size[i]), plus=bool(plus[i]))
-                for i in range(n)]
+        return _read_records(_reads_to_arrays(h))
     finally:
         abi.lib().kaamer_reads_free(h)
 
 
 def text_parser_geometry():
     """kaamer_text_parser_geometry -> dict(piece, wave_step, tile, lines): the tiling of the device parser's kernels"""
-    g = (C.c_uint32 * 4)()
-    abi.lib().kaamer_text_parser_geometry(g)
-    return dict(piece=int(g[0]), wave_step=int(g[1]), tile=int(g[2]), lines=int(g[3]))
+    return _geometry(abi.lib().kaamer_text_parser_geometry, ("piece", "wave_step", "tile", "lines"))
 
 
 def text_cut_fastq(text):
@@ -1719,22 +1465,21 @@ def _hip_runtime():
     return hip
 
 
-class TextParser:
+class TextParser(_Handle):
     """kaamer_text_parser_*: GetQueriesFastq / GetQueriesFasta on the device, for texts of up to max_text_bytes with up to
     max_records records (None: as many as such a text can hold) and max_lines lines (None: the FASTQ rule,
     max_text_bytes / 16 + 4 max_records + 1024; kaamer_text_parser_create_lines otherwise)"""
+    _FREE = "kaamer_text_parser_free"
 
     def __init__(self, max_text_bytes, max_records=None, device=0, max_lines=None):
         self.device = device
         self.max_text_bytes = int(max_text_bytes)
         if max_records is None:
             max_records = self.max_text_bytes // 2 + 1
-        h = C.c_void_p()
         if max_lines is None:
-            abi.check(abi.lib().kaamer_text_parser_create(device, self.max_text_bytes, int(max_records), C.byref(h)))
+            super().__init__(_new(abi.lib().kaamer_text_parser_create, device, self.max_text_bytes, int(max_records)))
         else:
-            abi.check(abi.lib().kaamer_text_parser_create_lines(device, self.max_text_bytes, int(max_records), int(max_lines), C.byref(h)))
-        self._h = h
+            super().__init__(_new(abi.lib().kaamer_text_parser_create_lines, device, self.max_text_bytes, int(max_records), int(max_lines)))
 
     def parse_device(self, d_text_ptr, n_bytes, stream=0, fmt="fastq", upper_last=False):
         """kaamer_parse_fastq_device (fmt "fasta": kaamer_parse_fasta_device) + kaamer_text_parser_finish on a device
@@ -1768,17 +1513,6 @@ class TextParser:
                     assert hip.hipMemcpy(arr.ctypes.data, C.c_void_p(ptr), arr.nbytes, 2) == 0
             del d
         return dict(seqs=seqs, offsets=offs, spans=spans, n_lines=int(r.n_lines))
-
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_text_parser_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def parse_fastq_device(text, device=0):
@@ -1821,9 +1555,7 @@ def bgzf_scan(data):
 
 def inflater_geometry():
     """kaamer_inflater_geometry -> dict(crc_segment, blocks_per_workgroup, cut_tile)"""
-    g = (C.c_uint32 * 3)()
-    abi.lib().kaamer_inflater_geometry(g)
-    return dict(crc_segment=int(g[0]), blocks_per_workgroup=int(g[1]), cut_tile=int(g[2]))
+    return _geometry(abi.lib().kaamer_inflater_geometry, ("crc_segment", "blocks_per_workgroup", "cut_tile"))
 
 
 def text_cut_fastq_device(text, device=0):
@@ -1839,17 +1571,16 @@ def text_cut_fastq_device(text, device=0):
     return int(cut.value)
 
 
-class Inflater:
+class Inflater(_Handle):
     """kaamer_inflater_*: BGZF blocks inflated on the device, one wave per block, for calls of up to max_blocks blocks
     within max_comp_bytes compressed bytes"""
+    _FREE = "kaamer_inflater_free"
 
     def __init__(self, max_comp_bytes, max_blocks, device=0):
         self.device = device
         self.max_comp_bytes = int(max_comp_bytes)
         self.max_blocks = int(max_blocks)
-        h = C.c_void_p()
-        abi.check(abi.lib().kaamer_inflater_create(device, self.max_comp_bytes, self.max_blocks, C.byref(h)))
-        self._h = h
+        super().__init__(_new(abi.lib().kaamer_inflater_create, device, self.max_comp_bytes, self.max_blocks))
 
     def inflate_device(self, d_comp_ptr, comp_bytes, d_blocks_ptr, n_blocks, d_out_ptr, out_cap, stream=0):
         """kaamer_inflate_bgzf_device + kaamer_inflater_finish on device buffers -> abi.InflateResult"""
@@ -1880,32 +1611,17 @@ class Inflater:
         return dict(text=whole[out_offset:out_offset + total].copy(), guard=(whole[:out_offset].copy(), whole[out_offset + total:].copy()),
                     status=status, n_bad=int(r.n_bad), first_bad=int(r.first_bad), first_bad_status=int(r.first_bad_status), out_bytes=int(r.out_bytes))
 
-    def close(self):
-        if self._h:
-            abi.lib().kaamer_inflater_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def align_pairs(seqs=None, packed=None, pairs=(), number_of_aa=0, sub_matrix="blosum62", gap_open=11, gap_extend=1, device=0):
     """kaamer_align_pairs: align.Align (align.go:46-161) for every (query index, subject index) pair -> list of dicts
     (None where the reference keeps an empty AlignmentResult: "No matrix found"; a ValueError-like status is returned as
     {"status": n})"""
-    buf, offs = packed if packed is not None else pack_sequences(seqs)
-    buf = np.ascontiguousarray(buf, dtype=np.uint8)
-    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    buf, offs, batch = packed_batch(seqs, packed)
     pq = np.ascontiguousarray([p[0] for p in pairs], dtype=np.uint32)
     ps = np.ascontiguousarray([p[1] for p in pairs], dtype=np.uint32)
-    h = C.c_void_p()
     L = abi.lib()
-    abi.check(L.kaamer_align_pairs(device, buf.ctypes.data if len(buf) else None, offs.ctypes.data, len(offs) - 1,
-                                   pq.ctypes.data if len(pq) else None, ps.ctypes.data if len(ps) else None, len(pq), int(number_of_aa),
-                                   sub_matrix.encode(), gap_open, gap_extend, C.byref(h)))
+    h = _new(L.kaamer_align_pairs, device, *batch, pq.ctypes.data if len(pq) else None, ps.ctypes.data if len(ps) else None, len(pq),
+             int(number_of_aa), sub_matrix.encode(), gap_open, gap_extend)
     try:
         n = L.kaamer_alignments_count(h)
         items = L.kaamer_alignments_items(h)

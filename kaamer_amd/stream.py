@@ -6,7 +6,7 @@ while chunk i is searched, and only what a caller reports comes back -- per ORF 
 the device post-steps.  This module is a thin ctypes caller: chunking and result bookkeeping only."""
 import numpy as np
 
-from . import abi
+from . import abi, api
 
 
 def chunk_bounds(offsets, max_seqs, max_bytes):
@@ -39,8 +39,7 @@ class StreamingSearcher:
     def run(self, buf, offsets, on_chunk=None):
         """Search every sequence of the packed host batch; `on_chunk(first_seq, n_seqs, top)` receives each chunk's
         api.TopResult (reported ORFs only, in input order).  Returns the summed counters."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        buf, offsets, _ = api.packed_batch(packed=(buf, offsets))
         total = {}
         fifo = []
 

@@ -10,13 +10,40 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_symbols():
+def _header():
     src = open(os.path.join(ROOT, "include", "kaamer_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(kaamer_[a-z_0-9]+)\s*\(", src)))
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(kaamer_[a-z_0-9]+)\s*\(", _header())))
+
+
+def _declared_arity():
+    """{function: number of parameters} of every declaration in the header; (void) is none.  The callback typedefs are
+    `(*name)(...)`, so their names are followed by ')' and do not match."""
+    out = {}
+    for name, params in re.findall(r"\b(kaamer_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", _header()):
+        params = params.strip()
+        assert name not in out, "%s is declared twice" % name
+        out[name] = 0 if params in ("", "void") else params.count(",") + 1
+    return out
 
 
 HOST_ONLY = bool(os.environ.get("KAAMER_HOST_ONLY"))   # the sanitized CPU build holds the host sources only
+
+
+def test_abi_arity_equals_the_header():
+    """abi.SYMBOLS is built from named argument groups: every entry has as many argtypes as the header's declaration has
+    parameters, and the header declares nothing else.  Needs the header's text and the table only."""
+    from kaamer_amd import abi
+    arity = _declared_arity()
+    assert sorted(arity) == _declared_symbols() == sorted(abi.SYMBOLS)
+    assert len(arity) >= 252
+    wrong = {n: (k, len(abi.SYMBOLS[n][1])) for n, k in arity.items() if k != len(abi.SYMBOLS[n][1])}
+    assert not wrong, "header parameters vs argtypes: %s" % wrong
+    for res, args in abi.SYMBOLS.values():
+        assert isinstance(args, list)
 
 
 @pytest.mark.skipif(HOST_ONLY, reason="host-only sanitized library")
