@@ -667,6 +667,12 @@ int kaamer_exchange_layout_fit(const kaamer_exchange_layout *capacity, uint32_t 
  * header scan only (an event), not for the stream. */
 int kaamer_exchange_stats(kaamer_workspace *merge_ws, uint32_t back, uint64_t out[4]);
 uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws);
+/* The prefix scan behind every offset array of a workspace (hit offsets, bitmap bases, pair offsets, piece offsets; tests
+ * put their boundary cases there): out[0] threads per workgroup, out[1] counts per thread, out[2] counts per tile
+ * (out[0] * out[1]), out[3] the greatest bound -- the batch's sequence count, the workspace's query capacity or the piece
+ * bound, by caller -- that one workgroup scans tile after tile with a carry; above it three launches scan one tile per
+ * workgroup. */
+void kaamer_scan_geometry(uint32_t out[4]);
 /* Blocks that carry PositionHits (search.go:442-452; -pos, cmd/kaamer/main.go:69) through the exchange: arrays = 4.
  * The block is the arrays = 3 block with two more sections:
  *     [8 + q_cap .. 8 + 2 q_cap)  per owned query: SizeInKmer (every shard translates alike: the W blocks must agree)
@@ -1309,8 +1315,9 @@ int kaamer_inflate_bgzf_device(kaamer_inflater *inf, const uint8_t *d_comp, uint
 /* Waits for the last inflate enqueued on `stream`; d_status is valid until the next inflate. */
 int kaamer_inflater_finish(kaamer_inflater *inf, void *stream, kaamer_inflate_result *out);
 /* The tiling (tests put their boundary cases there): out[0] bytes of output per lane of the CRC, out[1] BGZF blocks (waves)
- * per workgroup, out[2] bytes of text per workgroup of the cut kernel. */
-void kaamer_inflater_geometry(uint32_t out[3]);
+ * per workgroup, out[2] bytes of text per workgroup of the cut kernel, out[3] threads of the one workgroup that scans the
+ * blocks' sizes into their offsets: each takes ceil(n_blocks / out[3]) blocks in a row. */
+void kaamer_inflater_geometry(uint32_t out[4]);
 /* kaamer_text_cut_fastq of a text that lives on the device (the caller of the device inflate never holds it): waits. */
 int kaamer_text_cut_fastq_device(int device, const uint8_t *d_text, uint64_t n_bytes, void *stream, uint64_t *cut);
 

@@ -1049,6 +1049,12 @@ def _geometry(fn, names=("tile", "window", "store", "threads")):
     return dict(zip(names, (int(v) for v in g)))
 
 
+def scan_geometry():
+    """kaamer_scan_geometry -> dict(block, items, tile, single_max): threads per workgroup of the workspace's prefix scan,
+    counts per thread, counts per tile, and the greatest bound the one-workgroup form takes (above it: the tiled launches)"""
+    return _geometry(abi.lib().kaamer_scan_geometry, ("block", "items", "tile", "single_max"))
+
+
 def tsv_geometry():
     """kaamer_tsv_geometry -> dict(tile, window, store, threads): queries per tile of the write pass, bytes per LDS window
     (windows lie on multiples of it in the output), bytes a lane stores at once, threads per workgroup"""
@@ -1554,8 +1560,8 @@ def bgzf_scan(data):
 
 
 def inflater_geometry():
-    """kaamer_inflater_geometry -> dict(crc_segment, blocks_per_workgroup, cut_tile)"""
-    return _geometry(abi.lib().kaamer_inflater_geometry, ("crc_segment", "blocks_per_workgroup", "cut_tile"))
+    """kaamer_inflater_geometry -> dict(crc_segment, blocks_per_workgroup, cut_tile, scan_threads)"""
+    return _geometry(abi.lib().kaamer_inflater_geometry, ("crc_segment", "blocks_per_workgroup", "cut_tile", "scan_threads"))
 
 
 def text_cut_fastq_device(text, device=0):

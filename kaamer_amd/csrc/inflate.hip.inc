@@ -565,10 +565,10 @@ int kaamer_inflater_create(int device, uint64_t max_comp_bytes, uint32_t max_blo
     return KAAMER_OK;
 }
 
-void kaamer_inflater_geometry(uint32_t out[3])
+void kaamer_inflater_geometry(uint32_t out[4])
 {
     if (!out) return;
-    out[0] = INF_CRC_SEG; out[1] = INF_WAVES; out[2] = INF_CUT_TILE;
+    out[0] = INF_CRC_SEG; out[1] = INF_WAVES; out[2] = INF_CUT_TILE; out[3] = INF_SCAN_THREADS;
 }
 
 // the inflate, and behind it on the same stream -- when cut_len is not 0 -- the cut of cut_text[0, cut_len) (a text that

@@ -725,6 +725,7 @@ __device__ __forceinline__ void finalize_body(unsigned long long *replicas, kaam
 #define SCAN_BLOCK 1024
 #define SCAN_ITEMS 16
 #define SCAN_TILE (SCAN_BLOCK * SCAN_ITEMS)
+#define SCAN_SINGLE_MAX (8 * (uint64_t)SCAN_TILE)   // the greatest bound scan_u32_on gives to the one-workgroup form
 
 __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t *total)
 {
@@ -1004,7 +1005,7 @@ static void launch_group_merge(const CountParams &p, int grid, bool firstpos, hi
 // exclusive scan of cnt[0..*d_count) -> off[0..*d_count]; bound: host-side bound of *d_count (which launch, grid sizing)
 static void scan_u32_on(kaamer_workspace *ws, const uint32_t *cnt, const uint32_t *d_count, uint64_t bound, uint64_t *off, hipStream_t s)
 {
-    if (bound <= 8 * (uint64_t)SCAN_TILE) {
+    if (bound <= SCAN_SINGLE_MAX) {
         hipLaunchKernelGGL(scan_single_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, cnt, d_count, off);
     } else {
         const uint32_t nsb = (uint32_t)((bound + 1 + SCAN_TILE - 1) / SCAN_TILE);
@@ -1264,6 +1265,12 @@ int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out)
 void kaamer_workspace_free(kaamer_workspace *ws) { delete ws; }
 
 uint32_t kaamer_workspace_query_capacity(const kaamer_workspace *ws) { return ws ? ws->q_cap : 0u; }
+
+void kaamer_scan_geometry(uint32_t out[4])
+{
+    if (!out) return;
+    out[0] = SCAN_BLOCK; out[1] = SCAN_ITEMS; out[2] = SCAN_TILE; out[3] = (uint32_t)SCAN_SINGLE_MAX;
+}
 
 int kaamer_workspace_create(kaamer_index *ix, const kaamer_workspace_opts *opts, kaamer_workspace **out)
 {

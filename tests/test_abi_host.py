@@ -39,7 +39,10 @@ def test_abi_arity_equals_the_header():
     from kaamer_amd import abi
     arity = _declared_arity()
     assert sorted(arity) == _declared_symbols() == sorted(abi.SYMBOLS)
-    assert len(arity) >= 252
+    assert len(arity) >= 253
+    # the geometry getters the tests build their boundary cases from: each fills one u32 array
+    for n in ("kaamer_scan_geometry", "kaamer_text_parser_geometry", "kaamer_inflater_geometry", "kaamer_tsv_geometry", "kaamer_json_geometry"):
+        assert arity[n] == 1 and abi.SYMBOLS[n][0] is None, n
     wrong = {n: (k, len(abi.SYMBOLS[n][1])) for n, k in arity.items() if k != len(abi.SYMBOLS[n][1])}
     assert not wrong, "header parameters vs argtypes: %s" % wrong
     for res, args in abi.SYMBOLS.values():
@@ -55,6 +58,10 @@ def test_library_exports_every_declared_symbol(klib):
         assert hasattr(klib, n), "libkaamer_hip.so lacks %s" % n
     assert sorted(abi.SYMBOLS) == names, "abi.py and include/kaamer_hip.h disagree"
     assert klib.kaamer_abi_version() == 4
+    from kaamer_amd import api
+    g = api.scan_geometry()
+    assert g == dict(block=1024, items=16, tile=16384, single_max=131072) and g["tile"] == g["block"] * g["items"]
+    assert api.inflater_geometry()["scan_threads"] == 1024
 
 
 def test_product_does_not_use_the_oracle():

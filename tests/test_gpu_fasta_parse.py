@@ -5,6 +5,7 @@ import random
 
 import pytest
 
+import scancases
 from kaamer_amd import abi, api
 
 pytestmark = pytest.mark.gpu
@@ -241,3 +242,60 @@ def test_fuzz(parser, geo):
             out.append(ln)
             size += len(ln)
         _check(parser, b"".join(out), rng.random() < 0.5)
+
+
+# ---- the second round of the one-workgroup scans: more than 1024 tiles of text, more than 1024 blocks of lines ----
+
+@pytest.fixture(scope="module")
+def big_parser(klib, gpu_device, geo):
+    """a parser for texts of up to 2050 tiles and two rounds of line blocks"""
+    assert geo["lines"] == scancases.ROUND == 1024       # the scans' workgroups have as many threads as a block has lines
+    p = api.TextParser(2050 * geo["tile"], max_records=4096, device=gpu_device, max_lines=2 * scancases.ROUND * geo["lines"] + 4096)
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def line_cases(geo):
+    return scancases.line_block_cases("fasta", geo["lines"])
+
+
+@pytest.mark.parametrize("n_tiles", [1024, 1025, 2049])
+def test_more_tiles_than_one_round_of_the_tile_scan(big_parser, geo, n_tiles):
+    """pt_tile_scan_kernel takes 1024 tiles per round and carries the lines before them into the next: 1024 tiles are one
+    full round, 1025 a second round of one tile, 2049 a third.  Where a round ends, a '\\n' is the last byte of the tile
+    before and another the first byte of the next, with records on both sides: every line base of the later round is
+    wrong unless the carry is right."""
+    text, edges, n_rec = scancases.tiles_text("fasta", geo["tile"], n_tiles)
+    rounds = (n_tiles + scancases.ROUND - 1) // scancases.ROUND
+    assert (len(text) + geo["tile"] - 1) // geo["tile"] == n_tiles and rounds == {1024: 1, 1025: 2, 2049: 3}[n_tiles]
+    assert len(edges) == max(rounds - 1, 1) and all(text[e - 1:e + 1] == b"\n\n" for e in edges) and not text.endswith(b"\n")
+    if rounds > 1:
+        assert [e // geo["tile"] for e in edges] == [scancases.ROUND * k for k in range(1, rounds)]
+    assert len(text) <= big_parser.max_text_bytes and 100 < n_rec < 300
+    assert _both(big_parser, text) == n_rec
+
+
+@pytest.mark.parametrize("case", scancases.LINE_CASES)
+def test_more_line_blocks_than_one_round_of_the_block_scan(big_parser, geo, line_cases, case):
+    """pf_block_scan_kernel takes 1024 blocks of lines per round: the record and byte bases, the nearest header before a
+    block and the class of the lines around it cross from one round into the other"""
+    text, n_rec, blocks = line_cases[case]
+    assert scancases.kernel_blocks(text, geo["lines"]) == blocks
+    assert (blocks > scancases.ROUND) == (case != "B lines, the last one S")         # (that one fills one round to its last block)
+    assert _both(big_parser, text) == n_rec
+
+
+def test_line_capacity_behind_one_round(klib, gpu_device, geo):
+    B = scancases.ROUND * geo["lines"]
+    mark = b">"
+    text = scancases.lines_text(B + 2, True, {B - 1: mark + b"h", B: b"ACGT"})
+    p = api.TextParser(len(text), max_records=16, device=gpu_device, max_lines=B + 1)
+    try:
+        with pytest.raises(abi.KaamerError) as e:
+            p.parse(text, fmt="fasta")
+        assert e.value.code == abi.E_CAPACITY and "lines" in str(e.value)
+        assert _both(p, mark + b"r\nACGT\n") == 1                              # usable afterwards
+        assert _both(p, scancases.lines_text(B, False, {B - 2: mark + b"h", B - 1: b"ACGT"})) == 1
+    finally:
+        p.close()

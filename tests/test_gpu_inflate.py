@@ -21,6 +21,14 @@ def inflater(klib, gpu_device):
 
 
 @pytest.fixture(scope="module")
+def inflater_many(klib, gpu_device):
+    """an inflater for calls of more blocks than the offsets scan has threads"""
+    inf = api.Inflater(1 << 20, 3100, device=gpu_device)
+    yield inf
+    inf.close()
+
+
+@pytest.fixture(scope="module")
 def fastq(klib):
     return bytes(workload.fastq_text(workload.make_reads(workload.make_db(50), 1200, seed=9)))
 
@@ -95,6 +103,76 @@ def test_many_blocks_at_odd_offsets(inflater, fastq, n_blocks):
     assert at <= len(fastq)
     data = b"".join(bgzfmake.block(p, modes[i % len(modes)]) for i, p in enumerate(pieces))
     _assert_good(inflater, data, b"".join(pieces), out_offset=7)
+
+
+def many_small_blocks(fastq, n_blocks):
+    """(data, text, pieces): n_blocks BGZF blocks of 0 to 39 bytes of the fixture, every seventh empty, the modes in turn, and
+    a last block of 40 bytes, the largest"""
+    rng = np.random.default_rng(n_blocks)
+    modes = list(bgzfmake.MODES)
+    sizes = np.where(np.arange(n_blocks) % 7 == 0, 0, rng.integers(0, 40, n_blocks))
+    sizes[-1] = 40
+    ends = np.cumsum(sizes)
+    assert ends[-1] <= len(fastq) and sizes.max() == sizes[-1] and (sizes[:-1] < sizes[-1]).all()
+    pieces = [fastq[int(e - n):int(e)] for e, n in zip(ends, sizes)]
+    data = b"".join(bgzfmake.block(p, modes[i % len(modes)]) for i, p in enumerate(pieces))
+    return data, b"".join(pieces), pieces
+
+
+def blocks_per_scan_thread(n_blocks):
+    t = api.inflater_geometry()["scan_threads"]
+    return (n_blocks + t - 1) // t
+
+
+@pytest.mark.parametrize("n_blocks", [1024, 1025, 2047, 2048, 2049, 3001])
+def test_more_blocks_than_scan_threads(inflater_many, fastq, n_blocks):
+    """inf_offsets_kernel gives each of its 1024 threads ceil(n_blocks / 1024) blocks in a row: one at 1024; two from 1025
+    on -- with 1025 blocks thread 512 holds the last block alone and the stretches of threads 513 to 1023 start behind
+    it, with 2047 only thread 1023 is short (one block), 2048 fills every stretch; three at 2049 and 3001 (threads from
+    683 resp. 1001 start behind the last block).  Every block's text lies where the sum of the sizes before it says."""
+    t = api.inflater_geometry()["scan_threads"]
+    assert t == 1024
+    per = blocks_per_scan_thread(n_blocks)
+    assert per == {1024: 1, 1025: 2, 2047: 2, 2048: 2, 2049: 3, 3001: 3}[n_blocks]
+    idle = [k for k in range(t) if k * per >= n_blocks]             # threads whose stretch starts behind the last block
+    if n_blocks == 1025:
+        assert idle == list(range(513, 1024)) and 512 * per == n_blocks - 1
+    if n_blocks == 2047:
+        assert not idle and 1023 * per == n_blocks - 1
+    if n_blocks in (1024, 2048):
+        assert not idle and t * per == n_blocks
+    if n_blocks == 2049:
+        assert idle == list(range(683, 1024))
+    assert n_blocks <= inflater_many.max_blocks
+    data, text, _ = many_small_blocks(fastq, n_blocks)
+    assert len(data) <= inflater_many.max_comp_bytes
+    _assert_good(inflater_many, data, text, out_offset=7)
+
+
+def test_malformed_block_behind_the_first_stretch(inflater_many, fastq):
+    """two blocks per scan thread, and block 1024 -- the first of thread 512's stretch -- has a flipped CRC bit: its status,
+    first_bad, and the text of every other block where the offsets put it"""
+    n_blocks, bad_at = 1031, 1024
+    assert blocks_per_scan_thread(n_blocks) == 2 and bad_at == api.inflater_geometry()["scan_threads"]
+    data, text, pieces = many_small_blocks(fastq, n_blocks)
+    blocks, used = api.bgzf_scan(data)
+    assert used == len(data) and len(blocks) == n_blocks and len(pieces[bad_at]) > 0
+    raw = bytearray(data)
+    raw[int(blocks[bad_at + 1]["comp_off"]) - bgzfmake.HEADER - 8] ^= 1       # the CRC in block bad_at's trailer
+    blocks2, used2 = api.bgzf_scan(bytes(raw))
+    assert used2 == used and blocks2["crc"][bad_at] != blocks["crc"][bad_at] and (np.delete(blocks2["crc"], bad_at) == np.delete(blocks["crc"], bad_at)).all()
+    r = inflater_many.inflate(bytes(raw), blocks2, out_offset=3)
+    want_status = [0] * n_blocks
+    want_status[bad_at] = 7
+    assert r["status"].tolist() == want_status
+    assert (r["n_bad"], r["first_bad"], r["first_bad_status"], r["out_bytes"]) == (1, bad_at, 7, len(text))
+    a = sum(len(p) for p in pieces[:bad_at])
+    b = a + len(pieces[bad_at])
+    got = r["text"].tobytes()
+    assert got[:a] == text[:a] and got[b:] == text[b:]
+    assert got[a - len(pieces[bad_at - 1]):a] == pieces[bad_at - 1] and got[b:b + len(pieces[bad_at + 1])] == pieces[bad_at + 1]
+    assert (r["guard"][0] == 0xEE).all() and (r["guard"][1] == 0xEE).all()
+    _assert_good(inflater_many, data, text, out_offset=3)                     # the inflater is as good as new
 
 
 def test_malformed_blocks_end_with_their_status(inflater, fastq):

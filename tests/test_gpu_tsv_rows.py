@@ -67,6 +67,7 @@ def run_stage(ix, names, queries, K, positions, annotations, out_cap, stage=None
         home = out.cpu().numpy().tobytes()
         off = _home(res.d_line_off, lines + 1, np.uint64)
         run_stage.counts = _home(res.d_counts, 4, np.uint64).tolist()      # rows, bytes, status, raw scores outside the table
+        run_stage.off = off
         return home[:nbytes], off, home[nbytes:]
     finally:
         if own:
@@ -176,6 +177,26 @@ def test_tiles_that_end_on_window_boundaries(setup):
     names = [b"n" * name_len]
     got = check(setup, names, [tsvcases.query(0, 20, [(1, 5)]) for _ in range(n)], 1, False, False)
     assert len(got) == 64 * n and g["tile"] * 64 == g["window"]
+
+
+def test_more_tiles_than_one_round_of_the_scan(setup):
+    """65 537 queries are 257 tiles: out_scan_kernel, one workgroup that takes `threads` tiles per round, goes round twice
+    under the plain rows as well; hits on the first and the last query of the first tile, the first of the second, and on
+    either side of the second round's first tile.  Rows and line offsets against the restatement (check) and against the
+    host formatter."""
+    g = api.tsv_geometry()
+    n = g["tile"] * g["threads"] + 1
+    assert n == 65537 and (n + g["tile"] - 1) // g["tile"] == g["threads"] + 1        # the second round holds one tile
+    hit = (0, g["tile"] - 1, g["tile"], n - 2, n - 1)
+    assert hit == (0, 255, 256, 65535, 65536)
+    names = [b"sweep of tiles"]
+    queries = [tsvcases.query(0, 20 + i % 7, [(i % tsvcases.N_ENTRIES, 5 + i % 11)] if i in hit else []) for i in range(n)]
+    got = check(setup, names, queries, 1, False, True)
+    off = run_stage.off
+    assert got.count(b"\n") == len(hit) and run_stage.counts[:1] + run_stage.counts[2:] == [len(hit), 0, 0]
+    buf, spans = tsvcases.names_buffer(names)
+    host, host_off = api.format_tsv(tsvcases.host_top(queries), buf, spans, setup["table"], False, True)
+    assert got == host and off.tolist() == host_off.tolist()
 
 
 def test_capacity_and_the_next_call(setup):
