@@ -25,6 +25,14 @@ TABLE_MUL = 0x9E3779B1              # BigLdsTable::add_n: home slot = (id * TABL
 GRP_MIN_TABLE, GRP_MAX_TABLE = 64, 4096   # count_group.hip.inc
 PK_ARENA_ORF, PK_ARENA_ORF_LONG = 640, 1024   # search.hip
 PACK_SHIFT_NUCLEOTIDE = 9           # search.hip: ws->pack_shift
+# the LDS tier's window steps (tests/windowcases.py)
+INLINE_BIT = 1 << 31                # kaamer_layout.h: KH_INLINE_BIT
+GRP_SHIFT = 11                      # count_group.hip.inc: GRP_SHIFT (a protein batch counts units of 1 << GRP_SHIFT + 1 slots)
+GRP_FIT = (1 << GRP_SHIFT) - 64 + GRP_MAX_TABLE   # count_group.hip.inc: GRP_FIT, the slots of the group kernel's arena
+GRP_MAX_PROBES = 96                 # count_window.hip.inc: GRP_MAX_PROBES
+GRP_LONG_UNROLL = 4                 # count_group.hip.inc: GRP_LONG_UNROLL
+GRP_WQ_WINDOWS = 128                # count_group.hip.inc: s_wq[2 * 64], filled while "w < 128u"
+PK_WHINT = 64                       # count_pack.hip.inc: PK_WHINT
 
 ALPHA = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", dtype=np.uint8)
 _M32 = np.uint64(0xFFFFFFFF)
@@ -95,9 +103,13 @@ class Figures:
         self.idx = np.arange(self.P, dtype=np.int64) - np.repeat(off[:-1], cnt)   # its index in its list
         self.distinct = np.unique(self.ids)
         self.D = len(self.distinct)
-        # the counters a query adds: a list is a value that is not inline, i.e. a key with two ids or more
-        self.n_lists = int((cnt >= 2).sum())
-        self.n_list_ids = int(cnt[cnt >= 2].sum())
+        # the counters a query adds: a list is a value that is not inline, i.e. a key with two ids or more -- or with one
+        # id of 2^31 or more, which kaamer_layout.h cannot store inline (KH_INLINE_BIT is the value's top bit)
+        first = np.zeros(self.size, dtype=np.uint32)
+        first[cnt > 0] = self.ids[off[:-1][cnt > 0]]
+        self.listed = (cnt >= 2) | ((cnt == 1) & (first >= np.uint32(INLINE_BIT)))
+        self.n_lists = int(self.listed.sum())
+        self.n_list_ids = int(cnt[self.listed].sum())
         # partition
         self.R = min(MAX_RANGES, self.P // RANGE_POSTINGS + 2)
         per = self.P // self.R
