@@ -237,6 +237,37 @@ int kaamer_image_build_makedb(const kaamer_proteins *p, uint32_t shard, uint32_t
 /* the same on `device` (kaamer_image_build_proteins_device) */
 int kaamer_image_build_makedb_device(const kaamer_proteins *p, uint32_t shard, uint32_t n_shards,
                                      double load_factor, int device, kaamer_image **out);
+/* The FASTA reader on the device (makedb_fasta.hip.inc): the text is uploaded, read there, and the table comes back by bulk
+ * copies.  It computes kaamer_makedb_fasta's rules, stated per line (they are not the query reader's, kaamer_parse_fasta):
+ *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped; a line that is empty after
+ *            that is skipped (the documented divergence: the reference panics there)
+ *   class    H: the first byte is '>'.  S: every other non-empty line.  Nothing is trimmed: leading, trailing and interior
+ *            spaces and tabs, an interior '\r' and a '>' inside the line are sequence bytes, whitespace-only lines are S lines
+ *   entries  an H line and the S lines up to the next H line; S lines in front of the first H line form an entry of their
+ *            own with an empty EntryId and an empty name
+ *   ids      N = the H lines of the text; the entry the k-th H line opens gets id min(k + 1, N) as uint32 (the last two
+ *            entries share N), the entry without a header min(1, N); ids are not renumbered after drops
+ *   header   EntryId: the bytes after '>' up to the line's first ' '; ProteinName: everything after that space
+ *   sequence the entry's S lines concatenated, a-z -> A-Z, every other byte (>= 0x80 included) as it is
+ *   drops    ProteinName contains ", partial" (in the name only: ">abc, partial" has EntryId "abc," and is kept); fewer
+ *            than 7 sequence bytes
+ *   table    feature_names = {"ProteinName"}; KStats over the accepted entries
+ * A text holds at most 2^32 - 1 bytes (KAAMER_E_ARG beyond, before anything else is looked at: cut at kaamer_text_cut_fasta);
+ * one that starts with the gzip signature is taken as text, as kaamer_makedb_fasta takes it; a text with more lines than the
+ * reader indexes is KAAMER_E_CAPACITY, never a partial table.  Out of scope here: -offset / -length and strict_scanner (they
+ * stay on kaamer_makedb_text_range), TSV / EMBL / GBK, compressed input, a whole-file driver.
+ *
+ * kaamer_makedb_fasta's table from `text`, made on `device`: the scan loop started with proteinNb = nb_before and an
+ * empty pending entry; more = 1: input follows, the pending entry at the end is queued under N + 1 as the next header
+ * would do.  nb_before = 0, more = 0 is kaamer_makedb_fasta, field for field.  Pieces cut at kaamer_text_cut_fasta,
+ * each with the number of '>' lines in front of it and more = 1 on all but the last, merged with
+ * kaamer_proteins_merge, are the whole text's table. */
+int kaamer_makedb_fasta_device(const char *text, uint64_t len, uint64_t nb_before, int32_t more, int device,
+                               kaamer_proteins **out);
+/* text -> table + one shard's image; the sequences never leave the device between the reader and the builder.
+ * Image: byte for byte kaamer_image_build_makedb(kaamer_makedb_fasta(text)).  A bad shard: KAAMER_E_ARG. */
+int kaamer_image_build_fasta_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
+                                    double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
 /* One Protein entry (protein.proto).  Pointers go into the table and stay valid until it is freed;
  * feature i is features[feature_off[i] .. feature_off[i+1]). */
 typedef struct {
@@ -272,6 +303,10 @@ int kaamer_index_open_image(const kaamer_image *img, int device, kaamer_index **
 int kaamer_index_build_proteins(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids,
                                 uint32_t n_proteins, uint32_t shard, uint32_t n_shards,
                                 double load_factor, int device, kaamer_index **out);
+/* text -> table + serving index (kaamer_index_build_proteins' hand-over: the table stays on the device); the reader is
+ * kaamer_makedb_fasta_device's */
+int kaamer_index_build_fasta(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
+                             int device, kaamer_proteins **proteins, kaamer_index **out);
 int kaamer_index_open(const char *path, int device, kaamer_index **out);
 void kaamer_index_close(kaamer_index *ix);
 int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out);

@@ -415,6 +415,12 @@ SYMBOLS = {
 for _name in ("makedb_fasta", "makedb_tsv", "makedb_embl", "makedb_gbk", "parse_fasta", "parse_fastq"):
     SYMBOLS["kaamer_" + _name] = (C.c_int, TEXT_IN + NEW)
 
+# the database FASTA text read on the device: (text, len, nb_before, more, device, out), and the two builds that take the
+# text: (text, len, shard, n_shards, load_factor, device, proteins, out)
+SYMBOLS["kaamer_makedb_fasta_device"] = (C.c_int, TEXT_IN + [C.c_uint64, C.c_int32, C.c_int] + NEW)
+for _name in ("image_build_fasta_device", "index_build_fasta"):
+    SYMBOLS["kaamer_" + _name] = (C.c_int, TEXT_IN + [C.c_uint32, C.c_uint32, C.c_double, C.c_int] + NEW + NEW)
+
 # the packed-batch calls of an index and of a sharded index; search fills a result, submit a ticket for wait / discard
 for _p in ("", "sharded_"):
     # the reported hits, cgo-safe forms: (handle, seqs, offsets, n_seqs, seq_type, min_k_ratio, min_k_match, max_results[,

@@ -101,6 +101,15 @@ class Image(_Handle):
         return cls(_new(abi.lib().kaamer_image_build_proteins_device, *proteins, shard, n_shards, load_factor, int(device)))
 
     @classmethod
+    def from_fasta_text(cls, text, shard=0, n_shards=1, load_factor=0.5, device=0):
+        """(proteins, image) of a database FASTA text, read and built on GPU `device` (kaamer_image_build_fasta_device): the
+        sequences stay there between the reader and the builder."""
+        text = bytes(text)
+        p, im = C.c_void_p(), C.c_void_p()
+        abi.check(abi.lib().kaamer_image_build_fasta_device(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(im)))
+        return Proteins(p), cls(im)
+
+    @classmethod
     def merge(cls, images, load_factor=0.5, device=None):
         """kaamer-db -merge: the union of images of one shard (kaamer_image_merge).  device=None: on the host;
         device=d: the same image made on GPU d (byte-identical)."""
@@ -145,8 +154,15 @@ class Proteins(_Handle):
         return cls(_new(fn, text, len(text)))
 
     @classmethod
-    def from_fasta(cls, text):
-        return cls._make(abi.lib().kaamer_makedb_fasta, text)
+    def from_fasta(cls, text, device=None, nb_before=0, more=False):
+        """device=None: kaamer_makedb_fasta on the host.  device=d: the same table read on GPU d (kaamer_makedb_fasta_device);
+        there `text` may be a piece cut at text_cut_fasta: nb_before = the '>' lines in front of it, more = another piece follows."""
+        if device is None:
+            if nb_before or more:
+                raise ValueError("nb_before / more belong to the device reader")
+            return cls._make(abi.lib().kaamer_makedb_fasta, text)
+        text = bytes(text)
+        return cls(_new(abi.lib().kaamer_makedb_fasta_device, text, len(text), int(nb_before), int(bool(more)), int(device)))
 
     @classmethod
     def from_tsv(cls, text):
@@ -501,6 +517,14 @@ class Index(_Handle):
         """The table built on the device it is searched on (kaamer_index_build_proteins): no image in between."""
         keep, proteins = _proteins_args(seqs, packed, ids)
         return cls(_new(abi.lib().kaamer_index_build_proteins, *proteins, shard, n_shards, load_factor, int(device)), device)
+
+    @classmethod
+    def from_fasta_text(cls, text, shard=0, n_shards=1, load_factor=0.5, device=0):
+        """(proteins, index) of a database FASTA text, read and built on the device it is searched on (kaamer_index_build_fasta)"""
+        text = bytes(text)
+        p, ix = C.c_void_p(), C.c_void_p()
+        abi.check(abi.lib().kaamer_index_build_fasta(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(ix)))
+        return Proteins(p), cls(ix, device)
 
     @classmethod
     def open(cls, path, device=0):

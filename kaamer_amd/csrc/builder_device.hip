@@ -509,7 +509,53 @@ int bd_build_from_pairs(DevMem &d_pairs, DevMem &d_pairs_alt, uint64_t n_emit, u
 
 }  // namespace
 
-// The whole build; on success *out owns two device allocations (hipFree).  Inputs are host buffers.
+// The build from packed proteins that lie on the device: d_seqs holds total_res residues from offsets' origin on and 32
+// bytes of slack behind them.  `done` is called once the build has read the three buffers for the last time.
+static int bd_build_resident(const uint8_t *d_seqs, const uint64_t *d_off, const uint32_t *d_ids, uint32_t n_proteins, uint64_t origin,
+                             uint64_t total_res, uint32_t shard, uint32_t n_shards, double load, Trace &tr, const std::function<void()> &done,
+                             kaamer_device_image *out)
+{
+    DevMem d_st;
+    BD_HIP(d_st.alloc(sizeof(BuildStats)));
+    BD_HIP(hipMemset(d_st.p, 0, sizeof(BuildStats)));
+    BuildStats *st = d_st.as<BuildStats>();
+    BuildStats hs;
+    memset(&hs, 0, sizeof hs);
+
+    // ---- emit ----------------------------------------------------------------------------------------------
+    DevMem d_pairs, d_pairs_alt;
+    uint64_t n_emit = 0;
+    uint64_t n_tiles = 0;
+    if (total_res >= KAAMER_KMER_SIZE) {
+        n_tiles = (total_res + BD_TILE - 1) / BD_TILE;
+        if (n_tiles >= (1ull << 31)) return kaamer_fail(KAAMER_E_CAPACITY, "device build: database too large for one call");
+        hipLaunchKernelGGL(bd_windows_kernel<BD_COUNT>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs, d_off, d_ids, n_proteins, origin,
+                           total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st, FirstWindow{});
+        BD_HIP(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
+        n_emit = hs.n_windows;
+        tr.lap("count windows", n_emit);
+        BD_HIP(d_pairs.alloc(n_emit * 8));
+        BD_HIP(d_pairs_alt.alloc(n_emit * 8));
+        BD_HIP(hipMemset(st, 0, sizeof(BuildStats)));
+        hipLaunchKernelGGL(bd_windows_kernel<BD_EMIT>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs, d_off, d_ids, n_proteins, origin,
+                           total_res, shard, n_shards, d_pairs.as<uint64_t>(), n_emit, st, FirstWindow{});
+        BD_HIP(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
+        if (hs.bad || hs.n_windows != n_emit) return kaamer_fail(KAAMER_E_HIP, "device build: the emit pass disagrees with the count pass");
+        tr.lap("emit", n_emit);
+    }
+    // the order of the arena: a second run of the window kernel takes, per key, the smallest window position
+    const RankSource by_walk = [&](const FirstWindow &fw) {
+        hipLaunchKernelGGL(bd_windows_kernel<BD_FIRST>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs, d_off, d_ids, n_proteins, origin,
+                           total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st, fw);
+        BD_HIP(hipGetLastError());
+        done();
+        return (int)KAAMER_OK;
+    };
+    return bd_build_from_pairs(d_pairs, d_pairs_alt, n_emit, shard, n_shards, load, st, tr, origin + total_res, by_walk, out);
+}
+
+// The whole build; on success *out owns two device allocations (hipFree).  Inputs are host buffers: the upload, then the build
+// from device buffers.
 int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids, uint32_t n_proteins,
                            uint32_t shard, uint32_t n_shards, double load, int device, kaamer_device_image *out)
 {
@@ -523,19 +569,7 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
     BD_HIP(hipSetDevice(device));
     Trace tr;
     const uint64_t origin = n_proteins ? offsets[0] : 0, total_res = n_proteins ? offsets[n_proteins] - origin : 0;
-
-    DevMem d_st;
-    BD_HIP(d_st.alloc(sizeof(BuildStats)));
-    BD_HIP(hipMemset(d_st.p, 0, sizeof(BuildStats)));
-    BuildStats *st = d_st.as<BuildStats>();
-    BuildStats hs;
-    memset(&hs, 0, sizeof hs);
-
-    // ---- emit ----------------------------------------------------------------------------------------------
-    DevMem d_pairs, d_pairs_alt;
-    uint64_t n_emit = 0;
     DevMem d_seqs, d_off, d_ids;   // kept for the second run of the window kernel (the order of the arena)
-    uint64_t n_tiles = 0;
     if (total_res >= KAAMER_KMER_SIZE) {
         BD_HIP(d_seqs.alloc(total_res + 32));   // (a thread of the emit kernel reads 24 bytes from its first position)
         BD_HIP(d_off.alloc(((size_t)n_proteins + 1) * 8));
@@ -546,31 +580,22 @@ int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const u
             BD_HIP(hipMemcpy(d_ids.p, ids, (size_t)n_proteins * 4, hipMemcpyHostToDevice));
         }
         tr.lap("upload", total_res);
-        n_tiles = (total_res + BD_TILE - 1) / BD_TILE;
-        if (n_tiles >= (1ull << 31)) return kaamer_fail(KAAMER_E_CAPACITY, "device build: database too large for one call");
-        hipLaunchKernelGGL(bd_windows_kernel<BD_COUNT>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
-                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st, FirstWindow{});
-        BD_HIP(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
-        n_emit = hs.n_windows;
-        tr.lap("count windows", n_emit);
-        BD_HIP(d_pairs.alloc(n_emit * 8));
-        BD_HIP(d_pairs_alt.alloc(n_emit * 8));
-        BD_HIP(hipMemset(st, 0, sizeof(BuildStats)));
-        hipLaunchKernelGGL(bd_windows_kernel<BD_EMIT>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
-                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, d_pairs.as<uint64_t>(), n_emit, st, FirstWindow{});
-        BD_HIP(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
-        if (hs.bad || hs.n_windows != n_emit) return kaamer_fail(KAAMER_E_HIP, "device build: the emit pass disagrees with the count pass");
-        tr.lap("emit", n_emit);
     }
-    // the order of the arena: a second run of the window kernel takes, per key, the smallest window position
-    const RankSource by_walk = [&](const FirstWindow &fw) {
-        hipLaunchKernelGGL(bd_windows_kernel<BD_FIRST>, dim3((unsigned)n_tiles), dim3(BD_THREADS), 0, 0, d_seqs.as<uint8_t>(), d_off.as<uint64_t>(),
-                           d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, (uint64_t *)nullptr, 0ull, st, fw);
-        BD_HIP(hipGetLastError());
-        d_seqs.release(); d_off.release(); d_ids.release();   // (hipFree waits for the kernel)
-        return (int)KAAMER_OK;
-    };
-    return bd_build_from_pairs(d_pairs, d_pairs_alt, n_emit, shard, n_shards, load, st, tr, origin + total_res, by_walk, out);
+    const auto done = [&]() { d_seqs.release(); d_off.release(); d_ids.release(); };   // (hipFree waits for the kernel)
+    return bd_build_resident(d_seqs.as<uint8_t>(), d_off.as<uint64_t>(), d_ids.as<uint32_t>(), n_proteins, origin, total_res, shard, n_shards, load,
+                             tr, done, out);
+}
+
+// ... for a caller whose proteins are on the device already (the makedb FASTA reader: makedb_fasta.hip.inc); the three
+// buffers stay the caller's.  offsets[0] is 0; the table's ids are below 0xFFFFFFFF (a text has fewer '>' lines than that)
+int kaamer_build_resident(const uint8_t *d_seqs, const uint64_t *d_offsets, const uint32_t *d_ids, uint32_t n_proteins, uint64_t total_res,
+                          uint32_t shard, uint32_t n_shards, double load, int device, kaamer_device_image *out)
+{
+    out->d_buckets = nullptr;
+    out->d_arena = nullptr;
+    BD_HIP(hipSetDevice(device));
+    Trace tr;
+    return bd_build_resident(d_seqs, d_offsets, d_ids, n_proteins, 0, total_res, shard, n_shards, load, tr, [] {}, out);
 }
 
 namespace {
@@ -859,6 +884,8 @@ int bd_download(kaamer_device_image &di, kaamer_image **out)
 #include "merge_device.hip.inc"
 
 }  // namespace
+
+int kaamer_device_image_download(kaamer_device_image *di, kaamer_image **out) { return bd_download(*di, out); }
 
 extern "C" int kaamer_image_build_proteins_device(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids,
                                                   uint32_t n_proteins, uint32_t shard, uint32_t n_shards, double load_factor,

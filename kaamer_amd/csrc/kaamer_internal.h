@@ -28,6 +28,25 @@ struct kaamer_device_image {
 };
 int kaamer_build_on_device(const uint8_t *seqs, const uint64_t *offsets, const uint32_t *ids, uint32_t n_proteins,
                            uint32_t shard, uint32_t n_shards, double load, int device, kaamer_device_image *out);
+// ... the same build from packed proteins that lie on `device` already (offsets[0] = 0, 32 bytes of slack behind the last
+// residue); the three buffers stay the caller's
+int kaamer_build_resident(const uint8_t *d_seqs, const uint64_t *d_offsets, const uint32_t *d_ids, uint32_t n_proteins, uint64_t total_res,
+                          uint32_t shard, uint32_t n_shards, double load, int device, kaamer_device_image *out);
+// the host copy of an image that was made on the device; di's two allocations are freed
+int kaamer_device_image_download(kaamer_device_image *di, kaamer_image **out);
+// The table of a FASTA text whose accepted entries were packed elsewhere (the device reader): arrays of the right sizes for
+// the caller to fill with bulk copies (offsets n + 1 each, the first 0), then kaamer_proteins_fasta_seal for by_id and KStats
+struct kaamer_fasta_arrays {
+    uint32_t *ids;
+    uint8_t *seqs;
+    uint64_t *offsets;
+    char *entry_ids;
+    uint64_t *entry_off;
+    char *names;
+    uint64_t *name_off;
+};
+extern "C" kaamer_proteins *kaamer_proteins_fasta_new(uint32_t n, uint64_t seq_bytes, uint64_t id_bytes, uint64_t name_bytes, kaamer_fasta_arrays *a);
+extern "C" void kaamer_proteins_fasta_seal(kaamer_proteins *p);
 // what kaamer_image_merge and kaamer_image_merge_device check before anything is dereferenced (builder.cpp);
 // n_pairs[i] = the pairs input i enumerates
 int kaamer_merge_check(const kaamer_image *const *imgs, uint32_t n, uint64_t *n_pairs);

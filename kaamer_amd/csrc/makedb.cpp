@@ -535,6 +535,32 @@ int kaamer_image_build_makedb(const kaamer_proteins *p, uint32_t shard, uint32_t
                                        load_factor, out);
 }
 
+// the table of the device FASTA reader (makedb_fasta.hip.inc): sized here, filled there by bulk copies, sealed here
+kaamer_proteins *kaamer_proteins_fasta_new(uint32_t n, uint64_t seq_bytes, uint64_t id_bytes, uint64_t name_bytes, kaamer_fasta_arrays *a)
+{
+    kaamer_proteins *r = new (std::nothrow) kaamer_proteins();
+    if (!r) return nullptr;
+    try {
+        r->feature_names = { "ProteinName" };                                        // FASTA_DEF_FTS, inputFASTA.go:41
+        r->ids.resize(n); r->seqs.resize((size_t)seq_bytes); r->offsets.resize((size_t)n + 1);
+        r->entry_ids.resize((size_t)id_bytes); r->entry_off.resize((size_t)n + 1);
+        r->features.resize((size_t)name_bytes); r->feature_off.resize((size_t)n + 1);
+    } catch (const std::bad_alloc &) { delete r; return nullptr; }
+    a->ids = r->ids.data(); a->seqs = r->seqs.data(); a->offsets = r->offsets.data();
+    a->entry_ids = r->entry_ids.data(); a->entry_off = r->entry_off.data();
+    a->names = r->features.data(); a->name_off = r->feature_off.data();
+    return r;
+}
+
+void kaamer_proteins_fasta_seal(kaamer_proteins *r)
+{
+    const uint32_t n = (uint32_t)r->ids.size();
+    r->by_id.reserve(n);
+    for (uint32_t i = 0; i < n; i++) r->by_id[r->ids[i]] = i;                       // (a later record of an id wins, as add_protein)
+    r->n_aa = r->seqs.size();
+    r->n_kmers = r->n_aa - (uint64_t)n * (KAAMER_KMER_SIZE - 1);
+}
+
 // the packed proteins of a table, for the device builder (builder_device.hip)
 void kaamer_proteins_raw(const kaamer_proteins *p, const uint8_t **seqs, const uint64_t **offsets, const uint32_t **ids, uint32_t *n)
 {

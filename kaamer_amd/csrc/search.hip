@@ -1140,6 +1140,7 @@ static void subject_free(SubjectTable &t) { t = SubjectTable(); }
 
 #include "parse_text.hip.inc"
 #include "parse_fasta.hip.inc"
+#include "makedb_fasta.hip.inc"
 #include "inflate.hip.inc"
 
 extern "C" {
@@ -1207,15 +1208,7 @@ int kaamer_index_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
     kaamer_device_image di;
     const int rc = kaamer_build_on_device(seqs, offsets, ids, n_proteins, shard, n_shards, load_factor, device, &di);
     if (rc) return rc;
-    kaamer_index *ix = new (std::nothrow) kaamer_index();
-    if (!ix) { (void)hipFree(di.d_buckets); (void)hipFree(di.d_arena); return kaamer_fail(KAAMER_E_NOMEM, "index alloc"); }
-    ix->device = device;
-    ix->n_top = read_knobs().host_slots;
-    ix->hdr = di.hdr;
-    ix->d_buckets = di.d_buckets;
-    ix->d_arena = di.d_arena;   // its first 16 bytes are zero (builder_device.hip), as kaamer_index_open_image leaves them
-    *out = ix;
-    return KAAMER_OK;
+    return index_of_device_image(di, device, out);
 }
 
 int kaamer_index_open(const char *path, int device, kaamer_index **out)
