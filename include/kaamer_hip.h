@@ -268,6 +268,39 @@ int kaamer_makedb_fasta_device(const char *text, uint64_t len, uint64_t nb_befor
  * Image: byte for byte kaamer_image_build_makedb(kaamer_makedb_fasta(text)).  A bad shard: KAAMER_E_ARG. */
 int kaamer_image_build_fasta_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
                                     double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
+/* The TSV reader on the device (makedb_tsv.hip.inc): the rows are uploaded, read there, and the table with its feature
+ * columns comes back by bulk copies.  It computes kaamer_makedb_tsv's rules, stated per line:
+ *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped
+ *   header   the first line, split at every '\t' (read on the host, by the routine kaamer_makedb_tsv reads it with): a
+ *            column whose ASCII-lower-cased name is "entryid" is an EntryId column, "sequence" a Sequence column; every other
+ *            column is a feature, in column order, its name as written; duplicate feature names stay separate columns.  No
+ *            line at all or no EntryID column: KAAMER_E_FORMAT "TSV file doesn't contain 'EntryID' header"; no Sequence
+ *            column: the same with 'Sequence'
+ *   rows     every later line, an empty one included; its cells are the pieces between tabs.  Of H header columns only the
+ *            first H cells count: further cells are ignored (the documented divergence: the reference panics there),
+ *            missing cells are empty.  Where the header names EntryID or Sequence more than once, the last such column
+ *            that the row has wins
+ *   accept   a row whose Sequence cell has 7 bytes or more and whose EntryId cell is not empty; the k-th accepted row
+ *            (0-based) gets id id_base + k as uint32.  Nothing is upper-cased, nothing is trimmed (an interior '\r' is a
+ *            byte of its cell), bytes >= 0x80 stay as they are.  A rejected row takes no room anywhere
+ *   table    feature_names = the header's feature columns; features protein-major, n * n_features + 1 offsets; KStats over
+ *            the accepted rows
+ * A text holds at most 2^32 - 1 bytes (KAAMER_E_ARG beyond, before anything else is looked at: cut at any '\n'); a text with
+ * more lines than the reader indexes (2^32 - 16), or whose accepted rows times feature columns exceed that many cells, is
+ * KAAMER_E_CAPACITY, never a partial table.  Out of scope here: strict_scanner (it stays on kaamer_makedb_text), -offset /
+ * -length (the TSV loop ignores both), EMBL / GBK, compressed input, a whole-file driver.
+ *
+ * header == NULL: the first line of `text` is the header; with id_base = 0 the table is kaamer_makedb_tsv(text), field for
+ * field.  header != NULL: `header` (header_len bytes, no '\n' in it: KAAMER_E_ARG) is the header line without its line end and
+ * every line of `text` is a row.  That is the form for a file larger than one text: cut it at any '\n', give every piece the
+ * header and the number of rows accepted in front of it (kaamer_proteins_count of the pieces before), merge the tables
+ * with kaamer_proteins_merge: the whole text's table. */
+int kaamer_makedb_tsv_device(const char *text, uint64_t len, const char *header, uint64_t header_len,
+                             uint64_t id_base, int device, kaamer_proteins **out);
+/* text (header line first) -> table + one shard's image; the sequences never leave the device between the reader and the
+ * builder.  Image: byte for byte kaamer_image_build_makedb(kaamer_makedb_tsv(text)).  A bad shard: KAAMER_E_ARG. */
+int kaamer_image_build_tsv_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
+                                  double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
 /* One Protein entry (protein.proto).  Pointers go into the table and stay valid until it is freed;
  * feature i is features[feature_off[i] .. feature_off[i+1]). */
 typedef struct {
@@ -307,6 +340,9 @@ int kaamer_index_build_proteins(const uint8_t *seqs, const uint64_t *offsets, co
  * kaamer_makedb_fasta_device's */
 int kaamer_index_build_fasta(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
                              int device, kaamer_proteins **proteins, kaamer_index **out);
+/* ... the same from a TSV text (header line first); the reader is kaamer_makedb_tsv_device's */
+int kaamer_index_build_tsv(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
+                           int device, kaamer_proteins **proteins, kaamer_index **out);
 int kaamer_index_open(const char *path, int device, kaamer_index **out);
 void kaamer_index_close(kaamer_index *ix);
 int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out);

@@ -110,6 +110,15 @@ class Image(_Handle):
         return Proteins(p), cls(im)
 
     @classmethod
+    def from_tsv_text(cls, text, shard=0, n_shards=1, load_factor=0.5, device=0):
+        """(proteins, image) of a database TSV text (header line first), read and built on GPU `device`
+        (kaamer_image_build_tsv_device): the sequences stay there between the reader and the builder."""
+        text = bytes(text)
+        p, im = C.c_void_p(), C.c_void_p()
+        abi.check(abi.lib().kaamer_image_build_tsv_device(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(im)))
+        return Proteins(p), cls(im)
+
+    @classmethod
     def merge(cls, images, load_factor=0.5, device=None):
         """kaamer-db -merge: the union of images of one shard (kaamer_image_merge).  device=None: on the host;
         device=d: the same image made on GPU d (byte-identical)."""
@@ -165,8 +174,17 @@ class Proteins(_Handle):
         return cls(_new(abi.lib().kaamer_makedb_fasta_device, text, len(text), int(nb_before), int(bool(more)), int(device)))
 
     @classmethod
-    def from_tsv(cls, text):
-        return cls._make(abi.lib().kaamer_makedb_tsv, text)
+    def from_tsv(cls, text, device=None, header=None, id_base=0):
+        """device=None: kaamer_makedb_tsv on the host.  device=d: the same table read on GPU d (kaamer_makedb_tsv_device);
+        there `text` may be a piece of a file cut at any line end: header = the file's header line without its line end (every
+        line of the piece is a row then), id_base = the rows accepted in front of the piece (len() of the pieces before)."""
+        if device is None:
+            if header is not None or id_base:
+                raise ValueError("header / id_base belong to the device reader")
+            return cls._make(abi.lib().kaamer_makedb_tsv, text)
+        text = bytes(text)
+        header = None if header is None else bytes(header)
+        return cls(_new(abi.lib().kaamer_makedb_tsv_device, text, len(text), header, len(header or b""), int(id_base), int(device)))
 
     @classmethod
     def from_embl(cls, text):
@@ -524,6 +542,15 @@ class Index(_Handle):
         text = bytes(text)
         p, ix = C.c_void_p(), C.c_void_p()
         abi.check(abi.lib().kaamer_index_build_fasta(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(ix)))
+        return Proteins(p), cls(ix, device)
+
+    @classmethod
+    def from_tsv_text(cls, text, shard=0, n_shards=1, load_factor=0.5, device=0):
+        """(proteins, index) of a database TSV text (header line first), read and built on the device it is searched on
+        (kaamer_index_build_tsv)"""
+        text = bytes(text)
+        p, ix = C.c_void_p(), C.c_void_p()
+        abi.check(abi.lib().kaamer_index_build_tsv(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(ix)))
         return Proteins(p), cls(ix, device)
 
     @classmethod

@@ -34,19 +34,33 @@ int kaamer_build_resident(const uint8_t *d_seqs, const uint64_t *d_offsets, cons
                           uint32_t shard, uint32_t n_shards, double load, int device, kaamer_device_image *out);
 // the host copy of an image that was made on the device; di's two allocations are freed
 int kaamer_device_image_download(kaamer_device_image *di, kaamer_image **out);
-// The table of a FASTA text whose accepted entries were packed elsewhere (the device reader): arrays of the right sizes for
-// the caller to fill with bulk copies (offsets n + 1 each, the first 0), then kaamer_proteins_fasta_seal for by_id and KStats
-struct kaamer_fasta_arrays {
+// The table of a text whose accepted entries were packed elsewhere (the device readers): arrays of the right sizes for the
+// caller to fill with bulk copies (offsets and entry_off n + 1, feature_off n * features + 1, the first 0 each), then
+// kaamer_proteins_table_seal for by_id and KStats.  The FASTA reader's feature_names are {"ProteinName"}
+struct kaamer_table_arrays {
     uint32_t *ids;
     uint8_t *seqs;
     uint64_t *offsets;
     char *entry_ids;
     uint64_t *entry_off;
-    char *names;
-    uint64_t *name_off;
+    char *features;
+    uint64_t *feature_off;
 };
-extern "C" kaamer_proteins *kaamer_proteins_fasta_new(uint32_t n, uint64_t seq_bytes, uint64_t id_bytes, uint64_t name_bytes, kaamer_fasta_arrays *a);
-extern "C" void kaamer_proteins_fasta_seal(kaamer_proteins *p);
+kaamer_proteins *kaamer_proteins_table_new(const std::vector<std::string> &feature_names, uint32_t n, uint64_t seq_bytes, uint64_t id_bytes,
+                                           uint64_t feature_bytes, kaamer_table_arrays *a);
+extern "C" void kaamer_proteins_table_seal(kaamer_proteins *p);
+// The header row of a TSV database (inputTSV.go:94-115), one statement for the host reader and the device reader: slot[i] is
+// column i's feature index, or one of the two required columns ("entryid" / "sequence" in any ASCII case; each may occur more
+// than once).  [b, e): the line without its end (b == NULL: the text has no line).  KAAMER_E_FORMAT with the reader's two
+// messages when a required column is missing.
+enum { KAAMER_TSV_ENTRY_ID = -1, KAAMER_TSV_SEQUENCE = -2 };
+struct kaamer_tsv_columns {
+    std::vector<int> slot;
+    std::vector<std::string> feature_names;   // as written, duplicates kept
+};
+int kaamer_tsv_header(const char *b, const char *e, kaamer_tsv_columns *c);
+// ... of a text's first line (one trailing '\r' dropped); *rows_at: where the second line starts (len: there is none)
+int kaamer_tsv_header_of_text(const char *text, uint64_t len, kaamer_tsv_columns *c, uint64_t *rows_at);
 // what kaamer_image_merge and kaamer_image_merge_device check before anything is dereferenced (builder.cpp);
 // n_pairs[i] = the pairs input i enumerates
 int kaamer_merge_check(const kaamer_image *const *imgs, uint32_t n, uint64_t *n_pairs);

@@ -165,6 +165,52 @@ extern "C" {
 
 int kaamer_makedb_fasta(const char *text, uint64_t len, kaamer_proteins **out) { return makedb_fasta(text, len, Range(), out); }
 
+}  // extern "C"
+
+namespace {
+
+std::vector<std::string> split_tabs(const char *b, const char *e)
+{
+    std::vector<std::string> cols;
+    const char *s = b;
+    for (const char *c = b;; c++)
+        if (c == e || *c == '\t') { cols.emplace_back(s, c); s = c + 1; if (c == e) break; }
+    return cols;
+}
+
+}  // namespace
+
+// the header row [b, e) of a TSV, inputTSV.go:94-115 (b == nullptr: the text has no line): which column is what.  One
+// statement for kaamer_makedb_tsv and the device reader (makedb_tsv.hip.inc)
+int kaamer_tsv_header(const char *b, const char *e, kaamer_tsv_columns *c)
+{
+    c->slot.clear();
+    c->feature_names.clear();
+    if (!b) return kaamer_fail(KAAMER_E_FORMAT, "TSV file doesn't contain 'EntryID' header");
+    bool has_id = false, has_seq = false;
+    for (auto &f : split_tabs(b, e)) {
+        const std::string lf = lower(f);
+        if (lf == "entryid") { has_id = true; c->slot.push_back(KAAMER_TSV_ENTRY_ID); }
+        else if (lf == "sequence") { has_seq = true; c->slot.push_back(KAAMER_TSV_SEQUENCE); }
+        else { c->slot.push_back((int)c->feature_names.size()); c->feature_names.push_back(f); }
+    }
+    if (!has_id || !has_seq)
+        return kaamer_fail(KAAMER_E_FORMAT, has_id ? "TSV file doesn't contain 'Sequence' header" : "TSV file doesn't contain 'EntryID' header");
+    return KAAMER_OK;
+}
+
+// ... of the text's first line; *rows_at: where the line behind it starts (len: there is none)
+int kaamer_tsv_header_of_text(const char *text, uint64_t len, kaamer_tsv_columns *c, uint64_t *rows_at)
+{
+    Lines lr{ text, text + len };
+    const char *b = nullptr, *e = nullptr;
+    if (!lr.next(b, e)) b = e = nullptr;
+    *rows_at = (uint64_t)(lr.p - text);
+    return kaamer_tsv_header(b, e, c);
+}
+
+extern "C" {
+
 int kaamer_makedb_tsv(const char *text, uint64_t len, kaamer_proteins **out)
 {
     if (!out || (!text && len)) return kaamer_fail(KAAMER_E_ARG, "makedb_tsv: bad argument");
@@ -173,47 +219,26 @@ int kaamer_makedb_tsv(const char *text, uint64_t len, kaamer_proteins **out)
     if (!r) return kaamer_fail(KAAMER_E_NOMEM, "makedb_tsv");
     Lines lr{ text, text + len };
     const char *b, *e;
-    auto split = [](const char *b, const char *e) {
-        std::vector<std::string> cols;
-        const char *s = b;
-        for (const char *c = b;; c++)
-            if (c == e || *c == '\t') { cols.emplace_back(s, c); s = c + 1; if (c == e) break; }
-        return cols;
-    };
-    std::vector<std::string> header;
-    std::vector<int> feat_slot;  // column -> feature index, -1 entryid, -2 sequence
-    bool first = true;
+    kaamer_tsv_columns hdr;      // column -> feature index, or EntryId / Sequence
+    if (!lr.next(b, e)) b = e = nullptr;
+    const int hrc = kaamer_tsv_header(b, e, &hdr);                                   // :94-115
+    if (hrc) { delete r; return hrc; }
+    r->feature_names = hdr.feature_names;
+    const std::vector<int> &feat_slot = hdr.slot;
     uint32_t protein_nb = 0;                                                         // inputTSV.go:62
     while (lr.next(b, e)) {
-        if (first) {                                                                 // :94-115
-            header = split(b, e);
-            bool has_id = false, has_seq = false;
-            for (auto &f : header) {
-                const std::string lf = lower(f);
-                if (lf == "entryid") { has_id = true; feat_slot.push_back(-1); }
-                else if (lf == "sequence") { has_seq = true; feat_slot.push_back(-2); }
-                else { feat_slot.push_back((int)r->feature_names.size()); r->feature_names.push_back(f); }
-            }
-            if (!has_id || !has_seq) {
-                delete r;
-                return kaamer_fail(KAAMER_E_FORMAT, has_id ? "TSV file doesn't contain 'Sequence' header" : "TSV file doesn't contain 'EntryID' header");
-            }
-            first = false;
-            continue;
-        }
-        const std::vector<std::string> cols = split(b, e);                           // :118-119
+        const std::vector<std::string> cols = split_tabs(b, e);                      // :118-119
         std::string entry_id, seq;
         std::vector<std::string> feat(r->feature_names.size());
-        for (size_t i = 0; i < cols.size() && i < header.size(); i++) {              // :125-134
-            if (feat_slot[i] == -1) entry_id = cols[i];
-            else if (feat_slot[i] == -2) seq = cols[i];
+        for (size_t i = 0; i < cols.size() && i < feat_slot.size(); i++) {           // :125-134
+            if (feat_slot[i] == KAAMER_TSV_ENTRY_ID) entry_id = cols[i];
+            else if (feat_slot[i] == KAAMER_TSV_SEQUENCE) seq = cols[i];
             else feat[(size_t)feat_slot[i]] = cols[i];
         }
         if (seq.size() < KAAMER_KMER_SIZE || entry_id.empty()) continue;             // :137-139
         add_protein(r, protein_nb, entry_id, seq, feat);                             // :140-141: ids count the accepted rows
         protein_nb++;
     }
-    if (first) { delete r; return kaamer_fail(KAAMER_E_FORMAT, "TSV file doesn't contain 'EntryID' header"); }
     *out = r;
     return KAAMER_OK;
 }
@@ -535,24 +560,29 @@ int kaamer_image_build_makedb(const kaamer_proteins *p, uint32_t shard, uint32_t
                                        load_factor, out);
 }
 
-// the table of the device FASTA reader (makedb_fasta.hip.inc): sized here, filled there by bulk copies, sealed here
-kaamer_proteins *kaamer_proteins_fasta_new(uint32_t n, uint64_t seq_bytes, uint64_t id_bytes, uint64_t name_bytes, kaamer_fasta_arrays *a)
+}  // extern "C"
+
+// the table of a device reader (makedb_fasta.hip.inc, makedb_tsv.hip.inc): sized here, filled there by bulk copies, sealed here
+kaamer_proteins *kaamer_proteins_table_new(const std::vector<std::string> &feature_names, uint32_t n, uint64_t seq_bytes, uint64_t id_bytes,
+                                           uint64_t feature_bytes, kaamer_table_arrays *a)
 {
     kaamer_proteins *r = new (std::nothrow) kaamer_proteins();
     if (!r) return nullptr;
     try {
-        r->feature_names = { "ProteinName" };                                        // FASTA_DEF_FTS, inputFASTA.go:41
+        r->feature_names = feature_names;
         r->ids.resize(n); r->seqs.resize((size_t)seq_bytes); r->offsets.resize((size_t)n + 1);
         r->entry_ids.resize((size_t)id_bytes); r->entry_off.resize((size_t)n + 1);
-        r->features.resize((size_t)name_bytes); r->feature_off.resize((size_t)n + 1);
+        r->features.resize((size_t)feature_bytes); r->feature_off.resize((size_t)n * feature_names.size() + 1);
     } catch (const std::bad_alloc &) { delete r; return nullptr; }
     a->ids = r->ids.data(); a->seqs = r->seqs.data(); a->offsets = r->offsets.data();
     a->entry_ids = r->entry_ids.data(); a->entry_off = r->entry_off.data();
-    a->names = r->features.data(); a->name_off = r->feature_off.data();
+    a->features = r->features.data(); a->feature_off = r->feature_off.data();
     return r;
 }
 
-void kaamer_proteins_fasta_seal(kaamer_proteins *r)
+extern "C" {
+
+void kaamer_proteins_table_seal(kaamer_proteins *r)
 {
     const uint32_t n = (uint32_t)r->ids.size();
     r->by_id.reserve(n);

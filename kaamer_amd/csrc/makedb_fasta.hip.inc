@@ -400,9 +400,10 @@ struct MfReader {
     ~MfReader() { (void)hipSetDevice(device); }   // (before the buffers go)
 };
 
-// KAAMER_MAKEDB_TRACE: the reader's stages by HIP events, on stderr
+// KAAMER_MAKEDB_TRACE: a reader's stages by HIP events, on stderr
 struct MfTrace {
     bool on = getenv("KAAMER_MAKEDB_TRACE") != nullptr;
+    const char *format = "fasta";   // (makedb_tsv.hip.inc: "tsv")
     uint64_t bytes = 0;
     hipEvent_t a = nullptr, b = nullptr;
     ~MfTrace() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
@@ -414,7 +415,7 @@ struct MfTrace {
         (void)hipEventRecord(b, 0);
         (void)hipEventSynchronize(b);
         (void)hipEventElapsedTime(&ms, a, b);
-        fprintf(stderr, "[kaamer makedb fasta] %-16s %9.3f ms  %8.2f GB/s of text\n", what, ms, ms > 0 ? (double)bytes / ms * 1e-6 : 0.0);
+        fprintf(stderr, "[kaamer makedb %s] %-16s %9.3f ms  %8.2f GB/s of text\n", format, what, ms, ms > 0 ? (double)bytes / ms * 1e-6 : 0.0);
         (void)hipEventRecord(a, 0);
     }
 };
@@ -524,8 +525,8 @@ static int mf_table(MfReader &m, kaamer_proteins **out)
     MfTrace tr;
     tr.bytes = m.f.pt.n;
     tr.begin();
-    kaamer_fasta_arrays a;
-    kaamer_proteins *t = kaamer_proteins_fasta_new((uint32_t)m.n_rec, m.seq_bytes, m.id_bytes, m.name_bytes, &a);
+    kaamer_table_arrays a;
+    kaamer_proteins *t = kaamer_proteins_table_new({ "ProteinName" }, (uint32_t)m.n_rec, m.seq_bytes, m.id_bytes, m.name_bytes, &a);   // FASTA_DEF_FTS, inputFASTA.go:41
     if (!t) return kaamer_fail(KAAMER_E_NOMEM, "makedb_fasta_device: the table");
     const size_t n = (size_t)m.n_rec;
     hipError_t e = hipSuccess;
@@ -535,11 +536,11 @@ static int mf_table(MfReader &m, kaamer_proteins **out)
     get(a.seqs, m.d_seqs, (size_t)m.seq_bytes);
     get(a.entry_off, m.f.id_off, (n + 1) * 8);
     get(a.entry_ids, m.d_idb, (size_t)m.id_bytes);
-    get(a.name_off, m.f.name_off, (n + 1) * 8);
-    get(a.names, m.d_nameb, (size_t)m.name_bytes);
+    get(a.feature_off, m.f.name_off, (n + 1) * 8);
+    get(a.features, m.d_nameb, (size_t)m.name_bytes);
     if (e != hipSuccess) { kaamer_proteins_free(t); return kaamer_fail(KAAMER_E_HIP, "makedb_fasta_device: download: %s", hipGetErrorString(e)); }
     tr.lap("download");
-    kaamer_proteins_fasta_seal(t);
+    kaamer_proteins_table_seal(t);
     *out = t;
     return KAAMER_OK;
 }
@@ -572,10 +573,11 @@ int kaamer_makedb_fasta_device(const char *text, uint64_t len, uint64_t nb_befor
     return mf_table(m, out);
 }
 
-// the arguments of the two calls that build from a text
-static int mf_build_args(const char *who, const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, const void *proteins, const void *out)
+// the arguments of the calls that build from a text (`cut`: where such a text may be cut)
+static int mf_build_args(const char *who, const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, const void *proteins, const void *out,
+                         const char *cut = "(kaamer_text_cut_fasta)")
 {
-    if (len > 0xFFFFFFFFull) return kaamer_fail(KAAMER_E_ARG, "%s: a text holds at most 2^32 - 1 bytes: cut it (kaamer_text_cut_fasta)", who);
+    if (len > 0xFFFFFFFFull) return kaamer_fail(KAAMER_E_ARG, "%s: a text holds at most 2^32 - 1 bytes: cut it %s", who, cut);
     if (!proteins || !out || (!text && len) || n_shards == 0 || shard >= n_shards) return kaamer_fail(KAAMER_E_ARG, "%s: bad argument", who);
     return KAAMER_OK;
 }

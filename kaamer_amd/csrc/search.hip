@@ -1141,6 +1141,7 @@ static void subject_free(SubjectTable &t) { t = SubjectTable(); }
 #include "parse_text.hip.inc"
 #include "parse_fasta.hip.inc"
 #include "makedb_fasta.hip.inc"
+#include "makedb_tsv.hip.inc"
 #include "inflate.hip.inc"
 
 extern "C" {
