@@ -301,6 +301,51 @@ int kaamer_makedb_tsv_device(const char *text, uint64_t len, const char *header,
  * builder.  Image: byte for byte kaamer_image_build_makedb(kaamer_makedb_tsv(text)).  A bad shard: KAAMER_E_ARG. */
 int kaamer_image_build_tsv_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
                                   double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
+/* The EMBL reader on the device (makedb_embl.hip.inc): the text of a UniProt flat file (-f embl) is uploaded, read there,
+ * and the table with its ten feature columns comes back by bulk copies.  It computes kaamer_makedb_embl's rules
+ * (process_embl_entry is their statement), per line:
+ *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped.  A line that is then exactly
+ *            "//" ends an entry and takes a number, even when the entry is empty; "// ", "///" and "//\r\r" are ordinary
+ *            lines.  Lines shorter than 2 bytes are ignored; what lies behind the last "//" is never queued
+ *   tag      the first two bytes; only ID GN DE OX OS OC DR SQ and two spaces matter, every other line is skipped without
+ *            being read further
+ *   Skip     drops the whole entry: a line of a read tag with fewer than 5 bytes (a two-space line of 2 to 4 bytes too; a GN
+ *            line that short holds no "Name=" and is not read); ID / OX / DR with no field behind column 5; an OX first
+ *            field under 12 bytes; a matched DR (KEGG; GO; BioCyc; HAMAP;) without a second field; SQ with fewer than two
+ *            fields; a DE line under 19 bytes that is RecName or SubName, or under 17 bytes that is EC; a declared length
+ *            above the residues held
+ *   drops    a DE line whose [5:] contains none of RecName, SubName, EC= but contains "Flags: Fragment;"; a declared length
+ *            below 7 (the last SQ line wins, a number Atoi refuses is 0)
+ *   order    GN is looked at only while GeneName is empty: among the GN lines that contain "Name=" anywhere, the first that
+ *            is malformed (no field, or a first field under 5 bytes) or yields a non-empty value decides: Skip, or the value.
+ *            ProteinName: the last RecName line resets it, each later SubName appends ";;" + v if the value so far is
+ *            non-empty, else becomes the value; without a RecName the same from the first SubName.  EC, TaxId, EntryId: the
+ *            last line wins
+ *   separators  Organism (" ") and the four DR columns (";") in front of every contribution but the first, even when earlier
+ *            ones were empty; FullTaxonomy " " only when what is gathered so far is non-empty
+ *   values   " {.*};" is removed greedily (first " {" to the last "};" behind it), then all trailing ';' are cut, which may
+ *            reach in front of the removed span; OS loses all trailing '.'; GN is field 0 [5:], OX field 0 [12:], the DR value
+ *            field 1, each less its trailing ';'; fields split at ' ' and '\t'..'\r'
+ *   sequence every two-space line's bytes behind column 5 with ' ' removed, wherever the line stands; nothing is upper-cased,
+ *            bytes >= 0x80 stay.  Indexed is Sequence[:declared]; kaamer_fetch_hits returns sequence_len > length with the
+ *            whole string for an entry that holds more
+ *   table    feature_names = EMBL_DEF_FTS (ProteinName GeneName EC GO KEGG_ID BioCyc_ID HAMAP Organism TaxId FullTaxonomy);
+ *            KStats over the kept entries
+ * A text holds at most 2^32 - 1 bytes (KAAMER_E_ARG beyond, before anything else is looked at: cut at kaamer_text_cut_embl).
+ * One that starts with the gzip signature is inflated on the host first, as kaamer_makedb_embl does, and an inflated text
+ * beyond 2^32 - 1 bytes is KAAMER_E_ARG.  A text with more lines than the reader indexes (2^32 - 16) is KAAMER_E_CAPACITY,
+ * never a partial table.  Out of scope here: GBK, -offset / -length and strict_scanner (they stay on
+ * kaamer_makedb_text_range), a whole-file driver, compressed input on the device.
+ *
+ * nb_before: the "//" lines in front of this text; record k of it (1-based ordinal of its "//") gets id
+ * (uint32_t)(nb_before + k).  nb_before = 0 is kaamer_makedb_embl(text), field for field, for every input.  Pieces cut at
+ * kaamer_text_cut_embl, each with the "//" count in front of it, merged with kaamer_proteins_merge, are the whole text's
+ * table. */
+int kaamer_makedb_embl_device(const char *text, uint64_t len, uint64_t nb_before, int device, kaamer_proteins **out);
+/* text -> table + one shard's image; the builder sees the indexed prefixes where they lie on the device.  Image: byte for
+ * byte kaamer_image_build_makedb(kaamer_makedb_embl(text)).  A bad shard: KAAMER_E_ARG. */
+int kaamer_image_build_embl_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
+                                   double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
 /* One Protein entry (protein.proto).  Pointers go into the table and stay valid until it is freed;
  * feature i is features[feature_off[i] .. feature_off[i+1]). */
 typedef struct {
@@ -343,6 +388,9 @@ int kaamer_index_build_fasta(const char *text, uint64_t len, uint32_t shard, uin
 /* ... the same from a TSV text (header line first); the reader is kaamer_makedb_tsv_device's */
 int kaamer_index_build_tsv(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
                            int device, kaamer_proteins **proteins, kaamer_index **out);
+/* ... the same from an EMBL text; the reader is kaamer_makedb_embl_device's */
+int kaamer_index_build_embl(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
+                            int device, kaamer_proteins **proteins, kaamer_index **out);
 int kaamer_index_open(const char *path, int device, kaamer_index **out);
 void kaamer_index_close(kaamer_index *ix);
 int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out);
@@ -1463,6 +1511,10 @@ int kaamer_parse_fasta_device(kaamer_text_parser *p, const uint8_t *d_text, uint
  * line guarantees that a record follows the cut: every piece in front of a cut is parsed with upper_last = 1, the piece
  * at the end of the input with 0, and the pieces' records are the records of the whole. */
 uint64_t kaamer_text_cut_fasta(const char *text, uint64_t len);
+/* CPU only.  Where an EMBL text may be cut (kaamer_makedb_embl_device): the greatest p <= len such that text[0, p) ends with
+ * the line end of a line that is exactly "//" after the '\r' drop; 0: none.  A final "//" without '\n' counts only when it
+ * is the text's last line, and then p = len: of a prefix that ends inside a line this holds only if the input ends there. */
+uint64_t kaamer_text_cut_embl(const char *text, uint64_t len);
 /* kaamer_submit_text_top_flat / kaamer_search_text_top_flat for FASTA text (search_protein.go:38-120, search_nucleotide.go,
  * search_fastq.go with GetQueriesFasta inside): the same slot, ticket, wait, repeat beyond a bound (from the parsed
  * buffers), discard and kaamer_batch_top_text_spans.  seq_type: base KAAMER_PROTEIN, KAAMER_NUCLEOTIDE or KAAMER_READS, the

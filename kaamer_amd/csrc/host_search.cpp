@@ -272,6 +272,25 @@ uint64_t kaamer_text_cut_fasta(const char *text, uint64_t len)
     return 0;
 }
 
+// Where an EMBL text may be cut (the rules: include/kaamer_hip.h): behind the line end of a line that is exactly "//" once
+// its trailing '\r' is dropped.  Such a line closes an entry and takes a number; nothing else of the reader's state crosses
+// it.  One walk over the lines from the end.
+uint64_t kaamer_text_cut_embl(const char *text, uint64_t len)
+{
+    if (!text) return 0;
+    uint64_t le = len;   // the end of the line being looked at: the position of its '\n', or len
+    if (len && text[len - 1] == '\n') le = len - 1;
+    while (len) {
+        const char *nl = le ? (const char *)memrchr(text, '\n', (size_t)le) : nullptr;
+        const uint64_t ls = nl ? (uint64_t)(nl - text) + 1 : 0;
+        const uint64_t e = (le > ls && text[le - 1] == '\r') ? le - 1 : le;
+        if (e - ls == 2 && text[ls] == '/' && text[ls + 1] == '/') return le < len ? le + 1 : len;
+        if (!ls) break;
+        le = ls - 1;
+    }
+    return 0;
+}
+
 // The blocks of a BGZF stream, found without inflating (the rules: include/kaamer_hip.h).  A member is
 //   1f 8b 08 FLG=4 MTIME(4) XFL OS XLEN(2) | extra field of XLEN bytes: subfields SI1 SI2 SLEN(2) data | deflate | CRC32 ISIZE
 // and the subfield 'B' 'C' with SLEN 2 holds BSIZE = the member's size - 1.

@@ -49,6 +49,10 @@ struct kaamer_table_arrays {
 kaamer_proteins *kaamer_proteins_table_new(const std::vector<std::string> &feature_names, uint32_t n, uint64_t seq_bytes, uint64_t id_bytes,
                                            uint64_t feature_bytes, kaamer_table_arrays *a);
 extern "C" void kaamer_proteins_table_seal(kaamer_proteins *p);
+// ... and, for the EMBL reader, the whole strings of the n records that hold more residues than their SQ line declares
+// (Protein.Sequence against what is indexed, inputEMBL.go:293-312): record recs[i] stores bytes[off[i] .. off[i + 1]).
+// 0, or KAAMER_E_NOMEM
+int kaamer_proteins_table_full_seqs(kaamer_proteins *p, const uint32_t *recs, const uint64_t *off, const char *bytes, uint32_t n);
 // The header row of a TSV database (inputTSV.go:94-115), one statement for the host reader and the device reader: slot[i] is
 // column i's feature index, or one of the two required columns ("entryid" / "sequence" in any ASCII case; each may occur more
 // than once).  [b, e): the line without its end (b == NULL: the text has no line).  KAAMER_E_FORMAT with the reader's two

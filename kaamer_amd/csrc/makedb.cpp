@@ -562,7 +562,7 @@ int kaamer_image_build_makedb(const kaamer_proteins *p, uint32_t shard, uint32_t
 
 }  // extern "C"
 
-// the table of a device reader (makedb_fasta.hip.inc, makedb_tsv.hip.inc): sized here, filled there by bulk copies, sealed here
+// the table of a device reader (makedb_fasta.hip.inc, makedb_tsv.hip.inc, makedb_embl.hip.inc): sized here, filled there by bulk copies, sealed here
 kaamer_proteins *kaamer_proteins_table_new(const std::vector<std::string> &feature_names, uint32_t n, uint64_t seq_bytes, uint64_t id_bytes,
                                            uint64_t feature_bytes, kaamer_table_arrays *a)
 {
@@ -578,6 +578,16 @@ kaamer_proteins *kaamer_proteins_table_new(const std::vector<std::string> &featu
     a->entry_ids = r->entry_ids.data(); a->entry_off = r->entry_off.data();
     a->features = r->features.data(); a->feature_off = r->feature_off.data();
     return r;
+}
+
+// the whole strings of the records that hold more residues than they declare (makedb_embl.hip.inc): record recs[i] stores
+// bytes[off[i] .. off[i + 1]), as makedb_flat's send() leaves it in full_seq
+int kaamer_proteins_table_full_seqs(kaamer_proteins *r, const uint32_t *recs, const uint64_t *off, const char *bytes, uint32_t n)
+{
+    try {
+        for (uint32_t i = 0; i < n; i++) r->full_seq[recs[i]].assign(bytes + off[i], bytes + off[i + 1]);
+    } catch (const std::bad_alloc &) { return KAAMER_E_NOMEM; }
+    return KAAMER_OK;
 }
 
 extern "C" {

@@ -1142,6 +1142,7 @@ static void subject_free(SubjectTable &t) { t = SubjectTable(); }
 #include "parse_fasta.hip.inc"
 #include "makedb_fasta.hip.inc"
 #include "makedb_tsv.hip.inc"
+#include "makedb_embl.hip.inc"
 #include "inflate.hip.inc"
 
 extern "C" {

@@ -3,7 +3,10 @@
 // kaamer_search_fasta_file (byte source -> chunks cut before an '@' / a '>' that opens a line) over hand cases and random
 // texts, plain and gzip; every chunk is parsed with the host reader (FASTA: every chunk but the last with its last record
 // upper-cased, as upper_last = 1 does on the device) and the concatenation must equal the host parse of the whole text.
-// The FASTA cut is also held against a straight restatement of its rule.  CPU only.    make -C tools/text_cut_check test
+// The FASTA cut is also held against a straight restatement of its rule.  kaamer_text_cut_embl (the cut of the device EMBL
+// reader's pieces) goes the same way: hand cases and random texts against a restatement, and the host tables of the two pieces
+// a cut leaves (kaamer_makedb_embl, ids moved on by the terminators in front) against the whole text's.  CPU only.
+//   make -C tools/text_cut_check test
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -104,6 +107,43 @@ static bool fa_ref_chunks(const std::string &t, size_t budget, std::vector<size_
         a += take;
     }
     return true;
+}
+
+// ---- kaamer_text_cut_embl, restated: the end of the last line that is exactly "//" once one trailing '\r' is dropped
+static uint64_t embl_ref_cut(const std::string &t, uint64_t *n_terms = nullptr)
+{
+    uint64_t best = 0, n = 0;
+    for (size_t at = 0; at < t.size();) {
+        const size_t nl = t.find('\n', at);
+        const size_t end = nl == std::string::npos ? t.size() : nl, next = nl == std::string::npos ? t.size() : nl + 1;
+        size_t e = end;
+        if (e > at && t[e - 1] == '\r') e--;
+        if (e - at == 2 && t[at] == '/' && t[at + 1] == '/') { best = next; n++; }
+        at = next;
+    }
+    if (n_terms) *n_terms = n;
+    return best;
+}
+// every record of the host's table of an EMBL text: id + id_shift, EntryId, what is indexed, the stored Sequence, the cells
+static void embl_dump(const std::string &text, uint64_t id_shift, std::vector<std::string> *out, kaamer_proteins **keep)
+{
+    kaamer_proteins *p = nullptr;
+    const int rc = kaamer_makedb_embl(text.data(), text.size(), &p);
+    CHECK(rc == KAAMER_OK, "makedb_embl: %d", rc);
+    if (rc) return;
+    const uint32_t n = kaamer_proteins_count(p);
+    const uint32_t *ids = kaamer_proteins_ids(p);
+    const uint64_t *off = kaamer_proteins_offsets(p);
+    std::vector<kaamer_protein_entry> ent(n ? n : 1);
+    CHECK(kaamer_fetch_hits(p, ids, n, ent.data()) == KAAMER_OK, "fetch_hits");
+    for (uint32_t i = 0; i < n; i++) {
+        const kaamer_protein_entry &e = ent[i];
+        std::string r = std::to_string((uint32_t)(ids[i] + id_shift)) + "|" + std::string(e.entry_id, e.entry_id_len) + "|" +
+                        std::to_string(off[i + 1] - off[i]) + "|" + std::string((const char *)e.sequence, e.sequence_len);
+        for (uint32_t j = 0; j < e.n_features; j++) r += "|" + std::string(e.features + e.feature_off[j], e.features + e.feature_off[j + 1]);
+        out->push_back(r);
+    }
+    if (keep) *keep = p; else kaamer_proteins_free(p);
 }
 
 static std::string gzip_members(const std::string &text, size_t split)
@@ -267,6 +307,59 @@ int main()
     }
     CHECK(fa_fit * 2 >= 2000, "only %zu of 2000 random FASTA texts go through the chunk reader", fa_fit);
     CHECK(fa_with_cut * 4 >= 2000, "only %zu of 2000 random FASTA texts hold a cut", fa_with_cut);
+    // ---- EMBL: the cut by hand, against the restatement, and the pieces' tables against the whole text's
+    struct { const char *text; uint64_t cut; } em_hand[] = {
+        { "", 0 }, { "//", 2 }, { "//\n", 3 }, { "//\r\n", 4 }, { "//\r", 3 }, { "//\nID   x\n", 3 }, { "ID   x\n//", 9 }, { "ID   x\n//\n", 10 },
+        { "ID   x\r\n//\r\nID   y\r\n", 12 }, { "// \n", 0 }, { "///\n", 0 }, { " //\n", 0 }, { "//\r\r\n", 0 }, { "ID   x\nSQ\n", 0 }, { "\n", 0 },
+        { "\n\n//", 4 }, { "//\n//", 5 }, { "//\n//x", 3 }, { "a//\n//\nb//", 7 }, { "/", 0 }, { "/\n/\n", 0 },
+    };
+    for (auto &h : em_hand) {
+        const std::string t(h.text);
+        std::vector<char> exact(t.begin(), t.end());
+        const uint64_t cut = kaamer_text_cut_embl(exact.data(), exact.size());
+        CHECK(cut == h.cut, "EMBL cut of the hand case \"%s\": %llu, expected %llu", h.text, (unsigned long long)cut, (unsigned long long)h.cut);
+        CHECK(embl_ref_cut(t) == h.cut, "the restated EMBL cut of the hand case \"%s\"", h.text);
+    }
+    CHECK(kaamer_text_cut_embl(nullptr, 0) == 0, "NULL text");
+    const char *em_tokens[] = { "//", "//", "\n", "\n", "\r", "\r\n", "/", " ", "x", "ID   P1 x\n", "ID   P2 y\r\n", "SQ   SEQUENCE 8 AA;\n", "SQ   SEQUENCE 12 AA;\n",
+                                "     MAFSAEDVLK EYD\n", "     MKTAYIAK\r\n", "DE   RecName: Full=n {e};\n", "DR   GO; GO:1;\n", "OS   Org.\n", "//\n", "//\r\n" };
+    const size_t n_em = sizeof em_tokens / sizeof em_tokens[0];
+    size_t em_with_cut = 0, em_records = 0, em_second = 0;
+    for (int it = 0; it < 3000; it++) {
+        std::string text;
+        for (size_t i = 0, n = 10 + (size_t)rnd(60); i < n; i++) text += em_tokens[rnd(n_em)];
+        const std::string prefix = text.substr(0, (size_t)rnd(text.size() + 1));
+        std::vector<char> exact(prefix.begin(), prefix.end());
+        uint64_t n_terms = 0;
+        const uint64_t cut = kaamer_text_cut_embl(exact.data(), exact.size()), want = embl_ref_cut(prefix, &n_terms);
+        CHECK(cut == want, "EMBL cut of random text %d: %llu, the rule says %llu", it, (unsigned long long)cut, (unsigned long long)want);
+        em_with_cut += want != 0;
+        // (a prefix that ends inside a line: its last "//" is a terminator only if the input ends there, which the whole text denies)
+        if (cut == prefix.size() && cut < text.size() && prefix.back() != '\n') continue;
+        // the pieces [0, cut) and [cut, len) of the whole text: their tables, the second with its ids moved on, are the whole's
+        std::vector<std::string> whole, pieces;
+        kaamer_proteins *pw = nullptr, *pp[2] = { nullptr, nullptr }, *merged = nullptr;
+        embl_dump(text, 0, &whole, &pw);
+        embl_dump(text.substr(0, (size_t)cut), 0, &pieces, &pp[0]);
+        const size_t n_first = pieces.size();
+        embl_dump(text.substr((size_t)cut), n_terms, &pieces, &pp[1]);
+        CHECK(pieces == whole, "random EMBL text %d cut at %llu: %zu records piecewise, %zu at once", it, (unsigned long long)cut, pieces.size(), whole.size());
+        em_records += whole.size();
+        em_second += cut ? whole.size() - n_first : 0;
+        if (pw && pp[0] && pp[1]) {
+            CHECK(kaamer_proteins_merge(pp, 2, &merged) == KAAMER_OK, "proteins_merge");
+            const uint32_t n = merged ? kaamer_proteins_count(merged) : 0;
+            CHECK(merged && n == kaamer_proteins_count(pw), "merged records");
+            if (merged && n == kaamer_proteins_count(pw)) {
+                const bool same_off = !memcmp(kaamer_proteins_offsets(merged), kaamer_proteins_offsets(pw), ((size_t)n + 1) * 8);
+                CHECK(same_off, "merged offsets");
+                CHECK(!n || !same_off || !memcmp(kaamer_proteins_seqs(merged), kaamer_proteins_seqs(pw), (size_t)kaamer_proteins_offsets(pw)[n]), "merged sequences");
+            }
+        }
+        for (kaamer_proteins *q : { pw, pp[0], pp[1], merged }) if (q) kaamer_proteins_free(q);
+    }
+    CHECK(em_with_cut * 2 >= 3000, "only %zu of 3000 random EMBL texts hold a cut", em_with_cut);
+    CHECK(em_records >= 300 && em_second >= 50, "the random EMBL texts keep %zu records, %zu of them behind a cut", em_records, em_second);
     // the byte source's gzip rules: a stream that breaks off reads as what inflated before; a bad first header: nothing
     const std::string two = "@a\nACGT\n+\nIIII\n@b\nGGCC\n+\nIIII\n";
     std::string gz = gzip_members(two, 15);
