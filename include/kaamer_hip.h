@@ -346,6 +346,47 @@ int kaamer_makedb_embl_device(const char *text, uint64_t len, uint64_t nb_before
  * byte kaamer_image_build_makedb(kaamer_makedb_embl(text)).  A bad shard: KAAMER_E_ARG. */
 int kaamer_image_build_embl_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
                                    double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
+/* The GBK reader on the device (makedb_gbk.hip.inc): the text of a GenBank / GenPept flat file (-f gbk) is uploaded, read
+ * there, and the table with its three feature columns comes back by bulk copies.  It computes kaamer_makedb_gbk's rules
+ * (process_gbk_entry is their statement; where these words and that code differ, the code holds):
+ *   lines    split at '\n'; a last piece without '\n' is a line; one trailing '\r' is dropped.  A line that is then exactly
+ *            "//" ends an entry and takes a number, even when the entry is empty.  Lines shorter than 2 bytes change nothing
+ *            and contribute nothing; what lies behind the last "//" belongs to no entry
+ *   token    the line with leading and trailing ' ' removed (spaces only, not tabs), up to its first ' '; an all-space line
+ *            has the empty token.  Compared case-sensitively, it sets the section state: 0 for LOCUS ACCESSION KEYWORDS
+ *            SOURCE COMMENT REFERENCE DBLINK DBSOURCE, 1 DEFINITION, 2 VERSION, 3 ORGANISM, 4 FEATURES, 5 ORIGIN, 6 "//"
+ *            (" //" and "// x" are such lines inside an entry).  Any other token leaves the state as it is, every entry
+ *            starts in state 0, and a continuation line whose first word happens to be a keyword switches the state
+ *   contribution  under the state after the line's own token.  1: [12:] is appended to ProteinName, " " in front when what
+ *            is gathered so far is non-empty (an all-space line of 12 bytes or more adds a trailing space).  2: EntryId is
+ *            the first field of [12:], fields split at ' ' and '\t'..'\r'; the last such line wins.  3: while Organism is
+ *            empty, [12:] becomes Organism (an empty [12:] leaves it empty, the next line tries again); otherwise [12:] is
+ *            appended to FullTaxonomy, " " in front when that is non-empty.  5: [10:] with every ' ' removed and 'a'..'z'
+ *            upper-cased, other bytes (>= 0x80 too) as they are; the ORIGIN line itself contributes this way.  0, 4, 6:
+ *            nothing
+ *   Skip     drops the whole entry, where the reference would panic: a line of 2 to 11 bytes in state 1, 2 or 3; a line of
+ *            2 to 9 bytes in state 5, a bare ORIGIN among them; a state-2 line with no field behind column 12
+ *   drops    the joined ProteinName contains ", partial" (the match may span a join: one line ends in ',' and the next
+ *            one's [12:] starts with "partial"); fewer than 7 residues
+ *   ProteinName, last step  from the first " [" to the last "]." behind it is removed, on the joined string; the " [" may
+ *            be a join's space in front of a line that starts with '['
+ *   table    feature_names = GBK_DEF_FTS (ProteinName Organism FullTaxonomy); KStats over the kept entries.  GBK declares
+ *            no length, so no record has a whole string beside its indexed one: sequence_len == length
+ * A text holds at most 2^32 - 1 bytes (KAAMER_E_ARG beyond, before anything else is looked at: cut at kaamer_text_cut_embl,
+ * whose terminator is GBK's too).  One that starts with the gzip signature is inflated on the host first, as
+ * kaamer_makedb_gbk does, and an inflated text beyond 2^32 - 1 bytes is KAAMER_E_ARG.  A text with more lines than the reader
+ * indexes (2^32 - 16) is KAAMER_E_CAPACITY, never a partial table.  Out of scope here: -offset / -length and strict_scanner
+ * (they stay on kaamer_makedb_text_range), a whole-file driver, inflate on the device.
+ *
+ * nb_before: the "//" lines in front of this text; record k of it (1-based ordinal of its "//") gets id
+ * (uint32_t)(nb_before + k).  nb_before = 0 is kaamer_makedb_gbk(text), field for field, for every input.  Pieces cut at
+ * kaamer_text_cut_embl, each with the "//" count in front of it, merged with kaamer_proteins_merge, are the whole text's
+ * table. */
+int kaamer_makedb_gbk_device(const char *text, uint64_t len, uint64_t nb_before, int device, kaamer_proteins **out);
+/* text -> table + one shard's image; the builder sees the sequences where they lie on the device.  Image: byte for byte
+ * kaamer_image_build_makedb(kaamer_makedb_gbk(text)).  A bad shard: KAAMER_E_ARG. */
+int kaamer_image_build_gbk_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards,
+                                  double load_factor, int device, kaamer_proteins **proteins, kaamer_image **image);
 /* One Protein entry (protein.proto).  Pointers go into the table and stay valid until it is freed;
  * feature i is features[feature_off[i] .. feature_off[i+1]). */
 typedef struct {
@@ -391,6 +432,9 @@ int kaamer_index_build_tsv(const char *text, uint64_t len, uint32_t shard, uint3
 /* ... the same from an EMBL text; the reader is kaamer_makedb_embl_device's */
 int kaamer_index_build_embl(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
                             int device, kaamer_proteins **proteins, kaamer_index **out);
+/* ... the same from a GBK text; the reader is kaamer_makedb_gbk_device's */
+int kaamer_index_build_gbk(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor,
+                           int device, kaamer_proteins **proteins, kaamer_index **out);
 int kaamer_index_open(const char *path, int device, kaamer_index **out);
 void kaamer_index_close(kaamer_index *ix);
 int kaamer_index_get_stats(const kaamer_index *ix, kaamer_image_stats *out);
@@ -1513,7 +1557,8 @@ int kaamer_parse_fasta_device(kaamer_text_parser *p, const uint8_t *d_text, uint
 uint64_t kaamer_text_cut_fasta(const char *text, uint64_t len);
 /* CPU only.  Where an EMBL text may be cut (kaamer_makedb_embl_device): the greatest p <= len such that text[0, p) ends with
  * the line end of a line that is exactly "//" after the '\r' drop; 0: none.  A final "//" without '\n' counts only when it
- * is the text's last line, and then p = len: of a prefix that ends inside a line this holds only if the input ends there. */
+ * is the text's last line, and then p = len: of a prefix that ends inside a line this holds only if the input ends there.
+ * A GBK entry ends at the same line, so this is the cut for kaamer_makedb_gbk_device too. */
 uint64_t kaamer_text_cut_embl(const char *text, uint64_t len);
 /* kaamer_submit_text_top_flat / kaamer_search_text_top_flat for FASTA text (search_protein.go:38-120, search_nucleotide.go,
  * search_fastq.go with GetQueriesFasta inside): the same slot, ticket, wait, repeat beyond a bound (from the parsed

@@ -419,13 +419,15 @@ for _name in ("makedb_fasta", "makedb_tsv", "makedb_embl", "makedb_gbk", "parse_
 # text: (text, len, shard, n_shards, load_factor, device, proteins, out)
 SYMBOLS["kaamer_makedb_fasta_device"] = (C.c_int, TEXT_IN + [C.c_uint64, C.c_int32, C.c_int] + NEW)
 for _name in ("image_build_fasta_device", "index_build_fasta", "image_build_tsv_device", "index_build_tsv", "image_build_embl_device",
-              "index_build_embl"):
+              "index_build_embl", "image_build_gbk_device", "index_build_gbk"):
     SYMBOLS["kaamer_" + _name] = (C.c_int, TEXT_IN + [C.c_uint32, C.c_uint32, C.c_double, C.c_int] + NEW + NEW)
 # the database TSV rows read on the device: (text, len, header, header_len, id_base, device, out); its two builds are above
 SYMBOLS["kaamer_makedb_tsv_device"] = (C.c_int, TEXT_IN + TEXT_IN + [C.c_uint64, C.c_int] + NEW)
 # the database EMBL text read on the device: (text, len, nb_before, device, out), its cut rule; its two builds are above
 SYMBOLS["kaamer_makedb_embl_device"] = (C.c_int, TEXT_IN + [C.c_uint64, C.c_int] + NEW)
 SYMBOLS["kaamer_text_cut_embl"] = (C.c_uint64, TEXT_IN)
+# the database GBK text read on the device: (text, len, nb_before, device, out); its cut rule is the EMBL one, its two builds are above
+SYMBOLS["kaamer_makedb_gbk_device"] = (C.c_int, TEXT_IN + [C.c_uint64, C.c_int] + NEW)
 
 # the packed-batch calls of an index and of a sharded index; search fills a result, submit a ticket for wait / discard
 for _p in ("", "sharded_"):

@@ -128,6 +128,15 @@ class Image(_Handle):
         return Proteins(p), cls(im)
 
     @classmethod
+    def from_gbk_text(cls, text, shard=0, n_shards=1, load_factor=0.5, device=0):
+        """(proteins, image) of a database GBK text (GenBank / GenPept flat file), read and built on GPU `device`
+        (kaamer_image_build_gbk_device): the sequences stay there between the reader and the builder."""
+        text = bytes(text)
+        p, im = C.c_void_p(), C.c_void_p()
+        abi.check(abi.lib().kaamer_image_build_gbk_device(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(im)))
+        return Proteins(p), cls(im)
+
+    @classmethod
     def merge(cls, images, load_factor=0.5, device=None):
         """kaamer-db -merge: the union of images of one shard (kaamer_image_merge).  device=None: on the host;
         device=d: the same image made on GPU d (byte-identical)."""
@@ -207,8 +216,15 @@ class Proteins(_Handle):
         return cls(_new(abi.lib().kaamer_makedb_embl_device, text, len(text), int(nb_before), int(device)))
 
     @classmethod
-    def from_gbk(cls, text):
-        return cls._make(abi.lib().kaamer_makedb_gbk, text)
+    def from_gbk(cls, text, device=None, nb_before=0):
+        """device=None: kaamer_makedb_gbk on the host.  device=d: the same table read on GPU d (kaamer_makedb_gbk_device);
+        there `text` may be a piece cut at text_cut_gbk: nb_before = the "//" lines in front of it."""
+        if device is None:
+            if nb_before:
+                raise ValueError("nb_before belongs to the device reader")
+            return cls._make(abi.lib().kaamer_makedb_gbk, text)
+        text = bytes(text)
+        return cls(_new(abi.lib().kaamer_makedb_gbk_device, text, len(text), int(nb_before), int(device)))
 
     @classmethod
     def from_text(cls, text, fmt, offset=0, length=None, strict_scanner=False):
@@ -575,6 +591,14 @@ class Index(_Handle):
         text = bytes(text)
         p, ix = C.c_void_p(), C.c_void_p()
         abi.check(abi.lib().kaamer_index_build_embl(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(ix)))
+        return Proteins(p), cls(ix, device)
+
+    @classmethod
+    def from_gbk_text(cls, text, shard=0, n_shards=1, load_factor=0.5, device=0):
+        """(proteins, index) of a database GBK text, read and built on the device it is searched on (kaamer_index_build_gbk)"""
+        text = bytes(text)
+        p, ix = C.c_void_p(), C.c_void_p()
+        abi.check(abi.lib().kaamer_index_build_gbk(text, len(text), shard, n_shards, load_factor, int(device), C.byref(p), C.byref(ix)))
         return Proteins(p), cls(ix, device)
 
     @classmethod
@@ -1543,6 +1567,11 @@ def text_cut_embl(text):
     after the '\\r' drop (a final "//" without '\\n' counts as the text's last line: p = len); 0: none"""
     data = text.encode("latin-1") if isinstance(text, str) else bytes(text)
     return int(abi.lib().kaamer_text_cut_embl(data, len(data)))
+
+
+def text_cut_gbk(text):
+    """where a GBK text may be cut (Proteins.from_gbk on a device): its entries end as EMBL's do, so this is text_cut_embl"""
+    return text_cut_embl(text)
 
 
 def _hip_runtime():

@@ -90,6 +90,7 @@ struct MeParams {
     uint64_t *offsets, *id_off, *feat_off, *full_off;
     uint8_t *seqs, *idb, *featb, *fullb;
     uint64_t nb_before;
+    uint32_t n_feat;           // feature columns of a record: ME_FEATURES here (makedb_gbk.hip.inc: 3)
 };
 
 __global__ __launch_bounds__(PT_BLOCK) void me_lines_kernel(MeParams f)
@@ -359,12 +360,14 @@ __device__ __forceinline__ void me_copy(uint8_t *dst, const uint8_t *src, uint32
     for (uint32_t o = threadIdx.x & 63u; o < n; o += 64u) dst[o] = src[o];
 }
 // the non-space bytes of src[0, n) to out[done ..), what lies at `clip` and beyond left out; returns how many there were
-__device__ __forceinline__ uint32_t me_squeeze(uint8_t *out, uint32_t done, uint32_t clip, const uint8_t *src, uint32_t n)
+// (UPPER: 'a'..'z' upper-cased on the way, the GBK reader's rule)
+template <bool UPPER = false> __device__ __forceinline__ uint32_t me_squeeze(uint8_t *out, uint32_t done, uint32_t clip, const uint8_t *src, uint32_t n)
 {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t at = 0; at < n; at += 64u) {
         const uint32_t q = at + lane;
-        const uint32_t c = q < n ? src[q] : ' ';
+        uint32_t c = q < n ? src[q] : ' ';
+        if (UPPER && c >= 'a' && c <= 'z') c -= 32u;
         const unsigned long long m = __ballot(c != ' ');
         const uint32_t to = done + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
         if (c != ' ' && to < clip) out[to] = (uint8_t)c;
@@ -518,7 +521,7 @@ template <bool EMIT> __global__ __launch_bounds__(PT_LINES) void me_ent_kernel(M
         const unsigned long long n_rec = f.res[ME_R_RECORDS], n_full = f.res[ME_R_FULL];
         f.offsets[n_rec] = f.res[ME_R_SEQ_BYTES];
         f.id_off[n_rec] = f.res[ME_R_ID_BYTES];
-        f.feat_off[n_rec * ME_FEATURES] = f.res[ME_R_FEAT_BYTES];
+        f.feat_off[n_rec * f.n_feat] = f.res[ME_R_FEAT_BYTES];
         f.full_off[n_full] = f.res[ME_R_FULL_BYTES];
     }
     if (k64 < f.n_terms) {
@@ -570,6 +573,8 @@ struct MeReader {
     DevBuf<unsigned long long> d_res, d_ent64, d_rec64;
     MeParams f{};
     uint64_t n_rec = 0, seq_bytes = 0, id_bytes = 0, feat_bytes = 0, n_full = 0, full_bytes = 0;
+    const char *format = "embl";             // the format that was read, for messages and the trace
+    std::vector<std::string> feature_names;   // its columns
     ~MeReader() { (void)hipSetDevice(device); }   // (before the buffers go)
 };
 
@@ -581,19 +586,46 @@ static unsigned me_wave_grid(uint64_t waves, int n_cu)
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_before, int device)
+// What a flat-file format puts into me_read: its name and columns, and the launches between the shared steps (the line
+// starts, the terminators, the entry scans).  classify leaves kf (ME_TERM on every terminator line), the block's terminator
+// count and a worklist; read_lines finishes every line's record; fold<0> leaves MeEnt, fold<1> writes the kept entries.
+struct MeEmbl {
+    typedef MeReader Reader;
+    static const char *name() { return "embl"; }
+    static std::vector<std::string> feature_names()   // EMBL_DEF_FTS, inputEMBL.go:43
+    {
+        return { "ProteinName", "GeneName", "EC", "GO", "KEGG_ID", "BioCyc_ID", "HAMAP", "Organism", "TaxId", "FullTaxonomy" };
+    }
+    static int lines_ready(MeReader &, size_t, size_t) { return KAAMER_OK; }
+    static void classify(MeReader &m, uint32_t n_blk) { hipLaunchKernelGGL(me_classify_kernel, dim3(n_blk), dim3(PT_LINES), 0, 0, m.f); }
+    static int entries_ready(MeReader &, size_t) { return KAAMER_OK; }
+    static void read_lines(MeReader &m, size_t n_work, uint32_t, int n_cu)
+    {
+        if (n_work) hipLaunchKernelGGL(me_read_kernel, dim3(me_wave_grid(n_work, n_cu)), dim3(PT_BLOCK), 0, 0, m.f);
+    }
+    static void fold(MeReader &m, bool emit, unsigned grid)
+    {
+        if (emit) hipLaunchKernelGGL(me_fold_kernel<true>, dim3(grid), dim3(PT_BLOCK), 0, 0, m.f);
+        else hipLaunchKernelGGL(me_fold_kernel<false>, dim3(grid), dim3(PT_BLOCK), 0, 0, m.f);
+    }
+    static void release(MeReader &) {}
+};
+
+template <class F> static int me_read(typename F::Reader &m, const char *text, uint64_t len, uint64_t nb_before, int device)
 {
+    m.format = F::name();
+    m.feature_names = F::feature_names();
     int n_dev = 0;
     if (device < 0 || hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
         (void)hipGetLastError();
-        return kaamer_fail(KAAMER_E_ARG, "makedb_embl_device: there is no device %d", device);
+        return kaamer_fail(KAAMER_E_ARG, "makedb_%s_device: there is no device %d", m.format, device);
     }
     HIPCHK(hipSetDevice(device));
     m.device = device;
     hipDeviceProp_t prop;
     const int n_cu = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
     MfTrace tr;
-    tr.format = "embl";
+    tr.format = m.format;
     tr.bytes = len;
     tr.begin();
     const uint32_t n_tiles = (uint32_t)((len + PT_TILE - 1) / PT_TILE);
@@ -613,6 +645,7 @@ static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_befo
     p.res = m.d_res;
     f.res = m.d_res + PT_R_N;
     f.nb_before = nb_before;
+    f.n_feat = (uint32_t)m.feature_names.size();
     HIPCHK(hipMemset(m.d_res, 0, (PT_R_N + ME_R_N) * sizeof(unsigned long long)));
     if (n_tiles) hipLaunchKernelGGL(pt_count_kernel, dim3(n_tiles), dim3(PT_BLOCK), 0, 0, p);
     hipLaunchKernelGGL(pt_tile_scan_kernel, dim3(1), dim3(PT_LINES), 0, 0, p);
@@ -621,7 +654,7 @@ static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_befo
     HIPCHK(hipMemcpy(h_res, m.d_res, sizeof h_res, hipMemcpyDeviceToHost));
     tr.lap("count lines");
     const unsigned long long nl = h_res[PT_R_NL];
-    if (nl < 1 || nl > 0xFFFFFFF0ull) return kaamer_fail(KAAMER_E_CAPACITY, "makedb_embl_device: %llu lines in one text: cut it (kaamer_text_cut_embl)", nl);
+    if (nl < 1 || nl > 0xFFFFFFF0ull) return kaamer_fail(KAAMER_E_CAPACITY, "makedb_%s_device: %llu lines in one text: cut it (kaamer_text_cut_embl)", m.format, nl);
     const size_t nb = (size_t)((nl + PT_LINES - 1) / PT_LINES) + 1;
     rc = reserve_group(nullptr, GROW_EXACT, { want(m.d_line32, 3 * ((size_t)nl + 2) + 2 * nb), want(m.d_span, (size_t)nl + 1) });
     if (rc) return rc;
@@ -635,9 +668,11 @@ static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_befo
     }
     p.line_cap = (uint32_t)nl;
     const uint32_t n_blk = (uint32_t)(nb - 1);
+    rc = F::lines_ready(m, (size_t)nl, nb);
+    if (rc) return rc;
     hipLaunchKernelGGL(me_lines_kernel, dim3(n_tiles ? n_tiles : 1u), dim3(PT_BLOCK), 0, 0, f);
     tr.lap("lines");
-    hipLaunchKernelGGL(me_classify_kernel, dim3(n_blk), dim3(PT_LINES), 0, 0, f);
+    F::classify(m, n_blk);
     hipLaunchKernelGGL(me_term_scan_kernel, dim3(1), dim3(PT_LINES), 0, 0, f);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(h_res, m.d_res, sizeof h_res, hipMemcpyDeviceToHost));
@@ -654,11 +689,13 @@ static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_befo
     f.ent_a = m.d_ent64; f.ent_b = f.ent_a + (n_terms + 1); f.ent_c = f.ent_b + (n_terms + 1);
     f.eb_a = f.ent_c + (n_terms + 1); f.eb_b = f.eb_a + neb; f.eb_c = f.eb_b + neb;
     const uint32_t n_eblk = (uint32_t)(neb - 1);
+    rc = F::entries_ready(m, n_terms);
+    if (rc) return rc;
     if (n_terms) hipLaunchKernelGGL(me_terms_kernel, dim3(n_blk), dim3(PT_LINES), 0, 0, f);
-    if (n_work) hipLaunchKernelGGL(me_read_kernel, dim3(me_wave_grid(n_work, n_cu)), dim3(PT_BLOCK), 0, 0, f);
+    F::read_lines(m, n_work, n_blk, n_cu);
     tr.lap("read lines");
     if (n_terms) {
-        hipLaunchKernelGGL(me_fold_kernel<false>, dim3(me_wave_grid(n_terms, n_cu)), dim3(PT_BLOCK), 0, 0, f);
+        F::fold(m, false, me_wave_grid(n_terms, n_cu));
         hipLaunchKernelGGL(me_ent_kernel<false>, dim3(n_eblk), dim3(PT_LINES), 0, 0, f);
     }
     hipLaunchKernelGGL(me_ent_scan_kernel, dim3(1), dim3(PT_LINES), 0, 0, f);
@@ -668,22 +705,22 @@ static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_befo
     m.n_rec = r[ME_R_RECORDS]; m.seq_bytes = r[ME_R_SEQ_BYTES]; m.id_bytes = r[ME_R_ID_BYTES]; m.feat_bytes = r[ME_R_FEAT_BYTES];
     m.n_full = r[ME_R_FULL]; m.full_bytes = r[ME_R_FULL_BYTES];
     const size_t n = (size_t)m.n_rec, nf = (size_t)m.n_full;
-    if ((unsigned long long)n * ME_FEATURES > 0xFFFFFFF0ull)
-        return kaamer_fail(KAAMER_E_CAPACITY, "makedb_embl_device: %llu records in one text: cut it (kaamer_text_cut_embl)", (unsigned long long)m.n_rec);
-    rc = reserve_group(nullptr, GROW_EXACT, { want(m.d_rec32, (n + 1) + (nf + 1)), want(m.d_rec64, 2 * (n + 1) + (n * ME_FEATURES + 1) + (nf + 1)),
+    if ((unsigned long long)n * f.n_feat > 0xFFFFFFF0ull)
+        return kaamer_fail(KAAMER_E_CAPACITY, "makedb_%s_device: %llu records in one text: cut it (kaamer_text_cut_embl)", m.format, (unsigned long long)m.n_rec);
+    rc = reserve_group(nullptr, GROW_EXACT, { want(m.d_rec32, (n + 1) + (nf + 1)), want(m.d_rec64, 2 * (n + 1) + (n * f.n_feat + 1) + (nf + 1)),
                                               want(m.d_seqs, (size_t)m.seq_bytes + 3 * PT_PIECE), want(m.d_idb, (size_t)m.id_bytes + 2 * PT_PIECE),
                                               want(m.d_featb, (size_t)m.feat_bytes + 2 * PT_PIECE), want(m.d_fullb, (size_t)m.full_bytes + 2 * PT_PIECE) });
     if (rc) return rc;
     f.ids = m.d_rec32; f.full_rec = m.d_rec32 + (n + 1);
     f.offsets = reinterpret_cast<uint64_t *>(m.d_rec64.get());
-    f.id_off = f.offsets + (n + 1); f.feat_off = f.id_off + (n + 1); f.full_off = f.feat_off + (n * ME_FEATURES + 1);
+    f.id_off = f.offsets + (n + 1); f.feat_off = f.id_off + (n + 1); f.full_off = f.feat_off + (n * f.n_feat + 1);
     f.seqs = m.d_seqs; f.idb = m.d_idb; f.featb = m.d_featb; f.fullb = m.d_fullb;
     {   // (the builder's window kernel reads up to 17 bytes behind the last residue: they are zero, not left-over)
         const size_t whole = (size_t)(m.seq_bytes / PT_PIECE) * PT_PIECE;
         HIPCHK(hipMemset(m.d_seqs + whole, 0, (size_t)m.seq_bytes - whole + 3 * PT_PIECE));
     }
     hipLaunchKernelGGL(me_ent_kernel<true>, dim3(n_eblk ? n_eblk : 1u), dim3(PT_LINES), 0, 0, f);
-    if (n_terms) hipLaunchKernelGGL(me_fold_kernel<true>, dim3(me_wave_grid(n_terms, n_cu)), dim3(PT_BLOCK), 0, 0, f);
+    if (n_terms) F::fold(m, true, me_wave_grid(n_terms, n_cu));
     HIPCHK(hipGetLastError());
     tr.lap("entries, emit");
     return KAAMER_OK;
@@ -693,13 +730,12 @@ static int me_read(MeReader &m, const char *text, uint64_t len, uint64_t nb_befo
 static int me_table(MeReader &m, kaamer_proteins **out)
 {
     MfTrace tr;
-    tr.format = "embl";
+    tr.format = m.format;
     tr.bytes = m.f.pt.n;
     tr.begin();
     kaamer_table_arrays a;
-    kaamer_proteins *t = kaamer_proteins_table_new({ "ProteinName", "GeneName", "EC", "GO", "KEGG_ID", "BioCyc_ID", "HAMAP", "Organism", "TaxId", "FullTaxonomy" },
-                                                   (uint32_t)m.n_rec, m.seq_bytes, m.id_bytes, m.feat_bytes, &a);   // EMBL_DEF_FTS, inputEMBL.go:43
-    if (!t) return kaamer_fail(KAAMER_E_NOMEM, "makedb_embl_device: the table");
+    kaamer_proteins *t = kaamer_proteins_table_new(m.feature_names, (uint32_t)m.n_rec, m.seq_bytes, m.id_bytes, m.feat_bytes, &a);
+    if (!t) return kaamer_fail(KAAMER_E_NOMEM, "makedb_%s_device: the table", m.format);
     tr.lap("host table");
     const size_t n = (size_t)m.n_rec, nf = (size_t)m.n_full;
     hipError_t e = hipSuccess;
@@ -709,24 +745,24 @@ static int me_table(MeReader &m, kaamer_proteins **out)
     get(a.seqs, m.d_seqs, (size_t)m.seq_bytes);
     get(a.entry_off, m.f.id_off, (n + 1) * 8);
     get(a.entry_ids, m.d_idb, (size_t)m.id_bytes);
-    get(a.feature_off, m.f.feat_off, (n * ME_FEATURES + 1) * 8);
+    get(a.feature_off, m.f.feat_off, (n * m.f.n_feat + 1) * 8);
     get(a.features, m.d_featb, (size_t)m.feat_bytes);
     std::vector<uint32_t> full_rec;
     std::vector<uint64_t> full_off;
     std::vector<char> full_bytes;
     try { full_rec.resize(nf); full_off.resize(nf + 1); full_bytes.resize((size_t)m.full_bytes); }
-    catch (const std::bad_alloc &) { kaamer_proteins_free(t); return kaamer_fail(KAAMER_E_NOMEM, "makedb_embl_device: the whole sequences"); }
+    catch (const std::bad_alloc &) { kaamer_proteins_free(t); return kaamer_fail(KAAMER_E_NOMEM, "makedb_%s_device: the whole sequences", m.format); }
     if (nf) {
         get(full_rec.data(), m.f.full_rec, nf * 4);
         get(full_off.data(), m.f.full_off, (nf + 1) * 8);
         get(full_bytes.data(), m.d_fullb, (size_t)m.full_bytes);
     }
-    if (e != hipSuccess) { kaamer_proteins_free(t); return kaamer_fail(KAAMER_E_HIP, "makedb_embl_device: download: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { kaamer_proteins_free(t); return kaamer_fail(KAAMER_E_HIP, "makedb_%s_device: download: %s", m.format, hipGetErrorString(e)); }
     tr.lap("download");
     kaamer_proteins_table_seal(t);
     if (nf && kaamer_proteins_table_full_seqs(t, full_rec.data(), full_off.data(), full_bytes.data(), (uint32_t)nf)) {
         kaamer_proteins_free(t);
-        return kaamer_fail(KAAMER_E_NOMEM, "makedb_embl_device: the whole sequences");
+        return kaamer_fail(KAAMER_E_NOMEM, "makedb_%s_device: the whole sequences", m.format);
     }
     *out = t;
     return KAAMER_OK;
@@ -743,6 +779,24 @@ static int me_plain(const char *who, const char *&text, uint64_t &len, std::stri
     return KAAMER_OK;
 }
 
+// text -> the reader's buffers -> the build that takes device buffers (it sees the indexed prefixes) -> the table's host copy
+template <class F> static int me_build(typename F::Reader &m, const char *who, const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor, int device,
+                    kaamer_proteins **proteins, kaamer_device_image *di)
+{
+    std::string inflated;
+    int rc = me_plain(who, text, len, inflated);
+    if (rc) return rc;
+    rc = me_read<F>(m, text, len, 0, device);
+    if (rc) return rc;
+    F::release(m);
+    m.d_text.reset(); m.d_cnt32.reset(); m.d_line32.reset(); m.d_span.reset(); m.d_ent32.reset(); m.d_ent64.reset();   // (the build wants the room; hipFree waits for the fold)
+    rc = kaamer_build_resident(m.d_seqs, m.f.offsets, m.f.ids, (uint32_t)m.n_rec, m.seq_bytes, shard, n_shards, load_factor, device, di);
+    if (rc) return rc;
+    rc = me_table(m, proteins);
+    if (rc) { (void)hipFree(di->d_buckets); (void)hipFree(di->d_arena); }
+    return rc;
+}
+
 extern "C" {
 
 int kaamer_makedb_embl_device(const char *text, uint64_t len, uint64_t nb_before, int device, kaamer_proteins **out)
@@ -754,26 +808,9 @@ int kaamer_makedb_embl_device(const char *text, uint64_t len, uint64_t nb_before
     int rc = me_plain("makedb_embl_device", text, len, inflated);
     if (rc) return rc;
     MeReader m;
-    rc = me_read(m, text, len, nb_before, device);
+    rc = me_read<MeEmbl>(m, text, len, nb_before, device);
     if (rc) return rc;
     return me_table(m, out);
-}
-
-// text -> the reader's buffers -> the build that takes device buffers (it sees the indexed prefixes) -> the table's host copy
-static int me_build(MeReader &m, const char *who, const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor, int device,
-                    kaamer_proteins **proteins, kaamer_device_image *di)
-{
-    std::string inflated;
-    int rc = me_plain(who, text, len, inflated);
-    if (rc) return rc;
-    rc = me_read(m, text, len, 0, device);
-    if (rc) return rc;
-    m.d_text.reset(); m.d_cnt32.reset(); m.d_line32.reset(); m.d_span.reset(); m.d_ent32.reset(); m.d_ent64.reset();   // (the build wants the room; hipFree waits for the fold)
-    rc = kaamer_build_resident(m.d_seqs, m.f.offsets, m.f.ids, (uint32_t)m.n_rec, m.seq_bytes, shard, n_shards, load_factor, device, di);
-    if (rc) return rc;
-    rc = me_table(m, proteins);
-    if (rc) { (void)hipFree(di->d_buckets); (void)hipFree(di->d_arena); }
-    return rc;
 }
 
 int kaamer_image_build_embl_device(const char *text, uint64_t len, uint32_t shard, uint32_t n_shards, double load_factor, int device,
@@ -784,7 +821,7 @@ int kaamer_image_build_embl_device(const char *text, uint64_t len, uint32_t shar
     *proteins = nullptr; *image = nullptr;
     MeReader m;
     kaamer_device_image di;
-    rc = me_build(m, "image_build_embl_device", text, len, shard, n_shards, load_factor, device, proteins, &di);
+    rc = me_build<MeEmbl>(m, "image_build_embl_device", text, len, shard, n_shards, load_factor, device, proteins, &di);
     if (rc) return rc;
     rc = kaamer_device_image_download(&di, image);
     if (rc) { kaamer_proteins_free(*proteins); *proteins = nullptr; }
@@ -799,7 +836,7 @@ int kaamer_index_build_embl(const char *text, uint64_t len, uint32_t shard, uint
     *proteins = nullptr; *out = nullptr;
     MeReader m;
     kaamer_device_image di;
-    rc = me_build(m, "index_build_embl", text, len, shard, n_shards, load_factor, device, proteins, &di);
+    rc = me_build<MeEmbl>(m, "index_build_embl", text, len, shard, n_shards, load_factor, device, proteins, &di);
     if (rc) return rc;
     rc = index_of_device_image(di, device, out);
     if (rc) { kaamer_proteins_free(*proteins); *proteins = nullptr; }

@@ -1143,6 +1143,7 @@ static void subject_free(SubjectTable &t) { t = SubjectTable(); }
 #include "makedb_fasta.hip.inc"
 #include "makedb_tsv.hip.inc"
 #include "makedb_embl.hip.inc"
+#include "makedb_gbk.hip.inc"
 #include "inflate.hip.inc"
 
 extern "C" {
